@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- input MB/s of the MI355X-native MS-XCA compress path (BASELINE.json metric), 1 to N GPUs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 With N > 1 and no WORLD_SIZE in the environment the script starts its N ranks itself (torch.distributed.run, one
 process per GPU, rendezvous on 127.0.0.1); launched BY torch.distributed.run it is one of the ranks. A world size other
@@ -553,8 +553,41 @@ def real_files_leg(m, ctx, sharding, max_mb, data_dir, steps=3, cpu=True):
     return res
 
 
-def sharded_leg(m, ctx, cor, fmt, rank, world, steps, warmup, sharding, dev):
-    """One codec over the config-5 job: this rank's contiguous unit range, timed; whole-job figures by MAX / SUM over the ranks."""
+DUMP_SAMPLE_UNITS, DUMP_SAMPLE_PREFIX = 256, 32768   # --dump-outputs: compressed bytes of at most 256 units, 32 KiB of each (<= 32 MB as float32)
+
+
+def dump_outputs(m, job, out_dir, suffix=""):
+    """--dump-outputs: what the last timed step handed back for this rank's units, as float arrays, so that two builds can be compared output
+    for output. Per unit: status (status.npy), compressed length (compressed_len.npy) and a position-weighted sum of its compressed bytes
+    (compressed_checksum.npy: sum of byte * (offset mod 65536 + 1), exact in float64); and the compressed bytes themselves (the first 32 KiB)
+    of a fixed, seeded sample of units (sample_units.npy, sample_offsets.npy into sample_bytes.npy)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = job.n
+    d_packed, d_poff = m.compact_batch(job.ctx, job.out_off[:n], job.caps[:n], job.d_out, job.d_len)
+    torch.cuda.synchronize()
+    total = int(d_poff[n].item())
+    csum = torch.zeros(n, dtype=torch.int64, device=d_packed.device)
+    for a in range(0, total, 1 << 27):
+        pos = torch.arange(a, min(total, a + (1 << 27)), dtype=torch.int64, device=d_packed.device)
+        unit = torch.searchsorted(d_poff[1:], pos, right=True)
+        csum.index_add_(0, unit, d_packed[a:a + len(pos)].to(torch.int64) * ((pos - d_poff[unit]) % 65536 + 1))
+    poff = d_poff.cpu().numpy()
+    units = np.sort(np.random.default_rng(0).permutation(n)[:DUMP_SAMPLE_UNITS])
+    take = np.minimum(poff[units + 1] - poff[units], DUMP_SAMPLE_PREFIX)
+    sample = [d_packed[int(poff[u]):int(poff[u]) + int(t)] for u, t in zip(units, take)]
+    arrays = {"status": job.d_st[:n].cpu().numpy().astype(np.float32), "compressed_len": job.d_len[:n].cpu().numpy().astype(np.float64),
+              "compressed_checksum": csum.cpu().numpy().astype(np.float64), "sample_units": units.astype(np.float64),
+              "sample_offsets": np.concatenate([[0], np.cumsum(take)]).astype(np.float64),
+              "sample_bytes": (torch.cat(sample).cpu().numpy() if sample else np.zeros(0, np.uint8)).astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    del d_packed, d_poff
+
+
+def sharded_leg(m, ctx, cor, fmt, rank, world, steps, warmup, sharding, dev, dump_dir=None):
+    """One codec over the config-5 job: this rank's contiguous unit range, timed; whole-job figures by MAX / SUM over the ranks.
+    dump_dir: write what the last timed step computed there (dump_outputs)."""
     off, ln, desc = config5_units(cor, fmt)
     s, e, g0, g1, my_off, my_len = sharding.shard_job(off, ln, world, rank)
     d_in = cor.device_range(g0, g1)
@@ -564,6 +597,8 @@ def sharded_leg(m, ctx, cor, fmt, rank, world, steps, warmup, sharding, dev):
     parity = parity_gate(m, job, fmt, cor, int(s))
     if parity is False:
         sys.exit("bench.py: the %s output of this run differs from the reference's (tests/golden/corpus_full.json): no number is reported" % CODEC_OF[fmt])
+    if dump_dir:
+        dump_outputs(m, job, dump_dir, "" if world == 1 else "_rank%d" % rank)
     job_dt, job_bytes = sharding.reduce_job(dt, job.in_bytes * steps, device=dev)
     _, job_out = sharding.reduce_job(0.0, out_bytes, device=dev)
     assert job_bytes == int(ln.sum()) * steps, "the shards do not cover the job"
@@ -604,6 +639,8 @@ def main():
     ap.add_argument("--data-dir", default=None, help="the real-files leg over every file of this directory instead")
     ap.add_argument("--oversubscribe", action="store_true", help="TEST ONLY: let the N ranks share the visible GPUs (gloo for the timing reduction); "
                     "exercises the sharded multi-rank path on a 1-GPU box, the line is marked and is not an N-GPU measurement")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the headline leg's last step computed to "
+                    "DIR/<name>.npy (float32/float64; per-unit status, length and checksum, the bytes of a seeded sample of units)")
     args = ap.parse_args()
     want = max(1, args.gpus)
     if want > 1 and "WORLD_SIZE" not in os.environ:
@@ -628,7 +665,7 @@ def main():
     fmt = m.FORMATS[args.codec]
     steps2 = max(3, args.steps // 4)
 
-    head = sharded_leg(m, ctx, cor, fmt, rank, world, args.steps, args.warmup, sharding, rdev)
+    head = sharded_leg(m, ctx, cor, fmt, rank, world, args.steps, args.warmup, sharding, rdev, dump_dir=args.dump_outputs)
     res = {
         "metric": "input MB/s (%s compress, bit-exact with the reference CPU encoder)" % args.codec,
         "value": head["MB_per_s"], "unit": "MB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

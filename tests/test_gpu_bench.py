@@ -62,6 +62,27 @@ def test_the_drivers_own_command_prints_one_short_parseable_line():
     assert full["value"] == line["value"] and "single_gpu" in full["extra"] and "decompress" in full["extra"]
 
 
+def test_dump_outputs_writes_what_the_last_step_computed(tmp_path):
+    """--dump-outputs DIR: float arrays of the headline leg's last timed step (status, compressed length and checksum per unit, a seeded
+    sample of compressed bytes), under 64 MB in all; the lengths of the first replica are the reference's (tests/golden/corpus_full.json)."""
+    from ms_compress_amd import corpus
+    line = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extra", "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    a = {n: np.load(str(tmp_path / (n + ".npy"))) for n in ("status", "compressed_len", "compressed_checksum", "sample_units", "sample_offsets", "sample_bytes")}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(os.path.getsize(str(p)) for p in tmp_path.iterdir()) <= 64 << 20
+    n = len(a["status"])
+    assert n == line["config"]["units"] == 192 and (a["status"] == 0).all() and len(a["compressed_len"]) == len(a["compressed_checksum"]) == n
+    if corpus.source() == "synthetic":
+        gold = json.load(open(os.path.join(ROOT, "tests", "golden", "corpus_full.json")))
+        assert a["compressed_len"][:12].tolist() == [gold[name]["lznt1"]["len"] for name in corpus.NAMES]
+    assert (a["compressed_len"].reshape(16, 12) == a["compressed_len"][:12]).all()                  # every replica compressed alike
+    assert (a["compressed_checksum"].reshape(16, 12) == a["compressed_checksum"][:12]).all()
+    u = a["sample_units"].astype(int)
+    assert len(u) == min(n, 256) and (np.diff(a["sample_offsets"]) == np.minimum(a["compressed_len"][u], 32768)).all()
+    assert len(a["sample_bytes"]) == a["sample_offsets"][-1] and a["sample_bytes"].min() >= 0 and a["sample_bytes"].max() <= 255
+
+
 def test_two_ranks_share_the_gpu():
     """python bench.py --gpus 2 --oversubscribe: the sharded multi-rank path end to end (self-spawned ranks, gloo timing reduction,
     every rank's shard through the parity gate). One line, marked as a test run."""

@@ -7,6 +7,7 @@ import random
 import pytest
 
 import cases
+from refanswers import answer, digest
 
 pytestmark = pytest.mark.gpu
 NO_FLUSH, FLUSH, FINISH = 0, 2, 4
@@ -66,26 +67,31 @@ def plans(rnd, n):
         yield steps, rnd.choice((1, 3, 4098, 1 << 20))
 
 
-def test_lznt1_deflate_matches_reference_call_by_call(oracle, gpu_ctx):
-    import ms_compress_amd as m
-    ref = oracle.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
-    mine = m.load_library()
+def deflate_cases():
+    """(data, steps, tail window) for test_lznt1_deflate_matches_reference_call_by_call"""
     rnd = random.Random(9)
     datas = [b"", b"x", cases.family("words", 4096, rnd), cases.family("lz", 12289, rnd), cases.family("random", 9000, rnd),
              cases.mixed_buffer()[95000:95000 + 180000]]
+    return [(data, steps, tail) for data in datas for steps, tail in plans(rnd, len(data))]
+
+
+def ref_drive(ref, fmt, data, steps, tail, kind="deflate"):
+    """digest of drive() on the compiled reference (ref: its library, or None: the recorded answer)"""
+    return answer((kind, fmt, data, steps, tail), ref and (lambda: drive(ref, fmt, data, steps, tail)))
+
+
+def test_lznt1_deflate_matches_reference_call_by_call(oracle, gpu_ctx):
+    import ms_compress_amd as m
+    ref = oracle.load_ref()
+    mine = m.load_library()
     n_cmp = 0
-    for data in datas:
-        for steps, tail in plans(rnd, len(data)):
-            want = drive(ref, 2, data, steps, tail)
-            got = drive(mine, 2, data, steps, tail)
-            assert got[1] == want[1], (len(data), steps[:4], tail)
-            assert got[0] == want[0] and got[2] == want[2]
-            n_cmp += 1
+    for data, steps, tail in deflate_cases():
+        got = drive(mine, 2, data, steps, tail)
+        assert digest(got) == ref_drive(ref, 2, data, steps, tail), (len(data), steps[:4], tail, got[1][-3:])
+        n_cmp += 1
     assert n_cmp >= 50
     # without MSCOMP_FLUSH the stream is the one-shot output
-    data = datas[-1]
+    data = deflate_cases()[-1][0]
     out, _, end = drive(mine, 2, data, [(7000, 3000, NO_FLUSH)] * 40, 5000)
     assert end == 0 and out == oracle.oracle_compress(2, data)[1]
 
@@ -145,12 +151,8 @@ def drive_inflate(lib, fmt, stream, steps, tail_window, cap):
     return outbuf.raw[:opos], trace, end
 
 
-def test_lznt1_inflate_matches_reference_call_by_call(oracle, gpu_ctx):
-    import ms_compress_amd as m
-    ref = oracle.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
-    mine = m.load_library()
+def inflate_cases(oracle):
+    """(stream, capacity, steps, tail window) for test_lznt1_inflate_matches_reference_call_by_call"""
     rnd = random.Random(11)
     datas = [b"", b"x", cases.family("words", 4096, rnd), cases.family("lz", 12289, rnd), cases.family("random", 9000, rnd),
              cases.mixed_buffer()[95000:95000 + 120000]]
@@ -161,18 +163,29 @@ def test_lznt1_inflate_matches_reference_call_by_call(oracle, gpu_ctx):
     big = oracle.oracle_compress(2, datas[-1])[1]
     streams += [(big[:1] + bytes([big[1] ^ 0x40]) + big[2:], len(datas[-1])), (big[:5000] + b"\0\0" + big[5002:], len(datas[-1])),
                 (big[:3000] + bytes(rnd.getrandbits(8) for _ in range(50)) + big[3050:], len(datas[-1]))]
-    n_cmp = 0
+    out = []
     for stream, cap in streams:
         plans = [([], 1 << 30), ([(4096, 4096)] * 8, 1 << 30), ([(1000, 700)] * 30, 100), ([(3, 5000)] * 40, 4096)]
         for _ in range(3):
             plans.append(([(rnd.choice((1, 2, 3, 17, 4097, 4098, 4099, 10000, 60000)), rnd.choice((0, 1, 100, 4095, 4096, 4097, 9000, 1 << 20)))
                            for _ in range(rnd.randint(1, 40))], rnd.choice((1, 4095, 4096, 1 << 20))))
-        for steps, tail in plans:
-            want = drive_inflate(ref, 2, stream, steps, tail, cap)
-            got = drive_inflate(mine, 2, stream, steps, tail, cap)
-            assert got[1] == want[1], (len(stream), cap, steps[:4], tail, got[1][-3:], want[1][-3:])
-            assert got[0] == want[0] and got[2] == want[2]
-            n_cmp += 1
+        out += [(stream, cap, steps, tail) for steps, tail in plans]
+    return out
+
+
+def ref_drive_inflate(ref, fmt, stream, steps, tail, cap):
+    return answer(("inflate", fmt, stream, steps, tail, cap), ref and (lambda: drive_inflate(ref, fmt, stream, steps, tail, cap)))
+
+
+def test_lznt1_inflate_matches_reference_call_by_call(oracle, gpu_ctx):
+    import ms_compress_amd as m
+    ref = oracle.load_ref()
+    mine = m.load_library()
+    n_cmp = 0
+    for stream, cap, steps, tail in inflate_cases(oracle):
+        got = drive_inflate(mine, 2, stream, steps, tail, cap)
+        assert digest(got) == ref_drive_inflate(ref, 2, stream, steps, tail, cap), (len(stream), cap, steps[:4], tail, got[1][-3:])
+        n_cmp += 1
     assert n_cmp >= 200
 
 
@@ -182,29 +195,37 @@ def test_deflate_look_ahead_notices_changed_input(oracle, gpu_ctx):
     behind the consumed part rewritten between two calls: same trace, same output."""
     import ms_compress_amd as m
     ref = oracle.load_ref()
-    if ref is None:
-        pytest.skip("compiled reference not available")
+    assert digest(deflate_look_ahead_run(m.load_library())) == answer(("deflate look-ahead",), ref and (lambda: deflate_look_ahead_run(ref)))
+
+
+def deflate_look_ahead_run(lib):
+    """test_deflate_look_ahead_notices_changed_input on one library: (output, trace, status of ms_deflate_end)"""
     rnd = random.Random(9)
     a = cases.family("lz", 40000, rnd); b = cases.family("words", 40000, rnd)
+    for f in (lib.ms_deflate_init, lib.ms_deflate, lib.ms_deflate_end):
+        f.restype = C.c_int
+    lib.ms_deflate_init.argtypes = [C.c_int, C.POINTER(Stream)]; lib.ms_deflate.argtypes = [C.POINTER(Stream), C.c_int]; lib.ms_deflate_end.argtypes = [C.POINTER(Stream)]
+    s = Stream(); assert lib.ms_deflate_init(2, C.byref(s)) == 0
+    inbuf = C.create_string_buffer(a, len(a)); outbuf = C.create_string_buffer(200000)
+    ipos = opos = 0; trace = []
+    for i in range(4000):
+        if i == 3:                                               # after three calls: everything not yet consumed becomes other data
+            C.memmove(C.addressof(inbuf) + ipos, b[ipos:], len(a) - ipos)
+        s.in_ = C.addressof(inbuf) + ipos; s.in_avail = len(a) - ipos; s.out = C.addressof(outbuf) + opos; s.out_avail = 300
+        st = lib.ms_deflate(C.byref(s), FINISH)
+        ipos += (len(a) - ipos) - s.in_avail; opos += 300 - s.out_avail
+        trace.append((st, ipos, opos))
+        if st != 0:
+            break
+    return outbuf.raw[:opos], trace, lib.ms_deflate_end(C.byref(s))
 
-    def run(lib):
-        for f in (lib.ms_deflate_init, lib.ms_deflate, lib.ms_deflate_end):
-            f.restype = C.c_int
-        lib.ms_deflate_init.argtypes = [C.c_int, C.POINTER(Stream)]; lib.ms_deflate.argtypes = [C.POINTER(Stream), C.c_int]; lib.ms_deflate_end.argtypes = [C.POINTER(Stream)]
-        s = Stream(); assert lib.ms_deflate_init(2, C.byref(s)) == 0
-        inbuf = C.create_string_buffer(a, len(a)); outbuf = C.create_string_buffer(200000)
-        ipos = opos = 0; trace = []
-        for i in range(4000):
-            if i == 3:                                               # after three calls: everything not yet consumed becomes other data
-                C.memmove(C.addressof(inbuf) + ipos, b[ipos:], len(a) - ipos)
-            s.in_ = C.addressof(inbuf) + ipos; s.in_avail = len(a) - ipos; s.out = C.addressof(outbuf) + opos; s.out_avail = 300
-            st = lib.ms_deflate(C.byref(s), FINISH)
-            ipos += (len(a) - ipos) - s.in_avail; opos += 300 - s.out_avail
-            trace.append((st, ipos, opos))
-            if st != 0:
-                break
-        return outbuf.raw[:opos], trace, lib.ms_deflate_end(C.byref(s))
-    assert run(m.load_library()) == run(ref)
+
+def sa_deflate_cases():
+    """(data, steps, tail window) for test_lznt1_deflate_under_the_suffix_array_flavour"""
+    rnd = random.Random(21)
+    datas = [cases.family("words", 4096, rnd), cases.family("lz", 12289, rnd), bytes(rnd.choice(b"abc") for _ in range(30000)),
+             cases.mixed_buffer()[95000:95000 + 120000]]
+    return [(data, steps, tail) for data in datas for steps, tail in plans(rnd, len(data))]
 
 
 def test_lznt1_deflate_under_the_suffix_array_flavour(oracle, gpu_ctx):
@@ -213,24 +234,16 @@ def test_lznt1_deflate_under_the_suffix_array_flavour(oracle, gpu_ctx):
     one-shot output -- not the default flavour's."""
     import ms_compress_amd as m
     ref = oracle.load_ref_sa()
-    if ref is None:
-        pytest.skip("oracle/_ref/libMSCompression_sa.so not built")
     mine = m.load_library()
-    rnd = random.Random(21)
-    datas = [cases.family("words", 4096, rnd), cases.family("lz", 12289, rnd), bytes(rnd.choice(b"abc") for _ in range(30000)),
-             cases.mixed_buffer()[95000:95000 + 120000]]
     mine.mscomp_amd_set_lznt1_sa_dict(1)
     try:
         n_cmp = 0
-        for data in datas:
-            for steps, tail in plans(rnd, len(data)):
-                want = drive(ref, 2, data, steps, tail)
-                got = drive(mine, 2, data, steps, tail)
-                assert got[1] == want[1], (len(data), steps[:4], tail)
-                assert got[0] == want[0] and got[2] == want[2]
-                n_cmp += 1
+        for data, steps, tail in sa_deflate_cases():
+            got = drive(mine, 2, data, steps, tail)
+            assert digest(got) == ref_drive(ref, 2, data, steps, tail, "deflate sa"), (len(data), steps[:4], tail)
+            n_cmp += 1
         assert n_cmp >= 40
-        data = datas[2]
+        data = [d for d, _, _ in sa_deflate_cases() if len(d) == 30000][0]
         out, _, end = drive(mine, 2, data, [(7000, 3000, NO_FLUSH)] * 10, 5000)
         assert end == 0 and out == oracle.oracle_compress_sa(data)[1] and out != oracle.oracle_compress(2, data)[1]
     finally:
