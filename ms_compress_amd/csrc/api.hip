@@ -166,12 +166,7 @@ uint32_t chunks_of(MSCompFormat f, bool decompress, uint64_t n)
 
 extern "C" {
 
-#ifdef MSCOMP_AMD_DEV
-#define MSCOMP_AMD_FLAVOUR "; DEVELOPMENT flavour: + the measurement-mode Xpress+Huffman finders"
-#else
-#define MSCOMP_AMD_FLAVOUR ""
-#endif
-const char* mscomp_amd_version(void) { return "mscomp_amd 0.6 (gfx950, HIP; LZNT1 / Xpress / Xpress+Huffman compressors and decompressors, LZNT1 streaming, host batches over several GPUs" MSCOMP_AMD_FLAVOUR ")"; }
+const char* mscomp_amd_version(void) { return "mscomp_amd 0.6 (gfx950, HIP; LZNT1 / Xpress / Xpress+Huffman compressors and decompressors, LZNT1 streaming, host batches over several GPUs)"; }
 
 size_t lznt1_max_compressed_size(size_t n)       { return n + 3 + 2 * ((n + 4095) / 4096); }
 size_t xpress_max_compressed_size(size_t n)      { return n + 4 + 4 * (n / 32); }
@@ -448,16 +443,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	if (ok && format != MSCOMP_LZNT1) {
 		const size_t per = (size_t)p->n_chunks * 65536u * sizeof(uint16_t) + 64;
 		// (mlen3: 4 bytes per position, both halves of the match word)
-#ifdef MSCOMP_AMD_DEV
-		// (development flavour: Xpress+Huffman's sorted-span finder keeps its padded position array in `links` and its bucket starts, XS_STARTS_STRIDE
-		// words per chunk, in `lasthead` -- reserved only when that measurement mode is switched on)
-		static const bool xs_on = [] { const char* e = getenv("MSCOMP_AMD_XH_SORT"); return e && atoi(e) != 0; }();
-		const size_t lh = (xs_on && format == MSCOMP_XPRESS_HUFF) ? (size_t)p->n_chunks * XS_STARTS_STRIDE * sizeof(uint32_t) + 64 : per / 2 + 64;
-		const size_t lpad = xs_on ? 2 * XS_FRONT_PAD : 0;
-#else
-		const size_t lh = per / 2 + 64, lpad = 0;
-#endif
-		ok = c->links.reserve(per + lpad) && c->mlen3.reserve(2 * per) && c->lasthead.reserve(lh);
+		ok = c->links.reserve(per) && c->mlen3.reserve(2 * per) && c->lasthead.reserve(per / 2 + 64);
 		if (ok && format == MSCOMP_XPRESS) {
 			const size_t nw = (size_t)p->n_chunks * 1024u + 64;
 			ok = c->wtok.reserve(nw * 8) && c->wmat.reserve(nw * 8) && c->wfar.reserve(nw * 4);
@@ -650,17 +636,6 @@ static MSCompStatus plan_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t
 		uint32_t* extra = static_cast<uint32_t*>(c->extra.p); uint8_t* lens = static_cast<uint8_t*>(c->lens.p);
 		uint16_t* codes = static_cast<uint16_t*>(c->codes.p); uint32_t* fbflag = static_cast<uint32_t*>(c->fbflag.p);
 		uint32_t* fb_count = static_cast<uint32_t*>(c->fb_list.p); uint32_t* fb_list = fb_count + 16;
-#ifdef MSCOMP_AMD_DEV
-		static const bool xh_lazy = [] { const char* e = getenv("MSCOMP_AMD_XH_LAZY"); return e && atoi(e) != 0; }();   // measurement switch: the lazy finder of xhuff_lazy.hip
-		static const int xh_sort = [] { const char* e = getenv("MSCOMP_AMD_XH_SORT"); return e ? atoi(e) : 0; }();      // the finder of xpress_sort.hip (sorted spans instead of the chain walk)
-		if (xh_sort && !xh_lazy) {
-			{ KernelTimer t(c, "xp_sort_kernel"); launch_xp_sort(st, d_in, p->bt, links + XS_FRONT_PAD, reinterpret_cast<uint32_t*>(mlen3), reinterpret_cast<uint32_t*>(lasthead)); }
-			{ KernelTimer t(c, "xp_find2_kernel"); launch_xp_find2(st, d_in, p->bt, links + XS_FRONT_PAD, reinterpret_cast<const uint32_t*>(lasthead), reinterpret_cast<uint32_t*>(mlen3), 0xFFFFu, 1); }
-		} else if (xh_lazy) {
-			{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead); }
-			{ KernelTimer t(c, "xh_lazy_kernel"); launch_xh_lazy(st, d_in, p->bt, links, lasthead, mlen3); }
-		} else
-#endif
 		if (p->matches_ready) { p->matches_ready = false; }
 		else {
 			{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead); }

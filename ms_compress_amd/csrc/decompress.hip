@@ -1274,9 +1274,6 @@ extern "C" void mscomp_amd_debug_xhc_prof(unsigned long long* out) { (void)hipMe
 #define XHC_LOC(i)
 #define XHC_END()
 #endif
-#ifndef XHC_WIDE2
-#define XHC_WIDE2 1                                            // two windows of 64 bit offsets per step (0: one)
-#endif
 template <int PASS>
 __global__ __launch_bounds__(64) void xhc_parse_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, const u64* __restrict__ tok_prefix,
                                                       const u64* __restrict__ cand_prefix, XhcBufs xb, uint32_t* __restrict__ tok)
@@ -1389,7 +1386,6 @@ __global__ __launch_bounds__(64) void xhc_parse_kernel(const uint8_t* __restrict
 			// (:87) -- possibly to the end of the buffer. A candidate is not followed there: it counts as "not a chunk", and a buffer
 			// whose chain does not close without it goes to the serial walk, which follows the reference to the letter.
 			if (!writing && prod >= 65536u) { status = -3; break; }
-#if XHC_WIDE2
 			if (!skip_wide && prod < 65536u && bits >= 16u && endq - ip >= 24u) {
 				// ---- many symbols per step: lane b decodes the symbols that would start b and 64 + b bits from here (the code through the same
 				// tables, a match's offset bits behind it); the symbols that really follow each other are then a walk b -> b + bits taken from
@@ -1481,71 +1477,6 @@ __global__ __launch_bounds__(64) void xhc_parse_kernel(const uint8_t* __restrict
 					continue;
 				}
 			}
-#else
-			if (!skip_wide && prod < 65536u && bits >= 16u && endq - ip >= 16u) {
-				// ---- many symbols per step: lane b decodes the symbol that would start b bits from here (the code through the same tables, a match's
-				// offset bits behind it); the symbols that really follow each other are then a walk b -> b + bits taken from lane 0, by readlane.
-				// Stops in front of a match with length bytes (they sit in the byte stream, where the next 16 bits would be pulled from: the
-				// symbol-at-a-time code below takes that one) and in front of anything invalid; the bit buffer is rebuilt as Bitstream.h would hold it.
-				XHD_NEED(ip, 16u)
-				uint32_t d0, d1, d2;                                       // bytes ip .. ip + 11: six 16-bit words, each the next 16 bits of the stream
-				{
-					const uint32_t* in32 = reinterpret_cast<const uint32_t*>(S.in);
-					const uint32_t i_ = (ip >> 2) & (2u * XHD_INB / 4u - 1u), sh_ = ip & 3u, M_ = 2u * XHD_INB / 4u - 1u;
-					const uint32_t a_ = in32[i_], b_ = in32[(i_ + 1u) & M_], c_ = in32[(i_ + 2u) & M_], e_ = in32[(i_ + 3u) & M_];
-					d0 = __builtin_amdgcn_alignbyte(b_, a_, sh_); d1 = __builtin_amdgcn_alignbyte(c_, b_, sh_); d2 = __builtin_amdgcn_alignbyte(e_, c_, sh_);
-				}
-				#define XHD_SWAP16(x) (((x) << 16) | ((x) >> 16))              /* word k of the stream first: (w0 << 16) | w1 */
-				const u64 t0 = ((u64)XHD_SWAP16(d0) << 32) | XHD_SWAP16(d1), t1 = (u64)XHD_SWAP16(d2) << 32;
-				#undef XHD_SWAP16
-				const u64 s_hi = ((u64)mask << 32) | (t0 >> bits), s_lo = (t0 << (64u - bits)) | (t1 >> bits);   // the next 128 bits of the stream (bits + 96 of them real)
-				const uint32_t view = (uint32_t)((lane ? (s_hi << lane) | (s_lo >> (64u - lane)) : s_hi) >> 32);
-				const uint32_t x15 = view >> 17;
-				const uint32_t f = S.fast[x15 >> 6];
-				uint32_t n, sy;
-				if (f) { n = f & 0xFu; sy = f >> 4; }
-				else if (x15 < lims9) { n = 1; sy = 0xFFFFu; }               // a short code that no symbol has (the table says 0 for it too)
-				else {                                                       // a code of 10 to 15 bits: its length from the limits (wave-uniform, in registers), no loop
-					n = 10u + (x15 >= lim10 ? 1u : 0u) + (x15 >= lim11 ? 1u : 0u) + (x15 >= lim12 ? 1u : 0u) + (x15 >= lim13 ? 1u : 0u) + (x15 >= lim14 ? 1u : 0u);
-					const uint32_t s_ = S.poss[n] + ((x15 - S.lims[n - 1u]) >> (15u - n)); sy = s_ >= 512u ? 0xFFFFu : S.syms[s_];
-				}
-				const bool lit = sy < 0x100u, mat = !lit && sy != 0xFFFFu;
-				const uint32_t ob = (sy >> 4) & 0xFu;
-				const uint32_t cons = n + (mat ? ob : 0u);
-				const uint32_t moff = ob ? ((view << n) >> (32u - ob)) + (1u << ob) : 1u;
-				const uint32_t mlen = lit ? 1u : (sy & 0xFu) + 3u;
-				const bool evl = !lit && (!mat || (sy & 0xFu) == 0xFu);
-				const u64 evm = __ballot(evl);
-				const uint32_t step = evl ? 64u : cons;                      // (the walk ends on a symbol it must not take, which is then dropped again)
-				u64 mark = 0; uint32_t b = 0;
-				while (b < 64u) { mark |= (u64)1 << b; b += (uint32_t)__builtin_amdgcn_readlane((int)step, (int)b); }
-				if (mark & evm) { b = ctz64(mark & evm); mark &= ~evm; skip_wide = true; }   // (the next symbol is for the code below: no point in looking at it from 64 lanes again)
-				bool on = (mark >> lane) & 1u;
-				const uint32_t l = on ? mlen : 0u, incl = wave_incl_scan_add_u32(l), before = incl - l;
-				const u64 over = __ballot(on && prod + before >= 65536u);                    // the chunk is full in front of this symbol: the loop condition decides there
-				if (over) { const uint32_t sl = ctz64(over); mark &= ((u64)1 << sl) - 1u; b = sl; on = (mark >> lane) & 1u; }
-				if (mark) {
-					const uint32_t lastl = 63u - (uint32_t)__builtin_clzll(mark);
-					const uint32_t adv = (uint32_t)__builtin_amdgcn_readlane((int)incl, (int)lastl);
-					const u64 opi = op + before;
-					const uint32_t rch = (on && mat && (u64)moff > opi) ? (uint32_t)((u64)moff - opi) : 0u;    // how far the match reaches in front of the chunk (offsets are below 65536 + 32768)
-					if (__ballot(rch != 0)) { const uint32_t rmax = wave_max_u32(rch); if (rmax > reach) { reach = rmax; } }
-					const u64 ti = nt + popc_below(mark);
-					if (storing && on && ti < tokcap) { mytok[ti] = lit ? (0x80000000u | sy) : (moff | (mlen << 16)); }
-					nt += (uint32_t)__builtin_popcountll(mark);
-					XHC_CN(0, 1) XHC_CN(1, (uint32_t)__builtin_popcountll(mark)) XHC_LOC(0)
-					op += adv; prod += adv;
-					// Bitstream.h:61-75: a word is pulled whenever fewer than 16 bits are left
-					const int32_t avail = (int32_t)bits - (int32_t)b;
-					const uint32_t pulls = avail < 16 ? (uint32_t)(16 - avail + 15) >> 4 : 0u;
-					const uint32_t nb = (uint32_t)(avail + 16 * (int32_t)pulls);
-					const u64 x64 = b == 0 ? s_hi : (b < 64u ? (s_hi << b) | (s_lo >> (64u - b)) : s_lo << (b - 64u));
-					mask = (uint32_t)(x64 >> 32) & (nb >= 32u ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> nb));
-					bits = nb; ip += 2u * pulls;
-					continue;
-				}
-			}
-#endif
 			skip_wide = false;
 			XHC_CN(2, 1) XHC_LOC(1)
 			uint32_t sym;

@@ -23,11 +23,7 @@ bool serial_atomics_on_current_device();
 void set_serial_atomics(int device, int on);           // on: 1 = one lane at a time. device >= 0: that device's self-check verdict; device < 0: the process-wide test hook (its 0 does NOT clear a verdict)
 
 // ---- LZNT1 (lznt1.hip) ----
-#ifdef LZ_TBL_GLOBAL         /* dev variant (round 6): a 12-bit hash whose bucket-end table (8 KiB) leaves LDS after the sort -- it lies behind the chunk's image in its slot */
-#define LZNT1_SLOT (4352u + 8192u)
-#else
 #define LZNT1_SLOT 4352u     // scratch bytes per 4 KiB chunk image (2 B header + <=4096 B payload + emit slack)
-#endif
 void set_lznt1_mode(int mode);
 void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size);
 void launch_lznt1_sa_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size);   // lznt1_sa.hip: the suffix-array dictionary flavour
@@ -46,21 +42,6 @@ void launch_xp_find_range(hipStream_t st, const uint8_t* d_in, const BatchTables
 // arrays for a superset of the true token starts; the offsets of all other positions are 0.
 void launch_xp_lazy2(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, uint16_t* mlen3, uint16_t* moff);
 
-#ifdef MSCOMP_AMD_DEV
-// MEASUREMENT MODES, in the development flavour of the library only (libmscomp_amd_dev.so, `make dev`): two more Xpress+Huffman match finders that
-// give the same bytes as xp_find_kernel and lose to it. The product library has ONE finder per codec and does not contain them.
-// the lazy finder for Xpress+Huffman (xhuff_lazy.hip, round 5; a measurement mode, MSCOMP_AMD_XH_LAZY=1): the chunk's links in LDS, candidate bytes from L2
-void launch_xh_lazy(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, const uint16_t* lasthead, uint16_t* mlen3);
-
-// the finder without the dependent chain walk (xpress_sort.hip, round 5): positions sorted by (hash, position) per 64 KiB chunk, a position's
-// candidates read as one span of that array. sorted: u16 per position behind XS_FRONT_PAD entries of padding (the caller passes the padded
-// pointer); starts: XS_STARTS_STRIDE u32 per chunk (32768 bucket starts + the total); words: u32 per position -- xp_sort_kernel leaves
-// index | rank << 16 there, xp_find2_kernel replaces it by the match word (the mlen3 / moff array of the other finders).
-#define XS_STARTS_STRIDE 32832u
-#define XS_FRONT_PAD 32u
-void launch_xp_sort(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* sorted, uint32_t* words, uint32_t* starts);
-void launch_xp_find2(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* sorted, const uint32_t* starts, uint32_t* words, uint32_t max_off, int clip);
-#endif
 
 // ---- Xpress stream emission (xpress_emit.hip): one wavefront per unit ----
 void set_xpress_emit_mode(int mode);

@@ -40,11 +40,7 @@ __device__ unsigned long long g_lz_prof[16];
 #endif
 
 #ifndef LZ_TBL_BITS
-#ifdef LZ_TBL_GLOBAL
-#define LZ_TBL_BITS 12
-#else
 #define LZ_TBL_BITS 11
-#endif
 #endif
 #define LZ_TBL      (1u << LZ_TBL_BITS)
 #ifndef LZ_SELF
@@ -122,13 +118,8 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const uint1
 		const uint32_t mask3 = (1u << shift) + 2u;
 		maxlen = (n - p < mask3) ? n - p : mask3;
 		const uint32_t h = lz_hash(o0 & 0xFFFFFFu);          // >= 1
-#ifdef LZ_TBL_GLOBAL
-		const uint32_t se = ld32(reinterpret_cast<const uint8_t*>(s_cnt + (h - 1u)));   // (the table lies in global memory here: both ends in ONE 4-byte gather)
-		s = se & 0xFFFFu; e = se >> 16;
-#else
 		e = s_cnt[h];                                          // bucket h = [end[h-1], end[h])
 		s = s_cnt[h - 1u];
-#endif
 	}
 	// 1. the oldest LZ_SELF candidates (LZNT1Dictionary.h:124-135: in order, strictly longer wins, stop at max_len). With
 	// key = (len << 12) | (4095 - q) the reference's choice is simply the MAXIMUM of the candidates' keys: longest first,
@@ -149,9 +140,6 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const uint1
 	for (uint32_t j = 0; j <= LZ_SELF; ++j) { ex[j] = j < cnt && q[j] < p; }
 	const bool longer = maxlen > 16u;
 	const uint32_t capb = (maxlen < 16u ? maxlen : 16u) << 3;
-#if defined(LZ_PROBE) && LZ_PROBE == 5      /* dev probe (SUBTRACTIVE, not bit-exact): the eager scan of the odd windows is skipped (their positions are literals unless finished) */
-	if (!((wbase >> 6) & 1u))
-#endif
 	{
 		uint4 c[LZ_SELF];                                     // (all loads in flight together)
 		#pragma unroll
@@ -164,18 +152,10 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const uint1
 			key = kk > key ? kk : key;
 		}
 	}
-#if defined(LZ_PROBE) && LZ_PROBE == 1      /* dev probe: 40 more VALU instructions per window */
-	{ uint32_t y_ = key; _Pragma("unroll") for (int q_ = 0; q_ < 40; ++q_) { asm volatile("v_add_u32 %0, %0, %1" : "+v"(y_) : "v"(o0)); } asm volatile("" :: "v"(y_)); }
-#elif defined(LZ_PROBE) && LZ_PROBE == 2    /* dev probe: four more 16-byte LDS reads per window */
-	{ _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) { const uint4 y_ = lds_ld128(s_data, (p * 7u + 64u * q_) & 4095u); asm volatile("" :: "v"(y_.x), "v"(y_.y), "v"(y_.z), "v"(y_.w)); } }
-#endif
 	// 2. greedy walk; unresolved positions (a fifth older candidate exists and max_len was not reached) are finished by the whole wave
 	// when (and only when) the walk lands on them. (The masks are built from ballots of single compares, combined on the scalar
 	// unit: the ballot of a combined condition costs two more vector instructions. len <= maxlen, so "not reached" is key < maxlen << 12.)
 	u64 un = __builtin_amdgcn_ballot_w64(cnt > LZ_SELF) & __builtin_amdgcn_ballot_w64(q[LZ_SELF] < p) & __builtin_amdgcn_ballot_w64(key < (maxlen << 12));
-#if defined(LZ_PROBE) && LZ_PROBE == 6      /* dev probe (SUBTRACTIVE, not bit-exact): no position is ever finished by the wave -- the 4 eager candidates are all there is */
-	un = 0;
-#endif
 	u64 mm = __builtin_amdgcn_ballot_w64(key >= (3u << 12)) & ~un;              // resolved positions that have a match
 	// The serial loop only decides which candidates are TAKEN; everything else (which positions are literal tokens)
 	// is derived in parallel afterwards.
@@ -241,11 +221,6 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const uint1
 				const uint4 c = lz_ld128(s_data, qq);
 				uint32_t l2 = lz_diff_bits16(c.x ^ a0, c.y ^ a1, c.z ^ a2, c.w ^ a3, capL);   // in bits
 				if (valid && l2 >= 128u && longL) { const uint32_t l = lz_lcp_tail(s_data, qq, pL, maxL); l2 = (l < maxL ? l : maxL) << 3; }
-#if defined(LZ_PROBE) && LZ_PROBE == 3      /* dev probe: 20 more VALU instructions per finishing step */
-				{ uint32_t y_ = l2; _Pragma("unroll") for (int q_ = 0; q_ < 20; ++q_) { asm volatile("v_add_u32 %0, %0, %1" : "+v"(y_) : "v"(qq)); } asm volatile("" :: "v"(y_)); }
-#elif defined(LZ_PROBE) && LZ_PROBE == 4    /* dev probe: one more 16-byte LDS read per finishing step */
-				{ const uint4 y_ = lds_ld128(s_data, (qq * 7u + 64u) & 4095u); asm volatile("" :: "v"(y_.x), "v"(y_.y), "v"(y_.z), "v"(y_.w)); }
-#endif
 				uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(vmask));   // (a key below 3 << 12 is no match)
 				const uint32_t m = wave_max_u32(k2);
 				kbest = m > kbest ? m : kbest;                   // longest, then oldest (older blocks hold the larger 4095 - q)
@@ -487,29 +462,6 @@ template <bool serial>
 __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                           uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size)
 {
-#ifdef LZ_TBL_GLOBAL
-	// dev variant: 12-bit hash. 20 480 B exactly -> still 8 blocks per CU: the bucket-end table (8 KiB) shares its LDS with the parse records -- it is
-	// written to the chunk's scratch slot in global memory after the sort and looked up there by the parse (one 4-byte gather per lane and window) --
-	// the prefixes and flags of the emission take the place of the (then dead) bucket array, and the chunk has no pad behind it (a read behind the
-	// chunk falls into bucket[]: every length is capped by what the chunk has left).
-	struct __attribute__((aligned(16))) Lds {
-		uint8_t  data[4096];
-		uint16_t bucket[4096];
-		union {
-			uint16_t cnt[LZ_TBL];
-			struct { u64 tok[64], mat[64]; uint16_t endc[64]; uint16_t ptok[64][LZ4_MAXM]; uint32_t prog[LZ4_NSEG]; uint32_t used[LZ4_NSEG]; uint32_t segctr; uint32_t total[2]; } r;
-		};
-	};
-	static_assert(sizeof(Lds) <= 20480, "eight blocks per CU");
-	__shared__ Lds L;
-	uint8_t* const s_data = L.data; uint16_t* const s_cnt = L.cnt; uint16_t* const s_bucket = L.bucket;
-	u64* const s_tok = L.r.tok; u64* const s_mat = L.r.mat; uint16_t* const s_endc = L.r.endc; uint16_t (* const s_ptok)[LZ4_MAXM] = L.r.ptok;
-	uint32_t* const s_prog = L.r.prog; uint32_t* const s_used = L.r.used; uint32_t& s_segctr = L.r.segctr; uint32_t* const s_total = L.r.total;
-	uint16_t* const s_T = s_bucket;                                        // [64] tokens before window w          } after the parse (bucket[] is dead then)
-	uint16_t* const s_S = s_bucket + 64;                                   // [64] token bytes before window w     }
-	uint16_t* const s_flagpos = s_bucket + 128;                            // [512] byte position of group g's flag byte
-	uint32_t* const s_flagacc = reinterpret_cast<uint32_t*>(s_bucket + 640);   // [512] its bits
-#else
 	struct __attribute__((aligned(16))) Lds {                              // one object, the chunk first (see the kernel above); 20 432 B -> 8 blocks per CU
 		uint8_t  data[4096 + 32];
 		uint16_t bucket[4096];
@@ -532,7 +484,6 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	uint16_t* const s_flagpos = s_cnt + 128;                               // [512] byte position of group g's flag byte
 	uint32_t* const s_flagacc = reinterpret_cast<uint32_t*>(s_cnt + 640);  // [512] its bits (LZ_TBL u16 = 4096 B >= 1280 + 2048)
 
-#endif
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
 	const uint32_t c = blockIdx.x;
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, c);
@@ -553,15 +504,10 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		const uint32_t nvec = (((uintptr_t)src & 15u) == 0) ? (n & ~15u) : 0u;
 		for (uint32_t i = tid * 16u; i < nvec; i += 4096u) { *reinterpret_cast<uint4*>(s_data + i) = *reinterpret_cast<const uint4*>(src + i); }
 		for (uint32_t i = nvec + tid; i < n; i += 256u) { s_data[i] = src[i]; }
-#ifdef LZ_TBL_GLOBAL
-		for (uint32_t i = n + tid; i < 4096u; i += 256u) { s_data[i] = 0; }
-		for (uint32_t i = tid * 8u; i < LZ_TBL; i += 2048u) { *reinterpret_cast<uint4*>(s_cnt + i) = make_uint4(0, 0, 0, 0); }
-#else
 		for (uint32_t i = n + tid; i < 4096u + 32u; i += 256u) { s_data[i] = 0; }
 		for (uint32_t i = tid * 8u; i < LZ_TBL; i += 2048u) { *reinterpret_cast<uint4*>(s_cnt + i) = make_uint4(0, 0, 0, 0); }
 		if (tid < LZ4_NSEG) { s_prog[tid] = 0; s_used[tid] = 0; }
 		if (tid == 0) { s_segctr = 0; }
-#endif
 	}
 	__syncthreads();
 	LZ4_T(0)
@@ -619,18 +565,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		}
 	}
 	__syncthreads();
-#ifdef LZ_TBL_GLOBAL
-	// the table leaves LDS: 8 KiB behind the chunk's image in its scratch slot (same CU writes and reads it: L2-resident), the parse records take its place
-	uint16_t* __restrict__ const g_tbl = reinterpret_cast<uint16_t*>(img + 4352u);
-	for (uint32_t i = tid * 8u; i < LZ_TBL; i += 2048u) { *reinterpret_cast<uint4*>(g_tbl + i) = *reinterpret_cast<const uint4*>(s_cnt + i); }
-	__syncthreads();
-	if (tid < LZ4_NSEG) { s_prog[tid] = 0; s_used[tid] = 0; }
-	if (tid == 0) { s_segctr = 0; }
-	__syncthreads();
-	const uint16_t* const tbl = g_tbl;
-#else
 	const uint16_t* const tbl = s_cnt;
-#endif
 	LZ4_T(1)
 
 	// ---- C1. speculative parse of my segment ------------------------------------------------------------------------

@@ -26,7 +26,6 @@
 // walk, the match's full length (round 6); offsets of unvisited positions are 0.
 #include "common.h"
 #include "kernels.h"
-#include <cstdlib>
 
 namespace msc {
 
@@ -372,12 +371,7 @@ void launch_xp_lazy2(hipStream_t st, const uint8_t* d_in, const BatchTables& bt,
 	if (bt.n_chunks == 0) { return; }
 	// shapes measured on BASELINE configs[4] (ms per pass): 16 KiB tiles / 32-byte segments (512 lanes, 2 blocks = 16 waves per CU) 35.3;
 	// 16-byte segments with 1024 lanes at 64 registers 37.9; 8 KiB tiles / 16-byte segments (3 blocks = 24 waves) 39.5; / 8-byte segments 55.5
-	static const int variant = [] { const char* e = getenv("MSCOMP_AMD_XZ"); return e ? atoi(e) : 0; }();   // dev switch
-	switch (variant) {
-	case 1:  launch_xz<16384u, 16u, 8u>(st, d_in, bt, links, mlen3, moff); break;
-	case 2:  launch_xz<8192u, 16u, 6u>(st, d_in, bt, links, mlen3, moff); break;
-	default: launch_xz<16384u, 32u, 4u>(st, d_in, bt, links, mlen3, moff); break;
-	}
+	launch_xz<16384u, 32u, 4u>(st, d_in, bt, links, mlen3, moff);
 }
 
 } // namespace msc

@@ -22,7 +22,6 @@
 //                     (XpressDictionary.h:88-93) is the limit n-p-1.
 #include "common.h"
 #include "kernels.h"
-#include <cstdlib>
 
 namespace msc {
 
@@ -254,10 +253,8 @@ __global__ __launch_bounds__(NT) void xp_find_kernel(const uint8_t* __restrict__
 	}
 	__syncthreads();
 
-	// links of this chunk; the previous chunk's array directly precedes it, so a window-relative position xr is entry
-	// lkw[xr] of an array that starts where the window starts (unsigned 32-bit index: scalar base + lane offset)
+	// links of this chunk; the previous chunk's array directly precedes it
 	const uint16_t* __restrict__ lkg = links + (u64)lc * 65536u;
-	const uint16_t* __restrict__ lkw = lkg - (ptrdiff_t)(cbase - wstart); (void)lkw;   // (dev probes only)
 	const uint16_t* __restrict__ lh_prev = lasthead + (u64)(lc - (k ? 1u : 0u)) * 32768u;
 	const uint32_t tn = (cn - tstart < XP_TILE) ? cn - tstart : XP_TILE;
 	// 65535 as the previous chunk's head is indistinguishable from "none" (0xFFFF): decide by that position's hash
@@ -286,11 +283,7 @@ __global__ __launch_bounds__(NT) void xp_find_kernel(const uint8_t* __restrict__
 		const uint32_t pr = p0r + t;                                            // window-relative position of P
 		int32_t key = 2 << 16;
 		const bool can = ((u64)t + 2u < tail) && (!clip || cn - o >= 3u);
-#if defined(XF_PROBE) && XF_PROBE == 4       /* dev probe (SUBTRACTIVE, not bit-exact): walk 6 chain candidates instead of 11 */
-		uint32_t chain = 6;
-#else
 		uint32_t chain = 11;
-#endif
 		if (can) {
 			const uint4 oa = ld128(s_data, pr), ob = ld128(s_data, pr + 16u), oc = ld128(s_data, pr + 32u);
 			const uint32_t h = xp_hash3(oa.x);
@@ -322,37 +315,14 @@ __global__ __launch_bounds__(NT) void xp_find_kernel(const uint8_t* __restrict__
 				const uint32_t xr = (uint32_t)(rc + crel);                         // window-relative
 				// the link of the candidate is fetched first (L2 latency for Xpress+Huffman) and consumed after the compare
 				// (byte offset in 32 bits, zero-extended: the gather is `global_load_ushort v, v_offset, s[base]`)
-				uint32_t x;
-#if defined(XF_PROBE) && XF_PROBE == 7        /* dev probe (SUBTRACTIVE, not bit-exact): the link of ANOTHER position, chosen so that the 64 lanes of a wave read consecutive links (a coalesced load instead of a divergent gather; the chain then walks other, equally real, positions) */
-				x = (uint32_t)lkw[((uint32_t)pr - 1u - chain) & 0xFFFFu];
-				if (false)
-#endif
 				// (cache-scope variants of this gather: non-temporal 126.7 ms, sc1 / sc0 sc1 78.7, sc0 65.1, plain 64.9: the L1 serves ~60 % of the lanes)
-#if defined(XF_PROBE) && XF_PROBE == 8        /* dev probe (not bit-exact): NO link load and no dependent chain -- the next candidate lies 37 bytes further back; the compares are the product's */
-				x = (uint32_t)(rc - adj - 37) & 0xFFFFu; if (rc - adj < 37) { x = 0xFFFFu; }
-				if (false)
-#elif defined(XF_PROBE) && XF_PROBE == 9      /* dev probe (not bit-exact): the link gather on every SECOND step only (what a two-links-per-gather layout would issue), arithmetic in between */
-				x = (uint32_t)(rc - adj - 37) & 0xFFFFu; if (rc - adj < 37) { x = 0xFFFFu; }
-				if (chain & 1u)
-#endif
-				x = (LINKW == WINDOW) ? (uint32_t)s_links[xr - lrel]
-				                      : (uint32_t)*reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(lkb) + (u64)(uint32_t)((rc << 1) + 131072));
+				uint32_t x = (LINKW == WINDOW) ? (uint32_t)s_links[xr - lrel]
+				                               : (uint32_t)*reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(lkb) + (u64)(uint32_t)((rc << 1) + 131072));
 				// 16 bytes per step against my own 48 bytes held in registers (lengths are capped at 48 here)
 				uint4 c = ld128(s_data, xr);
-#if defined(XF_PROBE) && XF_PROBE == 1        /* dev probe: one more divergent global gather per step */
-				{ const uint32_t y = lkw[((uint32_t)xr * 7u + 13u) & 0xFFFFu]; asm volatile("" :: "v"(y)); }
-#elif defined(XF_PROBE) && XF_PROBE == 2      /* dev probe: ten more VALU instructions per step */
-				{ uint32_t y = (uint32_t)negd; _Pragma("unroll") for (int q_ = 0; q_ < 10; ++q_) { asm volatile("v_add_u32 %0, %0, %1" : "+v"(y) : "v"(c.x)); } asm volatile("" :: "v"(y)); }
-#elif defined(XF_PROBE) && XF_PROBE == 3      /* dev probe: five more LDS dword reads per step */
-				{ const uint4 y = ld128(s_data, ((uint32_t)xr * 5u + 77u) & 0xFFFFu); asm volatile("" :: "v"(y.x), "v"(y.y), "v"(y.z), "v"(y.w)); }
-#endif
 				// matched length in BITS, capped inside the minimum that finds the first difference (the low three bits are dropped below)
 				uint32_t lb = first_diff_bits16(c.x ^ oa.x, c.y ^ oa.y, c.z ^ oa.z, c.w ^ oa.w, capb);
-#if defined(XF_PROBE) && XF_PROBE == 5       /* dev probe (SUBTRACTIVE, not bit-exact): no compare beyond the first 16 bytes */
-				if (false) {
-#else
 				if (lb >= 128u && cap > 16u) {
-#endif
 					c = ld128(s_data, xr + 16u);
 					uint32_t l = 16u + first_diff16(make_uint4(c.x ^ ob.x, c.y ^ ob.y, c.z ^ ob.z, c.w ^ ob.w));
 					if (l == 32u && cap > 32u) {
@@ -414,8 +384,7 @@ void launch_xp_find_range(hipStream_t st, const uint8_t* d_in, const BatchTables
 	static PerDeviceOnce attr;
 	constexpr uint32_t TXP = 4096u, TXH = XH_TILE_SEL;
 	const uint32_t lds_xp = 0x2000u + TXP + 64u + (0x2000u + TXP) * 2u;           // data + all links of the window in LDS
-	static const uint32_t xh_pad = [] { const char* e = getenv("MSCOMP_AMD_XF_LDS_PAD_KB"); return e ? (uint32_t)atoi(e) * 1024u : 0u; }();   // dev: more LDS per block = fewer blocks per CU (occupancy probe)
-	const uint32_t lds_xh = 0x10000u + TXH + 64u + xh_pad;                        // data only (2 blocks/CU); links come from L2
+	const uint32_t lds_xh = 0x10000u + TXH + 64u;                                // data only (2 blocks/CU); links come from L2
 	if (attr.needed()) {
 		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_find_kernel<0x2000u, 0x2000u, 512u, TXP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xp);
 		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_find_kernel<0x10000u, 0u, 1024u, TXH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xh);
