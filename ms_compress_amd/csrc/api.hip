@@ -56,6 +56,7 @@ struct mscomp_amd_ctx {
 	int device = 0;
 	hipStream_t stream = nullptr;
 	DevBuf slots, slot_size, prefix, tile_sums;        // chunk scratch (grow-only, shared by all plans of the ctx)
+	DevBuf lzrec;                                      // LZNT1 parse records per chunk (LZNT1_REC bytes: match tokens per window)
 	DevBuf links, lasthead, mlen3, moff;               // Xpress-family match finder scratch (per 64 KiB link chunk)
 	DevBuf wtok, wmat, wfar;                           // Xpress parse records per 64-position window (token mask, match mask, far length)
 	DevBuf wrec, sbrec;                                // ... state / counts / prefixes per window (6 x u32), per super-block (tot 4 x u32, pre 3 x u64, seams)
@@ -77,7 +78,7 @@ struct mscomp_amd_ctx {
 	std::vector<hipEvent_t> free_events;
 	std::vector<DevBuf*> bufs()
 	{
-		return { &slots, &slot_size, &prefix, &tile_sums, &links, &lasthead, &mlen3, &moff, &wtok, &wmat, &wfar, &wrec, &sbrec,
+		return { &slots, &slot_size, &prefix, &tile_sums, &lzrec, &links, &lasthead, &mlen3, &moff, &wtok, &wmat, &wfar, &wrec, &sbrec,
 		         &tokbits, &counts, &extra, &lens, &codes, &fb_list, &fbflag, &dz_cin, &dz_csize, &dz_unit, &dz_tok, &dz_ntok, &dz_xhc, &dz_scr,
 		         &lzg_bsum, &lzg_dir, &lzg_words, &xps_buf, &cp_tab, &one_in, &one_out, &one_meta };
 	}
@@ -440,6 +441,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	          c->prefix.reserve(((size_t)p->n_chunks + 2) * sizeof(uint64_t)) &&
 	          c->tile_sums.reserve(((size_t)p->n_chunks / 1024 + 4) * sizeof(uint64_t));
 	if (ok && format == MSCOMP_LZNT1) { ok = c->slots.reserve((size_t)p->n_chunks * LZNT1_SLOT + 64); }
+	if (ok && format == MSCOMP_LZNT1 && !p->decompress && !p->lznt1_sa) { ok = c->lzrec.reserve((size_t)p->n_chunks * LZNT1_REC + 64); }
 	if (ok && format != MSCOMP_LZNT1) {
 		const size_t per = (size_t)p->n_chunks * 65536u * sizeof(uint16_t) + 64;
 		// (mlen3: 4 bytes per position, both halves of the match word)
@@ -610,7 +612,7 @@ static MSCompStatus plan_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t
 	case MSCOMP_LZNT1: {
 		uint8_t* slots = static_cast<uint8_t*>(c->slots.p);
 		if (p->lznt1_sa) { KernelTimer t(c, "lznt1_sa_chunk_kernel"); launch_lznt1_sa_chunks(st, d_in, p->bt, slots, slot_size); }
-		else { KernelTimer t(c, "lznt1_chunk_kernel"); launch_lznt1_chunks(st, d_in, p->bt, slots, slot_size); }
+		else { KernelTimer t(c, "lznt1_chunk_kernel"); launch_lznt1_chunks(st, d_in, p->bt, slots, slot_size, static_cast<uint16_t*>(c->lzrec.p)); }
 		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, slot_size, prefix, p->n_chunks, tile_sums); }
 		{ KernelTimer t(c, "concat_slots_kernel"); launch_concat_slots(st, slots, LZNT1_SLOT, slot_size, prefix, p->bt, d_out); }
 		{ KernelTimer t(c, "finalize_units_kernel"); launch_finalize_units(st, prefix, p->bt, d_out, d_out_len, d_status, 1); }

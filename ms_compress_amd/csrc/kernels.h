@@ -25,7 +25,8 @@ void set_serial_atomics(int device, int on);           // on: 1 = one lane at a 
 // ---- LZNT1 (lznt1.hip) ----
 #define LZNT1_SLOT 4352u     // scratch bytes per 4 KiB chunk image (2 B header + <=4096 B payload + emit slack)
 void set_lznt1_mode(int mode);
-void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size);
+#define LZNT1_REC  5632u     // scratch bytes of parse records per 4 KiB chunk (four-wave kernel: match tokens of 64 windows, two areas)
+void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs);
 void launch_lznt1_sa_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size);   // lznt1_sa.hip: the suffix-array dictionary flavour
 
 // ---- Xpress / Xpress+Huffman match finder (xpress_match.hip) ----

@@ -3,10 +3,10 @@
 // Replaces: lznt1_compress / lznt1_compress_chunk (/root/reference/src/lznt1_compress.cpp:233-273, :49-94) and
 // LZNT1Dictionary::Fill/Find (/root/reference/include/mscomp/LZNT1Dictionary.h:93-106, :114-143).
 //
-// One wavefront (64-thread block) = one 4 KiB chunk, everything staged in LDS (17.6 KiB -> 9 chunks in flight per CU):
+// One wavefront (64-thread block) = one 4 KiB chunk, everything staged in LDS (20.2 KiB -> 7 chunks in flight per CU):
 //   A. coalesced 16 B/lane load of the chunk into LDS;
 //   B. dictionary = the reference's per-key position arrays as ONE position-sorted bucket array in LDS, built by a stable
-//      counting sort on an 11-bit hash of the 3-byte key: histogram by LDS atomics, exclusive scan of the counts (DPP),
+//      counting sort on a 12-bit hash of the 3-byte key: histogram by LDS atomics, exclusive scan of the counts (DPP),
 //      then an ORDERED scatter in 64 ascending batches (one LDS gather + scatter of the bucket cursors per batch,
 //      intra-batch conflicts resolved with ballots). Afterwards cursor[h] = end of bucket h, so the candidates of a
 //      position are simply the entries of its bucket that are smaller than the position itself;
@@ -39,8 +39,12 @@ __device__ unsigned long long g_lz_prof[16];
 #define LZ_TEND
 #endif
 
+#ifdef LZ4_PROFILE   // dev-only: the four-wave kernel's phase cycles ([0..6], thread 0) and finishing steps ([7], all windows walked)
+__device__ unsigned long long g_lz4_prof[8];
+#endif
+
 #ifndef LZ_TBL_BITS
-#define LZ_TBL_BITS 11
+#define LZ_TBL_BITS 12   // bucket ends stay below 4096: twelve bits each (the four-wave kernel packs them after its sort)
 #endif
 #define LZ_TBL      (1u << LZ_TBL_BITS)
 #ifndef LZ_SELF
@@ -103,8 +107,12 @@ __device__ __forceinline__ uint32_t lz_diff_bits16(uint32_t x0, uint32_t x1, uin
 // position `entry` (the 4 oldest candidates per lane, the rest on demand), greedy walk, token mask. Returns the parse
 // position after the window; key = (len << 12) | (4095 - q) of this lane's match (valid where matchmask is set),
 // o0 = the 4 bytes at this lane's position, shift = its token split.
+// The bucket ends come from `tbl`: u16 per bucket (packed = false), or 12-bit fields, bucket h at bit 12 h (packed = true: the two ends a
+// position needs are 24 bits at bit 12 (h - 1), inside the two dwords from (12 (h - 1)) / 32 on -- one read2 and one v_alignbit, which
+// takes its shift modulo 32). The field of bucket 4095 ends in the last dword of the table: the dword after it is read and shifted out.
 struct LzWin { uint32_t key, o0, shift; u64 tokmask, matchmask; };
-__device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const uint16_t* s_cnt, const uint16_t* s_bucket, uint32_t n, uint32_t lane,
+template <bool packed>
+__device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void* tbl, const uint16_t* s_bucket, uint32_t n, uint32_t lane,
                                               uint32_t wbase, uint32_t entry, LzWin& r)
 {
 	entry = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry); wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);   // (uniform: keeps the walk's bookkeeping on the scalar unit)
@@ -118,8 +126,15 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const uint1
 		const uint32_t mask3 = (1u << shift) + 2u;
 		maxlen = (n - p < mask3) ? n - p : mask3;
 		const uint32_t h = lz_hash(o0 & 0xFFFFFFu);          // >= 1
-		e = s_cnt[h];                                          // bucket h = [end[h-1], end[h])
-		s = s_cnt[h - 1u];
+		if (packed) {                                          // bucket h = [end[h-1], end[h])
+			const uint32_t bit = h * 12u - 12u;
+			const uint32_t* const t = static_cast<const uint32_t*>(tbl) + (bit >> 5);
+			const uint32_t x = __builtin_amdgcn_alignbit(t[1], t[0], bit);
+			s = x & 0xFFFu; e = (x >> 12) & 0xFFFu;
+		} else {
+			e = static_cast<const uint16_t*>(tbl)[h];
+			s = static_cast<const uint16_t*>(tbl)[h - 1u];
+		}
 	}
 	// 1. the oldest LZ_SELF candidates (LZNT1Dictionary.h:124-135: in order, strictly longer wins, stop at max_len). With
 	// key = (len << 12) | (4095 - q) the reference's choice is simply the MAXIMUM of the candidates' keys: longest first,
@@ -210,6 +225,9 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const uint1
 			const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)o0, (int)mp), a1 = (uint32_t)__builtin_amdgcn_readlane((int)o1, (int)mp);
 			const uint32_t a2 = (uint32_t)__builtin_amdgcn_readlane((int)o2, (int)mp), a3 = (uint32_t)__builtin_amdgcn_readlane((int)o3, (int)mp);
 			uint32_t kbest = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)mp);
+#ifdef LZ4_PROFILE
+			uint32_t nsteps = 0;
+#endif
 			const uint32_t pL = wbase + mp;
 			const bool longL = maxL > 16u;
 			const uint32_t capL = (maxL < 16u ? maxL : 16u) << 3;
@@ -224,8 +242,14 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const uint1
 				uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(vmask));   // (a key below 3 << 12 is no match)
 				const uint32_t m = wave_max_u32(k2);
 				kbest = m > kbest ? m : kbest;                   // longest, then oldest (older blocks hold the larger 4095 - q)
+#ifdef LZ4_PROFILE
+				++nsteps;
+#endif
 				if ((kbest >> 12) == maxL || ~vmask) { break; }  // max_len reached / all older candidates seen
 			}
+#ifdef LZ4_PROFILE
+			if (lane == 0) { atomicAdd(&g_lz4_prof[7], (unsigned long long)nsteps); }
+#endif
 			if (lane == mp) { key = kbest; }
 			un = sgpr64(un & ~(((u64)1) << mp));
 			// literals before mp are settled; mp itself is now resolved: take its match, or step over it as a literal
@@ -324,7 +348,7 @@ __global__ __launch_bounds__(64) void lznt1_chunk_kernel(const uint8_t* __restri
 	}
 	__syncthreads();
 	LZ_T(1)
-	// ---- B2. inclusive scan of the 2048 counts -> bucket ENDS (bucket h = [end[h-1], end[h])): coalesced rounds of 8
+	// ---- B2. inclusive scan of the 4096 counts -> bucket ENDS (bucket h = [end[h-1], end[h])): coalesced rounds of 8
 	// bins per lane -----------------------------------------------------------------------------------------------------
 	{
 		uint32_t run = 0;
@@ -368,7 +392,7 @@ __global__ __launch_bounds__(64) void lznt1_chunk_kernel(const uint8_t* __restri
 		const uint32_t wend = (wbase + 64u < n) ? wbase + 64u : n;
 		if (entry >= wend) { continue; }                         // window wholly covered by a match
 		LzWin r;
-		const uint32_t cur = lz_window(s_data, s_cnt, s_bucket, n, lane, wbase, entry, r);
+		const uint32_t cur = lz_window<false>(s_data, s_cnt, s_bucket, n, lane, wbase, entry, r);
 		const uint32_t p = wbase + lane;
 		const uint32_t key = r.key, o0 = r.o0, shift = r.shift;
 		const u64 tokmask = r.tokmask, matchmask = r.matchmask;
@@ -442,47 +466,61 @@ extern "C" void mscomp_amd_debug_lz_prof(unsigned long long* out, int reset)
 // a window equals the recorded one), wave 0 checks that no repair ran through a whole segment (else it cascades,
 // serially), scans tokens / bytes per window, and the four waves emit their segments at known offsets; the flag bytes
 // are OR-ed into a per-group LDS array and stored at the end.
-// Segments (in windows): 4 of shrinking length (22 / 18 / 13 / 11) -- a window costs more the later it lies in the chunk
+// Segments (in windows): 4 of shrinking length (21 / 17 / 14 / 12) -- a window costs more the later it lies in the chunk
 // (fuller buckets) and every seam costs a repair. Round 5, after the window parse lost a quarter of its vector instructions (the
 // finishing steps, which grow along the chunk, lost less), configs[4]: boundaries 16/32/48: 56.9 ms, 18/34/49: 54.9, 20/37/51: 52.6,
-// 22/40/53: 52.5, 24/43/55 (rounds 3-4): 53.5, 26/46/57: 54.4.
+// 22/40/53: 52.5, 24/43/55 (rounds 3-4): 53.5, 26/46/57: 54.4. With the 12-bit hash (fewer finishing steps late in a chunk), configs[4] in ms and
+// configs[1..3]'s kernel time: 18/34/49: 53.14 / 1.043, 19/36/50: 52.49 / 1.012, 20/37/51: 52.29 / 0.991, 21/38/52: 52.33 / 0.977,
+// 22/40/53: 52.67 / 0.978, 23/41/54: 52.95 / 0.969, 24/43/55: 53.53 / 0.966.
 #define LZ4_NSEG 4u
 #ifndef LZ4_B1
-#define LZ4_B1 22u
-#define LZ4_B2 40u
-#define LZ4_B3 53u
+#define LZ4_B1 21u
+#define LZ4_B2 38u
+#define LZ4_B3 52u
 #endif
 __device__ __forceinline__ uint32_t lz4_seg_start(uint32_t j) { return j == 0 ? 0u : j == 1 ? LZ4_B1 : j == 2 ? LZ4_B2 : j == 3 ? LZ4_B3 : 64u; }
 #define LZ4_MAXM 22u                                             // matches that can START in one window of 64 positions
 #ifdef LZ4_PROFILE
-__device__ unsigned long long g_lz4_prof[8];
 extern "C" void mscomp_amd_debug_lz4_prof(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lz4_prof), 64); unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lz4_prof), z, 64); }
 #endif
+static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: LZNT1_REC = two areas of 64 windows of match tokens");
 template <bool serial>
 __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
-                                                          uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size)
+                                                          uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size, uint16_t* __restrict__ recs)
 {
-	struct __attribute__((aligned(16))) Lds {                              // one object, the chunk first (see the kernel above); 20 432 B -> 8 blocks per CU
-		uint8_t  data[4096 + 32];
-		uint16_t bucket[4096];
-		uint16_t cnt[LZ_TBL];                                              // counts -> bucket ends; after the parse: prefixes and flags (below)
-		u64      tok[64], mat[64];                                         // per window
+	// One object, the chunk first (see the kernel above), 20 480 B -> 8 blocks per CU. The chunk has no pad: the reads that run past its
+	// end (lz_ld128 / lds_ld32 reach up to 16 bytes beyond byte 4095, into the bucket array) and the bytes between n and 4096 only feed
+	// (a) keys of positions p with p + 3 <= n, whose fourth byte is masked off, (b) compares whose result is capped by
+	// max_len <= n - p (16-byte compares at 8 min(max_len, 16) bits, lz_lcp_tail clamped to max_len; a candidate q < p stops even
+	// earlier), (c) the raw chunk's copy, whose dwords past 2 + n land in the slot's slack and are never concatenated.
+	struct Ctl {                                                           // parse state, polled or small
+		u64      tok[64], mat[64];                                         // token / match mask per window
 		uint16_t endc[64];                                                 // parse position after the window
-		uint16_t ptok[64][LZ4_MAXM];                                       // its match tokens, in order
 		uint32_t prog[LZ4_NSEG];                                           // windows finished in segment j (index + 1)
 		uint32_t used[LZ4_NSEG];                                           // entry position the seam in front of segment j was repaired against
 		uint32_t segctr;                                                   // next segment to hand out
 		uint32_t total[2];
+		uint8_t  rep[64];                                                  // the window's match tokens are in the repair area (1) or the speculative one (0)
 	};
-	static_assert(sizeof(Lds) <= (LZ_TBL_BITS == 11 ? 20480 : 27306), "eight blocks per CU (dev variants with a wider hash: six)");
+	struct __attribute__((aligned(16))) Lds {
+		uint8_t  data[4096];
+		uint16_t bucket[4096];
+		union {
+			uint16_t cnt[LZ_TBL];                                          // sort: counts -> bucket ends; after the parse: prefixes and flags (below)
+			struct { uint32_t ends[LZ_TBL * 12u / 32u]; Ctl ctl; } parse;   // parse: the ends as 12-bit fields, then the control words
+		} t;
+	};
+	static_assert(LZ_TBL == 4096u, "the pack below hands 16 bucket ends to each of 256 threads");
+	static_assert(sizeof(Lds) <= 20480, "eight blocks per CU");
 	__shared__ Lds L;
-	uint8_t* const s_data = L.data; uint16_t* const s_cnt = L.cnt; uint16_t* const s_bucket = L.bucket;
-	u64* const s_tok = L.tok; u64* const s_mat = L.mat; uint16_t* const s_endc = L.endc; uint16_t (* const s_ptok)[LZ4_MAXM] = L.ptok;
-	uint32_t* const s_prog = L.prog; uint32_t* const s_used = L.used; uint32_t& s_segctr = L.segctr; uint32_t* const s_total = L.total;
-	uint16_t* const s_T = s_cnt;                                           // [64] tokens before window w          } after the parse
-	uint16_t* const s_S = s_cnt + 64;                                      // [64] token bytes before window w     }
+	uint8_t* const s_data = L.data; uint16_t* const s_cnt = L.t.cnt; uint16_t* const s_bucket = L.bucket;
+	Ctl& C = L.t.parse.ctl;
+	u64* const s_tok = C.tok; u64* const s_mat = C.mat; uint16_t* const s_endc = C.endc; uint8_t* const s_rep = C.rep;
+	uint32_t* const s_prog = C.prog; uint32_t* const s_used = C.used; uint32_t& s_segctr = C.segctr; uint32_t* const s_total = C.total;
+	uint16_t* const s_T = s_cnt;                                           // [64] tokens before window w          } after the parse, in the
+	uint16_t* const s_S = s_cnt + 64;                                      // [64] token bytes before window w     } dead packed ends
 	uint16_t* const s_flagpos = s_cnt + 128;                               // [512] byte position of group g's flag byte
-	uint32_t* const s_flagacc = reinterpret_cast<uint32_t*>(s_cnt + 640);  // [512] its bits (LZ_TBL u16 = 4096 B >= 1280 + 2048)
+	uint32_t* const s_flagacc = reinterpret_cast<uint32_t*>(s_cnt + 640);  // [512] its bits (1280 + 2048 B <= the ends' 6144 B)
 
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
 	const uint32_t c = blockIdx.x;
@@ -492,6 +530,10 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	const uint32_t n = left < 4096u ? (uint32_t)left : 4096u;
 	const uint8_t* __restrict__ src = d_in + bt.in_off[u] + coff;
 	uint8_t* __restrict__ img = slots + (u64)c * LZNT1_SLOT;
+	// the window's match tokens, in order: area 0 is written by the speculative parse of the window's own segment, area 1 by a seam
+	// repair or the cascade (s_rep says which holds). Two areas, because the repairing wave would otherwise race the speculative
+	// wave's global stores to the same words: its progress word in LDS does not wait for them.
+	uint16_t* __restrict__ rec = recs + (u64)c * (LZNT1_REC / sizeof(uint16_t));
 
 #ifdef LZ4_PROFILE
 	unsigned long long z_prev = __builtin_readcyclecounter();
@@ -504,10 +546,8 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		const uint32_t nvec = (((uintptr_t)src & 15u) == 0) ? (n & ~15u) : 0u;
 		for (uint32_t i = tid * 16u; i < nvec; i += 4096u) { *reinterpret_cast<uint4*>(s_data + i) = *reinterpret_cast<const uint4*>(src + i); }
 		for (uint32_t i = nvec + tid; i < n; i += 256u) { s_data[i] = src[i]; }
-		for (uint32_t i = n + tid; i < 4096u + 32u; i += 256u) { s_data[i] = 0; }
+		for (uint32_t i = n + tid; i < 4096u; i += 256u) { s_data[i] = 0; }
 		for (uint32_t i = tid * 8u; i < LZ_TBL; i += 2048u) { *reinterpret_cast<uint4*>(s_cnt + i) = make_uint4(0, 0, 0, 0); }
-		if (tid < LZ4_NSEG) { s_prog[tid] = 0; s_used[tid] = 0; }
-		if (tid == 0) { s_segctr = 0; }
 	}
 	__syncthreads();
 	LZ4_T(0)
@@ -565,24 +605,46 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		}
 	}
 	__syncthreads();
-	const uint16_t* const tbl = s_cnt;
+	// ---- B4. pack the bucket ends (<= 4094) into 12-bit fields in place: thread t reads ends 16 t .. 16 t + 15 (32 bytes at 32 t) and
+	// writes them as 6 dwords at 24 t; the freed top 2 KiB take the control words --------------------------------------------------
+	{
+		const uint4 a = reinterpret_cast<const uint4*>(s_cnt)[2u * tid], b = reinterpret_cast<const uint4*>(s_cnt)[2u * tid + 1u];
+		__syncthreads();
+		const uint32_t e[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };   // two ends each
+		uint32_t* const o = L.t.parse.ends + 6u * tid;
+		#pragma unroll
+		for (int k = 0; k < 2; ++k) {                                          // 8 ends -> 3 dwords
+			const uint32_t* v = e + 4 * k;
+			const uint32_t v0 = v[0] & 0xFFFFu, v1 = v[0] >> 16, v2 = v[1] & 0xFFFFu, v3 = v[1] >> 16;
+			const uint32_t v4 = v[2] & 0xFFFFu, v5 = v[2] >> 16, v6 = v[3] & 0xFFFFu, v7 = v[3] >> 16;
+			o[3 * k]      = v0 | (v1 << 12) | (v2 << 24);
+			o[3 * k + 1u] = (v2 >> 8) | (v3 << 4) | (v4 << 16) | (v5 << 28);
+			o[3 * k + 2u] = (v5 >> 4) | (v6 << 8) | (v7 << 20);
+		}
+		if (tid < LZ4_NSEG) { s_prog[tid] = 0; s_used[tid] = 0; }
+		if (tid < 16u) { reinterpret_cast<uint32_t*>(s_rep)[tid] = 0; }
+		if (tid == 0) { s_segctr = 0; }
+	}
+	__syncthreads();
+	const uint32_t* const tbl = L.t.parse.ends;
 	LZ4_T(1)
 
 	// ---- C1. speculative parse of my segment ------------------------------------------------------------------------
 	const uint32_t nw = (n + 63u) >> 6;
 	const uint32_t w0 = wv * 16u, w1 = (w0 + 16u < nw) ? w0 + 16u : nw;
-	// one window: parse, record. Returns the parse position after it.
-#define LZ4_WINDOW(w_, entry_, cur_out) { \
+	// one window: parse, record (the match tokens into area a_). Returns the parse position after it.
+#define LZ4_WINDOW(w_, entry_, cur_out, a_) { \
 		const uint32_t wb_ = (w_) * 64u; const uint32_t we_ = (wb_ + 64u < n) ? wb_ + 64u : n; \
 		if ((entry_) >= we_) { if (lane == 0) { s_tok[w_] = 0; s_mat[w_] = 0; } cur_out = (entry_); } \
 		else { \
-			LzWin r_; cur_out = lz_window(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); \
+			LzWin r_; cur_out = lz_window<true>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); \
 			if ((r_.matchmask >> lane) & (u64)1) { \
 				const uint32_t p_ = wb_ + lane, best_ = r_.key >> 12; \
-				s_ptok[w_][popc_below(r_.matchmask)] = (uint16_t)(((p_ - (4095u - (r_.key & 0xFFFu)) - 1u) << r_.shift) | (best_ - 3u)); \
+				rec[((a_) * 64u + (w_)) * LZ4_MAXM + popc_below(r_.matchmask)] = (uint16_t)(((p_ - (4095u - (r_.key & 0xFFFu)) - 1u) << r_.shift) | (best_ - 3u)); \
 			} \
 			if (lane == 0) { s_tok[w_] = r_.tokmask; s_mat[w_] = r_.matchmask; } \
-		} }
+		} \
+		if ((a_) && lane == 0) { s_rep[w_] = 1; } }
 	// the segments are handed out in order (with four of them: one per wave)
 	for (;;) {
 		uint32_t seg = 0;
@@ -594,7 +656,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		uint32_t entry = a0 * 64u;                                 // (exact for segment 0)
 		for (uint32_t w = a0; w < a1; ++w) {
 			uint32_t cur;
-			LZ4_WINDOW(w, entry, cur)
+			LZ4_WINDOW(w, entry, cur, 0u)
 			entry = cur;
 			if (lane == 0) { s_endc[w] = (uint16_t)cur; }
 			wave_fence();
@@ -611,7 +673,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 					wave_fence();
 					const uint32_t spec = s_endc[w];
 					uint32_t cur;
-					LZ4_WINDOW(w, entry, cur)
+					LZ4_WINDOW(w, entry, cur, 1u)
 					entry = cur;
 					if (lane == 0) { s_endc[w] = (uint16_t)cur; }
 					if (cur == spec) { break; }
@@ -632,7 +694,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			for (uint32_t w = lz4_seg_start(j); w < nw; ++w) {
 				const uint32_t spec = s_endc[w];
 				uint32_t cur;
-				LZ4_WINDOW(w, e2, cur)
+				LZ4_WINDOW(w, e2, cur, 1u)
 				e2 = cur;
 				if (lane == 0) { s_endc[w] = (uint16_t)cur; }
 				wave_fence();
@@ -644,7 +706,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			wave_fence();
 		}
 	}
-	__syncthreads();                                              // s_cnt is dead from here on: prefixes and flags take its place
+	__syncthreads();                                              // the packed ends are dead from here on: prefixes and flags take their place
 	for (uint32_t i = tid; i < 512u; i += 256u) { s_flagacc[i] = 0; }
 	if (wv == 0) {
 		const u64 tm = lane < nw ? s_tok[lane] : (u64)0, mk = lane < nw ? s_mat[lane] : (u64)0;
@@ -659,8 +721,18 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	const uint32_t csize = ((T + 7u) >> 3) + S;
 	uint32_t total;
 	if (csize < n) {
-		// ---- D1. emission of my segment: pos(t) = 2 (header) + (t div 8 + 1) + sum size(u<t) --------------------------
+		// ---- D1. emission of my windows: pos(t) = 2 (header) + (t div 8 + 1) + sum size(u<t) --------------------------
+		// the match tokens come from global memory (L2-warm: written by this block): the next window's read is issued before this
+		// window's emission, so that two are in flight
+		const auto ptok_of = [&](uint32_t w) -> uint32_t {
+			const u64 matchmask = s_mat[w];
+			return ((matchmask >> lane) & (u64)1) ? (uint32_t)rec[((uint32_t)s_rep[w] * 64u + w) * LZ4_MAXM + popc_below(matchmask)] : 0u;
+		};
+		uint32_t ptk_next = w0 < w1 ? ptok_of(w0) : 0u;
+		#pragma unroll 1
 		for (uint32_t w = w0; w < w1; ++w) {
+			const uint32_t ptk = ptk_next;
+			if (w + 1u < w1) { ptk_next = ptok_of(w + 1u); }
 			const u64 tokmask = s_tok[w];
 			if (tokmask == 0) { continue; }
 			const u64 matchmask = s_mat[w];
@@ -671,7 +743,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			if (is_tok) {
 				if ((t & 7u) == 0) { s_flagpos[t >> 3] = (uint16_t)(pos - 1u); }
 				if (is_m) {
-					const uint32_t tok = s_ptok[w][mbl];
+					const uint32_t tok = ptk;
 					img[pos] = (uint8_t)tok; img[pos + 1u] = (uint8_t)(tok >> 8);
 					atomicOr(&s_flagacc[t >> 3], 1u << (t & 7u));
 				} else { img[pos] = s_data[w * 64u + lane]; }
@@ -695,7 +767,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 
 static int g_lznt1_mode = 0;                                     // 0 = default, 1 = one wave per chunk, 2 = four waves per chunk (tests)
 void set_lznt1_mode(int mode) { g_lznt1_mode = mode; }
-void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size)
+void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs)
 {
 	if (bt.n_chunks == 0) { return; }
 	const int mode = g_lznt1_mode ? g_lznt1_mode : 2;                 // four waves per chunk: 1.43 vs 1.74 ms on the headline workload
@@ -704,8 +776,8 @@ void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables&
 		if (serial) { hipLaunchKernelGGL(lznt1_chunk_kernel<true>, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, slots, slot_size); }
 		else { hipLaunchKernelGGL(lznt1_chunk_kernel<false>, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, slots, slot_size); }
 	} else {
-		if (serial) { hipLaunchKernelGGL(lznt1_chunk4_kernel<true>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, slots, slot_size); }
-		else { hipLaunchKernelGGL(lznt1_chunk4_kernel<false>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, slots, slot_size); }
+		if (serial) { hipLaunchKernelGGL(lznt1_chunk4_kernel<true>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, slots, slot_size, recs); }
+		else { hipLaunchKernelGGL(lznt1_chunk4_kernel<false>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, slots, slot_size, recs); }
 	}
 }
 
