@@ -196,6 +196,29 @@ MSCompStatus mscomp_amd_decompress_batch(mscomp_amd_ctx* ctx, MSCompFormat forma
                                          uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap,
                                          uint64_t* d_out_len, int32_t* d_status);
 
+/* Decompressed-size query: what a decompress plan would report, without decoding. Unit i is d_in + in_off[i], in_len[i] bytes, and
+ * limit[i] (host, n_units entries; limit = NULL means UINT64_MAX for every unit) is the capacity L it is judged at. For every unit
+ *   d_status[i]   the status of ms_decompress(format, unit, in_len[i], out, &cap) with cap = L -- the same status a decompress plan with
+ *                 out_cap[i] = L reports (MSCOMP_OK / MSCOMP_BUF_ERROR / MSCOMP_DATA_ERROR)
+ *   d_out_len[i]  the *out_len of that call on MSCOMP_OK, 0 otherwise (64-bit: an Xpress stream can stand for more than 4 GiB)
+ *   d_need[i]     on MSCOMP_OK the smallest capacity at which that call returns MSCOMP_OK, 0 otherwise. It is d_out_len[i], except for an
+ *                 LZNT1 stream that ends in the End_of_buffer header 00 00 (which ms_compress writes, uncounted, whenever there is room):
+ *                 the decoder reads a header only while output room is left, so such a stream needs d_out_len[i] + 1.
+ * The capacities at which a unit decodes form the interval [need, infinity), with the same output at each. A unit that is MSCOMP_BUF_ERROR
+ * at L is NOT promised to decode at a larger L (an LZNT1 stream cut inside a chunk is BUF_ERROR at every capacity; some damaged streams
+ * are BUF_ERROR at small capacities and DATA_ERROR at large ones). d_out_len / d_need (uint64) and d_status (int32) are device arrays.
+ * Argument checks are those of mscomp_amd_plan_create_decompress (MSCOMP_ARG_ERROR for a bad format, null arrays, an in_len above
+ * 0xFFFFF000). Scratch and host work scale with the input bytes and the number of units, never with the limits. A size plan is executed
+ * only with mscomp_amd_plan_execute_size (asynchronous on the ctx stream, allocates nothing, does not synchronize), and that function takes
+ * nothing else: either one given the other kind of plan returns MSCOMP_ARG_ERROR. mscomp_amd_plan_destroy frees both kinds.
+ * mscomp_amd_decompressed_size_batch = create + execute + stream-synchronize + destroy. */
+MSCompStatus mscomp_amd_plan_create_size(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units,
+                                         const uint64_t* in_off, const uint64_t* in_len, const uint64_t* limit, mscomp_amd_plan** plan);
+MSCompStatus mscomp_amd_plan_execute_size(mscomp_amd_plan* plan, const uint8_t* d_in, uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status);
+MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units, const uint8_t* d_in,
+                                                const uint64_t* in_off, const uint64_t* in_len, const uint64_t* limit,
+                                                uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status);
+
 /* Batch helpers.
  * Capacity planning: out_cap[i] = what one ms_compress call needs at most for in_len[i] bytes (ms_max_compressed_size, + 2 for the LZNT1
  * End_of_buffer), out_off[i] = running offset rounded up to `align`; returns the total size of the output buffer ((uint64_t)-1: bad format).

@@ -34,6 +34,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "xpress_deflate_init", "xpress_deflate", "xpress_deflate_end", "xpress_inflate_init", "xpress_inflate", "xpress_inflate_end",
     "ms_decompress", "lznt1_decompress", "xpress_decompress", "xpress_huff_decompress", "mscomp_amd_plan_create_decompress", "mscomp_amd_decompress_batch",
     "mscomp_amd_version", "mscomp_amd_debug_xpress_matches", "mscomp_amd_debug_huff_lengths", "mscomp_amd_debug_lds_lane_order", "mscomp_amd_debug_set_xpress_emit", "mscomp_amd_debug_set_lznt1", "mscomp_amd_debug_set_serial_atomics", "mscomp_amd_compress_units_host", "mscomp_amd_decompress_units_host", "mscomp_amd_host_pool_release", "mscomp_amd_debug_set_finder", "mscomp_amd_debug_set_one_shot", "mscomp_amd_debug_set_xpress_decoder", "mscomp_amd_debug_lzg_open", "mscomp_amd_set_lznt1_sa_dict", "mscomp_amd_get_lznt1_sa_dict", "mscomp_amd_ctx_set_lznt1_sa_dict", "mscomp_amd_debug_hooks_enabled", "mscomp_amd_debug_lzd_walked",
+    "mscomp_amd_plan_create_size", "mscomp_amd_plan_execute_size", "mscomp_amd_decompressed_size_batch",
 ]
 
 
@@ -95,6 +96,13 @@ def load_library():
     lib.mscomp_amd_plan_create_decompress.restype = C.c_int
     lib.mscomp_amd_decompress_batch.argtypes = lib.mscomp_amd_compress_batch.argtypes
     lib.mscomp_amd_decompress_batch.restype = C.c_int
+    lib.mscomp_amd_plan_create_size.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_plan_create_size.restype = C.c_int
+    lib.mscomp_amd_plan_execute_size.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mscomp_amd_plan_execute_size.restype = C.c_int
+    lib.mscomp_amd_decompressed_size_batch.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mscomp_amd_decompressed_size_batch.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -265,6 +273,96 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+class SizePlan:
+    """A decompressed-size plan (mscomp_amd_plan_create_size): for every unit the status and length a decompress plan with
+    out_cap = limit would report, and the smallest capacity that decodes (``need``). ``limit`` None = no limit (2^64 - 1)."""
+
+    def __init__(self, ctx, fmt, in_off, in_len, limit=None):
+        self.ctx, self.fmt = ctx, int(fmt)
+        self.in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        self.in_len = np.ascontiguousarray(in_len, dtype=np.uint64)
+        assert self.in_off.ndim == 1 and self.in_off.shape == self.in_len.shape
+        self.limit = None if limit is None else np.ascontiguousarray(limit, dtype=np.uint64)
+        assert self.limit is None or self.limit.shape == self.in_off.shape
+        self.n_units = len(self.in_off)
+        self._h = C.c_void_p()
+        st = ctx.lib.mscomp_amd_plan_create_size(ctx._h, self.fmt, self.n_units, self.in_off.ctypes.data, self.in_len.ctypes.data,
+                                                 None if self.limit is None else self.limit.ctypes.data, C.byref(self._h))
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_plan_create_size")
+
+    def execute(self, d_in, d_out_len, d_need, d_status):
+        """Enqueue on the ctx stream. Arguments are torch CUDA tensors (uint8, int64/uint64[n], int64/uint64[n], int32[n])."""
+        st = self.ctx.lib.mscomp_amd_plan_execute_size(self._h, C.c_void_p(d_in.data_ptr()), C.c_void_p(d_out_len.data_ptr()),
+                                                       C.c_void_p(d_need.data_ptr()), C.c_void_p(d_status.data_ptr()))
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_plan_execute_size")
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.mscomp_amd_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _upload_units(units, dev):
+    import torch
+    lens = [len(u) for u in units]
+    in_off, in_total = pack_offsets(lens)
+    blob = np.zeros(in_total + 16, dtype=np.uint8)
+    for u, o in zip(units, in_off):
+        if len(u):
+            blob[int(o): int(o) + len(u)] = np.frombuffer(bytes(u), dtype=np.uint8)
+    return torch.from_numpy(blob).to(dev), in_off, lens
+
+
+def decompressed_sizes(fmt, units, limits=None, ctx=None):
+    """Size a list of independent compressed buffers on the GPU without decoding them. ``limits`` (optional, one per unit; default
+    no limit) is the capacity each is judged at. Returns numpy arrays (out_lens uint64, needs uint64, statuses int32): the status and
+    length ms_decompress would return with *out_len = limit, and the smallest capacity that decodes (0 where the status is not OK)."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    n = len(units)
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        d_in, in_off, lens = _upload_units(units, dev)
+        d_len = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
+        d_need = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        plan = SizePlan(ctx, fmt, in_off, lens, limits)
+        plan.execute(d_in, d_len, d_need, d_st)
+        ctx.stream.synchronize()
+        out = (d_len.cpu().numpy().view(np.uint64)[:n].copy(), d_need.cpu().numpy().view(np.uint64)[:n].copy(), d_st.cpu().numpy()[:n].copy())
+        plan.close()
+    if own:
+        ctx.close()
+    return out
+
+
+def decompress_units_auto(fmt, units, limits=None, ctx=None):
+    """Decompress a list of compressed buffers whose sizes are not known: sizes them first (decompressed_sizes, at ``limits``), then
+    decodes with capacity ``need`` for every unit, outputs back to back. Returns what decompress_units returns; a unit that is not
+    MSCOMP_OK at its limit gets None and its status from the size pass."""
+    own = ctx is None
+    ctx = ctx or Context()
+    _, need, st = decompressed_sizes(fmt, units, limits, ctx=ctx)
+    ok = [i for i in range(len(units)) if st[i] == MSCOMP_OK]
+    res, status = [None] * len(units), [int(x) for x in st]
+    if ok:
+        got, gst = decompress_units(fmt, [units[i] for i in ok], [int(need[i]) for i in ok], ctx=ctx)
+        for i, g, s in zip(ok, got, gst):
+            res[i], status[i] = g, s
+    if own:
+        ctx.close()
+    return res, status
 
 
 def compact_batch(ctx, out_off, out_cap, d_out, d_out_len):

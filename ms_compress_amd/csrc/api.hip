@@ -89,6 +89,7 @@ struct mscomp_amd_plan {
 	mscomp_amd_ctx* ctx = nullptr;
 	MSCompFormat format = MSCOMP_NONE;
 	bool decompress = false;
+	bool sizing = false;                               // a decompressed-size plan (mscomp_amd_plan_create_size): out_cap holds the limits, nothing is decoded
 	uint32_t n_units = 0, n_chunks = 0;
 	uint64_t total_in = 0, max_unit = 0;
 	bool lznt1_sa = false;                             // LZNT1: the suffix-array dictionary flavour -- fixed when the plan is created: a plan never changes its bytes under a running caller
@@ -262,7 +263,7 @@ int mscomp_amd_profile_read(mscomp_amd_ctx* c, const char** names, double* ms, u
 
 static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, bool decompress, size_t n_units,
                                      const uint64_t* in_off, const uint64_t* in_len,
-                                     const uint64_t* out_off, const uint64_t* out_cap, mscomp_amd_plan** out)
+                                     const uint64_t* out_off, const uint64_t* out_cap, mscomp_amd_plan** out, bool sizing = false)
 {
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
@@ -272,7 +273,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	mscomp_amd_plan* p = new (std::nothrow) mscomp_amd_plan();
 	if (!p) { return MSCOMP_MEM_ERROR; }
-	p->ctx = c; p->format = format; p->decompress = decompress; p->n_units = (uint32_t)n_units;
+	p->ctx = c; p->format = format; p->decompress = decompress; p->sizing = sizing; p->n_units = (uint32_t)n_units;
 	p->lznt1_sa = !decompress && format == MSCOMP_LZNT1 && lznt1_sa_for(c);
 
 	const size_t host_words = n_units * 4 + (n_units + 2) / 2 + 1;
@@ -333,16 +334,16 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 			for (size_t i = 0; i < n_units; ++i) {
 				tp[i] = slots; tp[n_units + 1 + i] = cands; tp[2 * (n_units + 1) + i] = scr;
 				const uint64_t by_in = 8 * in_len[i] + out_cap[i] / 32766u + 1, cnt = out_cap[i] < by_in ? out_cap[i] : by_in;
-				slots += cnt + 64;
+				if (!sizing) { slots += cnt + 64; }                        // (a size plan writes no tokens)
 				// candidate chunk starts: a chunk gives 65536 bytes and takes at least 260; a quarter more for windows that only look like a table
 				const uint64_t by_out = out_cap[i] / 65536u + 2, by_len = in_len[i] / 260u + 1, most = by_out < by_len ? by_out : by_len;
 				cands += most + most / 4 + 2;
-				if (out_cap[i] > 65536u) { scr += most + most / 4 + 2; }   // a buffer of several chunks: its candidates keep their tokens (no second walk)
+				if (out_cap[i] > 65536u && !sizing) { scr += most + most / 4 + 2; }   // a buffer of several chunks: its candidates keep their tokens (no second walk)
 			}
 			tp[n_units] = slots; tp[2 * n_units + 1] = cands; tp[3 * n_units + 2] = scr;
 			if (cands > 0x7FFFFFF0u) { p->tables.release(); delete p; return MSCOMP_ARG_ERROR; }
 			p->xhc_slots = (uint32_t)cands;
-			okd = p->tokpre.reserve(tp.size() * 8) && c->dz_tok.reserve(slots * 4 + 256) && c->dz_ntok.reserve((n_units + 1) * 8) &&
+			okd = p->tokpre.reserve(tp.size() * 8) && (sizing || c->dz_tok.reserve(slots * 4 + 256)) && c->dz_ntok.reserve((n_units + 1) * 8) &&
 			      c->dz_xhc.reserve(((size_t)n_units + 1) * 8 + (size_t)cands * (4 * 4 + 3 * 8) + 64);
 			{	// ... if that scratch is affordable: at most MSCOMP_AMD_XHC_SCR_MAX_MB (default 32 GiB; 0 = always walk twice) and at most half of
 				// what the device has free right now; a reservation that fails anyway switches the path off (the second walk needs no scratch)
@@ -354,7 +355,8 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 			if (okd && (hipMemcpyAsync(p->tokpre.p, tp.data(), tp.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
 			            hipStreamSynchronize(c->stream) != hipSuccess)) { p->tokpre.release(); p->tables.release(); delete p; return MSCOMP_ERRNO; }
 		}
-		if (okd && format == MSCOMP_XPRESS) {
+		if (okd && format == MSCOMP_XPRESS && sizing) { okd = c->dz_ntok.reserve((n_units + 1) * 8); }   // (token counts of the segment verdict)
+		if (okd && format == MSCOMP_XPRESS && !sizing) {
 			// a token takes at least one input byte and gives at least one output byte; a match one more token per 32766 bytes
 			std::vector<uint64_t> tp(n_units + 1);
 			uint64_t slots = 0;
@@ -368,7 +370,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 			if (okd && (hipMemcpyAsync(p->tokpre.p, tp.data(), tp.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
 			            hipStreamSynchronize(c->stream) != hipSuccess)) { p->tokpre.release(); p->tables.release(); delete p; return MSCOMP_ERRNO; }
 		}
-		if (okd && (format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF)) {
+		if (okd && !sizing && (format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF)) {
 			// units with room for LZG_MIN_CAP bytes or more get their bytes from all CUs (lzglobal.hip): 4 bytes of scratch per byte of capacity;
 			// when that is more than the budget (MSCOMP_AMD_LZG_MAX_MB, default 64 GiB of the 288; 0 switches the path off) the block-per-unit kernel takes them
 			static const uint64_t budget_env = [] { const char* e = getenv("MSCOMP_AMD_LZG_MAX_MB"); const long long v = e ? atoll(e) : 65536; return (uint64_t)(v < 0 ? 0 : v) << 20; }();
@@ -659,7 +661,7 @@ static MSCompStatus plan_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t
 
 MSCompStatus mscomp_amd_plan_execute(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
 {
-	if (!p || (p->n_units && (!d_out_len || !d_status)) || (p->total_in && !d_in)) { return MSCOMP_ARG_ERROR; }
+	if (!p || p->sizing || (p->n_units && (!d_out_len || !d_status)) || (p->total_in && !d_in)) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_ctx* c = p->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
@@ -716,6 +718,102 @@ MSCompStatus mscomp_amd_decompress_batch(mscomp_amd_ctx* c, MSCompFormat format,
 	MSCompStatus s = mscomp_amd_plan_create_decompress(c, format, n_units, in_off, in_len, out_off, out_cap, &p);
 	if (s != MSCOMP_OK) { return s; }
 	s = mscomp_amd_plan_execute(p, d_in, d_out, d_out_len, d_status);
+	DeviceGuard g(c->device);
+	if (hipStreamSynchronize(c->stream) != hipSuccess && s == MSCOMP_OK) { s = MSCOMP_ERRNO; }
+	mscomp_amd_plan_destroy(p);
+	return s;
+}
+
+// ---- decompressed-size query (include/mscomp_amd.h): the decoders' walks without the byte stage and without token stores ----
+// A size plan is a decompress plan whose out_cap table holds the limits and whose out_off table is zero: the kernels test against out_cap as
+// the decoders do, and none of them writes output. Scratch follows the input: no token slots, no lzglobal words, no candidate token scratch.
+MSCompStatus mscomp_amd_plan_create_size(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, const uint64_t* in_off, const uint64_t* in_len,
+                                         const uint64_t* limit, mscomp_amd_plan** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || (n_units && (!in_off || !in_len)) || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	std::vector<uint64_t> zero(n_units, 0), lim;
+	if (!limit) { lim.assign(n_units, ~(uint64_t)0); limit = lim.data(); }
+	return plan_create_impl(c, format, true, n_units, in_off, in_len, zero.data(), limit, out, true);
+}
+
+static void size_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status)
+{
+	mscomp_amd_ctx* c = p->ctx;
+	hipStream_t st = c->stream;
+	switch (p->format) {
+	case MSCOMP_LZNT1: {                                   // the header chain as in plan_launch, then every chunk sized, then the verdict at the limit
+		LzdBufs b;
+		b.cin = static_cast<uint32_t*>(c->dz_cin.p); b.csize = static_cast<uint16_t*>(c->dz_csize.p);
+		const size_t nk = (size_t)p->n_chunks * LZD_K;
+		b.segL = static_cast<uint32_t*>(c->dz_unit.p); b.segE = b.segL + nk; b.segcnt = b.segE + nk; b.segstop = b.segcnt + nk; b.segoff = b.segstop + nk;
+		b.selcnt = b.segoff + nk; b.seloff = b.selcnt + p->n_chunks;
+		b.stop = b.seloff + p->n_chunks; b.irregular = b.stop + p->n_units + 1u;
+		b.flat = static_cast<u64*>(c->prefix.p);
+		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b); }
+		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
+		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
+		{ KernelTimer t(c, "lzd_size_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, nullptr, 2); }
+		{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status, d_need); }
+		return;
+	}
+	case MSCOMP_XPRESS: {
+		u64* ntok = static_cast<u64*>(c->dz_ntok.p);
+		XpsTables x = {};
+		if (p->xps_big) {
+			const size_t nb = p->xps_big, upad = (nb + 1) / 2;
+			const uint64_t* t = static_cast<const uint64_t*>(p->xps_tab.p);
+			x.unit = reinterpret_cast<const uint32_t*>(t); x.seg_prefix = t + upad; x.n_big = p->xps_big; x.n_seg = p->xps_seg; x.seg_bytes = p->xps_seg_bytes; x.warm_bytes = p->xps_warm_bytes;
+			x.seg = c->xps_buf.p; x.mode = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->xps_buf.p) + (size_t)p->xps_seg * XPS_SEG_BYTES); x.done = x.mode + nb;
+			{ KernelTimer t2(c, "xps_walk_kernel"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, -1, x); }
+			for (uint32_t r = 0; r < XPS_ROUNDS; ++r) { KernelTimer t2(c, "xps_redo_kernels"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, -2, x); }
+			{ KernelTimer t2(c, "xps_size_kernel"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, -3, x); }
+		}
+		{ KernelTimer t(c, "xpt_size_kernel"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, 0, x); }
+		break;
+	}
+	default: {                                             // MSCOMP_XPRESS_HUFF
+		const u64* cp = static_cast<const u64*>(p->tokpre.p) + (p->n_units + 1u);
+		u64* ntok = static_cast<u64*>(c->dz_ntok.p);
+		XhcBufs xb = {};
+		{
+			const size_t nu = (size_t)p->n_units + 1, ns = p->xhc_slots;
+			uint8_t* q = static_cast<uint8_t*>(c->dz_xhc.p);
+			xb.res_prod = reinterpret_cast<u64*>(q); q += ns * 8; xb.res_ntok = reinterpret_cast<u64*>(q); q += ns * 8; xb.tok_off = reinterpret_cast<u64*>(q); q += ns * 8;
+			xb.cand_pos = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_end = reinterpret_cast<uint32_t*>(q); q += ns * 4;
+			xb.res_reach = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_state = reinterpret_cast<uint32_t*>(q); q += ns * 4;
+			xb.cand_cnt = reinterpret_cast<uint32_t*>(q); q += nu * 4; xb.mode = reinterpret_cast<uint32_t*>(q);
+		}
+		static const char* const names[4] = { "xhc_mark_kernel", "xhc_size_kernel", "xhc_chain_kernel", "xhd_size_kernel" };
+		for (int ph = 0; ph < 4; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_huff_size(st, d_in, p->bt, ntok, cp, p->xhc_slots, xb, d_out_len, d_status, ph); }
+		break;
+	}
+	}
+	// Xpress / Xpress+Huffman: the smallest capacity that decodes is the length itself (every length test is "does it fit"), and d_out_len is 0
+	// for a unit that is not MSCOMP_OK
+	(void)hipMemcpyAsync(d_need, d_out_len, (size_t)p->n_units * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
+}
+
+MSCompStatus mscomp_amd_plan_execute_size(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status)
+{
+	if (!p || !p->sizing || (p->n_units && (!d_out_len || !d_need || !d_status)) || (p->total_in && !d_in)) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = p->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (p->n_units) { size_launch(p, d_in, d_out_len, d_need, d_status); }
+	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
+}
+
+MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, const uint8_t* d_in,
+                                                const uint64_t* in_off, const uint64_t* in_len, const uint64_t* limit,
+                                                uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status)
+{
+	mscomp_amd_plan* p = nullptr;
+	MSCompStatus s = mscomp_amd_plan_create_size(c, format, n_units, in_off, in_len, limit, &p);
+	if (s != MSCOMP_OK) { return s; }
+	s = mscomp_amd_plan_execute_size(p, d_in, d_out_len, d_need, d_status);
 	DeviceGuard g(c->device);
 	if (hipStreamSynchronize(c->stream) != hipSuccess && s == MSCOMP_OK) { s = MSCOMP_ERRNO; }
 	mscomp_amd_plan_destroy(p);

@@ -7,6 +7,8 @@
 //                   speculatively and walked in parallel, one wave per chunk, writing 32-bit tokens              [comments at the kernels]
 //                   xhd_parse_kernel      the serial walk of a whole buffer, for what the speculation cannot do
 //                   lz_copy_kernel        tokens -> bytes, 64 at a time (sources chased with ds_bpermute / LDS / HBM)
+// Size query (mscomp_amd_plan_create_size): the same walks with every test and without the byte stage or any token store --
+//   lzd_chunk_kernel<false, true> (token phase only), xpt_parse_kernel<false> / xps_emit_kernel<false>, xhc_parse_kernel<3> / xhd_parse_kernel<false>.
 // Per unit, status and length are what the reference's one-shot call returns (MSCOMP_OK / MSCOMP_BUF_ERROR / MSCOMP_DATA_ERROR); the
 // oracle restates those semantics (oracle/mscomp_oracle.c) and tests/test_gpu_decompress.py compares both with the compiled reference.
 //
@@ -278,7 +280,9 @@ struct LzdLds {
 	uint16_t gs[464];                                  // start (data offset) of every flag group
 };
 
-// size (<= 4096) or LZD_ERR. The decoded bytes are left in L.out.
+// size (<= 4096) or LZD_ERR. BYTES: the decoded bytes are left in L.out; without it only the token phase runs (every test of the
+// chunk is made there: the byte stage cannot fail), for the size query.
+template <bool BYTES = true>
 __device__ __forceinline__ uint32_t lzd_decode_chunk(LzdLds& L, const uint8_t* __restrict__ src, uint32_t in_size, uint32_t lane)
 {
 	// ---- load: 16-byte words that hold at least one byte of the chunk ----
@@ -332,7 +336,7 @@ __device__ __forceinline__ uint32_t lzd_decode_chunk(LzdLds& L, const uint8_t* _
 		const uint32_t off = (raw >> sh) + 1u;
 		if (valid && (is_match ? (off > pos || pos + len > 4096u) : pos >= 4096u)) { err = 1; }   // :104-105; a literal beyond the chunk is our DATA_ERROR
 		if (__ballot(err)) { return LZD_ERR; }
-		if (valid) {
+		if (BYTES && valid) {
 			L.out[pos] = (uint8_t)(is_match ? off - 1u : raw);
 			atomicOr(reinterpret_cast<uint32_t*>(L.bm) + (pos >> 5), 1u << (pos & 31u));
 			if (is_match) { L.out[pos + 1u] = (uint8_t)((off - 1u) >> 8); atomicOr(reinterpret_cast<uint32_t*>(L.mb) + (pos >> 5), 1u << (pos & 31u)); }
@@ -341,6 +345,7 @@ __device__ __forceinline__ uint32_t lzd_decode_chunk(LzdLds& L, const uint8_t* _
 		sh = (uint32_t)__builtin_amdgcn_readlane((int)sh, 63);
 	}
 	const uint32_t total = base_pos;
+	if (!BYTES) { return total; }
 	__syncthreads();
 	// ---- bytes, 64 at a time: every byte finds its token and its source; sources inside the row are chased with bpermute ----
 	uint32_t carry = 0, carry_off = 0; bool carry_match = false;         // the token running when a row begins
@@ -404,8 +409,10 @@ __device__ __forceinline__ uint32_t seg_of_flat(const u64* __restrict__ prefix, 
 
 // EXACT = false: every chunk, written where it lands if all earlier chunks hold 4096 bytes; records the size.
 // EXACT = true: only units flagged irregular; chunks whose place differs are decoded again to the exact place.
+// SIZE (with EXACT = false): every chunk is only sized -- the token phase of a compressed chunk, the header of a stored one -- and nothing is written
+// but csize.
 // Chunks are numbered through the batch in stream order (flat[g] = number of the first chunk of segment g).
-template <bool EXACT>
+template <bool EXACT, bool SIZE = false>
 __global__ __launch_bounds__(64) void lzd_chunk_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, const uint32_t* __restrict__ cin,
                                                       const uint32_t* __restrict__ seloff, const u64* __restrict__ flat, uint16_t* __restrict__ csize,
                                                       const uint32_t* __restrict__ irregular, uint8_t* __restrict__ d_out)
@@ -434,15 +441,15 @@ __global__ __launch_bounds__(64) void lzd_chunk_kernel(const uint8_t* __restrict
 		const uint32_t in_size = (hdr & 0xFFFu) + 3u;
 		uint32_t size;
 		if (hdr & 0x8000u) {
-			size = lzd_decode_chunk(L, src, in_size, lane);
+			size = lzd_decode_chunk<!SIZE>(L, src, in_size, lane);
 		} else {                                                         // stored chunk (:192-209)
 			size = in_size - 2u;
-			for (uint32_t i = lane; i < size; i += 64u) { L.out[i] = src[2u + i]; }
+			for (uint32_t i = lane; !SIZE && i < size; i += 64u) { L.out[i] = src[2u + i]; }
 			__syncthreads();
 		}
 		if (!EXACT && lane == 0) { csize[c] = (uint16_t)size; }
 		const u64 cap = bt.out_cap[u];
-		if (size != LZD_ERR && pos < cap) {
+		if (!SIZE && size != LZD_ERR && pos < cap) {
 			const u64 room = cap - pos;
 			lzd_store(d_out + bt.out_off[u] + pos, L.out, room < size ? (uint32_t)room : size, lane);
 		}
@@ -453,9 +460,11 @@ __global__ __launch_bounds__(64) void lzd_chunk_kernel(const uint8_t* __restrict
 // ===================================================================================================================
 // (3) per unit: positions, status, out_len
 // ===================================================================================================================
+// d_need (size query, else null): the smallest capacity at which the unit decodes, on MSCOMP_OK -- one more than its length when the walk
+// ended at the End_of_buffer header 00 00, which is only read while output room is left (:252)
 __global__ __launch_bounds__(256) void lzd_finalize_kernel(BatchTables bt, const u64* __restrict__ flat, const uint32_t* __restrict__ stop,
                                                           const uint16_t* __restrict__ csize, uint32_t* __restrict__ irregular,
-                                                          u64* __restrict__ d_out_len, int32_t* __restrict__ d_status)
+                                                          u64* __restrict__ d_out_len, int32_t* __restrict__ d_status, u64* __restrict__ d_need)
 {
 	__shared__ uint32_t s_wsum[4], s_wev[4], s_wirr[4];
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6, u = blockIdx.x;
@@ -515,6 +524,7 @@ __global__ __launch_bounds__(256) void lzd_finalize_kernel(BatchTables bt, const
 	if (tid == 0) {
 		const bool any = s_wirr[0] | s_wirr[1] | s_wirr[2] | s_wirr[3];
 		d_status[u] = status; d_out_len[u] = status == 0 ? pos : 0;
+		if (d_need) { d_need[u] = status == 0 ? pos + (kind == LZD_ZERO_OK ? 1u : 0u) : 0; }
 		irregular[u] = any ? 1u : 0u;
 		if (any) { atomicOr(&irregular[bt.n_units], 1u); }
 	}
@@ -540,13 +550,14 @@ void launch_lzd_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& b
 	if (bt.n_units == 0) { return; }
 	const u64 est = (u64)bt.n_chunks * (LZD_SEG / 2048u);            // the count lives on the device; typical chunks are 2-4 KiB
 	const uint32_t grid = est < 16384u ? (uint32_t)est : 16384u;
-	if (exact) { hipLaunchKernelGGL(lzd_chunk_kernel<true>, dim3(grid), dim3(64), 0, st, d_in, bt, b.cin, b.seloff, b.flat, b.csize, b.irregular, d_out); }
-	else       { hipLaunchKernelGGL(lzd_chunk_kernel<false>, dim3(grid), dim3(64), 0, st, d_in, bt, b.cin, b.seloff, b.flat, b.csize, b.irregular, d_out); }
+	if (exact == 2)  { hipLaunchKernelGGL((lzd_chunk_kernel<false, true>), dim3(grid), dim3(64), 0, st, d_in, bt, b.cin, b.seloff, b.flat, b.csize, b.irregular, d_out); }
+	else if (exact)  { hipLaunchKernelGGL(lzd_chunk_kernel<true>, dim3(grid), dim3(64), 0, st, d_in, bt, b.cin, b.seloff, b.flat, b.csize, b.irregular, d_out); }
+	else             { hipLaunchKernelGGL(lzd_chunk_kernel<false>, dim3(grid), dim3(64), 0, st, d_in, bt, b.cin, b.seloff, b.flat, b.csize, b.irregular, d_out); }
 }
-void launch_lzd_finalize(hipStream_t st, const BatchTables& bt, const LzdBufs& b, u64* d_out_len, int32_t* d_status)
+void launch_lzd_finalize(hipStream_t st, const BatchTables& bt, const LzdBufs& b, u64* d_out_len, int32_t* d_status, u64* d_need)
 {
 	if (bt.n_units == 0) { return; }
-	hipLaunchKernelGGL(lzd_finalize_kernel, dim3(bt.n_units), dim3(256), 0, st, bt, b.flat, b.stop, b.csize, b.irregular, d_out_len, d_status);
+	hipLaunchKernelGGL(lzd_finalize_kernel, dim3(bt.n_units), dim3(256), 0, st, bt, b.flat, b.stop, b.csize, b.irregular, d_out_len, d_status, d_need);
 }
 
 // ===================================================================================================================
@@ -733,10 +744,11 @@ void launch_xpress_decompress(hipStream_t st, const uint8_t* d_in, const BatchTa
 // are made against the output offset `op` and the capacity; without it the walk only counts (tokens, bytes) -- for a stretch of a stream whose
 // place in the output is not known yet (xps_* below). It ends in front of the first flag word at or behind `limit` (running = true) or where
 // the reference's loop ends (status). Offsets are relative to the 16-byte aligned base `ab`, as in xpd_kernel.
+// CHECK (defaults to EMIT): the offset test of :442 against the absolute `op`. CHECK without EMIT is the size query's walk: every test, no store.
 struct XptWalk { uint32_t ip; u64 op, tc; uint32_t half, hp; bool have_half; int32_t status; bool running; };
 #define XPT_BLOCK() { __syncthreads(); *reinterpret_cast<uint4*>(s_in + (loaded & 1u) * XPT_INB + lane * 16u) = nxt; ++loaded; \
 	{ const u64 q_ = (u64)loaded * XPT_INB + lane * 16u; nxt = q_ < endq ? *reinterpret_cast<const uint4*>(ab + q_) : make_uint4(0, 0, 0, 0); } __syncthreads(); }
-template <bool EMIT>
+template <bool EMIT, bool CHECK = EMIT>
 __device__ __forceinline__ void xpt_walk(uint8_t* s_in, const uint8_t* __restrict__ ab, const uint32_t endq, uint32_t& loaded, uint4& nxt, XptWalk& W,
                                          const uint32_t limit, const u64 cap, uint32_t* __restrict__ mytok, const uint32_t lane)
 {
@@ -796,7 +808,7 @@ __device__ __forceinline__ void xpt_walk(uint8_t* s_in, const uint8_t* __restric
 			const uint32_t len = is_m ? (lng ? (e1 ? extb + 25u : nib + 10u) : (sym & 7u) + 3u) : 1u, off = (sym >> 3) + 1u;
 			const uint32_t l = plain ? len : 0u, incl = wave_incl_scan_add_u32(l);
 			const u64 opi = op + (incl - l);
-			const bool bad_off = EMIT && plain && is_m && (u64)off > opi;                                   // :442
+			const bool bad_off = CHECK && plain && is_m && (u64)off > opi;                                   // :442
 			const bool bad_cap = plain && (is_m ? (u64)len > cap - opi : opi >= cap);               // :443 / :455
 			const u64 eb = __ballot(bad_off || bad_cap);
 			if (eb) {
@@ -844,7 +856,7 @@ __device__ __forceinline__ void xpt_walk(uint8_t* s_in, const uint8_t* __restric
 				ll += 0xFu;
 			}
 			ll += 0x7u + 0x3u;
-			if (EMIT && (u64)loff > op) { status = -3; done = true; break; }     // :442
+			if (CHECK && (u64)loff > op) { status = -3; done = true; break; }    // :442
 			if ((u64)ll > cap - op) { status = -5; done = true; break; } // :443
 			const uint32_t np = ll / LZT_MAXLEN + (ll % LZT_MAXLEN ? 1u : 0u);    // pieces with the same offset copy the same bytes
 			for (uint32_t k = lane; EMIT && k < np; k += 64u) { mytok[tc + k] = ((k + 1u == np ? ll - (np - 1u) * LZT_MAXLEN : LZT_MAXLEN) << 16) | loff; }
@@ -858,6 +870,8 @@ __device__ __forceinline__ void xpt_walk(uint8_t* s_in, const uint8_t* __restric
 // ring start for a walk that begins at offset ip0 (from the aligned base): blocks ip0 / 1024 and the next one resident, the third on its way
 #define XPT_RING_START(ip0) { loaded = (ip0) / XPT_INB; { const u64 q_ = (u64)loaded * XPT_INB + lane * 16u; nxt = q_ < endq ? *reinterpret_cast<const uint4*>(ab + q_) : make_uint4(0, 0, 0, 0); } XPT_BLOCK() XPT_BLOCK() }
 
+// EMIT = false: the size query (tok / tok_prefix unused)
+template <bool EMIT = true>
 __global__ __launch_bounds__(64) void xpt_parse_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, const u64* __restrict__ tok_prefix, uint32_t* __restrict__ tok,
                                                       u64* __restrict__ ntok, u64* __restrict__ d_out_len, int32_t* __restrict__ d_status, const uint32_t* __restrict__ spec_done)
 {
@@ -867,7 +881,7 @@ __global__ __launch_bounds__(64) void xpt_parse_kernel(const uint8_t* __restrict
 	const uint32_t n = (uint32_t)bt.in_len[u];
 	const u64 cap = bt.out_cap[u];
 	const uint8_t* src = d_in + bt.in_off[u];
-	uint32_t* __restrict__ mytok = tok + tok_prefix[u];
+	uint32_t* __restrict__ mytok = EMIT ? tok + tok_prefix[u] : nullptr;
 	if (n < 5u) {                                                        // :414-418
 		bool ok = n == 0;
 		if (n == 4u) { ok = ((uint32_t)src[0] | ((uint32_t)src[1] << 8) | ((uint32_t)src[2] << 16) | ((uint32_t)src[3] << 24)) != 0xFFFFFFFFu; }
@@ -881,7 +895,7 @@ __global__ __launch_bounds__(64) void xpt_parse_kernel(const uint8_t* __restrict
 	uint32_t loaded; uint4 nxt;
 	XPT_RING_START(a0)
 	XptWalk W = { a0, 0, 0, 0, 0, false, -3, false };
-	xpt_walk<true>(s_in, ab, endq, loaded, nxt, W, 0xFFFFFFFFu, cap, mytok, lane);
+	xpt_walk<EMIT, true>(s_in, ab, endq, loaded, nxt, W, 0xFFFFFFFFu, cap, mytok, lane);
 	if (lane == 0) { d_status[u] = W.status; d_out_len[u] = W.status == 0 ? W.op : 0; ntok[u] = W.status == 0 ? W.tc : 0; }
 }
 
@@ -1022,6 +1036,8 @@ __global__ __launch_bounds__(256) void xps_check_kernel(BatchTables bt, XpsTable
 	}
 }
 
+// EMIT = false: the size query -- the same walk and tests, no token written (tok / tok_prefix unused)
+template <bool EMIT = true>
 __global__ __launch_bounds__(64) void xps_emit_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, XpsTables x, const u64* __restrict__ tok_prefix, uint32_t* __restrict__ tok)
 {
 	__shared__ __attribute__((aligned(16))) uint8_t s_in[2u * XPT_INB];
@@ -1042,7 +1058,7 @@ __global__ __launch_bounds__(64) void xps_emit_kernel(const uint8_t* __restrict_
 	XptWalk W = { seg[k].l_ip, seg[k].obase, seg[k].tbase, 0, 0, false, -3, false };
 	if (seg[k].l_hp != 0xFFFFFFFFu) { W.have_half = true; W.hp = seg[k].l_hp; W.half = ab[W.hp]; }
 	XPT_RING_START(W.ip)
-	xpt_walk<true>(s_in, ab, endq, loaded, nxt, W, lim, bt.out_cap[u], tok + tok_prefix[u], lane);
+	xpt_walk<EMIT, true>(s_in, ab, endq, loaded, nxt, W, lim, bt.out_cap[u], EMIT ? tok + tok_prefix[u] : nullptr, lane);
 	// the same walk as the one that was counted, now with the tests that need the output offset: anything else than the counted end is a failed test
 	// (... including the pending length nibble the walk leaves with: it seeds the next segment's walk, and a record rewritten by a later round while
 	// this segment was read could agree on everything else)
@@ -1074,7 +1090,9 @@ struct XhdLds {
 	uint32_t lims[16], poss[16];
 };
 
-// tokens of unit u: tok[tok_prefix[u] ...], ntok[u]; d_out_len / d_status as the caller sees them (the bytes follow in lz_copy_kernel)
+// tokens of unit u: tok[tok_prefix[u] ...], ntok[u]; d_out_len / d_status as the caller sees them (the bytes follow in lz_copy_kernel).
+// EMIT = false: the size query -- tokens only counted (tok / tok_prefix unused)
+template <bool EMIT = true>
 __global__ __launch_bounds__(64) void xhd_parse_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, const u64* __restrict__ tok_prefix,
                                                       uint32_t* __restrict__ tok, u64* __restrict__ ntok,
                                                       u64* __restrict__ d_out_len, int32_t* __restrict__ d_status, const uint32_t* __restrict__ mode)
@@ -1085,9 +1103,9 @@ __global__ __launch_bounds__(64) void xhd_parse_kernel(const uint8_t* __restrict
 	const uint32_t n = (uint32_t)bt.in_len[u];
 	const u64 cap = bt.out_cap[u];
 	const uint8_t* src = d_in + bt.in_off[u];
-	uint32_t* __restrict__ mytok = tok + tok_prefix[u];
+	uint32_t* __restrict__ mytok = EMIT ? tok + tok_prefix[u] : nullptr;
 	u64 nt = 0; uint32_t ns = 0, treg = 0;                               // tokens in HBM; tokens staged: token k of the batch waits in lane k
-	#define XHD_EMIT(w) { treg = lane == ns ? (w) : treg; ++ns; if (ns == 64u) { mytok[nt + lane] = treg; nt += 64u; ns = 0; } }
+	#define XHD_EMIT(w) { if (EMIT) { treg = lane == ns ? (w) : treg; } ++ns; if (ns == 64u) { if (EMIT) { mytok[nt + lane] = treg; } nt += 64u; ns = 0; } }
 	int32_t status = 1; u64 op = 0;                                      // 1 = running
 	// ---- input ring (see xpd_kernel) ----
 	const uint32_t a0 = (uint32_t)((uintptr_t)src & 15u);
@@ -1215,7 +1233,7 @@ __global__ __launch_bounds__(64) void xhd_parse_kernel(const uint8_t* __restrict
 	#undef XHD_SKIP
 	#undef XHD_MASK_ZERO
 	#undef XHD_DECODE
-	if (lane < ns) { mytok[nt + lane] = treg; }
+	if (EMIT && lane < ns) { mytok[nt + lane] = treg; }
 	#undef XHD_EMIT
 	if (lane == 0) { d_status[u] = status; d_out_len[u] = status == 0 ? op : 0; ntok[u] = status == 0 ? nt + ns : 0; }
 }
@@ -1262,7 +1280,7 @@ __global__ __launch_bounds__(256) void xhc_mark_kernel(const uint8_t* __restrict
 // ONE chunk per wave, wherever a candidate says a chunk starts (speculative: see xhc_mark_kernel / xhc_chain_kernel). PASS 1: every candidate
 // is measured (where the next chunk would start, bytes produced, how far its matches reach in front of the chunk, tokens; 2 = not a chunk);
 // the candidate at offset 0 is chunk 0 for sure and writes its tokens at once. PASS 2: the chunks the chain check accepted write their
-// tokens at their place in the unit's token stream.
+// tokens at their place in the unit's token stream. PASS 3 (the size query): PASS 1 without any token written, chunk 0 included.
 #ifdef XHC_PROFILE   // make EXTRA=-DXHC_PROFILE: steps / symbols per step / symbols one at a time, summed and the maximum per chunk (tools/dev/gpu_xhcprof.py)
 __device__ unsigned long long g_xhc_prof[8];
 extern "C" void mscomp_amd_debug_xhc_prof(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_xhc_prof), 64); unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_xhc_prof), z, 64); }
@@ -1288,16 +1306,16 @@ __global__ __launch_bounds__(64) void xhc_parse_kernel(const uint8_t* __restrict
 	// accepted chunks to their place), and PASS 2 is left with the chunks whose tokens did not fit (state bit 4)
 	const bool has_scr = xb.scr_prefix != nullptr && xb.scr_prefix[u + 1] > xb.scr_prefix[u];
 	if (PASS == 2 && (xb.mode[u] != XHC_SPEC || xb.tok_off[slot] == ~(u64)0 || xb.cand_pos[slot] == 0 || (has_scr && !(xb.res_state[slot] & 4u)))) { return; }
-	const bool writing = PASS == 2 || xb.cand_pos[slot] == 0;
+	const bool writing = PASS == 2 || xb.cand_pos[slot] == 0;           // (in PASS 3: walks on as chunk 0 does, without storing)
 	const bool scr = PASS == 1 && !writing && has_scr;
 	bool scr_ok = true;
 	const uint32_t at = xb.cand_pos[slot];
 	const uint32_t n = (uint32_t)bt.in_len[u];
 	const uint8_t* src = d_in + bt.in_off[u];
 	const u64 tok_at = PASS == 2 ? xb.tok_off[slot] : (u64)0;
-	uint32_t* __restrict__ mytok = scr ? xb.scr_tok + (xb.scr_prefix[u] + idx) * (u64)XHC_SCR : tok + tok_prefix[u] + tok_at;
-	const u64 tokcap = scr ? (u64)XHC_SCR : tok_prefix[u + 1] - tok_prefix[u] - tok_at;   // chunk 0 writes before the capacity is judged: never beyond the unit's slots
-	const bool storing = writing || scr;
+	uint32_t* __restrict__ mytok = PASS == 3 ? nullptr : scr ? xb.scr_tok + (xb.scr_prefix[u] + idx) * (u64)XHC_SCR : tok + tok_prefix[u] + tok_at;
+	const u64 tokcap = PASS == 3 ? 0 : scr ? (u64)XHC_SCR : tok_prefix[u + 1] - tok_prefix[u] - tok_at;   // chunk 0 writes before the capacity is judged: never beyond the unit's slots
+	const bool storing = PASS != 3 && (writing || scr);
 #ifdef XHC_PROFILE
 	uint32_t xhc_loc[2] = {0, 0};
 #endif
@@ -1511,7 +1529,7 @@ __global__ __launch_bounds__(64) void xhc_parse_kernel(const uint8_t* __restrict
 				XHD_SKIP(ob)
 				if (off > op && off - op > reach) { reach = off - op; }   // :120 is judged when the chunk's place in the output is known
 				op += len; prod = prod + len < prod ? 0xFFFFFFFFu : prod + len;
-				if (writing || (scr && len <= 4u * LZT_MAXLEN)) { while (len > LZT_MAXLEN) { XHD_EMIT(off | (LZT_MAXLEN << 16)) len -= LZT_MAXLEN; } }
+				if (PASS != 3 && (writing || (scr && len <= 4u * LZT_MAXLEN))) { while (len > LZT_MAXLEN) { XHD_EMIT(off | (LZT_MAXLEN << 16)) len -= LZT_MAXLEN; } }
 				else if (len > LZT_MAXLEN) { nt += (len - 1u) / LZT_MAXLEN; len = LZT_MAXLEN; scr_ok = false; }   // only counted: a candidate that is no chunk may "hold" gigabyte matches
 				XHD_EMIT(off | (len << 16))
 			}
@@ -1533,7 +1551,7 @@ __global__ __launch_bounds__(64) void xhc_parse_kernel(const uint8_t* __restrict
 	#undef XHD_DECODE
 	#undef XHD_EMIT
 	XHC_END()
-	if (PASS == 1 && lane == 0) {
+	if (PASS != 2 && lane == 0) {
 		xb.res_state[slot] = (status == 1 ? state : 2u) | ((scr && (!scr_ok || nt > XHC_SCR)) ? 4u : 0u); xb.res_end[slot] = next_at; xb.res_prod[slot] = op; xb.res_ntok[slot] = nt;
 		xb.res_reach[slot] = reach > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)reach;
 	}
@@ -1898,7 +1916,7 @@ void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const Ba
 	case 2: hipLaunchKernelGGL(xhc_chain_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, cand_prefix, xb, ntok, d_out_len, d_status); break;
 	case 3: if (xb.scr_prefix) { hipLaunchKernelGGL(xhc_gather_kernel, dim3(n_slots), dim3(256), 0, st, bt, tok_prefix, cand_prefix, xb, tok); }
 	        hipLaunchKernelGGL(xhc_parse_kernel<2>, dim3(n_slots), dim3(64), 0, st, d_in, bt, tok_prefix, cand_prefix, xb, tok); break;
-	case 4: hipLaunchKernelGGL(xhd_parse_kernel, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, xb.mode); break;
+	case 4: hipLaunchKernelGGL(xhd_parse_kernel<true>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, xb.mode); break;
 	default: {
 		if (g_lzb_attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_copy_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzbLds)); g_lzb_attr.done(); }
 		hipLaunchKernelGGL(lz_copy_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap);
@@ -1906,6 +1924,32 @@ void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const Ba
 		break;
 	}
 	}
+}
+
+void launch_xpress_huff_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, const u64* cand_prefix, uint32_t n_slots,
+                             const XhcBufs& xb, u64* d_out_len, int32_t* d_status, int phase)
+{
+	if (bt.n_units == 0) { return; }
+	switch (phase) {
+	case 0: launch_xpress_huff_decompress(st, d_in, bt, nullptr, nullptr, ntok, cand_prefix, n_slots, xb, nullptr, d_out_len, d_status, 0, ~(u64)0); break;
+	case 1: hipLaunchKernelGGL(xhc_parse_kernel<3>, dim3(n_slots), dim3(64), 0, st, d_in, bt, (const u64*)nullptr, cand_prefix, xb, (uint32_t*)nullptr); break;
+	case 2: launch_xpress_huff_decompress(st, d_in, bt, nullptr, nullptr, ntok, cand_prefix, n_slots, xb, nullptr, d_out_len, d_status, 2, ~(u64)0); break;
+	default: hipLaunchKernelGGL(xhd_parse_kernel<false>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, (const u64*)nullptr, (uint32_t*)nullptr, ntok, d_out_len, d_status, (const uint32_t*)xb.mode); break;
+	}
+}
+
+void launch_xpress_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, u64* d_out_len, int32_t* d_status, int phase, const XpsTables& x)
+{
+	if (bt.n_units == 0) { return; }
+	if (phase == -3) {                                                   // the verdict, then the emit walk without its stores
+		if (!x.n_big) { return; }
+		hipLaunchKernelGGL(xps_check_kernel<true>, dim3(x.n_big), dim3(256), 0, st, bt, x, ntok, d_out_len, d_status);
+		hipLaunchKernelGGL(xps_emit_kernel<false>, dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x, (const u64*)nullptr, (uint32_t*)nullptr);
+		return;
+	}
+	if (phase < 0) { launch_xpress_decompress_tokens(st, d_in, bt, nullptr, nullptr, ntok, nullptr, d_out_len, d_status, phase, ~(u64)0, x); return; }
+	hipLaunchKernelGGL(xpt_parse_kernel<false>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, (const u64*)nullptr, (uint32_t*)nullptr, ntok, d_out_len, d_status,
+	                   (const uint32_t*)(x.n_big ? x.done : nullptr));
 }
 
 void launch_xpress_decompress_tokens(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
@@ -1923,11 +1967,11 @@ void launch_xpress_decompress_tokens(hipStream_t st, const uint8_t* d_in, const 
 			hipLaunchKernelGGL(xps_walk_kernel<1>, dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x);
 		} else {
 			hipLaunchKernelGGL(xps_check_kernel<true>, dim3(x.n_big), dim3(256), 0, st, bt, x, ntok, d_out_len, d_status);
-			hipLaunchKernelGGL(xps_emit_kernel, dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x, tok_prefix, tok);
+			hipLaunchKernelGGL(xps_emit_kernel<true>, dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x, tok_prefix, tok);
 		}
 		return;
 	}
-	if (phase == 0) { hipLaunchKernelGGL(xpt_parse_kernel, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, (const uint32_t*)(x.n_big ? x.done : nullptr)); return; }
+	if (phase == 0) { hipLaunchKernelGGL(xpt_parse_kernel<true>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, (const uint32_t*)(x.n_big ? x.done : nullptr)); return; }
 	if (g_lzb_attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_copy_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzbLds)); g_lzb_attr.done(); }
 	if (phase == 1) { hipLaunchKernelGGL(lz_copy_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap); }
 	else { hipLaunchKernelGGL(lz_copy_block_kernel, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap); }
