@@ -13,11 +13,12 @@
 //   C. window by window (64 positions, lane = position), LAZILY like the reference (Find runs only where the greedy parse
 //      can start a token):
 //        1. every lane at or after the parse position scans the 4 OLDEST candidates of its position itself (unconditional
-//           loads in flight together, own bytes in registers, 16-byte compares, strictly-longer wins, early exit at max_len);
+//           loads in flight together, own bytes in registers, 16-byte compares, strictly-longer wins);
 //        2. the greedy walk runs on the scalar unit over ballot masks (s_ff1 over literal runs). When it lands on a
-//           position that still has unexamined candidates, the whole wave finishes that ONE position: 64 candidates per
-//           step, DPP max of (len, -position) = longest, oldest on ties, stop when max_len is reached. Positions covered
-//           by a match are never finished;
+//           position with a candidate that matched 16 bytes (and max_len > 16), the whole wave extends those candidates,
+//           256 bytes per step; when it lands on a position that still has unexamined candidates, the whole wave finishes
+//           that ONE position: 64 candidates per step, DPP max of (len, -position) = longest, oldest on ties, stop when
+//           max_len is reached. Positions covered by a match are never extended or finished;
 //        3. tokens go straight to the chunk's scratch slot, placed by the closed form
 //           pos(t) = (t div 8 + 1) + sum size(u<t)   (mbcnt prefix popcounts); flag bits collect in a 16-entry LDS ring;
 //   D. header (0xB000|size-1), or the raw chunk (0x3000|n-1) when the running size reaches n; util.hip concatenates slots.
@@ -39,8 +40,10 @@ __device__ unsigned long long g_lz_prof[16];
 #define LZ_TEND
 #endif
 
-#ifdef LZ4_PROFILE   // dev-only: the four-wave kernel's phase cycles ([0..6], thread 0) and finishing steps ([7], all windows walked)
-__device__ unsigned long long g_lz4_prof[8];
+#ifdef LZ4_PROFILE   // dev-only: the four-wave kernel's phase cycles ([0..6], thread 0); summed over all windows walked: finishing steps [7],
+                     // lz_lcp_tail wave-iterations of the finishing steps [8], long-pending stops [9], cooperative 256-byte extension steps [10]
+#define LZ4_NPROF 16
+__device__ unsigned long long g_lz4_prof[LZ4_NPROF];
 #endif
 
 #ifndef LZ_TBL_BITS
@@ -84,10 +87,11 @@ __device__ __forceinline__ uint4 lz_ld128(const uint8_t* base, uint32_t off)
 }
 // Common prefix beyond the first 16 (equal) bytes of d[q..] and d[p..]: 16 bytes per step; the result may exceed maxlen
 // (callers clamp).
-__device__ __forceinline__ uint32_t lz_lcp_tail(const uint8_t* d, uint32_t q, uint32_t p, uint32_t maxlen)
+__device__ __forceinline__ uint32_t lz_lcp_tail(const uint8_t* d, uint32_t q, uint32_t p, uint32_t maxlen, uint32_t& it)
 {
 	uint32_t l = 16u;
 	for (;;) {
+		++it;
 		uint4 a, b;
 		a = lz_ld128(d, q + l); b = lz_ld128(d, p + l);
 		const uint32_t f = first_nz_byte16(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
@@ -95,6 +99,30 @@ __device__ __forceinline__ uint32_t lz_lcp_tail(const uint8_t* d, uint32_t q, ui
 		if (f < 16u || l >= maxlen) { break; }
 	}
 	return l;
+}
+// The same with the whole wave, for ONE pair (q, p, l and maxlen wave-uniform, l < maxlen): lane i compares the dword at l + 4 i, 256 bytes
+// per step, from two aligned reads per side and v_alignbyte (the byte shifts are uniform: 4 i keeps the low bits); the first mismatch is the
+// ballot's lowest lane plus the first differing byte of its XOR. Offsets are taken modulo 4096 like lz_ld128's: what lies at or beyond
+// p + maxlen <= n is clamped away. Returns min(common prefix, maxlen).
+__device__ __forceinline__ uint32_t lz_lcp_wave(const uint8_t* d, uint32_t q, uint32_t p, uint32_t l, uint32_t maxlen, uint32_t lane, uint32_t& steps)
+{
+	const uint32_t shq = (q + l) & 3u, shp = (p + l) & 3u;
+	for (;;) {
+		const uint32_t oq = q + l + 4u * lane, op = p + l + 4u * lane;
+		const uint32_t* const aq = reinterpret_cast<const uint32_t*>(d + (oq & 0xFFCu));
+		const uint32_t* const ap = reinterpret_cast<const uint32_t*>(d + (op & 0xFFCu));
+		const uint32_t x = __builtin_amdgcn_alignbyte(aq[1], aq[0], shq) ^ __builtin_amdgcn_alignbyte(ap[1], ap[0], shp);
+		const u64 ne = __builtin_amdgcn_ballot_w64(x != 0u);
+		++steps;
+		if (ne) {
+			const uint32_t i = ctz64(ne);
+			l += 4u * i + ((uint32_t)__builtin_ctz((uint32_t)__builtin_amdgcn_readlane((int)x, (int)i)) >> 3);
+			break;
+		}
+		l += 256u;
+		if (l >= maxlen) { break; }
+	}
+	return l < maxlen ? l : maxlen;
 }
 // First difference of two 16-byte blocks given their XOR, as a BIT index limited to capbits (<= 128): common.h first_nz_byte16 without
 // its final shift -- the limit (8 x min(max_len, 16)) rides in the minimum that finds the difference, so the byte count needs no clamp.
@@ -153,34 +181,42 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	for (uint32_t j = 0; j <= LZ_SELF; ++j) { q[j] = wld16(const_cast<uint16_t*>(s_bucket) + s + j); }
 	#pragma unroll
 	for (uint32_t j = 0; j <= LZ_SELF; ++j) { ex[j] = j < cnt && q[j] < p; }
-	const bool longer = maxlen > 16u;
+	// The compares stop at min(max_len, 16) bytes. A candidate that reached 16 bytes with max_len > 16 is extended only when the walk lands on
+	// its position (step 2), by the whole wave: inside a long repeat every lane has such candidates, and the walk visits one or two of them.
 	const uint32_t capb = (maxlen < 16u ? maxlen : 16u) << 3;
+	u64 m16[LZ_SELF];                                         // lanes whose candidate k reached 16 bytes (kk >= 16 << 12 <=> it exists and did)
 	{
 		uint4 c[LZ_SELF];                                     // (all loads in flight together)
 		#pragma unroll
 		for (uint32_t k = 0; k < LZ_SELF; ++k) { c[k] = lz_ld128(s_data, q[k]); }
 		#pragma unroll
 		for (uint32_t k = 0; k < LZ_SELF; ++k) {
-			uint32_t lb = lz_diff_bits16(c[k].x ^ o0, c[k].y ^ o1, c[k].z ^ o2, c[k].w ^ o3, capb);     // length in bits (the low three dropped below)
-			if (ex[k] && lb >= 128u && longer) { const uint32_t l = lz_lcp_tail(s_data, q[k], p, maxlen); lb = (l < maxlen ? l : maxlen) << 3; }   // long match
+			const uint32_t lb = lz_diff_bits16(c[k].x ^ o0, c[k].y ^ o1, c[k].z ^ o2, c[k].w ^ o3, capb);     // length in bits (the low three dropped below)
 			const uint32_t kk = ex[k] ? (((lb & ~7u) << 9) | (q[k] ^ 4095u)) : 0u;
+			m16[k] = __builtin_amdgcn_ballot_w64(kk >= (16u << 12));
 			key = kk > key ? kk : key;
 		}
 	}
 	// 2. greedy walk; unresolved positions (a fifth older candidate exists and max_len was not reached) are finished by the whole wave
-	// when (and only when) the walk lands on them. (The masks are built from ballots of single compares, combined on the scalar
-	// unit: the ballot of a combined condition costs two more vector instructions. len <= maxlen, so "not reached" is key < maxlen << 12.)
-	u64 un = __builtin_amdgcn_ballot_w64(cnt > LZ_SELF) & __builtin_amdgcn_ballot_w64(q[LZ_SELF] < p) & __builtin_amdgcn_ballot_w64(key < (maxlen << 12));
-	u64 mm = __builtin_amdgcn_ballot_w64(key >= (3u << 12)) & ~un;              // resolved positions that have a match
+	// when (and only when) the walk lands on them, and so are the long-pending ones (a candidate reached 16 bytes, max_len > 16: the
+	// key is provisional), whose candidates are extended first. (The masks are built from ballots of single compares, combined on the
+	// scalar unit: the ballot of a combined condition costs two more vector instructions. len <= maxlen, so "not reached" is
+	// key < maxlen << 12; a long-pending lane's provisional key never reaches it.)
+	const u64 five = __builtin_amdgcn_ballot_w64(cnt > LZ_SELF) & __builtin_amdgcn_ballot_w64(q[LZ_SELF] < p);
+	u64 un = five & __builtin_amdgcn_ballot_w64(key < (maxlen << 12));
+	const u64 lp = sgpr64((m16[0] | m16[1] | m16[2] | m16[3]) & __builtin_amdgcn_ballot_w64(maxlen > 16u));
+	static_assert(LZ_SELF == 4u, "the long-pending mask ORs four candidates' masks");
+	u64 mm = __builtin_amdgcn_ballot_w64(key >= (3u << 12)) & ~un;              // resolved or long-pending positions that have a match
 	// The serial loop only decides which candidates are TAKEN; everything else (which positions are literal tokens)
 	// is derived in parallel afterwards.
 	u64 matchmask = 0;
 	const uint32_t wn = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wend - wbase));
-	// Every resolved match lane precomputes where the walk goes after taking it: the first stop (match or unresolved
-	// position) at or after its end, relative to the window (>= wn leaves it). The scalar walk is then one
-	// v_readlane per taken match; it leaves the asm block on an unresolved position (st = 1), which is finished by
-	// the whole wave. Stops are only ever removed at the walk's own position, so the table never goes stale ahead.
+	// Every resolved match lane precomputes where the walk goes after taking it: the first stop (match, unresolved or long-pending
+	// position) at or after its end, relative to the window (>= wn leaves it). The scalar walk is then one v_readlane per taken
+	// match; it leaves the asm block on an unresolved or long-pending position (st = 1), which the whole wave resolves. Stops are
+	// only ever removed at the walk's own position, so the table never goes stale ahead.
 	un = sgpr64(un); mm = sgpr64(mm);
+	const u64 pend = sgpr64(un | lp);
 	// (a target at or beyond wn only has to be >= wn: the walk ends there and the position after the window comes from the
 	// match ends below. So no guard for nx >= 64: the shift count wraps, and nx + anything is already >= 64 >= wn.)
 	const uint32_t nx = lane + (key >> 12);
@@ -202,7 +238,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 		asm volatile(
 			"s_nop 3\n\t"
 			"1:\n\t"
-			"s_bitcmp1_b64 %[un], %[mp]\n\t"
+			"s_bitcmp1_b64 %[pend], %[mp]\n\t"
 			"s_cbranch_scc1 3f\n\t"
 			"s_bitset1_b64 %[mk], %[mp]\n\t"
 			"v_readlane_b32 %[mp], %[J], %[mp]\n\t"
@@ -214,42 +250,67 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 			"s_mov_b32 %[st], 1\n\t"
 			"4:\n\t"
 			: [mp] "+s"(mp), [mk] "+s"(matchmask), [st] "=&s"(st)
-			: [un] "s"(un), [wn] "s"(wn), [J] "v"(J)
+			: [pend] "s"(pend), [wn] "s"(wn), [J] "v"(J)
 			: "scc");
 		if (st == 0) { break; }
 		{
-			// finish position wbase+mp: the candidates after the first LZ_SELF of its bucket, oldest first, 64 per step
 			const uint32_t sL = (uint32_t)__builtin_amdgcn_readlane((int)s, (int)mp);
-			const uint32_t eL = (uint32_t)__builtin_amdgcn_readlane((int)e, (int)mp);
 			const uint32_t maxL = (uint32_t)__builtin_amdgcn_readlane((int)maxlen, (int)mp);
-			const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)o0, (int)mp), a1 = (uint32_t)__builtin_amdgcn_readlane((int)o1, (int)mp);
-			const uint32_t a2 = (uint32_t)__builtin_amdgcn_readlane((int)o2, (int)mp), a3 = (uint32_t)__builtin_amdgcn_readlane((int)o3, (int)mp);
-			uint32_t kbest = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)mp);
-#ifdef LZ4_PROFILE
-			uint32_t nsteps = 0;
-#endif
 			const uint32_t pL = wbase + mp;
-			const bool longL = maxL > 16u;
-			const uint32_t capL = (maxL < 16u ? maxL : 16u) << 3;
-			for (uint32_t base = sL + LZ_SELF; base < eL; base += 64u) {
-				const uint32_t qq = s_bucket[base + lane];         // unconditional load (past the array's end it reads the table), masked below
-				const bool v1 = lane < eL - base, v2 = qq < pL;     // else: this lane is at or beyond pL's own entry
-				const bool valid = v1 && v2;
-				const u64 vmask = __builtin_amdgcn_ballot_w64(v1) & __builtin_amdgcn_ballot_w64(v2);
-				const uint4 c = lz_ld128(s_data, qq);
-				uint32_t l2 = lz_diff_bits16(c.x ^ a0, c.y ^ a1, c.z ^ a2, c.w ^ a3, capL);   // in bits
-				if (valid && l2 >= 128u && longL) { const uint32_t l = lz_lcp_tail(s_data, qq, pL, maxL); l2 = (l < maxL ? l : maxL) << 3; }
-				uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(vmask));   // (a key below 3 << 12 is no match)
-				const uint32_t m = wave_max_u32(k2);
-				kbest = m > kbest ? m : kbest;                   // longest, then oldest (older blocks hold the larger 4095 - q)
+			uint32_t kbest = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)mp);
+			bool fin = (un >> mp) & (u64)1;
+			if ((lp >> mp) & (u64)1) {
+				// long-pending: extend its candidates that reached 16 bytes, oldest first, with the whole wave; the first one that reaches
+				// max_len cannot be beaten (an older one would have to be longer). Then it is unresolved only if a fifth candidate exists
+				// and max_len was not reached.
+				const uint32_t qv = s_bucket[sL + (lane & (LZ_SELF - 1u))];   // (its first four entries: the candidates above)
+				uint32_t nst = 0;
+				#pragma unroll
+				for (uint32_t k = 0; k < LZ_SELF; ++k) {
+					if ((m16[k] >> mp) & (u64)1) {
+						const uint32_t qk = (uint32_t)__builtin_amdgcn_readlane((int)qv, (int)k);
+						const uint32_t l = lz_lcp_wave(s_data, qk, pL, 16u, maxL, lane, nst);
+						const uint32_t kk = (l << 12) | (qk ^ 4095u);
+						kbest = kk > kbest ? kk : kbest;
+						if (l == maxL) { break; }
+					}
+				}
+				fin = ((five >> mp) & (u64)1) && kbest < (maxL << 12);
 #ifdef LZ4_PROFILE
-				++nsteps;
+				if (lane == 0) { atomicAdd(&g_lz4_prof[9], 1ull); atomicAdd(&g_lz4_prof[10], (unsigned long long)nst); }
 #endif
-				if ((kbest >> 12) == maxL || ~vmask) { break; }  // max_len reached / all older candidates seen
 			}
+			if (fin) {
+				// finish position wbase+mp: the candidates after the first LZ_SELF of its bucket, oldest first, 64 per step
+				const uint32_t eL = (uint32_t)__builtin_amdgcn_readlane((int)e, (int)mp);
+				const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)o0, (int)mp), a1 = (uint32_t)__builtin_amdgcn_readlane((int)o1, (int)mp);
+				const uint32_t a2 = (uint32_t)__builtin_amdgcn_readlane((int)o2, (int)mp), a3 = (uint32_t)__builtin_amdgcn_readlane((int)o3, (int)mp);
 #ifdef LZ4_PROFILE
-			if (lane == 0) { atomicAdd(&g_lz4_prof[7], (unsigned long long)nsteps); }
+				uint32_t nsteps = 0, ntail = 0;
 #endif
+				const bool longL = maxL > 16u;
+				const uint32_t capL = (maxL < 16u ? maxL : 16u) << 3;
+				for (uint32_t base = sL + LZ_SELF; base < eL; base += 64u) {
+					const uint32_t qq = s_bucket[base + lane];         // unconditional load (past the array's end it reads the table), masked below
+					const bool v1 = lane < eL - base, v2 = qq < pL;     // else: this lane is at or beyond pL's own entry
+					const bool valid = v1 && v2;
+					const u64 vmask = __builtin_amdgcn_ballot_w64(v1) & __builtin_amdgcn_ballot_w64(v2);
+					const uint4 c = lz_ld128(s_data, qq);
+					uint32_t l2 = lz_diff_bits16(c.x ^ a0, c.y ^ a1, c.z ^ a2, c.w ^ a3, capL);   // in bits
+					uint32_t it = 0;
+					if (valid && l2 >= 128u && longL) { const uint32_t l = lz_lcp_tail(s_data, qq, pL, maxL, it); l2 = (l < maxL ? l : maxL) << 3; }
+					uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(vmask));   // (a key below 3 << 12 is no match)
+					const uint32_t m = wave_max_u32(k2);
+					kbest = m > kbest ? m : kbest;                   // longest, then oldest (older blocks hold the larger 4095 - q)
+#ifdef LZ4_PROFILE
+					++nsteps; ntail += wave_max_u32(it);
+#endif
+					if ((kbest >> 12) == maxL || ~vmask) { break; }  // max_len reached / all older candidates seen
+				}
+#ifdef LZ4_PROFILE
+				if (lane == 0) { atomicAdd(&g_lz4_prof[7], (unsigned long long)nsteps); atomicAdd(&g_lz4_prof[8], (unsigned long long)ntail); }
+#endif
+			}
 			if (lane == mp) { key = kbest; }
 			un = sgpr64(un & ~(((u64)1) << mp));
 			// literals before mp are settled; mp itself is now resolved: take its match, or step over it as a literal
@@ -481,7 +542,7 @@ extern "C" void mscomp_amd_debug_lz_prof(unsigned long long* out, int reset)
 __device__ __forceinline__ uint32_t lz4_seg_start(uint32_t j) { return j == 0 ? 0u : j == 1 ? LZ4_B1 : j == 2 ? LZ4_B2 : j == 3 ? LZ4_B3 : 64u; }
 #define LZ4_MAXM 22u                                             // matches that can START in one window of 64 positions
 #ifdef LZ4_PROFILE
-extern "C" void mscomp_amd_debug_lz4_prof(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lz4_prof), 64); unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lz4_prof), z, 64); }
+extern "C" void mscomp_amd_debug_lz4_prof(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lz4_prof), sizeof(unsigned long long) * LZ4_NPROF); unsigned long long z[LZ4_NPROF] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lz4_prof), z, sizeof z); }
 #endif
 static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: LZNT1_REC = two areas of 64 windows of match tokens");
 template <bool serial>

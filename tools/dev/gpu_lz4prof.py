@@ -10,7 +10,7 @@ name = sys.argv[1] if len(sys.argv) > 1 else "mozilla"
 ctx = m.Context()
 buf = corpus.by_name(name, 51220480).tobytes()
 out, st = m.compress_units(2, [buf])          # warm-up (tables, first-touch)
-z = (ctypes.c_ulonglong * 8)()
+z = (ctypes.c_ulonglong * 16)()                # (lznt1.hip LZ4_NPROF)
 ctx.lib.mscomp_amd_debug_lz4_prof(z)
 out, st = m.compress_units(2, [buf])
 ctx.lib.mscomp_amd_debug_lz4_prof(z)

@@ -35,10 +35,12 @@ if hasattr(lib, "mscomp_amd_debug_lz4_prof") or True:
     import ctypes as C
     try:
         lib.mscomp_amd_debug_set_lznt1(2)
-        buf = (C.c_ulonglong * 8)(); lib.mscomp_amd_debug_lz4_prof(buf)
+        buf = (C.c_ulonglong * 16)(); lib.mscomp_amd_debug_lz4_prof(buf)
         plan.execute(d_in, d_out, d_len, d_st); torch.cuda.synchronize(); lib.mscomp_amd_debug_lz4_prof(buf)
         nch = (n + 4095) // 4096
         print("wave 0 cycles per chunk: load %.0f | sort %.0f | parse(seg 0) %.0f | seam %.0f | wait %.0f | cascade+scan %.0f | emit %.0f" % tuple(buf[i] / nch for i in range(7)))
+        print("per chunk (all windows walked): finishing steps %.1f | their lz_lcp_tail wave-iterations %.1f | long-pending stops %.1f | "
+              "cooperative 256-byte steps %.1f" % tuple(buf[i] / nch for i in range(7, 11)))
     except AttributeError:
         pass
     lib.mscomp_amd_debug_set_lznt1(0)
