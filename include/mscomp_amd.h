@@ -219,6 +219,37 @@ MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* ctx, MSCompForma
                                                 const uint64_t* in_off, const uint64_t* in_len, const uint64_t* limit,
                                                 uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status);
 
+/* Decompress plans with device tables: created once from bounds, executed many times with unit tables that GPU work earlier on the ctx stream
+ * has written (the d_out_len of a compress plan, the d_need of the size query, the offsets of mscomp_amd_layout_dev or of
+ * mscomp_amd_compact_batch). n_units is fixed when the plan is created. Two caps apply to the units, summed in unit order:
+ *   total in_len  <= in_total_max   (across all units)
+ *   total out_cap <= out_total_max  (across all units)
+ * d_in_off, d_in_len, d_out_off, d_out_cap: device arrays of n_units uint64, read when the work runs on the ctx stream.
+ *   Per-unit results: for every unit that passes the checks below, d_status[i] and d_out_len[i], and the bytes on MSCOMP_OK, are exactly those
+ *                 of a decompress plan (mscomp_amd_plan_create_decompress) with the same values -- what one ms_decompress call returns.
+ *   Units that fail the checks: a unit gets MSCOMP_ARG_ERROR, d_out_len = 0, and nothing is read or written for it, if its in_len is above
+ *                 0xFFFFF000, or the running total of in_len up to and including it is above in_total_max, or the running total of out_cap up
+ *                 to and including it is above out_total_max. The other units are unaffected. Offsets are the caller's responsibility.
+ *   Execution:    mscomp_amd_plan_execute_dev is asynchronous on the ctx stream; it allocates nothing, does not synchronize and reads nothing back
+ *                 to the host. It may run while the ctx stream is being captured into a graph (it then enqueues plain launches). Outside
+ *                 capture it replays a graph of its own from its second execution on, captured again whenever one of its pointers changes.
+ *                 MSCOMP_ARG_ERROR for a null plan or array (d_in / d_out may be null when the matching bound is 0).
+ *   Plan kinds:   mscomp_amd_plan_execute and mscomp_amd_plan_execute_size return MSCOMP_ARG_ERROR for a dev plan, mscomp_amd_plan_execute_dev
+ *                 for any other plan, without enqueueing anything. mscomp_amd_plan_destroy frees every kind.
+ *   Creation:     the argument checks of mscomp_amd_plan_create_decompress (MSCOMP_ARG_ERROR for a null ctx or plan pointer or a bad format);
+ *                 MSCOMP_MEM_ERROR when the scratch for the bounds cannot be reserved. The scratch is reserved for the bounds, once.
+ * Dev plans decode without the optional paths that need tables chosen on the host (DESIGN_DECODERS.md): below 512 KiB of Xpress input and
+ * 1 MiB of capacity per unit they run the same kernels as a host plan; larger units decode to the same bytes, more slowly. */
+MSCompStatus mscomp_amd_plan_create_decompress_dev(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units,
+                                                   uint64_t in_total_max, uint64_t out_total_max, mscomp_amd_plan** plan);
+MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* plan, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                         uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+                                         uint64_t* d_out_len, int32_t* d_status);
+/* Exclusive running sum of d_cap[i] rounded up to `align` (0 counts as 1), written to d_off[0..n_units] (d_off[n_units] = total; a sum beyond
+ * 2^64 - 1 stays there), on the ctx stream: it turns d_need of the size query, or d_out_len of a compress plan, into a packed layout without
+ * leaving the GPU. d_cap and d_off are device arrays (uint64). Asynchronous; allocates nothing. */
+MSCompStatus mscomp_amd_layout_dev(mscomp_amd_ctx* ctx, size_t n_units, const uint64_t* d_cap, uint64_t align, uint64_t* d_off);
+
 /* Batch helpers.
  * Capacity planning: out_cap[i] = what one ms_compress call needs at most for in_len[i] bytes (ms_max_compressed_size, + 2 for the LZNT1
  * End_of_buffer), out_off[i] = running offset rounded up to `align`; returns the total size of the output buffer ((uint64_t)-1: bad format).

@@ -35,6 +35,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "ms_decompress", "lznt1_decompress", "xpress_decompress", "xpress_huff_decompress", "mscomp_amd_plan_create_decompress", "mscomp_amd_decompress_batch",
     "mscomp_amd_version", "mscomp_amd_debug_xpress_matches", "mscomp_amd_debug_huff_lengths", "mscomp_amd_debug_lds_lane_order", "mscomp_amd_debug_set_xpress_emit", "mscomp_amd_debug_set_lznt1", "mscomp_amd_debug_set_serial_atomics", "mscomp_amd_compress_units_host", "mscomp_amd_decompress_units_host", "mscomp_amd_host_pool_release", "mscomp_amd_debug_set_finder", "mscomp_amd_debug_set_one_shot", "mscomp_amd_debug_set_xpress_decoder", "mscomp_amd_debug_lzg_open", "mscomp_amd_set_lznt1_sa_dict", "mscomp_amd_get_lznt1_sa_dict", "mscomp_amd_ctx_set_lznt1_sa_dict", "mscomp_amd_debug_hooks_enabled", "mscomp_amd_debug_lzd_walked",
     "mscomp_amd_plan_create_size", "mscomp_amd_plan_execute_size", "mscomp_amd_decompressed_size_batch",
+    "mscomp_amd_plan_create_decompress_dev", "mscomp_amd_plan_execute_dev", "mscomp_amd_layout_dev",
 ]
 
 
@@ -103,6 +104,12 @@ def load_library():
     lib.mscomp_amd_decompressed_size_batch.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_decompressed_size_batch.restype = C.c_int
+    lib.mscomp_amd_plan_create_decompress_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_plan_create_decompress_dev.restype = C.c_int
+    lib.mscomp_amd_plan_execute_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 8
+    lib.mscomp_amd_plan_execute_dev.restype = C.c_int
+    lib.mscomp_amd_layout_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.mscomp_amd_layout_dev.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -310,6 +317,51 @@ class SizePlan:
             self.close()
         except Exception:
             pass
+
+
+class DevPlan:
+    """A decompress plan with device tables (mscomp_amd_plan_create_decompress_dev): made once for n_units units whose in_len sum to at most
+    in_total_max and whose out_cap sum to at most out_total_max, then executed with unit tables that live on the device."""
+
+    def __init__(self, ctx, fmt, n_units, in_total_max, out_total_max):
+        self.ctx, self.fmt, self.n_units = ctx, int(fmt), int(n_units)
+        self.in_total_max, self.out_total_max = int(in_total_max), int(out_total_max)
+        self._h = C.c_void_p()
+        st = ctx.lib.mscomp_amd_plan_create_decompress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.out_total_max, C.byref(self._h))
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_plan_create_decompress_dev")
+
+    def execute(self, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status):
+        """Enqueue on the ctx stream (nothing is synchronized or read back). Arguments are torch CUDA tensors: uint8 input and output, int64 /
+        uint64 tables of n_units entries (offsets, lengths, capacities; results d_out_len), int32 d_status."""
+        ptrs = [C.c_void_p(t.data_ptr()) for t in (d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status)]
+        st = self.ctx.lib.mscomp_amd_plan_execute_dev(self._h, *ptrs)
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_plan_execute_dev")
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.mscomp_amd_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def layout_dev(ctx, d_cap, align=16, d_off=None):
+    """mscomp_amd_layout_dev: the exclusive running sum of d_cap rounded up to ``align``, on the device (int64 tensor of n + 1 offsets, the
+    last one the total), enqueued on the ctx stream. ``d_off`` (optional) is the tensor to write."""
+    import torch
+    n = d_cap.numel()
+    if d_off is None:
+        d_off = torch.empty(n + 1, dtype=torch.int64, device=d_cap.device)
+    st = ctx.lib.mscomp_amd_layout_dev(ctx._h, n, C.c_void_p(d_cap.data_ptr()), int(align), C.c_void_p(d_off.data_ptr()))
+    if st != MSCOMP_OK:
+        raise MSCompError(st, "mscomp_amd_layout_dev")
+    return d_off
 
 
 def _upload_units(units, dev):

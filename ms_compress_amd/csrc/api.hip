@@ -90,6 +90,8 @@ struct mscomp_amd_plan {
 	MSCompFormat format = MSCOMP_NONE;
 	bool decompress = false;
 	bool sizing = false;                               // a decompressed-size plan (mscomp_amd_plan_create_size): out_cap holds the limits, nothing is decoded
+	bool dev = false;                                  // a decompress plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev)
+	uint64_t in_total_max = 0, out_total_max = 0;      // ... and the bounds its scratch was reserved for
 	uint32_t n_units = 0, n_chunks = 0;
 	uint64_t total_in = 0, max_unit = 0;
 	bool lznt1_sa = false;                             // LZNT1: the suffix-array dictionary flavour -- fixed when the plan is created: a plan never changes its bytes under a running caller
@@ -108,7 +110,7 @@ struct mscomp_amd_plan {
 	// the launch sequence of plan_execute as a hipGraph: captured on the plan's second execution, replayed while the
 	// arguments and the scratch buffers stay where they were
 	hipGraphExec_t gexec = nullptr;
-	const void* g_args[4] = { nullptr, nullptr, nullptr, nullptr };
+	const void* g_args[9] = {};                        // (a dev plan's graph: its nine pointers)
 	uint64_t g_epoch = 0, g_mode = 0;
 	uint32_t executions = 0;
 };
@@ -540,6 +542,31 @@ static XpressWinBufs xpress_win_bufs(mscomp_amd_ctx* c, uint32_t n_chunks)
 	return b;
 }
 
+// the scratch of the LZNT1 header chain, laid out for the plan's chunk (segment) count
+static LzdBufs lzd_bufs(mscomp_amd_ctx* c, const mscomp_amd_plan* p)
+{
+	LzdBufs b;
+	b.cin = static_cast<uint32_t*>(c->dz_cin.p); b.csize = static_cast<uint16_t*>(c->dz_csize.p);
+	const size_t nk = (size_t)p->n_chunks * LZD_K;
+	b.segL = static_cast<uint32_t*>(c->dz_unit.p); b.segE = b.segL + nk; b.segcnt = b.segE + nk; b.segstop = b.segcnt + nk; b.segoff = b.segstop + nk;
+	b.selcnt = b.segoff + nk; b.seloff = b.selcnt + p->n_chunks;
+	b.stop = b.seloff + p->n_chunks; b.irregular = b.stop + p->n_units + 1u;
+	b.flat = static_cast<u64*>(c->prefix.p);
+	return b;
+}
+// the candidate records of Xpress+Huffman decompression, laid out for the plan's candidate slots (the token scratch, if any, is set by the caller)
+static XhcBufs xhc_bufs(mscomp_amd_ctx* c, const mscomp_amd_plan* p)
+{
+	XhcBufs xb = {};
+	const size_t nu = (size_t)p->n_units + 1, ns = p->xhc_slots;
+	uint8_t* q = static_cast<uint8_t*>(c->dz_xhc.p);
+	xb.res_prod = reinterpret_cast<u64*>(q); q += ns * 8; xb.res_ntok = reinterpret_cast<u64*>(q); q += ns * 8; xb.tok_off = reinterpret_cast<u64*>(q); q += ns * 8;
+	xb.cand_pos = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_end = reinterpret_cast<uint32_t*>(q); q += ns * 4;
+	xb.res_reach = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_state = reinterpret_cast<uint32_t*>(q); q += ns * 4;
+	xb.cand_cnt = reinterpret_cast<uint32_t*>(q); q += nu * 4; xb.mode = reinterpret_cast<uint32_t*>(q);
+	return xb;
+}
+
 static MSCompStatus plan_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
 {
 	mscomp_amd_ctx* c = p->ctx;
@@ -550,13 +577,7 @@ static MSCompStatus plan_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t
 	if (p->decompress) {
 		switch (p->format) {
 		case MSCOMP_LZNT1: {
-			LzdBufs b;
-			b.cin = static_cast<uint32_t*>(c->dz_cin.p); b.csize = static_cast<uint16_t*>(c->dz_csize.p);
-			const size_t nk = (size_t)p->n_chunks * LZD_K;
-			b.segL = static_cast<uint32_t*>(c->dz_unit.p); b.segE = b.segL + nk; b.segcnt = b.segE + nk; b.segstop = b.segcnt + nk; b.segoff = b.segstop + nk;
-			b.selcnt = b.segoff + nk; b.seloff = b.selcnt + p->n_chunks;
-			b.stop = b.seloff + p->n_chunks; b.irregular = b.stop + p->n_units + 1u;
-			b.flat = prefix;
+			const LzdBufs b = lzd_bufs(c, p);
 			{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b); }
 			{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
 			{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, prefix, p->n_chunks, tile_sums); }
@@ -588,16 +609,8 @@ static MSCompStatus plan_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t
 		case MSCOMP_XPRESS_HUFF: {
 			const u64* tp = static_cast<const u64*>(p->tokpre.p); uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
 			const u64* cp = tp + (p->n_units + 1u);
-			XhcBufs xb = {};
+			XhcBufs xb = xhc_bufs(c, p);
 			if (p->xhc_scr) { xb.scr_prefix = tp + 2 * (p->n_units + 1u); xb.scr_tok = static_cast<uint32_t*>(c->dz_scr.p); }
-			{
-				const size_t nu = (size_t)p->n_units + 1, ns = p->xhc_slots;
-				uint8_t* q = static_cast<uint8_t*>(c->dz_xhc.p);
-				xb.res_prod = reinterpret_cast<u64*>(q); q += ns * 8; xb.res_ntok = reinterpret_cast<u64*>(q); q += ns * 8; xb.tok_off = reinterpret_cast<u64*>(q); q += ns * 8;
-				xb.cand_pos = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_end = reinterpret_cast<uint32_t*>(q); q += ns * 4;
-				xb.res_reach = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_state = reinterpret_cast<uint32_t*>(q); q += ns * 4;
-				xb.cand_cnt = reinterpret_cast<uint32_t*>(q); q += nu * 4; xb.mode = reinterpret_cast<uint32_t*>(q);
-			}
 			static const char* const names[6] = { "xhc_mark_kernel", "xhc_parse_kernel", "xhc_chain_kernel", "xhc_parse2_kernel", "xhd_parse_kernel", "lz_copy_kernel" };
 			for (int ph = 0; ph < 6; ++ph) {
 				KernelTimer t(c, names[ph]);
@@ -661,7 +674,7 @@ static MSCompStatus plan_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t
 
 MSCompStatus mscomp_amd_plan_execute(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
 {
-	if (!p || p->sizing || (p->n_units && (!d_out_len || !d_status)) || (p->total_in && !d_in)) { return MSCOMP_ARG_ERROR; }
+	if (!p || p->sizing || p->dev || (p->n_units && (!d_out_len || !d_status)) || (p->total_in && !d_in)) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_ctx* c = p->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
@@ -745,13 +758,7 @@ static void size_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out
 	hipStream_t st = c->stream;
 	switch (p->format) {
 	case MSCOMP_LZNT1: {                                   // the header chain as in plan_launch, then every chunk sized, then the verdict at the limit
-		LzdBufs b;
-		b.cin = static_cast<uint32_t*>(c->dz_cin.p); b.csize = static_cast<uint16_t*>(c->dz_csize.p);
-		const size_t nk = (size_t)p->n_chunks * LZD_K;
-		b.segL = static_cast<uint32_t*>(c->dz_unit.p); b.segE = b.segL + nk; b.segcnt = b.segE + nk; b.segstop = b.segcnt + nk; b.segoff = b.segstop + nk;
-		b.selcnt = b.segoff + nk; b.seloff = b.selcnt + p->n_chunks;
-		b.stop = b.seloff + p->n_chunks; b.irregular = b.stop + p->n_units + 1u;
-		b.flat = static_cast<u64*>(c->prefix.p);
+		const LzdBufs b = lzd_bufs(c, p);
 		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b); }
 		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
 		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
@@ -777,15 +784,7 @@ static void size_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out
 	default: {                                             // MSCOMP_XPRESS_HUFF
 		const u64* cp = static_cast<const u64*>(p->tokpre.p) + (p->n_units + 1u);
 		u64* ntok = static_cast<u64*>(c->dz_ntok.p);
-		XhcBufs xb = {};
-		{
-			const size_t nu = (size_t)p->n_units + 1, ns = p->xhc_slots;
-			uint8_t* q = static_cast<uint8_t*>(c->dz_xhc.p);
-			xb.res_prod = reinterpret_cast<u64*>(q); q += ns * 8; xb.res_ntok = reinterpret_cast<u64*>(q); q += ns * 8; xb.tok_off = reinterpret_cast<u64*>(q); q += ns * 8;
-			xb.cand_pos = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_end = reinterpret_cast<uint32_t*>(q); q += ns * 4;
-			xb.res_reach = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_state = reinterpret_cast<uint32_t*>(q); q += ns * 4;
-			xb.cand_cnt = reinterpret_cast<uint32_t*>(q); q += nu * 4; xb.mode = reinterpret_cast<uint32_t*>(q);
-		}
+		const XhcBufs xb = xhc_bufs(c, p);
 		static const char* const names[4] = { "xhc_mark_kernel", "xhc_size_kernel", "xhc_chain_kernel", "xhd_size_kernel" };
 		for (int ph = 0; ph < 4; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_huff_size(st, d_in, p->bt, ntok, cp, p->xhc_slots, xb, d_out_len, d_status, ph); }
 		break;
@@ -818,6 +817,154 @@ MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* c, MSCompFormat 
 	if (hipStreamSynchronize(c->stream) != hipSuccess && s == MSCOMP_OK) { s = MSCOMP_ERRNO; }
 	mscomp_amd_plan_destroy(p);
 	return s;
+}
+
+// ---- decompress plans with device tables (include/mscomp_amd.h): created from bounds, tables built on the device by every execution ----
+// The plan holds its bounds and scratch sized for them; p->tables holds what the table pass (devplan.hip) writes each time:
+//   san (4 x n u64: in_off | in_len | out_off | out_cap, zero for a rejected unit) | chunk prefix (u32, n + 1) | token prefix | candidate
+//   prefix (u64, n + 1 each) | reject (u32, n)
+// and bt points into it with n_chunks = the bound (the kernels that are gridded by chunks return past chunk_prefix[n_units]). The paths that
+// need host-chosen tables stay off: no xps_* segments, no lzglobal.hip stage, no Xpress+Huffman token scratch.
+static size_t dev_table_words(uint64_t n) { return 4 * n + (n + 2) / 2 + 1 + 2 * (n + 1) + (n + 1) / 2 + 1; }
+
+MSCompStatus mscomp_amd_plan_create_decompress_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint64_t out_total_max,
+                                                   mscomp_amd_plan** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	// the bounds of the per-unit counts summed over the batch: every accepted unit has in_len <= 0xFFFFF000 and the accepted ones sum to at
+	// most in_total_max / out_total_max; a rejected unit counts as an empty one (one chunk, 64 token slots, 3 candidates)
+	const uint64_t N = n_units, I = in_total_max < N * 0xFFFFF000ull ? in_total_max : N * 0xFFFFF000ull, O = out_total_max;
+	uint64_t chunks = N, toks = 0, cands = 0;
+	if (format == MSCOMP_LZNT1) { chunks = N + I / LZD_SEG; }
+	if (format == MSCOMP_XPRESS_HUFF) { chunks = N + I / XHC_TILE_BYTES; }
+	if (chunks > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
+	if (format != MSCOMP_LZNT1) {
+		const uint64_t by_in = (format == MSCOMP_XPRESS ? 1 : 8) * I + O / 32766u + N;   // (I < 2^45 here for Xpress+Huffman: its chunk bound held)
+		toks = (O < by_in ? O : by_in) + 64 * N;
+		if (toks > (1ull << 46)) { return MSCOMP_MEM_ERROR; }
+	}
+	if (format == MSCOMP_XPRESS_HUFF) {
+		const uint64_t by_out = O / 65536u + 2 * N, by_len = I / 260u + N, most = by_out < by_len ? by_out : by_len;
+		cands = most + most / 4 + 2 * N;
+		if (cands > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
+	}
+	mscomp_amd_plan* p = new (std::nothrow) mscomp_amd_plan();
+	if (!p) { return MSCOMP_MEM_ERROR; }
+	p->ctx = c; p->format = format; p->decompress = true; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
+	p->in_total_max = in_total_max; p->out_total_max = out_total_max; p->total_in = in_total_max; p->xhc_slots = (uint32_t)cands;
+	bool ok = p->tables.reserve(dev_table_words(N) * 8);
+	if (ok && format == MSCOMP_LZNT1) {
+		ok = c->prefix.reserve((chunks + 2) * sizeof(uint64_t)) && c->tile_sums.reserve((chunks / 1024 + 4) * sizeof(uint64_t)) &&
+		     c->dz_cin.reserve(chunks * LZD_SLOTS * 4 + 64) && c->dz_csize.reserve(chunks * LZD_SLOTS * 2 + 64) &&
+		     c->dz_unit.reserve((chunks * (5 * LZD_K + 2) + N * 2 + 8) * 4);
+	}
+	if (ok && format != MSCOMP_LZNT1) { ok = c->dz_tok.reserve(toks * 4 + 256) && c->dz_ntok.reserve((N + 1) * 8); }
+	if (ok && format == MSCOMP_XPRESS_HUFF) { ok = c->dz_xhc.reserve((N + 1) * 8 + cands * (4 * 4 + 3 * 8) + 64); }
+	if (!ok) { (void)hipGetLastError(); p->tables.release(); delete p; return MSCOMP_MEM_ERROR; }
+	u64* san = static_cast<u64*>(p->tables.p);
+	p->bt.in_off = san; p->bt.in_len = san + N; p->bt.out_off = san + 2 * N; p->bt.out_cap = san + 3 * N;
+	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(san + 4 * N);
+	p->bt.n_units = p->n_units; p->bt.n_chunks = p->n_chunks;
+	*out = p;
+	return MSCOMP_OK;
+}
+
+static void dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint8_t* d_out,
+                       const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+{
+	mscomp_amd_ctx* c = p->ctx;
+	hipStream_t st = c->stream;
+	const uint32_t n = p->n_units;
+	u64* san = static_cast<u64*>(p->tables.p);
+	uint32_t* chunk_prefix = reinterpret_cast<uint32_t*>(san + 4 * (size_t)n);
+	u64* tp = san + 4 * (size_t)n + (n + 2u) / 2 + 1;                 // token prefix, then the candidate prefix
+	uint32_t* reject = reinterpret_cast<uint32_t*>(tp + 2 * ((size_t)n + 1));
+	{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_tables(st, (int)p->format, n, p->in_total_max, p->out_total_max, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, tp, reject); }
+	const u64 no_lzg = ~(u64)0;
+	switch (p->format) {
+	case MSCOMP_LZNT1: {
+		const LzdBufs b = lzd_bufs(c, p);
+		launch_dev_zero(st, b.selcnt, p->n_chunks);                     // segments past the real count add nothing to the scan
+		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b, true); }
+		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
+		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
+		{ KernelTimer t(c, "lzd_chunk_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 0); }
+		{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status); }
+		{ KernelTimer t(c, "lzd_replace_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 1); }
+		break;
+	}
+	case MSCOMP_XPRESS: {                                       // the flag-word token path without segments (g_xpd_mode 2)
+		uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
+		static const char* const names[3] = {"xpt_parse_kernel", "lz_copy_kernel", "lz_copy_block_kernel"};
+		const XpsTables x = {};
+		for (int ph = 0; ph < 3; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, ph, no_lzg, x); }
+		break;
+	}
+	default: {                                                  // MSCOMP_XPRESS_HUFF, without token scratch (the accepted chunks are walked twice)
+		uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
+		const XhcBufs xb = xhc_bufs(c, p);
+		static const char* const names[6] = { "xhc_mark_kernel", "xhc_parse_kernel", "xhc_chain_kernel", "xhc_parse2_kernel", "xhd_parse_kernel", "lz_copy_kernel" };
+		for (int ph = 0; ph < 6; ++ph) {
+			KernelTimer t(c, names[ph]);
+			launch_xpress_huff_decompress(st, d_in, p->bt, tp, tok, ntok, tp + (n + 1u), p->xhc_slots, xb, d_out, d_out_len, d_status, ph, no_lzg, true);
+		}
+		break;
+	}
+	}
+	{ KernelTimer t(c, "dv_reject_kernel"); launch_dev_reject(st, reject, n, d_out_len, d_status); }
+}
+
+MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                         uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!p || !p->dev) { return MSCOMP_ARG_ERROR; }
+	if (p->n_units && (!d_in_off || !d_in_len || !d_out_off || !d_out_cap || !d_out_len || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if ((p->in_total_max && !d_in) || (p->out_total_max && !d_out)) { return MSCOMP_ARG_ERROR; }
+	if (p->n_units == 0) { return MSCOMP_OK; }
+	mscomp_amd_ctx* c = p->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	// While the caller captures the ctx stream, plain launches go into the caller's graph. Otherwise, from the second execution on, the
+	// launches are replayed as the plan's own graph (as plan_execute does), captured again whenever a pointer, the scratch or a kernel
+	// switch moved. A stream whose capture state cannot be read counts as captured.
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
+	static const bool no_graph = getenv("MSCOMP_AMD_NO_GRAPH") != nullptr;
+	if (cs == hipStreamCaptureStatusNone && !no_graph && !c->profiling && ++p->executions >= 2) {
+		const void* args[9] = { d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, nullptr };
+		const uint64_t mode_now = g_mode_epoch.load(std::memory_order_acquire);
+		const bool same = p->gexec && p->g_epoch == c->epoch && p->g_mode == mode_now && memcmp(p->g_args, args, sizeof args) == 0;
+		if (!same) {
+			if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
+			hipGraph_t graph = nullptr;
+			if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+				dev_launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status);
+				const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
+				if (ee == hipSuccess && graph && hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0) == hipSuccess) {
+					p->g_epoch = c->epoch; p->g_mode = mode_now; memcpy(p->g_args, args, sizeof args);
+				} else { p->gexec = nullptr; }
+				if (graph) { (void)hipGraphDestroy(graph); }
+			}
+			(void)hipGetLastError();
+		}
+		if (p->gexec) { return hipGraphLaunch(p->gexec, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
+	}
+	dev_launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status);
+	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
+}
+
+MSCompStatus mscomp_amd_layout_dev(mscomp_amd_ctx* c, size_t n_units, const uint64_t* d_cap, uint64_t align, uint64_t* d_off)
+{
+	if (!c || !d_off || (n_units && !d_cap) || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	launch_layout_dev(c->stream, d_cap, (uint32_t)n_units, align, d_off);
+	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
 // Stage-level test hook: per-position (len-3 capped at 45, offset) of ONE unit as found by the HIP match finder.

@@ -63,6 +63,9 @@ __device__ __forceinline__ uint32_t lzd_step(uint32_t& pos, uint32_t n, RD rd, u
 
 // per segment g and chain k < LZD_K: segL (landing), segE (first header of the next segment, or LZD_ENDED), segcnt (headers inside the segment),
 // segstop (what ended the chain | last byte << 8), segoff (where its header offsets start in cin[g * LZD_SLOTS ...]; LZD_NONE: not recorded)
+// DEV (plans whose tables are built on the device, mscomp_amd_plan_create_decompress_dev): the grid is sized for the plan's bound, and the blocks
+// past the batch's real segment count (chunk_prefix[n_units], written by the table pass) return at once.
+template <bool DEV = false>
 __global__ __launch_bounds__(LZD_THREADS) void lzd_seg_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, uint32_t* __restrict__ cin,
                                                             uint32_t* __restrict__ segL, uint32_t* __restrict__ segE,
                                                             uint32_t* __restrict__ segcnt, uint32_t* __restrict__ segstop, uint32_t* __restrict__ segoff)
@@ -70,6 +73,7 @@ __global__ __launch_bounds__(LZD_THREADS) void lzd_seg_kernel(const uint8_t* __r
 	extern __shared__ __attribute__((aligned(16))) uint8_t s_win[];
 	__shared__ uint32_t s_min, s_land[LZD_K], s_cnt[LZD_K];
 	const uint32_t tid = threadIdx.x, g = blockIdx.x;
+	if (DEV && g >= bt.chunk_prefix[bt.n_units]) { return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, g), s = g - bt.chunk_prefix[u];
 	const uint32_t n = (uint32_t)bt.in_len[u];
 	const uint8_t* base = d_in + bt.in_off[u];
@@ -532,13 +536,15 @@ __global__ __launch_bounds__(256) void lzd_finalize_kernel(BatchTables bt, const
 
 __global__ void lzd_clear_kernel(uint32_t* p) { *p = 0; }
 
-void launch_lzd_segments(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b)
+void launch_lzd_segments(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b, bool dev)
 {
 	if (bt.n_units == 0) { return; }
-	static PerDeviceOnce attr;
-	if (attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lzd_seg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LZD_LDS); attr.done(); }
+	static PerDeviceOnce attr, attr_dev;
+	if (!dev && attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lzd_seg_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LZD_LDS); attr.done(); }
+	if (dev && attr_dev.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lzd_seg_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LZD_LDS); attr_dev.done(); }
 	hipLaunchKernelGGL(lzd_clear_kernel, dim3(1), dim3(1), 0, st, b.irregular + bt.n_units);
-	hipLaunchKernelGGL(lzd_seg_kernel, dim3(bt.n_chunks), dim3(LZD_THREADS), LZD_LDS, st, d_in, bt, b.cin, b.segL, b.segE, b.segcnt, b.segstop, b.segoff);
+	if (dev) { hipLaunchKernelGGL(lzd_seg_kernel<true>, dim3(bt.n_chunks), dim3(LZD_THREADS), LZD_LDS, st, d_in, bt, b.cin, b.segL, b.segE, b.segcnt, b.segstop, b.segoff); }
+	else { hipLaunchKernelGGL(lzd_seg_kernel<false>, dim3(bt.n_chunks), dim3(LZD_THREADS), LZD_LDS, st, d_in, bt, b.cin, b.segL, b.segE, b.segcnt, b.segstop, b.segoff); }
 }
 void launch_lzd_verify(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b)
 {
@@ -1249,11 +1255,14 @@ __global__ __launch_bounds__(64) void xhd_parse_kernel(const uint8_t* __restrict
 // a broken chain, an error inside a chunk, output beyond the capacity) sends the buffer to the serial walk, which reports the reference's status.
 #define XHC_TILE 16384u                 // input bytes per block of xhc_mark_kernel
 #define XHC_MAXC 8192u                  // candidates of a buffer the chain check can hold
+// DEV: as lzd_seg_kernel<true>, the tiles past the batch's real count return at once
+template <bool DEV = false>
 __global__ __launch_bounds__(256) void xhc_mark_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, const u64* __restrict__ cand_prefix, XhcBufs xb)
 {
 	__shared__ uint8_t s_b[XHC_TILE + 256u + 16u];
 	__shared__ uint32_t s_k[256];
 	const uint32_t tile = blockIdx.x, tid = threadIdx.x;
+	if (DEV && tile >= bt.chunk_prefix[bt.n_units]) { return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, tile), t = tile - bt.chunk_prefix[u];
 	const uint32_t n = (uint32_t)bt.in_len[u];
 	const uint8_t* __restrict__ src = d_in + bt.in_off[u];
@@ -1906,12 +1915,18 @@ __global__ __launch_bounds__(LZB_NT) void lz_copy_block_kernel(BatchTables bt, c
 
 void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
                                    const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb,
-                                   uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap)
+                                   uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, bool dev)
 {
 	if (bt.n_units == 0) { return; }
 	switch (phase) {
-	case 0: (void)hipMemsetAsync(xb.cand_cnt, 0, ((size_t)bt.n_units + 1) * sizeof(uint32_t), st);
-	        hipLaunchKernelGGL(xhc_mark_kernel, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, cand_prefix, xb); break;
+	case 0: if (dev) {                                                   // (a kernel, not a memset: kernels.h launch_dev_zero)
+	            launch_dev_zero(st, xb.cand_cnt, bt.n_units + 1u);
+	            hipLaunchKernelGGL(xhc_mark_kernel<true>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, cand_prefix, xb);
+	        } else {
+	            (void)hipMemsetAsync(xb.cand_cnt, 0, ((size_t)bt.n_units + 1) * sizeof(uint32_t), st);
+	            hipLaunchKernelGGL(xhc_mark_kernel<false>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, cand_prefix, xb);
+	        }
+	        break;
 	case 1: hipLaunchKernelGGL(xhc_parse_kernel<1>, dim3(n_slots), dim3(64), 0, st, d_in, bt, tok_prefix, cand_prefix, xb, tok); break;
 	case 2: hipLaunchKernelGGL(xhc_chain_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, cand_prefix, xb, ntok, d_out_len, d_status); break;
 	case 3: if (xb.scr_prefix) { hipLaunchKernelGGL(xhc_gather_kernel, dim3(n_slots), dim3(256), 0, st, bt, tok_prefix, cand_prefix, xb, tok); }

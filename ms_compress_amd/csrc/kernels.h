@@ -75,7 +75,8 @@ void launch_xh_encode(hipStream_t st, const uint8_t* d_in, const BatchTables& bt
 #define LZD_K     8u         // speculated chains kept per segment
 struct LzdBufs { uint32_t* cin; uint16_t* csize; uint32_t* segL; uint32_t* segE; uint32_t* segcnt; uint32_t* segstop; uint32_t* segoff;   /* LZD_K per segment */
                  uint32_t* selcnt; uint32_t* seloff; uint32_t* stop; uint32_t* irregular; u64* flat; };
-void launch_lzd_segments(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b);
+// dev: a plan with device-built tables (bt.n_chunks is its bound; the blocks past chunk_prefix[n_units] return at once)
+void launch_lzd_segments(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b, bool dev = false);
 uint32_t lzd_read_walked();
 void launch_lzd_verify(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b);
 // exact: 0 decode every chunk, 1 decode the irregular units' chunks again to their places, 2 size every chunk only (the size query; d_out unused)
@@ -116,7 +117,7 @@ struct XhcBufs { uint32_t* cand_cnt; uint32_t* mode; uint32_t* cand_pos; uint32_
 #define XHC_SCR 65600u                                    // a candidate gives up to 65536 tokens before its 65536th byte
 void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
                                    const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb,
-                                   uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap);
+                                   uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, bool dev = false);   // dev: as launch_lzd_segments
 // the size query: phases 0 mark, 1 measure every candidate (no tokens written, chunk 0 included), 2 chain check, 3 serial walk without tokens
 void launch_xpress_huff_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, const u64* cand_prefix, uint32_t n_slots,
                              const XhcBufs& xb, u64* d_out_len, int32_t* d_status, int phase);
@@ -143,6 +144,20 @@ struct LzgTables {
 // phase 0 = directory (3 kernels), 1 = lzg_expand_kernel, 2 = the pointer passes
 void launch_lz_copy_global(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok,
                            const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, int phase);
+
+// ---- plans with device-built tables (devplan.hip) ----
+// One block walks the units in tiles of 1024: per unit, the checks of mscomp_amd_plan_execute_dev (in_len <= 0xFFFFF000, running totals of
+// in_len / out_cap within the bounds), the unit's table row (in_off | in_len | out_off | out_cap; all zero for a rejected unit) in san
+// (4 x n), reject[u], and the prefix arrays of the chunk counts (u32, n + 1 entries), the token slots and the candidate slots (u64, n + 1
+// each, the candidate prefix right behind the token prefix) with the formulas plan_create_impl uses on the host.
+void launch_dev_tables(hipStream_t st, int format, uint32_t n, u64 in_total_max, u64 out_total_max, const u64* in_off, const u64* in_len,
+                       const u64* out_off, const u64* out_cap, u64* san, uint32_t* chunk_prefix, u64* tok_prefix, uint32_t* reject);
+// p[0..n) = 0 as a kernel (a dev plan's launches hold no memset: they go into graphs the caller captures)
+void launch_dev_zero(hipStream_t st, uint32_t* p, uint32_t n);
+// units with reject[u]: status MSCOMP_ARG_ERROR, length 0 (after the decoders, which saw them as empty units with no room)
+void launch_dev_reject(hipStream_t st, const uint32_t* reject, uint32_t n, u64* d_out_len, int32_t* d_status);
+// off[0..n] = exclusive running sum of cap[i] rounded up to align (saturating at 2^64 - 1)
+void launch_layout_dev(hipStream_t st, const u64* cap, uint32_t n, u64 align, u64* off);
 
 // ---- utilities (util.hip) ----
 // prefix[0..n] = exclusive scan of sizes[0..n) as u64 (prefix[n] = total). block_sums: scratch of ceil(n/1024)+1 u64.
