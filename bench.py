@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- input MB/s of the MI355X-native MS-XCA compress path (BASELINE.json metric), 1 to N GPUs.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N > 1 and no WORLD_SIZE in the environment the script starts its N ranks itself (torch.distributed.run, one
 process per GPU, rendezvous on 127.0.0.1); launched BY torch.distributed.run it is one of the ranks. A world size other
@@ -15,15 +15,18 @@ resident in HBM. value = bytes of the whole job x K / max-over-ranks time of the
 both sides). After the timed region every rank checks what its first replica of the 12 files compressed to against the
 digests of the REAL reference (tests/golden/corpus_full.json) -- `parity_checked` -- and refuses to print a number otherwise. The headline codec is LZNT1 (one unit per file, 4 KiB chunks inside: 827 936 chunks); Xpress (51 824
 independent 64 KiB units) and Xpress+Huffman (one unit per file, 64 KiB chunks with the previous chunk as window) run on
-the same batch right after and are reported under extra.config5, reduced over the ranks the same way.
+the same batch right after with `--full` and are reported under extra.config5, reduced over the ranks the same way.
 
-Rank 0 prints ONE SHORT JSON line (< 4 KB, scalars only; `short_line` below): the contract's keys, `config` (the workload and, per codec, MB/s,
-ms per step, roofline fraction, parity verdict, CPU figures, the one-rank-of-8 ratio as flat keys), `roofline` (dominant kernel: algorithmic bytes
-per launch / HIP-event kernel time vs the 8 TB/s HBM peak; `traffic` from the committed PMC passes of the same command) and, at N = 1, `cpu_baseline`
-(the reference's own CPU encoder, oracle/_ref, on this host's cores: the leg's unit list in one pass, the load-balanced figure, one thread). The WHOLE
-document -- BASELINE configs[1..3] one by one with their host-pointer end-to-end figures, what one rank of an 8-GPU run holds, the suffix-array
-flavour, the decompression legs, every kernel's time and the counter-derived `secondary` block of every roofline -- is written to
-bench_extra.json beside this script (and to gpurun_out/ when that exists); `--full` prints it instead of the short line.
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, the parity gate, `--dump-outputs`, and rank 0 prints
+ONE SHORT JSON line (< 4 KB, scalars only; `short_line` below): the contract's keys, `config` (the workload and the headline codec's MB/s, ms per
+step, roofline fraction and parity verdict as flat keys) and `roofline` (dominant kernel of the timed steps: algorithmic bytes per launch /
+HIP-event kernel time vs the 8 TB/s HBM peak; `traffic` from the committed PMC passes of the same command). Everything else runs with `--full`
+only (`--config5-only`, `--real-files` and `--data-dir` narrow or widen it and imply it): the other two codecs, whose MB/s, ms per step, roofline
+fraction, parity verdict, CPU figures and one-rank-of-8 ratio join `config`, and, at N = 1, `cpu_baseline` (the reference's own CPU encoder,
+oracle/_ref, on this host's cores: the leg's unit list in one pass, the load-balanced figure, one thread). The WHOLE document of a `--full` run --
+BASELINE configs[1..3] one by one with their host-pointer end-to-end figures, what one rank of an 8-GPU run holds, the suffix-array flavour, the
+decompression legs, every kernel's time and the counter-derived `secondary` block of every roofline -- is written to
+bench_extra.json beside this script.
 """
 import argparse
 import json
@@ -630,18 +633,21 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--codec", default="lznt1", choices=["lznt1", "xpress", "xpress_huff"], help="headline codec")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
-    ap.add_argument("--no-extra", action="store_true", help="headline leg only")
-    ap.add_argument("--config5-only", action="store_true", help="the three codecs over BASELINE configs[4], none of the other legs")
-    ap.add_argument("--full", action="store_true", help="print the whole document (every leg, every kernel) instead of the short line; it is written to bench_extra.json either way")
+    ap.add_argument("--full", action="store_true", help="run every leg, not only the headline: the other two codecs over the same batch, the CPU baselines, "
+                    "BASELINE configs[1..3], one rank of an 8-GPU run, the suffix-array flavour, the decompression legs; the whole document goes to bench_extra.json")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the cpu_baseline legs")
+    ap.add_argument("--no-extra", action="store_true", help="--full with the headline leg only (and its cpu_baseline)")
+    ap.add_argument("--config5-only", action="store_true", help="the three codecs over BASELINE configs[4], none of the other legs (implies --full)")
     ap.add_argument("--real-files", type=int, nargs="?", const=1100, default=0, metavar="MB", help="also run the three codecs over REAL files of this box (tools/real_corpus.py; "
-                    "~1.1 GB by default, read from disk: minutes on a fresh box) and compare every unit with the reference's CPU encoder; results in bench_extra.json")
-    ap.add_argument("--data-dir", default=None, help="the real-files leg over every file of this directory instead")
+                    "~1.1 GB by default, read from disk: minutes on a fresh box) and compare every unit with the reference's CPU encoder; results in bench_extra.json "
+                    "(implies --full)")
+    ap.add_argument("--data-dir", default=None, help="the real-files leg over every file of this directory instead (implies --full)")
     ap.add_argument("--oversubscribe", action="store_true", help="TEST ONLY: let the N ranks share the visible GPUs (gloo for the timing reduction); "
                     "exercises the sharded multi-rank path on a 1-GPU box, the line is marked and is not an N-GPU measurement")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the headline leg's last step computed to "
                     "DIR/<name>.npy (float32/float64; per-unit status, length and checksum, the bytes of a seeded sample of units)")
     args = ap.parse_args()
+    args.full = args.full or args.config5_only or bool(args.real_files) or bool(args.data_dir)
     want = max(1, args.gpus)
     if want > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(want)
@@ -682,10 +688,10 @@ def main():
     }
     if args.oversubscribe:
         res["oversubscribed"] = "TEST RUN: %d ranks shared %d GPU(s); not an %d-GPU measurement" % (world, torch.cuda.device_count(), world)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         res["cpu_baseline"] = cpu_baseline(fmt, cor)
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         c5 = {}
         for codec in ("lznt1", "xpress", "xpress_huff"):
             if codec != args.codec:
@@ -694,7 +700,7 @@ def main():
                 if rank == 0 and world == 1 and not args.no_cpu:
                     c5[codec]["cpu_baseline"] = cpu_baseline(m.FORMATS[codec], cor)
         extra["config5"] = c5
-    if world == 1 and not args.no_extra and not args.config5_only:
+    if args.full and world == 1 and not args.no_extra and not args.config5_only:
         single = {}
         for key, wl in (("lznt1", "mozilla"), ("xpress", "silesia_units64k"), ("xpress_huff", "silesia_files"), ("xpress_huff_unit_mode", "silesia_units64k")):
             codec = "xpress_huff" if key.startswith("xpress_huff") else key      # Xpress+Huffman in file mode AND in unit mode (every 64 KiB unit independent, each with EOS)
@@ -759,8 +765,8 @@ def main():
         extra["decompress_files"] = decf
     if world == 1 and (args.real_files or args.data_dir):
         extra["real_files"] = real_files_leg(m, ctx, sharding, args.real_files or 1100, args.data_dir, cpu=not args.no_cpu)
-    # The line the driver parses: SHORT (< 4 KB), scalars only, no sentences. Everything else -- the other legs, every kernel's time,
-    # the secondary-bound counters -- goes to bench_extra.json beside this script (and gpurun_out/ when that exists, so that it travels back).
+    # The line a benchmark record parses: SHORT (< 4 KB), scalars only, no sentences. Everything else a --full run measures -- the other legs, every
+    # kernel's time, the secondary-bound counters -- goes to bench_extra.json beside this script.
     legs = {args.codec: head}
     legs.update(extra.get("config5", {}))
     for codec, leg in legs.items():
@@ -783,16 +789,13 @@ def main():
         full["extra"] = extra
     line = short_line(res)
     if rank == 0:
-        for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
-            if os.path.isdir(d):
-                try:
-                    json.dump(full, open(os.path.join(d, "bench_extra.json"), "w"), indent=1)
-                except OSError:
-                    pass
         if args.full:
-            line = full
+            try:
+                json.dump(full, open(os.path.join(ROOT, "bench_extra.json"), "w"), indent=1)
+            except OSError:
+                pass
         text = json.dumps(line, separators=(",", ":"))
-        if not args.full and len(text) >= 4000:            # never print a line the driver cannot keep: shed the optional parts instead (bench_extra.json has them)
+        if len(text) >= 4000:            # never print a line a benchmark record cannot keep: shed the optional parts instead (bench_extra.json has them)
             for k in [k for k in line["config"] if k.endswith(("_cpu_MB_per_s", "_cpu_balanced_MB_per_s", "_one_rank_of_8_rate_vs_whole_job", "_ms_per_step", "_real_files_MB_per_s"))]:
                 del line["config"][k]
             if "cpu_baseline" in line:

@@ -31,10 +31,10 @@ def _bench(args, env=None, timeout=900):
 
 
 def test_the_drivers_own_command_prints_one_short_parseable_line():
-    """EXACTLY what the driver runs at N = 1 (all legs, CPU baselines included; only K and W smaller): the last stdout line must parse, stay
-    under 4 KiB (the driver's record keeps the last 8 KB of stdout: round 4's 20 KB line was lost to it) and carry the headline objects;
+    """EXACTLY the --full run made once per change at N = 1 (all legs, CPU baselines included; only K and W smaller): the last stdout line must parse,
+    stay under 4 KiB (a benchmark record keeps the last 8 KB of stdout: round 4's 20 KB line was lost to it) and carry the headline objects;
     the long document goes to bench_extra.json."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"], cwd=ROOT, capture_output=True, text=True, timeout=1500)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     out = r.stdout.rstrip("\n").splitlines()
     assert len(r.stdout) < 8192 and len(out[-1]) < 4096, (len(r.stdout), len(out[-1]))
@@ -60,6 +60,22 @@ def test_the_drivers_own_command_prints_one_short_parseable_line():
     no_prose(line)
     full = json.load(open(os.path.join(ROOT, "bench_extra.json")))
     assert full["value"] == line["value"] and "single_gpu" in full["extra"] and "decompress" in full["extra"]
+
+
+def test_a_plain_run_times_the_headline_leg_alone():
+    """The plain command (no --full): one short line with the contract's keys and the headline leg through the parity gate, and nothing else --
+    no other codec, no CPU baseline, no bench_extra.json."""
+    extra = os.path.join(ROOT, "bench_extra.json")
+    before = os.stat(extra).st_mtime_ns if os.path.exists(extra) else None
+    line = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1"])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert key in line, key
+    assert line["metric"] == "input MB/s (lznt1 compress, bit-exact with the reference CPU encoder)" and line["unit"] == "MB/s" and line["dtype"] == "u8"
+    assert line["higher_is_better"] is True and line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["config"]["bytes_per_step"] == 3391017280 and 0 < line["roofline"]["frac"] < 1
+    assert line["parity_checked"] == {"lznt1": True} and "cpu_baseline" not in line
+    assert not [k for k in line["config"] if k.startswith("xpress")], line["config"]
+    assert (os.stat(extra).st_mtime_ns if os.path.exists(extra) else None) == before
 
 
 def test_dump_outputs_writes_what_the_last_step_computed(tmp_path):

@@ -2,9 +2,9 @@
 # Run on the GPU box (through gpurun): everything profiles/<tag>_* is made of. Output: gpurun_out/prof_<tag>/, condensed by
 # tools/update_profiles.py into profiles/.
 #   usage: bash tools/collect_profiles.sh r02 [quick]
-#  1. (last, so that it carries the counters of this very run) the default bench line;
-#  2. rocprofv3 --kernel-trace --stats of the HEADLINE command (bench.py --no-extra: every launch of the dominant kernel is the
-#     headline workload, so its average duration is comparable with the HIP-event figure of the line) and of the full default command;
+#  1. (last, so that it carries the counters of this very run) the bench line of bench.py --full;
+#  2. rocprofv3 --kernel-trace --stats of the HEADLINE command (bench.py without --full: every launch of the dominant kernel is the
+#     headline workload, so its average duration is comparable with the HIP-event figure of the line) and of the --full command;
 #  3. HBM traffic: separate --pmc FETCH_SIZE / --pmc WRITE_SIZE passes (TCC counters do not fit one pass), per leg (tools/gpu_leg.py);
 #  4. SQ counters of the configs[4] legs and the single-GPU legs in two passes of 8 (issue / wait shares, instruction mix, LDS pipe, conflicts).
 set -u
@@ -46,9 +46,9 @@ python tools/gpu_oneshot.py > $D/oneshot_host_pointers.txt 2>&1
 [ -x tools/dev/issue_peak2 ] && tools/dev/issue_peak2 > $D/issue_peak2.txt 2>&1
 # the counter summaries go into profiles/ of THIS copy of the repository first: the bench line below attaches them (roofline.traffic / .secondary)
 python tools/update_profiles.py $D $TAG > $D/update_on_box.log 2>&1
-python bench.py 2> $D/bench.err | tail -1 > $D/bench.json
+python bench.py --full 2> $D/bench.err | tail -1 > $D/bench.json
 cp bench_extra.json $D/bench_extra.json 2>/dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o kt_head -- python bench.py --no-extra --no-cpu --steps 5 --warmup 1 2> $D/kt_head.err | tail -1 > $D/bench_headline_under_rocprof.json
-[ -n "$QUICK" ] || rocprofv3 --kernel-trace --stats --output-format csv -d $D -o kt_full -- python bench.py --no-cpu --steps 4 --warmup 1 2> $D/kt_full.err | tail -1 > $D/bench_full_under_rocprof.json
+[ -n "$QUICK" ] || rocprofv3 --kernel-trace --stats --output-format csv -d $D -o kt_full -- python bench.py --full --no-cpu --steps 4 --warmup 1 2> $D/kt_full.err | tail -1 > $D/bench_full_under_rocprof.json
 find $D -name "*.db" -delete; find $D -name "*.csv" | wc -l
 du -sh $D

@@ -39,7 +39,7 @@ if os.path.exists(os.path.join(src, "kt_head_kernel_stats.csv")):
                       "rocprofv3 --kernel-trace --stats -- python bench.py --no-extra --no-cpu --steps 5 --warmup 1   (the headline leg alone: LZNT1 over BASELINE configs[4])")
     if os.path.exists(os.path.join(src, "kt_full_kernel_stats.csv")):
         txt += "\n" + stats_table(os.path.join(src, "kt_full_kernel_stats.csv"),
-                                  "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu --steps 4 --warmup 1   (all legs, compressors and decompressors: a kernel's launches mix workloads)")
+                                  "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu --steps 4 --warmup 1   (all legs, compressors and decompressors: a kernel's launches mix workloads)")
     for codec in ("lznt1", "xpress", "xpress_huff"):
         f = os.path.join(src, "kt_config5_%s_kernel_stats.csv" % codec)
         if os.path.exists(f):
