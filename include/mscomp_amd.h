@@ -311,6 +311,11 @@ void         mscomp_amd_debug_set_lznt1(int mode);
  * whose speculation held nothing usable is walked again by one lane. Returns how many segments that happened to since the last call
  * (synchronizes the stream). */
 uint32_t     mscomp_amd_debug_lzd_walked(mscomp_amd_ctx* ctx);
+/* Test hook: which path the last decompress or size execution on ctx took, per unit (synchronizes the stream). Xpress+Huffman: one word per
+ * unit, 2 = its chunks were decoded in parallel from speculated chunk starts, 1 = the serial walk. Xpress: one word per unit of at least
+ * 512 KiB input, in unit order, 2 = walked by segments, 0 = the one-wave walk; none when the plan does not take the segment path. LZNT1:
+ * none. Writes min(count, cap) words to out and returns the count, -1 on error. */
+int          mscomp_amd_debug_decode_modes(mscomp_amd_ctx* ctx, uint32_t* out, size_t cap);
 /* Hardware self-check: the LZNT1 bucket sort and the Xpress chain links rely on gfx950 serving the returning
  * same-address LDS atomics of one wave instruction in lane order. Returns the number of lanes (over blocks x rounds x 64
  * lanes x {add, exchange}, keys drawn from nkeys <= 2048 values) that were served out of order: 0 on gfx950;

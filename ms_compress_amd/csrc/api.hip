@@ -73,6 +73,7 @@ struct mscomp_amd_ctx {
 	std::vector<DevBuf> table_pool;                    // table buffers of destroyed plans, reused by the next plan (hipFree waits for the whole device: it would stall pipelines that create a plan per batch)
 	uint64_t epoch = 1;                                // bumped when one of the buffers above moves (captured graphs are stale then)
 	int lznt1_sa = -1;                                 // LZNT1 dictionary flavour of the plans this context creates: -1 = the process default at plan creation, 0 / 1 = set for this context
+	const uint32_t* dbg_mode = nullptr; uint32_t dbg_mode_n = 0;   // where the last decompress / size execution left its per-unit path verdicts (mscomp_amd_debug_decode_modes)
 	bool profiling = false;
 	std::vector<ProfRec> recs;
 	std::vector<hipEvent_t> free_events;
@@ -567,6 +568,19 @@ static XhcBufs xhc_bufs(mscomp_amd_ctx* c, const mscomp_amd_plan* p)
 	return xb;
 }
 
+// the per-unit path verdicts an execution of p leaves in the ctx scratch: Xpress+Huffman, XHC_SPEC / XHC_SERIAL for every unit (xhc_chain_kernel);
+// Xpress, the segment walk's mode for every unit with XPS_MIN_IN input bytes or more (2 = done by segments, 0 = the one-wave walk), none when
+// the plan does not take that path
+static void note_modes(mscomp_amd_plan* p)
+{
+	mscomp_amd_ctx* c = p->ctx;
+	c->dbg_mode = nullptr; c->dbg_mode_n = 0;
+	if (p->format == MSCOMP_XPRESS_HUFF && p->n_units) { c->dbg_mode = xhc_bufs(c, p).mode; c->dbg_mode_n = p->n_units; }
+	if (p->format == MSCOMP_XPRESS && p->xps_big && (p->sizing || g_xpd_mode.load(std::memory_order_relaxed) == 0)) {
+		c->dbg_mode = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(c->xps_buf.p) + (size_t)p->xps_seg * XPS_SEG_BYTES); c->dbg_mode_n = p->xps_big;
+	}
+}
+
 static MSCompStatus plan_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
 {
 	mscomp_amd_ctx* c = p->ctx;
@@ -679,6 +693,7 @@ MSCompStatus mscomp_amd_plan_execute(mscomp_amd_plan* p, const uint8_t* d_in, ui
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	static const bool no_graph = getenv("MSCOMP_AMD_NO_GRAPH") != nullptr;
+	if (p->decompress) { note_modes(p); }
 	++p->executions;
 	// A plan that is executed repeatedly replays its 4-9 launches as one hipGraph (the gaps between the launches are
 	// ~3 % of an LZNT1 pass). Not while profiling (the per-kernel events are not part of the graph), not on the first
@@ -801,7 +816,7 @@ MSCompStatus mscomp_amd_plan_execute_size(mscomp_amd_plan* p, const uint8_t* d_i
 	mscomp_amd_ctx* c = p->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (p->n_units) { size_launch(p, d_in, d_out_len, d_need, d_status); }
+	if (p->n_units) { note_modes(p); size_launch(p, d_in, d_out_len, d_need, d_status); }
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
@@ -929,6 +944,7 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in
 	mscomp_amd_ctx* c = p->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
+	note_modes(p);
 	// While the caller captures the ctx stream, plain launches go into the caller's graph. Otherwise, from the second execution on, the
 	// launches are replayed as the plan's own graph (as plan_execute does), captured again whenever a pointer, the scratch or a kernel
 	// switch moved. A stream whose capture state cannot be read counts as captured.
@@ -1078,6 +1094,15 @@ int mscomp_amd_debug_lzg_open(mscomp_amd_ctx* c, uint64_t words, uint32_t* out)
 	DeviceGuard g(c->device);
 	if (!g.ok || hipStreamSynchronize(c->stream) != hipSuccess) { return -1; }
 	return hipMemcpy(out, static_cast<uint32_t*>(c->lzg_words.p) + words, LZG_PASSES * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+int mscomp_amd_debug_decode_modes(mscomp_amd_ctx* c, uint32_t* out, size_t cap)
+{	// test hook: the per-unit path verdicts of the last decompress or size execution on c (note_modes)
+	if (!c || (cap && !out)) { return -1; }
+	DeviceGuard g(c->device);
+	if (!g.ok || hipStreamSynchronize(c->stream) != hipSuccess) { return -1; }
+	const uint32_t n = c->dbg_mode_n;
+	if (n && cap && hipMemcpy(out, c->dbg_mode, (n < cap ? n : cap) * 4, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	return (int)n;
 }
 void mscomp_amd_debug_set_xpress_decoder(int mode) { if (!test_hooks_on()) { return; } g_xpd_mode.store(mode, std::memory_order_relaxed); g_mode_epoch.fetch_add(1, std::memory_order_acq_rel); }
 void mscomp_amd_debug_set_finder(int mode) { if (!test_hooks_on()) { return; } g_finder_mode.store(mode, std::memory_order_relaxed); g_mode_epoch.fetch_add(1, std::memory_order_acq_rel); }

@@ -20,7 +20,7 @@ ref, ref_sa = loader.load_ref(), loader.load_ref_sa()
 assert ref is not None and ref_sa is not None, "oracle/_ref missing: run make -C oracle"
 
 # 1. the CPU tests: every answer they ask the live reference for is kept
-rc = pytest.main(["-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_vs_ref.py"),
+rc = pytest.main(["-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_vs_ref.py"), os.path.join(ROOT, "tests", "test_foreign_streams.py"),
                   os.path.join(ROOT, "tests", "test_abi.py") + "::test_xpress_deflate_entry_points_answer_like_the_reference"])
 assert rc == 0, "the CPU tests against the live reference failed: nothing recorded"
 
@@ -39,6 +39,10 @@ data = cases.mixed_buffer()
 for f in (2, 3, 4):
     bad = test_gpu_decompress.corrupted(f, loader.oracle_compress(f, data)[1])
     refanswers.answer(("decompress", f, bad, len(data)), lambda: loader.ref_decompress(f, bad, len(data)))
+import test_foreign_streams as tf          # (the GPU side of test_gpu_foreign_streams.py asks the same family questions)
+for f in (2, 3, 4):
+    fam, _ = tf.family(f)
+    tf.reference_answer(loader, f, fam, tf.checker_results(loader, f, fam)[1])
 refanswers.record()
 print("%d answers recorded in %s" % (len(refanswers.live_answers), refanswers.PATH))
 
