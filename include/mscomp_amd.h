@@ -250,6 +250,36 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* plan, const uint8_t* d
  * leaving the GPU. d_cap and d_off are device arrays (uint64). Asynchronous; allocates nothing. */
 MSCompStatus mscomp_amd_layout_dev(mscomp_amd_ctx* ctx, size_t n_units, const uint64_t* d_cap, uint64_t align, uint64_t* d_off);
 
+/* Compress plans with device tables: the compressing half of the same pipeline. Created once from bounds and executed with
+ * mscomp_amd_plan_execute_dev (the same nine arguments) on unit tables that GPU work has written -- the d_out_len of a decompress dev plan, say,
+ * with the offsets of mscomp_amd_plan_layout_dev. n_units is fixed when the plan is created. Two caps apply to the units:
+ *   in_len of one unit <= in_unit_max
+ *   total in_len       <= in_total_max   (summed in unit order)
+ * Compression scratch depends on the input alone: there is no output bound.
+ *   Per-unit results: for every unit that passes the checks below, d_status[i] and d_out_len[i], and the bytes on MSCOMP_OK, are exactly those
+ *                 of a compress plan (mscomp_amd_plan_create) with the same values: MSCOMP_BUF_ERROR for a short capacity, LZNT1's uncounted
+ *                 00 00 when two bytes of room are left.
+ *   Units that fail the checks: a unit gets MSCOMP_ARG_ERROR, d_out_len = 0, and nothing is read or written for it, if its in_len is above
+ *                 in_unit_max, or the running total of in_len up to and including it is above in_total_max. The other units are unaffected.
+ *                 Offsets and capacities are the caller's responsibility.
+ *   Execution:    as for decompress dev plans (asynchronous, no allocation, no synchronisation, nothing read back; plain launches while the ctx
+ *                 stream is being captured, a graph of its own from the second execution on otherwise). MSCOMP_ARG_ERROR for a null plan or
+ *                 array (d_in may be null when in_total_max is 0; d_out is needed whenever n_units > 0).
+ *   Plan kinds:   mscomp_amd_plan_execute and mscomp_amd_plan_execute_size return MSCOMP_ARG_ERROR for it without enqueueing anything.
+ *   Creation:     the argument checks of mscomp_amd_plan_create (MSCOMP_ARG_ERROR for a null ctx or plan pointer, a bad format, n_units above
+ *                 0x7FFFFFF0), and MSCOMP_ARG_ERROR for in_unit_max 0 or above 0xFFFFF000; MSCOMP_MEM_ERROR when the bounds exceed what the
+ *                 scratch can address or the scratch cannot be reserved. The scratch is reserved for the bounds, once.
+ *   Fixed at creation, as for host plans: the LZNT1 dictionary flavour (mscomp_amd_ctx_set_lznt1_sa_dict), and the Xpress match finder, chosen
+ *                 by in_unit_max as a host plan chooses it by its largest unit. */
+MSCompStatus mscomp_amd_plan_create_compress_dev(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units,
+                                                 uint64_t in_total_max, uint64_t in_unit_max, mscomp_amd_plan** plan);
+/* The device form of mscomp_amd_plan_layout: d_out_cap[i] = the largest output of one unit of d_in_len[i] bytes (that of
+ * mscomp_amd_plan_layout; d_out_cap may be NULL), d_out_off[0..n_units] = the exclusive running sum of the capacities rounded up to `align`
+ * (0 counts as 1), d_out_off[n_units] = total, saturating as mscomp_amd_layout_dev. One launch on the ctx stream; allocates nothing.
+ * MSCOMP_ARG_ERROR for a bad format, a null ctx or d_out_off, or a null d_in_len with n_units > 0. */
+MSCompStatus mscomp_amd_plan_layout_dev(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units, const uint64_t* d_in_len,
+                                        uint64_t align, uint64_t* d_out_off, uint64_t* d_out_cap);
+
 /* Batch helpers.
  * Capacity planning: out_cap[i] = what one ms_compress call needs at most for in_len[i] bytes (ms_max_compressed_size, + 2 for the LZNT1
  * End_of_buffer), out_off[i] = running offset rounded up to `align`; returns the total size of the output buffer ((uint64_t)-1: bad format).

@@ -36,6 +36,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_version", "mscomp_amd_debug_xpress_matches", "mscomp_amd_debug_huff_lengths", "mscomp_amd_debug_lds_lane_order", "mscomp_amd_debug_set_xpress_emit", "mscomp_amd_debug_set_lznt1", "mscomp_amd_debug_set_serial_atomics", "mscomp_amd_compress_units_host", "mscomp_amd_decompress_units_host", "mscomp_amd_host_pool_release", "mscomp_amd_debug_set_finder", "mscomp_amd_debug_set_one_shot", "mscomp_amd_debug_set_xpress_decoder", "mscomp_amd_debug_lzg_open", "mscomp_amd_set_lznt1_sa_dict", "mscomp_amd_get_lznt1_sa_dict", "mscomp_amd_ctx_set_lznt1_sa_dict", "mscomp_amd_debug_hooks_enabled", "mscomp_amd_debug_lzd_walked", "mscomp_amd_debug_decode_modes",
     "mscomp_amd_plan_create_size", "mscomp_amd_plan_execute_size", "mscomp_amd_decompressed_size_batch",
     "mscomp_amd_plan_create_decompress_dev", "mscomp_amd_plan_execute_dev", "mscomp_amd_layout_dev",
+    "mscomp_amd_plan_create_compress_dev", "mscomp_amd_plan_layout_dev",
 ]
 
 
@@ -110,6 +111,10 @@ def load_library():
     lib.mscomp_amd_plan_execute_dev.restype = C.c_int
     lib.mscomp_amd_layout_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.mscomp_amd_layout_dev.restype = C.c_int
+    lib.mscomp_amd_plan_create_compress_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_plan_create_compress_dev.restype = C.c_int
+    lib.mscomp_amd_plan_layout_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.mscomp_amd_plan_layout_dev.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -351,6 +356,36 @@ class DevPlan:
             self.close()
         except Exception:
             pass
+
+
+class CompressDevPlan(DevPlan):
+    """A compress plan with device tables (mscomp_amd_plan_create_compress_dev): made once for n_units units of at most in_unit_max bytes each
+    whose in_len sum to at most in_total_max, then executed (``execute``, as DevPlan's) with unit tables that live on the device."""
+
+    def __init__(self, ctx, fmt, n_units, in_total_max, in_unit_max):
+        self.ctx, self.fmt, self.n_units = ctx, int(fmt), int(n_units)
+        self.in_total_max, self.in_unit_max = int(in_total_max), int(in_unit_max)
+        self._h = C.c_void_p()
+        st = ctx.lib.mscomp_amd_plan_create_compress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.in_unit_max, C.byref(self._h))
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_plan_create_compress_dev")
+
+
+def plan_layout_dev(ctx, fmt, d_in_len, align=16, d_off=None, d_cap=None):
+    """mscomp_amd_plan_layout_dev: per unit the largest compressed size of d_in_len[i] bytes in format ``fmt`` (d_cap), and their exclusive
+    running sum rounded up to ``align`` (d_off, n + 1 entries, the last one the total), on the device and enqueued on the ctx stream. Returns
+    (d_off, d_cap); either is allocated (int64) when not given."""
+    import torch
+    n = d_in_len.numel()
+    if d_off is None:
+        d_off = torch.empty(n + 1, dtype=torch.int64, device=d_in_len.device)
+    if d_cap is None:
+        d_cap = torch.empty(n, dtype=torch.int64, device=d_in_len.device)
+    st = ctx.lib.mscomp_amd_plan_layout_dev(ctx._h, int(fmt), n, C.c_void_p(d_in_len.data_ptr()), int(align),
+                                            C.c_void_p(d_off.data_ptr()), C.c_void_p(d_cap.data_ptr()))
+    if st != MSCOMP_OK:
+        raise MSCompError(st, "mscomp_amd_plan_layout_dev")
+    return d_off, d_cap
 
 
 def layout_dev(ctx, d_cap, align=16, d_off=None):

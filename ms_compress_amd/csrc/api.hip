@@ -91,8 +91,9 @@ struct mscomp_amd_plan {
 	MSCompFormat format = MSCOMP_NONE;
 	bool decompress = false;
 	bool sizing = false;                               // a decompressed-size plan (mscomp_amd_plan_create_size): out_cap holds the limits, nothing is decoded
-	bool dev = false;                                  // a decompress plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev)
+	bool dev = false;                                  // a plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev / _compress_dev)
 	uint64_t in_total_max = 0, out_total_max = 0;      // ... and the bounds its scratch was reserved for
+	uint64_t in_unit_max = 0;                          // (compress dev plans: the largest unit they take)
 	uint32_t n_units = 0, n_chunks = 0;
 	uint64_t total_in = 0, max_unit = 0;
 	bool lznt1_sa = false;                             // LZNT1: the suffix-array dictionary flavour -- fixed when the plan is created: a plan never changes its bytes under a running caller
@@ -934,17 +935,135 @@ static void dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* 
 	{ KernelTimer t(c, "dv_reject_kernel"); launch_dev_reject(st, reject, n, d_out_len, d_status); }
 }
 
+// ---- compress plans with device tables (include/mscomp_amd.h): the compressing half of the same pipeline ----
+// p->tables holds san (4 x n u64, as above) | chunk prefix (u32, n + 1) | reject (u32, n), written by dv_ctables_kernel at every execution.
+// bt.n_chunks is the plan's chunk bound; every chunk-gridded kernel runs its DEV instance, which returns past chunk_prefix[n_units].
+static size_t cdev_table_words(uint64_t n) { return 4 * n + (n + 2) / 2 + (n + 1) / 2 + 1; }
+
+MSCompStatus mscomp_amd_plan_create_compress_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint64_t in_unit_max,
+                                                 mscomp_amd_plan** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || n_units > 0x7FFFFFF0u || in_unit_max == 0 || in_unit_max > 0xFFFFF000ull) { return MSCOMP_ARG_ERROR; }
+	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	// chunks of the accepted units: each has at most ceil(U / k), and as sum ceil(L / k) <= N + floor(sum L / k), at most N + floor(I / k) in all
+	// (the first term keeps a batch of 64 KiB units at one link chunk -- 448 KiB of Xpress match scratch -- per unit)
+	const uint64_t N = n_units, U = in_unit_max, I = in_total_max < N * U ? in_total_max : N * U;
+	const uint64_t k = format == MSCOMP_LZNT1 ? 4096u : 65536u;
+	const uint64_t by_unit = N * ((U + k - 1) / k), by_total = N + I / k, chunks = by_unit < by_total ? by_unit : by_total;
+	if (chunks > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
+	mscomp_amd_plan* p = new (std::nothrow) mscomp_amd_plan();
+	if (!p) { return MSCOMP_MEM_ERROR; }
+	p->ctx = c; p->format = format; p->decompress = false; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
+	p->in_total_max = in_total_max; p->in_unit_max = U; p->total_in = in_total_max; p->max_unit = U;   // (max_unit: the Xpress finder, as plan_launch chooses it)
+	p->lznt1_sa = format == MSCOMP_LZNT1 && lznt1_sa_for(c);
+	// the scratch of plan_create_impl for this many chunks
+	bool ok = p->tables.reserve(cdev_table_words(N) * 8) &&
+	          c->slot_size.reserve((chunks + 1) * sizeof(uint32_t)) && c->prefix.reserve((chunks + 2) * sizeof(uint64_t)) &&
+	          c->tile_sums.reserve((chunks / 1024 + 4) * sizeof(uint64_t));
+	if (ok && format == MSCOMP_LZNT1) { ok = c->slots.reserve(chunks * LZNT1_SLOT + 64); }
+	if (ok && format == MSCOMP_LZNT1 && !p->lznt1_sa) { ok = c->lzrec.reserve(chunks * LZNT1_REC + 64); }
+	if (ok && format != MSCOMP_LZNT1) {
+		const size_t per = chunks * 65536u * sizeof(uint16_t) + 64;
+		ok = c->links.reserve(per) && c->mlen3.reserve(2 * per) && c->lasthead.reserve(per / 2 + 64);
+		if (ok && format == MSCOMP_XPRESS) {
+			const size_t nw = chunks * 1024u + 64;
+			ok = c->wtok.reserve(nw * 8) && c->wmat.reserve(nw * 8) && c->wfar.reserve(nw * 4);
+			if (ok && xpress_emit_mode_for(p->n_units, p->n_chunks) == 4) {   // (launch_xpress_emit chooses from the same two numbers)
+				const size_t ns = chunks + 1;
+				ok = c->wrec.reserve(nw * 6 * 4) && c->sbrec.reserve(ns * (16 + 24 + 16 * 8 * 4 + 16 * 2 * 8 + 8));
+			}
+		}
+	}
+	if (ok && format == MSCOMP_XPRESS_HUFF) {
+		const size_t nc = chunks + 1;
+		ok = c->tokbits.reserve(nc * 1024 * 8) && c->counts.reserve(nc * 512 * 4) && c->extra.reserve(nc * 4) &&
+		     c->lens.reserve(nc * 512) && c->codes.reserve(nc * 1024) && c->fb_list.reserve(nc * 4 + 64) && c->fbflag.reserve(nc * 4);
+	}
+	if (!ok) { (void)hipGetLastError(); p->tables.release(); delete p; return MSCOMP_MEM_ERROR; }
+	// the one-time kernel attributes of the instances this plan launches: set now, so that no first launch happens inside a caller's capture
+	if (format == MSCOMP_LZNT1 && p->lznt1_sa) { prepare_lznt1_sa(true); }
+	if (format != MSCOMP_LZNT1) { prepare_xp_match(true); }
+	if (format == MSCOMP_XPRESS) { prepare_xp_lazy2(true); }
+	if (format == MSCOMP_XPRESS_HUFF) { prepare_xh_fallback(); }
+	u64* san = static_cast<u64*>(p->tables.p);
+	p->bt.in_off = san; p->bt.in_len = san + N; p->bt.out_off = san + 2 * N; p->bt.out_cap = san + 3 * N;
+	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(san + 4 * N);
+	p->bt.n_units = p->n_units; p->bt.n_chunks = p->n_chunks;
+	*out = p;
+	return MSCOMP_OK;
+}
+
+static void dev_compress_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint8_t* d_out,
+                                const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+{
+	mscomp_amd_ctx* c = p->ctx;
+	hipStream_t st = c->stream;
+	const uint32_t n = p->n_units;
+	u64* san = static_cast<u64*>(p->tables.p);
+	uint32_t* chunk_prefix = reinterpret_cast<uint32_t*>(san + 4 * (size_t)n);
+	uint32_t* reject = chunk_prefix + 2 * ((n + 2u) / 2);
+	uint32_t* slot_size = static_cast<uint32_t*>(c->slot_size.p);
+	u64* prefix = static_cast<u64*>(c->prefix.p);
+	u64* tile_sums = static_cast<u64*>(c->tile_sums.p);
+	{ KernelTimer t(c, "dv_ctables_kernel"); launch_dev_ctables(st, (int)p->format, n, p->in_total_max, p->in_unit_max, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, reject); }
+	switch (p->format) {
+	case MSCOMP_LZNT1: {                                        // (the chunk kernels write a size of 0 for the chunks past the real count)
+		uint8_t* slots = static_cast<uint8_t*>(c->slots.p);
+		if (p->lznt1_sa) { KernelTimer t(c, "lznt1_sa_chunk_kernel"); launch_lznt1_sa_chunks(st, d_in, p->bt, slots, slot_size, true); }
+		else { KernelTimer t(c, "lznt1_chunk_kernel"); launch_lznt1_chunks(st, d_in, p->bt, slots, slot_size, static_cast<uint16_t*>(c->lzrec.p), true); }
+		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, slot_size, prefix, p->n_chunks, tile_sums); }
+		{ KernelTimer t(c, "concat_slots_kernel"); launch_concat_slots(st, slots, LZNT1_SLOT, slot_size, prefix, p->bt, d_out, true); }
+		{ KernelTimer t(c, "finalize_units_kernel"); launch_finalize_units(st, prefix, p->bt, d_out, d_out_len, d_status, 1); }
+		break;
+	}
+	case MSCOMP_XPRESS: {
+		uint16_t* links = static_cast<uint16_t*>(c->links.p); uint16_t* lasthead = static_cast<uint16_t*>(c->lasthead.p);
+		uint16_t* mlen3 = static_cast<uint16_t*>(c->mlen3.p); uint16_t* moff = mlen3 + 1;
+		{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead, true); }
+		if (g_finder_mode.load(std::memory_order_relaxed) != 2 && p->in_unit_max <= 65536u) { KernelTimer t(c, "xp_lazy2_kernel"); launch_xp_lazy2(st, d_in, p->bt, links, mlen3, moff, true); }
+		else { KernelTimer t(c, "xp_find_kernel"); launch_xp_find(st, d_in, p->bt, links, lasthead, mlen3, moff, 0x2000u, 0, true); }
+		{ KernelTimer t(c, "xpress_emit_kernel"); launch_xpress_emit(st, d_in, p->bt, mlen3, moff, xpress_win_bufs(c, p->n_chunks), d_out, d_out_len, d_status, true); }
+		break;
+	}
+	default: {                                                  // MSCOMP_XPRESS_HUFF (xh_huff_kernel<true> writes a size of 0 for the chunks past the real count)
+		uint16_t* links = static_cast<uint16_t*>(c->links.p); uint16_t* lasthead = static_cast<uint16_t*>(c->lasthead.p);
+		uint16_t* mlen3 = static_cast<uint16_t*>(c->mlen3.p); uint16_t* moff = mlen3 + 1;
+		u64* tokbits = static_cast<u64*>(c->tokbits.p); uint32_t* counts = static_cast<uint32_t*>(c->counts.p);
+		uint32_t* extra = static_cast<uint32_t*>(c->extra.p); uint8_t* lens = static_cast<uint8_t*>(c->lens.p);
+		uint16_t* codes = static_cast<uint16_t*>(c->codes.p); uint32_t* fbflag = static_cast<uint32_t*>(c->fbflag.p);
+		uint32_t* fb_count = static_cast<uint32_t*>(c->fb_list.p); uint32_t* fb_list = fb_count + 16;
+		{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead, true); }
+		{ KernelTimer t(c, "xp_find_kernel"); launch_xp_find(st, d_in, p->bt, links, lasthead, mlen3, moff, 0xFFFFu, 1, true); }
+		{ KernelTimer t(c, "xh_parse_kernel"); launch_xh_parse(st, d_in, p->bt, mlen3, moff, tokbits, counts, extra, true); }
+		{ KernelTimer t(c, "xh_huff_kernel"); launch_xh_huff(st, p->bt, counts, extra, lens, codes, slot_size, fb_list, fb_count, fbflag, true); }
+		{ KernelTimer t(c, "xh_fallback_kernel"); launch_xh_fallback(st, d_in, p->bt, fb_list, fb_count, XH_FB_BLOCKS, tokbits, lens, codes, slot_size); }
+		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, slot_size, prefix, p->n_chunks, tile_sums); }
+		{ KernelTimer t(c, "xh_encode_kernel"); launch_xh_encode(st, d_in, p->bt, mlen3, moff, tokbits, lens, codes, fbflag, prefix, d_out, true); }
+		{ KernelTimer t(c, "finalize_units_kernel"); launch_finalize_units(st, prefix, p->bt, d_out, d_out_len, d_status, 0); }
+		break;
+	}
+	}
+	{ KernelTimer t(c, "dv_reject_kernel"); launch_dev_reject(st, reject, n, d_out_len, d_status); }
+}
+
 MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                          uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
 {
 	if (!p || !p->dev) { return MSCOMP_ARG_ERROR; }
 	if (p->n_units && (!d_in_off || !d_in_len || !d_out_off || !d_out_cap || !d_out_len || !d_status)) { return MSCOMP_ARG_ERROR; }
 	if ((p->in_total_max && !d_in) || (p->out_total_max && !d_out)) { return MSCOMP_ARG_ERROR; }
+	if (!p->decompress && p->n_units && !d_out) { return MSCOMP_ARG_ERROR; }   // (a compress plan has no output bound: an empty unit may get LZNT1's 00 00)
 	if (p->n_units == 0) { return MSCOMP_OK; }
 	mscomp_amd_ctx* c = p->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	note_modes(p);
+	if (p->decompress) { note_modes(p); }
+	void (*const launch)(mscomp_amd_plan*, const uint8_t*, const uint64_t*, const uint64_t*, uint8_t*, const uint64_t*, const uint64_t*, uint64_t*, int32_t*) =
+		p->decompress ? dev_launch : dev_compress_launch;
 	// While the caller captures the ctx stream, plain launches go into the caller's graph. Otherwise, from the second execution on, the
 	// launches are replayed as the plan's own graph (as plan_execute does), captured again whenever a pointer, the scratch or a kernel
 	// switch moved. A stream whose capture state cannot be read counts as captured.
@@ -959,7 +1078,7 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in
 			if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
 			hipGraph_t graph = nullptr;
 			if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-				dev_launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status);
+				launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status);
 				const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
 				if (ee == hipSuccess && graph && hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0) == hipSuccess) {
 					p->g_epoch = c->epoch; p->g_mode = mode_now; memcpy(p->g_args, args, sizeof args);
@@ -970,7 +1089,7 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in
 		}
 		if (p->gexec) { return hipGraphLaunch(p->gexec, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
 	}
-	dev_launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status);
+	launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status);
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
@@ -980,6 +1099,17 @@ MSCompStatus mscomp_amd_layout_dev(mscomp_amd_ctx* c, size_t n_units, const uint
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	launch_layout_dev(c->stream, d_cap, (uint32_t)n_units, align, d_off);
+	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
+}
+
+MSCompStatus mscomp_amd_plan_layout_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, const uint64_t* d_in_len, uint64_t align,
+                                        uint64_t* d_out_off, uint64_t* d_out_cap)
+{
+	if (!c || !d_out_off || (n_units && !d_in_len) || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	launch_clayout_dev(c->stream, (int)format, d_in_len, (uint32_t)n_units, align, d_out_off, d_out_cap);
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 

@@ -115,6 +115,10 @@ __device__ __forceinline__ uint32_t unit_of_chunk(const uint32_t* __restrict__ p
 	return lo;
 }
 
+// Plans whose tables are built on the device (DEV kernel instances): the grid is sized for the plan's bound, and a chunk at or past the batch's
+// real count (chunk_prefix[n_units], written by the table pass) belongs to no unit -- unit_of_chunk would hand it to the last one
+__device__ __forceinline__ bool past_real_chunks(const BatchTables& bt, uint32_t c) { return c >= bt.chunk_prefix[bt.n_units]; }
+
 // Cooperative byte copy global->global: src is 4-byte aligned (a scratch slot), dst has any alignment.
 // Body moves aligned dwords on the destination side, funnel-shifting two source dwords.
 __device__ __forceinline__ void copy_from_aligned(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src,

@@ -26,22 +26,27 @@ void set_serial_atomics(int device, int on);           // on: 1 = one lane at a 
 #define LZNT1_SLOT 4352u     // scratch bytes per 4 KiB chunk image (2 B header + <=4096 B payload + emit slack)
 void set_lznt1_mode(int mode);
 #define LZNT1_REC  5632u     // scratch bytes of parse records per 4 KiB chunk (four-wave kernel: match tokens of 64 windows, two areas)
-void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs);
-void launch_lznt1_sa_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size);   // lznt1_sa.hip: the suffix-array dictionary flavour
+// dev (here and below): a compress plan with device-built tables -- bt.n_chunks is its bound, and the chunk-gridded kernels return past
+// chunk_prefix[n_units] (their DEV instances; host plans run the original ones). prepare_*: the one-time LDS attributes of a launcher's kernels.
+void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs, bool dev = false);
+void launch_lznt1_sa_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, bool dev = false);   // lznt1_sa.hip: the suffix-array dictionary flavour
+void prepare_lznt1_sa(bool dev);
 
 // ---- Xpress / Xpress+Huffman match finder (xpress_match.hip) ----
 // links: u16 per position (64 KiB "link chunks", chunk-major), lasthead: 32768 u16 per link chunk,
 // mlen3/moff: per position len-3 (capped at 48-3) and offset (0 = no match).
-void launch_xp_links(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* links, uint16_t* lasthead);
+void launch_xp_links(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* links, uint16_t* lasthead, bool dev = false);
 void launch_xp_find(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, const uint16_t* lasthead,
-                    uint16_t* mlen3, uint16_t* moff, uint32_t max_off, int clip);
+                    uint16_t* mlen3, uint16_t* moff, uint32_t max_off, int clip, bool dev = false);
+void prepare_xp_match(bool dev);
 // the same over chunks [chunk_base, chunk_base + chunk_count) only (the pipelined one-shot call: a range's kernels run while the next range is on its way up)
-void launch_xp_links_range(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* links, uint16_t* lasthead, uint32_t chunk_base, uint32_t chunk_count);
+void launch_xp_links_range(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* links, uint16_t* lasthead, uint32_t chunk_base, uint32_t chunk_count, bool dev = false);
 void launch_xp_find_range(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, const uint16_t* lasthead,
-                          uint16_t* mlen3, uint16_t* moff, uint32_t max_off, int clip, uint32_t chunk_base, uint32_t chunk_count);
+                          uint16_t* mlen3, uint16_t* moff, uint32_t max_off, int clip, uint32_t chunk_base, uint32_t chunk_count, bool dev = false);
 // the lazy finder (xpress_lazy.hip): Find only where a greedy parse can start a token -- Xpress, every unit at most 64 KiB. Fills the same
 // arrays for a superset of the true token starts; the offsets of all other positions are 0.
-void launch_xp_lazy2(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, uint16_t* mlen3, uint16_t* moff);
+void launch_xp_lazy2(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, uint16_t* mlen3, uint16_t* moff, bool dev = false);
+void prepare_xp_lazy2(bool dev);
 
 
 // ---- Xpress stream emission (xpress_emit.hip): one wavefront per unit ----
@@ -51,18 +56,19 @@ int xpress_emit_mode_for(uint32_t n_units, uint32_t n_chunks);
 struct XpressWinBufs { u64* wtok; u64* wmat; uint32_t* wfar; uint32_t* wecur; uint32_t* weF; uint32_t* wsum; uint32_t* wnr; uint32_t* ws0; uint32_t* ws1;
                        uint32_t* sbtot; u64* sbpre; uint32_t* seam; u64* seampos; uint32_t* used; };
 void launch_xpress_emit(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* mlen3, const uint16_t* moff,
-                        const XpressWinBufs& wb, uint8_t* d_out, u64* d_out_len, int32_t* d_status);
+                        const XpressWinBufs& wb, uint8_t* d_out, u64* d_out_len, int32_t* d_status, bool dev = false);
 
 // ---- Xpress+Huffman chunk pipeline (xhuff.hip) ----
 void launch_xh_parse(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* mlen3, const uint16_t* moff,
-                     u64* tokbits, uint32_t* counts, uint32_t* extra);
+                     u64* tokbits, uint32_t* counts, uint32_t* extra, bool dev = false);
 void launch_xh_huff(hipStream_t st, const BatchTables& bt, const uint32_t* counts, const uint32_t* extra, uint8_t* lens, uint16_t* codes,
-                    uint32_t* chunk_size, uint32_t* fb_list, uint32_t* fb_count, uint32_t* fbflag);
+                    uint32_t* chunk_size, uint32_t* fb_list, uint32_t* fb_count, uint32_t* fbflag, bool dev = false);   // dev: fb_count zeroed by a kernel
 void launch_xh_huff_debug(hipStream_t st, const uint32_t* counts, uint8_t* lens, uint32_t n);
 void launch_xh_fallback(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint32_t* fb_list, const uint32_t* fb_count,
                         uint32_t blocks, u64* tokbits, uint8_t* lens, uint16_t* codes, uint32_t* chunk_size);
+void prepare_xh_fallback();
 void launch_xh_encode(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* mlen3, const uint16_t* moff,
-                      const u64* tokbits, const uint8_t* lens, const uint16_t* codes, const uint32_t* fbflag, const u64* prefix, uint8_t* d_out);
+                      const u64* tokbits, const uint8_t* lens, const uint16_t* codes, const uint32_t* fbflag, const u64* prefix, uint8_t* d_out, bool dev = false);
 
 // ---- decompressors (decompress.hip) ----
 // LZNT1: the compressed input of a unit is cut into segments of LZD_SEG bytes (chunk_prefix[u] = first segment of unit u, n_chunks =
@@ -158,13 +164,20 @@ void launch_dev_zero(hipStream_t st, uint32_t* p, uint32_t n);
 void launch_dev_reject(hipStream_t st, const uint32_t* reject, uint32_t n, u64* d_out_len, int32_t* d_status);
 // off[0..n] = exclusive running sum of cap[i] rounded up to align (saturating at 2^64 - 1)
 void launch_layout_dev(hipStream_t st, const u64* cap, uint32_t n, u64 align, u64* off);
+// compress plans (mscomp_amd_plan_create_compress_dev): per unit the checks in_len <= in_unit_max and running total of in_len <= in_total_max,
+// the sanitised row in san (as above), reject[u], and chunk_prefix (u32, n + 1) with chunks_of(format, false, L): 4 KiB chunks for LZNT1,
+// 64 KiB for the Xpress formats, none for an empty or a rejected unit
+void launch_dev_ctables(hipStream_t st, int format, uint32_t n, u64 in_total_max, u64 in_unit_max, const u64* in_off, const u64* in_len,
+                        const u64* out_off, const u64* out_cap, u64* san, uint32_t* chunk_prefix, uint32_t* reject);
+// mscomp_amd_plan_layout_dev: cap[i] = the format's largest output for in_len[i] (cap may be null), off[0..n] as launch_layout_dev
+void launch_clayout_dev(hipStream_t st, int format, const u64* in_len, uint32_t n, u64 align, u64* off, u64* cap);
 
 // ---- utilities (util.hip) ----
 // prefix[0..n] = exclusive scan of sizes[0..n) as u64 (prefix[n] = total). block_sums: scratch of ceil(n/1024)+1 u64.
 void launch_scan_sizes(hipStream_t st, const uint32_t* sizes, u64* prefix, uint32_t n, u64* block_sums);
 // Concatenate the chunk images of every unit into the caller's output (skips units that do not fit).
 void launch_concat_slots(hipStream_t st, const uint8_t* slots, uint32_t slot_stride, const uint32_t* slot_size,
-                         const u64* prefix, const BatchTables& bt, uint8_t* d_out);
+                         const u64* prefix, const BatchTables& bt, uint8_t* d_out, bool dev = false);
 // Per unit: out_len, status (OK / BUF_ERROR); LZNT1 also appends the uncounted 00 00 End_of_buffer when room.
 // outputs of a batch packed back to back: packed_off[0..n] (device), bytes of unit u at d_packed + packed_off[u]
 void launch_compact(hipStream_t st, const uint8_t* d_out, const u64* d_out_off, const uint32_t* d_tile_prefix, uint32_t n_units, uint32_t n_tiles,

@@ -345,7 +345,9 @@ __device__ __forceinline__ uint32_t lz_ordered_add(uint32_t* addr, uint32_t v, b
 	return old;
 }
 
-template <bool serial>    // (a template, not an argument: the default kernels are the code they were)
+// DEV (compress plans with device tables): the grid is the plan's bound of chunks, and the blocks past the batch's real count return at once
+// with a size of 0 (what scan_sizes reads for them); host plans run the <.., false> instances
+template <bool serial, bool DEV = false>    // (a template, not an argument: the default kernels are the code they were)
 __global__ __launch_bounds__(64) void lznt1_chunk_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                         uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size)
 {
@@ -365,6 +367,7 @@ __global__ __launch_bounds__(64) void lznt1_chunk_kernel(const uint8_t* __restri
 
 	const uint32_t lane = threadIdx.x;
 	const uint32_t c = blockIdx.x;
+	if (DEV && past_real_chunks(bt, c)) { if (lane == 0) { slot_size[c] = 0; } return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, c);
 	const u64 coff = (u64)(c - bt.chunk_prefix[u]) * 4096u;
 	const u64 left = bt.in_len[u] - coff;
@@ -545,7 +548,7 @@ __device__ __forceinline__ uint32_t lz4_seg_start(uint32_t j) { return j == 0 ? 
 extern "C" void mscomp_amd_debug_lz4_prof(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lz4_prof), sizeof(unsigned long long) * LZ4_NPROF); unsigned long long z[LZ4_NPROF] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lz4_prof), z, sizeof z); }
 #endif
 static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: LZNT1_REC = two areas of 64 windows of match tokens");
-template <bool serial>
+template <bool serial, bool DEV = false>                         // DEV: as lznt1_chunk_kernel
 __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                           uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size, uint16_t* __restrict__ recs)
 {
@@ -585,6 +588,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
 	const uint32_t c = blockIdx.x;
+	if (DEV && past_real_chunks(bt, c)) { if (tid == 0) { slot_size[c] = 0; } return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, c);
 	const u64 coff = (u64)(c - bt.chunk_prefix[u]) * 4096u;
 	const u64 left = bt.in_len[u] - coff;
@@ -826,20 +830,39 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 #undef LZ4_WINDOW
 }
 
+// DEV = true: the instances of compress plans with device tables, compiled in lznt1_dev.hip (this file included with LZNT1_DEV_TU defined), so
+// that this file's code object holds the host plans' kernels alone, as before
+template <bool DEV>
+static void launch_lznt1_chunks_t(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs,
+                                  int mode, bool serial)
+{
+	if (mode == 1) {
+		if (serial) { hipLaunchKernelGGL((lznt1_chunk_kernel<true, DEV>), dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, slots, slot_size); }
+		else { hipLaunchKernelGGL((lznt1_chunk_kernel<false, DEV>), dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, slots, slot_size); }
+	} else {
+		if (serial) { hipLaunchKernelGGL((lznt1_chunk4_kernel<true, DEV>), dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, slots, slot_size, recs); }
+		else { hipLaunchKernelGGL((lznt1_chunk4_kernel<false, DEV>), dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, slots, slot_size, recs); }
+	}
+}
+void launch_lznt1_chunks_dev(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs,
+                             int mode, bool serial);
+#ifndef LZNT1_DEV_TU
 static int g_lznt1_mode = 0;                                     // 0 = default, 1 = one wave per chunk, 2 = four waves per chunk (tests)
 void set_lznt1_mode(int mode) { g_lznt1_mode = mode; }
-void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs)
+void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
 	const int mode = g_lznt1_mode ? g_lznt1_mode : 2;                 // four waves per chunk: 1.43 vs 1.74 ms on the headline workload
 	const bool serial = serial_atomics_on_current_device();
-	if (mode == 1) {
-		if (serial) { hipLaunchKernelGGL(lznt1_chunk_kernel<true>, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, slots, slot_size); }
-		else { hipLaunchKernelGGL(lznt1_chunk_kernel<false>, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, slots, slot_size); }
-	} else {
-		if (serial) { hipLaunchKernelGGL(lznt1_chunk4_kernel<true>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, slots, slot_size, recs); }
-		else { hipLaunchKernelGGL(lznt1_chunk4_kernel<false>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, slots, slot_size, recs); }
-	}
+	if (dev) { launch_lznt1_chunks_dev(st, d_in, bt, slots, slot_size, recs, mode, serial); }
+	else { launch_lznt1_chunks_t<false>(st, d_in, bt, slots, slot_size, recs, mode, serial); }
 }
+#else
+void launch_lznt1_chunks_dev(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs,
+                             int mode, bool serial)
+{
+	launch_lznt1_chunks_t<true>(st, d_in, bt, slots, slot_size, recs, mode, serial);
+}
+#endif
 
 } // namespace msc

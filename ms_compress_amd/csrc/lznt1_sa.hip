@@ -76,6 +76,7 @@ __device__ __forceinline__ uint32_t sa_range_min(const uint16_t* m, uint32_t l, 
 	return res;
 }
 
+template <bool DEV = false>                                          // DEV: as lznt1_chunk_kernel (lznt1.hip)
 __global__ __launch_bounds__(SA_NT) void lznt1_sa_chunk_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                               uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size)
 {
@@ -83,6 +84,7 @@ __global__ __launch_bounds__(SA_NT) void lznt1_sa_chunk_kernel(const uint8_t* __
 	SaLds& L = *reinterpret_cast<SaLds*>(sa_smem);
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
 	const uint32_t c = blockIdx.x;
+	if (DEV && past_real_chunks(bt, c)) { if (tid == 0) { slot_size[c] = 0; } return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, c);
 	const u64 coff = (u64)(c - bt.chunk_prefix[u]) * 4096u;
 	const u64 left = bt.in_len[u] - coff;
@@ -400,12 +402,18 @@ __global__ __launch_bounds__(SA_NT) void lznt1_sa_chunk_kernel(const uint8_t* __
 	SA_TM(5)
 }
 
-void launch_lznt1_sa_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size)
+void prepare_lznt1_sa(bool dev)
+{
+	static PerDeviceOnce attr, attr_dev;
+	if (!dev && attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lznt1_sa_chunk_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SaLds)); attr.done(); }
+	if (dev && attr_dev.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lznt1_sa_chunk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SaLds)); attr_dev.done(); }
+}
+void launch_lznt1_sa_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
-	static PerDeviceOnce attr;
-	if (attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lznt1_sa_chunk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SaLds)); attr.done(); }
-	hipLaunchKernelGGL(lznt1_sa_chunk_kernel, dim3(bt.n_chunks), dim3(SA_NT), sizeof(SaLds), st, d_in, bt, slots, slot_size);
+	prepare_lznt1_sa(dev);
+	if (dev) { hipLaunchKernelGGL(lznt1_sa_chunk_kernel<true>, dim3(bt.n_chunks), dim3(SA_NT), sizeof(SaLds), st, d_in, bt, slots, slot_size); }
+	else { hipLaunchKernelGGL(lznt1_sa_chunk_kernel<false>, dim3(bt.n_chunks), dim3(SA_NT), sizeof(SaLds), st, d_in, bt, slots, slot_size); }
 }
 
 } // namespace msc

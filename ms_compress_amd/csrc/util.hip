@@ -73,13 +73,14 @@ void launch_scan_sizes(hipStream_t st, const uint32_t* sizes, u64* prefix, uint3
 	hipLaunchKernelGGL(scan_add_kernel, dim3((n + 256u) / 256u), dim3(256), 0, st, prefix, n, tile_sums, nt);
 }
 
-// one wave per chunk image
+// one wave per chunk image (DEV: the chunks past the batch's real count return, common.h past_real_chunks)
+template <bool DEV = false>
 __global__ __launch_bounds__(256) void concat_slots_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride,
                                                           const uint32_t* __restrict__ slot_size, const u64* __restrict__ prefix,
                                                           BatchTables bt, uint8_t* __restrict__ d_out)
 {
 	const uint32_t c = blockIdx.x * 4u + (threadIdx.x >> 6);
-	if (c >= bt.n_chunks) { return; }
+	if (c >= bt.n_chunks || (DEV && past_real_chunks(bt, c))) { return; }
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, c);
 	const u64 ustart = prefix[bt.chunk_prefix[u]];
@@ -90,10 +91,11 @@ __global__ __launch_bounds__(256) void concat_slots_kernel(const uint8_t* __rest
 }
 
 void launch_concat_slots(hipStream_t st, const uint8_t* slots, uint32_t slot_stride, const uint32_t* slot_size,
-                         const u64* prefix, const BatchTables& bt, uint8_t* d_out)
+                         const u64* prefix, const BatchTables& bt, uint8_t* d_out, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
-	hipLaunchKernelGGL(concat_slots_kernel, dim3((bt.n_chunks + 3u) / 4u), dim3(256), 0, st, slots, slot_stride, slot_size, prefix, bt, d_out);
+	if (dev) { hipLaunchKernelGGL(concat_slots_kernel<true>, dim3((bt.n_chunks + 3u) / 4u), dim3(256), 0, st, slots, slot_stride, slot_size, prefix, bt, d_out); }
+	else { hipLaunchKernelGGL(concat_slots_kernel<false>, dim3((bt.n_chunks + 3u) / 4u), dim3(256), 0, st, slots, slot_stride, slot_size, prefix, bt, d_out); }
 }
 
 __global__ __launch_bounds__(256) void finalize_units_kernel(const u64* __restrict__ prefix, BatchTables bt, uint8_t* __restrict__ d_out,

@@ -189,6 +189,8 @@ extern "C" void mscomp_amd_debug_xp_prof(unsigned long long* out) { (void)hipMem
 #else
 #define XP_T(i)
 #endif
+// DEV (compress plans with device tables): the chunks past the batch's real count return at once; host plans run the <false> instances
+template <bool DEV = false>
 __global__ __launch_bounds__(256) void xh_parse_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                       S16 mlen3, S16 moff,
                                                       u64* __restrict__ tokbits, uint32_t* __restrict__ counts, uint32_t* __restrict__ extra)
@@ -198,6 +200,7 @@ __global__ __launch_bounds__(256) void xh_parse_kernel(const uint8_t* __restrict
 	__shared__ uint32_t s_xtra[4];
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = xh_uniform(tid >> 6);
 	const uint32_t lc = blockIdx.x;
+	if (DEV && past_real_chunks(bt, lc)) { return; }
 	const ChunkGeom g = chunk_geom(bt, lc);
 	const uint8_t* __restrict__ d = d_in + bt.in_off[g.u];
 	const u64 gbase = (u64)lc * 65536u;
@@ -452,6 +455,8 @@ template <class H> __device__ __forceinline__ void huff_store(const H& h, uint32
 	reinterpret_cast<uint4*>(codes_out)[lane] = reinterpret_cast<const uint4*>(h.codes)[lane];
 }
 
+// DEV: as xh_parse_kernel; such a chunk has a size of 0 (what scan_sizes reads for it)
+template <bool DEV = false>
 __global__ __launch_bounds__(64) void xh_huff_kernel(BatchTables bt, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ extra,
                                                     uint8_t* __restrict__ lens_out, uint16_t* __restrict__ codes_out,
                                                     uint32_t* __restrict__ chunk_size, uint32_t* __restrict__ fb_list, uint32_t* __restrict__ fb_count,
@@ -460,6 +465,7 @@ __global__ __launch_bounds__(64) void xh_huff_kernel(BatchTables bt, const uint3
 	__shared__ HuffLdsFast h;
 	const uint32_t lane = threadIdx.x;
 	const uint32_t lc = blockIdx.x;
+	if (DEV && past_real_chunks(bt, lc)) { if (lane == 0) { chunk_size[lc] = 0; } return; }
 	const ChunkGeom g = chunk_geom(bt, lc);
 	uint32_t mycnt[8], wl[8];                                     // counts / leaf weights of the symbols lane + 64 k
 	#pragma unroll
@@ -644,6 +650,7 @@ __global__ __launch_bounds__(512) void xh_fallback_kernel(const uint8_t* __restr
 // ===================================================================================================================
 // encode
 // ===================================================================================================================
+template <bool DEV = false>                                       // DEV: as xh_parse_kernel
 __global__ __launch_bounds__(64) void xh_encode_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                       S16 mlen3, S16 moff,
                                                       const u64* __restrict__ tokbits, const uint8_t* __restrict__ lens_in, const uint16_t* __restrict__ codes_in,
@@ -656,6 +663,7 @@ __global__ __launch_bounds__(64) void xh_encode_kernel(const uint8_t* __restrict
 	__shared__ uint32_t s_slot[256];                               // byte position of word w (mod 256)
 	const uint32_t lane = threadIdx.x;
 	const uint32_t lc = blockIdx.x;
+	if (DEV && past_real_chunks(bt, lc)) { return; }
 	const ChunkGeom g = chunk_geom(bt, lc);
 	const u64 ustart = prefix[bt.chunk_prefix[g.u]];
 	const u64 utotal = prefix[bt.chunk_prefix[g.u + 1]] - ustart;
@@ -807,32 +815,43 @@ __global__ __launch_bounds__(64) void xh_encode_kernel(const uint8_t* __restrict
 // launchers
 // ===================================================================================================================
 void launch_xh_parse(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* mlen3, const uint16_t* moff,
-                     u64* tokbits, uint32_t* counts, uint32_t* extra)
+                     u64* tokbits, uint32_t* counts, uint32_t* extra, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
-	hipLaunchKernelGGL(xh_parse_kernel, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, mlen3, moff, tokbits, counts, extra);
+	if (dev) { hipLaunchKernelGGL(xh_parse_kernel<true>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, mlen3, moff, tokbits, counts, extra); }
+	else { hipLaunchKernelGGL(xh_parse_kernel<false>, dim3(bt.n_chunks), dim3(256), 0, st, d_in, bt, mlen3, moff, tokbits, counts, extra); }
 }
 void launch_xh_huff(hipStream_t st, const BatchTables& bt, const uint32_t* counts, const uint32_t* extra, uint8_t* lens, uint16_t* codes,
-                    uint32_t* chunk_size, uint32_t* fb_list, uint32_t* fb_count, uint32_t* fbflag)
+                    uint32_t* chunk_size, uint32_t* fb_list, uint32_t* fb_count, uint32_t* fbflag, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
-	(void)hipMemsetAsync(fb_count, 0, sizeof(uint32_t), st);
-	hipLaunchKernelGGL(xh_huff_kernel, dim3(bt.n_chunks), dim3(64), 0, st, bt, counts, extra, lens, codes, chunk_size, fb_list, fb_count, fbflag);
+	if (dev) {                                                   // (a kernel, not a memset: a dev plan's launches go into graphs the caller captures)
+		launch_dev_zero(st, fb_count, 1u);
+		hipLaunchKernelGGL(xh_huff_kernel<true>, dim3(bt.n_chunks), dim3(64), 0, st, bt, counts, extra, lens, codes, chunk_size, fb_list, fb_count, fbflag);
+	} else {
+		(void)hipMemsetAsync(fb_count, 0, sizeof(uint32_t), st);
+		hipLaunchKernelGGL(xh_huff_kernel<false>, dim3(bt.n_chunks), dim3(64), 0, st, bt, counts, extra, lens, codes, chunk_size, fb_list, fb_count, fbflag);
+	}
+}
+void prepare_xh_fallback()
+{
+	static PerDeviceOnce attr;
+	if (attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(xh_fallback_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XH_FB_POOL_BYTES); attr.done(); }
 }
 void launch_xh_fallback(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint32_t* fb_list, const uint32_t* fb_count,
                         uint32_t blocks, u64* tokbits, uint8_t* lens, uint16_t* codes, uint32_t* chunk_size)
 {
 	if (bt.n_chunks == 0) { return; }
 	const uint32_t grid = bt.n_chunks < blocks ? bt.n_chunks : blocks;
-	static PerDeviceOnce attr;
-	if (attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(xh_fallback_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XH_FB_POOL_BYTES); attr.done(); }
+	prepare_xh_fallback();
 	hipLaunchKernelGGL(xh_fallback_kernel, dim3(grid), dim3(512), XH_FB_POOL_BYTES, st, d_in, bt, fb_list, fb_count, tokbits, lens, codes, chunk_size);
 }
 void launch_xh_encode(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* mlen3, const uint16_t* moff,
-                      const u64* tokbits, const uint8_t* lens, const uint16_t* codes, const uint32_t* fbflag, const u64* prefix, uint8_t* d_out)
+                      const u64* tokbits, const uint8_t* lens, const uint16_t* codes, const uint32_t* fbflag, const u64* prefix, uint8_t* d_out, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
-	hipLaunchKernelGGL(xh_encode_kernel, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, mlen3, moff, tokbits, lens, codes, fbflag, prefix, d_out);
+	if (dev) { hipLaunchKernelGGL(xh_encode_kernel<true>, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, mlen3, moff, tokbits, lens, codes, fbflag, prefix, d_out); }
+	else { hipLaunchKernelGGL(xh_encode_kernel<false>, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, mlen3, moff, tokbits, lens, codes, fbflag, prefix, d_out); }
 }
 
 } // namespace msc

@@ -833,6 +833,8 @@ __device__ __forceinline__ void xe3_scan_sb(uint32_t lane, uint32_t nsb, const u
 	if (lane == 0) { tot[0] = nc; tot[1] = rc; tot[2] = sc0; tot[3] = sc1; }
 }
 
+// DEV (compress plans with device tables): the super-blocks past the batch's real chunk count return at once
+template <bool DEV = false>
 __global__ __launch_bounds__(1024) void xe3_walk_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, S16 mlen3,
                                                        S16 moff, Xe3 x)
 {
@@ -841,6 +843,7 @@ __global__ __launch_bounds__(1024) void xe3_walk_kernel(const uint8_t* __restric
 	__shared__ uint16_t s_in_len[16][256];
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
 	const uint32_t lc = blockIdx.x;
+	if (DEV && past_real_chunks(bt, lc)) { return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, lc);
 	const uint32_t k = lc - bt.chunk_prefix[u];
 	const u64 n = bt.in_len[u];
@@ -946,11 +949,14 @@ __device__ __forceinline__ void xe3_repair_seam(const uint8_t* __restrict__ d, u
 
 // all seams between super-blocks at once, one wave each (a repair that does not re-synchronise inside its super-block
 // changes that super-block's end state: xe3_fix_kernel notices and cascades)
+// DEV: as xe3_walk_kernel
+template <bool DEV = false>
 __global__ __launch_bounds__(64) void xe3_seam_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, S16 mlen3,
                                                      S16 moff, Xe3 x, uint32_t* __restrict__ used)
 {
 	const uint32_t lane = threadIdx.x;
 	const uint32_t lc = blockIdx.x;
+	if (DEV && past_real_chunks(bt, lc)) { return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, lc);
 	const uint32_t k = lc - bt.chunk_prefix[u];
 	if (k == 0) { return; }
@@ -1033,6 +1039,8 @@ __global__ __launch_bounds__(64) void xe3_fix_kernel(const uint8_t* __restrict__
 	}
 }
 
+// DEV: as xe3_walk_kernel
+template <bool DEV = false>
 __global__ __launch_bounds__(1024) void xe3_emit_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, S16 mlen3,
                                                        S16 moff, Xe3 x, uint8_t* __restrict__ d_out)
 {
@@ -1043,6 +1051,7 @@ __global__ __launch_bounds__(1024) void xe3_emit_kernel(const uint8_t* __restric
 	__shared__ u64      s_in_mask[16][8];
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
 	const uint32_t lc = blockIdx.x;
+	if (DEV && past_real_chunks(bt, lc)) { return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, lc);
 	const uint32_t k = lc - bt.chunk_prefix[u];
 	const u64 n = bt.in_len[u];
@@ -1176,7 +1185,7 @@ int xpress_emit_mode_for(uint32_t n_units, uint32_t n_chunks)
 	return n_units <= 1024u ? 2 : 1;
 }
 void launch_xpress_emit(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* mlen3, const uint16_t* moff,
-                        const XpressWinBufs& wb, uint8_t* d_out, u64* d_out_len, int32_t* d_status)
+                        const XpressWinBufs& wb, uint8_t* d_out, u64* d_out_len, int32_t* d_status, bool dev)
 {
 	if (bt.n_units == 0) { return; }
 	int mode = xpress_emit_mode_for(bt.n_units, bt.n_chunks);
@@ -1187,10 +1196,16 @@ void launch_xpress_emit(hipStream_t st, const uint8_t* d_in, const BatchTables& 
 	else if (mode == 3) { hipLaunchKernelGGL(xpress_emit2_kernel<16u>, dim3(bt.n_units), dim3(1024), 0, st, d_in, bt, mlen3, moff, wtok, wmat, wfar, d_out, d_out_len, d_status); }
 	else {
 		Xe3 x = { wb.wtok, wb.wmat, wb.wfar, wb.wecur, wb.weF, wb.wsum, wb.wnr, wb.ws0, wb.ws1, wb.sbtot, wb.sbpre, wb.seam, wb.seampos };
-		if (bt.n_chunks) { hipLaunchKernelGGL(xe3_walk_kernel, dim3(bt.n_chunks), dim3(1024), 0, st, d_in, bt, mlen3, moff, x); }
-		if (bt.n_chunks) { hipLaunchKernelGGL(xe3_seam_kernel, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, mlen3, moff, x, wb.used); }
+		if (bt.n_chunks && dev) {
+			hipLaunchKernelGGL(xe3_walk_kernel<true>, dim3(bt.n_chunks), dim3(1024), 0, st, d_in, bt, mlen3, moff, x);
+			hipLaunchKernelGGL(xe3_seam_kernel<true>, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, mlen3, moff, x, wb.used);
+		} else if (bt.n_chunks) {
+			hipLaunchKernelGGL(xe3_walk_kernel<false>, dim3(bt.n_chunks), dim3(1024), 0, st, d_in, bt, mlen3, moff, x);
+			hipLaunchKernelGGL(xe3_seam_kernel<false>, dim3(bt.n_chunks), dim3(64), 0, st, d_in, bt, mlen3, moff, x, wb.used);
+		}
 		hipLaunchKernelGGL(xe3_fix_kernel, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, mlen3, moff, x, wb.used, d_out_len, d_status);
-		if (bt.n_chunks) { hipLaunchKernelGGL(xe3_emit_kernel, dim3(bt.n_chunks), dim3(1024), 0, st, d_in, bt, mlen3, moff, x, d_out); }
+		if (bt.n_chunks && dev) { hipLaunchKernelGGL(xe3_emit_kernel<true>, dim3(bt.n_chunks), dim3(1024), 0, st, d_in, bt, mlen3, moff, x, d_out); }
+		else if (bt.n_chunks) { hipLaunchKernelGGL(xe3_emit_kernel<false>, dim3(bt.n_chunks), dim3(1024), 0, st, d_in, bt, mlen3, moff, x, d_out); }
 		hipLaunchKernelGGL(xe3_stitch_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, x, d_out);
 	}
 }

@@ -64,7 +64,8 @@ extern "C" void mscomp_amd_debug_xz_prof(unsigned long long* out) { (void)hipMem
 #endif
 
 // LDS: data [XZ_WIN + TILE + XZ_PAD] | links u16 [XZ_WIN + TILE] | claim bits [TILE / 32] | list [XZ_LIST] | counters [4] | long-match cache [XZ_CACHE] u64
-template <uint32_t TILE, uint32_t SEG, uint32_t WPE>   // WPE: waves per SIMD the register budget allows (HIP's second launch bound)
+// DEV (compress plans with device tables): the link chunks past the batch's real count return at once; host plans run the <.., false> instance
+template <uint32_t TILE, uint32_t SEG, uint32_t WPE, bool DEV = false>   // WPE: waves per SIMD the register budget allows (HIP's second launch bound)
 __global__ __launch_bounds__(TILE / SEG, WPE) void xp_lazy2_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, const uint16_t* __restrict__ links,
                                                              S16 mlen3, S16 moff)
 {
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(TILE / SEG, WPE) void xp_lazy2_kernel(const uint8_t
 
 	const uint32_t tid = threadIdx.x, lane = tid & 63u;
 	const uint32_t lc = blockIdx.x;                          // units of at most 64 KiB: unit == link chunk
+	if (DEV && past_real_chunks(bt, lc)) { return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, lc);
 	const u64 n64 = bt.in_len[u];
 	const uint32_t cn = (uint32_t)n64;                       // <= 65536
@@ -358,20 +360,22 @@ __global__ __launch_bounds__(TILE / SEG, WPE) void xp_lazy2_kernel(const uint8_t
 }
 
 // units of at most 64 KiB only (the caller checks): one block per unit
-template <uint32_t TILE, uint32_t SEG, uint32_t WPE>
-static void launch_xz(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, uint16_t* mlen3, uint16_t* moff)
+// shapes measured on BASELINE configs[4] (ms per pass): 16 KiB tiles / 32-byte segments (512 lanes, 2 blocks = 16 waves per CU) 35.3;
+// 16-byte segments with 1024 lanes at 64 registers 37.9; 8 KiB tiles / 16-byte segments (3 blocks = 24 waves) 39.5; / 8-byte segments 55.5
+#define XZ_SHAPE 16384u, 32u, 4u
+static constexpr uint32_t xz_lds(uint32_t tile) { return XZ_WIN + tile + XZ_PAD + (XZ_WIN + tile) * 2u + tile / 8u + XZ_LIST * 4u + 16u + XZ_CACHE * 8u; }
+void prepare_xp_lazy2(bool dev)                          // the one-time LDS attribute of the host (dev = false) or the DEV instance
 {
-	const uint32_t lds = XZ_WIN + TILE + XZ_PAD + (XZ_WIN + TILE) * 2u + TILE / 8u + XZ_LIST * 4u + 16u + XZ_CACHE * 8u;
-	static PerDeviceOnce attr;
-	if (attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_lazy2_kernel<TILE, SEG, WPE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr.done(); }
-	hipLaunchKernelGGL((xp_lazy2_kernel<TILE, SEG, WPE>), dim3(bt.n_chunks), dim3(TILE / SEG), lds, st, d_in, bt, links, mlen3, moff);
+	static PerDeviceOnce attr, attr_dev;
+	if (!dev && attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_lazy2_kernel<XZ_SHAPE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xz_lds(16384u)); attr.done(); }
+	if (dev && attr_dev.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_lazy2_kernel<XZ_SHAPE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xz_lds(16384u)); attr_dev.done(); }
 }
-void launch_xp_lazy2(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, uint16_t* mlen3, uint16_t* moff)
+void launch_xp_lazy2(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, uint16_t* mlen3, uint16_t* moff, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
-	// shapes measured on BASELINE configs[4] (ms per pass): 16 KiB tiles / 32-byte segments (512 lanes, 2 blocks = 16 waves per CU) 35.3;
-	// 16-byte segments with 1024 lanes at 64 registers 37.9; 8 KiB tiles / 16-byte segments (3 blocks = 24 waves) 39.5; / 8-byte segments 55.5
-	launch_xz<16384u, 32u, 4u>(st, d_in, bt, links, mlen3, moff);
+	prepare_xp_lazy2(dev);
+	if (dev) { hipLaunchKernelGGL((xp_lazy2_kernel<XZ_SHAPE, true>), dim3(bt.n_chunks), dim3(16384u / 32u), xz_lds(16384u), st, d_in, bt, links, mlen3, moff); }
+	else { hipLaunchKernelGGL((xp_lazy2_kernel<XZ_SHAPE, false>), dim3(bt.n_chunks), dim3(16384u / 32u), xz_lds(16384u), st, d_in, bt, links, mlen3, moff); }
 }
 
 } // namespace msc

@@ -81,7 +81,8 @@ __device__ __forceinline__ uint32_t first_diff_bits16(uint32_t x0, uint32_t x1, 
 // lane order (gfx950 behaviour, tools/dev/lds_order_test.hip; every parity test depends on it), so each position
 // receives exactly the most recent earlier position with its hash: the chain link of XpressDictionary.h:120-135.
 // No conflict detection, no head gather/scatter pairs: 8 exchanges in flight, links leave as coalesced u16 stores.
-template <bool serial>    // serial: the exchange one lane at a time (kernels.h set_serial_atomics); a template so that the default kernel is the code it was
+// DEV (compress plans with device tables): the link chunks past the batch's real count return at once; host plans run the <.., false> instances
+template <bool serial, bool DEV = false>    // serial: the exchange one lane at a time (kernels.h set_serial_atomics); a template so that the default kernel is the code it was
 __global__ __launch_bounds__(1024) void xp_links_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                       uint16_t* __restrict__ links, uint16_t* __restrict__ lasthead, uint32_t chunk_base)
 {
@@ -91,6 +92,7 @@ __global__ __launch_bounds__(1024) void xp_links_kernel(const uint8_t* __restric
 
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
 	const uint32_t lc = chunk_base + blockIdx.x;
+	if (DEV && past_real_chunks(bt, lc)) { return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, lc);
 	const uint32_t k = lc - bt.chunk_prefix[u];
 	const u64 n = bt.in_len[u];
@@ -201,7 +203,7 @@ extern "C" void mscomp_amd_debug_xf_prof(unsigned long long* out) { (void)hipMem
 #else
 #define XF_CNT(i, v)
 #endif
-template <uint32_t WINDOW, uint32_t LINKW, uint32_t NT, uint32_t XP_TILE>   // LINKW: how many positions before the tile have their links in LDS
+template <uint32_t WINDOW, uint32_t LINKW, uint32_t NT, uint32_t XP_TILE, bool DEV = false>   // LINKW: how many positions before the tile have their links in LDS; DEV: as xp_links_kernel
 __global__ __launch_bounds__(NT) void xp_find_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                      const uint16_t* __restrict__ links, const uint16_t* __restrict__ lasthead,
                                                      S16 mlen3, S16 moff,
@@ -221,6 +223,7 @@ __global__ __launch_bounds__(NT) void xp_find_kernel(const uint8_t* __restrict__
 	constexpr uint32_t TPC = 65536u / XP_TILE;                                // tiles per chunk
 	const uint32_t lc = bid / TPC;
 	const uint32_t tstart = (bid % TPC) * XP_TILE;                            // tile start inside the chunk
+	if (DEV && past_real_chunks(bt, lc)) { return; }
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, lc);
 	const uint32_t k = lc - bt.chunk_prefix[u];
 	const u64 n = bt.in_len[u];
@@ -357,49 +360,69 @@ __global__ __launch_bounds__(NT) void xp_find_kernel(const uint8_t* __restrict__
 }
 
 
-void launch_xp_links_range(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* links, uint16_t* lasthead, uint32_t chunk_base, uint32_t chunk_count)
+// the one-time LDS attributes of the links / find kernels: host (dev = false) or DEV instances (set when a compress dev plan is created, so that
+// no first launch happens inside a caller's capture)
+#define XH_TILE_SEL 8192u
+static constexpr uint32_t TXP = 4096u, TXH = XH_TILE_SEL;
+static constexpr uint32_t LDS_XP = 0x2000u + TXP + 64u + (0x2000u + TXP) * 2u;        // data + all links of the window in LDS
+static constexpr uint32_t LDS_XH = 0x10000u + TXH + 64u;                             // data only (2 blocks/CU); links come from L2
+template <bool DEV>
+static void xp_match_attributes()
+{
+	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_links_kernel<false, DEV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XL_LDS_BYTES);
+	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_links_kernel<true, DEV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XL_LDS_BYTES);
+	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_find_kernel<0x2000u, 0x2000u, 512u, TXP, DEV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_XP);
+	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_find_kernel<0x10000u, 0u, 1024u, TXH, DEV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_XH);
+}
+void prepare_xp_match(bool dev)
+{
+	static PerDeviceOnce attr, attr_dev;
+	if (!dev && attr.needed()) { xp_match_attributes<false>(); attr.done(); }
+	if (dev && attr_dev.needed()) { xp_match_attributes<true>(); attr_dev.done(); }
+}
+
+template <bool DEV>
+static void launch_xp_links_t(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* links, uint16_t* lasthead, uint32_t chunk_base, uint32_t chunk_count)
+{
+	const uint32_t lds = XL_LDS_BYTES;
+	if (serial_atomics_on_current_device()) { hipLaunchKernelGGL((xp_links_kernel<true, DEV>), dim3(chunk_count), dim3(1024), lds, st, d_in, bt, links, lasthead, chunk_base); }
+	else { hipLaunchKernelGGL((xp_links_kernel<false, DEV>), dim3(chunk_count), dim3(1024), lds, st, d_in, bt, links, lasthead, chunk_base); }
+}
+void launch_xp_links_range(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* links, uint16_t* lasthead, uint32_t chunk_base, uint32_t chunk_count, bool dev)
 {
 	if (chunk_count == 0) { return; }
-	const uint32_t lds = XL_LDS_BYTES;
-	static PerDeviceOnce attr;
-	if (attr.needed()) {
-		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_links_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_links_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		attr.done();
-	}
-	if (serial_atomics_on_current_device()) { hipLaunchKernelGGL(xp_links_kernel<true>, dim3(chunk_count), dim3(1024), lds, st, d_in, bt, links, lasthead, chunk_base); }
-	else { hipLaunchKernelGGL(xp_links_kernel<false>, dim3(chunk_count), dim3(1024), lds, st, d_in, bt, links, lasthead, chunk_base); }
+	prepare_xp_match(dev);
+	if (dev) { launch_xp_links_t<true>(st, d_in, bt, links, lasthead, chunk_base, chunk_count); }
+	else { launch_xp_links_t<false>(st, d_in, bt, links, lasthead, chunk_base, chunk_count); }
 }
-void launch_xp_links(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* links, uint16_t* lasthead)
+void launch_xp_links(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint16_t* links, uint16_t* lasthead, bool dev)
 {
-	launch_xp_links_range(st, d_in, bt, links, lasthead, 0u, bt.n_chunks);
+	launch_xp_links_range(st, d_in, bt, links, lasthead, 0u, bt.n_chunks, dev);
 }
 // tile = positions per block: 4096 for Xpress (4 blocks/CU), 8192 for Xpress+Huffman (the 64 KiB window is re-staged half as
 // often; 72 KiB of LDS, still 2 blocks/CU)
-#define XH_TILE_SEL 8192u
-void launch_xp_find_range(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, const uint16_t* lasthead,
-                          uint16_t* mlen3, uint16_t* moff, uint32_t max_off, int clip, uint32_t chunk_base, uint32_t chunk_count)
+template <bool DEV>
+static void launch_xp_find_t(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, const uint16_t* lasthead,
+                             uint16_t* mlen3, uint16_t* moff, uint32_t max_off, int clip, uint32_t chunk_base, uint32_t chunk_count)
 {
-	if (chunk_count == 0) { return; }
-	static PerDeviceOnce attr;
-	constexpr uint32_t TXP = 4096u, TXH = XH_TILE_SEL;
-	const uint32_t lds_xp = 0x2000u + TXP + 64u + (0x2000u + TXP) * 2u;           // data + all links of the window in LDS
-	const uint32_t lds_xh = 0x10000u + TXH + 64u;                                // data only (2 blocks/CU); links come from L2
-	if (attr.needed()) {
-		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_find_kernel<0x2000u, 0x2000u, 512u, TXP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xp);
-		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(xp_find_kernel<0x10000u, 0u, 1024u, TXH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xh);
-		attr.done();
-	}
 	if (max_off <= 0x2000u) {
-		hipLaunchKernelGGL((xp_find_kernel<0x2000u, 0x2000u, 512u, TXP>), dim3(chunk_count * (65536u / TXP)), dim3(512), lds_xp, st, d_in, bt, links, lasthead, mlen3, moff, max_off, clip, chunk_base * (65536u / TXP));
+		hipLaunchKernelGGL((xp_find_kernel<0x2000u, 0x2000u, 512u, TXP, DEV>), dim3(chunk_count * (65536u / TXP)), dim3(512), LDS_XP, st, d_in, bt, links, lasthead, mlen3, moff, max_off, clip, chunk_base * (65536u / TXP));
 	} else {
-		hipLaunchKernelGGL((xp_find_kernel<0x10000u, 0u, 1024u, TXH>), dim3(chunk_count * (65536u / TXH)), dim3(1024), lds_xh, st, d_in, bt, links, lasthead, mlen3, moff, max_off, clip, chunk_base * (65536u / TXH));
+		hipLaunchKernelGGL((xp_find_kernel<0x10000u, 0u, 1024u, TXH, DEV>), dim3(chunk_count * (65536u / TXH)), dim3(1024), LDS_XH, st, d_in, bt, links, lasthead, mlen3, moff, max_off, clip, chunk_base * (65536u / TXH));
 	}
 }
-void launch_xp_find(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, const uint16_t* lasthead,
-                    uint16_t* mlen3, uint16_t* moff, uint32_t max_off, int clip)
+void launch_xp_find_range(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, const uint16_t* lasthead,
+                          uint16_t* mlen3, uint16_t* moff, uint32_t max_off, int clip, uint32_t chunk_base, uint32_t chunk_count, bool dev)
 {
-	launch_xp_find_range(st, d_in, bt, links, lasthead, mlen3, moff, max_off, clip, 0u, bt.n_chunks);
+	if (chunk_count == 0) { return; }
+	prepare_xp_match(dev);
+	if (dev) { launch_xp_find_t<true>(st, d_in, bt, links, lasthead, mlen3, moff, max_off, clip, chunk_base, chunk_count); }
+	else { launch_xp_find_t<false>(st, d_in, bt, links, lasthead, mlen3, moff, max_off, clip, chunk_base, chunk_count); }
+}
+void launch_xp_find(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* links, const uint16_t* lasthead,
+                    uint16_t* mlen3, uint16_t* moff, uint32_t max_off, int clip, bool dev)
+{
+	launch_xp_find_range(st, d_in, bt, links, lasthead, mlen3, moff, max_off, clip, 0u, bt.n_chunks, dev);
 }
 
 } // namespace msc
