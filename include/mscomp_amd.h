@@ -305,6 +305,10 @@ MSCompStatus mscomp_amd_debug_xpress_matches(mscomp_amd_ctx* ctx, const uint8_t*
 /* Stage-level test hook: the code lengths HuffmanEncoder<15,512>::CreateCodes (include/mscomp/HuffmanEncoder.h:58-107, the heap build with
  * its > 15-bit rescale loop) gives for n histograms of 512 counts; h_counts (n x 512 uint32) and h_lens (n x 512 bytes) are host arrays. */
 MSCompStatus mscomp_amd_debug_huff_lengths(mscomp_amd_ctx* ctx, const uint32_t* h_counts, size_t n, uint8_t* h_lens);
+/* Stage-level test hook: the same for HuffmanEncoder<15,512>::CreateCodesSlow (HuffmanEncoder.h:129-226, package-merge), run by the device
+ * function the literals-only fallback of Xpress+Huffman runs. A fallback chunk has literals and the end-of-stream symbol only and the kernel's
+ * package pool is sized for these 257 leaves: a histogram with a count on a symbol above 0x100 is MSCOMP_ARG_ERROR. */
+MSCompStatus mscomp_amd_debug_huff_lengths_slow(mscomp_amd_ctx* ctx, const uint32_t* h_counts, size_t n, uint8_t* h_lens);
 /* The mscomp_amd_debug_set_* hooks below choose between BIT-IDENTICAL kernels for the tests and are process-wide; the library ignores them unless
  * MSCOMP_AMD_TEST_HOOKS=1 was in the environment when it was loaded (1 = they work). A deployment never sets it. */
 int          mscomp_amd_debug_hooks_enabled(void);

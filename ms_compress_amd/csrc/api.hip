@@ -1194,6 +1194,21 @@ MSCompStatus mscomp_amd_debug_huff_lengths(mscomp_amd_ctx* c, const uint32_t* h_
 	return ok ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
+// ... and HuffmanEncoder<15,512>::CreateCodesSlow (HuffmanEncoder.h:129-226) by the fallback kernel's own package-merge. Counts on the symbols
+// 0..0x100 only, as a fallback chunk has them: the kernel's package pool is sized for 257 leaves, so any other histogram is an argument error.
+MSCompStatus mscomp_amd_debug_huff_lengths_slow(mscomp_amd_ctx* c, const uint32_t* h_counts, size_t n, uint8_t* h_lens)
+{
+	if (!c || (n && (!h_counts || !h_lens)) || n > 0x100000u) { return MSCOMP_ARG_ERROR; }
+	for (size_t i = 0; i < n; ++i) { for (size_t s = 0x101; s < 512; ++s) { if (h_counts[i * 512 + s]) { return MSCOMP_ARG_ERROR; } } }
+	if (!n) { return MSCOMP_OK; }
+	DeviceGuard g(c->device);
+	if (!g.ok || !c->counts.reserve(n * 2048) || !c->lens.reserve(n * 512)) { return MSCOMP_MEM_ERROR; }
+	bool ok = hipMemcpyAsync(c->counts.p, h_counts, n * 2048, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+	if (ok) { launch_xh_huff_slow_debug(c->stream, static_cast<const uint32_t*>(c->counts.p), static_cast<uint8_t*>(c->lens.p), (uint32_t)n); }
+	ok = ok && hipMemcpyAsync(h_lens, c->lens.p, n * 512, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+	return ok ? MSCOMP_OK : MSCOMP_ERRNO;
+}
+
 int mscomp_amd_debug_hooks_enabled(void) { return test_hooks_on() ? 1 : 0; }
 // Test hook: which Xpress parse/emit kernel runs (0 = chosen by batch size, 1 = one wave per unit, 2 = four waves per unit).
 void mscomp_amd_debug_set_xpress_emit(int mode) { if (!test_hooks_on()) { return; } set_xpress_emit_mode(mode); g_mode_epoch.fetch_add(1, std::memory_order_acq_rel); }

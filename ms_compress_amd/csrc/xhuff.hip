@@ -520,6 +520,92 @@ extern "C" void mscomp_amd_debug_fb_prof(unsigned long long* out) { (void)hipMem
 #else
 #define FB_T(i)
 #endif
+// CreateCodesSlow (HuffmanEncoder.h:129-226) by one block of 512 threads: from the histogram in h.cnt (symbols 0..0x100 only: the package
+// pool holds multiplicity vectors over these 257 leaves; thread s = symbol s) to the code lengths in h.lens. The caller has synchronised
+// after the last write of h.cnt and synchronises before it reads h.lens. Shared by xh_fallback_kernel and the stage-test kernel below.
+#ifdef XF_PROFILE
+#define FB_PREV_PARAM , unsigned long long& fb_prev
+#define FB_PREV_ARG , fb_prev
+#else
+#define FB_PREV_PARAM
+#define FB_PREV_ARG
+#endif
+__device__ __forceinline__ void xh_lengths_slow(HuffLds& h, uint16_t* leaf, uint32_t* lcnt, uint16_t* item, u64 (*pcnt)[512], uint32_t* nsh,
+                                                uint8_t* const pool, const uint32_t tid FB_PREV_PARAM)
+{
+	// present symbols, stable-sorted by count (ties: symbol order)  -- rank = #{(count, sym) smaller}
+	const uint32_t myc = h.cnt[tid];
+	h.lens[tid] = myc ? 15 : 0;
+	uint32_t rank = 0;
+	if (myc) { for (uint32_t s = 0; s < 512u; ++s) { const uint32_t c = h.cnt[s]; rank += (c != 0) && (c < myc || (c == myc && s < tid)); } }
+	if (tid == 0) { nsh[0] = 0; }
+	__syncthreads();
+	if (myc) { leaf[rank] = (uint16_t)tid; lcnt[rank] = myc; atomicAdd(&nsh[0], 1u); }
+	__syncthreads();
+	const uint32_t nleaf = nsh[0];
+	FB_T(1)
+	if (nleaf == 1) { if (myc) { h.lens[tid] = 1; } }
+	else {
+		// Package-merge, 15 rounds. A round merges the sorted leaves with the sorted packages of the previous round
+		// (a leaf goes first on equal counts) and pairs consecutive items. The merge is rank arithmetic -- every
+		// leaf and every package finds its place with one binary search, in parallel -- and the per-symbol
+		// multiplicity vectors of the new packages are then summed column-wise (thread s = symbol s) with
+		// independent, coalesced loads. (The serial two-finger merge this replaces was one dependent L2 round trip
+		// per item: 1.2 ms for a single chunk.)
+		uint32_t ncur = 0;
+		int mylen = myc ? 15 : 0;
+		for (uint32_t round = 0; round < 15u; ++round) {
+			const uint8_t* cur = pool + (round & 1u) * XH_FB_GEN_BYTES;
+			uint8_t* nxt = pool + ((round & 1u) ^ 1u) * XH_FB_GEN_BYTES;
+			const u64* pc = pcnt[round & 1u]; u64* pn = pcnt[(round & 1u) ^ 1u];
+			const uint32_t M = ncur + nleaf, nn = M >> 1;
+			if (tid < nleaf) {                                   // my leaf: after the packages that are strictly lighter
+				const u64 x = lcnt[tid];
+				uint32_t lo = 0, hi = ncur;
+				while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (pc[mid] < x) { lo = mid + 1u; } else { hi = mid; } }
+				item[tid + lo] = (uint16_t)(0x8000u | leaf[tid]);
+			}
+			if (tid < ncur) {                                    // my package: after the leaves that are not heavier
+				const u64 x = pc[tid];
+				uint32_t lo = 0, hi = nleaf;
+				while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((u64)lcnt[mid] <= x) { lo = mid + 1u; } else { hi = mid; } }
+				item[tid + lo] = (uint16_t)tid;
+			}
+			__syncthreads();
+			FB_T(2)
+			if (tid < nn) {
+				const uint32_t a = item[2u * tid], b2 = item[2u * tid + 1u];
+				pn[tid] = ((a & 0x8000u) ? (u64)h.cnt[a & 0x7FFFu] : pc[a]) + ((b2 & 0x8000u) ? (u64)h.cnt[b2 & 0x7FFFu] : pc[b2]);
+			}
+			// multiplicity vectors of the new packages: wave w sums the packages k = w, w+8, ...; lane l owns the dword
+			// of symbols 4l..4l+3 (byte-wise sums, no carries: a multiplicity stays below 256) and lane 0 the EOS byte
+			{
+				const uint32_t wv = tid >> 6, lane = tid & 63u;
+				const uint32_t* cur32 = reinterpret_cast<const uint32_t*>(cur);
+				uint32_t* nxt32 = reinterpret_cast<uint32_t*>(nxt);
+				for (uint32_t k = wv; k < nn; k += 8u) {
+					const uint32_t a = xh_uniform(item[2u * k]), b2 = xh_uniform(item[2u * k + 1u]);
+					uint32_t va, vb, ea, eb;
+					if (a & 0x8000u) { const uint32_t sy = a & 0x7FFFu; va = (sy < 256u && lane == (sy >> 2)) ? 1u << ((sy & 3u) * 8u) : 0u; ea = (sy == 256u); }
+					else { va = cur32[a * (XH_FB_STRIDE / 4u) + lane]; ea = cur[a * XH_FB_STRIDE + 256u]; }
+					if (b2 & 0x8000u) { const uint32_t sy = b2 & 0x7FFFu; vb = (sy < 256u && lane == (sy >> 2)) ? 1u << ((sy & 3u) * 8u) : 0u; eb = (sy == 256u); }
+					else { vb = cur32[b2 * (XH_FB_STRIDE / 4u) + lane]; eb = cur[b2 * XH_FB_STRIDE + 256u]; }
+					nxt32[k * (XH_FB_STRIDE / 4u) + lane] = va + vb;
+					if (lane == 0) { nxt[k * XH_FB_STRIDE + 256u] = (uint8_t)(ea + eb); }
+				}
+			}
+			if ((M & 1u) && tid <= 0x100u) {                     // the leftover item is dropped
+				const uint32_t a = item[M - 1u];
+				mylen -= (a & 0x8000u) ? (int)((a & 0x7FFFu) == tid) : (int)cur[a * XH_FB_STRIDE + tid];
+			}
+			ncur = nn;
+			__syncthreads();
+			FB_T(3)
+		}
+		h.lens[tid] = (uint8_t)mylen;
+	}
+}
+
 __global__ __launch_bounds__(512) void xh_fallback_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                          const uint32_t* __restrict__ fb_list, const uint32_t* __restrict__ fb_count,
                                                          u64* __restrict__ tokbits,
@@ -560,77 +646,7 @@ __global__ __launch_bounds__(512) void xh_fallback_kernel(const uint8_t* __restr
 		if (tid == 0 && g.last) { h.cnt[0x100] += 1u; }
 		__syncthreads();
 		FB_T(0)
-		// present symbols, stable-sorted by count (ties: symbol order)  -- rank = #{(count, sym) smaller}
-		const uint32_t myc = h.cnt[tid];
-		h.lens[tid] = myc ? 15 : 0;
-		uint32_t rank = 0;
-		if (myc) { for (uint32_t s = 0; s < 512u; ++s) { const uint32_t c = h.cnt[s]; rank += (c != 0) && (c < myc || (c == myc && s < tid)); } }
-		if (tid == 0) { s_n[0] = 0; }
-		__syncthreads();
-		if (myc) { s_leaf[rank] = (uint16_t)tid; s_lcnt[rank] = myc; atomicAdd(&s_n[0], 1u); }
-		__syncthreads();
-		const uint32_t nleaf = s_n[0];
-		FB_T(1)
-		if (nleaf == 1) { if (myc) { h.lens[tid] = 1; } }
-		else {
-			// Package-merge, 15 rounds. A round merges the sorted leaves with the sorted packages of the previous round
-			// (a leaf goes first on equal counts) and pairs consecutive items. The merge is rank arithmetic -- every
-			// leaf and every package finds its place with one binary search, in parallel -- and the per-symbol
-			// multiplicity vectors of the new packages are then summed column-wise (thread s = symbol s) with
-			// independent, coalesced loads. (The serial two-finger merge this replaces was one dependent L2 round trip
-			// per item: 1.2 ms for a single chunk.)
-			uint32_t ncur = 0;
-			int mylen = myc ? 15 : 0;
-			for (uint32_t round = 0; round < 15u; ++round) {
-				const uint8_t* cur = gen0 + (round & 1u) * XH_FB_GEN_BYTES;
-				uint8_t* nxt = gen0 + ((round & 1u) ^ 1u) * XH_FB_GEN_BYTES;
-				const u64* pc = s_pc[round & 1u]; u64* pn = s_pc[(round & 1u) ^ 1u];
-				const uint32_t M = ncur + nleaf, nn = M >> 1;
-				if (tid < nleaf) {                                   // my leaf: after the packages that are strictly lighter
-					const u64 x = s_lcnt[tid];
-					uint32_t lo = 0, hi = ncur;
-					while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (pc[mid] < x) { lo = mid + 1u; } else { hi = mid; } }
-					s_item[tid + lo] = (uint16_t)(0x8000u | s_leaf[tid]);
-				}
-				if (tid < ncur) {                                    // my package: after the leaves that are not heavier
-					const u64 x = pc[tid];
-					uint32_t lo = 0, hi = nleaf;
-					while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((u64)s_lcnt[mid] <= x) { lo = mid + 1u; } else { hi = mid; } }
-					s_item[tid + lo] = (uint16_t)tid;
-				}
-				__syncthreads();
-				FB_T(2)
-				if (tid < nn) {
-					const uint32_t a = s_item[2u * tid], b2 = s_item[2u * tid + 1u];
-					pn[tid] = ((a & 0x8000u) ? (u64)h.cnt[a & 0x7FFFu] : pc[a]) + ((b2 & 0x8000u) ? (u64)h.cnt[b2 & 0x7FFFu] : pc[b2]);
-				}
-				// multiplicity vectors of the new packages: wave w sums the packages k = w, w+8, ...; lane l owns the dword
-				// of symbols 4l..4l+3 (byte-wise sums, no carries: a multiplicity stays below 256) and lane 0 the EOS byte
-				{
-					const uint32_t wv = tid >> 6, lane = tid & 63u;
-					const uint32_t* cur32 = reinterpret_cast<const uint32_t*>(cur);
-					uint32_t* nxt32 = reinterpret_cast<uint32_t*>(nxt);
-					for (uint32_t k = wv; k < nn; k += 8u) {
-						const uint32_t a = xh_uniform(s_item[2u * k]), b2 = xh_uniform(s_item[2u * k + 1u]);
-						uint32_t va, vb, ea, eb;
-						if (a & 0x8000u) { const uint32_t sy = a & 0x7FFFu; va = (sy < 256u && lane == (sy >> 2)) ? 1u << ((sy & 3u) * 8u) : 0u; ea = (sy == 256u); }
-						else { va = cur32[a * (XH_FB_STRIDE / 4u) + lane]; ea = cur[a * XH_FB_STRIDE + 256u]; }
-						if (b2 & 0x8000u) { const uint32_t sy = b2 & 0x7FFFu; vb = (sy < 256u && lane == (sy >> 2)) ? 1u << ((sy & 3u) * 8u) : 0u; eb = (sy == 256u); }
-						else { vb = cur32[b2 * (XH_FB_STRIDE / 4u) + lane]; eb = cur[b2 * XH_FB_STRIDE + 256u]; }
-						nxt32[k * (XH_FB_STRIDE / 4u) + lane] = va + vb;
-						if (lane == 0) { nxt[k * XH_FB_STRIDE + 256u] = (uint8_t)(ea + eb); }
-					}
-				}
-				if ((M & 1u) && tid <= 0x100u) {                     // the leftover item is dropped
-					const uint32_t a = s_item[M - 1u];
-					mylen -= (a & 0x8000u) ? (int)((a & 0x7FFFu) == tid) : (int)cur[a * XH_FB_STRIDE + tid];
-				}
-				ncur = nn;
-				__syncthreads();
-				FB_T(3)
-			}
-			h.lens[tid] = (uint8_t)mylen;
-		}
+		xh_lengths_slow(h, s_leaf, s_lcnt, s_item, s_pc, s_n, gen0, tid FB_PREV_ARG);
 		__syncthreads();
 		// size: xh_calc_compressed_len_no_matching (:189-194)
 		if (tid < 64u) {
@@ -645,6 +661,28 @@ __global__ __launch_bounds__(512) void xh_fallback_kernel(const uint8_t* __restr
 		if (tid < 64u) { huff_store(h, tid, lens_out + (u64)lc * 512u, codes_out + (u64)lc * 512u); }
 		FB_T(4)
 	}
+}
+
+// Stage-level test hook: code lengths of CreateCodesSlow for histograms given directly (counts on symbols 0..0x100 only), by the
+// product's own xh_lengths_slow, one block per histogram
+__global__ __launch_bounds__(512) void xh_huff_slow_debug_kernel(const uint32_t* __restrict__ counts, uint8_t* __restrict__ lens_out)
+{
+	__shared__ HuffLds h;
+	__shared__ uint16_t s_leaf[512];
+	__shared__ uint32_t s_lcnt[512];
+	__shared__ uint16_t s_item[1024];
+	__shared__ u64 s_pc[2][512];
+	__shared__ uint32_t s_n[4];
+	extern __shared__ __attribute__((aligned(16))) uint8_t fb_pool_lds[];
+	const uint32_t tid = threadIdx.x;
+#ifdef XF_PROFILE
+	unsigned long long fb_prev = __builtin_readcyclecounter();
+#endif
+	h.cnt[tid] = counts[(u64)blockIdx.x * 512u + tid];
+	__syncthreads();
+	xh_lengths_slow(h, s_leaf, s_lcnt, s_item, s_pc, s_n, fb_pool_lds, tid FB_PREV_ARG);
+	__syncthreads();
+	lens_out[(u64)blockIdx.x * 512u + tid] = h.lens[tid];
 }
 
 // ===================================================================================================================
@@ -837,6 +875,12 @@ void prepare_xh_fallback()
 {
 	static PerDeviceOnce attr;
 	if (attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(xh_fallback_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XH_FB_POOL_BYTES); attr.done(); }
+}
+void launch_xh_huff_slow_debug(hipStream_t st, const uint32_t* counts, uint8_t* lens, uint32_t n)
+{
+	static PerDeviceOnce attr;
+	if (attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(xh_huff_slow_debug_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)XH_FB_POOL_BYTES); attr.done(); }
+	if (n) { hipLaunchKernelGGL(xh_huff_slow_debug_kernel, dim3(n), dim3(512), XH_FB_POOL_BYTES, st, counts, lens); }
 }
 void launch_xh_fallback(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint32_t* fb_list, const uint32_t* fb_count,
                         uint32_t blocks, u64* tokbits, uint8_t* lens, uint16_t* codes, uint32_t* chunk_size)

@@ -62,6 +62,9 @@ def load_oracle():
         lib.orc_time_units_ex.restype = C.c_double
         lib.orc_time_units_ex2.argtypes = lib.orc_time_units_ex.argtypes + [C.POINTER(C.c_double)]
         lib.orc_time_units_ex2.restype = C.c_double
+        for f in (lib.orc_xpress_huff_decisions, lib.orc_lznt1_decisions):
+            f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+            f.restype = C.c_long
         _oracle = lib
     return _oracle
 
@@ -132,6 +135,35 @@ def oracle_compress(fmt, data, cap=None):
     if cap is None:
         cap = lib.orc_max_compressed_size(fmt, len(data))
     return _one_shot(lib.orc_compress, fmt, data, cap)
+
+
+XH_DECISION_FIELDS = ("n", "last", "comp", "limit", "extra", "len1", "len3", "fell_back", "size")
+LZNT1_DECISION_FIELDS = ("n", "S", "raw", "groups", "cross_group")
+
+
+def _decisions(fn, fields, data, chunk):
+    data = bytes(data)
+    cap = (len(data) + chunk - 1) // chunk
+    rec = (C.c_uint64 * (len(fields) * max(cap, 1)))()
+    k = fn(data, len(data), rec, cap)
+    if k != cap:
+        raise RuntimeError("decision probe: %d records for %d chunks" % (k, cap))
+    return [dict(zip(fields, (int(v) for v in rec[i * len(fields):(i + 1) * len(fields)]))) for i in range(cap)]
+
+
+def xpress_huff_decisions(data):
+    """One dict per 64 KiB chunk of what orc_compress decides for it (mscomp_oracle.h): XH_DECISION_FIELDS."""
+    return _decisions(load_oracle().orc_xpress_huff_decisions, XH_DECISION_FIELDS, data, 65536)
+
+
+def lznt1_decisions(data, sa=False):
+    """One dict per 4096-byte chunk (LZNT1_DECISION_FIELDS); sa: the suffix-array dictionary flavour."""
+    lib = load_oracle()
+    lib.orc_set_lznt1_sa_dict(1 if sa else 0)
+    try:
+        return _decisions(lib.orc_lznt1_decisions, LZNT1_DECISION_FIELDS, data, 4096)
+    finally:
+        lib.orc_set_lznt1_sa_dict(0)
 
 
 def oracle_decompress(fmt, data, out_len):

@@ -157,9 +157,12 @@ static inline void lznt1_split(unsigned pos, unsigned* shift, unsigned* mask3)
 
 /* lznt1_compress_chunk (lznt1_compress.cpp:49-94). Returns the payload size, or 0 when the chunk must be
  * stored raw (running size reaches n, :85-86). out must have room for n bytes. */
+/* decision probe (orc_lznt1_decisions): when set, the parse of a chunk that goes raw is finished all the same (sizes only, nothing
+ * more is written) and every chunk leaves a record {n, S, raw, groups, first group whose running size reached n (or groups)} */
+static __thread uint64_t* orc_lz_rec; static __thread size_t orc_lz_nrec, orc_lz_maxrec;
 static unsigned lznt1_chunk(lznt1_dict* d, const uint8_t* c, unsigned n, uint8_t* out)
 {
-	unsigned pos = 0, o = 0;
+	unsigned pos = 0, o = 0, groups = 0, crossed = 0, cross_at = 0;
 	static __thread lznt1_sa_dict sd;
 	const int sa = orc_lznt1_sa;
 	if (sa) { lznt1_sa_fill(&sd, c, n); } else { lznt1_fill(d, c, n); }
@@ -173,10 +176,22 @@ static unsigned lznt1_chunk(lznt1_dict* d, const uint8_t* c, unsigned n, uint8_t
 			if (len >= 3) { put16(grp + g, ((off - 1) << shift) | (len - 3)); g += 2; flags |= 1u << i; pos += len; }
 			else { grp[g++] = c[pos++]; }
 		}
-		if (o + 1 + g >= n) { return 0; }
-		out[o++] = (uint8_t)flags; memcpy(out + o, grp, g); o += g;
+		if (!crossed && o + 1 + g >= n) {
+			if (!orc_lz_rec) { return 0; }
+			crossed = 1; cross_at = groups;
+		}
+		if (crossed) { o += 1 + g; }
+		else { out[o++] = (uint8_t)flags; memcpy(out + o, grp, g); o += g; }
+		++groups;
 	}
-	return o;
+	if (orc_lz_rec) {
+		if (orc_lz_nrec < orc_lz_maxrec) {
+			uint64_t* r = orc_lz_rec + 5 * orc_lz_nrec;
+			r[0] = n; r[1] = o; r[2] = crossed; r[3] = groups; r[4] = crossed ? cross_at : groups;
+		}
+		++orc_lz_nrec;
+	}
+	return crossed ? 0 : o;
 }
 
 /* lznt1_compress (lznt1_compress.cpp:233-273) */
@@ -597,6 +612,9 @@ static size_t xh_emit(const xh_tok* t, size_t nt, const uint8_t* lens, const uin
 	return ob_finish(&b);
 }
 
+/* decision probe (orc_xpress_huff_decisions): when set, every chunk leaves a record
+ * {in_len, last, comp of the LZ parse, limit, extra, matches with len-3 in 15..269, matches with len-3 >= 270, fell_back, final size} */
+static __thread uint64_t* orc_xh_rec; static __thread size_t orc_xh_nrec, orc_xh_maxrec;
 static int xpress_huff_compress_o(const uint8_t* d, size_t n, uint8_t* out, size_t* out_len)
 {
 	const size_t cap = *out_len;
@@ -612,7 +630,7 @@ static int xpress_huff_compress_o(const uint8_t* d, size_t n, uint8_t* out, size
 		const size_t ce = (n - cs > 65536) ? cs + 65536 : n;
 		const int last = (ce == n);
 		uint32_t counts[512]; uint8_t lens[512]; uint16_t codes[512];
-		size_t nt = 0, extra = 0;
+		size_t nt = 0, extra = 0, n1 = 0, n3 = 0;
 		memset(counts, 0, sizeof counts);
 		for (size_t p = cs; p < ce; ) {                                   /* xh_compress_lz77 (:52-153) */
 			const size_t rem = ce - p;
@@ -624,6 +642,7 @@ static int xpress_huff_compress_o(const uint8_t* d, size_t n, uint8_t* out, size
 				tok[nt].sym = (uint16_t)(0x100 | (ob << 4) | (l3 < 15 ? l3 : 15));
 				tok[nt].offlow = (uint16_t)(off ^ (1u << ob)); tok[nt].L = l3;
 				extra += (l3 > 0xFFFF) ? 7 : (l3 >= 270) ? 3 : (l3 >= 15) ? 1 : 0;
+				n1 += (l3 >= 15 && l3 < 270); n3 += (l3 >= 270);
 				p += len;
 			} else { tok[nt].sym = d[p++]; tok[nt].offlow = 0; tok[nt].L = 0; }
 			++counts[tok[nt++].sym];
@@ -633,7 +652,9 @@ static int xpress_huff_compress_o(const uint8_t* d, size_t n, uint8_t* out, size
 		size_t bits = 16;                                                 /* xh_calc_compressed_len (:181-188) */
 		for (unsigned s = 0; s < 512; ++s) { bits += (size_t)(lens[s] + (s >= 0x100 ? ((s >> 4) & 0xF) : 0)) * counts[s]; }
 		size_t comp = (bits + 15) / 16 * 2 + extra;
-		if (comp > (last ? (ce - cs) + 36 : 65538)) {                     /* fallback (:274-280 / :310-316) */
+		const size_t limit = last ? (ce - cs) + 36 : 65538, lz_comp = comp;
+		const int fell_back = comp > limit;
+		if (fell_back) {                                                  /* fallback (:274-280 / :310-316) */
 			memset(counts, 0, sizeof counts);
 			nt = 0;
 			for (size_t p = cs; p < ce; ++p) { tok[nt].sym = d[p]; tok[nt].offlow = 0; tok[nt].L = 0; ++counts[d[p]]; ++nt; }
@@ -642,6 +663,13 @@ static int xpress_huff_compress_o(const uint8_t* d, size_t n, uint8_t* out, size
 			bits = 16;
 			for (unsigned s = 0; s <= 0x100; ++s) { bits += (size_t)lens[s] * counts[s]; }
 			comp = (bits + 15) / 16 * 2;
+		}
+		if (orc_xh_rec) {
+			if (orc_xh_nrec < orc_xh_maxrec) {
+				uint64_t* r = orc_xh_rec + 9 * orc_xh_nrec;
+				r[0] = ce - cs; r[1] = (uint64_t)last; r[2] = lz_comp; r[3] = limit; r[4] = extra; r[5] = n1; r[6] = n3; r[7] = (uint64_t)fell_back; r[8] = 256 + comp;
+			}
+			++orc_xh_nrec;
 		}
 		if (cap - op < 256 + comp) { free(tok); free(tmp); free(L.pred); return ORC_BUF_ERROR; }
 		canonical_codes(lens, codes);
@@ -809,6 +837,36 @@ int orc_decompress(int format, const uint8_t* in, size_t n, uint8_t* out, size_t
 	case ORC_XPRESS_HUFF: return xpress_huff_decompress_o(in, n, out, out_len);
 	default: return ORC_ARG_ERROR;
 	}
+}
+
+/* ===================================================================================================
+ * Decision probes: the SAME code as orc_compress, run once more with a record per chunk of what it decided and by how much.
+ * They choose and label test inputs (tests/thresholds.py); each returns the number of chunks (records past `cap` are counted, not
+ * written) or a negative status.
+ * =================================================================================================*/
+long orc_xpress_huff_decisions(const uint8_t* in, size_t n, uint64_t* rec, size_t cap)
+{
+	size_t out_len = orc_max_compressed_size(ORC_XPRESS_HUFF, n);
+	uint8_t* out = (uint8_t*)malloc(out_len + 16);
+	if (!out) { return ORC_MEM_ERROR; }
+	orc_xh_rec = rec; orc_xh_nrec = 0; orc_xh_maxrec = cap;
+	const int st = xpress_huff_compress_o(in, n, out, &out_len);
+	const long k = (long)orc_xh_nrec;
+	orc_xh_rec = NULL;
+	free(out);
+	return st == ORC_OK ? k : (long)st;
+}
+long orc_lznt1_decisions(const uint8_t* in, size_t n, uint64_t* rec, size_t cap)
+{
+	size_t out_len = orc_max_compressed_size(ORC_LZNT1, n);
+	uint8_t* out = (uint8_t*)malloc(out_len + 16);
+	if (!out) { return ORC_MEM_ERROR; }
+	orc_lz_rec = rec; orc_lz_nrec = 0; orc_lz_maxrec = cap;
+	const int st = lznt1_compress_o(in, n, out, &out_len);
+	const long k = (long)orc_lz_nrec;
+	orc_lz_rec = NULL;
+	free(out);
+	return st == ORC_OK ? k : (long)st;
 }
 
 /* ===================================================================================================

@@ -36,6 +36,17 @@ void orc_lznt1_match_table(const uint8_t* chunk, unsigned n, uint16_t* len, uint
  * p >= n-2 are set to len 2. No lagging-fill rule here (that is parse state, not dictionary state). */
 void orc_xpress_match_table(const uint8_t* buf, size_t n, uint32_t max_offset, uint32_t* len, uint32_t* off);
 
+/* Decision probes: orc_compress's own code, run with one record of uint64 per chunk. They return the number of chunks (records past
+ * `cap` are counted, not written) or a negative status.
+ *   Xpress+Huffman, 9 words per 64 KiB chunk: in_len, last, comp (xh_calc_compressed_len of the LZ parse), limit (65538, or in_len + 36
+ *     for the last chunk), extra (raw length bytes), matches with len-3 in 15..269, matches with len-3 >= 270, fell_back (comp > limit),
+ *     final size of the chunk (256 + the size of what was written).
+ *   LZNT1, 5 words per chunk: n, S (body size of the finished parse: the early exit to raw is ignored), raw (S >= n), groups of eight
+ *     tokens, index of the first group whose running size reached n (= groups when none did). Honours orc_set_lznt1_sa_dict. */
+enum { ORC_XH_DECISION_WORDS = 9, ORC_LZNT1_DECISION_WORDS = 5 };
+long orc_xpress_huff_decisions(const uint8_t* in, size_t n, uint64_t* records, size_t cap);
+long orc_lznt1_decisions(const uint8_t* in, size_t n, uint64_t* records, size_t cap);
+
 /* Multi-threaded "independent units" driver used for the cpu_baseline timing and for batch parity:
  * unit i = in[in_off[i] .. in_off[i+1]) compressed with one one-shot call into out[out_off[i] ..
  * out_off[i+1]) ; out_len[i] receives the size, status[i] the status. threads <= 0 -> 1. */
