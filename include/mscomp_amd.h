@@ -220,8 +220,8 @@ MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* ctx, MSCompForma
                                                 uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status);
 
 /* Decompress plans with device tables: created once from bounds, executed many times with unit tables that GPU work earlier on the ctx stream
- * has written (the d_out_len of a compress plan, the d_need of the size query, the offsets of mscomp_amd_layout_dev or of
- * mscomp_amd_compact_batch). n_units is fixed when the plan is created. Two caps apply to the units, summed in unit order:
+ * has written (the d_out_len of a compress plan or dev plan, the d_need of a size dev plan or of the size query, the offsets of
+ * mscomp_amd_layout_dev, mscomp_amd_compact_dev or mscomp_amd_compact_batch). n_units is fixed when the plan is created. Two caps apply to the units, summed in unit order:
  *   total in_len  <= in_total_max   (across all units)
  *   total out_cap <= out_total_max  (across all units)
  * d_in_off, d_in_len, d_out_off, d_out_cap: device arrays of n_units uint64, read when the work runs on the ctx stream.
@@ -235,7 +235,7 @@ MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* ctx, MSCompForma
  *                 capture it replays a graph of its own from its second execution on, captured again whenever one of its pointers changes.
  *                 MSCOMP_ARG_ERROR for a null plan or array (d_in / d_out may be null when the matching bound is 0).
  *   Plan kinds:   mscomp_amd_plan_execute and mscomp_amd_plan_execute_size return MSCOMP_ARG_ERROR for a dev plan, mscomp_amd_plan_execute_dev
- *                 for any other plan, without enqueueing anything. mscomp_amd_plan_destroy frees every kind.
+ *                 for any other plan (a size dev plan included), without enqueueing anything. mscomp_amd_plan_destroy frees every kind.
  *   Creation:     the argument checks of mscomp_amd_plan_create_decompress (MSCOMP_ARG_ERROR for a null ctx or plan pointer or a bad format);
  *                 MSCOMP_MEM_ERROR when the scratch for the bounds cannot be reserved. The scratch is reserved for the bounds, once.
  * Dev plans decode without the optional paths that need tables chosen on the host (DESIGN_DECODERS.md): below 512 KiB of Xpress input and
@@ -249,6 +249,37 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* plan, const uint8_t* d
  * 2^64 - 1 stays there), on the ctx stream: it turns d_need of the size query, or d_out_len of a compress plan, into a packed layout without
  * leaving the GPU. d_cap and d_off are device arrays (uint64). Asynchronous; allocates nothing. */
 MSCompStatus mscomp_amd_layout_dev(mscomp_amd_ctx* ctx, size_t n_units, const uint64_t* d_cap, uint64_t align, uint64_t* d_off);
+
+/* Size plans with device tables: the decompressed-size query (mscomp_amd_plan_create_size) of a batch whose tables GPU work has written -- the
+ * d_out_len of a compress dev plan with the offsets of mscomp_amd_plan_layout_dev or mscomp_amd_compact_dev, say. Created once from bounds;
+ * n_units is fixed when the plan is created. One cap applies to the units, summed in unit order:
+ *   total in_len  <= in_total_max   (across all units)
+ * A size plan's scratch follows the input alone (no token slots, no candidate token scratch): there is no output bound.
+ * d_in_off, d_in_len, d_limit: device arrays of n_units uint64, read when the work runs on the ctx stream. d_limit = NULL means no limit
+ * (UINT64_MAX for every unit), as for the host form.
+ *   Per-unit results: for every unit that passes the checks below, d_status[i], d_out_len[i] and d_need[i] are exactly those of a size plan
+ *                 (mscomp_amd_plan_create_size) with the same offset, length and limit -- LZNT1's need = length + 1 for a stream that ends in
+ *                 the End_of_buffer header included.
+ *   Units that fail the checks: a unit gets MSCOMP_ARG_ERROR, d_out_len = d_need = 0, and nothing is read for it, if its in_len is above
+ *                 0xFFFFF000, or the running total of in_len up to and including it is above in_total_max (running totals stay at
+ *                 2^64 - 1 once they get there). The other units are unaffected. Offsets are the caller's responsibility.
+ *   Execution:    mscomp_amd_plan_execute_size_dev is asynchronous on the ctx stream; it allocates nothing, does not synchronize and reads nothing
+ *                 back to the host. Its launches are kernels only (d_need too is written by a kernel). It may run while the ctx stream is being
+ *                 captured into a graph (it then enqueues plain launches). Outside capture it replays a graph of its own from its second
+ *                 execution on, captured again whenever one of its pointers changes. MSCOMP_ARG_ERROR for a null plan or array (d_in may be
+ *                 null when in_total_max is 0, d_limit always).
+ *   Plan kinds:   mscomp_amd_plan_execute, mscomp_amd_plan_execute_size and mscomp_amd_plan_execute_dev return MSCOMP_ARG_ERROR for a size dev
+ *                 plan, mscomp_amd_plan_execute_size_dev for any other plan, without enqueueing anything. mscomp_amd_plan_destroy frees it.
+ *   Creation:     the argument checks of mscomp_amd_plan_create_decompress_dev (MSCOMP_ARG_ERROR for a null ctx or plan pointer, a bad format,
+ *                 n_units above 0x7FFFFFF0); MSCOMP_MEM_ERROR when the bounds exceed what the scratch can address or the scratch cannot be
+ *                 reserved. The scratch is reserved for (n_units, in_total_max), once, and never grows.
+ * As decompress dev plans, size dev plans take only the paths that need no tables chosen on the host (DESIGN_DECODERS.md): an Xpress stream of
+ * 512 KiB or more is sized by the one-wave walk instead of by segments -- the same answers, more slowly. */
+MSCompStatus mscomp_amd_plan_create_size_dev(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units,
+                                             uint64_t in_total_max, mscomp_amd_plan** plan);
+MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* plan, const uint8_t* d_in,
+                                              const uint64_t* d_in_off, const uint64_t* d_in_len, const uint64_t* d_limit,
+                                              uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status);
 
 /* Compress plans with device tables: the compressing half of the same pipeline. Created once from bounds and executed with
  * mscomp_amd_plan_execute_dev (the same nine arguments) on unit tables that GPU work has written -- the d_out_len of a decompress dev plan, say,
@@ -291,6 +322,23 @@ MSCompStatus mscomp_amd_plan_layout_dev(mscomp_amd_ctx* ctx, MSCompFormat format
 uint64_t     mscomp_amd_plan_layout(MSCompFormat format, size_t n_units, const uint64_t* in_len, uint64_t align, uint64_t* out_off, uint64_t* out_cap);
 MSCompStatus mscomp_amd_compact_batch(mscomp_amd_ctx* ctx, size_t n_units, const uint8_t* d_out, const uint64_t* out_off, const uint64_t* out_cap,
                                       const uint64_t* d_out_len, uint8_t* d_packed, uint64_t* d_packed_off);
+
+/* Compaction with device tables: packs n_units byte ranges of d_src back to back into d_packed without the host knowing where they are or
+ * how long -- the outputs of a compress dev plan, say (d_src_off = the offsets of mscomp_amd_plan_layout_dev, d_len = the plan's d_out_len;
+ * a unit that is not MSCOMP_OK has length 0 there). d_src_off, d_len: device arrays of n_units uint64; d_packed_off: n_units + 1.
+ *   d_packed_off[0..n_units] = the exclusive running sum of d_len[i] rounded up to `align` (0 counts as 1), d_packed_off[n_units] = total,
+ *                 a sum beyond 2^64 - 1 stays there: exactly what mscomp_amd_layout_dev(ctx, n_units, d_len, align, ...) writes.
+ *   d_packed:     the d_len[i] bytes at d_src + d_src_off[i] go to d_packed + d_packed_off[i]; the padding between two units is written as
+ *                 zero, so the packed bytes [0, total) are reproducible. Source addresses may have any alignment. d_packed must not overlap
+ *                 the source ranges.
+ *   packed_cap:   nothing is written at or behind d_packed + packed_cap. A unit whose end d_packed_off[i] + d_len[i] lies beyond packed_cap is
+ *                 not copied at all (no partial unit); the caller learns of it from d_packed_off[n_units] > packed_cap, on the device.
+ * Asynchronous on the ctx stream: two kernel launches whose geometry depends on n_units and the device only; no host table, no upload, no
+ * synchronisation, no allocation, no scratch -- it may run while the ctx stream is being captured into a graph. MSCOMP_ARG_ERROR for a null
+ * ctx or d_packed_off, for a null d_src, d_src_off, d_len or d_packed with n_units > 0, and for n_units above 0x7FFFFFF0. n_units = 0 writes
+ * d_packed_off[0] = 0 (from a kernel). */
+MSCompStatus mscomp_amd_compact_dev(mscomp_amd_ctx* ctx, size_t n_units, const uint8_t* d_src, const uint64_t* d_src_off,
+                                    const uint64_t* d_len, uint64_t align, uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_packed_off);
 
 /* ---- measurement hooks (bench.py / profiles) ---- */
 /* When enabled, every kernel launch of plan_execute is bracketed by hipEvents on the ctx stream. */

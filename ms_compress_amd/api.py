@@ -37,6 +37,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_plan_create_size", "mscomp_amd_plan_execute_size", "mscomp_amd_decompressed_size_batch",
     "mscomp_amd_plan_create_decompress_dev", "mscomp_amd_plan_execute_dev", "mscomp_amd_layout_dev",
     "mscomp_amd_plan_create_compress_dev", "mscomp_amd_plan_layout_dev",
+    "mscomp_amd_plan_create_size_dev", "mscomp_amd_plan_execute_size_dev", "mscomp_amd_compact_dev",
 ]
 
 
@@ -115,6 +116,12 @@ def load_library():
     lib.mscomp_amd_plan_create_compress_dev.restype = C.c_int
     lib.mscomp_amd_plan_layout_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout_dev.restype = C.c_int
+    lib.mscomp_amd_plan_create_size_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_plan_create_size_dev.restype = C.c_int
+    lib.mscomp_amd_plan_execute_size_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+    lib.mscomp_amd_plan_execute_size_dev.restype = C.c_int
+    lib.mscomp_amd_compact_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.mscomp_amd_compact_dev.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -371,6 +378,54 @@ class CompressDevPlan(DevPlan):
         st = ctx.lib.mscomp_amd_plan_create_compress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.in_unit_max, C.byref(self._h))
         if st != MSCOMP_OK:
             raise MSCompError(st, "mscomp_amd_plan_create_compress_dev")
+
+
+class SizeDevPlan(DevPlan):
+    """A size plan with device tables (mscomp_amd_plan_create_size_dev): made once for n_units units whose in_len sum to at most in_total_max,
+    then executed with unit tables (offsets, lengths, optional limits) that live on the device."""
+
+    def __init__(self, ctx, fmt, n_units, in_total_max):
+        self.ctx, self.fmt, self.n_units = ctx, int(fmt), int(n_units)
+        self.in_total_max = int(in_total_max)
+        self._h = C.c_void_p()
+        st = ctx.lib.mscomp_amd_plan_create_size_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, C.byref(self._h))
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_plan_create_size_dev")
+
+    def execute(self, d_in, d_in_off, d_in_len, d_out_len, d_need, d_status, d_limit=None):
+        """Enqueue on the ctx stream (nothing is synchronized or read back). Arguments are torch CUDA tensors: uint8 input, int64 / uint64
+        tables of n_units entries (offsets, lengths, d_limit or None = no limit; results d_out_len, d_need), int32 d_status."""
+        ptrs = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status)]
+        st = self.ctx.lib.mscomp_amd_plan_execute_size_dev(self._h, *ptrs)
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_plan_execute_size_dev")
+
+
+def compact_dev(ctx, d_src, d_src_off, d_len, align=1, d_packed=None, d_packed_off=None, packed_cap=None):
+    """mscomp_amd_compact_dev: the d_len[i] bytes at d_src + d_src_off[i] packed in unit order into d_packed, every start rounded up to
+    ``align``, the padding zeroed; d_packed_off (int64, n + 1) gets the offsets layout_dev(d_len, align) would write, the last one the total.
+    All tables are device tensors; enqueued on the ctx stream, nothing is synchronized or read back. Returns (d_packed, d_packed_off) and
+    allocates only the arguments left None. ``packed_cap`` is the room of d_packed in bytes (default: all of a given d_packed). When d_packed
+    is None its size is ``packed_cap`` -- the total is NOT read back to size it -- or, without one, d_src.numel() + n * (align - 1): enough
+    whenever the units do not overlap in d_src. A unit that ends beyond packed_cap is left out whole; d_packed_off[n] > packed_cap says so."""
+    import torch
+    n = d_len.numel()
+    align = max(1, int(align))
+    if d_packed is None:
+        if packed_cap is None:
+            packed_cap = d_src.numel() + n * (align - 1)
+        d_packed = torch.empty(max(1, int(packed_cap)), dtype=torch.uint8, device=d_len.device)
+    elif packed_cap is None:
+        packed_cap = d_packed.numel()
+    if int(packed_cap) > d_packed.numel():
+        raise ValueError("packed_cap exceeds d_packed")
+    if d_packed_off is None:
+        d_packed_off = torch.empty(n + 1, dtype=torch.int64, device=d_len.device)
+    st = ctx.lib.mscomp_amd_compact_dev(ctx._h, n, C.c_void_p(d_src.data_ptr()), C.c_void_p(d_src_off.data_ptr()), C.c_void_p(d_len.data_ptr()),
+                                        align, C.c_void_p(d_packed.data_ptr()), int(packed_cap), C.c_void_p(d_packed_off.data_ptr()))
+    if st != MSCOMP_OK:
+        raise MSCompError(st, "mscomp_amd_compact_dev")
+    return d_packed, d_packed_off
 
 
 def plan_layout_dev(ctx, fmt, d_in_len, align=16, d_off=None, d_cap=None):

@@ -54,6 +54,7 @@ const uint32_t XH_FB_BLOCKS = 256;                     // persistent blocks of t
 
 struct mscomp_amd_ctx {
 	int device = 0;
+	uint32_t cpd_blocks = 0;                           // the fixed grid of mscomp_amd_compact_dev on this device (asked once, here: never inside a capture)
 	hipStream_t stream = nullptr;
 	DevBuf slots, slot_size, prefix, tile_sums;        // chunk scratch (grow-only, shared by all plans of the ctx)
 	DevBuf lzrec;                                      // LZNT1 parse records per chunk (LZNT1_REC bytes: match tokens per window)
@@ -91,7 +92,7 @@ struct mscomp_amd_plan {
 	MSCompFormat format = MSCOMP_NONE;
 	bool decompress = false;
 	bool sizing = false;                               // a decompressed-size plan (mscomp_amd_plan_create_size): out_cap holds the limits, nothing is decoded
-	bool dev = false;                                  // a plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev / _compress_dev)
+	bool dev = false;                                  // a plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev / _compress_dev; with sizing: _size_dev)
 	uint64_t in_total_max = 0, out_total_max = 0;      // ... and the bounds its scratch was reserved for
 	uint64_t in_unit_max = 0;                          // (compress dev plans: the largest unit they take)
 	uint32_t n_units = 0, n_chunks = 0;
@@ -112,7 +113,7 @@ struct mscomp_amd_plan {
 	// the launch sequence of plan_execute as a hipGraph: captured on the plan's second execution, replayed while the
 	// arguments and the scratch buffers stay where they were
 	hipGraphExec_t gexec = nullptr;
-	const void* g_args[9] = {};                        // (a dev plan's graph: its nine pointers)
+	const void* g_args[9] = {};                        // (a dev plan's graph: its eight pointers, a size dev plan's seven)
 	uint64_t g_epoch = 0, g_mode = 0;
 	uint32_t executions = 0;
 };
@@ -227,6 +228,7 @@ MSCompStatus mscomp_amd_ctx_create(int device, void* hip_stream, mscomp_amd_ctx*
 	mscomp_amd_ctx* c = new (std::nothrow) mscomp_amd_ctx();
 	if (!c) { return MSCOMP_MEM_ERROR; }
 	c->device = device; c->stream = (hipStream_t)hip_stream;
+	c->cpd_blocks = compact_dev_blocks();
 	*out = c;
 	return MSCOMP_OK;
 }
@@ -813,7 +815,7 @@ static void size_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out
 
 MSCompStatus mscomp_amd_plan_execute_size(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status)
 {
-	if (!p || !p->sizing || (p->n_units && (!d_out_len || !d_need || !d_status)) || (p->total_in && !d_in)) { return MSCOMP_ARG_ERROR; }
+	if (!p || !p->sizing || p->dev || (p->n_units && (!d_out_len || !d_need || !d_status)) || (p->total_in && !d_in)) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_ctx* c = p->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
@@ -882,6 +884,8 @@ MSCompStatus mscomp_amd_plan_create_decompress_dev(mscomp_amd_ctx* c, MSCompForm
 	if (ok && format != MSCOMP_LZNT1) { ok = c->dz_tok.reserve(toks * 4 + 256) && c->dz_ntok.reserve((N + 1) * 8); }
 	if (ok && format == MSCOMP_XPRESS_HUFF) { ok = c->dz_xhc.reserve((N + 1) * 8 + cands * (4 * 4 + 3 * 8) + 64); }
 	if (!ok) { (void)hipGetLastError(); p->tables.release(); delete p; return MSCOMP_MEM_ERROR; }
+	// the one-time kernel attributes of the instances this plan launches: set now, so that no first launch happens inside a caller's capture
+	if (format == MSCOMP_LZNT1) { prepare_lzd_segments(true); } else { prepare_lz_copy_block(); }
 	u64* san = static_cast<u64*>(p->tables.p);
 	p->bt.in_off = san; p->bt.in_len = san + N; p->bt.out_off = san + 2 * N; p->bt.out_cap = san + 3 * N;
 	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(san + 4 * N);
@@ -1050,35 +1054,24 @@ static void dev_compress_launch(mscomp_amd_plan* p, const uint8_t* d_in, const u
 	{ KernelTimer t(c, "dv_reject_kernel"); launch_dev_reject(st, reject, n, d_out_len, d_status); }
 }
 
-MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
-                                         uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+// The launches of a dev plan, given as `launch`. While the caller captures the ctx stream, plain launches go into the caller's graph. Otherwise,
+// from the second execution on, the launches are replayed as the plan's own graph (as plan_execute does), captured again whenever a pointer
+// (args), the scratch or a kernel switch moved. A stream whose capture state cannot be read counts as captured.
+extern "C++" template <class Launch>
+static MSCompStatus dev_run(mscomp_amd_plan* p, const void* const (&args)[9], const Launch& launch)
 {
-	if (!p || !p->dev) { return MSCOMP_ARG_ERROR; }
-	if (p->n_units && (!d_in_off || !d_in_len || !d_out_off || !d_out_cap || !d_out_len || !d_status)) { return MSCOMP_ARG_ERROR; }
-	if ((p->in_total_max && !d_in) || (p->out_total_max && !d_out)) { return MSCOMP_ARG_ERROR; }
-	if (!p->decompress && p->n_units && !d_out) { return MSCOMP_ARG_ERROR; }   // (a compress plan has no output bound: an empty unit may get LZNT1's 00 00)
-	if (p->n_units == 0) { return MSCOMP_OK; }
 	mscomp_amd_ctx* c = p->ctx;
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (p->decompress) { note_modes(p); }
-	void (*const launch)(mscomp_amd_plan*, const uint8_t*, const uint64_t*, const uint64_t*, uint8_t*, const uint64_t*, const uint64_t*, uint64_t*, int32_t*) =
-		p->decompress ? dev_launch : dev_compress_launch;
-	// While the caller captures the ctx stream, plain launches go into the caller's graph. Otherwise, from the second execution on, the
-	// launches are replayed as the plan's own graph (as plan_execute does), captured again whenever a pointer, the scratch or a kernel
-	// switch moved. A stream whose capture state cannot be read counts as captured.
 	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
 	if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
 	static const bool no_graph = getenv("MSCOMP_AMD_NO_GRAPH") != nullptr;
 	if (cs == hipStreamCaptureStatusNone && !no_graph && !c->profiling && ++p->executions >= 2) {
-		const void* args[9] = { d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, nullptr };
 		const uint64_t mode_now = g_mode_epoch.load(std::memory_order_acquire);
 		const bool same = p->gexec && p->g_epoch == c->epoch && p->g_mode == mode_now && memcmp(p->g_args, args, sizeof args) == 0;
 		if (!same) {
 			if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
 			hipGraph_t graph = nullptr;
 			if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-				launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status);
+				launch();
 				const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
 				if (ee == hipSuccess && graph && hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0) == hipSuccess) {
 					p->g_epoch = c->epoch; p->g_mode = mode_now; memcpy(p->g_args, args, sizeof args);
@@ -1089,8 +1082,124 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in
 		}
 		if (p->gexec) { return hipGraphLaunch(p->gexec, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
 	}
-	launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status);
+	launch();
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
+}
+
+MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                         uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!p || !p->dev || p->sizing) { return MSCOMP_ARG_ERROR; }
+	if (p->n_units && (!d_in_off || !d_in_len || !d_out_off || !d_out_cap || !d_out_len || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if ((p->in_total_max && !d_in) || (p->out_total_max && !d_out)) { return MSCOMP_ARG_ERROR; }
+	if (!p->decompress && p->n_units && !d_out) { return MSCOMP_ARG_ERROR; }   // (a compress plan has no output bound: an empty unit may get LZNT1's 00 00)
+	if (p->n_units == 0) { return MSCOMP_OK; }
+	mscomp_amd_ctx* c = p->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (p->decompress) { note_modes(p); }
+	const void* args[9] = { d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, nullptr };
+	return dev_run(p, args, [&] { (p->decompress ? dev_launch : dev_compress_launch)(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status); });
+}
+
+// ---- size plans with device tables (include/mscomp_amd.h): the size query of a batch whose tables GPU work has written ----
+// A decompress dev plan whose table pass takes the limits for the capacities (devplan.hip dv_tables_kernel<true>) and whose launches are those
+// of size_launch without the segment phases of large Xpress streams. p->tables is laid out as a decompress dev plan's (the token prefix is
+// written and not used: a size plan stores no tokens). Scratch follows the input alone.
+MSCompStatus mscomp_amd_plan_create_size_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, mscomp_amd_plan** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	// the bounds of mscomp_amd_plan_create_decompress_dev with no output bound: a unit's candidate slots are then bounded by its input
+	// (in_len / 260 + 1, a quarter more, + 2), whatever its limit
+	const uint64_t N = n_units, I = in_total_max < N * 0xFFFFF000ull ? in_total_max : N * 0xFFFFF000ull;
+	uint64_t chunks = N, cands = 0;
+	if (format == MSCOMP_LZNT1) { chunks = N + I / LZD_SEG; }
+	if (format == MSCOMP_XPRESS_HUFF) { chunks = N + I / XHC_TILE_BYTES; }
+	if (chunks > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
+	if (format == MSCOMP_XPRESS_HUFF) {
+		const uint64_t most = I / 260u + N;
+		cands = most + most / 4 + 2 * N;
+		if (cands > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
+	}
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	mscomp_amd_plan* p = new (std::nothrow) mscomp_amd_plan();
+	if (!p) { return MSCOMP_MEM_ERROR; }
+	p->ctx = c; p->format = format; p->decompress = true; p->sizing = true; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
+	p->in_total_max = in_total_max; p->total_in = in_total_max; p->xhc_slots = (uint32_t)cands;
+	bool ok = p->tables.reserve(dev_table_words(N) * 8);
+	if (ok && format == MSCOMP_LZNT1) {
+		ok = c->prefix.reserve((chunks + 2) * sizeof(uint64_t)) && c->tile_sums.reserve((chunks / 1024 + 4) * sizeof(uint64_t)) &&
+		     c->dz_cin.reserve(chunks * LZD_SLOTS * 4 + 64) && c->dz_csize.reserve(chunks * LZD_SLOTS * 2 + 64) &&
+		     c->dz_unit.reserve((chunks * (5 * LZD_K + 2) + N * 2 + 8) * 4);
+	}
+	if (ok && format != MSCOMP_LZNT1) { ok = c->dz_ntok.reserve((N + 1) * 8); }
+	if (ok && format == MSCOMP_XPRESS_HUFF) { ok = c->dz_xhc.reserve((N + 1) * 8 + cands * (4 * 4 + 3 * 8) + 64); }
+	if (!ok) { (void)hipGetLastError(); p->tables.release(); delete p; return MSCOMP_MEM_ERROR; }
+	if (format == MSCOMP_LZNT1) { prepare_lzd_segments(true); }     // (its first execution may be captured by the caller)
+	u64* san = static_cast<u64*>(p->tables.p);
+	p->bt.in_off = san; p->bt.in_len = san + N; p->bt.out_off = san + 2 * N; p->bt.out_cap = san + 3 * N;
+	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(san + 4 * N);
+	p->bt.n_units = p->n_units; p->bt.n_chunks = p->n_chunks;
+	*out = p;
+	return MSCOMP_OK;
+}
+
+static void size_dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, const uint64_t* d_limit,
+                            uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status)
+{
+	mscomp_amd_ctx* c = p->ctx;
+	hipStream_t st = c->stream;
+	const uint32_t n = p->n_units;
+	u64* san = static_cast<u64*>(p->tables.p);
+	uint32_t* chunk_prefix = reinterpret_cast<uint32_t*>(san + 4 * (size_t)n);
+	u64* tp = san + 4 * (size_t)n + (n + 2u) / 2 + 1;                 // token prefix (not used), then the candidate prefix
+	uint32_t* reject = reinterpret_cast<uint32_t*>(tp + 2 * ((size_t)n + 1));
+	{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_stables(st, (int)p->format, n, p->in_total_max, d_in_off, d_in_len, d_limit, san, chunk_prefix, tp, reject); }
+	switch (p->format) {
+	case MSCOMP_LZNT1: {                                        // size_launch's sequence on the DEV instance of the segment kernel
+		const LzdBufs b = lzd_bufs(c, p);
+		launch_dev_zero(st, b.selcnt, p->n_chunks);                     // segments past the real count add nothing to the scan
+		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b, true); }
+		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
+		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
+		{ KernelTimer t(c, "lzd_size_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, nullptr, 2); }
+		{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status, d_need); }
+		break;
+	}
+	case MSCOMP_XPRESS: {                                       // every stream by the one-wave walk
+		const XpsTables x = {};
+		{ KernelTimer t(c, "xpt_size_kernel"); launch_xpress_size(st, d_in, p->bt, static_cast<u64*>(c->dz_ntok.p), d_out_len, d_status, 0, x); }
+		break;
+	}
+	default: {                                                  // MSCOMP_XPRESS_HUFF
+		u64* ntok = static_cast<u64*>(c->dz_ntok.p);
+		const XhcBufs xb = xhc_bufs(c, p);
+		static const char* const names[4] = { "xhc_mark_kernel", "xhc_size_kernel", "xhc_chain_kernel", "xhd_size_kernel" };
+		for (int ph = 0; ph < 4; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_huff_size(st, d_in, p->bt, ntok, tp + (n + 1u), p->xhc_slots, xb, d_out_len, d_status, ph, true); }
+		break;
+	}
+	}
+	// rejected units; and need = length where the kernels above did not write it (LZNT1's finalize did)
+	{ KernelTimer t(c, "dv_size_finish_kernel"); launch_dev_size_finish(st, reject, n, d_out_len, d_need, d_status, p->format != MSCOMP_LZNT1); }
+}
+
+MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                              const uint64_t* d_limit, uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status)
+{
+	if (!p || !p->dev || !p->sizing) { return MSCOMP_ARG_ERROR; }
+	if (p->n_units && (!d_in_off || !d_in_len || !d_out_len || !d_need || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if (p->in_total_max && !d_in) { return MSCOMP_ARG_ERROR; }
+	if (p->n_units == 0) { return MSCOMP_OK; }
+	mscomp_amd_ctx* c = p->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	note_modes(p);
+	const void* args[9] = { d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status, nullptr, nullptr };
+	return dev_run(p, args, [&] { size_dev_launch(p, d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status); });
 }
 
 MSCompStatus mscomp_amd_layout_dev(mscomp_amd_ctx* c, size_t n_units, const uint64_t* d_cap, uint64_t align, uint64_t* d_off)
@@ -1157,6 +1266,17 @@ MSCompStatus mscomp_amd_compact_batch(mscomp_amd_ctx* c, size_t n_units, const u
 	if (hipMemcpyAsync(c->cp_tab.p, host.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { return MSCOMP_ERRNO; }
 	const u64* d_off = static_cast<const u64*>(c->cp_tab.p);
 	launch_compact(c->stream, d_out, d_off, reinterpret_cast<const uint32_t*>(d_off + n_units), (uint32_t)n_units, (uint32_t)tiles, d_out_len, d_packed_off, d_packed);
+	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
+}
+
+// Compaction from device tables: one scan launch (the offsets of mscomp_amd_layout_dev) and one copy launch on a grid fixed by the CU count.
+MSCompStatus mscomp_amd_compact_dev(mscomp_amd_ctx* c, size_t n_units, const uint8_t* d_src, const uint64_t* d_src_off, const uint64_t* d_len,
+                                    uint64_t align, uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_packed_off)
+{
+	if (!c || !d_packed_off || (n_units && (!d_src || !d_src_off || !d_len || !d_packed)) || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	launch_compact_dev(c->stream, (uint32_t)n_units, d_src, d_src_off, d_len, align, d_packed, packed_cap, d_packed_off, c->cpd_blocks);
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 

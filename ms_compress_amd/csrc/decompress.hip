@@ -536,12 +536,16 @@ __global__ __launch_bounds__(256) void lzd_finalize_kernel(BatchTables bt, const
 
 __global__ void lzd_clear_kernel(uint32_t* p) { *p = 0; }
 
-void launch_lzd_segments(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b, bool dev)
+void prepare_lzd_segments(bool dev)
 {
-	if (bt.n_units == 0) { return; }
 	static PerDeviceOnce attr, attr_dev;
 	if (!dev && attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lzd_seg_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LZD_LDS); attr.done(); }
 	if (dev && attr_dev.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lzd_seg_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LZD_LDS); attr_dev.done(); }
+}
+void launch_lzd_segments(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b, bool dev)
+{
+	if (bt.n_units == 0) { return; }
+	prepare_lzd_segments(dev);
 	hipLaunchKernelGGL(lzd_clear_kernel, dim3(1), dim3(1), 0, st, b.irregular + bt.n_units);
 	if (dev) { hipLaunchKernelGGL(lzd_seg_kernel<true>, dim3(bt.n_chunks), dim3(LZD_THREADS), LZD_LDS, st, d_in, bt, b.cin, b.segL, b.segE, b.segcnt, b.segstop, b.segoff); }
 	else { hipLaunchKernelGGL(lzd_seg_kernel<false>, dim3(bt.n_chunks), dim3(LZD_THREADS), LZD_LDS, st, d_in, bt, b.cin, b.segL, b.segE, b.segcnt, b.segstop, b.segoff); }
@@ -1913,6 +1917,11 @@ __global__ __launch_bounds__(LZB_NT) void lz_copy_block_kernel(BatchTables bt, c
 	}
 }
 
+void prepare_lz_copy_block()
+{
+	if (g_lzb_attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_copy_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzbLds)); g_lzb_attr.done(); }
+}
+
 void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
                                    const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb,
                                    uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, bool dev)
@@ -1933,7 +1942,7 @@ void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const Ba
 	        hipLaunchKernelGGL(xhc_parse_kernel<2>, dim3(n_slots), dim3(64), 0, st, d_in, bt, tok_prefix, cand_prefix, xb, tok); break;
 	case 4: hipLaunchKernelGGL(xhd_parse_kernel<true>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, xb.mode); break;
 	default: {
-		if (g_lzb_attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_copy_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzbLds)); g_lzb_attr.done(); }
+		prepare_lz_copy_block();
 		hipLaunchKernelGGL(lz_copy_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap);
 		hipLaunchKernelGGL(lz_copy_block_kernel, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap);
 		break;
@@ -1942,11 +1951,11 @@ void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const Ba
 }
 
 void launch_xpress_huff_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, const u64* cand_prefix, uint32_t n_slots,
-                             const XhcBufs& xb, u64* d_out_len, int32_t* d_status, int phase)
+                             const XhcBufs& xb, u64* d_out_len, int32_t* d_status, int phase, bool dev)
 {
 	if (bt.n_units == 0) { return; }
 	switch (phase) {
-	case 0: launch_xpress_huff_decompress(st, d_in, bt, nullptr, nullptr, ntok, cand_prefix, n_slots, xb, nullptr, d_out_len, d_status, 0, ~(u64)0); break;
+	case 0: launch_xpress_huff_decompress(st, d_in, bt, nullptr, nullptr, ntok, cand_prefix, n_slots, xb, nullptr, d_out_len, d_status, 0, ~(u64)0, dev); break;
 	case 1: hipLaunchKernelGGL(xhc_parse_kernel<3>, dim3(n_slots), dim3(64), 0, st, d_in, bt, (const u64*)nullptr, cand_prefix, xb, (uint32_t*)nullptr); break;
 	case 2: launch_xpress_huff_decompress(st, d_in, bt, nullptr, nullptr, ntok, cand_prefix, n_slots, xb, nullptr, d_out_len, d_status, 2, ~(u64)0); break;
 	default: hipLaunchKernelGGL(xhd_parse_kernel<false>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, (const u64*)nullptr, (uint32_t*)nullptr, ntok, d_out_len, d_status, (const uint32_t*)xb.mode); break;
@@ -1987,7 +1996,7 @@ void launch_xpress_decompress_tokens(hipStream_t st, const uint8_t* d_in, const 
 		return;
 	}
 	if (phase == 0) { hipLaunchKernelGGL(xpt_parse_kernel<true>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, (const uint32_t*)(x.n_big ? x.done : nullptr)); return; }
-	if (g_lzb_attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_copy_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzbLds)); g_lzb_attr.done(); }
+	prepare_lz_copy_block();
 	if (phase == 1) { hipLaunchKernelGGL(lz_copy_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap); }
 	else { hipLaunchKernelGGL(lz_copy_block_kernel, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap); }
 }

@@ -1,6 +1,7 @@
 // devplan.hip -- the tables of a decompress plan built on the device (mscomp_amd_plan_create_decompress_dev / _execute_dev), those of a
-// compress plan (mscomp_amd_plan_create_compress_dev), and the device-side layout scans (mscomp_amd_layout_dev, mscomp_amd_plan_layout_dev). The decoders then run on these tables unchanged (DESIGN_DECODERS.md, "Plans with
-// device tables").
+// compress plan (mscomp_amd_plan_create_compress_dev) and of a size plan (mscomp_amd_plan_create_size_dev), the device-side layout scans
+// (mscomp_amd_layout_dev, mscomp_amd_plan_layout_dev) and compaction from device tables (mscomp_amd_compact_dev). The decoders then run on
+// these tables unchanged (DESIGN_DECODERS.md, "Plans with device tables").
 #include "kernels.h"
 
 namespace msc {
@@ -33,6 +34,9 @@ __device__ __forceinline__ void dv_block_scan(u64 (&v)[K], u64 (&carry)[K], u64 
 	__syncthreads();
 }
 
+// SIZING (size plans): out_off is not read (every unit's is 0), out_cap holds the limits (null: 2^64 - 1 for every unit) and there is no
+// bound on their sum
+template <bool SIZING>
 __global__ __launch_bounds__(DV_THREADS) void dv_tables_kernel(int format, uint32_t n, u64 in_max, u64 out_max,
                                                               const u64* __restrict__ in_off, const u64* __restrict__ in_len,
                                                               const u64* __restrict__ out_off, const u64* __restrict__ out_cap,
@@ -47,10 +51,10 @@ __global__ __launch_bounds__(DV_THREADS) void dv_tables_kernel(int format, uint3
 	for (uint32_t base = 0; base < n; base += DV_THREADS) {
 		const uint32_t i = base + tid;
 		const bool live = i < n;
-		const u64 len = live ? in_len[i] : 0, cap = live ? out_cap[i] : 0;
+		const u64 len = live ? in_len[i] : 0, cap = !live ? 0 : SIZING && !out_cap ? ~(u64)0 : out_cap[i];
 		u64 r[2] = {len, cap};
 		dv_block_scan<2>(r, run, s_w);                                   // running totals up to and including unit i
-		const bool rej = live && (len > 0xFFFFF000ull || r[0] > in_max || r[1] > out_max);
+		const bool rej = live && (len > 0xFFFFF000ull || r[0] > in_max || (!SIZING && r[1] > out_max));
 		const u64 L = rej ? 0 : len, C = rej ? 0 : cap;                  // a rejected unit is an empty unit without room
 		// the host formulas of plan_create_impl: chunks_of(format, true, L); token slots; Xpress+Huffman candidate slots
 		u64 c[3] = {0, 0, 0};
@@ -65,7 +69,7 @@ __global__ __launch_bounds__(DV_THREADS) void dv_tables_kernel(int format, uint3
 				const u64 by_out = C / 65536u + 2u, by_len = L / 260u + 1u, most = by_out < by_len ? by_out : by_len;
 				c[2] = most + most / 4u + 2u;
 			}
-			san[i] = rej ? 0 : in_off[i]; san[n + i] = L; san[2u * (size_t)n + i] = rej ? 0 : out_off[i]; san[3u * (size_t)n + i] = C;
+			san[i] = rej ? 0 : in_off[i]; san[n + i] = L; san[2u * (size_t)n + i] = rej || SIZING ? 0 : out_off[i]; san[3u * (size_t)n + i] = C;
 			reject[i] = rej ? 1u : 0u;
 		}
 		dv_block_scan<3>(c, cnt, s_w);                                   // inclusive: the prefix entry behind unit i
@@ -109,6 +113,17 @@ __global__ __launch_bounds__(256) void dv_reject_kernel(const uint32_t* __restri
 	if (u < n && reject[u]) { d_status[u] = -2; d_out_len[u] = 0; }   // MSCOMP_ARG_ERROR
 }
 
+// The last kernel of a size dev plan: a rejected unit gets MSCOMP_ARG_ERROR with length and need 0; need = length for the others when the
+// format's size kernels do not write need themselves (Xpress, Xpress+Huffman: every length test is "does it fit")
+__global__ __launch_bounds__(256) void dv_size_finish_kernel(const uint32_t* __restrict__ reject, uint32_t n, u64* __restrict__ d_out_len, u64* __restrict__ d_need,
+                                                            int32_t* __restrict__ d_status, int copy_need)
+{
+	const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+	if (u >= n) { return; }
+	if (reject[u]) { d_status[u] = -2; d_out_len[u] = 0; d_need[u] = 0; }
+	else if (copy_need) { d_need[u] = d_out_len[u]; }
+}
+
 // FORMAT 0: src holds the capacities; 2 / 3 / 4 (LZNT1 / Xpress / Xpress+Huffman): src holds input lengths, and the capacity of each is the
 // format's largest output (api.hip mscomp_amd_plan_layout), written to cap_out when that is not null
 template <int FORMAT>
@@ -147,8 +162,21 @@ void launch_dev_zero(hipStream_t st, uint32_t* p, uint32_t n)
 void launch_dev_tables(hipStream_t st, int format, uint32_t n, u64 in_total_max, u64 out_total_max, const u64* in_off, const u64* in_len,
                        const u64* out_off, const u64* out_cap, u64* san, uint32_t* chunk_prefix, u64* tok_prefix, uint32_t* reject)
 {
-	hipLaunchKernelGGL(dv_tables_kernel, dim3(1), dim3(DV_THREADS), 0, st, format, n, in_total_max, out_total_max, in_off, in_len, out_off, out_cap,
+	hipLaunchKernelGGL(dv_tables_kernel<false>, dim3(1), dim3(DV_THREADS), 0, st, format, n, in_total_max, out_total_max, in_off, in_len, out_off, out_cap,
 	                   san, chunk_prefix, tok_prefix, reject);
+}
+
+void launch_dev_stables(hipStream_t st, int format, uint32_t n, u64 in_total_max, const u64* in_off, const u64* in_len, const u64* limit,
+                        u64* san, uint32_t* chunk_prefix, u64* tok_prefix, uint32_t* reject)
+{
+	hipLaunchKernelGGL(dv_tables_kernel<true>, dim3(1), dim3(DV_THREADS), 0, st, format, n, in_total_max, ~(u64)0, in_off, in_len, (const u64*)nullptr, limit,
+	                   san, chunk_prefix, tok_prefix, reject);
+}
+
+void launch_dev_size_finish(hipStream_t st, const uint32_t* reject, uint32_t n, u64* d_out_len, u64* d_need, int32_t* d_status, bool copy_need)
+{
+	if (n == 0) { return; }
+	hipLaunchKernelGGL(dv_size_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, reject, n, d_out_len, d_need, d_status, copy_need ? 1 : 0);
 }
 
 void launch_dev_reject(hipStream_t st, const uint32_t* reject, uint32_t n, u64* d_out_len, int32_t* d_status)
@@ -175,6 +203,101 @@ void launch_dev_ctables(hipStream_t st, int format, uint32_t n, u64 in_total_max
 {
 	hipLaunchKernelGGL(dv_ctables_kernel, dim3(1), dim3(DV_THREADS), 0, st, format, n, in_total_max, in_unit_max, in_off, in_len, out_off, out_cap,
 	                   san, chunk_prefix, reject);
+}
+
+// ---- compaction from device tables (mscomp_amd_compact_dev) ----
+// The packed byte range [0, min(off[n], cap)) is cut into equal slices, one per block of a grid that is fixed by the CU count: a block finds
+// the unit its slice starts in by binary search in off[] and walks the units from there, so the work follows the bytes moved and one long
+// unit is spread over as many blocks as its bytes cover. Per unit piece: a bytewise head up to the destination's next 16-byte boundary, a
+// body of 16-byte stores (16-byte loads where the source is aligned alike, loads of alignment 1 otherwise), a bytewise tail. No byte of the
+// source outside the piece is read. A unit that ends beyond cap is left out whole, and so is everything behind it.
+#define CPD_THREADS 256u
+#define CPD_SLICE_MIN 4096u                              // a slice is a multiple of this (small batches: fewer blocks, whole pieces)
+struct __attribute__((packed)) cpd_u16 { uint32_t w[4]; };  // 16 bytes of alignment 1
+
+template <bool ZERO>
+__device__ __forceinline__ void cpd_move(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, u64 cnt, uint32_t tid)
+{
+	u64 head = (16u - ((uintptr_t)dst & 15u)) & 15u;
+	if (head > cnt) { head = cnt; }
+	const u64 body = (cnt - head) >> 4, tail0 = head + body * 16u;
+	const bool has_head = tid < head, has_tail = tid >= 64u && tail0 + (tid - 64u) < cnt;   // (the tail on the second wave: at most 15 bytes)
+	uint4* __restrict__ d16 = reinterpret_cast<uint4*>(dst + head);
+	if (ZERO) {
+		if (has_head) { dst[tid] = 0; }
+		if (has_tail) { dst[tail0 + (tid - 64u)] = 0; }
+		for (u64 k = tid; k < body; k += CPD_THREADS) { d16[k] = make_uint4(0, 0, 0, 0); }
+		return;
+	}
+	// every load of a step before its stores: a piece of up to 16 KiB + 30 bytes costs one round trip to memory, not one per access
+	const uint8_t hb = has_head ? src[tid] : (uint8_t)0, tb = has_tail ? src[tail0 + (tid - 64u)] : (uint8_t)0;
+	const bool same = (((uintptr_t)src + head) & 15u) == 0;              // source and destination aligned alike: 16-byte loads
+	const uint4* __restrict__ sa = reinterpret_cast<const uint4*>(src + head);
+	const cpd_u16* __restrict__ su = reinterpret_cast<const cpd_u16*>(src + head);
+	for (u64 k0 = 0; k0 < body || k0 == 0; k0 += 4u * CPD_THREADS) {
+		uint4 v[4];
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) {
+			const u64 k = k0 + j * CPD_THREADS + tid;
+			if (k < body) {
+				if (same) { v[j] = sa[k]; }
+				else { const cpd_u16 t = su[k]; v[j] = make_uint4(t.w[0], t.w[1], t.w[2], t.w[3]); }
+			}
+		}
+		if (k0 == 0) {
+			if (has_head) { dst[tid] = hb; }
+			if (has_tail) { dst[tail0 + (tid - 64u)] = tb; }
+		}
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) {
+			const u64 k = k0 + j * CPD_THREADS + tid;
+			if (k < body) { d16[k] = v[j]; }
+		}
+	}
+}
+
+__global__ __launch_bounds__(CPD_THREADS) void cpd_copy_kernel(const uint8_t* __restrict__ src, const u64* __restrict__ src_off, const u64* __restrict__ len,
+                                                              const u64* __restrict__ off, uint32_t n, u64 cap, uint8_t* __restrict__ dst)
+{
+	const uint32_t tid = threadIdx.x;
+	const u64 total = off[n], range = total < cap ? total : cap;
+	u64 per = (range + gridDim.x - 1u) / gridDim.x;
+	per = (per + (CPD_SLICE_MIN - 1u)) & ~(u64)(CPD_SLICE_MIN - 1u);
+	const u64 lo = (u64)blockIdx.x * per;
+	if (lo >= range) { return; }
+	const u64 hi = range - lo < per ? range : lo + per;
+	uint32_t a = 0, b = n;                                               // the first unit with off[u + 1] > lo (there is one: off[n] > lo)
+	while (a < b) { const uint32_t m = a + (b - a) / 2u; if (off[m + 1u] > lo) { b = m; } else { a = m + 1u; } }
+	// the table row of the next unit is fetched while this unit's bytes move
+	u64 o = off[a], L = len[a], e = off[a + 1u], so = src_off[a];
+	for (uint32_t u = a; o < hi; ++u) {
+		const bool more = u + 1u < n;
+		const u64 nL = more ? len[u + 1u] : 0, ne = more ? off[u + 2u] : 0, nso = more ? src_off[u + 1u] : 0;
+		if (L > cap - o) { break; }                                         // (o < hi <= cap) ends beyond cap: not copied, and nothing behind it is below cap
+		const u64 d0 = o > lo ? o : lo, d1 = o + L < hi ? o + L : hi;
+		if (d0 < d1) { cpd_move<false>(dst + d0, src + so + (d0 - o), d1 - d0, tid); }
+		const u64 p0 = o + L > lo ? o + L : lo, p1 = e < hi ? e : hi;      // the padding up to the next unit
+		if (p0 < p1) { cpd_move<true>(dst + p0, nullptr, p1 - p0, tid); }
+		if (!more) { break; }
+		o = e; L = nL; e = ne; so = nso;
+	}
+}
+
+// blocks of cpd_copy_kernel that are resident on the current device at once: its grid (a block more per CU would wait for a whole round)
+uint32_t compact_dev_blocks()
+{
+	int dev = 0, cus = 0, per_cu = 0;
+	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cpd_copy_kernel, (int)CPD_THREADS, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 4; }
+	return (uint32_t)cus * (uint32_t)per_cu;
+}
+
+void launch_compact_dev(hipStream_t st, uint32_t n, const uint8_t* src, const u64* src_off, const u64* len, u64 align, uint8_t* packed, u64 cap,
+                        u64* off, uint32_t blocks)
+{
+	launch_layout_dev(st, len, n, align, off);
+	if (n == 0 || cap == 0) { return; }
+	hipLaunchKernelGGL(cpd_copy_kernel, dim3(blocks), dim3(CPD_THREADS), 0, st, src, src_off, len, off, n, cap, packed);
 }
 
 } // namespace msc

@@ -84,6 +84,7 @@ struct LzdBufs { uint32_t* cin; uint16_t* csize; uint32_t* segL; uint32_t* segE;
                  uint32_t* selcnt; uint32_t* seloff; uint32_t* stop; uint32_t* irregular; u64* flat; };
 // dev: a plan with device-built tables (bt.n_chunks is its bound; the blocks past chunk_prefix[n_units] return at once)
 void launch_lzd_segments(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b, bool dev = false);
+void prepare_lzd_segments(bool dev);                      // its one-time LDS attribute (a dev plan sets it when it is created: its first execution may be captured)
 uint32_t lzd_read_walked();
 void launch_lzd_verify(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b);
 // exact: 0 decode every chunk, 1 decode the irregular units' chunks again to their places, 2 size every chunk only (the size query; d_out unused)
@@ -125,9 +126,10 @@ struct XhcBufs { uint32_t* cand_cnt; uint32_t* mode; uint32_t* cand_pos; uint32_
 void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
                                    const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb,
                                    uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, bool dev = false);   // dev: as launch_lzd_segments
+void prepare_lz_copy_block();                             // the one-time LDS attribute of lz_copy_block_kernel (tokens -> bytes of both Xpress formats)
 // the size query: phases 0 mark, 1 measure every candidate (no tokens written, chunk 0 included), 2 chain check, 3 serial walk without tokens
 void launch_xpress_huff_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, const u64* cand_prefix, uint32_t n_slots,
-                             const XhcBufs& xb, u64* d_out_len, int32_t* d_status, int phase);
+                             const XhcBufs& xb, u64* d_out_len, int32_t* d_status, int phase, bool dev = false);   // dev: as launch_lzd_segments
 
 // ---- tokens -> bytes for large units by all CUs (lzglobal.hip) ----
 #define LZG_PASSES 33u                                    // pointer passes launched (chains halve at least: 2^32 bytes); a pass returns at once when the one before left nothing open
@@ -159,6 +161,17 @@ void launch_lz_copy_global(hipStream_t st, const LzgTables& g, const BatchTables
 // each, the candidate prefix right behind the token prefix) with the formulas plan_create_impl uses on the host.
 void launch_dev_tables(hipStream_t st, int format, uint32_t n, u64 in_total_max, u64 out_total_max, const u64* in_off, const u64* in_len,
                        const u64* out_off, const u64* out_cap, u64* san, uint32_t* chunk_prefix, u64* tok_prefix, uint32_t* reject);
+// size plans (mscomp_amd_plan_create_size_dev): the same pass with out_off = 0 and out_cap = limit for every unit (limit null: 2^64 - 1) and
+// no bound on the limits' sum; the prefix arrays are those of a host size plan with these values
+void launch_dev_stables(hipStream_t st, int format, uint32_t n, u64 in_total_max, const u64* in_off, const u64* in_len, const u64* limit,
+                        u64* san, uint32_t* chunk_prefix, u64* tok_prefix, uint32_t* reject);
+// the last launch of a size dev plan: units with reject[u] get MSCOMP_ARG_ERROR, length 0, need 0; copy_need: need = length for the others
+void launch_dev_size_finish(hipStream_t st, const uint32_t* reject, uint32_t n, u64* d_out_len, u64* d_need, int32_t* d_status, bool copy_need);
+// mscomp_amd_compact_dev: off[0..n] as launch_layout_dev(len, align), then the len[u] bytes at src + src_off[u] to packed + off[u], the
+// padding between units zeroed, nothing at or behind packed + cap; `blocks` = the fixed grid of the copy, compact_dev_blocks() of the device
+uint32_t compact_dev_blocks();
+void launch_compact_dev(hipStream_t st, uint32_t n, const uint8_t* src, const u64* src_off, const u64* len, u64 align, uint8_t* packed, u64 cap,
+                        u64* off, uint32_t blocks);
 // p[0..n) = 0 as a kernel (a dev plan's launches hold no memset: they go into graphs the caller captures)
 void launch_dev_zero(hipStream_t st, uint32_t* p, uint32_t n);
 // units with reject[u]: status MSCOMP_ARG_ERROR, length 0 (after the decoders, which saw them as empty units with no room)
