@@ -40,8 +40,13 @@ __device__ unsigned long long g_lz_prof[16];
 #define LZ_TEND
 #endif
 
-#ifdef LZ4_PROFILE   // dev-only: the four-wave kernel's phase cycles ([0..6], thread 0); summed over all windows walked: finishing steps [7],
-                     // lz_lcp_tail wave-iterations of the finishing steps [8], long-pending stops [9], cooperative 256-byte extension steps [10]
+#ifdef LZ4_PROFILE_EVENTS   // (the event counters below; they imply the phase timers)
+#define LZ4_PROFILE
+#endif
+#ifdef LZ4_PROFILE   // dev-only: the four-wave kernel's phase cycles ([0..6], thread 0). With LZ4_PROFILE_EVENTS, summed over all windows walked: finishing
+                     // steps [7], lz_lcp_tail wave-iterations of the finishing steps [8], long-pending stops [9], cooperative 256-byte extension steps [10].
+                     // The event counters are same-address global atomics from inside the parse, some 300 per chunk: they hold up every global
+                     // access of the kernel and inflate the phase cycles of load, parse and emit many times over, so the two are read in separate builds.
 #define LZ4_NPROF 16
 __device__ unsigned long long g_lz4_prof[LZ4_NPROF];
 #endif
@@ -276,7 +281,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 					}
 				}
 				fin = ((five >> mp) & (u64)1) && kbest < (maxL << 12);
-#ifdef LZ4_PROFILE
+#ifdef LZ4_PROFILE_EVENTS
 				if (lane == 0) { atomicAdd(&g_lz4_prof[9], 1ull); atomicAdd(&g_lz4_prof[10], (unsigned long long)nst); }
 #endif
 			}
@@ -285,7 +290,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 				const uint32_t eL = (uint32_t)__builtin_amdgcn_readlane((int)e, (int)mp);
 				const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)o0, (int)mp), a1 = (uint32_t)__builtin_amdgcn_readlane((int)o1, (int)mp);
 				const uint32_t a2 = (uint32_t)__builtin_amdgcn_readlane((int)o2, (int)mp), a3 = (uint32_t)__builtin_amdgcn_readlane((int)o3, (int)mp);
-#ifdef LZ4_PROFILE
+#ifdef LZ4_PROFILE_EVENTS
 				uint32_t nsteps = 0, ntail = 0;
 #endif
 				const bool longL = maxL > 16u;
@@ -302,12 +307,12 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 					uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(vmask));   // (a key below 3 << 12 is no match)
 					const uint32_t m = wave_max_u32(k2);
 					kbest = m > kbest ? m : kbest;                   // longest, then oldest (older blocks hold the larger 4095 - q)
-#ifdef LZ4_PROFILE
+#ifdef LZ4_PROFILE_EVENTS
 					++nsteps; ntail += wave_max_u32(it);
 #endif
 					if ((kbest >> 12) == maxL || ~vmask) { break; }  // max_len reached / all older candidates seen
 				}
-#ifdef LZ4_PROFILE
+#ifdef LZ4_PROFILE_EVENTS
 				if (lane == 0) { atomicAdd(&g_lz4_prof[7], (unsigned long long)nsteps); atomicAdd(&g_lz4_prof[8], (unsigned long long)ntail); }
 #endif
 			}
@@ -522,8 +527,10 @@ extern "C" void mscomp_amd_debug_lz_prof(unsigned long long* out, int reset)
 // ===================================================================================================================
 // Four waves per chunk (same bytes as the kernel above)
 // ===================================================================================================================
-// The sort (B) stays with wave 0 -- the rank trick needs the positions in order -- but the lazy parse (C), 85 % of the
-// time, is split: the parse's only state is the position of the next token, so wave j parses the windows
+// The sort (B) ranks the positions with one returning atomic each, like the kernel above, on three waves at once: the rank
+// trick needs the positions in order only inside a wave's own part of the chunk, every part counts in a field of its own
+// of a bucket's word, and the counts of the parts in front are added afterwards (section B below). The lazy parse (C), most
+// of the time, is split: the parse's only state is the position of the next token, so wave j parses the windows
 // [16 j, 16 j + 16) SPECULATIVELY as if a token started at position 1024 j, records per window the token mask, the match
 // mask, the 16-bit match tokens (a match token depends on its position only) and the parse position after it; then wave
 // j repairs the seam BEHIND its segment (it continues with its true position into segment j+1 until the position after
@@ -543,6 +550,12 @@ extern "C" void mscomp_amd_debug_lz_prof(unsigned long long* out, int reset)
 #define LZ4_B3 52u
 #endif
 __device__ __forceinline__ uint32_t lz4_seg_start(uint32_t j) { return j == 0 ? 0u : j == 1 ? LZ4_B1 : j == 2 ? LZ4_B2 : j == 3 ? LZ4_B3 : 64u; }
+// the sort's three parts (wave 0: batches [0, P1), wave 1: [P1, P2), wave 2: [P2, 64)); the count fields below fit their lengths
+#define LZ4_P1 15u
+#define LZ4_P2 39u
+#define LZ4_PMAX 25u                                             // batches in the longest part
+static_assert(LZ4_P1 * 64u <= 0x3FFu && (LZ4_P2 - LZ4_P1) * 64u <= 0x7FFu && (64u - LZ4_P2) * 64u <= 0x7FFu, "a part fits its count field");
+static_assert(LZ4_P1 <= LZ4_PMAX && LZ4_P2 - LZ4_P1 <= LZ4_PMAX && 64u - LZ4_P2 == LZ4_PMAX, "LZ4_PMAX");
 #define LZ4_MAXM 22u                                             // matches that can START in one window of 64 positions
 #ifdef LZ4_PROFILE
 extern "C" void mscomp_amd_debug_lz4_prof(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lz4_prof), sizeof(unsigned long long) * LZ4_NPROF); unsigned long long z[LZ4_NPROF] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lz4_prof), z, sizeof z); }
@@ -570,13 +583,16 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		uint8_t  data[4096];
 		uint16_t bucket[4096];
 		union {
-			uint16_t cnt[LZ_TBL];                                          // sort: counts -> bucket ends; after the parse: prefixes and flags (below)
+			uint16_t cnt[LZ_TBL];                                          // after the parse: prefixes and flags (below)
 			struct { uint32_t ends[LZ_TBL * 12u / 32u]; Ctl ctl; } parse;   // parse: the ends as 12-bit fields, then the control words
 		} t;
 	};
 	static_assert(LZ_TBL == 4096u, "the pack below hands 16 bucket ends to each of 256 threads");
 	static_assert(sizeof(Lds) <= 20480, "eight blocks per CU");
+	static_assert(offsetof(Lds, t) == offsetof(Lds, bucket) + sizeof(Lds::bucket) && sizeof(Lds::bucket) + sizeof(Lds::t) == LZ_TBL * sizeof(uint32_t),
+	              "the sort's count words (one dword per bucket) lie over the bucket array and the union behind it");
 	__shared__ Lds L;
+	uint32_t* const s_cw = reinterpret_cast<uint32_t*>(L.bucket);         // [LZ_TBL] the sort's count words (section B)
 	uint8_t* const s_data = L.data; uint16_t* const s_cnt = L.t.cnt; uint16_t* const s_bucket = L.bucket;
 	Ctl& C = L.t.parse.ctl;
 	u64* const s_tok = C.tok; u64* const s_mat = C.mat; uint16_t* const s_endc = C.endc; uint8_t* const s_rep = C.rep;
@@ -612,83 +628,125 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		for (uint32_t i = tid * 16u; i < nvec; i += 4096u) { *reinterpret_cast<uint4*>(s_data + i) = *reinterpret_cast<const uint4*>(src + i); }
 		for (uint32_t i = nvec + tid; i < n; i += 256u) { s_data[i] = src[i]; }
 		for (uint32_t i = n + tid; i < 4096u; i += 256u) { s_data[i] = 0; }
-		for (uint32_t i = tid * 8u; i < LZ_TBL; i += 2048u) { *reinterpret_cast<uint4*>(s_cnt + i) = make_uint4(0, 0, 0, 0); }
+		for (uint32_t i = tid * 4u; i < LZ_TBL; i += 1024u) { *reinterpret_cast<uint4*>(s_cw + i) = make_uint4(0, 0, 0, 0); }
 	}
 	__syncthreads();
 	LZ4_T(0)
-	// ---- B. position-sorted buckets (wave 0; see the kernel above) ---------------------------------------------------
-	// histogram (all waves: the counts commute) -> exclusive scan (bucket starts) -> ordered scatter through the start
-	// cursors (wave 0): the returning atomic hands out the slots of a bucket in position order (batches ascending, lane
-	// order inside a batch) and leaves every cursor at its bucket's END, which is what the parse looks up. (No
-	// per-position ranks to keep in registers: this kernel wants 8 blocks of 4 waves per CU.)
+	// ---- B. position-sorted buckets: a stable counting sort by hash, ONE returning atomic per position, three waves at once -------
+	// The chunk's 64 batches of 64 positions are three consecutive parts -- batches [0, 15), [15, 39), [39, 64) = 960 / 1536 / 1600
+	// positions, for waves 0 / 1 / 2 -- and a bucket's count word holds one counter per part: 10 bits for part 0, 11 bits each for parts
+	// 1 and 2. A field cannot count past its part's length (960 <= 1023, 1600 <= 2047), so nothing carries into a neighbour and there is
+	// no overflow path. The 4096 words lie over the bucket array and the table union behind it (16 KiB, both dead until B3 / B4).
+	//   B1. a wave walks its part in ascending batches and adds 1 to its field. What the atomic returns in that field is the position's
+	//       rank among the same-hash positions of its PART: batches of a wave execute in order, the lanes of one DS instruction are served
+	//       in lane order (what `serial` replaces), and the other waves' adds go to other fields. Ranks stay in registers, two per VGPR.
+	//   B2. the counts are final: waves 1 and 2 add the counts of the parts in front of their own to their ranks; every thread takes
+	//       the words of 16 consecutive buckets and sums them; waves 0 and 1 leave their totals in the two halves of word 0 (bucket 0 is
+	//       always empty, lz_hash), wave 3's prefix is the chunk's number of keys minus its own total: no barrier for the partial sums.
+	//   B3. every table word has been read: a thread writes the ENDS of its 16 buckets as 12-bit fields (6 dwords at 24 tid), and the
+	//       control words are initialised behind them.
+	//   B4. scatter with plain stores: bucket[end[h - 1] + rank] = p.
+	// Wave 3 has no part: it stages, scans and packs with the others.
 	{
 		const uint32_t nb = (n + 63u) >> 6;
-		for (uint32_t b = wv; b < nb; b += 4u) {
-			const uint32_t p = b * 64u + lane;
-			if (p + 2u < n) {
-				const uint32_t h = lz_hash(lds_ld32(s_data, p) & 0xFFFFFFu);
-				atomicAdd(reinterpret_cast<uint32_t*>(s_cnt) + (h >> 1), (h & 1u) ? 0x10000u : 1u);
-			}
-		}
-	}
-	__syncthreads();
-	if (wv == 0) {
-		const uint32_t nb = (n + 63u) >> 6;
-		wave_fence();
-		{
-			uint32_t run = 0;
-			for (uint32_t k = 0; k < LZ_TBL / 512u; ++k) {
-				uint4 a = reinterpret_cast<uint4*>(s_cnt)[k * 64u + lane];
-				uint32_t w[4] = { a.x, a.y, a.z, a.w };
-				uint32_t sum = 0;
-				#pragma unroll
-				for (int i = 0; i < 4; ++i) { sum += (w[i] & 0xFFFFu) + (w[i] >> 16); }
-				const uint32_t incl = wave_incl_scan_add_u32(sum);
-				uint32_t r = run + incl - sum;
-				#pragma unroll
-				for (int i = 0; i < 4; ++i) { const uint32_t lo = w[i] & 0xFFFFu, hi = w[i] >> 16; w[i] = r | ((r + lo) << 16); r += lo + hi; }
-				reinterpret_cast<uint4*>(s_cnt)[k * 64u + lane] = make_uint4(w[0], w[1], w[2], w[3]);
-				run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-			}
-		}
-		wave_fence();
-		// 8 batches per round: their 8 atomics are issued back to back (DS operations of a wave execute in order; the
-		// wavefront-scope form keeps the compiler from waiting for each one)
-		for (uint32_t b0 = 0; b0 < nb; b0 += 8u) {
-			uint32_t h[8], old[8];
-			#pragma unroll
-			for (int j = 0; j < 8; ++j) { h[j] = lz_hash(lds_ld32(s_data, ((b0 + j) * 64u + lane) & 4095u) & 0xFFFFFFu); }
-			#pragma unroll
-			for (int j = 0; j < 8; ++j) {
-				old[j] = lz_ordered_add<serial>(reinterpret_cast<uint32_t*>(s_cnt) + (h[j] >> 1), (h[j] & 1u) ? 0x10000u : 1u, (b0 + j) * 64u + lane + 2u < n, lane);
-			}
-			#pragma unroll
-			for (int j = 0; j < 8; ++j) {
-				const uint32_t p = (b0 + j) * 64u + lane;
-				if (p + 2u < n) { s_bucket[(h[j] & 1u) ? old[j] >> 16 : old[j] & 0xFFFFu] = (uint16_t)p; }
-			}
-		}
-	}
-	__syncthreads();
-	// ---- B4. pack the bucket ends (<= 4094) into 12-bit fields in place: thread t reads ends 16 t .. 16 t + 15 (32 bytes at 32 t) and
-	// writes them as 6 dwords at 24 t; the freed top 2 KiB take the control words --------------------------------------------------
-	{
-		const uint4 a = reinterpret_cast<const uint4*>(s_cnt)[2u * tid], b = reinterpret_cast<const uint4*>(s_cnt)[2u * tid + 1u];
-		__syncthreads();
-		const uint32_t e[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };   // two ends each
-		uint32_t* const o = L.t.parse.ends + 6u * tid;
+		const uint32_t pb0 = wv == 0 ? 0u : wv == 1u ? LZ4_P1 : wv == 2u ? LZ4_P2 : 64u;     // my part: batches [pb0, pb1)
+		const uint32_t pe = wv == 0 ? LZ4_P1 : wv == 1u ? LZ4_P2 : 64u;
+		const uint32_t pb1 = pe < nb ? pe : nb;
+		const uint32_t fsh = wv == 0 ? 0u : wv == 1u ? 10u : 21u, fm = wv == 0 ? 0x3FFu : 0x7FFu;   // my field
+		uint32_t rk[(LZ4_PMAX + 1u) / 2u];
 		#pragma unroll
-		for (int k = 0; k < 2; ++k) {                                          // 8 ends -> 3 dwords
-			const uint32_t* v = e + 4 * k;
-			const uint32_t v0 = v[0] & 0xFFFFu, v1 = v[0] >> 16, v2 = v[1] & 0xFFFFu, v3 = v[1] >> 16;
-			const uint32_t v4 = v[2] & 0xFFFFu, v5 = v[2] >> 16, v6 = v[3] & 0xFFFFu, v7 = v[3] >> 16;
-			o[3 * k]      = v0 | (v1 << 12) | (v2 << 24);
-			o[3 * k + 1u] = (v2 >> 8) | (v3 << 4) | (v4 << 16) | (v5 << 28);
-			o[3 * k + 2u] = (v5 >> 4) | (v6 << 8) | (v7 << 20);
+		for (uint32_t i = 0; i < (LZ4_PMAX + 1u) / 2u; ++i) { rk[i] = 0; }
+		// B1. rounds of 8 batches: their atomics are issued back to back (DS operations of a wave execute in order; the wavefront-scope
+		// form keeps the compiler from waiting for each one). An inactive lane's rank stays 0.
+		#pragma unroll
+		for (uint32_t j0 = 0; j0 < LZ4_PMAX; j0 += 8u) {
+			if (pb0 + j0 < pb1) {
+				uint32_t h[8], old[8];
+				#pragma unroll
+				for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { h[j] = lz_hash(lds_ld32(s_data, ((pb0 + j0 + j) * 64u + lane) & 4095u) & 0xFFFFFFu); } }
+				#pragma unroll
+				for (uint32_t j = 0; j < 8u; ++j) {
+					if (j0 + j < LZ4_PMAX) { const uint32_t b = pb0 + j0 + j; old[j] = lz_ordered_add<serial>(s_cw + h[j], 1u << fsh, b < pb1 && b * 64u + lane + 2u < n, lane); }
+				}
+				#pragma unroll
+				for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { rk[(j0 + j) >> 1] |= ((old[j] >> fsh) & fm) << (16u * ((j0 + j) & 1u)); } }
+			}
 		}
-		if (tid < LZ4_NSEG) { s_prog[tid] = 0; s_used[tid] = 0; }
-		if (tid < 16u) { reinterpret_cast<uint32_t*>(s_rep)[tid] = 0; }
-		if (tid == 0) { s_segctr = 0; }
+		__syncthreads();
+		// B2. (a lane without a key has rank 0 and adds at most 1023 + 2047 of some other bucket: nothing carries into the upper half)
+		if (wv == 1u || wv == 2u) {
+			const uint32_t m1 = wv == 2u ? 0x7FFu : 0u;
+			#pragma unroll
+			for (uint32_t j0 = 0; j0 < LZ4_PMAX; j0 += 8u) {
+				if (pb0 + j0 < pb1) {
+					uint32_t w[8];
+					#pragma unroll
+					for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { w[j] = s_cw[lz_hash(lds_ld32(s_data, ((pb0 + j0 + j) * 64u + lane) & 4095u) & 0xFFFFFFu)]; } }
+					#pragma unroll
+					for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { rk[(j0 + j) >> 1] += ((w[j] & 0x3FFu) + ((w[j] >> 10) & m1)) << (16u * ((j0 + j) & 1u)); } }
+					__builtin_amdgcn_sched_barrier(0);                        // (the rounds are independent: merged, their reads in flight cost the eighth block's registers)
+				}
+			}
+		}
+		uint32_t tot[8], sum = 0;                                         // the sizes of buckets 16 tid .. 16 tid + 15, two per register
+		#pragma unroll
+		for (uint32_t k = 0; k < 4u; ++k) {
+			const uint4 a = reinterpret_cast<const uint4*>(s_cw)[4u * tid + k];
+			uint32_t x[4] = { a.x, a.y, a.z, a.w };
+			#pragma unroll
+			for (uint32_t i = 0; i < 4u; ++i) { x[i] = (x[i] & 0x3FFu) + ((x[i] >> 10) & 0x7FFu) + (x[i] >> 21); }
+			if (k == 0 && tid == 0) { x[0] = 0; }                          // (word 0 counts nothing: it carries the wave totals)
+			sum += (x[0] + x[1]) + (x[2] + x[3]);
+			tot[2u * k] = x[0] | (x[1] << 16); tot[2u * k + 1u] = x[2] | (x[3] << 16);
+			__builtin_amdgcn_sched_barrier(0);                            // (as above)
+		}
+		const uint32_t incl = wave_incl_scan_add_u32(sum);
+		const uint32_t wtot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+		if (lane == 63u && wv < 2u) { reinterpret_cast<uint16_t*>(s_cw)[wv] = (uint16_t)wtot; }
+		__syncthreads();
+		// B3.
+		{
+			const uint32_t x = s_cw[0];
+			const uint32_t keys = n > 2u ? n - 2u : 0u;                   // positions p with p + 2 < n
+			const uint32_t wpre = wv == 0 ? 0u : wv == 1u ? (x & 0xFFFFu) : wv == 2u ? (x & 0xFFFFu) + (x >> 16) : keys - wtot;
+			uint32_t r = wpre + incl - sum;
+			uint32_t* const o = L.t.parse.ends + 6u * tid;
+			#pragma unroll
+			for (int k = 0; k < 2; ++k) {                                 // 8 ends -> 3 dwords
+				uint32_t v[8];
+				#pragma unroll
+				for (int i = 0; i < 4; ++i) { r += tot[4 * k + i] & 0xFFFFu; v[2 * i] = r; r += tot[4 * k + i] >> 16; v[2 * i + 1] = r; }
+				o[3 * k]      = v[0] | (v[1] << 12) | (v[2] << 24);
+				o[3 * k + 1u] = (v[2] >> 8) | (v[3] << 4) | (v[4] << 16) | (v[5] << 28);
+				o[3 * k + 2u] = (v[5] >> 4) | (v[6] << 8) | (v[7] << 20);
+			}
+			if (tid < LZ4_NSEG) { s_prog[tid] = 0; s_used[tid] = 0; }
+			if (tid < 16u) { reinterpret_cast<uint32_t*>(s_rep)[tid] = 0; }
+			if (tid == 0) { s_segctr = 0; }
+		}
+		__syncthreads();
+		// B4. (start(h): the lookup of lz_window<true>)
+		#pragma unroll
+		for (uint32_t j0 = 0; j0 < LZ4_PMAX; j0 += 8u) {
+			if (pb0 + j0 < pb1) {
+				uint32_t st[8];
+				#pragma unroll
+				for (uint32_t j = 0; j < 8u; ++j) {
+					if (j0 + j < LZ4_PMAX) {
+						const uint32_t bit = lz_hash(lds_ld32(s_data, ((pb0 + j0 + j) * 64u + lane) & 4095u) & 0xFFFFFFu) * 12u - 12u;
+						const uint32_t* const t = L.t.parse.ends + (bit >> 5);
+						st[j] = __builtin_amdgcn_alignbit(t[1], t[0], bit) & 0xFFFu;
+					}
+				}
+				#pragma unroll
+				for (uint32_t j = 0; j < 8u; ++j) {
+					if (j0 + j < LZ4_PMAX) {
+						const uint32_t b = pb0 + j0 + j, p = b * 64u + lane;
+						if (b < pb1 && p + 2u < n) { s_bucket[st[j] + ((rk[(j0 + j) >> 1] >> (16u * ((j0 + j) & 1u))) & 0xFFFFu)] = (uint16_t)p; }
+					}
+				}
+			}
+		}
 	}
 	__syncthreads();
 	const uint32_t* const tbl = L.t.parse.ends;
