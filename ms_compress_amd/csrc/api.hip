@@ -8,6 +8,7 @@
 #include "kernels.h"
 #include <atomic>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <condition_variable>
@@ -94,14 +95,13 @@ struct mscomp_amd_plan {
 	bool sizing = false;                               // a decompressed-size plan (mscomp_amd_plan_create_size): out_cap holds the limits, nothing is decoded
 	bool dev = false;                                  // a plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev / _compress_dev; with sizing: _size_dev)
 	uint64_t in_total_max = 0, out_total_max = 0;      // ... and the bounds its scratch was reserved for
-	uint64_t in_unit_max = 0;                          // (compress dev plans: the largest unit they take)
 	uint32_t n_units = 0, n_chunks = 0;
-	uint64_t total_in = 0, max_unit = 0;
+	uint64_t total_in = 0, max_unit = 0;               // (max_unit of a compress dev plan: the largest unit it takes)
 	bool lznt1_sa = false;                             // LZNT1: the suffix-array dictionary flavour -- fixed when the plan is created: a plan never changes its bytes under a running caller
-	bool matches_ready = false;                        // the caller has run the links + find kernels of this execution itself, range by range (the pipelined one-shot call): plan_launch skips them once
+	bool matches_ready = false;                        // the caller has run the links + find kernels of this execution itself, range by range (the pipelined one-shot call): compress_launch skips them once
 	bool no_graph = false;                             // one-shot plans run with changing buffer addresses: a captured graph would be re-captured every time
-	DevBuf tables;                                     // in_off | out_off | chunk_prefix
-	DevBuf tokpre;                                     // decompression by tokens: first token slot | first candidate slot of every unit (2 x (n_units + 1) u64)
+	DevBuf tables;                                     // in_off | in_len | out_off | out_cap | chunk_prefix; dev plans: what their table pass writes (reserve_dev_tables)
+	DevBuf tokpre;                                     // decompression by tokens (host plans): first token slot | first candidate slot | first token-scratch slot of every unit (n_units + 1 u64 each)
 	uint32_t xhc_slots = 0;                            // candidate chunk slots of the batch
 	uint64_t xhc_scr = 0;                              // token-scratch slots (candidates of multi-chunk buffers), 0 = none
 	DevBuf lzg_tab;                                    // lzglobal.hip: unit (u32 x n_big, padded) | tb_prefix | tile_prefix | word_prefix (u64 x (n_big + 1) each)
@@ -109,13 +109,19 @@ struct mscomp_amd_plan {
 	uint64_t lzg_words = 0;
 	DevBuf xps_tab;                                    // xps_*: unit (u32 x n_big, padded) | seg_prefix (u64 x (n_big + 1))
 	uint32_t xps_big = 0, xps_seg = 0, xps_seg_bytes = 0, xps_warm_bytes = 0;
+	// what the launch code reads, resolved when the plan is created (the launch functions do not know where a creator put it): the columns of
+	// `tables`; the prefixes, in tokpre for host plans and in `tables` for dev plans; reject (u32 x n_units), written by a dev plan's table pass
 	BatchTables bt{};
-	// the launch sequence of plan_execute as a hipGraph: captured on the plan's second execution, replayed while the
+	u64* tok_prefix = nullptr; u64* cand_prefix = nullptr; u64* scr_prefix = nullptr;
+	uint32_t* reject = nullptr;
+	// the plan's launch sequence as a hipGraph (plan_run): captured on the plan's second execution, replayed while the
 	// arguments and the scratch buffers stay where they were
 	hipGraphExec_t gexec = nullptr;
-	const void* g_args[9] = {};                        // (a dev plan's graph: its eight pointers, a size dev plan's seven)
+	const void* g_args[9] = {};                        // (a host plan's four pointers, a dev plan's eight, a size dev plan's seven)
 	uint64_t g_epoch = 0, g_mode = 0;
 	uint32_t executions = 0;
+	// (on the plan's device, its stream idle. mscomp_amd_plan_destroy hands `tables` to the context's pool first)
+	~mscomp_amd_plan() { if (gexec) { (void)hipGraphExecDestroy(gexec); } tables.release(); tokpre.release(); lzg_tab.release(); xps_tab.release(); }
 };
 
 namespace {
@@ -155,29 +161,15 @@ uint64_t optional_scratch_budget(uint64_t env_cap, size_t already_held)
 	return env_cap < half ? env_cap : half;
 }
 
-uint32_t chunks_of(MSCompFormat f, bool decompress, uint64_t n)
-{
-	if (decompress) {                                  // LZNT1: segments of the header walk; Xpress+Huffman: tiles of the candidate search
-		if (f == MSCOMP_LZNT1) { return (uint32_t)(n ? (n + LZD_SEG - 1u) / LZD_SEG : 1u); }
-		if (f == MSCOMP_XPRESS_HUFF) { return (uint32_t)(n ? (n + XHC_TILE_BYTES - 1u) / XHC_TILE_BYTES : 1u); }
-		return 1u;
-	}
-	switch (f) {
-	case MSCOMP_LZNT1:       return (uint32_t)((n + 4095u) / 4096u);
-	case MSCOMP_XPRESS_HUFF: return (uint32_t)((n + 65535u) / 65536u);   // n==0 -> 0 chunks, 0 bytes of output
-	default:                 return (uint32_t)((n + 65535u) / 65536u);   // Xpress: 64 KiB link chunks (one stream per unit)
-	}
-}
-
 } // namespace
 
 extern "C" {
 
 const char* mscomp_amd_version(void) { return "mscomp_amd 0.6 (gfx950, HIP; LZNT1 / Xpress / Xpress+Huffman compressors and decompressors, LZNT1 streaming, host batches over several GPUs)"; }
 
-size_t lznt1_max_compressed_size(size_t n)       { return n + 3 + 2 * ((n + 4095) / 4096); }
-size_t xpress_max_compressed_size(size_t n)      { return n + 4 + 4 * (n / 32); }
-size_t xpress_huff_max_compressed_size(size_t n) { return n + 34 + 258 + 258 * (n / 65536); }
+size_t lznt1_max_compressed_size(size_t n)       { return lznt1_max_out(n); }
+size_t xpress_max_compressed_size(size_t n)      { return xpress_max_out(n); }
+size_t xpress_huff_max_compressed_size(size_t n) { return xpress_huff_max_out(n); }
 #ifndef MSCOMP_AMD_NO_FACADE   /* define when src/mscomp.cpp of the reference is linked too */
 size_t ms_max_compressed_size(MSCompFormat f, size_t n)
 {
@@ -267,6 +259,64 @@ int mscomp_amd_profile_read(mscomp_amd_ctx* c, const char** names, double* ms, u
 	return n;
 }
 
+// bt from the plan's table buffer and counts: in_off | in_len | out_off | out_cap (u64 x n_units each) | chunk_prefix (u32 x (n_units + 1))
+static void set_bt(mscomp_amd_plan* p)
+{
+	const size_t n = p->n_units;
+	const u64* d = static_cast<const u64*>(p->tables.p);
+	p->bt.in_off = d; p->bt.in_len = d + n; p->bt.out_off = d + 2 * n; p->bt.out_cap = d + 3 * n;
+	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(d + 4 * n);
+	p->bt.n_units = p->n_units; p->bt.n_chunks = p->n_chunks;
+}
+// a table to a plan-owned buffer, waited for (the table is the caller's local)
+static bool upload(mscomp_amd_ctx* c, const DevBuf& b, const std::vector<uint64_t>& tab)
+{
+	return hipMemcpyAsync(b.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+}
+
+// ---- the ctx scratch of a plan, reserved when the plan is created so that execute() never allocates ----
+// Host plans call these with their exact counts, dev plans with their bounds.
+static bool reserve_scan(mscomp_amd_ctx* c, size_t n_chunks)   // launch_scan_sizes over the chunks
+{
+	return c->prefix.reserve((n_chunks + 2) * sizeof(uint64_t)) && c->tile_sums.reserve((n_chunks / 1024 + 4) * sizeof(uint64_t));
+}
+static bool reserve_compress_scratch(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, size_t n_chunks, bool lznt1_sa)
+{
+	bool ok = c->slot_size.reserve((n_chunks + 1) * sizeof(uint32_t)) && reserve_scan(c, n_chunks);
+	if (ok && format == MSCOMP_LZNT1) { ok = c->slots.reserve(n_chunks * LZNT1_SLOT + 64) && (lznt1_sa || c->lzrec.reserve(n_chunks * LZNT1_REC + 64)); }
+	if (ok && format != MSCOMP_LZNT1) {
+		const size_t per = n_chunks * 65536u * sizeof(uint16_t) + 64;
+		// (mlen3: 4 bytes per position, both halves of the match word)
+		ok = c->links.reserve(per) && c->mlen3.reserve(2 * per) && c->lasthead.reserve(per / 2 + 64);
+	}
+	if (ok && format == MSCOMP_XPRESS) {
+		const size_t nw = n_chunks * 1024u + 64, ns = n_chunks + 1;
+		ok = c->wtok.reserve(nw * 8) && c->wmat.reserve(nw * 8) && c->wfar.reserve(nw * 4);
+		if (ok && xpress_emit_mode_for((uint32_t)n_units, (uint32_t)n_chunks) == 4) {    // the block-per-super-block kernels (launch_xpress_emit chooses from the same two numbers)
+			ok = c->wrec.reserve(nw * 6 * 4) && c->sbrec.reserve(ns * (16 + 24 + 16 * 8 * 4 + 16 * 2 * 8 + 8));
+		}
+	}
+	if (ok && format == MSCOMP_XPRESS_HUFF) {
+		const size_t nc = n_chunks + 1;
+		ok = c->tokbits.reserve(nc * 1024 * 8) && c->counts.reserve(nc * 512 * 4) && c->extra.reserve(nc * 4) &&
+		     c->lens.reserve(nc * 512) && c->codes.reserve(nc * 1024) && c->fb_list.reserve(nc * 4 + 64) && c->fbflag.reserve(nc * 4);
+	}
+	return ok;
+}
+static bool reserve_lzd_scratch(mscomp_amd_ctx* c, size_t n_units, size_t n_chunks)   // the LZNT1 header chain (lzd_bufs), beside reserve_scan
+{
+	return c->dz_cin.reserve(n_chunks * LZD_SLOTS * 4 + 64) && c->dz_csize.reserve(n_chunks * LZD_SLOTS * 2 + 64) &&
+	       c->dz_unit.reserve((n_chunks * (5 * LZD_K + 2) + n_units * 2 + 8) * 4);
+}
+static bool reserve_tokens(mscomp_amd_ctx* c, size_t n_units, uint64_t slots, bool store)   // Xpress formats: token counts; 32-bit tokens unless a size plan asks
+{
+	return (!store || c->dz_tok.reserve(slots * 4 + 256)) && c->dz_ntok.reserve((n_units + 1) * 8);
+}
+static bool reserve_xhc(mscomp_amd_ctx* c, size_t n_units, uint64_t cands)   // Xpress+Huffman candidate records (xhc_bufs)
+{
+	return c->dz_xhc.reserve((n_units + 1) * 8 + (size_t)cands * (4 * 4 + 3 * 8) + 64);
+}
+
 static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, bool decompress, size_t n_units,
                                      const uint64_t* in_off, const uint64_t* in_len,
                                      const uint64_t* out_off, const uint64_t* out_cap, mscomp_amd_plan** out, bool sizing = false)
@@ -277,7 +327,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	mscomp_amd_plan* p = new (std::nothrow) mscomp_amd_plan();
+	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());   // (every return below that is not the last one gives up the plan and what it holds)
 	if (!p) { return MSCOMP_MEM_ERROR; }
 	p->ctx = c; p->format = format; p->decompress = decompress; p->sizing = sizing; p->n_units = (uint32_t)n_units;
 	p->lznt1_sa = !decompress && format == MSCOMP_LZNT1 && lznt1_sa_for(c);
@@ -302,11 +352,11 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	for (size_t i = 0; i < n_units; ++i) {
 		h[i] = in_off[i]; h[n_units + i] = in_len[i]; h[2 * n_units + i] = out_off[i]; h[3 * n_units + i] = out_cap[i];
 		h_cp[i] = (uint32_t)chunks;
-		if (decompress && in_len[i] > 0xFFFFF000u) { delete p; return MSCOMP_ARG_ERROR; }   // offsets inside a unit are 32-bit (4 GiB - 4096 at most)
-		chunks += chunks_of(format, decompress, in_len[i]);
+		if (decompress && in_len[i] > 0xFFFFF000u) { return MSCOMP_ARG_ERROR; }   // offsets inside a unit are 32-bit (4 GiB - 4096 at most)
+		chunks += decompress ? decode_chunks(format, in_len[i]) : compress_chunks(format, in_len[i]);
 		total += in_len[i];
 		if (in_len[i] > p->max_unit) { p->max_unit = in_len[i]; }
-		if (chunks > 0x7FFFFFF0u) { delete p; return MSCOMP_ARG_ERROR; }
+		if (chunks > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
 	}
 	h_cp[n_units] = (uint32_t)chunks;
 	p->n_chunks = (uint32_t)chunks;
@@ -317,159 +367,116 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 		for (size_t i = 0; i < c->table_pool.size(); ++i) { if (c->table_pool[i].cap >= bytes && (best == c->table_pool.size() || c->table_pool[i].cap < c->table_pool[best].cap)) { best = i; } }
 		if (best < c->table_pool.size()) { p->tables = c->table_pool[best]; c->table_pool.erase(c->table_pool.begin() + (long)best); }
 	}
-	if (!p->tables.reserve(bytes)) { delete p; return MSCOMP_MEM_ERROR; }
-	if (hipMemcpyAsync(p->tables.p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { p->tables.release(); delete p; return MSCOMP_ERRNO; }
-	if (pinned) { if (hipEventRecord(c->h_tab_ev, c->stream) != hipSuccess) { p->tables.release(); delete p; return MSCOMP_ERRNO; } c->h_tab_busy = true; }
-	else if (hipStreamSynchronize(c->stream) != hipSuccess) { p->tables.release(); delete p; return MSCOMP_ERRNO; }
-	uint64_t* d = static_cast<uint64_t*>(p->tables.p);
-	p->bt.in_off = d; p->bt.in_len = d + n_units; p->bt.out_off = d + 2 * n_units; p->bt.out_cap = d + 3 * n_units;
-	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(d + 4 * n_units);
-	p->bt.n_units = p->n_units; p->bt.n_chunks = p->n_chunks;
+	if (!p->tables.reserve(bytes)) { return MSCOMP_MEM_ERROR; }
+	if (hipMemcpyAsync(p->tables.p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { return MSCOMP_ERRNO; }
+	if (pinned) { if (hipEventRecord(c->h_tab_ev, c->stream) != hipSuccess) { return MSCOMP_ERRNO; } c->h_tab_busy = true; }
+	else if (hipStreamSynchronize(c->stream) != hipSuccess) { return MSCOMP_ERRNO; }
+	set_bt(p.get());
 
-	// size the ctx scratch now so that execute() never allocates
-	if (decompress) {
-		bool okd = c->prefix.reserve(((size_t)p->n_chunks + 2) * sizeof(uint64_t)) && c->tile_sums.reserve(((size_t)p->n_chunks / 1024 + 4) * sizeof(uint64_t));
-		if (okd && format == MSCOMP_LZNT1) {
-			okd = c->dz_cin.reserve((size_t)p->n_chunks * LZD_SLOTS * 4 + 64) && c->dz_csize.reserve((size_t)p->n_chunks * LZD_SLOTS * 2 + 64) &&
-			      c->dz_unit.reserve(((size_t)p->n_chunks * (5 * LZD_K + 2) + (size_t)n_units * 2 + 8) * 4);
-		}
-		if (okd && format == MSCOMP_XPRESS_HUFF) {
-			// a symbol gives one token, a match one more per 32766 bytes; no token without an output byte
-			std::vector<uint64_t> tp(3 * (n_units + 1));                  // first token slot | first candidate slot | first token-scratch slot of every unit
-			uint64_t slots = 0, cands = 0, scr = 0;
-			for (size_t i = 0; i < n_units; ++i) {
-				tp[i] = slots; tp[n_units + 1 + i] = cands; tp[2 * (n_units + 1) + i] = scr;
-				const uint64_t by_in = 8 * in_len[i] + out_cap[i] / 32766u + 1, cnt = out_cap[i] < by_in ? out_cap[i] : by_in;
-				if (!sizing) { slots += cnt + 64; }                        // (a size plan writes no tokens)
-				// candidate chunk starts: a chunk gives 65536 bytes and takes at least 260; a quarter more for windows that only look like a table
-				const uint64_t by_out = out_cap[i] / 65536u + 2, by_len = in_len[i] / 260u + 1, most = by_out < by_len ? by_out : by_len;
-				cands += most + most / 4 + 2;
-				if (out_cap[i] > 65536u && !sizing) { scr += most + most / 4 + 2; }   // a buffer of several chunks: its candidates keep their tokens (no second walk)
-			}
-			tp[n_units] = slots; tp[2 * n_units + 1] = cands; tp[3 * n_units + 2] = scr;
-			if (cands > 0x7FFFFFF0u) { p->tables.release(); delete p; return MSCOMP_ARG_ERROR; }
-			p->xhc_slots = (uint32_t)cands;
-			okd = p->tokpre.reserve(tp.size() * 8) && (sizing || c->dz_tok.reserve(slots * 4 + 256)) && c->dz_ntok.reserve((n_units + 1) * 8) &&
-			      c->dz_xhc.reserve(((size_t)n_units + 1) * 8 + (size_t)cands * (4 * 4 + 3 * 8) + 64);
-			{	// ... if that scratch is affordable: at most MSCOMP_AMD_XHC_SCR_MAX_MB (default 32 GiB; 0 = always walk twice) and at most half of
-				// what the device has free right now; a reservation that fails anyway switches the path off (the second walk needs no scratch)
-				static const uint64_t scr_env = [] { const char* e = getenv("MSCOMP_AMD_XHC_SCR_MAX_MB"); const long long v = e ? atoll(e) : 32768; return (uint64_t)(v < 0 ? 0 : v) << 20; }();
-				const uint64_t need = scr * XHC_SCR * 4 + 64, scr_budget = optional_scratch_budget(scr_env, c->dz_scr.cap);
-				if (scr && (need > scr_budget || !okd || !c->dz_scr.reserve(need))) { for (size_t i = 0; i <= n_units; ++i) { tp[2 * (n_units + 1) + i] = 0; } scr = 0; }
-				p->xhc_scr = scr;
-			}
-			if (okd && (hipMemcpyAsync(p->tokpre.p, tp.data(), tp.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-			            hipStreamSynchronize(c->stream) != hipSuccess)) { p->tokpre.release(); p->tables.release(); delete p; return MSCOMP_ERRNO; }
-		}
-		if (okd && format == MSCOMP_XPRESS && sizing) { okd = c->dz_ntok.reserve((n_units + 1) * 8); }   // (token counts of the segment verdict)
-		if (okd && format == MSCOMP_XPRESS && !sizing) {
-			// a token takes at least one input byte and gives at least one output byte; a match one more token per 32766 bytes
-			std::vector<uint64_t> tp(n_units + 1);
-			uint64_t slots = 0;
-			for (size_t i = 0; i < n_units; ++i) {
-				tp[i] = slots;
-				const uint64_t by_in = in_len[i] + out_cap[i] / 32766u + 1, cnt = out_cap[i] < by_in ? out_cap[i] : by_in;
-				slots += cnt + 64;
-			}
-			tp[n_units] = slots;
-			okd = p->tokpre.reserve(tp.size() * 8) && c->dz_tok.reserve(slots * 4 + 256) && c->dz_ntok.reserve((n_units + 1) * 8);
-			if (okd && (hipMemcpyAsync(p->tokpre.p, tp.data(), tp.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-			            hipStreamSynchronize(c->stream) != hipSuccess)) { p->tokpre.release(); p->tables.release(); delete p; return MSCOMP_ERRNO; }
-		}
-		if (okd && !sizing && (format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF)) {
-			// units with room for LZG_MIN_CAP bytes or more get their bytes from all CUs (lzglobal.hip): 4 bytes of scratch per byte of capacity;
-			// when that is more than the budget (MSCOMP_AMD_LZG_MAX_MB, default 64 GiB of the 288; 0 switches the path off) the block-per-unit kernel takes them
-			static const uint64_t budget_env = [] { const char* e = getenv("MSCOMP_AMD_LZG_MAX_MB"); const long long v = e ? atoll(e) : 65536; return (uint64_t)(v < 0 ? 0 : v) << 20; }();
-			const uint64_t budget = optional_scratch_budget(budget_env, c->lzg_words.cap);   // ... and never more than half of the free HBM: the block kernel needs none of it
-			std::vector<uint32_t> big;
-			uint64_t words = 0;
-			bool too_large = false;                                       // (32-bit word indices: a unit with room for 4 GiB keeps the whole plan on the block kernel, which every such unit then takes)
-			for (size_t i = 0; i < n_units; ++i) { if (out_cap[i] >= 0xFFFFFF00ull) { too_large = true; } else if (out_cap[i] >= LZG_MIN_CAP) { big.push_back((uint32_t)i); words += out_cap[i] + 64; } }
-			if (too_large) { big.clear(); }
-			// ... and when it pays: the all-CU stage costs about 22 ms per GB of output whatever the units are (74 ms for 192 files, 3.39 GB), the
-			// block-per-unit kernel about 1 ms per MB of the LARGEST unit as long as there are no more large units than CUs (51 ms for the same 192
-			// files, whose largest is 51 MB; 60 ms for 12 of them, where the all-CU stage takes 5 ms)
-			bool pays = false;
-			{
-				uint64_t tot = 0, mx = 0;
-				for (uint32_t i : big) { tot += out_cap[i]; mx = out_cap[i] > mx ? out_cap[i] : mx; }
-				const double mb = 1.0 / (1 << 20), c_all = 0.022 * (double)tot * mb, per_cu = (double)tot * mb / 256.0, c_blk = 1.0 * ((double)mx * mb > per_cu ? (double)mx * mb : per_cu);
-				pays = c_all < c_blk;
-			}
-			if (!big.empty() && pays && words * 4 <= budget) {
-				const size_t nb = big.size(), upad = (nb + 1) / 2;              // the unit list in whole u64 slots
-				std::vector<uint64_t> tab(upad + 3 * (nb + 1));
-				memcpy(tab.data(), big.data(), nb * 4);
-				uint64_t* tbp = tab.data() + upad; uint64_t* tlp = tbp + nb + 1; uint64_t* wdp = tlp + nb + 1;
-				uint64_t tb = 0, tl = 0, wd = 0;
-				for (size_t k = 0; k < nb; ++k) {
-					const size_t i = big[k];
-					const uint64_t by_in = (format == MSCOMP_XPRESS ? 1 : 8) * in_len[i] + out_cap[i] / 32766u + 1, cnt = (out_cap[i] < by_in ? out_cap[i] : by_in) + 64;   // (the unit's token slots, as above)
-					tbp[k] = tb; tlp[k] = tl; wdp[k] = wd;
-					tb += (cnt + 8191) / 8192; tl += (out_cap[i] + (1u << LZG_TILE_SHIFT) - 1) >> LZG_TILE_SHIFT; wd += out_cap[i] + 64;
-				}
-				tbp[nb] = tb; tlp[nb] = tl; wdp[nb] = wd;
-				if (tb < 0x7FFFFFF0ull && tl < 0x7FFFFFF0ull) {
-					// an allocation that fails here only switches this (optional) path off: the block-per-unit kernel takes the units instead
-					const bool got = p->lzg_tab.reserve(tab.size() * 8) && c->lzg_bsum.reserve(tb * 8 + 64) && c->lzg_dir.reserve(tl * 8 + 64) && c->lzg_words.reserve(wd * 4 + LZG_PASSES * 4 + tl + 64);
-					if (got && (hipMemcpyAsync(p->lzg_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-					            hipStreamSynchronize(c->stream) != hipSuccess)) { p->lzg_tab.release(); p->tokpre.release(); p->tables.release(); delete p; return MSCOMP_ERRNO; }
-					if (got) { p->lzg_big = (uint32_t)nb; p->lzg_tb = (uint32_t)tb; p->lzg_tiles = (uint32_t)tl; p->lzg_words = wd; }
-					else { p->lzg_tab.release(); (void)hipGetLastError(); }
-				}
-			}
-		}
-		if (okd && format == MSCOMP_XPRESS) {
-			std::vector<uint32_t> big;
-			for (size_t i = 0; i < n_units; ++i) { if (in_len[i] >= XPS_MIN_IN) { big.push_back((uint32_t)i); } }
-			if (!big.empty()) {
-				const size_t nb = big.size(), upad = (nb + 1) / 2;
-				std::vector<uint64_t> tab(upad + nb + 1);
-				memcpy(tab.data(), big.data(), nb * 4);
-				// segment size / warm-up (MSCOMP_AMD_XPS_SEG_KB / _WARM_KB override the defaults, for measurements)
-				static const uint32_t seg_b = [] { const char* e = getenv("MSCOMP_AMD_XPS_SEG_KB"); const long v = e ? atol(e) : 0; return (uint32_t)(v >= 4 && v <= 65536 ? v << 10 : XPS_SEG); }();
-				static const uint32_t warm_b = [] { const char* e = getenv("MSCOMP_AMD_XPS_WARM_KB"); const long v = e ? atol(e) : 0; const uint32_t w = (uint32_t)(v >= 1 && v <= 65536 ? v << 10 : XPS_WARM); return w < seg_b ? w : seg_b; }();
-				p->xps_seg_bytes = seg_b; p->xps_warm_bytes = warm_b;
-				uint64_t sg = 0;
-				for (size_t k = 0; k < nb; ++k) { tab[upad + k] = sg; sg += (in_len[big[k]] + seg_b - 1) / seg_b; }
-				tab[upad + nb] = sg;
-				if (sg < 0x7FFFFFF0ull) {
-					okd = p->xps_tab.reserve(tab.size() * 8) && c->xps_buf.reserve(sg * XPS_SEG_BYTES + nb * 4 + n_units * 4 + 64);
-					if (okd && (hipMemcpyAsync(p->xps_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-					            hipStreamSynchronize(c->stream) != hipSuccess)) { p->xps_tab.release(); p->lzg_tab.release(); p->tokpre.release(); p->tables.release(); delete p; return MSCOMP_ERRNO; }
-					if (okd) { p->xps_big = (uint32_t)nb; p->xps_seg = (uint32_t)sg; }
-				}
-			}
-		}
-		if (!okd) { p->xps_tab.release(); p->lzg_tab.release(); p->tokpre.release(); p->tables.release(); delete p; return MSCOMP_MEM_ERROR; }
-		*out = p;
+	if (!decompress) {
+		if (!reserve_compress_scratch(c, format, n_units, p->n_chunks, p->lznt1_sa)) { return MSCOMP_MEM_ERROR; }
+		*out = p.release();
 		return MSCOMP_OK;
 	}
-	bool ok = c->slot_size.reserve(((size_t)p->n_chunks + 1) * sizeof(uint32_t)) &&
-	          c->prefix.reserve(((size_t)p->n_chunks + 2) * sizeof(uint64_t)) &&
-	          c->tile_sums.reserve(((size_t)p->n_chunks / 1024 + 4) * sizeof(uint64_t));
-	if (ok && format == MSCOMP_LZNT1) { ok = c->slots.reserve((size_t)p->n_chunks * LZNT1_SLOT + 64); }
-	if (ok && format == MSCOMP_LZNT1 && !p->decompress && !p->lznt1_sa) { ok = c->lzrec.reserve((size_t)p->n_chunks * LZNT1_REC + 64); }
-	if (ok && format != MSCOMP_LZNT1) {
-		const size_t per = (size_t)p->n_chunks * 65536u * sizeof(uint16_t) + 64;
-		// (mlen3: 4 bytes per position, both halves of the match word)
-		ok = c->links.reserve(per) && c->mlen3.reserve(2 * per) && c->lasthead.reserve(per / 2 + 64);
-		if (ok && format == MSCOMP_XPRESS) {
-			const size_t nw = (size_t)p->n_chunks * 1024u + 64;
-			ok = c->wtok.reserve(nw * 8) && c->wmat.reserve(nw * 8) && c->wfar.reserve(nw * 4);
-			if (ok && xpress_emit_mode_for(p->n_units, p->n_chunks) == 4) {    // the block-per-super-block kernels
-				const size_t ns = (size_t)p->n_chunks + 1;
-				ok = c->wrec.reserve(nw * 6 * 4) && c->sbrec.reserve(ns * (16 + 24 + 16 * 8 * 4 + 16 * 2 * 8 + 8));
+	bool okd = reserve_scan(c, p->n_chunks);
+	if (okd && format == MSCOMP_LZNT1) { okd = reserve_lzd_scratch(c, n_units, p->n_chunks); }
+	if (okd && format != MSCOMP_LZNT1) {
+		// tokpre: first token slot | Xpress+Huffman: first candidate slot | first token-scratch slot of every unit. A size plan writes no
+		// tokens (its token prefix stays zero; an Xpress size plan has no table at all)
+		const bool xh = format == MSCOMP_XPRESS_HUFF;
+		const size_t row = n_units + 1;
+		std::vector<uint64_t> tp(xh ? 3 * row : sizing ? 0 : row);
+		uint64_t slots = 0, cands = 0, scr = 0;
+		for (size_t i = 0; i < n_units; ++i) {
+			if (!sizing) { tp[i] = slots; slots += token_slots(format, in_len[i], out_cap[i]); }
+			if (xh) {
+				const uint64_t most = candidate_slots(in_len[i], out_cap[i]);
+				tp[row + i] = cands; tp[2 * row + i] = scr;
+				cands += most;
+				if (out_cap[i] > 65536u && !sizing) { scr += most; }        // a buffer of several chunks: its candidates keep their tokens (no second walk)
+			}
+		}
+		if (!sizing) { tp[n_units] = slots; }
+		if (xh) { tp[row + n_units] = cands; tp[2 * row + n_units] = scr; }
+		if (cands > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+		p->xhc_slots = (uint32_t)cands;
+		okd = p->tokpre.reserve(tp.size() * 8) && reserve_tokens(c, n_units, slots, !sizing) && (!xh || reserve_xhc(c, n_units, cands));
+		if (xh) {
+			// ... if that scratch is affordable: at most MSCOMP_AMD_XHC_SCR_MAX_MB (default 32 GiB; 0 = always walk twice) and at most half of
+			// what the device has free right now; a reservation that fails anyway switches the path off (the second walk needs no scratch)
+			static const uint64_t scr_env = [] { const char* e = getenv("MSCOMP_AMD_XHC_SCR_MAX_MB"); const long long v = e ? atoll(e) : 32768; return (uint64_t)(v < 0 ? 0 : v) << 20; }();
+			const uint64_t need = scr * XHC_SCR * 4 + 64, scr_budget = optional_scratch_budget(scr_env, c->dz_scr.cap);
+			if (scr && (need > scr_budget || !okd || !c->dz_scr.reserve(need))) { for (size_t i = 0; i <= n_units; ++i) { tp[2 * row + i] = 0; } scr = 0; }
+			p->xhc_scr = scr;
+		}
+		if (okd && !tp.empty() && !upload(c, p->tokpre, tp)) { return MSCOMP_ERRNO; }
+		p->tok_prefix = static_cast<u64*>(p->tokpre.p);
+		if (xh) { p->cand_prefix = p->tok_prefix + row; p->scr_prefix = p->tok_prefix + 2 * row; }
+	}
+	if (okd && !sizing && (format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF)) {
+		// units with room for LZG_MIN_CAP bytes or more get their bytes from all CUs (lzglobal.hip): 4 bytes of scratch per byte of capacity;
+		// when that is more than the budget (MSCOMP_AMD_LZG_MAX_MB, default 64 GiB of the 288; 0 switches the path off) the block-per-unit kernel takes them
+		static const uint64_t budget_env = [] { const char* e = getenv("MSCOMP_AMD_LZG_MAX_MB"); const long long v = e ? atoll(e) : 65536; return (uint64_t)(v < 0 ? 0 : v) << 20; }();
+		const uint64_t budget = optional_scratch_budget(budget_env, c->lzg_words.cap);   // ... and never more than half of the free HBM: the block kernel needs none of it
+		std::vector<uint32_t> big;
+		uint64_t words = 0;
+		bool too_large = false;                                       // (32-bit word indices: a unit with room for 4 GiB keeps the whole plan on the block kernel, which every such unit then takes)
+		for (size_t i = 0; i < n_units; ++i) { if (out_cap[i] >= 0xFFFFFF00ull) { too_large = true; } else if (out_cap[i] >= LZG_MIN_CAP) { big.push_back((uint32_t)i); words += out_cap[i] + 64; } }
+		if (too_large) { big.clear(); }
+		// ... and when it pays: the all-CU stage costs about 22 ms per GB of output whatever the units are (74 ms for 192 files, 3.39 GB), the
+		// block-per-unit kernel about 1 ms per MB of the LARGEST unit as long as there are no more large units than CUs (51 ms for the same 192
+		// files, whose largest is 51 MB; 60 ms for 12 of them, where the all-CU stage takes 5 ms)
+		bool pays = false;
+		{
+			uint64_t tot = 0, mx = 0;
+			for (uint32_t i : big) { tot += out_cap[i]; mx = out_cap[i] > mx ? out_cap[i] : mx; }
+			const double mb = 1.0 / (1 << 20), c_all = 0.022 * (double)tot * mb, per_cu = (double)tot * mb / 256.0, c_blk = 1.0 * ((double)mx * mb > per_cu ? (double)mx * mb : per_cu);
+			pays = c_all < c_blk;
+		}
+		if (!big.empty() && pays && words * 4 <= budget) {
+			const size_t nb = big.size(), upad = (nb + 1) / 2;              // the unit list in whole u64 slots
+			std::vector<uint64_t> tab(upad + 3 * (nb + 1));
+			memcpy(tab.data(), big.data(), nb * 4);
+			uint64_t* tbp = tab.data() + upad; uint64_t* tlp = tbp + nb + 1; uint64_t* wdp = tlp + nb + 1;
+			uint64_t tb = 0, tl = 0, wd = 0;
+			for (size_t k = 0; k < nb; ++k) {
+				const size_t i = big[k];
+				tbp[k] = tb; tlp[k] = tl; wdp[k] = wd;
+				tb += (token_slots(format, in_len[i], out_cap[i]) + 8191) / 8192; tl += (out_cap[i] + (1u << LZG_TILE_SHIFT) - 1) >> LZG_TILE_SHIFT; wd += out_cap[i] + 64;
+			}
+			tbp[nb] = tb; tlp[nb] = tl; wdp[nb] = wd;
+			if (tb < 0x7FFFFFF0ull && tl < 0x7FFFFFF0ull) {
+				// an allocation that fails here only switches this (optional) path off: the block-per-unit kernel takes the units instead
+				const bool got = p->lzg_tab.reserve(tab.size() * 8) && c->lzg_bsum.reserve(tb * 8 + 64) && c->lzg_dir.reserve(tl * 8 + 64) && c->lzg_words.reserve(wd * 4 + LZG_PASSES * 4 + tl + 64);
+				if (got && !upload(c, p->lzg_tab, tab)) { return MSCOMP_ERRNO; }
+				if (got) { p->lzg_big = (uint32_t)nb; p->lzg_tb = (uint32_t)tb; p->lzg_tiles = (uint32_t)tl; p->lzg_words = wd; }
+				else { p->lzg_tab.release(); (void)hipGetLastError(); }
 			}
 		}
 	}
-	if (ok && format == MSCOMP_XPRESS_HUFF) {
-		const size_t nc = (size_t)p->n_chunks + 1;
-		ok = c->tokbits.reserve(nc * 1024 * 8) && c->counts.reserve(nc * 512 * 4) && c->extra.reserve(nc * 4) &&
-		     c->lens.reserve(nc * 512) && c->codes.reserve(nc * 1024) && c->fb_list.reserve(nc * 4 + 64) && c->fbflag.reserve(nc * 4);
+	if (okd && format == MSCOMP_XPRESS) {
+		std::vector<uint32_t> big;
+		for (size_t i = 0; i < n_units; ++i) { if (in_len[i] >= XPS_MIN_IN) { big.push_back((uint32_t)i); } }
+		if (!big.empty()) {
+			const size_t nb = big.size(), upad = (nb + 1) / 2;
+			std::vector<uint64_t> tab(upad + nb + 1);
+			memcpy(tab.data(), big.data(), nb * 4);
+			// segment size / warm-up (MSCOMP_AMD_XPS_SEG_KB / _WARM_KB override the defaults, for measurements)
+			static const uint32_t seg_b = [] { const char* e = getenv("MSCOMP_AMD_XPS_SEG_KB"); const long v = e ? atol(e) : 0; return (uint32_t)(v >= 4 && v <= 65536 ? v << 10 : XPS_SEG); }();
+			static const uint32_t warm_b = [] { const char* e = getenv("MSCOMP_AMD_XPS_WARM_KB"); const long v = e ? atol(e) : 0; const uint32_t w = (uint32_t)(v >= 1 && v <= 65536 ? v << 10 : XPS_WARM); return w < seg_b ? w : seg_b; }();
+			p->xps_seg_bytes = seg_b; p->xps_warm_bytes = warm_b;
+			uint64_t sg = 0;
+			for (size_t k = 0; k < nb; ++k) { tab[upad + k] = sg; sg += (in_len[big[k]] + seg_b - 1) / seg_b; }
+			tab[upad + nb] = sg;
+			if (sg < 0x7FFFFFF0ull) {
+				okd = p->xps_tab.reserve(tab.size() * 8) && c->xps_buf.reserve(sg * XPS_SEG_BYTES + nb * 4 + n_units * 4 + 64);
+				if (okd && !upload(c, p->xps_tab, tab)) { return MSCOMP_ERRNO; }
+				if (okd) { p->xps_big = (uint32_t)nb; p->xps_seg = (uint32_t)sg; }
+			}
+		}
 	}
-	if (!ok) { p->tables.release(); delete p; return MSCOMP_MEM_ERROR; }
-	*out = p;
+	if (!okd) { return MSCOMP_MEM_ERROR; }
+	*out = p.release();
 	return MSCOMP_OK;
 }
 
@@ -489,7 +496,6 @@ void mscomp_amd_plan_destroy(mscomp_amd_plan* p)
 	if (!p) { return; }
 	DeviceGuard g(p->ctx->device);
 	(void)hipStreamSynchronize(p->ctx->stream);
-	if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); }
 	if (p->tables.p) {
 		// the pool keeps the 8 LARGEST buffers it has seen: a full pool gives up its smallest one for a larger one (a pool full of
 		// small buffers made every larger plan hipFree on destroy -- a device-wide wait)
@@ -498,10 +504,9 @@ void mscomp_amd_plan_destroy(mscomp_amd_plan* p)
 		else {
 			size_t least = 0;
 			for (size_t i = 1; i < pool.size(); ++i) { if (pool[i].cap < pool[least].cap) { least = i; } }
-			if (pool[least].cap < p->tables.cap) { DevBuf t = pool[least]; pool[least] = p->tables; p->tables = t; }   // (the smaller one is released below)
+			if (pool[least].cap < p->tables.cap) { DevBuf t = pool[least]; pool[least] = p->tables; p->tables = t; }   // (the smaller one is released with the plan)
 		}
 	}
-	p->tables.release(); p->tokpre.release(); p->lzg_tab.release(); p->xps_tab.release();
 	delete p;
 }
 
@@ -571,6 +576,18 @@ static XhcBufs xhc_bufs(mscomp_amd_ctx* c, const mscomp_amd_plan* p)
 	return xb;
 }
 
+// the segment tables and scratch of the large Xpress streams of p (xps_*): none when the plan does not take that path
+static XpsTables xps_tables(const mscomp_amd_plan* p, mscomp_amd_ctx* c)
+{
+	XpsTables x = {};
+	if (!p->xps_big) { return x; }
+	const size_t nb = p->xps_big, upad = (nb + 1) / 2;
+	const uint64_t* t = static_cast<const uint64_t*>(p->xps_tab.p);
+	x.unit = reinterpret_cast<const uint32_t*>(t); x.seg_prefix = t + upad; x.n_big = p->xps_big; x.n_seg = p->xps_seg; x.seg_bytes = p->xps_seg_bytes; x.warm_bytes = p->xps_warm_bytes;
+	x.seg = c->xps_buf.p; x.mode = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->xps_buf.p) + (size_t)p->xps_seg * XPS_SEG_BYTES); x.done = x.mode + nb;
+	return x;
+}
+
 // the per-unit path verdicts an execution of p leaves in the ctx scratch: Xpress+Huffman, XHC_SPEC / XHC_SERIAL for every unit (xhc_chain_kernel);
 // Xpress, the segment walk's mode for every unit with XPS_MIN_IN input bytes or more (2 = done by segments, 0 = the one-wave walk), none when
 // the plan does not take that path
@@ -579,140 +596,136 @@ static void note_modes(mscomp_amd_plan* p)
 	mscomp_amd_ctx* c = p->ctx;
 	c->dbg_mode = nullptr; c->dbg_mode_n = 0;
 	if (p->format == MSCOMP_XPRESS_HUFF && p->n_units) { c->dbg_mode = xhc_bufs(c, p).mode; c->dbg_mode_n = p->n_units; }
-	if (p->format == MSCOMP_XPRESS && p->xps_big && (p->sizing || g_xpd_mode.load(std::memory_order_relaxed) == 0)) {
-		c->dbg_mode = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(c->xps_buf.p) + (size_t)p->xps_seg * XPS_SEG_BYTES); c->dbg_mode_n = p->xps_big;
-	}
+	if (p->format == MSCOMP_XPRESS && p->xps_big && (p->sizing || g_xpd_mode.load(std::memory_order_relaxed) == 0)) { c->dbg_mode = xps_tables(p, c).mode; c->dbg_mode_n = p->xps_big; }
 }
 
-static MSCompStatus plan_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
+// ---- the launch sequences: one per direction, for host-table and device-table plans alike ----
+// A dev plan runs the DEV instances of the chunk-gridded kernels (p->dev: bt.n_chunks is its bound, the blocks past chunk_prefix[n_units] return at
+// once); its table pass goes in front of these launches and its reject pass behind them, at the call site (mscomp_amd_plan_execute_dev /
+// _execute_size_dev). The paths that need host-chosen tables are off for it by their zero counts: no xps_* segments, no lzglobal.hip stage, no
+// Xpress+Huffman token scratch.
+static void decode_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
 {
 	mscomp_amd_ctx* c = p->ctx;
 	hipStream_t st = c->stream;
+	const u64* tp = p->tok_prefix; uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
+	const u64 gmin = p->lzg_big ? (u64)LZG_MIN_CAP : ~(u64)0;
+	switch (p->format) {
+	case MSCOMP_LZNT1: {
+		const LzdBufs b = lzd_bufs(c, p);
+		if (p->dev) { launch_dev_zero(st, b.selcnt, p->n_chunks); }       // segments past the real count add nothing to the scan (a kernel, no memset: the launches may go into a caller's graph)
+		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b, p->dev); }
+		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
+		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
+		{ KernelTimer t(c, "lzd_chunk_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 0); }
+		{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status); }
+		{ KernelTimer t(c, "lzd_replace_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 1); }
+		return;
+	}
+	case MSCOMP_XPRESS: {                                          // tokens a flag word at a time, then the copy kernels; large streams of host plans by segments first
+		const int mode = p->dev ? 2 : g_xpd_mode.load(std::memory_order_relaxed);   // (the test hook switches host plans only)
+		if (mode == 1) { KernelTimer t(c, "xpd_kernel"); launch_xpress_decompress(st, d_in, p->bt, d_out, d_out_len, d_status); return; }
+		static const char* const names[3] = {"xpt_parse_kernel", "lz_copy_kernel", "lz_copy_block_kernel"};
+		const XpsTables x = mode != 2 ? xps_tables(p, c) : XpsTables{};
+		if (x.n_big) {
+			{ KernelTimer t2(c, "xps_walk_kernel"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -1, gmin, x); }
+			static const uint32_t rounds = [] { const char* e = getenv("MSCOMP_AMD_XPS_ROUNDS"); const long v = e ? atol(e) : 0; return (uint32_t)(v >= 1 && v <= 256 ? v : XPS_ROUNDS); }();
+			for (uint32_t r = 0; r < rounds; ++r) { KernelTimer t2(c, "xps_redo_kernels"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -2, gmin, x); }
+			{ KernelTimer t2(c, "xps_emit_kernel"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -3, gmin, x); }
+		}
+		for (int ph = 0; ph < 3; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, ph, gmin, x); }
+		break;
+	}
+	default: {                                                     // MSCOMP_XPRESS_HUFF (without token scratch the accepted chunks are walked twice)
+		XhcBufs xb = xhc_bufs(c, p);
+		if (p->xhc_scr) { xb.scr_prefix = p->scr_prefix; xb.scr_tok = static_cast<uint32_t*>(c->dz_scr.p); }
+		static const char* const names[6] = { "xhc_mark_kernel", "xhc_parse_kernel", "xhc_chain_kernel", "xhc_parse2_kernel", "xhd_parse_kernel", "lz_copy_kernel" };
+		for (int ph = 0; ph < 6; ++ph) {
+			KernelTimer t(c, names[ph]);
+			launch_xpress_huff_decompress(st, d_in, p->bt, tp, tok, ntok, p->cand_prefix, p->xhc_slots, xb, d_out, d_out_len, d_status, ph, gmin, p->dev);
+		}
+		break;
+	}
+	}
+	run_lz_copy_global(c, p, st, tp, tok, ntok, d_out_len, d_status, d_out);
+}
+
+static void compress_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
+{
+	mscomp_amd_ctx* c = p->ctx;
+	hipStream_t st = c->stream;
+	const bool dev = p->dev;
 	uint32_t* slot_size = static_cast<uint32_t*>(c->slot_size.p);
 	u64* prefix = static_cast<u64*>(c->prefix.p);
 	u64* tile_sums = static_cast<u64*>(c->tile_sums.p);
-	if (p->decompress) {
-		switch (p->format) {
-		case MSCOMP_LZNT1: {
-			const LzdBufs b = lzd_bufs(c, p);
-			{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b); }
-			{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
-			{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, prefix, p->n_chunks, tile_sums); }
-			{ KernelTimer t(c, "lzd_chunk_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 0); }
-			{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status); }
-			{ KernelTimer t(c, "lzd_replace_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 1); }
-			return MSCOMP_OK;
-		}
-		case MSCOMP_XPRESS: {
-			if (g_xpd_mode.load(std::memory_order_relaxed) == 1) { KernelTimer t(c, "xpd_kernel"); launch_xpress_decompress(st, d_in, p->bt, d_out, d_out_len, d_status); return MSCOMP_OK; }
-			const u64* tp = static_cast<const u64*>(p->tokpre.p); uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
-			static const char* const names[3] = {"xpt_parse_kernel", "lz_copy_kernel", "lz_copy_block_kernel"};
-			const u64 gmin = p->lzg_big ? (u64)LZG_MIN_CAP : ~(u64)0;
-			XpsTables x = {};
-			if (p->xps_big && g_xpd_mode.load(std::memory_order_relaxed) != 2) {
-				const size_t nb = p->xps_big, upad = (nb + 1) / 2;
-				const uint64_t* t = static_cast<const uint64_t*>(p->xps_tab.p);
-				x.unit = reinterpret_cast<const uint32_t*>(t); x.seg_prefix = t + upad; x.n_big = p->xps_big; x.n_seg = p->xps_seg; x.seg_bytes = p->xps_seg_bytes; x.warm_bytes = p->xps_warm_bytes;
-				x.seg = c->xps_buf.p; x.mode = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->xps_buf.p) + (size_t)p->xps_seg * XPS_SEG_BYTES); x.done = x.mode + nb;
-				{ KernelTimer t2(c, "xps_walk_kernel"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -1, gmin, x); }
-				static const uint32_t rounds = [] { const char* e = getenv("MSCOMP_AMD_XPS_ROUNDS"); const long v = e ? atol(e) : 0; return (uint32_t)(v >= 1 && v <= 256 ? v : XPS_ROUNDS); }();
-				for (uint32_t r = 0; r < rounds; ++r) { KernelTimer t2(c, "xps_redo_kernels"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -2, gmin, x); }
-				{ KernelTimer t2(c, "xps_emit_kernel"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -3, gmin, x); }
-			}
-			for (int ph = 0; ph < 3; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, ph, gmin, x); }
-			run_lz_copy_global(c, p, st, tp, tok, ntok, d_out_len, d_status, d_out);
-			return MSCOMP_OK;
-		}
-		case MSCOMP_XPRESS_HUFF: {
-			const u64* tp = static_cast<const u64*>(p->tokpre.p); uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
-			const u64* cp = tp + (p->n_units + 1u);
-			XhcBufs xb = xhc_bufs(c, p);
-			if (p->xhc_scr) { xb.scr_prefix = tp + 2 * (p->n_units + 1u); xb.scr_tok = static_cast<uint32_t*>(c->dz_scr.p); }
-			static const char* const names[6] = { "xhc_mark_kernel", "xhc_parse_kernel", "xhc_chain_kernel", "xhc_parse2_kernel", "xhd_parse_kernel", "lz_copy_kernel" };
-			for (int ph = 0; ph < 6; ++ph) {
-				KernelTimer t(c, names[ph]);
-				launch_xpress_huff_decompress(st, d_in, p->bt, tp, tok, ntok, cp, p->xhc_slots, xb, d_out, d_out_len, d_status, ph, p->lzg_big ? (u64)LZG_MIN_CAP : ~(u64)0);
-			}
-			run_lz_copy_global(c, p, st, tp, tok, ntok, d_out_len, d_status, d_out);
-			return MSCOMP_OK;
-		}
-		default:
-			return MSCOMP_ARG_ERROR;
-		}
-	}
+	uint16_t* links = static_cast<uint16_t*>(c->links.p); uint16_t* lasthead = static_cast<uint16_t*>(c->lasthead.p);
+	uint16_t* mlen3 = static_cast<uint16_t*>(c->mlen3.p); uint16_t* moff = mlen3 + 1;   /* one word per position: length - 3 | offset << 16 (common.h S16) */
+	const bool find = !p->matches_ready;                           // (Xpress formats: the pipelined one-shot call has run links + find itself, for this execution only)
+	p->matches_ready = false;
 	switch (p->format) {
-	case MSCOMP_LZNT1: {
+	case MSCOMP_LZNT1: {                                           // (dev: the chunk kernels write a size of 0 for the chunks past the real count)
 		uint8_t* slots = static_cast<uint8_t*>(c->slots.p);
-		if (p->lznt1_sa) { KernelTimer t(c, "lznt1_sa_chunk_kernel"); launch_lznt1_sa_chunks(st, d_in, p->bt, slots, slot_size); }
-		else { KernelTimer t(c, "lznt1_chunk_kernel"); launch_lznt1_chunks(st, d_in, p->bt, slots, slot_size, static_cast<uint16_t*>(c->lzrec.p)); }
+		if (p->lznt1_sa) { KernelTimer t(c, "lznt1_sa_chunk_kernel"); launch_lznt1_sa_chunks(st, d_in, p->bt, slots, slot_size, dev); }
+		else { KernelTimer t(c, "lznt1_chunk_kernel"); launch_lznt1_chunks(st, d_in, p->bt, slots, slot_size, static_cast<uint16_t*>(c->lzrec.p), dev); }
 		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, slot_size, prefix, p->n_chunks, tile_sums); }
-		{ KernelTimer t(c, "concat_slots_kernel"); launch_concat_slots(st, slots, LZNT1_SLOT, slot_size, prefix, p->bt, d_out); }
+		{ KernelTimer t(c, "concat_slots_kernel"); launch_concat_slots(st, slots, LZNT1_SLOT, slot_size, prefix, p->bt, d_out, dev); }
 		{ KernelTimer t(c, "finalize_units_kernel"); launch_finalize_units(st, prefix, p->bt, d_out, d_out_len, d_status, 1); }
 		break;
 	}
 	case MSCOMP_XPRESS: {
-		uint16_t* links = static_cast<uint16_t*>(c->links.p); uint16_t* lasthead = static_cast<uint16_t*>(c->lasthead.p);
-		uint16_t* mlen3 = static_cast<uint16_t*>(c->mlen3.p); uint16_t* moff = mlen3 + 1;   /* one word per position: length - 3 | offset << 16 (common.h S16) */
-		if (p->matches_ready) { p->matches_ready = false; }
-		else {
-			{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead); }
+		if (find) {
+			{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead, dev); }
 			// units of one link chunk: Find only where a greedy parse can start a token, window and links in LDS; longer streams: every position
-			if (g_finder_mode.load(std::memory_order_relaxed) != 2 && p->max_unit <= 65536u) { KernelTimer t(c, "xp_lazy2_kernel"); launch_xp_lazy2(st, d_in, p->bt, links, mlen3, moff); }
-			else { KernelTimer t(c, "xp_find_kernel"); launch_xp_find(st, d_in, p->bt, links, lasthead, mlen3, moff, 0x2000u, 0); }
+			if (g_finder_mode.load(std::memory_order_relaxed) != 2 && p->max_unit <= 65536u) { KernelTimer t(c, "xp_lazy2_kernel"); launch_xp_lazy2(st, d_in, p->bt, links, mlen3, moff, dev); }
+			else { KernelTimer t(c, "xp_find_kernel"); launch_xp_find(st, d_in, p->bt, links, lasthead, mlen3, moff, 0x2000u, 0, dev); }
 		}
-		{ KernelTimer t(c, "xpress_emit_kernel"); launch_xpress_emit(st, d_in, p->bt, mlen3, moff, xpress_win_bufs(c, p->n_chunks), d_out, d_out_len, d_status); }
+		{ KernelTimer t(c, "xpress_emit_kernel"); launch_xpress_emit(st, d_in, p->bt, mlen3, moff, xpress_win_bufs(c, p->n_chunks), d_out, d_out_len, d_status, dev); }
 		break;
 	}
-	case MSCOMP_XPRESS_HUFF: {
-		uint16_t* links = static_cast<uint16_t*>(c->links.p); uint16_t* lasthead = static_cast<uint16_t*>(c->lasthead.p);
-		uint16_t* mlen3 = static_cast<uint16_t*>(c->mlen3.p); uint16_t* moff = mlen3 + 1;   /* one word per position: length - 3 | offset << 16 (common.h S16) */
+	default: {                                                     // MSCOMP_XPRESS_HUFF (dev: xh_huff_kernel<true> writes a size of 0 for the chunks past the real count)
 		u64* tokbits = static_cast<u64*>(c->tokbits.p); uint32_t* counts = static_cast<uint32_t*>(c->counts.p);
 		uint32_t* extra = static_cast<uint32_t*>(c->extra.p); uint8_t* lens = static_cast<uint8_t*>(c->lens.p);
 		uint16_t* codes = static_cast<uint16_t*>(c->codes.p); uint32_t* fbflag = static_cast<uint32_t*>(c->fbflag.p);
 		uint32_t* fb_count = static_cast<uint32_t*>(c->fb_list.p); uint32_t* fb_list = fb_count + 16;
-		if (p->matches_ready) { p->matches_ready = false; }
-		else {
-			{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead); }
-			{ KernelTimer t(c, "xp_find_kernel"); launch_xp_find(st, d_in, p->bt, links, lasthead, mlen3, moff, 0xFFFFu, 1); }
+		if (find) {
+			{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead, dev); }
+			{ KernelTimer t(c, "xp_find_kernel"); launch_xp_find(st, d_in, p->bt, links, lasthead, mlen3, moff, 0xFFFFu, 1, dev); }
 		}
-		{ KernelTimer t(c, "xh_parse_kernel"); launch_xh_parse(st, d_in, p->bt, mlen3, moff, tokbits, counts, extra); }
-		{ KernelTimer t(c, "xh_huff_kernel"); launch_xh_huff(st, p->bt, counts, extra, lens, codes, slot_size, fb_list, fb_count, fbflag); }
+		{ KernelTimer t(c, "xh_parse_kernel"); launch_xh_parse(st, d_in, p->bt, mlen3, moff, tokbits, counts, extra, dev); }
+		{ KernelTimer t(c, "xh_huff_kernel"); launch_xh_huff(st, p->bt, counts, extra, lens, codes, slot_size, fb_list, fb_count, fbflag, dev); }
 		{ KernelTimer t(c, "xh_fallback_kernel"); launch_xh_fallback(st, d_in, p->bt, fb_list, fb_count, XH_FB_BLOCKS, tokbits, lens, codes, slot_size); }
 		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, slot_size, prefix, p->n_chunks, tile_sums); }
-		{ KernelTimer t(c, "xh_encode_kernel"); launch_xh_encode(st, d_in, p->bt, mlen3, moff, tokbits, lens, codes, fbflag, prefix, d_out); }
+		{ KernelTimer t(c, "xh_encode_kernel"); launch_xh_encode(st, d_in, p->bt, mlen3, moff, tokbits, lens, codes, fbflag, prefix, d_out, dev); }
 		{ KernelTimer t(c, "finalize_units_kernel"); launch_finalize_units(st, prefix, p->bt, d_out, d_out_len, d_status, 0); }
 		break;
 	}
-	default:
-		return MSCOMP_ARG_ERROR;
 	}
-	return MSCOMP_OK;
 }
 
-MSCompStatus mscomp_amd_plan_execute(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
+// One execution of a plan: its launches, given as `launch`. A plan that is executed repeatedly replays them as one hipGraph (the gaps between
+// the 4-9 launches are ~3 % of an LZNT1 pass): captured on the second execution and again whenever a pointer (args), the ctx scratch or a
+// kernel switch moved. Plain launches instead: on the first execution (one-time function attributes are set there), while profiling (the
+// per-kernel events are not part of a graph), with MSCOMP_AMD_NO_GRAPH, for no_graph plans, and while the caller captures the ctx stream (the
+// launches then go into the caller's graph; a stream whose capture state cannot be read counts as captured). Only executions that may replay
+// are counted.
+extern "C++" template <class Launch>
+static MSCompStatus plan_run(mscomp_amd_plan* p, const void* const (&args)[9], const Launch& launch)
 {
-	if (!p || p->sizing || p->dev || (p->n_units && (!d_out_len || !d_status)) || (p->total_in && !d_in)) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_ctx* c = p->ctx;
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
 	static const bool no_graph = getenv("MSCOMP_AMD_NO_GRAPH") != nullptr;
-	if (p->decompress) { note_modes(p); }
-	++p->executions;
-	// A plan that is executed repeatedly replays its 4-9 launches as one hipGraph (the gaps between the launches are
-	// ~3 % of an LZNT1 pass). Not while profiling (the per-kernel events are not part of the graph), not on the first
-	// execution (one-time function attributes are set there).
-	if (!no_graph && !p->no_graph && !c->profiling && p->executions >= 2 && p->n_units) {
+	if (cs == hipStreamCaptureStatusNone && !no_graph && !p->no_graph && !c->profiling && p->n_units && ++p->executions >= 2) {
 		const uint64_t mode_now = g_mode_epoch.load(std::memory_order_acquire);
-		const bool same = p->gexec && p->g_epoch == c->epoch && p->g_mode == mode_now && p->g_args[0] == d_in && p->g_args[1] == d_out &&
-		                  p->g_args[2] == d_out_len && p->g_args[3] == d_status;
+		const bool same = p->gexec && p->g_epoch == c->epoch && p->g_mode == mode_now && memcmp(p->g_args, args, sizeof args) == 0;
 		if (!same) {
 			if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
 			hipGraph_t graph = nullptr;
 			if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-				const MSCompStatus ls = plan_launch(p, d_in, d_out, d_out_len, d_status);
+				launch();
 				const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
-				if (ls == MSCOMP_OK && ee == hipSuccess && graph && hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0) == hipSuccess) {
-					p->g_epoch = c->epoch; p->g_mode = mode_now; p->g_args[0] = d_in; p->g_args[1] = d_out; p->g_args[2] = d_out_len; p->g_args[3] = d_status;
+				if (ee == hipSuccess && graph && hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0) == hipSuccess) {
+					p->g_epoch = c->epoch; p->g_mode = mode_now; memcpy(p->g_args, args, sizeof args);
 				} else { p->gexec = nullptr; }
 				if (graph) { (void)hipGraphDestroy(graph); }
 			}
@@ -720,9 +733,18 @@ MSCompStatus mscomp_amd_plan_execute(mscomp_amd_plan* p, const uint8_t* d_in, ui
 		}
 		if (p->gexec) { return hipGraphLaunch(p->gexec, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
 	}
-	const MSCompStatus ls = plan_launch(p, d_in, d_out, d_out_len, d_status);
-	if (ls != MSCOMP_OK) { return ls; }
+	launch();
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
+}
+
+MSCompStatus mscomp_amd_plan_execute(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!p || p->sizing || p->dev || (p->n_units && (!d_out_len || !d_status)) || (p->total_in && !d_in)) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(p->ctx->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (p->decompress) { note_modes(p); }
+	const void* args[9] = { d_in, d_out, d_out_len, d_status };
+	return plan_run(p, args, [&] { (p->decompress ? decode_launch : compress_launch)(p, d_in, d_out, d_out_len, d_status); });
 }
 
 MSCompStatus mscomp_amd_compress_batch(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units,
@@ -774,24 +796,21 @@ static void size_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out
 {
 	mscomp_amd_ctx* c = p->ctx;
 	hipStream_t st = c->stream;
+	u64* ntok = static_cast<u64*>(c->dz_ntok.p);
 	switch (p->format) {
-	case MSCOMP_LZNT1: {                                   // the header chain as in plan_launch, then every chunk sized, then the verdict at the limit
+	case MSCOMP_LZNT1: {                                   // the header chain as in decode_launch, then every chunk sized, then the verdict at the limit (which writes need)
 		const LzdBufs b = lzd_bufs(c, p);
-		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b); }
+		if (p->dev) { launch_dev_zero(st, b.selcnt, p->n_chunks); }   // (as in decode_launch)
+		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b, p->dev); }
 		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
 		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
 		{ KernelTimer t(c, "lzd_size_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, nullptr, 2); }
 		{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status, d_need); }
-		return;
+		break;
 	}
-	case MSCOMP_XPRESS: {
-		u64* ntok = static_cast<u64*>(c->dz_ntok.p);
-		XpsTables x = {};
-		if (p->xps_big) {
-			const size_t nb = p->xps_big, upad = (nb + 1) / 2;
-			const uint64_t* t = static_cast<const uint64_t*>(p->xps_tab.p);
-			x.unit = reinterpret_cast<const uint32_t*>(t); x.seg_prefix = t + upad; x.n_big = p->xps_big; x.n_seg = p->xps_seg; x.seg_bytes = p->xps_seg_bytes; x.warm_bytes = p->xps_warm_bytes;
-			x.seg = c->xps_buf.p; x.mode = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->xps_buf.p) + (size_t)p->xps_seg * XPS_SEG_BYTES); x.done = x.mode + nb;
+	case MSCOMP_XPRESS: {                                  // large streams of host plans by segments, the others (a dev plan: every stream) by the one-wave walk
+		const XpsTables x = xps_tables(p, c);
+		if (x.n_big) {
 			{ KernelTimer t2(c, "xps_walk_kernel"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, -1, x); }
 			for (uint32_t r = 0; r < XPS_ROUNDS; ++r) { KernelTimer t2(c, "xps_redo_kernels"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, -2, x); }
 			{ KernelTimer t2(c, "xps_size_kernel"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, -3, x); }
@@ -800,17 +819,12 @@ static void size_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out
 		break;
 	}
 	default: {                                             // MSCOMP_XPRESS_HUFF
-		const u64* cp = static_cast<const u64*>(p->tokpre.p) + (p->n_units + 1u);
-		u64* ntok = static_cast<u64*>(c->dz_ntok.p);
 		const XhcBufs xb = xhc_bufs(c, p);
 		static const char* const names[4] = { "xhc_mark_kernel", "xhc_size_kernel", "xhc_chain_kernel", "xhd_size_kernel" };
-		for (int ph = 0; ph < 4; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_huff_size(st, d_in, p->bt, ntok, cp, p->xhc_slots, xb, d_out_len, d_status, ph); }
+		for (int ph = 0; ph < 4; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_huff_size(st, d_in, p->bt, ntok, p->cand_prefix, p->xhc_slots, xb, d_out_len, d_status, ph, p->dev); }
 		break;
 	}
 	}
-	// Xpress / Xpress+Huffman: the smallest capacity that decodes is the length itself (every length test is "does it fit"), and d_out_len is 0
-	// for a unit that is not MSCOMP_OK
-	(void)hipMemcpyAsync(d_need, d_out_len, (size_t)p->n_units * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
 }
 
 MSCompStatus mscomp_amd_plan_execute_size(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status)
@@ -819,7 +833,13 @@ MSCompStatus mscomp_amd_plan_execute_size(mscomp_amd_plan* p, const uint8_t* d_i
 	mscomp_amd_ctx* c = p->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (p->n_units) { note_modes(p); size_launch(p, d_in, d_out_len, d_need, d_status); }
+	if (p->n_units) {
+		note_modes(p);
+		size_launch(p, d_in, d_out_len, d_need, d_status);
+		// Xpress / Xpress+Huffman: the smallest capacity that decodes is the length itself (every length test is "does it fit"), and d_out_len is 0
+		// for a unit that is not MSCOMP_OK
+		if (p->format != MSCOMP_LZNT1) { (void)hipMemcpyAsync(d_need, d_out_len, (size_t)p->n_units * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream); }
+	}
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
@@ -837,31 +857,41 @@ MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* c, MSCompFormat 
 	return s;
 }
 
-// ---- decompress plans with device tables (include/mscomp_amd.h): created from bounds, tables built on the device by every execution ----
+// ---- plans with device tables (include/mscomp_amd.h): created from bounds, tables built on the device by every execution ----
 // The plan holds its bounds and scratch sized for them; p->tables holds what the table pass (devplan.hip) writes each time:
-//   san (4 x n u64: in_off | in_len | out_off | out_cap, zero for a rejected unit) | chunk prefix (u32, n + 1) | token prefix | candidate
-//   prefix (u64, n + 1 each) | reject (u32, n)
-// and bt points into it with n_chunks = the bound (the kernels that are gridded by chunks return past chunk_prefix[n_units]). The paths that
-// need host-chosen tables stay off: no xps_* segments, no lzglobal.hip stage, no Xpress+Huffman token scratch.
-static size_t dev_table_words(uint64_t n) { return 4 * n + (n + 2) / 2 + 1 + 2 * (n + 1) + (n + 1) / 2 + 1; }
+//   san (4 x n u64: in_off | in_len | out_off | out_cap, zero for a rejected unit) | chunk prefix (u32, n + 1) | decompress and size plans:
+//   token prefix | candidate prefix (u64, n + 1 each) | reject (u32, n)
+// and bt points into it with n_chunks = the bound (the kernels that are gridded by chunks return past chunk_prefix[n_units]). The only place
+// that knows this layout: the launch code reads p->bt, p->tok_prefix, p->cand_prefix and p->reject.
+static bool reserve_dev_tables(mscomp_amd_plan* p)
+{
+	const size_t n = p->n_units, cpw = (n + 2) / 2 + (p->decompress ? 1 : 0), tpw = p->decompress ? 2 * (n + 1) : 0;
+	if (!p->tables.reserve((4 * n + cpw + tpw + (n + 1) / 2 + 1) * 8)) { return false; }
+	set_bt(p);
+	u64* tp = static_cast<u64*>(p->tables.p) + 4 * n + cpw;
+	if (p->decompress) { p->tok_prefix = tp; p->cand_prefix = tp + (n + 1); }
+	p->reject = reinterpret_cast<uint32_t*>(tp + tpw);
+	return true;
+}
 
-MSCompStatus mscomp_amd_plan_create_decompress_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint64_t out_total_max,
-                                                   mscomp_amd_plan** out)
+// Decompress plans, and size plans: a decompress dev plan whose table pass takes the limits for the capacities (devplan.hip
+// dv_tables_kernel<true>), with no bound on their sum (out_total_max = 2^64 - 1 here: a unit's candidate slots are then bounded by its input,
+// whatever its limit) and whose scratch follows the input alone (the token prefix is written and not used: a size plan stores no tokens).
+static MSCompStatus create_decode_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint64_t out_total_max, bool sizing,
+                                      mscomp_amd_plan** out)
 {
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
 	if (!c || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
 	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	// the bounds of the per-unit counts summed over the batch: every accepted unit has in_len <= 0xFFFFF000 and the accepted ones sum to at
+	// the bounds of the per-unit counts summed over the batch (checked before the context is used): every accepted unit has in_len <= 0xFFFFF000 and the accepted ones sum to at
 	// most in_total_max / out_total_max; a rejected unit counts as an empty one (one chunk, 64 token slots, 3 candidates)
 	const uint64_t N = n_units, I = in_total_max < N * 0xFFFFF000ull ? in_total_max : N * 0xFFFFF000ull, O = out_total_max;
 	uint64_t chunks = N, toks = 0, cands = 0;
 	if (format == MSCOMP_LZNT1) { chunks = N + I / LZD_SEG; }
 	if (format == MSCOMP_XPRESS_HUFF) { chunks = N + I / XHC_TILE_BYTES; }
 	if (chunks > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
-	if (format != MSCOMP_LZNT1) {
+	if (format != MSCOMP_LZNT1 && !sizing) {
 		const uint64_t by_in = (format == MSCOMP_XPRESS ? 1 : 8) * I + O / 32766u + N;   // (I < 2^45 here for Xpress+Huffman: its chunk bound held)
 		toks = (O < by_in ? O : by_in) + 64 * N;
 		if (toks > (1ull << 46)) { return MSCOMP_MEM_ERROR; }
@@ -871,79 +901,33 @@ MSCompStatus mscomp_amd_plan_create_decompress_dev(mscomp_amd_ctx* c, MSCompForm
 		cands = most + most / 4 + 2 * N;
 		if (cands > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
 	}
-	mscomp_amd_plan* p = new (std::nothrow) mscomp_amd_plan();
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());
 	if (!p) { return MSCOMP_MEM_ERROR; }
-	p->ctx = c; p->format = format; p->decompress = true; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
-	p->in_total_max = in_total_max; p->out_total_max = out_total_max; p->total_in = in_total_max; p->xhc_slots = (uint32_t)cands;
-	bool ok = p->tables.reserve(dev_table_words(N) * 8);
-	if (ok && format == MSCOMP_LZNT1) {
-		ok = c->prefix.reserve((chunks + 2) * sizeof(uint64_t)) && c->tile_sums.reserve((chunks / 1024 + 4) * sizeof(uint64_t)) &&
-		     c->dz_cin.reserve(chunks * LZD_SLOTS * 4 + 64) && c->dz_csize.reserve(chunks * LZD_SLOTS * 2 + 64) &&
-		     c->dz_unit.reserve((chunks * (5 * LZD_K + 2) + N * 2 + 8) * 4);
-	}
-	if (ok && format != MSCOMP_LZNT1) { ok = c->dz_tok.reserve(toks * 4 + 256) && c->dz_ntok.reserve((N + 1) * 8); }
-	if (ok && format == MSCOMP_XPRESS_HUFF) { ok = c->dz_xhc.reserve((N + 1) * 8 + cands * (4 * 4 + 3 * 8) + 64); }
-	if (!ok) { (void)hipGetLastError(); p->tables.release(); delete p; return MSCOMP_MEM_ERROR; }
+	p->ctx = c; p->format = format; p->decompress = true; p->sizing = sizing; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
+	p->in_total_max = in_total_max; p->out_total_max = sizing ? 0 : out_total_max; p->total_in = in_total_max; p->xhc_slots = (uint32_t)cands;
+	bool ok = reserve_dev_tables(p.get());
+	if (ok && format == MSCOMP_LZNT1) { ok = reserve_scan(c, chunks) && reserve_lzd_scratch(c, N, chunks); }
+	if (ok && format != MSCOMP_LZNT1) { ok = reserve_tokens(c, N, toks, !sizing); }
+	if (ok && format == MSCOMP_XPRESS_HUFF) { ok = reserve_xhc(c, N, cands); }
+	if (!ok) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	// the one-time kernel attributes of the instances this plan launches: set now, so that no first launch happens inside a caller's capture
-	if (format == MSCOMP_LZNT1) { prepare_lzd_segments(true); } else { prepare_lz_copy_block(); }
-	u64* san = static_cast<u64*>(p->tables.p);
-	p->bt.in_off = san; p->bt.in_len = san + N; p->bt.out_off = san + 2 * N; p->bt.out_cap = san + 3 * N;
-	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(san + 4 * N);
-	p->bt.n_units = p->n_units; p->bt.n_chunks = p->n_chunks;
-	*out = p;
+	if (format == MSCOMP_LZNT1) { prepare_lzd_segments(true); } else if (!sizing) { prepare_lz_copy_block(); }
+	*out = p.release();
 	return MSCOMP_OK;
 }
-
-static void dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint8_t* d_out,
-                       const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+MSCompStatus mscomp_amd_plan_create_decompress_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint64_t out_total_max,
+                                                   mscomp_amd_plan** out)
 {
-	mscomp_amd_ctx* c = p->ctx;
-	hipStream_t st = c->stream;
-	const uint32_t n = p->n_units;
-	u64* san = static_cast<u64*>(p->tables.p);
-	uint32_t* chunk_prefix = reinterpret_cast<uint32_t*>(san + 4 * (size_t)n);
-	u64* tp = san + 4 * (size_t)n + (n + 2u) / 2 + 1;                 // token prefix, then the candidate prefix
-	uint32_t* reject = reinterpret_cast<uint32_t*>(tp + 2 * ((size_t)n + 1));
-	{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_tables(st, (int)p->format, n, p->in_total_max, p->out_total_max, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, tp, reject); }
-	const u64 no_lzg = ~(u64)0;
-	switch (p->format) {
-	case MSCOMP_LZNT1: {
-		const LzdBufs b = lzd_bufs(c, p);
-		launch_dev_zero(st, b.selcnt, p->n_chunks);                     // segments past the real count add nothing to the scan
-		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b, true); }
-		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
-		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
-		{ KernelTimer t(c, "lzd_chunk_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 0); }
-		{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status); }
-		{ KernelTimer t(c, "lzd_replace_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 1); }
-		break;
-	}
-	case MSCOMP_XPRESS: {                                       // the flag-word token path without segments (g_xpd_mode 2)
-		uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
-		static const char* const names[3] = {"xpt_parse_kernel", "lz_copy_kernel", "lz_copy_block_kernel"};
-		const XpsTables x = {};
-		for (int ph = 0; ph < 3; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, ph, no_lzg, x); }
-		break;
-	}
-	default: {                                                  // MSCOMP_XPRESS_HUFF, without token scratch (the accepted chunks are walked twice)
-		uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
-		const XhcBufs xb = xhc_bufs(c, p);
-		static const char* const names[6] = { "xhc_mark_kernel", "xhc_parse_kernel", "xhc_chain_kernel", "xhc_parse2_kernel", "xhd_parse_kernel", "lz_copy_kernel" };
-		for (int ph = 0; ph < 6; ++ph) {
-			KernelTimer t(c, names[ph]);
-			launch_xpress_huff_decompress(st, d_in, p->bt, tp, tok, ntok, tp + (n + 1u), p->xhc_slots, xb, d_out, d_out_len, d_status, ph, no_lzg, true);
-		}
-		break;
-	}
-	}
-	{ KernelTimer t(c, "dv_reject_kernel"); launch_dev_reject(st, reject, n, d_out_len, d_status); }
+	return create_decode_dev(c, format, n_units, in_total_max, out_total_max, false, out);
+}
+MSCompStatus mscomp_amd_plan_create_size_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, mscomp_amd_plan** out)
+{
+	return create_decode_dev(c, format, n_units, in_total_max, ~(uint64_t)0, true, out);
 }
 
-// ---- compress plans with device tables (include/mscomp_amd.h): the compressing half of the same pipeline ----
-// p->tables holds san (4 x n u64, as above) | chunk prefix (u32, n + 1) | reject (u32, n), written by dv_ctables_kernel at every execution.
-// bt.n_chunks is the plan's chunk bound; every chunk-gridded kernel runs its DEV instance, which returns past chunk_prefix[n_units].
-static size_t cdev_table_words(uint64_t n) { return 4 * n + (n + 2) / 2 + (n + 1) / 2 + 1; }
-
+// Compress plans: the compressing half of the same pipeline (tables by dv_ctables_kernel).
 MSCompStatus mscomp_amd_plan_create_compress_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint64_t in_unit_max,
                                                  mscomp_amd_plan** out)
 {
@@ -956,134 +940,21 @@ MSCompStatus mscomp_amd_plan_create_compress_dev(mscomp_amd_ctx* c, MSCompFormat
 	// chunks of the accepted units: each has at most ceil(U / k), and as sum ceil(L / k) <= N + floor(sum L / k), at most N + floor(I / k) in all
 	// (the first term keeps a batch of 64 KiB units at one link chunk -- 448 KiB of Xpress match scratch -- per unit)
 	const uint64_t N = n_units, U = in_unit_max, I = in_total_max < N * U ? in_total_max : N * U;
-	const uint64_t k = format == MSCOMP_LZNT1 ? 4096u : 65536u;
-	const uint64_t by_unit = N * ((U + k - 1) / k), by_total = N + I / k, chunks = by_unit < by_total ? by_unit : by_total;
+	const uint64_t by_unit = N * compress_chunks(format, U), by_total = N + I / compress_chunk_bytes(format), chunks = by_unit < by_total ? by_unit : by_total;
 	if (chunks > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
-	mscomp_amd_plan* p = new (std::nothrow) mscomp_amd_plan();
+	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());
 	if (!p) { return MSCOMP_MEM_ERROR; }
 	p->ctx = c; p->format = format; p->decompress = false; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
-	p->in_total_max = in_total_max; p->in_unit_max = U; p->total_in = in_total_max; p->max_unit = U;   // (max_unit: the Xpress finder, as plan_launch chooses it)
+	p->in_total_max = in_total_max; p->total_in = in_total_max; p->max_unit = U;   // (max_unit: the bound dv_ctables_kernel checks, and the Xpress finder as compress_launch chooses it)
 	p->lznt1_sa = format == MSCOMP_LZNT1 && lznt1_sa_for(c);
-	// the scratch of plan_create_impl for this many chunks
-	bool ok = p->tables.reserve(cdev_table_words(N) * 8) &&
-	          c->slot_size.reserve((chunks + 1) * sizeof(uint32_t)) && c->prefix.reserve((chunks + 2) * sizeof(uint64_t)) &&
-	          c->tile_sums.reserve((chunks / 1024 + 4) * sizeof(uint64_t));
-	if (ok && format == MSCOMP_LZNT1) { ok = c->slots.reserve(chunks * LZNT1_SLOT + 64); }
-	if (ok && format == MSCOMP_LZNT1 && !p->lznt1_sa) { ok = c->lzrec.reserve(chunks * LZNT1_REC + 64); }
-	if (ok && format != MSCOMP_LZNT1) {
-		const size_t per = chunks * 65536u * sizeof(uint16_t) + 64;
-		ok = c->links.reserve(per) && c->mlen3.reserve(2 * per) && c->lasthead.reserve(per / 2 + 64);
-		if (ok && format == MSCOMP_XPRESS) {
-			const size_t nw = chunks * 1024u + 64;
-			ok = c->wtok.reserve(nw * 8) && c->wmat.reserve(nw * 8) && c->wfar.reserve(nw * 4);
-			if (ok && xpress_emit_mode_for(p->n_units, p->n_chunks) == 4) {   // (launch_xpress_emit chooses from the same two numbers)
-				const size_t ns = chunks + 1;
-				ok = c->wrec.reserve(nw * 6 * 4) && c->sbrec.reserve(ns * (16 + 24 + 16 * 8 * 4 + 16 * 2 * 8 + 8));
-			}
-		}
-	}
-	if (ok && format == MSCOMP_XPRESS_HUFF) {
-		const size_t nc = chunks + 1;
-		ok = c->tokbits.reserve(nc * 1024 * 8) && c->counts.reserve(nc * 512 * 4) && c->extra.reserve(nc * 4) &&
-		     c->lens.reserve(nc * 512) && c->codes.reserve(nc * 1024) && c->fb_list.reserve(nc * 4 + 64) && c->fbflag.reserve(nc * 4);
-	}
-	if (!ok) { (void)hipGetLastError(); p->tables.release(); delete p; return MSCOMP_MEM_ERROR; }
+	if (!reserve_dev_tables(p.get()) || !reserve_compress_scratch(c, format, N, chunks, p->lznt1_sa)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	// the one-time kernel attributes of the instances this plan launches: set now, so that no first launch happens inside a caller's capture
 	if (format == MSCOMP_LZNT1 && p->lznt1_sa) { prepare_lznt1_sa(true); }
 	if (format != MSCOMP_LZNT1) { prepare_xp_match(true); }
 	if (format == MSCOMP_XPRESS) { prepare_xp_lazy2(true); }
 	if (format == MSCOMP_XPRESS_HUFF) { prepare_xh_fallback(); }
-	u64* san = static_cast<u64*>(p->tables.p);
-	p->bt.in_off = san; p->bt.in_len = san + N; p->bt.out_off = san + 2 * N; p->bt.out_cap = san + 3 * N;
-	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(san + 4 * N);
-	p->bt.n_units = p->n_units; p->bt.n_chunks = p->n_chunks;
-	*out = p;
+	*out = p.release();
 	return MSCOMP_OK;
-}
-
-static void dev_compress_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint8_t* d_out,
-                                const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
-{
-	mscomp_amd_ctx* c = p->ctx;
-	hipStream_t st = c->stream;
-	const uint32_t n = p->n_units;
-	u64* san = static_cast<u64*>(p->tables.p);
-	uint32_t* chunk_prefix = reinterpret_cast<uint32_t*>(san + 4 * (size_t)n);
-	uint32_t* reject = chunk_prefix + 2 * ((n + 2u) / 2);
-	uint32_t* slot_size = static_cast<uint32_t*>(c->slot_size.p);
-	u64* prefix = static_cast<u64*>(c->prefix.p);
-	u64* tile_sums = static_cast<u64*>(c->tile_sums.p);
-	{ KernelTimer t(c, "dv_ctables_kernel"); launch_dev_ctables(st, (int)p->format, n, p->in_total_max, p->in_unit_max, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, reject); }
-	switch (p->format) {
-	case MSCOMP_LZNT1: {                                        // (the chunk kernels write a size of 0 for the chunks past the real count)
-		uint8_t* slots = static_cast<uint8_t*>(c->slots.p);
-		if (p->lznt1_sa) { KernelTimer t(c, "lznt1_sa_chunk_kernel"); launch_lznt1_sa_chunks(st, d_in, p->bt, slots, slot_size, true); }
-		else { KernelTimer t(c, "lznt1_chunk_kernel"); launch_lznt1_chunks(st, d_in, p->bt, slots, slot_size, static_cast<uint16_t*>(c->lzrec.p), true); }
-		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, slot_size, prefix, p->n_chunks, tile_sums); }
-		{ KernelTimer t(c, "concat_slots_kernel"); launch_concat_slots(st, slots, LZNT1_SLOT, slot_size, prefix, p->bt, d_out, true); }
-		{ KernelTimer t(c, "finalize_units_kernel"); launch_finalize_units(st, prefix, p->bt, d_out, d_out_len, d_status, 1); }
-		break;
-	}
-	case MSCOMP_XPRESS: {
-		uint16_t* links = static_cast<uint16_t*>(c->links.p); uint16_t* lasthead = static_cast<uint16_t*>(c->lasthead.p);
-		uint16_t* mlen3 = static_cast<uint16_t*>(c->mlen3.p); uint16_t* moff = mlen3 + 1;
-		{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead, true); }
-		if (g_finder_mode.load(std::memory_order_relaxed) != 2 && p->in_unit_max <= 65536u) { KernelTimer t(c, "xp_lazy2_kernel"); launch_xp_lazy2(st, d_in, p->bt, links, mlen3, moff, true); }
-		else { KernelTimer t(c, "xp_find_kernel"); launch_xp_find(st, d_in, p->bt, links, lasthead, mlen3, moff, 0x2000u, 0, true); }
-		{ KernelTimer t(c, "xpress_emit_kernel"); launch_xpress_emit(st, d_in, p->bt, mlen3, moff, xpress_win_bufs(c, p->n_chunks), d_out, d_out_len, d_status, true); }
-		break;
-	}
-	default: {                                                  // MSCOMP_XPRESS_HUFF (xh_huff_kernel<true> writes a size of 0 for the chunks past the real count)
-		uint16_t* links = static_cast<uint16_t*>(c->links.p); uint16_t* lasthead = static_cast<uint16_t*>(c->lasthead.p);
-		uint16_t* mlen3 = static_cast<uint16_t*>(c->mlen3.p); uint16_t* moff = mlen3 + 1;
-		u64* tokbits = static_cast<u64*>(c->tokbits.p); uint32_t* counts = static_cast<uint32_t*>(c->counts.p);
-		uint32_t* extra = static_cast<uint32_t*>(c->extra.p); uint8_t* lens = static_cast<uint8_t*>(c->lens.p);
-		uint16_t* codes = static_cast<uint16_t*>(c->codes.p); uint32_t* fbflag = static_cast<uint32_t*>(c->fbflag.p);
-		uint32_t* fb_count = static_cast<uint32_t*>(c->fb_list.p); uint32_t* fb_list = fb_count + 16;
-		{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead, true); }
-		{ KernelTimer t(c, "xp_find_kernel"); launch_xp_find(st, d_in, p->bt, links, lasthead, mlen3, moff, 0xFFFFu, 1, true); }
-		{ KernelTimer t(c, "xh_parse_kernel"); launch_xh_parse(st, d_in, p->bt, mlen3, moff, tokbits, counts, extra, true); }
-		{ KernelTimer t(c, "xh_huff_kernel"); launch_xh_huff(st, p->bt, counts, extra, lens, codes, slot_size, fb_list, fb_count, fbflag, true); }
-		{ KernelTimer t(c, "xh_fallback_kernel"); launch_xh_fallback(st, d_in, p->bt, fb_list, fb_count, XH_FB_BLOCKS, tokbits, lens, codes, slot_size); }
-		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, slot_size, prefix, p->n_chunks, tile_sums); }
-		{ KernelTimer t(c, "xh_encode_kernel"); launch_xh_encode(st, d_in, p->bt, mlen3, moff, tokbits, lens, codes, fbflag, prefix, d_out, true); }
-		{ KernelTimer t(c, "finalize_units_kernel"); launch_finalize_units(st, prefix, p->bt, d_out, d_out_len, d_status, 0); }
-		break;
-	}
-	}
-	{ KernelTimer t(c, "dv_reject_kernel"); launch_dev_reject(st, reject, n, d_out_len, d_status); }
-}
-
-// The launches of a dev plan, given as `launch`. While the caller captures the ctx stream, plain launches go into the caller's graph. Otherwise,
-// from the second execution on, the launches are replayed as the plan's own graph (as plan_execute does), captured again whenever a pointer
-// (args), the scratch or a kernel switch moved. A stream whose capture state cannot be read counts as captured.
-extern "C++" template <class Launch>
-static MSCompStatus dev_run(mscomp_amd_plan* p, const void* const (&args)[9], const Launch& launch)
-{
-	mscomp_amd_ctx* c = p->ctx;
-	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-	if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-	static const bool no_graph = getenv("MSCOMP_AMD_NO_GRAPH") != nullptr;
-	if (cs == hipStreamCaptureStatusNone && !no_graph && !c->profiling && ++p->executions >= 2) {
-		const uint64_t mode_now = g_mode_epoch.load(std::memory_order_acquire);
-		const bool same = p->gexec && p->g_epoch == c->epoch && p->g_mode == mode_now && memcmp(p->g_args, args, sizeof args) == 0;
-		if (!same) {
-			if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
-			hipGraph_t graph = nullptr;
-			if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-				launch();
-				const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
-				if (ee == hipSuccess && graph && hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0) == hipSuccess) {
-					p->g_epoch = c->epoch; p->g_mode = mode_now; memcpy(p->g_args, args, sizeof args);
-				} else { p->gexec = nullptr; }
-				if (graph) { (void)hipGraphDestroy(graph); }
-			}
-			(void)hipGetLastError();
-		}
-		if (p->gexec) { return hipGraphLaunch(p->gexec, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
-	}
-	launch();
-	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
 MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -1098,93 +969,20 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	if (p->decompress) { note_modes(p); }
-	const void* args[9] = { d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, nullptr };
-	return dev_run(p, args, [&] { (p->decompress ? dev_launch : dev_compress_launch)(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status); });
-}
-
-// ---- size plans with device tables (include/mscomp_amd.h): the size query of a batch whose tables GPU work has written ----
-// A decompress dev plan whose table pass takes the limits for the capacities (devplan.hip dv_tables_kernel<true>) and whose launches are those
-// of size_launch without the segment phases of large Xpress streams. p->tables is laid out as a decompress dev plan's (the token prefix is
-// written and not used: a size plan stores no tokens). Scratch follows the input alone.
-MSCompStatus mscomp_amd_plan_create_size_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, mscomp_amd_plan** out)
-{
-	if (!out) { return MSCOMP_ARG_ERROR; }
-	*out = nullptr;
-	if (!c || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
-	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
-	// the bounds of mscomp_amd_plan_create_decompress_dev with no output bound: a unit's candidate slots are then bounded by its input
-	// (in_len / 260 + 1, a quarter more, + 2), whatever its limit
-	const uint64_t N = n_units, I = in_total_max < N * 0xFFFFF000ull ? in_total_max : N * 0xFFFFF000ull;
-	uint64_t chunks = N, cands = 0;
-	if (format == MSCOMP_LZNT1) { chunks = N + I / LZD_SEG; }
-	if (format == MSCOMP_XPRESS_HUFF) { chunks = N + I / XHC_TILE_BYTES; }
-	if (chunks > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
-	if (format == MSCOMP_XPRESS_HUFF) {
-		const uint64_t most = I / 260u + N;
-		cands = most + most / 4 + 2 * N;
-		if (cands > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
-	}
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	mscomp_amd_plan* p = new (std::nothrow) mscomp_amd_plan();
-	if (!p) { return MSCOMP_MEM_ERROR; }
-	p->ctx = c; p->format = format; p->decompress = true; p->sizing = true; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
-	p->in_total_max = in_total_max; p->total_in = in_total_max; p->xhc_slots = (uint32_t)cands;
-	bool ok = p->tables.reserve(dev_table_words(N) * 8);
-	if (ok && format == MSCOMP_LZNT1) {
-		ok = c->prefix.reserve((chunks + 2) * sizeof(uint64_t)) && c->tile_sums.reserve((chunks / 1024 + 4) * sizeof(uint64_t)) &&
-		     c->dz_cin.reserve(chunks * LZD_SLOTS * 4 + 64) && c->dz_csize.reserve(chunks * LZD_SLOTS * 2 + 64) &&
-		     c->dz_unit.reserve((chunks * (5 * LZD_K + 2) + N * 2 + 8) * 4);
-	}
-	if (ok && format != MSCOMP_LZNT1) { ok = c->dz_ntok.reserve((N + 1) * 8); }
-	if (ok && format == MSCOMP_XPRESS_HUFF) { ok = c->dz_xhc.reserve((N + 1) * 8 + cands * (4 * 4 + 3 * 8) + 64); }
-	if (!ok) { (void)hipGetLastError(); p->tables.release(); delete p; return MSCOMP_MEM_ERROR; }
-	if (format == MSCOMP_LZNT1) { prepare_lzd_segments(true); }     // (its first execution may be captured by the caller)
-	u64* san = static_cast<u64*>(p->tables.p);
-	p->bt.in_off = san; p->bt.in_len = san + N; p->bt.out_off = san + 2 * N; p->bt.out_cap = san + 3 * N;
-	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(san + 4 * N);
-	p->bt.n_units = p->n_units; p->bt.n_chunks = p->n_chunks;
-	*out = p;
-	return MSCOMP_OK;
-}
-
-static void size_dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, const uint64_t* d_limit,
-                            uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status)
-{
-	mscomp_amd_ctx* c = p->ctx;
-	hipStream_t st = c->stream;
-	const uint32_t n = p->n_units;
-	u64* san = static_cast<u64*>(p->tables.p);
-	uint32_t* chunk_prefix = reinterpret_cast<uint32_t*>(san + 4 * (size_t)n);
-	u64* tp = san + 4 * (size_t)n + (n + 2u) / 2 + 1;                 // token prefix (not used), then the candidate prefix
-	uint32_t* reject = reinterpret_cast<uint32_t*>(tp + 2 * ((size_t)n + 1));
-	{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_stables(st, (int)p->format, n, p->in_total_max, d_in_off, d_in_len, d_limit, san, chunk_prefix, tp, reject); }
-	switch (p->format) {
-	case MSCOMP_LZNT1: {                                        // size_launch's sequence on the DEV instance of the segment kernel
-		const LzdBufs b = lzd_bufs(c, p);
-		launch_dev_zero(st, b.selcnt, p->n_chunks);                     // segments past the real count add nothing to the scan
-		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b, true); }
-		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
-		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
-		{ KernelTimer t(c, "lzd_size_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, nullptr, 2); }
-		{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status, d_need); }
-		break;
-	}
-	case MSCOMP_XPRESS: {                                       // every stream by the one-wave walk
-		const XpsTables x = {};
-		{ KernelTimer t(c, "xpt_size_kernel"); launch_xpress_size(st, d_in, p->bt, static_cast<u64*>(c->dz_ntok.p), d_out_len, d_status, 0, x); }
-		break;
-	}
-	default: {                                                  // MSCOMP_XPRESS_HUFF
-		u64* ntok = static_cast<u64*>(c->dz_ntok.p);
-		const XhcBufs xb = xhc_bufs(c, p);
-		static const char* const names[4] = { "xhc_mark_kernel", "xhc_size_kernel", "xhc_chain_kernel", "xhd_size_kernel" };
-		for (int ph = 0; ph < 4; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_huff_size(st, d_in, p->bt, ntok, tp + (n + 1u), p->xhc_slots, xb, d_out_len, d_status, ph, true); }
-		break;
-	}
-	}
-	// rejected units; and need = length where the kernels above did not write it (LZNT1's finalize did)
-	{ KernelTimer t(c, "dv_size_finish_kernel"); launch_dev_size_finish(st, reject, n, d_out_len, d_need, d_status, p->format != MSCOMP_LZNT1); }
+	const void* args[9] = { d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status };
+	return plan_run(p, args, [&] {
+		u64* san = static_cast<u64*>(p->tables.p); uint32_t* chunk_prefix = const_cast<uint32_t*>(p->bt.chunk_prefix);
+		const int f = (int)p->format; const uint32_t n = p->n_units;
+		if (p->decompress) {
+			{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_tables(c->stream, f, n, p->in_total_max, p->out_total_max, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, p->tok_prefix, p->reject); }
+			decode_launch(p, d_in, d_out, d_out_len, d_status);
+		} else {
+			{ KernelTimer t(c, "dv_ctables_kernel"); launch_dev_ctables(c->stream, f, n, p->in_total_max, p->max_unit, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, p->reject); }
+			compress_launch(p, d_in, d_out, d_out_len, d_status);
+		}
+		// the units the table pass rejected (the kernels saw them as empty units without room)
+		{ KernelTimer t(c, "dv_reject_kernel"); launch_dev_reject(c->stream, p->reject, n, d_out_len, d_status); }
+	});
 }
 
 MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -1198,8 +996,15 @@ MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* p, const uint8_t*
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	note_modes(p);
-	const void* args[9] = { d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status, nullptr, nullptr };
-	return dev_run(p, args, [&] { size_dev_launch(p, d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status); });
+	const void* args[9] = { d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status };
+	return plan_run(p, args, [&] {
+		{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_stables(c->stream, (int)p->format, p->n_units, p->in_total_max, d_in_off, d_in_len, d_limit, static_cast<u64*>(p->tables.p),
+		                                                          const_cast<uint32_t*>(p->bt.chunk_prefix), p->tok_prefix, p->reject); }
+		size_launch(p, d_in, d_out_len, d_need, d_status);
+		// rejected units; and need = length where the kernels above did not write it (LZNT1's finalize did) -- a kernel, where a host size plan
+		// ends with a copy: no memcpy node in a caller's graph
+		{ KernelTimer t(c, "dv_size_finish_kernel"); launch_dev_size_finish(c->stream, p->reject, p->n_units, d_out_len, d_need, d_status, p->format != MSCOMP_LZNT1); }
+	});
 }
 
 MSCompStatus mscomp_amd_layout_dev(mscomp_amd_ctx* c, size_t n_units, const uint64_t* d_cap, uint64_t align, uint64_t* d_off)
@@ -1222,22 +1027,15 @@ MSCompStatus mscomp_amd_plan_layout_dev(mscomp_amd_ctx* c, MSCompFormat format, 
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
-// Stage-level test hook: per-position (len-3 capped at 45, offset) of ONE unit as found by the HIP match finder.
-// h_len3/h_off: host arrays of in_len u16. max_off 0x2000 (Xpress) or 0xFFFF (Xpress+Huffman, clip to 64 KiB chunks).
 // ---- batch helpers: capacity planning and device-side compaction ----
 uint64_t mscomp_amd_plan_layout(MSCompFormat format, size_t n_units, const uint64_t* in_len, uint64_t align, uint64_t* out_off, uint64_t* out_cap)
 {
 	if (!align) { align = 1; }
 	uint64_t pos = 0;
+	const bool known = format == MSCOMP_NONE || format == MSCOMP_LZNT1 || format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF;
+	if (n_units && !known) { return (uint64_t)-1; }
 	for (size_t i = 0; i < n_units; ++i) {
-		size_t cap;
-		switch ((int)format) {
-		case MSCOMP_LZNT1:       cap = lznt1_max_compressed_size((size_t)in_len[i]) + 2; break;   // room for the uncounted End_of_buffer
-		case MSCOMP_XPRESS:      cap = xpress_max_compressed_size((size_t)in_len[i]); break;
-		case MSCOMP_XPRESS_HUFF: cap = xpress_huff_max_compressed_size((size_t)in_len[i]); break;
-		case MSCOMP_NONE:        cap = (size_t)in_len[i]; break;
-		default:                 return (uint64_t)-1;
-		}
+		const uint64_t cap = layout_cap((int)format, in_len[i]);     // (common.h: the format's largest output; MSCOMP_NONE, the length)
 		if (out_off) { out_off[i] = pos; }
 		if (out_cap) { out_cap[i] = cap; }
 		pos += (cap + align - 1) / align * align;
@@ -1280,6 +1078,8 @@ MSCompStatus mscomp_amd_compact_dev(mscomp_amd_ctx* c, size_t n_units, const uin
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
+// Stage-level test hook: per-position (len-3 capped at 45, offset) of ONE unit as found by the HIP match finder.
+// h_len3/h_off: host arrays of in_len u16. max_off 0x2000 (Xpress) or 0xFFFF (Xpress+Huffman, clip to 64 KiB chunks).
 MSCompStatus mscomp_amd_debug_xpress_matches(mscomp_amd_ctx* c, const uint8_t* d_in, size_t in_len, uint32_t max_off, int clip,
                                              uint16_t* h_len3, uint16_t* h_off)
 {
@@ -1332,7 +1132,6 @@ MSCompStatus mscomp_amd_debug_huff_lengths_slow(mscomp_amd_ctx* c, const uint32_
 int mscomp_amd_debug_hooks_enabled(void) { return test_hooks_on() ? 1 : 0; }
 // Test hook: which Xpress parse/emit kernel runs (0 = chosen by batch size, 1 = one wave per unit, 2 = four waves per unit).
 void mscomp_amd_debug_set_xpress_emit(int mode) { if (!test_hooks_on()) { return; } set_xpress_emit_mode(mode); g_mode_epoch.fetch_add(1, std::memory_order_acq_rel); }
-// ... and which LZNT1 chunk kernel (0 = default, 1 = one wave per chunk, 2 = four waves per chunk).
 uint32_t mscomp_amd_debug_lzd_walked(mscomp_amd_ctx* c)
 {
 	if (!c) { return 0xFFFFFFFFu; }
@@ -1372,6 +1171,7 @@ int mscomp_amd_debug_decode_modes(mscomp_amd_ctx* c, uint32_t* out, size_t cap)
 void mscomp_amd_debug_set_xpress_decoder(int mode) { if (!test_hooks_on()) { return; } g_xpd_mode.store(mode, std::memory_order_relaxed); g_mode_epoch.fetch_add(1, std::memory_order_acq_rel); }
 void mscomp_amd_debug_set_finder(int mode) { if (!test_hooks_on()) { return; } g_finder_mode.store(mode, std::memory_order_relaxed); g_mode_epoch.fetch_add(1, std::memory_order_acq_rel); }
 void mscomp_amd_debug_set_one_shot(int mode) { if (!test_hooks_on()) { return; } g_one_zero_copy.store(mode == 1 ? 0 : 1, std::memory_order_relaxed); }
+// Test hook: which LZNT1 chunk kernel (0 = default, 1 = one wave per chunk, 2 = four waves per chunk).
 void mscomp_amd_debug_set_lznt1(int mode) { if (!test_hooks_on()) { return; } set_lznt1_mode(mode); g_mode_epoch.fetch_add(1, std::memory_order_acq_rel); }
 // Test hook: 1 = the order-independent form of the LZNT1 bucket sort and the Xpress chain links on every device (what a device that fails the
 // lane-order self-check gets), 0 = back to one atomic per 64 positions

@@ -104,6 +104,48 @@ struct BatchTables {
 	uint32_t        n_chunks;
 };
 
+// ---- the counts a plan is sized by ------------------------------------------------------------------------
+// One definition for the host (api.hip: exact tables of host plans, bounds of dev plans) and for the table passes that build the same
+// tables on the device (devplan.hip): a dev plan gives the host plan's bytes and statuses because both take their counts from here.
+// `format` is the MSCompFormat value: 2 LZNT1, 3 Xpress, 4 Xpress+Huffman.
+#define LZD_SEG        49152u                             // LZNT1 decompression: input bytes per segment of the header walk
+#define XHC_TILE_BYTES 16384u                             // Xpress+Huffman decompression: input bytes per tile of the candidate search
+// chunks of a unit of n input bytes when it is compressed: 4 KiB chunks for LZNT1, 64 KiB for the Xpress formats (Xpress: link chunks, one
+// stream per unit); an empty unit has none and gets 0 bytes of output
+__host__ __device__ inline u64 compress_chunk_bytes(int format) { return format == 2 ? 4096u : 65536u; }
+__host__ __device__ inline u64 compress_chunks(int format, u64 n) { const u64 k = compress_chunk_bytes(format); return (n + k - 1u) / k; }
+// ... and when it is decompressed: LZNT1, segments of the header walk; Xpress+Huffman, tiles of the candidate search; at least one
+__host__ __device__ inline u64 decode_chunks(int format, u64 n)
+{
+	if (format == 2) { return n ? (n + LZD_SEG - 1u) / LZD_SEG : 1u; }
+	if (format == 4) { return n ? (n + XHC_TILE_BYTES - 1u) / XHC_TILE_BYTES : 1u; }
+	return 1u;
+}
+// token slots of a unit of `len` compressed bytes with room for `cap`: a token takes at least one input byte (Xpress; an Xpress+Huffman
+// symbol at least one bit) and gives at least one output byte, and a match is cut into one more token per 32766 bytes (LZT_MAXLEN of
+// decompress.hip); 64 slots of slack
+__host__ __device__ inline u64 token_slots(int format, u64 len, u64 cap)
+{
+	const u64 by_in = (format == 3 ? 1u : 8u) * len + cap / 32766u + 1u;
+	return (cap < by_in ? cap : by_in) + 64u;
+}
+// candidate chunk starts of an Xpress+Huffman unit: a chunk gives 65536 bytes and takes at least 260; a quarter more for windows that only
+// look like a table
+__host__ __device__ inline u64 candidate_slots(u64 len, u64 cap)
+{
+	const u64 by_out = cap / 65536u + 2u, by_len = len / 260u + 1u, most = by_out < by_len ? by_out : by_len;
+	return most + most / 4u + 2u;
+}
+// the largest output of n input bytes (the reference's *_max_compressed_size), and the capacity mscomp_amd_plan_layout gives such a unit
+__host__ __device__ inline u64 lznt1_max_out(u64 n)       { return n + 3u + 2u * ((n + 4095u) / 4096u); }
+__host__ __device__ inline u64 xpress_max_out(u64 n)      { return n + 4u + 4u * (n / 32u); }
+__host__ __device__ inline u64 xpress_huff_max_out(u64 n) { return n + 34u + 258u + 258u * (n / 65536u); }
+__host__ __device__ inline u64 layout_cap(int format, u64 n)
+{
+	return format == 2 ? lznt1_max_out(n) + 2u            // room for the uncounted End_of_buffer
+	     : format == 3 ? xpress_max_out(n) : format == 4 ? xpress_huff_max_out(n) : n;
+}
+
 // largest u with chunk_prefix[u] <= c   (uniform per block: scalar loads)
 __device__ __forceinline__ uint32_t unit_of_chunk(const uint32_t* __restrict__ prefix, uint32_t n_units, uint32_t c)
 {

@@ -56,19 +56,12 @@ __global__ __launch_bounds__(DV_THREADS) void dv_tables_kernel(int format, uint3
 		dv_block_scan<2>(r, run, s_w);                                   // running totals up to and including unit i
 		const bool rej = live && (len > 0xFFFFF000ull || r[0] > in_max || (!SIZING && r[1] > out_max));
 		const u64 L = rej ? 0 : len, C = rej ? 0 : cap;                  // a rejected unit is an empty unit without room
-		// the host formulas of plan_create_impl: chunks_of(format, true, L); token slots; Xpress+Huffman candidate slots
+		// the counts of a host plan (common.h; api.hip plan_create_impl): chunks; token slots; Xpress+Huffman candidate slots
 		u64 c[3] = {0, 0, 0};
 		if (live) {
-			if (format == 2) { c[0] = L ? (L + LZD_SEG - 1u) / LZD_SEG : 1u; }
-			else if (format == 3) {
-				const u64 by_in = L + C / 32766u + 1u;
-				c[0] = 1; c[1] = (C < by_in ? C : by_in) + 64u;
-			} else {
-				const u64 by_in = 8u * L + C / 32766u + 1u;
-				c[0] = L ? (L + XHC_TILE_BYTES - 1u) / XHC_TILE_BYTES : 1u; c[1] = (C < by_in ? C : by_in) + 64u;
-				const u64 by_out = C / 65536u + 2u, by_len = L / 260u + 1u, most = by_out < by_len ? by_out : by_len;
-				c[2] = most + most / 4u + 2u;
-			}
+			if (format == 2) { c[0] = decode_chunks(2, L); }
+			else if (format == 3) { c[0] = decode_chunks(3, L); c[1] = token_slots(3, L, C); }
+			else { c[0] = decode_chunks(4, L); c[1] = token_slots(4, L, C); c[2] = candidate_slots(L, C); }
 			san[i] = rej ? 0 : in_off[i]; san[n + i] = L; san[2u * (size_t)n + i] = rej || SIZING ? 0 : out_off[i]; san[3u * (size_t)n + i] = C;
 			reject[i] = rej ? 1u : 0u;
 		}
@@ -77,7 +70,7 @@ __global__ __launch_bounds__(DV_THREADS) void dv_tables_kernel(int format, uint3
 	}
 }
 
-// The compress form: per unit the checks of a compress dev plan, the sanitised row and the chunk prefix of chunks_of(format, false, L) (api.hip).
+// The compress form: per unit the checks of a compress dev plan, the sanitised row and the chunk prefix of compress_chunks(format, L) (common.h).
 // A rejected unit is an empty unit without room and has no chunks, so that no chunk-gridded kernel visits it.
 __global__ __launch_bounds__(DV_THREADS) void dv_ctables_kernel(int format, uint32_t n, u64 in_max, u64 unit_max,
                                                                const u64* __restrict__ in_off, const u64* __restrict__ in_len,
@@ -86,7 +79,7 @@ __global__ __launch_bounds__(DV_THREADS) void dv_ctables_kernel(int format, uint
 {
 	__shared__ u64 s_w[1][DV_WAVES];
 	const uint32_t tid = threadIdx.x;
-	const u64 k = format == 2 ? 4096u : 65536u;                      // LZNT1: 4 KiB chunks; Xpress, Xpress+Huffman: 64 KiB
+	const u64 k = compress_chunk_bytes(format);                      // (read once: the choice stays in two SGPRs over the loop)
 	u64 run[1] = {0}, cnt[1] = {0};
 	if (tid == 0) { chunk_prefix[0] = 0; }
 	for (uint32_t base = 0; base < n; base += DV_THREADS) {
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(DV_THREADS) void dv_ctables_kernel(int format, uint
 		dv_block_scan<1>(r, run, s_w);                                   // running total of in_len up to and including unit i
 		const bool rej = live && (len > unit_max || r[0] > in_max);
 		const u64 L = rej ? 0 : len;
-		u64 c[1] = {(L + k - 1u) / k};                                   // (L <= 0xFFFFF000: no overflow)
+		u64 c[1] = {(L + k - 1u) / k};                                   // compress_chunks(format, L) (L <= 0xFFFFF000: no overflow)
 		if (live) {
 			san[i] = rej ? 0 : in_off[i]; san[n + i] = L; san[2u * (size_t)n + i] = rej ? 0 : out_off[i]; san[3u * (size_t)n + i] = rej ? 0 : out_cap[i];
 			reject[i] = rej ? 1u : 0u;
@@ -125,7 +118,7 @@ __global__ __launch_bounds__(256) void dv_size_finish_kernel(const uint32_t* __r
 }
 
 // FORMAT 0: src holds the capacities; 2 / 3 / 4 (LZNT1 / Xpress / Xpress+Huffman): src holds input lengths, and the capacity of each is the
-// format's largest output (api.hip mscomp_amd_plan_layout), written to cap_out when that is not null
+// format's largest output (common.h layout_cap, as mscomp_amd_plan_layout), written to cap_out when that is not null
 template <int FORMAT>
 __global__ __launch_bounds__(DV_THREADS) void dv_layout_kernel(const u64* __restrict__ src, uint32_t n, u64 align, u64* __restrict__ off, u64* __restrict__ cap_out)
 {
@@ -136,9 +129,7 @@ __global__ __launch_bounds__(DV_THREADS) void dv_layout_kernel(const u64* __rest
 	for (uint32_t base = 0; base < n; base += DV_THREADS) {
 		const uint32_t i = base + tid;
 		const u64 s = i < n ? src[i] : 0;
-		const u64 c = FORMAT == 2 ? s + 3u + 2u * ((s + 4095u) / 4096u) + 2u     // + the uncounted End_of_buffer
-		            : FORMAT == 3 ? s + 4u + 4u * (s / 32u)
-		            : FORMAT == 4 ? s + 34u + 258u + 258u * (s / 65536u) : s;
+		const u64 c = layout_cap(FORMAT, s);
 		if (FORMAT != 0 && cap_out && i < n) { cap_out[i] = c; }
 		const u64 q = c / align + (c % align ? 1u : 0u);
 		u64 v[1] = { q > ~(u64)0 / align ? ~(u64)0 : q * align };

@@ -76,7 +76,7 @@ void launch_xh_encode(hipStream_t st, const uint8_t* d_in, const BatchTables& bt
 // segments of the batch). cin: header offsets, LZD_SLOTS per segment (u32); segL / segE / segcnt / segstop / segoff per speculated
 // chain; selcnt / seloff per segment (the true chain); flat: u64 exclusive scan of selcnt (n_chunks + 1) = number of the first chunk of a segment; csize: decoded size or 0x8000 per
 // chunk number (u16); stop / irregular (+1 global flag) per unit.
-#define LZD_SEG   49152u
+// (LZD_SEG: common.h, beside decode_chunks)
 #define LZD_HEAD  12288u
 #define LZD_SLOTS (LZD_SEG / 3u + 2u)
 #define LZD_K     8u         // speculated chains kept per segment
@@ -117,7 +117,7 @@ void launch_xpress_size(hipStream_t st, const uint8_t* d_in, const BatchTables& 
 // Xpress+Huffman, in phases: 0 mark candidate chunk starts, 1 walk every candidate as one chunk, 2 chain check per buffer, 3 tokens of the
 // accepted chunks, 4 serial walk of the buffers the speculation could not do, 5 tokens -> bytes. tok_prefix[u] = first token slot of unit u,
 // cand_prefix[u] = first candidate slot (n_slots in all); per candidate slot: offset, next offset, reach, state, bytes, tokens, token offset.
-#define XHC_TILE_BYTES 16384u
+// (XHC_TILE_BYTES: common.h, beside decode_chunks)
 enum { XHC_SERIAL = 1, XHC_SPEC = 2 };
 struct XhcBufs { uint32_t* cand_cnt; uint32_t* mode; uint32_t* cand_pos; uint32_t* res_end; uint32_t* res_reach; uint32_t* res_state;
                  u64* res_prod; u64* res_ntok; u64* tok_off;
@@ -158,7 +158,7 @@ void launch_lz_copy_global(hipStream_t st, const LzgTables& g, const BatchTables
 // One block walks the units in tiles of 1024: per unit, the checks of mscomp_amd_plan_execute_dev (in_len <= 0xFFFFF000, running totals of
 // in_len / out_cap within the bounds), the unit's table row (in_off | in_len | out_off | out_cap; all zero for a rejected unit) in san
 // (4 x n), reject[u], and the prefix arrays of the chunk counts (u32, n + 1 entries), the token slots and the candidate slots (u64, n + 1
-// each, the candidate prefix right behind the token prefix) with the formulas plan_create_impl uses on the host.
+// each, the candidate prefix right behind the token prefix) with the counts plan_create_impl uses on the host (common.h).
 void launch_dev_tables(hipStream_t st, int format, uint32_t n, u64 in_total_max, u64 out_total_max, const u64* in_off, const u64* in_len,
                        const u64* out_off, const u64* out_cap, u64* san, uint32_t* chunk_prefix, u64* tok_prefix, uint32_t* reject);
 // size plans (mscomp_amd_plan_create_size_dev): the same pass with out_off = 0 and out_cap = limit for every unit (limit null: 2^64 - 1) and
@@ -179,7 +179,7 @@ void launch_dev_reject(hipStream_t st, const uint32_t* reject, uint32_t n, u64* 
 // off[0..n] = exclusive running sum of cap[i] rounded up to align (saturating at 2^64 - 1)
 void launch_layout_dev(hipStream_t st, const u64* cap, uint32_t n, u64 align, u64* off);
 // compress plans (mscomp_amd_plan_create_compress_dev): per unit the checks in_len <= in_unit_max and running total of in_len <= in_total_max,
-// the sanitised row in san (as above), reject[u], and chunk_prefix (u32, n + 1) with chunks_of(format, false, L): 4 KiB chunks for LZNT1,
+// the sanitised row in san (as above), reject[u], and chunk_prefix (u32, n + 1) with compress_chunks(format, L): 4 KiB chunks for LZNT1,
 // 64 KiB for the Xpress formats, none for an empty or a rejected unit
 void launch_dev_ctables(hipStream_t st, int format, uint32_t n, u64 in_total_max, u64 in_unit_max, const u64* in_off, const u64* in_len,
                         const u64* out_off, const u64* out_cap, u64* san, uint32_t* chunk_prefix, uint32_t* reject);
