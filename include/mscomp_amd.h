@@ -239,7 +239,8 @@ MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* ctx, MSCompForma
  *   Creation:     the argument checks of mscomp_amd_plan_create_decompress (MSCOMP_ARG_ERROR for a null ctx or plan pointer or a bad format);
  *                 MSCOMP_MEM_ERROR when the scratch for the bounds cannot be reserved. The scratch is reserved for the bounds, once.
  * Dev plans decode without the optional paths that need tables chosen on the host (DESIGN_DECODERS.md): below 512 KiB of Xpress input and
- * 1 MiB of capacity per unit they run the same kernels as a host plan; larger units decode to the same bytes, more slowly. */
+ * 1 MiB of capacity per unit they run the same kernels as a host plan; larger units decode to the same bytes, more slowly
+ * (mscomp_amd_plan_create_decompress_dev_ex below builds those tables on the device). */
 MSCompStatus mscomp_amd_plan_create_decompress_dev(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units,
                                                    uint64_t in_total_max, uint64_t out_total_max, mscomp_amd_plan** plan);
 MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* plan, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -274,12 +275,40 @@ MSCompStatus mscomp_amd_layout_dev(mscomp_amd_ctx* ctx, size_t n_units, const ui
  *                 n_units above 0x7FFFFFF0); MSCOMP_MEM_ERROR when the bounds exceed what the scratch can address or the scratch cannot be
  *                 reserved. The scratch is reserved for (n_units, in_total_max), once, and never grows.
  * As decompress dev plans, size dev plans take only the paths that need no tables chosen on the host (DESIGN_DECODERS.md): an Xpress stream of
- * 512 KiB or more is sized by the one-wave walk instead of by segments -- the same answers, more slowly. */
+ * 512 KiB or more is sized by the one-wave walk instead of by segments -- the same answers, more slowly
+ * (mscomp_amd_plan_create_size_dev_ex below builds the segment tables on the device). */
 MSCompStatus mscomp_amd_plan_create_size_dev(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units,
                                              uint64_t in_total_max, mscomp_amd_plan** plan);
 MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* plan, const uint8_t* d_in,
                                               const uint64_t* d_in_off, const uint64_t* d_in_len, const uint64_t* d_limit,
                                               uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status);
+
+/* Dev plans for batches with large units. The two creators above leave the optional paths of a host plan out, because a host plan chooses
+ * them from its host tables. With MSCOMP_AMD_DEV_LARGE_UNITS the plan builds those paths' tables on the device too, at every execution, by
+ * the arithmetic a host plan uses (csrc/common.h), and takes the host plan's decisions for the same per-unit values:
+ *   Xpress, decompress and size plans:  streams of 512 KiB input or more are walked by segments;
+ *   both Xpress formats, decompress:    units with room for 1 MiB or more get their bytes from all CUs -- for no unit of the batch when one
+ *                                       has room for 0xFFFFFF00 bytes or more, or when the stage does not pay for the batch's capacities;
+ *   Xpress+Huffman, decompress:         units with room for more than 64 KiB keep their candidates' tokens in scratch (no second walk).
+ * flags = 0 is exactly the creator without _ex; any other bit is MSCOMP_ARG_ERROR; LZNT1 accepts the flag and is unchanged by it. The
+ * other creation checks and statuses, execution (mscomp_amd_plan_execute_dev / _execute_size_dev, same arguments), per-unit results,
+ * rejects and plan kinds are those of the creators above: asynchronous, nothing allocated, nothing read back, kernels only, a launch
+ * sequence fixed by the creation bounds. A rejected unit is an empty unit and takes no path.
+ * The flag is opt-in for what it costs whether or not a batch holds a large unit:
+ *   scratch    the all-CU stage reserves 4 bytes per byte of out_total_max (+ 64 per possible unit) when the plan is created, the token
+ *              scratch 256 KiB per possible candidate of the units it could take. Both are optional: above MSCOMP_AMD_LZG_MAX_MB /
+ *              MSCOMP_AMD_XHC_SCR_MAX_MB or half of the free device memory, or not to be had, the path is off for the life of the plan --
+ *              creation succeeds, and the block-per-unit kernel / the second walk take the units, as in a host plan;
+ *   launches   the stages' launches are in the sequence every time (Xpress: the segment walk with its 8 redo rounds; both: the path pass,
+ *              the directory, the expansion and 33 pointer passes of the all-CU stage), gridded by the bounds; their blocks return at once
+ *              when the batch has no unit for them. Measured on 3 239 units of 64 KiB (1 x MI355X, DESIGN_DECODERS.md, "Plans with device
+ *              tables"): + 8.5 % for Xpress (0.24 ms), + 2.2 % for Xpress+Huffman against the plan without the flag; one 27 MB Xpress
+ *              stream: 7.07 ms with the flag, 659 ms without, 6.98 ms for a host plan. */
+#define MSCOMP_AMD_DEV_LARGE_UNITS 1u
+MSCompStatus mscomp_amd_plan_create_decompress_dev_ex(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units,
+                                                      uint64_t in_total_max, uint64_t out_total_max, uint32_t flags, mscomp_amd_plan** plan);
+MSCompStatus mscomp_amd_plan_create_size_dev_ex(mscomp_amd_ctx* ctx, MSCompFormat format, size_t n_units,
+                                                uint64_t in_total_max, uint32_t flags, mscomp_amd_plan** plan);
 
 /* Compress plans with device tables: the compressing half of the same pipeline. Created once from bounds and executed with
  * mscomp_amd_plan_execute_dev (the same nine arguments) on unit tables that GPU work has written -- the d_out_len of a decompress dev plan, say,
@@ -377,7 +406,8 @@ MSCompStatus mscomp_amd_ctx_set_lznt1_sa_dict(mscomp_amd_ctx* ctx, int on);
  * Xpress+Huffman uses), 1 = one wave per stream taking a token per step and moving the bytes itself (round 1's kernel). Process-wide. */
 void         mscomp_amd_debug_set_xpress_decoder(int mode);
 /* Test hook: after a decompression whose large units (capacity >= 1 MiB) got their bytes from csrc/lzglobal.hip: out[0..32] = words still
- * pointing after each pointer pass (`words` = sum over those units of capacity + 64). 0 = read. */
+ * pointing after each pointer pass (`words` = sum over those units of capacity + 64; not used when a dev plan with
+ * MSCOMP_AMD_DEV_LARGE_UNITS ran last: the library knows where that plan keeps them). 0 = read. */
 int          mscomp_amd_debug_lzg_open(mscomp_amd_ctx* ctx, uint64_t words, uint32_t* out);
 /* Test hook: how the Xpress match finder runs. 1 = default: batches whose units are at most 64 KiB run Find only where a greedy parse can
  * start a token (csrc/xpress_lazy.hip); 2 = Find for every position everywhere (xp_find_kernel, what longer streams and Xpress+Huffman
@@ -398,6 +428,11 @@ uint32_t     mscomp_amd_debug_lzd_walked(mscomp_amd_ctx* ctx);
  * 512 KiB input, in unit order, 2 = walked by segments, 0 = the one-wave walk; none when the plan does not take the segment path. LZNT1:
  * none. Writes min(count, cap) words to out and returns the count, -1 on error. */
 int          mscomp_amd_debug_decode_modes(mscomp_amd_ctx* ctx, uint32_t* out, size_t cap);
+/* Test hook: what the plan's last execution put on the optional decoding paths (synchronizes the stream): out[0] = units walked by
+ * segments, out[1] = units on the all-CU byte stage, out[2] = candidate slots with token scratch. A host plan: the counts chosen when it
+ * was created; a dev plan with MSCOMP_AMD_DEV_LARGE_UNITS: read back from the tables its last execution built (0 before the first); any
+ * other dev plan: 0. Returns 0, -1 on error. Works with or without MSCOMP_AMD_TEST_HOOKS (it switches nothing). */
+int          mscomp_amd_debug_plan_paths(mscomp_amd_plan* plan, uint32_t out[3]);
 /* Hardware self-check: the LZNT1 bucket sort and the Xpress chain links rely on gfx950 serving the returning
  * same-address LDS atomics of one wave instruction in lane order. Returns the number of lanes (over blocks x rounds x 64
  * lanes x {add, exchange}, keys drawn from nkeys <= 2048 values) that were served out of order: 0 on gfx950;

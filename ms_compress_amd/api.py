@@ -38,7 +38,9 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_plan_create_decompress_dev", "mscomp_amd_plan_execute_dev", "mscomp_amd_layout_dev",
     "mscomp_amd_plan_create_compress_dev", "mscomp_amd_plan_layout_dev",
     "mscomp_amd_plan_create_size_dev", "mscomp_amd_plan_execute_size_dev", "mscomp_amd_compact_dev",
+    "mscomp_amd_plan_create_decompress_dev_ex", "mscomp_amd_plan_create_size_dev_ex", "mscomp_amd_debug_plan_paths",
 ]
+MSCOMP_AMD_DEV_LARGE_UNITS = 1
 
 
 class MSCompError(RuntimeError):
@@ -118,6 +120,12 @@ def load_library():
     lib.mscomp_amd_plan_layout_dev.restype = C.c_int
     lib.mscomp_amd_plan_create_size_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.POINTER(C.c_void_p)]
     lib.mscomp_amd_plan_create_size_dev.restype = C.c_int
+    lib.mscomp_amd_plan_create_decompress_dev_ex.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_plan_create_decompress_dev_ex.restype = C.c_int
+    lib.mscomp_amd_plan_create_size_dev_ex.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_plan_create_size_dev_ex.restype = C.c_int
+    lib.mscomp_amd_debug_plan_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.mscomp_amd_debug_plan_paths.restype = C.c_int
     lib.mscomp_amd_plan_execute_size_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 7
     lib.mscomp_amd_plan_execute_size_dev.restype = C.c_int
     lib.mscomp_amd_compact_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -337,13 +345,20 @@ class SizePlan:
 
 class DevPlan:
     """A decompress plan with device tables (mscomp_amd_plan_create_decompress_dev): made once for n_units units whose in_len sum to at most
-    in_total_max and whose out_cap sum to at most out_total_max, then executed with unit tables that live on the device."""
+    in_total_max and whose out_cap sum to at most out_total_max, then executed with unit tables that live on the device.
+    ``large_units`` (MSCOMP_AMD_DEV_LARGE_UNITS): the plan also builds the tables of a host plan's paths for large units on the device
+    (segment walk, all-CU byte stage, candidate token scratch), at the price of their scratch and launches in every execution."""
 
-    def __init__(self, ctx, fmt, n_units, in_total_max, out_total_max):
+    def __init__(self, ctx, fmt, n_units, in_total_max, out_total_max, large_units=False):
         self.ctx, self.fmt, self.n_units = ctx, int(fmt), int(n_units)
         self.in_total_max, self.out_total_max = int(in_total_max), int(out_total_max)
+        self.large_units = bool(large_units)
         self._h = C.c_void_p()
-        st = ctx.lib.mscomp_amd_plan_create_decompress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.out_total_max, C.byref(self._h))
+        if self.large_units:
+            st = ctx.lib.mscomp_amd_plan_create_decompress_dev_ex(ctx._h, self.fmt, self.n_units, self.in_total_max, self.out_total_max,
+                                                                  MSCOMP_AMD_DEV_LARGE_UNITS, C.byref(self._h))
+        else:
+            st = ctx.lib.mscomp_amd_plan_create_decompress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.out_total_max, C.byref(self._h))
         if st != MSCOMP_OK:
             raise MSCompError(st, "mscomp_amd_plan_create_decompress_dev")
 
@@ -382,13 +397,18 @@ class CompressDevPlan(DevPlan):
 
 class SizeDevPlan(DevPlan):
     """A size plan with device tables (mscomp_amd_plan_create_size_dev): made once for n_units units whose in_len sum to at most in_total_max,
-    then executed with unit tables (offsets, lengths, optional limits) that live on the device."""
+    then executed with unit tables (offsets, lengths, optional limits) that live on the device. ``large_units``: as DevPlan's (Xpress
+    streams of 512 KiB or more are sized by segments)."""
 
-    def __init__(self, ctx, fmt, n_units, in_total_max):
+    def __init__(self, ctx, fmt, n_units, in_total_max, large_units=False):
         self.ctx, self.fmt, self.n_units = ctx, int(fmt), int(n_units)
         self.in_total_max = int(in_total_max)
+        self.large_units = bool(large_units)
         self._h = C.c_void_p()
-        st = ctx.lib.mscomp_amd_plan_create_size_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, C.byref(self._h))
+        if self.large_units:
+            st = ctx.lib.mscomp_amd_plan_create_size_dev_ex(ctx._h, self.fmt, self.n_units, self.in_total_max, MSCOMP_AMD_DEV_LARGE_UNITS, C.byref(self._h))
+        else:
+            st = ctx.lib.mscomp_amd_plan_create_size_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, C.byref(self._h))
         if st != MSCOMP_OK:
             raise MSCompError(st, "mscomp_amd_plan_create_size_dev")
 
@@ -399,6 +419,15 @@ class SizeDevPlan(DevPlan):
         st = self.ctx.lib.mscomp_amd_plan_execute_size_dev(self._h, *ptrs)
         if st != MSCOMP_OK:
             raise MSCompError(st, "mscomp_amd_plan_execute_size_dev")
+
+
+def plan_paths(plan):
+    """mscomp_amd_debug_plan_paths (test hook; synchronizes the stream): what the last execution of a decompress or size plan of any kind put
+    on the optional paths -- (units walked by segments, units on the all-CU byte stage, candidate slots with token scratch)."""
+    out = (C.c_uint32 * 3)()
+    if plan.ctx.lib.mscomp_amd_debug_plan_paths(plan._h, out) != 0:
+        raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_debug_plan_paths")
+    return (int(out[0]), int(out[1]), int(out[2]))
 
 
 def compact_dev(ctx, d_src, d_src_off, d_len, align=1, d_packed=None, d_packed_off=None, packed_cap=None):

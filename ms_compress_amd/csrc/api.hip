@@ -76,6 +76,8 @@ struct mscomp_amd_ctx {
 	uint64_t epoch = 1;                                // bumped when one of the buffers above moves (captured graphs are stale then)
 	int lznt1_sa = -1;                                 // LZNT1 dictionary flavour of the plans this context creates: -1 = the process default at plan creation, 0 / 1 = set for this context
 	const uint32_t* dbg_mode = nullptr; uint32_t dbg_mode_n = 0;   // where the last decompress / size execution left its per-unit path verdicts (mscomp_amd_debug_decode_modes)
+	const uint32_t* dbg_lzg_open = nullptr;            // the open-word counters of the last execution when a dev plan with large units ran it (they lie behind the words of its BOUND)
+	const uint32_t* dbg_mode_cnt = nullptr;            // ... and, for a dev plan with large units, where its path pass left their number (device memory; dbg_mode_n is then the bound)
 	bool profiling = false;
 	std::vector<ProfRec> recs;
 	std::vector<hipEvent_t> free_events;
@@ -94,6 +96,9 @@ struct mscomp_amd_plan {
 	bool decompress = false;
 	bool sizing = false;                               // a decompressed-size plan (mscomp_amd_plan_create_size): out_cap holds the limits, nothing is decoded
 	bool dev = false;                                  // a plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev / _compress_dev; with sizing: _size_dev)
+	bool large = false;                                // ... with MSCOMP_AMD_DEV_LARGE_UNITS: the tables of the optional paths are built there too (xhc_scr, lzg_*, xps_big / xps_seg hold the bounds
+	                                                   // they were reserved for, 0 = the path is off for the plan; the counts of an execution are in xps_cnt / lzg_cnt, device memory)
+	uint32_t* xps_cnt = nullptr; uint32_t* lzg_cnt = nullptr;   // (behind the prefix arrays of xps_tab / lzg_tab)
 	uint64_t in_total_max = 0, out_total_max = 0;      // ... and the bounds its scratch was reserved for
 	uint32_t n_units = 0, n_chunks = 0;
 	uint64_t total_in = 0, max_unit = 0;               // (max_unit of a compress dev plan: the largest unit it takes)
@@ -120,6 +125,7 @@ struct mscomp_amd_plan {
 	const void* g_args[9] = {};                        // (a host plan's four pointers, a dev plan's eight, a size dev plan's seven)
 	uint64_t g_epoch = 0, g_mode = 0;
 	uint32_t executions = 0;
+	bool ran = false;                                  // executed at least once (mscomp_amd_debug_plan_paths: a dev plan's counts are those of its last execution)
 	// (on the plan's device, its stream idle. mscomp_amd_plan_destroy hands `tables` to the context's pool first)
 	~mscomp_amd_plan() { if (gexec) { (void)hipGraphExecDestroy(gexec); } tables.release(); tokpre.release(); lzg_tab.release(); xps_tab.release(); }
 };
@@ -317,6 +323,15 @@ static bool reserve_xhc(mscomp_amd_ctx* c, size_t n_units, uint64_t cands)   // 
 	return c->dz_xhc.reserve((n_units + 1) * 8 + (size_t)cands * (4 * 4 + 3 * 8) + 64);
 }
 
+// ---- the optional paths: their environment settings (read once), for host plans and for the bounds of dev plans with large units ----
+// segment size / warm-up of the segment walk (MSCOMP_AMD_XPS_SEG_KB / _WARM_KB override the defaults, for measurements)
+static uint32_t xps_seg_env() { static const uint32_t b = [] { const char* e = getenv("MSCOMP_AMD_XPS_SEG_KB"); const long v = e ? atol(e) : 0; return (uint32_t)(v >= 4 && v <= 65536 ? v << 10 : XPS_SEG); }(); return b; }
+static uint32_t xps_warm_env() { static const uint32_t b = [] { const char* e = getenv("MSCOMP_AMD_XPS_WARM_KB"); const long v = e ? atol(e) : 0; const uint32_t w = (uint32_t)(v >= 1 && v <= 65536 ? v << 10 : XPS_WARM); return w < xps_seg_env() ? w : xps_seg_env(); }(); return b; }
+// the all-CU byte stage: MSCOMP_AMD_LZG_MAX_MB, default 64 GiB of the 288; 0 switches the path off
+static uint64_t lzg_budget_env() { static const uint64_t b = [] { const char* e = getenv("MSCOMP_AMD_LZG_MAX_MB"); const long long v = e ? atoll(e) : 65536; return (uint64_t)(v < 0 ? 0 : v) << 20; }(); return b; }
+// the candidate token scratch: MSCOMP_AMD_XHC_SCR_MAX_MB, default 32 GiB; 0 = always walk twice
+static uint64_t xhc_scr_env() { static const uint64_t b = [] { const char* e = getenv("MSCOMP_AMD_XHC_SCR_MAX_MB"); const long long v = e ? atoll(e) : 32768; return (uint64_t)(v < 0 ? 0 : v) << 20; }(); return b; }
+
 static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, bool decompress, size_t n_units,
                                      const uint64_t* in_off, const uint64_t* in_len,
                                      const uint64_t* out_off, const uint64_t* out_cap, mscomp_amd_plan** out, bool sizing = false)
@@ -393,7 +408,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 				const uint64_t most = candidate_slots(in_len[i], out_cap[i]);
 				tp[row + i] = cands; tp[2 * row + i] = scr;
 				cands += most;
-				if (out_cap[i] > 65536u && !sizing) { scr += most; }        // a buffer of several chunks: its candidates keep their tokens (no second walk)
+				if (!sizing) { scr += scratch_slots(in_len[i], out_cap[i]); }   // a buffer of several chunks: its candidates keep their tokens (no second walk)
 			}
 		}
 		if (!sizing) { tp[n_units] = slots; }
@@ -404,8 +419,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 		if (xh) {
 			// ... if that scratch is affordable: at most MSCOMP_AMD_XHC_SCR_MAX_MB (default 32 GiB; 0 = always walk twice) and at most half of
 			// what the device has free right now; a reservation that fails anyway switches the path off (the second walk needs no scratch)
-			static const uint64_t scr_env = [] { const char* e = getenv("MSCOMP_AMD_XHC_SCR_MAX_MB"); const long long v = e ? atoll(e) : 32768; return (uint64_t)(v < 0 ? 0 : v) << 20; }();
-			const uint64_t need = scr * XHC_SCR * 4 + 64, scr_budget = optional_scratch_budget(scr_env, c->dz_scr.cap);
+			const uint64_t need = scr * XHC_SCR * 4 + 64, scr_budget = optional_scratch_budget(xhc_scr_env(), c->dz_scr.cap);
 			if (scr && (need > scr_budget || !okd || !c->dz_scr.reserve(need))) { for (size_t i = 0; i <= n_units; ++i) { tp[2 * row + i] = 0; } scr = 0; }
 			p->xhc_scr = scr;
 		}
@@ -416,23 +430,16 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	if (okd && !sizing && (format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF)) {
 		// units with room for LZG_MIN_CAP bytes or more get their bytes from all CUs (lzglobal.hip): 4 bytes of scratch per byte of capacity;
 		// when that is more than the budget (MSCOMP_AMD_LZG_MAX_MB, default 64 GiB of the 288; 0 switches the path off) the block-per-unit kernel takes them
-		static const uint64_t budget_env = [] { const char* e = getenv("MSCOMP_AMD_LZG_MAX_MB"); const long long v = e ? atoll(e) : 65536; return (uint64_t)(v < 0 ? 0 : v) << 20; }();
-		const uint64_t budget = optional_scratch_budget(budget_env, c->lzg_words.cap);   // ... and never more than half of the free HBM: the block kernel needs none of it
+		const uint64_t budget = optional_scratch_budget(lzg_budget_env(), c->lzg_words.cap);   // ... and never more than half of the free HBM: the block kernel needs none of it
 		std::vector<uint32_t> big;
 		uint64_t words = 0;
 		bool too_large = false;                                       // (32-bit word indices: a unit with room for 4 GiB keeps the whole plan on the block kernel, which every such unit then takes)
-		for (size_t i = 0; i < n_units; ++i) { if (out_cap[i] >= 0xFFFFFF00ull) { too_large = true; } else if (out_cap[i] >= LZG_MIN_CAP) { big.push_back((uint32_t)i); words += out_cap[i] + 64; } }
+		for (size_t i = 0; i < n_units; ++i) { if (lzg_too_large(out_cap[i])) { too_large = true; } else if (lzg_takes(out_cap[i])) { big.push_back((uint32_t)i); words += lzg_words(out_cap[i]); } }
 		if (too_large) { big.clear(); }
-		// ... and when it pays: the all-CU stage costs about 22 ms per GB of output whatever the units are (74 ms for 192 files, 3.39 GB), the
-		// block-per-unit kernel about 1 ms per MB of the LARGEST unit as long as there are no more large units than CUs (51 ms for the same 192
-		// files, whose largest is 51 MB; 60 ms for 12 of them, where the all-CU stage takes 5 ms)
-		bool pays = false;
-		{
-			uint64_t tot = 0, mx = 0;
-			for (uint32_t i : big) { tot += out_cap[i]; mx = out_cap[i] > mx ? out_cap[i] : mx; }
-			const double mb = 1.0 / (1 << 20), c_all = 0.022 * (double)tot * mb, per_cu = (double)tot * mb / 256.0, c_blk = 1.0 * ((double)mx * mb > per_cu ? (double)mx * mb : per_cu);
-			pays = c_all < c_blk;
-		}
+		// ... and when it pays (common.h lzg_pays)
+		uint64_t tot = 0, mx = 0;
+		for (uint32_t i : big) { tot += out_cap[i]; mx = out_cap[i] > mx ? out_cap[i] : mx; }
+		const bool pays = lzg_pays(tot, mx);
 		if (!big.empty() && pays && words * 4 <= budget) {
 			const size_t nb = big.size(), upad = (nb + 1) / 2;              // the unit list in whole u64 slots
 			std::vector<uint64_t> tab(upad + 3 * (nb + 1));
@@ -442,7 +449,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 			for (size_t k = 0; k < nb; ++k) {
 				const size_t i = big[k];
 				tbp[k] = tb; tlp[k] = tl; wdp[k] = wd;
-				tb += (token_slots(format, in_len[i], out_cap[i]) + 8191) / 8192; tl += (out_cap[i] + (1u << LZG_TILE_SHIFT) - 1) >> LZG_TILE_SHIFT; wd += out_cap[i] + 64;
+				tb += lzg_token_blocks(format, in_len[i], out_cap[i]); tl += lzg_tiles(out_cap[i]); wd += lzg_words(out_cap[i]);
 			}
 			tbp[nb] = tb; tlp[nb] = tl; wdp[nb] = wd;
 			if (tb < 0x7FFFFFF0ull && tl < 0x7FFFFFF0ull) {
@@ -456,17 +463,15 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	}
 	if (okd && format == MSCOMP_XPRESS) {
 		std::vector<uint32_t> big;
-		for (size_t i = 0; i < n_units; ++i) { if (in_len[i] >= XPS_MIN_IN) { big.push_back((uint32_t)i); } }
+		for (size_t i = 0; i < n_units; ++i) { if (xps_takes(in_len[i])) { big.push_back((uint32_t)i); } }
 		if (!big.empty()) {
 			const size_t nb = big.size(), upad = (nb + 1) / 2;
 			std::vector<uint64_t> tab(upad + nb + 1);
 			memcpy(tab.data(), big.data(), nb * 4);
-			// segment size / warm-up (MSCOMP_AMD_XPS_SEG_KB / _WARM_KB override the defaults, for measurements)
-			static const uint32_t seg_b = [] { const char* e = getenv("MSCOMP_AMD_XPS_SEG_KB"); const long v = e ? atol(e) : 0; return (uint32_t)(v >= 4 && v <= 65536 ? v << 10 : XPS_SEG); }();
-			static const uint32_t warm_b = [] { const char* e = getenv("MSCOMP_AMD_XPS_WARM_KB"); const long v = e ? atol(e) : 0; const uint32_t w = (uint32_t)(v >= 1 && v <= 65536 ? v << 10 : XPS_WARM); return w < seg_b ? w : seg_b; }();
+			const uint32_t seg_b = xps_seg_env(), warm_b = xps_warm_env();
 			p->xps_seg_bytes = seg_b; p->xps_warm_bytes = warm_b;
 			uint64_t sg = 0;
-			for (size_t k = 0; k < nb; ++k) { tab[upad + k] = sg; sg += (in_len[big[k]] + seg_b - 1) / seg_b; }
+			for (size_t k = 0; k < nb; ++k) { tab[upad + k] = sg; sg += xps_segments(in_len[big[k]], seg_b); }
 			tab[upad + nb] = sg;
 			if (sg < 0x7FFFFFF0ull) {
 				okd = p->xps_tab.reserve(tab.size() * 8) && c->xps_buf.reserve(sg * XPS_SEG_BYTES + nb * 4 + n_units * 4 + 64);
@@ -513,7 +518,7 @@ void mscomp_amd_plan_destroy(mscomp_amd_plan* p)
 static LzgTables lzg_tables(const mscomp_amd_plan* p, mscomp_amd_ctx* c)
 {
 	LzgTables g = {};
-	g.n_big = p->lzg_big; g.n_tb = p->lzg_tb; g.n_tiles = p->lzg_tiles;
+	g.n_big = p->lzg_big; g.n_tb = p->lzg_tb; g.n_tiles = p->lzg_tiles; g.cnt = p->lzg_cnt;
 	if (!g.n_big) { return g; }
 	const size_t nb = g.n_big, upad = (nb + 1) / 2;
 	const uint64_t* t = static_cast<const uint64_t*>(p->lzg_tab.p);
@@ -583,7 +588,7 @@ static XpsTables xps_tables(const mscomp_amd_plan* p, mscomp_amd_ctx* c)
 	if (!p->xps_big) { return x; }
 	const size_t nb = p->xps_big, upad = (nb + 1) / 2;
 	const uint64_t* t = static_cast<const uint64_t*>(p->xps_tab.p);
-	x.unit = reinterpret_cast<const uint32_t*>(t); x.seg_prefix = t + upad; x.n_big = p->xps_big; x.n_seg = p->xps_seg; x.seg_bytes = p->xps_seg_bytes; x.warm_bytes = p->xps_warm_bytes;
+	x.unit = reinterpret_cast<const uint32_t*>(t); x.seg_prefix = t + upad; x.n_big = p->xps_big; x.n_seg = p->xps_seg; x.seg_bytes = p->xps_seg_bytes; x.warm_bytes = p->xps_warm_bytes; x.cnt = p->xps_cnt;
 	x.seg = c->xps_buf.p; x.mode = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->xps_buf.p) + (size_t)p->xps_seg * XPS_SEG_BYTES); x.done = x.mode + nb;
 	return x;
 }
@@ -594,22 +599,25 @@ static XpsTables xps_tables(const mscomp_amd_plan* p, mscomp_amd_ctx* c)
 static void note_modes(mscomp_amd_plan* p)
 {
 	mscomp_amd_ctx* c = p->ctx;
-	c->dbg_mode = nullptr; c->dbg_mode_n = 0;
+	c->dbg_mode = nullptr; c->dbg_mode_n = 0; c->dbg_mode_cnt = nullptr;
+	c->dbg_lzg_open = p->large && p->lzg_big ? static_cast<const uint32_t*>(c->lzg_words.p) + p->lzg_words : nullptr;
 	if (p->format == MSCOMP_XPRESS_HUFF && p->n_units) { c->dbg_mode = xhc_bufs(c, p).mode; c->dbg_mode_n = p->n_units; }
-	if (p->format == MSCOMP_XPRESS && p->xps_big && (p->sizing || g_xpd_mode.load(std::memory_order_relaxed) == 0)) { c->dbg_mode = xps_tables(p, c).mode; c->dbg_mode_n = p->xps_big; }
+	if (p->format == MSCOMP_XPRESS && p->xps_big && (p->sizing || p->large || g_xpd_mode.load(std::memory_order_relaxed) == 0)) { c->dbg_mode = xps_tables(p, c).mode; c->dbg_mode_n = p->xps_big; c->dbg_mode_cnt = p->xps_cnt; }
 }
 
 // ---- the launch sequences: one per direction, for host-table and device-table plans alike ----
 // A dev plan runs the DEV instances of the chunk-gridded kernels (p->dev: bt.n_chunks is its bound, the blocks past chunk_prefix[n_units] return at
 // once); its table pass goes in front of these launches and its reject pass behind them, at the call site (mscomp_amd_plan_execute_dev /
-// _execute_size_dev). The paths that need host-chosen tables are off for it by their zero counts: no xps_* segments, no lzglobal.hip stage, no
-// Xpress+Huffman token scratch.
+// _execute_size_dev). The optional paths -- xps_* segments, the lzglobal.hip stage, Xpress+Huffman token scratch -- are off for a plain dev plan
+// by their zero counts; a dev plan with large units (p->large) has their bounds in the same fields, a path pass behind its table pass that
+// builds their tables, and runs the DEV instances of their kernels, which read the counts of the execution from device memory.
 static void decode_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
 {
 	mscomp_amd_ctx* c = p->ctx;
 	hipStream_t st = c->stream;
 	const u64* tp = p->tok_prefix; uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
-	const u64 gmin = p->lzg_big ? (u64)LZG_MIN_CAP : ~(u64)0;
+	const u64 gmin = p->lzg_big ? (u64)LZG_MIN_CAP : ~(u64)0;           // (host plans; p->large: the byte kernels read lzg_cnt instead)
+	const uint32_t* gcnt = p->large && p->lzg_big ? p->lzg_cnt : nullptr;
 	switch (p->format) {
 	case MSCOMP_LZNT1: {
 		const LzdBufs b = lzd_bufs(c, p);
@@ -623,7 +631,7 @@ static void decode_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_ou
 		return;
 	}
 	case MSCOMP_XPRESS: {                                          // tokens a flag word at a time, then the copy kernels; large streams of host plans by segments first
-		const int mode = p->dev ? 2 : g_xpd_mode.load(std::memory_order_relaxed);   // (the test hook switches host plans only)
+		const int mode = p->dev ? (p->large ? 0 : 2) : g_xpd_mode.load(std::memory_order_relaxed);   // (the test hook switches host plans only; a dev plan walks by segments when it was created for large units)
 		if (mode == 1) { KernelTimer t(c, "xpd_kernel"); launch_xpress_decompress(st, d_in, p->bt, d_out, d_out_len, d_status); return; }
 		static const char* const names[3] = {"xpt_parse_kernel", "lz_copy_kernel", "lz_copy_block_kernel"};
 		const XpsTables x = mode != 2 ? xps_tables(p, c) : XpsTables{};
@@ -633,7 +641,7 @@ static void decode_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_ou
 			for (uint32_t r = 0; r < rounds; ++r) { KernelTimer t2(c, "xps_redo_kernels"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -2, gmin, x); }
 			{ KernelTimer t2(c, "xps_emit_kernel"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -3, gmin, x); }
 		}
-		for (int ph = 0; ph < 3; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, ph, gmin, x); }
+		for (int ph = 0; ph < 3; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, ph, gmin, x, gcnt); }
 		break;
 	}
 	default: {                                                     // MSCOMP_XPRESS_HUFF (without token scratch the accepted chunks are walked twice)
@@ -642,7 +650,7 @@ static void decode_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_ou
 		static const char* const names[6] = { "xhc_mark_kernel", "xhc_parse_kernel", "xhc_chain_kernel", "xhc_parse2_kernel", "xhd_parse_kernel", "lz_copy_kernel" };
 		for (int ph = 0; ph < 6; ++ph) {
 			KernelTimer t(c, names[ph]);
-			launch_xpress_huff_decompress(st, d_in, p->bt, tp, tok, ntok, p->cand_prefix, p->xhc_slots, xb, d_out, d_out_len, d_status, ph, gmin, p->dev);
+			launch_xpress_huff_decompress(st, d_in, p->bt, tp, tok, ntok, p->cand_prefix, p->xhc_slots, xb, d_out, d_out_len, d_status, ph, gmin, p->dev, gcnt);
 		}
 		break;
 	}
@@ -860,29 +868,103 @@ MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* c, MSCompFormat 
 // ---- plans with device tables (include/mscomp_amd.h): created from bounds, tables built on the device by every execution ----
 // The plan holds its bounds and scratch sized for them; p->tables holds what the table pass (devplan.hip) writes each time:
 //   san (4 x n u64: in_off | in_len | out_off | out_cap, zero for a rejected unit) | chunk prefix (u32, n + 1) | decompress and size plans:
-//   token prefix | candidate prefix (u64, n + 1 each) | reject (u32, n)
+//   token prefix | candidate prefix (u64, n + 1 each) | Xpress+Huffman decompress plans with large units: token-scratch prefix (u64, n + 1) |
+//   reject (u32, n)
 // and bt points into it with n_chunks = the bound (the kernels that are gridded by chunks return past chunk_prefix[n_units]). The only place
 // that knows this layout: the launch code reads p->bt, p->tok_prefix, p->cand_prefix and p->reject.
 static bool reserve_dev_tables(mscomp_amd_plan* p)
 {
-	const size_t n = p->n_units, cpw = (n + 2) / 2 + (p->decompress ? 1 : 0), tpw = p->decompress ? 2 * (n + 1) : 0;
+	const bool scr = p->large && p->format == MSCOMP_XPRESS_HUFF && !p->sizing;
+	const size_t n = p->n_units, cpw = (n + 2) / 2 + (p->decompress ? 1 : 0), tpw = p->decompress ? (scr ? 3 : 2) * (n + 1) : 0;
 	if (!p->tables.reserve((4 * n + cpw + tpw + (n + 1) / 2 + 1) * 8)) { return false; }
 	set_bt(p);
 	u64* tp = static_cast<u64*>(p->tables.p) + 4 * n + cpw;
 	if (p->decompress) { p->tok_prefix = tp; p->cand_prefix = tp + (n + 1); }
+	if (scr) { p->scr_prefix = tp + 2 * (n + 1); }
 	p->reject = reinterpret_cast<uint32_t*>(tp + tpw);
 	return true;
+}
+
+// The optional paths of a dev plan with large units (Xpress formats): tables and scratch for the most that a batch within the plan's bounds
+// can put on each path, by the thresholds of common.h. N units, I input bytes, O bytes of capacity, toks token slots at most (create_decode_dev):
+//   segment walk    a stream taken has XPS_MIN_IN bytes or more: min(N, I / XPS_MIN_IN) streams, I / segment + that many segments
+//   all-CU stage    a unit taken has room for LZG_MIN_CAP bytes or more: B = min(N, O / LZG_MIN_CAP) units, O + 64 B words, O / 8192 + B tiles,
+//                   toks / 8192 + B token blocks
+//   token scratch   a unit taken has room for more than 65536 bytes: S = min(N, O / 65537) units, whose candidate slots are bounded as the
+//                   plan's are, with S for N
+// The all-CU stage and the token scratch are optional as in a host plan: over the budget (of the bounds, here) or not to be had, the path is
+// off for the life of the plan (its bound stays 0) and the block-per-unit kernel / the second walk take the units. false: out of memory.
+static bool reserve_dev_paths(mscomp_amd_plan* p, uint64_t N, uint64_t I, uint64_t O, uint64_t toks)
+{
+	mscomp_amd_ctx* c = p->ctx;
+	if (p->format == MSCOMP_XPRESS) {
+		const uint32_t seg_b = xps_seg_env();
+		const uint64_t nb = N < I / XPS_MIN_IN ? N : I / XPS_MIN_IN, sg = I / seg_b + nb;
+		if (nb && sg < 0x7FFFFFF0ull) {
+			const size_t upad = (nb + 1) / 2;
+			if (!p->xps_tab.reserve((upad + nb + 1 + 1) * 8) || !c->xps_buf.reserve(sg * XPS_SEG_BYTES + nb * 4 + N * 4 + 64)) { return false; }
+			p->xps_big = (uint32_t)nb; p->xps_seg = (uint32_t)sg; p->xps_seg_bytes = seg_b; p->xps_warm_bytes = xps_warm_env();
+			p->xps_cnt = reinterpret_cast<uint32_t*>(static_cast<uint64_t*>(p->xps_tab.p) + upad + nb + 1);
+		}
+	}
+	if (p->sizing) { return true; }
+	const uint64_t B = N < O / LZG_MIN_CAP ? N : O / LZG_MIN_CAP;
+	if (B && O < (1ull << 60)) {
+		const uint64_t wd = O + 64 * B, tl = (O >> LZG_TILE_SHIFT) + B, tb = toks / 8192 + B;
+		const uint64_t budget = optional_scratch_budget(lzg_budget_env(), c->lzg_words.cap);
+		if (wd <= budget / 4 && tb < 0x7FFFFFF0ull && tl < 0x7FFFFFF0ull) {
+			const size_t upad = (B + 1) / 2;
+			const bool got = p->lzg_tab.reserve((upad + 3 * (B + 1) + 2) * 8) && c->lzg_bsum.reserve(tb * 8 + 64) && c->lzg_dir.reserve(tl * 8 + 64) && c->lzg_words.reserve(wd * 4 + LZG_PASSES * 4 + tl + 64);
+			if (got) {
+				p->lzg_big = (uint32_t)B; p->lzg_tb = (uint32_t)tb; p->lzg_tiles = (uint32_t)tl; p->lzg_words = wd;
+				p->lzg_cnt = reinterpret_cast<uint32_t*>(static_cast<uint64_t*>(p->lzg_tab.p) + upad + 3 * (B + 1));
+			} else { p->lzg_tab.release(); (void)hipGetLastError(); }
+		}
+	}
+	if (p->format == MSCOMP_XPRESS_HUFF) {
+		const uint64_t S = N < O / 65537u ? N : O / 65537u;
+		const uint64_t by_out = O / 65536u + 2 * S, by_len = I / 260u + S, most = by_out < by_len ? by_out : by_len, scr = most + most / 4 + 2 * S;
+		const uint64_t budget = optional_scratch_budget(xhc_scr_env(), c->dz_scr.cap);
+		if (S && scr <= budget / (XHC_SCR * 4ull) && scr * XHC_SCR * 4 + 64 <= budget) {
+			if (c->dz_scr.reserve(scr * XHC_SCR * 4 + 64)) { p->xhc_scr = scr; } else { (void)hipGetLastError(); }
+		}
+	}
+	return true;
+}
+// what the path pass of such a plan writes (kernels.h DevPaths): the parts whose path the plan has
+static DevPaths dev_paths(const mscomp_amd_plan* p)
+{
+	DevPaths d = {};
+	if (p->xps_big) {
+		uint64_t* t = static_cast<uint64_t*>(p->xps_tab.p);
+		d.xps_unit = reinterpret_cast<uint32_t*>(t); d.xps_seg_prefix = t + (p->xps_big + 1u) / 2u; d.xps_cnt = p->xps_cnt;
+		d.xps_seg_bytes = p->xps_seg_bytes; d.xps_max = p->xps_big; d.xps_seg_max = p->xps_seg;
+	}
+	if (p->lzg_big) {
+		uint64_t* t = static_cast<uint64_t*>(p->lzg_tab.p);
+		const size_t nb = p->lzg_big, upad = (nb + 1) / 2;
+		d.lzg_unit = reinterpret_cast<uint32_t*>(t); d.lzg_tb_prefix = t + upad; d.lzg_tile_prefix = d.lzg_tb_prefix + nb + 1; d.lzg_word_prefix = d.lzg_tile_prefix + nb + 1;
+		d.lzg_cnt = p->lzg_cnt; d.lzg_max = p->lzg_big; d.lzg_tb_max = p->lzg_tb; d.lzg_tile_max = p->lzg_tiles; d.lzg_word_max = p->lzg_words;
+	}
+	if (p->xhc_scr) { d.scr_prefix = p->scr_prefix; }
+	return d;
+}
+static void run_dev_paths(mscomp_amd_plan* p)
+{
+	if (!p->large || !(p->xps_big || p->lzg_big || p->xhc_scr)) { return; }
+	KernelTimer t(p->ctx, "dv_paths_kernel");
+	launch_dev_paths(p->ctx->stream, (int)p->format, p->n_units, static_cast<const u64*>(p->tables.p), dev_paths(p));
 }
 
 // Decompress plans, and size plans: a decompress dev plan whose table pass takes the limits for the capacities (devplan.hip
 // dv_tables_kernel<true>), with no bound on their sum (out_total_max = 2^64 - 1 here: a unit's candidate slots are then bounded by its input,
 // whatever its limit) and whose scratch follows the input alone (the token prefix is written and not used: a size plan stores no tokens).
 static MSCompStatus create_decode_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint64_t out_total_max, bool sizing,
-                                      mscomp_amd_plan** out)
+                                      uint32_t flags, mscomp_amd_plan** out)
 {
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
-	if (!c || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+	if (!c || n_units > 0x7FFFFFF0u || (flags & ~MSCOMP_AMD_DEV_LARGE_UNITS)) { return MSCOMP_ARG_ERROR; }
 	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
 	// the bounds of the per-unit counts summed over the batch (checked before the context is used): every accepted unit has in_len <= 0xFFFFF000 and the accepted ones sum to at
 	// most in_total_max / out_total_max; a rejected unit counts as an empty one (one chunk, 64 token slots, 3 candidates)
@@ -907,24 +989,36 @@ static MSCompStatus create_decode_dev(mscomp_amd_ctx* c, MSCompFormat format, si
 	if (!p) { return MSCOMP_MEM_ERROR; }
 	p->ctx = c; p->format = format; p->decompress = true; p->sizing = sizing; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
 	p->in_total_max = in_total_max; p->out_total_max = sizing ? 0 : out_total_max; p->total_in = in_total_max; p->xhc_slots = (uint32_t)cands;
+	p->large = (flags & MSCOMP_AMD_DEV_LARGE_UNITS) && format != MSCOMP_LZNT1;   // (LZNT1 has no optional paths: its dev plans run the host plan's kernels already)
 	bool ok = reserve_dev_tables(p.get());
 	if (ok && format == MSCOMP_LZNT1) { ok = reserve_scan(c, chunks) && reserve_lzd_scratch(c, N, chunks); }
 	if (ok && format != MSCOMP_LZNT1) { ok = reserve_tokens(c, N, toks, !sizing); }
 	if (ok && format == MSCOMP_XPRESS_HUFF) { ok = reserve_xhc(c, N, cands); }
+	if (ok && p->large) { ok = reserve_dev_paths(p.get(), N, I, O, toks); }
 	if (!ok) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	// the one-time kernel attributes of the instances this plan launches: set now, so that no first launch happens inside a caller's capture
 	if (format == MSCOMP_LZNT1) { prepare_lzd_segments(true); } else if (!sizing) { prepare_lz_copy_block(); }
+	if (p->lzg_big) { prepare_lz_copy_global(true); }
 	*out = p.release();
 	return MSCOMP_OK;
 }
 MSCompStatus mscomp_amd_plan_create_decompress_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint64_t out_total_max,
                                                    mscomp_amd_plan** out)
 {
-	return create_decode_dev(c, format, n_units, in_total_max, out_total_max, false, out);
+	return create_decode_dev(c, format, n_units, in_total_max, out_total_max, false, 0, out);
+}
+MSCompStatus mscomp_amd_plan_create_decompress_dev_ex(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint64_t out_total_max,
+                                                      uint32_t flags, mscomp_amd_plan** out)
+{
+	return create_decode_dev(c, format, n_units, in_total_max, out_total_max, false, flags, out);
+}
+MSCompStatus mscomp_amd_plan_create_size_dev_ex(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, uint32_t flags, mscomp_amd_plan** out)
+{
+	return create_decode_dev(c, format, n_units, in_total_max, ~(uint64_t)0, true, flags, out);
 }
 MSCompStatus mscomp_amd_plan_create_size_dev(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, uint64_t in_total_max, mscomp_amd_plan** out)
 {
-	return create_decode_dev(c, format, n_units, in_total_max, ~(uint64_t)0, true, out);
+	return create_decode_dev(c, format, n_units, in_total_max, ~(uint64_t)0, true, 0, out);
 }
 
 // Compress plans: the compressing half of the same pipeline (tables by dv_ctables_kernel).
@@ -969,12 +1063,14 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	if (p->decompress) { note_modes(p); }
+	p->ran = true;
 	const void* args[9] = { d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status };
 	return plan_run(p, args, [&] {
 		u64* san = static_cast<u64*>(p->tables.p); uint32_t* chunk_prefix = const_cast<uint32_t*>(p->bt.chunk_prefix);
 		const int f = (int)p->format; const uint32_t n = p->n_units;
 		if (p->decompress) {
 			{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_tables(c->stream, f, n, p->in_total_max, p->out_total_max, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, p->tok_prefix, p->reject); }
+			run_dev_paths(p);
 			decode_launch(p, d_in, d_out, d_out_len, d_status);
 		} else {
 			{ KernelTimer t(c, "dv_ctables_kernel"); launch_dev_ctables(c->stream, f, n, p->in_total_max, p->max_unit, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, p->reject); }
@@ -996,10 +1092,12 @@ MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* p, const uint8_t*
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	note_modes(p);
+	p->ran = true;
 	const void* args[9] = { d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status };
 	return plan_run(p, args, [&] {
 		{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_stables(c->stream, (int)p->format, p->n_units, p->in_total_max, d_in_off, d_in_len, d_limit, static_cast<u64*>(p->tables.p),
 		                                                          const_cast<uint32_t*>(p->bt.chunk_prefix), p->tok_prefix, p->reject); }
+		run_dev_paths(p);
 		size_launch(p, d_in, d_out_len, d_need, d_status);
 		// rejected units; and need = length where the kernels above did not write it (LZNT1's finalize did) -- a kernel, where a host size plan
 		// ends with a copy: no memcpy node in a caller's graph
@@ -1157,14 +1255,33 @@ int mscomp_amd_debug_lzg_open(mscomp_amd_ctx* c, uint64_t words, uint32_t* out)
 	if (!c || !out || !c->lzg_words.p) { return -1; }
 	DeviceGuard g(c->device);
 	if (!g.ok || hipStreamSynchronize(c->stream) != hipSuccess) { return -1; }
-	return hipMemcpy(out, static_cast<uint32_t*>(c->lzg_words.p) + words, LZG_PASSES * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+	const uint32_t* open = c->dbg_lzg_open ? c->dbg_lzg_open : static_cast<uint32_t*>(c->lzg_words.p) + words;   // (a dev plan with large units keeps them behind the words of its bound)
+	return hipMemcpy(out, open, LZG_PASSES * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+int mscomp_amd_debug_plan_paths(mscomp_amd_plan* p, uint32_t out[3])
+{	// test hook: units on the segment walk, units on the all-CU stage, candidate slots with token scratch, as of the plan's last execution: the
+	// host's counts for a host plan, the path pass's for a dev plan with large units (read back), none for any other dev plan
+	if (!p || !out) { return -1; }
+	DeviceGuard g(p->ctx->device);
+	if (!g.ok || hipStreamSynchronize(p->ctx->stream) != hipSuccess) { return -1; }
+	out[0] = p->xps_big; out[1] = p->lzg_big; out[2] = (uint32_t)(p->xhc_scr < 0xFFFFFFFFull ? p->xhc_scr : 0xFFFFFFFFull);
+	if (!p->large) { return 0; }
+	out[0] = out[1] = out[2] = 0;
+	if (!p->ran) { return 0; }
+	uint64_t scr = 0;
+	if (p->xps_big && hipMemcpy(&out[0], p->xps_cnt, 4, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (p->lzg_big && hipMemcpy(&out[1], p->lzg_cnt, 4, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (p->xhc_scr && hipMemcpy(&scr, p->scr_prefix + p->n_units, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	out[2] = (uint32_t)(scr < 0xFFFFFFFFull ? scr : 0xFFFFFFFFull);
+	return 0;
 }
 int mscomp_amd_debug_decode_modes(mscomp_amd_ctx* c, uint32_t* out, size_t cap)
 {	// test hook: the per-unit path verdicts of the last decompress or size execution on c (note_modes)
 	if (!c || (cap && !out)) { return -1; }
 	DeviceGuard g(c->device);
 	if (!g.ok || hipStreamSynchronize(c->stream) != hipSuccess) { return -1; }
-	const uint32_t n = c->dbg_mode_n;
+	uint32_t n = c->dbg_mode_n;
+	if (c->dbg_mode_cnt && hipMemcpy(&n, c->dbg_mode_cnt, 4, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }   // (a dev plan with large units: the streams its last execution took)
 	if (n && cap && hipMemcpy(out, c->dbg_mode, (n < cap ? n : cap) * 4, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
 	return (int)n;
 }

@@ -136,6 +136,35 @@ __host__ __device__ inline u64 candidate_slots(u64 len, u64 cap)
 	const u64 by_out = cap / 65536u + 2u, by_len = len / 260u + 1u, most = by_out < by_len ? by_out : by_len;
 	return most + most / 4u + 2u;
 }
+// ---- the optional paths of a decompress / size plan --------------------------------------------------------
+// Which units take them and what they add to the path's tables: api.hip plan_create_impl decides with these on the host, the path pass of a
+// dev plan with large units (devplan.hip dv_paths_kernel) on the device, so both make the same decisions for the same per-unit values.
+#define XPS_MIN_IN (512u << 10)                           // Xpress streams with at least this much input are walked by segments (decompress.hip, xps_*)
+#define LZG_MIN_CAP (1u << 20)                            // units with at least this much output capacity get their bytes from all CUs (lzglobal.hip), when the plan has the scratch for it
+#ifndef LZG_TILE_SHIFT
+#define LZG_TILE_SHIFT 13                                   // output bytes per tile of lzg_expand_kernel: 8 KiB (32 KiB tiles: expansion 0.78 -> 1.37 ms, passes 4.1 -> 4.6 ms on the 12 files)
+#endif
+__host__ __device__ inline bool xps_takes(u64 len) { return len >= XPS_MIN_IN; }
+__host__ __device__ inline u64 xps_segments(u64 len, uint32_t seg_bytes) { return (len + seg_bytes - 1u) / seg_bytes; }
+// the all-CU byte stage: 32-bit word indices, so one unit with room for 4 GiB keeps the whole batch on the block kernel
+__host__ __device__ inline bool lzg_too_large(u64 cap) { return cap >= 0xFFFFFF00ull; }
+__host__ __device__ inline bool lzg_takes(u64 cap) { return cap >= LZG_MIN_CAP && !lzg_too_large(cap); }
+__host__ __device__ inline u64 lzg_token_blocks(int format, u64 len, u64 cap) { return (token_slots(format, len, cap) + 8191u) / 8192u; }
+__host__ __device__ inline u64 lzg_tiles(u64 cap) { return (cap + (1u << LZG_TILE_SHIFT) - 1u) >> LZG_TILE_SHIFT; }
+__host__ __device__ inline u64 lzg_words(u64 cap) { return cap + 64u; }
+// ... and whether it pays, from the summed and the largest capacity of the units it would take: the all-CU stage costs about 22 ms per GB
+// of output whatever the units are (74 ms for 192 files, 3.39 GB), the block-per-unit kernel about 1 ms per MB of the LARGEST unit as long
+// as there are no more large units than CUs (51 ms for the same 192 files, whose largest is 51 MB; 60 ms for 12 of them, where the all-CU
+// stage takes 5 ms). Products and quotients of doubles only: the host and the device round them alike.
+__host__ __device__ inline bool lzg_pays(u64 cap_total, u64 cap_max)
+{
+	const double mb = 1.0 / (1 << 20), c_all = 0.022 * (double)cap_total * mb, per_cu = (double)cap_total * mb / 256.0;
+	const double c_blk = 1.0 * ((double)cap_max * mb > per_cu ? (double)cap_max * mb : per_cu);
+	return c_all < c_blk;
+}
+// Xpress+Huffman: a buffer of several chunks keeps its candidates' tokens in scratch (no second walk): scratch slots of a unit
+__host__ __device__ inline u64 scratch_slots(u64 len, u64 cap) { return cap > 65536u ? candidate_slots(len, cap) : 0u; }
+
 // the largest output of n input bytes (the reference's *_max_compressed_size), and the capacity mscomp_amd_plan_layout gives such a unit
 __host__ __device__ inline u64 lznt1_max_out(u64 n)       { return n + 3u + 2u * ((n + 4095u) / 4096u); }
 __host__ __device__ inline u64 xpress_max_out(u64 n)      { return n + 4u + 4u * (n / 32u); }

@@ -930,23 +930,29 @@ __global__ __launch_bounds__(64) void xpt_parse_kernel(const uint8_t* __restrict
 struct XpsSeg { uint32_t l_ip, l_hp, e_ip, e_hp, kind, redo; u64 ntok, nout, tbase, obase, pad_; };
 static_assert(sizeof(XpsSeg) == XPS_SEG_BYTES, "XpsSeg");   // l_hp / e_hp: 0xFFFFFFFF = no nibble pending; kind: 0 ran on, 1 the stream ended well, 2 anything else
 __device__ __forceinline__ XpsSeg* xps_segs(const XpsTables& x, uint32_t b) { return reinterpret_cast<XpsSeg*>(static_cast<uint8_t*>(x.seg) + x.seg_prefix[b] * XPS_SEG_BYTES); }
-__device__ __forceinline__ void xps_segment_of(const XpsTables& x, uint32_t flat, uint32_t& b, uint32_t& k)
+__device__ __forceinline__ void xps_segment_of(const XpsTables& x, uint32_t n_big, uint32_t flat, uint32_t& b, uint32_t& k)
 {
-	uint32_t lo = 0, hi = x.n_big;
+	uint32_t lo = 0, hi = n_big;
 	while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (x.seg_prefix[mid] <= flat) { lo = mid; } else { hi = mid; } }
 	b = lo; k = flat - (uint32_t)x.seg_prefix[lo];
 }
+// DEV instances (a dev plan with large units): the grids are sized for the plan's bounds, the stream list and the counts of this execution
+// were written by its path pass (x.cnt: streams, segments), and a block past the real count returns at once. The <false> instances are the
+// kernels of host plans, which grid by the counts themselves.
+template <bool DEV> __device__ __forceinline__ uint32_t xps_streams(const XpsTables& x) { return DEV ? x.cnt[0] : x.n_big; }
 
-__global__ void xps_init_kernel(XpsTables x) { const uint32_t b = blockIdx.x * 256u + threadIdx.x; if (b < x.n_big) { x.mode[b] = 1u; } }
+template <bool DEV>
+__global__ void xps_init_kernel(XpsTables x) { const uint32_t b = blockIdx.x * 256u + threadIdx.x; if (b < xps_streams<DEV>(x)) { x.mode[b] = 1u; } }
 
 // ROUND 0: every segment (speculative start); ROUND > 0: the segments the check marked, from the exit of the segment before
-template <int ROUND>
+template <int ROUND, bool DEV>
 __global__ __launch_bounds__(64) void xps_walk_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, XpsTables x)
 {
 	__shared__ __attribute__((aligned(16))) uint8_t s_in[2u * XPT_INB];
 	const uint32_t lane = threadIdx.x;
+	if (DEV && blockIdx.x >= x.cnt[1]) { return; }
 	uint32_t b, k;
-	xps_segment_of(x, blockIdx.x, b, k);
+	xps_segment_of(x, xps_streams<DEV>(x), blockIdx.x, b, k);
 	const uint32_t u = x.unit[b];
 	XpsSeg* __restrict__ seg = xps_segs(x, b);
 	const uint32_t nseg = (uint32_t)(x.seg_prefix[b + 1] - x.seg_prefix[b]);
@@ -993,11 +999,12 @@ __global__ __launch_bounds__(64) void xps_walk_kernel(const uint8_t* __restrict_
 }
 
 // which segments hold; LAST: sums, verdict (mode 2 = done by segments, 0 = the one-wave walk takes the stream) and the caller's results
-template <bool LAST>
+template <bool LAST, bool DEV>
 __global__ __launch_bounds__(256) void xps_check_kernel(BatchTables bt, XpsTables x, u64* __restrict__ ntok, u64* __restrict__ d_out_len, int32_t* __restrict__ d_status)
 {
 	__shared__ uint32_t s_bad;
 	__shared__ u64 s_t[4], s_o[4];
+	if (DEV && blockIdx.x >= x.cnt[0]) { return; }
 	const uint32_t tid = threadIdx.x, b = blockIdx.x, u = x.unit[b];
 	XpsSeg* __restrict__ seg = xps_segs(x, b);
 	const uint32_t nseg = (uint32_t)(x.seg_prefix[b + 1] - x.seg_prefix[b]);
@@ -1047,13 +1054,14 @@ __global__ __launch_bounds__(256) void xps_check_kernel(BatchTables bt, XpsTable
 }
 
 // EMIT = false: the size query -- the same walk and tests, no token written (tok / tok_prefix unused)
-template <bool EMIT = true>
+template <bool EMIT, bool DEV>
 __global__ __launch_bounds__(64) void xps_emit_kernel(const uint8_t* __restrict__ d_in, BatchTables bt, XpsTables x, const u64* __restrict__ tok_prefix, uint32_t* __restrict__ tok)
 {
 	__shared__ __attribute__((aligned(16))) uint8_t s_in[2u * XPT_INB];
 	const uint32_t lane = threadIdx.x;
+	if (DEV && blockIdx.x >= x.cnt[1]) { return; }
 	uint32_t b, k;
-	xps_segment_of(x, blockIdx.x, b, k);
+	xps_segment_of(x, xps_streams<DEV>(x), blockIdx.x, b, k);
 	if (x.mode[b] != 2u) { return; }
 	const uint32_t u = x.unit[b];
 	const XpsSeg* __restrict__ seg = xps_segs(x, b);
@@ -1076,9 +1084,6 @@ __global__ __launch_bounds__(64) void xps_emit_kernel(const uint8_t* __restrict_
 	const bool same = W.ip == seg[k].e_ip && W.tc == seg[k].tbase + seg[k].ntok && W.op == seg[k].obase + seg[k].nout && (W.running ? (seg[k].kind == 0u && e_hp == seg[k].e_hp) : (seg[k].kind == 1u && W.status == 0));
 	if (!same && lane == 0) { x.done[u] = 0; }                            // the one-wave walk takes the stream after all
 }
-
-void launch_xpress_decompress_tokens(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
-                                     uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, const XpsTables& x);
 
 // ===================================================================================================================
 // Xpress+Huffman: one wave per buffer
@@ -1634,13 +1639,19 @@ __global__ __launch_bounds__(256) void xhc_gather_kernel(BatchTables bt, const u
 #define LZC_W 2048u
 struct LzcLds { __attribute__((aligned(16))) uint8_t win[LZC_W + 64]; uint32_t info[LZC_W]; u64 bm[LZC_W / 64u]; };
 
+// The capacity from which a unit is left to lzglobal.hip: a value the host knows (host plans; plain dev plans: none), or -- DEV, a dev plan with
+// large units -- LZG_MIN_CAP when this execution's path pass left units on that stage (its count, in device memory), none otherwise
+template <bool DEV> struct LzgMin { u64 v; __device__ __forceinline__ u64 get() const { return v; } };
+template <> struct LzgMin<true> { const uint32_t* cnt; __device__ __forceinline__ u64 get() const { return cnt[0] ? (u64)LZG_MIN_CAP : ~(u64)0; } };
+
+template <bool DEV>
 __global__ __launch_bounds__(64) void lz_copy_kernel(BatchTables bt, const u64* __restrict__ tok_prefix, const uint32_t* __restrict__ tok,
                                                     const u64* __restrict__ ntok, const u64* __restrict__ d_out_len, const int32_t* __restrict__ d_status,
-                                                    uint8_t* __restrict__ d_out, uint32_t lzb_min, u64 lzg_min_cap)
+                                                    uint8_t* __restrict__ d_out, uint32_t lzb_min, LzgMin<DEV> lzg_min_cap)
 {
 	__shared__ LzcLds L;
 	const uint32_t lane = threadIdx.x, u = blockIdx.x;
-	if (d_status[u] != 0 || bt.out_cap[u] >= lzg_min_cap) { return; }   // (units with that much room: lzglobal.hip)
+	if (d_status[u] != 0 || bt.out_cap[u] >= lzg_min_cap.get()) { return; }   // (units with that much room: lzglobal.hip)
 	const u64 total = d_out_len[u], nt = ntok[u];
 	if (total >= lzb_min) { return; }                                    // larger units: lz_copy_block_kernel
 	const uint32_t* __restrict__ mytok = tok + tok_prefix[u];
@@ -1752,14 +1763,15 @@ extern "C" void mscomp_amd_debug_lzb_prof(unsigned long long* out) { (void)hipMe
 #define LZB_CN(i, v)
 #endif
 static PerDeviceOnce g_lzb_attr;                                          // the dynamic-LDS attribute of lz_copy_block_kernel, per device (two launch sites)
+template <bool DEV>
 __global__ __launch_bounds__(LZB_NT) void lz_copy_block_kernel(BatchTables bt, const u64* __restrict__ tok_prefix, const uint32_t* __restrict__ tok,
                                                               const u64* __restrict__ ntok, const u64* __restrict__ d_out_len, const int32_t* __restrict__ d_status,
-                                                              uint8_t* __restrict__ d_out, uint32_t lzb_min, u64 lzg_min_cap)
+                                                              uint8_t* __restrict__ d_out, uint32_t lzb_min, LzgMin<DEV> lzg_min_cap)
 {
 	extern __shared__ __attribute__((aligned(16))) uint8_t lzb_smem[];
 	LzbLds& L = *reinterpret_cast<LzbLds*>(lzb_smem);
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6, u = blockIdx.x;
-	if (d_status[u] != 0 || bt.out_cap[u] >= lzg_min_cap) { return; }   // (units with that much room: lzglobal.hip)
+	if (d_status[u] != 0 || bt.out_cap[u] >= lzg_min_cap.get()) { return; }   // (units with that much room: lzglobal.hip)
 	const u64 total = d_out_len[u], nt = ntok[u];
 	if (total < lzb_min) { return; }
 	const uint32_t* __restrict__ mytok = tok + tok_prefix[u];
@@ -1919,12 +1931,29 @@ __global__ __launch_bounds__(LZB_NT) void lz_copy_block_kernel(BatchTables bt, c
 
 void prepare_lz_copy_block()
 {
-	if (g_lzb_attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_copy_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzbLds)); g_lzb_attr.done(); }
+	if (!g_lzb_attr.needed()) { return; }
+	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_copy_block_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzbLds));
+	(void)hipFuncSetAttribute(reinterpret_cast<const void*>(lz_copy_block_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzbLds));
+	g_lzb_attr.done();
+}
+// tokens -> bytes of both Xpress formats: the wave kernel (phase 0) or the block kernel (1); lzg_cnt: kernels.h launch_xpress_decompress_tokens
+static void launch_lz_copy(hipStream_t st, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len,
+                           const int32_t* d_status, uint8_t* d_out, int phase, u64 lzg_min_cap, const uint32_t* lzg_cnt)
+{
+	prepare_lz_copy_block();
+	const LzgMin<false> hm = { lzg_min_cap }; const LzgMin<true> dm = { lzg_cnt };
+	if (phase == 0) {
+		if (lzg_cnt) { hipLaunchKernelGGL(lz_copy_kernel<true>, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), dm); }
+		else { hipLaunchKernelGGL(lz_copy_kernel<false>, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), hm); }
+	} else {
+		if (lzg_cnt) { hipLaunchKernelGGL(lz_copy_block_kernel<true>, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), dm); }
+		else { hipLaunchKernelGGL(lz_copy_block_kernel<false>, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), hm); }
+	}
 }
 
 void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
                                    const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb,
-                                   uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, bool dev)
+                                   uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, bool dev, const uint32_t* lzg_cnt)
 {
 	if (bt.n_units == 0) { return; }
 	switch (phase) {
@@ -1941,12 +1970,10 @@ void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const Ba
 	case 3: if (xb.scr_prefix) { hipLaunchKernelGGL(xhc_gather_kernel, dim3(n_slots), dim3(256), 0, st, bt, tok_prefix, cand_prefix, xb, tok); }
 	        hipLaunchKernelGGL(xhc_parse_kernel<2>, dim3(n_slots), dim3(64), 0, st, d_in, bt, tok_prefix, cand_prefix, xb, tok); break;
 	case 4: hipLaunchKernelGGL(xhd_parse_kernel<true>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, xb.mode); break;
-	default: {
-		prepare_lz_copy_block();
-		hipLaunchKernelGGL(lz_copy_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap);
-		hipLaunchKernelGGL(lz_copy_block_kernel, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap);
+	default:
+		launch_lz_copy(st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, 0, lzg_min_cap, lzg_cnt);
+		launch_lz_copy(st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, 1, lzg_min_cap, lzg_cnt);
 		break;
-	}
 	}
 }
 
@@ -1962,43 +1989,51 @@ void launch_xpress_huff_size(hipStream_t st, const uint8_t* d_in, const BatchTab
 	}
 }
 
+// the segment kernels of both launchers below (phases -1 / -2 / -3; EMIT: tokens written, the decoders; false: the size query)
+template <bool DEV>
+static void xps_phase(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
+                      u64* d_out_len, int32_t* d_status, int phase, const XpsTables& x, bool emit)
+{
+	if (phase == -1) {
+		if (DEV) { launch_dev_zero(st, x.done, bt.n_units); }             // (a kernel, not a memset: kernels.h launch_dev_zero)
+		else { (void)hipMemsetAsync(x.done, 0, (size_t)bt.n_units * 4u, st); }
+		hipLaunchKernelGGL(xps_init_kernel<DEV>, dim3((x.n_big + 255u) / 256u), dim3(256), 0, st, x);
+		hipLaunchKernelGGL((xps_walk_kernel<0, DEV>), dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x);
+	} else if (phase == -2) {
+		hipLaunchKernelGGL((xps_check_kernel<false, DEV>), dim3(x.n_big), dim3(256), 0, st, bt, x, ntok, d_out_len, d_status);
+		hipLaunchKernelGGL((xps_walk_kernel<1, DEV>), dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x);
+	} else {
+		hipLaunchKernelGGL((xps_check_kernel<true, DEV>), dim3(x.n_big), dim3(256), 0, st, bt, x, ntok, d_out_len, d_status);
+		if (emit) { hipLaunchKernelGGL((xps_emit_kernel<true, DEV>), dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x, tok_prefix, tok); }
+		else { hipLaunchKernelGGL((xps_emit_kernel<false, DEV>), dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x, (const u64*)nullptr, (uint32_t*)nullptr); }
+	}
+}
+
 void launch_xpress_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, u64* d_out_len, int32_t* d_status, int phase, const XpsTables& x)
 {
 	if (bt.n_units == 0) { return; }
-	if (phase == -3) {                                                   // the verdict, then the emit walk without its stores
+	if (phase < 0) {                                                     // -1 speculative walks, -2 one round of check + walk again, -3 the verdict, then the emit walk without its stores
 		if (!x.n_big) { return; }
-		hipLaunchKernelGGL(xps_check_kernel<true>, dim3(x.n_big), dim3(256), 0, st, bt, x, ntok, d_out_len, d_status);
-		hipLaunchKernelGGL(xps_emit_kernel<false>, dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x, (const u64*)nullptr, (uint32_t*)nullptr);
+		if (x.cnt) { xps_phase<true>(st, d_in, bt, nullptr, nullptr, ntok, d_out_len, d_status, phase, x, false); }
+		else { xps_phase<false>(st, d_in, bt, nullptr, nullptr, ntok, d_out_len, d_status, phase, x, false); }
 		return;
 	}
-	if (phase < 0) { launch_xpress_decompress_tokens(st, d_in, bt, nullptr, nullptr, ntok, nullptr, d_out_len, d_status, phase, ~(u64)0, x); return; }
 	hipLaunchKernelGGL(xpt_parse_kernel<false>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, (const u64*)nullptr, (uint32_t*)nullptr, ntok, d_out_len, d_status,
 	                   (const uint32_t*)(x.n_big ? x.done : nullptr));
 }
 
 void launch_xpress_decompress_tokens(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
-                                     uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, const XpsTables& x)
+                                     uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, const XpsTables& x, const uint32_t* lzg_cnt)
 {
 	if (bt.n_units == 0) { return; }
 	if (phase < 0) {                                                     // large streams by segments (nothing to do without any): -1 speculative walks, -2 one round of check + walk again, -3 verdict + tokens
 		if (!x.n_big) { return; }
-		if (phase == -1) {
-			(void)hipMemsetAsync(x.done, 0, (size_t)bt.n_units * 4u, st);
-			hipLaunchKernelGGL(xps_init_kernel, dim3((x.n_big + 255u) / 256u), dim3(256), 0, st, x);
-			hipLaunchKernelGGL(xps_walk_kernel<0>, dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x);
-		} else if (phase == -2) {
-			hipLaunchKernelGGL(xps_check_kernel<false>, dim3(x.n_big), dim3(256), 0, st, bt, x, ntok, d_out_len, d_status);
-			hipLaunchKernelGGL(xps_walk_kernel<1>, dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x);
-		} else {
-			hipLaunchKernelGGL(xps_check_kernel<true>, dim3(x.n_big), dim3(256), 0, st, bt, x, ntok, d_out_len, d_status);
-			hipLaunchKernelGGL(xps_emit_kernel<true>, dim3(x.n_seg), dim3(64), 0, st, d_in, bt, x, tok_prefix, tok);
-		}
+		if (x.cnt) { xps_phase<true>(st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, phase, x, true); }
+		else { xps_phase<false>(st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, phase, x, true); }
 		return;
 	}
 	if (phase == 0) { hipLaunchKernelGGL(xpt_parse_kernel<true>, dim3(bt.n_units), dim3(64), 0, st, d_in, bt, tok_prefix, tok, ntok, d_out_len, d_status, (const uint32_t*)(x.n_big ? x.done : nullptr)); return; }
-	prepare_lz_copy_block();
-	if (phase == 1) { hipLaunchKernelGGL(lz_copy_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap); }
-	else { hipLaunchKernelGGL(lz_copy_block_kernel, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), lzg_min_cap); }
+	launch_lz_copy(st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, phase - 1, lzg_min_cap, lzg_cnt);
 }
 
 } // namespace msc

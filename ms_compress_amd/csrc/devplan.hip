@@ -70,6 +70,57 @@ __global__ __launch_bounds__(DV_THREADS) void dv_tables_kernel(int format, uint3
 	}
 }
 
+// The path pass of a dev plan with large units: which units take the optional paths of a host plan, and those paths' tables (kernels.h
+// DevPaths). It reads the sanitised rows the table pass has just written, so a rejected unit is an empty unit here too and enters no list.
+// Per tile of 1024 units one scan of seven values: the stable compaction of the qualifying unit indices (rank = scanned flag) and the
+// prefixes of what each adds. The verdicts that need the whole batch -- a unit too large for the all-CU stage, the stage not paying -- are
+// written at the end, as counts of 0. A list that would pass the entries it was reserved for (the creation bounds say it cannot) is off too.
+__global__ __launch_bounds__(DV_THREADS) void dv_paths_kernel(int format, uint32_t n, const u64* __restrict__ san, DevPaths dp)
+{
+	__shared__ u64 s_w[7][DV_WAVES];
+	__shared__ unsigned long long s_mx;
+	__shared__ uint32_t s_huge;
+	const uint32_t tid = threadIdx.x;
+	const u64* __restrict__ in_len = san + n;
+	const u64* __restrict__ out_cap = san + 3u * (size_t)n;
+	const bool xps = dp.xps_unit != nullptr, lzg = dp.lzg_unit != nullptr, scr = dp.scr_prefix != nullptr;
+	u64 run[7] = {0, 0, 0, 0, 0, 0, 0}, mx = 0;
+	bool huge = false;
+	if (tid == 0) { s_mx = 0; s_huge = 0; if (scr) { dp.scr_prefix[0] = 0; } }
+	__syncthreads();
+	for (uint32_t base = 0; base < n; base += DV_THREADS) {
+		const uint32_t i = base + tid;
+		const bool live = i < n;
+		const u64 L = live ? in_len[i] : 0, C = live ? out_cap[i] : 0;
+		const bool qx = xps && xps_takes(L), qg = lzg && lzg_takes(C);
+		if (lzg && lzg_too_large(C)) { huge = true; }
+		if (qg && C > mx) { mx = C; }
+		const u64 segs = qx ? xps_segments(L, dp.xps_seg_bytes) : 0, tb = qg ? lzg_token_blocks(format, L, C) : 0, tl = qg ? lzg_tiles(C) : 0, wd = qg ? lzg_words(C) : 0;
+		u64 v[7] = {qx ? 1u : 0u, segs, qg ? 1u : 0u, tb, tl, wd, scr ? scratch_slots(L, C) : 0};
+		dv_block_scan<7>(v, run, s_w);                                   // inclusive: rank + 1 of a unit taken, the prefix entries behind it
+		if (qx && v[0] <= dp.xps_max) { const u64 k = v[0] - 1u; dp.xps_unit[k] = i; dp.xps_seg_prefix[k] = v[1] - segs; }
+		if (qg && v[2] <= dp.lzg_max) { const u64 k = v[2] - 1u; dp.lzg_unit[k] = i; dp.lzg_tb_prefix[k] = v[3] - tb; dp.lzg_tile_prefix[k] = v[4] - tl; dp.lzg_word_prefix[k] = v[5] - wd; }
+		if (scr && live) { dp.scr_prefix[i + 1u] = v[6]; }
+	}
+	if (huge) { atomicOr(&s_huge, 1u); }
+	if (mx) { atomicMax(&s_mx, (unsigned long long)mx); }
+	__syncthreads();
+	if (tid != 0) { return; }
+	if (xps) {
+		const bool on = run[0] <= dp.xps_max && run[1] <= dp.xps_seg_max;
+		const uint32_t nb = on ? (uint32_t)run[0] : 0u;
+		if (on) { dp.xps_seg_prefix[nb] = run[1]; }
+		dp.xps_cnt[0] = nb; dp.xps_cnt[1] = on ? (uint32_t)run[1] : 0u;
+	}
+	if (lzg) {
+		const u64 nb = run[2];
+		const bool fits = nb <= dp.lzg_max && run[3] <= dp.lzg_tb_max && run[4] <= dp.lzg_tile_max && run[5] <= dp.lzg_word_max;
+		const bool on = nb != 0 && fits && !s_huge && lzg_pays(run[5] - 64u * nb, s_mx);   // (run[5]: sum of capacity + 64)
+		if (on) { dp.lzg_tb_prefix[nb] = run[3]; dp.lzg_tile_prefix[nb] = run[4]; dp.lzg_word_prefix[nb] = run[5]; }
+		dp.lzg_cnt[0] = on ? (uint32_t)nb : 0u; dp.lzg_cnt[1] = on ? (uint32_t)run[3] : 0u; dp.lzg_cnt[2] = on ? (uint32_t)run[4] : 0u;
+	}
+}
+
 // The compress form: per unit the checks of a compress dev plan, the sanitised row and the chunk prefix of compress_chunks(format, L) (common.h).
 // A rejected unit is an empty unit without room and has no chunks, so that no chunk-gridded kernel visits it.
 __global__ __launch_bounds__(DV_THREADS) void dv_ctables_kernel(int format, uint32_t n, u64 in_max, u64 unit_max,
@@ -155,6 +206,11 @@ void launch_dev_tables(hipStream_t st, int format, uint32_t n, u64 in_total_max,
 {
 	hipLaunchKernelGGL(dv_tables_kernel<false>, dim3(1), dim3(DV_THREADS), 0, st, format, n, in_total_max, out_total_max, in_off, in_len, out_off, out_cap,
 	                   san, chunk_prefix, tok_prefix, reject);
+}
+
+void launch_dev_paths(hipStream_t st, int format, uint32_t n, const u64* san, const DevPaths& dp)
+{
+	hipLaunchKernelGGL(dv_paths_kernel, dim3(1), dim3(DV_THREADS), 0, st, format, n, san, dp);
 }
 
 void launch_dev_stables(hipStream_t st, int format, uint32_t n, u64 in_total_max, const u64* in_off, const u64* in_len, const u64* limit,

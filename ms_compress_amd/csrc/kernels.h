@@ -97,7 +97,6 @@ void launch_xpress_decompress(hipStream_t st, const uint8_t* d_in, const BatchTa
 #define XPS_SEG    16384u                                 // input bytes per segment (12 whole files, segment / warm-up KiB: 32/32 15.5 ms, 16/16 14.1, 8/8 19.6, 32/8 21.2)
 #define XPS_WARM   16384u                                 // a speculative walk starts this far before its segment
 #define XPS_SEG_BYTES 64u
-#define XPS_MIN_IN (512u << 10)                           // streams with at least this much input
 #define XPS_ROUNDS 8u                                     // rounds of "walk the segments again that do not hold"
 struct XpsTables {
 	const uint32_t* unit;          // n_big: the streams taken
@@ -107,10 +106,13 @@ struct XpsTables {
 	uint32_t* done;                // per unit of the batch: XPS_DONE when the one-wave walk has nothing to do
 	uint32_t  n_big, n_seg;
 	uint32_t  seg_bytes, warm_bytes; // input bytes per segment; a speculative walk starts this far before its segment (<= seg_bytes)
+	const uint32_t* cnt;           // null: a host plan, n_big / n_seg are the counts. A dev plan with large units: n_big / n_seg are its bounds (grids,
+	                               // scratch layout) and cnt[0] / cnt[1] the counts of this execution, written by its path pass (the DEV kernel instances read them)
 };
 // the same through 32-bit tokens: phase -1 = the segment kernels, 0 = xpt_parse_kernel (a flag word at a time), 1 = lz_copy_kernel, 2 = lz_copy_block_kernel
 void launch_xpress_decompress_tokens(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
-                                     uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, const XpsTables& x);
+                                     uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, const XpsTables& x,
+                                     const uint32_t* lzg_cnt = nullptr);   // lzg_cnt: a dev plan with large units -- the byte kernels leave the units of LZG_MIN_CAP and more to lzglobal.hip when lzg_cnt[0] != 0
 // the size query: the same walks with every test and no token written (phases -1 / -2 / -3 as above, 0 = the one-wave walk); ntok: n_units counts
 void launch_xpress_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, u64* d_out_len, int32_t* d_status, int phase, const XpsTables& x);
 
@@ -125,7 +127,8 @@ struct XhcBufs { uint32_t* cand_cnt; uint32_t* mode; uint32_t* cand_pos; uint32_
 #define XHC_SCR 65600u                                    // a candidate gives up to 65536 tokens before its 65536th byte
 void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
                                    const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb,
-                                   uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, bool dev = false);   // dev: as launch_lzd_segments
+                                   uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, bool dev = false,   // dev: as launch_lzd_segments
+                                   const uint32_t* lzg_cnt = nullptr);                                                                 // lzg_cnt: as launch_xpress_decompress_tokens
 void prepare_lz_copy_block();                             // the one-time LDS attribute of lz_copy_block_kernel (tokens -> bytes of both Xpress formats)
 // the size query: phases 0 mark, 1 measure every candidate (no tokens written, chunk 0 included), 2 chain check, 3 serial walk without tokens
 void launch_xpress_huff_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, const u64* cand_prefix, uint32_t n_slots,
@@ -133,10 +136,7 @@ void launch_xpress_huff_size(hipStream_t st, const uint8_t* d_in, const BatchTab
 
 // ---- tokens -> bytes for large units by all CUs (lzglobal.hip) ----
 #define LZG_PASSES 33u                                    // pointer passes launched (chains halve at least: 2^32 bytes); a pass returns at once when the one before left nothing open
-#ifndef LZG_TILE_SHIFT
-#define LZG_TILE_SHIFT 13                                   // output bytes per tile of lzg_expand_kernel: 8 KiB (32 KiB tiles: expansion 0.78 -> 1.37 ms, passes 4.1 -> 4.6 ms on the 12 files)
-#endif
-#define LZG_MIN_CAP (1u << 20)                            // units with at least this much output capacity take this path (when the plan has the scratch for it)
+// (LZG_TILE_SHIFT, LZG_MIN_CAP: common.h, beside lzg_takes; XPS_MIN_IN there too)
 struct LzgTables {
 	const uint32_t* unit;          // n_big: the units taken
 	const u64* tb_prefix;          // n_big + 1: first token block (8192 tokens) of each
@@ -149,8 +149,10 @@ struct LzgTables {
 	uint32_t* open;                // LZG_PASSES counters: words still pointing after each pass
 	uint8_t*  tile_pass;           // per tile: the pointer pass that has to look at it next (0xFF: none)
 	uint32_t  n_big, n_tb, n_tiles;
+	const uint32_t* cnt;           // as XpsTables::cnt: cnt[0] units taken (0: the stage does not run in this execution), cnt[1] token blocks, cnt[2] tiles
 };
 // phase 0 = directory (3 kernels), 1 = lzg_expand_kernel, 2 = the pointer passes
+void prepare_lz_copy_global(bool dev);                    // the one-time LDS attribute of lzg_expand_kernel (a dev plan sets it when it is created, as prepare_lzd_segments)
 void launch_lz_copy_global(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok,
                            const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, int phase);
 
@@ -161,6 +163,17 @@ void launch_lz_copy_global(hipStream_t st, const LzgTables& g, const BatchTables
 // each, the candidate prefix right behind the token prefix) with the counts plan_create_impl uses on the host (common.h).
 void launch_dev_tables(hipStream_t st, int format, uint32_t n, u64 in_total_max, u64 out_total_max, const u64* in_off, const u64* in_len,
                        const u64* out_off, const u64* out_cap, u64* san, uint32_t* chunk_prefix, u64* tok_prefix, uint32_t* reject);
+// The path pass of a dev plan with large units (MSCOMP_AMD_DEV_LARGE_UNITS), one block behind the table pass: from the sanitised rows, the
+// tables plan_create_impl builds on the host for the optional paths, with the same arithmetic (common.h). Each of the three parts is off
+// when its first pointer is null.
+struct DevPaths {
+	uint32_t* xps_unit; u64* xps_seg_prefix; uint32_t* xps_cnt;       // Xpress streams walked by segments: units in unit order, first segment of each, {units, segments}
+	uint32_t  xps_seg_bytes, xps_max, xps_seg_max;                    // (*_max: the entries the lists and the scratch were reserved for)
+	uint32_t* lzg_unit; u64* lzg_tb_prefix; u64* lzg_tile_prefix; u64* lzg_word_prefix; uint32_t* lzg_cnt;   // the all-CU byte stage: {units, token blocks, tiles}, all 0 when the stage is off for the batch
+	uint32_t  lzg_max; u64 lzg_tb_max, lzg_tile_max, lzg_word_max;
+	u64*      scr_prefix;                                             // Xpress+Huffman: first token-scratch slot of every unit (n + 1)
+};
+void launch_dev_paths(hipStream_t st, int format, uint32_t n, const u64* san, const DevPaths& dp);
 // size plans (mscomp_amd_plan_create_size_dev): the same pass with out_off = 0 and out_cap = limit for every unit (limit null: 2^64 - 1) and
 // no bound on the limits' sum; the prefix arrays are those of a host size plan with these values
 void launch_dev_stables(hipStream_t st, int format, uint32_t n, u64 in_total_max, const u64* in_off, const u64* in_len, const u64* limit,

@@ -48,13 +48,20 @@ __device__ __forceinline__ u64 lzg_block_excl(u64 v, u64* s_w, uint32_t tid, u64
 	return base + x - v;
 }
 
+// DEV instances (a dev plan with large units): the grid is sized for the plan's bounds, the unit list and the counts of this execution were
+// written by its path pass (g.cnt: units, token blocks, tiles), and a block past the real count returns at once. The <false> instances are
+// the kernels of host plans, which grid by the counts themselves.
+template <bool DEV> __device__ __forceinline__ uint32_t lzg_units(const LzgTables& g) { return DEV ? g.cnt[0] : g.n_big; }
+
 // ---- directory ----------------------------------------------------------------------------------------------------------------------------
+template <bool DEV>
 __global__ __launch_bounds__(LZG_NT) void lzg_sums_kernel(LzgTables g, const u64* __restrict__ tok_prefix, const uint32_t* __restrict__ tok, const u64* __restrict__ ntok,
                                                          const int32_t* __restrict__ d_status)
 {
 	__shared__ u64 s_w[16];
 	const uint32_t tid = threadIdx.x;
-	const uint32_t b = lzg_seg(g.tb_prefix, g.n_big, blockIdx.x), u = g.unit[b];
+	if (DEV && blockIdx.x >= g.cnt[1]) { return; }
+	const uint32_t b = lzg_seg(g.tb_prefix, lzg_units<DEV>(g), blockIdx.x), u = g.unit[b];
 	const u64 j = blockIdx.x - g.tb_prefix[b];
 	if (d_status[u] != 0) { return; }
 	const u64 nt = ntok[u];
@@ -68,9 +75,11 @@ __global__ __launch_bounds__(LZG_NT) void lzg_sums_kernel(LzgTables g, const u64
 	if (tid == 0) { g.bsum[blockIdx.x] = tot; }
 }
 
+template <bool DEV>
 __global__ __launch_bounds__(LZG_NT) void lzg_scan_kernel(LzgTables g, const u64* __restrict__ ntok, const int32_t* __restrict__ d_status)
 {
 	__shared__ u64 s_w[16];
+	if (DEV && blockIdx.x >= g.cnt[0]) { return; }
 	const uint32_t tid = threadIdx.x, b = blockIdx.x, u = g.unit[b];
 	if (d_status[u] != 0) { return; }
 	const u64 nb = (ntok[u] + LZG_TB - 1u) / LZG_TB;
@@ -86,12 +95,14 @@ __global__ __launch_bounds__(LZG_NT) void lzg_scan_kernel(LzgTables g, const u64
 	}
 }
 
+template <bool DEV>
 __global__ __launch_bounds__(LZG_NT) void lzg_dir_kernel(LzgTables g, const u64* __restrict__ tok_prefix, const uint32_t* __restrict__ tok, const u64* __restrict__ ntok,
                                                         const u64* __restrict__ d_out_len, const int32_t* __restrict__ d_status)
 {
 	__shared__ u64 s_w[16];
 	const uint32_t tid = threadIdx.x;
-	const uint32_t b = lzg_seg(g.tb_prefix, g.n_big, blockIdx.x), u = g.unit[b];
+	if (DEV && blockIdx.x >= g.cnt[1]) { return; }
+	const uint32_t b = lzg_seg(g.tb_prefix, lzg_units<DEV>(g), blockIdx.x), u = g.unit[b];
 	const u64 j = blockIdx.x - g.tb_prefix[b];
 	if (d_status[u] != 0) { return; }
 	const u64 nt = ntok[u], total = d_out_len[u];
@@ -126,6 +137,7 @@ struct LzgLds {
 #define LZG_W_VAL 0x80000000u                                      // | byte
 #define LZG_W_EXT 0x40000000u                                      // | how far before the tile start (1 .. 65535)
 
+template <bool DEV>
 __global__ __launch_bounds__(LZG_NT) void lzg_expand_kernel(LzgTables g, BatchTables bt, const u64* __restrict__ tok_prefix, const uint32_t* __restrict__ tok,
                                                            const u64* __restrict__ ntok, const u64* __restrict__ d_out_len, const int32_t* __restrict__ d_status,
                                                            uint8_t* __restrict__ d_out)
@@ -133,7 +145,8 @@ __global__ __launch_bounds__(LZG_NT) void lzg_expand_kernel(LzgTables g, BatchTa
 	extern __shared__ __attribute__((aligned(16))) uint8_t lzg_smem[];
 	LzgLds& L = *reinterpret_cast<LzgLds*>(lzg_smem);
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-	const uint32_t b = lzg_seg(g.tile_prefix, g.n_big, blockIdx.x), u = g.unit[b];
+	if (DEV && blockIdx.x >= g.cnt[2]) { return; }
+	const uint32_t b = lzg_seg(g.tile_prefix, lzg_units<DEV>(g), blockIdx.x), u = g.unit[b];
 	const u64 k = blockIdx.x - g.tile_prefix[b];
 	if (d_status[u] != 0) { return; }
 	const u64 total = d_out_len[u], nt = ntok[u], w0 = k * LZG_T;
@@ -249,14 +262,16 @@ __global__ __launch_bounds__(LZG_NT) void lzg_expand_kernel(LzgTables g, BatchTa
 
 // ---- pointer passes ------------------------------------------------------------------------------------------------------------------------
 #define LZG_HOPS 8u
+template <bool DEV>
 __global__ __launch_bounds__(256) void lzg_jump_kernel(LzgTables g, BatchTables bt, const u64* __restrict__ d_out_len, const int32_t* __restrict__ d_status,
                                                       uint8_t* __restrict__ d_out, uint32_t pass, uint32_t hops)
 {
 	if (pass > 0 && g.open[pass - 1u] == 0) { return; }                  // the pass before left nothing open
 	uint32_t still_all = 0;
-	for (uint32_t tile = blockIdx.x; tile < g.n_tiles; tile += gridDim.x) {
+	const uint32_t n_tiles = DEV ? g.cnt[2] : g.n_tiles;
+	for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
 		if (g.tile_pass[tile] != pass) { continue; }                     // all its words are values already (or it lies behind the unit's end)
-		const uint32_t b = lzg_seg(g.tile_prefix, g.n_big, tile), u = g.unit[b];
+		const uint32_t b = lzg_seg(g.tile_prefix, lzg_units<DEV>(g), tile), u = g.unit[b];
 		const u64 total = d_out_len[u], w0 = (u64)(tile - g.tile_prefix[b]) * LZG_T;
 		if (d_status[u] != 0 || w0 >= total) { continue; }                 // (a tile the expansion did not visit: its flag is stale)
 		uint32_t* __restrict__ P = g.words + g.word_prefix[b];
@@ -288,27 +303,46 @@ __global__ __launch_bounds__(256) void lzg_jump_kernel(LzgTables g, BatchTables 
 	}
 }
 
+template <bool DEV>
+static void lz_copy_global_phase(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok,
+                                 const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, int phase)
+{
+	switch (phase) {
+	case 0:
+		if (DEV) { launch_dev_zero(st, g.open, LZG_PASSES); }             // (a kernel, not a memset: kernels.h launch_dev_zero)
+		else { (void)hipMemsetAsync(g.open, 0, LZG_PASSES * sizeof(uint32_t), st); }
+		hipLaunchKernelGGL(lzg_sums_kernel<DEV>, dim3(g.n_tb), dim3(LZG_NT), 0, st, g, tok_prefix, tok, ntok, d_status);
+		hipLaunchKernelGGL(lzg_scan_kernel<DEV>, dim3(g.n_big), dim3(LZG_NT), 0, st, g, ntok, d_status);
+		hipLaunchKernelGGL(lzg_dir_kernel<DEV>, dim3(g.n_tb), dim3(LZG_NT), 0, st, g, tok_prefix, tok, ntok, d_out_len, d_status);
+		break;
+	case 1:
+		prepare_lz_copy_global(DEV);
+		hipLaunchKernelGGL(lzg_expand_kernel<DEV>, dim3(g.n_tiles), dim3(LZG_NT), sizeof(LzgLds), st, g, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out);
+		break;
+	default: {
+		static const uint32_t hops = [] { const char* e = getenv("MSCOMP_AMD_LZG_HOPS"); const long v = e ? atol(e) : 0; return (uint32_t)(v > 0 && v < 1000 ? v : LZG_HOPS); }();
+		for (uint32_t pass = 0; pass < LZG_PASSES; ++pass) { hipLaunchKernelGGL(lzg_jump_kernel<DEV>, dim3(g.n_tiles < 4096u ? g.n_tiles : 4096u), dim3(256), 0, st, g, bt, d_out_len, d_status, d_out, pass, hops); }
+		break;
+	}
+	}
+}
+
+void prepare_lz_copy_global(bool dev)
+{
+	static PerDeviceOnce attr[2];
+	PerDeviceOnce& a = attr[dev ? 1 : 0];
+	if (!a.needed()) { return; }
+	const void* f = dev ? reinterpret_cast<const void*>(lzg_expand_kernel<true>) : reinterpret_cast<const void*>(lzg_expand_kernel<false>);
+	(void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzgLds));
+	a.done();
+}
+
 void launch_lz_copy_global(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok,
                            const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, int phase)
 {
 	if (g.n_big == 0) { return; }
-	switch (phase) {
-	case 0:
-		(void)hipMemsetAsync(g.open, 0, LZG_PASSES * sizeof(uint32_t), st);
-		hipLaunchKernelGGL(lzg_sums_kernel, dim3(g.n_tb), dim3(LZG_NT), 0, st, g, tok_prefix, tok, ntok, d_status);
-		hipLaunchKernelGGL(lzg_scan_kernel, dim3(g.n_big), dim3(LZG_NT), 0, st, g, ntok, d_status);
-		hipLaunchKernelGGL(lzg_dir_kernel, dim3(g.n_tb), dim3(LZG_NT), 0, st, g, tok_prefix, tok, ntok, d_out_len, d_status);
-		break;
-	case 1:
-		{ static PerDeviceOnce attr; if (attr.needed()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lzg_expand_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzgLds)); attr.done(); } }
-		hipLaunchKernelGGL(lzg_expand_kernel, dim3(g.n_tiles), dim3(LZG_NT), sizeof(LzgLds), st, g, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out);
-		break;
-	default: {
-		static const uint32_t hops = [] { const char* e = getenv("MSCOMP_AMD_LZG_HOPS"); const long v = e ? atol(e) : 0; return (uint32_t)(v > 0 && v < 1000 ? v : LZG_HOPS); }();
-		for (uint32_t pass = 0; pass < LZG_PASSES; ++pass) { hipLaunchKernelGGL(lzg_jump_kernel, dim3(g.n_tiles < 4096u ? g.n_tiles : 4096u), dim3(256), 0, st, g, bt, d_out_len, d_status, d_out, pass, hops); }
-		break;
-	}
-	}
+	if (g.cnt) { lz_copy_global_phase<true>(st, g, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, phase); }
+	else { lz_copy_global_phase<false>(st, g, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, phase); }
 }
 
 } // namespace msc

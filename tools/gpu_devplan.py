@@ -5,6 +5,7 @@ Compress leg: compress dev plans (mscomp_amd_plan_create_compress_dev) against h
 Reported per case (HIP events after a warm-up, mean of `reps` executions):
   host_ms       mscomp_amd_plan_execute of one host plan (its own graph replayed)
   dev_ms        mscomp_amd_plan_execute_dev of one dev plan, tables in device memory (its own graph replayed)
+  large_ms      the same of a dev plan created with MSCOMP_AMD_DEV_LARGE_UNITS (decompress leg; compress plans have no such paths)
   host_batch_ms create + execute + destroy of a host plan per batch, to the end of the batch (host clock)
   dev_batch_ms  one dev plan executed per batch, tables written on the device, to the end of the batch (host clock)
 The outputs of both plans are compared byte for byte. Prints one line per case and a JSON list at the end.
@@ -79,7 +80,14 @@ def run(ctx, fmt, units, label, reps):
     dev_ms = event_ms(lambda: d.execute(d_c, t_coff, t_clen, d_do, t_ooff, t_ocap, d_dl, d_ds), reps)
     torch.cuda.synchronize()
     ok = bool((d_hs == 0).all()) and torch.equal(d_hs, d_ds) and torch.equal(d_hl, d_dl) and torch.equal(d_ho, d_do)
+    host_paths = m.api.plan_paths(q)
     q.close()
+    for t in (d_do, d_dl, d_ds):
+        t.zero_()
+    g = m.DevPlan(ctx, fmt, n, int(clens.sum()), int(lens.sum()), large_units=True)
+    large_ms = event_ms(lambda: g.execute(d_c, t_coff, t_clen, d_do, t_ooff, t_ocap, d_dl, d_ds), reps)
+    torch.cuda.synchronize()
+    ok = ok and torch.equal(d_hs, d_ds) and torch.equal(d_hl, d_dl) and torch.equal(d_ho, d_do) and m.api.plan_paths(g) == host_paths
 
     def host_batch():
         h = m.Plan(ctx, fmt, c_off, clens, in_off, lens, decompress=True)
@@ -94,12 +102,24 @@ def run(ctx, fmt, units, label, reps):
     host_batch_ms = wall_ms(host_batch, reps)
     dev_batch_ms = wall_ms(dev_batch, reps)
     d.close()
+
+    def large_batch():
+        t_clen.copy_(d_len)
+        g.execute(d_c, t_coff, t_clen, d_do, t_ooff, t_ocap, d_dl, d_ds)
+        torch.cuda.current_stream().synchronize()
+
+    large_batch_ms = wall_ms(large_batch, reps)
+    g.close()
     out = int(lens.sum())
     r = {"format": fmt, "units": label, "n_units": n, "in_bytes": int(clens.sum()), "out_bytes": out, "ok": ok,
          "host_ms": round(host_ms, 3), "dev_ms": round(dev_ms, 3), "dev_over_host": round(dev_ms / host_ms, 3),
-         "host_batch_ms": round(host_batch_ms, 3), "dev_batch_ms": round(dev_batch_ms, 3), "batch_ratio": round(dev_batch_ms / host_batch_ms, 3)}
-    print("fmt %d %-26s %s  host %8.3f ms  dev %8.3f ms (x%.3f)  per batch: create+execute %8.3f ms, dev plan %8.3f ms (x%.3f)"
-          % (fmt, label, "ok" if ok else "MISMATCH", host_ms, dev_ms, r["dev_over_host"], host_batch_ms, dev_batch_ms, r["batch_ratio"]), flush=True)
+         "large_ms": round(large_ms, 3), "large_over_host": round(large_ms / host_ms, 3), "large_over_dev": round(large_ms / dev_ms, 3),
+         "paths": list(host_paths),
+         "host_batch_ms": round(host_batch_ms, 3), "dev_batch_ms": round(dev_batch_ms, 3), "batch_ratio": round(dev_batch_ms / host_batch_ms, 3),
+         "large_batch_ms": round(large_batch_ms, 3)}
+    print("fmt %d %-26s %s  host %8.3f ms  dev %8.3f ms (x%.3f)  dev, large units %8.3f ms (x%.3f of host)  per batch: create+execute %8.3f ms, dev plan %8.3f ms (x%.3f), large units %8.3f ms"
+          % (fmt, label, "ok" if ok else "MISMATCH", host_ms, dev_ms, r["dev_over_host"], large_ms, r["large_over_host"], host_batch_ms, dev_batch_ms,
+             r["batch_ratio"], large_batch_ms), flush=True)
     return r
 
 

@@ -1,7 +1,8 @@
 """The two stages that take device tables since size dev plans and mscomp_amd_compact_dev, against their host-table forms on the same units.
 Size leg: a size dev plan (mscomp_amd_plan_create_size_dev) against a host size plan on the rows of tools/gpu_devplan.py (the bench corpus
   cut into 3 239 units of 64 KiB per format; mozilla, 51 MB, as one unit per format): HIP events after a warm-up, the two plans alternated
-  in blocks of 5 executions until each has `reps`; results compared entry for entry.
+  in blocks of 5 executions until each has `reps`; results compared entry for entry. large_ms: a size dev plan created with
+  MSCOMP_AMD_DEV_LARGE_UNITS, alternated with the host plan in the same way.
 Compact leg: mscomp_amd_compact_dev against mscomp_amd_compact_batch on the compressed outputs of the configs[4]-shaped batch (the 12 files,
   16 replicas: Xpress as 51 824 units of 64 KiB, LZNT1 as 192 whole files), outputs at their capacities:
   batch_wall_ms  compact_batch to the end of the stream, host clock (its table upload and synchronise included)
@@ -89,11 +90,20 @@ def run_size(ctx, fmt, units, label, reps):
     host_ms, dev_ms = alternate(lambda: host.execute(d_c, *res[0]), lambda: dev.execute(d_c, t_off, d_clen, *res[1]), reps)
     torch.cuda.synchronize()
     ok = all(torch.equal(a, b) for a, b in zip(*res)) and bool((res[0][2] == 0).all())
-    host.close()
     dev.close()
+    for t in res[1]:
+        t.zero_()
+    large = m.SizeDevPlan(ctx, fmt, n, int(clens.sum()), large_units=True)
+    _, large_ms = alternate(lambda: host.execute(d_c, *res[0]), lambda: large.execute(d_c, t_off, d_clen, *res[1]), reps)
+    torch.cuda.synchronize()
+    ok = ok and all(torch.equal(a, b) for a, b in zip(*res)) and m.api.plan_paths(large) == m.api.plan_paths(host)
+    host.close()
+    large.close()
     r = {"leg": "size", "format": fmt, "units": label, "n_units": n, "in_bytes": int(clens.sum()), "ok": ok,
-         "host_ms": round(host_ms, 4), "dev_ms": round(dev_ms, 4), "dev_over_host": round(dev_ms / host_ms, 3)}
-    print("size fmt %d %-26s %s  host %9.4f ms  dev %9.4f ms (x%.3f)" % (fmt, label, "ok" if ok else "MISMATCH", host_ms, dev_ms, r["dev_over_host"]), flush=True)
+         "host_ms": round(host_ms, 4), "dev_ms": round(dev_ms, 4), "dev_over_host": round(dev_ms / host_ms, 3),
+         "large_ms": round(large_ms, 4), "large_over_host": round(large_ms / host_ms, 3)}
+    print("size fmt %d %-26s %s  host %9.4f ms  dev %9.4f ms (x%.3f)  dev, large units %9.4f ms (x%.3f)"
+          % (fmt, label, "ok" if ok else "MISMATCH", host_ms, dev_ms, r["dev_over_host"], large_ms, r["large_over_host"]), flush=True)
     return r
 
 
