@@ -369,6 +369,66 @@ MSCompStatus mscomp_amd_compact_batch(mscomp_amd_ctx* ctx, size_t n_units, const
 MSCompStatus mscomp_amd_compact_dev(mscomp_amd_ctx* ctx, size_t n_units, const uint8_t* d_src, const uint64_t* d_src_off,
                                     const uint64_t* d_len, uint64_t align, uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_packed_off);
 
+/* Block containers: the shape in which these codecs are deployed (WIM resources, WOF-compressed files, NTFS compression units). A resource
+ * (one caller buffer) is cut into blocks of block_size bytes, every block is compressed on its own, a block that does not shrink is stored
+ * raw, the stored blocks are packed back to back, and a table of offsets says where each one is -- so a reader who wants a range of a
+ * resource decodes only the blocks that hold it. One call handles a batch of n_res resources; all tables are device arrays, written and
+ * read by kernels on the ctx stream. (A block is the container's piece; the codecs' own 4 KiB / 64 KiB chunks keep their name.)
+ * The payloads are this library's ms_compress bytes and the tables plain uint64 arrays beside the data: byte compatibility with a particular
+ * WIM, WOF or NTFS writer is not claimed, and serialising to one of those on-disk headers is the caller's.
+ *   Creation:     block_size = B is a power of two from 4096 to 524288; flags must be 0. n_blocks_max = n_res + in_total_max / B
+ *                 (mscomp_amd_blocks_bound) bounds the blocks of any batch whose lengths sum to at most in_total_max. All scratch is
+ *                 reserved here, once, and never grows: a compress and a decompress dev plan for n_blocks_max units (of at most B bytes;
+ *                 within in_total_max bytes in and out), the staging area of the compressed blocks -- 1 byte per byte of in_total_max + 16
+ *                 per resource --, and 64 bytes of tables per possible block + 28 per resource. MSCOMP_ARG_ERROR for a null ctx or bk, a bad
+ *                 format, a bad block_size, non-zero flags, n_res above 0x7FFFFFF0; MSCOMP_MEM_ERROR when n_blocks_max exceeds 0x7FFFFFF0 or
+ *                 the scratch cannot be reserved. The LZNT1 dictionary flavour is fixed here, as for a compress dev plan.
+ *   Compress:     d_res_off, d_res_len, d_status: n_res entries; d_block_first: n_res + 1; d_block_off: n_blocks_max + 1.
+ *                 Resource r is the d_res_len[r] bytes at d_in + d_res_off[r]. It is rejected -- MSCOMP_ARG_ERROR, no blocks, nothing read --
+ *                 when the running total of d_res_len up to and including it exceeds in_total_max. An accepted resource has
+ *                 ceil(len / B) blocks (an empty one none), block j being its bytes [j B, min(len, (j + 1) B)).
+ *                 d_block_first = the exclusive running count of blocks, d_block_first[n_res] = their number nb.
+ *                 Stored form of a block: c = the bytes one ms_compress(format, block) call writes with ample capacity (the counted length:
+ *                 LZNT1's uncounted trailing 00 00 is not stored) when len(c) < len(block), the raw block otherwise -- never longer than
+ *                 its data. d_block_off[0..nb] = the exclusive running sum of the stored lengths, without padding; the entries
+ *                 nb + 1 .. n_blocks_max repeat d_block_off[nb]. d_packed[0 .. d_block_off[nb]) holds the stored blocks in order.
+ *                 Nothing is written at or behind d_packed + packed_cap: a block that would end beyond it is not written at all and its
+ *                 resource gets MSCOMP_BUF_ERROR, the tables still holding the full layout (the rule of mscomp_amd_compact_dev). Every
+ *                 other resource gets MSCOMP_OK.
+ *   Decompress:   d_range = NULL means every block; otherwise 2 n_res uint64, per resource a first block f and a count c, both clipped to the
+ *                 resource's block count. want = min(len, (f + c) B) - f B bytes (0 for c = 0) go to d_out + d_out_off[r]. Per resource, in
+ *                 this order, each leaving the other resources alone:
+ *                   1. MSCOMP_ARG_ERROR, nothing read or written: the running total of d_res_len up to and including it exceeds
+ *                      in_total_max, or d_block_first[r] or d_block_first[r + 1] exceeds n_blocks_max;
+ *                   2. MSCOMP_DATA_ERROR: d_block_first[r + 1] - d_block_first[r] is not ceil(len / B);
+ *                   3. MSCOMP_BUF_ERROR, nothing written: want > d_out_cap[r];
+ *                   4. every block in range, by its stored length s = off[j + 1] - off[j] and its data length e: s = e is copied;
+ *                      0 < s < e is decoded exactly as ms_decompress with capacity e, and must give MSCOMP_OK and e bytes; anything
+ *                      else -- s > e, s = 0, a decreasing table, an end beyond packed_len, another decoder status or length -- is
+ *                      MSCOMP_DATA_ERROR for the resource. A block that fails a table check is never read.
+ *                 MSCOMP_OK: d_out_len[r] = want and the bytes are that slice of the resource. Otherwise d_out_len[r] = 0, the bytes
+ *                 inside the resource's capacity are unspecified and nothing is written outside it. Blocks outside the range are not
+ *                 decoded and cost nothing but their share of the fixed launches.
+ *   Execution:    as mscomp_amd_plan_execute_dev: asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation, no
+ *                 synchronisation, nothing read back, a launch sequence fixed by the creation bounds, all on the one stream. Legal while
+ *                 the caller captures the ctx stream, the first execution included (plain launches then); outside capture each of the two
+ *                 calls replays a graph of its own from its second execution on, captured again when an argument changes.
+ *                 MSCOMP_ARG_ERROR for a null bk or a null required array (d_in, d_packed and d_out may be null when in_total_max is 0,
+ *                 d_range always). */
+typedef struct mscomp_amd_blocks mscomp_amd_blocks;
+MSCompStatus mscomp_amd_blocks_create(mscomp_amd_ctx* ctx, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t in_total_max,
+                                      uint32_t flags, mscomp_amd_blocks** bk);
+void         mscomp_amd_blocks_destroy(mscomp_amd_blocks* bk);
+uint64_t     mscomp_amd_blocks_bound(const mscomp_amd_blocks* bk);   /* n_blocks_max; 0 for NULL */
+MSCompStatus mscomp_amd_blocks_compress(mscomp_amd_blocks* bk, const uint8_t* d_in, const uint64_t* d_res_off, const uint64_t* d_res_len,
+                                        uint8_t* d_packed, uint64_t packed_cap,
+                                        uint64_t* d_block_first, uint64_t* d_block_off, int32_t* d_status);
+MSCompStatus mscomp_amd_blocks_decompress(mscomp_amd_blocks* bk, const uint8_t* d_packed, uint64_t packed_len,
+                                          const uint64_t* d_block_first, const uint64_t* d_block_off, const uint64_t* d_res_len,
+                                          const uint64_t* d_range,
+                                          uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+                                          uint64_t* d_out_len, int32_t* d_status);
+
 /* ---- measurement hooks (bench.py / profiles) ---- */
 /* When enabled, every kernel launch of plan_execute is bracketed by hipEvents on the ctx stream. */
 void         mscomp_amd_profile_enable(mscomp_amd_ctx* ctx, int on);

@@ -9,4 +9,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   MSCOMP_ARG_ERROR, MSCOMP_DATA_ERROR, MSCOMP_MEM_ERROR, MSCOMP_BUF_ERROR, FORMATS, CHUNK,
                   MSCompError, load_library, max_compressed_size, compress, compress_units, compress_units_host, decompress_units_host, HostViews, pack_offsets, decompress, decompress_units, compact_batch,
                   Context, Plan, SizePlan, decompressed_sizes, decompress_units_auto, DevPlan, layout_dev,
-                  CompressDevPlan, plan_layout_dev, SizeDevPlan, compact_dev)
+                  CompressDevPlan, plan_layout_dev, SizeDevPlan, compact_dev,
+                  BlockContainer, blocks_compress, blocks_decompress)

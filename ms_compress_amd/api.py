@@ -39,6 +39,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_plan_create_compress_dev", "mscomp_amd_plan_layout_dev",
     "mscomp_amd_plan_create_size_dev", "mscomp_amd_plan_execute_size_dev", "mscomp_amd_compact_dev",
     "mscomp_amd_plan_create_decompress_dev_ex", "mscomp_amd_plan_create_size_dev_ex", "mscomp_amd_debug_plan_paths",
+    "mscomp_amd_blocks_create", "mscomp_amd_blocks_destroy", "mscomp_amd_blocks_bound", "mscomp_amd_blocks_compress", "mscomp_amd_blocks_decompress",
 ]
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 
@@ -130,6 +131,16 @@ def load_library():
     lib.mscomp_amd_plan_execute_size_dev.restype = C.c_int
     lib.mscomp_amd_compact_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.mscomp_amd_compact_dev.restype = C.c_int
+    lib.mscomp_amd_blocks_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_blocks_create.restype = C.c_int
+    lib.mscomp_amd_blocks_destroy.argtypes = [C.c_void_p]
+    lib.mscomp_amd_blocks_destroy.restype = None
+    lib.mscomp_amd_blocks_bound.argtypes = [C.c_void_p]
+    lib.mscomp_amd_blocks_bound.restype = C.c_uint64
+    lib.mscomp_amd_blocks_compress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mscomp_amd_blocks_compress.restype = C.c_int
+    lib.mscomp_amd_blocks_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9
+    lib.mscomp_amd_blocks_decompress.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -419,6 +430,134 @@ class SizeDevPlan(DevPlan):
         st = self.ctx.lib.mscomp_amd_plan_execute_size_dev(self._h, *ptrs)
         if st != MSCOMP_OK:
             raise MSCompError(st, "mscomp_amd_plan_execute_size_dev")
+
+
+class BlockContainer:
+    """A block container (mscomp_amd_blocks_create): resources cut into blocks of ``block_size`` bytes (a power of two, 4096 .. 524288), every
+    block compressed on its own or stored raw when it does not shrink, the stored blocks packed back to back behind an offset table. Made
+    once for ``n_res`` resources whose lengths sum to at most ``in_total_max``; ``n_blocks_max`` = n_res + in_total_max // block_size bounds
+    the blocks of a batch. All scratch is reserved here: two inner dev plans, 64 bytes of tables per possible block, and a staging area of
+    1 byte per byte of in_total_max + 16 per resource. Both calls enqueue kernels on the ctx stream and nothing else (nothing is
+    synchronized or read back; legal inside a capture of that stream). Arguments are torch CUDA tensors: uint8 data, int64 / uint64 tables,
+    int32 statuses."""
+
+    def __init__(self, ctx, fmt, block_size, n_res, in_total_max):
+        self.ctx, self.fmt, self.block_size = ctx, int(fmt), int(block_size)
+        self.n_res, self.in_total_max = int(n_res), int(in_total_max)
+        self._h = C.c_void_p()
+        st = ctx.lib.mscomp_amd_blocks_create(ctx._h, self.fmt, self.block_size, self.n_res, self.in_total_max, 0, C.byref(self._h))
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_blocks_create")
+        self.n_blocks_max = int(ctx.lib.mscomp_amd_blocks_bound(self._h))
+
+    def compress(self, d_in, d_res_off, d_res_len, d_packed, d_block_first, d_block_off, d_status, packed_cap=None):
+        """Resource r = d_res_len[r] bytes at d_in + d_res_off[r] (n_res entries each). Writes d_block_first (n_res + 1: the running count
+        of blocks), d_block_off (n_blocks_max + 1: the running sum of the stored lengths, the entries behind the last block repeating the
+        total), the stored blocks to d_packed[0 .. total) and d_status (n_res). Nothing is written at or behind ``packed_cap`` (default:
+        all of d_packed); a block that would end beyond it is left out and its resource gets MSCOMP_BUF_ERROR."""
+        cap = d_packed.numel() if packed_cap is None else int(packed_cap)
+        if cap > d_packed.numel():
+            raise ValueError("packed_cap exceeds d_packed")
+        p = [C.c_void_p(t.data_ptr()) for t in (d_in, d_res_off, d_res_len, d_packed, d_block_first, d_block_off, d_status)]
+        st = self.ctx.lib.mscomp_amd_blocks_compress(self._h, p[0], p[1], p[2], p[3], cap, p[4], p[5], p[6])
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_blocks_compress")
+
+    def decompress(self, d_packed, d_block_first, d_block_off, d_res_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_range=None,
+                   packed_len=None):
+        """Decodes, per resource, the blocks of ``d_range`` (2 x n_res: first block, count; both clipped; None = every block) to
+        d_out + d_out_off[r], at most d_out_cap[r] bytes. d_status[r] is MSCOMP_OK with d_out_len[r] = the bytes the range stands for,
+        MSCOMP_ARG_ERROR (beyond the creation bounds), MSCOMP_DATA_ERROR (a damaged table or payload) or MSCOMP_BUF_ERROR (capacity), with
+        d_out_len[r] = 0. ``packed_len``: the valid bytes of d_packed (default: all of it)."""
+        plen = d_packed.numel() if packed_len is None else int(packed_len)
+        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_packed, d_block_first, d_block_off, d_res_len, d_range, d_out, d_out_off,
+                                                                         d_out_cap, d_out_len, d_status)]
+        st = self.ctx.lib.mscomp_amd_blocks_decompress(self._h, p[0], plen, *p[1:])
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_blocks_decompress")
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.mscomp_amd_blocks_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def blocks_compress(fmt, buffers, block_size, ctx=None):
+    """The block container of a list of byte strings (one resource each), built on the GPU. Returns numpy arrays (packed uint8, block_first
+    uint64 of n + 1, block_off uint64 of nb + 1, statuses int32): block j of resource r is
+    packed[block_off[block_first[r] + j] : block_off[block_first[r] + j + 1]], the bytes of ms_compress for that block when they are
+    shorter than the block, the block itself otherwise."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    n = len(buffers)
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        d_in, in_off, lens = _upload_units(buffers, dev)
+        total = int(sum(lens))
+        bk = BlockContainer(ctx, fmt, block_size, n, total)
+        d_off = torch.from_numpy(np.ascontiguousarray(in_off, dtype=np.uint64).view(np.int64).copy()).to(dev) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        d_len = torch.tensor(lens or [0], dtype=torch.int64, device=dev)
+        d_packed = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
+        d_first = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_boff = torch.zeros(bk.n_blocks_max + 1, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        bk.compress(d_in, d_off, d_len, d_packed, d_first, d_boff, d_st, packed_cap=total)
+        ctx.stream.synchronize()
+        first = d_first.cpu().numpy().view(np.uint64).copy()
+        nb = int(first[n])
+        boff = d_boff.cpu().numpy().view(np.uint64)[: nb + 1].copy()
+        packed = d_packed.cpu().numpy()[: int(boff[nb])].copy()
+        st = d_st.cpu().numpy()[:n].copy()
+        bk.close()
+    if own:
+        ctx.close()
+    return packed, first, boff, st
+
+
+def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, ranges=None, ctx=None):
+    """Decode resources of a block container on the GPU: ``lengths`` are the resources' original lengths, ``ranges`` (optional) one
+    (first block, count) pair per resource, clipped to its blocks; default: whole resources. Returns (list of bytes, or None where the status
+    is not MSCOMP_OK; list of status)."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    n = len(lengths)
+    lens = [int(x) for x in lengths]
+    total = int(sum(lens))
+    out_off, out_total = pack_offsets(lens)
+    dev = torch.device("cuda", ctx.device)
+
+    def up(a, least):
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+        a = np.concatenate([a, np.full(max(0, least - len(a)), a[-1] if len(a) else 0, dtype=np.uint64)])
+        return torch.from_numpy(a.view(np.int64).copy()).to(dev)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        bk = BlockContainer(ctx, fmt, block_size, n, total)
+        packed = np.ascontiguousarray(np.frombuffer(bytes(packed), dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed, dtype=np.uint8)
+        d_packed = torch.zeros(len(packed) + 16, dtype=torch.uint8, device=dev)
+        if len(packed):
+            d_packed[: len(packed)] = torch.from_numpy(packed.copy()).to(dev)
+        d_first, d_boff = up(block_first, n + 1), up(block_off, bk.n_blocks_max + 1)
+        d_len, d_ooff, d_ocap = up(lens, 1), up(out_off, 1), up(lens, 1)
+        d_range = None if ranges is None else up(np.asarray(ranges, dtype=np.uint64).reshape(-1), 2)
+        d_out = torch.zeros(out_total + 16, dtype=torch.uint8, device=dev)
+        d_olen = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        bk.decompress(d_packed, d_first, d_boff, d_len, d_out, d_ooff, d_ocap, d_olen, d_st, d_range=d_range, packed_len=len(packed))
+        ctx.stream.synchronize()
+        h_out, h_len, h_st = d_out.cpu().numpy(), d_olen.cpu().numpy(), d_st.cpu().numpy()
+        bk.close()
+    res = [bytes(h_out[int(out_off[i]): int(out_off[i]) + int(h_len[i])]) if h_st[i] == MSCOMP_OK else None for i in range(n)]
+    if own:
+        ctx.close()
+    return res, [int(x) for x in h_st[:n]]
 
 
 def plan_paths(plan):

@@ -122,7 +122,7 @@ struct mscomp_amd_plan {
 	// the plan's launch sequence as a hipGraph (plan_run): captured on the plan's second execution, replayed while the
 	// arguments and the scratch buffers stay where they were
 	hipGraphExec_t gexec = nullptr;
-	const void* g_args[9] = {};                        // (a host plan's four pointers, a dev plan's eight, a size dev plan's seven)
+	const void* g_args[12] = {};                       // (a host plan's four pointers, a dev plan's eight, a size dev plan's seven; a block container's eight and eleven)
 	uint64_t g_epoch = 0, g_mode = 0;
 	uint32_t executions = 0;
 	bool ran = false;                                  // executed at least once (mscomp_amd_debug_plan_paths: a dev plan's counts are those of its last execution)
@@ -716,9 +716,10 @@ static void compress_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_
 // per-kernel events are not part of a graph), with MSCOMP_AMD_NO_GRAPH, for no_graph plans, and while the caller captures the ctx stream (the
 // launches then go into the caller's graph; a stream whose capture state cannot be read counts as captured). Only executions that may replay
 // are counted.
-extern "C++" template <class Launch>
-static MSCompStatus plan_run(mscomp_amd_plan* p, const void* const (&args)[9], const Launch& launch)
+extern "C++" template <class Launch, size_t N>
+static MSCompStatus plan_run(mscomp_amd_plan* p, const void* const (&args)[N], const Launch& launch)
 {
+	static_assert(N <= sizeof p->g_args / sizeof p->g_args[0], "g_args holds the arguments of every caller");
 	mscomp_amd_ctx* c = p->ctx;
 	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
 	if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
@@ -1051,6 +1052,26 @@ MSCompStatus mscomp_amd_plan_create_compress_dev(mscomp_amd_ctx* c, MSCompFormat
 	return MSCOMP_OK;
 }
 
+// The launches of one execution of a compress or decompress dev plan: mscomp_amd_plan_execute_dev runs them through plan_run, a block
+// container inside its own sequence (it is that call's plan_run, or the caller's capture, that may turn them into a graph).
+static void dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                       uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+{
+	mscomp_amd_ctx* c = p->ctx;
+	u64* san = static_cast<u64*>(p->tables.p); uint32_t* chunk_prefix = const_cast<uint32_t*>(p->bt.chunk_prefix);
+	const int f = (int)p->format; const uint32_t n = p->n_units;
+	if (p->decompress) {
+		{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_tables(c->stream, f, n, p->in_total_max, p->out_total_max, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, p->tok_prefix, p->reject); }
+		run_dev_paths(p);
+		decode_launch(p, d_in, d_out, d_out_len, d_status);
+	} else {
+		{ KernelTimer t(c, "dv_ctables_kernel"); launch_dev_ctables(c->stream, f, n, p->in_total_max, p->max_unit, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, p->reject); }
+		compress_launch(p, d_in, d_out, d_out_len, d_status);
+	}
+	// the units the table pass rejected (the kernels saw them as empty units without room)
+	{ KernelTimer t(c, "dv_reject_kernel"); launch_dev_reject(c->stream, p->reject, n, d_out_len, d_status); }
+}
+
 MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                          uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
 {
@@ -1065,20 +1086,7 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in
 	if (p->decompress) { note_modes(p); }
 	p->ran = true;
 	const void* args[9] = { d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status };
-	return plan_run(p, args, [&] {
-		u64* san = static_cast<u64*>(p->tables.p); uint32_t* chunk_prefix = const_cast<uint32_t*>(p->bt.chunk_prefix);
-		const int f = (int)p->format; const uint32_t n = p->n_units;
-		if (p->decompress) {
-			{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_tables(c->stream, f, n, p->in_total_max, p->out_total_max, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, p->tok_prefix, p->reject); }
-			run_dev_paths(p);
-			decode_launch(p, d_in, d_out, d_out_len, d_status);
-		} else {
-			{ KernelTimer t(c, "dv_ctables_kernel"); launch_dev_ctables(c->stream, f, n, p->in_total_max, p->max_unit, d_in_off, d_in_len, d_out_off, d_out_cap, san, chunk_prefix, p->reject); }
-			compress_launch(p, d_in, d_out, d_out_len, d_status);
-		}
-		// the units the table pass rejected (the kernels saw them as empty units without room)
-		{ KernelTimer t(c, "dv_reject_kernel"); launch_dev_reject(c->stream, p->reject, n, d_out_len, d_status); }
-	});
+	return plan_run(p, args, [&] { dev_launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status); });
 }
 
 MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -1174,6 +1182,118 @@ MSCompStatus mscomp_amd_compact_dev(mscomp_amd_ctx* c, size_t n_units, const uin
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	launch_compact_dev(c->stream, (uint32_t)n_units, d_src, d_src_off, d_len, align, d_packed, packed_cap, d_packed_off, c->cpd_blocks);
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
+}
+
+// ---- block containers (include/mscomp_amd.h; kernels: blocks.hip) ----
+// A container owns two inner dev plans over blocks as units -- compress: n_blocks_max units of at most block_size bytes; decompress: the same
+// number of units within in_total_max bytes on either side --, a staging area for the compressed blocks and its own tables. Its two calls
+// run the inner plans' launches (dev_launch) between their own passes, through plan_run with a record of their own (crun / drun: plans that
+// hold nothing but the graph of the call), so the inner plans never capture: the graph is the call's, or the caller's.
+struct mscomp_amd_blocks {
+	mscomp_amd_ctx* ctx = nullptr;
+	MSCompFormat format = MSCOMP_NONE;
+	uint32_t shift = 0, n_res = 0, n_blocks = 0;       // block_size = 1 << shift; n_blocks = n_blocks_max
+	uint64_t in_total_max = 0;
+	mscomp_amd_plan* cplan = nullptr; mscomp_amd_plan* dplan = nullptr;   // (null when n_blocks is 0)
+	mscomp_amd_plan crun, drun;
+	DevBuf tab, stage;                                 // BlocksTab; staged compressed blocks: in_total_max + 16 n_res bytes
+	BlocksTab t{};
+};
+
+static void blocks_tab(mscomp_amd_blocks* b)
+{
+	const size_t n = b->n_res, m = b->n_blocks;
+	u64* q = static_cast<u64*>(b->tab.p);
+	BlocksTab& t = b->t;
+	t.res_a = q; t.res_b = q + n; t.unit_first = q + 2 * n; q += 3 * n + 1;
+	t.in_off = q; t.in_len = q + m; t.out_off = q + 2 * m; t.out_cap = q + 3 * m; t.ulen = q + 4 * m; t.aux_a = q + 5 * m; t.aux_b = q + 6 * m; q += 7 * m;
+	t.rstat = reinterpret_cast<int32_t*>(q); t.ustat = t.rstat + n; t.act = reinterpret_cast<uint32_t*>(t.ustat + m);
+}
+
+MSCompStatus mscomp_amd_blocks_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t in_total_max, uint32_t flags,
+                                      mscomp_amd_blocks** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || n_res > 0x7FFFFFF0u || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
+	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	const uint64_t by_bytes = in_total_max / block_size;
+	if (by_bytes > 0x7FFFFFF0ull - n_res) { return MSCOMP_MEM_ERROR; }   // (checked before the context is used; in_total_max < 2^50 from here on)
+	const uint64_t M = n_res + by_bytes;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_blocks> b(new (std::nothrow) mscomp_amd_blocks());
+	if (!b) { return MSCOMP_MEM_ERROR; }
+	b->ctx = c; b->format = format; b->shift = (uint32_t)__builtin_ctz(block_size); b->n_res = (uint32_t)n_res; b->n_blocks = (uint32_t)M; b->in_total_max = in_total_max;
+	b->crun.ctx = b->drun.ctx = c; b->crun.n_units = b->drun.n_units = (uint32_t)n_res;
+	MSCompStatus st = MSCOMP_OK;
+	if (!b->tab.reserve((3 * n_res + 1 + 7 * M) * 8 + (n_res + 2 * M) * 4 + 64) || !b->stage.reserve(in_total_max + 16 * (uint64_t)n_res + 64)) { st = MSCOMP_MEM_ERROR; }
+	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_compress_dev(c, format, M, in_total_max, block_size, &b->cplan); }
+	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, in_total_max, in_total_max, &b->dplan); }
+	if (st != MSCOMP_OK) {
+		(void)hipGetLastError();
+		mscomp_amd_plan_destroy(b->cplan); mscomp_amd_plan_destroy(b->dplan);
+		b->tab.release(); b->stage.release();
+		return st;
+	}
+	blocks_tab(b.get());
+	*out = b.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_blocks_destroy(mscomp_amd_blocks* b)
+{
+	if (!b) { return; }
+	DeviceGuard g(b->ctx->device);
+	(void)hipStreamSynchronize(b->ctx->stream);
+	mscomp_amd_plan_destroy(b->cplan); mscomp_amd_plan_destroy(b->dplan);
+	b->tab.release(); b->stage.release();
+	delete b;                                              // (crun / drun give up their graphs)
+}
+
+uint64_t mscomp_amd_blocks_bound(const mscomp_amd_blocks* b) { return b ? b->n_blocks : 0; }
+
+MSCompStatus mscomp_amd_blocks_compress(mscomp_amd_blocks* b, const uint8_t* d_in, const uint64_t* d_res_off, const uint64_t* d_res_len,
+                                        uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_block_first, uint64_t* d_block_off, int32_t* d_status)
+{
+	if (!b || !d_block_first || !d_block_off || (b->n_res && (!d_res_off || !d_res_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (b->in_total_max && (!d_in || !d_packed)) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = b->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (b->cplan) { b->cplan->ran = true; }
+	const void* args[8] = { d_in, d_res_off, d_res_len, d_packed, reinterpret_cast<const void*>((uintptr_t)packed_cap), d_block_first, d_block_off, d_status };
+	return plan_run(&b->crun, args, [&] {
+		const BlocksTab& t = b->t;
+		uint8_t* stage = static_cast<uint8_t*>(b->stage.p);
+		{ KernelTimer k(c, "bk_ctables"); launch_blocks_ctables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_off, d_res_len, d_block_first, t); }
+		if (b->cplan) { dev_launch(b->cplan, d_in, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		{ KernelTimer k(c, "bk_select_kernel"); launch_blocks_select(c->stream, b->n_res, b->n_blocks, packed_cap, d_in, stage, d_block_first, t, d_block_off, d_status); }
+		{ KernelTimer k(c, "cpd_copy_kernel"); launch_pack_ptrs(c->stream, b->n_blocks, t.aux_b, t.aux_a, d_block_off, d_packed, packed_cap, c->cpd_blocks); }
+	});
+}
+
+MSCompStatus mscomp_amd_blocks_decompress(mscomp_amd_blocks* b, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
+                                          const uint64_t* d_block_off, const uint64_t* d_res_len, const uint64_t* d_range,
+                                          uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!b || !d_block_first || !d_block_off || (b->n_res && (!d_res_len || !d_out_off || !d_out_cap || !d_out_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (b->in_total_max && (!d_packed || !d_out)) { return MSCOMP_ARG_ERROR; }
+	if (b->n_res == 0) { return MSCOMP_OK; }               // (nothing to report on)
+	mscomp_amd_ctx* c = b->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (b->dplan) { note_modes(b->dplan); b->dplan->ran = true; }
+	const void* args[11] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_range,
+	                         d_out, d_out_off, d_out_cap, d_out_len, d_status };
+	return plan_run(&b->drun, args, [&] {
+		const BlocksTab& t = b->t;
+		{ KernelTimer k(c, "bk_dtables"); launch_blocks_dtables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, packed_len, d_res_len, d_block_first, d_block_off,
+		                                                        d_range, d_out_off, d_out_cap, t); }
+		if (b->dplan) { dev_launch(b->dplan, d_packed, t.in_off, t.in_len, d_out, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		{ KernelTimer k(c, "bk_rawcopy_kernel"); launch_blocks_rawcopy(c->stream, b->n_blocks, b->shift, d_packed, d_out, t, c->cpd_blocks); }
+		{ KernelTimer k(c, "bk_dfold_kernel"); launch_blocks_dfold(c->stream, b->n_res, t, d_out_len, d_status); }
+	});
 }
 
 // Stage-level test hook: per-position (len-3 capped at 45, offset) of ONE unit as found by the HIP match finder.

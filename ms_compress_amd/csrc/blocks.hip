@@ -1,0 +1,257 @@
+// blocks.hip -- the table, select, raw-copy and fold passes of a block container (mscomp_amd_blocks_*, include/mscomp_amd.h): a batch of
+// resources cut into blocks of B = 1 << shift bytes, every block compressed on its own or stored raw, packed back to back behind a table of
+// offsets. The two big stages are a compress and a decompress dev plan over the blocks as units (api.hip runs them between these passes,
+// unchanged); the pack pass is compaction's copy with a source address per unit (devplan.hip cpd_copy_kernel<true>). DESIGN.md 4.7.
+#include "kernels.h"
+
+namespace msc {
+
+// largest r with first[r] <= b (first[0] = 0 <= b < first[n]): the resource that holds block b; empty resources in front of it are skipped
+__device__ __forceinline__ uint32_t res_of_block(const u64* __restrict__ first, uint32_t n, u64 b)
+{
+	uint32_t lo = 0, hi = n;
+	while (hi - lo > 1) {
+		const uint32_t mid = lo + ((hi - lo) >> 1);
+		if (first[mid] <= b) { lo = mid; } else { hi = mid; }
+	}
+	return lo;
+}
+
+// ---- compress ----
+// One block walks the resources in tiles of 1024: the bounds check (running total of res_len <= in_max; a rejected resource has no blocks),
+// block_first (n + 1), and where the resource's compressed blocks are staged: resources back to back in block order, every start rounded up
+// to 16, block j at + j * B -- so the staging area is in_max + 16 n bytes whatever the mix of lengths.
+__global__ __launch_bounds__(DV_THREADS) void bk_cres_kernel(uint32_t n, uint32_t shift, u64 in_max, const u64* __restrict__ res_len,
+                                                            u64* __restrict__ block_first, u64* __restrict__ stage_base, int32_t* __restrict__ rstat)
+{
+	__shared__ u64 s_w[2][DV_WAVES];
+	const uint32_t tid = threadIdx.x;
+	const u64 B = (u64)1 << shift;
+	u64 run[1] = {0}, cnt[2] = {0, 0};
+	if (tid == 0) { block_first[0] = 0; }
+	for (uint32_t base = 0; base < n; base += DV_THREADS) {
+		const uint32_t i = base + tid;
+		const bool live = i < n;
+		const u64 len = live ? res_len[i] : 0;
+		u64 r[1] = {len};
+		dv_block_scan<1>(r, run, s_w);                                   // running total up to and including resource i
+		const bool rej = live && r[0] > in_max;
+		const u64 L = rej ? 0 : len, room = (L + 15u) & ~(u64)15u;       // (L <= in_max < 2^50, mscomp_amd_blocks_create: no overflow)
+		u64 c[2] = {(L + B - 1u) >> shift, room};
+		dv_block_scan<2>(c, cnt, s_w);
+		if (live) { block_first[i + 1u] = c[0]; stage_base[i] = c[1] - room; rstat[i] = rej ? -2 : 0; }   // MSCOMP_ARG_ERROR
+	}
+}
+
+// The inner compress plan's unit tables, one thread per possible block: input res_off + j B, staging capacity len - 1 (a block that does not
+// shrink is MSCOMP_BUF_ERROR there, and is stored raw). Blocks at or past the real count are empty units without room.
+__global__ __launch_bounds__(256) void bk_cunits_kernel(uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* __restrict__ res_off, const u64* __restrict__ res_len,
+                                                       const u64* __restrict__ block_first, const u64* __restrict__ stage_base,
+                                                       u64* __restrict__ in_off, u64* __restrict__ in_len, u64* __restrict__ out_off, u64* __restrict__ out_cap)
+{
+	const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+	if (b >= nbmax) { return; }
+	const u64 B = (u64)1 << shift;
+	u64 io = 0, il = 0, oo = 0, oc = 0;
+	if (b < block_first[n_res]) {
+		const uint32_t r = res_of_block(block_first, n_res, b);
+		const u64 at = (b - block_first[r]) << shift, left = res_len[r] - at;
+		io = res_off[r] + at; il = left < B ? left : B; oo = stage_base[r] + at; oc = il - 1u;
+	}
+	in_off[b] = io; in_len[b] = il; out_off[b] = oo; out_cap[b] = oc;
+}
+
+// Select, scan and status in one block: per block the stored form (the staged bytes when the inner plan fitted them into len - 1, the raw
+// input otherwise) as a length and a source address, block_off (nbmax + 1; the entries behind the real count repeat the total), and then
+// per resource MSCOMP_ARG_ERROR / MSCOMP_BUF_ERROR (its last block ends beyond cap: the pack pass leaves such blocks out) / MSCOMP_OK.
+__global__ __launch_bounds__(DV_THREADS) void bk_select_kernel(uint32_t n_res, uint32_t nbmax, u64 cap, const uint8_t* __restrict__ d_in, const uint8_t* __restrict__ stage,
+                                                              const u64* __restrict__ block_first, const u64* __restrict__ in_off, const u64* __restrict__ in_len,
+                                                              const u64* __restrict__ st_off, const u64* __restrict__ clen, const int32_t* __restrict__ cstat,
+                                                              u64* __restrict__ slen, u64* __restrict__ src, u64* block_off,
+                                                              const int32_t* __restrict__ rstat, int32_t* __restrict__ d_status)
+{
+	__shared__ u64 s_w[1][DV_WAVES];
+	const uint32_t tid = threadIdx.x;
+	u64 run[1] = {0};
+	if (tid == 0) { block_off[0] = 0; }
+	for (uint32_t base = 0; base < nbmax; base += DV_THREADS) {
+		const uint32_t b = base + tid;
+		const bool live = b < nbmax;
+		const u64 L = live ? in_len[b] : 0;                               // (0 behind the real count)
+		const bool comp = L != 0 && cstat[b] == 0 && clen[b] < L;
+		u64 v[1] = {comp ? clen[b] : L};
+		const u64 s = v[0];
+		dv_block_scan<1>(v, run, s_w);
+		if (live) {
+			block_off[b + 1u] = v[0]; slen[b] = s;
+			src[b] = L == 0 ? 0 : (u64)(uintptr_t)(comp ? stage + st_off[b] : d_in + in_off[b]);
+		}
+	}
+	__syncthreads();                                                     // block_off is read back below, by other threads of this block
+	for (uint32_t r = tid; r < n_res; r += DV_THREADS) {
+		int32_t st = rstat[r];
+		const u64 f0 = block_first[r], f1 = block_first[r + 1u];
+		if (st == 0 && f1 > f0 && block_off[f1] > cap) { st = -5; }      // MSCOMP_BUF_ERROR (the offsets only grow: the last block tells)
+		d_status[r] = st;
+	}
+}
+
+// ---- decompress ----
+#define BK_SKIP   0u
+#define BK_COPY   1u
+#define BK_DECODE 2u
+#define BK_FAIL   3u                                      // (the action word of a unit: kind | data length << 2)
+
+// One block walks the resources: the per-resource checks in their order (bounds -> MSCOMP_ARG_ERROR, block count -> MSCOMP_DATA_ERROR,
+// capacity -> MSCOMP_BUF_ERROR), the clipped range and the bytes it stands for, and unit_first (n + 1): the inner plan's units are the
+// blocks IN RANGE of the resources that passed, numbered densely in resource order -- a numbering that is this pass's own running sum,
+// so that a damaged block_first cannot make two resources share a unit or send the search below astray.
+__global__ __launch_bounds__(DV_THREADS) void bk_dres_kernel(uint32_t n, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* __restrict__ res_len,
+                                                            const u64* __restrict__ block_first, const u64* __restrict__ range, const u64* __restrict__ out_cap,
+                                                            u64* __restrict__ unit_first, u64* __restrict__ rf, u64* __restrict__ want, int32_t* __restrict__ rstat)
+{
+	__shared__ u64 s_w[1][DV_WAVES];
+	const uint32_t tid = threadIdx.x;
+	const u64 B = (u64)1 << shift;
+	u64 run[1] = {0}, cnt[1] = {0};
+	if (tid == 0) { unit_first[0] = 0; }
+	for (uint32_t base = 0; base < n; base += DV_THREADS) {
+		const uint32_t i = base + tid;
+		const bool live = i < n;
+		const u64 len = live ? res_len[i] : 0;
+		u64 r[1] = {len};
+		dv_block_scan<1>(r, run, s_w);
+		int32_t st = 0;
+		u64 f = 0, c = 0, w = 0;
+		if (live) {
+			const u64 f0 = block_first[i], f1 = block_first[i + 1u];
+			if (r[0] > in_max || f0 > nbmax || f1 > nbmax) { st = -2; }
+			else {
+				const u64 nblk = (len + B - 1u) >> shift;
+				if (f1 - f0 != nblk) { st = -3; }
+				else {
+					const u64 qf = range ? range[2u * (size_t)i] : 0, qc = range ? range[2u * (size_t)i + 1u] : nblk;
+					f = qf < nblk ? qf : nblk; c = qc < nblk - f ? qc : nblk - f;
+					if (c) { const u64 end = (f + c) << shift; w = (len < end ? len : end) - (f << shift); }
+					if (w > out_cap[i]) { st = -5; }
+				}
+			}
+		}
+		u64 k[1] = {st == 0 ? c : 0};
+		dv_block_scan<1>(k, cnt, s_w);
+		if (live) { unit_first[i + 1u] = k[0]; rf[i] = f; want[i] = w; rstat[i] = st; }
+	}
+}
+
+// The inner decompress plan's unit tables and the action words, one thread per possible unit. A block whose stored length s equals its data
+// length e is copied, 0 < s < e is decoded into capacity e at its final place; everything else -- a decreasing table, an end beyond
+// packed_len, s > e, s = 0 -- fails the resource without a byte of the block being read. Only blocks to decode reach the inner plan with a
+// length; all other units are empty there, with capacity 0.
+__global__ __launch_bounds__(256) void bk_dunits_kernel(uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 packed_len, const u64* __restrict__ res_len,
+                                                       const u64* __restrict__ block_first, const u64* __restrict__ block_off, const u64* __restrict__ d_out_off,
+                                                       const u64* __restrict__ unit_first, const u64* __restrict__ rf,
+                                                       u64* __restrict__ in_off, u64* __restrict__ in_len, u64* __restrict__ out_off, u64* __restrict__ out_cap,
+                                                       u64* __restrict__ raw_src, u64* __restrict__ raw_dst, uint32_t* __restrict__ act)
+{
+	const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+	if (u >= nbmax) { return; }
+	const u64 B = (u64)1 << shift;
+	u64 io = 0, il = 0, oo = 0, oc = 0, rs = 0, rd = 0;
+	uint32_t a = BK_SKIP;
+	if (u < unit_first[n_res]) {
+		const uint32_t r = res_of_block(unit_first, n_res, u);
+		const u64 k = u - unit_first[r], jb = rf[r] + k, j = block_first[r] + jb;    // (j < block_first[r + 1] <= nbmax: bk_dres_kernel)
+		const u64 left = res_len[r] - (jb << shift), e = left < B ? left : B;
+		const u64 o0 = block_off[j], o1 = block_off[j + 1u], dst = d_out_off[r] + (k << shift);
+		if (o1 < o0 || o1 > packed_len) { a = BK_FAIL; }
+		else {
+			const u64 s = o1 - o0;
+			if (s == e) { a = BK_COPY; rs = o0; rd = dst; }
+			else if (s != 0 && s < e) { a = BK_DECODE; io = o0; il = s; oo = dst; oc = e; }
+			else { a = BK_FAIL; }
+		}
+		a |= (uint32_t)e << 2;                                             // (e <= 512 KiB)
+	}
+	in_off[u] = io; in_len[u] = il; out_off[u] = oo; out_cap[u] = oc; raw_src[u] = rs; raw_dst[u] = rd; act[u] = a;
+}
+
+// The raw blocks to their places, in pieces of 16 KiB handed out round robin to a grid fixed by the CU count: one 512 KiB block is moved by
+// 32 workgroups, and a unit that is not a raw block costs one load of its action word per piece it could have had.
+#define BK_PIECE_SHIFT 14u
+__global__ __launch_bounds__(CPD_THREADS) void bk_rawcopy_kernel(uint32_t nbmax, uint32_t ppu_shift, const uint8_t* __restrict__ packed, uint8_t* __restrict__ out,
+                                                                const u64* __restrict__ raw_src, const u64* __restrict__ raw_dst, const uint32_t* __restrict__ act)
+{
+	const u64 items = (u64)nbmax << ppu_shift;
+	for (u64 i = blockIdx.x; i < items; i += gridDim.x) {
+		const uint32_t u = (uint32_t)(i >> ppu_shift), a = act[u];
+		const u64 at = (i & (((u64)1 << ppu_shift) - 1u)) << BK_PIECE_SHIFT, e = a >> 2;
+		if ((a & 3u) != BK_COPY || at >= e) { continue; }
+		const u64 cnt = e - at < ((u64)1 << BK_PIECE_SHIFT) ? e - at : (u64)1 << BK_PIECE_SHIFT;
+		cpd_move<false>(out + raw_dst[u] + at, packed + raw_src[u] + at, cnt, threadIdx.x);
+	}
+}
+
+// One wave per resource: its units' verdicts (a failed table check; a decoder status other than MSCOMP_OK or a length other than e) folded
+// behind the resource's own, into d_status and d_out_len.
+__global__ __launch_bounds__(256) void bk_dfold_kernel(uint32_t n_res, const u64* __restrict__ unit_first, const uint32_t* __restrict__ act,
+                                                      const u64* __restrict__ dlen, const int32_t* __restrict__ dstat, const int32_t* __restrict__ rstat,
+                                                      const u64* __restrict__ want, u64* __restrict__ d_out_len, int32_t* __restrict__ d_status)
+{
+	const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+	if (r >= n_res) { return; }
+	const int32_t st = rstat[r];
+	bool bad = false;
+	if (st == 0) {
+		for (u64 u = unit_first[r] + lane; u < unit_first[r + 1u]; u += 64u) {
+			const uint32_t a = act[u], kind = a & 3u;
+			if (kind == BK_FAIL || (kind == BK_DECODE && (dstat[u] != 0 || dlen[u] != (u64)(a >> 2)))) { bad = true; }
+		}
+	}
+	const bool any_bad = __ballot(bad) != 0;
+	if (lane == 0) {
+		const int32_t s = st != 0 ? st : any_bad ? -3 : 0;                 // MSCOMP_DATA_ERROR
+		d_status[r] = s; d_out_len[r] = s == 0 ? want[r] : 0;
+	}
+}
+
+void launch_blocks_ctables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* res_off, const u64* res_len,
+                           u64* block_first, const BlocksTab& t)
+{
+	hipLaunchKernelGGL(bk_cres_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_res, shift, in_max, res_len, block_first, t.res_a, t.rstat);
+	if (nbmax == 0) { return; }
+	hipLaunchKernelGGL(bk_cunits_kernel, dim3((nbmax + 255u) / 256u), dim3(256), 0, st, n_res, nbmax, shift, res_off, res_len, block_first, t.res_a,
+	                   t.in_off, t.in_len, t.out_off, t.out_cap);
+}
+
+void launch_blocks_select(hipStream_t st, uint32_t n_res, uint32_t nbmax, u64 cap, const uint8_t* d_in, const uint8_t* stage, const u64* block_first,
+                          const BlocksTab& t, u64* block_off, int32_t* d_status)
+{
+	hipLaunchKernelGGL(bk_select_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_res, nbmax, cap, d_in, stage, block_first, t.in_off, t.in_len, t.out_off,
+	                   t.ulen, t.ustat, t.aux_a, t.aux_b, block_off, t.rstat, d_status);
+}
+
+void launch_blocks_dtables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, u64 packed_len, const u64* res_len,
+                           const u64* block_first, const u64* block_off, const u64* range, const u64* d_out_off, const u64* d_out_cap, const BlocksTab& t)
+{
+	hipLaunchKernelGGL(bk_dres_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_res, nbmax, shift, in_max, res_len, block_first, range, d_out_cap,
+	                   t.unit_first, t.res_b, t.res_a, t.rstat);
+	if (nbmax == 0) { return; }
+	hipLaunchKernelGGL(bk_dunits_kernel, dim3((nbmax + 255u) / 256u), dim3(256), 0, st, n_res, nbmax, shift, packed_len, res_len, block_first, block_off, d_out_off,
+	                   t.unit_first, t.res_b, t.in_off, t.in_len, t.out_off, t.out_cap, t.aux_a, t.aux_b, t.act);
+}
+
+void launch_blocks_rawcopy(hipStream_t st, uint32_t nbmax, uint32_t shift, const uint8_t* packed, uint8_t* out, const BlocksTab& t, uint32_t blocks)
+{
+	if (nbmax == 0) { return; }
+	const uint32_t ppu_shift = shift > BK_PIECE_SHIFT ? shift - BK_PIECE_SHIFT : 0u;
+	const u64 items = (u64)nbmax << ppu_shift;
+	hipLaunchKernelGGL(bk_rawcopy_kernel, dim3((uint32_t)(items < blocks ? items : blocks)), dim3(CPD_THREADS), 0, st, nbmax, ppu_shift, packed, out, t.aux_a, t.aux_b, t.act);
+}
+
+void launch_blocks_dfold(hipStream_t st, uint32_t n_res, const BlocksTab& t, u64* d_out_len, int32_t* d_status)
+{
+	if (n_res == 0) { return; }
+	hipLaunchKernelGGL(bk_dfold_kernel, dim3((n_res + 3u) / 4u), dim3(256), 0, st, n_res, t.unit_first, t.act, t.ulen, t.ustat, t.rstat, t.res_a, d_out_len, d_status);
+}
+
+} // namespace msc

@@ -219,4 +219,77 @@ __device__ __forceinline__ void copy_from_aligned(uint8_t* __restrict__ dst, con
 	for (uint32_t i = head + body * 4u + tid; i < n; i += nthr) { dst[i] = src[i]; }
 }
 
+// ---- shared by devplan.hip and blocks.hip: the table passes' block scan, and the 16-byte-lane copy of compaction ----
+#define DV_THREADS 1024u
+#define DV_WAVES   (DV_THREADS / 64u)
+
+__device__ __forceinline__ u64 sat_add(u64 a, u64 b) { const u64 s = a + b; return s < a ? ~(u64)0 : s; }
+
+// Inclusive scan of K values per thread over the block (saturating add: associative, so the order of the partial sums does not matter),
+// continued from carry; carry becomes carry + the tile's total in every thread.
+template <int K>
+__device__ __forceinline__ void dv_block_scan(u64 (&v)[K], u64 (&carry)[K], u64 (*s_w)[DV_WAVES])
+{
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+	#pragma unroll
+	for (int k = 0; k < K; ++k) {
+		#pragma unroll
+		for (uint32_t d = 1; d < 64u; d <<= 1) { const u64 o = __shfl_up(v[k], d, 64); if (lane >= d) { v[k] = sat_add(v[k], o); } }
+		if (lane == 63u) { s_w[k][w] = v[k]; }
+	}
+	__syncthreads();
+	#pragma unroll
+	for (int k = 0; k < K; ++k) {
+		u64 before = carry[k], tot = carry[k];
+		for (uint32_t i = 0; i < DV_WAVES; ++i) { if (i < w) { before = sat_add(before, s_w[k][i]); } tot = sat_add(tot, s_w[k][i]); }
+		v[k] = sat_add(v[k], before);
+		carry[k] = tot;
+	}
+	__syncthreads();
+}
+
+#define CPD_THREADS 256u
+struct __attribute__((packed)) cpd_u16 { uint32_t w[4]; };  // 16 bytes of alignment 1
+
+template <bool ZERO>
+__device__ __forceinline__ void cpd_move(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, u64 cnt, uint32_t tid)
+{
+	u64 head = (16u - ((uintptr_t)dst & 15u)) & 15u;
+	if (head > cnt) { head = cnt; }
+	const u64 body = (cnt - head) >> 4, tail0 = head + body * 16u;
+	const bool has_head = tid < head, has_tail = tid >= 64u && tail0 + (tid - 64u) < cnt;   // (the tail on the second wave: at most 15 bytes)
+	uint4* __restrict__ d16 = reinterpret_cast<uint4*>(dst + head);
+	if (ZERO) {
+		if (has_head) { dst[tid] = 0; }
+		if (has_tail) { dst[tail0 + (tid - 64u)] = 0; }
+		for (u64 k = tid; k < body; k += CPD_THREADS) { d16[k] = make_uint4(0, 0, 0, 0); }
+		return;
+	}
+	// every load of a step before its stores: a piece of up to 16 KiB + 30 bytes costs one round trip to memory, not one per access
+	const uint8_t hb = has_head ? src[tid] : (uint8_t)0, tb = has_tail ? src[tail0 + (tid - 64u)] : (uint8_t)0;
+	const bool same = (((uintptr_t)src + head) & 15u) == 0;              // source and destination aligned alike: 16-byte loads
+	const uint4* __restrict__ sa = reinterpret_cast<const uint4*>(src + head);
+	const cpd_u16* __restrict__ su = reinterpret_cast<const cpd_u16*>(src + head);
+	for (u64 k0 = 0; k0 < body || k0 == 0; k0 += 4u * CPD_THREADS) {
+		uint4 v[4];
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) {
+			const u64 k = k0 + j * CPD_THREADS + tid;
+			if (k < body) {
+				if (same) { v[j] = sa[k]; }
+				else { const cpd_u16 t = su[k]; v[j] = make_uint4(t.w[0], t.w[1], t.w[2], t.w[3]); }
+			}
+		}
+		if (k0 == 0) {
+			if (has_head) { dst[tid] = hb; }
+			if (has_tail) { dst[tail0 + (tid - 64u)] = tb; }
+		}
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) {
+			const u64 k = k0 + j * CPD_THREADS + tid;
+			if (k < body) { d16[k] = v[j]; }
+		}
+	}
+}
+
 } // namespace msc

@@ -6,34 +6,6 @@
 
 namespace msc {
 
-#define DV_THREADS 1024u
-#define DV_WAVES   (DV_THREADS / 64u)
-
-__device__ __forceinline__ u64 sat_add(u64 a, u64 b) { const u64 s = a + b; return s < a ? ~(u64)0 : s; }
-
-// Inclusive scan of K values per thread over the block (saturating add: associative, so the order of the partial sums does not matter),
-// continued from carry; carry becomes carry + the tile's total in every thread.
-template <int K>
-__device__ __forceinline__ void dv_block_scan(u64 (&v)[K], u64 (&carry)[K], u64 (*s_w)[DV_WAVES])
-{
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-	#pragma unroll
-	for (int k = 0; k < K; ++k) {
-		#pragma unroll
-		for (uint32_t d = 1; d < 64u; d <<= 1) { const u64 o = __shfl_up(v[k], d, 64); if (lane >= d) { v[k] = sat_add(v[k], o); } }
-		if (lane == 63u) { s_w[k][w] = v[k]; }
-	}
-	__syncthreads();
-	#pragma unroll
-	for (int k = 0; k < K; ++k) {
-		u64 before = carry[k], tot = carry[k];
-		for (uint32_t i = 0; i < DV_WAVES; ++i) { if (i < w) { before = sat_add(before, s_w[k][i]); } tot = sat_add(tot, s_w[k][i]); }
-		v[k] = sat_add(v[k], before);
-		carry[k] = tot;
-	}
-	__syncthreads();
-}
-
 // SIZING (size plans): out_off is not read (every unit's is 0), out_cap holds the limits (null: 2^64 - 1 for every unit) and there is no
 // bound on their sum
 template <bool SIZING>
@@ -258,51 +230,10 @@ void launch_dev_ctables(hipStream_t st, int format, uint32_t n, u64 in_total_max
 // unit is spread over as many blocks as its bytes cover. Per unit piece: a bytewise head up to the destination's next 16-byte boundary, a
 // body of 16-byte stores (16-byte loads where the source is aligned alike, loads of alignment 1 otherwise), a bytewise tail. No byte of the
 // source outside the piece is read. A unit that ends beyond cap is left out whole, and so is everything behind it.
-#define CPD_THREADS 256u
 #define CPD_SLICE_MIN 4096u                              // a slice is a multiple of this (small batches: fewer blocks, whole pieces)
-struct __attribute__((packed)) cpd_u16 { uint32_t w[4]; };  // 16 bytes of alignment 1
 
-template <bool ZERO>
-__device__ __forceinline__ void cpd_move(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, u64 cnt, uint32_t tid)
-{
-	u64 head = (16u - ((uintptr_t)dst & 15u)) & 15u;
-	if (head > cnt) { head = cnt; }
-	const u64 body = (cnt - head) >> 4, tail0 = head + body * 16u;
-	const bool has_head = tid < head, has_tail = tid >= 64u && tail0 + (tid - 64u) < cnt;   // (the tail on the second wave: at most 15 bytes)
-	uint4* __restrict__ d16 = reinterpret_cast<uint4*>(dst + head);
-	if (ZERO) {
-		if (has_head) { dst[tid] = 0; }
-		if (has_tail) { dst[tail0 + (tid - 64u)] = 0; }
-		for (u64 k = tid; k < body; k += CPD_THREADS) { d16[k] = make_uint4(0, 0, 0, 0); }
-		return;
-	}
-	// every load of a step before its stores: a piece of up to 16 KiB + 30 bytes costs one round trip to memory, not one per access
-	const uint8_t hb = has_head ? src[tid] : (uint8_t)0, tb = has_tail ? src[tail0 + (tid - 64u)] : (uint8_t)0;
-	const bool same = (((uintptr_t)src + head) & 15u) == 0;              // source and destination aligned alike: 16-byte loads
-	const uint4* __restrict__ sa = reinterpret_cast<const uint4*>(src + head);
-	const cpd_u16* __restrict__ su = reinterpret_cast<const cpd_u16*>(src + head);
-	for (u64 k0 = 0; k0 < body || k0 == 0; k0 += 4u * CPD_THREADS) {
-		uint4 v[4];
-		#pragma unroll
-		for (uint32_t j = 0; j < 4u; ++j) {
-			const u64 k = k0 + j * CPD_THREADS + tid;
-			if (k < body) {
-				if (same) { v[j] = sa[k]; }
-				else { const cpd_u16 t = su[k]; v[j] = make_uint4(t.w[0], t.w[1], t.w[2], t.w[3]); }
-			}
-		}
-		if (k0 == 0) {
-			if (has_head) { dst[tid] = hb; }
-			if (has_tail) { dst[tail0 + (tid - 64u)] = tb; }
-		}
-		#pragma unroll
-		for (uint32_t j = 0; j < 4u; ++j) {
-			const u64 k = k0 + j * CPD_THREADS + tid;
-			if (k < body) { d16[k] = v[j]; }
-		}
-	}
-}
-
+// PTRS (the block container's pack pass, blocks.hip): src_off[u] holds the address of unit u's bytes and src is not used
+template <bool PTRS>
 __global__ __launch_bounds__(CPD_THREADS) void cpd_copy_kernel(const uint8_t* __restrict__ src, const u64* __restrict__ src_off, const u64* __restrict__ len,
                                                               const u64* __restrict__ off, uint32_t n, u64 cap, uint8_t* __restrict__ dst)
 {
@@ -322,7 +253,7 @@ __global__ __launch_bounds__(CPD_THREADS) void cpd_copy_kernel(const uint8_t* __
 		const u64 nL = more ? len[u + 1u] : 0, ne = more ? off[u + 2u] : 0, nso = more ? src_off[u + 1u] : 0;
 		if (L > cap - o) { break; }                                         // (o < hi <= cap) ends beyond cap: not copied, and nothing behind it is below cap
 		const u64 d0 = o > lo ? o : lo, d1 = o + L < hi ? o + L : hi;
-		if (d0 < d1) { cpd_move<false>(dst + d0, src + so + (d0 - o), d1 - d0, tid); }
+		if (d0 < d1) { cpd_move<false>(dst + d0, (PTRS ? reinterpret_cast<const uint8_t*>((uintptr_t)so) : src + so) + (d0 - o), d1 - d0, tid); }
 		const u64 p0 = o + L > lo ? o + L : lo, p1 = e < hi ? e : hi;      // the padding up to the next unit
 		if (p0 < p1) { cpd_move<true>(dst + p0, nullptr, p1 - p0, tid); }
 		if (!more) { break; }
@@ -335,7 +266,7 @@ uint32_t compact_dev_blocks()
 {
 	int dev = 0, cus = 0, per_cu = 0;
 	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cpd_copy_kernel, (int)CPD_THREADS, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 4; }
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cpd_copy_kernel<false>, (int)CPD_THREADS, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 4; }
 	return (uint32_t)cus * (uint32_t)per_cu;
 }
 
@@ -344,7 +275,14 @@ void launch_compact_dev(hipStream_t st, uint32_t n, const uint8_t* src, const u6
 {
 	launch_layout_dev(st, len, n, align, off);
 	if (n == 0 || cap == 0) { return; }
-	hipLaunchKernelGGL(cpd_copy_kernel, dim3(blocks), dim3(CPD_THREADS), 0, st, src, src_off, len, off, n, cap, packed);
+	hipLaunchKernelGGL(cpd_copy_kernel<false>, dim3(blocks), dim3(CPD_THREADS), 0, st, src, src_off, len, off, n, cap, packed);
+}
+
+// The same copy for units that lie in two buffers: src_ptr[u] = the address of unit u's len[u] bytes, off[0..n] already written (blocks.hip)
+void launch_pack_ptrs(hipStream_t st, uint32_t n, const u64* src_ptr, const u64* len, const u64* off, uint8_t* packed, u64 cap, uint32_t blocks)
+{
+	if (n == 0) { return; }
+	hipLaunchKernelGGL(cpd_copy_kernel<true>, dim3(blocks), dim3(CPD_THREADS), 0, st, (const uint8_t*)nullptr, src_ptr, len, off, n, cap, packed);
 }
 
 } // namespace msc

@@ -185,6 +185,9 @@ void launch_dev_size_finish(hipStream_t st, const uint32_t* reject, uint32_t n, 
 uint32_t compact_dev_blocks();
 void launch_compact_dev(hipStream_t st, uint32_t n, const uint8_t* src, const u64* src_off, const u64* len, u64 align, uint8_t* packed, u64 cap,
                         u64* off, uint32_t blocks);
+// the copy of mscomp_amd_compact_dev with a source address per unit (src_ptr[u], for len[u] bytes) and offsets that are already there
+// (off[0..n], growing, off[n] = total): what a block container packs, its blocks lying in the staging area or in the caller's input
+void launch_pack_ptrs(hipStream_t st, uint32_t n, const u64* src_ptr, const u64* len, const u64* off, uint8_t* packed, u64 cap, uint32_t blocks);
 // p[0..n) = 0 as a kernel (a dev plan's launches hold no memset: they go into graphs the caller captures)
 void launch_dev_zero(hipStream_t st, uint32_t* p, uint32_t n);
 // units with reject[u]: status MSCOMP_ARG_ERROR, length 0 (after the decoders, which saw them as empty units with no room)
@@ -198,6 +201,35 @@ void launch_dev_ctables(hipStream_t st, int format, uint32_t n, u64 in_total_max
                         const u64* out_off, const u64* out_cap, u64* san, uint32_t* chunk_prefix, uint32_t* reject);
 // mscomp_amd_plan_layout_dev: cap[i] = the format's largest output for in_len[i] (cap may be null), off[0..n] as launch_layout_dev
 void launch_clayout_dev(hipStream_t st, int format, const u64* in_len, uint32_t n, u64 align, u64* off, u64* cap);
+
+// ---- block containers (blocks.hip; mscomp_amd_blocks_*) ----
+// The container's own tables, in one buffer (api.hip blocks_tab is the only place that knows the layout). n = resources, m = the bound of
+// the blocks; the seven unit columns are what the inner dev plans read and write, with the container's blocks (compress) or the blocks in
+// range (decompress) as units.
+struct BlocksTab {
+	u64* res_a;                                        // n: compress, where a resource's blocks are staged; decompress, the bytes its range stands for
+	u64* res_b;                                        // n: decompress, first block of the clipped range
+	u64* unit_first;                                   // n + 1: decompress, first unit of every resource
+	u64 *in_off, *in_len, *out_off, *out_cap;          // m each: the inner plan's unit tables
+	u64* ulen;                                         // m: the inner plan's d_out_len
+	u64 *aux_a, *aux_b;                                // m each: compress, stored length | source address; decompress, raw block's offset in packed | in out
+	int32_t* rstat;                                    // n: the resource's own status (bounds, block count, capacity)
+	int32_t* ustat;                                    // m: the inner plan's d_status
+	uint32_t* act;                                     // m: decompress, kind | data length << 2
+};
+// compress, in front of the inner plan: bounds check, block_first (n_res + 1) and the unit tables (two launches: one block over the resources,
+// one thread per possible block)
+void launch_blocks_ctables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* res_off, const u64* res_len,
+                           u64* block_first, const BlocksTab& t);
+// compress, behind it: stored form per block (t.aux_a / t.aux_b for launch_pack_ptrs), block_off (nbmax + 1), d_status (one block)
+void launch_blocks_select(hipStream_t st, uint32_t n_res, uint32_t nbmax, u64 cap, const uint8_t* d_in, const uint8_t* stage, const u64* block_first,
+                          const BlocksTab& t, u64* block_off, int32_t* d_status);
+// decompress, in front of the inner plan: the per-resource checks and the range, then unit tables and action words (two launches)
+void launch_blocks_dtables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, u64 packed_len, const u64* res_len,
+                           const u64* block_first, const u64* block_off, const u64* range, const u64* d_out_off, const u64* d_out_cap, const BlocksTab& t);
+// decompress, behind it: raw blocks to their places (`blocks` = compact_dev_blocks()), then status and length per resource
+void launch_blocks_rawcopy(hipStream_t st, uint32_t nbmax, uint32_t shift, const uint8_t* packed, uint8_t* out, const BlocksTab& t, uint32_t blocks);
+void launch_blocks_dfold(hipStream_t st, uint32_t n_res, const BlocksTab& t, u64* d_out_len, int32_t* d_status);
 
 // ---- utilities (util.hip) ----
 // prefix[0..n] = exclusive scan of sizes[0..n) as u64 (prefix[n] = total). block_sums: scratch of ceil(n/1024)+1 u64.
