@@ -534,8 +534,9 @@ static void run_lz_copy_global(mscomp_amd_ctx* c, const mscomp_amd_plan* p, hipS
 {
 	if (!p->lzg_big) { return; }
 	const LzgTables g = lzg_tables(p, c);
-	static const char* const names[3] = {"lzg_dir_kernels", "lzg_expand_kernel", "lzg_jump_kernel"};
-	for (int ph = 0; ph < 3; ++ph) { KernelTimer t(c, names[ph]); launch_lz_copy_global(st, g, p->bt, tp, tok, ntok, d_out_len, d_status, d_out, ph); }
+	{ KernelTimer t(c, "lzg_dir_kernels"); launch_lzg_directory(st, g, tp, tok, ntok, d_out_len, d_status); }
+	{ KernelTimer t(c, "lzg_expand_kernel"); launch_lzg_expand(st, g, p->bt, tp, tok, ntok, d_out_len, d_status, d_out); }
+	{ KernelTimer t(c, "lzg_jump_kernel"); launch_lzg_jump(st, g, p->bt, d_out_len, d_status, d_out); }
 }
 
 static XpressWinBufs xpress_win_bufs(mscomp_amd_ctx* c, uint32_t n_chunks)
@@ -625,33 +626,35 @@ static void decode_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_ou
 		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b, p->dev); }
 		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
 		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
-		{ KernelTimer t(c, "lzd_chunk_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 0); }
+		{ KernelTimer t(c, "lzd_chunk_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out); }
 		{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status); }
-		{ KernelTimer t(c, "lzd_replace_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, d_out, 1); }
+		{ KernelTimer t(c, "lzd_replace_kernel"); launch_lzd_replace(st, d_in, p->bt, b, d_out); }
 		return;
 	}
 	case MSCOMP_XPRESS: {                                          // tokens a flag word at a time, then the copy kernels; large streams of host plans by segments first
 		const int mode = p->dev ? (p->large ? 0 : 2) : g_xpd_mode.load(std::memory_order_relaxed);   // (the test hook switches host plans only; a dev plan walks by segments when it was created for large units)
 		if (mode == 1) { KernelTimer t(c, "xpd_kernel"); launch_xpress_decompress(st, d_in, p->bt, d_out, d_out_len, d_status); return; }
-		static const char* const names[3] = {"xpt_parse_kernel", "lz_copy_kernel", "lz_copy_block_kernel"};
 		const XpsTables x = mode != 2 ? xps_tables(p, c) : XpsTables{};
 		if (x.n_big) {
-			{ KernelTimer t2(c, "xps_walk_kernel"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -1, gmin, x); }
+			{ KernelTimer t2(c, "xps_walk_kernel"); launch_xps_walk(st, d_in, p->bt, x); }
 			static const uint32_t rounds = [] { const char* e = getenv("MSCOMP_AMD_XPS_ROUNDS"); const long v = e ? atol(e) : 0; return (uint32_t)(v >= 1 && v <= 256 ? v : XPS_ROUNDS); }();
-			for (uint32_t r = 0; r < rounds; ++r) { KernelTimer t2(c, "xps_redo_kernels"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -2, gmin, x); }
-			{ KernelTimer t2(c, "xps_emit_kernel"); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, -3, gmin, x); }
+			for (uint32_t r = 0; r < rounds; ++r) { KernelTimer t2(c, "xps_redo_kernels"); launch_xps_redo(st, d_in, p->bt, x, ntok, d_out_len, d_status); }
+			{ KernelTimer t2(c, "xps_emit_kernel"); launch_xps_emit(st, d_in, p->bt, x, tp, tok, ntok, d_out_len, d_status); }
 		}
-		for (int ph = 0; ph < 3; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_decompress_tokens(st, d_in, p->bt, tp, tok, ntok, d_out, d_out_len, d_status, ph, gmin, x, gcnt); }
+		{ KernelTimer t(c, "xpt_parse_kernel"); launch_xpt_parse(st, d_in, p->bt, tp, tok, ntok, d_out_len, d_status, x); }
+		{ KernelTimer t(c, "lz_copy_kernel"); launch_lz_copy(st, p->bt, tp, tok, ntok, d_out_len, d_status, d_out, gmin, gcnt); }
+		{ KernelTimer t(c, "lz_copy_block_kernel"); launch_lz_copy_block(st, p->bt, tp, tok, ntok, d_out_len, d_status, d_out, gmin, gcnt); }
 		break;
 	}
 	default: {                                                     // MSCOMP_XPRESS_HUFF (without token scratch the accepted chunks are walked twice)
 		XhcBufs xb = xhc_bufs(c, p);
 		if (p->xhc_scr) { xb.scr_prefix = p->scr_prefix; xb.scr_tok = static_cast<uint32_t*>(c->dz_scr.p); }
-		static const char* const names[6] = { "xhc_mark_kernel", "xhc_parse_kernel", "xhc_chain_kernel", "xhc_parse2_kernel", "xhd_parse_kernel", "lz_copy_kernel" };
-		for (int ph = 0; ph < 6; ++ph) {
-			KernelTimer t(c, names[ph]);
-			launch_xpress_huff_decompress(st, d_in, p->bt, tp, tok, ntok, p->cand_prefix, p->xhc_slots, xb, d_out, d_out_len, d_status, ph, gmin, p->dev, gcnt);
-		}
+		{ KernelTimer t(c, "xhc_mark_kernel"); launch_xhc_mark(st, d_in, p->bt, p->cand_prefix, xb, p->dev); }
+		{ KernelTimer t(c, "xhc_parse_kernel"); launch_xhc_candidates(st, d_in, p->bt, tp, p->cand_prefix, p->xhc_slots, xb, tok); }
+		{ KernelTimer t(c, "xhc_chain_kernel"); launch_xhc_chain(st, p->bt, p->cand_prefix, xb, ntok, d_out_len, d_status); }
+		{ KernelTimer t(c, "xhc_parse2_kernel"); launch_xhc_tokens(st, d_in, p->bt, tp, p->cand_prefix, p->xhc_slots, xb, tok); }
+		{ KernelTimer t(c, "xhd_parse_kernel"); launch_xhd_parse(st, d_in, p->bt, tp, tok, ntok, d_out_len, d_status, xb.mode); }
+		{ KernelTimer t(c, "lz_copy_kernel"); launch_lz_copy(st, p->bt, tp, tok, ntok, d_out_len, d_status, d_out, gmin, gcnt); launch_lz_copy_block(st, p->bt, tp, tok, ntok, d_out_len, d_status, d_out, gmin, gcnt); }   // (both under one name)
 		break;
 	}
 	}
@@ -813,24 +816,26 @@ static void size_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out
 		{ KernelTimer t(c, "lzd_seg_kernel"); launch_lzd_segments(st, d_in, p->bt, b, p->dev); }
 		{ KernelTimer t(c, "lzd_verify_kernel"); launch_lzd_verify(st, d_in, p->bt, b); }
 		{ KernelTimer t(c, "scan_sizes"); launch_scan_sizes(st, b.selcnt, b.flat, p->n_chunks, static_cast<u64*>(c->tile_sums.p)); }
-		{ KernelTimer t(c, "lzd_size_kernel"); launch_lzd_chunks(st, d_in, p->bt, b, nullptr, 2); }
+		{ KernelTimer t(c, "lzd_size_kernel"); launch_lzd_sizes(st, d_in, p->bt, b); }
 		{ KernelTimer t(c, "lzd_finalize_kernel"); launch_lzd_finalize(st, p->bt, b, d_out_len, d_status, d_need); }
 		break;
 	}
 	case MSCOMP_XPRESS: {                                  // large streams of host plans by segments, the others (a dev plan: every stream) by the one-wave walk
 		const XpsTables x = xps_tables(p, c);
 		if (x.n_big) {
-			{ KernelTimer t2(c, "xps_walk_kernel"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, -1, x); }
-			for (uint32_t r = 0; r < XPS_ROUNDS; ++r) { KernelTimer t2(c, "xps_redo_kernels"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, -2, x); }
-			{ KernelTimer t2(c, "xps_size_kernel"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, -3, x); }
+			{ KernelTimer t2(c, "xps_walk_kernel"); launch_xps_walk(st, d_in, p->bt, x); }
+			for (uint32_t r = 0; r < XPS_ROUNDS; ++r) { KernelTimer t2(c, "xps_redo_kernels"); launch_xps_redo(st, d_in, p->bt, x, ntok, d_out_len, d_status); }
+			{ KernelTimer t2(c, "xps_size_kernel"); launch_xps_size(st, d_in, p->bt, x, ntok, d_out_len, d_status); }
 		}
-		{ KernelTimer t(c, "xpt_size_kernel"); launch_xpress_size(st, d_in, p->bt, ntok, d_out_len, d_status, 0, x); }
+		{ KernelTimer t(c, "xpt_size_kernel"); launch_xpt_size(st, d_in, p->bt, ntok, d_out_len, d_status, x); }
 		break;
 	}
 	default: {                                             // MSCOMP_XPRESS_HUFF
 		const XhcBufs xb = xhc_bufs(c, p);
-		static const char* const names[4] = { "xhc_mark_kernel", "xhc_size_kernel", "xhc_chain_kernel", "xhd_size_kernel" };
-		for (int ph = 0; ph < 4; ++ph) { KernelTimer t(c, names[ph]); launch_xpress_huff_size(st, d_in, p->bt, ntok, p->cand_prefix, p->xhc_slots, xb, d_out_len, d_status, ph, p->dev); }
+		{ KernelTimer t(c, "xhc_mark_kernel"); launch_xhc_mark(st, d_in, p->bt, p->cand_prefix, xb, p->dev); }
+		{ KernelTimer t(c, "xhc_size_kernel"); launch_xhc_candidates_size(st, d_in, p->bt, p->cand_prefix, p->xhc_slots, xb); }
+		{ KernelTimer t(c, "xhc_chain_kernel"); launch_xhc_chain(st, p->bt, p->cand_prefix, xb, ntok, d_out_len, d_status); }
+		{ KernelTimer t(c, "xhd_size_kernel"); launch_xhd_size(st, d_in, p->bt, ntok, d_out_len, d_status, xb.mode); }
 		break;
 	}
 	}

@@ -122,8 +122,8 @@ __host__ __device__ inline u64 decode_chunks(int format, u64 n)
 	return 1u;
 }
 // token slots of a unit of `len` compressed bytes with room for `cap`: a token takes at least one input byte (Xpress; an Xpress+Huffman
-// symbol at least one bit) and gives at least one output byte, and a match is cut into one more token per 32766 bytes (LZT_MAXLEN of
-// decompress.hip); 64 slots of slack
+// symbol at least one bit) and gives at least one output byte, and a match is cut into one more token per LZT_MAXLEN bytes; 64 slots of slack
+#define LZT_MAXLEN 32766u                                 // longest match a 32-bit token holds (15 bits); longer ones are cut into pieces (xpress_decode.hip, xhuff_decode.hip)
 __host__ __device__ inline u64 token_slots(int format, u64 len, u64 cap)
 {
 	const u64 by_in = (format == 3 ? 1u : 8u) * len + cap / 32766u + 1u;
@@ -139,7 +139,7 @@ __host__ __device__ inline u64 candidate_slots(u64 len, u64 cap)
 // ---- the optional paths of a decompress / size plan --------------------------------------------------------
 // Which units take them and what they add to the path's tables: api.hip plan_create_impl decides with these on the host, the path pass of a
 // dev plan with large units (devplan.hip dv_paths_kernel) on the device, so both make the same decisions for the same per-unit values.
-#define XPS_MIN_IN (512u << 10)                           // Xpress streams with at least this much input are walked by segments (decompress.hip, xps_*)
+#define XPS_MIN_IN (512u << 10)                           // Xpress streams with at least this much input are walked by segments (xpress_decode.hip, xps_*)
 #define LZG_MIN_CAP (1u << 20)                            // units with at least this much output capacity get their bytes from all CUs (lzglobal.hip), when the plan has the scratch for it
 #ifndef LZG_TILE_SHIFT
 #define LZG_TILE_SHIFT 13                                   // output bytes per tile of lzg_expand_kernel: 8 KiB (32 KiB tiles: expansion 0.78 -> 1.37 ms, passes 4.1 -> 4.6 ms on the 12 files)
@@ -185,10 +185,30 @@ __device__ __forceinline__ uint32_t unit_of_chunk(const uint32_t* __restrict__ p
 	}
 	return lo;
 }
+// the same over a u64 prefix: largest g with prefix[g] <= c (LZNT1: the exclusive scan of the per-segment chunk counts, empty segments share an
+// entry with their successor; Xpress+Huffman: the candidate slots of the units)
+__device__ __forceinline__ uint32_t seg_of_flat(const u64* __restrict__ prefix, uint32_t n_seg, u64 c)
+{
+	uint32_t lo = 0, hi = n_seg;
+	while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (prefix[mid] <= c) { lo = mid; } else { hi = mid; } }
+	return lo;
+}
 
 // Plans whose tables are built on the device (DEV kernel instances): the grid is sized for the plan's bound, and a chunk at or past the batch's
 // real count (chunk_prefix[n_units], written by the table pass) belongs to no unit -- unit_of_chunk would hand it to the last one
 __device__ __forceinline__ bool past_real_chunks(const BatchTables& bt, uint32_t c) { return c >= bt.chunk_prefix[bt.n_units]; }
+
+// LDS bytes [0, n) -> global dst (any alignment), one wave (the LZNT1 chunk kernel and lz_copy_kernel)
+__device__ __forceinline__ void lzd_store(uint8_t* __restrict__ dst, const uint8_t* lds, uint32_t n, uint32_t lane)
+{
+	uint32_t head = (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u);
+	if (head > n) { head = n; }
+	if (lane < head) { dst[lane] = lds[lane]; }
+	const uint32_t body = (n - head) >> 2;
+	uint32_t* __restrict__ d32 = reinterpret_cast<uint32_t*>(dst + head);
+	for (uint32_t i = lane; i < body; i += 64u) { d32[i] = lds_ld32(lds, head + i * 4u); }
+	for (uint32_t i = head + body * 4u + lane; i < n; i += 64u) { dst[i] = lds[i]; }
+}
 
 // Cooperative byte copy global->global: src is 4-byte aligned (a scratch slot), dst has any alignment.
 // Body moves aligned dwords on the destination side, funnel-shifting two source dwords.

@@ -71,8 +71,8 @@ void prepare_xh_fallback();
 void launch_xh_encode(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const uint16_t* mlen3, const uint16_t* moff,
                       const u64* tokbits, const uint8_t* lens, const uint16_t* codes, const uint32_t* fbflag, const u64* prefix, uint8_t* d_out, bool dev = false);
 
-// ---- decompressors (decompress.hip) ----
-// LZNT1: the compressed input of a unit is cut into segments of LZD_SEG bytes (chunk_prefix[u] = first segment of unit u, n_chunks =
+// ---- decompressors: LZNT1 (lznt1_decode.hip) ----
+// The compressed input of a unit is cut into segments of LZD_SEG bytes (chunk_prefix[u] = first segment of unit u, n_chunks =
 // segments of the batch). cin: header offsets, LZD_SLOTS per segment (u32); segL / segE / segcnt / segstop / segoff per speculated
 // chain; selcnt / seloff per segment (the true chain); flat: u64 exclusive scan of selcnt (n_chunks + 1) = number of the first chunk of a segment; csize: decoded size or 0x8000 per
 // chunk number (u16); stop / irregular (+1 global flag) per unit.
@@ -87,13 +87,16 @@ void launch_lzd_segments(hipStream_t st, const uint8_t* d_in, const BatchTables&
 void prepare_lzd_segments(bool dev);                      // its one-time LDS attribute (a dev plan sets it when it is created: its first execution may be captured)
 uint32_t lzd_read_walked();
 void launch_lzd_verify(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b);
-// exact: 0 decode every chunk, 1 decode the irregular units' chunks again to their places, 2 size every chunk only (the size query; d_out unused)
-void launch_lzd_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b, uint8_t* d_out, int exact);
+// lzd_chunk_kernel: every chunk decoded | the irregular units' chunks decoded again to their places | every chunk only sized (the size query)
+void launch_lzd_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b, uint8_t* d_out);
+void launch_lzd_replace(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b, uint8_t* d_out);
+void launch_lzd_sizes(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const LzdBufs& b);
 void launch_lzd_finalize(hipStream_t st, const BatchTables& bt, const LzdBufs& b, u64* d_out_len, int32_t* d_status, u64* d_need = nullptr);
 
-// Xpress: one wave per stream
+// ---- decompressors: Xpress (xpress_decode.hip) ----
+// xpd_kernel: one wave walks and copies one stream
 void launch_xpress_decompress(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* d_out, u64* d_out_len, int32_t* d_status);
-// large Xpress streams by segments (decompress.hip, xps_*): plan tables + scratch
+// large Xpress streams by segments (xps_*): plan tables + scratch
 #define XPS_SEG    16384u                                 // input bytes per segment (12 whole files, segment / warm-up KiB: 32/32 15.5 ms, 16/16 14.1, 8/8 19.6, 32/8 21.2)
 #define XPS_WARM   16384u                                 // a speculative walk starts this far before its segment
 #define XPS_SEG_BYTES 64u
@@ -109,30 +112,43 @@ struct XpsTables {
 	const uint32_t* cnt;           // null: a host plan, n_big / n_seg are the counts. A dev plan with large units: n_big / n_seg are its bounds (grids,
 	                               // scratch layout) and cnt[0] / cnt[1] the counts of this execution, written by its path pass (the DEV kernel instances read them)
 };
-// the same through 32-bit tokens: phase -1 = the segment kernels, 0 = xpt_parse_kernel (a flag word at a time), 1 = lz_copy_kernel, 2 = lz_copy_block_kernel
-void launch_xpress_decompress_tokens(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
-                                     uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, const XpsTables& x,
-                                     const uint32_t* lzg_cnt = nullptr);   // lzg_cnt: a dev plan with large units -- the byte kernels leave the units of LZG_MIN_CAP and more to lzglobal.hip when lzg_cnt[0] != 0
-// the size query: the same walks with every test and no token written (phases -1 / -2 / -3 as above, 0 = the one-wave walk); ntok: n_units counts
-void launch_xpress_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, u64* d_out_len, int32_t* d_status, int phase, const XpsTables& x);
+// The same through 32-bit tokens, the large streams by segments first (the DEV instances when x.cnt is set; no launch when x.n_big == 0).
+// walk: x.done zeroed, xps_init_kernel, xps_walk_kernel<0>, the speculative walks. redo: xps_check_kernel<false>, xps_walk_kernel<1>, one round of
+// "walk the segments again that do not hold". emit: xps_check_kernel<true>, the verdict, and xps_emit_kernel<true>; size: xps_emit_kernel<false>, no stores.
+void launch_xps_walk(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const XpsTables& x);
+void launch_xps_redo(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const XpsTables& x, u64* ntok, u64* d_out_len, int32_t* d_status);
+void launch_xps_emit(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const XpsTables& x, const u64* tok_prefix, uint32_t* tok, u64* ntok, u64* d_out_len, int32_t* d_status);
+void launch_xps_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const XpsTables& x, u64* ntok, u64* d_out_len, int32_t* d_status);
+// xpt_parse_kernel<true>, a wave per stream x.done does not mark (x.n_big == 0: every stream); size: <false>, every test, no token written (ntok: n_units counts)
+void launch_xpt_parse(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok, u64* d_out_len, int32_t* d_status, const XpsTables& x);
+void launch_xpt_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, u64* d_out_len, int32_t* d_status, const XpsTables& x);
 
-// Xpress+Huffman, in phases: 0 mark candidate chunk starts, 1 walk every candidate as one chunk, 2 chain check per buffer, 3 tokens of the
-// accepted chunks, 4 serial walk of the buffers the speculation could not do, 5 tokens -> bytes. tok_prefix[u] = first token slot of unit u,
-// cand_prefix[u] = first candidate slot (n_slots in all); per candidate slot: offset, next offset, reach, state, bytes, tokens, token offset.
-// (XHC_TILE_BYTES: common.h, beside decode_chunks)
+// ---- decompressors: Xpress+Huffman (xhuff_decode.hip) ----
+// tok_prefix[u] = first token slot of unit u, cand_prefix[u] = first candidate slot (n_slots in all); per candidate slot: offset, next offset,
+// reach, state, bytes, tokens, token offset. (XHC_TILE_BYTES: common.h, beside decode_chunks)
 enum { XHC_SERIAL = 1, XHC_SPEC = 2 };
 struct XhcBufs { uint32_t* cand_cnt; uint32_t* mode; uint32_t* cand_pos; uint32_t* res_end; uint32_t* res_reach; uint32_t* res_state;
                  u64* res_prod; u64* res_ntok; u64* tok_off;
                  const u64* scr_prefix; uint32_t* scr_tok; };   // token scratch: first scratch slot of every unit (n_units + 1; equal = none), XHC_SCR tokens per candidate
 #define XHC_SCR 65600u                                    // a candidate gives up to 65536 tokens before its 65536th byte
-void launch_xpress_huff_decompress(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok,
-                                   const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb,
-                                   uint8_t* d_out, u64* d_out_len, int32_t* d_status, int phase, u64 lzg_min_cap, bool dev = false,   // dev: as launch_lzd_segments
-                                   const uint32_t* lzg_cnt = nullptr);                                                                 // lzg_cnt: as launch_xpress_decompress_tokens
-void prepare_lz_copy_block();                             // the one-time LDS attribute of lz_copy_block_kernel (tokens -> bytes of both Xpress formats)
-// the size query: phases 0 mark, 1 measure every candidate (no tokens written, chunk 0 included), 2 chain check, 3 serial walk without tokens
-void launch_xpress_huff_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, const u64* cand_prefix, uint32_t n_slots,
-                             const XhcBufs& xb, u64* d_out_len, int32_t* d_status, int phase, bool dev = false);   // dev: as launch_lzd_segments
+// In the order they run. mark: xb.cand_cnt zeroed, xhc_mark_kernel lists the candidate chunk starts (dev: as launch_lzd_segments). candidates:
+// xhc_parse_kernel<1> walks every candidate as one chunk; size: <3>, which only measures (no tokens written, chunk 0 included). chain: xhc_chain_kernel,
+// per buffer. tokens: xhc_gather_kernel when there is token scratch, xhc_parse_kernel<2> for the accepted chunks. xhd: xhd_parse_kernel<true>, the
+// serial walk of the buffers the speculation could not do (mode: xb.mode); size: <false>, tokens only counted.
+void launch_xhc_mark(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* cand_prefix, const XhcBufs& xb, bool dev);
+void launch_xhc_candidates(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb, uint32_t* tok);
+void launch_xhc_candidates_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb);
+void launch_xhc_chain(hipStream_t st, const BatchTables& bt, const u64* cand_prefix, const XhcBufs& xb, u64* ntok, u64* d_out_len, int32_t* d_status);
+void launch_xhc_tokens(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, const u64* cand_prefix, uint32_t n_slots, const XhcBufs& xb, uint32_t* tok);
+void launch_xhd_parse(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* tok_prefix, uint32_t* tok, u64* ntok, u64* d_out_len, int32_t* d_status, const uint32_t* mode);
+void launch_xhd_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, u64* ntok, u64* d_out_len, int32_t* d_status, const uint32_t* mode);
+
+// ---- tokens -> bytes of both Xpress formats (lz_copy.hip): lz_copy_kernel, a wave per unit, and lz_copy_block_kernel, a block per larger one ----
+// Units of lzg_min_cap output bytes and more are left to lzglobal.hip; with lzg_cnt (a dev plan with large units) the DEV instances, which leave the
+// units of LZG_MIN_CAP and more when lzg_cnt[0] != 0
+void launch_lz_copy(hipStream_t st, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, u64 lzg_min_cap, const uint32_t* lzg_cnt);
+void launch_lz_copy_block(hipStream_t st, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, u64 lzg_min_cap, const uint32_t* lzg_cnt);
+void prepare_lz_copy_block();                             // the one-time LDS attribute of lz_copy_block_kernel
 
 // ---- tokens -> bytes for large units by all CUs (lzglobal.hip) ----
 #define LZG_PASSES 33u                                    // pointer passes launched (chains halve at least: 2^32 bytes); a pass returns at once when the one before left nothing open
@@ -151,10 +167,12 @@ struct LzgTables {
 	uint32_t  n_big, n_tb, n_tiles;
 	const uint32_t* cnt;           // as XpsTables::cnt: cnt[0] units taken (0: the stage does not run in this execution), cnt[1] token blocks, cnt[2] tiles
 };
-// phase 0 = directory (3 kernels), 1 = lzg_expand_kernel, 2 = the pointer passes
 void prepare_lz_copy_global(bool dev);                    // the one-time LDS attribute of lzg_expand_kernel (a dev plan sets it when it is created, as prepare_lzd_segments)
-void launch_lz_copy_global(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok,
-                           const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, int phase);
+// directory: g.open zeroed, lzg_sums_kernel, lzg_scan_kernel, lzg_dir_kernel; expand: lzg_expand_kernel; jump: LZG_PASSES launches of lzg_jump_kernel.
+// Each picks the DEV instances from g.cnt and launches nothing when g.n_big == 0.
+void launch_lzg_directory(hipStream_t st, const LzgTables& g, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status);
+void launch_lzg_expand(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out);
+void launch_lzg_jump(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out);
 
 // ---- plans with device-built tables (devplan.hip) ----
 // One block walks the units in tiles of 1024: per unit, the checks of mscomp_amd_plan_execute_dev (in_len <= 0xFFFFF000, running totals of

@@ -1,7 +1,7 @@
 // lzglobal.hip -- tokens -> bytes for LARGE units, by all CUs (the last stage of Xpress / Xpress+Huffman decompression).
 //
 // The copy loop of the reference decoders (/root/reference/src/xpress_decompress.cpp:442-452, xpress_huff_decompress.cpp:120-127) produces a
-// byte from a literal or from an earlier byte of the output: a chain through the output. lz_copy_block_kernel (decompress.hip) walks it 8 KiB
+// byte from a literal or from an earlier byte of the output: a chain through the output. lz_copy_block_kernel (lz_copy.hip) walks it 8 KiB
 // at a time with ONE block per unit: 30 000 cycles per tile, 78 ms for the 51 MB of mozilla, while 255 CUs look on. Here the unit is cut into
 // tiles of 8192 output bytes that are worked on by different blocks at the same time:
 //   lzg_sums_kernel / lzg_scan_kernel / lzg_dir_kernel   where every token starts (prefix sum of the token lengths over the unit, 8192 tokens
@@ -303,30 +303,6 @@ __global__ __launch_bounds__(256) void lzg_jump_kernel(LzgTables g, BatchTables 
 	}
 }
 
-template <bool DEV>
-static void lz_copy_global_phase(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok,
-                                 const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, int phase)
-{
-	switch (phase) {
-	case 0:
-		if (DEV) { launch_dev_zero(st, g.open, LZG_PASSES); }             // (a kernel, not a memset: kernels.h launch_dev_zero)
-		else { (void)hipMemsetAsync(g.open, 0, LZG_PASSES * sizeof(uint32_t), st); }
-		hipLaunchKernelGGL(lzg_sums_kernel<DEV>, dim3(g.n_tb), dim3(LZG_NT), 0, st, g, tok_prefix, tok, ntok, d_status);
-		hipLaunchKernelGGL(lzg_scan_kernel<DEV>, dim3(g.n_big), dim3(LZG_NT), 0, st, g, ntok, d_status);
-		hipLaunchKernelGGL(lzg_dir_kernel<DEV>, dim3(g.n_tb), dim3(LZG_NT), 0, st, g, tok_prefix, tok, ntok, d_out_len, d_status);
-		break;
-	case 1:
-		prepare_lz_copy_global(DEV);
-		hipLaunchKernelGGL(lzg_expand_kernel<DEV>, dim3(g.n_tiles), dim3(LZG_NT), sizeof(LzgLds), st, g, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out);
-		break;
-	default: {
-		static const uint32_t hops = [] { const char* e = getenv("MSCOMP_AMD_LZG_HOPS"); const long v = e ? atol(e) : 0; return (uint32_t)(v > 0 && v < 1000 ? v : LZG_HOPS); }();
-		for (uint32_t pass = 0; pass < LZG_PASSES; ++pass) { hipLaunchKernelGGL(lzg_jump_kernel<DEV>, dim3(g.n_tiles < 4096u ? g.n_tiles : 4096u), dim3(256), 0, st, g, bt, d_out_len, d_status, d_out, pass, hops); }
-		break;
-	}
-	}
-}
-
 void prepare_lz_copy_global(bool dev)
 {
 	static PerDeviceOnce attr[2];
@@ -337,12 +313,36 @@ void prepare_lz_copy_global(bool dev)
 	a.done();
 }
 
-void launch_lz_copy_global(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok,
-                           const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, int phase)
+// ---- launchers: directory, expansion, pointer passes (the DEV instances when the tables were built on the device: kernels.h LzgTables::cnt) ----
+template <bool DEV>
+static void lzg_directory(hipStream_t st, const LzgTables& g, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status)
+{
+	if (DEV) { launch_dev_zero(st, g.open, LZG_PASSES); }                 // (a kernel, not a memset: kernels.h launch_dev_zero)
+	else { (void)hipMemsetAsync(g.open, 0, LZG_PASSES * sizeof(uint32_t), st); }
+	hipLaunchKernelGGL(lzg_sums_kernel<DEV>, dim3(g.n_tb), dim3(LZG_NT), 0, st, g, tok_prefix, tok, ntok, d_status);
+	hipLaunchKernelGGL(lzg_scan_kernel<DEV>, dim3(g.n_big), dim3(LZG_NT), 0, st, g, ntok, d_status);
+	hipLaunchKernelGGL(lzg_dir_kernel<DEV>, dim3(g.n_tb), dim3(LZG_NT), 0, st, g, tok_prefix, tok, ntok, d_out_len, d_status);
+}
+template <bool DEV>
+static void lzg_jump(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out)
+{
+	static const uint32_t hops = [] { const char* e = getenv("MSCOMP_AMD_LZG_HOPS"); const long v = e ? atol(e) : 0; return (uint32_t)(v > 0 && v < 1000 ? v : LZG_HOPS); }();
+	for (uint32_t pass = 0; pass < LZG_PASSES; ++pass) { hipLaunchKernelGGL(lzg_jump_kernel<DEV>, dim3(g.n_tiles < 4096u ? g.n_tiles : 4096u), dim3(256), 0, st, g, bt, d_out_len, d_status, d_out, pass, hops); }
+}
+void launch_lzg_directory(hipStream_t st, const LzgTables& g, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status)
+{
+	if (g.n_big) { (g.cnt ? lzg_directory<true> : lzg_directory<false>)(st, g, tok_prefix, tok, ntok, d_out_len, d_status); }
+}
+void launch_lzg_expand(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out)
 {
 	if (g.n_big == 0) { return; }
-	if (g.cnt) { lz_copy_global_phase<true>(st, g, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, phase); }
-	else { lz_copy_global_phase<false>(st, g, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, phase); }
+	prepare_lz_copy_global(g.cnt != nullptr);
+	if (g.cnt) { hipLaunchKernelGGL(lzg_expand_kernel<true>, dim3(g.n_tiles), dim3(LZG_NT), sizeof(LzgLds), st, g, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out); }
+	else { hipLaunchKernelGGL(lzg_expand_kernel<false>, dim3(g.n_tiles), dim3(LZG_NT), sizeof(LzgLds), st, g, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out); }
+}
+void launch_lzg_jump(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out)
+{
+	if (g.n_big) { (g.cnt ? lzg_jump<true> : lzg_jump<false>)(st, g, bt, d_out_len, d_status, d_out); }
 }
 
 } // namespace msc

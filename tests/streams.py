@@ -694,7 +694,7 @@ def xpress_huff_family(seed=3, big=True):
 def xpress_huff_big(seed):
     """multi-MB buffers where every chunk after the first starts off the grid: all codes complete (the chunk-parallel path takes them), and
     one incomplete code among complete ones (the serial walk must take it). Their last chunk ends short of the mark: a chunk that is still
-    reading past it is left to the serial walk on purpose (csrc/decompress.hip, xhc_parse_kernel)"""
+    reading past it is left to the serial walk on purpose (csrc/xhuff_decode.hip, xhc_parse_kernel)"""
     rnd = random.Random(seed)
     out = []
     for k, n in enumerate((40, 48)):

@@ -272,7 +272,7 @@ def test_large_units_get_their_bytes_from_all_cus(oracle, gpu_ctx, fmt):
 
 
 def test_segment_and_tile_edges_of_large_streams(oracle, gpu_ctx):
-    """Xpress streams whose length sits on the edges of the segment walk (csrc/decompress.hip xps_*: streams from 512 KiB, 16 KiB segments) and
+    """Xpress streams whose length sits on the edges of the segment walk (csrc/xpress_decode.hip xps_*: streams from 512 KiB, 16 KiB segments) and
     outputs on the edges of the byte stage (csrc/lzglobal.hip: capacities from 1 MiB, 8 KiB tiles): prefixes of valid streams cut at those
     lengths, 600 KB of random bytes as a "stream", capacities one byte around 1 MiB -- status and bytes of the checker in every case."""
     import ms_compress_amd as m

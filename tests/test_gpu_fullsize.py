@@ -106,7 +106,7 @@ def test_whole_buffer_xpress_large(oracle, gpu_ctx):
 
 @pytest.mark.parametrize("fmt", [3, 4])
 def test_whole_files_come_back(gpu_ctx, fmt):
-    """All 12 files as 12 whole buffers -- one Xpress stream each (segment walks, csrc/decompress.hip xps_*), one Xpress+Huffman buffer each
+    """All 12 files as 12 whole buffers -- one Xpress stream each (segment walks, csrc/xpress_decode.hip xps_*), one Xpress+Huffman buffer each
     (chunk-parallel walk with token scratch) -- compressed (digests of the REFERENCE's output: tests/golden/corpus_full.json) and decompressed in one
     batch; the bytes of the large units come from csrc/lzglobal.hip. Also through the token-at-a-time Xpress kernel (mode 1) and without the
     segment walk (mode 2): the same bytes."""
