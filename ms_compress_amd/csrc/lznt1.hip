@@ -43,11 +43,17 @@ __device__ unsigned long long g_lz_prof[16];
 #ifdef LZ4_PROFILE_EVENTS   // (the event counters below; they imply the phase timers)
 #define LZ4_PROFILE
 #endif
-#ifdef LZ4_PROFILE   // dev-only: the four-wave kernel's phase cycles ([0..6], thread 0). With LZ4_PROFILE_EVENTS, summed over all windows walked: finishing
-                     // steps [7], lz_lcp_tail wave-iterations of the finishing steps [8], long-pending stops [9], cooperative 256-byte extension steps [10].
+#ifdef LZ4_PROFILE   // dev-only: the four-wave kernel's phase cycles, per WAVE: slot [LZ4_NSLOT wv + i] is wave wv's time in phase i, kept in lane i of one
+                     // vector register until the kernel's end (one atomic per slot and wave then). Even slots are work, the odd slot behind each is the
+                     // idle time in front of the barrier that ends it: 0 load, 2 B1 rank, 4 B2 re-read + bucket sums, 6 B3 pack, 8 B4 scatter, 10 parse of the
+                     // wave's segment + seam, 12 cascade check, 14 flag clear + scans, 16 token staging + emit loop, 18 flag bytes, header, size.
+                     // With LZ4_PROFILE_EVENTS, summed over all windows walked, behind the phase slots: finishing steps [+0], lz_lcp_tail wave-iterations of the
+                     // finishing steps [+1], long-pending stops [+2], cooperative 256-byte extension steps [+3].
                      // The event counters are same-address global atomics from inside the parse, some 300 per chunk: they hold up every global
                      // access of the kernel and inflate the phase cycles of load, parse and emit many times over, so the two are read in separate builds.
-#define LZ4_NPROF 16
+#define LZ4_NSLOT 20
+#define LZ4_NEV   (4 * LZ4_NSLOT)
+#define LZ4_NPROF (LZ4_NEV + 4)
 __device__ unsigned long long g_lz4_prof[LZ4_NPROF];
 #endif
 
@@ -282,7 +288,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 				}
 				fin = ((five >> mp) & (u64)1) && kbest < (maxL << 12);
 #ifdef LZ4_PROFILE_EVENTS
-				if (lane == 0) { atomicAdd(&g_lz4_prof[9], 1ull); atomicAdd(&g_lz4_prof[10], (unsigned long long)nst); }
+				if (lane == 0) { atomicAdd(&g_lz4_prof[LZ4_NEV + 2], 1ull); atomicAdd(&g_lz4_prof[LZ4_NEV + 3], (unsigned long long)nst); }
 #endif
 			}
 			if (fin) {
@@ -313,7 +319,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 					if ((kbest >> 12) == maxL || ~vmask) { break; }  // max_len reached / all older candidates seen
 				}
 #ifdef LZ4_PROFILE_EVENTS
-				if (lane == 0) { atomicAdd(&g_lz4_prof[7], (unsigned long long)nsteps); atomicAdd(&g_lz4_prof[8], (unsigned long long)ntail); }
+				if (lane == 0) { atomicAdd(&g_lz4_prof[LZ4_NEV], (unsigned long long)nsteps); atomicAdd(&g_lz4_prof[LZ4_NEV + 1], (unsigned long long)ntail); }
 #endif
 			}
 			if (lane == mp) { key = kbest; }
@@ -550,12 +556,22 @@ extern "C" void mscomp_amd_debug_lz_prof(unsigned long long* out, int reset)
 #define LZ4_B3 52u
 #endif
 __device__ __forceinline__ uint32_t lz4_seg_start(uint32_t j) { return j == 0 ? 0u : j == 1 ? LZ4_B1 : j == 2 ? LZ4_B2 : j == 3 ? LZ4_B3 : 64u; }
-// the sort's three parts (wave 0: batches [0, P1), wave 1: [P1, P2), wave 2: [P2, 64)); the count fields below fit their lengths
+// the sort's three parts (wave 0: batches [0, P1), wave 1: [P1, P2), wave 2: [P2, 64)). A part's count field is as wide as its length asks: 10 bits up
+// to 15 batches (960 positions), else 11 (up to 31 batches = 1 984); the three fields share one dword
+#ifndef LZ4_P1
 #define LZ4_P1 15u
 #define LZ4_P2 39u
-#define LZ4_PMAX 25u                                             // batches in the longest part
-static_assert(LZ4_P1 * 64u <= 0x3FFu && (LZ4_P2 - LZ4_P1) * 64u <= 0x7FFu && (64u - LZ4_P2) * 64u <= 0x7FFu, "a part fits its count field");
-static_assert(LZ4_P1 <= LZ4_PMAX && LZ4_P2 - LZ4_P1 <= LZ4_PMAX && 64u - LZ4_P2 == LZ4_PMAX, "LZ4_PMAX");
+#endif
+__host__ __device__ constexpr uint32_t lz4_max3(uint32_t a, uint32_t b, uint32_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
+__host__ __device__ constexpr uint32_t lz4_field_bits(uint32_t batches) { return batches * 64u <= 0x3FFu ? 10u : 11u; }
+#define LZ4_PMAX lz4_max3(LZ4_P1, LZ4_P2 - LZ4_P1, 64u - LZ4_P2)    // batches in the longest part
+#define LZ4_F0 lz4_field_bits(LZ4_P1)                               // field widths of parts 0, 1, 2 (part 0 at bit 0, the others behind it)
+#define LZ4_F1 lz4_field_bits(LZ4_P2 - LZ4_P1)
+#define LZ4_F2 lz4_field_bits(64u - LZ4_P2)
+static_assert(LZ4_P1 >= 1u && LZ4_P1 < LZ4_P2 && LZ4_P2 < 64u, "three parts, none empty");
+static_assert(LZ4_P1 * 64u <= (1u << LZ4_F0) - 1u && (LZ4_P2 - LZ4_P1) * 64u <= (1u << LZ4_F1) - 1u && (64u - LZ4_P2) * 64u <= (1u << LZ4_F2) - 1u, "a part fits its count field");
+static_assert(LZ4_F0 + LZ4_F1 + LZ4_F2 <= 32u, "the three fields share a dword");
+static_assert(LZ4_P1 <= LZ4_PMAX && LZ4_P2 - LZ4_P1 <= LZ4_PMAX && 64u - LZ4_P2 <= LZ4_PMAX, "LZ4_PMAX");
 #define LZ4_MAXM 22u                                             // matches that can START in one window of 64 positions
 #ifdef LZ4_PROFILE
 extern "C" void mscomp_amd_debug_lz4_prof(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lz4_prof), sizeof(unsigned long long) * LZ4_NPROF); unsigned long long z[LZ4_NPROF] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lz4_prof), z, sizeof z); }
@@ -617,10 +633,13 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	uint16_t* __restrict__ rec = recs + (u64)c * (LZNT1_REC / sizeof(uint16_t));
 
 #ifdef LZ4_PROFILE
-	unsigned long long z_prev = __builtin_readcyclecounter();
-#define LZ4_T(i) { const unsigned long long t_ = __builtin_readcyclecounter(); if (tid == 0) { atomicAdd(&g_lz4_prof[i], t_ - z_prev); } z_prev = t_; }
+	uint32_t z_prev; asm volatile("v_mov_b32 %0, %1" : "=v"(z_prev) : "s"((uint32_t)__builtin_readcyclecounter()));   // (the low dword: a phase is far below 2^32 cycles)
+	uint32_t z_acc = 0;                                                    // (lane i keeps slot i; the last time stamp in a vector register too: with scalar ones the build loses its eighth block)
+#define LZ4_T(i) { uint32_t t_; asm volatile("v_mov_b32 %0, %1" : "=v"(t_) : "s"((uint32_t)__builtin_readcyclecounter())); z_acc += lane == (i) ? t_ - z_prev : 0u; z_prev = t_; }
+#define LZ4_TEND { if (lane < LZ4_NSLOT) { atomicAdd(&g_lz4_prof[LZ4_NSLOT * wv + lane], (unsigned long long)z_acc); } }
 #else
 #define LZ4_T(i)
+#define LZ4_TEND
 #endif
 	// ---- A. stage the chunk, clear the count table (all waves) ------------------------------------------------------
 	{
@@ -630,34 +649,39 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		for (uint32_t i = n + tid; i < 4096u; i += 256u) { s_data[i] = 0; }
 		for (uint32_t i = tid * 4u; i < LZ_TBL; i += 1024u) { *reinterpret_cast<uint4*>(s_cw + i) = make_uint4(0, 0, 0, 0); }
 	}
-	__syncthreads();
 	LZ4_T(0)
+	__syncthreads();
+	LZ4_T(1)
 	// ---- B. position-sorted buckets: a stable counting sort by hash, ONE returning atomic per position, three waves at once -------
 	// The chunk's 64 batches of 64 positions are three consecutive parts -- batches [0, 15), [15, 39), [39, 64) = 960 / 1536 / 1600
 	// positions, for waves 0 / 1 / 2 -- and a bucket's count word holds one counter per part: 10 bits for part 0, 11 bits each for parts
-	// 1 and 2. A field cannot count past its part's length (960 <= 1023, 1600 <= 2047), so nothing carries into a neighbour and there is
-	// no overflow path. The 4096 words lie over the bucket array and the table union behind it (16 KiB, both dead until B3 / B4).
+	// 1 and 2 (LZ4_F0 / F1 / F2 follow the parts' lengths). A field cannot count past its part's length (960 <= 1023, 1600 <= 2047), so
+	// nothing carries into a neighbour and there is no overflow path. Other splits (round 12, headline MB/s against 69 1xx for this one):
+	// 25 / 24 / 15 69 158 / 68 902, 27 / 22 / 15 69 002 / 69 082, 29 / 20 / 15 68 569 / 68 832 -- wave 0 without a re-read gains nothing from a longer part. The 4096 words lie over the bucket array and the table union behind it (16 KiB, both dead until B3 / B4).
 	//   B1. a wave walks its part in ascending batches and adds 1 to its field. What the atomic returns in that field is the position's
 	//       rank among the same-hash positions of its PART: batches of a wave execute in order, the lanes of one DS instruction are served
-	//       in lane order (what `serial` replaces), and the other waves' adds go to other fields. Ranks stay in registers, two per VGPR.
-	//   B2. the counts are final: waves 1 and 2 add the counts of the parts in front of their own to their ranks; every thread takes
+	//       in lane order (what `serial` replaces), and the other waves' adds go to other fields. This is the only pass that HASHES a position
+	//       (unaligned dword read, mask, multiply, shift, select for hash 0): hash and rank stay in one register per position, hash << 12 | rank.
+	//   B2. the counts are final: waves 1 and 2 add the counts of the parts in front of their own to their ranks -- the count word is read at
+	//       the hash kept in the register; the sum stays below 4 096, so nothing carries into the hash; every thread takes
 	//       the words of 16 consecutive buckets and sums them; waves 0 and 1 leave their totals in the two halves of word 0 (bucket 0 is
 	//       always empty, lz_hash), wave 3's prefix is the chunk's number of keys minus its own total: no barrier for the partial sums.
 	//   B3. every table word has been read: a thread writes the ENDS of its 16 buckets as 12-bit fields (6 dwords at 24 tid), and the
 	//       control words are initialised behind them.
-	//   B4. scatter with plain stores: bucket[end[h - 1] + rank] = p.
+	//   B4. scatter with plain stores: bucket[end[h - 1] + rank] = p, h and rank from the register.
 	// Wave 3 has no part: it stages, scans and packs with the others.
 	{
 		const uint32_t nb = (n + 63u) >> 6;
 		const uint32_t pb0 = wv == 0 ? 0u : wv == 1u ? LZ4_P1 : wv == 2u ? LZ4_P2 : 64u;     // my part: batches [pb0, pb1)
 		const uint32_t pe = wv == 0 ? LZ4_P1 : wv == 1u ? LZ4_P2 : 64u;
 		const uint32_t pb1 = pe < nb ? pe : nb;
-		const uint32_t fsh = wv == 0 ? 0u : wv == 1u ? 10u : 21u, fm = wv == 0 ? 0x3FFu : 0x7FFu;   // my field
-		uint32_t rk[(LZ4_PMAX + 1u) / 2u];
+		const uint32_t fsh = wv == 0 ? 0u : wv == 1u ? LZ4_F0 : LZ4_F0 + LZ4_F1;          // my field
+		const uint32_t fm = (1u << (wv == 0 ? LZ4_F0 : wv == 1u ? LZ4_F1 : LZ4_F2)) - 1u;
+		uint32_t hr[LZ4_PMAX];                                            // per position of mine: hash << 12 | rank
 		#pragma unroll
-		for (uint32_t i = 0; i < (LZ4_PMAX + 1u) / 2u; ++i) { rk[i] = 0; }
+		for (uint32_t i = 0; i < LZ4_PMAX; ++i) { hr[i] = 0; }
 		// B1. rounds of 8 batches: their atomics are issued back to back (DS operations of a wave execute in order; the wavefront-scope
-		// form keeps the compiler from waiting for each one). An inactive lane's rank stays 0.
+		// form keeps the compiler from waiting for each one). An inactive lane's rank stays 0. This is the ONLY place that hashes a position.
 		#pragma unroll
 		for (uint32_t j0 = 0; j0 < LZ4_PMAX; j0 += 8u) {
 			if (pb0 + j0 < pb1) {
@@ -669,21 +693,25 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 					if (j0 + j < LZ4_PMAX) { const uint32_t b = pb0 + j0 + j; old[j] = lz_ordered_add<serial>(s_cw + h[j], 1u << fsh, b < pb1 && b * 64u + lane + 2u < n, lane); }
 				}
 				#pragma unroll
-				for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { rk[(j0 + j) >> 1] |= ((old[j] >> fsh) & fm) << (16u * ((j0 + j) & 1u)); } }
+				for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { hr[j0 + j] = (h[j] << 12) | ((old[j] >> fsh) & fm); } }
 			}
 		}
+		LZ4_T(2)
 		__syncthreads();
-		// B2. (a lane without a key has rank 0 and adds at most 1023 + 2047 of some other bucket: nothing carries into the upper half)
+		LZ4_T(3)
+		// B2. (a lane without a key has rank 0 and adds at most the lengths of parts 0 and 1 of some other bucket, below 4 096: nothing carries into
+		// the hash above the rank)
+		static_assert(LZ4_P2 * 64u < 4096u, "rank + counts in front stay in 12 bits");
 		if (wv == 1u || wv == 2u) {
-			const uint32_t m1 = wv == 2u ? 0x7FFu : 0u;
+			const uint32_t m1 = wv == 2u ? (1u << LZ4_F1) - 1u : 0u;
 			#pragma unroll
 			for (uint32_t j0 = 0; j0 < LZ4_PMAX; j0 += 8u) {
 				if (pb0 + j0 < pb1) {
 					uint32_t w[8];
 					#pragma unroll
-					for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { w[j] = s_cw[lz_hash(lds_ld32(s_data, ((pb0 + j0 + j) * 64u + lane) & 4095u) & 0xFFFFFFu)]; } }
+					for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { w[j] = s_cw[hr[j0 + j] >> 12]; } }
 					#pragma unroll
-					for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { rk[(j0 + j) >> 1] += ((w[j] & 0x3FFu) + ((w[j] >> 10) & m1)) << (16u * ((j0 + j) & 1u)); } }
+					for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { hr[j0 + j] += (w[j] & ((1u << LZ4_F0) - 1u)) + ((w[j] >> LZ4_F0) & m1); } }
 					__builtin_amdgcn_sched_barrier(0);                        // (the rounds are independent: merged, their reads in flight cost the eighth block's registers)
 				}
 			}
@@ -694,7 +722,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			const uint4 a = reinterpret_cast<const uint4*>(s_cw)[4u * tid + k];
 			uint32_t x[4] = { a.x, a.y, a.z, a.w };
 			#pragma unroll
-			for (uint32_t i = 0; i < 4u; ++i) { x[i] = (x[i] & 0x3FFu) + ((x[i] >> 10) & 0x7FFu) + (x[i] >> 21); }
+			for (uint32_t i = 0; i < 4u; ++i) { x[i] = (x[i] & ((1u << LZ4_F0) - 1u)) + ((x[i] >> LZ4_F0) & ((1u << LZ4_F1) - 1u)) + (x[i] >> (LZ4_F0 + LZ4_F1)); }
 			if (k == 0 && tid == 0) { x[0] = 0; }                          // (word 0 counts nothing: it carries the wave totals)
 			sum += (x[0] + x[1]) + (x[2] + x[3]);
 			tot[2u * k] = x[0] | (x[1] << 16); tot[2u * k + 1u] = x[2] | (x[3] << 16);
@@ -703,7 +731,9 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		const uint32_t incl = wave_incl_scan_add_u32(sum);
 		const uint32_t wtot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 		if (lane == 63u && wv < 2u) { reinterpret_cast<uint16_t*>(s_cw)[wv] = (uint16_t)wtot; }
+		LZ4_T(4)
 		__syncthreads();
+		LZ4_T(5)
 		// B3.
 		{
 			const uint32_t x = s_cw[0];
@@ -724,7 +754,9 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			if (tid < 16u) { reinterpret_cast<uint32_t*>(s_rep)[tid] = 0; }
 			if (tid == 0) { s_segctr = 0; }
 		}
+		LZ4_T(6)
 		__syncthreads();
+		LZ4_T(7)
 		// B4. (start(h): the lookup of lz_window<true>)
 		#pragma unroll
 		for (uint32_t j0 = 0; j0 < LZ4_PMAX; j0 += 8u) {
@@ -733,7 +765,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 				#pragma unroll
 				for (uint32_t j = 0; j < 8u; ++j) {
 					if (j0 + j < LZ4_PMAX) {
-						const uint32_t bit = lz_hash(lds_ld32(s_data, ((pb0 + j0 + j) * 64u + lane) & 4095u) & 0xFFFFFFu) * 12u - 12u;
+						const uint32_t bit = (hr[j0 + j] >> 12) * 12u - 12u;          // (every lane of a round that ran holds a hash >= 1, active or not)
 						const uint32_t* const t = L.t.parse.ends + (bit >> 5);
 						st[j] = __builtin_amdgcn_alignbit(t[1], t[0], bit) & 0xFFFu;
 					}
@@ -742,15 +774,16 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 				for (uint32_t j = 0; j < 8u; ++j) {
 					if (j0 + j < LZ4_PMAX) {
 						const uint32_t b = pb0 + j0 + j, p = b * 64u + lane;
-						if (b < pb1 && p + 2u < n) { s_bucket[st[j] + ((rk[(j0 + j) >> 1] >> (16u * ((j0 + j) & 1u))) & 0xFFFFu)] = (uint16_t)p; }
+						if (b < pb1 && p + 2u < n) { s_bucket[st[j] + (hr[j0 + j] & 0xFFFu)] = (uint16_t)p; }
 					}
 				}
 			}
 		}
 	}
+	LZ4_T(8)
 	__syncthreads();
 	const uint32_t* const tbl = L.t.parse.ends;
-	LZ4_T(1)
+	LZ4_T(9)
 
 	// ---- C1. speculative parse of my segment ------------------------------------------------------------------------
 	const uint32_t nw = (n + 63u) >> 6;
@@ -804,10 +837,9 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			}
 		}
 	}
-	LZ4_T(2)
-	LZ4_T(3)
+	LZ4_T(10)
 	__syncthreads();
-	LZ4_T(4)
+	LZ4_T(11)
 	// ---- C3. (wave 0) cascade check, then tokens / bytes before every window -----------------------------------------
 	if (wv == 0) {
 		for (uint32_t j = 1; j < LZ4_NSEG && lz4_seg_start(j) < nw; ++j) {
@@ -829,8 +861,33 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			wave_fence();
 		}
 	}
+	LZ4_T(12)
 	__syncthreads();                                              // the packed ends are dead from here on: prefixes and flags take their place
+	LZ4_T(13)
 	for (uint32_t i = tid; i < 512u; i += 256u) { s_flagacc[i] = 0; }
+	// ---- D0. the match tokens of my 16 windows, from the records in global memory (L2-warm: written by this block) into my piece of the dead
+	// bucket array, in ONE coalesced pass of dwords (a window's LZ4_MAXM tokens are 11 dwords; 176 per wave = three loads per lane, all in
+	// flight together, under wave 0's scans). Lane l < 16 knows window w0 + l: how many matches start in it and which area holds its tokens;
+	// a dword is fetched only if the window has a token for it. The emission loop then reads LDS alone.
+	static_assert(LZNT1_SLOT <= 0xFFFFFFFFu && (LZ4_MAXM & 1u) == 0 && LZ4_NSEG * 16u * LZ4_MAXM <= 4096u, "a window's tokens are whole dwords; four pieces fit the bucket array");
+	uint32_t* const s_ptk = reinterpret_cast<uint32_t*>(s_bucket) + wv * (16u * LZ4_MAXM / 2u);
+#ifndef LZ4_PROBE_EMIT
+	{
+		const uint32_t wl0 = w0 + (lane & 15u);
+		const uint32_t info = wl0 < w1 ? (uint32_t)__popcll(s_mat[wl0]) | ((uint32_t)s_rep[wl0] << 8) : 0u;
+		const uint32_t* __restrict__ const rec32 = reinterpret_cast<const uint32_t*>(rec);
+		uint32_t v[3]; bool ld[3];
+		#pragma unroll
+		for (uint32_t k = 0; k < 3u; ++k) {
+			const uint32_t idx = lane + 64u * k, wl = idx / (LZ4_MAXM / 2u), m2 = idx - wl * (LZ4_MAXM / 2u);
+			const uint32_t inf = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(wl * 4u), (int)info);
+			ld[k] = idx < 16u * LZ4_MAXM / 2u && 2u * m2 < (inf & 0xFFu);
+			v[k] = ld[k] ? rec32[((inf >> 8) * 64u + w0 + wl) * (LZ4_MAXM / 2u) + m2] : 0u;
+		}
+		#pragma unroll
+		for (uint32_t k = 0; k < 3u; ++k) { if (ld[k]) { s_ptk[lane + 64u * k] = v[k]; } }
+	}
+#endif
 	if (wv == 0) {
 		const u64 tm = lane < nw ? s_tok[lane] : (u64)0, mk = lane < nw ? s_mat[lane] : (u64)0;
 		const uint32_t nt = (uint32_t)__popcll(tm), ns = nt + (uint32_t)__popcll(mk);
@@ -838,24 +895,18 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		s_T[lane] = (uint16_t)(ti - nt); s_S[lane] = (uint16_t)(si - ns);
 		if (lane == 63u) { s_total[0] = ti; s_total[1] = si; }
 	}
+	LZ4_T(14)
 	__syncthreads();
-	LZ4_T(5)
+	LZ4_T(15)
 	const uint32_t T = s_total[0], S = s_total[1];
 	const uint32_t csize = ((T + 7u) >> 3) + S;
 	uint32_t total;
 	if (csize < n) {
 		// ---- D1. emission of my windows: pos(t) = 2 (header) + (t div 8 + 1) + sum size(u<t) --------------------------
-		// the match tokens come from global memory (L2-warm: written by this block): the next window's read is issued before this
-		// window's emission, so that two are in flight
-		const auto ptok_of = [&](uint32_t w) -> uint32_t {
-			const u64 matchmask = s_mat[w];
-			return ((matchmask >> lane) & (u64)1) ? (uint32_t)rec[((uint32_t)s_rep[w] * 64u + w) * LZ4_MAXM + popc_below(matchmask)] : 0u;
-		};
-		uint32_t ptk_next = w0 < w1 ? ptok_of(w0) : 0u;
+		// the match tokens come from my piece of LDS (D0): token k of window w at 16-bit index (w - w0) LZ4_MAXM + k. No global load and no
+		// dependent LDS read sit in the loop; the byte stores address the chunk's slot with one scalar base and 32-bit offsets.
 		#pragma unroll 1
 		for (uint32_t w = w0; w < w1; ++w) {
-			const uint32_t ptk = ptk_next;
-			if (w + 1u < w1) { ptk_next = ptok_of(w + 1u); }
 			const u64 tokmask = s_tok[w];
 			if (tokmask == 0) { continue; }
 			const u64 matchmask = s_mat[w];
@@ -866,13 +917,19 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			if (is_tok) {
 				if ((t & 7u) == 0) { s_flagpos[t >> 3] = (uint16_t)(pos - 1u); }
 				if (is_m) {
-					const uint32_t tok = ptk;
+#ifdef LZ4_PROBE_EMIT   // dev-only, NOT exact, timing only: the emission without any token read
+					const uint32_t tok = 0x1003u;
+#else
+					const uint32_t tok = reinterpret_cast<const uint16_t*>(s_ptk)[(w - w0) * LZ4_MAXM + mbl];
+#endif
 					img[pos] = (uint8_t)tok; img[pos + 1u] = (uint8_t)(tok >> 8);
 					atomicOr(&s_flagacc[t >> 3], 1u << (t & 7u));
 				} else { img[pos] = s_data[w * 64u + lane]; }
 			}
 		}
+		LZ4_T(16)
 		__syncthreads();
+		LZ4_T(17)
 		for (uint32_t g = tid; g < ((T + 7u) >> 3); g += 256u) { img[s_flagpos[g]] = (uint8_t)s_flagacc[g]; }
 		if (tid == 0) { img[0] = (uint8_t)(0xB000u | (csize - 1u)); img[1] = (uint8_t)((0xB000u | (csize - 1u)) >> 8); }
 		total = 2u + csize;
@@ -884,7 +941,8 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		total = 2u + n;
 	}
 	if (tid == 0) { slot_size[c] = total; }
-	LZ4_T(6)
+	LZ4_T(18)
+	LZ4_TEND
 #undef LZ4_WINDOW
 }
 

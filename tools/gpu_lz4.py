@@ -35,12 +35,15 @@ if hasattr(lib, "mscomp_amd_debug_lz4_prof") or True:
     import ctypes as C
     try:
         lib.mscomp_amd_debug_set_lznt1(2)
-        buf = (C.c_ulonglong * 16)(); lib.mscomp_amd_debug_lz4_prof(buf)
+        NSLOT = 20                                  # (lznt1.hip LZ4_NSLOT: per wave, even slots work, odd slots the idle time in front of the next barrier)
+        buf = (C.c_ulonglong * (4 * NSLOT + 4))(); lib.mscomp_amd_debug_lz4_prof(buf)
         plan.execute(d_in, d_out, d_len, d_st); torch.cuda.synchronize(); lib.mscomp_amd_debug_lz4_prof(buf)
         nch = (n + 4095) // 4096
-        print("wave 0 cycles per chunk: load %.0f | sort %.0f | parse(seg 0) %.0f | seam %.0f | wait %.0f | cascade+scan %.0f | emit %.0f" % tuple(buf[i] / nch for i in range(7)))
-        print("per chunk (all windows walked): finishing steps %.1f | their lz_lcp_tail wave-iterations %.1f | long-pending stops %.1f | "
-              "cooperative 256-byte steps %.1f" % tuple(buf[i] / nch for i in range(7, 11)))
+        names = ["load", "B1 rank", "B2 re-read+sums", "B3 pack", "B4 scatter", "parse+seam", "cascade", "clear+scans", "stage+emit", "flags+header"]
+        for wv in range(4):
+            print("wave %d cycles per chunk, work (idle before the barrier): " % wv + " | ".join("%s %.0f (%.0f)" % (names[i], buf[NSLOT * wv + 2 * i] / nch, buf[NSLOT * wv + 2 * i + 1] / nch) for i in range(10)))
+        print("per chunk (all windows walked, -DLZ4_PROFILE_EVENTS): finishing steps %.1f | their lz_lcp_tail wave-iterations %.1f | long-pending stops %.1f | "
+              "cooperative 256-byte steps %.1f" % tuple(buf[4 * NSLOT + i] / nch for i in range(4)))
     except AttributeError:
         pass
     lib.mscomp_amd_debug_set_lznt1(0)
