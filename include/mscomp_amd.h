@@ -369,6 +369,31 @@ MSCompStatus mscomp_amd_compact_batch(mscomp_amd_ctx* ctx, size_t n_units, const
 MSCompStatus mscomp_amd_compact_dev(mscomp_amd_ctx* ctx, size_t n_units, const uint8_t* d_src, const uint64_t* d_src_off,
                                     const uint64_t* d_len, uint64_t align, uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_packed_off);
 
+/* CRC-32 of a batch in HBM, from device tables: d_crc[i] = the CRC-32 of zlib, PNG and Ethernet (reflected polynomial 0xEDB88320, initial value
+ * and final XOR 0xFFFFFFFF; 0 for an empty unit, 0xCBF43926 for "123456789") of the d_in_len[i] bytes at d_in + d_in_off[i]. Created once from
+ * bounds, as the other plans with device tables; n_units is fixed when the plan is created. Units may have any alignment, may overlap and may
+ * come in any order: they are only read. d_in_off, d_in_len: device arrays of n_units uint64; d_crc: n_units uint32; d_status: n_units int32.
+ *   Units that fail the check: a unit whose running total of d_in_len, up to and including it, exceeds in_total_max gets MSCOMP_ARG_ERROR and
+ *                 d_crc = 0, and nothing is read for it. Every other unit gets MSCOMP_OK. (Running totals stay at 2^64 - 1 once they get there.)
+ *   Execution:    asynchronous on the ctx stream: three kernel launches whose geometry is fixed by n_units and the device -- one block that
+ *                 checks and sums the lengths, a thread per unit that seeds d_crc, and a grid of 4 blocks per CU that cuts the batch's bytes into equal slices, so that one unit of
+ *                 50 MB is spread over every CU and 100 000 units of 40 bytes over the same grid; the parts of a unit are folded into d_crc[i]
+ *                 with atomic XORs, in any order, to the same bits. No memset or copy node, no allocation, no synchronisation, nothing read
+ *                 back. Plain launches while the ctx stream is being captured; otherwise a graph of its own from the second execution on.
+ *                 MSCOMP_ARG_ERROR for a null plan or array (d_in may be null when in_total_max is 0).
+ *   Plan kinds:   mscomp_amd_plan_execute, _execute_dev, _execute_size and _execute_size_dev return MSCOMP_ARG_ERROR for a CRC plan,
+ *                 mscomp_amd_plan_execute_crc_dev for any other plan, without enqueueing anything. mscomp_amd_plan_destroy frees it.
+ *   Creation:     MSCOMP_ARG_ERROR for a null ctx or plan pointer, n_units above 0x7FFFFFF0, or in_total_max of 2^50 or more (a unit's length
+ *                 times 8 is an exponent of 53 bits at most; a container's in_total_max is below 2^50 by its own checks); MSCOMP_MEM_ERROR when the tables (16 bytes per
+ *                 unit) cannot be reserved. They are reserved here, once.
+ * The kernel's sizes, for tests and for callers who lay out their units: a wave takes MSCOMP_AMD_CRC_ROW_BYTES per step (64 lanes with a run of
+ * 64 bytes each), in rows that end at the last 16-byte boundary of a unit's part; a slice is a multiple of MSCOMP_AMD_CRC_SLICE_BYTES. */
+#define MSCOMP_AMD_CRC_ROW_BYTES   4096u
+#define MSCOMP_AMD_CRC_SLICE_BYTES 16384u
+MSCompStatus mscomp_amd_plan_create_crc_dev(mscomp_amd_ctx* ctx, size_t n_units, uint64_t in_total_max, mscomp_amd_plan** plan);
+MSCompStatus mscomp_amd_plan_execute_crc_dev(mscomp_amd_plan* plan, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                             uint32_t* d_crc, int32_t* d_status);
+
 /* Block containers: the shape in which these codecs are deployed (WIM resources, WOF-compressed files, NTFS compression units). A resource
  * (one caller buffer) is cut into blocks of block_size bytes, every block is compressed on its own, a block that does not shrink is stored
  * raw, the stored blocks are packed back to back, and a table of offsets says where each one is -- so a reader who wants a range of a
@@ -380,7 +405,7 @@ MSCompStatus mscomp_amd_compact_dev(mscomp_amd_ctx* ctx, size_t n_units, const u
  *                 (mscomp_amd_blocks_bound) bounds the blocks of any batch whose lengths sum to at most in_total_max. All scratch is
  *                 reserved here, once, and never grows: a compress and a decompress dev plan for n_blocks_max units (of at most B bytes;
  *                 within in_total_max bytes in and out), the staging area of the compressed blocks -- 1 byte per byte of in_total_max + 16
- *                 per resource --, and 64 bytes of tables per possible block + 28 per resource. MSCOMP_ARG_ERROR for a null ctx or bk, a bad
+ *                 per resource --, and 68 bytes of tables per possible block + 28 per resource. MSCOMP_ARG_ERROR for a null ctx or bk, a bad
  *                 format, a bad block_size, non-zero flags, n_res above 0x7FFFFFF0; MSCOMP_MEM_ERROR when n_blocks_max exceeds 0x7FFFFFF0 or
  *                 the scratch cannot be reserved. The LZNT1 dictionary flavour is fixed here, as for a compress dev plan.
  *   Compress:     d_res_off, d_res_len, d_status: n_res entries; d_block_first: n_res + 1; d_block_off: n_blocks_max + 1.
@@ -414,7 +439,26 @@ MSCompStatus mscomp_amd_compact_dev(mscomp_amd_ctx* ctx, size_t n_units, const u
  *                 the caller captures the ctx stream, the first execution included (plain launches then); outside capture each of the two
  *                 calls replays a graph of its own from its second execution on, captured again when an argument changes.
  *                 MSCOMP_ARG_ERROR for a null bk or a null required array (d_in, d_packed and d_out may be null when in_total_max is 0,
- *                 d_range always). */
+ *                 d_range always).
+ *   Checksums:    the decoders check structure only, and a raw block is not checked at all: a flipped byte can decode to MSCOMP_OK. The two
+ *                 calls below keep a CRC-32 (as mscomp_amd_plan_execute_crc_dev's) per block beside the container and hold decoded data to it.
+ *                 The checksum is over the DATA, not the stored form: re-encoding a container with another codec or with another block size
+ *                 keeps every resource CRC, and with the same block size every block CRC. They use the container's tables and 4 bytes more
+ *                 per possible block, reserved at creation.
+ *                 Crc: d_data, d_res_off, d_res_len as compress's input -- run it on that input before compress, or on anything else of the
+ *                 same lengths. Resources are accepted and rejected as compress does it (MSCOMP_ARG_ERROR, no blocks, nothing read), blocks
+ *                 numbered by the same running count: d_block_crc[j] (n_blocks_max entries) belongs to the block compress puts at
+ *                 d_block_off[j]; the entries at or behind the real count are 0. d_res_crc (n_res entries, may be NULL): the CRC-32 of every
+ *                 whole resource, 0 for a rejected one -- from the same pass over the bytes, every part of a block being folded in a second
+ *                 time at its distance to the resource's end. d_status (n_res): MSCOMP_OK or MSCOMP_ARG_ERROR.
+ *                 Check: after decompress, with the same d_res_len, d_block_first, d_range and d_out_off, and decompress's d_out_len and
+ *                 d_status (in and out). A resource whose d_status is not MSCOMP_OK on entry is left alone and nothing of it is read. A
+ *                 resource that is MSCOMP_OK is held to checks 1 and 2 above (the same statuses, d_out_len = 0); then block k of its clipped
+ *                 range is read at d_out + d_out_off[r] + k B and its CRC-32 compared with d_block_crc[d_block_first[r] + f + k]. Any
+ *                 mismatch: MSCOMP_DATA_ERROR, d_out_len[r] = 0. A resource that passes is not written, nor is any other resource.
+ *                 Both run as the other two calls do (a fixed launch sequence of kernels; legal inside a capture from the first execution;
+ *                 a graph of their own otherwise). MSCOMP_ARG_ERROR for a null bk or a null required array (d_data / d_out may be null when
+ *                 in_total_max is 0; d_res_crc and d_range always). */
 typedef struct mscomp_amd_blocks mscomp_amd_blocks;
 MSCompStatus mscomp_amd_blocks_create(mscomp_amd_ctx* ctx, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t in_total_max,
                                       uint32_t flags, mscomp_amd_blocks** bk);
@@ -428,6 +472,11 @@ MSCompStatus mscomp_amd_blocks_decompress(mscomp_amd_blocks* bk, const uint8_t* 
                                           const uint64_t* d_range,
                                           uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
                                           uint64_t* d_out_len, int32_t* d_status);
+MSCompStatus mscomp_amd_blocks_crc(mscomp_amd_blocks* bk, const uint8_t* d_data, const uint64_t* d_res_off, const uint64_t* d_res_len,
+                                   uint32_t* d_block_crc /* n_blocks_max */, uint32_t* d_res_crc /* n_res, may be NULL */, int32_t* d_status);
+MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* bk, const uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_res_len,
+                                     const uint64_t* d_block_first, const uint64_t* d_range, const uint32_t* d_block_crc,
+                                     uint64_t* d_out_len, int32_t* d_status /* in and out */);
 
 /* ---- measurement hooks (bench.py / profiles) ---- */
 /* When enabled, every kernel launch of plan_execute is bracketed by hipEvents on the ctx stream. */

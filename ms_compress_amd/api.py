@@ -40,6 +40,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_plan_create_size_dev", "mscomp_amd_plan_execute_size_dev", "mscomp_amd_compact_dev",
     "mscomp_amd_plan_create_decompress_dev_ex", "mscomp_amd_plan_create_size_dev_ex", "mscomp_amd_debug_plan_paths",
     "mscomp_amd_blocks_create", "mscomp_amd_blocks_destroy", "mscomp_amd_blocks_bound", "mscomp_amd_blocks_compress", "mscomp_amd_blocks_decompress",
+    "mscomp_amd_plan_create_crc_dev", "mscomp_amd_plan_execute_crc_dev", "mscomp_amd_blocks_crc", "mscomp_amd_blocks_check",
 ]
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 
@@ -141,6 +142,14 @@ def load_library():
     lib.mscomp_amd_blocks_compress.restype = C.c_int
     lib.mscomp_amd_blocks_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9
     lib.mscomp_amd_blocks_decompress.restype = C.c_int
+    lib.mscomp_amd_plan_create_crc_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_plan_create_crc_dev.restype = C.c_int
+    lib.mscomp_amd_plan_execute_crc_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+    lib.mscomp_amd_plan_execute_crc_dev.restype = C.c_int
+    lib.mscomp_amd_blocks_crc.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+    lib.mscomp_amd_blocks_crc.restype = C.c_int
+    lib.mscomp_amd_blocks_check.argtypes = [C.c_void_p] + [C.c_void_p] * 8
+    lib.mscomp_amd_blocks_check.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -432,6 +441,26 @@ class SizeDevPlan(DevPlan):
             raise MSCompError(st, "mscomp_amd_plan_execute_size_dev")
 
 
+class CrcDevPlan(DevPlan):
+    """A CRC-32 plan with device tables (mscomp_amd_plan_create_crc_dev): made once for n_units units whose lengths sum to at most
+    in_total_max, then executed with unit tables that live on the device. The value is zlib's crc32."""
+
+    def __init__(self, ctx, n_units, in_total_max):
+        self.ctx, self.n_units, self.in_total_max = ctx, int(n_units), int(in_total_max)
+        self._h = C.c_void_p()
+        st = ctx.lib.mscomp_amd_plan_create_crc_dev(ctx._h, self.n_units, self.in_total_max, C.byref(self._h))
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_plan_create_crc_dev")
+
+    def execute(self, d_in, d_in_off, d_in_len, d_crc, d_status):
+        """Enqueue on the ctx stream (nothing is synchronized or read back). Arguments are torch CUDA tensors: uint8 input, int64 / uint64
+        offsets and lengths of n_units entries, int32 d_crc (the 32 bits of each CRC) and int32 d_status."""
+        ptrs = [C.c_void_p(t.data_ptr()) for t in (d_in, d_in_off, d_in_len, d_crc, d_status)]
+        st = self.ctx.lib.mscomp_amd_plan_execute_crc_dev(self._h, *ptrs)
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_plan_execute_crc_dev")
+
+
 class BlockContainer:
     """A block container (mscomp_amd_blocks_create): resources cut into blocks of ``block_size`` bytes (a power of two, 4096 .. 524288), every
     block compressed on its own or stored raw when it does not shrink, the stored blocks packed back to back behind an offset table. Made
@@ -475,6 +504,23 @@ class BlockContainer:
         st = self.ctx.lib.mscomp_amd_blocks_decompress(self._h, p[0], plen, *p[1:])
         if st != MSCOMP_OK:
             raise MSCompError(st, "mscomp_amd_blocks_decompress")
+
+    def crc(self, d_data, d_res_off, d_res_len, d_block_crc, d_status, d_res_crc=None):
+        """CRC-32 of the uncompressed blocks of the resources (as compress takes them): d_block_crc (int32, n_blocks_max; entry j belongs to the
+        block compress puts at d_block_off[j], the entries behind the last block are 0), d_res_crc (optional, int32, n_res: the CRC-32 of
+        every whole resource, from the same pass) and d_status (n_res: MSCOMP_OK, or MSCOMP_ARG_ERROR as compress gives it)."""
+        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_data, d_res_off, d_res_len, d_block_crc, d_res_crc, d_status)]
+        st = self.ctx.lib.mscomp_amd_blocks_crc(self._h, *p)
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_blocks_crc")
+
+    def check(self, d_out, d_out_off, d_res_len, d_block_first, d_block_crc, d_out_len, d_status, d_range=None):
+        """After decompress, with its tables and results: every block of the (clipped) range of every resource that is MSCOMP_OK in d_status
+        is read back from d_out and held to d_block_crc; a mismatch turns the resource into MSCOMP_DATA_ERROR with d_out_len = 0."""
+        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status)]
+        st = self.ctx.lib.mscomp_amd_blocks_check(self._h, *p)
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_blocks_check")
 
     def close(self):
         if self._h:
@@ -521,10 +567,62 @@ def blocks_compress(fmt, buffers, block_size, ctx=None):
     return packed, first, boff, st
 
 
-def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, ranges=None, ctx=None):
+def crc32_units(units, ctx=None):
+    """zlib's crc32 of every byte string of a list, computed on the GPU (CrcDevPlan). Returns a numpy uint32 array."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    n = len(units)
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        d_in, in_off, lens = _upload_units(units, dev)
+        d_off = torch.from_numpy(np.ascontiguousarray(in_off, dtype=np.uint64).view(np.int64).copy()).to(dev) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        d_len = torch.tensor(lens or [0], dtype=torch.int64, device=dev)
+        d_crc = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        plan = CrcDevPlan(ctx, n, int(sum(lens)))
+        plan.execute(d_in, d_off, d_len, d_crc, d_st)
+        ctx.stream.synchronize()
+        out, st = d_crc.cpu().numpy().view(np.uint32)[:n].copy(), d_st.cpu().numpy()[:n]
+        plan.close()
+    if own:
+        ctx.close()
+    if st.any():
+        raise MSCompError(int(st[st != 0][0]), "mscomp_amd_plan_execute_crc_dev")
+    return out
+
+
+def blocks_crc(fmt, buffers, block_size, ctx=None):
+    """The checksums a block container keeps beside a list of byte strings (one resource each), computed on the GPU. Returns numpy uint32
+    arrays (block_crc of nb entries, in the block order of blocks_compress; res_crc of n): zlib's crc32 of every block and of every resource."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    n = len(buffers)
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        d_in, in_off, lens = _upload_units(buffers, dev)
+        bk = BlockContainer(ctx, fmt, block_size, n, int(sum(lens)))
+        d_off = torch.from_numpy(np.ascontiguousarray(in_off, dtype=np.uint64).view(np.int64).copy()).to(dev) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+        d_len = torch.tensor(lens or [0], dtype=torch.int64, device=dev)
+        d_bcrc = torch.zeros(max(1, bk.n_blocks_max), dtype=torch.int32, device=dev)
+        d_rcrc = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        bk.crc(d_in, d_off, d_len, d_bcrc, d_st, d_res_crc=d_rcrc)
+        ctx.stream.synchronize()
+        nb = sum((x + block_size - 1) // block_size for x in lens)
+        out = d_bcrc.cpu().numpy().view(np.uint32)[:nb].copy(), d_rcrc.cpu().numpy().view(np.uint32)[:n].copy()
+        bk.close()
+    if own:
+        ctx.close()
+    return out
+
+
+def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, ranges=None, ctx=None, block_crc=None):
     """Decode resources of a block container on the GPU: ``lengths`` are the resources' original lengths, ``ranges`` (optional) one
-    (first block, count) pair per resource, clipped to its blocks; default: whole resources. Returns (list of bytes, or None where the status
-    is not MSCOMP_OK; list of status)."""
+    (first block, count) pair per resource, clipped to its blocks; default: whole resources. ``block_crc`` (optional, as blocks_crc returns
+    it): the decoded blocks are held to these checksums, and a resource with a mismatch gets MSCOMP_DATA_ERROR. Returns (list of bytes, or
+    None where the status is not MSCOMP_OK; list of status)."""
     import torch
     own = ctx is None
     ctx = ctx or Context()
@@ -551,6 +649,12 @@ def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, 
         d_olen = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
         d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         bk.decompress(d_packed, d_first, d_boff, d_len, d_out, d_ooff, d_ocap, d_olen, d_st, d_range=d_range, packed_len=len(packed))
+        if block_crc is not None:
+            h_crc = np.zeros(max(1, bk.n_blocks_max), dtype=np.uint32)
+            k = min(len(block_crc), len(h_crc))
+            h_crc[:k] = np.asarray(block_crc, dtype=np.uint32)[:k]
+            d_crc = torch.from_numpy(h_crc.view(np.int32).copy()).to(dev)
+            bk.check(d_out, d_ooff, d_len, d_first, d_crc, d_olen, d_st, d_range=d_range)
         ctx.stream.synchronize()
         h_out, h_len, h_st = d_out.cpu().numpy(), d_olen.cpu().numpy(), d_st.cpu().numpy()
         bk.close()

@@ -56,6 +56,7 @@ const uint32_t XH_FB_BLOCKS = 256;                     // persistent blocks of t
 struct mscomp_amd_ctx {
 	int device = 0;
 	uint32_t cpd_blocks = 0;                           // the fixed grid of mscomp_amd_compact_dev on this device (asked once, here: never inside a capture)
+	uint32_t crc_blocks = 0;                           // ... and that of the CRC kernel (crc32.hip)
 	hipStream_t stream = nullptr;
 	DevBuf slots, slot_size, prefix, tile_sums;        // chunk scratch (grow-only, shared by all plans of the ctx)
 	DevBuf lzrec;                                      // LZNT1 parse records per chunk (LZNT1_REC bytes: match tokens per window)
@@ -96,6 +97,7 @@ struct mscomp_amd_plan {
 	bool decompress = false;
 	bool sizing = false;                               // a decompressed-size plan (mscomp_amd_plan_create_size): out_cap holds the limits, nothing is decoded
 	bool dev = false;                                  // a plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev / _compress_dev; with sizing: _size_dev)
+	bool crc = false;                                  // a CRC plan (mscomp_amd_plan_create_crc_dev): a dev plan without a format; tables = cum (u64 x (n_units + 1)) | off (u64 x n_units)
 	bool large = false;                                // ... with MSCOMP_AMD_DEV_LARGE_UNITS: the tables of the optional paths are built there too (xhc_scr, lzg_*, xps_big / xps_seg hold the bounds
 	                                                   // they were reserved for, 0 = the path is off for the plan; the counts of an execution are in xps_cnt / lzg_cnt, device memory)
 	uint32_t* xps_cnt = nullptr; uint32_t* lzg_cnt = nullptr;   // (behind the prefix arrays of xps_tab / lzg_tab)
@@ -227,6 +229,7 @@ MSCompStatus mscomp_amd_ctx_create(int device, void* hip_stream, mscomp_amd_ctx*
 	if (!c) { return MSCOMP_MEM_ERROR; }
 	c->device = device; c->stream = (hipStream_t)hip_stream;
 	c->cpd_blocks = compact_dev_blocks();
+	c->crc_blocks = crc_dev_blocks();
 	*out = c;
 	return MSCOMP_OK;
 }
@@ -1080,7 +1083,7 @@ static void dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* 
 MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                          uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
 {
-	if (!p || !p->dev || p->sizing) { return MSCOMP_ARG_ERROR; }
+	if (!p || !p->dev || p->sizing || p->crc) { return MSCOMP_ARG_ERROR; }
 	if (p->n_units && (!d_in_off || !d_in_len || !d_out_off || !d_out_cap || !d_out_len || !d_status)) { return MSCOMP_ARG_ERROR; }
 	if ((p->in_total_max && !d_in) || (p->out_total_max && !d_out)) { return MSCOMP_ARG_ERROR; }
 	if (!p->decompress && p->n_units && !d_out) { return MSCOMP_ARG_ERROR; }   // (a compress plan has no output bound: an empty unit may get LZNT1's 00 00)
@@ -1115,6 +1118,42 @@ MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* p, const uint8_t*
 		// rejected units; and need = length where the kernels above did not write it (LZNT1's finalize did) -- a kernel, where a host size plan
 		// ends with a copy: no memcpy node in a caller's graph
 		{ KernelTimer t(c, "dv_size_finish_kernel"); launch_dev_size_finish(c->stream, p->reject, p->n_units, d_out_len, d_need, d_status, p->format != MSCOMP_LZNT1); }
+	});
+}
+
+// ---- CRC-32 of a batch in HBM (include/mscomp_amd.h; kernels: crc32.hip) ----
+MSCompStatus mscomp_amd_plan_create_crc_dev(mscomp_amd_ctx* c, size_t n_units, uint64_t in_total_max, mscomp_amd_plan** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || n_units > 0x7FFFFFF0u || in_total_max >= (1ull << 50)) { return MSCOMP_ARG_ERROR; }   // (distances to a unit's end stay below 2^50: crc32.hip crc_xpow)
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());
+	if (!p) { return MSCOMP_MEM_ERROR; }
+	p->ctx = c; p->dev = true; p->crc = true; p->n_units = (uint32_t)n_units; p->in_total_max = in_total_max; p->total_in = in_total_max;
+	if (!p->tables.reserve((2 * n_units + 1) * 8)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	*out = p.release();
+	return MSCOMP_OK;
+}
+
+MSCompStatus mscomp_amd_plan_execute_crc_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                             uint32_t* d_crc, int32_t* d_status)
+{
+	if (!p || !p->crc) { return MSCOMP_ARG_ERROR; }
+	if (p->n_units && (!d_in_off || !d_in_len || !d_crc || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if (p->in_total_max && !d_in) { return MSCOMP_ARG_ERROR; }
+	if (p->n_units == 0) { return MSCOMP_OK; }
+	mscomp_amd_ctx* c = p->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	p->ran = true;
+	const void* args[5] = { d_in, d_in_off, d_in_len, d_crc, d_status };
+	return plan_run(p, args, [&] {
+		u64* cum = static_cast<u64*>(p->tables.p); u64* off = cum + p->n_units + 1u;
+		{ KernelTimer t(c, "crc_tables_kernel"); launch_crc_tables(c->stream, p->n_units, p->in_total_max, d_in_off, d_in_len, off, cum, d_status); }
+		{ KernelTimer t(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, p->n_units, cum, d_crc, nullptr, nullptr); }
+		{ KernelTimer t(c, "crc_kernel"); launch_crc_units(c->stream, p->n_units, d_in, off, cum, d_crc, nullptr, nullptr, nullptr, c->crc_blocks); }
 	});
 }
 
@@ -1200,7 +1239,7 @@ struct mscomp_amd_blocks {
 	uint32_t shift = 0, n_res = 0, n_blocks = 0;       // block_size = 1 << shift; n_blocks = n_blocks_max
 	uint64_t in_total_max = 0;
 	mscomp_amd_plan* cplan = nullptr; mscomp_amd_plan* dplan = nullptr;   // (null when n_blocks is 0)
-	mscomp_amd_plan crun, drun;
+	mscomp_amd_plan crun, drun, krun, vrun;            // (krun: mscomp_amd_blocks_crc, vrun: _check)
 	DevBuf tab, stage;                                 // BlocksTab; staged compressed blocks: in_total_max + 16 n_res bytes
 	BlocksTab t{};
 };
@@ -1212,7 +1251,7 @@ static void blocks_tab(mscomp_amd_blocks* b)
 	BlocksTab& t = b->t;
 	t.res_a = q; t.res_b = q + n; t.unit_first = q + 2 * n; q += 3 * n + 1;
 	t.in_off = q; t.in_len = q + m; t.out_off = q + 2 * m; t.out_cap = q + 3 * m; t.ulen = q + 4 * m; t.aux_a = q + 5 * m; t.aux_b = q + 6 * m; q += 7 * m;
-	t.rstat = reinterpret_cast<int32_t*>(q); t.ustat = t.rstat + n; t.act = reinterpret_cast<uint32_t*>(t.ustat + m);
+	t.rstat = reinterpret_cast<int32_t*>(q); t.ustat = t.rstat + n; t.act = reinterpret_cast<uint32_t*>(t.ustat + m); t.ucrc = t.act + m;
 }
 
 MSCompStatus mscomp_amd_blocks_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t in_total_max, uint32_t flags,
@@ -1230,9 +1269,9 @@ MSCompStatus mscomp_amd_blocks_create(mscomp_amd_ctx* c, MSCompFormat format, ui
 	std::unique_ptr<mscomp_amd_blocks> b(new (std::nothrow) mscomp_amd_blocks());
 	if (!b) { return MSCOMP_MEM_ERROR; }
 	b->ctx = c; b->format = format; b->shift = (uint32_t)__builtin_ctz(block_size); b->n_res = (uint32_t)n_res; b->n_blocks = (uint32_t)M; b->in_total_max = in_total_max;
-	b->crun.ctx = b->drun.ctx = c; b->crun.n_units = b->drun.n_units = (uint32_t)n_res;
+	b->crun.ctx = b->drun.ctx = b->krun.ctx = b->vrun.ctx = c; b->crun.n_units = b->drun.n_units = b->krun.n_units = b->vrun.n_units = (uint32_t)n_res;
 	MSCompStatus st = MSCOMP_OK;
-	if (!b->tab.reserve((3 * n_res + 1 + 7 * M) * 8 + (n_res + 2 * M) * 4 + 64) || !b->stage.reserve(in_total_max + 16 * (uint64_t)n_res + 64)) { st = MSCOMP_MEM_ERROR; }
+	if (!b->tab.reserve((3 * n_res + 1 + 7 * M) * 8 + (n_res + 3 * M) * 4 + 64) || !b->stage.reserve(in_total_max + 16 * (uint64_t)n_res + 64)) { st = MSCOMP_MEM_ERROR; }
 	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_compress_dev(c, format, M, in_total_max, block_size, &b->cplan); }
 	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, in_total_max, in_total_max, &b->dplan); }
 	if (st != MSCOMP_OK) {
@@ -1298,6 +1337,56 @@ MSCompStatus mscomp_amd_blocks_decompress(mscomp_amd_blocks* b, const uint8_t* d
 		if (b->dplan) { dev_launch(b->dplan, d_packed, t.in_off, t.in_len, d_out, t.out_off, t.out_cap, t.ulen, t.ustat); }
 		{ KernelTimer k(c, "bk_rawcopy_kernel"); launch_blocks_rawcopy(c->stream, b->n_blocks, b->shift, d_packed, d_out, t, c->cpd_blocks); }
 		{ KernelTimer k(c, "bk_dfold_kernel"); launch_blocks_dfold(c->stream, b->n_res, t, d_out_len, d_status); }
+	});
+}
+
+// The checksums of a container: both calls are a table pass of their own, the CRC table pass and the CRC kernel over the blocks as units
+// (crc32.hip), on the container's tables -- every column is a temporary of one call, so the ones compress and decompress use serve here too:
+//   crc     t.unit_first = block_first, t.in_off / t.in_len = the blocks (bk_cunits_kernel), t.aux_a .. = cum (m + 1), t.act = resource of a block,
+//           t.ulen = the resource's bytes behind it, t.ucrc = x^(8 times that), t.res_a .. = the running sum the resources' seeds are made with (n + 1)
+//   check   t.unit_first / t.res_b = units and first block of the clipped ranges, t.in_off / t.in_len = the blocks in d_out, t.ulen = their entry
+//           of d_block_crc, t.aux_a .. = cum, t.ucrc = what was read
+MSCompStatus mscomp_amd_blocks_crc(mscomp_amd_blocks* b, const uint8_t* d_data, const uint64_t* d_res_off, const uint64_t* d_res_len,
+                                   uint32_t* d_block_crc, uint32_t* d_res_crc, int32_t* d_status)
+{
+	if (!b || (b->n_blocks && !d_block_crc) || (b->n_res && (!d_res_off || !d_res_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (b->in_total_max && !d_data) { return MSCOMP_ARG_ERROR; }
+	if (b->n_res == 0) { return MSCOMP_OK; }               // (no resource, no block: n_blocks_max is 0 too)
+	mscomp_amd_ctx* c = b->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[6] = { d_data, d_res_off, d_res_len, d_block_crc, d_res_crc, d_status };
+	return plan_run(&b->krun, args, [&] {
+		const BlocksTab& t = b->t;
+		{ KernelTimer k(c, "bk_ctables"); launch_blocks_ctables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_off, d_res_len, t.unit_first, t); }
+		{ KernelTimer k(c, "bk_crcgroups_kernel"); launch_blocks_crcgroups(c->stream, b->n_res, b->n_blocks, b->shift, d_res_len, t.unit_first, t); }
+		// the resources' statuses and seeds (the check of bk_cres_kernel once more, with the seed of an empty unit for a rejected resource), then the blocks' seeds and factors
+		{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, b->n_res, b->in_total_max, nullptr, d_res_len, nullptr, t.res_a, d_status); }
+		{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, b->n_res, t.res_a, d_res_crc, nullptr, nullptr); }
+		{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, b->n_blocks, ~(u64)0, nullptr, t.in_len, nullptr, t.aux_a, nullptr); }
+		{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, b->n_blocks, t.aux_a, d_block_crc, t.ulen, d_res_crc ? t.ucrc : nullptr); }
+		{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, b->n_blocks, d_data, t.in_off, t.aux_a, d_block_crc, t.act, t.ucrc, d_res_crc, c->crc_blocks); }
+	});
+}
+
+MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* b, const uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_res_len,
+                                     const uint64_t* d_block_first, const uint64_t* d_range, const uint32_t* d_block_crc,
+                                     uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!b || !d_block_first || (b->n_blocks && !d_block_crc) || (b->n_res && (!d_out_off || !d_res_len || !d_out_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (b->in_total_max && !d_out) { return MSCOMP_ARG_ERROR; }
+	if (b->n_res == 0) { return MSCOMP_OK; }
+	mscomp_amd_ctx* c = b->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[8] = { d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status };
+	return plan_run(&b->vrun, args, [&] {
+		const BlocksTab& t = b->t;
+		{ KernelTimer k(c, "bk_ktables"); launch_blocks_ktables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_len, d_block_first, d_range, d_out_off, d_status, t); }
+		{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, b->n_blocks, ~(u64)0, nullptr, t.in_len, nullptr, t.aux_a, nullptr); }
+		{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, b->n_blocks, t.aux_a, t.ucrc, nullptr, nullptr); }
+		{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, b->n_blocks, d_out, t.in_off, t.aux_a, t.ucrc, nullptr, nullptr, nullptr, c->crc_blocks); }
+		{ KernelTimer k(c, "bk_kfold_kernel"); launch_blocks_kfold(c->stream, b->n_res, d_block_crc, t, d_out_len, d_status); }
 	});
 }
 

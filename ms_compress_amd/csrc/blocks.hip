@@ -214,6 +214,94 @@ __global__ __launch_bounds__(256) void bk_dfold_kernel(uint32_t n_res, const u64
 	}
 }
 
+// ---- checksums (mscomp_amd_blocks_crc / _check; the CRC kernels themselves: crc32.hip) ----
+// crc, behind bk_cres_kernel and bk_cunits_kernel, one thread per possible block: the resource a block belongs to and the bytes of the resource
+// behind the block -- the second distance, by which the block's parts add up to the CRC of the whole resource in the same pass
+__global__ __launch_bounds__(256) void bk_crcgroups_kernel(uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* __restrict__ res_len, const u64* __restrict__ block_first,
+                                                          const u64* __restrict__ in_len, uint32_t* __restrict__ grp, u64* __restrict__ after)
+{
+	const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+	if (b >= nbmax) { return; }
+	uint32_t g = 0; u64 a = 0;
+	if (b < block_first[n_res]) {
+		g = res_of_block(block_first, n_res, b);
+		a = res_len[g] - ((b - block_first[g]) << shift) - in_len[b];
+	}
+	grp[b] = g; after[b] = a;
+}
+
+#define BK_LEAVE 1                                        // (rstat of a resource that was not MSCOMP_OK on entry to check: not a status)
+// check: bk_dres_kernel's checks 1 and 2 and its clipped range for the resources that are MSCOMP_OK on entry; the others have no units
+__global__ __launch_bounds__(DV_THREADS) void bk_kres_kernel(uint32_t n, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* __restrict__ res_len,
+                                                            const u64* __restrict__ block_first, const u64* __restrict__ range, const int32_t* __restrict__ d_status,
+                                                            u64* __restrict__ unit_first, u64* __restrict__ rf, int32_t* __restrict__ rstat)
+{
+	__shared__ u64 s_w[1][DV_WAVES];
+	const uint32_t tid = threadIdx.x;
+	const u64 B = (u64)1 << shift;
+	u64 run[1] = {0}, cnt[1] = {0};
+	if (tid == 0) { unit_first[0] = 0; }
+	for (uint32_t base = 0; base < n; base += DV_THREADS) {
+		const uint32_t i = base + tid;
+		const bool live = i < n;
+		const u64 len = live ? res_len[i] : 0;
+		u64 r[1] = {len};
+		dv_block_scan<1>(r, run, s_w);
+		int32_t st = BK_LEAVE;
+		u64 f = 0, c = 0;
+		if (live && d_status[i] == 0) {
+			const u64 f0 = block_first[i], f1 = block_first[i + 1u];
+			st = 0;
+			if (r[0] > in_max || f0 > nbmax || f1 > nbmax) { st = -2; }
+			else {
+				const u64 nblk = (len + B - 1u) >> shift;
+				if (f1 - f0 != nblk) { st = -3; }
+				else {
+					const u64 qf = range ? range[2u * (size_t)i] : 0, qc = range ? range[2u * (size_t)i + 1u] : nblk;
+					f = qf < nblk ? qf : nblk; c = qc < nblk - f ? qc : nblk - f;
+				}
+			}
+		}
+		u64 k[1] = {st == 0 ? c : 0};
+		dv_block_scan<1>(k, cnt, s_w);
+		if (live) { unit_first[i + 1u] = k[0]; rf[i] = f; rstat[i] = st; }
+	}
+}
+
+// ... one thread per possible unit: where the block lies in the decoded output, its data length, and which entry of d_block_crc it answers to
+__global__ __launch_bounds__(256) void bk_kunits_kernel(uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* __restrict__ res_len, const u64* __restrict__ block_first,
+                                                       const u64* __restrict__ d_out_off, const u64* __restrict__ unit_first, const u64* __restrict__ rf,
+                                                       u64* __restrict__ in_off, u64* __restrict__ in_len, u64* __restrict__ which)
+{
+	const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+	if (u >= nbmax) { return; }
+	const u64 B = (u64)1 << shift;
+	u64 io = 0, il = 0, j = 0;
+	if (u < unit_first[n_res]) {
+		const uint32_t r = res_of_block(unit_first, n_res, u);
+		const u64 k = u - unit_first[r], jb = rf[r] + k;
+		const u64 left = res_len[r] - (jb << shift);
+		j = block_first[r] + jb;                                           // (< block_first[r + 1] <= nbmax: bk_kres_kernel)
+		io = d_out_off[r] + (k << shift); il = left < B ? left : B;
+	}
+	in_off[u] = io; in_len[u] = il; which[u] = j;
+}
+
+// ... one wave per resource, behind the CRC kernels: a failed table check, or a block whose CRC is not the one given, into d_status and
+// d_out_len. A resource that passes, or was not MSCOMP_OK on entry, is not written.
+__global__ __launch_bounds__(256) void bk_kfold_kernel(uint32_t n_res, const u64* __restrict__ unit_first, const u64* __restrict__ which, const uint32_t* __restrict__ ucrc,
+                                                      const uint32_t* __restrict__ block_crc, const int32_t* __restrict__ rstat, u64* __restrict__ d_out_len, int32_t* __restrict__ d_status)
+{
+	const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+	if (r >= n_res) { return; }
+	const int32_t st = rstat[r];
+	if (st == BK_LEAVE) { return; }
+	bool bad = false;
+	if (st == 0) { for (u64 u = unit_first[r] + lane; u < unit_first[r + 1u]; u += 64u) { if (ucrc[u] != block_crc[which[u]]) { bad = true; } } }
+	const bool any_bad = __ballot(bad) != 0;
+	if (lane == 0 && (st != 0 || any_bad)) { d_status[r] = st != 0 ? st : -3; d_out_len[r] = 0; }   // MSCOMP_DATA_ERROR
+}
+
 void launch_blocks_ctables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* res_off, const u64* res_len,
                            u64* block_first, const BlocksTab& t)
 {
@@ -252,6 +340,27 @@ void launch_blocks_dfold(hipStream_t st, uint32_t n_res, const BlocksTab& t, u64
 {
 	if (n_res == 0) { return; }
 	hipLaunchKernelGGL(bk_dfold_kernel, dim3((n_res + 3u) / 4u), dim3(256), 0, st, n_res, t.unit_first, t.act, t.ulen, t.ustat, t.rstat, t.res_a, d_out_len, d_status);
+}
+
+void launch_blocks_crcgroups(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* res_len, const u64* block_first, const BlocksTab& t)
+{
+	if (nbmax == 0) { return; }
+	hipLaunchKernelGGL(bk_crcgroups_kernel, dim3((nbmax + 255u) / 256u), dim3(256), 0, st, n_res, nbmax, shift, res_len, block_first, t.in_len, t.act, t.ulen);
+}
+
+void launch_blocks_ktables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* res_len, const u64* block_first,
+                           const u64* range, const u64* d_out_off, const int32_t* d_status, const BlocksTab& t)
+{
+	hipLaunchKernelGGL(bk_kres_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_res, nbmax, shift, in_max, res_len, block_first, range, d_status, t.unit_first, t.res_b, t.rstat);
+	if (nbmax == 0) { return; }
+	hipLaunchKernelGGL(bk_kunits_kernel, dim3((nbmax + 255u) / 256u), dim3(256), 0, st, n_res, nbmax, shift, res_len, block_first, d_out_off, t.unit_first, t.res_b,
+	                   t.in_off, t.in_len, t.ulen);
+}
+
+void launch_blocks_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_crc, const BlocksTab& t, u64* d_out_len, int32_t* d_status)
+{
+	if (n_res == 0) { return; }
+	hipLaunchKernelGGL(bk_kfold_kernel, dim3((n_res + 3u) / 4u), dim3(256), 0, st, n_res, t.unit_first, t.ulen, t.ucrc, block_crc, t.rstat, d_out_len, d_status);
 }
 
 } // namespace msc

@@ -1,0 +1,244 @@
+// crc32.hip -- CRC-32 (zlib / PNG / Ethernet: reflected polynomial 0xEDB88320, initial value and final XOR 0xFFFFFFFF) of a batch of units in
+// HBM, from device tables: mscomp_amd_plan_create_crc_dev / _execute_crc_dev and the block container's mscomp_amd_blocks_crc / _check
+// (include/mscomp_amd.h).
+//
+// CRC-32 is linear over GF(2): with raw(M) the register after M from an initial value of 0, and |M| in bytes,
+//   raw(A || B) = raw(A) * x^(8 |B|)  ^  raw(B)                 (mod P; leading zero bytes leave raw() alone)
+//   crc32(M)    = raw(M)  ^  0xFFFFFFFF * x^(8 |M|)  ^  0xFFFFFFFF
+// So a unit may be cut anywhere: every part adds raw(part) * x^(8 d), d = the bytes between the part's end and the unit's end, with an atomic
+// XOR, in any order, onto a value the table pass has seeded with the last two terms. A register is a polynomial with the coefficient of x^0 in
+// bit 31 (zlib's multmodp form), so "a zero byte more" is "times x^8".
+#include "../../include/mscomp_amd.h"
+#include "kernels.h"
+
+namespace msc {
+
+#define CRC_POLY 0xEDB88320u
+#define CRC_ONE  0x80000000u                              // x^0
+#define CRC_ROW  MSCOMP_AMD_CRC_ROW_BYTES                 // bytes a wave takes per step: 64 lanes x 64 bytes
+#define CRC_RUN  (CRC_ROW / 64u)                          // ... a lane's run in it: four 16-byte loads
+#define CRC_THREADS 256u
+
+// a * b mod P, the bits of a from x^0 up
+__host__ __device__ constexpr uint32_t crc_mul(uint32_t a, uint32_t b)
+{
+	uint32_t p = 0;
+	for (int i = 0; i < 32; ++i) { p ^= b & (0u - (a >> 31)); a <<= 1; b = (b >> 1) ^ (CRC_POLY & (0u - (b & 1u))); }
+	return p;
+}
+
+// What the kernels read: slicing tables t[j][b] = raw(b, then j zero bytes); a[k][b] = (b in byte k of a register) * x^(8 (CRC_ROW - CRC_RUN)):
+// a lane's register carried over the other lanes' runs of a row; c[l] = x^(8 CRC_RUN (63 - l)): lane l's run to the end of the row;
+// x2n[k] = x^(2^k). Built by the compiler.
+struct CrcTables { uint32_t t[16][256]; uint32_t a[4][256]; uint32_t c[64]; uint32_t x2n[64]; };
+constexpr CrcTables make_crc_tables()
+{
+	CrcTables r{};
+	for (uint32_t b = 0; b < 256u; ++b) {
+		uint32_t v = b;
+		for (int i = 0; i < 8; ++i) { v = (v >> 1) ^ (CRC_POLY & (0u - (v & 1u))); }
+		r.t[0][b] = v;
+	}
+	for (uint32_t j = 1; j < 16u; ++j) { for (uint32_t b = 0; b < 256u; ++b) { const uint32_t v = r.t[j - 1u][b]; r.t[j][b] = (v >> 8) ^ r.t[0][v & 255u]; } }
+	r.x2n[0] = CRC_ONE >> 1;
+	for (uint32_t k = 1; k < 64u; ++k) { r.x2n[k] = crc_mul(r.x2n[k - 1u], r.x2n[k - 1u]); }
+	uint32_t run = CRC_ONE, adv = CRC_ONE;                               // x^(8 CRC_RUN), x^(8 (CRC_ROW - CRC_RUN))
+	for (uint32_t k = 0, n = 8u * CRC_RUN; n; ++k, n >>= 1) { if (n & 1u) { run = crc_mul(run, r.x2n[k]); } }
+	for (uint32_t k = 0, n = 8u * (CRC_ROW - CRC_RUN); n; ++k, n >>= 1) { if (n & 1u) { adv = crc_mul(adv, r.x2n[k]); } }
+	r.c[63] = CRC_ONE;
+	for (uint32_t l = 63; l-- > 0;) { r.c[l] = crc_mul(r.c[l + 1u], run); }
+	for (uint32_t k = 0; k < 4u; ++k) {                                   // linear in b: the eight single bits, then their sums
+		r.a[k][0] = 0;
+		for (uint32_t b = 1; b < 256u; ++b) { const uint32_t low = b & (0u - b); r.a[k][b] = low == b ? crc_mul(b << (8u * k), adv) : r.a[k][b ^ low] ^ r.a[k][low]; }
+	}
+	return r;
+}
+__device__ const CrcTables g_crc_tab = make_crc_tables();
+
+// x^n (n = 8 d < 2^53): square and multiply over the bits of n
+__device__ __forceinline__ uint32_t crc_xpow(u64 n)
+{
+	uint32_t r = CRC_ONE;
+	for (uint32_t k = 0; n; ++k, n >>= 1) { if (n & 1u) { r = crc_mul(r, g_crc_tab.x2n[k]); } }
+	return r;
+}
+// the two terms of crc32() that do not depend on the data
+__device__ __forceinline__ uint32_t crc_seed(u64 len) { return len ? crc_mul(0xFFFFFFFFu, crc_xpow(len << 3)) ^ 0xFFFFFFFFu : 0u; }
+
+// ---- the table pass ----
+// One block walks the units in tiles of 1024: the bounds check of the dev plans (running total of in_len <= in_max; a rejected unit is an
+// empty unit: MSCOMP_ARG_ERROR, crc 0, nothing read), cum[0..n] = the running sum of the accepted lengths -- the byte range the main kernel
+// cuts into slices --, and off[i] (zero for a rejected unit). in_off / off and status may be null (the block container has checked its resources
+// itself and reads its own offsets). The one block does nothing but the two scans: the seeds, which cost products, are crc_seed_kernel's.
+__global__ __launch_bounds__(DV_THREADS) void crc_tables_kernel(uint32_t n, u64 in_max, const u64* __restrict__ in_off, const u64* __restrict__ in_len,
+                                                               u64* __restrict__ off, u64* __restrict__ cum, int32_t* __restrict__ status)
+{
+	__shared__ u64 s_w[1][DV_WAVES];
+	const uint32_t tid = threadIdx.x;
+	u64 run[1] = {0}, acc[1] = {0};
+	if (tid == 0) { cum[0] = 0; }
+	for (uint32_t base = 0; base < n; base += DV_THREADS) {
+		const uint32_t i = base + tid;
+		const bool live = i < n;
+		const u64 len = live ? in_len[i] : 0;
+		u64 r[1] = {len};
+		dv_block_scan<1>(r, run, s_w);                                   // running total up to and including unit i
+		const bool rej = live && r[0] > in_max;
+		const u64 L = rej ? 0 : len;
+		u64 c[1] = {L};
+		dv_block_scan<1>(c, acc, s_w);
+		if (live) {
+			cum[i + 1u] = c[0];
+			if (off) { off[i] = rej ? 0 : in_off[i]; }
+			if (status) { status[i] = rej ? -2 : 0; }                       // MSCOMP_ARG_ERROR
+		}
+	}
+}
+
+// One thread per unit, behind the table pass: crc[i] = the seed of a unit of cum[i + 1] - cum[i] bytes (0 for an empty or rejected one) and,
+// for the container's blocks, fac[i] = x^(8 after[i]): the factor that carries a block's terms on to the end of its resource.
+__global__ __launch_bounds__(256) void crc_seed_kernel(uint32_t n, const u64* __restrict__ cum, uint32_t* __restrict__ crc, const u64* __restrict__ after, uint32_t* __restrict__ fac)
+{
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= n) { return; }
+	if (crc) { crc[i] = crc_seed(cum[i + 1u] - cum[i]); }
+	if (fac) { fac[i] = crc_xpow(after[i] << 3); }
+}
+
+// ---- the main kernel ----
+__device__ __forceinline__ uint32_t crc_step16(const uint32_t (*t)[256], uint32_t st, uint4 v)
+{
+	const uint32_t x = v.x ^ st;
+	return t[15][x & 255u] ^ t[14][(x >> 8) & 255u] ^ t[13][(x >> 16) & 255u] ^ t[12][x >> 24] ^
+	       t[11][v.y & 255u] ^ t[10][(v.y >> 8) & 255u] ^ t[9][(v.y >> 16) & 255u] ^ t[8][v.y >> 24] ^
+	       t[7][v.z & 255u] ^ t[6][(v.z >> 8) & 255u] ^ t[5][(v.z >> 16) & 255u] ^ t[4][v.z >> 24] ^
+	       t[3][v.w & 255u] ^ t[2][(v.w >> 8) & 255u] ^ t[1][(v.w >> 16) & 255u] ^ t[0][v.w >> 24];
+}
+// the 16 bytes at the 16-aligned address q of a part that starts at p: whole, or its bytes from p on behind zeros, or -- all in front of p -- zeros
+__device__ __forceinline__ uint4 crc_load_front(uintptr_t q, uintptr_t p)
+{
+	if (q >= p) { return *reinterpret_cast<const uint4*>(q); }
+	uint32_t w[4] = {0, 0, 0, 0};
+	if (q + 16u > p) { for (uint32_t j = (uint32_t)(p - q); j < 16u; ++j) { w[j >> 2] |= (uint32_t)*reinterpret_cast<const uint8_t*>(q + j) << (8u * (j & 3u)); } }
+	return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
+{
+	#pragma unroll
+	for (uint32_t d = 32; d; d >>= 1) { v ^= __shfl_xor(v, d, 64); }
+	return v;
+}
+
+// One wave, one part [p, p + len) of a unit: raw(body) and raw(tail) in every lane, the tail being the t < 16 bytes behind the last 16-byte
+// boundary (all of a part that holds none). The body is laid out in rows of CRC_ROW bytes that END at that boundary, lane l taking the
+// CRC_RUN bytes at 64 l of every row with aligned 16-byte loads; what a first row has in front of p counts as zeros, which a raw register
+// does not see. So lane l's last byte is always CRC_RUN (63 - l) bytes short of the body's end, and the lanes combine by one multiplication
+// with a constant each. No byte outside the part is read.
+__device__ __forceinline__ void crc_part(const uint32_t (*t)[256], const uint32_t (*a)[256], const uint32_t* c, uintptr_t p, u64 len, uint32_t lane,
+                                         uint32_t& body, uint32_t& tail, uint32_t& tlen)
+{
+	const uintptr_t end = p + len, e16 = end & ~(uintptr_t)15u;
+	const uintptr_t t0 = e16 > p ? e16 : p;
+	tlen = (uint32_t)(end - t0);
+	uint32_t tb = 0;
+	if (lane < tlen) { tb = *reinterpret_cast<const uint8_t*>(t0 + lane); }   // (in flight while the body runs)
+	uint32_t st = 0;
+	if (e16 > p) {
+		const u64 rows = ((u64)(e16 - p) + (CRC_ROW - 1u)) / CRC_ROW;
+		uintptr_t q = e16 - rows * CRC_ROW + (uintptr_t)lane * CRC_RUN;      // (may lie in front of p, and of the buffer: compared, not read)
+		{
+			const uint4 v0 = crc_load_front(q, p), v1 = crc_load_front(q + 16u, p), v2 = crc_load_front(q + 32u, p), v3 = crc_load_front(q + 48u, p);
+			st = crc_step16(t, st, v0); st = crc_step16(t, st, v1); st = crc_step16(t, st, v2); st = crc_step16(t, st, v3);
+		}
+		for (u64 r = 1; r < rows; ++r) {
+			q += CRC_ROW;
+			const uint4* __restrict__ s = reinterpret_cast<const uint4*>(q);
+			const uint4 v0 = s[0], v1 = s[1], v2 = s[2], v3 = s[3];
+			st = a[0][st & 255u] ^ a[1][(st >> 8) & 255u] ^ a[2][(st >> 16) & 255u] ^ a[3][st >> 24];
+			st = crc_step16(t, st, v0); st = crc_step16(t, st, v1); st = crc_step16(t, st, v2); st = crc_step16(t, st, v3);
+		}
+		st = crc_mul(st, c[lane]);
+	}
+	body = wave_xor(st);
+	uint32_t ts = 0;
+	for (uint32_t j = 0; j < tlen; ++j) { const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)tb, (int)j); ts = (ts >> 8) ^ t[0][(ts ^ b) & 255u]; }
+	tail = ts;
+}
+
+// The byte range [0, cum[n]) of the batch is cut into equal slices, one per WAVE of a grid fixed by the CU count (cpd_copy_kernel cuts the
+// packed range the same way, per block): a wave finds the unit its slice starts in by binary search in cum[] and walks the units from there.
+// Per part of a unit: raw(body) and raw(tail), each times x^(8 distance to the unit's end) -- two lanes take the two products at once --,
+// XORed onto crc[u]; and, GROUPS, the same sum times fac[u] onto gcrc[grp[u]]: the unit is a block, the group its resource, fac[u] =
+// x^(8 bytes of the resource behind the block), so the resource's CRC costs one product more per part.
+template <bool GROUPS>
+__global__ __launch_bounds__(CRC_THREADS) void crc_kernel(const uint8_t* __restrict__ base, const u64* __restrict__ off, const u64* __restrict__ cum, uint32_t n,
+                                                         uint32_t* __restrict__ crc, const uint32_t* __restrict__ grp, const uint32_t* __restrict__ fac, uint32_t* __restrict__ gcrc)
+{
+	__shared__ uint32_t s_t[16][256];
+	__shared__ uint32_t s_a[4][256];
+	__shared__ uint32_t s_c[64];
+	const uint32_t tid = threadIdx.x, lane = tid & 63u;
+	{
+		const uint32_t* __restrict__ g = &g_crc_tab.t[0][0];
+		uint32_t* s = &s_t[0][0];
+		for (uint32_t i = tid; i < 16u * 256u; i += CRC_THREADS) { s[i] = g[i]; }
+		for (uint32_t i = tid; i < 4u * 256u; i += CRC_THREADS) { (&s_a[0][0])[i] = (&g_crc_tab.a[0][0])[i]; }
+		if (tid < 64u) { s_c[tid] = g_crc_tab.c[tid]; }
+	}
+	__syncthreads();
+	const u64 total = cum[n], nw = (u64)gridDim.x * (CRC_THREADS / 64u), w = (u64)blockIdx.x * (CRC_THREADS / 64u) + (tid >> 6);
+	u64 per = total / nw + 1u;                                          // (total < 2^50: the creators refuse larger bounds)
+	per = (per + (MSCOMP_AMD_CRC_SLICE_BYTES - 1u)) & ~(u64)(MSCOMP_AMD_CRC_SLICE_BYTES - 1u);
+	const u64 lo = w * per;
+	if (lo >= total) { return; }
+	const u64 hi = total - lo < per ? total : lo + per;
+	uint32_t x = 0, y = n;                                               // the first unit with cum[u + 1] > lo (there is one: cum[n] > lo)
+	while (x < y) { const uint32_t m = x + (y - x) / 2u; if (cum[m + 1u] > lo) { y = m; } else { x = m + 1u; } }
+	for (uint32_t u = x; u < n; ++u) {
+		const u64 o = cum[u], e = cum[u + 1u];
+		if (o >= hi) { break; }
+		const u64 p0 = o > lo ? o : lo, p1 = e < hi ? e : hi;
+		if (p0 >= p1) { continue; }                                         // (an empty unit)
+		uint32_t body, tail, tlen;
+		crc_part(s_t, s_a, s_c, (uintptr_t)(base + off[u] + (p0 - o)), p1 - p0, lane, body, tail, tlen);
+		// lane 0: the body, tlen bytes further from the unit's end than lane 1's tail
+		uint32_t v = lane == 0 ? body : lane == 1 ? tail : 0u;
+		const u64 dist = (e - p1) + (lane == 0 ? tlen : 0u);
+		if (v != 0 && dist != 0) { v = crc_mul(v, crc_xpow(dist << 3)); }
+		v ^= __shfl_xor(v, 1, 64);
+		if (lane == 0 && v != 0) {
+			atomicXor(&crc[u], v);
+			if (GROUPS) { atomicXor(&gcrc[grp[u]], crc_mul(v, fac[u])); }
+		}
+	}
+}
+
+// blocks of crc_kernel that are resident on the current device at once, four per CU at most: its grid
+uint32_t crc_dev_blocks()
+{
+	int dev = 0, cus = 0, per_cu = 0;
+	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crc_kernel<true>, (int)CRC_THREADS, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 4; }
+	return (uint32_t)cus * (uint32_t)(per_cu < 4 ? per_cu : 4);
+}
+
+void launch_crc_tables(hipStream_t st, uint32_t n, u64 in_total_max, const u64* in_off, const u64* in_len, u64* off, u64* cum, int32_t* status)
+{
+	hipLaunchKernelGGL(crc_tables_kernel, dim3(1), dim3(DV_THREADS), 0, st, n, in_total_max, in_off, in_len, off, cum, status);
+}
+
+void launch_crc_seeds(hipStream_t st, uint32_t n, const u64* cum, uint32_t* crc, const u64* after, uint32_t* fac)
+{
+	if (n == 0 || (!crc && !fac)) { return; }
+	hipLaunchKernelGGL(crc_seed_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, n, cum, crc, after, fac);
+}
+
+void launch_crc_units(hipStream_t st, uint32_t n, const uint8_t* base, const u64* off, const u64* cum, uint32_t* crc,
+                      const uint32_t* grp, const uint32_t* fac, uint32_t* gcrc, uint32_t blocks)
+{
+	if (n == 0) { return; }
+	if (gcrc) { hipLaunchKernelGGL(crc_kernel<true>, dim3(blocks), dim3(CRC_THREADS), 0, st, base, off, cum, n, crc, grp, fac, gcrc); }
+	else { hipLaunchKernelGGL(crc_kernel<false>, dim3(blocks), dim3(CRC_THREADS), 0, st, base, off, cum, n, crc, grp, fac, gcrc); }
+}
+
+} // namespace msc

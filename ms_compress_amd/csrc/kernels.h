@@ -233,7 +233,8 @@ struct BlocksTab {
 	u64 *aux_a, *aux_b;                                // m each: compress, stored length | source address; decompress, raw block's offset in packed | in out
 	int32_t* rstat;                                    // n: the resource's own status (bounds, block count, capacity)
 	int32_t* ustat;                                    // m: the inner plan's d_status
-	uint32_t* act;                                     // m: decompress, kind | data length << 2
+	uint32_t* act;                                     // m: decompress, kind | data length << 2; crc, the block's resource
+	uint32_t* ucrc;                                    // m: check, the CRC-32 of every block read; crc, x^(8 bytes of the resource behind the block)
 };
 // compress, in front of the inner plan: bounds check, block_first (n_res + 1) and the unit tables (two launches: one block over the resources,
 // one thread per possible block)
@@ -248,6 +249,26 @@ void launch_blocks_dtables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint3
 // decompress, behind it: raw blocks to their places (`blocks` = compact_dev_blocks()), then status and length per resource
 void launch_blocks_rawcopy(hipStream_t st, uint32_t nbmax, uint32_t shift, const uint8_t* packed, uint8_t* out, const BlocksTab& t, uint32_t blocks);
 void launch_blocks_dfold(hipStream_t st, uint32_t n_res, const BlocksTab& t, u64* d_out_len, int32_t* d_status);
+// crc, behind launch_blocks_ctables: per block its resource (t.act) and the resource's bytes behind it (t.ulen), for launch_crc_units
+void launch_blocks_crcgroups(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* res_len, const u64* block_first, const BlocksTab& t);
+// check, in front of the CRC kernels: checks 1 and 2 and the clipped range of the resources that are MSCOMP_OK in d_status (t.unit_first, t.res_b,
+// t.rstat), then per unit where the block lies in the output (t.in_off, t.in_len) and its entry of d_block_crc (t.ulen); behind them: the verdicts
+void launch_blocks_ktables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* res_len, const u64* block_first,
+                           const u64* range, const u64* d_out_off, const int32_t* d_status, const BlocksTab& t);
+void launch_blocks_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_crc, const BlocksTab& t, u64* d_out_len, int32_t* d_status);
+
+// ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
+// the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status
+// MSCOMP_ARG_ERROR), off[i] = its offset. in_off / off and status may be null.
+void launch_crc_tables(hipStream_t st, uint32_t n, u64 in_total_max, const u64* in_off, const u64* in_len, u64* off, u64* cum, int32_t* status);
+// behind it, one thread per unit: crc[i] = the terms of the CRC of cum[i + 1] - cum[i] bytes that do not depend on the data; fac[i] =
+// x^(8 after[i]). Either pair may be null.
+void launch_crc_seeds(hipStream_t st, uint32_t n, const u64* cum, uint32_t* crc, const u64* after, uint32_t* fac);
+// the bytes: crc[u] ^= the data terms of the cum[u + 1] - cum[u] bytes at base + off[u]; with gcrc, also gcrc[grp[u]] ^= the same terms times
+// fac[u]. `blocks` = the fixed grid, crc_dev_blocks() of the device
+uint32_t crc_dev_blocks();
+void launch_crc_units(hipStream_t st, uint32_t n, const uint8_t* base, const u64* off, const u64* cum, uint32_t* crc,
+                      const uint32_t* grp, const uint32_t* fac, uint32_t* gcrc, uint32_t blocks);
 
 // ---- utilities (util.hip) ----
 // prefix[0..n] = exclusive scan of sizes[0..n) as u64 (prefix[n] = total). block_sums: scratch of ceil(n/1024)+1 u64.
