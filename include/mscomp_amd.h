@@ -478,6 +478,62 @@ MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* bk, const uint8_t* d_out
                                      const uint64_t* d_block_first, const uint64_t* d_range, const uint32_t* d_block_crc,
                                      uint64_t* d_out_len, int32_t* d_status /* in and out */);
 
+/* Block readers: byte-range reads from a block container, batched. A request q = (r, off, len) asks for the bytes [off, off + len) of
+ * resource r, as pread does; one call serves n_req of them, scattered over any resources in any order, and writes exactly those bytes. The
+ * reader is an object of its own, sized by what one call READS: it needs no mscomp_amd_blocks object, only the tables a container wrote and
+ * the packed bytes. A block that several requests touch is decoded once, and checked once.
+ *   Creation:     block_size = B and format as the container's; flags must be 0. n_res resources, whose tables are d_block_first (n_res + 1
+ *                 entries), d_block_off (n_blocks_table + 1: the container's n_blocks_max + 1) and d_res_len (n_res). n_req requests per
+ *                 call, fixed here. blocks_max bounds the blocks one call may touch (rule 5). All scratch is reserved here, once, and never
+ *                 grows: a block cache of blocks_max B bytes, one decompress dev plan for blocks_max units within blocks_max B bytes in and
+ *                 out, and the reader's tables: 88 bytes per unit of blocks_max, 44 per request, 4 per entry of the block table.
+ *                 MSCOMP_ARG_ERROR for a null ctx or rd, a bad format, a bad block_size, non-zero flags, or any of n_res, n_blocks_table,
+ *                 n_req, blocks_max above 0x7FFFFFF0; MSCOMP_MEM_ERROR when the scratch cannot be reserved, or blocks_max B bytes are more
+ *                 than a decompress dev plan can address. Every check comes before the context is used; *rd is cleared on failure.
+ *   Read:         d_req = 3 n_req uint64: resource, offset, length. d_out_off, d_out_cap, d_out_len, d_status: n_req entries. With
+ *                 L = d_res_len[r], per request, in this order, each leaving every other request alone:
+ *                   1. MSCOMP_ARG_ERROR, nothing read: r >= n_res, or d_block_first[r] or d_block_first[r + 1] exceeds n_blocks_table;
+ *                   2. MSCOMP_DATA_ERROR: d_block_first[r + 1] - d_block_first[r] is not ceil(L / B);
+ *                   3. the range is clipped: off' = min(off, L), want = min(len, L - off') -- no sum of off and len is formed, a len of
+ *                      2^64 - 1 means "to the end". want = 0 is MSCOMP_OK with no blocks;
+ *                   4. MSCOMP_BUF_ERROR: want > d_out_cap[q];
+ *                   5. the budget: the request covers cnt = the blocks off' / B .. (off' + want - 1) / B of the resource. The running
+ *                      total of cnt over all requests that passed 1-4, in request order and including this one, must not exceed
+ *                      blocks_max; otherwise MSCOMP_ARG_ERROR (the dev plans' rule for bounds). The total counts covering blocks BEFORE
+ *                      any sharing: two requests into one block count 2. So admission is a running sum that does not depend on which
+ *                      requests share blocks, and a caller who sizes blocks_max by the sum of its requests' blocks is never refused;
+ *                   6. every covering block passes the container's table checks (mscomp_amd_blocks_decompress, step 4; a block that fails
+ *                      one is never read): s = e is raw and read where it lies, 0 < s < e is decoded exactly as ms_decompress with capacity
+ *                      e and must give MSCOMP_OK and e bytes; with d_block_crc non-null (the array mscomp_amd_blocks_crc wrote), the CRC-32
+ *                      of the whole block, decoded or raw, must equal d_block_crc[block]. Any failure is MSCOMP_DATA_ERROR for every
+ *                      request that covers that block, and for no other.
+ *                 MSCOMP_OK: d_out_len[q] = want and exactly the bytes [off', off' + want) of the resource lie at d_out + d_out_off[q], at
+ *                 any alignment; nothing outside these want bytes is written. Otherwise d_out_len[q] = 0 and nothing is written for the
+ *                 request at all: the verdicts are folded before the bytes move. Requests may repeat and overlap on the input side;
+ *                 overlap on the output side is the caller's responsibility.
+ *   Sharing:      a unit is one (request, covering block) pair of an admitted request; the lowest unit that covers a block owns it. Only
+ *                 owners are decoded (into cache slot `unit`) or, raw, read in d_packed, and only owners' blocks are checksummed; every
+ *                 unit gathers from its owner. mscomp_amd_reader_counts gives, for the last execution, out[0] = units, out[1] = distinct
+ *                 blocks, out[2] = those that were decoded rather than raw (a block that failed a table check is neither). It
+ *                 synchronises the stream, works without MSCOMP_AMD_TEST_HOOKS and returns -1 on error, 0 otherwise.
+ *   Execution:    as the container's calls: asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation, no
+ *                 synchronisation, nothing read back, a launch sequence fixed by the creation bounds. Legal while the caller captures the
+ *                 ctx stream, the first execution included; outside capture the call replays a graph of its own from its second execution
+ *                 on, captured again when an argument changes. MSCOMP_ARG_ERROR for a null rd or a null required array (d_packed and d_out
+ *                 may be null when blocks_max is 0, d_res_len when n_res is 0, the request arrays when n_req is 0, d_block_crc always).
+ *                 n_req = 0 returns MSCOMP_OK. */
+typedef struct mscomp_amd_reader mscomp_amd_reader;
+MSCompStatus mscomp_amd_reader_create(mscomp_amd_ctx* ctx, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table,
+                                      size_t n_req, uint64_t blocks_max, uint32_t flags, mscomp_amd_reader** rd);
+void         mscomp_amd_reader_destroy(mscomp_amd_reader* rd);
+MSCompStatus mscomp_amd_reader_read(mscomp_amd_reader* rd, const uint8_t* d_packed, uint64_t packed_len,
+                                    const uint64_t* d_block_first, const uint64_t* d_block_off, const uint64_t* d_res_len,
+                                    const uint32_t* d_block_crc /* may be NULL */,
+                                    const uint64_t* d_req /* 3 n_req: resource, offset, length */,
+                                    uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+                                    uint64_t* d_out_len, int32_t* d_status);
+int          mscomp_amd_reader_counts(mscomp_amd_reader* rd, uint32_t out[3]);
+
 /* ---- measurement hooks (bench.py / profiles) ---- */
 /* When enabled, every kernel launch of plan_execute is bracketed by hipEvents on the ctx stream. */
 void         mscomp_amd_profile_enable(mscomp_amd_ctx* ctx, int on);

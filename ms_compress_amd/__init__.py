@@ -11,4 +11,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   Context, Plan, SizePlan, decompressed_sizes, decompress_units_auto, DevPlan, layout_dev,
                   CompressDevPlan, plan_layout_dev, SizeDevPlan, compact_dev,
                   BlockContainer, blocks_compress, blocks_decompress,
-                  CrcDevPlan, crc32_units, blocks_crc)
+                  CrcDevPlan, crc32_units, blocks_crc,
+                  BlockReader, blocks_read)

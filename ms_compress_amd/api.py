@@ -41,6 +41,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_plan_create_decompress_dev_ex", "mscomp_amd_plan_create_size_dev_ex", "mscomp_amd_debug_plan_paths",
     "mscomp_amd_blocks_create", "mscomp_amd_blocks_destroy", "mscomp_amd_blocks_bound", "mscomp_amd_blocks_compress", "mscomp_amd_blocks_decompress",
     "mscomp_amd_plan_create_crc_dev", "mscomp_amd_plan_execute_crc_dev", "mscomp_amd_blocks_crc", "mscomp_amd_blocks_check",
+    "mscomp_amd_reader_create", "mscomp_amd_reader_destroy", "mscomp_amd_reader_read", "mscomp_amd_reader_counts",
 ]
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 
@@ -150,6 +151,14 @@ def load_library():
     lib.mscomp_amd_blocks_crc.restype = C.c_int
     lib.mscomp_amd_blocks_check.argtypes = [C.c_void_p] + [C.c_void_p] * 8
     lib.mscomp_amd_blocks_check.restype = C.c_int
+    lib.mscomp_amd_reader_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_reader_create.restype = C.c_int
+    lib.mscomp_amd_reader_destroy.argtypes = [C.c_void_p]
+    lib.mscomp_amd_reader_destroy.restype = None
+    lib.mscomp_amd_reader_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 10
+    lib.mscomp_amd_reader_read.restype = C.c_int
+    lib.mscomp_amd_reader_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.mscomp_amd_reader_counts.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -662,6 +671,111 @@ def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, 
     if own:
         ctx.close()
     return res, [int(x) for x in h_st[:n]]
+
+
+class BlockReader:
+    """A block reader (mscomp_amd_reader_create): batched byte-range reads from a block container, by its tables alone. Made once for
+    ``n_req`` requests per call that together cover at most ``blocks_max`` blocks (counted per request, before any sharing); the tables are
+    those of a container of ``n_res`` resources whose d_block_off has ``n_blocks_table`` + 1 entries. All scratch is reserved here: a cache
+    of blocks_max blocks, one inner dev plan, 88 bytes of tables per unit of blocks_max, 44 per request and 4 per block-table entry. read()
+    enqueues kernels on the ctx stream and nothing else (legal inside a capture of that stream). Arguments are torch CUDA tensors: uint8
+    data, int64 / uint64 tables, int32 statuses and checksums."""
+
+    def __init__(self, ctx, fmt, block_size, n_res, n_blocks_table, n_req, blocks_max):
+        self.ctx, self.fmt, self.block_size = ctx, int(fmt), int(block_size)
+        self.n_res, self.n_blocks_table, self.n_req, self.blocks_max = int(n_res), int(n_blocks_table), int(n_req), int(blocks_max)
+        self._h = C.c_void_p()
+        st = ctx.lib.mscomp_amd_reader_create(ctx._h, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_req, self.blocks_max, 0,
+                                              C.byref(self._h))
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_reader_create")
+
+    def read(self, d_packed, d_block_first, d_block_off, d_res_len, d_req, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_block_crc=None,
+             packed_len=None):
+        """Request q = (resource, offset, length) = d_req[3 q .. 3 q + 2], clipped to the resource as pread does. d_status[q] is MSCOMP_OK
+        with d_out_len[q] = the clipped length and exactly those bytes at d_out + d_out_off[q]; or MSCOMP_ARG_ERROR (no such resource, or
+        over the budget of blocks_max), MSCOMP_BUF_ERROR (more than d_out_cap[q]) or MSCOMP_DATA_ERROR (a damaged table or block; with
+        ``d_block_crc``, as BlockContainer.crc wrote it, a block whose CRC-32 differs) with d_out_len[q] = 0 and nothing written.
+        ``packed_len``: the valid bytes of d_packed (default: all of it)."""
+        plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
+        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_out,
+                                                                         d_out_off, d_out_cap, d_out_len, d_status)]
+        st = self.ctx.lib.mscomp_amd_reader_read(self._h, p[0], plen, *p[1:])
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_reader_read")
+
+    def counts(self):
+        """(units, distinct blocks, blocks decoded rather than raw) of the last read(); synchronizes the stream."""
+        out = (C.c_uint32 * 3)()
+        if self.ctx.lib.mscomp_amd_reader_counts(self._h, out) != 0:
+            raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_reader_counts")
+        return (int(out[0]), int(out[1]), int(out[2]))
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.mscomp_amd_reader_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def blocks_read(fmt, packed, block_first, block_off, lengths, block_size, requests, ctx=None, block_crc=None):
+    """Read byte ranges of a block container on the GPU: ``requests`` is a list of (resource, offset, length), each clipped to its resource
+    as pread does; ``lengths`` are the resources' original lengths. ``block_crc`` (optional, as blocks_crc returns it): every block read is
+    held to its checksum. Returns (list of bytes, or None where the status is not MSCOMP_OK; list of status)."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    n, nq = len(lengths), len(requests)
+    lens = [int(x) for x in lengths]
+    B = int(block_size)
+    M64 = (1 << 64) - 1
+    reqs = [(int(r) & M64, int(o) & M64, int(ln) & M64) for r, o, ln in requests]
+    wants, blocks = [], 0
+    for r, o, ln in reqs:                                      # the capacities, and the budget: the covering blocks of every request, unshared
+        L = lens[r] if r < n else 0
+        o = min(o, L)
+        w = min(ln, L - o)
+        wants.append(w)
+        blocks += ((o + w - 1) // B - o // B + 1) if w else 0
+    out_off, out_total = pack_offsets(wants)
+    nbt = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
+    dev = torch.device("cuda", ctx.device)
+
+    def up(a, least):
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+        a = np.concatenate([a, np.full(max(0, least - len(a)), a[-1] if len(a) else 0, dtype=np.uint64)])
+        return torch.from_numpy(a.view(np.int64).copy()).to(dev)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        rd = BlockReader(ctx, fmt, B, n, nbt, nq, blocks)
+        packed = np.ascontiguousarray(np.frombuffer(bytes(packed), dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed, dtype=np.uint8)
+        d_packed = torch.zeros(len(packed) + 16, dtype=torch.uint8, device=dev)
+        if len(packed):
+            d_packed[: len(packed)] = torch.from_numpy(packed.copy()).to(dev)
+        d_first, d_boff, d_len = up(block_first, n + 1), up(block_off, nbt + 1), up(lens, 1)
+        d_req = up(np.array(reqs, dtype=np.uint64).reshape(-1), 3)
+        d_ooff, d_ocap = up(out_off, 1), up(wants, 1)
+        d_crc = None
+        if block_crc is not None:
+            h_crc = np.zeros(max(1, nbt), dtype=np.uint32)
+            k = min(len(block_crc), len(h_crc))
+            h_crc[:k] = np.asarray(block_crc, dtype=np.uint32)[:k]
+            d_crc = torch.from_numpy(h_crc.view(np.int32).copy()).to(dev)
+        d_out = torch.zeros(out_total + 16, dtype=torch.uint8, device=dev)
+        d_olen = torch.zeros(max(1, nq), dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, nq), dtype=torch.int32, device=dev)
+        rd.read(d_packed, d_first, d_boff, d_len, d_req, d_out, d_ooff, d_ocap, d_olen, d_st, d_block_crc=d_crc, packed_len=len(packed))
+        ctx.stream.synchronize()
+        h_out, h_len, h_st = d_out.cpu().numpy(), d_olen.cpu().numpy(), d_st.cpu().numpy()
+        rd.close()
+    res = [bytes(h_out[int(out_off[i]): int(out_off[i]) + int(h_len[i])]) if h_st[i] == MSCOMP_OK else None for i in range(nq)]
+    if own:
+        ctx.close()
+    return res, [int(x) for x in h_st[:nq]]
 
 
 def plan_paths(plan):

@@ -124,7 +124,7 @@ struct mscomp_amd_plan {
 	// the plan's launch sequence as a hipGraph (plan_run): captured on the plan's second execution, replayed while the
 	// arguments and the scratch buffers stay where they were
 	hipGraphExec_t gexec = nullptr;
-	const void* g_args[12] = {};                       // (a host plan's four pointers, a dev plan's eight, a size dev plan's seven; a block container's eight and eleven)
+	const void* g_args[12] = {};                       // (a host plan's four pointers, a dev plan's eight, a size dev plan's seven; a block container's eight and eleven; a block reader's twelve)
 	uint64_t g_epoch = 0, g_mode = 0;
 	uint32_t executions = 0;
 	bool ran = false;                                  // executed at least once (mscomp_amd_debug_plan_paths: a dev plan's counts are those of its last execution)
@@ -965,6 +965,29 @@ static void run_dev_paths(mscomp_amd_plan* p)
 	launch_dev_paths(p->ctx->stream, (int)p->format, p->n_units, static_cast<const u64*>(p->tables.p), dev_paths(p));
 }
 
+// The bounds of a decompress dev plan's per-unit counts summed over the batch: every accepted unit has in_len <= 0xFFFFF000 and the accepted
+// ones sum to at most in_total_max / out_total_max; a rejected unit counts as an empty one (one chunk, 64 token slots, 3 candidates).
+// false: more than the tables can address (MSCOMP_MEM_ERROR). Needs no device: a creator calls it before the context is used.
+static bool decode_dev_counts(MSCompFormat format, uint64_t N, uint64_t in_total_max, uint64_t O, bool sizing, uint64_t& I, uint64_t& chunks, uint64_t& toks, uint64_t& cands)
+{
+	I = in_total_max < N * 0xFFFFF000ull ? in_total_max : N * 0xFFFFF000ull;
+	chunks = N; toks = 0; cands = 0;
+	if (format == MSCOMP_LZNT1) { chunks = N + I / LZD_SEG; }
+	if (format == MSCOMP_XPRESS_HUFF) { chunks = N + I / XHC_TILE_BYTES; }
+	if (chunks > 0x7FFFFFF0ull) { return false; }
+	if (format != MSCOMP_LZNT1 && !sizing) {
+		const uint64_t by_in = (format == MSCOMP_XPRESS ? 1 : 8) * I + O / 32766u + N;   // (I < 2^45 here for Xpress+Huffman: its chunk bound held)
+		toks = (O < by_in ? O : by_in) + 64 * N;
+		if (toks > (1ull << 46)) { return false; }
+	}
+	if (format == MSCOMP_XPRESS_HUFF) {
+		const uint64_t by_out = O / 65536u + 2 * N, by_len = I / 260u + N, most = by_out < by_len ? by_out : by_len;
+		cands = most + most / 4 + 2 * N;
+		if (cands > 0x7FFFFFF0ull) { return false; }
+	}
+	return true;
+}
+
 // Decompress plans, and size plans: a decompress dev plan whose table pass takes the limits for the capacities (devplan.hip
 // dv_tables_kernel<true>), with no bound on their sum (out_total_max = 2^64 - 1 here: a unit's candidate slots are then bounded by its input,
 // whatever its limit) and whose scratch follows the input alone (the token prefix is written and not used: a size plan stores no tokens).
@@ -975,23 +998,10 @@ static MSCompStatus create_decode_dev(mscomp_amd_ctx* c, MSCompFormat format, si
 	*out = nullptr;
 	if (!c || n_units > 0x7FFFFFF0u || (flags & ~MSCOMP_AMD_DEV_LARGE_UNITS)) { return MSCOMP_ARG_ERROR; }
 	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
-	// the bounds of the per-unit counts summed over the batch (checked before the context is used): every accepted unit has in_len <= 0xFFFFF000 and the accepted ones sum to at
-	// most in_total_max / out_total_max; a rejected unit counts as an empty one (one chunk, 64 token slots, 3 candidates)
-	const uint64_t N = n_units, I = in_total_max < N * 0xFFFFF000ull ? in_total_max : N * 0xFFFFF000ull, O = out_total_max;
-	uint64_t chunks = N, toks = 0, cands = 0;
-	if (format == MSCOMP_LZNT1) { chunks = N + I / LZD_SEG; }
-	if (format == MSCOMP_XPRESS_HUFF) { chunks = N + I / XHC_TILE_BYTES; }
-	if (chunks > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
-	if (format != MSCOMP_LZNT1 && !sizing) {
-		const uint64_t by_in = (format == MSCOMP_XPRESS ? 1 : 8) * I + O / 32766u + N;   // (I < 2^45 here for Xpress+Huffman: its chunk bound held)
-		toks = (O < by_in ? O : by_in) + 64 * N;
-		if (toks > (1ull << 46)) { return MSCOMP_MEM_ERROR; }
-	}
-	if (format == MSCOMP_XPRESS_HUFF) {
-		const uint64_t by_out = O / 65536u + 2 * N, by_len = I / 260u + N, most = by_out < by_len ? by_out : by_len;
-		cands = most + most / 4 + 2 * N;
-		if (cands > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
-	}
+	const uint64_t N = n_units;
+	uint64_t I = 0, chunks = 0, toks = 0, cands = 0;
+	if (!decode_dev_counts(format, N, in_total_max, out_total_max, sizing, I, chunks, toks, cands)) { return MSCOMP_MEM_ERROR; }   // (checked before the context is used)
+	const uint64_t O = out_total_max;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());
@@ -1388,6 +1398,122 @@ MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* b, const uint8_t* d_out,
 		{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, b->n_blocks, d_out, t.in_off, t.aux_a, t.ucrc, nullptr, nullptr, nullptr, c->crc_blocks); }
 		{ KernelTimer k(c, "bk_kfold_kernel"); launch_blocks_kfold(c->stream, b->n_res, d_block_crc, t, d_out_len, d_status); }
 	});
+}
+
+// ---- block readers (include/mscomp_amd.h; kernels: reader.hip) ----
+// A reader owns one inner decompress dev plan over blocks_max units within blocks_max B bytes on either side, the cache those units are
+// decoded into and its own tables: everything is sized by what one call may read, nothing by what the container holds but the 4 bytes per
+// entry of its block table. The call runs the inner plan's launches (dev_launch) and the CRC kernels between its own passes, through plan_run
+// with a record of its own (run), as a container does.
+struct mscomp_amd_reader {
+	mscomp_amd_ctx* ctx = nullptr;
+	MSCompFormat format = MSCOMP_NONE;
+	uint32_t shift = 0, n_res = 0, nbt = 0, n_req = 0, m = 0;   // block_size = 1 << shift; nbt = n_blocks_table; m = blocks_max
+	mscomp_amd_plan* dplan = nullptr;                  // (null when blocks_max is 0)
+	mscomp_amd_plan run;
+	DevBuf tab, cache;                                 // ReaderTab; blocks_max slots of block_size bytes
+	ReaderTab t{};
+	bool ran = false;
+};
+
+static size_t reader_tab_bytes(size_t n, size_t m, size_t nbt) { return (5 * n + 1 + 8 * m + 1) * 8 + (n + 6 * m + nbt + 2) * 4 + 64; }
+static void reader_tab(mscomp_amd_reader* r)
+{
+	const size_t n = r->n_req, m = r->m;
+	u64* q = static_cast<u64*>(r->tab.p);
+	ReaderTab& t = r->t;
+	t.q_off = q; t.q_want = q + n; t.q_j0 = q + 2 * n; t.q_len = q + 3 * n; t.unit_first = q + 4 * n; q += 5 * n + 1;
+	t.in_off = q; t.in_len = q + m; t.out_off = q + 2 * m; t.out_cap = q + 3 * m; t.ulen = q + 4 * m; t.src = q + 5 * m; t.clen = q + 6 * m; t.cum = q + 7 * m; q += 8 * m + 1;
+	t.q_stat = reinterpret_cast<int32_t*>(q); t.ustat = t.q_stat + n;
+	t.act = reinterpret_cast<uint32_t*>(t.ustat + m); t.owner = t.act + m; t.uq = t.act + 2 * m; t.ublk = t.act + 3 * m; t.ucrc = t.act + 4 * m;
+	t.own = t.act + 5 * m; t.cnt = t.own + r->nbt;
+}
+
+MSCompStatus mscomp_amd_reader_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_req,
+                                      uint64_t blocks_max, uint32_t flags, mscomp_amd_reader** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
+	if (n_res > 0x7FFFFFF0u || n_blocks_table > 0x7FFFFFF0u || n_req > 0x7FFFFFF0u || blocks_max > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	const uint64_t M = blocks_max, bytes = M * block_size;                // (< 2^50)
+	uint64_t I = 0, chunks = 0, toks = 0, cands = 0;
+	if (!decode_dev_counts(format, M, bytes, bytes, false, I, chunks, toks, cands)) { return MSCOMP_MEM_ERROR; }   // (what the inner plan would refuse: checked before the context is used)
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_reader> r(new (std::nothrow) mscomp_amd_reader());
+	if (!r) { return MSCOMP_MEM_ERROR; }
+	r->ctx = c; r->format = format; r->shift = (uint32_t)__builtin_ctz(block_size); r->n_res = (uint32_t)n_res; r->nbt = (uint32_t)n_blocks_table;
+	r->n_req = (uint32_t)n_req; r->m = (uint32_t)M;
+	r->run.ctx = c; r->run.n_units = (uint32_t)n_req;
+	MSCompStatus st = MSCOMP_OK;
+	if (!r->tab.reserve(reader_tab_bytes(n_req, M, n_blocks_table)) || (M && !r->cache.reserve(bytes + 64))) { st = MSCOMP_MEM_ERROR; }
+	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, bytes, bytes, &r->dplan); }
+	if (st != MSCOMP_OK) {
+		(void)hipGetLastError();
+		mscomp_amd_plan_destroy(r->dplan);
+		r->tab.release(); r->cache.release();
+		return st;
+	}
+	reader_tab(r.get());
+	*out = r.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_reader_destroy(mscomp_amd_reader* r)
+{
+	if (!r) { return; }
+	DeviceGuard g(r->ctx->device);
+	(void)hipStreamSynchronize(r->ctx->stream);
+	mscomp_amd_plan_destroy(r->dplan);
+	r->tab.release(); r->cache.release();
+	delete r;                                              // (run gives up its graph)
+}
+
+MSCompStatus mscomp_amd_reader_read(mscomp_amd_reader* r, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
+                                    const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_req,
+                                    uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!r || !d_block_first || !d_block_off || (r->n_res && !d_res_len)) { return MSCOMP_ARG_ERROR; }
+	if (r->n_req && (!d_req || !d_out_off || !d_out_cap || !d_out_len || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if (r->m && (!d_packed || !d_out)) { return MSCOMP_ARG_ERROR; }
+	if (r->n_req == 0) { return MSCOMP_OK; }               // (nothing to report on)
+	mscomp_amd_ctx* c = r->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (r->dplan) { note_modes(r->dplan); r->dplan->ran = true; }
+	r->ran = true;
+	const void* args[12] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
+	                         d_out, d_out_off, d_out_cap, d_out_len, d_status };
+	return plan_run(&r->run, args, [&] {
+		const ReaderTab& t = r->t;
+		uint8_t* cache = static_cast<uint8_t*>(r->cache.p);
+		{ KernelTimer k(c, "rd_req_kernel"); launch_reader_requests(c->stream, r->n_req, r->n_res, r->nbt, r->m, r->shift, d_res_len, d_block_first, d_req, d_out_cap, t); }
+		{ KernelTimer k(c, "rd_units"); launch_reader_units(c->stream, r->n_req, r->nbt, r->m, r->shift, packed_len, d_packed, cache, d_block_off, t); }
+		if (r->dplan) { dev_launch(r->dplan, d_packed, t.in_off, t.in_len, cache, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (d_block_crc && r->m) {                                          // the owners' blocks lie under two bases: their addresses go in as offsets from a null one
+			{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, r->m, ~(u64)0, nullptr, t.clen, nullptr, t.cum, nullptr); }
+			{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, r->m, t.cum, t.ucrc, nullptr, nullptr); }
+			{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, r->m, nullptr, t.src, t.cum, t.ucrc, nullptr, nullptr, nullptr, c->crc_blocks); }
+		}
+		{ KernelTimer k(c, "rd_fold_kernel"); launch_reader_fold(c->stream, r->n_req, d_block_crc, t, d_out_len, d_status); }
+		{ KernelTimer k(c, "rd_gather_kernel"); launch_reader_gather(c->stream, r->n_req, r->m, r->shift, d_out, d_out_off, t, c->cpd_blocks); }
+	});
+}
+
+int mscomp_amd_reader_counts(mscomp_amd_reader* r, uint32_t out[3])
+{	// units, distinct blocks and decoded blocks of the reader's last execution (read back; none before the first)
+	if (!r || !out) { return -1; }
+	DeviceGuard g(r->ctx->device);
+	if (!g.ok || hipStreamSynchronize(r->ctx->stream) != hipSuccess) { return -1; }
+	out[0] = out[1] = out[2] = 0;
+	if (!r->ran) { return 0; }
+	uint64_t units = 0;
+	if (hipMemcpy(&units, r->t.unit_first + r->n_req, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (hipMemcpy(&out[1], r->t.cnt, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	out[0] = (uint32_t)units;
+	return 0;
 }
 
 // Stage-level test hook: per-position (len-3 capped at 45, offset) of ONE unit as found by the HIP match finder.

@@ -6,17 +6,6 @@
 
 namespace msc {
 
-// largest r with first[r] <= b (first[0] = 0 <= b < first[n]): the resource that holds block b; empty resources in front of it are skipped
-__device__ __forceinline__ uint32_t res_of_block(const u64* __restrict__ first, uint32_t n, u64 b)
-{
-	uint32_t lo = 0, hi = n;
-	while (hi - lo > 1) {
-		const uint32_t mid = lo + ((hi - lo) >> 1);
-		if (first[mid] <= b) { lo = mid; } else { hi = mid; }
-	}
-	return lo;
-}
-
 // ---- compress ----
 // One block walks the resources in tiles of 1024: the bounds check (running total of res_len <= in_max; a rejected resource has no blocks),
 // block_first (n + 1), and where the resource's compressed blocks are staged: resources back to back in block order, every start rounded up

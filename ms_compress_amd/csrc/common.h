@@ -268,6 +268,18 @@ __device__ __forceinline__ void dv_block_scan(u64 (&v)[K], u64 (&carry)[K], u64 
 	__syncthreads();
 }
 
+// largest r with first[r] <= b (first[0] = 0 <= b < first[n]): the resource that holds block b of a block container, or the request that
+// holds unit b of a block reader; empty ones in front of it are skipped (blocks.hip, reader.hip)
+__device__ __forceinline__ uint32_t res_of_block(const u64* __restrict__ first, uint32_t n, u64 b)
+{
+	uint32_t lo = 0, hi = n;
+	while (hi - lo > 1) {
+		const uint32_t mid = lo + ((hi - lo) >> 1);
+		if (first[mid] <= b) { lo = mid; } else { hi = mid; }
+	}
+	return lo;
+}
+
 #define CPD_THREADS 256u
 struct __attribute__((packed)) cpd_u16 { uint32_t w[4]; };  // 16 bytes of alignment 1
 

@@ -257,6 +257,32 @@ void launch_blocks_ktables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint3
                            const u64* range, const u64* d_out_off, const int32_t* d_status, const BlocksTab& t);
 void launch_blocks_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_crc, const BlocksTab& t, u64* d_out_len, int32_t* d_status);
 
+// ---- block readers (reader.hip; mscomp_amd_reader_*) ----
+// The reader's own tables, in one buffer (api.hip reader_tab is the only place that knows the layout). n = requests, m = blocks_max: the
+// bound of the units, a unit being one (request, covering block) pair of an admitted request; nbt = the entries of the container's block table.
+struct ReaderTab {
+	u64 *q_off, *q_want, *q_j0, *q_len;                // n each: clipped offset, bytes wanted, container index of the first covering block, the resource's length
+	u64* unit_first;                                   // n + 1: first unit of every request
+	int32_t* q_stat;                                   // n: the request's own status (checks 1-5), then -- behind the fold -- its final one
+	u64 *in_off, *in_len, *out_off, *out_cap, *ulen;   // m each: the inner plan's unit tables and d_out_len (only an owner that is decoded has a length)
+	u64* src;                                          // m: an owner's block, as an address: its cache slot, or its place in d_packed when stored raw
+	u64 *clen, *cum;                                   // m, m + 1: the bytes the CRC kernel reads of every unit (an owner that passed the table checks: e) and their running sum
+	int32_t* ustat;                                    // m: the inner plan's d_status
+	uint32_t *act, *owner, *uq, *ublk, *ucrc;          // m each: kind | data length << 2; the unit that owns this unit's block; its request; its block; the CRC-32 read
+	uint32_t* own;                                     // nbt: per block of the container the bid of its owner (~unit, 0 = nobody)
+	uint32_t* cnt;                                     // 2: distinct blocks of the last execution, and those that were decoded
+};
+// checks 1-5 per request, the clipped ranges and unit_first (one block)
+void launch_reader_requests(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, const u64* res_len,
+                            const u64* block_first, const u64* req, const u64* out_cap, const ReaderTab& t);
+// behind it: t.own cleared, one owner per covering block, then the table checks and the inner plan's unit tables (three launches)
+void launch_reader_units(hipStream_t st, uint32_t n_req, uint32_t nbt, uint32_t m, uint32_t shift, u64 packed_len, const uint8_t* packed,
+                         const uint8_t* cache, const u64* block_off, const ReaderTab& t);
+// behind the inner plan and the CRC kernels: status and length per request (block_crc may be null), then the slices of the MSCOMP_OK
+// requests to d_out (`blocks` = compact_dev_blocks())
+void launch_reader_fold(hipStream_t st, uint32_t n_req, const uint32_t* block_crc, const ReaderTab& t, u64* d_out_len, int32_t* d_status);
+void launch_reader_gather(hipStream_t st, uint32_t n_req, uint32_t m, uint32_t shift, uint8_t* out, const u64* out_off, const ReaderTab& t, uint32_t blocks);
+
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status
 // MSCOMP_ARG_ERROR), off[i] = its offset. in_off / off and status may be null.
