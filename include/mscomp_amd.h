@@ -534,6 +534,75 @@ MSCompStatus mscomp_amd_reader_read(mscomp_amd_reader* rd, const uint8_t* d_pack
                                     uint64_t* d_out_len, int32_t* d_status);
 int          mscomp_amd_reader_counts(mscomp_amd_reader* rd, uint32_t out[3]);
 
+/* Block writers: byte-range writes into a block container, batched and out of place. A request q = (r, off, len) overwrites the bytes
+ * [off, off + len) of resource r, as pwrite does within a file's length; one call applies n_req of them and writes a NEW container -- packed
+ * bytes, offset table and, when the old one has them, block checksums -- in which only the blocks the writes touched were decoded, patched
+ * and encoded again, and every other block is carried over as it was stored. A writer is an object of its own, sized by what one call
+ * WRITES; like a reader it needs only the tables a container wrote and the packed bytes. A write never changes a resource's length.
+ *   Creation:     exactly as mscomp_amd_reader_create: the same arguments, the same checks in the same order before the context is used
+ *                 (MSCOMP_ARG_ERROR; MSCOMP_MEM_ERROR where blocks_max B bytes are more than a dev plan can address), flags 0, *wr cleared
+ *                 on failure. All scratch is reserved here, once, and never grows: a block cache of blocks_max B bytes, a staging area of
+ *                 blocks_max B bytes, a decompress and a compress dev plan for blocks_max units within blocks_max B bytes each, and the
+ *                 writer's tables: 96 bytes per unit of blocks_max, 44 per request, 8 per entry of the block table. The LZNT1 dictionary
+ *                 flavour is fixed here, as for mscomp_amd_blocks_create.
+ *   Out of place: the old container is d_packed (packed_len valid bytes), d_block_off (n_blocks_table + 1) and d_block_crc (n_blocks_table,
+ *                 may be NULL); it is only read. The new one goes to d_new_packed (nothing at or behind new_cap), d_new_block_off
+ *                 (n_blocks_table + 1) and d_new_block_crc (n_blocks_table; NULL exactly when d_block_crc is), which must not overlap the
+ *                 old arrays. d_block_first (n_res + 1) and d_res_len (n_res) serve both. A caller ping-pongs two sets of buffers.
+ *   Write:        d_req = 3 n_req uint64: resource, offset, length; the bytes of request q are read at d_src + d_src_off[q], at any
+ *                 alignment. d_written, d_status: n_req entries; d_res_status: n_res. The rules, in this order:
+ *                   0. the table as a whole: nb = d_block_first[n_res] must not exceed n_blocks_table and d_block_first must not decrease
+ *                      anywhere. Otherwise every request and every resource gets MSCOMP_ARG_ERROR, every d_written is 0, d_new_block_off
+ *                      and d_new_block_crc are all 0, and nothing else is written;
+ *                   1. MSCOMP_ARG_ERROR: r >= n_res (the reader's rule 1);
+ *                   2. MSCOMP_DATA_ERROR: d_block_first[r + 1] - d_block_first[r] is not ceil(L / B), L = d_res_len[r];
+ *                   3. the range is clipped as the reader clips it: off' = min(off, L), want = min(len, L - off'); no sum of off and len
+ *                      is formed. want = 0 is MSCOMP_OK with no blocks. There is no capacity rule: the source is the want bytes;
+ *                   4. the budget, the reader's rule 5 unchanged: the running total of covering blocks over the requests that passed 1-3,
+ *                      before any sharing, must not exceed blocks_max; otherwise MSCOMP_ARG_ERROR;
+ *                   5. every covering block must be readable: it passes the container's table checks, decodes exactly as ms_decompress
+ *                      with capacity e to e bytes, and -- with d_block_crc -- has the CRC-32 the table says (the reader's rule 6). Any
+ *                      failure is MSCOMP_DATA_ERROR for every request that covers that block, and for no other. A block is decoded and
+ *                      checked once, however many requests touch it; in this version also when the requests overwrite all of it;
+ *                   6. verdicts before bytes: d_status[q] = MSCOMP_OK and d_written[q] = want only if every rule passed; otherwise
+ *                      d_written[q] = 0 and none of the request's bytes are applied to any block;
+ *                   7. the data of a touched block is its old data with the MSCOMP_OK requests applied in request order: where two
+ *                      requests cover the same byte, the later one wins, whatever order the hardware runs them in;
+ *                   8. the new container: a block is dirty when at least one MSCOMP_OK request covers it. A dirty block's stored form is
+ *                      the rule of mscomp_amd_blocks_compress on its new data (ms_compress's counted bytes when shorter, the raw block
+ *                      otherwise) and its CRC-32 is computed again. A clean block -- one that only failed requests touched included --
+ *                      keeps its stored bytes and its checksum verbatim; a clean block whose old entries are not
+ *                      d_block_off[j] <= d_block_off[j + 1] <= packed_len was unreadable and gets the stored length 0 (it stays
+ *                      unreadable). d_new_block_off[0 .. nb] is the exclusive running sum of the new stored lengths, the entries above nb
+ *                      repeat the total; d_new_block_crc is 0 at and above nb; d_new_packed[0 .. total) holds the blocks in order;
+ *                   9. capacity, the rule of mscomp_amd_blocks_compress: a block that would end beyond new_cap is not written and its
+ *                      resource gets d_res_status = MSCOMP_BUF_ERROR, the tables still hold the full layout; every other resource gets
+ *                      MSCOMP_OK. A stored block is never longer than its data, so new_cap = the sum of the data lengths never refuses.
+ *                 Consequence: when the old container was written by mscomp_amd_blocks_compress and all its blocks are healthy, the new
+ *                 one is byte for byte what mscomp_amd_blocks_compress and mscomp_amd_blocks_crc write for the patched data.
+ *                 Resource checksums (mscomp_amd_blocks_crc's d_res_crc) are not maintained; a resource cannot grow or shrink.
+ *   Counts:       mscomp_amd_writer_counts gives, for the last execution, out[0] = units (as a reader's), out[1] = distinct blocks touched,
+ *                 out[2] = blocks encoded again (the dirty ones); all 0 after a refused table. Otherwise as mscomp_amd_reader_counts.
+ *   Execution:    as the reader's: asynchronous on the ctx stream, kernels only, no allocation, no synchronisation, nothing read back, a
+ *                 launch sequence fixed by the creation bounds; legal inside a caller's capture from the first execution, a graph of its
+ *                 own from the second. MSCOMP_ARG_ERROR for a null wr or a null required array (d_src may be null when blocks_max is 0,
+ *                 d_packed and d_new_packed when blocks_max and n_blocks_table are 0, d_res_len and d_res_status when n_res is 0, the
+ *                 request arrays when n_req is 0), or when exactly one of d_block_crc and d_new_block_crc is null. n_req = 0 is legal and
+ *                 copies the container unchanged (unreadable entries become empty ones). */
+typedef struct mscomp_amd_writer mscomp_amd_writer;
+MSCompStatus mscomp_amd_writer_create(mscomp_amd_ctx* ctx, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table,
+                                      size_t n_req, uint64_t blocks_max, uint32_t flags, mscomp_amd_writer** wr);
+void         mscomp_amd_writer_destroy(mscomp_amd_writer* wr);
+MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* wr, const uint8_t* d_packed, uint64_t packed_len,
+                                     const uint64_t* d_block_first, const uint64_t* d_block_off, const uint64_t* d_res_len,
+                                     const uint32_t* d_block_crc /* may be NULL */,
+                                     const uint64_t* d_req /* 3 n_req: resource, offset, length */,
+                                     const uint8_t* d_src, const uint64_t* d_src_off,
+                                     uint8_t* d_new_packed, uint64_t new_cap, uint64_t* d_new_block_off /* n_blocks_table + 1 */,
+                                     uint32_t* d_new_block_crc /* NULL exactly when d_block_crc is */,
+                                     uint64_t* d_written /* n_req */, int32_t* d_status /* n_req */, int32_t* d_res_status /* n_res */);
+int          mscomp_amd_writer_counts(mscomp_amd_writer* wr, uint32_t out[3]);
+
 /* ---- measurement hooks (bench.py / profiles) ---- */
 /* When enabled, every kernel launch of plan_execute is bracketed by hipEvents on the ctx stream. */
 void         mscomp_amd_profile_enable(mscomp_amd_ctx* ctx, int on);

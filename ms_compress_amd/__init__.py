@@ -12,4 +12,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   CompressDevPlan, plan_layout_dev, SizeDevPlan, compact_dev,
                   BlockContainer, blocks_compress, blocks_decompress,
                   CrcDevPlan, crc32_units, blocks_crc,
-                  BlockReader, blocks_read)
+                  BlockReader, blocks_read,
+                  BlockWriter, blocks_write)

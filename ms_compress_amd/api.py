@@ -42,6 +42,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_blocks_create", "mscomp_amd_blocks_destroy", "mscomp_amd_blocks_bound", "mscomp_amd_blocks_compress", "mscomp_amd_blocks_decompress",
     "mscomp_amd_plan_create_crc_dev", "mscomp_amd_plan_execute_crc_dev", "mscomp_amd_blocks_crc", "mscomp_amd_blocks_check",
     "mscomp_amd_reader_create", "mscomp_amd_reader_destroy", "mscomp_amd_reader_read", "mscomp_amd_reader_counts",
+    "mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_write", "mscomp_amd_writer_counts",
 ]
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 
@@ -159,6 +160,14 @@ def load_library():
     lib.mscomp_amd_reader_read.restype = C.c_int
     lib.mscomp_amd_reader_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.mscomp_amd_reader_counts.restype = C.c_int
+    lib.mscomp_amd_writer_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_writer_create.restype = C.c_int
+    lib.mscomp_amd_writer_destroy.argtypes = [C.c_void_p]
+    lib.mscomp_amd_writer_destroy.restype = None
+    lib.mscomp_amd_writer_write.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 8 + [C.c_uint64] + [C.c_void_p] * 5
+    lib.mscomp_amd_writer_write.restype = C.c_int
+    lib.mscomp_amd_writer_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.mscomp_amd_writer_counts.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -776,6 +785,128 @@ def blocks_read(fmt, packed, block_first, block_off, lengths, block_size, reques
     if own:
         ctx.close()
     return res, [int(x) for x in h_st[:nq]]
+
+
+class BlockWriter:
+    """A block writer (mscomp_amd_writer_create): batched byte-range writes into a block container, out of place. Made once for ``n_req``
+    requests per call that together cover at most ``blocks_max`` blocks (counted per request, before any sharing), against the tables of
+    a container of ``n_res`` resources whose d_block_off has ``n_blocks_table`` + 1 entries. All scratch is reserved here: a cache and a
+    staging area of blocks_max blocks each, two inner dev plans, 96 bytes of tables per unit of blocks_max, 44 per request and 8 per
+    block-table entry. write() enqueues kernels on the ctx stream and nothing else (legal inside a capture of that stream). Arguments
+    are torch CUDA tensors: uint8 data, int64 / uint64 tables, int32 statuses and checksums."""
+
+    def __init__(self, ctx, fmt, block_size, n_res, n_blocks_table, n_req, blocks_max):
+        self.ctx, self.fmt, self.block_size = ctx, int(fmt), int(block_size)
+        self.n_res, self.n_blocks_table, self.n_req, self.blocks_max = int(n_res), int(n_blocks_table), int(n_req), int(blocks_max)
+        self._h = C.c_void_p()
+        st = ctx.lib.mscomp_amd_writer_create(ctx._h, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_req, self.blocks_max, 0,
+                                              C.byref(self._h))
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_writer_create")
+
+    def write(self, d_packed, d_block_first, d_block_off, d_res_len, d_req, d_src, d_src_off, d_new_packed, d_new_block_off, d_written, d_status,
+              d_res_status, d_block_crc=None, d_new_block_crc=None, packed_len=None, new_cap=None):
+        """Request q = (resource, offset, length) = d_req[3 q .. 3 q + 2], clipped to the resource as the reader clips it; its bytes are read
+        at d_src + d_src_off[q]. The old container (d_packed, d_block_off, d_block_crc) is only read; the new one is written to
+        d_new_packed (nothing at or behind ``new_cap``, default: all of it), d_new_block_off and d_new_block_crc (given exactly when
+        d_block_crc is). d_status[q] is MSCOMP_OK with d_written[q] = the clipped length, or MSCOMP_ARG_ERROR (no such resource, or over
+        the budget of blocks_max) or MSCOMP_DATA_ERROR (a damaged table or block) with d_written[q] = 0 and no byte of the request
+        applied. d_res_status[r] is MSCOMP_BUF_ERROR when a block of the resource did not fit below new_cap. A touched block is decoded,
+        patched in request order and encoded again; every other block keeps its stored bytes."""
+        plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
+        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
+        if d_new_packed is not None and cap > d_new_packed.numel():
+            raise ValueError("new_cap exceeds d_new_packed")
+        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_src,
+                                                                         d_src_off, d_new_packed, d_new_block_off, d_new_block_crc, d_written,
+                                                                         d_status, d_res_status)]
+        st = self.ctx.lib.mscomp_amd_writer_write(self._h, p[0], plen, *p[1:9], cap, *p[9:])
+        if st != MSCOMP_OK:
+            raise MSCompError(st, "mscomp_amd_writer_write")
+
+    def counts(self):
+        """(units, distinct blocks touched, blocks encoded again) of the last write(); synchronizes the stream."""
+        out = (C.c_uint32 * 3)()
+        if self.ctx.lib.mscomp_amd_writer_counts(self._h, out) != 0:
+            raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_writer_counts")
+        return (int(out[0]), int(out[1]), int(out[2]))
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.mscomp_amd_writer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def blocks_write(fmt, packed, block_first, block_off, lengths, block_size, writes, ctx=None, block_crc=None):
+    """Write byte ranges into a block container on the GPU: ``writes`` is a list of (resource, offset, bytes), each clipped to its resource
+    (a write never changes a resource's length); ``lengths`` are the resources' original lengths; ``block_crc`` (optional, as blocks_crc
+    returns it): every block touched is held to its checksum first, and the new container gets checksums too. Returns numpy arrays and
+    lists (new_packed uint8, new_block_off uint64, new_block_crc uint32 or None, written, statuses, res_statuses): the new container
+    shares block_first and lengths with the old one."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    n, nq = len(lengths), len(writes)
+    lens = [int(x) for x in lengths]
+    B = int(block_size)
+    M64 = (1 << 64) - 1
+    reqs = [(int(r) & M64, int(o) & M64, len(b)) for r, o, b in writes]
+    blocks = 0
+    for r, o, ln in reqs:                                      # the budget: the covering blocks of every request, unshared
+        L = lens[r] if r < n else 0
+        o = min(o, L)
+        w = min(ln, L - o)
+        blocks += ((o + w - 1) // B - o // B + 1) if w else 0
+    src_off, src_total = pack_offsets([len(b) for _, _, b in writes])
+    nbt = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
+    total = int(sum(lens))
+    dev = torch.device("cuda", ctx.device)
+
+    def up(a, least):
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+        a = np.concatenate([a, np.full(max(0, least - len(a)), a[-1] if len(a) else 0, dtype=np.uint64)])
+        return torch.from_numpy(a.view(np.int64).copy()).to(dev)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        wr = BlockWriter(ctx, fmt, B, n, nbt, nq, blocks)
+        packed = np.ascontiguousarray(np.frombuffer(bytes(packed), dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed, dtype=np.uint8)
+        d_packed = torch.zeros(len(packed) + 16, dtype=torch.uint8, device=dev)
+        if len(packed):
+            d_packed[: len(packed)] = torch.from_numpy(packed.copy()).to(dev)
+        h_src = np.zeros(src_total + 16, dtype=np.uint8)
+        for (_, _, b), o in zip(writes, src_off):
+            h_src[int(o): int(o) + len(b)] = np.frombuffer(bytes(b), dtype=np.uint8)
+        d_src = torch.from_numpy(h_src).to(dev)
+        d_first, d_boff, d_len = up(block_first, n + 1), up(block_off, nbt + 1), up(lens, 1)
+        d_req, d_soff = up(np.array(reqs, dtype=np.uint64).reshape(-1), 3), up(src_off, 1)
+        d_crc = d_ncrc = None
+        if block_crc is not None:
+            h_crc = np.zeros(max(1, nbt), dtype=np.uint32)
+            k = min(len(block_crc), len(h_crc))
+            h_crc[:k] = np.asarray(block_crc, dtype=np.uint32)[:k]
+            d_crc = torch.from_numpy(h_crc.view(np.int32).copy()).to(dev)
+            d_ncrc = torch.zeros(max(1, nbt), dtype=torch.int32, device=dev)
+        d_new = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
+        d_noff = torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
+        d_wr = torch.zeros(max(1, nq), dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, nq), dtype=torch.int32, device=dev)
+        d_rst = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        wr.write(d_packed, d_first, d_boff, d_len, d_req, d_src, d_soff, d_new, d_noff, d_wr, d_st, d_rst, d_block_crc=d_crc, d_new_block_crc=d_ncrc,
+                 packed_len=len(packed), new_cap=total)
+        ctx.stream.synchronize()
+        noff = d_noff.cpu().numpy().view(np.uint64).copy()
+        new_packed = d_new.cpu().numpy()[: min(int(noff[nbt]), total)].copy()
+        ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nbt].copy()
+        h_wr, h_st, h_rst = d_wr.cpu().numpy().view(np.uint64), d_st.cpu().numpy(), d_rst.cpu().numpy()
+        wr.close()
+    if own:
+        ctx.close()
+    return new_packed, noff, ncrc, [int(x) for x in h_wr[:nq]], [int(x) for x in h_st[:nq]], [int(x) for x in h_rst[:n]]
 
 
 def plan_paths(plan):

@@ -124,7 +124,7 @@ struct mscomp_amd_plan {
 	// the plan's launch sequence as a hipGraph (plan_run): captured on the plan's second execution, replayed while the
 	// arguments and the scratch buffers stay where they were
 	hipGraphExec_t gexec = nullptr;
-	const void* g_args[12] = {};                       // (a host plan's four pointers, a dev plan's eight, a size dev plan's seven; a block container's eight and eleven; a block reader's twelve)
+	const void* g_args[16] = {};                       // (a host plan's four pointers, a dev plan's eight, a size dev plan's seven; a block container's eight and eleven; a block reader's twelve; a block writer's sixteen)
 	uint64_t g_epoch = 0, g_mode = 0;
 	uint32_t executions = 0;
 	bool ran = false;                                  // executed at least once (mscomp_amd_debug_plan_paths: a dev plan's counts are those of its last execution)
@@ -1513,6 +1513,139 @@ int mscomp_amd_reader_counts(mscomp_amd_reader* r, uint32_t out[3])
 	if (hipMemcpy(&units, r->t.unit_first + r->n_req, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
 	if (hipMemcpy(&out[1], r->t.cnt, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
 	out[0] = (uint32_t)units;
+	return 0;
+}
+
+// ---- block writers (include/mscomp_amd.h; kernels: writer.hip and the reader's) ----
+// A writer owns what a reader owns -- the inner decompress dev plan over blocks_max units, the cache, the reader's tables -- and beside it an
+// inner compress dev plan over the same units (a dirty block is compressed from its cache slot into its staging slot), the staging area and
+// three more columns. The call runs the reader's passes up to the fold, then its own, through plan_run with a record of its own.
+struct mscomp_amd_writer {
+	mscomp_amd_ctx* ctx = nullptr;
+	MSCompFormat format = MSCOMP_NONE;
+	uint32_t shift = 0, n_res = 0, nbt = 0, n_req = 0, m = 0;   // as a reader's
+	mscomp_amd_plan* dplan = nullptr; mscomp_amd_plan* cplan = nullptr;   // (null when blocks_max is 0)
+	mscomp_amd_plan run;
+	DevBuf tab, cache, stage;                          // WriterTab; blocks_max slots of block_size bytes each
+	WriterTab t{};
+	bool ran = false;
+};
+
+static size_t writer_tab_bytes(size_t n, size_t m, size_t nbt) { return (5 * n + 1 + 8 * m + 1) * 8 + (n + 8 * m + 2 * nbt + 4) * 4 + 64; }
+static void writer_tab(mscomp_amd_writer* w)
+{
+	const size_t n = w->n_req, m = w->m;
+	u64* q = static_cast<u64*>(w->tab.p);
+	ReaderTab& t = w->t.r;
+	t.q_off = q; t.q_want = q + n; t.q_j0 = q + 2 * n; t.q_len = q + 3 * n; t.unit_first = q + 4 * n; q += 5 * n + 1;
+	t.in_off = q; t.in_len = q + m; t.out_off = q + 2 * m; t.out_cap = q + 3 * m; t.ulen = q + 4 * m; t.src = q + 5 * m; t.clen = q + 6 * m; t.cum = q + 7 * m; q += 8 * m + 1;
+	t.q_stat = reinterpret_cast<int32_t*>(q); t.ustat = t.q_stat + n;
+	t.act = reinterpret_cast<uint32_t*>(t.ustat + m); t.owner = t.act + m; t.uq = t.act + 2 * m; t.ublk = t.act + 3 * m; t.ucrc = t.act + 4 * m;
+	w->t.next = t.act + 5 * m; w->t.dirty = t.act + 6 * m;
+	t.own = t.act + 7 * m; w->t.head = t.own + w->nbt; t.cnt = w->t.head + w->nbt;
+}
+
+MSCompStatus mscomp_amd_writer_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_req,
+                                      uint64_t blocks_max, uint32_t flags, mscomp_amd_writer** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
+	if (n_res > 0x7FFFFFF0u || n_blocks_table > 0x7FFFFFF0u || n_req > 0x7FFFFFF0u || blocks_max > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
+	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	const uint64_t M = blocks_max, bytes = M * block_size;                // (< 2^50)
+	uint64_t I = 0, chunks = 0, toks = 0, cands = 0;
+	if (!decode_dev_counts(format, M, bytes, bytes, false, I, chunks, toks, cands)) { return MSCOMP_MEM_ERROR; }   // (as a reader: checked before the context is used)
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_writer> w(new (std::nothrow) mscomp_amd_writer());
+	if (!w) { return MSCOMP_MEM_ERROR; }
+	w->ctx = c; w->format = format; w->shift = (uint32_t)__builtin_ctz(block_size); w->n_res = (uint32_t)n_res; w->nbt = (uint32_t)n_blocks_table;
+	w->n_req = (uint32_t)n_req; w->m = (uint32_t)M;
+	w->run.ctx = c; w->run.n_units = (uint32_t)n_req;
+	MSCompStatus st = MSCOMP_OK;
+	if (!w->tab.reserve(writer_tab_bytes(n_req, M, n_blocks_table)) || (M && (!w->cache.reserve(bytes + 64) || !w->stage.reserve(bytes + 64)))) { st = MSCOMP_MEM_ERROR; }
+	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, bytes, bytes, &w->dplan); }
+	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_compress_dev(c, format, M, bytes, block_size, &w->cplan); }   // (fixes the LZNT1 dictionary flavour)
+	if (st != MSCOMP_OK) {
+		(void)hipGetLastError();
+		mscomp_amd_plan_destroy(w->dplan); mscomp_amd_plan_destroy(w->cplan);
+		w->tab.release(); w->cache.release(); w->stage.release();
+		return st;
+	}
+	writer_tab(w.get());
+	*out = w.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_writer_destroy(mscomp_amd_writer* w)
+{
+	if (!w) { return; }
+	DeviceGuard g(w->ctx->device);
+	(void)hipStreamSynchronize(w->ctx->stream);
+	mscomp_amd_plan_destroy(w->dplan); mscomp_amd_plan_destroy(w->cplan);
+	w->tab.release(); w->cache.release(); w->stage.release();
+	delete w;                                              // (run gives up its graph)
+}
+
+MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* w, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
+                                     const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_req,
+                                     const uint8_t* d_src, const uint64_t* d_src_off, uint8_t* d_new_packed, uint64_t new_cap, uint64_t* d_new_block_off,
+                                     uint32_t* d_new_block_crc, uint64_t* d_written, int32_t* d_status, int32_t* d_res_status)
+{
+	if (!w || !d_block_first || !d_block_off || !d_new_block_off || (w->n_res && (!d_res_len || !d_res_status))) { return MSCOMP_ARG_ERROR; }
+	if (w->n_req && (!d_req || !d_src_off || !d_written || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if ((w->m && !d_src) || ((w->m || w->nbt) && (!d_packed || !d_new_packed))) { return MSCOMP_ARG_ERROR; }
+	if ((d_block_crc == nullptr) != (d_new_block_crc == nullptr)) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = w->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (w->dplan) { note_modes(w->dplan); w->dplan->ran = true; w->cplan->ran = true; }
+	w->ran = true;
+	const void* args[16] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
+	                         d_src, d_src_off, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_off, d_new_block_crc,
+	                         d_written, d_status, d_res_status };
+	return plan_run(&w->run, args, [&] {
+		const WriterTab& wt = w->t;
+		const ReaderTab& t = wt.r;
+		uint8_t* cache = static_cast<uint8_t*>(w->cache.p); uint8_t* stage = static_cast<uint8_t*>(w->stage.p);
+		// the reader's passes: admission (without its capacity rule), owners, the owners' blocks decoded, checksummed and judged
+		{ KernelTimer k(c, "rd_req_kernel"); launch_reader_requests(c->stream, w->n_req, w->n_res, w->nbt, w->m, w->shift, d_res_len, d_block_first, d_req, nullptr, t); }
+		{ KernelTimer k(c, "rd_units"); launch_reader_units(c->stream, w->n_req, w->nbt, w->m, w->shift, packed_len, d_packed, cache, d_block_off, t); }
+		{ KernelTimer k(c, "wr_link"); launch_writer_link(c->stream, w->n_req, w->nbt, w->m, wt); }
+		if (w->dplan) { dev_launch(w->dplan, d_packed, t.in_off, t.in_len, cache, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (d_block_crc && w->m) {
+			{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, w->m, ~(u64)0, nullptr, t.clen, nullptr, t.cum, nullptr); }
+			{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, w->m, t.cum, t.ucrc, nullptr, nullptr); }
+			{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, w->m, nullptr, t.src, t.cum, t.ucrc, nullptr, nullptr, nullptr, c->crc_blocks); }
+		}
+		if (w->n_req) { KernelTimer k(c, "rd_fold_kernel"); launch_reader_fold(c->stream, w->n_req, d_block_crc, t, d_written, d_status); }
+		// the writer's own: patch, re-encode and checksum the dirty blocks, lay out, move
+		{ KernelTimer k(c, "wr_patch"); launch_writer_patch(c->stream, w->n_req, w->m, w->shift, d_src, d_src_off, cache, wt, c->cpd_blocks); }
+		if (w->cplan) { dev_launch(w->cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (d_block_crc && w->m) {
+			{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, w->m, ~(u64)0, nullptr, t.clen, nullptr, t.cum, nullptr); }
+			{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, w->m, t.cum, t.ucrc, nullptr, nullptr); }
+			{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, w->m, nullptr, t.src, t.cum, t.ucrc, nullptr, nullptr, nullptr, c->crc_blocks); }
+		}
+		{ KernelTimer k(c, "wr_layout_kernel"); launch_writer_layout(c->stream, w->n_req, w->n_res, w->nbt, w->m, packed_len, new_cap, d_block_first, d_block_off, d_block_crc,
+		                                                             wt, d_new_block_off, d_new_block_crc, d_written, d_status, d_res_status); }
+		{ KernelTimer k(c, "wr_move_kernel"); launch_writer_move(c->stream, w->nbt, w->shift, new_cap, d_packed, d_block_off, stage, cache, d_new_block_off, wt, d_new_packed, c->cpd_blocks); }
+	});
+}
+
+int mscomp_amd_writer_counts(mscomp_amd_writer* w, uint32_t out[3])
+{	// units, distinct blocks and re-encoded blocks of the writer's last execution (read back; none before the first, none for a refused table)
+	if (!w || !out) { return -1; }
+	DeviceGuard g(w->ctx->device);
+	if (!g.ok || hipStreamSynchronize(w->ctx->stream) != hipSuccess) { return -1; }
+	out[0] = out[1] = out[2] = 0;
+	if (!w->ran) { return 0; }
+	uint64_t units = 0;
+	uint32_t cnt[4] = {};
+	if (hipMemcpy(&units, w->t.r.unit_first + w->n_req, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (hipMemcpy(cnt, w->t.r.cnt, 16, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (cnt[3] == 0 && w->m) { out[0] = (uint32_t)units; out[1] = cnt[0]; out[2] = cnt[2]; }
 	return 0;
 }
 

@@ -324,4 +324,47 @@ __device__ __forceinline__ void cpd_move(uint8_t* __restrict__ dst, const uint8_
 	}
 }
 
+// ---- shared by reader.hip and writer.hip: the action word of a unit, the piece of the byte-moving passes, and one wave's move ----
+#define RD_SKIP   0u                                      // not an owner (or no unit at all): nothing to decode, read or check
+#define RD_COPY   1u                                      // a raw block: read in d_packed
+#define RD_DECODE 2u                                      // decoded into its cache slot
+#define RD_FAIL   3u                                      // failed a table check: never read (the action word of a unit: kind | data length << 2)
+#define RD_PIECE_SHIFT 14u                                // the gather and the patch move their bytes in pieces of 16 KiB
+
+// cnt <= 16 KiB bytes by one wave, as cpd_move moves a piece by a block: a bytewise head up to the destination's next 16-byte boundary
+// (lanes 0..14), a body of 16-byte stores (16-byte loads where the source is aligned alike, loads of alignment 1 otherwise, four in flight
+// per lane), a bytewise tail (lanes 16..30). No byte outside the two ranges is touched.
+__device__ __forceinline__ void rd_wave_move(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t cnt, uint32_t lane)
+{
+	uint32_t head = (16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u;
+	if (head > cnt) { head = cnt; }
+	const uint32_t body = (cnt - head) >> 4, tail0 = head + body * 16u;
+	const bool has_head = lane < head, has_tail = lane >= 16u && tail0 + (lane - 16u) < cnt;
+	const uint8_t hb = has_head ? src[lane] : (uint8_t)0, tb = has_tail ? src[tail0 + (lane - 16u)] : (uint8_t)0;
+	const bool same = (((uintptr_t)src + head) & 15u) == 0;
+	uint4* __restrict__ d16 = reinterpret_cast<uint4*>(dst + head);
+	const uint4* __restrict__ sa = reinterpret_cast<const uint4*>(src + head);
+	const cpd_u16* __restrict__ su = reinterpret_cast<const cpd_u16*>(src + head);
+	for (uint32_t k0 = 0; k0 < body || k0 == 0; k0 += 4u * 64u) {
+		uint4 v[4];
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) {
+			const uint32_t k = k0 + j * 64u + lane;
+			if (k < body) {
+				if (same) { v[j] = sa[k]; }
+				else { const cpd_u16 x = su[k]; v[j] = make_uint4(x.w[0], x.w[1], x.w[2], x.w[3]); }
+			}
+		}
+		if (k0 == 0) {
+			if (has_head) { dst[lane] = hb; }
+			if (has_tail) { dst[tail0 + (lane - 16u)] = tb; }
+		}
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) {
+			const uint32_t k = k0 + j * 64u + lane;
+			if (k < body) { d16[k] = v[j]; }
+		}
+	}
+}
+
 } // namespace msc

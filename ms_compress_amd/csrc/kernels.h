@@ -272,7 +272,7 @@ struct ReaderTab {
 	uint32_t* own;                                     // nbt: per block of the container the bid of its owner (~unit, 0 = nobody)
 	uint32_t* cnt;                                     // 2: distinct blocks of the last execution, and those that were decoded
 };
-// checks 1-5 per request, the clipped ranges and unit_first (one block)
+// checks 1-5 per request, the clipped ranges and unit_first (one block). out_cap null: without check 4 (a block writer's admission)
 void launch_reader_requests(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, const u64* res_len,
                             const u64* block_first, const u64* req, const u64* out_cap, const ReaderTab& t);
 // behind it: t.own cleared, one owner per covering block, then the table checks and the inner plan's unit tables (three launches)
@@ -282,6 +282,30 @@ void launch_reader_units(hipStream_t st, uint32_t n_req, uint32_t nbt, uint32_t 
 // requests to d_out (`blocks` = compact_dev_blocks())
 void launch_reader_fold(hipStream_t st, uint32_t n_req, const uint32_t* block_crc, const ReaderTab& t, u64* d_out_len, int32_t* d_status);
 void launch_reader_gather(hipStream_t st, uint32_t n_req, uint32_t m, uint32_t shift, uint8_t* out, const u64* out_off, const ReaderTab& t, uint32_t blocks);
+
+// ---- block writers (writer.hip; mscomp_amd_writer_*) ----
+// A writer admits, shares, decodes and judges with the reader's passes, on a ReaderTab of its own, and adds three columns to it (api.hip
+// writer_tab knows the layout).
+struct WriterTab {
+	ReaderTab r;                                       // (r.cnt has four words here: [2] = dirty blocks, [3] = 1 when the table as a whole was refused)
+	uint32_t* head;                                    // nbt: the last unit that joined a block's list, + 1 (0 = none); behind the layout pass, the move pass's word of the block
+	uint32_t* next;                                    // m: the unit that joined the list before this one, + 1
+	uint32_t* dirty;                                   // m: 1 for an owner whose block an MSCOMP_OK request covers
+};
+// behind launch_reader_units: t.head cleared, every unit linked to its block (two launches)
+void launch_writer_link(hipStream_t st, uint32_t n_req, uint32_t nbt, uint32_t m, const WriterTab& t);
+// behind the fold: raw owners loaded into the cache, the MSCOMP_OK requests applied in request order, t.dirty; then the unit tables of the inner
+// compress plan (r.in_off .. r.out_cap) and of the CRC kernels (r.src, r.clen) over the dirty owners (two launches; `blocks` = compact_dev_blocks())
+void launch_writer_patch(hipStream_t st, uint32_t n_req, uint32_t m, uint32_t shift, const uint8_t* src, const u64* src_off, uint8_t* cache,
+                         const WriterTab& t, uint32_t blocks);
+// behind the compress plan and the CRC kernels, one block: rule 0, new_off (nbt + 1), new_crc (nbt, may be null with block_crc), the move pass's
+// words, d_res_status, and -- for a refused table -- d_status and d_written
+void launch_writer_layout(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, u64 packed_len, u64 cap, const u64* block_first,
+                          const u64* block_off, const uint32_t* block_crc, const WriterTab& t, u64* new_off, uint32_t* new_crc, u64* d_written,
+                          int32_t* d_status, int32_t* d_res_status);
+// every block to dst + new_off[j]: clean ones from packed, dirty ones from stage or cache; nothing at or behind dst + cap
+void launch_writer_move(hipStream_t st, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* packed, const u64* block_off, const uint8_t* stage,
+                        const uint8_t* cache, const u64* new_off, const WriterTab& t, uint8_t* dst, uint32_t blocks);
 
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status

@@ -7,14 +7,11 @@
 
 namespace msc {
 
-#define RD_SKIP   0u                                      // not an owner (or no unit at all): nothing to decode, read or check
-#define RD_COPY   1u                                      // a raw block: read in d_packed
-#define RD_DECODE 2u                                      // decoded into its cache slot
-#define RD_FAIL   3u                                      // failed a table check: never read (the action word of a unit: kind | data length << 2)
-
 // One block walks the requests in tiles of 1024: checks 1-5 of the header in their order, the clipped range, the first covering block, and
 // unit_first (n + 1). Two scans: the covering blocks of every request that passed checks 1-4 (the budget's running total, which does not
-// know about sharing), and those of the admitted requests (the unit numbering).
+// know about sharing), and those of the admitted requests (the unit numbering). CAP: check 4, the reader's capacity rule -- a block writer
+// (writer.hip) admits its requests with the same pass and has no such rule (out_cap is not read).
+template <bool CAP>
 __global__ __launch_bounds__(DV_THREADS) void rd_req_kernel(uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift,
                                                            const u64* __restrict__ res_len, const u64* __restrict__ block_first, const u64* __restrict__ req,
                                                            const u64* __restrict__ out_cap, ReaderTab t)
@@ -39,7 +36,7 @@ __global__ __launch_bounds__(DV_THREADS) void rd_req_kernel(uint32_t n_req, uint
 				else if (f1 - f0 != (L >> shift) + ((L & (B - 1u)) ? 1u : 0u)) { st = -3; }   // MSCOMP_DATA_ERROR (from here on L < 2^50: nbt < 2^31 blocks)
 				else {
 					o = off < L ? off : L; w = len < L - o ? len : L - o;
-					if (w > out_cap[q]) { st = -5; w = 0; }                       // MSCOMP_BUF_ERROR
+					if (CAP && w > out_cap[q]) { st = -5; w = 0; }                       // MSCOMP_BUF_ERROR
 					else if (w) { c = ((o + w - 1u) >> shift) - (o >> shift) + 1u; j0 = f0 + (o >> shift); }
 				}
 			}
@@ -124,49 +121,12 @@ __global__ __launch_bounds__(256) void rd_fold_kernel(uint32_t n_req, const uint
 	}
 }
 
-// cnt <= 16 KiB bytes by one wave, as cpd_move moves a piece by a block: a bytewise head up to the destination's next 16-byte boundary
-// (lanes 0..14), a body of 16-byte stores (16-byte loads where the source is aligned alike, loads of alignment 1 otherwise, four in flight
-// per lane), a bytewise tail (lanes 16..30). No byte outside the two ranges is touched.
-__device__ __forceinline__ void rd_wave_move(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t cnt, uint32_t lane)
-{
-	uint32_t head = (16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u;
-	if (head > cnt) { head = cnt; }
-	const uint32_t body = (cnt - head) >> 4, tail0 = head + body * 16u;
-	const bool has_head = lane < head, has_tail = lane >= 16u && tail0 + (lane - 16u) < cnt;
-	const uint8_t hb = has_head ? src[lane] : (uint8_t)0, tb = has_tail ? src[tail0 + (lane - 16u)] : (uint8_t)0;
-	const bool same = (((uintptr_t)src + head) & 15u) == 0;
-	uint4* __restrict__ d16 = reinterpret_cast<uint4*>(dst + head);
-	const uint4* __restrict__ sa = reinterpret_cast<const uint4*>(src + head);
-	const cpd_u16* __restrict__ su = reinterpret_cast<const cpd_u16*>(src + head);
-	for (uint32_t k0 = 0; k0 < body || k0 == 0; k0 += 4u * 64u) {
-		uint4 v[4];
-		#pragma unroll
-		for (uint32_t j = 0; j < 4u; ++j) {
-			const uint32_t k = k0 + j * 64u + lane;
-			if (k < body) {
-				if (same) { v[j] = sa[k]; }
-				else { const cpd_u16 x = su[k]; v[j] = make_uint4(x.w[0], x.w[1], x.w[2], x.w[3]); }
-			}
-		}
-		if (k0 == 0) {
-			if (has_head) { dst[lane] = hb; }
-			if (has_tail) { dst[tail0 + (lane - 16u)] = tb; }
-		}
-		#pragma unroll
-		for (uint32_t j = 0; j < 4u; ++j) {
-			const uint32_t k = k0 + j * 64u + lane;
-			if (k < body) { d16[k] = v[j]; }
-		}
-	}
-}
-
 // The gather. A unit of an MSCOMP_OK request moves the part of its block that the request wants from its owner's source (cache slot or
 // d_packed) to its place in d_out, in pieces of 16 KiB: an item is one (unit, piece) pair, items = units of this call << ppu_shift. The items
 // are dealt to the waves of a fixed grid in runs of `per` <= 64, so that few items spread over many waves and many items keep every lane of
 // a wave busy reading table rows: a LANE works out the source, destination and length of one item -- the dependent table loads of 64 items
 // are in flight together --, then the WAVE moves the non-empty ones one after the other. A 64-byte request so costs a wave one round trip
 // to memory, not a workgroup one.
-#define RD_PIECE_SHIFT 14u
 __global__ __launch_bounds__(256) void rd_gather_kernel(uint32_t n_req, uint32_t shift, uint32_t ppu_shift, uint8_t* __restrict__ out, const u64* __restrict__ out_off, ReaderTab t)
 {
 	const uint32_t lane = threadIdx.x & 63u;
@@ -203,7 +163,8 @@ __global__ __launch_bounds__(256) void rd_gather_kernel(uint32_t n_req, uint32_t
 void launch_reader_requests(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, const u64* res_len,
                             const u64* block_first, const u64* req, const u64* out_cap, const ReaderTab& t)
 {
-	hipLaunchKernelGGL(rd_req_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_req, n_res, nbt, m, shift, res_len, block_first, req, out_cap, t);
+	if (out_cap) { hipLaunchKernelGGL(rd_req_kernel<true>, dim3(1), dim3(DV_THREADS), 0, st, n_req, n_res, nbt, m, shift, res_len, block_first, req, out_cap, t); }
+	else { hipLaunchKernelGGL(rd_req_kernel<false>, dim3(1), dim3(DV_THREADS), 0, st, n_req, n_res, nbt, m, shift, res_len, block_first, req, out_cap, t); }
 }
 
 void launch_reader_units(hipStream_t st, uint32_t n_req, uint32_t nbt, uint32_t m, uint32_t shift, u64 packed_len, const uint8_t* packed,
