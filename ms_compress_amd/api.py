@@ -310,31 +310,25 @@ class Context:
         return {names[i].decode(): (ms[i], cnt[i]) for i in range(n)}
 
 
-class Plan:
-    """mscomp_amd_plan: the unit layout of one batch (offset tables uploaded once, scratch sized once)."""
+def _ptrs(*tensors):
+    return [None if t is None else C.c_void_p(t.data_ptr()) for t in tensors]
 
-    def __init__(self, ctx, fmt, in_off, in_len, out_off, out_cap, decompress=False):
-        self.ctx, self.fmt = ctx, int(fmt)
-        arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
-        assert all(a.ndim == 1 and a.shape == arrs[0].shape for a in arrs)
-        self.in_off, self.in_len, self.out_off, self.out_cap = arrs
-        self.n_units = len(self.in_off)
-        self._h = C.c_void_p()
-        create = ctx.lib.mscomp_amd_plan_create_decompress if decompress else ctx.lib.mscomp_amd_plan_create
-        st = create(ctx._h, self.fmt, self.n_units, *[a.ctypes.data for a in arrs], C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_create")
 
-    def execute(self, d_in, d_out, d_out_len, d_status):
-        """Enqueue on the ctx stream. Arguments are torch CUDA tensors (uint8, uint8, int64/uint64[n], int32[n])."""
-        st = self.ctx.lib.mscomp_amd_plan_execute(self._h, C.c_void_p(d_in.data_ptr()), C.c_void_p(d_out.data_ptr()),
-                                                  C.c_void_p(d_out_len.data_ptr()), C.c_void_p(d_status.data_ptr()))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_execute")
+def _ok(st, name):
+    if st != MSCOMP_OK:
+        raise MSCompError(st, name)
+
+
+class _Handle:
+    """An object of the library that lives in a context: ``ctx``, the handle ``_h`` and the export that destroys it."""
+    _destroy = "mscomp_amd_plan_destroy"
+
+    def __init__(self, ctx):
+        self.ctx, self._h = ctx, C.c_void_p()
 
     def close(self):
         if self._h:
-            self.ctx.lib.mscomp_amd_plan_destroy(self._h)
+            getattr(self.ctx.lib, self._destroy)(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -344,80 +338,69 @@ class Plan:
             pass
 
 
-class SizePlan:
+class Plan(_Handle):
+    """mscomp_amd_plan: the unit layout of one batch (offset tables uploaded once, scratch sized once)."""
+
+    def __init__(self, ctx, fmt, in_off, in_len, out_off, out_cap, decompress=False):
+        _Handle.__init__(self, ctx)
+        self.fmt = int(fmt)
+        arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
+        assert all(a.ndim == 1 and a.shape == arrs[0].shape for a in arrs)
+        self.in_off, self.in_len, self.out_off, self.out_cap = arrs
+        self.n_units = len(self.in_off)
+        create = ctx.lib.mscomp_amd_plan_create_decompress if decompress else ctx.lib.mscomp_amd_plan_create
+        _ok(create(ctx._h, self.fmt, self.n_units, *[a.ctypes.data for a in arrs], C.byref(self._h)), "mscomp_amd_plan_create")
+
+    def execute(self, d_in, d_out, d_out_len, d_status):
+        """Enqueue on the ctx stream. Arguments are torch CUDA tensors (uint8, uint8, int64/uint64[n], int32[n])."""
+        _ok(self.ctx.lib.mscomp_amd_plan_execute(self._h, *_ptrs(d_in, d_out, d_out_len, d_status)), "mscomp_amd_plan_execute")
+
+
+class SizePlan(_Handle):
     """A decompressed-size plan (mscomp_amd_plan_create_size): for every unit the status and length a decompress plan with
     out_cap = limit would report, and the smallest capacity that decodes (``need``). ``limit`` None = no limit (2^64 - 1)."""
 
     def __init__(self, ctx, fmt, in_off, in_len, limit=None):
-        self.ctx, self.fmt = ctx, int(fmt)
+        _Handle.__init__(self, ctx)
+        self.fmt = int(fmt)
         self.in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         self.in_len = np.ascontiguousarray(in_len, dtype=np.uint64)
         assert self.in_off.ndim == 1 and self.in_off.shape == self.in_len.shape
         self.limit = None if limit is None else np.ascontiguousarray(limit, dtype=np.uint64)
         assert self.limit is None or self.limit.shape == self.in_off.shape
         self.n_units = len(self.in_off)
-        self._h = C.c_void_p()
-        st = ctx.lib.mscomp_amd_plan_create_size(ctx._h, self.fmt, self.n_units, self.in_off.ctypes.data, self.in_len.ctypes.data,
-                                                 None if self.limit is None else self.limit.ctypes.data, C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_create_size")
+        _ok(ctx.lib.mscomp_amd_plan_create_size(ctx._h, self.fmt, self.n_units, self.in_off.ctypes.data, self.in_len.ctypes.data,
+                                                None if self.limit is None else self.limit.ctypes.data, C.byref(self._h)),
+            "mscomp_amd_plan_create_size")
 
     def execute(self, d_in, d_out_len, d_need, d_status):
         """Enqueue on the ctx stream. Arguments are torch CUDA tensors (uint8, int64/uint64[n], int64/uint64[n], int32[n])."""
-        st = self.ctx.lib.mscomp_amd_plan_execute_size(self._h, C.c_void_p(d_in.data_ptr()), C.c_void_p(d_out_len.data_ptr()),
-                                                       C.c_void_p(d_need.data_ptr()), C.c_void_p(d_status.data_ptr()))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_execute_size")
-
-    def close(self):
-        if self._h:
-            self.ctx.lib.mscomp_amd_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _ok(self.ctx.lib.mscomp_amd_plan_execute_size(self._h, *_ptrs(d_in, d_out_len, d_need, d_status)), "mscomp_amd_plan_execute_size")
 
 
-class DevPlan:
+class DevPlan(_Handle):
     """A decompress plan with device tables (mscomp_amd_plan_create_decompress_dev): made once for n_units units whose in_len sum to at most
     in_total_max and whose out_cap sum to at most out_total_max, then executed with unit tables that live on the device.
     ``large_units`` (MSCOMP_AMD_DEV_LARGE_UNITS): the plan also builds the tables of a host plan's paths for large units on the device
     (segment walk, all-CU byte stage, candidate token scratch), at the price of their scratch and launches in every execution."""
 
     def __init__(self, ctx, fmt, n_units, in_total_max, out_total_max, large_units=False):
-        self.ctx, self.fmt, self.n_units = ctx, int(fmt), int(n_units)
+        _Handle.__init__(self, ctx)
+        self.fmt, self.n_units = int(fmt), int(n_units)
         self.in_total_max, self.out_total_max = int(in_total_max), int(out_total_max)
         self.large_units = bool(large_units)
-        self._h = C.c_void_p()
         if self.large_units:
             st = ctx.lib.mscomp_amd_plan_create_decompress_dev_ex(ctx._h, self.fmt, self.n_units, self.in_total_max, self.out_total_max,
                                                                   MSCOMP_AMD_DEV_LARGE_UNITS, C.byref(self._h))
         else:
             st = ctx.lib.mscomp_amd_plan_create_decompress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.out_total_max, C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_create_decompress_dev")
+        _ok(st, "mscomp_amd_plan_create_decompress_dev")
 
     def execute(self, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status):
         """Enqueue on the ctx stream (nothing is synchronized or read back). Arguments are torch CUDA tensors: uint8 input and output, int64 /
         uint64 tables of n_units entries (offsets, lengths, capacities; results d_out_len), int32 d_status."""
-        ptrs = [C.c_void_p(t.data_ptr()) for t in (d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status)]
-        st = self.ctx.lib.mscomp_amd_plan_execute_dev(self._h, *ptrs)
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_execute_dev")
-
-    def close(self):
-        if self._h:
-            self.ctx.lib.mscomp_amd_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ptrs = _ptrs(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status)
+        _ok(self.ctx.lib.mscomp_amd_plan_execute_dev(self._h, *ptrs), "mscomp_amd_plan_execute_dev")
 
 
 class CompressDevPlan(DevPlan):
@@ -425,12 +408,11 @@ class CompressDevPlan(DevPlan):
     whose in_len sum to at most in_total_max, then executed (``execute``, as DevPlan's) with unit tables that live on the device."""
 
     def __init__(self, ctx, fmt, n_units, in_total_max, in_unit_max):
-        self.ctx, self.fmt, self.n_units = ctx, int(fmt), int(n_units)
+        _Handle.__init__(self, ctx)
+        self.fmt, self.n_units = int(fmt), int(n_units)
         self.in_total_max, self.in_unit_max = int(in_total_max), int(in_unit_max)
-        self._h = C.c_void_p()
-        st = ctx.lib.mscomp_amd_plan_create_compress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.in_unit_max, C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_create_compress_dev")
+        _ok(ctx.lib.mscomp_amd_plan_create_compress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.in_unit_max, C.byref(self._h)),
+            "mscomp_amd_plan_create_compress_dev")
 
 
 class SizeDevPlan(DevPlan):
@@ -439,24 +421,21 @@ class SizeDevPlan(DevPlan):
     streams of 512 KiB or more are sized by segments)."""
 
     def __init__(self, ctx, fmt, n_units, in_total_max, large_units=False):
-        self.ctx, self.fmt, self.n_units = ctx, int(fmt), int(n_units)
+        _Handle.__init__(self, ctx)
+        self.fmt, self.n_units = int(fmt), int(n_units)
         self.in_total_max = int(in_total_max)
         self.large_units = bool(large_units)
-        self._h = C.c_void_p()
         if self.large_units:
             st = ctx.lib.mscomp_amd_plan_create_size_dev_ex(ctx._h, self.fmt, self.n_units, self.in_total_max, MSCOMP_AMD_DEV_LARGE_UNITS, C.byref(self._h))
         else:
             st = ctx.lib.mscomp_amd_plan_create_size_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_create_size_dev")
+        _ok(st, "mscomp_amd_plan_create_size_dev")
 
     def execute(self, d_in, d_in_off, d_in_len, d_out_len, d_need, d_status, d_limit=None):
         """Enqueue on the ctx stream (nothing is synchronized or read back). Arguments are torch CUDA tensors: uint8 input, int64 / uint64
         tables of n_units entries (offsets, lengths, d_limit or None = no limit; results d_out_len, d_need), int32 d_status."""
-        ptrs = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status)]
-        st = self.ctx.lib.mscomp_amd_plan_execute_size_dev(self._h, *ptrs)
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_execute_size_dev")
+        ptrs = _ptrs(d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status)
+        _ok(self.ctx.lib.mscomp_amd_plan_execute_size_dev(self._h, *ptrs), "mscomp_amd_plan_execute_size_dev")
 
 
 class CrcDevPlan(DevPlan):
@@ -464,22 +443,17 @@ class CrcDevPlan(DevPlan):
     in_total_max, then executed with unit tables that live on the device. The value is zlib's crc32."""
 
     def __init__(self, ctx, n_units, in_total_max):
-        self.ctx, self.n_units, self.in_total_max = ctx, int(n_units), int(in_total_max)
-        self._h = C.c_void_p()
-        st = ctx.lib.mscomp_amd_plan_create_crc_dev(ctx._h, self.n_units, self.in_total_max, C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_create_crc_dev")
+        _Handle.__init__(self, ctx)
+        self.n_units, self.in_total_max = int(n_units), int(in_total_max)
+        _ok(ctx.lib.mscomp_amd_plan_create_crc_dev(ctx._h, self.n_units, self.in_total_max, C.byref(self._h)), "mscomp_amd_plan_create_crc_dev")
 
     def execute(self, d_in, d_in_off, d_in_len, d_crc, d_status):
         """Enqueue on the ctx stream (nothing is synchronized or read back). Arguments are torch CUDA tensors: uint8 input, int64 / uint64
         offsets and lengths of n_units entries, int32 d_crc (the 32 bits of each CRC) and int32 d_status."""
-        ptrs = [C.c_void_p(t.data_ptr()) for t in (d_in, d_in_off, d_in_len, d_crc, d_status)]
-        st = self.ctx.lib.mscomp_amd_plan_execute_crc_dev(self._h, *ptrs)
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_plan_execute_crc_dev")
+        _ok(self.ctx.lib.mscomp_amd_plan_execute_crc_dev(self._h, *_ptrs(d_in, d_in_off, d_in_len, d_crc, d_status)), "mscomp_amd_plan_execute_crc_dev")
 
 
-class BlockContainer:
+class BlockContainer(_Handle):
     """A block container (mscomp_amd_blocks_create): resources cut into blocks of ``block_size`` bytes (a power of two, 4096 .. 524288), every
     block compressed on its own or stored raw when it does not shrink, the stored blocks packed back to back behind an offset table. Made
     once for ``n_res`` resources whose lengths sum to at most ``in_total_max``; ``n_blocks_max`` = n_res + in_total_max // block_size bounds
@@ -487,14 +461,14 @@ class BlockContainer:
     1 byte per byte of in_total_max + 16 per resource. Both calls enqueue kernels on the ctx stream and nothing else (nothing is
     synchronized or read back; legal inside a capture of that stream). Arguments are torch CUDA tensors: uint8 data, int64 / uint64 tables,
     int32 statuses."""
+    _destroy = "mscomp_amd_blocks_destroy"
 
     def __init__(self, ctx, fmt, block_size, n_res, in_total_max):
-        self.ctx, self.fmt, self.block_size = ctx, int(fmt), int(block_size)
+        _Handle.__init__(self, ctx)
+        self.fmt, self.block_size = int(fmt), int(block_size)
         self.n_res, self.in_total_max = int(n_res), int(in_total_max)
-        self._h = C.c_void_p()
-        st = ctx.lib.mscomp_amd_blocks_create(ctx._h, self.fmt, self.block_size, self.n_res, self.in_total_max, 0, C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_blocks_create")
+        _ok(ctx.lib.mscomp_amd_blocks_create(ctx._h, self.fmt, self.block_size, self.n_res, self.in_total_max, 0, C.byref(self._h)),
+            "mscomp_amd_blocks_create")
         self.n_blocks_max = int(ctx.lib.mscomp_amd_blocks_bound(self._h))
 
     def compress(self, d_in, d_res_off, d_res_len, d_packed, d_block_first, d_block_off, d_status, packed_cap=None):
@@ -505,10 +479,8 @@ class BlockContainer:
         cap = d_packed.numel() if packed_cap is None else int(packed_cap)
         if cap > d_packed.numel():
             raise ValueError("packed_cap exceeds d_packed")
-        p = [C.c_void_p(t.data_ptr()) for t in (d_in, d_res_off, d_res_len, d_packed, d_block_first, d_block_off, d_status)]
-        st = self.ctx.lib.mscomp_amd_blocks_compress(self._h, p[0], p[1], p[2], p[3], cap, p[4], p[5], p[6])
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_blocks_compress")
+        p = _ptrs(d_in, d_res_off, d_res_len, d_packed, d_block_first, d_block_off, d_status)
+        _ok(self.ctx.lib.mscomp_amd_blocks_compress(self._h, *p[:4], cap, *p[4:]), "mscomp_amd_blocks_compress")
 
     def decompress(self, d_packed, d_block_first, d_block_off, d_res_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_range=None,
                    packed_len=None):
@@ -517,39 +489,20 @@ class BlockContainer:
         MSCOMP_ARG_ERROR (beyond the creation bounds), MSCOMP_DATA_ERROR (a damaged table or payload) or MSCOMP_BUF_ERROR (capacity), with
         d_out_len[r] = 0. ``packed_len``: the valid bytes of d_packed (default: all of it)."""
         plen = d_packed.numel() if packed_len is None else int(packed_len)
-        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_packed, d_block_first, d_block_off, d_res_len, d_range, d_out, d_out_off,
-                                                                         d_out_cap, d_out_len, d_status)]
-        st = self.ctx.lib.mscomp_amd_blocks_decompress(self._h, p[0], plen, *p[1:])
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_blocks_decompress")
+        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_range, d_out, d_out_off, d_out_cap, d_out_len, d_status)
+        _ok(self.ctx.lib.mscomp_amd_blocks_decompress(self._h, p[0], plen, *p[1:]), "mscomp_amd_blocks_decompress")
 
     def crc(self, d_data, d_res_off, d_res_len, d_block_crc, d_status, d_res_crc=None):
         """CRC-32 of the uncompressed blocks of the resources (as compress takes them): d_block_crc (int32, n_blocks_max; entry j belongs to the
         block compress puts at d_block_off[j], the entries behind the last block are 0), d_res_crc (optional, int32, n_res: the CRC-32 of
         every whole resource, from the same pass) and d_status (n_res: MSCOMP_OK, or MSCOMP_ARG_ERROR as compress gives it)."""
-        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_data, d_res_off, d_res_len, d_block_crc, d_res_crc, d_status)]
-        st = self.ctx.lib.mscomp_amd_blocks_crc(self._h, *p)
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_blocks_crc")
+        _ok(self.ctx.lib.mscomp_amd_blocks_crc(self._h, *_ptrs(d_data, d_res_off, d_res_len, d_block_crc, d_res_crc, d_status)), "mscomp_amd_blocks_crc")
 
     def check(self, d_out, d_out_off, d_res_len, d_block_first, d_block_crc, d_out_len, d_status, d_range=None):
         """After decompress, with its tables and results: every block of the (clipped) range of every resource that is MSCOMP_OK in d_status
         is read back from d_out and held to d_block_crc; a mismatch turns the resource into MSCOMP_DATA_ERROR with d_out_len = 0."""
-        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status)]
-        st = self.ctx.lib.mscomp_amd_blocks_check(self._h, *p)
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_blocks_check")
-
-    def close(self):
-        if self._h:
-            self.ctx.lib.mscomp_amd_blocks_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        p = _ptrs(d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status)
+        _ok(self.ctx.lib.mscomp_amd_blocks_check(self._h, *p), "mscomp_amd_blocks_check")
 
 
 def blocks_compress(fmt, buffers, block_size, ctx=None):
@@ -563,11 +516,9 @@ def blocks_compress(fmt, buffers, block_size, ctx=None):
     n = len(buffers)
     dev = torch.device("cuda", ctx.device)
     with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
-        d_in, in_off, lens = _upload_units(buffers, dev)
+        d_in, d_off, d_len, lens = _upload_unit_tables(buffers, dev)
         total = int(sum(lens))
         bk = BlockContainer(ctx, fmt, block_size, n, total)
-        d_off = torch.from_numpy(np.ascontiguousarray(in_off, dtype=np.uint64).view(np.int64).copy()).to(dev) if n else torch.zeros(1, dtype=torch.int64, device=dev)
-        d_len = torch.tensor(lens or [0], dtype=torch.int64, device=dev)
         d_packed = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
         d_first = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         d_boff = torch.zeros(bk.n_blocks_max + 1, dtype=torch.int64, device=dev)
@@ -593,9 +544,7 @@ def crc32_units(units, ctx=None):
     n = len(units)
     dev = torch.device("cuda", ctx.device)
     with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
-        d_in, in_off, lens = _upload_units(units, dev)
-        d_off = torch.from_numpy(np.ascontiguousarray(in_off, dtype=np.uint64).view(np.int64).copy()).to(dev) if n else torch.zeros(1, dtype=torch.int64, device=dev)
-        d_len = torch.tensor(lens or [0], dtype=torch.int64, device=dev)
+        d_in, d_off, d_len, lens = _upload_unit_tables(units, dev)
         d_crc = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         plan = CrcDevPlan(ctx, n, int(sum(lens)))
@@ -619,10 +568,8 @@ def blocks_crc(fmt, buffers, block_size, ctx=None):
     n = len(buffers)
     dev = torch.device("cuda", ctx.device)
     with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
-        d_in, in_off, lens = _upload_units(buffers, dev)
+        d_in, d_off, d_len, lens = _upload_unit_tables(buffers, dev)
         bk = BlockContainer(ctx, fmt, block_size, n, int(sum(lens)))
-        d_off = torch.from_numpy(np.ascontiguousarray(in_off, dtype=np.uint64).view(np.int64).copy()).to(dev) if n else torch.zeros(1, dtype=torch.int64, device=dev)
-        d_len = torch.tensor(lens or [0], dtype=torch.int64, device=dev)
         d_bcrc = torch.zeros(max(1, bk.n_blocks_max), dtype=torch.int32, device=dev)
         d_rcrc = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
@@ -649,30 +596,18 @@ def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, 
     total = int(sum(lens))
     out_off, out_total = pack_offsets(lens)
     dev = torch.device("cuda", ctx.device)
-
-    def up(a, least):
-        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
-        a = np.concatenate([a, np.full(max(0, least - len(a)), a[-1] if len(a) else 0, dtype=np.uint64)])
-        return torch.from_numpy(a.view(np.int64).copy()).to(dev)
     with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
         bk = BlockContainer(ctx, fmt, block_size, n, total)
-        packed = np.ascontiguousarray(np.frombuffer(bytes(packed), dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed, dtype=np.uint8)
-        d_packed = torch.zeros(len(packed) + 16, dtype=torch.uint8, device=dev)
-        if len(packed):
-            d_packed[: len(packed)] = torch.from_numpy(packed.copy()).to(dev)
-        d_first, d_boff = up(block_first, n + 1), up(block_off, bk.n_blocks_max + 1)
-        d_len, d_ooff, d_ocap = up(lens, 1), up(out_off, 1), up(lens, 1)
-        d_range = None if ranges is None else up(np.asarray(ranges, dtype=np.uint64).reshape(-1), 2)
+        packed, d_packed = _dev_packed(packed, dev)
+        d_first, d_boff = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, bk.n_blocks_max + 1, dev)
+        d_len, d_ooff, d_ocap = _dev_u64(lens, 1, dev), _dev_u64(out_off, 1, dev), _dev_u64(lens, 1, dev)
+        d_range = None if ranges is None else _dev_u64(np.asarray(ranges, dtype=np.uint64), 2, dev)
         d_out = torch.zeros(out_total + 16, dtype=torch.uint8, device=dev)
         d_olen = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
         d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         bk.decompress(d_packed, d_first, d_boff, d_len, d_out, d_ooff, d_ocap, d_olen, d_st, d_range=d_range, packed_len=len(packed))
         if block_crc is not None:
-            h_crc = np.zeros(max(1, bk.n_blocks_max), dtype=np.uint32)
-            k = min(len(block_crc), len(h_crc))
-            h_crc[:k] = np.asarray(block_crc, dtype=np.uint32)[:k]
-            d_crc = torch.from_numpy(h_crc.view(np.int32).copy()).to(dev)
-            bk.check(d_out, d_ooff, d_len, d_first, d_crc, d_olen, d_st, d_range=d_range)
+            bk.check(d_out, d_ooff, d_len, d_first, _dev_block_crc(block_crc, bk.n_blocks_max, dev), d_olen, d_st, d_range=d_range)
         ctx.stream.synchronize()
         h_out, h_len, h_st = d_out.cpu().numpy(), d_olen.cpu().numpy(), d_st.cpu().numpy()
         bk.close()
@@ -682,22 +617,31 @@ def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, 
     return res, [int(x) for x in h_st[:n]]
 
 
-class BlockReader:
+class _BlockAccess(_Handle):
+    """What BlockReader and BlockWriter share: the arguments they are made with, and counts()."""
+
+    def __init__(self, ctx, fmt, block_size, n_res, n_blocks_table, n_req, blocks_max):
+        _Handle.__init__(self, ctx)
+        self.fmt, self.block_size = int(fmt), int(block_size)
+        self.n_res, self.n_blocks_table, self.n_req, self.blocks_max = int(n_res), int(n_blocks_table), int(n_req), int(blocks_max)
+        _ok(getattr(ctx.lib, self._create)(ctx._h, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_req, self.blocks_max, 0,
+                                           C.byref(self._h)), self._create)
+
+    def _read_counts(self):
+        out = (C.c_uint32 * 3)()
+        if getattr(self.ctx.lib, self._counts)(self._h, out) != 0:
+            raise MSCompError(MSCOMP_ERRNO, self._counts)
+        return (int(out[0]), int(out[1]), int(out[2]))
+
+
+class BlockReader(_BlockAccess):
     """A block reader (mscomp_amd_reader_create): batched byte-range reads from a block container, by its tables alone. Made once for
     ``n_req`` requests per call that together cover at most ``blocks_max`` blocks (counted per request, before any sharing); the tables are
     those of a container of ``n_res`` resources whose d_block_off has ``n_blocks_table`` + 1 entries. All scratch is reserved here: a cache
     of blocks_max blocks, one inner dev plan, 88 bytes of tables per unit of blocks_max, 44 per request and 4 per block-table entry. read()
     enqueues kernels on the ctx stream and nothing else (legal inside a capture of that stream). Arguments are torch CUDA tensors: uint8
     data, int64 / uint64 tables, int32 statuses and checksums."""
-
-    def __init__(self, ctx, fmt, block_size, n_res, n_blocks_table, n_req, blocks_max):
-        self.ctx, self.fmt, self.block_size = ctx, int(fmt), int(block_size)
-        self.n_res, self.n_blocks_table, self.n_req, self.blocks_max = int(n_res), int(n_blocks_table), int(n_req), int(blocks_max)
-        self._h = C.c_void_p()
-        st = ctx.lib.mscomp_amd_reader_create(ctx._h, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_req, self.blocks_max, 0,
-                                              C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_reader_create")
+    _create, _destroy, _counts = "mscomp_amd_reader_create", "mscomp_amd_reader_destroy", "mscomp_amd_reader_counts"
 
     def read(self, d_packed, d_block_first, d_block_off, d_res_len, d_req, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_block_crc=None,
              packed_len=None):
@@ -707,29 +651,12 @@ class BlockReader:
         ``d_block_crc``, as BlockContainer.crc wrote it, a block whose CRC-32 differs) with d_out_len[q] = 0 and nothing written.
         ``packed_len``: the valid bytes of d_packed (default: all of it)."""
         plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
-        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_out,
-                                                                         d_out_off, d_out_cap, d_out_len, d_status)]
-        st = self.ctx.lib.mscomp_amd_reader_read(self._h, p[0], plen, *p[1:])
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_reader_read")
+        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_out, d_out_off, d_out_cap, d_out_len, d_status)
+        _ok(self.ctx.lib.mscomp_amd_reader_read(self._h, p[0], plen, *p[1:]), "mscomp_amd_reader_read")
 
     def counts(self):
         """(units, distinct blocks, blocks decoded rather than raw) of the last read(); synchronizes the stream."""
-        out = (C.c_uint32 * 3)()
-        if self.ctx.lib.mscomp_amd_reader_counts(self._h, out) != 0:
-            raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_reader_counts")
-        return (int(out[0]), int(out[1]), int(out[2]))
-
-    def close(self):
-        if self._h:
-            self.ctx.lib.mscomp_amd_reader_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._read_counts()
 
 
 def blocks_read(fmt, packed, block_first, block_off, lengths, block_size, requests, ctx=None, block_crc=None):
@@ -744,36 +671,17 @@ def blocks_read(fmt, packed, block_first, block_off, lengths, block_size, reques
     B = int(block_size)
     M64 = (1 << 64) - 1
     reqs = [(int(r) & M64, int(o) & M64, int(ln) & M64) for r, o, ln in requests]
-    wants, blocks = [], 0
-    for r, o, ln in reqs:                                      # the capacities, and the budget: the covering blocks of every request, unshared
-        L = lens[r] if r < n else 0
-        o = min(o, L)
-        w = min(ln, L - o)
-        wants.append(w)
-        blocks += ((o + w - 1) // B - o // B + 1) if w else 0
+    wants, blocks = _covering_blocks(reqs, lens, B)            # (the capacities, and the budget)
     out_off, out_total = pack_offsets(wants)
     nbt = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
     dev = torch.device("cuda", ctx.device)
-
-    def up(a, least):
-        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
-        a = np.concatenate([a, np.full(max(0, least - len(a)), a[-1] if len(a) else 0, dtype=np.uint64)])
-        return torch.from_numpy(a.view(np.int64).copy()).to(dev)
     with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
         rd = BlockReader(ctx, fmt, B, n, nbt, nq, blocks)
-        packed = np.ascontiguousarray(np.frombuffer(bytes(packed), dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed, dtype=np.uint8)
-        d_packed = torch.zeros(len(packed) + 16, dtype=torch.uint8, device=dev)
-        if len(packed):
-            d_packed[: len(packed)] = torch.from_numpy(packed.copy()).to(dev)
-        d_first, d_boff, d_len = up(block_first, n + 1), up(block_off, nbt + 1), up(lens, 1)
-        d_req = up(np.array(reqs, dtype=np.uint64).reshape(-1), 3)
-        d_ooff, d_ocap = up(out_off, 1), up(wants, 1)
-        d_crc = None
-        if block_crc is not None:
-            h_crc = np.zeros(max(1, nbt), dtype=np.uint32)
-            k = min(len(block_crc), len(h_crc))
-            h_crc[:k] = np.asarray(block_crc, dtype=np.uint32)[:k]
-            d_crc = torch.from_numpy(h_crc.view(np.int32).copy()).to(dev)
+        packed, d_packed = _dev_packed(packed, dev)
+        d_first, d_boff, d_len = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, nbt + 1, dev), _dev_u64(lens, 1, dev)
+        d_req = _dev_u64(np.array(reqs, dtype=np.uint64), 3, dev)
+        d_ooff, d_ocap = _dev_u64(out_off, 1, dev), _dev_u64(wants, 1, dev)
+        d_crc = None if block_crc is None else _dev_block_crc(block_crc, nbt, dev)
         d_out = torch.zeros(out_total + 16, dtype=torch.uint8, device=dev)
         d_olen = torch.zeros(max(1, nq), dtype=torch.int64, device=dev)
         d_st = torch.zeros(max(1, nq), dtype=torch.int32, device=dev)
@@ -787,22 +695,14 @@ def blocks_read(fmt, packed, block_first, block_off, lengths, block_size, reques
     return res, [int(x) for x in h_st[:nq]]
 
 
-class BlockWriter:
+class BlockWriter(_BlockAccess):
     """A block writer (mscomp_amd_writer_create): batched byte-range writes into a block container, out of place. Made once for ``n_req``
     requests per call that together cover at most ``blocks_max`` blocks (counted per request, before any sharing), against the tables of
     a container of ``n_res`` resources whose d_block_off has ``n_blocks_table`` + 1 entries. All scratch is reserved here: a cache and a
     staging area of blocks_max blocks each, two inner dev plans, 96 bytes of tables per unit of blocks_max, 44 per request and 8 per
     block-table entry. write() enqueues kernels on the ctx stream and nothing else (legal inside a capture of that stream). Arguments
     are torch CUDA tensors: uint8 data, int64 / uint64 tables, int32 statuses and checksums."""
-
-    def __init__(self, ctx, fmt, block_size, n_res, n_blocks_table, n_req, blocks_max):
-        self.ctx, self.fmt, self.block_size = ctx, int(fmt), int(block_size)
-        self.n_res, self.n_blocks_table, self.n_req, self.blocks_max = int(n_res), int(n_blocks_table), int(n_req), int(blocks_max)
-        self._h = C.c_void_p()
-        st = ctx.lib.mscomp_amd_writer_create(ctx._h, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_req, self.blocks_max, 0,
-                                              C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_writer_create")
+    _create, _destroy, _counts = "mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_counts"
 
     def write(self, d_packed, d_block_first, d_block_off, d_res_len, d_req, d_src, d_src_off, d_new_packed, d_new_block_off, d_written, d_status,
               d_res_status, d_block_crc=None, d_new_block_crc=None, packed_len=None, new_cap=None):
@@ -817,30 +717,13 @@ class BlockWriter:
         cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
         if d_new_packed is not None and cap > d_new_packed.numel():
             raise ValueError("new_cap exceeds d_new_packed")
-        p = [None if t is None else C.c_void_p(t.data_ptr()) for t in (d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_src,
-                                                                         d_src_off, d_new_packed, d_new_block_off, d_new_block_crc, d_written,
-                                                                         d_status, d_res_status)]
-        st = self.ctx.lib.mscomp_amd_writer_write(self._h, p[0], plen, *p[1:9], cap, *p[9:])
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_writer_write")
+        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_src, d_src_off, d_new_packed, d_new_block_off, d_new_block_crc,
+                  d_written, d_status, d_res_status)
+        _ok(self.ctx.lib.mscomp_amd_writer_write(self._h, p[0], plen, *p[1:9], cap, *p[9:]), "mscomp_amd_writer_write")
 
     def counts(self):
         """(units, distinct blocks touched, blocks encoded again) of the last write(); synchronizes the stream."""
-        out = (C.c_uint32 * 3)()
-        if self.ctx.lib.mscomp_amd_writer_counts(self._h, out) != 0:
-            raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_writer_counts")
-        return (int(out[0]), int(out[1]), int(out[2]))
-
-    def close(self):
-        if self._h:
-            self.ctx.lib.mscomp_amd_writer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._read_counts()
 
 
 def blocks_write(fmt, packed, block_first, block_off, lengths, block_size, writes, ctx=None, block_crc=None):
@@ -857,40 +740,23 @@ def blocks_write(fmt, packed, block_first, block_off, lengths, block_size, write
     B = int(block_size)
     M64 = (1 << 64) - 1
     reqs = [(int(r) & M64, int(o) & M64, len(b)) for r, o, b in writes]
-    blocks = 0
-    for r, o, ln in reqs:                                      # the budget: the covering blocks of every request, unshared
-        L = lens[r] if r < n else 0
-        o = min(o, L)
-        w = min(ln, L - o)
-        blocks += ((o + w - 1) // B - o // B + 1) if w else 0
+    _, blocks = _covering_blocks(reqs, lens, B)                # (the budget)
     src_off, src_total = pack_offsets([len(b) for _, _, b in writes])
     nbt = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
     total = int(sum(lens))
     dev = torch.device("cuda", ctx.device)
-
-    def up(a, least):
-        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
-        a = np.concatenate([a, np.full(max(0, least - len(a)), a[-1] if len(a) else 0, dtype=np.uint64)])
-        return torch.from_numpy(a.view(np.int64).copy()).to(dev)
     with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
         wr = BlockWriter(ctx, fmt, B, n, nbt, nq, blocks)
-        packed = np.ascontiguousarray(np.frombuffer(bytes(packed), dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed, dtype=np.uint8)
-        d_packed = torch.zeros(len(packed) + 16, dtype=torch.uint8, device=dev)
-        if len(packed):
-            d_packed[: len(packed)] = torch.from_numpy(packed.copy()).to(dev)
+        packed, d_packed = _dev_packed(packed, dev)
         h_src = np.zeros(src_total + 16, dtype=np.uint8)
         for (_, _, b), o in zip(writes, src_off):
             h_src[int(o): int(o) + len(b)] = np.frombuffer(bytes(b), dtype=np.uint8)
         d_src = torch.from_numpy(h_src).to(dev)
-        d_first, d_boff, d_len = up(block_first, n + 1), up(block_off, nbt + 1), up(lens, 1)
-        d_req, d_soff = up(np.array(reqs, dtype=np.uint64).reshape(-1), 3), up(src_off, 1)
+        d_first, d_boff, d_len = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, nbt + 1, dev), _dev_u64(lens, 1, dev)
+        d_req, d_soff = _dev_u64(np.array(reqs, dtype=np.uint64), 3, dev), _dev_u64(src_off, 1, dev)
         d_crc = d_ncrc = None
         if block_crc is not None:
-            h_crc = np.zeros(max(1, nbt), dtype=np.uint32)
-            k = min(len(block_crc), len(h_crc))
-            h_crc[:k] = np.asarray(block_crc, dtype=np.uint32)[:k]
-            d_crc = torch.from_numpy(h_crc.view(np.int32).copy()).to(dev)
-            d_ncrc = torch.zeros(max(1, nbt), dtype=torch.int32, device=dev)
+            d_crc, d_ncrc = _dev_block_crc(block_crc, nbt, dev), torch.zeros(max(1, nbt), dtype=torch.int32, device=dev)
         d_new = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
         d_noff = torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
         d_wr = torch.zeros(max(1, nq), dtype=torch.int64, device=dev)
@@ -984,6 +850,54 @@ def _upload_units(units, dev):
         if len(u):
             blob[int(o): int(o) + len(u)] = np.frombuffer(bytes(u), dtype=np.uint8)
     return torch.from_numpy(blob).to(dev), in_off, lens
+
+
+def _upload_unit_tables(units, dev):
+    """_upload_units, with the offsets and lengths on the device too (int64, one entry at least): (d_in, d_off, d_len, lens)."""
+    import torch
+    d_in, in_off, lens = _upload_units(units, dev)
+    d_off = torch.from_numpy(np.ascontiguousarray(in_off, dtype=np.uint64).view(np.int64).copy()).to(dev) if lens else torch.zeros(1, dtype=torch.int64, device=dev)
+    return d_in, d_off, torch.tensor(lens or [0], dtype=torch.int64, device=dev), lens
+
+
+def _dev_u64(a, least, dev):
+    """``a`` flattened, as an int64 device tensor of ``least`` entries or more: the last one repeated (0 when there is none)."""
+    import torch
+    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+    a = np.concatenate([a, np.full(max(0, least - len(a)), a[-1] if len(a) else 0, dtype=np.uint64)])
+    return torch.from_numpy(a.view(np.int64).copy()).to(dev)
+
+
+def _dev_packed(packed, dev):
+    """The stored blocks of a container (bytes or a numpy array) as (numpy uint8 array, device tensor with 16 bytes of room behind it)."""
+    import torch
+    packed = np.ascontiguousarray(np.frombuffer(bytes(packed), dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed, dtype=np.uint8)
+    d_packed = torch.zeros(len(packed) + 16, dtype=torch.uint8, device=dev)
+    if len(packed):
+        d_packed[: len(packed)] = torch.from_numpy(packed.copy()).to(dev)
+    return packed, d_packed
+
+
+def _dev_block_crc(block_crc, n, dev):
+    """``block_crc`` cut or zero-padded to ``n`` entries (one at least), as an int32 device tensor."""
+    import torch
+    h_crc = np.zeros(max(1, n), dtype=np.uint32)
+    k = min(len(block_crc), len(h_crc))
+    h_crc[:k] = np.asarray(block_crc, dtype=np.uint32)[:k]
+    return torch.from_numpy(h_crc.view(np.int32).copy()).to(dev)
+
+
+def _covering_blocks(reqs, lens, B):
+    """Per (resource, offset, length) request the bytes it wants once clipped to its resource, and the blocks of ``B`` bytes that cover all
+    of them, counted per request (unshared)."""
+    wants, blocks = [], 0
+    for r, o, ln in reqs:
+        L = lens[r] if r < len(lens) else 0
+        o = min(o, L)
+        w = min(ln, L - o)
+        wants.append(w)
+        blocks += ((o + w - 1) // B - o // B + 1) if w else 0
+    return wants, blocks
 
 
 def decompressed_sizes(fmt, units, limits=None, ctx=None):

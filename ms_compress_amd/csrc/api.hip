@@ -4,159 +4,34 @@
 // Reference boundary mirrored here: ms_compress / ms_max_compressed_size (/root/reference/src/mscomp.cpp:96-117),
 // lznt1_compress (/root/reference/src/lznt1_compress.cpp:233), xpress_compress (/root/reference/src/xpress_compress.cpp:240),
 // xpress_huff_compress (/root/reference/src/xpress_huff_compress.cpp:247).
-#include "../../include/mscomp_amd.h"
-#include "kernels.h"
-#include <atomic>
-#include <cstdlib>
-#include <memory>
+#include "host.h"
 #include <mutex>
 #include <thread>
 #include <condition_variable>
-#include <hip/hip_runtime.h>
-#include <new>
 #include <string>
-#include <vector>
-#include <cstring>
 
 using namespace msc;
-
-namespace {
 
 // A captured hipGraph of a plan holds raw scratch pointers and a kernel choice. Two counters say when it is stale:
 // the context's own epoch (bumped whenever one of ITS device buffers moves; a context is used by one host thread at a
 // time, so a plain counter) and a process-wide one for the test hooks that switch kernels (atomic: any thread may call them
-// while other threads execute plans).
-static std::atomic<uint64_t> g_mode_epoch{1};
+// while other threads execute plans; host.h declares it for the other host files).
+std::atomic<uint64_t> msc::g_mode_epoch{1};
+// The mscomp_amd_debug_set_* hooks pick between bit-identical kernels for the tests. They are process-wide, so the product ignores them unless the
+// process asked for them BEFORE the library was loaded (MSCOMP_AMD_TEST_HOOKS=1: tests/conftest.py and the tools do): a deployment cannot have its
+// kernels switched under it by a stray call (VERDICT r05 weak 8).
+bool msc::test_hooks_on() { static const bool on = [] { const char* e = getenv("MSCOMP_AMD_TEST_HOOKS"); return e && *e == '1'; }(); return on; }
+
+namespace {
+
 static std::atomic<int> g_finder_mode{1};              // 1 = default (Xpress units up to 64 KiB: the lazy finder, xpress_lazy.hip), 2 = Find for every position everywhere
 static int lznt1_sa_env() { const char* e = getenv("MSCOMP_AMD_LZNT1_SA_DICT"); return (e && *e && *e != '0') ? 1 : 0; }
 static std::atomic<int> g_lznt1_sa{lznt1_sa_env()};    // 1 = LZNT1 compresses with the suffix-array dictionary flavour (lznt1_sa.hip; the reference's MSCOMP_WITH_LZNT1_SA_DICT build)
 static std::atomic<int> g_one_zero_copy{[] { const char* e = getenv("MSCOMP_AMD_ONE_ZEROCOPY"); return (e && *e == '0') ? 0 : 1; }()};   // large host-pointer LZNT1 calls: 1 = caller buffers mapped, one launch (default), 0 = slices on three streams
 static std::atomic<int> g_xpd_mode{0};                 // Xpress decompression: 0 = tokens a flag word at a time + copy kernels (default; large streams by segments), 1 = xpd_kernel (a token at a time, bytes in the same wave), 2 = as 0 without the segments
-struct DevBuf {
-	void* p = nullptr; size_t cap = 0;
-	uint64_t* epoch = nullptr;                         // the owning context's epoch (null for plan-owned tables)
-	bool reserve(size_t n)
-	{
-		if (n <= cap) { return true; }
-		if (epoch) { ++*epoch; }
-		if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-		const size_t want = n + n / 8 + 256;
-		if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return false; }
-		cap = want; return true;
-	}
-	void release() { if (p) { (void)hipFree(p); if (epoch) { ++*epoch; } } p = nullptr; cap = 0; }
-};
-
-struct ProfRec { const char* name; hipEvent_t a, b; };
-bool lznt1_sa_for(const mscomp_amd_ctx* c);              // the flavour a plan created in `c` right now would get
 const uint32_t XH_FB_BLOCKS = 256;                     // persistent blocks of the fallback kernel (one per CU: its package pool fills the LDS)
-
-} // namespace
-
-struct mscomp_amd_ctx {
-	int device = 0;
-	uint32_t cpd_blocks = 0;                           // the fixed grid of mscomp_amd_compact_dev on this device (asked once, here: never inside a capture)
-	uint32_t crc_blocks = 0;                           // ... and that of the CRC kernel (crc32.hip)
-	hipStream_t stream = nullptr;
-	DevBuf slots, slot_size, prefix, tile_sums;        // chunk scratch (grow-only, shared by all plans of the ctx)
-	DevBuf lzrec;                                      // LZNT1 parse records per chunk (LZNT1_REC bytes: match tokens per window)
-	DevBuf links, lasthead, mlen3, moff;               // Xpress-family match finder scratch (per 64 KiB link chunk)
-	DevBuf wtok, wmat, wfar;                           // Xpress parse records per 64-position window (token mask, match mask, far length)
-	DevBuf wrec, sbrec;                                // ... state / counts / prefixes per window (6 x u32), per super-block (tot 4 x u32, pre 3 x u64, seams)
-	DevBuf tokbits, counts, extra, lens, codes, fb_list, fbflag;   // Xpress+Huffman per-chunk scratch
-	DevBuf dz_cin, dz_csize, dz_unit;                  // LZNT1 decompression: header offset / decoded size per chunk slot, per-unit records
-	DevBuf dz_scr;                                     // Xpress+Huffman decompression: token scratch of the candidates of multi-chunk buffers
-	DevBuf dz_tok, dz_ntok, dz_xhc;                    // Xpress+Huffman decompression: 32-bit tokens of every unit, token counts, candidate chunk records
-	DevBuf lzg_bsum, lzg_dir, lzg_words;               // tokens -> bytes of large units by all CUs (lzglobal.hip): token block sums, tile directory, a word per output byte + pass counters
-	DevBuf xps_buf;                                    // large Xpress streams by segments: segment records | mode per stream | done per unit
-	DevBuf cp_tab;                                     // compaction: out_off (u64) | tile_prefix (u32) of the batch being packed
-	DevBuf one_in, one_out, one_meta;                  // staging of the host-pointer one-shot path
-	void* h_tab = nullptr; size_t h_tab_cap = 0;       // pinned staging of a plan's tables: they go up stream-ordered, plan_create does not wait for the stream
-	hipEvent_t h_tab_ev = nullptr; bool h_tab_busy = false;   // (a stream that shares a hardware queue with a busy one would make that wait as long as the other's kernels)
-	std::vector<DevBuf> table_pool;                    // table buffers of destroyed plans, reused by the next plan (hipFree waits for the whole device: it would stall pipelines that create a plan per batch)
-	uint64_t epoch = 1;                                // bumped when one of the buffers above moves (captured graphs are stale then)
-	int lznt1_sa = -1;                                 // LZNT1 dictionary flavour of the plans this context creates: -1 = the process default at plan creation, 0 / 1 = set for this context
-	const uint32_t* dbg_mode = nullptr; uint32_t dbg_mode_n = 0;   // where the last decompress / size execution left its per-unit path verdicts (mscomp_amd_debug_decode_modes)
-	const uint32_t* dbg_lzg_open = nullptr;            // the open-word counters of the last execution when a dev plan with large units ran it (they lie behind the words of its BOUND)
-	const uint32_t* dbg_mode_cnt = nullptr;            // ... and, for a dev plan with large units, where its path pass left their number (device memory; dbg_mode_n is then the bound)
-	bool profiling = false;
-	std::vector<ProfRec> recs;
-	std::vector<hipEvent_t> free_events;
-	std::vector<DevBuf*> bufs()
-	{
-		return { &slots, &slot_size, &prefix, &tile_sums, &lzrec, &links, &lasthead, &mlen3, &moff, &wtok, &wmat, &wfar, &wrec, &sbrec,
-		         &tokbits, &counts, &extra, &lens, &codes, &fb_list, &fbflag, &dz_cin, &dz_csize, &dz_unit, &dz_tok, &dz_ntok, &dz_xhc, &dz_scr,
-		         &lzg_bsum, &lzg_dir, &lzg_words, &xps_buf, &cp_tab, &one_in, &one_out, &one_meta };
-	}
-	mscomp_amd_ctx() { for (DevBuf* b : bufs()) { b->epoch = &epoch; } }
-};
-
-struct mscomp_amd_plan {
-	mscomp_amd_ctx* ctx = nullptr;
-	MSCompFormat format = MSCOMP_NONE;
-	bool decompress = false;
-	bool sizing = false;                               // a decompressed-size plan (mscomp_amd_plan_create_size): out_cap holds the limits, nothing is decoded
-	bool dev = false;                                  // a plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev / _compress_dev; with sizing: _size_dev)
-	bool crc = false;                                  // a CRC plan (mscomp_amd_plan_create_crc_dev): a dev plan without a format; tables = cum (u64 x (n_units + 1)) | off (u64 x n_units)
-	bool large = false;                                // ... with MSCOMP_AMD_DEV_LARGE_UNITS: the tables of the optional paths are built there too (xhc_scr, lzg_*, xps_big / xps_seg hold the bounds
-	                                                   // they were reserved for, 0 = the path is off for the plan; the counts of an execution are in xps_cnt / lzg_cnt, device memory)
-	uint32_t* xps_cnt = nullptr; uint32_t* lzg_cnt = nullptr;   // (behind the prefix arrays of xps_tab / lzg_tab)
-	uint64_t in_total_max = 0, out_total_max = 0;      // ... and the bounds its scratch was reserved for
-	uint32_t n_units = 0, n_chunks = 0;
-	uint64_t total_in = 0, max_unit = 0;               // (max_unit of a compress dev plan: the largest unit it takes)
-	bool lznt1_sa = false;                             // LZNT1: the suffix-array dictionary flavour -- fixed when the plan is created: a plan never changes its bytes under a running caller
-	bool matches_ready = false;                        // the caller has run the links + find kernels of this execution itself, range by range (the pipelined one-shot call): compress_launch skips them once
-	bool no_graph = false;                             // one-shot plans run with changing buffer addresses: a captured graph would be re-captured every time
-	DevBuf tables;                                     // in_off | in_len | out_off | out_cap | chunk_prefix; dev plans: what their table pass writes (reserve_dev_tables)
-	DevBuf tokpre;                                     // decompression by tokens (host plans): first token slot | first candidate slot | first token-scratch slot of every unit (n_units + 1 u64 each)
-	uint32_t xhc_slots = 0;                            // candidate chunk slots of the batch
-	uint64_t xhc_scr = 0;                              // token-scratch slots (candidates of multi-chunk buffers), 0 = none
-	DevBuf lzg_tab;                                    // lzglobal.hip: unit (u32 x n_big, padded) | tb_prefix | tile_prefix | word_prefix (u64 x (n_big + 1) each)
-	uint32_t lzg_big = 0, lzg_tb = 0, lzg_tiles = 0;   // units taken by that path (0: not used), their token blocks and tiles
-	uint64_t lzg_words = 0;
-	DevBuf xps_tab;                                    // xps_*: unit (u32 x n_big, padded) | seg_prefix (u64 x (n_big + 1))
-	uint32_t xps_big = 0, xps_seg = 0, xps_seg_bytes = 0, xps_warm_bytes = 0;
-	// what the launch code reads, resolved when the plan is created (the launch functions do not know where a creator put it): the columns of
-	// `tables`; the prefixes, in tokpre for host plans and in `tables` for dev plans; reject (u32 x n_units), written by a dev plan's table pass
-	BatchTables bt{};
-	u64* tok_prefix = nullptr; u64* cand_prefix = nullptr; u64* scr_prefix = nullptr;
-	uint32_t* reject = nullptr;
-	// the plan's launch sequence as a hipGraph (plan_run): captured on the plan's second execution, replayed while the
-	// arguments and the scratch buffers stay where they were
-	hipGraphExec_t gexec = nullptr;
-	const void* g_args[16] = {};                       // (a host plan's four pointers, a dev plan's eight, a size dev plan's seven; a block container's eight and eleven; a block reader's twelve; a block writer's sixteen)
-	uint64_t g_epoch = 0, g_mode = 0;
-	uint32_t executions = 0;
-	bool ran = false;                                  // executed at least once (mscomp_amd_debug_plan_paths: a dev plan's counts are those of its last execution)
-	// (on the plan's device, its stream idle. mscomp_amd_plan_destroy hands `tables` to the context's pool first)
-	~mscomp_amd_plan() { if (gexec) { (void)hipGraphExecDestroy(gexec); } tables.release(); tokpre.release(); lzg_tab.release(); xps_tab.release(); }
-};
-
-namespace {
-
-// The mscomp_amd_debug_set_* hooks pick between bit-identical kernels for the tests. They are process-wide, so the product ignores them unless the
-// process asked for them BEFORE the library was loaded (MSCOMP_AMD_TEST_HOOKS=1: tests/conftest.py and the tools do): a deployment cannot have its
-// kernels switched under it by a stray call (VERDICT r05 weak 8).
-bool test_hooks_on() { static const bool on = [] { const char* e = getenv("MSCOMP_AMD_TEST_HOOKS"); return e && *e == '1'; }(); return on; }
+// the flavour a plan created in `c` right now would get
 bool lznt1_sa_for(const mscomp_amd_ctx* c) { return (c->lznt1_sa >= 0 ? c->lznt1_sa : g_lznt1_sa.load(std::memory_order_relaxed)) != 0; }
-
-struct DeviceGuard {
-	int prev = -1; bool ok = true;
-	explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; } if (prev != dev) { ok = hipSetDevice(dev) == hipSuccess; } }
-	~DeviceGuard() { int cur = -1; if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) { (void)hipSetDevice(prev); } }
-};
-
-hipEvent_t get_event(mscomp_amd_ctx* c)
-{
-	if (!c->free_events.empty()) { hipEvent_t e = c->free_events.back(); c->free_events.pop_back(); return e; }
-	hipEvent_t e = nullptr; (void)hipEventCreate(&e); return e;
-}
-struct KernelTimer {
-	mscomp_amd_ctx* c; ProfRec r;
-	KernelTimer(mscomp_amd_ctx* ctx, const char* name) : c(ctx), r{name, nullptr, nullptr}
-	{ if (c->profiling) { r.a = get_event(c); r.b = get_event(c); (void)hipEventRecord(r.a, c->stream); } }
-	~KernelTimer() { if (c->profiling) { (void)hipEventRecord(r.b, c->stream); c->recs.push_back(r); } }
-};
 
 // Bytes an OPTIONAL fast-path scratch buffer may take: the environment's cap, and never more than half of what the device has free
 // right now (what the buffer already holds counts as free: reserve() reuses it). The fast paths have fallbacks that need no scratch,
@@ -600,7 +475,7 @@ static XpsTables xps_tables(const mscomp_amd_plan* p, mscomp_amd_ctx* c)
 // the per-unit path verdicts an execution of p leaves in the ctx scratch: Xpress+Huffman, XHC_SPEC / XHC_SERIAL for every unit (xhc_chain_kernel);
 // Xpress, the segment walk's mode for every unit with XPS_MIN_IN input bytes or more (2 = done by segments, 0 = the one-wave walk), none when
 // the plan does not take that path
-static void note_modes(mscomp_amd_plan* p)
+extern "C++" void msc::note_modes(mscomp_amd_plan* p)
 {
 	mscomp_amd_ctx* c = p->ctx;
 	c->dbg_mode = nullptr; c->dbg_mode_n = 0; c->dbg_mode_cnt = nullptr;
@@ -714,42 +589,6 @@ static void compress_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_
 		break;
 	}
 	}
-}
-
-// One execution of a plan: its launches, given as `launch`. A plan that is executed repeatedly replays them as one hipGraph (the gaps between
-// the 4-9 launches are ~3 % of an LZNT1 pass): captured on the second execution and again whenever a pointer (args), the ctx scratch or a
-// kernel switch moved. Plain launches instead: on the first execution (one-time function attributes are set there), while profiling (the
-// per-kernel events are not part of a graph), with MSCOMP_AMD_NO_GRAPH, for no_graph plans, and while the caller captures the ctx stream (the
-// launches then go into the caller's graph; a stream whose capture state cannot be read counts as captured). Only executions that may replay
-// are counted.
-extern "C++" template <class Launch, size_t N>
-static MSCompStatus plan_run(mscomp_amd_plan* p, const void* const (&args)[N], const Launch& launch)
-{
-	static_assert(N <= sizeof p->g_args / sizeof p->g_args[0], "g_args holds the arguments of every caller");
-	mscomp_amd_ctx* c = p->ctx;
-	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-	if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-	static const bool no_graph = getenv("MSCOMP_AMD_NO_GRAPH") != nullptr;
-	if (cs == hipStreamCaptureStatusNone && !no_graph && !p->no_graph && !c->profiling && p->n_units && ++p->executions >= 2) {
-		const uint64_t mode_now = g_mode_epoch.load(std::memory_order_acquire);
-		const bool same = p->gexec && p->g_epoch == c->epoch && p->g_mode == mode_now && memcmp(p->g_args, args, sizeof args) == 0;
-		if (!same) {
-			if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
-			hipGraph_t graph = nullptr;
-			if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-				launch();
-				const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
-				if (ee == hipSuccess && graph && hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0) == hipSuccess) {
-					p->g_epoch = c->epoch; p->g_mode = mode_now; memcpy(p->g_args, args, sizeof args);
-				} else { p->gexec = nullptr; }
-				if (graph) { (void)hipGraphDestroy(graph); }
-			}
-			(void)hipGetLastError();
-		}
-		if (p->gexec) { return hipGraphLaunch(p->gexec, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
-	}
-	launch();
-	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
 MSCompStatus mscomp_amd_plan_execute(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status)
@@ -968,7 +807,7 @@ static void run_dev_paths(mscomp_amd_plan* p)
 // The bounds of a decompress dev plan's per-unit counts summed over the batch: every accepted unit has in_len <= 0xFFFFF000 and the accepted
 // ones sum to at most in_total_max / out_total_max; a rejected unit counts as an empty one (one chunk, 64 token slots, 3 candidates).
 // false: more than the tables can address (MSCOMP_MEM_ERROR). Needs no device: a creator calls it before the context is used.
-static bool decode_dev_counts(MSCompFormat format, uint64_t N, uint64_t in_total_max, uint64_t O, bool sizing, uint64_t& I, uint64_t& chunks, uint64_t& toks, uint64_t& cands)
+extern "C++" bool msc::decode_dev_counts(MSCompFormat format, uint64_t N, uint64_t in_total_max, uint64_t O, bool sizing, uint64_t& I, uint64_t& chunks, uint64_t& toks, uint64_t& cands)
 {
 	I = in_total_max < N * 0xFFFFF000ull ? in_total_max : N * 0xFFFFF000ull;
 	chunks = N; toks = 0; cands = 0;
@@ -1072,8 +911,8 @@ MSCompStatus mscomp_amd_plan_create_compress_dev(mscomp_amd_ctx* c, MSCompFormat
 
 // The launches of one execution of a compress or decompress dev plan: mscomp_amd_plan_execute_dev runs them through plan_run, a block
 // container inside its own sequence (it is that call's plan_run, or the caller's capture, that may turn them into a graph).
-static void dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
-                       uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+extern "C++" void msc::dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                   uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
 {
 	mscomp_amd_ctx* c = p->ctx;
 	u64* san = static_cast<u64*>(p->tables.p); uint32_t* chunk_prefix = const_cast<uint32_t*>(p->bt.chunk_prefix);
@@ -1236,417 +1075,6 @@ MSCompStatus mscomp_amd_compact_dev(mscomp_amd_ctx* c, size_t n_units, const uin
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	launch_compact_dev(c->stream, (uint32_t)n_units, d_src, d_src_off, d_len, align, d_packed, packed_cap, d_packed_off, c->cpd_blocks);
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
-}
-
-// ---- block containers (include/mscomp_amd.h; kernels: blocks.hip) ----
-// A container owns two inner dev plans over blocks as units -- compress: n_blocks_max units of at most block_size bytes; decompress: the same
-// number of units within in_total_max bytes on either side --, a staging area for the compressed blocks and its own tables. Its two calls
-// run the inner plans' launches (dev_launch) between their own passes, through plan_run with a record of their own (crun / drun: plans that
-// hold nothing but the graph of the call), so the inner plans never capture: the graph is the call's, or the caller's.
-struct mscomp_amd_blocks {
-	mscomp_amd_ctx* ctx = nullptr;
-	MSCompFormat format = MSCOMP_NONE;
-	uint32_t shift = 0, n_res = 0, n_blocks = 0;       // block_size = 1 << shift; n_blocks = n_blocks_max
-	uint64_t in_total_max = 0;
-	mscomp_amd_plan* cplan = nullptr; mscomp_amd_plan* dplan = nullptr;   // (null when n_blocks is 0)
-	mscomp_amd_plan crun, drun, krun, vrun;            // (krun: mscomp_amd_blocks_crc, vrun: _check)
-	DevBuf tab, stage;                                 // BlocksTab; staged compressed blocks: in_total_max + 16 n_res bytes
-	BlocksTab t{};
-};
-
-static void blocks_tab(mscomp_amd_blocks* b)
-{
-	const size_t n = b->n_res, m = b->n_blocks;
-	u64* q = static_cast<u64*>(b->tab.p);
-	BlocksTab& t = b->t;
-	t.res_a = q; t.res_b = q + n; t.unit_first = q + 2 * n; q += 3 * n + 1;
-	t.in_off = q; t.in_len = q + m; t.out_off = q + 2 * m; t.out_cap = q + 3 * m; t.ulen = q + 4 * m; t.aux_a = q + 5 * m; t.aux_b = q + 6 * m; q += 7 * m;
-	t.rstat = reinterpret_cast<int32_t*>(q); t.ustat = t.rstat + n; t.act = reinterpret_cast<uint32_t*>(t.ustat + m); t.ucrc = t.act + m;
-}
-
-MSCompStatus mscomp_amd_blocks_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t in_total_max, uint32_t flags,
-                                      mscomp_amd_blocks** out)
-{
-	if (!out) { return MSCOMP_ARG_ERROR; }
-	*out = nullptr;
-	if (!c || flags || n_res > 0x7FFFFFF0u || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
-	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
-	const uint64_t by_bytes = in_total_max / block_size;
-	if (by_bytes > 0x7FFFFFF0ull - n_res) { return MSCOMP_MEM_ERROR; }   // (checked before the context is used; in_total_max < 2^50 from here on)
-	const uint64_t M = n_res + by_bytes;
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	std::unique_ptr<mscomp_amd_blocks> b(new (std::nothrow) mscomp_amd_blocks());
-	if (!b) { return MSCOMP_MEM_ERROR; }
-	b->ctx = c; b->format = format; b->shift = (uint32_t)__builtin_ctz(block_size); b->n_res = (uint32_t)n_res; b->n_blocks = (uint32_t)M; b->in_total_max = in_total_max;
-	b->crun.ctx = b->drun.ctx = b->krun.ctx = b->vrun.ctx = c; b->crun.n_units = b->drun.n_units = b->krun.n_units = b->vrun.n_units = (uint32_t)n_res;
-	MSCompStatus st = MSCOMP_OK;
-	if (!b->tab.reserve((3 * n_res + 1 + 7 * M) * 8 + (n_res + 3 * M) * 4 + 64) || !b->stage.reserve(in_total_max + 16 * (uint64_t)n_res + 64)) { st = MSCOMP_MEM_ERROR; }
-	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_compress_dev(c, format, M, in_total_max, block_size, &b->cplan); }
-	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, in_total_max, in_total_max, &b->dplan); }
-	if (st != MSCOMP_OK) {
-		(void)hipGetLastError();
-		mscomp_amd_plan_destroy(b->cplan); mscomp_amd_plan_destroy(b->dplan);
-		b->tab.release(); b->stage.release();
-		return st;
-	}
-	blocks_tab(b.get());
-	*out = b.release();
-	return MSCOMP_OK;
-}
-
-void mscomp_amd_blocks_destroy(mscomp_amd_blocks* b)
-{
-	if (!b) { return; }
-	DeviceGuard g(b->ctx->device);
-	(void)hipStreamSynchronize(b->ctx->stream);
-	mscomp_amd_plan_destroy(b->cplan); mscomp_amd_plan_destroy(b->dplan);
-	b->tab.release(); b->stage.release();
-	delete b;                                              // (crun / drun give up their graphs)
-}
-
-uint64_t mscomp_amd_blocks_bound(const mscomp_amd_blocks* b) { return b ? b->n_blocks : 0; }
-
-MSCompStatus mscomp_amd_blocks_compress(mscomp_amd_blocks* b, const uint8_t* d_in, const uint64_t* d_res_off, const uint64_t* d_res_len,
-                                        uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_block_first, uint64_t* d_block_off, int32_t* d_status)
-{
-	if (!b || !d_block_first || !d_block_off || (b->n_res && (!d_res_off || !d_res_len || !d_status))) { return MSCOMP_ARG_ERROR; }
-	if (b->in_total_max && (!d_in || !d_packed)) { return MSCOMP_ARG_ERROR; }
-	mscomp_amd_ctx* c = b->ctx;
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (b->cplan) { b->cplan->ran = true; }
-	const void* args[8] = { d_in, d_res_off, d_res_len, d_packed, reinterpret_cast<const void*>((uintptr_t)packed_cap), d_block_first, d_block_off, d_status };
-	return plan_run(&b->crun, args, [&] {
-		const BlocksTab& t = b->t;
-		uint8_t* stage = static_cast<uint8_t*>(b->stage.p);
-		{ KernelTimer k(c, "bk_ctables"); launch_blocks_ctables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_off, d_res_len, d_block_first, t); }
-		if (b->cplan) { dev_launch(b->cplan, d_in, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
-		{ KernelTimer k(c, "bk_select_kernel"); launch_blocks_select(c->stream, b->n_res, b->n_blocks, packed_cap, d_in, stage, d_block_first, t, d_block_off, d_status); }
-		{ KernelTimer k(c, "cpd_copy_kernel"); launch_pack_ptrs(c->stream, b->n_blocks, t.aux_b, t.aux_a, d_block_off, d_packed, packed_cap, c->cpd_blocks); }
-	});
-}
-
-MSCompStatus mscomp_amd_blocks_decompress(mscomp_amd_blocks* b, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
-                                          const uint64_t* d_block_off, const uint64_t* d_res_len, const uint64_t* d_range,
-                                          uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
-{
-	if (!b || !d_block_first || !d_block_off || (b->n_res && (!d_res_len || !d_out_off || !d_out_cap || !d_out_len || !d_status))) { return MSCOMP_ARG_ERROR; }
-	if (b->in_total_max && (!d_packed || !d_out)) { return MSCOMP_ARG_ERROR; }
-	if (b->n_res == 0) { return MSCOMP_OK; }               // (nothing to report on)
-	mscomp_amd_ctx* c = b->ctx;
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (b->dplan) { note_modes(b->dplan); b->dplan->ran = true; }
-	const void* args[11] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_range,
-	                         d_out, d_out_off, d_out_cap, d_out_len, d_status };
-	return plan_run(&b->drun, args, [&] {
-		const BlocksTab& t = b->t;
-		{ KernelTimer k(c, "bk_dtables"); launch_blocks_dtables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, packed_len, d_res_len, d_block_first, d_block_off,
-		                                                        d_range, d_out_off, d_out_cap, t); }
-		if (b->dplan) { dev_launch(b->dplan, d_packed, t.in_off, t.in_len, d_out, t.out_off, t.out_cap, t.ulen, t.ustat); }
-		{ KernelTimer k(c, "bk_rawcopy_kernel"); launch_blocks_rawcopy(c->stream, b->n_blocks, b->shift, d_packed, d_out, t, c->cpd_blocks); }
-		{ KernelTimer k(c, "bk_dfold_kernel"); launch_blocks_dfold(c->stream, b->n_res, t, d_out_len, d_status); }
-	});
-}
-
-// The checksums of a container: both calls are a table pass of their own, the CRC table pass and the CRC kernel over the blocks as units
-// (crc32.hip), on the container's tables -- every column is a temporary of one call, so the ones compress and decompress use serve here too:
-//   crc     t.unit_first = block_first, t.in_off / t.in_len = the blocks (bk_cunits_kernel), t.aux_a .. = cum (m + 1), t.act = resource of a block,
-//           t.ulen = the resource's bytes behind it, t.ucrc = x^(8 times that), t.res_a .. = the running sum the resources' seeds are made with (n + 1)
-//   check   t.unit_first / t.res_b = units and first block of the clipped ranges, t.in_off / t.in_len = the blocks in d_out, t.ulen = their entry
-//           of d_block_crc, t.aux_a .. = cum, t.ucrc = what was read
-MSCompStatus mscomp_amd_blocks_crc(mscomp_amd_blocks* b, const uint8_t* d_data, const uint64_t* d_res_off, const uint64_t* d_res_len,
-                                   uint32_t* d_block_crc, uint32_t* d_res_crc, int32_t* d_status)
-{
-	if (!b || (b->n_blocks && !d_block_crc) || (b->n_res && (!d_res_off || !d_res_len || !d_status))) { return MSCOMP_ARG_ERROR; }
-	if (b->in_total_max && !d_data) { return MSCOMP_ARG_ERROR; }
-	if (b->n_res == 0) { return MSCOMP_OK; }               // (no resource, no block: n_blocks_max is 0 too)
-	mscomp_amd_ctx* c = b->ctx;
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	const void* args[6] = { d_data, d_res_off, d_res_len, d_block_crc, d_res_crc, d_status };
-	return plan_run(&b->krun, args, [&] {
-		const BlocksTab& t = b->t;
-		{ KernelTimer k(c, "bk_ctables"); launch_blocks_ctables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_off, d_res_len, t.unit_first, t); }
-		{ KernelTimer k(c, "bk_crcgroups_kernel"); launch_blocks_crcgroups(c->stream, b->n_res, b->n_blocks, b->shift, d_res_len, t.unit_first, t); }
-		// the resources' statuses and seeds (the check of bk_cres_kernel once more, with the seed of an empty unit for a rejected resource), then the blocks' seeds and factors
-		{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, b->n_res, b->in_total_max, nullptr, d_res_len, nullptr, t.res_a, d_status); }
-		{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, b->n_res, t.res_a, d_res_crc, nullptr, nullptr); }
-		{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, b->n_blocks, ~(u64)0, nullptr, t.in_len, nullptr, t.aux_a, nullptr); }
-		{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, b->n_blocks, t.aux_a, d_block_crc, t.ulen, d_res_crc ? t.ucrc : nullptr); }
-		{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, b->n_blocks, d_data, t.in_off, t.aux_a, d_block_crc, t.act, t.ucrc, d_res_crc, c->crc_blocks); }
-	});
-}
-
-MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* b, const uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_res_len,
-                                     const uint64_t* d_block_first, const uint64_t* d_range, const uint32_t* d_block_crc,
-                                     uint64_t* d_out_len, int32_t* d_status)
-{
-	if (!b || !d_block_first || (b->n_blocks && !d_block_crc) || (b->n_res && (!d_out_off || !d_res_len || !d_out_len || !d_status))) { return MSCOMP_ARG_ERROR; }
-	if (b->in_total_max && !d_out) { return MSCOMP_ARG_ERROR; }
-	if (b->n_res == 0) { return MSCOMP_OK; }
-	mscomp_amd_ctx* c = b->ctx;
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	const void* args[8] = { d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status };
-	return plan_run(&b->vrun, args, [&] {
-		const BlocksTab& t = b->t;
-		{ KernelTimer k(c, "bk_ktables"); launch_blocks_ktables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_len, d_block_first, d_range, d_out_off, d_status, t); }
-		{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, b->n_blocks, ~(u64)0, nullptr, t.in_len, nullptr, t.aux_a, nullptr); }
-		{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, b->n_blocks, t.aux_a, t.ucrc, nullptr, nullptr); }
-		{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, b->n_blocks, d_out, t.in_off, t.aux_a, t.ucrc, nullptr, nullptr, nullptr, c->crc_blocks); }
-		{ KernelTimer k(c, "bk_kfold_kernel"); launch_blocks_kfold(c->stream, b->n_res, d_block_crc, t, d_out_len, d_status); }
-	});
-}
-
-// ---- block readers (include/mscomp_amd.h; kernels: reader.hip) ----
-// A reader owns one inner decompress dev plan over blocks_max units within blocks_max B bytes on either side, the cache those units are
-// decoded into and its own tables: everything is sized by what one call may read, nothing by what the container holds but the 4 bytes per
-// entry of its block table. The call runs the inner plan's launches (dev_launch) and the CRC kernels between its own passes, through plan_run
-// with a record of its own (run), as a container does.
-struct mscomp_amd_reader {
-	mscomp_amd_ctx* ctx = nullptr;
-	MSCompFormat format = MSCOMP_NONE;
-	uint32_t shift = 0, n_res = 0, nbt = 0, n_req = 0, m = 0;   // block_size = 1 << shift; nbt = n_blocks_table; m = blocks_max
-	mscomp_amd_plan* dplan = nullptr;                  // (null when blocks_max is 0)
-	mscomp_amd_plan run;
-	DevBuf tab, cache;                                 // ReaderTab; blocks_max slots of block_size bytes
-	ReaderTab t{};
-	bool ran = false;
-};
-
-static size_t reader_tab_bytes(size_t n, size_t m, size_t nbt) { return (5 * n + 1 + 8 * m + 1) * 8 + (n + 6 * m + nbt + 2) * 4 + 64; }
-static void reader_tab(mscomp_amd_reader* r)
-{
-	const size_t n = r->n_req, m = r->m;
-	u64* q = static_cast<u64*>(r->tab.p);
-	ReaderTab& t = r->t;
-	t.q_off = q; t.q_want = q + n; t.q_j0 = q + 2 * n; t.q_len = q + 3 * n; t.unit_first = q + 4 * n; q += 5 * n + 1;
-	t.in_off = q; t.in_len = q + m; t.out_off = q + 2 * m; t.out_cap = q + 3 * m; t.ulen = q + 4 * m; t.src = q + 5 * m; t.clen = q + 6 * m; t.cum = q + 7 * m; q += 8 * m + 1;
-	t.q_stat = reinterpret_cast<int32_t*>(q); t.ustat = t.q_stat + n;
-	t.act = reinterpret_cast<uint32_t*>(t.ustat + m); t.owner = t.act + m; t.uq = t.act + 2 * m; t.ublk = t.act + 3 * m; t.ucrc = t.act + 4 * m;
-	t.own = t.act + 5 * m; t.cnt = t.own + r->nbt;
-}
-
-MSCompStatus mscomp_amd_reader_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_req,
-                                      uint64_t blocks_max, uint32_t flags, mscomp_amd_reader** out)
-{
-	if (!out) { return MSCOMP_ARG_ERROR; }
-	*out = nullptr;
-	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
-	if (n_res > 0x7FFFFFF0u || n_blocks_table > 0x7FFFFFF0u || n_req > 0x7FFFFFF0u || blocks_max > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
-	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
-	const uint64_t M = blocks_max, bytes = M * block_size;                // (< 2^50)
-	uint64_t I = 0, chunks = 0, toks = 0, cands = 0;
-	if (!decode_dev_counts(format, M, bytes, bytes, false, I, chunks, toks, cands)) { return MSCOMP_MEM_ERROR; }   // (what the inner plan would refuse: checked before the context is used)
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	std::unique_ptr<mscomp_amd_reader> r(new (std::nothrow) mscomp_amd_reader());
-	if (!r) { return MSCOMP_MEM_ERROR; }
-	r->ctx = c; r->format = format; r->shift = (uint32_t)__builtin_ctz(block_size); r->n_res = (uint32_t)n_res; r->nbt = (uint32_t)n_blocks_table;
-	r->n_req = (uint32_t)n_req; r->m = (uint32_t)M;
-	r->run.ctx = c; r->run.n_units = (uint32_t)n_req;
-	MSCompStatus st = MSCOMP_OK;
-	if (!r->tab.reserve(reader_tab_bytes(n_req, M, n_blocks_table)) || (M && !r->cache.reserve(bytes + 64))) { st = MSCOMP_MEM_ERROR; }
-	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, bytes, bytes, &r->dplan); }
-	if (st != MSCOMP_OK) {
-		(void)hipGetLastError();
-		mscomp_amd_plan_destroy(r->dplan);
-		r->tab.release(); r->cache.release();
-		return st;
-	}
-	reader_tab(r.get());
-	*out = r.release();
-	return MSCOMP_OK;
-}
-
-void mscomp_amd_reader_destroy(mscomp_amd_reader* r)
-{
-	if (!r) { return; }
-	DeviceGuard g(r->ctx->device);
-	(void)hipStreamSynchronize(r->ctx->stream);
-	mscomp_amd_plan_destroy(r->dplan);
-	r->tab.release(); r->cache.release();
-	delete r;                                              // (run gives up its graph)
-}
-
-MSCompStatus mscomp_amd_reader_read(mscomp_amd_reader* r, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
-                                    const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_req,
-                                    uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
-{
-	if (!r || !d_block_first || !d_block_off || (r->n_res && !d_res_len)) { return MSCOMP_ARG_ERROR; }
-	if (r->n_req && (!d_req || !d_out_off || !d_out_cap || !d_out_len || !d_status)) { return MSCOMP_ARG_ERROR; }
-	if (r->m && (!d_packed || !d_out)) { return MSCOMP_ARG_ERROR; }
-	if (r->n_req == 0) { return MSCOMP_OK; }               // (nothing to report on)
-	mscomp_amd_ctx* c = r->ctx;
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (r->dplan) { note_modes(r->dplan); r->dplan->ran = true; }
-	r->ran = true;
-	const void* args[12] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
-	                         d_out, d_out_off, d_out_cap, d_out_len, d_status };
-	return plan_run(&r->run, args, [&] {
-		const ReaderTab& t = r->t;
-		uint8_t* cache = static_cast<uint8_t*>(r->cache.p);
-		{ KernelTimer k(c, "rd_req_kernel"); launch_reader_requests(c->stream, r->n_req, r->n_res, r->nbt, r->m, r->shift, d_res_len, d_block_first, d_req, d_out_cap, t); }
-		{ KernelTimer k(c, "rd_units"); launch_reader_units(c->stream, r->n_req, r->nbt, r->m, r->shift, packed_len, d_packed, cache, d_block_off, t); }
-		if (r->dplan) { dev_launch(r->dplan, d_packed, t.in_off, t.in_len, cache, t.out_off, t.out_cap, t.ulen, t.ustat); }
-		if (d_block_crc && r->m) {                                          // the owners' blocks lie under two bases: their addresses go in as offsets from a null one
-			{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, r->m, ~(u64)0, nullptr, t.clen, nullptr, t.cum, nullptr); }
-			{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, r->m, t.cum, t.ucrc, nullptr, nullptr); }
-			{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, r->m, nullptr, t.src, t.cum, t.ucrc, nullptr, nullptr, nullptr, c->crc_blocks); }
-		}
-		{ KernelTimer k(c, "rd_fold_kernel"); launch_reader_fold(c->stream, r->n_req, d_block_crc, t, d_out_len, d_status); }
-		{ KernelTimer k(c, "rd_gather_kernel"); launch_reader_gather(c->stream, r->n_req, r->m, r->shift, d_out, d_out_off, t, c->cpd_blocks); }
-	});
-}
-
-int mscomp_amd_reader_counts(mscomp_amd_reader* r, uint32_t out[3])
-{	// units, distinct blocks and decoded blocks of the reader's last execution (read back; none before the first)
-	if (!r || !out) { return -1; }
-	DeviceGuard g(r->ctx->device);
-	if (!g.ok || hipStreamSynchronize(r->ctx->stream) != hipSuccess) { return -1; }
-	out[0] = out[1] = out[2] = 0;
-	if (!r->ran) { return 0; }
-	uint64_t units = 0;
-	if (hipMemcpy(&units, r->t.unit_first + r->n_req, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
-	if (hipMemcpy(&out[1], r->t.cnt, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
-	out[0] = (uint32_t)units;
-	return 0;
-}
-
-// ---- block writers (include/mscomp_amd.h; kernels: writer.hip and the reader's) ----
-// A writer owns what a reader owns -- the inner decompress dev plan over blocks_max units, the cache, the reader's tables -- and beside it an
-// inner compress dev plan over the same units (a dirty block is compressed from its cache slot into its staging slot), the staging area and
-// three more columns. The call runs the reader's passes up to the fold, then its own, through plan_run with a record of its own.
-struct mscomp_amd_writer {
-	mscomp_amd_ctx* ctx = nullptr;
-	MSCompFormat format = MSCOMP_NONE;
-	uint32_t shift = 0, n_res = 0, nbt = 0, n_req = 0, m = 0;   // as a reader's
-	mscomp_amd_plan* dplan = nullptr; mscomp_amd_plan* cplan = nullptr;   // (null when blocks_max is 0)
-	mscomp_amd_plan run;
-	DevBuf tab, cache, stage;                          // WriterTab; blocks_max slots of block_size bytes each
-	WriterTab t{};
-	bool ran = false;
-};
-
-static size_t writer_tab_bytes(size_t n, size_t m, size_t nbt) { return (5 * n + 1 + 8 * m + 1) * 8 + (n + 8 * m + 2 * nbt + 4) * 4 + 64; }
-static void writer_tab(mscomp_amd_writer* w)
-{
-	const size_t n = w->n_req, m = w->m;
-	u64* q = static_cast<u64*>(w->tab.p);
-	ReaderTab& t = w->t.r;
-	t.q_off = q; t.q_want = q + n; t.q_j0 = q + 2 * n; t.q_len = q + 3 * n; t.unit_first = q + 4 * n; q += 5 * n + 1;
-	t.in_off = q; t.in_len = q + m; t.out_off = q + 2 * m; t.out_cap = q + 3 * m; t.ulen = q + 4 * m; t.src = q + 5 * m; t.clen = q + 6 * m; t.cum = q + 7 * m; q += 8 * m + 1;
-	t.q_stat = reinterpret_cast<int32_t*>(q); t.ustat = t.q_stat + n;
-	t.act = reinterpret_cast<uint32_t*>(t.ustat + m); t.owner = t.act + m; t.uq = t.act + 2 * m; t.ublk = t.act + 3 * m; t.ucrc = t.act + 4 * m;
-	w->t.next = t.act + 5 * m; w->t.dirty = t.act + 6 * m;
-	t.own = t.act + 7 * m; w->t.head = t.own + w->nbt; t.cnt = w->t.head + w->nbt;
-}
-
-MSCompStatus mscomp_amd_writer_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_req,
-                                      uint64_t blocks_max, uint32_t flags, mscomp_amd_writer** out)
-{
-	if (!out) { return MSCOMP_ARG_ERROR; }
-	*out = nullptr;
-	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
-	if (n_res > 0x7FFFFFF0u || n_blocks_table > 0x7FFFFFF0u || n_req > 0x7FFFFFF0u || blocks_max > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
-	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
-	const uint64_t M = blocks_max, bytes = M * block_size;                // (< 2^50)
-	uint64_t I = 0, chunks = 0, toks = 0, cands = 0;
-	if (!decode_dev_counts(format, M, bytes, bytes, false, I, chunks, toks, cands)) { return MSCOMP_MEM_ERROR; }   // (as a reader: checked before the context is used)
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	std::unique_ptr<mscomp_amd_writer> w(new (std::nothrow) mscomp_amd_writer());
-	if (!w) { return MSCOMP_MEM_ERROR; }
-	w->ctx = c; w->format = format; w->shift = (uint32_t)__builtin_ctz(block_size); w->n_res = (uint32_t)n_res; w->nbt = (uint32_t)n_blocks_table;
-	w->n_req = (uint32_t)n_req; w->m = (uint32_t)M;
-	w->run.ctx = c; w->run.n_units = (uint32_t)n_req;
-	MSCompStatus st = MSCOMP_OK;
-	if (!w->tab.reserve(writer_tab_bytes(n_req, M, n_blocks_table)) || (M && (!w->cache.reserve(bytes + 64) || !w->stage.reserve(bytes + 64)))) { st = MSCOMP_MEM_ERROR; }
-	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, bytes, bytes, &w->dplan); }
-	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_compress_dev(c, format, M, bytes, block_size, &w->cplan); }   // (fixes the LZNT1 dictionary flavour)
-	if (st != MSCOMP_OK) {
-		(void)hipGetLastError();
-		mscomp_amd_plan_destroy(w->dplan); mscomp_amd_plan_destroy(w->cplan);
-		w->tab.release(); w->cache.release(); w->stage.release();
-		return st;
-	}
-	writer_tab(w.get());
-	*out = w.release();
-	return MSCOMP_OK;
-}
-
-void mscomp_amd_writer_destroy(mscomp_amd_writer* w)
-{
-	if (!w) { return; }
-	DeviceGuard g(w->ctx->device);
-	(void)hipStreamSynchronize(w->ctx->stream);
-	mscomp_amd_plan_destroy(w->dplan); mscomp_amd_plan_destroy(w->cplan);
-	w->tab.release(); w->cache.release(); w->stage.release();
-	delete w;                                              // (run gives up its graph)
-}
-
-MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* w, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
-                                     const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_req,
-                                     const uint8_t* d_src, const uint64_t* d_src_off, uint8_t* d_new_packed, uint64_t new_cap, uint64_t* d_new_block_off,
-                                     uint32_t* d_new_block_crc, uint64_t* d_written, int32_t* d_status, int32_t* d_res_status)
-{
-	if (!w || !d_block_first || !d_block_off || !d_new_block_off || (w->n_res && (!d_res_len || !d_res_status))) { return MSCOMP_ARG_ERROR; }
-	if (w->n_req && (!d_req || !d_src_off || !d_written || !d_status)) { return MSCOMP_ARG_ERROR; }
-	if ((w->m && !d_src) || ((w->m || w->nbt) && (!d_packed || !d_new_packed))) { return MSCOMP_ARG_ERROR; }
-	if ((d_block_crc == nullptr) != (d_new_block_crc == nullptr)) { return MSCOMP_ARG_ERROR; }
-	mscomp_amd_ctx* c = w->ctx;
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (w->dplan) { note_modes(w->dplan); w->dplan->ran = true; w->cplan->ran = true; }
-	w->ran = true;
-	const void* args[16] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
-	                         d_src, d_src_off, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_off, d_new_block_crc,
-	                         d_written, d_status, d_res_status };
-	return plan_run(&w->run, args, [&] {
-		const WriterTab& wt = w->t;
-		const ReaderTab& t = wt.r;
-		uint8_t* cache = static_cast<uint8_t*>(w->cache.p); uint8_t* stage = static_cast<uint8_t*>(w->stage.p);
-		// the reader's passes: admission (without its capacity rule), owners, the owners' blocks decoded, checksummed and judged
-		{ KernelTimer k(c, "rd_req_kernel"); launch_reader_requests(c->stream, w->n_req, w->n_res, w->nbt, w->m, w->shift, d_res_len, d_block_first, d_req, nullptr, t); }
-		{ KernelTimer k(c, "rd_units"); launch_reader_units(c->stream, w->n_req, w->nbt, w->m, w->shift, packed_len, d_packed, cache, d_block_off, t); }
-		{ KernelTimer k(c, "wr_link"); launch_writer_link(c->stream, w->n_req, w->nbt, w->m, wt); }
-		if (w->dplan) { dev_launch(w->dplan, d_packed, t.in_off, t.in_len, cache, t.out_off, t.out_cap, t.ulen, t.ustat); }
-		if (d_block_crc && w->m) {
-			{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, w->m, ~(u64)0, nullptr, t.clen, nullptr, t.cum, nullptr); }
-			{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, w->m, t.cum, t.ucrc, nullptr, nullptr); }
-			{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, w->m, nullptr, t.src, t.cum, t.ucrc, nullptr, nullptr, nullptr, c->crc_blocks); }
-		}
-		if (w->n_req) { KernelTimer k(c, "rd_fold_kernel"); launch_reader_fold(c->stream, w->n_req, d_block_crc, t, d_written, d_status); }
-		// the writer's own: patch, re-encode and checksum the dirty blocks, lay out, move
-		{ KernelTimer k(c, "wr_patch"); launch_writer_patch(c->stream, w->n_req, w->m, w->shift, d_src, d_src_off, cache, wt, c->cpd_blocks); }
-		if (w->cplan) { dev_launch(w->cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
-		if (d_block_crc && w->m) {
-			{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, w->m, ~(u64)0, nullptr, t.clen, nullptr, t.cum, nullptr); }
-			{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, w->m, t.cum, t.ucrc, nullptr, nullptr); }
-			{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, w->m, nullptr, t.src, t.cum, t.ucrc, nullptr, nullptr, nullptr, c->crc_blocks); }
-		}
-		{ KernelTimer k(c, "wr_layout_kernel"); launch_writer_layout(c->stream, w->n_req, w->n_res, w->nbt, w->m, packed_len, new_cap, d_block_first, d_block_off, d_block_crc,
-		                                                             wt, d_new_block_off, d_new_block_crc, d_written, d_status, d_res_status); }
-		{ KernelTimer k(c, "wr_move_kernel"); launch_writer_move(c->stream, w->nbt, w->shift, new_cap, d_packed, d_block_off, stage, cache, d_new_block_off, wt, d_new_packed, c->cpd_blocks); }
-	});
-}
-
-int mscomp_amd_writer_counts(mscomp_amd_writer* w, uint32_t out[3])
-{	// units, distinct blocks and re-encoded blocks of the writer's last execution (read back; none before the first, none for a refused table)
-	if (!w || !out) { return -1; }
-	DeviceGuard g(w->ctx->device);
-	if (!g.ok || hipStreamSynchronize(w->ctx->stream) != hipSuccess) { return -1; }
-	out[0] = out[1] = out[2] = 0;
-	if (!w->ran) { return 0; }
-	uint64_t units = 0;
-	uint32_t cnt[4] = {};
-	if (hipMemcpy(&units, w->t.r.unit_first + w->n_req, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
-	if (hipMemcpy(cnt, w->t.r.cnt, 16, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
-	if (cnt[3] == 0 && w->m) { out[0] = (uint32_t)units; out[1] = cnt[0]; out[2] = cnt[2]; }
-	return 0;
 }
 
 // Stage-level test hook: per-position (len-3 capped at 45, offset) of ONE unit as found by the HIP match finder.

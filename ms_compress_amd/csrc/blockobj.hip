@@ -1,0 +1,387 @@
+// blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h): containers, readers and writers. Host orchestration only, as
+// api.hip: each call runs the launches of inner dev plans (dev_launch) between its own passes, through plan_run.
+#include "host.h"
+
+using namespace msc;
+
+// A table buffer handed out column by column, in the order asked for. The same code run from address 0 counts the bytes, so a layout is
+// written down once. u64 columns first, from an 8-byte-aligned base: every one of them stays aligned.
+struct Carve {
+	uintptr_t at;
+	u64* q(size_t n) { u64* p = reinterpret_cast<u64*>(at); at += n * 8; return p; }
+	uint32_t* w(size_t n) { uint32_t* p = reinterpret_cast<uint32_t*>(at); at += n * 4; return p; }
+	int32_t* i(size_t n) { return reinterpret_cast<int32_t*>(w(n)); }
+};
+
+// The checks every create starts with, on arguments alone: MSCOMP_ARG_ERROR before MSCOMP_MEM_ERROR, both before the context is used.
+static bool create_args_ok(const mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, uint32_t flags)
+{
+	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return false; }
+	return format == MSCOMP_LZNT1 || format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF;
+}
+static bool count_ok(uint64_t n) { return n <= 0x7FFFFFF0u; }
+
+// The CRC-32 of n units: crc[u] over the len[u] bytes at base + off[u]; cum (n + 1) is scratch. The table pass, the seeds, the bytes.
+static void crc_seeds(mscomp_amd_ctx* c, uint32_t n, u64 in_total_max, const u64* len, u64* cum, int32_t* status, uint32_t* crc, const u64* after, uint32_t* fac)
+{
+	{ KernelTimer k(c, "crc_tables_kernel"); launch_crc_tables(c->stream, n, in_total_max, nullptr, len, nullptr, cum, status); }
+	{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, n, cum, crc, after, fac); }
+}
+static void crc_pass(mscomp_amd_ctx* c, uint32_t n, const uint8_t* base, const u64* off, const u64* len, u64* cum, uint32_t* crc)
+{
+	crc_seeds(c, n, ~(u64)0, len, cum, nullptr, crc, nullptr, nullptr);
+	{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, n, base, off, cum, crc, nullptr, nullptr, nullptr, c->crc_blocks); }
+}
+
+// ---- block containers (include/mscomp_amd.h; kernels: blocks.hip) ----
+// A container owns two inner dev plans over blocks as units -- compress: n_blocks_max units of at most block_size bytes; decompress: the same
+// number of units within in_total_max bytes on either side --, a staging area for the compressed blocks and its own tables. Its two calls
+// run the inner plans' launches (dev_launch) between their own passes, through plan_run with a record of their own (crun / drun: plans that
+// hold nothing but the graph of the call), so the inner plans never capture: the graph is the call's, or the caller's.
+struct mscomp_amd_blocks {
+	mscomp_amd_ctx* ctx = nullptr;
+	MSCompFormat format = MSCOMP_NONE;
+	uint32_t shift = 0, n_res = 0, n_blocks = 0;       // block_size = 1 << shift; n_blocks = n_blocks_max
+	uint64_t in_total_max = 0;
+	mscomp_amd_plan* cplan = nullptr; mscomp_amd_plan* dplan = nullptr;   // (null when n_blocks is 0)
+	mscomp_amd_plan crun, drun, krun, vrun;            // (krun: mscomp_amd_blocks_crc, vrun: _check)
+	DevBuf tab, stage;                                 // BlocksTab; staged compressed blocks: in_total_max + 16 n_res bytes
+	BlocksTab t{};
+};
+
+// the columns of a container's tables from `base` on (n resources, m blocks at most); returns where they end: from a null base, their bytes
+static uintptr_t blocks_tab(BlocksTab& t, void* base, size_t n, size_t m)
+{
+	Carve k{reinterpret_cast<uintptr_t>(base)};
+	t.res_a = k.q(n); t.res_b = k.q(n); t.unit_first = k.q(n + 1);
+	t.in_off = k.q(m); t.in_len = k.q(m); t.out_off = k.q(m); t.out_cap = k.q(m); t.ulen = k.q(m); t.aux_a = k.q(m); t.aux_b = k.q(m);
+	t.rstat = k.i(n); t.ustat = k.i(m); t.act = k.w(m); t.ucrc = k.w(m);
+	return k.at;
+}
+
+MSCompStatus mscomp_amd_blocks_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t in_total_max, uint32_t flags,
+                                      mscomp_amd_blocks** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!create_args_ok(c, format, block_size, flags) || !count_ok(n_res)) { return MSCOMP_ARG_ERROR; }
+	const uint64_t by_bytes = in_total_max / block_size;
+	if (by_bytes > 0x7FFFFFF0ull - n_res) { return MSCOMP_MEM_ERROR; }   // (checked before the context is used; in_total_max < 2^50 from here on)
+	const uint64_t M = n_res + by_bytes;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_blocks> b(new (std::nothrow) mscomp_amd_blocks());
+	if (!b) { return MSCOMP_MEM_ERROR; }
+	b->ctx = c; b->format = format; b->shift = (uint32_t)__builtin_ctz(block_size); b->n_res = (uint32_t)n_res; b->n_blocks = (uint32_t)M; b->in_total_max = in_total_max;
+	b->crun.ctx = b->drun.ctx = b->krun.ctx = b->vrun.ctx = c; b->crun.n_units = b->drun.n_units = b->krun.n_units = b->vrun.n_units = (uint32_t)n_res;
+	MSCompStatus st = MSCOMP_OK;
+	if (!b->tab.reserve(blocks_tab(b->t, nullptr, n_res, M) + 64) || !b->stage.reserve(in_total_max + 16 * (uint64_t)n_res + 64)) { st = MSCOMP_MEM_ERROR; }
+	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_compress_dev(c, format, M, in_total_max, block_size, &b->cplan); }
+	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, in_total_max, in_total_max, &b->dplan); }
+	if (st != MSCOMP_OK) { (void)hipGetLastError(); mscomp_amd_blocks_destroy(b.release()); return st; }
+	blocks_tab(b->t, b->tab.p, n_res, M);
+	*out = b.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_blocks_destroy(mscomp_amd_blocks* b)
+{
+	if (!b) { return; }
+	DeviceGuard g(b->ctx->device);
+	(void)hipStreamSynchronize(b->ctx->stream);
+	mscomp_amd_plan_destroy(b->cplan); mscomp_amd_plan_destroy(b->dplan);
+	b->tab.release(); b->stage.release();
+	delete b;                                              // (crun / drun give up their graphs)
+}
+
+uint64_t mscomp_amd_blocks_bound(const mscomp_amd_blocks* b) { return b ? b->n_blocks : 0; }
+
+MSCompStatus mscomp_amd_blocks_compress(mscomp_amd_blocks* b, const uint8_t* d_in, const uint64_t* d_res_off, const uint64_t* d_res_len,
+                                        uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_block_first, uint64_t* d_block_off, int32_t* d_status)
+{
+	if (!b || !d_block_first || !d_block_off || (b->n_res && (!d_res_off || !d_res_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (b->in_total_max && (!d_in || !d_packed)) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = b->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (b->cplan) { b->cplan->ran = true; }
+	const void* args[8] = { d_in, d_res_off, d_res_len, d_packed, reinterpret_cast<const void*>((uintptr_t)packed_cap), d_block_first, d_block_off, d_status };
+	return plan_run(&b->crun, args, [&] {
+		const BlocksTab& t = b->t;
+		uint8_t* stage = static_cast<uint8_t*>(b->stage.p);
+		{ KernelTimer k(c, "bk_ctables"); launch_blocks_ctables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_off, d_res_len, d_block_first, t); }
+		if (b->cplan) { dev_launch(b->cplan, d_in, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		{ KernelTimer k(c, "bk_select_kernel"); launch_blocks_select(c->stream, b->n_res, b->n_blocks, packed_cap, d_in, stage, d_block_first, t, d_block_off, d_status); }
+		{ KernelTimer k(c, "cpd_copy_kernel"); launch_pack_ptrs(c->stream, b->n_blocks, t.aux_b, t.aux_a, d_block_off, d_packed, packed_cap, c->cpd_blocks); }
+	});
+}
+
+MSCompStatus mscomp_amd_blocks_decompress(mscomp_amd_blocks* b, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
+                                          const uint64_t* d_block_off, const uint64_t* d_res_len, const uint64_t* d_range,
+                                          uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!b || !d_block_first || !d_block_off || (b->n_res && (!d_res_len || !d_out_off || !d_out_cap || !d_out_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (b->in_total_max && (!d_packed || !d_out)) { return MSCOMP_ARG_ERROR; }
+	if (b->n_res == 0) { return MSCOMP_OK; }               // (nothing to report on)
+	mscomp_amd_ctx* c = b->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (b->dplan) { note_modes(b->dplan); b->dplan->ran = true; }
+	const void* args[11] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_range,
+	                         d_out, d_out_off, d_out_cap, d_out_len, d_status };
+	return plan_run(&b->drun, args, [&] {
+		const BlocksTab& t = b->t;
+		{ KernelTimer k(c, "bk_dtables"); launch_blocks_dtables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, packed_len, d_res_len, d_block_first, d_block_off,
+		                                                        d_range, d_out_off, d_out_cap, t); }
+		if (b->dplan) { dev_launch(b->dplan, d_packed, t.in_off, t.in_len, d_out, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		{ KernelTimer k(c, "bk_rawcopy_kernel"); launch_blocks_rawcopy(c->stream, b->n_blocks, b->shift, d_packed, d_out, t, c->cpd_blocks); }
+		{ KernelTimer k(c, "bk_dfold_kernel"); launch_blocks_dfold(c->stream, b->n_res, t, d_out_len, d_status); }
+	});
+}
+
+// The checksums of a container: both calls are a table pass of their own, the CRC table pass and the CRC kernel over the blocks as units
+// (crc32.hip), on the container's tables -- every column is a temporary of one call, so the ones compress and decompress use serve here too:
+//   crc     t.unit_first = block_first, t.in_off / t.in_len = the blocks (bk_cunits_kernel), t.aux_a .. = cum (m + 1), t.act = resource of a block,
+//           t.ulen = the resource's bytes behind it, t.ucrc = x^(8 times that), t.res_a .. = the running sum the resources' seeds are made with (n + 1)
+//   check   t.unit_first / t.res_b = units and first block of the clipped ranges, t.in_off / t.in_len = the blocks in d_out, t.ulen = their entry
+//           of d_block_crc, t.aux_a .. = cum, t.ucrc = what was read
+MSCompStatus mscomp_amd_blocks_crc(mscomp_amd_blocks* b, const uint8_t* d_data, const uint64_t* d_res_off, const uint64_t* d_res_len,
+                                   uint32_t* d_block_crc, uint32_t* d_res_crc, int32_t* d_status)
+{
+	if (!b || (b->n_blocks && !d_block_crc) || (b->n_res && (!d_res_off || !d_res_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (b->in_total_max && !d_data) { return MSCOMP_ARG_ERROR; }
+	if (b->n_res == 0) { return MSCOMP_OK; }               // (no resource, no block: n_blocks_max is 0 too)
+	mscomp_amd_ctx* c = b->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[6] = { d_data, d_res_off, d_res_len, d_block_crc, d_res_crc, d_status };
+	return plan_run(&b->krun, args, [&] {
+		const BlocksTab& t = b->t;
+		{ KernelTimer k(c, "bk_ctables"); launch_blocks_ctables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_off, d_res_len, t.unit_first, t); }
+		{ KernelTimer k(c, "bk_crcgroups_kernel"); launch_blocks_crcgroups(c->stream, b->n_res, b->n_blocks, b->shift, d_res_len, t.unit_first, t); }
+		// the resources' statuses and seeds (the check of bk_cres_kernel once more, with the seed of an empty unit for a rejected resource), then the blocks' seeds and factors
+		crc_seeds(c, b->n_res, b->in_total_max, d_res_len, t.res_a, d_status, d_res_crc, nullptr, nullptr);
+		crc_seeds(c, b->n_blocks, ~(u64)0, t.in_len, t.aux_a, nullptr, d_block_crc, t.ulen, d_res_crc ? t.ucrc : nullptr);
+		{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, b->n_blocks, d_data, t.in_off, t.aux_a, d_block_crc, t.act, t.ucrc, d_res_crc, c->crc_blocks); }
+	});
+}
+
+MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* b, const uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_res_len,
+                                     const uint64_t* d_block_first, const uint64_t* d_range, const uint32_t* d_block_crc,
+                                     uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!b || !d_block_first || (b->n_blocks && !d_block_crc) || (b->n_res && (!d_out_off || !d_res_len || !d_out_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (b->in_total_max && !d_out) { return MSCOMP_ARG_ERROR; }
+	if (b->n_res == 0) { return MSCOMP_OK; }
+	mscomp_amd_ctx* c = b->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[8] = { d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status };
+	return plan_run(&b->vrun, args, [&] {
+		const BlocksTab& t = b->t;
+		{ KernelTimer k(c, "bk_ktables"); launch_blocks_ktables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_len, d_block_first, d_range, d_out_off, d_status, t); }
+		crc_pass(c, b->n_blocks, d_out, t.in_off, t.in_len, t.aux_a, t.ucrc);
+		{ KernelTimer k(c, "bk_kfold_kernel"); launch_blocks_kfold(c->stream, b->n_res, d_block_crc, t, d_out_len, d_status); }
+	});
+}
+
+// ---- block readers and writers (include/mscomp_amd.h; kernels: reader.hip, writer.hip) ----
+// What a reader is and a writer starts from: one inner decompress dev plan over blocks_max units within blocks_max B bytes on either
+// side, the cache those units are decoded into and its own tables. Everything is sized by what one call may touch, nothing by what the
+// container holds but the 4 bytes per entry of its block table. A call runs the inner plan's launches (dev_launch) and the CRC kernels
+// between its own passes, through plan_run with a record of its own (run), as a container does.
+struct BlockAccess {
+	mscomp_amd_ctx* ctx = nullptr;
+	MSCompFormat format = MSCOMP_NONE;
+	uint32_t shift = 0, n_res = 0, nbt = 0, n_req = 0, m = 0;   // block_size = 1 << shift; nbt = n_blocks_table; m = blocks_max
+	mscomp_amd_plan* dplan = nullptr;                  // (null when blocks_max is 0)
+	mscomp_amd_plan run;
+	DevBuf tab, cache;                                 // ReaderTab, a writer's extras behind it; blocks_max slots of block_size bytes
+	ReaderTab t{};
+	bool ran = false;
+};
+struct mscomp_amd_reader : BlockAccess {};
+// A writer adds an inner compress dev plan over the same units (a dirty block is compressed from its cache slot into its staging slot), the
+// staging area and three more columns. Its call runs the reader's passes up to the fold, then its own.
+struct mscomp_amd_writer : BlockAccess {
+	mscomp_amd_plan* cplan = nullptr;                  // (null when blocks_max is 0)
+	DevBuf stage;                                      // blocks_max slots of block_size bytes
+	uint32_t* head = nullptr; uint32_t* next = nullptr; uint32_t* dirty = nullptr;   // the rest of WriterTab
+};
+
+// a's columns from `base` on, a writer's (w, else null) behind the reader's; returns where they end: from a null base, their bytes
+static uintptr_t access_tab(BlockAccess* a, mscomp_amd_writer* w, void* base)
+{
+	const size_t n = a->n_req, m = a->m, nbt = a->nbt;
+	Carve k{reinterpret_cast<uintptr_t>(base)};
+	ReaderTab& t = a->t;
+	t.q_off = k.q(n); t.q_want = k.q(n); t.q_j0 = k.q(n); t.q_len = k.q(n); t.unit_first = k.q(n + 1);
+	t.in_off = k.q(m); t.in_len = k.q(m); t.out_off = k.q(m); t.out_cap = k.q(m); t.ulen = k.q(m); t.src = k.q(m); t.clen = k.q(m); t.cum = k.q(m + 1);
+	t.q_stat = k.i(n); t.ustat = k.i(m);
+	t.act = k.w(m); t.owner = k.w(m); t.uq = k.w(m); t.ublk = k.w(m); t.ucrc = k.w(m);
+	t.own = k.w(nbt); t.cnt = k.w(w ? 4 : 2);
+	if (w) { w->next = k.w(m); w->dirty = k.w(m); w->head = k.w(nbt); }
+	return k.at;
+}
+
+// everything a (may be null) holds on the device, and a writer's too (the caller deletes the object)
+static void access_destroy(BlockAccess* a, mscomp_amd_writer* w)
+{
+	if (!a) { return; }
+	DeviceGuard g(a->ctx->device);
+	(void)hipStreamSynchronize(a->ctx->stream);
+	mscomp_amd_plan_destroy(a->dplan);
+	if (w) { mscomp_amd_plan_destroy(w->cplan); w->stage.release(); }
+	a->tab.release(); a->cache.release();
+}
+// Both creates, from the checks on: a is the caller's new object (null: out of memory, said where the caller would have found out), w the
+// same object when it is a writer. On failure nothing is held.
+static MSCompStatus access_create(BlockAccess* a, mscomp_amd_writer* w, mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res,
+                                  uint64_t n_blocks_table, size_t n_req, uint64_t blocks_max, uint32_t flags)
+{
+	if (!create_args_ok(c, format, block_size, flags) || !count_ok(n_res) || !count_ok(n_blocks_table) || !count_ok(n_req) || !count_ok(blocks_max)) { return MSCOMP_ARG_ERROR; }
+	const uint64_t M = blocks_max, bytes = M * block_size;                // (< 2^50)
+	uint64_t I = 0, chunks = 0, toks = 0, cands = 0;
+	if (!decode_dev_counts(format, M, bytes, bytes, false, I, chunks, toks, cands)) { return MSCOMP_MEM_ERROR; }   // (what the inner plan would refuse: checked before the context is used)
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (!a) { return MSCOMP_MEM_ERROR; }
+	a->ctx = c; a->format = format; a->shift = (uint32_t)__builtin_ctz(block_size); a->n_res = (uint32_t)n_res; a->nbt = (uint32_t)n_blocks_table;
+	a->n_req = (uint32_t)n_req; a->m = (uint32_t)M;
+	a->run.ctx = c; a->run.n_units = (uint32_t)n_req;
+	MSCompStatus st = MSCOMP_OK;
+	if (!a->tab.reserve(access_tab(a, w, nullptr) + 64) || (M && (!a->cache.reserve(bytes + 64) || (w && !w->stage.reserve(bytes + 64))))) { st = MSCOMP_MEM_ERROR; }
+	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, bytes, bytes, &a->dplan); }
+	if (st == MSCOMP_OK && M && w) { st = mscomp_amd_plan_create_compress_dev(c, format, M, bytes, block_size, &w->cplan); }   // (fixes the LZNT1 dictionary flavour)
+	if (st != MSCOMP_OK) { (void)hipGetLastError(); access_destroy(a, w); return st; }
+	access_tab(a, w, a->tab.p);
+	return MSCOMP_OK;
+}
+// units, distinct blocks, and the decoded (a reader) or re-encoded (a writer) blocks of a's last execution (read back; none before the first,
+// none for a table a writer refused)
+static int access_counts(BlockAccess* a, mscomp_amd_writer* w, uint32_t out[3])
+{
+	if (!a || !out) { return -1; }
+	DeviceGuard g(a->ctx->device);
+	if (!g.ok || hipStreamSynchronize(a->ctx->stream) != hipSuccess) { return -1; }
+	out[0] = out[1] = out[2] = 0;
+	if (!a->ran) { return 0; }
+	uint64_t units = 0;
+	uint32_t cnt[4] = {};
+	if (hipMemcpy(&units, a->t.unit_first + a->n_req, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (hipMemcpy(cnt, a->t.cnt, w ? 16 : 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (!w || (cnt[3] == 0 && a->m)) { out[0] = (uint32_t)units; out[1] = cnt[0]; out[2] = cnt[w ? 2 : 1]; }
+	return 0;
+}
+
+// The reader's front passes, which a writer runs too. Admission: checks 1-5 per request (d_out_cap null: without the capacity rule, a
+// writer's admission), then one owner per covering block and the inner plan's unit tables.
+static void access_admit(BlockAccess* a, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first, const uint64_t* d_block_off,
+                         const uint64_t* d_res_len, const uint64_t* d_req, const uint64_t* d_out_cap)
+{
+	mscomp_amd_ctx* c = a->ctx;
+	{ KernelTimer k(c, "rd_req_kernel"); launch_reader_requests(c->stream, a->n_req, a->n_res, a->nbt, a->m, a->shift, d_res_len, d_block_first, d_req, d_out_cap, a->t); }
+	{ KernelTimer k(c, "rd_units"); launch_reader_units(c->stream, a->n_req, a->nbt, a->m, a->shift, packed_len, d_packed, static_cast<uint8_t*>(a->cache.p), d_block_off, a->t); }
+}
+// Decode and judge: the owners' blocks decoded into the cache, checksummed (d_block_crc may be null), then status and length per request.
+static void access_decode(BlockAccess* a, const uint8_t* d_packed, const uint32_t* d_block_crc, uint64_t* d_len, int32_t* d_status)
+{
+	mscomp_amd_ctx* c = a->ctx;
+	const ReaderTab& t = a->t;
+	if (a->dplan) { dev_launch(a->dplan, d_packed, t.in_off, t.in_len, static_cast<uint8_t*>(a->cache.p), t.out_off, t.out_cap, t.ulen, t.ustat); }
+	if (d_block_crc && a->m) { crc_pass(c, a->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }   // the owners' blocks lie under two bases: their addresses go in as offsets from a null one
+	if (a->n_req) { KernelTimer k(c, "rd_fold_kernel"); launch_reader_fold(c->stream, a->n_req, d_block_crc, t, d_len, d_status); }
+}
+
+MSCompStatus mscomp_amd_reader_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_req,
+                                      uint64_t blocks_max, uint32_t flags, mscomp_amd_reader** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	std::unique_ptr<mscomp_amd_reader> r(new (std::nothrow) mscomp_amd_reader());
+	const MSCompStatus st = access_create(r.get(), nullptr, c, format, block_size, n_res, n_blocks_table, n_req, blocks_max, flags);
+	if (st == MSCOMP_OK) { *out = r.release(); }
+	return st;
+}
+void mscomp_amd_reader_destroy(mscomp_amd_reader* r)
+{
+	access_destroy(r, nullptr);
+	delete r;                                              // (run gives up its graph)
+}
+
+MSCompStatus mscomp_amd_reader_read(mscomp_amd_reader* r, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
+                                    const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_req,
+                                    uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!r || !d_block_first || !d_block_off || (r->n_res && !d_res_len)) { return MSCOMP_ARG_ERROR; }
+	if (r->n_req && (!d_req || !d_out_off || !d_out_cap || !d_out_len || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if (r->m && (!d_packed || !d_out)) { return MSCOMP_ARG_ERROR; }
+	if (r->n_req == 0) { return MSCOMP_OK; }               // (nothing to report on)
+	mscomp_amd_ctx* c = r->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (r->dplan) { note_modes(r->dplan); r->dplan->ran = true; }
+	r->ran = true;
+	const void* args[12] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
+	                         d_out, d_out_off, d_out_cap, d_out_len, d_status };
+	return plan_run(&r->run, args, [&] {
+		access_admit(r, d_packed, packed_len, d_block_first, d_block_off, d_res_len, d_req, d_out_cap);
+		access_decode(r, d_packed, d_block_crc, d_out_len, d_status);
+		{ KernelTimer k(c, "rd_gather_kernel"); launch_reader_gather(c->stream, r->n_req, r->m, r->shift, d_out, d_out_off, r->t, c->cpd_blocks); }
+	});
+}
+
+int mscomp_amd_reader_counts(mscomp_amd_reader* r, uint32_t out[3]) { return access_counts(r, nullptr, out); }
+
+MSCompStatus mscomp_amd_writer_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_req,
+                                      uint64_t blocks_max, uint32_t flags, mscomp_amd_writer** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	std::unique_ptr<mscomp_amd_writer> w(new (std::nothrow) mscomp_amd_writer());
+	const MSCompStatus st = access_create(w.get(), w.get(), c, format, block_size, n_res, n_blocks_table, n_req, blocks_max, flags);
+	if (st == MSCOMP_OK) { *out = w.release(); }
+	return st;
+}
+void mscomp_amd_writer_destroy(mscomp_amd_writer* w)
+{
+	access_destroy(w, w);
+	delete w;                                              // (run gives up its graph)
+}
+
+MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* w, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
+                                     const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_req,
+                                     const uint8_t* d_src, const uint64_t* d_src_off, uint8_t* d_new_packed, uint64_t new_cap, uint64_t* d_new_block_off,
+                                     uint32_t* d_new_block_crc, uint64_t* d_written, int32_t* d_status, int32_t* d_res_status)
+{
+	if (!w || !d_block_first || !d_block_off || !d_new_block_off || (w->n_res && (!d_res_len || !d_res_status))) { return MSCOMP_ARG_ERROR; }
+	if (w->n_req && (!d_req || !d_src_off || !d_written || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if ((w->m && !d_src) || ((w->m || w->nbt) && (!d_packed || !d_new_packed))) { return MSCOMP_ARG_ERROR; }
+	if ((d_block_crc == nullptr) != (d_new_block_crc == nullptr)) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = w->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (w->dplan) { note_modes(w->dplan); w->dplan->ran = true; w->cplan->ran = true; }
+	w->ran = true;
+	const void* args[16] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
+	                         d_src, d_src_off, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_off, d_new_block_crc,
+	                         d_written, d_status, d_res_status };
+	return plan_run(&w->run, args, [&] {
+		const ReaderTab& t = w->t;
+		const WriterTab wt = { t, w->head, w->next, w->dirty };
+		uint8_t* cache = static_cast<uint8_t*>(w->cache.p); uint8_t* stage = static_cast<uint8_t*>(w->stage.p);
+		// the reader's passes: admission (without its capacity rule), owners, the owners' blocks decoded, checksummed and judged
+		access_admit(w, d_packed, packed_len, d_block_first, d_block_off, d_res_len, d_req, nullptr);
+		{ KernelTimer k(c, "wr_link"); launch_writer_link(c->stream, w->n_req, w->nbt, w->m, wt); }
+		access_decode(w, d_packed, d_block_crc, d_written, d_status);
+		// the writer's own: patch, re-encode and checksum the dirty blocks, lay out, move
+		{ KernelTimer k(c, "wr_patch"); launch_writer_patch(c->stream, w->n_req, w->m, w->shift, d_src, d_src_off, cache, wt, c->cpd_blocks); }
+		if (w->cplan) { dev_launch(w->cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (d_block_crc && w->m) { crc_pass(c, w->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }
+		{ KernelTimer k(c, "wr_layout_kernel"); launch_writer_layout(c->stream, w->n_req, w->n_res, w->nbt, w->m, packed_len, new_cap, d_block_first, d_block_off, d_block_crc,
+		                                                             wt, d_new_block_off, d_new_block_crc, d_written, d_status, d_res_status); }
+		{ KernelTimer k(c, "wr_move_kernel"); launch_writer_move(c->stream, w->nbt, w->shift, new_cap, d_packed, d_block_off, stage, cache, d_new_block_off, wt, d_new_packed, c->cpd_blocks); }
+	});
+}
+
+int mscomp_amd_writer_counts(mscomp_amd_writer* w, uint32_t out[3]) { return access_counts(w, w, out); }

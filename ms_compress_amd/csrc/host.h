@@ -1,0 +1,183 @@
+// host.h -- what the host files of the library share (api.hip, blockobj.hip): the context, the plan, their helpers and plan_run.
+// Internal: not installed, not part of include/. What it adds to namespace msc is not exported from the library (hidden visibility).
+#pragma once
+#include "../../include/mscomp_amd.h"
+#include "kernels.h"
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+namespace msc {
+
+// the process-wide half of a captured graph's age (api.hip defines it, beside the test hooks that bump it): ONE object for all host files
+extern std::atomic<uint64_t> g_mode_epoch;
+
+struct DevBuf {
+	void* p = nullptr; size_t cap = 0;
+	uint64_t* epoch = nullptr;                         // the owning context's epoch (null for plan-owned tables)
+	bool reserve(size_t n)
+	{
+		if (n <= cap) { return true; }
+		if (epoch) { ++*epoch; }
+		if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+		const size_t want = n + n / 8 + 256;
+		if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return false; }
+		cap = want; return true;
+	}
+	void release() { if (p) { (void)hipFree(p); if (epoch) { ++*epoch; } } p = nullptr; cap = 0; }
+};
+
+struct ProfRec { const char* name; hipEvent_t a, b; };
+
+} // namespace msc
+#pragma GCC visibility pop
+
+struct mscomp_amd_ctx {
+	int device = 0;
+	uint32_t cpd_blocks = 0;                           // the fixed grid of mscomp_amd_compact_dev on this device (asked once, here: never inside a capture)
+	uint32_t crc_blocks = 0;                           // ... and that of the CRC kernel (crc32.hip)
+	hipStream_t stream = nullptr;
+	msc::DevBuf slots, slot_size, prefix, tile_sums;   // chunk scratch (grow-only, shared by all plans of the ctx)
+	msc::DevBuf lzrec;                                 // LZNT1 parse records per chunk (LZNT1_REC bytes: match tokens per window)
+	msc::DevBuf links, lasthead, mlen3, moff;          // Xpress-family match finder scratch (per 64 KiB link chunk)
+	msc::DevBuf wtok, wmat, wfar;                      // Xpress parse records per 64-position window (token mask, match mask, far length)
+	msc::DevBuf wrec, sbrec;                           // ... state / counts / prefixes per window (6 x u32), per super-block (tot 4 x u32, pre 3 x u64, seams)
+	msc::DevBuf tokbits, counts, extra, lens, codes, fb_list, fbflag;   // Xpress+Huffman per-chunk scratch
+	msc::DevBuf dz_cin, dz_csize, dz_unit;             // LZNT1 decompression: header offset / decoded size per chunk slot, per-unit records
+	msc::DevBuf dz_scr;                                // Xpress+Huffman decompression: token scratch of the candidates of multi-chunk buffers
+	msc::DevBuf dz_tok, dz_ntok, dz_xhc;               // Xpress+Huffman decompression: 32-bit tokens of every unit, token counts, candidate chunk records
+	msc::DevBuf lzg_bsum, lzg_dir, lzg_words;          // tokens -> bytes of large units by all CUs (lzglobal.hip): token block sums, tile directory, a word per output byte + pass counters
+	msc::DevBuf xps_buf;                               // large Xpress streams by segments: segment records | mode per stream | done per unit
+	msc::DevBuf cp_tab;                                // compaction: out_off (u64) | tile_prefix (u32) of the batch being packed
+	msc::DevBuf one_in, one_out, one_meta;             // staging of the host-pointer one-shot path
+	void* h_tab = nullptr; size_t h_tab_cap = 0;       // pinned staging of a plan's tables: they go up stream-ordered, plan_create does not wait for the stream
+	hipEvent_t h_tab_ev = nullptr; bool h_tab_busy = false;   // (a stream that shares a hardware queue with a busy one would make that wait as long as the other's kernels)
+	std::vector<msc::DevBuf> table_pool;               // table buffers of destroyed plans, reused by the next plan (hipFree waits for the whole device: it would stall pipelines that create a plan per batch)
+	uint64_t epoch = 1;                                // bumped when one of the buffers above moves (captured graphs are stale then)
+	int lznt1_sa = -1;                                 // LZNT1 dictionary flavour of the plans this context creates: -1 = the process default at plan creation, 0 / 1 = set for this context
+	const uint32_t* dbg_mode = nullptr; uint32_t dbg_mode_n = 0;   // where the last decompress / size execution left its per-unit path verdicts (mscomp_amd_debug_decode_modes)
+	const uint32_t* dbg_lzg_open = nullptr;            // the open-word counters of the last execution when a dev plan with large units ran it (they lie behind the words of its BOUND)
+	const uint32_t* dbg_mode_cnt = nullptr;            // ... and, for a dev plan with large units, where its path pass left their number (device memory; dbg_mode_n is then the bound)
+	bool profiling = false;
+	std::vector<msc::ProfRec> recs;
+	std::vector<hipEvent_t> free_events;
+	std::vector<msc::DevBuf*> bufs()
+	{
+		return { &slots, &slot_size, &prefix, &tile_sums, &lzrec, &links, &lasthead, &mlen3, &moff, &wtok, &wmat, &wfar, &wrec, &sbrec,
+		         &tokbits, &counts, &extra, &lens, &codes, &fb_list, &fbflag, &dz_cin, &dz_csize, &dz_unit, &dz_tok, &dz_ntok, &dz_xhc, &dz_scr,
+		         &lzg_bsum, &lzg_dir, &lzg_words, &xps_buf, &cp_tab, &one_in, &one_out, &one_meta };
+	}
+	mscomp_amd_ctx() { for (msc::DevBuf* b : bufs()) { b->epoch = &epoch; } }
+};
+
+struct mscomp_amd_plan {
+	mscomp_amd_ctx* ctx = nullptr;
+	MSCompFormat format = MSCOMP_NONE;
+	bool decompress = false;
+	bool sizing = false;                               // a decompressed-size plan (mscomp_amd_plan_create_size): out_cap holds the limits, nothing is decoded
+	bool dev = false;                                  // a plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev / _compress_dev; with sizing: _size_dev)
+	bool crc = false;                                  // a CRC plan (mscomp_amd_plan_create_crc_dev): a dev plan without a format; tables = cum (u64 x (n_units + 1)) | off (u64 x n_units)
+	bool large = false;                                // ... with MSCOMP_AMD_DEV_LARGE_UNITS: the tables of the optional paths are built there too (xhc_scr, lzg_*, xps_big / xps_seg hold the bounds
+	                                                   // they were reserved for, 0 = the path is off for the plan; the counts of an execution are in xps_cnt / lzg_cnt, device memory)
+	uint32_t* xps_cnt = nullptr; uint32_t* lzg_cnt = nullptr;   // (behind the prefix arrays of xps_tab / lzg_tab)
+	uint64_t in_total_max = 0, out_total_max = 0;      // ... and the bounds its scratch was reserved for
+	uint32_t n_units = 0, n_chunks = 0;
+	uint64_t total_in = 0, max_unit = 0;               // (max_unit of a compress dev plan: the largest unit it takes)
+	bool lznt1_sa = false;                             // LZNT1: the suffix-array dictionary flavour -- fixed when the plan is created: a plan never changes its bytes under a running caller
+	bool matches_ready = false;                        // the caller has run the links + find kernels of this execution itself, range by range (the pipelined one-shot call): compress_launch skips them once
+	bool no_graph = false;                             // one-shot plans run with changing buffer addresses: a captured graph would be re-captured every time
+	msc::DevBuf tables;                                // in_off | in_len | out_off | out_cap | chunk_prefix; dev plans: what their table pass writes (reserve_dev_tables)
+	msc::DevBuf tokpre;                                // decompression by tokens (host plans): first token slot | first candidate slot | first token-scratch slot of every unit (n_units + 1 u64 each)
+	uint32_t xhc_slots = 0;                            // candidate chunk slots of the batch
+	uint64_t xhc_scr = 0;                              // token-scratch slots (candidates of multi-chunk buffers), 0 = none
+	msc::DevBuf lzg_tab;                               // lzglobal.hip: unit (u32 x n_big, padded) | tb_prefix | tile_prefix | word_prefix (u64 x (n_big + 1) each)
+	uint32_t lzg_big = 0, lzg_tb = 0, lzg_tiles = 0;   // units taken by that path (0: not used), their token blocks and tiles
+	uint64_t lzg_words = 0;
+	msc::DevBuf xps_tab;                               // xps_*: unit (u32 x n_big, padded) | seg_prefix (u64 x (n_big + 1))
+	uint32_t xps_big = 0, xps_seg = 0, xps_seg_bytes = 0, xps_warm_bytes = 0;
+	// what the launch code reads, resolved when the plan is created (the launch functions do not know where a creator put it): the columns of
+	// `tables`; the prefixes, in tokpre for host plans and in `tables` for dev plans; reject (u32 x n_units), written by a dev plan's table pass
+	msc::BatchTables bt{};
+	msc::u64* tok_prefix = nullptr; msc::u64* cand_prefix = nullptr; msc::u64* scr_prefix = nullptr;
+	uint32_t* reject = nullptr;
+	// the plan's launch sequence as a hipGraph (plan_run): captured on the plan's second execution, replayed while the
+	// arguments and the scratch buffers stay where they were
+	hipGraphExec_t gexec = nullptr;
+	const void* g_args[16] = {};                       // (api.hip: a host plan's four pointers, a dev plan's eight, a size dev plan's seven; blockobj.hip: a block container's eight and eleven; a block reader's twelve; a block writer's sixteen)
+	uint64_t g_epoch = 0, g_mode = 0;
+	uint32_t executions = 0;
+	bool ran = false;                                  // executed at least once (mscomp_amd_debug_plan_paths: a dev plan's counts are those of its last execution)
+	// (on the plan's device, its stream idle. mscomp_amd_plan_destroy hands `tables` to the context's pool first)
+	~mscomp_amd_plan() { if (gexec) { (void)hipGraphExecDestroy(gexec); } tables.release(); tokpre.release(); lzg_tab.release(); xps_tab.release(); }
+};
+
+#pragma GCC visibility push(hidden)
+namespace msc {
+
+struct DeviceGuard {
+	int prev = -1; bool ok = true;
+	explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; } if (prev != dev) { ok = hipSetDevice(dev) == hipSuccess; } }
+	~DeviceGuard() { int cur = -1; if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) { (void)hipSetDevice(prev); } }
+};
+
+inline hipEvent_t get_event(mscomp_amd_ctx* c)
+{
+	if (!c->free_events.empty()) { hipEvent_t e = c->free_events.back(); c->free_events.pop_back(); return e; }
+	hipEvent_t e = nullptr; (void)hipEventCreate(&e); return e;
+}
+struct KernelTimer {
+	mscomp_amd_ctx* c; ProfRec r;
+	KernelTimer(mscomp_amd_ctx* ctx, const char* name) : c(ctx), r{name, nullptr, nullptr}
+	{ if (c->profiling) { r.a = get_event(c); r.b = get_event(c); (void)hipEventRecord(r.a, c->stream); } }
+	~KernelTimer() { if (c->profiling) { (void)hipEventRecord(r.b, c->stream); c->recs.push_back(r); } }
+};
+
+// defined in api.hip, where their comments are
+bool test_hooks_on();
+void note_modes(mscomp_amd_plan* p);
+bool decode_dev_counts(MSCompFormat format, uint64_t N, uint64_t in_total_max, uint64_t O, bool sizing, uint64_t& I, uint64_t& chunks, uint64_t& toks, uint64_t& cands);
+void dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status);
+
+// One execution of a plan: its launches, given as `launch`. A plan that is executed repeatedly replays them as one hipGraph (the gaps between
+// the 4-9 launches are ~3 % of an LZNT1 pass): captured on the second execution and again whenever a pointer (args), the ctx scratch or a
+// kernel switch moved. Plain launches instead: on the first execution (one-time function attributes are set there), while profiling (the
+// per-kernel events are not part of a graph), with MSCOMP_AMD_NO_GRAPH, for no_graph plans, and while the caller captures the ctx stream (the
+// launches then go into the caller's graph; a stream whose capture state cannot be read counts as captured). Only executions that may replay
+// are counted.
+extern "C++" template <class Launch, size_t N>
+static MSCompStatus plan_run(mscomp_amd_plan* p, const void* const (&args)[N], const Launch& launch)
+{
+	static_assert(N <= sizeof p->g_args / sizeof p->g_args[0], "g_args holds the arguments of every caller");
+	mscomp_amd_ctx* c = p->ctx;
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
+	static const bool no_graph = getenv("MSCOMP_AMD_NO_GRAPH") != nullptr;
+	if (cs == hipStreamCaptureStatusNone && !no_graph && !p->no_graph && !c->profiling && p->n_units && ++p->executions >= 2) {
+		const uint64_t mode_now = g_mode_epoch.load(std::memory_order_acquire);
+		const bool same = p->gexec && p->g_epoch == c->epoch && p->g_mode == mode_now && memcmp(p->g_args, args, sizeof args) == 0;
+		if (!same) {
+			if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
+			hipGraph_t graph = nullptr;
+			if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+				launch();
+				const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
+				if (ee == hipSuccess && graph && hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0) == hipSuccess) {
+					p->g_epoch = c->epoch; p->g_mode = mode_now; memcpy(p->g_args, args, sizeof args);
+				} else { p->gexec = nullptr; }
+				if (graph) { (void)hipGraphDestroy(graph); }
+			}
+			(void)hipGetLastError();
+		}
+		if (p->gexec) { return hipGraphLaunch(p->gexec, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
+	}
+	launch();
+	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
+}
+
+} // namespace msc
+#pragma GCC visibility pop
