@@ -543,8 +543,9 @@ int          mscomp_amd_reader_counts(mscomp_amd_reader* rd, uint32_t out[3]);
  *                 (MSCOMP_ARG_ERROR; MSCOMP_MEM_ERROR where blocks_max B bytes are more than a dev plan can address), flags 0, *wr cleared
  *                 on failure. All scratch is reserved here, once, and never grows: a block cache of blocks_max B bytes, a staging area of
  *                 blocks_max B bytes, a decompress and a compress dev plan for blocks_max units within blocks_max B bytes each, and the
- *                 writer's tables: 96 bytes per unit of blocks_max, 44 per request, 8 per entry of the block table. The LZNT1 dictionary
- *                 flavour is fixed here, as for mscomp_amd_blocks_create.
+ *                 writer's tables: 96 bytes per unit of blocks_max, 44 per request, 8 per entry of the block table and -- for
+ *                 mscomp_amd_writer_resize -- 12 per resource + 8. The LZNT1 dictionary flavour is fixed here, as for
+ *                 mscomp_amd_blocks_create.
  *   Out of place: the old container is d_packed (packed_len valid bytes), d_block_off (n_blocks_table + 1) and d_block_crc (n_blocks_table,
  *                 may be NULL); it is only read. The new one goes to d_new_packed (nothing at or behind new_cap), d_new_block_off
  *                 (n_blocks_table + 1) and d_new_block_crc (n_blocks_table; NULL exactly when d_block_crc is), which must not overlap the
@@ -580,7 +581,8 @@ int          mscomp_amd_reader_counts(mscomp_amd_reader* rd, uint32_t out[3]);
  *                      MSCOMP_OK. A stored block is never longer than its data, so new_cap = the sum of the data lengths never refuses.
  *                 Consequence: when the old container was written by mscomp_amd_blocks_compress and all its blocks are healthy, the new
  *                 one is byte for byte what mscomp_amd_blocks_compress and mscomp_amd_blocks_crc write for the patched data.
- *                 Resource checksums (mscomp_amd_blocks_crc's d_res_crc) are not maintained; a resource cannot grow or shrink.
+ *                 A write never changes a resource's length: mscomp_amd_writer_resize below does. Resource checksums
+ *                 (mscomp_amd_blocks_crc's d_res_crc) are not maintained: mscomp_amd_res_crc_dev derives them from the block checksums.
  *   Counts:       mscomp_amd_writer_counts gives, for the last execution, out[0] = units (as a reader's), out[1] = distinct blocks touched,
  *                 out[2] = blocks encoded again (the dirty ones); all 0 after a refused table. Otherwise as mscomp_amd_reader_counts.
  *   Execution:    as the reader's: asynchronous on the ctx stream, kernels only, no allocation, no synchronisation, nothing read back, a
@@ -602,6 +604,83 @@ MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* wr, const uint8_t* d_pac
                                      uint32_t* d_new_block_crc /* NULL exactly when d_block_crc is */,
                                      uint64_t* d_written /* n_req */, int32_t* d_status /* n_req */, int32_t* d_res_status /* n_res */);
 int          mscomp_amd_writer_counts(mscomp_amd_writer* wr, uint32_t out[3]);
+
+/* Resize: the writer's second call, ftruncate beside pread and pwrite. Every resource r gets the length d_want_len[r]: cut there, or
+ * extended with zeros. Out of place as write is: the old container (d_packed, d_block_first, d_block_off, d_res_len, d_block_crc) is only
+ * read, and a new one is written -- d_new_packed (nothing at or behind new_cap), d_new_block_first (n_res + 1), d_new_block_off
+ * (n_blocks_table + 1), d_new_block_crc (n_blocks_table; NULL exactly when d_block_crc is) and d_new_res_len (n_res) --, which must not
+ * overlap the old arrays. Only the block whose data length changes is decoded, and only it and the blocks that did not exist are encoded;
+ * every other kept block is carried as it was stored, at its new place in the table. Appending is resize, then write: two passes over the
+ * container.
+ *   Scratch:      what the writer reserved when it was created: the cache and the staging area (blocks_max B each), both inner dev plans,
+ *                 and the table buffer, of which 12 bytes per resource + 8 serve this call alone.
+ *   Notation:     B the block size, L = d_res_len[r], W = d_want_len[r], n = d_block_first[r + 1] - d_block_first[r] the old block count,
+ *                 n' = W / B + (W % B != 0) the wanted one (no sum is formed that can overflow). For a block k < min(n, n') the old data
+ *                 length is e = min(B, L - k B) and the new one e' = min(B, W - k B); the block is CHANGED when e != e' -- at most one per
+ *                 resource, k = min(n, n') - 1. The blocks n <= k < n' are FRESH, the blocks k >= n' are dropped. The resource costs
+ *                 cnt = (1 if it has a changed block) + max(0, n' - n).
+ *   Rules:        in this order:
+ *                   0. the table as a whole, the writer's rule 0: d_block_first[n_res] must not exceed n_blocks_table and d_block_first
+ *                      must not decrease anywhere. Otherwise every d_res_status is MSCOMP_ARG_ERROR, d_new_block_first, d_new_block_off,
+ *                      d_new_block_crc and d_new_res_len are all 0, and nothing else is written;
+ *                   1. block count: MSCOMP_DATA_ERROR when n is not ceil(L / B). The resource is carried as it is;
+ *                   2. no change: W = L is MSCOMP_OK and costs nothing;
+ *                   3. the budget: the running total of cnt over the resources that passed rules 1 and 2, in resource order, including
+ *                      this one and including refused ones, must not exceed blocks_max; otherwise MSCOMP_ARG_ERROR. A plain prefix sum,
+ *                      as the reader's budget is: once it is exceeded, every later resource that changes is refused, a free cut included;
+ *                   4. readable: a changed block must be readable exactly as the writer's rule 5 demands -- the container's table checks,
+ *                      a decode to e bytes, and with d_block_crc the CRC-32 the table says; otherwise MSCOMP_DATA_ERROR. Fresh blocks
+ *                      need no read;
+ *                   5. a resource refused by rule 1, 3 or 4 is CARRIED: its length stays L, its count stays n, all its blocks are clean;
+ *                   6. new data: a changed block's is the first min(e, e') bytes of its old data, then zeros up to e'; a fresh block's is
+ *                      e' zero bytes. Both are dirty: their stored form follows the rule of mscomp_amd_blocks_compress (every fresh block
+ *                      goes through the compress plan like any other unit) and their CRC-32 is computed again when the arrays are given;
+ *                   7. every other kept block is clean: old entry d_block_first[r] + k becomes new entry d_new_block_first[r] + k with
+ *                      its stored bytes and checksum verbatim; an unreadable clean entry gets the stored length 0 (the writer's rule 8);
+ *                   8. room in the table: nb' = the sum of the final counts, n' for an accepted resource and n for a carried one. When
+ *                      nb' exceeds n_blocks_table the whole call is refused as under rule 0. (Checked where the layout is made, behind
+ *                      rule 4: a carried truncation counts with its old n.)
+ *                   9. the tables: d_new_block_first is the exclusive running count of blocks, d_new_block_first[n_res] = nb';
+ *                      d_new_block_off[0 .. nb'] the running sum of the stored lengths, the entries above nb' repeat the total;
+ *                      d_new_block_crc is 0 at and above nb'; d_new_res_len[r] is W for an accepted resource and L for a carried one;
+ *                  10. capacity, the writer's rule 9: a block that would end beyond new_cap is not written and its resource gets
+ *                      MSCOMP_BUF_ERROR, which replaces whatever status the resource had; the tables still hold the full layout.
+ *                 Consequence: when the old container was written by mscomp_amd_blocks_compress and _crc, is healthy, and every resource
+ *                 is accepted, the new packed bytes, d_new_block_first, d_new_block_off and d_new_block_crc are byte for byte what those
+ *                 two calls write for the resized data. W = 0 drops every block and decodes nothing; L = 0 makes every block fresh.
+ *   Counts:       mscomp_amd_writer_counts after a resize: out[0] = the units (the admitted resources' changed and fresh blocks), out[1] =
+ *                 the blocks decoded (the admitted changed blocks: each is decoded, or read where it lies when stored raw, once), out[2] =
+ *                 the blocks encoded (the accepted resources' units); all 0 after a refused table.
+ *   Execution:    as write: asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation, no synchronisation,
+ *                 nothing read back, a launch sequence fixed by the creation bounds; legal inside a caller's capture from the first
+ *                 execution, a graph of its own -- not write's -- from the second. MSCOMP_ARG_ERROR for a null wr, d_block_first,
+ *                 d_block_off, d_new_block_first or d_new_block_off, a null d_res_len, d_want_len, d_new_res_len or d_res_status when
+ *                 n_res > 0, a null d_packed or d_new_packed unless blocks_max and n_blocks_table are 0, or when exactly one of
+ *                 d_block_crc and d_new_block_crc is null.
+ *   Left out:     resize and write fused in one call; one shared encoding for runs of fresh zero blocks (each is encoded on its own);
+ *                 growth beyond blocks_max B bytes per call. */
+MSCompStatus mscomp_amd_writer_resize(mscomp_amd_writer* wr, const uint8_t* d_packed, uint64_t packed_len,
+                                      const uint64_t* d_block_first, const uint64_t* d_block_off, const uint64_t* d_res_len,
+                                      const uint32_t* d_block_crc /* may be NULL */,
+                                      const uint64_t* d_want_len /* n_res */,
+                                      uint8_t* d_new_packed, uint64_t new_cap,
+                                      uint64_t* d_new_block_first /* n_res + 1 */, uint64_t* d_new_block_off /* n_blocks_table + 1 */,
+                                      uint32_t* d_new_block_crc /* NULL exactly when d_block_crc is */,
+                                      uint64_t* d_new_res_len /* n_res */, int32_t* d_res_status /* n_res */);
+
+/* Resource checksums from block checksums. After a write or a resize the block CRC-32s are current and the resource CRC-32s that
+ * mscomp_amd_blocks_crc once wrote are stale; the block checksums determine them, and no data has to be read:
+ *   d_res_crc[r] = XOR over the resource's blocks j of d_block_crc[j] x^(8 d_j)  (mod the CRC polynomial), d_j = the resource's bytes behind block j
+ * -- zlib's crc32_combine applied along the resource; 0 for an empty resource. d_block_first (n_res + 1, never decreasing: the table a
+ * container wrote), d_res_len (n_res), d_block_crc (n_blocks_table). Per resource: MSCOMP_ARG_ERROR when d_block_first[r] or
+ * d_block_first[r + 1] exceeds n_blocks_table, MSCOMP_DATA_ERROR when the block count is not ceil(L / B); d_res_crc[r] is 0 in both cases.
+ * Two launches: a seed kernel over the resources, then a fixed grid dealt over the BLOCKS of the table -- one resource of a million blocks
+ * spreads over every CU --, each block folded into its resource's word with an atomic XOR. Asynchronous on the ctx stream, no scratch, no
+ * allocation, nothing read back; may be captured. MSCOMP_ARG_ERROR, before the context is used, for a null ctx, a block_size that is not
+ * a power of two from 4096 to 524288, n_res or n_blocks_table above 0x7FFFFFF0, or a null array when n_res > 0. n_res = 0 returns MSCOMP_OK. */
+MSCompStatus mscomp_amd_res_crc_dev(mscomp_amd_ctx* ctx, uint32_t block_size, size_t n_res, uint64_t n_blocks_table,
+                                    const uint64_t* d_block_first, const uint64_t* d_res_len, const uint32_t* d_block_crc,
+                                    uint32_t* d_res_crc /* n_res */, int32_t* d_status /* n_res */);
 
 /* ---- measurement hooks (bench.py / profiles) ---- */
 /* When enabled, every kernel launch of plan_execute is bracketed by hipEvents on the ctx stream. */

@@ -43,6 +43,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_plan_create_crc_dev", "mscomp_amd_plan_execute_crc_dev", "mscomp_amd_blocks_crc", "mscomp_amd_blocks_check",
     "mscomp_amd_reader_create", "mscomp_amd_reader_destroy", "mscomp_amd_reader_read", "mscomp_amd_reader_counts",
     "mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_write", "mscomp_amd_writer_counts",
+    "mscomp_amd_writer_resize", "mscomp_amd_res_crc_dev",
 ]
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 
@@ -168,6 +169,10 @@ def load_library():
     lib.mscomp_amd_writer_write.restype = C.c_int
     lib.mscomp_amd_writer_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.mscomp_amd_writer_counts.restype = C.c_int
+    lib.mscomp_amd_writer_resize.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 5
+    lib.mscomp_amd_writer_resize.restype = C.c_int
+    lib.mscomp_amd_res_crc_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint64] + [C.c_void_p] * 5
+    lib.mscomp_amd_res_crc_dev.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -699,9 +704,10 @@ class BlockWriter(_BlockAccess):
     """A block writer (mscomp_amd_writer_create): batched byte-range writes into a block container, out of place. Made once for ``n_req``
     requests per call that together cover at most ``blocks_max`` blocks (counted per request, before any sharing), against the tables of
     a container of ``n_res`` resources whose d_block_off has ``n_blocks_table`` + 1 entries. All scratch is reserved here: a cache and a
-    staging area of blocks_max blocks each, two inner dev plans, 96 bytes of tables per unit of blocks_max, 44 per request and 8 per
-    block-table entry. write() enqueues kernels on the ctx stream and nothing else (legal inside a capture of that stream). Arguments
-    are torch CUDA tensors: uint8 data, int64 / uint64 tables, int32 statuses and checksums."""
+    staging area of blocks_max blocks each, two inner dev plans, 96 bytes of tables per unit of blocks_max, 44 per request, 8 per
+    block-table entry and 12 per resource. write() and resize() enqueue kernels on the ctx stream and nothing else (legal inside a capture
+    of that stream); for resize() blocks_max bounds the blocks whose data changes: per resource the block the new end falls into, and the
+    blocks that did not exist. Arguments are torch CUDA tensors: uint8 data, int64 / uint64 tables, int32 statuses and checksums."""
     _create, _destroy, _counts = "mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_counts"
 
     def write(self, d_packed, d_block_first, d_block_off, d_res_len, d_req, d_src, d_src_off, d_new_packed, d_new_block_off, d_written, d_status,
@@ -721,8 +727,26 @@ class BlockWriter(_BlockAccess):
                   d_written, d_status, d_res_status)
         _ok(self.ctx.lib.mscomp_amd_writer_write(self._h, p[0], plen, *p[1:9], cap, *p[9:]), "mscomp_amd_writer_write")
 
+    def resize(self, d_packed, d_block_first, d_block_off, d_res_len, d_want_len, d_new_packed, d_new_block_first, d_new_block_off, d_new_res_len,
+               d_res_status, d_block_crc=None, d_new_block_crc=None, packed_len=None, new_cap=None):
+        """Every resource r cut or zero-extended to d_want_len[r] bytes (mscomp_amd_writer_resize), out of place as write(): the new
+        container goes to d_new_packed (nothing at or behind ``new_cap``, default: all of it), d_new_block_first (n_res + 1),
+        d_new_block_off (n_blocks_table + 1), d_new_block_crc (given exactly when d_block_crc is) and d_new_res_len (n_res).
+        d_res_status[r] is MSCOMP_OK, or MSCOMP_DATA_ERROR (a wrong block count, or an unreadable block where the length changes inside
+        it) or MSCOMP_ARG_ERROR (over the budget of blocks_max changed and fresh blocks) with the resource carried as it was, or
+        MSCOMP_BUF_ERROR (a block did not fit below new_cap); all MSCOMP_ARG_ERROR with zeroed tables when the new table needs more than
+        n_blocks_table rows. Only the block the new end falls into is decoded; it and the fresh blocks are encoded."""
+        plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
+        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
+        if d_new_packed is not None and cap > d_new_packed.numel():
+            raise ValueError("new_cap exceeds d_new_packed")
+        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_want_len, d_new_packed, d_new_block_first, d_new_block_off,
+                  d_new_block_crc, d_new_res_len, d_res_status)
+        _ok(self.ctx.lib.mscomp_amd_writer_resize(self._h, p[0], plen, *p[1:7], cap, *p[7:]), "mscomp_amd_writer_resize")
+
     def counts(self):
-        """(units, distinct blocks touched, blocks encoded again) of the last write(); synchronizes the stream."""
+        """(units, distinct blocks touched, blocks encoded again) of the last write(), or (units, changed blocks decoded, blocks encoded) of
+        the last resize(); synchronizes the stream."""
         return self._read_counts()
 
 
@@ -773,6 +797,82 @@ def blocks_write(fmt, packed, block_first, block_off, lengths, block_size, write
     if own:
         ctx.close()
     return new_packed, noff, ncrc, [int(x) for x in h_wr[:nq]], [int(x) for x in h_st[:nq]], [int(x) for x in h_rst[:n]]
+
+
+def blocks_resize(fmt, packed, block_first, block_off, lengths, block_size, new_lengths, ctx=None, block_crc=None):
+    """Cut or zero-extend the resources of a block container to ``new_lengths`` on the GPU (BlockWriter.resize); ``lengths`` are their
+    lengths now, ``block_crc`` as blocks_crc returns it (optional: the block a cut falls into is held to its checksum first, and the new
+    container gets checksums too). Returns numpy arrays and lists (new_packed uint8, new_block_off uint64, new_block_crc uint32 or None,
+    new_first uint64 of n + 1, new_lengths, res_statuses); the tables have as many rows as the resized container needs."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    n = len(lengths)
+    lens, want = [int(x) for x in lengths], [int(x) for x in new_lengths]
+    if len(want) != n:
+        raise ValueError("one new length per resource")
+    B = int(block_size)
+    blocks = lambda x: (x + B - 1) // B
+    # (the block the shorter of the two lengths ends in changes its data length unless that end is a block boundary)
+    budget = sum((1 if min(a, b) % B else 0) + max(0, blocks(b) - blocks(a)) for a, b in zip(lens, want) if a != b)
+    nb_old = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
+    nbt = max(nb_old, sum(blocks(max(a, b)) for a, b in zip(lens, want)))
+    room = sum(max(a, b) for a, b in zip(lens, want))
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        wr = BlockWriter(ctx, fmt, B, n, nbt, 0, budget)
+        packed, d_packed = _dev_packed(packed, dev)
+        d_first, d_boff, d_len, d_want = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, nbt + 1, dev), _dev_u64(lens, 1, dev), _dev_u64(want, 1, dev)
+        d_crc = d_ncrc = None
+        if block_crc is not None:
+            d_crc, d_ncrc = _dev_block_crc(block_crc, nbt, dev), torch.zeros(max(1, nbt), dtype=torch.int32, device=dev)
+        d_new = torch.zeros(room + 16, dtype=torch.uint8, device=dev)
+        d_nfirst = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_noff = torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
+        d_nlen = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
+        d_rst = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        wr.resize(d_packed, d_first, d_boff, d_len, d_want, d_new, d_nfirst, d_noff, d_nlen, d_rst, d_block_crc=d_crc, d_new_block_crc=d_ncrc,
+                  packed_len=len(packed), new_cap=room)
+        ctx.stream.synchronize()
+        nfirst = d_nfirst.cpu().numpy().view(np.uint64).copy()
+        nb = int(nfirst[n])
+        noff = d_noff.cpu().numpy().view(np.uint64)[: nb + 1].copy()
+        new_packed = d_new.cpu().numpy()[: min(int(noff[nb]), room)].copy()
+        ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nb].copy()
+        h_len, h_rst = d_nlen.cpu().numpy().view(np.uint64), d_rst.cpu().numpy()
+        wr.close()
+    if own:
+        ctx.close()
+    return new_packed, noff, ncrc, nfirst, [int(x) for x in h_len[:n]], [int(x) for x in h_rst[:n]]
+
+
+def res_crc_from_blocks(block_first, lengths, block_crc, block_size, ctx=None):
+    """zlib's crc32 of every whole resource of a block container from its block checksums alone (mscomp_amd_res_crc_dev): no data is read.
+    Returns (numpy uint32 array of n, list of status)."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    n = len(lengths)
+    nbt = len(np.asarray(block_crc).reshape(-1))
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        d_first, d_len = _dev_u64(block_first, n + 1, dev), _dev_u64([int(x) for x in lengths], 1, dev)
+        d_bcrc = _dev_block_crc(block_crc, nbt, dev)
+        d_rcrc = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        res_crc_dev(ctx, block_size, n, nbt, d_first, d_len, d_bcrc, d_rcrc, d_st)
+        ctx.stream.synchronize()
+        out, st = d_rcrc.cpu().numpy().view(np.uint32)[:n].copy(), [int(x) for x in d_st.cpu().numpy()[:n]]
+    if own:
+        ctx.close()
+    return out, st
+
+
+def res_crc_dev(ctx, block_size, n_res, n_blocks_table, d_block_first, d_res_len, d_block_crc, d_res_crc, d_status):
+    """mscomp_amd_res_crc_dev on torch CUDA tensors: d_res_crc[r] (int32) = the CRC-32 of resource r from d_block_crc, d_status[r] MSCOMP_OK,
+    MSCOMP_ARG_ERROR (a table entry beyond n_blocks_table) or MSCOMP_DATA_ERROR (a wrong block count). Kernels on the ctx stream only."""
+    _ok(ctx.lib.mscomp_amd_res_crc_dev(ctx._h, int(block_size), int(n_res), int(n_blocks_table),
+                                       *_ptrs(d_block_first, d_res_len, d_block_crc, d_res_crc, d_status)), "mscomp_amd_res_crc_dev")
 
 
 def plan_paths(plan):

@@ -202,11 +202,15 @@ struct BlockAccess {
 };
 struct mscomp_amd_reader : BlockAccess {};
 // A writer adds an inner compress dev plan over the same units (a dirty block is compressed from its cache slot into its staging slot), the
-// staging area and three more columns. Its call runs the reader's passes up to the fold, then its own.
+// staging area and three more columns. Its call runs the reader's passes up to the fold, then its own. Its second call, resize, runs on
+// the same scratch with a record of its own (rrun: write and resize keep separate graphs) and two columns per resource.
 struct mscomp_amd_writer : BlockAccess {
 	mscomp_amd_plan* cplan = nullptr;                  // (null when blocks_max is 0)
+	mscomp_amd_plan rrun;
 	DevBuf stage;                                      // blocks_max slots of block_size bytes
 	uint32_t* head = nullptr; uint32_t* next = nullptr; uint32_t* dirty = nullptr;   // the rest of WriterTab
+	uint64_t* ru_first = nullptr; int32_t* rstat = nullptr;                          // the rest of ResizeTab
+	bool resized = false;                              // the last execution was a resize (mscomp_amd_writer_counts)
 };
 
 // a's columns from `base` on, a writer's (w, else null) behind the reader's; returns where they end: from a null base, their bytes
@@ -217,10 +221,11 @@ static uintptr_t access_tab(BlockAccess* a, mscomp_amd_writer* w, void* base)
 	ReaderTab& t = a->t;
 	t.q_off = k.q(n); t.q_want = k.q(n); t.q_j0 = k.q(n); t.q_len = k.q(n); t.unit_first = k.q(n + 1);
 	t.in_off = k.q(m); t.in_len = k.q(m); t.out_off = k.q(m); t.out_cap = k.q(m); t.ulen = k.q(m); t.src = k.q(m); t.clen = k.q(m); t.cum = k.q(m + 1);
+	if (w) { w->ru_first = k.q((size_t)a->n_res + 1); }
 	t.q_stat = k.i(n); t.ustat = k.i(m);
 	t.act = k.w(m); t.owner = k.w(m); t.uq = k.w(m); t.ublk = k.w(m); t.ucrc = k.w(m);
 	t.own = k.w(nbt); t.cnt = k.w(w ? 4 : 2);
-	if (w) { w->next = k.w(m); w->dirty = k.w(m); w->head = k.w(nbt); }
+	if (w) { w->next = k.w(m); w->dirty = k.w(m); w->head = k.w(nbt); w->rstat = k.i(a->n_res); }
 	return k.at;
 }
 
@@ -249,6 +254,7 @@ static MSCompStatus access_create(BlockAccess* a, mscomp_amd_writer* w, mscomp_a
 	a->ctx = c; a->format = format; a->shift = (uint32_t)__builtin_ctz(block_size); a->n_res = (uint32_t)n_res; a->nbt = (uint32_t)n_blocks_table;
 	a->n_req = (uint32_t)n_req; a->m = (uint32_t)M;
 	a->run.ctx = c; a->run.n_units = (uint32_t)n_req;
+	if (w) { w->rrun.ctx = c; w->rrun.n_units = (uint32_t)n_res; }
 	MSCompStatus st = MSCOMP_OK;
 	if (!a->tab.reserve(access_tab(a, w, nullptr) + 64) || (M && (!a->cache.reserve(bytes + 64) || (w && !w->stage.reserve(bytes + 64))))) { st = MSCOMP_MEM_ERROR; }
 	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, bytes, bytes, &a->dplan); }
@@ -268,9 +274,10 @@ static int access_counts(BlockAccess* a, mscomp_amd_writer* w, uint32_t out[3])
 	if (!a->ran) { return 0; }
 	uint64_t units = 0;
 	uint32_t cnt[4] = {};
-	if (hipMemcpy(&units, a->t.unit_first + a->n_req, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	const uint64_t* d_units = w && w->resized ? w->ru_first + a->n_res : a->t.unit_first + a->n_req;   // (a resize numbers its units per resource)
+	if (hipMemcpy(&units, d_units, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
 	if (hipMemcpy(cnt, a->t.cnt, w ? 16 : 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
-	if (!w || (cnt[3] == 0 && a->m)) { out[0] = (uint32_t)units; out[1] = cnt[0]; out[2] = cnt[w ? 2 : 1]; }
+	if (!w || (cnt[3] == 0 && a->m)) { out[0] = (uint32_t)units; out[1] = cnt[0]; out[2] = cnt[w ? 2 : 1]; }   // (a resize: cnt[0] = its changed blocks, each decoded or read raw once)
 	return 0;
 }
 
@@ -362,7 +369,7 @@ MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* w, const uint8_t* d_pack
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	if (w->dplan) { note_modes(w->dplan); w->dplan->ran = true; w->cplan->ran = true; }
-	w->ran = true;
+	w->ran = true; w->resized = false;
 	const void* args[16] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
 	                         d_src, d_src_off, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_off, d_new_block_crc,
 	                         d_written, d_status, d_res_status };
@@ -385,3 +392,56 @@ MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* w, const uint8_t* d_pack
 }
 
 int mscomp_amd_writer_counts(mscomp_amd_writer* w, uint32_t out[3]) { return access_counts(w, w, out); }
+
+// The writer's second call. Per resource: rules 0-3 and the units (the changed block, the fresh blocks); the changed blocks decoded into
+// their cache slots, checksummed and judged (rule 4); the units' new data trimmed and zero-filled in the cache; the compress plan and the CRC
+// kernels over them; the layout over the NEW table rows (rule 8); the move.
+MSCompStatus mscomp_amd_writer_resize(mscomp_amd_writer* w, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
+                                      const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_want_len,
+                                      uint8_t* d_new_packed, uint64_t new_cap, uint64_t* d_new_block_first, uint64_t* d_new_block_off,
+                                      uint32_t* d_new_block_crc, uint64_t* d_new_res_len, int32_t* d_res_status)
+{
+	if (!w || !d_block_first || !d_block_off || !d_new_block_first || !d_new_block_off) { return MSCOMP_ARG_ERROR; }
+	if (w->n_res && (!d_res_len || !d_want_len || !d_new_res_len || !d_res_status)) { return MSCOMP_ARG_ERROR; }
+	if ((w->m || w->nbt) && (!d_packed || !d_new_packed)) { return MSCOMP_ARG_ERROR; }
+	if ((d_block_crc == nullptr) != (d_new_block_crc == nullptr)) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = w->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (w->dplan) { note_modes(w->dplan); w->dplan->ran = true; w->cplan->ran = true; }
+	w->ran = true; w->resized = true;
+	const void* args[14] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_want_len,
+	                         d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc,
+	                         d_new_res_len, d_res_status };
+	return plan_run(&w->rrun, args, [&] {
+		const ReaderTab& t = w->t;
+		const ResizeTab rt = { { t, w->head, w->next, w->dirty }, w->ru_first, w->rstat };
+		uint8_t* cache = static_cast<uint8_t*>(w->cache.p); uint8_t* stage = static_cast<uint8_t*>(w->stage.p);
+		{ KernelTimer k(c, "rs_units"); launch_resize_units(c->stream, w->n_res, w->nbt, w->m, w->shift, packed_len, d_packed, cache, d_block_first, d_block_off,
+		                                                    d_res_len, d_want_len, rt); }
+		if (w->dplan) { dev_launch(w->dplan, d_packed, t.in_off, t.in_len, cache, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (d_block_crc && w->m) { crc_pass(c, w->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }
+		{ KernelTimer k(c, "rs_fold_kernel"); launch_resize_fold(c->stream, w->n_res, w->m, w->shift, d_block_first, d_res_len, d_want_len, d_block_crc, rt); }
+		{ KernelTimer k(c, "rs_fill"); launch_resize_fill(c->stream, w->n_res, w->m, w->shift, cache, rt, c->cpd_blocks); }
+		if (w->cplan) { dev_launch(w->cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (d_block_crc && w->m) { crc_pass(c, w->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }
+		{ KernelTimer k(c, "rs_layout_kernel"); launch_resize_layout(c->stream, w->n_res, w->nbt, w->shift, packed_len, new_cap, d_block_first, d_block_off, d_res_len,
+		                                                             d_want_len, d_block_crc, rt, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_res_status); }
+		{ KernelTimer k(c, "rs_move_kernel"); launch_resize_move(c->stream, w->n_res, w->nbt, w->shift, new_cap, d_packed, d_block_first, d_block_off, stage, cache,
+		                                                         d_new_block_first, d_new_block_off, rt, d_new_packed, c->cpd_blocks); }
+	});
+}
+
+// ---- resource CRCs from block CRCs (include/mscomp_amd.h; kernels: crc32.hip) ----
+MSCompStatus mscomp_amd_res_crc_dev(mscomp_amd_ctx* c, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, const uint64_t* d_block_first,
+                                    const uint64_t* d_res_len, const uint32_t* d_block_crc, uint32_t* d_res_crc, int32_t* d_status)
+{
+	if (!c || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u)) || !count_ok(n_res) || !count_ok(n_blocks_table)) { return MSCOMP_ARG_ERROR; }
+	if (n_res && (!d_block_first || !d_res_len || !d_block_crc || !d_res_crc || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if (n_res == 0) { return MSCOMP_OK; }                  // (nothing to report on)
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	{ KernelTimer k(c, "res_crc"); launch_res_crc(c->stream, (uint32_t)n_res, (uint32_t)n_blocks_table, (uint32_t)__builtin_ctz(block_size), d_block_first, d_res_len,
+	                                              d_block_crc, d_res_crc, d_status, c->crc_blocks); }
+	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
+}

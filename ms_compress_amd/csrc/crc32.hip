@@ -213,6 +213,50 @@ __global__ __launch_bounds__(CRC_THREADS) void crc_kernel(const uint8_t* __restr
 	}
 }
 
+// ---- resource CRCs from block CRCs (mscomp_amd_res_crc_dev) ----
+// crc32(A || B) = crc32(A) x^(8 |B|) ^ crc32(B) ^ (terms of the lengths alone), and along a whole resource those terms cancel: the CRC-32 of
+// a resource is the XOR over its blocks j of block_crc[j] x^(8 d_j), d_j = the resource's bytes behind block j (zlib's crc32_combine applied
+// along the resource). No data is read.
+// One thread per resource: its status by its own two table entries, and the word the blocks are folded into.
+__global__ __launch_bounds__(256) void rcrc_seed_kernel(uint32_t n_res, uint32_t nbt, uint32_t shift, const u64* __restrict__ block_first, const u64* __restrict__ res_len,
+                                                       uint32_t* __restrict__ res_crc, int32_t* __restrict__ status)
+{
+	const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+	if (r >= n_res) { return; }
+	const u64 f0 = block_first[r], f1 = block_first[r + 1u], L = res_len[r];
+	int32_t st = 0;
+	if (f0 > nbt || f1 > nbt) { st = -2; }                                 // MSCOMP_ARG_ERROR
+	else if (f1 - f0 != (L >> shift) + ((L & (((u64)1 << shift) - 1u)) ? 1u : 0u)) { st = -3; }   // MSCOMP_DATA_ERROR
+	status[r] = st; res_crc[r] = 0;
+}
+// A fixed grid dealt over the BLOCKS of the table, so that one resource of a million blocks spreads over every CU. A block finds its
+// resource by binary search (res_of_block) and takes part when it lies inside an MSCOMP_OK resource. A wave whose 64 blocks share one
+// resource folds them in registers first and issues one atomic.
+__global__ __launch_bounds__(256) void rcrc_fold_kernel(uint32_t n_res, uint32_t nbt, uint32_t shift, const u64* __restrict__ block_first, const u64* __restrict__ res_len,
+                                                       const uint32_t* __restrict__ block_crc, const int32_t* __restrict__ status, uint32_t* __restrict__ res_crc)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	const u64 step = (u64)gridDim.x * 256u;
+	for (u64 base = (u64)blockIdx.x * 256u + (threadIdx.x & ~63u); base < nbt; base += step) {
+		const u64 j = base + lane;
+		uint32_t r = 0xFFFFFFFFu, v = 0;
+		if (j < nbt) {
+			const uint32_t x = res_of_block(block_first, n_res, j);
+			const u64 f0 = block_first[x], f1 = block_first[x + 1u];
+			if (f0 <= j && j < f1 && status[x] == 0) {
+				const u64 L = res_len[x], end = (j - f0 + 1u) << shift;          // (f1 - f0 = ceil(L / B) <= nbt: no overflow)
+				r = x; v = block_crc[j];
+				if (v != 0 && end < L) { v = crc_mul(v, crc_xpow((L - end) << 3)); }
+			}
+		}
+		const uint32_t r0 = uniform(r);
+		if (__ballot(r != r0) == 0) {
+			v = wave_xor(v);
+			if (lane == 0 && r0 != 0xFFFFFFFFu && v != 0) { atomicXor(&res_crc[r0], v); }
+		} else if (r != 0xFFFFFFFFu && v != 0) { atomicXor(&res_crc[r], v); }
+	}
+}
+
 // blocks of crc_kernel that are resident on the current device at once, four per CU at most: its grid
 uint32_t crc_dev_blocks()
 {
@@ -239,6 +283,16 @@ void launch_crc_units(hipStream_t st, uint32_t n, const uint8_t* base, const u64
 	if (n == 0) { return; }
 	if (gcrc) { hipLaunchKernelGGL(crc_kernel<true>, dim3(blocks), dim3(CRC_THREADS), 0, st, base, off, cum, n, crc, grp, fac, gcrc); }
 	else { hipLaunchKernelGGL(crc_kernel<false>, dim3(blocks), dim3(CRC_THREADS), 0, st, base, off, cum, n, crc, grp, fac, gcrc); }
+}
+
+void launch_res_crc(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, const u64* block_first, const u64* res_len, const uint32_t* block_crc,
+                    uint32_t* res_crc, int32_t* status, uint32_t blocks)
+{
+	if (n_res == 0) { return; }
+	hipLaunchKernelGGL(rcrc_seed_kernel, dim3((n_res + 255u) / 256u), dim3(256), 0, st, n_res, nbt, shift, block_first, res_len, res_crc, status);
+	if (nbt == 0) { return; }
+	const uint32_t need = (nbt + 255u) / 256u;
+	hipLaunchKernelGGL(rcrc_fold_kernel, dim3(need < blocks ? need : blocks), dim3(256), 0, st, n_res, nbt, shift, block_first, res_len, block_crc, status, res_crc);
 }
 
 } // namespace msc

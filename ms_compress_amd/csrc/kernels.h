@@ -307,6 +307,33 @@ void launch_writer_layout(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32
 void launch_writer_move(hipStream_t st, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* packed, const u64* block_off, const uint8_t* stage,
                         const uint8_t* cache, const u64* new_off, const WriterTab& t, uint8_t* dst, uint32_t blocks);
 
+// mscomp_amd_writer_resize, the writer's second call: the same tables, and two columns per resource behind them. A unit is a block whose
+// data changes: the changed block of an admitted resource (its unit 0, when there is one), then its fresh blocks in order. Of the unit
+// columns r.uq is the unit's resource, r.ublk its block within the resource, r.owner the data length e2 it will have, r.act kind | e << 2 of
+// a changed block (RD_SKIP for a fresh one); r.cnt: [0] changed blocks, [2] blocks encoded, [3] = 1 for a refused table.
+struct ResizeTab {
+	WriterTab w;
+	u64* ru_first;                                     // n_res + 1: first unit of every resource
+	int32_t* rstat;                                    // n_res: the resource's status by rules 1 and 3, then -- behind the fold -- by rule 4 too
+};
+// rules 0-3 and ru_first (one block), then the units' rows: the changed blocks' table checks and the inner decompress plan's unit tables
+void launch_resize_units(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, u64 packed_len, const uint8_t* packed, const uint8_t* cache,
+                         const u64* block_first, const u64* block_off, const u64* res_len, const u64* want, const ResizeTab& t);
+// behind the decompress plan and the CRC kernels: rule 4 per resource (block_crc may be null)
+void launch_resize_fold(hipStream_t st, uint32_t n_res, uint32_t m, uint32_t shift, const u64* block_first, const u64* res_len, const u64* want,
+                        const uint32_t* block_crc, const ResizeTab& t);
+// the new data of the accepted resources' units in their cache slots (kept bytes, then zeros), then the unit tables of the inner compress plan
+// and of the CRC kernels over them (two launches; `blocks` = compact_dev_blocks())
+void launch_resize_fill(hipStream_t st, uint32_t n_res, uint32_t m, uint32_t shift, uint8_t* cache, const ResizeTab& t, uint32_t blocks);
+// behind the compress plan and the CRC kernels, one block: new_first (n_res + 1), rule 8, new_off (nbt + 1), new_crc (nbt, may be null with
+// block_crc), the move pass's word per NEW row (t.w.head), new_len and res_status (n_res)
+void launch_resize_layout(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 packed_len, u64 cap, const u64* block_first, const u64* block_off,
+                          const u64* res_len, const u64* want, const uint32_t* block_crc, const ResizeTab& t, u64* new_first, u64* new_off, uint32_t* new_crc,
+                          u64* new_len, int32_t* res_status);
+// every new row to dst + new_off[row]: clean ones from their old row in packed, dirty ones from stage or cache; nothing at or behind dst + cap
+void launch_resize_move(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* packed, const u64* block_first, const u64* block_off,
+                        const uint8_t* stage, const uint8_t* cache, const u64* new_first, const u64* new_off, const ResizeTab& t, uint8_t* dst, uint32_t blocks);
+
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status
 // MSCOMP_ARG_ERROR), off[i] = its offset. in_off / off and status may be null.
@@ -319,6 +346,12 @@ void launch_crc_seeds(hipStream_t st, uint32_t n, const u64* cum, uint32_t* crc,
 uint32_t crc_dev_blocks();
 void launch_crc_units(hipStream_t st, uint32_t n, const uint8_t* base, const u64* off, const u64* cum, uint32_t* crc,
                       const uint32_t* grp, const uint32_t* fac, uint32_t* gcrc, uint32_t blocks);
+
+// mscomp_amd_res_crc_dev: res_crc[r] = the CRC-32 of resource r from its blocks' CRC-32s alone. A seed kernel (one thread per resource:
+// status, res_crc = 0), then a fixed grid over the table's blocks: each finds its resource and folds block_crc[j] x^(8 bytes of the
+// resource behind block j) into the resource's word with an atomic XOR. `blocks` = crc_dev_blocks()
+void launch_res_crc(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, const u64* block_first, const u64* res_len, const uint32_t* block_crc,
+                    uint32_t* res_crc, int32_t* status, uint32_t blocks);
 
 // ---- utilities (util.hip) ----
 // prefix[0..n] = exclusive scan of sizes[0..n) as u64 (prefix[n] = total). block_sums: scratch of ceil(n/1024)+1 u64.

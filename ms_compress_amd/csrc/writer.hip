@@ -4,6 +4,8 @@
 // this file load the raw owners into their cache slots and apply the MSCOMP_OK requests in request order, hand the dirty blocks to a
 // compress dev plan and the CRC kernels (api.hip runs both between these passes, unchanged), lay the new container out around them and move
 // every block -- clean ones from the old container, dirty ones from the staging area or the cache -- to its new place. DESIGN.md 4.10.
+// mscomp_amd_writer_resize (the rs_* kernels below) is the writer's second call: every resource cut or zero-extended to a
+// wanted length, the one block whose data length changes and the fresh blocks as the units, the same inner plans, CRC kernels and scratch.
 #include "kernels.h"
 
 namespace msc {
@@ -211,6 +213,310 @@ __global__ __launch_bounds__(CPD_THREADS) void wr_move_kernel(uint32_t nbt, uint
 	}
 }
 
+// ---- resize (mscomp_amd_writer_resize) ----
+// A resource of L bytes in n blocks becomes one of W bytes in n2 = ceil(W / B). Of the blocks both have, only the last one, kc, can change
+// its data length (e -> e2): it is the resource's unit 0 when it does; the fresh blocks n .. n2 - 1 are the units behind it. Only called
+// for a resource that passed rule 1 (n = ceil(L / B) < 2^31), so no product below overflows.
+struct RsGeo { u64 n2, kc, cnt; uint32_t e, e2; bool changed; };
+__device__ __forceinline__ RsGeo rs_geo(u64 L, u64 W, u64 n, uint32_t shift)
+{
+	const u64 B = (u64)1 << shift;
+	RsGeo g;
+	g.n2 = (W >> shift) + ((W & (B - 1u)) ? 1u : 0u);
+	const u64 mn = n < g.n2 ? n : g.n2;
+	g.kc = 0; g.e = 0; g.e2 = 0; g.changed = false;
+	if (mn) {
+		g.kc = mn - 1u;
+		const u64 l = L - (g.kc << shift), w = W - (g.kc << shift);
+		g.e = (uint32_t)(l < B ? l : B); g.e2 = (uint32_t)(w < B ? w : B); g.changed = g.e != g.e2;
+	}
+	g.cnt = (g.changed ? 1u : 0u) + (g.n2 > n ? g.n2 - n : 0u);
+	return g;
+}
+
+// One block walks the resources in tiles of 1024. Rule 0 first (the table as a whole: a refused table has no units, cnt[3] says so to the
+// passes behind). Then rules 1-3 per resource, as rd_req_kernel runs the reader's: the cost of every resource that passed rules 1 and 2 in
+// one scan (the budget's running total, refused ones included), the cost of the admitted ones in a second (the unit numbering, ru_first).
+__global__ __launch_bounds__(DV_THREADS) void rs_res_kernel(uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, const u64* __restrict__ block_first,
+                                                           const u64* __restrict__ res_len, const u64* __restrict__ want, ResizeTab t)
+{
+	__shared__ u64 s_w[1][DV_WAVES];
+	const uint32_t tid = threadIdx.x;
+	const u64 B = (u64)1 << shift;
+	int wrong = block_first[n_res] > nbt ? 1 : 0;
+	for (uint32_t i = tid; i < n_res; i += DV_THREADS) { if (block_first[i] > block_first[i + 1u]) { wrong = 1; } }
+	const bool bad = __syncthreads_or(wrong) != 0;
+	if (tid == 0) { t.ru_first[0] = 0; t.w.r.cnt[0] = 0; t.w.r.cnt[1] = 0; t.w.r.cnt[2] = 0; t.w.r.cnt[3] = bad ? 1u : 0u; }
+	u64 run[1] = {0}, acc[1] = {0};
+	for (uint32_t base = 0; base < n_res; base += DV_THREADS) {
+		const uint32_t r = base + tid;
+		const bool live = r < n_res;
+		int32_t st = 0;
+		u64 c = 0;
+		bool moves = false;
+		if (live && bad) { st = -2; }                                       // MSCOMP_ARG_ERROR
+		else if (live) {
+			const u64 f0 = block_first[r], n = block_first[r + 1u] - f0, L = res_len[r], W = want[r];
+			if (n != (L >> shift) + ((L & (B - 1u)) ? 1u : 0u)) { st = -3; }    // MSCOMP_DATA_ERROR
+			else if (W != L) { moves = true; c = rs_geo(L, W, n, shift).cnt; }
+		}
+		u64 v[1] = {c};
+		dv_block_scan<1>(v, run, s_w);                                    // running total of the costs, this resource included
+		if (moves && v[0] > m) { st = -2; c = 0; }                          // over the budget, as everything that changes behind it
+		u64 k[1] = {c};
+		dv_block_scan<1>(k, acc, s_w);
+		if (live) { t.ru_first[r + 1u] = k[0]; t.rstat[r] = st; }
+	}
+}
+
+// One thread per possible unit: its resource (binary search in ru_first) and its block. A changed block runs the container's table checks
+// as rd_units_kernel runs them and becomes a unit of the inner decompress plan (cache slot u B, capacity e) or, raw, is read in d_packed;
+// a fresh block has nothing to read. r.owner[u] = e2, the data length the unit will have. cnt[0] counts the changed blocks.
+__global__ __launch_bounds__(256) void rs_units_kernel(uint32_t n_res, uint32_t m, uint32_t shift, u64 packed_len, const uint8_t* __restrict__ packed,
+                                                      const uint8_t* __restrict__ cache, const u64* __restrict__ block_first, const u64* __restrict__ block_off,
+                                                      const u64* __restrict__ res_len, const u64* __restrict__ want, ResizeTab t)
+{
+	const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+	if (u >= m) { return; }
+	const ReaderTab& rt = t.w.r;
+	const u64 B = (u64)1 << shift;
+	u64 io = 0, il = 0, oo = 0, oc = 0, sa = 0, cl = 0;
+	uint32_t a = RD_SKIP, e2 = 0;
+	bool chg = false;
+	if (u < t.ru_first[n_res]) {
+		const uint32_t r = res_of_block(t.ru_first, n_res, u);
+		const u64 f0 = block_first[r], n = block_first[r + 1u] - f0, W = want[r], idx = u - t.ru_first[r];
+		const RsGeo g = rs_geo(res_len[r], W, n, shift);
+		u64 k;
+		if (g.changed && idx == 0) {
+			chg = true; k = g.kc; e2 = g.e2;
+			const u64 j = f0 + k, e = g.e, o0 = block_off[j], o1 = block_off[j + 1u];   // (j < block_first[r + 1] <= nbt: rule 0)
+			if (o1 < o0 || o1 > packed_len) { a = RD_FAIL; }
+			else {
+				const u64 s = o1 - o0;
+				if (s == e) { a = RD_COPY; sa = (u64)(uintptr_t)(packed + o0); cl = e; }
+				else if (s != 0 && s < e) { a = RD_DECODE; io = o0; il = s; oo = (u64)u << shift; oc = e; sa = (u64)(uintptr_t)(cache + oo); cl = e; }
+				else { a = RD_FAIL; }
+			}
+			a |= (uint32_t)e << 2;
+		} else {
+			k = n + idx - (g.changed ? 1u : 0u);                              // (< n2 <= n + m < 2^32)
+			const u64 left = W - (k << shift);
+			e2 = (uint32_t)(left < B ? left : B);
+		}
+		rt.uq[u] = r; rt.ublk[u] = (uint32_t)k;
+	}
+	rt.in_off[u] = io; rt.in_len[u] = il; rt.out_off[u] = oo; rt.out_cap[u] = oc; rt.src[u] = sa; rt.clen[u] = cl; rt.act[u] = a; rt.owner[u] = e2;
+	const u64 changed = __ballot(chg);
+	if ((threadIdx.x & 63u) == 0 && changed) { atomicAdd(&rt.cnt[0], (uint32_t)__popcll(changed)); }
+}
+
+// One thread per resource, behind the decompress plan and the CRC kernels: rule 4, the verdict on its changed block as rd_fold_kernel folds
+// an owner's (a failed table check; a decoder status other than MSCOMP_OK or a length other than e; with block_crc, another CRC-32).
+__global__ __launch_bounds__(256) void rs_fold_kernel(uint32_t n_res, uint32_t shift, const u64* __restrict__ block_first, const u64* __restrict__ res_len,
+                                                     const u64* __restrict__ want, const uint32_t* __restrict__ block_crc, ResizeTab t)
+{
+	const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+	if (r >= n_res || t.rstat[r] != 0 || t.ru_first[r] == t.ru_first[r + 1u]) { return; }
+	const ReaderTab& rt = t.w.r;
+	const u64 f0 = block_first[r];
+	const RsGeo g = rs_geo(res_len[r], want[r], block_first[r + 1u] - f0, shift);
+	if (!g.changed) { return; }
+	const u64 o = t.ru_first[r];
+	const uint32_t a = rt.act[o], kind = a & 3u;
+	bool bad = kind == RD_FAIL || (kind == RD_DECODE && (rt.ustat[o] != 0 || rt.ulen[o] != (u64)(a >> 2)));
+	if (!bad && block_crc && rt.ucrc[o] != block_crc[f0 + g.kc]) { bad = true; }
+	if (bad) { t.rstat[r] = -3; }                                         // MSCOMP_DATA_ERROR: the resource is carried
+}
+
+// cnt zero bytes at dst by one wave, in the shape of rd_wave_move's stores: a bytewise head up to the next 16-byte boundary, 16-byte
+// stores, a bytewise tail (lanes 16..30)
+__device__ __forceinline__ void rs_wave_zero(uint8_t* __restrict__ dst, uint32_t cnt, uint32_t lane)
+{
+	uint32_t head = (16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u;
+	if (head > cnt) { head = cnt; }
+	const uint32_t body = (cnt - head) >> 4, tail0 = head + body * 16u;
+	if (lane < head) { dst[lane] = 0; }
+	if (lane >= 16u && tail0 + (lane - 16u) < cnt) { dst[tail0 + (lane - 16u)] = 0; }
+	uint4* __restrict__ d16 = reinterpret_cast<uint4*>(dst + head);
+	for (uint32_t k = lane; k < body; k += 64u) { d16[k] = make_uint4(0, 0, 0, 0); }
+}
+
+// Trim and fill: the new data of the accepted resources' units, in their cache slots. An item is one (unit, 16 KiB piece) pair dealt to the
+// waves of a fixed grid as wr_patch_kernel deals them. Of a changed block the first min(e, e2) bytes stay -- a decoded one has them in its
+// slot, a raw one's piece is loaded from d_packed --, the bytes from there to e2 are zeros; a fresh block is e2 zeros.
+__global__ __launch_bounds__(256) void rs_fill_kernel(uint32_t n_res, uint32_t shift, uint32_t ppu_shift, uint8_t* __restrict__ cache, ResizeTab t)
+{
+	const ReaderTab& rt = t.w.r;
+	const uint32_t lane = threadIdx.x & 63u;
+	const u64 items = t.ru_first[n_res] << ppu_shift, nw = (u64)gridDim.x * 4u, w = (u64)blockIdx.x * 4u + (threadIdx.x >> 6);
+	u64 per = (items + nw - 1u) / nw;
+	per = per < 1u ? 1u : per > 64u ? 64u : per;
+	for (u64 base = w * per; base < items; base += nw * per) {
+		uint32_t o = 0, a0 = 0, a1 = 0, keep = 0;
+		u64 sa = 0;
+		const u64 i = base + lane;
+		if (lane < per && i < items) {
+			const uint32_t u = (uint32_t)(i >> ppu_shift), e2 = rt.owner[u];
+			const u64 at = (i & (((u64)1 << ppu_shift) - 1u)) << RD_PIECE_SHIFT;
+			if (t.rstat[rt.uq[u]] == 0 && at < e2) {
+				const uint32_t a = rt.act[u], e = a >> 2;                      // (a fresh block: RD_SKIP, e = 0)
+				o = u; a0 = (uint32_t)at; a1 = e2 - at < ((u64)1 << RD_PIECE_SHIFT) ? e2 : (uint32_t)at + (1u << RD_PIECE_SHIFT);
+				keep = e < e2 ? e : e2;
+				if ((a & 3u) == RD_COPY) { sa = rt.src[u]; }
+			}
+		}
+		u64 todo = __ballot(a1 > a0);
+		while (todo) {
+			const int l = __ffsll((unsigned long long)todo) - 1;
+			todo &= todo - 1u;
+			const uint32_t b0 = __shfl(a0, l, 64), b1 = __shfl(a1, l, 64), kp = __shfl(keep, l, 64);
+			const u64 s = __shfl(sa, l, 64);
+			uint8_t* slot = cache + ((u64)__shfl(o, l, 64) << shift);
+			const uint32_t c1 = kp < b1 ? kp : b1, z0 = kp > b0 ? kp : b0;
+			if (s && b0 < c1) { rd_wave_move(slot + b0, reinterpret_cast<const uint8_t*>((uintptr_t)s) + b0, c1 - b0, lane); }
+			if (z0 < b1) { rs_wave_zero(slot + z0, b1 - z0, lane); }
+		}
+	}
+}
+
+// One thread per possible unit, behind the fill: a unit of an accepted resource becomes a unit of the inner compress plan -- cache slot in,
+// staging slot out, capacity e2 - 1 -- and of the CRC kernels, as wr_cunits_kernel makes a dirty owner one; every other unit is empty in
+// both. cnt[2] counts them: the blocks encoded.
+__global__ __launch_bounds__(256) void rs_cunits_kernel(uint32_t n_res, uint32_t m, uint32_t shift, const uint8_t* __restrict__ cache, ResizeTab t)
+{
+	const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+	if (u >= m) { return; }
+	const ReaderTab& rt = t.w.r;
+	const bool d = u < t.ru_first[n_res] && t.rstat[rt.uq[u]] == 0;
+	const u64 e2 = d ? rt.owner[u] : 0, at = d ? (u64)u << shift : 0;
+	rt.in_off[u] = at; rt.in_len[u] = e2; rt.out_off[u] = at; rt.out_cap[u] = d ? e2 - 1u : 0;
+	rt.src[u] = d ? (u64)(uintptr_t)(cache + at) : 0; rt.clen[u] = e2; t.w.dirty[u] = d ? 1u : 0u;
+	const u64 enc = __ballot(d);
+	if ((threadIdx.x & 63u) == 0 && enc) { atomicAdd(&rt.cnt[2], (uint32_t)__popcll(enc)); }
+}
+
+// Layout, one block. A scan over the resources gives the final block counts -- n2 for an accepted resource, n for a carried one -- and
+// new_first; rule 8 holds their sum against the table. A scan over the NEW table rows then gives every row its stored length, checksum and
+// move word (in t.head): a row finds its resource by binary search in new_first and is the changed block or a fresh one of an accepted
+// resource -- dirty, its stored form by bk_select_kernel's rule from the compress plan's results -- or a kept block, clean at old row
+// block_first[r] + k. Then the resources' statuses and lengths. A refused table (rule 0 or 8) writes zeros and MSCOMP_ARG_ERROR only.
+__global__ __launch_bounds__(DV_THREADS) void rs_layout_kernel(uint32_t n_res, uint32_t nbt, uint32_t shift, u64 packed_len, u64 cap, const u64* __restrict__ block_first,
+                                                              const u64* __restrict__ block_off, const u64* __restrict__ res_len, const u64* __restrict__ want,
+                                                              const uint32_t* __restrict__ block_crc, ResizeTab t, u64* new_first, u64* new_off,
+                                                              uint32_t* __restrict__ new_crc, u64* __restrict__ new_len, int32_t* __restrict__ res_status)
+{
+	__shared__ u64 s_w[1][DV_WAVES];
+	const uint32_t tid = threadIdx.x;
+	const ReaderTab& rt = t.w.r;
+	const u64 B = (u64)1 << shift;
+	const bool bad0 = rt.cnt[3] != 0;
+	u64 run[1] = {0};
+	if (tid == 0) { new_first[0] = 0; new_off[0] = 0; }
+	for (uint32_t base = 0; base < n_res; base += DV_THREADS) {
+		const uint32_t r = base + tid;
+		const bool live = r < n_res;
+		u64 c = 0;
+		if (live && !bad0) {
+			c = block_first[r + 1u] - block_first[r];
+			if (t.rstat[r] == 0) { const u64 W = want[r]; c = (W >> shift) + ((W & (B - 1u)) ? 1u : 0u); }   // (W = L: the same count)
+		}
+		u64 v[1] = {c};
+		dv_block_scan<1>(v, run, s_w);
+		if (live) { new_first[r + 1u] = v[0]; }
+	}
+	const u64 nbn = run[0];
+	__syncthreads();                                                     // new_first is read back below, by other threads of this block; cnt[3] was read above
+	if (bad0 || nbn > nbt) {
+		if (tid == 0) { rt.cnt[3] = 1u; }
+		for (uint32_t i = tid; i <= n_res; i += DV_THREADS) { new_first[i] = 0; if (i < n_res) { new_len[i] = 0; res_status[i] = -2; } }
+		for (uint32_t j = tid; j <= nbt; j += DV_THREADS) { new_off[j] = 0; if (new_crc && j < nbt) { new_crc[j] = 0; } }
+		return;
+	}
+	u64 sum[1] = {0};
+	for (uint32_t base = 0; base < nbt; base += DV_THREADS) {
+		const uint32_t j = base + tid;
+		const bool live = j < nbt;
+		u64 len = 0;
+		uint32_t crc = 0, word = WR_NONE;
+		if (live && j < nbn) {
+			const uint32_t r = res_of_block(new_first, n_res, j);
+			const u64 k = j - new_first[r], f0 = block_first[r], n = block_first[r + 1u] - f0, L = res_len[r], W = want[r];
+			bool dirty = false;
+			u64 u = 0, e2 = 0;
+			if (t.rstat[r] == 0 && W != L) {
+				const RsGeo g = rs_geo(L, W, n, shift);
+				if (g.changed && k == g.kc) { dirty = true; u = t.ru_first[r]; e2 = g.e2; }
+				else if (k >= n) { dirty = true; u = t.ru_first[r] + (g.changed ? 1u : 0u) + (k - n); const u64 left = W - (k << shift); e2 = left < B ? left : B; }
+			}
+			if (dirty) {
+				const bool comp = rt.ustat[u] == 0 && rt.ulen[u] < e2;
+				len = comp ? rt.ulen[u] : e2; crc = rt.ucrc[u]; word = WR_DIRTY + 2u * (uint32_t)u + (comp ? 1u : 0u);
+			} else {
+				const u64 o0 = block_off[f0 + k], o1 = block_off[f0 + k + 1u];
+				if (o0 <= o1 && o1 <= packed_len) { len = o1 - o0; }
+				crc = block_crc ? block_crc[f0 + k] : 0u; word = len ? WR_CLEAN : WR_NONE;
+			}
+		}
+		u64 v[1] = {len};
+		dv_block_scan<1>(v, sum, s_w);
+		if (live) { new_off[j + 1u] = v[0]; t.w.head[j] = word; if (new_crc) { new_crc[j] = crc; } }
+	}
+	__syncthreads();                                                     // new_off is read back below
+	for (uint32_t r = tid; r < n_res; r += DV_THREADS) {
+		const u64 n0 = new_first[r], n1 = new_first[r + 1u];
+		const int32_t st = t.rstat[r];
+		res_status[r] = (n1 > n0 && new_off[n1] > cap) ? -5 : st;           // MSCOMP_BUF_ERROR replaces what the resource had (the offsets only grow: the last block tells)
+		new_len[r] = st == 0 ? want[r] : res_len[r];
+	}
+}
+
+// Move, in the shape of wr_move_kernel: equal slices of the new byte range over a fixed grid, 64 new table rows looked at at once. A clean
+// row's old row is block_first[r] + (row - new_first[r]); the clean rows from j on whose old row lies as far from the new one as row j's
+// follow one another in the old table too, so they are ONE copy shifted by a constant. The distance changes only where a resource in
+// between grew, shrank or was carried: runs break at resource boundaries, and nowhere else.
+__global__ __launch_bounds__(CPD_THREADS) void rs_move_kernel(uint32_t n_res, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* __restrict__ packed,
+                                                             const u64* __restrict__ block_first, const u64* __restrict__ block_off, const uint8_t* __restrict__ stage,
+                                                             const uint8_t* __restrict__ cache, const u64* __restrict__ new_first, const u64* __restrict__ new_off,
+                                                             const uint32_t* __restrict__ word, const uint32_t* __restrict__ cnt, uint8_t* __restrict__ dst)
+{
+	if (cnt[3] != 0) { return; }                                         // a refused table: nothing is written
+	const uint32_t tid = threadIdx.x, lane = tid & 63u;
+	const u64 total = new_off[nbt], range = total < cap ? total : cap;
+	u64 per = (range + gridDim.x - 1u) / gridDim.x;
+	per = (per + 4095u) & ~(u64)4095u;
+	const u64 lo = (u64)blockIdx.x * per;
+	if (lo >= range) { return; }
+	const u64 hi = range - lo < per ? range : lo + per;
+	uint32_t j = 0, b = nbt;                                             // the first row with new_off[j + 1] > lo (there is one: new_off[nbt] > lo)
+	while (j < b) { const uint32_t mid = j + (b - j) / 2u; if (new_off[mid + 1u] > lo) { b = mid; } else { j = mid + 1u; } }
+	while (j < nbt) {
+		const u64 o = new_off[j];
+		if (o >= hi) { break; }
+		const uint32_t row = j + lane;
+		u64 e1 = 0, old = 0;
+		bool clean = false;
+		if (row < nbt) {
+			e1 = new_off[row + 1u]; clean = word[row] == WR_CLEAN && e1 <= cap;
+			if (clean) { const uint32_t r = res_of_block(new_first, n_res, row); old = block_first[r] + (row - new_first[r]); }   // (a clean row lies below new_first[n_res])
+		}
+		const u64 old0 = __shfl(old, 0, 64);
+		const u64 others = ~__ballot(clean && old - row == old0 - j);
+		const uint32_t k = others ? (uint32_t)__ffsll((unsigned long long)others) - 1u : 64u;   // rows of the run from j on (the same in every wave of the block)
+		const uint8_t* s = nullptr;
+		u64 end = o;
+		if (k) { end = __shfl(e1, (int)k - 1, 64); s = packed + block_off[old0]; j += k; }
+		else {
+			const uint32_t wd = word[j];
+			end = new_off[j + 1u];
+			if (wd >= WR_DIRTY && end <= cap) { s = ((wd & 1u) ? stage : cache) + ((u64)((wd - WR_DIRTY) >> 1) << shift); }
+			++j;
+		}
+		const u64 d0 = o > lo ? o : lo, d1 = end < hi ? end : hi;
+		if (s && d0 < d1) { cpd_move<false>(dst + d0, s + (d0 - o), d1 - d0, tid); }
+	}
+}
+
 void launch_writer_link(hipStream_t st, uint32_t n_req, uint32_t nbt, uint32_t m, const WriterTab& t)
 {
 	if (m == 0) { return; }
@@ -241,6 +547,46 @@ void launch_writer_move(hipStream_t st, uint32_t nbt, uint32_t shift, u64 cap, c
 {
 	if (nbt == 0) { return; }
 	hipLaunchKernelGGL(wr_move_kernel, dim3(blocks), dim3(CPD_THREADS), 0, st, nbt, shift, cap, packed, block_off, stage, cache, new_off, t.head, t.r.cnt, dst);
+}
+
+void launch_resize_units(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, u64 packed_len, const uint8_t* packed, const uint8_t* cache,
+                         const u64* block_first, const u64* block_off, const u64* res_len, const u64* want, const ResizeTab& t)
+{
+	hipLaunchKernelGGL(rs_res_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_res, nbt, m, shift, block_first, res_len, want, t);
+	if (m == 0) { return; }
+	hipLaunchKernelGGL(rs_units_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, n_res, m, shift, packed_len, packed, cache, block_first, block_off, res_len, want, t);
+}
+
+void launch_resize_fold(hipStream_t st, uint32_t n_res, uint32_t m, uint32_t shift, const u64* block_first, const u64* res_len, const u64* want,
+                        const uint32_t* block_crc, const ResizeTab& t)
+{
+	if (m == 0 || n_res == 0) { return; }
+	hipLaunchKernelGGL(rs_fold_kernel, dim3((n_res + 255u) / 256u), dim3(256), 0, st, n_res, shift, block_first, res_len, want, block_crc, t);
+}
+
+void launch_resize_fill(hipStream_t st, uint32_t n_res, uint32_t m, uint32_t shift, uint8_t* cache, const ResizeTab& t, uint32_t blocks)
+{
+	if (m == 0) { return; }
+	const uint32_t ppu_shift = shift > RD_PIECE_SHIFT ? shift - RD_PIECE_SHIFT : 0u;
+	const u64 need = (((u64)m << ppu_shift) + 255u) / 256u;                // a lane per item at the bound
+	hipLaunchKernelGGL(rs_fill_kernel, dim3((uint32_t)(need < blocks ? need : blocks)), dim3(256), 0, st, n_res, shift, ppu_shift, cache, t);
+	hipLaunchKernelGGL(rs_cunits_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, n_res, m, shift, cache, t);
+}
+
+void launch_resize_layout(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 packed_len, u64 cap, const u64* block_first, const u64* block_off,
+                          const u64* res_len, const u64* want, const uint32_t* block_crc, const ResizeTab& t, u64* new_first, u64* new_off, uint32_t* new_crc,
+                          u64* new_len, int32_t* res_status)
+{
+	hipLaunchKernelGGL(rs_layout_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_res, nbt, shift, packed_len, cap, block_first, block_off, res_len, want, block_crc, t,
+	                   new_first, new_off, new_crc, new_len, res_status);
+}
+
+void launch_resize_move(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* packed, const u64* block_first, const u64* block_off,
+                        const uint8_t* stage, const uint8_t* cache, const u64* new_first, const u64* new_off, const ResizeTab& t, uint8_t* dst, uint32_t blocks)
+{
+	if (nbt == 0) { return; }
+	hipLaunchKernelGGL(rs_move_kernel, dim3(blocks), dim3(CPD_THREADS), 0, st, n_res, nbt, shift, cap, packed, block_first, block_off, stage, cache, new_first, new_off,
+	                   t.w.head, t.w.r.cnt, dst);
 }
 
 } // namespace msc
