@@ -668,6 +668,78 @@ MSCompStatus mscomp_amd_writer_resize(mscomp_amd_writer* wr, const uint8_t* d_pa
                                       uint32_t* d_new_block_crc /* NULL exactly when d_block_crc is */,
                                       uint64_t* d_new_res_len /* n_res */, int32_t* d_res_status /* n_res */);
 
+/* Splice: a new container made of a list of picks (source, resource) out of up to MSCOMP_AMD_SPLICE_SRC_MAX source containers, without
+ * decoding a byte. Deleting, reordering, duplicating and appending resources and merging containers are all pick lists. The stored form of
+ * a block depends only on its data, the format and B, so a block is carried verbatim -- no format argument: the stored bytes are never
+ * interpreted. Carrying them only makes sense between containers of ONE format and ONE block size: that is the caller's duty, nothing
+ * here can check it. The only pass over the data is one move at copy speed.
+ *   Creation:     MSCOMP_ARG_ERROR, all checked before the context is used and with *sp cleared, for a null ctx or sp, a block_size that is
+ *                 not a power of two from 4096 to 524288, n_src of 0 or above MSCOMP_AMD_SPLICE_SRC_MAX, non-zero flags, or n_pick or
+ *                 n_blocks_table (the rows of the NEW container's table) above 0x7FFFFFF0; MSCOMP_MEM_ERROR when the scratch cannot be
+ *                 reserved.
+ *   Scratch:      reserved once, at creation: 8 n_blocks_table + 64 bytes (the address of every new row's stored bytes).
+ *   Sources:      src is a HOST array of n_src views, each a source container as its writer left it. The views are read on the host and
+ *                 travel by value in the kernel arguments; nothing is uploaded. The sources are only read; the new arrays must not overlap
+ *                 any source array.
+ *   Notation:     pick p = (s, r) = d_pick[2 p], d_pick[2 p + 1] becomes resource p of the new container. B the block size,
+ *                 L = src[s].d_res_len[r], first / off = src[s].d_block_first / d_block_off, n = first[r + 1] - first[r].
+ *   Rules:        per pick, in this order:
+ *                   1. MSCOMP_ARG_ERROR, nothing of the pick read further, when s >= n_src, r >= src[s].n_res, first[r] > first[r + 1]
+ *                      or first[r + 1] > src[s].n_blocks_table;
+ *                   2. block count: MSCOMP_DATA_ERROR when n is not L / B + (L % B != 0) (no sum is formed that can overflow);
+ *                   3. room in the table: the running total of n over the picks that passed rules 1 and 2, in pick order, including this
+ *                      pick and including picks refused here, must not exceed n_blocks_table; otherwise MSCOMP_ARG_ERROR. A saturating
+ *                      prefix sum, as the reader's budget and resize's rule 3: once it is crossed every later pick with blocks is
+ *                      refused; a pick without blocks is never refused here;
+ *                   4. a refused pick is an EMPTY resource of the new container: d_new_res_len[p] = 0 and no rows. The pick index is
+ *                      always the resource index;
+ *                   5. an accepted pick: d_new_res_len[p] = L, and new row d_new_block_first[p] + k takes source row first[r] + k: its
+ *                      stored bytes verbatim and, when checksums are carried, its CRC word verbatim. A source entry j that is not
+ *                      off[j] <= off[j + 1] <= packed_len of its source has the stored length 0 and is never read (the writer's rule 8).
+ *                      Nothing else about a block is judged: a damaged block stays damaged and is found by whoever decodes it;
+ *                   6. the tables: d_new_block_first is the exclusive running count of rows, d_new_block_first[n_pick] = nb';
+ *                      d_new_block_off[0 .. nb'] the running sum of the stored lengths, the entries above nb' repeat the total;
+ *                      d_new_block_crc is 0 at and above nb';
+ *                   7. capacity, the writer's rule 9: a block that would end beyond new_cap is not written and its pick gets
+ *                      MSCOMP_BUF_ERROR, which replaces MSCOMP_OK; the tables still hold the full layout, and nothing at or behind
+ *                      new_cap is ever written.
+ *                 Picks may repeat (the resource is duplicated). n_pick = 0 is legal and writes an empty container.
+ *                 Consequence: when every source was written by mscomp_amd_blocks_compress and _crc with one format and one B and is
+ *                 healthy, and every pick is accepted, the new packed bytes, d_new_block_first, d_new_block_off and d_new_block_crc are
+ *                 byte for byte what those two calls write for the picked resources' data in pick order, in a container with
+ *                 n_blocks_max = n_blocks_table.
+ *   Checksums:    with a non-null d_new_block_crc every view must have a d_block_crc (otherwise MSCOMP_ARG_ERROR); with a null one the
+ *                 views' arrays are ignored.
+ *   Execution:    as the writer's: asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation, no
+ *                 synchronisation, nothing read back, two launches fixed by the creation bounds (the layout, one workgroup; the move, a
+ *                 fixed grid); legal inside a caller's capture from the first execution, a graph of its own from the second outside one,
+ *                 captured again when an argument changes -- a field of a view counts as an argument. MSCOMP_ARG_ERROR for a null sp or
+ *                 src, a null d_pick, d_new_res_len or d_status when n_pick > 0, a null d_new_block_first or d_new_block_off, a null
+ *                 d_new_packed unless n_blocks_table is 0, or a view with a null table (or null d_packed with packed_len > 0) while its
+ *                 n_res > 0.
+ *   Left out:     a layout pass tiled over several workgroups (one workgroup scans the picks and the rows: the floor of the call on
+ *                 tables of tens of thousands of rows); splice and write or resize fused in one call; more than four sources per call
+ *                 (splice twice). */
+#define MSCOMP_AMD_SPLICE_SRC_MAX 4u
+typedef struct mscomp_amd_blocks_view {     /* one source container as its writer left it; only read */
+    const uint8_t*  d_packed;  uint64_t packed_len;
+    const uint64_t* d_block_first;          /* n_res + 1 */
+    const uint64_t* d_block_off;            /* n_blocks_table + 1 */
+    const uint64_t* d_res_len;              /* n_res */
+    const uint32_t* d_block_crc;            /* n_blocks_table, may be NULL */
+    uint64_t n_res, n_blocks_table;
+} mscomp_amd_blocks_view;
+typedef struct mscomp_amd_splicer mscomp_amd_splicer;
+MSCompStatus mscomp_amd_splicer_create(mscomp_amd_ctx* ctx, uint32_t block_size, uint32_t n_src, size_t n_pick,
+                                       uint64_t n_blocks_table /* of the NEW container */, uint32_t flags, mscomp_amd_splicer** sp);
+void         mscomp_amd_splicer_destroy(mscomp_amd_splicer* sp);
+MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* sp, const mscomp_amd_blocks_view* src /* host array, n_src */,
+                                       const uint64_t* d_pick /* 2 n_pick: source, resource */,
+                                       uint8_t* d_new_packed, uint64_t new_cap,
+                                       uint64_t* d_new_block_first /* n_pick + 1 */, uint64_t* d_new_block_off /* n_blocks_table + 1 */,
+                                       uint32_t* d_new_block_crc /* n_blocks_table, may be NULL */,
+                                       uint64_t* d_new_res_len /* n_pick */, int32_t* d_status /* n_pick */);
+
 /* Resource checksums from block checksums. After a write or a resize the block CRC-32s are current and the resource CRC-32s that
  * mscomp_amd_blocks_crc once wrote are stale; the block checksums determine them, and no data has to be read:
  *   d_res_crc[r] = XOR over the resource's blocks j of d_block_crc[j] x^(8 d_j)  (mod the CRC polynomial), d_j = the resource's bytes behind block j

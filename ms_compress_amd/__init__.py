@@ -13,4 +13,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   BlockContainer, blocks_compress, blocks_decompress,
                   CrcDevPlan, crc32_units, blocks_crc,
                   BlockReader, blocks_read,
-                  BlockWriter, blocks_write, blocks_resize, res_crc_dev, res_crc_from_blocks)
+                  BlockWriter, blocks_write, blocks_resize, res_crc_dev, res_crc_from_blocks,
+                  BlockSplicer, BlocksView, blocks_splice, MSCOMP_AMD_SPLICE_SRC_MAX)

@@ -44,8 +44,16 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_reader_create", "mscomp_amd_reader_destroy", "mscomp_amd_reader_read", "mscomp_amd_reader_counts",
     "mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_write", "mscomp_amd_writer_counts",
     "mscomp_amd_writer_resize", "mscomp_amd_res_crc_dev",
+    "mscomp_amd_splicer_create", "mscomp_amd_splicer_destroy", "mscomp_amd_splicer_splice",
 ]
+MSCOMP_AMD_SPLICE_SRC_MAX = 4
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
+
+
+class BlocksView(C.Structure):
+    """mscomp_amd_blocks_view: one source container of a splice, as device addresses"""
+    _fields_ = [("d_packed", C.c_void_p), ("packed_len", C.c_uint64), ("d_block_first", C.c_void_p), ("d_block_off", C.c_void_p),
+                ("d_res_len", C.c_void_p), ("d_block_crc", C.c_void_p), ("n_res", C.c_uint64), ("n_blocks_table", C.c_uint64)]
 
 
 class MSCompError(RuntimeError):
@@ -173,6 +181,12 @@ def load_library():
     lib.mscomp_amd_writer_resize.restype = C.c_int
     lib.mscomp_amd_res_crc_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint64] + [C.c_void_p] * 5
     lib.mscomp_amd_res_crc_dev.restype = C.c_int
+    lib.mscomp_amd_splicer_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_splicer_create.restype = C.c_int
+    lib.mscomp_amd_splicer_destroy.argtypes = [C.c_void_p]
+    lib.mscomp_amd_splicer_destroy.restype = None
+    lib.mscomp_amd_splicer_splice.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
+    lib.mscomp_amd_splicer_splice.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -844,6 +858,96 @@ def blocks_resize(fmt, packed, block_first, block_off, lengths, block_size, new_
     if own:
         ctx.close()
     return new_packed, noff, ncrc, nfirst, [int(x) for x in h_len[:n]], [int(x) for x in h_rst[:n]]
+
+
+class BlockSplicer(_Handle):
+    """A block splicer (mscomp_amd_splicer_create): a new container made of ``n_pick`` picks (source, resource) out of ``n_src`` (1 .. 4)
+    source containers of one format and one ``block_size``, without decoding a byte; ``n_blocks_table`` is the number of rows of the NEW
+    container's table. All scratch is reserved here: 8 bytes per row of that table + 64. splice() enqueues two kernels on the ctx stream
+    and nothing else (legal inside a capture of that stream). Arguments are torch CUDA tensors: uint8 data, int64 / uint64 tables, int32
+    statuses and checksums."""
+    _destroy = "mscomp_amd_splicer_destroy"
+
+    def __init__(self, ctx, block_size, n_src, n_pick, n_blocks_table):
+        _Handle.__init__(self, ctx)
+        self.block_size, self.n_src, self.n_pick, self.n_blocks_table = int(block_size), int(n_src), int(n_pick), int(n_blocks_table)
+        _ok(ctx.lib.mscomp_amd_splicer_create(ctx._h, self.block_size, self.n_src, self.n_pick, self.n_blocks_table, 0, C.byref(self._h)),
+            "mscomp_amd_splicer_create")
+
+    def splice(self, sources, d_pick, d_new_packed, d_new_block_first, d_new_block_off, d_new_res_len, d_status, d_new_block_crc=None, new_cap=None):
+        """``sources``: n_src tuples (d_packed, d_block_first, d_block_off, d_res_len, d_block_crc or None, packed_len or None = all of
+        d_packed) or objects with these attributes; a source has d_res_len.numel() resources and d_block_off.numel() - 1 table rows unless
+        it says otherwise (``n_res``, ``n_blocks_table``). Pick p = (d_pick[2 p], d_pick[2 p + 1]) = (source, resource) becomes resource p
+        of the new container: d_new_block_first (n_pick + 1), d_new_block_off (n_blocks_table + 1), d_new_block_crc (optional; every source
+        needs checksums then), d_new_res_len and d_status (n_pick), the stored blocks to d_new_packed (nothing at or behind ``new_cap``,
+        default: all of it). d_status[p] is MSCOMP_OK, MSCOMP_ARG_ERROR (no such source or resource, a broken table entry, or no room in
+        the new table) or MSCOMP_DATA_ERROR (a wrong block count) with pick p an empty resource, or MSCOMP_BUF_ERROR (a block did not fit
+        below new_cap)."""
+        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
+        if d_new_packed is not None and cap > d_new_packed.numel():
+            raise ValueError("new_cap exceeds d_new_packed")
+        if len(sources) != self.n_src:
+            raise ValueError("one source per n_src")
+        views = (BlocksView * self.n_src)()
+        names = ("d_packed", "d_block_first", "d_block_off", "d_res_len", "d_block_crc", "packed_len", "n_res", "n_blocks_table")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        for v, s in zip(views, sources):
+            f = dict(zip(names, s)) if isinstance(s, (tuple, list)) else {k: getattr(s, k, None) for k in names}
+            v.d_packed, v.d_block_first, v.d_block_off = ptr(f["d_packed"]), ptr(f["d_block_first"]), ptr(f["d_block_off"])
+            v.d_res_len, v.d_block_crc = ptr(f["d_res_len"]), ptr(f.get("d_block_crc"))
+            plen = f.get("packed_len")
+            v.packed_len = (0 if f["d_packed"] is None else f["d_packed"].numel()) if plen is None else int(plen)
+            nr, nt = f.get("n_res"), f.get("n_blocks_table")
+            v.n_res = (0 if f["d_res_len"] is None else f["d_res_len"].numel()) if nr is None else int(nr)
+            v.n_blocks_table = (0 if f["d_block_off"] is None else max(0, f["d_block_off"].numel() - 1)) if nt is None else int(nt)
+        p = _ptrs(d_pick, d_new_packed, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_status)
+        _ok(self.ctx.lib.mscomp_amd_splicer_splice(self._h, views, p[0], p[1], cap, *p[2:]), "mscomp_amd_splicer_splice")
+
+
+def blocks_splice(containers, picks, block_size, ctx=None):
+    """A new block container from resources of up to four others on the GPU (BlockSplicer), no block decoded: ``containers`` is a list of
+    (packed, block_first, block_off, lengths, block_crc or None) of one format and ``block_size``, ``picks`` a list of (container,
+    resource): pick p becomes resource p. The new container gets checksums when every source has them. Returns numpy arrays and lists
+    (new_packed uint8, new_first uint64 of n + 1, new_block_off uint64 of nb + 1, new_lengths, new_block_crc uint32 or None, statuses)."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    B = int(block_size)
+    M64 = (1 << 64) - 1
+    npk = len(picks)
+    lens = [[int(x) for x in c[3]] for c in containers]
+    got = [lens[s][r] if 0 <= s < len(lens) and 0 <= r < len(lens[s]) else 0 for s, r in picks]
+    nbt = sum((L + B - 1) // B for L in got)
+    room = sum(got)
+    with_crc = all(c[4] is not None for c in containers)
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        sp = BlockSplicer(ctx, B, len(containers), npk, nbt)
+        srcs = []
+        for (packed, first, off, _, crc), ln in zip(containers, lens):
+            packed, d_packed = _dev_packed(packed, dev)
+            rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
+            srcs.append((d_packed, _dev_u64(first, len(ln) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(ln, 1, dev),
+                         _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(ln), rows))
+        d_pick = _dev_u64(np.array([(int(s) & M64, int(r) & M64) for s, r in picks], dtype=np.uint64), 2, dev)
+        d_new = torch.zeros(room + 16, dtype=torch.uint8, device=dev)
+        d_nfirst = torch.zeros(npk + 1, dtype=torch.int64, device=dev)
+        d_noff = torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
+        d_ncrc = torch.zeros(max(1, nbt), dtype=torch.int32, device=dev) if with_crc else None
+        d_nlen = torch.zeros(max(1, npk), dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, npk), dtype=torch.int32, device=dev)
+        sp.splice(srcs, d_pick, d_new, d_nfirst, d_noff, d_nlen, d_st, d_new_block_crc=d_ncrc, new_cap=room)
+        ctx.stream.synchronize()
+        nfirst = d_nfirst.cpu().numpy().view(np.uint64).copy()
+        nb = int(nfirst[npk])
+        noff = d_noff.cpu().numpy().view(np.uint64)[: nb + 1].copy()
+        new_packed = d_new.cpu().numpy()[: min(int(noff[nb]), room)].copy()
+        ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nb].copy()
+        h_len, h_st = d_nlen.cpu().numpy().view(np.uint64), d_st.cpu().numpy()
+        sp.close()
+    if own:
+        ctx.close()
+    return new_packed, nfirst, noff, [int(x) for x in h_len[:npk]], ncrc, [int(x) for x in h_st[:npk]]
 
 
 def res_crc_from_blocks(block_first, lengths, block_crc, block_size, ctx=None):

@@ -1,4 +1,4 @@
-// blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h): containers, readers and writers. Host orchestration only, as
+// blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h): containers, readers, writers and splicers. Host orchestration only, as
 // api.hip: each call runs the launches of inner dev plans (dev_launch) between its own passes, through plan_run.
 #include "host.h"
 
@@ -429,6 +429,71 @@ MSCompStatus mscomp_amd_writer_resize(mscomp_amd_writer* w, const uint8_t* d_pac
 		                                                             d_want_len, d_block_crc, rt, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_res_status); }
 		{ KernelTimer k(c, "rs_move_kernel"); launch_resize_move(c->stream, w->n_res, w->nbt, w->shift, new_cap, d_packed, d_block_first, d_block_off, stage, cache,
 		                                                         d_new_block_first, d_new_block_off, rt, d_new_packed, c->cpd_blocks); }
+	});
+}
+
+// ---- block splicers (include/mscomp_amd.h; kernels: splice.hip) ----
+// A splicer holds one column -- the address of every new row's stored bytes -- and the graph of its call. The sources are read on the host
+// and go into the kernel arguments by value, so every field of a view is part of the graph's key.
+struct mscomp_amd_splicer {
+	mscomp_amd_ctx* ctx = nullptr;
+	uint32_t shift = 0, n_src = 0, n_pick = 0, nbt = 0;    // block_size = 1 << shift; nbt = n_blocks_table of the NEW container
+	mscomp_amd_plan run;
+	DevBuf addr;                                           // u64 x nbt
+};
+static_assert(sizeof(mscomp_amd_blocks_view) == sizeof(SpliceView) && sizeof(SpliceView) == 8 * sizeof(void*), "a view is eight words of the graph's key");
+
+MSCompStatus mscomp_amd_splicer_create(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_pick, uint64_t n_blocks_table, uint32_t flags,
+                                       mscomp_amd_splicer** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
+	if (n_src == 0 || n_src > MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_pick) || !count_ok(n_blocks_table)) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_splicer> s(new (std::nothrow) mscomp_amd_splicer());
+	if (!s) { return MSCOMP_MEM_ERROR; }
+	s->ctx = c; s->shift = (uint32_t)__builtin_ctz(block_size); s->n_src = n_src; s->n_pick = (uint32_t)n_pick; s->nbt = (uint32_t)n_blocks_table;
+	s->run.ctx = c; s->run.n_units = 1;                    // (an empty pick list writes an empty container: it replays too)
+	if (!s->addr.reserve(8 * (size_t)n_blocks_table + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	*out = s.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_splicer_destroy(mscomp_amd_splicer* s)
+{
+	if (!s) { return; }
+	DeviceGuard g(s->ctx->device);
+	(void)hipStreamSynchronize(s->ctx->stream);
+	s->addr.release();
+	delete s;                                              // (run gives up its graph)
+}
+
+MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* s, const mscomp_amd_blocks_view* src, const uint64_t* d_pick, uint8_t* d_new_packed, uint64_t new_cap,
+                                       uint64_t* d_new_block_first, uint64_t* d_new_block_off, uint32_t* d_new_block_crc, uint64_t* d_new_res_len, int32_t* d_status)
+{
+	if (!s || !src || !d_new_block_first || !d_new_block_off || (s->nbt && !d_new_packed)) { return MSCOMP_ARG_ERROR; }
+	if (s->n_pick && (!d_pick || !d_new_res_len || !d_status)) { return MSCOMP_ARG_ERROR; }
+	SpliceSrc k{};
+	for (uint32_t i = 0; i < s->n_src; ++i) {
+		const mscomp_amd_blocks_view& v = src[i];
+		if (v.n_res && (!v.d_block_first || !v.d_block_off || !v.d_res_len || (v.packed_len && !v.d_packed))) { return MSCOMP_ARG_ERROR; }
+		if (d_new_block_crc && !v.d_block_crc) { return MSCOMP_ARG_ERROR; }
+		k.v[i] = { v.d_packed, v.packed_len, v.d_block_first, v.d_block_off, v.d_res_len, d_new_block_crc ? v.d_block_crc : nullptr, v.n_res, v.n_blocks_table };
+	}
+	mscomp_amd_ctx* c = s->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[40] = {};
+	memcpy(args, &k, sizeof k);
+	const void* rest[8] = { d_pick, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_status };
+	memcpy(args + 32, rest, sizeof rest);
+	u64* addr = static_cast<u64*>(s->addr.p);
+	return plan_run(&s->run, args, [&] {
+		{ KernelTimer t(c, "sp_layout_kernel"); launch_splice_layout(c->stream, k, s->n_src, s->n_pick, s->nbt, s->shift, new_cap, d_pick, d_new_block_first, d_new_block_off,
+		                                                             d_new_block_crc, d_new_res_len, d_status, addr); }
+		{ KernelTimer t(c, "sp_move_kernel"); launch_splice_move(c->stream, s->nbt, new_cap, d_new_block_off, addr, d_new_packed, c->cpd_blocks); }
 	});
 }
 

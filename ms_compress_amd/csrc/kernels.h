@@ -334,6 +334,24 @@ void launch_resize_layout(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t
 void launch_resize_move(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* packed, const u64* block_first, const u64* block_off,
                         const uint8_t* stage, const uint8_t* cache, const u64* new_first, const u64* new_off, const ResizeTab& t, uint8_t* dst, uint32_t blocks);
 
+// ---- block splicers (splice.hip; mscomp_amd_splicer_*) ----
+// One source container of a splice as the kernels take it (the fields of mscomp_amd_blocks_view), and the sources of a call: they travel by
+// value in the kernel arguments, the unused ones zeroed.
+struct SpliceView {
+	const uint8_t* packed; u64 packed_len;
+	const u64* first; const u64* off; const u64* res_len;  // n_res + 1, nbt + 1, n_res
+	const uint32_t* crc;                               // nbt (read only when the new container gets checksums)
+	u64 n_res, nbt;
+};
+struct SpliceSrc { SpliceView v[4]; };
+// one block: rules 1-3 per pick (pick: 2 n_pick, source and resource), new_first (n_pick + 1), new_len and status (n_pick), then per NEW row
+// new_off (nbt + 1), new_crc (nbt, may be null) and addr (nbt: where the row's stored bytes lie, 0 for nothing to move), then rule 7
+void launch_splice_layout(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n_pick, uint32_t nbt, uint32_t shift, u64 cap, const u64* pick,
+                          u64* new_first, u64* new_off, uint32_t* new_crc, u64* new_len, int32_t* status, u64* addr);
+// every new row with an address to dst + new_off[row], runs of back-to-back rows as one copy; nothing at or behind dst + cap
+// (`blocks` = compact_dev_blocks())
+void launch_splice_move(hipStream_t st, uint32_t nbt, u64 cap, const u64* new_off, const u64* addr, uint8_t* dst, uint32_t blocks);
+
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status
 // MSCOMP_ARG_ERROR), off[i] = its offset. in_off / off and status may be null.
