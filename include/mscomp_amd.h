@@ -543,7 +543,7 @@ int          mscomp_amd_reader_counts(mscomp_amd_reader* rd, uint32_t out[3]);
  *                 (MSCOMP_ARG_ERROR; MSCOMP_MEM_ERROR where blocks_max B bytes are more than a dev plan can address), flags 0, *wr cleared
  *                 on failure. All scratch is reserved here, once, and never grows: a block cache of blocks_max B bytes, a staging area of
  *                 blocks_max B bytes, a decompress and a compress dev plan for blocks_max units within blocks_max B bytes each, and the
- *                 writer's tables: 96 bytes per unit of blocks_max, 44 per request, 8 per entry of the block table and -- for
+ *                 writer's tables: 96 bytes per unit of blocks_max, 44 per request, 16 per entry of the block table and -- for
  *                 mscomp_amd_writer_resize -- 12 per resource + 8. The LZNT1 dictionary flavour is fixed here, as for
  *                 mscomp_amd_blocks_create.
  *   Out of place: the old container is d_packed (packed_len valid bytes), d_block_off (n_blocks_table + 1) and d_block_crc (n_blocks_table,

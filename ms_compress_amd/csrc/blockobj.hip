@@ -202,13 +202,13 @@ struct BlockAccess {
 };
 struct mscomp_amd_reader : BlockAccess {};
 // A writer adds an inner compress dev plan over the same units (a dirty block is compressed from its cache slot into its staging slot), the
-// staging area and three more columns. Its call runs the reader's passes up to the fold, then its own. Its second call, resize, runs on
+// staging area and four more columns. Its call runs the reader's passes up to the fold, then its own. Its second call, resize, runs on
 // the same scratch with a record of its own (rrun: write and resize keep separate graphs) and two columns per resource.
 struct mscomp_amd_writer : BlockAccess {
 	mscomp_amd_plan* cplan = nullptr;                  // (null when blocks_max is 0)
 	mscomp_amd_plan rrun;
 	DevBuf stage;                                      // blocks_max slots of block_size bytes
-	uint32_t* head = nullptr; uint32_t* next = nullptr; uint32_t* dirty = nullptr;   // the rest of WriterTab
+	uint32_t* head = nullptr; uint32_t* next = nullptr; uint32_t* dirty = nullptr; uint64_t* addr = nullptr;   // the rest of WriterTab
 	uint64_t* ru_first = nullptr; int32_t* rstat = nullptr;                          // the rest of ResizeTab
 	bool resized = false;                              // the last execution was a resize (mscomp_amd_writer_counts)
 };
@@ -221,7 +221,7 @@ static uintptr_t access_tab(BlockAccess* a, mscomp_amd_writer* w, void* base)
 	ReaderTab& t = a->t;
 	t.q_off = k.q(n); t.q_want = k.q(n); t.q_j0 = k.q(n); t.q_len = k.q(n); t.unit_first = k.q(n + 1);
 	t.in_off = k.q(m); t.in_len = k.q(m); t.out_off = k.q(m); t.out_cap = k.q(m); t.ulen = k.q(m); t.src = k.q(m); t.clen = k.q(m); t.cum = k.q(m + 1);
-	if (w) { w->ru_first = k.q((size_t)a->n_res + 1); }
+	if (w) { w->ru_first = k.q((size_t)a->n_res + 1); w->addr = k.q(nbt); }
 	t.q_stat = k.i(n); t.ustat = k.i(m);
 	t.act = k.w(m); t.owner = k.w(m); t.uq = k.w(m); t.ublk = k.w(m); t.ucrc = k.w(m);
 	t.own = k.w(nbt); t.cnt = k.w(w ? 4 : 2);
@@ -375,7 +375,7 @@ MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* w, const uint8_t* d_pack
 	                         d_written, d_status, d_res_status };
 	return plan_run(&w->run, args, [&] {
 		const ReaderTab& t = w->t;
-		const WriterTab wt = { t, w->head, w->next, w->dirty };
+		const WriterTab wt = { t, w->head, w->next, w->dirty, w->addr };
 		uint8_t* cache = static_cast<uint8_t*>(w->cache.p); uint8_t* stage = static_cast<uint8_t*>(w->stage.p);
 		// the reader's passes: admission (without its capacity rule), owners, the owners' blocks decoded, checksummed and judged
 		access_admit(w, d_packed, packed_len, d_block_first, d_block_off, d_res_len, d_req, nullptr);
@@ -385,9 +385,9 @@ MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* w, const uint8_t* d_pack
 		{ KernelTimer k(c, "wr_patch"); launch_writer_patch(c->stream, w->n_req, w->m, w->shift, d_src, d_src_off, cache, wt, c->cpd_blocks); }
 		if (w->cplan) { dev_launch(w->cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
 		if (d_block_crc && w->m) { crc_pass(c, w->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }
-		{ KernelTimer k(c, "wr_layout_kernel"); launch_writer_layout(c->stream, w->n_req, w->n_res, w->nbt, w->m, packed_len, new_cap, d_block_first, d_block_off, d_block_crc,
-		                                                             wt, d_new_block_off, d_new_block_crc, d_written, d_status, d_res_status); }
-		{ KernelTimer k(c, "wr_move_kernel"); launch_writer_move(c->stream, w->nbt, w->shift, new_cap, d_packed, d_block_off, stage, cache, d_new_block_off, wt, d_new_packed, c->cpd_blocks); }
+		{ KernelTimer k(c, "wr_layout_kernel"); launch_writer_layout(c->stream, w->n_req, w->n_res, w->nbt, w->m, w->shift, packed_len, new_cap, d_packed, stage, cache, d_block_first,
+		                                                             d_block_off, d_block_crc, wt, d_new_block_off, d_new_block_crc, d_written, d_status, d_res_status); }
+		{ KernelTimer k(c, "bk_move_kernel"); launch_blocks_move(c->stream, w->nbt, new_cap, d_new_block_off, w->addr, d_new_packed, c->cpd_blocks); }
 	});
 }
 
@@ -415,7 +415,7 @@ MSCompStatus mscomp_amd_writer_resize(mscomp_amd_writer* w, const uint8_t* d_pac
 	                         d_new_res_len, d_res_status };
 	return plan_run(&w->rrun, args, [&] {
 		const ReaderTab& t = w->t;
-		const ResizeTab rt = { { t, w->head, w->next, w->dirty }, w->ru_first, w->rstat };
+		const ResizeTab rt = { { t, w->head, w->next, w->dirty, w->addr }, w->ru_first, w->rstat };
 		uint8_t* cache = static_cast<uint8_t*>(w->cache.p); uint8_t* stage = static_cast<uint8_t*>(w->stage.p);
 		{ KernelTimer k(c, "rs_units"); launch_resize_units(c->stream, w->n_res, w->nbt, w->m, w->shift, packed_len, d_packed, cache, d_block_first, d_block_off,
 		                                                    d_res_len, d_want_len, rt); }
@@ -425,14 +425,13 @@ MSCompStatus mscomp_amd_writer_resize(mscomp_amd_writer* w, const uint8_t* d_pac
 		{ KernelTimer k(c, "rs_fill"); launch_resize_fill(c->stream, w->n_res, w->m, w->shift, cache, rt, c->cpd_blocks); }
 		if (w->cplan) { dev_launch(w->cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
 		if (d_block_crc && w->m) { crc_pass(c, w->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }
-		{ KernelTimer k(c, "rs_layout_kernel"); launch_resize_layout(c->stream, w->n_res, w->nbt, w->shift, packed_len, new_cap, d_block_first, d_block_off, d_res_len,
-		                                                             d_want_len, d_block_crc, rt, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_res_status); }
-		{ KernelTimer k(c, "rs_move_kernel"); launch_resize_move(c->stream, w->n_res, w->nbt, w->shift, new_cap, d_packed, d_block_first, d_block_off, stage, cache,
-		                                                         d_new_block_first, d_new_block_off, rt, d_new_packed, c->cpd_blocks); }
+		{ KernelTimer k(c, "rs_layout_kernel"); launch_resize_layout(c->stream, w->n_res, w->nbt, w->shift, packed_len, new_cap, d_packed, stage, cache, d_block_first, d_block_off,
+		                                                             d_res_len, d_want_len, d_block_crc, rt, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_res_status); }
+		{ KernelTimer k(c, "bk_move_kernel"); launch_blocks_move(c->stream, w->nbt, new_cap, d_new_block_off, w->addr, d_new_packed, c->cpd_blocks); }
 	});
 }
 
-// ---- block splicers (include/mscomp_amd.h; kernels: splice.hip) ----
+// ---- block splicers (include/mscomp_amd.h; kernels: splice.hip, the move in blocks.hip) ----
 // A splicer holds one column -- the address of every new row's stored bytes -- and the graph of its call. The sources are read on the host
 // and go into the kernel arguments by value, so every field of a view is part of the graph's key.
 struct mscomp_amd_splicer {
@@ -493,7 +492,7 @@ MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* s, const mscomp_amd_b
 	return plan_run(&s->run, args, [&] {
 		{ KernelTimer t(c, "sp_layout_kernel"); launch_splice_layout(c->stream, k, s->n_src, s->n_pick, s->nbt, s->shift, new_cap, d_pick, d_new_block_first, d_new_block_off,
 		                                                             d_new_block_crc, d_new_res_len, d_status, addr); }
-		{ KernelTimer t(c, "sp_move_kernel"); launch_splice_move(c->stream, s->nbt, new_cap, d_new_block_off, addr, d_new_packed, c->cpd_blocks); }
+		{ KernelTimer t(c, "bk_move_kernel"); launch_blocks_move(c->stream, s->nbt, new_cap, d_new_block_off, addr, d_new_packed, c->cpd_blocks); }
 	});
 }
 

@@ -291,6 +291,49 @@ __global__ __launch_bounds__(256) void bk_kfold_kernel(uint32_t n_res, const u64
 	if (lane == 0 && (st != 0 || any_bad)) { d_status[r] = st != 0 ? st : -3; d_out_len[r] = 0; }   // MSCOMP_DATA_ERROR
 }
 
+// ---- move (the last pass of mscomp_amd_writer_write, _writer_resize and mscomp_amd_splicer_splice) ----
+// The only pass over a whole new container, and it knows nothing of where a row's bytes come from: the call's layout pass wrote addr[row],
+// the address of the row's stored bytes, or 0 for a row that is not moved (nothing stored, unreadable, or ending beyond cap). The new byte
+// range [0, min(total, cap)) is cut into equal slices, one per block of a fixed grid, as compaction cuts it (cpd_copy_kernel); a workgroup
+// finds the row its slice starts in and walks on from there, 64 table rows looked at at once, a row per lane. The rows from j on whose
+// address lies as far from their new offset as row j's lie back to back at the source too, so they are ONE copy shifted by a constant:
+// the untouched rows of an old container, consecutive picks of consecutive resources, raw dirty blocks in consecutive cache slots. A run
+// ends where the source, or the place in it, changes. A refused table has new_off all zeros: the range is empty.
+__global__ __launch_bounds__(CPD_THREADS) void bk_move_kernel(uint32_t nbt, u64 cap, const u64* __restrict__ new_off, const u64* __restrict__ addr,
+                                                             uint8_t* __restrict__ dst)
+{
+	const uint32_t tid = threadIdx.x, lane = tid & 63u;
+	const u64 total = new_off[nbt], range = total < cap ? total : cap;
+	u64 per = (range + gridDim.x - 1u) / gridDim.x;
+	per = (per + 4095u) & ~(u64)4095u;
+	const u64 lo = (u64)blockIdx.x * per;
+	if (lo >= range) { return; }
+	const u64 hi = range - lo < per ? range : lo + per;
+	uint32_t j = 0, b = nbt;                                             // the first row with new_off[j + 1] > lo (there is one: new_off[nbt] > lo)
+	while (j < b) { const uint32_t mid = j + (b - j) / 2u; if (new_off[mid + 1u] > lo) { b = mid; } else { j = mid + 1u; } }
+	while (j < nbt) {
+		const u64 o = new_off[j];
+		if (o >= hi) { break; }
+		const uint32_t row = j + lane;
+		u64 e0 = 0, e1 = 0, at = 0;
+		if (row < nbt) { e0 = new_off[row]; e1 = new_off[row + 1u]; at = addr[row]; }
+		const u64 at0 = __shfl(at, 0, 64);
+		const u64 others = ~__ballot(at != 0 && at - e0 == at0 - o);
+		const uint32_t k = others ? (uint32_t)__ffsll((unsigned long long)others) - 1u : 64u;   // rows of the run from j on (the same in every wave of the block)
+		if (k == 0) { ++j; continue; }
+		const u64 end = __shfl(e1, (int)k - 1, 64);
+		j += k;
+		const u64 d0 = o > lo ? o : lo, d1 = end < hi ? end : hi;
+		if (d0 < d1) { cpd_move<false>(dst + d0, reinterpret_cast<const uint8_t*>((uintptr_t)at0) + (d0 - o), d1 - d0, tid); }
+	}
+}
+
+void launch_blocks_move(hipStream_t st, uint32_t nbt, u64 cap, const u64* new_off, const u64* addr, uint8_t* dst, uint32_t blocks)
+{
+	if (nbt == 0) { return; }
+	hipLaunchKernelGGL(bk_move_kernel, dim3(blocks), dim3(CPD_THREADS), 0, st, nbt, cap, new_off, addr, dst);
+}
+
 void launch_blocks_ctables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* res_off, const u64* res_len,
                            u64* block_first, const BlocksTab& t)
 {

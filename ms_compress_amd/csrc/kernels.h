@@ -221,7 +221,7 @@ void launch_dev_ctables(hipStream_t st, int format, uint32_t n, u64 in_total_max
 void launch_clayout_dev(hipStream_t st, int format, const u64* in_len, uint32_t n, u64 align, u64* off, u64* cap);
 
 // ---- block containers (blocks.hip; mscomp_amd_blocks_*) ----
-// The container's own tables, in one buffer (api.hip blocks_tab is the only place that knows the layout). n = resources, m = the bound of
+// The container's own tables, in one buffer (blockobj.hip blocks_tab is the only place that knows the layout). n = resources, m = the bound of
 // the blocks; the seven unit columns are what the inner dev plans read and write, with the container's blocks (compress) or the blocks in
 // range (decompress) as units.
 struct BlocksTab {
@@ -256,9 +256,12 @@ void launch_blocks_crcgroups(hipStream_t st, uint32_t n_res, uint32_t nbmax, uin
 void launch_blocks_ktables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* res_len, const u64* block_first,
                            const u64* range, const u64* d_out_off, const int32_t* d_status, const BlocksTab& t);
 void launch_blocks_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_crc, const BlocksTab& t, u64* d_out_len, int32_t* d_status);
+// the last pass of a write, a resize and a splice: every row of the new table (nbt) with a non-zero addr[row] to dst + new_off[row], runs of rows
+// whose addr - new_off is constant as one copy; nothing at or behind dst + cap (`blocks` = compact_dev_blocks())
+void launch_blocks_move(hipStream_t st, uint32_t nbt, u64 cap, const u64* new_off, const u64* addr, uint8_t* dst, uint32_t blocks);
 
 // ---- block readers (reader.hip; mscomp_amd_reader_*) ----
-// The reader's own tables, in one buffer (api.hip reader_tab is the only place that knows the layout). n = requests, m = blocks_max: the
+// The reader's own tables, in one buffer (blockobj.hip access_tab is the only place that knows the layout). n = requests, m = blocks_max: the
 // bound of the units, a unit being one (request, covering block) pair of an admitted request; nbt = the entries of the container's block table.
 struct ReaderTab {
 	u64 *q_off, *q_want, *q_j0, *q_len;                // n each: clipped offset, bytes wanted, container index of the first covering block, the resource's length
@@ -284,13 +287,14 @@ void launch_reader_fold(hipStream_t st, uint32_t n_req, const uint32_t* block_cr
 void launch_reader_gather(hipStream_t st, uint32_t n_req, uint32_t m, uint32_t shift, uint8_t* out, const u64* out_off, const ReaderTab& t, uint32_t blocks);
 
 // ---- block writers (writer.hip; mscomp_amd_writer_*) ----
-// A writer admits, shares, decodes and judges with the reader's passes, on a ReaderTab of its own, and adds three columns to it (api.hip
-// writer_tab knows the layout).
+// A writer admits, shares, decodes and judges with the reader's passes, on a ReaderTab of its own, and adds four columns to it
+// (blockobj.hip access_tab knows the layout).
 struct WriterTab {
 	ReaderTab r;                                       // (r.cnt has four words here: [2] = dirty blocks, [3] = 1 when the table as a whole was refused)
-	uint32_t* head;                                    // nbt: the last unit that joined a block's list, + 1 (0 = none); behind the layout pass, the move pass's word of the block
+	uint32_t* head;                                    // nbt: the last unit that joined a block's list, + 1 (0 = none)
 	uint32_t* next;                                    // m: the unit that joined the list before this one, + 1
 	uint32_t* dirty;                                   // m: 1 for an owner whose block an MSCOMP_OK request covers
+	u64* addr;                                         // nbt: from the layout pass, where a new row's stored bytes lie (0 = nothing to move): launch_blocks_move
 };
 // behind launch_reader_units: t.head cleared, every unit linked to its block (two launches)
 void launch_writer_link(hipStream_t st, uint32_t n_req, uint32_t nbt, uint32_t m, const WriterTab& t);
@@ -298,14 +302,11 @@ void launch_writer_link(hipStream_t st, uint32_t n_req, uint32_t nbt, uint32_t m
 // compress plan (r.in_off .. r.out_cap) and of the CRC kernels (r.src, r.clen) over the dirty owners (two launches; `blocks` = compact_dev_blocks())
 void launch_writer_patch(hipStream_t st, uint32_t n_req, uint32_t m, uint32_t shift, const uint8_t* src, const u64* src_off, uint8_t* cache,
                          const WriterTab& t, uint32_t blocks);
-// behind the compress plan and the CRC kernels, one block: rule 0, new_off (nbt + 1), new_crc (nbt, may be null with block_crc), the move pass's
-// words, d_res_status, and -- for a refused table -- d_status and d_written
-void launch_writer_layout(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, u64 packed_len, u64 cap, const u64* block_first,
-                          const u64* block_off, const uint32_t* block_crc, const WriterTab& t, u64* new_off, uint32_t* new_crc, u64* d_written,
-                          int32_t* d_status, int32_t* d_res_status);
-// every block to dst + new_off[j]: clean ones from packed, dirty ones from stage or cache; nothing at or behind dst + cap
-void launch_writer_move(hipStream_t st, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* packed, const u64* block_off, const uint8_t* stage,
-                        const uint8_t* cache, const u64* new_off, const WriterTab& t, uint8_t* dst, uint32_t blocks);
+// behind the compress plan and the CRC kernels, one block: rule 0, new_off (nbt + 1), new_crc (nbt, may be null with block_crc), t.addr (clean
+// blocks in packed, dirty ones in stage or cache), d_res_status, and -- for a refused table -- d_status and d_written
+void launch_writer_layout(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, u64 packed_len, u64 cap, const uint8_t* packed,
+                          const uint8_t* stage, const uint8_t* cache, const u64* block_first, const u64* block_off, const uint32_t* block_crc, const WriterTab& t,
+                          u64* new_off, uint32_t* new_crc, u64* d_written, int32_t* d_status, int32_t* d_res_status);
 
 // mscomp_amd_writer_resize, the writer's second call: the same tables, and two columns per resource behind them. A unit is a block whose
 // data changes: the changed block of an admitted resource (its unit 0, when there is one), then its fresh blocks in order. Of the unit
@@ -326,13 +327,10 @@ void launch_resize_fold(hipStream_t st, uint32_t n_res, uint32_t m, uint32_t shi
 // and of the CRC kernels over them (two launches; `blocks` = compact_dev_blocks())
 void launch_resize_fill(hipStream_t st, uint32_t n_res, uint32_t m, uint32_t shift, uint8_t* cache, const ResizeTab& t, uint32_t blocks);
 // behind the compress plan and the CRC kernels, one block: new_first (n_res + 1), rule 8, new_off (nbt + 1), new_crc (nbt, may be null with
-// block_crc), the move pass's word per NEW row (t.w.head), new_len and res_status (n_res)
-void launch_resize_layout(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 packed_len, u64 cap, const u64* block_first, const u64* block_off,
-                          const u64* res_len, const u64* want, const uint32_t* block_crc, const ResizeTab& t, u64* new_first, u64* new_off, uint32_t* new_crc,
-                          u64* new_len, int32_t* res_status);
-// every new row to dst + new_off[row]: clean ones from their old row in packed, dirty ones from stage or cache; nothing at or behind dst + cap
-void launch_resize_move(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* packed, const u64* block_first, const u64* block_off,
-                        const uint8_t* stage, const uint8_t* cache, const u64* new_first, const u64* new_off, const ResizeTab& t, uint8_t* dst, uint32_t blocks);
+// block_crc), t.w.addr per NEW row (clean ones at their old row in packed, dirty ones in stage or cache), new_len and res_status (n_res)
+void launch_resize_layout(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 packed_len, u64 cap, const uint8_t* packed, const uint8_t* stage,
+                          const uint8_t* cache, const u64* block_first, const u64* block_off, const u64* res_len, const u64* want, const uint32_t* block_crc,
+                          const ResizeTab& t, u64* new_first, u64* new_off, uint32_t* new_crc, u64* new_len, int32_t* res_status);
 
 // ---- block splicers (splice.hip; mscomp_amd_splicer_*) ----
 // One source container of a splice as the kernels take it (the fields of mscomp_amd_blocks_view), and the sources of a call: they travel by
@@ -345,12 +343,9 @@ struct SpliceView {
 };
 struct SpliceSrc { SpliceView v[4]; };
 // one block: rules 1-3 per pick (pick: 2 n_pick, source and resource), new_first (n_pick + 1), new_len and status (n_pick), then per NEW row
-// new_off (nbt + 1), new_crc (nbt, may be null) and addr (nbt: where the row's stored bytes lie, 0 for nothing to move), then rule 7
+// new_off (nbt + 1), new_crc (nbt, may be null) and addr (nbt, for launch_blocks_move), then rule 7
 void launch_splice_layout(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n_pick, uint32_t nbt, uint32_t shift, u64 cap, const u64* pick,
                           u64* new_first, u64* new_off, uint32_t* new_crc, u64* new_len, int32_t* status, u64* addr);
-// every new row with an address to dst + new_off[row], runs of back-to-back rows as one copy; nothing at or behind dst + cap
-// (`blocks` = compact_dev_blocks())
-void launch_splice_move(hipStream_t st, uint32_t nbt, u64 cap, const u64* new_off, const u64* addr, uint8_t* dst, uint32_t blocks);
 
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status

@@ -1,7 +1,8 @@
 // splice.hip -- the passes of a block splicer (mscomp_amd_splicer_*, include/mscomp_amd.h): a new block container made of picks
 // (source, resource) out of up to four source containers. No block is decoded or encoded: the stored form of a block depends only on its
 // data, the format and the block size, so the layout pass hands every row of the new table the ADDRESS of its stored bytes and the move
-// pass carries them, back-to-back rows of one source as one copy. The sources travel by value in the kernel arguments. DESIGN.md 4.12.
+// pass (blocks.hip bk_move_kernel) carries them, back-to-back rows of one source as one copy. The sources travel by value in the kernel
+// arguments. DESIGN.md 4.12.
 #include "kernels.h"
 
 namespace msc {
@@ -82,49 +83,10 @@ __global__ __launch_bounds__(DV_THREADS) void sp_layout_kernel(SpliceView v0, Sp
 	}
 }
 
-// Move, in the shape of rs_move_kernel: equal slices of the new byte range below cap over a fixed grid, 64 new table rows looked at at once.
-// The rows from j on whose address lies as far from their new offset as row j's lie back to back in one source too, so they are ONE copy,
-// whichever picks they belong to: consecutive picks of consecutive resources merge, and a run ends where the source, or the place in it,
-// changes. A row without an address (nothing stored, unreadable, or ending beyond cap) is skipped.
-__global__ __launch_bounds__(CPD_THREADS) void sp_move_kernel(uint32_t nbt, u64 cap, const u64* __restrict__ new_off, const u64* __restrict__ addr,
-                                                             uint8_t* __restrict__ dst)
-{
-	const uint32_t tid = threadIdx.x, lane = tid & 63u;
-	const u64 total = new_off[nbt], range = total < cap ? total : cap;
-	u64 per = (range + gridDim.x - 1u) / gridDim.x;
-	per = (per + 4095u) & ~(u64)4095u;
-	const u64 lo = (u64)blockIdx.x * per;
-	if (lo >= range) { return; }
-	const u64 hi = range - lo < per ? range : lo + per;
-	uint32_t j = 0, b = nbt;                                             // the first row with new_off[j + 1] > lo (there is one: new_off[nbt] > lo)
-	while (j < b) { const uint32_t mid = j + (b - j) / 2u; if (new_off[mid + 1u] > lo) { b = mid; } else { j = mid + 1u; } }
-	while (j < nbt) {
-		const u64 o = new_off[j];
-		if (o >= hi) { break; }
-		const uint32_t row = j + lane;
-		u64 e0 = 0, e1 = 0, at = 0;
-		if (row < nbt) { e0 = new_off[row]; e1 = new_off[row + 1u]; at = addr[row]; }
-		const u64 at0 = __shfl(at, 0, 64);
-		const u64 others = ~__ballot(at != 0 && at - e0 == at0 - o);
-		const uint32_t k = others ? (uint32_t)__ffsll((unsigned long long)others) - 1u : 64u;   // rows of the run from j on (the same in every wave of the block)
-		if (k == 0) { ++j; continue; }
-		const u64 end = __shfl(e1, (int)k - 1, 64);
-		j += k;
-		const u64 d0 = o > lo ? o : lo, d1 = end < hi ? end : hi;
-		if (d0 < d1) { cpd_move<false>(dst + d0, reinterpret_cast<const uint8_t*>((uintptr_t)at0) + (d0 - o), d1 - d0, tid); }
-	}
-}
-
 void launch_splice_layout(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n_pick, uint32_t nbt, uint32_t shift, u64 cap, const u64* pick,
                           u64* new_first, u64* new_off, uint32_t* new_crc, u64* new_len, int32_t* status, u64* addr)
 {
 	hipLaunchKernelGGL(sp_layout_kernel, dim3(1), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n_src, n_pick, nbt, shift, cap, pick, new_first, new_off, new_crc, new_len, status, addr);
-}
-
-void launch_splice_move(hipStream_t st, uint32_t nbt, u64 cap, const u64* new_off, const u64* addr, uint8_t* dst, uint32_t blocks)
-{
-	if (nbt == 0) { return; }
-	hipLaunchKernelGGL(sp_move_kernel, dim3(blocks), dim3(CPD_THREADS), 0, st, nbt, cap, new_off, addr, dst);
 }
 
 } // namespace msc

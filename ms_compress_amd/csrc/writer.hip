@@ -2,17 +2,14 @@
 // out of place. The requests are admitted, the covering blocks get their owners, and the owners' blocks are decoded, checksummed and folded
 // into verdicts by the reader's passes (reader.hip, unchanged: a write reads every block it touches first). Behind the fold the passes of
 // this file load the raw owners into their cache slots and apply the MSCOMP_OK requests in request order, hand the dirty blocks to a
-// compress dev plan and the CRC kernels (api.hip runs both between these passes, unchanged), lay the new container out around them and move
-// every block -- clean ones from the old container, dirty ones from the staging area or the cache -- to its new place. DESIGN.md 4.10.
+// compress dev plan and the CRC kernels (blockobj.hip runs both between these passes, unchanged) and lay the new container out around them:
+// every block's new offset, checksum and the ADDRESS of its stored bytes -- a clean one's in the old container, a dirty one's in the staging
+// area or the cache --, which the containers' move pass (blocks.hip bk_move_kernel) carries to their new places. DESIGN.md 4.10.
 // mscomp_amd_writer_resize (the rs_* kernels below) is the writer's second call: every resource cut or zero-extended to a
 // wanted length, the one block whose data length changes and the fresh blocks as the units, the same inner plans, CRC kernels and scratch.
 #include "kernels.h"
 
 namespace msc {
-
-#define WR_CLEAN 0u                                       // the move pass's word of a block: stored bytes carried over from d_packed
-#define WR_NONE  1u                                       // nothing to move (no such block, a stored length of 0, an unreadable table entry)
-#define WR_DIRTY 2u                                       // from here on: 2 + 2 * owner unit + (1: the staged bytes, 0: the cache slot, raw)
 
 // One thread per possible unit: the unit joins the list of its block (head[j] = the last unit that came, + 1; next[u] = the one before it).
 // The order of a list is the order the hardware ran the units in; the patch pass sorts it.
@@ -108,26 +105,55 @@ __global__ __launch_bounds__(256) void wr_patch_kernel(uint32_t n_req, uint32_t 
 	}
 }
 
-// One thread per possible unit, behind the patch: a dirty owner becomes a unit of the inner compress plan -- its cache slot in, its staging
-// slot out, capacity e - 1 as a block container gives it -- and of the CRC kernels; every other unit is empty in both. The columns are the
-// ones the decompress plan and the old blocks' CRC used: the fold has read them.
+// Unit u of the inner compress plan and of the CRC kernels: with `on`, the e data bytes in its cache slot in, its staging slot out, capacity
+// e - 1 as a block container gives it; otherwise empty in both (e = 0).
+__device__ __forceinline__ void wr_cunit(const ReaderTab& r, uint32_t u, bool on, u64 e, uint32_t shift, const uint8_t* __restrict__ cache)
+{
+	const u64 at = on ? (u64)u << shift : 0;
+	r.in_off[u] = at; r.in_len[u] = e; r.out_off[u] = at; r.out_cap[u] = on ? e - 1u : 0;
+	r.src[u] = on ? (u64)(uintptr_t)(cache + at) : 0; r.clen[u] = e;
+}
+
+// One thread per possible unit, behind the patch: a dirty owner becomes a unit of the inner compress plan and of the CRC kernels; every
+// other unit is empty in both. The columns are the ones the decompress plan and the old blocks' CRC used: the fold has read them.
 __global__ __launch_bounds__(256) void wr_cunits_kernel(uint32_t n_req, uint32_t m, uint32_t shift, const uint8_t* __restrict__ cache, WriterTab t)
 {
 	const uint32_t u = blockIdx.x * 256u + threadIdx.x;
 	if (u >= m) { return; }
-	const ReaderTab& r = t.r;
-	const bool d = u < r.unit_first[n_req] && t.dirty[u] != 0;
-	const u64 e = d ? r.act[u] >> 2 : 0, at = d ? (u64)u << shift : 0;
-	r.in_off[u] = at; r.in_len[u] = e; r.out_off[u] = at; r.out_cap[u] = d ? e - 1u : 0;
-	r.src[u] = d ? (u64)(uintptr_t)(cache + at) : 0; r.clen[u] = e;
+	const bool d = u < t.r.unit_first[n_req] && t.dirty[u] != 0;
+	wr_cunit(t.r, u, d, d ? t.r.act[u] >> 2 : 0, shift, cache);
 }
 
-// Layout, one block. Rule 0 first: the table as a whole (block_first[n_res] within the table, block_first never decreasing). Then one scan
-// over the block table: the new stored length of every block -- a dirty one's from the compress plan (the staged bytes when they fitted
-// into e - 1, the raw block otherwise: bk_select_kernel's rule), a clean one's from the old table, 0 for an entry that cannot be read --,
-// new_block_off, the merged CRC table, and the move pass's word per block (in t.head, which the patch is done with). Then the resources'
-// statuses by the capacity rule of a block container; a refused table overwrites what the fold reported for the requests.
-__global__ __launch_bounds__(DV_THREADS) void wr_layout_kernel(uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, u64 packed_len, u64 cap,
+// Rule 0, asked by a whole block of DV_THREADS: the table as a whole (block_first[n_res] within the table, block_first never decreasing)
+__device__ __forceinline__ bool wr_table_bad(uint32_t n_res, uint32_t nbt, const u64* __restrict__ block_first)
+{
+	int wrong = block_first[n_res] > nbt ? 1 : 0;
+	for (uint32_t i = threadIdx.x; i < n_res; i += DV_THREADS) { if (block_first[i] > block_first[i + 1u]) { wrong = 1; } }
+	return __syncthreads_or(wrong) != 0;
+}
+
+// One row of a new table: its stored length, checksum and where its stored bytes lie. A dirty row is unit u with e data bytes: its stored
+// form by bk_select_kernel's rule from the compress plan's results (the staged bytes when they fitted into e - 1, the raw block in the cache
+// otherwise). A clean row is row `old` of the old table, length 0 for an entry that cannot be read.
+__device__ __forceinline__ void wr_row(const ReaderTab& r, bool dirty, u64 u, u64 e, uint32_t shift, const uint8_t* __restrict__ stage, const uint8_t* __restrict__ cache,
+                                       u64 old, const uint8_t* __restrict__ packed, u64 packed_len, const u64* __restrict__ block_off, const uint32_t* __restrict__ block_crc,
+                                       u64& len, uint32_t& crc, u64& at)
+{
+	if (dirty) {
+		const bool comp = r.ustat[u] == 0 && r.ulen[u] < e;
+		len = comp ? r.ulen[u] : e; crc = r.ucrc[u]; at = (u64)(uintptr_t)((comp ? stage : cache) + (u << shift));
+	} else {
+		const u64 o0 = block_off[old], o1 = block_off[old + 1u];
+		len = o0 <= o1 && o1 <= packed_len ? o1 - o0 : 0; crc = block_crc ? block_crc[old] : 0u; at = (u64)(uintptr_t)(packed + o0);
+	}
+}
+
+// Layout, one block. Rule 0 first. Then one scan over the block table: every block's row (wr_row: a dirty owner's block, or the same row
+// of the old table), new_block_off, the merged CRC table, and the move pass's address per block -- 0 for a block without stored bytes or
+// ending beyond cap. Then the resources' statuses by the capacity rule of a block container; a refused table is all empty rows (new_off
+// all zeros: the move pass has no range), and overwrites what the fold reported for the requests.
+__global__ __launch_bounds__(DV_THREADS) void wr_layout_kernel(uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, u64 packed_len, u64 cap,
+                                                              const uint8_t* __restrict__ packed, const uint8_t* __restrict__ stage, const uint8_t* __restrict__ cache,
                                                               const u64* __restrict__ block_first, const u64* __restrict__ block_off, const uint32_t* __restrict__ block_crc,
                                                               WriterTab t, u64* new_off, uint32_t* __restrict__ new_crc, u64* __restrict__ d_written,
                                                               int32_t* __restrict__ d_status, int32_t* __restrict__ d_res_status)
@@ -136,31 +162,22 @@ __global__ __launch_bounds__(DV_THREADS) void wr_layout_kernel(uint32_t n_req, u
 	const uint32_t tid = threadIdx.x;
 	const ReaderTab& r = t.r;
 	const u64 nb = block_first[n_res];
-	int wrong = nb > nbt ? 1 : 0;
-	for (uint32_t i = tid; i < n_res; i += DV_THREADS) { if (block_first[i] > block_first[i + 1u]) { wrong = 1; } }
-	const bool bad = __syncthreads_or(wrong) != 0;
+	const bool bad = wr_table_bad(n_res, nbt, block_first);
 	if (tid == 0) { r.cnt[3] = bad ? 1u : 0u; new_off[0] = 0; }
 	u64 run[1] = {0};
 	for (uint32_t base = 0; base < nbt; base += DV_THREADS) {
 		const uint32_t j = base + tid;
 		const bool live = j < nbt;
-		u64 len = 0;
-		uint32_t crc = 0, word = WR_NONE;
+		u64 len = 0, at = 0;
+		uint32_t crc = 0;
 		if (live && !bad && j < nb) {
 			const uint32_t bid = m ? r.own[j] : 0u, o = ~bid;                 // (own is cleared and bid for only when a call can have units)
-			if (bid != 0 && t.dirty[o] != 0) {
-				const u64 e = r.act[o] >> 2;
-				const bool comp = r.ustat[o] == 0 && r.ulen[o] < e;
-				len = comp ? r.ulen[o] : e; crc = r.ucrc[o]; word = WR_DIRTY + 2u * o + (comp ? 1u : 0u);
-			} else {
-				const u64 o0 = block_off[j], o1 = block_off[j + 1u];
-				if (o0 <= o1 && o1 <= packed_len) { len = o1 - o0; }
-				crc = block_crc ? block_crc[j] : 0u; word = len ? WR_CLEAN : WR_NONE;
-			}
+			const bool dirty = bid != 0 && t.dirty[o] != 0;
+			wr_row(r, dirty, o, dirty ? r.act[o] >> 2 : 0, shift, stage, cache, j, packed, packed_len, block_off, block_crc, len, crc, at);
 		}
 		u64 v[1] = {len};
 		dv_block_scan<1>(v, run, s_w);
-		if (live) { new_off[j + 1u] = v[0]; t.head[j] = word; if (new_crc) { new_crc[j] = crc; } }
+		if (live) { new_off[j + 1u] = v[0]; t.addr[j] = (len != 0 && v[0] <= cap) ? at : 0; if (new_crc) { new_crc[j] = crc; } }
 	}
 	__syncthreads();                                                     // new_off is read back below, by other threads of this block
 	for (uint32_t i = tid; i < n_res; i += DV_THREADS) {
@@ -168,49 +185,6 @@ __global__ __launch_bounds__(DV_THREADS) void wr_layout_kernel(uint32_t n_req, u
 		d_res_status[i] = bad ? -2 : (f1 > f0 && new_off[f1] > cap) ? -5 : 0;   // MSCOMP_ARG_ERROR; MSCOMP_BUF_ERROR (the offsets only grow: the last block tells)
 	}
 	if (bad) { for (uint32_t q = tid; q < n_req; q += DV_THREADS) { d_status[q] = -2; d_written[q] = 0; } }
-}
-
-// Move: the only pass over the whole container. The new byte range [0, min(total, cap)) is cut into equal slices, one per block of a fixed
-// grid, as compaction cuts it (cpd_copy_kernel); a workgroup finds the block its slice starts in and walks on from there. 64 table rows
-// are looked at at once, a row per lane: the clean blocks in front of the first row that is not clean lie back to back in d_packed and go
-// back to back into the new container, so they are ONE copy that is shifted by a constant -- a container of small blocks with a few dirty
-// ones moves in long runs, not block by block. A dirty block comes from its staging slot or, raw, from its cache slot. A block that would
-// end beyond cap is not written, nor is anything behind it.
-__global__ __launch_bounds__(CPD_THREADS) void wr_move_kernel(uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* __restrict__ packed, const u64* __restrict__ block_off,
-                                                             const uint8_t* __restrict__ stage, const uint8_t* __restrict__ cache, const u64* __restrict__ new_off,
-                                                             const uint32_t* __restrict__ word, const uint32_t* __restrict__ cnt, uint8_t* __restrict__ dst)
-{
-	if (cnt[3] != 0) { return; }                                         // a refused table: nothing is written
-	const uint32_t tid = threadIdx.x, lane = tid & 63u;
-	const u64 total = new_off[nbt], range = total < cap ? total : cap;
-	u64 per = (range + gridDim.x - 1u) / gridDim.x;
-	per = (per + 4095u) & ~(u64)4095u;
-	const u64 lo = (u64)blockIdx.x * per;
-	if (lo >= range) { return; }
-	const u64 hi = range - lo < per ? range : lo + per;
-	uint32_t j = 0, b = nbt;                                             // the first block with new_off[j + 1] > lo (there is one: new_off[nbt] > lo)
-	while (j < b) { const uint32_t mid = j + (b - j) / 2u; if (new_off[mid + 1u] > lo) { b = mid; } else { j = mid + 1u; } }
-	while (j < nbt) {
-		const u64 o = new_off[j];
-		if (o >= hi) { break; }
-		const uint32_t row = j + lane;
-		u64 e1 = 0;
-		bool clean = false;
-		if (row < nbt) { e1 = new_off[row + 1u]; clean = word[row] == WR_CLEAN && e1 <= cap; }
-		const u64 others = ~__ballot(clean);
-		const uint32_t k = others ? (uint32_t)__ffsll((unsigned long long)others) - 1u : 64u;   // clean rows from j on (the same in every wave of the block)
-		const uint8_t* s = nullptr;
-		u64 end = o;
-		if (k) { end = __shfl(e1, (int)k - 1, 64); s = packed + block_off[j]; j += k; }
-		else {
-			const uint32_t wd = word[j];
-			end = new_off[j + 1u];
-			if (wd >= WR_DIRTY && end <= cap) { s = ((wd & 1u) ? stage : cache) + ((u64)((wd - WR_DIRTY) >> 1) << shift); }
-			++j;
-		}
-		const u64 d0 = o > lo ? o : lo, d1 = end < hi ? end : hi;
-		if (s && d0 < d1) { cpd_move<false>(dst + d0, s + (d0 - o), d1 - d0, tid); }
-	}
 }
 
 // ---- resize (mscomp_amd_writer_resize) ----
@@ -234,18 +208,16 @@ __device__ __forceinline__ RsGeo rs_geo(u64 L, u64 W, u64 n, uint32_t shift)
 	return g;
 }
 
-// One block walks the resources in tiles of 1024. Rule 0 first (the table as a whole: a refused table has no units, cnt[3] says so to the
-// passes behind). Then rules 1-3 per resource, as rd_req_kernel runs the reader's: the cost of every resource that passed rules 1 and 2 in
-// one scan (the budget's running total, refused ones included), the cost of the admitted ones in a second (the unit numbering, ru_first).
+// One block walks the resources in tiles of 1024. Rule 0 first (a refused table has no units, cnt[3] says so to the passes behind). Then
+// rules 1-3 per resource, as rd_req_kernel runs the reader's: the cost of every resource that passed rules 1 and 2 in one scan (the
+// budget's running total, refused ones included), the cost of the admitted ones in a second (the unit numbering, ru_first).
 __global__ __launch_bounds__(DV_THREADS) void rs_res_kernel(uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, const u64* __restrict__ block_first,
                                                            const u64* __restrict__ res_len, const u64* __restrict__ want, ResizeTab t)
 {
 	__shared__ u64 s_w[1][DV_WAVES];
 	const uint32_t tid = threadIdx.x;
 	const u64 B = (u64)1 << shift;
-	int wrong = block_first[n_res] > nbt ? 1 : 0;
-	for (uint32_t i = tid; i < n_res; i += DV_THREADS) { if (block_first[i] > block_first[i + 1u]) { wrong = 1; } }
-	const bool bad = __syncthreads_or(wrong) != 0;
+	const bool bad = wr_table_bad(n_res, nbt, block_first);
 	if (tid == 0) { t.ru_first[0] = 0; t.w.r.cnt[0] = 0; t.w.r.cnt[1] = 0; t.w.r.cnt[2] = 0; t.w.r.cnt[3] = bad ? 1u : 0u; }
 	u64 run[1] = {0}, acc[1] = {0};
 	for (uint32_t base = 0; base < n_res; base += DV_THREADS) {
@@ -380,28 +352,27 @@ __global__ __launch_bounds__(256) void rs_fill_kernel(uint32_t n_res, uint32_t s
 	}
 }
 
-// One thread per possible unit, behind the fill: a unit of an accepted resource becomes a unit of the inner compress plan -- cache slot in,
-// staging slot out, capacity e2 - 1 -- and of the CRC kernels, as wr_cunits_kernel makes a dirty owner one; every other unit is empty in
-// both. cnt[2] counts them: the blocks encoded.
+// One thread per possible unit, behind the fill: a unit of an accepted resource becomes a unit of the inner compress plan and of the CRC
+// kernels, e2 bytes long, as wr_cunits_kernel makes a dirty owner one; every other unit is empty in both. cnt[2] counts them: the blocks encoded.
 __global__ __launch_bounds__(256) void rs_cunits_kernel(uint32_t n_res, uint32_t m, uint32_t shift, const uint8_t* __restrict__ cache, ResizeTab t)
 {
 	const uint32_t u = blockIdx.x * 256u + threadIdx.x;
 	if (u >= m) { return; }
 	const ReaderTab& rt = t.w.r;
 	const bool d = u < t.ru_first[n_res] && t.rstat[rt.uq[u]] == 0;
-	const u64 e2 = d ? rt.owner[u] : 0, at = d ? (u64)u << shift : 0;
-	rt.in_off[u] = at; rt.in_len[u] = e2; rt.out_off[u] = at; rt.out_cap[u] = d ? e2 - 1u : 0;
-	rt.src[u] = d ? (u64)(uintptr_t)(cache + at) : 0; rt.clen[u] = e2; t.w.dirty[u] = d ? 1u : 0u;
+	wr_cunit(rt, u, d, d ? rt.owner[u] : 0, shift, cache);
+	t.w.dirty[u] = d ? 1u : 0u;
 	const u64 enc = __ballot(d);
 	if ((threadIdx.x & 63u) == 0 && enc) { atomicAdd(&rt.cnt[2], (uint32_t)__popcll(enc)); }
 }
 
 // Layout, one block. A scan over the resources gives the final block counts -- n2 for an accepted resource, n for a carried one -- and
 // new_first; rule 8 holds their sum against the table. A scan over the NEW table rows then gives every row its stored length, checksum and
-// move word (in t.head): a row finds its resource by binary search in new_first and is the changed block or a fresh one of an accepted
-// resource -- dirty, its stored form by bk_select_kernel's rule from the compress plan's results -- or a kept block, clean at old row
-// block_first[r] + k. Then the resources' statuses and lengths. A refused table (rule 0 or 8) writes zeros and MSCOMP_ARG_ERROR only.
-__global__ __launch_bounds__(DV_THREADS) void rs_layout_kernel(uint32_t n_res, uint32_t nbt, uint32_t shift, u64 packed_len, u64 cap, const u64* __restrict__ block_first,
+// address (wr_row): a row finds its resource by binary search in new_first and is the changed block or a fresh one of an accepted
+// resource -- dirty -- or a kept block, clean at old row block_first[r] + k. Then the resources' statuses and lengths. A refused table
+// (rule 0 or 8) writes zeros and MSCOMP_ARG_ERROR only: new_off is all zeros, the move pass has no range and reads no address.
+__global__ __launch_bounds__(DV_THREADS) void rs_layout_kernel(uint32_t n_res, uint32_t nbt, uint32_t shift, u64 packed_len, u64 cap, const uint8_t* __restrict__ packed,
+                                                              const uint8_t* __restrict__ stage, const uint8_t* __restrict__ cache, const u64* __restrict__ block_first,
                                                               const u64* __restrict__ block_off, const u64* __restrict__ res_len, const u64* __restrict__ want,
                                                               const uint32_t* __restrict__ block_crc, ResizeTab t, u64* new_first, u64* new_off,
                                                               uint32_t* __restrict__ new_crc, u64* __restrict__ new_len, int32_t* __restrict__ res_status)
@@ -437,8 +408,8 @@ __global__ __launch_bounds__(DV_THREADS) void rs_layout_kernel(uint32_t n_res, u
 	for (uint32_t base = 0; base < nbt; base += DV_THREADS) {
 		const uint32_t j = base + tid;
 		const bool live = j < nbt;
-		u64 len = 0;
-		uint32_t crc = 0, word = WR_NONE;
+		u64 len = 0, at = 0;
+		uint32_t crc = 0;
 		if (live && j < nbn) {
 			const uint32_t r = res_of_block(new_first, n_res, j);
 			const u64 k = j - new_first[r], f0 = block_first[r], n = block_first[r + 1u] - f0, L = res_len[r], W = want[r];
@@ -449,18 +420,11 @@ __global__ __launch_bounds__(DV_THREADS) void rs_layout_kernel(uint32_t n_res, u
 				if (g.changed && k == g.kc) { dirty = true; u = t.ru_first[r]; e2 = g.e2; }
 				else if (k >= n) { dirty = true; u = t.ru_first[r] + (g.changed ? 1u : 0u) + (k - n); const u64 left = W - (k << shift); e2 = left < B ? left : B; }
 			}
-			if (dirty) {
-				const bool comp = rt.ustat[u] == 0 && rt.ulen[u] < e2;
-				len = comp ? rt.ulen[u] : e2; crc = rt.ucrc[u]; word = WR_DIRTY + 2u * (uint32_t)u + (comp ? 1u : 0u);
-			} else {
-				const u64 o0 = block_off[f0 + k], o1 = block_off[f0 + k + 1u];
-				if (o0 <= o1 && o1 <= packed_len) { len = o1 - o0; }
-				crc = block_crc ? block_crc[f0 + k] : 0u; word = len ? WR_CLEAN : WR_NONE;
-			}
+			wr_row(rt, dirty, u, e2, shift, stage, cache, f0 + k, packed, packed_len, block_off, block_crc, len, crc, at);
 		}
 		u64 v[1] = {len};
 		dv_block_scan<1>(v, sum, s_w);
-		if (live) { new_off[j + 1u] = v[0]; t.w.head[j] = word; if (new_crc) { new_crc[j] = crc; } }
+		if (live) { new_off[j + 1u] = v[0]; t.w.addr[j] = (len != 0 && v[0] <= cap) ? at : 0; if (new_crc) { new_crc[j] = crc; } }
 	}
 	__syncthreads();                                                     // new_off is read back below
 	for (uint32_t r = tid; r < n_res; r += DV_THREADS) {
@@ -468,52 +432,6 @@ __global__ __launch_bounds__(DV_THREADS) void rs_layout_kernel(uint32_t n_res, u
 		const int32_t st = t.rstat[r];
 		res_status[r] = (n1 > n0 && new_off[n1] > cap) ? -5 : st;           // MSCOMP_BUF_ERROR replaces what the resource had (the offsets only grow: the last block tells)
 		new_len[r] = st == 0 ? want[r] : res_len[r];
-	}
-}
-
-// Move, in the shape of wr_move_kernel: equal slices of the new byte range over a fixed grid, 64 new table rows looked at at once. A clean
-// row's old row is block_first[r] + (row - new_first[r]); the clean rows from j on whose old row lies as far from the new one as row j's
-// follow one another in the old table too, so they are ONE copy shifted by a constant. The distance changes only where a resource in
-// between grew, shrank or was carried: runs break at resource boundaries, and nowhere else.
-__global__ __launch_bounds__(CPD_THREADS) void rs_move_kernel(uint32_t n_res, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* __restrict__ packed,
-                                                             const u64* __restrict__ block_first, const u64* __restrict__ block_off, const uint8_t* __restrict__ stage,
-                                                             const uint8_t* __restrict__ cache, const u64* __restrict__ new_first, const u64* __restrict__ new_off,
-                                                             const uint32_t* __restrict__ word, const uint32_t* __restrict__ cnt, uint8_t* __restrict__ dst)
-{
-	if (cnt[3] != 0) { return; }                                         // a refused table: nothing is written
-	const uint32_t tid = threadIdx.x, lane = tid & 63u;
-	const u64 total = new_off[nbt], range = total < cap ? total : cap;
-	u64 per = (range + gridDim.x - 1u) / gridDim.x;
-	per = (per + 4095u) & ~(u64)4095u;
-	const u64 lo = (u64)blockIdx.x * per;
-	if (lo >= range) { return; }
-	const u64 hi = range - lo < per ? range : lo + per;
-	uint32_t j = 0, b = nbt;                                             // the first row with new_off[j + 1] > lo (there is one: new_off[nbt] > lo)
-	while (j < b) { const uint32_t mid = j + (b - j) / 2u; if (new_off[mid + 1u] > lo) { b = mid; } else { j = mid + 1u; } }
-	while (j < nbt) {
-		const u64 o = new_off[j];
-		if (o >= hi) { break; }
-		const uint32_t row = j + lane;
-		u64 e1 = 0, old = 0;
-		bool clean = false;
-		if (row < nbt) {
-			e1 = new_off[row + 1u]; clean = word[row] == WR_CLEAN && e1 <= cap;
-			if (clean) { const uint32_t r = res_of_block(new_first, n_res, row); old = block_first[r] + (row - new_first[r]); }   // (a clean row lies below new_first[n_res])
-		}
-		const u64 old0 = __shfl(old, 0, 64);
-		const u64 others = ~__ballot(clean && old - row == old0 - j);
-		const uint32_t k = others ? (uint32_t)__ffsll((unsigned long long)others) - 1u : 64u;   // rows of the run from j on (the same in every wave of the block)
-		const uint8_t* s = nullptr;
-		u64 end = o;
-		if (k) { end = __shfl(e1, (int)k - 1, 64); s = packed + block_off[old0]; j += k; }
-		else {
-			const uint32_t wd = word[j];
-			end = new_off[j + 1u];
-			if (wd >= WR_DIRTY && end <= cap) { s = ((wd & 1u) ? stage : cache) + ((u64)((wd - WR_DIRTY) >> 1) << shift); }
-			++j;
-		}
-		const u64 d0 = o > lo ? o : lo, d1 = end < hi ? end : hi;
-		if (s && d0 < d1) { cpd_move<false>(dst + d0, s + (d0 - o), d1 - d0, tid); }
 	}
 }
 
@@ -534,19 +452,12 @@ void launch_writer_patch(hipStream_t st, uint32_t n_req, uint32_t m, uint32_t sh
 	hipLaunchKernelGGL(wr_cunits_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, n_req, m, shift, cache, t);
 }
 
-void launch_writer_layout(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, u64 packed_len, u64 cap, const u64* block_first,
-                          const u64* block_off, const uint32_t* block_crc, const WriterTab& t, u64* new_off, uint32_t* new_crc, u64* d_written,
-                          int32_t* d_status, int32_t* d_res_status)
+void launch_writer_layout(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, u64 packed_len, u64 cap, const uint8_t* packed,
+                          const uint8_t* stage, const uint8_t* cache, const u64* block_first, const u64* block_off, const uint32_t* block_crc, const WriterTab& t,
+                          u64* new_off, uint32_t* new_crc, u64* d_written, int32_t* d_status, int32_t* d_res_status)
 {
-	hipLaunchKernelGGL(wr_layout_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_req, n_res, nbt, m, packed_len, cap, block_first, block_off, block_crc, t,
-	                   new_off, new_crc, d_written, d_status, d_res_status);
-}
-
-void launch_writer_move(hipStream_t st, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* packed, const u64* block_off, const uint8_t* stage,
-                        const uint8_t* cache, const u64* new_off, const WriterTab& t, uint8_t* dst, uint32_t blocks)
-{
-	if (nbt == 0) { return; }
-	hipLaunchKernelGGL(wr_move_kernel, dim3(blocks), dim3(CPD_THREADS), 0, st, nbt, shift, cap, packed, block_off, stage, cache, new_off, t.head, t.r.cnt, dst);
+	hipLaunchKernelGGL(wr_layout_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_req, n_res, nbt, m, shift, packed_len, cap, packed, stage, cache, block_first, block_off,
+	                   block_crc, t, new_off, new_crc, d_written, d_status, d_res_status);
 }
 
 void launch_resize_units(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, u64 packed_len, const uint8_t* packed, const uint8_t* cache,
@@ -573,20 +484,12 @@ void launch_resize_fill(hipStream_t st, uint32_t n_res, uint32_t m, uint32_t shi
 	hipLaunchKernelGGL(rs_cunits_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, n_res, m, shift, cache, t);
 }
 
-void launch_resize_layout(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 packed_len, u64 cap, const u64* block_first, const u64* block_off,
-                          const u64* res_len, const u64* want, const uint32_t* block_crc, const ResizeTab& t, u64* new_first, u64* new_off, uint32_t* new_crc,
-                          u64* new_len, int32_t* res_status)
+void launch_resize_layout(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 packed_len, u64 cap, const uint8_t* packed, const uint8_t* stage,
+                          const uint8_t* cache, const u64* block_first, const u64* block_off, const u64* res_len, const u64* want, const uint32_t* block_crc,
+                          const ResizeTab& t, u64* new_first, u64* new_off, uint32_t* new_crc, u64* new_len, int32_t* res_status)
 {
-	hipLaunchKernelGGL(rs_layout_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_res, nbt, shift, packed_len, cap, block_first, block_off, res_len, want, block_crc, t,
-	                   new_first, new_off, new_crc, new_len, res_status);
-}
-
-void launch_resize_move(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, u64 cap, const uint8_t* packed, const u64* block_first, const u64* block_off,
-                        const uint8_t* stage, const uint8_t* cache, const u64* new_first, const u64* new_off, const ResizeTab& t, uint8_t* dst, uint32_t blocks)
-{
-	if (nbt == 0) { return; }
-	hipLaunchKernelGGL(rs_move_kernel, dim3(blocks), dim3(CPD_THREADS), 0, st, n_res, nbt, shift, cap, packed, block_first, block_off, stage, cache, new_first, new_off,
-	                   t.w.head, t.w.r.cnt, dst);
+	hipLaunchKernelGGL(rs_layout_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_res, nbt, shift, packed_len, cap, packed, stage, cache, block_first, block_off, res_len, want,
+	                   block_crc, t, new_first, new_off, new_crc, new_len, res_status);
 }
 
 } // namespace msc

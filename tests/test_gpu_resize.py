@@ -12,6 +12,7 @@ import read_model as R
 import resize_model as Z
 import write_model as W
 from test_gpu_read import Rig, _d64, FMTS, BLOCKS, FILL, ALL, MIXED, TEXT, ZEROS5, MIXED5, RANDOM1
+from test_gpu_write import long_runs_rig
 from test_resize_model import SPARE, mixes
 
 pytestmark = pytest.mark.gpu
@@ -277,6 +278,39 @@ def test_damage(rigs, oracle, fmt, B):
     d_hurt = rig.d_packed.clone(); d_hurt[at] = int(hurt[at])
     mo, got = zs.check(oracle, want, packed=d_hurt, model_packed=bytes(hurt))
     assert mo["res_status"] == [M.ARG] * n and not got["off"].any() and mo["counts"] == (0, 0, 0)
+
+
+def test_long_runs_and_slice_edges(gpu_ctx, oracle):
+    """the move pass where its runs matter, on the container of test_gpu_write.long_runs_rig: (a) 311 clean rows in one run that is shifted by
+    a row as well as by bytes; (b) a clean run that ends at its resource's changed block, the resource behind it a run at another distance;
+    (c) the long resource carried with MSCOMP_DATA_ERROR between two that change; (d) as (b), new_cap inside the long resource"""
+    rig, g = long_runs_rig(gpu_ctx)
+    zs, B, lens = Resizes(rig), rig.B, rig.lens
+    # (a) the first cut to 1 byte, the last extended by 2 B + 5
+    want = [1, lens[1], lens[2] + 2 * B + 5]
+    mo, got = zs.check(oracle, want)
+    g2 = int(got["first"][1])
+    assert mo["res_status"] == [0] * 3 and mo["new_len"] == want and g2 == g - 1 and (int(got["off"][g2]) - int(rig.off[g])) % 16 != 0
+    assert (got["off"][g2: g2 + 312] - got["off"][g2] == rig.off[g: g + 312] - rig.off[g]).all()
+    zs.check_consequence(got, Z.resized(rig.bufs, want))
+    # (b) the long one cut by 100 B + 7: 211 blocks, the last one changed
+    want = [lens[0], lens[1] - (100 * B + 7), lens[2]]
+    full, got = zs.check(oracle, want)
+    assert full["res_status"] == [0] * 3 and full["new_len"] == want and full["counts"] == (1, 1, 1) and int(got["first"][2]) == g + 211
+    assert int(got["off"][g + 211]) - int(rig.off[g + 311]) != int(got["off"][g + 210]) - int(rig.off[g + 210])
+    zs.check_consequence(got, Z.resized(rig.bufs, want))
+    # (c) a length that asks for one block more than the long resource has
+    odd = list(lens); odd[1] += B
+    want = [1, lens[1] - 5, lens[2] + 2 * B + 5]
+    mo, got = zs.check(oracle, want, lens=odd, read_back=False)
+    assert mo["res_status"] == [0, M.DATA, 0] and mo["new_len"] == [1, odd[1], want[2]] and int(got["first"][2]) - int(got["first"][1]) == 311
+    # (d) new_cap one byte into row 100 of the long resource
+    want = [lens[0], lens[1] - (100 * B + 7), lens[2]]
+    at = int(full["off"][g + 100])
+    mo, got = zs.check(oracle, want, new_cap=at + 1)
+    assert int(full["off"][g + 101]) - at > 1 and mo["res_status"] == [0, M.BUF, M.BUF] and (got["off"] == full["off"]).all()
+    assert len(mo["packed"]) == at and (got["image"][at:] == FILL).all()
+    zs.close()
 
 
 def test_checksum_arrays_come_in_pairs(rigs):

@@ -253,6 +253,53 @@ def test_damage(rigs, oracle, fmt, B):
     assert (got["image"][int(full["off"][int(rig.first[-1]) - 1]):] == FILL).all()
 
 
+def long_runs_rig(ctx):
+    """(Rig, first row of the long resource) of test_gpu_splice's test_long_runs_and_slice_edges container, with its shape assertions: B = 4096,
+    Xpress, a small text resource, one of 311 blocks -- random and text by turns, then 150 blocks of zeros (hundreds of rows within one
+    4096-byte slice of the new container), then text --, a small random one"""
+    B = 4096
+    long = (M.build({"kind": "mixed", "seed": 21, "mult": 100, "add": 0}, B) + bytes(150 * B) + M.build({"kind": "text", "seed": 22, "mult": 60, "add": 17}, B))
+    small = [M.build({"kind": "text", "seed": 23, "mult": 1, "add": 5}, B), M.build({"kind": "random", "seed": 24, "mult": 0, "add": 77}, B)]
+    rig = Rig(ctx, FMTS["xpress"], B, [small[0], long, small[1]])
+    stored = np.diff(rig.off[: int(rig.first[-1]) + 1].astype(np.int64))
+    assert int(rig.first[2] - rig.first[1]) == 311 and len(set(stored.tolist())) > 20 and (stored[120:240] < 64).all()
+    return rig, int(rig.first[1])
+
+
+def test_long_runs_and_slice_edges(gpu_ctx, oracle):
+    """the move pass where its runs matter, on the container of long_runs_rig, one writer per case: (a) clean runs longer than 64 rows between
+    dirty rows, one of them among hundreds of rows that share a 4096-byte slice; (b) every row behind the first shifted by a constant that
+    is no multiple of 16; (c) three raw dirty blocks in consecutive cache slots; (d) as (a), new_cap inside the long resource"""
+    rig, g = long_runs_rig(gpu_ctx)
+    ws, B, LONG = Writes(rig), rig.B, 1
+    stored = lambda off, j: int(off[j + 1] - off[j])
+    rs = np.random.RandomState(31)
+    # (a) 64 bytes into blocks 0, 70, 200 and 310 (its 17 bytes: the request is clipped)
+    a = [(LONG, 100, 64), (LONG, 70 * B + 1000, 64), (LONG, 200 * B + 4000, 64), (LONG, 310 * B, 64)]
+    sa = [rs.bytes(64) for _ in a]
+    full, got = ws.check(oracle, a, sa)
+    assert full["status"] == [0] * 4 and full["written"] == [64, 64, 64, 17] and full["res_status"] == [0] * 3 and full["counts"] == (4, 4, 4)
+    assert stored(full["off"], g + 200) != stored(rig.off, g + 200)                 # the rows behind the zero block move
+    ws.check_rule_10(got, a, sa)
+    # (b) the first small resource's first block changes its stored length
+    b, sb = [(0, 33, 64)], [rs.bytes(64)]
+    mo, got = ws.check(oracle, b, sb)
+    shift = int(mo["off"][g]) - int(rig.off[g])
+    assert mo["status"] == [0] and shift % 16 != 0 and (mo["off"][g:] - rig.off[g:] == np.uint64(shift)).all()
+    ws.check_rule_10(got, b, sb)
+    # (c) 3 B random bytes over blocks 10, 11 and 12: three units in a row, all stored raw
+    c, sc = [(LONG, 10 * B, 3 * B)], [rs.bytes(3 * B)]
+    mo, got = ws.check(oracle, c, sc)
+    assert mo["status"] == [0] and mo["counts"] == (3, 3, 3) and [stored(mo["off"], g + k) for k in (10, 11, 12)] == [B] * 3
+    ws.check_rule_10(got, c, sc)
+    # (d) new_cap one byte into row 150 of the long resource: that row and everything behind it is absent
+    at = int(full["off"][g + 150])
+    mo, got = ws.check(oracle, a, sa, new_cap=at + 1)
+    assert stored(full["off"], g + 150) > 1 and mo["res_status"] == [0, M.BUF, M.BUF] and mo["status"] == [0] * 4
+    assert (got["off"] == full["off"]).all() and len(mo["packed"]) == at and (got["image"][at:] == FILL).all()
+    rig.close()
+
+
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_repeats_and_ping_pong(rigs, oracle, fmt):
     """one writer executed three times with other requests and other source bytes of the same counts (its graph is captured again when an

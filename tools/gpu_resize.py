@@ -22,7 +22,7 @@ from gpu_read import event_ms, tab  # noqa: E402
 
 B, GROW = 65536, 3
 CRC = ("crc_tables_kernel", "crc_seed_kernel", "crc_kernel")
-OWN = {"tables": ("rs_units", "rs_fold_kernel"), "fill": ("rs_fill",), "layout": ("rs_layout_kernel",), "move": ("rs_move_kernel",), "crc": CRC}
+OWN = {"tables": ("rs_units", "rs_fold_kernel"), "fill": ("rs_fill",), "layout": ("rs_layout_kernel",), "move": ("bk_move_kernel",), "crc": CRC}
 
 
 def run(ctx, fmt, files, reps):
@@ -41,8 +41,8 @@ def run(ctx, fmt, files, reps):
     zu8 = lambda: torch.zeros(room + 16, dtype=torch.uint8, device="cuda")
     bk = m.BlockContainer(ctx, fmt, B, n, room)
     nbt = bk.n_blocks_max
-    off, _ = m.pack_offsets([max(a, b) for a, b in zip(lens, want)])
-    blob = np.zeros(room + 16 * n + 16, dtype=np.uint8)
+    off, span = m.pack_offsets([max(a, b) for a, b in zip(lens, want)])
+    blob = np.zeros(span + 16, dtype=np.uint8)
     for o, f in zip(off, files):
         blob[int(o): int(o) + len(f)] = f
     d_in, t_off, t_len, t_want = torch.from_numpy(blob).cuda(), tab(off), tab(lens), tab(want)

@@ -72,7 +72,7 @@ def run(ctx, fmt, B, files, reps):
     splice()
     prof = ctx.profile_read()
     ctx.profile_enable(False)
-    layout_ms, move_ms = prof["sp_layout_kernel"][0], prof["sp_move_kernel"][0]
+    layout_ms, move_ms = prof["sp_layout_kernel"][0], prof["bk_move_kernel"][0]
     d_copy = torch.zeros_like(d_new)
     copy_ms = event_ms(lambda: d_copy[: want.packed_bytes].copy_(d_new[: want.packed_bytes]), reps)
     # what it replaces: decode the rest (the dropped resource's range is empty), compress + crc of it

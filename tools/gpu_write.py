@@ -23,7 +23,7 @@ from gpu_read import event_ms, tab  # noqa: E402
 
 TABLES = ("rd_req_kernel", "rd_units", "wr_link", "rd_fold_kernel")
 CRC = ("crc_tables_kernel", "crc_seed_kernel", "crc_kernel")
-OWN = {"tables": TABLES, "patch": ("wr_patch",), "layout": ("wr_layout_kernel",), "move": ("wr_move_kernel",), "crc": CRC}
+OWN = {"tables": TABLES, "patch": ("wr_patch",), "layout": ("wr_layout_kernel",), "move": ("bk_move_kernel",), "crc": CRC}
 
 
 class Writes:
@@ -142,7 +142,7 @@ def run(ctx, fmt, files, B, reps):
     a.close()
     # (b) 10 000 x 64 bytes: resources by their share of the bytes, offsets uniform
     rs = np.random.RandomState(2024)
-    r = rs.choice(n, size=10000, p=np.asarray(lens, dtype=np.float64) / total)
+    r = rs.choice(n, size=10000, p=np.asarray(lens, dtype=np.float64) / sum(lens))
     o = (rs.random_sample(10000) * (np.asarray(lens)[r] - 64)).astype(np.uint64)
     b = Writes(ctx, fmt, B, n, nbt, lens, total, np.stack([r.astype(np.uint64), o, np.full(10000, 64, dtype=np.uint64)], axis=1), 8)
     b_ms = event_ms(lambda: b.run(c, True), reps)
