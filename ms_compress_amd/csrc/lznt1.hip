@@ -13,11 +13,15 @@
 //   C. window by window (64 positions, lane = position), LAZILY like the reference (Find runs only where the greedy parse
 //      can start a token):
 //        1. every lane at or after the parse position scans the 4 OLDEST candidates of its position itself (unconditional
-//           loads in flight together, own bytes in registers, 16-byte compares, strictly-longer wins);
+//           loads in flight together, strictly-longer wins). Which bucket entries are candidates needs no count: the position is itself
+//           an entry of its bucket, behind its older same-hash positions, so the candidates are the entries in front of the first one
+//           that is not smaller than the position (a prefix-AND of ballots). The compares have two stages: the first 8 bytes always,
+//           bytes 8..15 only if a candidate of some lane of the wave agreed on all 8 and max_len allows more;
 //        2. the greedy walk runs on the scalar unit over ballot masks (s_ff1 over literal runs). When it lands on a
 //           position with a candidate that matched 16 bytes (and max_len > 16), the whole wave extends those candidates,
 //           256 bytes per step; when it lands on a position that still has unexamined candidates, the whole wave finishes
-//           that ONE position: 64 candidates per step, DPP max of (len, -position) = longest, oldest on ties, stop when
+//           that ONE position: 64 candidates per step (the lanes in front of the position's own entry; the step that holds it is the
+//           last), the same two stages, DPP max of (len, -position) = longest, oldest on ties, stop when
 //           max_len is reached. Positions covered by a match are never extended or finished;
 //        3. tokens go straight to the chunk's scratch slot, placed by the closed form
 //           pos(t) = (t div 8 + 1) + sum size(u<t)   (mbcnt prefix popcounts); flag bits collect in a 16-entry LDS ring;
@@ -142,13 +146,44 @@ __device__ __forceinline__ uint32_t lz_diff_bits16(uint32_t x0, uint32_t x1, uin
 	const uint32_t a = ffbl_raw(x1) | 32u, b = ffbl_raw(x2) | 64u, c = ffbl_raw(x3) | 96u;
 	return min3u(min3u(ffbl_raw(x0), a, b), c, capbits);
 }
+// The FIRST STAGE of a candidate compare: the first LZ_S1 = 8 bytes, from three aligned dwords. Most candidates differ from the position inside
+// them; bytes 8..15 and what follows are a second stage that the wave runs only when one of its candidates needs it. (A first stage of 12 bytes
+// runs its second stage less often and still lost: round 13 in profiles/HISTORY.md.)
+#define LZ_S1 8u
+struct LzS1 { uint32_t x, y; };
+__device__ __forceinline__ LzS1 lz_ld_s1(const uint8_t* base, uint32_t off)
+{
+	const uint32_t* a = reinterpret_cast<const uint32_t*>(base + (off & 0xFFCu));
+	const uint32_t sh = off & 3u;
+	const uint32_t w0 = a[0], w1 = a[1], w2 = a[2];
+	return LzS1{ __builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh) };
+}
+// first difference as a BIT index limited to capbits (<= 64), given the XOR of the two sides (lz_diff_bits16's form)
+__device__ __forceinline__ uint32_t lz_diff_bits_s1(uint32_t x0, uint32_t x1, uint32_t capbits)
+{
+	return min3u(ffbl_raw(x0), ffbl_raw(x1) | 32u, capbits);
+}
+// The SECOND STAGE: bytes 8..15 (the dwords behind the first stage's: a caller that has read those pays for two more)
+struct LzS2 { uint32_t z, w; };
+__device__ __forceinline__ LzS2 lz_ld_s2(const uint8_t* base, uint32_t off)
+{
+	const uint32_t* a = reinterpret_cast<const uint32_t*>(base + (off & 0xFFCu));
+	const uint32_t sh = off & 3u;
+	const uint32_t w2 = a[2], w3 = a[3], w4 = a[4];
+	return LzS2{ __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh) };
+}
+// first difference of bytes 8..15 as a bit index of the 16 bytes, limited to capbits (<= 128), for a pair whose first 8 bytes are equal
+__device__ __forceinline__ uint32_t lz_diff_bits_s2(uint32_t xz, uint32_t xw, uint32_t capbits)
+{
+	return min3u(ffbl_raw(xz) | 64u, ffbl_raw(xw) | 96u, capbits);
+}
 // One window (64 positions, lane = position) of the lazy parse of a chunk: Find for the positions at / after the parse
 // position `entry` (the 4 oldest candidates per lane, the rest on demand), greedy walk, token mask. Returns the parse
 // position after the window; key = (len << 12) | (4095 - q) of this lane's match (valid where matchmask is set),
 // o0 = the 4 bytes at this lane's position, shift = its token split.
-// The bucket ends come from `tbl`: u16 per bucket (packed = false), or 12-bit fields, bucket h at bit 12 h (packed = true: the two ends a
-// position needs are 24 bits at bit 12 (h - 1), inside the two dwords from (12 (h - 1)) / 32 on -- one read2 and one v_alignbit, which
-// takes its shift modulo 32). The field of bucket 4095 ends in the last dword of the table: the dword after it is read and shifted out.
+// A position needs the START of its bucket, the end of the bucket in front of it, from `tbl`: u16 per bucket (packed = false), or 12-bit fields,
+// bucket h at bit 12 h (packed = true: the field at bit 12 (h - 1) lies inside the two dwords from (12 (h - 1)) / 32 on -- one read2 and one
+// v_alignbit, which takes its shift modulo 32). The field of bucket 4094 ends in the last dword of the table: the dword after it is read and shifted out.
 struct LzWin { uint32_t key, o0, shift; u64 tokmask, matchmask; };
 template <bool packed>
 __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void* tbl, const uint16_t* s_bucket, uint32_t n, uint32_t lane,
@@ -157,21 +192,27 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	entry = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry); wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);   // (uniform: keeps the walk's bookkeeping on the scalar unit)
 	const uint32_t wend = (wbase + 64u < n) ? wbase + 64u : n;
 	const uint32_t p = wbase + lane;
-	const uint4 own = lz_ld128(s_data, p);                       // (aligned dword reads: a misaligned 16-byte read is replayed)
-	const uint32_t o0 = own.x, o1 = own.y, o2 = own.z, o3 = own.w;
+	const LzS1 own = lz_ld_s1(s_data, p);                        // (aligned dword reads: a misaligned read is replayed; bytes 8..15 are read by a second stage)
+	const uint32_t o0 = own.x, o1 = own.y;
 	const uint32_t shift = lz_shift(p);
-	uint32_t maxlen = 0, s = 0, e = 0;                        // my candidates: bucket[s..e) entries that are < p (ascending)
-	if (p >= entry && p > 0 && p + 3u <= n) {
-		const uint32_t mask3 = (1u << shift) + 2u;
-		maxlen = (n - p < mask3) ? n - p : mask3;
-		const uint32_t h = lz_hash(o0 & 0xFFFFFFu);          // >= 1
-		if (packed) {                                          // bucket h = [end[h-1], end[h])
+	const uint32_t mask3 = (1u << shift) + 2u;
+	// my candidates: the entries from bucket[s] on that are < p (ascending). A position is ACTIVE if entry <= p, 0 < p and p + 3 <= n: ranges of the
+	// window, so the mask of active lanes comes from the scalar unit, and it is applied once, to the candidates' existence below. Every lane looks
+	// its bucket up, active or not (any 3 bytes hash to a bucket of the table), and an inactive lane's max_len is never used.
+	uint32_t rel;                                                // the next token start, relative to the window (entry < wend here: < 64)
+	asm("s_max_u32 %0, %1, %2\n\ts_sub_u32 %0, %0, %2" : "=&s"(rel) : "s"(entry), "s"(wbase) : "scc");   // (a saturating subtract would go to the vector unit)
+	const uint32_t lo = (wbase == 0 && rel == 0) ? 1u : rel;
+	const uint32_t hi = n > wbase + 2u ? (n - wbase - 2u < 64u ? n - wbase - 2u : 64u) : 0u;                          // lanes [lo, hi)
+	const u64 act = sgpr64((~(u64)0 << lo) & (hi >= 64u ? ~(u64)0 : (((u64)1 << hi) - 1u)));
+	const uint32_t maxlen = (n - p < mask3) ? n - p : mask3;
+	uint32_t s;
+	{
+		const uint32_t h = lz_hash(o0 & 0xFFFFFFu);              // >= 1
+		if (packed) {                                          // bucket h starts at end[h-1]
 			const uint32_t bit = h * 12u - 12u;
 			const uint32_t* const t = static_cast<const uint32_t*>(tbl) + (bit >> 5);
-			const uint32_t x = __builtin_amdgcn_alignbit(t[1], t[0], bit);
-			s = x & 0xFFFu; e = (x >> 12) & 0xFFFu;
+			s = __builtin_amdgcn_alignbit(t[1], t[0], bit) & 0xFFFu;
 		} else {
-			e = static_cast<const uint16_t*>(tbl)[h];
 			s = static_cast<const uint16_t*>(tbl)[h - 1u];
 		}
 	}
@@ -181,30 +222,55 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	// beat a candidate that reached max_len. A key below 3 << 12 (hash collision) is "no match" to everything downstream.
 	uint32_t key = 0;
 	// All loads are UNCONDITIONAL so that they issue back to back and are waited for once: the five bucket entries from one
-	// address (entries past the bucket's end -- the next buckets', or the first words of the table behind the array -- are
-	// masked by the count), the candidates' bytes with the offset taken modulo 4096.
+	// address, the candidates' bytes with the offset taken modulo 4096.
+	// Which entries are candidates needs no count (the OWN-ENTRY rule): an active position has p + 3 <= n, so it is a key of the sort
+	// and itself an entry of its bucket, behind its r older same-hash positions; entries ascend, so bucket[s + j] < p holds for
+	// every j < r and fails at j = r. "Candidate j exists" is the prefix-AND over j' <= j of bucket[s + j'] < p, on the ballots.
+	// What is read behind the own entry -- the next buckets' entries, the unused slots of a short chunk (leftovers of the sort's
+	// count words) or the first words of the table behind the array -- may be smaller than p and is cut off by the prefix.
+	// An inactive lane reads five entries of whatever bucket its bytes hash to: the mask of active lanes cuts them off.
 	uint32_t q[LZ_SELF + 1u];
-	bool ex[LZ_SELF + 1u];                                    // candidate j exists: j < e - s and it lies before me
-	const uint32_t cnt = e - s;
+	u64 ex[LZ_SELF + 1u];                                     // lanes whose candidate j exists
 	#pragma unroll
 	// (five 2-byte reads, kept apart by the relaxed-atomic form: merged into an 8-byte + a 2-byte read, as the compiler does with plain loads, the 8-byte
 	// one is only 2-byte aligned and is replayed -- SQ_LDS_UNALIGNED_STALL 14 % of the LDS pipe's busy cycles, 54.4 against 53.3 ms on configs[4])
 	for (uint32_t j = 0; j <= LZ_SELF; ++j) { q[j] = wld16(const_cast<uint16_t*>(s_bucket) + s + j); }
 	#pragma unroll
-	for (uint32_t j = 0; j <= LZ_SELF; ++j) { ex[j] = j < cnt && q[j] < p; }
-	// The compares stop at min(max_len, 16) bytes. A candidate that reached 16 bytes with max_len > 16 is extended only when the walk lands on
-	// its position (step 2), by the whole wave: inside a long repeat every lane has such candidates, and the walk visits one or two of them.
-	const uint32_t capb = (maxlen < 16u ? maxlen : 16u) << 3;
-	u64 m16[LZ_SELF];                                         // lanes whose candidate k reached 16 bytes (kk >= 16 << 12 <=> it exists and did)
+	for (uint32_t j = 0; j <= LZ_SELF; ++j) { ex[j] = (j ? ex[j - 1u] : act) & __builtin_amdgcn_ballot_w64(q[j] < p); }
+	// The compares stop at min(max_len, 16) bytes, in two stages: the first 8 bytes of the four candidates always; all 16 only if some lane of
+	// the wave has an existing candidate that agreed on the whole first stage while its max_len allows more (one wave-uniform test; then every
+	// lane compares bytes 8..15 of its four candidates). A candidate that reached 16 bytes with
+	// max_len > 16 is extended only when the walk lands on its position (step 2), by the whole wave: inside a long repeat every lane has such
+	// candidates, and the walk visits one or two of them.
+	const uint32_t capb = (maxlen < 16u ? maxlen : 16u) << 3, cap1 = (maxlen < LZ_S1 ? maxlen : LZ_S1) << 3;
+	u64 m16[LZ_SELF];                                         // lanes whose candidate k exists and reached 16 bytes
 	{
-		uint4 c[LZ_SELF];                                     // (all loads in flight together)
+		uint32_t lb[LZ_SELF];                                 // length in bits (the low three dropped below)
+		{
+			LzS1 c[LZ_SELF];                                  // (all loads in flight together)
+			#pragma unroll
+			for (uint32_t k = 0; k < LZ_SELF; ++k) { c[k] = lz_ld_s1(s_data, q[k]); }
+			#pragma unroll
+			for (uint32_t k = 0; k < LZ_SELF; ++k) { lb[k] = lz_diff_bits_s1(c[k].x ^ o0, c[k].y ^ o1, cap1); }
+		}
+		u64 more = 0;
 		#pragma unroll
-		for (uint32_t k = 0; k < LZ_SELF; ++k) { c[k] = lz_ld128(s_data, q[k]); }
+		for (uint32_t k = 0; k < LZ_SELF; ++k) { more |= __builtin_amdgcn_ballot_w64(lb[k] >= 8u * LZ_S1) & ex[k]; m16[k] = 0; }
+		if (more & __builtin_amdgcn_ballot_w64(maxlen > LZ_S1)) {
+			const LzS2 a = lz_ld_s2(s_data, p);
+			LzS2 c[LZ_SELF];
+			#pragma unroll
+			for (uint32_t k = 0; k < LZ_SELF; ++k) { c[k] = lz_ld_s2(s_data, q[k]); }
+			#pragma unroll
+			for (uint32_t k = 0; k < LZ_SELF; ++k) {                     // (a candidate that stopped inside the first stage keeps its bits)
+				const uint32_t l2 = lz_diff_bits_s2(c[k].z ^ a.z, c[k].w ^ a.w, capb);
+				lb[k] = lb[k] >= 8u * LZ_S1 ? l2 : lb[k];
+				m16[k] = __builtin_amdgcn_ballot_w64(lb[k] >= 128u) & ex[k];
+			}
+		}
 		#pragma unroll
 		for (uint32_t k = 0; k < LZ_SELF; ++k) {
-			const uint32_t lb = lz_diff_bits16(c[k].x ^ o0, c[k].y ^ o1, c[k].z ^ o2, c[k].w ^ o3, capb);     // length in bits (the low three dropped below)
-			const uint32_t kk = ex[k] ? (((lb & ~7u) << 9) | (q[k] ^ 4095u)) : 0u;
-			m16[k] = __builtin_amdgcn_ballot_w64(kk >= (16u << 12));
+			uint32_t kk; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(kk) : "v"(((lb[k] & ~7u) << 9) | (q[k] ^ 4095u)), "s"(ex[k]));
 			key = kk > key ? kk : key;
 		}
 	}
@@ -213,7 +279,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	// key is provisional), whose candidates are extended first. (The masks are built from ballots of single compares, combined on the
 	// scalar unit: the ballot of a combined condition costs two more vector instructions. len <= maxlen, so "not reached" is
 	// key < maxlen << 12; a long-pending lane's provisional key never reaches it.)
-	const u64 five = __builtin_amdgcn_ballot_w64(cnt > LZ_SELF) & __builtin_amdgcn_ballot_w64(q[LZ_SELF] < p);
+	const u64 five = ex[LZ_SELF];
 	u64 un = five & __builtin_amdgcn_ballot_w64(key < (maxlen << 12));
 	const u64 lp = sgpr64((m16[0] | m16[1] | m16[2] | m16[3]) & __builtin_amdgcn_ballot_w64(maxlen > 16u));
 	static_assert(LZ_SELF == 4u, "the long-pending mask ORs four candidates' masks");
@@ -234,10 +300,9 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	const u64 restl = (un | mm) >> (nx & 63u);
 	const uint32_t zl = min3u(ffbl_raw((uint32_t)restl), ffbl_raw((uint32_t)(restl >> 32)) | 32u, 64u);   // 64 = no stop left
 	const uint32_t J = (nx + zl < wn) ? nx + zl : wn;
-	uint32_t mp, rel;                                            // rel: the next token start, relative to the window (entry < wend here: < 64)
+	uint32_t mp;
 	{
 		// first stop at or after the next token start, on the scalar unit: the asm output pins the chain there
-		asm("s_max_u32 %0, %1, %2\n\ts_sub_u32 %0, %0, %2" : "=&s"(rel) : "s"(entry), "s"(wbase) : "scc");   // (a saturating subtract would go to the vector unit)
 		u64 rest; asm("s_lshr_b64 %0, %1, %2" : "=s"(rest) : "s"(un | mm), "s"(rel) : "scc");
 		mp = rest ? rel + ctz64(rest) : wn;
 	}
@@ -286,37 +351,46 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 						if (l == maxL) { break; }
 					}
 				}
-				fin = ((five >> mp) & (u64)1) && kbest < (maxL << 12);
+				fin = ((un >> mp) & (u64)1) && kbest < (maxL << 12);   // (un's bit: the provisional key is below max_len, so it is `five`'s)
 #ifdef LZ4_PROFILE_EVENTS
 				if (lane == 0) { atomicAdd(&g_lz4_prof[LZ4_NEV + 2], 1ull); atomicAdd(&g_lz4_prof[LZ4_NEV + 3], (unsigned long long)nst); }
 #endif
 			}
 			if (fin) {
 				// finish position wbase+mp: the candidates after the first LZ_SELF of its bucket, oldest first, 64 per step
-				const uint32_t eL = (uint32_t)__builtin_amdgcn_readlane((int)e, (int)mp);
+				// (the own-entry rule again: the candidates of a step are the lanes below the first entry that is not < pL, and the step that holds
+				// pL's own entry is the last. fin implies a fifth candidate, so the own entry lies at or behind `base`, inside the array.)
+				// Two stages: every step compares the first 8 bytes; bytes 8..15 and the tail beyond 16 only in a step in which a candidate
+				// agreed on all of them and max_len allows more (a step holds few candidates that do: tools/dev/lz_stage_study.c).
 				const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)o0, (int)mp), a1 = (uint32_t)__builtin_amdgcn_readlane((int)o1, (int)mp);
-				const uint32_t a2 = (uint32_t)__builtin_amdgcn_readlane((int)o2, (int)mp), a3 = (uint32_t)__builtin_amdgcn_readlane((int)o3, (int)mp);
 #ifdef LZ4_PROFILE_EVENTS
 				uint32_t nsteps = 0, ntail = 0;
 #endif
-				const bool longL = maxL > 16u;
-				const uint32_t capL = (maxL < 16u ? maxL : 16u) << 3;
-				for (uint32_t base = sL + LZ_SELF; base < eL; base += 64u) {
-					const uint32_t qq = s_bucket[base + lane];         // unconditional load (past the array's end it reads the table), masked below
-					const bool v1 = lane < eL - base, v2 = qq < pL;     // else: this lane is at or beyond pL's own entry
-					const bool valid = v1 && v2;
-					const u64 vmask = __builtin_amdgcn_ballot_w64(v1) & __builtin_amdgcn_ballot_w64(v2);
-					const uint4 c = lz_ld128(s_data, qq);
-					uint32_t l2 = lz_diff_bits16(c.x ^ a0, c.y ^ a1, c.z ^ a2, c.w ^ a3, capL);   // in bits
+				const uint32_t capL = (maxL < 16u ? maxL : 16u) << 3, cap1L = (maxL < LZ_S1 ? maxL : LZ_S1) << 3;
+				for (uint32_t base = sL + LZ_SELF; ; base += 64u) {
+					const uint32_t qq = s_bucket[base + lane];         // unconditional load (past the array's end it reads the table: behind the own entry)
+					const u64 lt = __builtin_amdgcn_ballot_w64(qq < pL);
+					const u64 vmask = lt & ~(lt + 1u);                 // the lanes below the first one at or beyond pL's own entry
+					const LzS1 c1 = lz_ld_s1(s_data, qq);
+					uint32_t l2 = lz_diff_bits_s1(c1.x ^ a0, c1.y ^ a1, cap1L);   // in bits
 					uint32_t it = 0;
-					if (valid && l2 >= 128u && longL) { const uint32_t l = lz_lcp_tail(s_data, qq, pL, maxL, it); l2 = (l < maxL ? l : maxL) << 3; }
+					// (max_len is tested afresh in every step, which the empty asm enforces: hoisted out of the loop, "max_len > 8" and "max_len > 16" become
+					// two 64-bit masks that live across it, 98 scalar registers instead of 94 -- see the note on 96 at lznt1_chunk4_kernel)
+					uint32_t mL = maxL; asm volatile("" : "+s"(mL));
+					if (mL > LZ_S1 && (__builtin_amdgcn_ballot_w64(l2 >= 8u * LZ_S1) & vmask)) {
+						// (a candidate that stopped inside the first stage keeps its bits)
+						const LzS2 a = lz_ld_s2(s_data, pL), c = lz_ld_s2(s_data, qq);
+						const uint32_t l3 = lz_diff_bits_s2(c.z ^ a.z, c.w ^ a.w, capL);
+						l2 = l2 >= 8u * LZ_S1 ? l3 : l2;
+						if (mL > 16u && l2 >= 128u && ((vmask >> lane) & (u64)1)) { const uint32_t l = lz_lcp_tail(s_data, qq, pL, maxL, it); l2 = (l < maxL ? l : maxL) << 3; }
+					}
 					uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(vmask));   // (a key below 3 << 12 is no match)
 					const uint32_t m = wave_max_u32(k2);
 					kbest = m > kbest ? m : kbest;                   // longest, then oldest (older blocks hold the larger 4095 - q)
 #ifdef LZ4_PROFILE_EVENTS
 					++nsteps; ntail += wave_max_u32(it);
 #endif
-					if ((kbest >> 12) == maxL || ~vmask) { break; }  // max_len reached / all older candidates seen
+					if ((kbest >> 12) == maxL || ~lt) { break; }     // max_len reached / all older candidates seen
 				}
 #ifdef LZ4_PROFILE_EVENTS
 				if (lane == 0) { atomicAdd(&g_lz4_prof[LZ4_NEV], (unsigned long long)nsteps); atomicAdd(&g_lz4_prof[LZ4_NEV + 1], (unsigned long long)ntail); }
@@ -364,7 +438,7 @@ __global__ __launch_bounds__(64) void lznt1_chunk_kernel(const uint8_t* __restri
 {
 	// ONE LDS object, the chunk FIRST: its 16-byte reads then need no address arithmetic beyond the AND that aligns them (the DS offset
 	// fields reach 1 KiB / 64 KiB from the register address), and the bucket array is followed by the count table (lz_window reads up to
-	// four entries past a bucket's end)
+	// four entries past its own entry in the bucket array)
 	struct __attribute__((aligned(16))) Lds {
 		uint8_t  data[4096 + 32];
 		uint16_t bucket[4096];      // positions sorted by (hash, position)
@@ -577,6 +651,10 @@ static_assert(LZ4_P1 <= LZ4_PMAX && LZ4_P2 - LZ4_P1 <= LZ4_PMAX && 64u - LZ4_P2 
 extern "C" void mscomp_amd_debug_lz4_prof(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lz4_prof), sizeof(unsigned long long) * LZ4_NPROF); unsigned long long z[LZ4_NPROF] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lz4_prof), z, sizeof z); }
 #endif
 static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: LZNT1_REC = two areas of 64 windows of match tokens");
+// (The kernel must stay at or below 96 scalar registers, of which it uses 93: the hardware hands them out in sixteens, 800 per SIMD, so the 97th
+// costs every CU its eighth block, while the compiler's own occupancy figure still says 8 up to 100. Round 13 in profiles/HISTORY.md: builds of this parse
+// at 98 and 100 ran 5.8 waves per CU-cycle instead of 6.8 and lost 5 to 7 % of the headline. Nothing guards it but the A/B run of a change: an
+// `amdgpu_num_sgpr` limit makes the compiler spill, which tests/test_lznt1_resources.py forbids.)
 template <bool serial, bool DEV = false>                         // DEV: as lznt1_chunk_kernel
 __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                           uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size, uint16_t* __restrict__ recs)
