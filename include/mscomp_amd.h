@@ -740,6 +740,75 @@ MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* sp, const mscomp_amd_
                                        uint32_t* d_new_block_crc /* n_blocks_table, may be NULL */,
                                        uint64_t* d_new_res_len /* n_pick */, int32_t* d_status /* n_pick */);
 
+/* Dedup: which resources of up to MSCOMP_AMD_SPLICE_SRC_MAX source containers hold the same bytes, without decoding a byte, answered as
+ * the pick list mscomp_amd_splicer_splice takes -- "merge these containers and keep one copy of everything" is dedup, then splice, with no
+ * host round trip between them. The stored form of a block depends only on its data, the format and B, so between containers of ONE format
+ * and ONE block size (the caller's duty, as for splice) equal data means equal stored bytes, and equality is decided on the stored form.
+ * Candidates are found from the tables and 32 bytes per row; the only pass over the data is the compare that confirms a candidate, which
+ * reads the duplicates, and what they duplicate, once.
+ *   Creation:     MSCOMP_ARG_ERROR, all checked before the context is used and with *dd cleared, for a null ctx or dd, a block_size that is
+ *                 not a power of two from 4096 to 524288, n_src of 0 or above MSCOMP_AMD_SPLICE_SRC_MAX, non-zero flags, or n_res_total or
+ *                 n_blocks_total above 0x7FFFFFF0; MSCOMP_MEM_ERROR when the scratch cannot be reserved.
+ *   Scratch:      reserved once, at creation, and never grown: 56 n_res_total + 840 bytes (per resource its first row in the call's row
+ *                 numbering, its key, its slot, its candidate, its flag and its place in the list of the refuted; a key table of
+ *                 2 n_res_total + 64 slots of 12 bytes). n_blocks_total bounds the tables a call may bring and sizes the grids; nothing is
+ *                 kept per row.
+ *   Sources:      src is a HOST array of n_src views, handled as splice handles them: read on the host, passed by value, only read. The
+ *                 output arrays must not overlap any source array.
+ *   Numbering:    resource r of source s is g = src[0].n_res + ... + src[s - 1].n_res + r; N = the sum of all n_res must not exceed
+ *                 n_res_total and the sum of all n_blocks_table must not exceed n_blocks_total: otherwise MSCOMP_ARG_ERROR from the call,
+ *                 on the host, with nothing launched.
+ *   Notation:     as splice's: B the block size, L = src[s].d_res_len[r], first / off = src[s].d_block_first / d_block_off,
+ *                 n = first[r + 1] - first[r]; the stored length of row j is off[j + 1] - off[j].
+ *   Rules:        per resource g = (s, r), in this order:
+ *                   1. MSCOMP_ARG_ERROR when first[r] > first[r + 1] or first[r + 1] > src[s].n_blocks_table;
+ *                   2. MSCOMP_DATA_ERROR when n is not L / B + (L % B != 0);
+ *                   3. MSCOMP_DATA_ERROR when any of its rows j is not off[j] <= off[j + 1] <= packed_len of its source. No byte of
+ *                      such a resource is read;
+ *                   4. a resource refused by rules 1-3 is its own representative and nobody else's: d_rep[g] = g, it counts as unique
+ *                      and is picked -- splice judges it again by its own rules;
+ *                   5. two accepted resources are EQUAL when their L are equal and, row by row, their stored lengths are equal, their
+ *                      stored bytes are equal and -- when checksums take part -- their CRC words are equal. Two empty resources are equal;
+ *                   6. d_rep[g] is the smallest accepted h <= g equal to g, d_status[g] = MSCOMP_OK;
+ *                   7. g is unique when d_rep[g] == g. d_pick holds the unique resources in ascending g as (s, r) pairs; every entry at or
+ *                      behind 2 n_unique, up to 2 n_res_total, is 0xFFFFFFFFFFFFFFFF -- splice's rule 1 makes an empty resource of such a
+ *                      pick, so a splicer created for n_res_total picks takes the array as it is. d_new_index[g] is the rank of d_rep[g]
+ *                      among the unique resources. The entries of d_rep, d_new_index and d_status at and behind N are not written.
+ *                      d_count[0] = n_unique, d_count[1] = N, d_count[2] = the stored bytes of all resources that are not unique -- what a
+ *                      splice of the picks saves --, d_count[3] = the refuted (below).
+ *                 N = 0 is legal and writes d_count = {0, 0, 0, 0} (and the padding of d_pick when one is given).
+ *                 Consequence: splicing d_pick[0 .. 2 n_unique) out of the same views gives a container whose resource d_new_index[g] has
+ *                 the length, the rows, the stored bytes and the CRC words of g, for every accepted g.
+ *   Key:          the KEY TUPLE of an accepted resource is L and, per row, the stored length s, the CRC word when checksums take part,
+ *                 the first min(16, s) and the last min(16, s) stored bytes. Equal resources have equal tuples. The tuple is mixed into
+ *                 64 bits; the candidate of a resource is the smallest accepted resource with the same key. REFUTED, d_count[3], is the
+ *                 number of accepted resources that share their key with a smaller accepted resource but are not equal to the smallest
+ *                 such one -- they are still answered exactly, by rule 6. (Two different tuples that meet in their 64 bits would count
+ *                 here too: about N^2 / 2^65 of all calls.) The four counts are the same from run to run.
+ *   Checksums:    they take part exactly when every view has a non-null d_block_crc; otherwise all the arrays are ignored.
+ *   Execution:    as the splicer's: asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation, no
+ *                 synchronisation, nothing read back, eight launches fixed by the creation bounds (two of one workgroup: rules 1 and 2
+ *                 with the row numbering, and settle with emit); legal inside a caller's capture from the first execution, a graph of
+ *                 its own from the second outside one, captured again when an argument changes -- a field of a view counts as an
+ *                 argument. MSCOMP_ARG_ERROR for a null dd, src or d_count, any other null output array when N > 0, or a view with a
+ *                 null table (or null d_packed with packed_len > 0) while its n_res > 0.
+ *   Left out:     block-level sharing inside one container (the running-sum offset table cannot express two rows at one address); a
+ *                 tiled settle stage -- the refuted are settled by ONE workgroup, each against the earlier unique ones of its key, whole
+ *                 resources compared one after the other: the floor of the call on adversarial inputs, as is the one workgroup that
+ *                 scans the resources; tables whose resources overlap (damaged ones that still pass rules 1-3) are read once per
+ *                 resource that claims a row, so the work follows the sum of n, not the table; dedup fused with splice in one call; more
+ *                 than four sources per call. */
+typedef struct mscomp_amd_deduper mscomp_amd_deduper;
+MSCompStatus mscomp_amd_deduper_create(mscomp_amd_ctx* ctx, uint32_t block_size, uint32_t n_src, size_t n_res_total,
+                                       uint64_t n_blocks_total, uint32_t flags, mscomp_amd_deduper** dd);
+void         mscomp_amd_deduper_destroy(mscomp_amd_deduper* dd);
+MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* dd, const mscomp_amd_blocks_view* src /* host array, n_src */,
+                                      uint64_t* d_rep       /* n_res_total */,
+                                      uint64_t* d_new_index /* n_res_total */,
+                                      uint64_t* d_pick      /* 2 n_res_total: source, resource */,
+                                      uint64_t* d_count     /* 4 */,
+                                      int32_t*  d_status    /* n_res_total */);
+
 /* Resource checksums from block checksums. After a write or a resize the block CRC-32s are current and the resource CRC-32s that
  * mscomp_amd_blocks_crc once wrote are stale; the block checksums determine them, and no data has to be read:
  *   d_res_crc[r] = XOR over the resource's blocks j of d_block_crc[j] x^(8 d_j)  (mod the CRC polynomial), d_j = the resource's bytes behind block j

@@ -14,4 +14,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   CrcDevPlan, crc32_units, blocks_crc,
                   BlockReader, blocks_read,
                   BlockWriter, blocks_write, blocks_resize, res_crc_dev, res_crc_from_blocks,
-                  BlockSplicer, BlocksView, blocks_splice, MSCOMP_AMD_SPLICE_SRC_MAX)
+                  BlockSplicer, BlocksView, blocks_splice, MSCOMP_AMD_SPLICE_SRC_MAX,
+                  BlockDeduper, blocks_dedup)

@@ -45,6 +45,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_write", "mscomp_amd_writer_counts",
     "mscomp_amd_writer_resize", "mscomp_amd_res_crc_dev",
     "mscomp_amd_splicer_create", "mscomp_amd_splicer_destroy", "mscomp_amd_splicer_splice",
+    "mscomp_amd_deduper_create", "mscomp_amd_deduper_destroy", "mscomp_amd_deduper_dedup",
 ]
 MSCOMP_AMD_SPLICE_SRC_MAX = 4
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
@@ -187,6 +188,12 @@ def load_library():
     lib.mscomp_amd_splicer_destroy.restype = None
     lib.mscomp_amd_splicer_splice.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
     lib.mscomp_amd_splicer_splice.restype = C.c_int
+    lib.mscomp_amd_deduper_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_deduper_create.restype = C.c_int
+    lib.mscomp_amd_deduper_destroy.argtypes = [C.c_void_p]
+    lib.mscomp_amd_deduper_destroy.restype = None
+    lib.mscomp_amd_deduper_dedup.argtypes = [C.c_void_p, C.POINTER(BlocksView)] + [C.c_void_p] * 5
+    lib.mscomp_amd_deduper_dedup.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -860,6 +867,23 @@ def blocks_resize(fmt, packed, block_first, block_off, lengths, block_size, new_
     return new_packed, noff, ncrc, nfirst, [int(x) for x in h_len[:n]], [int(x) for x in h_rst[:n]]
 
 
+def _blocks_views(sources):
+    """a BlocksView array from the ``sources`` of BlockSplicer.splice / BlockDeduper.dedup"""
+    views = (BlocksView * len(sources))()
+    names = ("d_packed", "d_block_first", "d_block_off", "d_res_len", "d_block_crc", "packed_len", "n_res", "n_blocks_table")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    for v, s in zip(views, sources):
+        f = dict(zip(names, s)) if isinstance(s, (tuple, list)) else {k: getattr(s, k, None) for k in names}
+        v.d_packed, v.d_block_first, v.d_block_off = ptr(f["d_packed"]), ptr(f["d_block_first"]), ptr(f["d_block_off"])
+        v.d_res_len, v.d_block_crc = ptr(f["d_res_len"]), ptr(f.get("d_block_crc"))
+        plen = f.get("packed_len")
+        v.packed_len = (0 if f["d_packed"] is None else f["d_packed"].numel()) if plen is None else int(plen)
+        nr, nt = f.get("n_res"), f.get("n_blocks_table")
+        v.n_res = (0 if f["d_res_len"] is None else f["d_res_len"].numel()) if nr is None else int(nr)
+        v.n_blocks_table = (0 if f["d_block_off"] is None else max(0, f["d_block_off"].numel() - 1)) if nt is None else int(nt)
+    return views
+
+
 class BlockSplicer(_Handle):
     """A block splicer (mscomp_amd_splicer_create): a new container made of ``n_pick`` picks (source, resource) out of ``n_src`` (1 .. 4)
     source containers of one format and one ``block_size``, without decoding a byte; ``n_blocks_table`` is the number of rows of the NEW
@@ -888,18 +912,7 @@ class BlockSplicer(_Handle):
             raise ValueError("new_cap exceeds d_new_packed")
         if len(sources) != self.n_src:
             raise ValueError("one source per n_src")
-        views = (BlocksView * self.n_src)()
-        names = ("d_packed", "d_block_first", "d_block_off", "d_res_len", "d_block_crc", "packed_len", "n_res", "n_blocks_table")
-        ptr = lambda t: None if t is None else t.data_ptr()
-        for v, s in zip(views, sources):
-            f = dict(zip(names, s)) if isinstance(s, (tuple, list)) else {k: getattr(s, k, None) for k in names}
-            v.d_packed, v.d_block_first, v.d_block_off = ptr(f["d_packed"]), ptr(f["d_block_first"]), ptr(f["d_block_off"])
-            v.d_res_len, v.d_block_crc = ptr(f["d_res_len"]), ptr(f.get("d_block_crc"))
-            plen = f.get("packed_len")
-            v.packed_len = (0 if f["d_packed"] is None else f["d_packed"].numel()) if plen is None else int(plen)
-            nr, nt = f.get("n_res"), f.get("n_blocks_table")
-            v.n_res = (0 if f["d_res_len"] is None else f["d_res_len"].numel()) if nr is None else int(nr)
-            v.n_blocks_table = (0 if f["d_block_off"] is None else max(0, f["d_block_off"].numel() - 1)) if nt is None else int(nt)
+        views = _blocks_views(sources)
         p = _ptrs(d_pick, d_new_packed, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_status)
         _ok(self.ctx.lib.mscomp_amd_splicer_splice(self._h, views, p[0], p[1], cap, *p[2:]), "mscomp_amd_splicer_splice")
 
@@ -948,6 +961,68 @@ def blocks_splice(containers, picks, block_size, ctx=None):
     if own:
         ctx.close()
     return new_packed, nfirst, noff, [int(x) for x in h_len[:npk]], ncrc, [int(x) for x in h_st[:npk]]
+
+
+class BlockDeduper(_Handle):
+    """A block deduper (mscomp_amd_deduper_create): which resources of ``n_src`` (1 .. 4) source containers of one format and one
+    ``block_size`` hold the same bytes, decided on the stored blocks without decoding one, for up to ``n_res_total`` resources and
+    ``n_blocks_total`` table rows in all sources together. All scratch is reserved here: 56 bytes per resource + 840. dedup() enqueues
+    eight kernels on the ctx stream and nothing else (legal inside a capture of that stream). Arguments are torch CUDA tensors: int64 /
+    uint64 tables, int32 statuses."""
+    _destroy = "mscomp_amd_deduper_destroy"
+
+    def __init__(self, ctx, block_size, n_src, n_res_total, n_blocks_total):
+        _Handle.__init__(self, ctx)
+        self.block_size, self.n_src, self.n_res_total, self.n_blocks_total = int(block_size), int(n_src), int(n_res_total), int(n_blocks_total)
+        _ok(ctx.lib.mscomp_amd_deduper_create(ctx._h, self.block_size, self.n_src, self.n_res_total, self.n_blocks_total, 0, C.byref(self._h)),
+            "mscomp_amd_deduper_create")
+
+    def dedup(self, sources, d_rep, d_new_index, d_pick, d_count, d_status):
+        """``sources``: as BlockSplicer.splice takes them; their resources are numbered back to back, g = 0 .. N - 1. d_rep[g] = the smallest
+        resource equal to g (g itself for a unique or a refused one), d_new_index[g] = the rank of d_rep[g] among the unique ones, d_pick
+        (2 n_res_total) = the unique resources as (source, resource) pairs, padded with 2^64 - 1 -- the pick list of a BlockSplicer made
+        for n_res_total picks --, d_count (4) = unique resources, N, stored bytes of the others, refuted candidates; d_status[g] is
+        MSCOMP_OK, MSCOMP_ARG_ERROR (a broken block_first entry) or MSCOMP_DATA_ERROR (a wrong block count, a broken block_off entry).
+        Checksums take part in the comparison when every source has them."""
+        if len(sources) != self.n_src:
+            raise ValueError("one source per n_src")
+        _ok(self.ctx.lib.mscomp_amd_deduper_dedup(self._h, _blocks_views(sources), *_ptrs(d_rep, d_new_index, d_pick, d_count, d_status)),
+            "mscomp_amd_deduper_dedup")
+
+
+def blocks_dedup(containers, block_size, ctx=None):
+    """The duplicate resources among up to four block containers on the GPU (BlockDeduper), no block decoded: ``containers`` as
+    blocks_splice takes them. Returns host lists (rep, new_index, picks of the unique resources as (container, resource), counts,
+    statuses): blocks_splice(containers, picks, block_size) is the merged container with one copy of everything, and resource g of the
+    sources is its resource new_index[g]."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    lens = [[int(x) for x in c[3]] for c in containers]
+    n = sum(len(ln) for ln in lens)
+    with_crc = all(c[4] is not None for c in containers)
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        srcs, rows_all = [], 0
+        for (packed, first, off, _, crc), ln in zip(containers, lens):
+            packed, d_packed = _dev_packed(packed, dev)
+            rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
+            rows_all += rows
+            srcs.append((d_packed, _dev_u64(first, len(ln) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(ln, 1, dev),
+                         _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(ln), rows))
+        dd = BlockDeduper(ctx, block_size, len(containers), n, rows_all)
+        d_rep, d_idx = torch.zeros(max(1, n), dtype=torch.int64, device=dev), torch.zeros(max(1, n), dtype=torch.int64, device=dev)
+        d_pick, d_cnt = torch.zeros(max(1, 2 * n), dtype=torch.int64, device=dev), torch.zeros(4, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        dd.dedup(srcs, d_rep, d_idx, d_pick, d_cnt, d_st)
+        ctx.stream.synchronize()
+        counts = [int(x) for x in d_cnt.cpu().numpy().view(np.uint64)]
+        picks = d_pick.cpu().numpy().view(np.uint64)[: 2 * counts[0]].reshape(-1, 2)
+        rep, idx, st = d_rep.cpu().numpy().view(np.uint64)[:n], d_idx.cpu().numpy().view(np.uint64)[:n], d_st.cpu().numpy()[:n]
+        dd.close()
+    if own:
+        ctx.close()
+    return [int(x) for x in rep], [int(x) for x in idx], [(int(s), int(r)) for s, r in picks], counts, [int(x) for x in st]
 
 
 def res_crc_from_blocks(block_first, lengths, block_crc, block_size, ctx=None):

@@ -1,4 +1,4 @@
-// blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h): containers, readers, writers and splicers. Host orchestration only, as
+// blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h): containers, readers, writers, splicers and dedupers. Host orchestration only, as
 // api.hip: each call runs the launches of inner dev plans (dev_launch) between its own passes, through plan_run.
 #include "host.h"
 
@@ -493,6 +493,91 @@ MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* s, const mscomp_amd_b
 		{ KernelTimer t(c, "sp_layout_kernel"); launch_splice_layout(c->stream, k, s->n_src, s->n_pick, s->nbt, s->shift, new_cap, d_pick, d_new_block_first, d_new_block_off,
 		                                                             d_new_block_crc, d_new_res_len, d_status, addr); }
 		{ KernelTimer t(c, "bk_move_kernel"); launch_blocks_move(c->stream, s->nbt, new_cap, d_new_block_off, addr, d_new_packed, c->cpd_blocks); }
+	});
+}
+
+// ---- block dedupers (include/mscomp_amd.h; kernels: dedup.hip) ----
+// A deduper holds its tables -- sized by the bound of the resources alone -- and the graph of its call. The sources are read on the host
+// and go into the kernel arguments by value, as a splicer's.
+struct mscomp_amd_deduper {
+	mscomp_amd_ctx* ctx = nullptr;
+	uint32_t shift = 0, n_src = 0, n_res = 0, nbt = 0;     // block_size = 1 << shift; the bounds n_res_total and n_blocks_total
+	mscomp_amd_plan run;
+	DevBuf tab;                                            // DedupTab
+	DedupTab t{};
+};
+
+// the columns of a deduper's tables from `base` on (n = n_res_total); returns where they end: from a null base, their bytes
+static uintptr_t dedup_tab(DedupTab& t, void* base, size_t n)
+{
+	Carve k{reinterpret_cast<uintptr_t>(base)};
+	t.slots = 2 * (u64)n + 64;
+	t.ufirst = k.q(n + 1); t.key = k.q(n); t.tkey = k.q(t.slots);
+	t.tmin = k.w(t.slots); t.slot_of = k.w(n); t.cand = k.w(n); t.flag = k.w(n); t.rlist = k.w(n);
+	return k.at;
+}
+
+MSCompStatus mscomp_amd_deduper_create(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res_total, uint64_t n_blocks_total, uint32_t flags,
+                                       mscomp_amd_deduper** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
+	if (n_src == 0 || n_src > MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_res_total) || !count_ok(n_blocks_total)) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
+	if (!d) { return MSCOMP_MEM_ERROR; }
+	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = n_src; d->n_res = (uint32_t)n_res_total; d->nbt = (uint32_t)n_blocks_total;
+	d->run.ctx = c; d->run.n_units = 1;                    // (a call without resources writes its counts: it replays too)
+	if (!d->tab.reserve(dedup_tab(d->t, nullptr, n_res_total) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	dedup_tab(d->t, d->tab.p, n_res_total);
+	*out = d.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_deduper_destroy(mscomp_amd_deduper* d)
+{
+	if (!d) { return; }
+	DeviceGuard g(d->ctx->device);
+	(void)hipStreamSynchronize(d->ctx->stream);
+	d->tab.release();
+	delete d;                                              // (run gives up its graph)
+}
+
+MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* src, uint64_t* d_rep, uint64_t* d_new_index, uint64_t* d_pick,
+                                      uint64_t* d_count, int32_t* d_status)
+{
+	if (!d || !src || !d_count) { return MSCOMP_ARG_ERROR; }
+	SpliceSrc k{};
+	uint64_t n = 0, rows = 0;                              // (at most four terms below 2^64 / 4 each once checked: no overflow)
+	bool with_crc = true;
+	for (uint32_t i = 0; i < d->n_src; ++i) {
+		const mscomp_amd_blocks_view& v = src[i];
+		if (v.n_res && (!v.d_block_first || !v.d_block_off || !v.d_res_len || (v.packed_len && !v.d_packed))) { return MSCOMP_ARG_ERROR; }
+		if (v.n_res > d->n_res || v.n_blocks_table > d->nbt) { return MSCOMP_ARG_ERROR; }
+		n += v.n_res; rows += v.n_blocks_table;
+		with_crc = with_crc && v.d_block_crc;
+	}
+	if (n > d->n_res || rows > d->nbt) { return MSCOMP_ARG_ERROR; }
+	if (n && (!d_rep || !d_new_index || !d_pick || !d_status)) { return MSCOMP_ARG_ERROR; }
+	for (uint32_t i = 0; i < d->n_src; ++i) {
+		const mscomp_amd_blocks_view& v = src[i];
+		k.v[i] = { v.d_packed, v.packed_len, v.d_block_first, v.d_block_off, v.d_res_len, with_crc ? v.d_block_crc : nullptr, v.n_res, v.n_blocks_table };
+	}
+	mscomp_amd_ctx* c = d->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[40] = {};
+	memcpy(args, &k, sizeof k);
+	const void* rest[5] = { d_rep, d_new_index, d_pick, d_count, d_status };
+	memcpy(args + 32, rest, sizeof rest);
+	const uint32_t N = (uint32_t)n;
+	return plan_run(&d->run, args, [&] {
+		{ KernelTimer t(c, "dd_judge"); launch_dedup_judge(c->stream, k, N, d->n_res, d->nbt, d->shift, d->t, d_status, c->crc_blocks); }
+		{ KernelTimer t(c, "dd_keys"); launch_dedup_keys(c->stream, k, N, d->n_res, d->nbt, with_crc, d->t, d_status, c->crc_blocks); }
+		{ KernelTimer t(c, "dd_confirm_kernel"); launch_dedup_confirm(c->stream, k, N, d->n_res, d->nbt, d->shift, with_crc, d->t, c->cpd_blocks); }
+		{ KernelTimer t(c, "dd_settle_kernel"); launch_dedup_settle(c->stream, k, N, d->n_res, with_crc, d->t, d_rep, d_new_index, d_pick, d_count); }
 	});
 }
 

@@ -1,0 +1,359 @@
+// dedup.hip -- the passes of a block deduper (mscomp_amd_deduper_*, include/mscomp_amd.h): which resources of up to four block containers
+// of one format and one block size hold the same bytes, decided on the STORED form -- the stored form of a block depends only on its data,
+// the format and the block size -- and answered as a pick list a splicer takes. Candidates come from the tables and 32 bytes per row (a
+// 64-bit key per resource, an open-addressing table over the keys); the only pass over the data is the compare that confirms a candidate.
+// The sources travel by value in the kernel arguments, as a splicer's. DESIGN.md 4.13.
+#include "kernels.h"
+
+namespace msc {
+
+#define DD_PIECE_SHIFT 14u                                 // the confirm pass compares in pieces of 16 KiB, as the raw copy and the gather move
+#define DD_SLICE_MIN   6u                                  // ... and a block takes six pieces at least: what it looks up per row is paid once per 96 KiB or less
+
+// global resource g (< n0 + n1 + n2 + n3) as source and resource: the sources' resources are numbered back to back
+__device__ __forceinline__ void dd_locate(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, u64 g, u64& s, u64& r)
+{
+	s = 0; r = g;
+	if (r >= v0.n_res) { r -= v0.n_res; s = 1; if (r >= v1.n_res) { r -= v1.n_res; s = 2; if (r >= v2.n_res) { r -= v2.n_res; s = 3; } } }
+}
+
+__device__ __forceinline__ u64 dd_mix(u64 x)                // (splitmix64's finaliser)
+{
+	x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+	return x;
+}
+
+__device__ __forceinline__ u64 dd_wave_xor(u64 v)
+{
+	#pragma unroll
+	for (uint32_t d = 32u; d; d >>= 1) { v ^= __shfl_xor(v, d, 64); }
+	return v;
+}
+
+// the key table: every slot empty, no index yet
+__global__ __launch_bounds__(256) void dd_clear_kernel(u64 slots, u64* __restrict__ tkey, uint32_t* __restrict__ tmin)
+{
+	for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < slots; i += (u64)gridDim.x * 256u) { tkey[i] = 0; tmin[i] = 0xFFFFFFFFu; }
+}
+
+// Seed, one block, in the shape of sp_layout_kernel: rules 1 and 2 per resource, the status, the key word seeded with L, the mismatch flag
+// cleared, and ufirst (n + 1): the rows of the resources that passed, numbered densely in resource order -- this pass's own running sum, so
+// that a damaged block_first cannot send the row passes' search astray (bk_dres_kernel).
+__global__ __launch_bounds__(DV_THREADS) void dd_seed_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t shift,
+                                                            u64* __restrict__ ufirst, u64* __restrict__ key, uint32_t* __restrict__ flag, int32_t* __restrict__ status)
+{
+	__shared__ u64 s_w[1][DV_WAVES];
+	const uint32_t tid = threadIdx.x;
+	const u64 B = (u64)1 << shift;
+	u64 run[1] = {0};
+	if (tid == 0) { ufirst[0] = 0; }
+	for (uint32_t base = 0; base < n; base += DV_THREADS) {
+		const uint32_t g = base + tid;
+		const bool live = g < n;
+		u64 rows = 0, L = 0;
+		int32_t st = 0;
+		if (live) {
+			u64 s, r;
+			dd_locate(v0, v1, v2, g, s, r);
+			const SpliceView v = sp_view(v0, v1, v2, v3, s);
+			const u64 f0 = v.first[r], f1 = v.first[r + 1u];
+			if (f0 > f1 || f1 > v.nbt) { st = -2; }                          // rule 1: MSCOMP_ARG_ERROR
+			else {
+				L = v.res_len[r]; rows = f1 - f0;
+				if (rows != (L >> shift) + ((L & (B - 1u)) ? 1u : 0u)) { st = -3; rows = 0; }   // rule 2: MSCOMP_DATA_ERROR
+			}
+		}
+		u64 a[1] = {rows};
+		dv_block_scan<1>(a, run, s_w);
+		if (live) { ufirst[g + 1u] = a[0]; key[g] = st == 0 ? dd_mix(L ^ 0x9E3779B97F4A7C15ull) : 0; flag[g] = 0; status[g] = st; }
+	}
+}
+
+// The row passes: a fixed grid dealt over the ROWS of the resources that passed rules 1 and 2, so that one resource of a million rows
+// spreads over every CU (rcrc_fold_kernel). A row finds its resource by binary search in ufirst. KEY false: rule 3 -- a row that is not
+// off[j] <= off[j + 1] <= packed_len refuses its resource; every writer stores the same value. KEY true, behind it: the rows of the
+// resources that are still accepted fold a 64-bit mix of (row number, stored length, CRC word, first and last min(16, s) stored bytes)
+// into their resource's key word with an atomic XOR; a wave whose 64 rows share one resource folds them in registers first.
+template <bool KEY>
+__global__ __launch_bounds__(256) void dd_rows_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t with_crc,
+                                                     const u64* __restrict__ ufirst, u64* __restrict__ key, int32_t* status)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	const u64 units = ufirst[n], step = (u64)gridDim.x * 256u;
+	for (u64 base = (u64)blockIdx.x * 256u + (threadIdx.x & ~63u); base < units; base += step) {
+		const u64 u = base + lane;
+		uint32_t g = 0xFFFFFFFFu;
+		u64 h = 0;
+		if (u < units) {
+			const uint32_t x = res_of_block(ufirst, n, u);
+			u64 s, r;
+			dd_locate(v0, v1, v2, x, s, r);
+			const SpliceView v = sp_view(v0, v1, v2, v3, s);
+			const u64 k = u - ufirst[x], j = v.first[r] + k;                  // (j < first[r + 1] <= v.nbt: rule 1)
+			const u64 o0 = v.off[j], o1 = v.off[j + 1u];
+			if (!KEY) {
+				if (!(o0 <= o1 && o1 <= v.packed_len)) { status[x] = -3; }     // rule 3: MSCOMP_DATA_ERROR
+			} else if (status[x] == 0) {
+				const u64 len = o1 - o0;
+				const uint8_t* p = v.packed + o0;
+				u64 w[4] = {0, 0, 0, 0};                                       // first 16 | last 16 stored bytes
+				if (len >= 16u) {
+					const cpd_u16 a = *reinterpret_cast<const cpd_u16*>(p), b = *reinterpret_cast<const cpd_u16*>(p + len - 16u);
+					w[0] = a.w[0] | (u64)a.w[1] << 32; w[1] = a.w[2] | (u64)a.w[3] << 32; w[2] = b.w[0] | (u64)b.w[1] << 32; w[3] = b.w[2] | (u64)b.w[3] << 32;
+				} else {
+					for (uint32_t i = 0; i < (uint32_t)len; ++i) { w[i >> 3] |= (u64)p[i] << ((i & 7u) * 8u); }
+					w[2] = w[0]; w[3] = w[1];
+				}
+				h = dd_mix(k + 1u);
+				h = dd_mix(h ^ len);
+				if (with_crc) { h = dd_mix(h ^ ((u64)v.crc[j] | (u64)1 << 32)); }
+				h = dd_mix(h ^ w[0]); h = dd_mix(h ^ w[1]); h = dd_mix(h ^ w[2]); h = dd_mix(h ^ w[3]);
+				g = x;
+			}
+		}
+		if (KEY) {
+			const uint32_t g0 = uniform(g);
+			if (__ballot(g != g0) == 0) {
+				h = dd_wave_xor(h);
+				if (lane == 0 && g0 != 0xFFFFFFFFu) { atomicXor(reinterpret_cast<unsigned long long*>(&key[g0]), (unsigned long long)h); }
+			} else if (g != 0xFFFFFFFFu) { atomicXor(reinterpret_cast<unsigned long long*>(&key[g]), (unsigned long long)h); }
+		}
+	}
+}
+
+// One thread per accepted resource: its key into the open-addressing table -- a 64-bit compare-and-swap claims an empty slot for the key,
+// linear probing past slots of other keys --, and its index into the slot's minimum. A slot holds one key, so two resources share a slot
+// exactly when they share their key; the minimum does not depend on the order of arrival.
+__global__ __launch_bounds__(256) void dd_insert_kernel(uint32_t n, u64 slots, const u64* __restrict__ key, const int32_t* __restrict__ status,
+                                                       u64* tkey, uint32_t* tmin, uint32_t* __restrict__ slot_of)
+{
+	for (u64 g = (u64)blockIdx.x * 256u + threadIdx.x; g < n; g += (u64)gridDim.x * 256u) {
+		if (status[g] != 0) { continue; }
+		const u64 kk = key[g] ? key[g] : 1u;                                  // (0 is the empty slot)
+		u64 at = dd_mix(kk) % slots;
+		for (;;) {
+			const u64 was = atomicCAS(reinterpret_cast<unsigned long long*>(&tkey[at]), 0ull, (unsigned long long)kk);
+			if (was == 0 || was == kk) { break; }
+			at = at + 1u == slots ? 0 : at + 1u;                                // (the table has more slots than there are resources: the walk ends)
+		}
+		atomicMin(&tmin[at], (uint32_t)g);
+		slot_of[g] = (uint32_t)at;
+	}
+}
+
+// behind it, one thread per resource: the candidate -- the smallest accepted resource with the same key, itself for a refused one -- and
+// the first thing that can tell two resources of one key apart: their lengths
+__global__ __launch_bounds__(256) void dd_cand_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, const int32_t* __restrict__ status,
+                                                     const uint32_t* __restrict__ tmin, const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ cand,
+                                                     uint32_t* __restrict__ flag)
+{
+	for (u64 g = (u64)blockIdx.x * 256u + threadIdx.x; g < n; g += (u64)gridDim.x * 256u) {
+		uint32_t c = (uint32_t)g;
+		if (status[g] == 0) {
+			c = tmin[slot_of[g]];
+			if (c != (uint32_t)g) {
+				u64 s, r, sc, rc;
+				dd_locate(v0, v1, v2, g, s, r); dd_locate(v0, v1, v2, c, sc, rc);
+				if (sp_view(v0, v1, v2, v3, s).res_len[r] != sp_view(v0, v1, v2, v3, sc).res_len[rc]) { flag[g] = 1u; }
+			}
+		}
+		cand[g] = c;
+	}
+}
+
+// Whether the cnt bytes at a and at b differ, by NT threads (NT >= 128): the two sides have independent alignment -- stored blocks are
+// packed without padding --, so, as cpd_move moves them, a bytewise head up to a's next 16-byte boundary, a body of 16-byte loads on a
+// (16-byte loads on b too where it is aligned alike, loads of alignment 1 otherwise, four of either side in flight per thread), a bytewise
+// tail on the second wave. The answer is this thread's part: the caller folds it.
+template <uint32_t NT>
+__device__ __forceinline__ bool dd_differs(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, u64 cnt, uint32_t tid)
+{
+	u64 head = (16u - ((uintptr_t)a & 15u)) & 15u;
+	if (head > cnt) { head = cnt; }
+	const u64 body = (cnt - head) >> 4, tail0 = head + body * 16u;
+	bool d = false;
+	if (tid < head) { d = a[tid] != b[tid]; }
+	if (tid >= 64u && tail0 + (tid - 64u) < cnt) { d = d || a[tail0 + (tid - 64u)] != b[tail0 + (tid - 64u)]; }
+	const bool same = (((uintptr_t)b + head) & 15u) == 0;
+	const uint4* __restrict__ pa = reinterpret_cast<const uint4*>(a + head);
+	const uint4* __restrict__ pb = reinterpret_cast<const uint4*>(b + head);
+	const cpd_u16* __restrict__ ub = reinterpret_cast<const cpd_u16*>(b + head);
+	for (u64 k0 = 0; k0 < body; k0 += 4u * NT) {
+		uint4 x[4], y[4];
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) {
+			const u64 k = k0 + j * NT + tid;
+			x[j] = y[j] = make_uint4(0, 0, 0, 0);
+			if (k < body) {
+				x[j] = pa[k];
+				if (same) { y[j] = pb[k]; }
+				else { const cpd_u16 t = ub[k]; y[j] = make_uint4(t.w[0], t.w[1], t.w[2], t.w[3]); }
+			}
+		}
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) { d = d || ((x[j].x ^ y[j].x) | (x[j].y ^ y[j].y) | (x[j].z ^ y[j].z) | (x[j].w ^ y[j].w)) != 0; }
+	}
+	return d;
+}
+
+// Confirm: the (row, piece of 16 KiB) items of the same row numbering, cut into equal slices, one per block of a fixed grid; a block walks
+// the rows of its slice, and what it has to look up it looks up once per row (its resource once per resource). A row of an accepted
+// resource that is not its key's minimum is compared with the same row of the minimum: the stored lengths, the CRC words, then the
+// pieces of the slice as one stretch of bytes. A mismatch sets the resource's flag: every writer stores the same value, so no ordering is
+// needed. A workgroup looks at the flag before it starts a row and skips it when set -- what that saves is time alone: the flag ends as
+// 1 exactly when something differs. (A flag set by dd_cand_kernel says that the lengths differ: then the two resources' rows do not pair
+// up, and no row of the resource is looked at.)
+__global__ __launch_bounds__(CPD_THREADS) void dd_confirm_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t ppu_shift, uint32_t with_crc,
+                                                                const u64* __restrict__ ufirst, const uint32_t* __restrict__ cand, uint32_t* flag)
+{
+	const uint32_t tid = threadIdx.x;
+	const u64 units = ufirst[n] < ((u64)1 << 56) ? ufirst[n] : (u64)1 << 56, items = units << ppu_shift;
+	u64 per = (items + gridDim.x - 1u) / gridDim.x;
+	per = per < DD_SLICE_MIN ? DD_SLICE_MIN : per;
+	const u64 lo = (u64)blockIdx.x * per;
+	if (lo >= items) { return; }
+	const u64 hi = items - lo < per ? items : lo + per;
+	uint32_t g = 0;
+	u64 g_end = 0;                                                         // the rows below g_end that are not below ufirst[g] are g's
+	for (u64 i = lo; i < hi; ) {
+		const u64 u = i >> ppu_shift, next = (u + 1u) << ppu_shift, end = next < hi ? next : hi;   // the row's items in this slice: [i, end)
+		// (a row's last piece runs to the end of the row: nothing bounds a stored length but packed_len, so a row of a damaged table that passes
+		// rule 3 may be longer than its pieces -- one workgroup then takes the rest)
+		const u64 at = (i - (u << ppu_shift)) << DD_PIECE_SHIFT, upto = end == next ? ~(u64)0 : (end - (u << ppu_shift)) << DD_PIECE_SHIFT;
+		i = end;
+		if (u >= g_end) { g = res_of_block(ufirst, n, u); g_end = ufirst[g + 1u]; }
+		const uint32_t c = cand[g];
+		if (c == g || flag[g] != 0) { continue; }
+		u64 s, r, sc, rc;
+		dd_locate(v0, v1, v2, g, s, r); dd_locate(v0, v1, v2, c, sc, rc);
+		const SpliceView v = sp_view(v0, v1, v2, v3, s), w = sp_view(v0, v1, v2, v3, sc);
+		const u64 k = u - ufirst[g], j = v.first[r] + k, jc = w.first[rc] + k;  // (equal lengths, both accepted: equal row counts)
+		const u64 o0 = v.off[j], len = v.off[j + 1u] - o0, c0 = w.off[jc], clen = w.off[jc + 1u] - c0;
+		if (len != clen || (with_crc && v.crc[j] != w.crc[jc])) {
+			if (tid == 0) { flag[g] = 1u; }
+			continue;
+		}
+		if (at >= len) { continue; }
+		if (dd_differs<CPD_THREADS>(v.packed + o0 + at, w.packed + c0 + at, (upto < len ? upto : len) - at, tid)) { flag[g] = 1u; }
+	}
+}
+
+// whether accepted resources g and c are equal, by the whole block (every thread calls it and gets the same answer): the lengths, then
+// row by row the stored lengths and the CRC words, then the stored bytes
+__device__ bool dd_equal(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, const SpliceView& v3, uint32_t with_crc, uint32_t g, uint32_t c)
+{
+	const uint32_t tid = threadIdx.x;
+	u64 s, r, sc, rc;
+	dd_locate(v0, v1, v2, g, s, r); dd_locate(v0, v1, v2, c, sc, rc);
+	const SpliceView v = sp_view(v0, v1, v2, v3, s), w = sp_view(v0, v1, v2, v3, sc);
+	if (v.res_len[r] != w.res_len[rc]) { return false; }
+	const u64 f = v.first[r], rows = v.first[r + 1u] - f, fc = w.first[rc];
+	bool d = false;
+	for (u64 k = tid; k < rows; k += DV_THREADS) {
+		if (v.off[f + k + 1u] - v.off[f + k] != w.off[fc + k + 1u] - w.off[fc + k] || (with_crc && v.crc[f + k] != w.crc[fc + k])) { d = true; }
+	}
+	if (__syncthreads_or(d)) { return false; }
+	for (u64 k = 0; k < rows; ++k) {
+		const u64 o0 = v.off[f + k], len = v.off[f + k + 1u] - o0;
+		if (__syncthreads_or(dd_differs<DV_THREADS>(v.packed + o0, w.packed + w.off[fc + k], len, tid))) { return false; }
+	}
+	return true;
+}
+
+// Settle and emit, one block. The representatives the flags decide (a refused resource: itself; its key's minimum: itself; a confirmed
+// one: the minimum) and the list of the REFUTED -- accepted, not the minimum, not equal to it -- in ascending order; count[3] is its
+// length. The refuted are then answered exactly, one after the other: equal resources share their key, so the only resources a refuted
+// one can still be equal to are the earlier refuted ones of its slot that stayed their own representative. Then the scan over
+// rep[g] == g: new_index, pick with its padding up to 2 n_max, count.
+__global__ __launch_bounds__(DV_THREADS) void dd_settle_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t n_max, uint32_t with_crc,
+                                                              const uint32_t* __restrict__ cand, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ slot_of,
+                                                              uint32_t* rlist, u64* rep, u64* new_index, u64* __restrict__ pick,
+                                                              u64* __restrict__ count)
+{
+	__shared__ u64 s_w[2][DV_WAVES];
+	const uint32_t tid = threadIdx.x;
+	u64 nref[1] = {0};
+	for (uint32_t base = 0; base < n; base += DV_THREADS) {
+		const uint32_t g = base + tid;
+		const bool live = g < n;
+		bool refuted = false;
+		if (live) {
+			const uint32_t c = cand[g];                                        // (g itself for a refused resource)
+			refuted = c != g && flag[g] != 0;
+			rep[g] = refuted ? g : c;
+		}
+		u64 a[1] = {refuted ? 1u : 0u};
+		dv_block_scan<1>(a, nref, s_w);
+		if (refuted) { rlist[a[0] - 1u] = g; }
+	}
+	__syncthreads();                                                     // rlist and rep are read back below, by other threads of this block
+	for (u64 i = 0; i < nref[0]; ++i) {
+		const uint32_t g = rlist[i];
+		uint32_t to = g;
+		for (u64 j = 0; j < i; ++j) {
+			const uint32_t c = rlist[j];
+			if (slot_of[c] == slot_of[g] && rep[c] == c && dd_equal(v0, v1, v2, v3, with_crc, g, c)) { to = c; break; }
+		}
+		__syncthreads();                                                   // (every thread has read rep before one of them writes it)
+		if (tid == 0) { rep[g] = to; }
+		__syncthreads();
+	}
+	u64 tot[2] = {0, 0};                                                   // unique resources | stored bytes of the others
+	for (uint32_t base = 0; base < n; base += DV_THREADS) {
+		const uint32_t g = base + tid;
+		const bool live = g < n, uniq = live && rep[g] == g;
+		u64 s = 0, r = 0, saved = 0;
+		if (live) {
+			dd_locate(v0, v1, v2, g, s, r);
+			if (!uniq) { const SpliceView v = sp_view(v0, v1, v2, v3, s); saved = v.off[v.first[r + 1u]] - v.off[v.first[r]]; }   // (accepted: its offsets only grow)
+		}
+		u64 a[2] = {uniq ? 1u : 0u, saved};
+		dv_block_scan<2>(a, tot, s_w);
+		if (uniq) { const u64 q = a[0] - 1u; new_index[g] = q; pick[2u * q] = s; pick[2u * q + 1u] = r; }
+	}
+	__syncthreads();                                                     // the unique resources' new_index is read back below
+	for (uint32_t g = tid; g < n; g += DV_THREADS) { if (rep[g] != g) { new_index[g] = new_index[rep[g]]; } }
+	if (pick) { for (u64 e = 2u * tot[0] + tid; e < 2u * (u64)n_max; e += DV_THREADS) { pick[e] = ~(u64)0; } }
+	if (tid == 0) { count[0] = tot[0]; count[1] = n; count[2] = tot[1]; count[3] = nref[0]; }
+}
+
+static dim3 dd_grid(u64 items, uint32_t per_block, uint32_t blocks)
+{
+	const u64 need = (items + per_block - 1u) / per_block;
+	return dim3((uint32_t)(need < blocks ? need : blocks));
+}
+
+void launch_dedup_judge(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, const DedupTab& t, int32_t* status, uint32_t blocks)
+{
+	if (n_max == 0) { return; }
+	hipLaunchKernelGGL(dd_clear_kernel, dd_grid(t.slots, 256u, blocks), dim3(256), 0, st, t.slots, t.tkey, t.tmin);
+	hipLaunchKernelGGL(dd_seed_kernel, dim3(1), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, shift, t.ufirst, t.key, t.flag, status);
+	if (rows_max == 0) { return; }
+	hipLaunchKernelGGL(dd_rows_kernel<false>, dd_grid(rows_max, 256u, blocks), dim3(256), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, 0u, t.ufirst, t.key, status);
+}
+
+void launch_dedup_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, bool with_crc, const DedupTab& t, int32_t* status, uint32_t blocks)
+{
+	if (n_max == 0) { return; }
+	if (rows_max) {
+		hipLaunchKernelGGL(dd_rows_kernel<true>, dd_grid(rows_max, 256u, blocks), dim3(256), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, with_crc ? 1u : 0u, t.ufirst, t.key, status);
+	}
+	hipLaunchKernelGGL(dd_insert_kernel, dd_grid(n_max, 256u, blocks), dim3(256), 0, st, n, t.slots, t.key, status, t.tkey, t.tmin, t.slot_of);
+	hipLaunchKernelGGL(dd_cand_kernel, dd_grid(n_max, 256u, blocks), dim3(256), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, status, t.tmin, t.slot_of, t.cand, t.flag);
+}
+
+void launch_dedup_confirm(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, bool with_crc, const DedupTab& t, uint32_t blocks)
+{
+	if (n_max == 0 || rows_max == 0) { return; }
+	const uint32_t ppu_shift = shift > DD_PIECE_SHIFT ? shift - DD_PIECE_SHIFT : 0u;
+	hipLaunchKernelGGL(dd_confirm_kernel, dd_grid((u64)rows_max << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, ppu_shift,
+	                   with_crc ? 1u : 0u, t.ufirst, t.cand, t.flag);
+}
+
+void launch_dedup_settle(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, bool with_crc, const DedupTab& t, u64* rep, u64* new_index, u64* pick, u64* count)
+{
+	hipLaunchKernelGGL(dd_settle_kernel, dim3(1), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, n_max, with_crc ? 1u : 0u, t.cand, t.flag, t.slot_of, t.rlist,
+	                   rep, new_index, pick, count);
+}
+
+} // namespace msc

@@ -342,10 +342,40 @@ struct SpliceView {
 	u64 n_res, nbt;
 };
 struct SpliceSrc { SpliceView v[4]; };
+// source s of the call (s < n_src <= 4), by selects over four arguments: an array indexed with a lane's s would be copied into scratch memory
+#define SP_PICK(f) (s == 1u ? v1.f : s == 2u ? v2.f : s == 3u ? v3.f : v0.f)
+__device__ __forceinline__ SpliceView sp_view(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, const SpliceView& v3, u64 s)
+{
+	return SpliceView{ SP_PICK(packed), SP_PICK(packed_len), SP_PICK(first), SP_PICK(off), SP_PICK(res_len), SP_PICK(crc), SP_PICK(n_res), SP_PICK(nbt) };
+}
+#undef SP_PICK
 // one block: rules 1-3 per pick (pick: 2 n_pick, source and resource), new_first (n_pick + 1), new_len and status (n_pick), then per NEW row
 // new_off (nbt + 1), new_crc (nbt, may be null) and addr (nbt, for launch_blocks_move), then rule 7
 void launch_splice_layout(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n_pick, uint32_t nbt, uint32_t shift, u64 cap, const u64* pick,
                           u64* new_first, u64* new_off, uint32_t* new_crc, u64* new_len, int32_t* status, u64* addr);
+
+// ---- block dedupers (dedup.hip; mscomp_amd_deduper_*) ----
+// The deduper's own tables, in one buffer (blockobj.hip dedup_tab is the only place that knows the layout). n = n_res_total, the bound of
+// the resources of all sources together; slots = 2 n + 64, the key table.
+struct DedupTab {
+	u64* ufirst;                                       // n + 1: first row of every resource, in a numbering of the rows of the resources that passed rules 1 and 2
+	u64* key;                                          // n: the resource's 64-bit key
+	u64* tkey;                                         // slots: the key a slot was claimed for (0 = empty)
+	uint32_t* tmin;                                    // slots: the smallest resource with the slot's key
+	uint32_t *slot_of, *cand, *flag;                   // n each: the resource's slot; the smallest accepted resource with its key; 1 = not equal to that one
+	uint32_t* rlist;                                   // n: the refuted resources, ascending
+	u64 slots;
+};
+// The call in four stages, eight launches fixed by n_max and rows_max (the creation bounds; every grid is sized by them, none is launched
+// with an empty one); n = the resources of this call (<= n_max), status = d_status, which the stages read back.
+// judge: the key table cleared, rules 1 and 2 and the row numbering (one block), rule 3 (a fixed grid over the rows); `blocks` = crc_dev_blocks()
+void launch_dedup_judge(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, const DedupTab& t, int32_t* status, uint32_t blocks);
+// keys: the accepted resources' keys (the same grid over the rows), the keys into the table, the candidates (a thread per resource)
+void launch_dedup_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, bool with_crc, const DedupTab& t, int32_t* status, uint32_t blocks);
+// confirm: the byte compare, a fixed grid over (row, 16 KiB piece) items; `blocks` = compact_dev_blocks()
+void launch_dedup_confirm(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, bool with_crc, const DedupTab& t, uint32_t blocks);
+// settle and emit (one block): rep, new_index (n each), pick (2 n_max, may be null when n is 0), count (4)
+void launch_dedup_settle(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, bool with_crc, const DedupTab& t, u64* rep, u64* new_index, u64* pick, u64* count);
 
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status

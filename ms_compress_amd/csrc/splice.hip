@@ -7,14 +7,6 @@
 
 namespace msc {
 
-// source s of the call (s < n_src <= 4), by selects over four arguments: an array indexed with a lane's s would be copied into scratch memory
-#define SP_PICK(f) (s == 1u ? v1.f : s == 2u ? v2.f : s == 3u ? v3.f : v0.f)
-__device__ __forceinline__ SpliceView sp_view(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, const SpliceView& v3, u64 s)
-{
-	return SpliceView{ SP_PICK(packed), SP_PICK(packed_len), SP_PICK(first), SP_PICK(off), SP_PICK(res_len), SP_PICK(crc), SP_PICK(n_res), SP_PICK(nbt) };
-}
-#undef SP_PICK
-
 // Layout, one block, in the shape of rs_layout_kernel. A pass over the picks in tiles: rules 1 and 2 per pick, a scan of the block counts
 // of the picks that passed them -- rule 3 holds it against the table --, then a scan of the counts that stayed, which is new_first; new_len
 // and the provisional statuses. A scan over the NEW table rows then gives every row its stored length, checksum and address: a row finds
