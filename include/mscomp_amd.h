@@ -740,6 +740,83 @@ MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* sp, const mscomp_amd_
                                        uint32_t* d_new_block_crc /* n_blocks_table, may be NULL */,
                                        uint64_t* d_new_res_len /* n_pick */, int32_t* d_status /* n_pick */);
 
+/* Splice by block extents: the splicer's second call. A new resource is the concatenation of EXTENTS -- block-aligned runs of blocks of
+ * source resources -- instead of one whole resource, so joining resources, splitting one at a block boundary, cutting a block-aligned
+ * range out (FALLOC_FL_COLLAPSE_RANGE), inserting blocks of another resource (FALLOC_FL_INSERT_RANGE) and keeping the first k blocks are
+ * all extent lists, and none decodes a byte: the stored form of a block depends only on its data, the format and B, and that holds per
+ * block. One format and one block size are the caller's duty, as for splice.
+ *   Creation:     mscomp_amd_splicer_create_extents makes a mscomp_amd_splicer (destroyed by mscomp_amd_splicer_destroy) for n_res new
+ *                 resources made of at most n_ext extents in all. Errors and bounds as mscomp_amd_splicer_create, all checked before the
+ *                 context is used and with *sp cleared; n_res and n_ext each have the bound of n_pick (0x7FFFFFF0). Such a splicer also
+ *                 serves mscomp_amd_splicer_splice with n_pick = n_res (its scratch is a superset; the two calls keep separate graphs). A
+ *                 splicer made by mscomp_amd_splicer_create answers mscomp_amd_splicer_splice_extents with MSCOMP_ARG_ERROR and launches
+ *                 nothing.
+ *   Scratch:      reserved once, at creation: 8 n_blocks_table + 8 n_ext + 8 ceil(n_blocks_table / MSCOMP_AMD_SPLICE_ROW_TILE) + 80 bytes
+ *                 (the address of every new row's stored bytes; one word per extent, + 1, for the extent's first new row; the stored
+ *                 bytes of every tile of rows; the flag word of rule 0; 64 bytes of slack).
+ *   Sources:      as splice's: a HOST array of n_src views, read on the host, passed by value, only read.
+ *   Meaning:      new resource q is the concatenation of its extents e = d_ext_first[q] .. d_ext_first[q + 1] - 1, in that order. Extent
+ *                 e = (s, r, k0, c) = d_ext[4 e .. 4 e + 3] stands for the blocks k0 .. k0 + c - 1 of resource r of source s;
+ *                 c = 0xFFFFFFFFFFFFFFFF means "through the resource's last block", that is n - k0.
+ *   Notation:     as splice's: B the block size, L = src[s].d_res_len[r], first / off = src[s].d_block_first / d_block_off,
+ *                 n = first[r + 1] - first[r].
+ *   Rules:        in this order:
+ *                   0. the extent table as a whole: d_ext_first must not decrease anywhere and d_ext_first[n_res] must not exceed n_ext.
+ *                      Otherwise every d_status is MSCOMP_ARG_ERROR, d_new_block_first, d_new_block_off, d_new_block_crc and
+ *                      d_new_res_len are all 0, and nothing else is written (resize's rule 0). d_ext_first[n_res] is the count n_e of
+ *                      extents in use; the entries of d_ext at and behind n_e -- and those in front of d_ext_first[0] -- are never read;
+ *                   1. per extent, source and resource: MSCOMP_ARG_ERROR, nothing of the extent read further, when s >= n_src,
+ *                      r >= src[s].n_res, first[r] > first[r + 1] or first[r + 1] > src[s].n_blocks_table;
+ *                   2. per extent, block count: MSCOMP_DATA_ERROR when n is not L / B + (L % B != 0);
+ *                   3. per extent, the range: MSCOMP_ARG_ERROR when k0 > n, or when c is not all-ones and c > n - k0 (no sum is formed
+ *                      that can overflow). c = 0, or all-ones with k0 = n, is a legal EMPTY extent. The extent's data length len_e is
+ *                      L - k0 B when it reaches block n - 1 and c B otherwise; 0 for an empty extent, and for one refused by rules 1-3;
+ *                   4. per resource, alignment: every extent of the resource except its last non-empty one must have len_e % B == 0 -- a
+ *                      short block can only be the last block of the new resource; otherwise MSCOMP_ARG_ERROR, for the extent that ends
+ *                      short;
+ *                   5. refusal: a resource with an extent refused by rules 1-4 is refused, with the status of its lowest-indexed refused
+ *                      extent;
+ *                   6. room in the table, splice's rule 3 over resources: the saturating running total of the block counts of the
+ *                      resources that passed rules 1-5, in resource order, including this resource and including resources refused here,
+ *                      must not exceed n_blocks_table; otherwise MSCOMP_ARG_ERROR. A resource without blocks is never refused here;
+ *                   7. a refused resource is an EMPTY resource of the new container: d_new_res_len[q] = 0 and no rows. Resource indices
+ *                      never shift;
+ *                   8. an accepted resource: d_new_res_len[q] is the sum of its len_e, and its rows are its extents' source rows in
+ *                      order -- new row (first new row of extent e) + i takes source row first[r] + k0 + i: its stored bytes verbatim and,
+ *                      when checksums are carried, its CRC word verbatim. An unreadable source entry becomes an empty row (splice's rule
+ *                      5). Nothing else about a block is judged;
+ *                   9. the tables, the capacity and the checksum arrays: splice's rules 6 and 7 and its "Checksums" paragraph, unchanged,
+ *                      with d_new_block_first[n_res] = nb'.
+ *                 Extents may repeat and overlap (the blocks are duplicated). A resource with no extents is an empty resource with
+ *                 MSCOMP_OK. n_res = 0 is legal and writes an empty container.
+ *                 Consequence: when every source was written by mscomp_amd_blocks_compress and _crc with one format and one B and is
+ *                 healthy, and every resource is accepted, the new packed bytes, d_new_block_first, d_new_block_off and d_new_block_crc
+ *                 are byte for byte what those two calls write for the concatenated extent data, in a container with
+ *                 n_blocks_max = n_blocks_table; mscomp_amd_res_crc_dev over the new tables gives the CRC-32 of each new resource's data.
+ *   Execution:    as the splicer's: asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation, no
+ *                 synchronisation, nothing read back, five launches fixed by the creation bounds (one when n_blocks_table is 0): the
+ *                 extent pass, one workgroup; the row passes in tiles of MSCOMP_AMD_SPLICE_ROW_TILE rows of the new table -- the tiles'
+ *                 sums, their running sum (one workgroup), the rows --; the move, a fixed grid. The verdict of rule 0 is one flag word in
+ *                 the scratch: the extent pass writes it, every later pass reads it, the launches are the same either way. Legal inside a
+ *                 caller's capture from the first execution, a graph of its own from the second outside one, captured again when an
+ *                 argument changes -- a field of a view counts as an argument. MSCOMP_ARG_ERROR for a null sp or src, a splicer made for
+ *                 picks, a null d_ext_first, a null d_ext when n_ext > 0, a null d_new_res_len or d_status when n_res > 0, a null
+ *                 d_new_block_first or d_new_block_off, a null d_new_packed unless n_blocks_table is 0, or a view with a null table (or
+ *                 null d_packed with packed_len > 0) while its n_res > 0.
+ *   Left out:     extents that start or end inside a block (they need a decode of the edge blocks: a writer's job); moving
+ *                 mscomp_amd_splicer_splice onto the tiled layout; more than four sources per call. */
+#define MSCOMP_AMD_SPLICE_ROW_TILE 1024u
+MSCompStatus mscomp_amd_splicer_create_extents(mscomp_amd_ctx* ctx, uint32_t block_size, uint32_t n_src, size_t n_res /* of the NEW container */,
+                                               size_t n_ext, uint64_t n_blocks_table /* of the NEW container */, uint32_t flags,
+                                               mscomp_amd_splicer** sp);
+MSCompStatus mscomp_amd_splicer_splice_extents(mscomp_amd_splicer* sp, const mscomp_amd_blocks_view* src /* host array, n_src */,
+                                               const uint64_t* d_ext_first /* n_res + 1 */,
+                                               const uint64_t* d_ext /* 4 n_ext: source, resource, first block k0, block count c */,
+                                               uint8_t* d_new_packed, uint64_t new_cap,
+                                               uint64_t* d_new_block_first /* n_res + 1 */, uint64_t* d_new_block_off /* n_blocks_table + 1 */,
+                                               uint32_t* d_new_block_crc /* n_blocks_table, may be NULL */,
+                                               uint64_t* d_new_res_len /* n_res */, int32_t* d_status /* n_res */);
+
 /* Dedup: which resources of up to MSCOMP_AMD_SPLICE_SRC_MAX source containers hold the same bytes, without decoding a byte, answered as
  * the pick list mscomp_amd_splicer_splice takes -- "merge these containers and keep one copy of everything" is dedup, then splice, with no
  * host round trip between them. The stored form of a block depends only on its data, the format and B, so between containers of ONE format

@@ -14,5 +14,6 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   CrcDevPlan, crc32_units, blocks_crc,
                   BlockReader, blocks_read,
                   BlockWriter, blocks_write, blocks_resize, res_crc_dev, res_crc_from_blocks,
-                  BlockSplicer, BlocksView, blocks_splice, MSCOMP_AMD_SPLICE_SRC_MAX,
+                  BlockSplicer, BlocksView, blocks_splice, MSCOMP_AMD_SPLICE_SRC_MAX, MSCOMP_AMD_SPLICE_ROW_TILE,
+                  blocks_splice_extents, blocks_concat, blocks_split_at, blocks_cut_range,
                   BlockDeduper, blocks_dedup)

@@ -45,9 +45,11 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_write", "mscomp_amd_writer_counts",
     "mscomp_amd_writer_resize", "mscomp_amd_res_crc_dev",
     "mscomp_amd_splicer_create", "mscomp_amd_splicer_destroy", "mscomp_amd_splicer_splice",
+    "mscomp_amd_splicer_create_extents", "mscomp_amd_splicer_splice_extents",
     "mscomp_amd_deduper_create", "mscomp_amd_deduper_destroy", "mscomp_amd_deduper_dedup",
 ]
 MSCOMP_AMD_SPLICE_SRC_MAX = 4
+MSCOMP_AMD_SPLICE_ROW_TILE = 1024                              # rows of the new table per workgroup of splice_extents' row passes
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 
 
@@ -188,6 +190,10 @@ def load_library():
     lib.mscomp_amd_splicer_destroy.restype = None
     lib.mscomp_amd_splicer_splice.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
     lib.mscomp_amd_splicer_splice.restype = C.c_int
+    lib.mscomp_amd_splicer_create_extents.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_splicer_create_extents.restype = C.c_int
+    lib.mscomp_amd_splicer_splice_extents.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
+    lib.mscomp_amd_splicer_splice_extents.restype = C.c_int
     lib.mscomp_amd_deduper_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
     lib.mscomp_amd_deduper_create.restype = C.c_int
     lib.mscomp_amd_deduper_destroy.argtypes = [C.c_void_p]
@@ -917,42 +923,62 @@ class BlockSplicer(_Handle):
         _ok(self.ctx.lib.mscomp_amd_splicer_splice(self._h, views, p[0], p[1], cap, *p[2:]), "mscomp_amd_splicer_splice")
 
 
-def blocks_splice(containers, picks, block_size, ctx=None):
-    """A new block container from resources of up to four others on the GPU (BlockSplicer), no block decoded: ``containers`` is a list of
-    (packed, block_first, block_off, lengths, block_crc or None) of one format and ``block_size``, ``picks`` a list of (container,
-    resource): pick p becomes resource p. The new container gets checksums when every source has them. Returns numpy arrays and lists
-    (new_packed uint8, new_first uint64 of n + 1, new_block_off uint64 of nb + 1, new_lengths, new_block_crc uint32 or None, statuses)."""
+    @classmethod
+    def for_extents(cls, ctx, block_size, n_src, n_res, n_ext, n_blocks_table):
+        """A splicer for splice_extents() (mscomp_amd_splicer_create_extents): ``n_res`` new resources made of at most ``n_ext`` extents in
+        all. Its scratch adds 8 bytes per extent and 8 per SPLICE_ROW_TILE rows of the new table; it serves splice() too, with
+        n_pick = n_res."""
+        self = cls.__new__(cls)
+        _Handle.__init__(self, ctx)
+        self.block_size, self.n_src, self.n_pick, self.n_blocks_table = int(block_size), int(n_src), int(n_res), int(n_blocks_table)
+        self.n_res, self.n_ext = int(n_res), int(n_ext)
+        _ok(ctx.lib.mscomp_amd_splicer_create_extents(ctx._h, self.block_size, self.n_src, self.n_res, self.n_ext, self.n_blocks_table, 0, C.byref(self._h)),
+            "mscomp_amd_splicer_create_extents")
+        return self
+
+    def splice_extents(self, sources, d_ext_first, d_ext, d_new_packed, d_new_block_first, d_new_block_off, d_new_res_len, d_status, d_new_block_crc=None,
+                       new_cap=None):
+        """``sources`` as for splice(). New resource q is the concatenation of the extents d_ext_first[q] .. d_ext_first[q + 1] - 1; extent e =
+        d_ext[4 e .. 4 e + 3] = (source, resource, first block, block count; a count of 2**64 - 1 = through the last block). The outputs
+        are splice()'s, per new resource. d_status[q] is MSCOMP_OK, MSCOMP_ARG_ERROR (no such source, resource or block range, a broken
+        table entry, an extent that ends short in front of another, or no room in the new table) or MSCOMP_DATA_ERROR (a wrong block
+        count) with resource q empty, or MSCOMP_BUF_ERROR (a block did not fit below new_cap)."""
+        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
+        if d_new_packed is not None and cap > d_new_packed.numel():
+            raise ValueError("new_cap exceeds d_new_packed")
+        if len(sources) != self.n_src:
+            raise ValueError("one source per n_src")
+        views = _blocks_views(sources)
+        p = _ptrs(d_ext_first, d_ext, d_new_packed, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_status)
+        _ok(self.ctx.lib.mscomp_amd_splicer_splice_extents(self._h, views, p[0], p[1], p[2], cap, *p[3:]), "mscomp_amd_splicer_splice_extents")
+
+
+def _splice_host(containers, n_new, nbt, room, ctx, make, run):
+    """what blocks_splice and blocks_splice_extents share: the sources uploaded, the new arrays made, ``run`` called, the results fetched"""
     import torch
     own = ctx is None
     ctx = ctx or Context()
-    B = int(block_size)
-    M64 = (1 << 64) - 1
-    npk = len(picks)
     lens = [[int(x) for x in c[3]] for c in containers]
-    got = [lens[s][r] if 0 <= s < len(lens) and 0 <= r < len(lens[s]) else 0 for s, r in picks]
-    nbt = sum((L + B - 1) // B for L in got)
-    room = sum(got)
     with_crc = all(c[4] is not None for c in containers)
     dev = torch.device("cuda", ctx.device)
     with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
-        sp = BlockSplicer(ctx, B, len(containers), npk, nbt)
+        sp = make(ctx)
         srcs = []
         for (packed, first, off, _, crc), ln in zip(containers, lens):
             packed, d_packed = _dev_packed(packed, dev)
             rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
             srcs.append((d_packed, _dev_u64(first, len(ln) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(ln, 1, dev),
                          _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(ln), rows))
-        d_pick = _dev_u64(np.array([(int(s) & M64, int(r) & M64) for s, r in picks], dtype=np.uint64), 2, dev)
         d_new = torch.zeros(room + 16, dtype=torch.uint8, device=dev)
-        d_nfirst = torch.zeros(npk + 1, dtype=torch.int64, device=dev)
+        d_nfirst = torch.zeros(n_new + 1, dtype=torch.int64, device=dev)
         d_noff = torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
         d_ncrc = torch.zeros(max(1, nbt), dtype=torch.int32, device=dev) if with_crc else None
-        d_nlen = torch.zeros(max(1, npk), dtype=torch.int64, device=dev)
-        d_st = torch.zeros(max(1, npk), dtype=torch.int32, device=dev)
-        sp.splice(srcs, d_pick, d_new, d_nfirst, d_noff, d_nlen, d_st, d_new_block_crc=d_ncrc, new_cap=room)
+        d_nlen = torch.zeros(max(1, n_new), dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, n_new), dtype=torch.int32, device=dev)
+        run(sp, srcs, dev, d_new, d_nfirst, d_noff, d_nlen, d_st, d_ncrc)
         ctx.stream.synchronize()
         nfirst = d_nfirst.cpu().numpy().view(np.uint64).copy()
-        nb = int(nfirst[npk])
+        nb = int(nfirst[n_new])
         noff = d_noff.cpu().numpy().view(np.uint64)[: nb + 1].copy()
         new_packed = d_new.cpu().numpy()[: min(int(noff[nb]), room)].copy()
         ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nb].copy()
@@ -960,7 +986,71 @@ def blocks_splice(containers, picks, block_size, ctx=None):
         sp.close()
     if own:
         ctx.close()
-    return new_packed, nfirst, noff, [int(x) for x in h_len[:npk]], ncrc, [int(x) for x in h_st[:npk]]
+    return new_packed, nfirst, noff, [int(x) for x in h_len[:n_new]], ncrc, [int(x) for x in h_st[:n_new]]
+
+
+def blocks_splice_extents(containers, resources, block_size, ctx=None):
+    """A new block container whose resources are made of block extents of up to four others on the GPU (BlockSplicer.splice_extents), no
+    block decoded: ``containers`` as for blocks_splice, ``resources`` a list -- one entry per new resource -- of lists of (container,
+    resource, first block, block count), a count of None meaning "through the last block". Every extent but the last non-empty one of a
+    new resource must end on a block boundary. Returns what blocks_splice returns."""
+    B = int(block_size)
+    M64 = (1 << 64) - 1
+    lens = [[int(x) for x in c[3]] for c in containers]
+    ext, ext_first, nbt, room = [], [0], 0, 0
+    for exts in resources:
+        for s, r, k0, c in exts:
+            ext.append((int(s) & M64, int(r) & M64, int(k0) & M64, M64 if c is None else int(c) & M64))
+            if 0 <= s < len(lens) and 0 <= r < len(lens[s]):       # what the extent can bring at most: sizes the new arrays
+                n = (lens[s][r] + B - 1) // B
+                k = min(max(int(k0), 0), n)
+                cnt = n - k if c is None else min(max(int(c), 0), n - k)
+                nbt += cnt
+                room += min(cnt * B, lens[s][r] - k * B) if cnt else 0
+        ext_first.append(len(ext))
+    n_res = len(resources)
+
+    def run(sp, srcs, dev, d_new, d_nfirst, d_noff, d_nlen, d_st, d_ncrc):
+        d_ext = _dev_u64(np.array(ext, dtype=np.uint64).reshape(-1), 4, dev)
+        sp.splice_extents(srcs, _dev_u64(ext_first, 1, dev), d_ext, d_new, d_nfirst, d_noff, d_nlen, d_st, d_new_block_crc=d_ncrc, new_cap=room)
+    return _splice_host(containers, n_res, nbt, room, ctx, lambda c: BlockSplicer.for_extents(c, B, len(containers), n_res, len(ext), nbt), run)
+
+
+def blocks_concat(containers, parts, block_size, ctx=None):
+    """One resource that joins the whole resources ``parts`` = [(container, resource), ...] in that order (every part but the last non-empty
+    one must be a whole number of blocks long). Returns what blocks_splice returns, for a container of one resource."""
+    return blocks_splice_extents(containers, [[(s, r, 0, None) for s, r in parts]], block_size, ctx=ctx)
+
+
+def blocks_split_at(container, resource, k, block_size, ctx=None):
+    """Resource ``resource`` of ``container`` split in front of its block ``k``: a container of two resources, the blocks [0, k) and the
+    blocks from k on. Returns what blocks_splice returns."""
+    return blocks_splice_extents([container], [[(0, resource, 0, k)], [(0, resource, k, None)]], block_size, ctx=ctx)
+
+
+def blocks_cut_range(container, resource, k0, count, block_size, ctx=None):
+    """Resource ``resource`` of ``container`` without its blocks [k0, k0 + count) (FALLOC_FL_COLLAPSE_RANGE): a container of one resource.
+    Returns what blocks_splice returns."""
+    return blocks_splice_extents([container], [[(0, resource, 0, k0), (0, resource, k0 + count, None)]], block_size, ctx=ctx)
+
+
+def blocks_splice(containers, picks, block_size, ctx=None):
+    """A new block container from resources of up to four others on the GPU (BlockSplicer), no block decoded: ``containers`` is a list of
+    (packed, block_first, block_off, lengths, block_crc or None) of one format and ``block_size``, ``picks`` a list of (container,
+    resource): pick p becomes resource p. The new container gets checksums when every source has them. Returns numpy arrays and lists
+    (new_packed uint8, new_first uint64 of n + 1, new_block_off uint64 of nb + 1, new_lengths, new_block_crc uint32 or None, statuses)."""
+    B = int(block_size)
+    M64 = (1 << 64) - 1
+    npk = len(picks)
+    lens = [[int(x) for x in c[3]] for c in containers]
+    got = [lens[s][r] if 0 <= s < len(lens) and 0 <= r < len(lens[s]) else 0 for s, r in picks]
+    nbt = sum((L + B - 1) // B for L in got)
+    room = sum(got)
+
+    def run(sp, srcs, dev, d_new, d_nfirst, d_noff, d_nlen, d_st, d_ncrc):
+        d_pick = _dev_u64(np.array([(int(s) & M64, int(r) & M64) for s, r in picks], dtype=np.uint64), 2, dev)
+        sp.splice(srcs, d_pick, d_new, d_nfirst, d_noff, d_nlen, d_st, d_new_block_crc=d_ncrc, new_cap=room)
+    return _splice_host(containers, npk, nbt, room, ctx, lambda c: BlockSplicer(c, B, len(containers), npk, nbt), run)
 
 
 class BlockDeduper(_Handle):

@@ -437,27 +437,56 @@ MSCompStatus mscomp_amd_writer_resize(mscomp_amd_writer* w, const uint8_t* d_pac
 struct mscomp_amd_splicer {
 	mscomp_amd_ctx* ctx = nullptr;
 	uint32_t shift = 0, n_src = 0, n_pick = 0, nbt = 0;    // block_size = 1 << shift; nbt = n_blocks_table of the NEW container
-	mscomp_amd_plan run;
-	DevBuf addr;                                           // u64 x nbt
+	uint32_t n_ext = 0;                                    // (a splicer made for extents: n_pick is its n_res)
+	bool extents = false;                                  // made by mscomp_amd_splicer_create_extents: the scratch holds a SpliceExtTab
+	mscomp_amd_plan run, xrun;                             // (splice and splice_extents keep separate graphs)
+	DevBuf addr;                                           // u64 x nbt; a splicer made for extents: SpliceExtTab, the address column first
+	SpliceExtTab t{};
 };
 static_assert(sizeof(mscomp_amd_blocks_view) == sizeof(SpliceView) && sizeof(SpliceView) == 8 * sizeof(void*), "a view is eight words of the graph's key");
+static_assert(SX_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header states");
 
-MSCompStatus mscomp_amd_splicer_create(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_pick, uint64_t n_blocks_table, uint32_t flags,
-                                       mscomp_amd_splicer** out)
+// the columns of a splicer made for extents from `base` on; returns where they end: from a null base, their bytes
+static uintptr_t splice_ext_tab(SpliceExtTab& t, void* base, size_t nbt, size_t n_ext)
 {
-	if (!out) { return MSCOMP_ARG_ERROR; }
+	Carve k{reinterpret_cast<uintptr_t>(base)};
+	t.addr = k.q(nbt); t.ext_row = k.q(n_ext + 1); t.tsum = k.q(splice_row_tiles((uint32_t)nbt)); t.flag = k.w(2);
+	return k.at;
+}
+
+// both creates, from the null check of `out` on (`extents`: with the scratch of mscomp_amd_splicer_splice_extents)
+static MSCompStatus splicer_create(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_pick, bool extents, size_t n_ext, uint64_t n_blocks_table,
+                                   uint32_t flags, mscomp_amd_splicer** out)
+{
 	*out = nullptr;
 	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
-	if (n_src == 0 || n_src > MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_pick) || !count_ok(n_blocks_table)) { return MSCOMP_ARG_ERROR; }
+	if (n_src == 0 || n_src > MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_pick) || !count_ok(n_ext) || !count_ok(n_blocks_table)) { return MSCOMP_ARG_ERROR; }
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	std::unique_ptr<mscomp_amd_splicer> s(new (std::nothrow) mscomp_amd_splicer());
 	if (!s) { return MSCOMP_MEM_ERROR; }
 	s->ctx = c; s->shift = (uint32_t)__builtin_ctz(block_size); s->n_src = n_src; s->n_pick = (uint32_t)n_pick; s->nbt = (uint32_t)n_blocks_table;
-	s->run.ctx = c; s->run.n_units = 1;                    // (an empty pick list writes an empty container: it replays too)
-	if (!s->addr.reserve(8 * (size_t)n_blocks_table + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	s->n_ext = (uint32_t)n_ext; s->extents = extents;
+	s->run.ctx = s->xrun.ctx = c; s->run.n_units = s->xrun.n_units = 1;   // (an empty pick list writes an empty container: it replays too)
+	const size_t bytes = extents ? splice_ext_tab(s->t, nullptr, n_blocks_table, n_ext) : 8 * (size_t)n_blocks_table;
+	if (!s->addr.reserve(bytes + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	if (extents) { splice_ext_tab(s->t, s->addr.p, n_blocks_table, n_ext); }
 	*out = s.release();
 	return MSCOMP_OK;
+}
+
+MSCompStatus mscomp_amd_splicer_create(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_pick, uint64_t n_blocks_table, uint32_t flags,
+                                       mscomp_amd_splicer** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	return splicer_create(c, block_size, n_src, n_pick, false, 0, n_blocks_table, flags, out);
+}
+
+MSCompStatus mscomp_amd_splicer_create_extents(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res, size_t n_ext, uint64_t n_blocks_table,
+                                               uint32_t flags, mscomp_amd_splicer** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	return splicer_create(c, block_size, n_src, n_res, true, n_ext, n_blocks_table, flags, out);
 }
 
 void mscomp_amd_splicer_destroy(mscomp_amd_splicer* s)
@@ -469,18 +498,25 @@ void mscomp_amd_splicer_destroy(mscomp_amd_splicer* s)
 	delete s;                                              // (run gives up its graph)
 }
 
+// the views of a call as the kernels take them; false: a view with a null table, or without checksums where the new container gets them
+static bool splice_views(const mscomp_amd_splicer* s, const mscomp_amd_blocks_view* src, bool with_crc, SpliceSrc& k)
+{
+	for (uint32_t i = 0; i < s->n_src; ++i) {
+		const mscomp_amd_blocks_view& v = src[i];
+		if (v.n_res && (!v.d_block_first || !v.d_block_off || !v.d_res_len || (v.packed_len && !v.d_packed))) { return false; }
+		if (with_crc && !v.d_block_crc) { return false; }
+		k.v[i] = { v.d_packed, v.packed_len, v.d_block_first, v.d_block_off, v.d_res_len, with_crc ? v.d_block_crc : nullptr, v.n_res, v.n_blocks_table };
+	}
+	return true;
+}
+
 MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* s, const mscomp_amd_blocks_view* src, const uint64_t* d_pick, uint8_t* d_new_packed, uint64_t new_cap,
                                        uint64_t* d_new_block_first, uint64_t* d_new_block_off, uint32_t* d_new_block_crc, uint64_t* d_new_res_len, int32_t* d_status)
 {
 	if (!s || !src || !d_new_block_first || !d_new_block_off || (s->nbt && !d_new_packed)) { return MSCOMP_ARG_ERROR; }
 	if (s->n_pick && (!d_pick || !d_new_res_len || !d_status)) { return MSCOMP_ARG_ERROR; }
 	SpliceSrc k{};
-	for (uint32_t i = 0; i < s->n_src; ++i) {
-		const mscomp_amd_blocks_view& v = src[i];
-		if (v.n_res && (!v.d_block_first || !v.d_block_off || !v.d_res_len || (v.packed_len && !v.d_packed))) { return MSCOMP_ARG_ERROR; }
-		if (d_new_block_crc && !v.d_block_crc) { return MSCOMP_ARG_ERROR; }
-		k.v[i] = { v.d_packed, v.packed_len, v.d_block_first, v.d_block_off, v.d_res_len, d_new_block_crc ? v.d_block_crc : nullptr, v.n_res, v.n_blocks_table };
-	}
+	if (!splice_views(s, src, d_new_block_crc != nullptr, k)) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_ctx* c = s->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
@@ -493,6 +529,35 @@ MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* s, const mscomp_amd_b
 		{ KernelTimer t(c, "sp_layout_kernel"); launch_splice_layout(c->stream, k, s->n_src, s->n_pick, s->nbt, s->shift, new_cap, d_pick, d_new_block_first, d_new_block_off,
 		                                                             d_new_block_crc, d_new_res_len, d_status, addr); }
 		{ KernelTimer t(c, "bk_move_kernel"); launch_blocks_move(c->stream, s->nbt, new_cap, d_new_block_off, addr, d_new_packed, c->cpd_blocks); }
+	});
+}
+
+// Splice by extents: the extent pass, the three row passes tiled over the new table, the move.
+MSCompStatus mscomp_amd_splicer_splice_extents(mscomp_amd_splicer* s, const mscomp_amd_blocks_view* src, const uint64_t* d_ext_first, const uint64_t* d_ext,
+                                               uint8_t* d_new_packed, uint64_t new_cap, uint64_t* d_new_block_first, uint64_t* d_new_block_off,
+                                               uint32_t* d_new_block_crc, uint64_t* d_new_res_len, int32_t* d_status)
+{
+	if (!s || !s->extents || !src || !d_ext_first || !d_new_block_first || !d_new_block_off || (s->nbt && !d_new_packed)) { return MSCOMP_ARG_ERROR; }
+	if ((s->n_ext && !d_ext) || (s->n_pick && (!d_new_res_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	SpliceSrc k{};
+	if (!splice_views(s, src, d_new_block_crc != nullptr, k)) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = s->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[41] = {};
+	memcpy(args, &k, sizeof k);
+	const void* rest[9] = { d_ext_first, d_ext, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc,
+	                        d_new_res_len, d_status };
+	memcpy(args + 32, rest, sizeof rest);
+	return plan_run(&s->xrun, args, [&] {
+		{ KernelTimer t(c, "sx_extent_kernel"); launch_splice_extents(c->stream, k, s->n_src, s->n_pick, s->n_ext, s->nbt, s->shift, d_ext_first, d_ext, d_new_block_first,
+		                                                              d_new_block_off, d_new_res_len, d_status, s->t); }
+		if (s->nbt) {
+			{ KernelTimer t(c, "sx_tile_kernel"); launch_splice_tiles(c->stream, k, s->n_pick, s->nbt, d_ext_first, d_ext, d_new_block_first, d_new_block_off, d_new_block_crc, s->t); }
+			{ KernelTimer t(c, "sx_tilescan_kernel"); launch_splice_tilescan(c->stream, s->nbt, s->t); }
+			{ KernelTimer t(c, "sx_rows_kernel"); launch_splice_rows(c->stream, s->n_pick, s->nbt, new_cap, d_ext_first, d_new_block_first, d_new_block_off, d_new_block_crc, d_status, s->t); }
+		}
+		{ KernelTimer t(c, "bk_move_kernel"); launch_blocks_move(c->stream, s->nbt, new_cap, d_new_block_off, s->t.addr, d_new_packed, c->cpd_blocks); }
 	});
 }
 

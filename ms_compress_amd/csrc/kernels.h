@@ -354,6 +354,28 @@ __device__ __forceinline__ SpliceView sp_view(const SpliceView& v0, const Splice
 void launch_splice_layout(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n_pick, uint32_t nbt, uint32_t shift, u64 cap, const u64* pick,
                           u64* new_first, u64* new_off, uint32_t* new_crc, u64* new_len, int32_t* status, u64* addr);
 
+// mscomp_amd_splicer_splice_extents: a new resource is a list of extents (source, resource, first block, block count). The splicer's
+// scratch for it (blockobj.hip splice_ext_tab knows the layout):
+#define SX_TILE DV_THREADS                             // rows per workgroup of the row passes (MSCOMP_AMD_SPLICE_ROW_TILE)
+inline uint32_t splice_row_tiles(uint32_t nbt) { return (nbt + SX_TILE - 1u) / SX_TILE; }
+struct SpliceExtTab {
+	u64* addr;                                         // nbt: where a new row's stored bytes lie (0 = nothing to move): launch_blocks_move
+	u64* ext_row;                                      // n_ext + 1: the running counts of the extent pass, then every extent's first new row
+	u64* tsum;                                         // splice_row_tiles(nbt): the stored bytes of a tile of rows, then their running sum
+	uint32_t* flag;                                    // 1: the extent table as a whole was refused (rule 0)
+};
+// the extent pass (one block): rules 0-6, new_first (n_res + 1), new_len and status (n_res), new_off[0], t.ext_row, t.flag
+void launch_splice_extents(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n_res, uint32_t n_ext, uint32_t nbt, uint32_t shift, const u64* ext_first,
+                           const u64* ext, u64* new_first, u64* new_off, u64* new_len, int32_t* status, const SpliceExtTab& t);
+// behind it, the three-launch scan over the NEW table's rows in tiles of SX_TILE (nbt > 0). tiles: per row its stored length (left in
+// new_off[row + 1]), new_crc (nbt, may be null) and t.addr, per tile its sum; tilescan (one block): the running sum of the tile sums; rows:
+// new_off (nbt + 1) and the capacity rule
+void launch_splice_tiles(hipStream_t st, const SpliceSrc& src, uint32_t n_res, uint32_t nbt, const u64* ext_first, const u64* ext, const u64* new_first, u64* new_off,
+                         uint32_t* new_crc, const SpliceExtTab& t);
+void launch_splice_tilescan(hipStream_t st, uint32_t nbt, const SpliceExtTab& t);
+void launch_splice_rows(hipStream_t st, uint32_t n_res, uint32_t nbt, u64 cap, const u64* ext_first, const u64* new_first, u64* new_off, uint32_t* new_crc, int32_t* status,
+                        const SpliceExtTab& t);
+
 // ---- block dedupers (dedup.hip; mscomp_amd_deduper_*) ----
 // The deduper's own tables, in one buffer (blockobj.hip dedup_tab is the only place that knows the layout). n = n_res_total, the bound of
 // the resources of all sources together; slots = 2 n + 64, the key table.
