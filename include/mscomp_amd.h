@@ -964,6 +964,31 @@ int          mscomp_amd_debug_decode_modes(mscomp_amd_ctx* ctx, uint32_t* out, s
  * was created; a dev plan with MSCOMP_AMD_DEV_LARGE_UNITS: read back from the tables its last execution built (0 before the first); any
  * other dev plan: 0. Returns 0, -1 on error. Works with or without MSCOMP_AMD_TEST_HOOKS (it switches nothing). */
 int          mscomp_amd_debug_plan_paths(mscomp_amd_plan* plan, uint32_t out[3]);
+/* Test hooks for the scratch contract: what an execution reads from scratch it has written itself, and no kernel touches
+ * the slack behind the bytes a buffer was reserved for. A target is (kind, object): a context (NULL = the calling thread's context of the
+ * one-shot entries, if it has one yet) with its scratch buffers; a plan with its tables; a block container, reader, writer, splicer or
+ * deduper with its own buffers and those of the dev plans inside it (names "cplan.*", "dplan.*"). All three need MSCOMP_AMD_TEST_HOOKS=1 and
+ * return -1 without it, for a null object, an unknown kind or a failed device call; then nothing is touched. */
+#define MSCOMP_AMD_SCRATCH_CTX     0
+#define MSCOMP_AMD_SCRATCH_PLAN    1
+#define MSCOMP_AMD_SCRATCH_BLOCKS  2
+#define MSCOMP_AMD_SCRATCH_READER  3
+#define MSCOMP_AMD_SCRATCH_WRITER  4
+#define MSCOMP_AMD_SCRATCH_SPLICER 5
+#define MSCOMP_AMD_SCRATCH_DEDUPER 6
+typedef struct mscomp_amd_scratch_rec {
+	const char* name;                /* static string: the buffer's name in the library's source */
+	uint64_t asked, cap, changed;    /* the most bytes it was reserved for, the bytes it has, bytes of [asked, cap) that differ from `byte` */
+} mscomp_amd_scratch_rec;
+/* The names of a context's scratch buffers, in the order of a report on a context: min(count, cap) of them to names, returns the count.
+ * Needs no device. */
+int          mscomp_amd_debug_scratch_names(const char** names, int cap);
+/* Fills, on the context's stream, every buffer of the target over all its bytes (slack_only 0) or over its slack [asked, cap) alone
+ * (slack_only 1) with `byte`; captured graphs stay valid (no buffer moves). The tables of a plan with HOST tables hold what its creation
+ * uploaded: such a plan refuses slack_only 0 (-1). Returns the number of buffers filled. */
+int          mscomp_amd_debug_scratch_poison(int kind, void* object, int slack_only, int byte);
+/* Synchronizes the stream, then one record per buffer of the target, min(count, cap) of them; returns the count. */
+int          mscomp_amd_debug_scratch_report(int kind, void* object, int byte, mscomp_amd_scratch_rec* recs, int cap);
 /* Hardware self-check: the LZNT1 bucket sort and the Xpress chain links rely on gfx950 serving the returning
  * same-address LDS atomics of one wave instruction in lane order. Returns the number of lanes (over blocks x rounds x 64
  * lanes x {add, exchange}, keys drawn from nkeys <= 2048 values) that were served out of order: 0 on gfx950;

@@ -10,6 +10,7 @@ GPU is visible they raise.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -47,10 +48,16 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_splicer_create", "mscomp_amd_splicer_destroy", "mscomp_amd_splicer_splice",
     "mscomp_amd_splicer_create_extents", "mscomp_amd_splicer_splice_extents",
     "mscomp_amd_deduper_create", "mscomp_amd_deduper_destroy", "mscomp_amd_deduper_dedup",
+    "mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report",
 ]
 MSCOMP_AMD_SPLICE_SRC_MAX = 4
 MSCOMP_AMD_SPLICE_ROW_TILE = 1024                              # rows of the new table per workgroup of splice_extents' row passes
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
+
+
+class ScratchRec(C.Structure):
+    """mscomp_amd_scratch_rec: one buffer of a scratch report"""
+    _fields_ = [("name", C.c_char_p), ("asked", C.c_uint64), ("cap", C.c_uint64), ("changed", C.c_uint64)]
 
 
 class BlocksView(C.Structure):
@@ -247,6 +254,12 @@ def load_library():
     lib.mscomp_amd_debug_lzd_walked.restype = C.c_uint32
     lib.mscomp_amd_debug_decode_modes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.mscomp_amd_debug_decode_modes.restype = C.c_int
+    lib.mscomp_amd_debug_scratch_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
+    lib.mscomp_amd_debug_scratch_names.restype = C.c_int
+    lib.mscomp_amd_debug_scratch_poison.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int]
+    lib.mscomp_amd_debug_scratch_poison.restype = C.c_int
+    lib.mscomp_amd_debug_scratch_report.argtypes = [C.c_int, C.c_void_p, C.c_int, C.POINTER(ScratchRec), C.c_int]
+    lib.mscomp_amd_debug_scratch_report.restype = C.c_int
     _lib = lib
     return lib
 
@@ -308,12 +321,16 @@ class Context:
             s = torch.cuda.current_stream() if stream is None else stream
         self.stream = s
         self._h = C.c_void_p()
+        self._handles = weakref.WeakSet()                  # the plans and block objects that live in this context (_Handle)
         st = self.lib.mscomp_amd_ctx_create(self.device, C.c_void_p(s.cuda_stream), C.byref(self._h))
         if st != MSCOMP_OK:
             raise MSCompError(st, "mscomp_amd_ctx_create")
 
     def close(self):
+        """Destroys the context, and first whatever still lives in it: an object's destroy call reads its context."""
         if self._h:
+            for h in list(self._handles):
+                h.close()
             self.lib.mscomp_amd_ctx_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -357,6 +374,7 @@ class _Handle:
 
     def __init__(self, ctx):
         self.ctx, self._h = ctx, C.c_void_p()
+        ctx._handles.add(self)
 
     def close(self):
         if self._h:
@@ -1151,6 +1169,44 @@ def plan_paths(plan):
     if plan.ctx.lib.mscomp_amd_debug_plan_paths(plan._h, out) != 0:
         raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_debug_plan_paths")
     return (int(out[0]), int(out[1]), int(out[2]))
+
+
+def _scratch_target(target):
+    """(kind, handle) of a scratch hook's target: None (the calling thread's one-shot context), a Context, a plan of any kind or a block object"""
+    if target is None or isinstance(target, Context):
+        return 0, (None if target is None else target._h)
+    kinds = ((BlockContainer, 2), (BlockReader, 3), (BlockWriter, 4), (BlockSplicer, 5), (BlockDeduper, 6), (_Handle, 1))
+    return next(k for cls, k in kinds if isinstance(target, cls)), target._h
+
+
+def scratch_names():
+    """mscomp_amd_debug_scratch_names (test hook, needs no device): the names of a context's scratch buffers, in a report's order."""
+    lib = load_library()
+    n = lib.mscomp_amd_debug_scratch_names(None, 0)
+    if n < 0:
+        raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_debug_scratch_names")
+    names = (C.c_char_p * n)()
+    lib.mscomp_amd_debug_scratch_names(names, n)
+    return [x.decode() for x in names]
+
+
+def scratch_poison(target, byte, slack_only=False):
+    """mscomp_amd_debug_scratch_poison (test hook): every buffer of ``target`` -- None, a Context, a plan, a block object -- filled with
+    ``byte`` on the context's stream, whole or over its slack alone. Returns the number of buffers filled, -1 when refused."""
+    kind, h = _scratch_target(target)
+    return load_library().mscomp_amd_debug_scratch_poison(kind, h, 1 if slack_only else 0, int(byte))
+
+
+def scratch_report(target, byte):
+    """mscomp_amd_debug_scratch_report (test hook; synchronizes the stream): {name: (asked, cap, changed)} over the buffers of ``target``,
+    changed = the bytes of [asked, cap) that differ from ``byte``. Raises MSCompError when refused."""
+    kind, h = _scratch_target(target)
+    lib = load_library()
+    recs = (ScratchRec * 64)()
+    n = lib.mscomp_amd_debug_scratch_report(kind, h, int(byte), recs, 64)
+    if n < 0 or n > 64:
+        raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_debug_scratch_report")
+    return {recs[i].name.decode(): (int(recs[i].asked), int(recs[i].cap), int(recs[i].changed)) for i in range(n)}
 
 
 def compact_dev(ctx, d_src, d_src_off, d_len, align=1, d_packed=None, d_packed_off=None, packed_cap=None):

@@ -258,7 +258,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	{	// the smallest pooled buffer that is large enough, else a new one
 		size_t best = c->table_pool.size();
 		for (size_t i = 0; i < c->table_pool.size(); ++i) { if (c->table_pool[i].cap >= bytes && (best == c->table_pool.size() || c->table_pool[i].cap < c->table_pool[best].cap)) { best = i; } }
-		if (best < c->table_pool.size()) { p->tables = c->table_pool[best]; c->table_pool.erase(c->table_pool.begin() + (long)best); }
+		if (best < c->table_pool.size()) { p->tables = c->table_pool[best]; p->tables.asked = 0; c->table_pool.erase(c->table_pool.begin() + (long)best); }   // (asked: this plan's own, from the reserve below)
 	}
 	if (!p->tables.reserve(bytes)) { return MSCOMP_MEM_ERROR; }
 	if (hipMemcpyAsync(p->tables.p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { return MSCOMP_ERRNO; }
@@ -1267,7 +1267,79 @@ struct OneShotTls {
 	}
 };
 
+OneShotTls& one_shot_tls() { thread_local OneShotTls tls; return tls; }
+
 } // namespace
+
+// ---- the scratch hooks (include/mscomp_amd.h): fill scratch with a byte, count the slack bytes that changed ----
+// the buffers a plan owns (owner 0: the plan itself, 1 / 2: the compress / decompress plan inside a block object); a dev plan rewrites all
+// of them in every execution, a host plan's hold what its creation uploaded
+extern "C++" void msc::scratch_of_plan(mscomp_amd_plan* p, int owner, std::vector<ScratchEnt>& v)
+{
+	static const char* const names[3][4] = { { "tables", "tokpre", "lzg_tab", "xps_tab" }, { "cplan.tables", "cplan.tokpre", "cplan.lzg_tab", "cplan.xps_tab" },
+	                                         { "dplan.tables", "dplan.tokpre", "dplan.lzg_tab", "dplan.xps_tab" } };
+	if (!p) { return; }
+	DevBuf* const b[4] = { &p->tables, &p->tokpre, &p->lzg_tab, &p->xps_tab };
+	for (int i = 0; i < 4; ++i) { v.push_back(ScratchEnt{ names[owner][i], b[i], !p->dev }); }
+}
+// the target of a hook: its context (null: none, or the hooks are off) and its buffers
+static mscomp_amd_ctx* scratch_target(int kind, void* obj, std::vector<ScratchEnt>& v)
+{
+	if (!test_hooks_on()) { return nullptr; }
+	if (kind == MSCOMP_AMD_SCRATCH_CTX) {
+		mscomp_amd_ctx* c = obj ? static_cast<mscomp_amd_ctx*>(obj) : one_shot_tls().ctx;
+		if (c) { v = c->scratch(); }
+		return c;
+	}
+	if (!obj) { return nullptr; }
+	if (kind == MSCOMP_AMD_SCRATCH_PLAN) { mscomp_amd_plan* p = static_cast<mscomp_amd_plan*>(obj); scratch_of_plan(p, 0, v); return p->ctx; }
+	return scratch_of_object(kind, obj, v);
+}
+int mscomp_amd_debug_scratch_names(const char** names, int cap)
+{
+	if (!test_hooks_on() || (cap > 0 && !names)) { return -1; }
+#define MSC_X(n) #n,
+	static const char* const all[] = { MSC_CTX_BUFS(MSC_X) };      // (the list mscomp_amd_ctx::scratch() is made from)
+#undef MSC_X
+	const int n = (int)(sizeof all / sizeof all[0]);
+	for (int i = 0; i < n && i < cap; ++i) { names[i] = all[i]; }
+	return n;
+}
+int mscomp_amd_debug_scratch_poison(int kind, void* obj, int slack_only, int byte)
+{
+	std::vector<ScratchEnt> v;
+	mscomp_amd_ctx* c = scratch_target(kind, obj, v);
+	if (!c) { return -1; }
+	if (!slack_only) { for (const ScratchEnt& e : v) { if (e.keeps) { return -1; } } }   // a host plan's tables are uploaded once: only their slack may go
+	DeviceGuard g(c->device);
+	if (!g.ok) { return -1; }
+	int filled = 0;
+	for (const ScratchEnt& e : v) {
+		const size_t from = slack_only ? e.b->asked : 0;
+		if (!e.b->p || from >= e.b->cap) { continue; }
+		if (hipMemsetAsync(static_cast<uint8_t*>(e.b->p) + from, byte & 0xFF, e.b->cap - from, c->stream) != hipSuccess) { (void)hipGetLastError(); return -1; }
+		++filled;
+	}
+	return filled;
+}
+int mscomp_amd_debug_scratch_report(int kind, void* obj, int byte, mscomp_amd_scratch_rec* recs, int cap)
+{
+	std::vector<ScratchEnt> v;
+	mscomp_amd_ctx* c = scratch_target(kind, obj, v);
+	if (!c || (cap > 0 && !recs)) { return -1; }
+	DeviceGuard g(c->device);
+	if (!g.ok || hipStreamSynchronize(c->stream) != hipSuccess) { return -1; }
+	std::vector<uint8_t> host;
+	for (int i = 0; i < (int)v.size() && i < cap; ++i) {
+		const DevBuf& b = *v[(size_t)i].b;
+		recs[i].name = v[(size_t)i].name; recs[i].asked = b.asked; recs[i].cap = b.cap; recs[i].changed = 0;
+		if (!b.p || b.asked >= b.cap) { continue; }
+		host.resize(b.cap - b.asked);
+		if (hipMemcpy(host.data(), static_cast<const uint8_t*>(b.p) + b.asked, host.size(), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -1; }
+		for (uint8_t x : host) { recs[i].changed += x != (uint8_t)byte; }
+	}
+	return (int)v.size();
+}
 
 // Page-locking of caller buffers for the large host-pointer calls. hipHostRegister refuses a range that overlaps a registered one, and a range
 // one thread unregisters while another thread's copy of the same pages is in flight would pull the pages from under that copy (two threads may
@@ -1461,7 +1533,7 @@ static MSCompStatus lznt1_zero_copy(OneShotTls& tls, bool decompress, const uint
 static MSCompStatus one_shot(MSCompFormat format, bool decompress, const uint8_t* in, size_t in_len, uint8_t* out, size_t* out_len)
 {
 	if (!out_len || (in_len && !in) || (*out_len && !out)) { return MSCOMP_ARG_ERROR; }
-	thread_local OneShotTls tls;
+	OneShotTls& tls = one_shot_tls();
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess) { return MSCOMP_ERRNO; }   // no GPU / no HIP runtime: fail loudly, never fall back
 	if (tls.ctx && tls.ctx->device != dev) { tls.drop(); }

@@ -646,6 +646,29 @@ MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* d, const mscomp_amd_bl
 	});
 }
 
+// ---- the scratch hooks' view of the objects above (api.hip: mscomp_amd_debug_scratch_*) ----
+extern "C++" mscomp_amd_ctx* msc::scratch_of_object(int kind, void* obj, std::vector<ScratchEnt>& v)
+{
+	const auto access = [&v](BlockAccess* a) { v.push_back(ScratchEnt{ "tab", &a->tab, false }); v.push_back(ScratchEnt{ "cache", &a->cache, false }); scratch_of_plan(a->dplan, 2, v); };
+	switch (kind) {
+	case MSCOMP_AMD_SCRATCH_BLOCKS: {
+		mscomp_amd_blocks* b = static_cast<mscomp_amd_blocks*>(obj);
+		v.push_back(ScratchEnt{ "tab", &b->tab, false }); v.push_back(ScratchEnt{ "stage", &b->stage, false });
+		scratch_of_plan(b->cplan, 1, v); scratch_of_plan(b->dplan, 2, v);
+		return b->ctx;
+	}
+	case MSCOMP_AMD_SCRATCH_READER: { mscomp_amd_reader* r = static_cast<mscomp_amd_reader*>(obj); access(r); return r->ctx; }
+	case MSCOMP_AMD_SCRATCH_WRITER: {
+		mscomp_amd_writer* w = static_cast<mscomp_amd_writer*>(obj);
+		access(w); v.push_back(ScratchEnt{ "stage", &w->stage, false }); scratch_of_plan(w->cplan, 1, v);
+		return w->ctx;
+	}
+	case MSCOMP_AMD_SCRATCH_SPLICER: { mscomp_amd_splicer* s = static_cast<mscomp_amd_splicer*>(obj); v.push_back(ScratchEnt{ "addr", &s->addr, false }); return s->ctx; }
+	case MSCOMP_AMD_SCRATCH_DEDUPER: { mscomp_amd_deduper* d = static_cast<mscomp_amd_deduper*>(obj); v.push_back(ScratchEnt{ "tab", &d->tab, false }); return d->ctx; }
+	default: return nullptr;
+	}
+}
+
 // ---- resource CRCs from block CRCs (include/mscomp_amd.h; kernels: crc32.hip) ----
 MSCompStatus mscomp_amd_res_crc_dev(mscomp_amd_ctx* c, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, const uint64_t* d_block_first,
                                     const uint64_t* d_res_len, const uint32_t* d_block_crc, uint32_t* d_res_crc, int32_t* d_status)

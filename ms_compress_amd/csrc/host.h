@@ -18,18 +18,22 @@ extern std::atomic<uint64_t> g_mode_epoch;
 
 struct DevBuf {
 	void* p = nullptr; size_t cap = 0;
+	size_t asked = 0;                                  // the largest n reserve was asked for since the buffer was last empty: [asked, cap) is slack no kernel may touch (the scratch hooks)
 	uint64_t* epoch = nullptr;                         // the owning context's epoch (null for plan-owned tables)
 	bool reserve(size_t n)
 	{
+		if (n > asked) { asked = n; }
 		if (n <= cap) { return true; }
 		if (epoch) { ++*epoch; }
 		if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
 		const size_t want = n + n / 8 + 256;
-		if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return false; }
+		if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; asked = 0; return false; }
 		cap = want; return true;
 	}
-	void release() { if (p) { (void)hipFree(p); if (epoch) { ++*epoch; } } p = nullptr; cap = 0; }
+	void release() { if (p) { (void)hipFree(p); if (epoch) { ++*epoch; } } p = nullptr; cap = 0; asked = 0; }
 };
+// one buffer of a scratch hook's target (mscomp_amd_debug_scratch_*): `keeps` = it holds what its creation uploaded (a host plan's tables)
+struct ScratchEnt { const char* name; DevBuf* b; bool keeps; };
 
 struct ProfRec { const char* name; hipEvent_t a, b; };
 
@@ -43,7 +47,7 @@ struct mscomp_amd_ctx {
 	hipStream_t stream = nullptr;
 	msc::DevBuf slots, slot_size, prefix, tile_sums;   // chunk scratch (grow-only, shared by all plans of the ctx)
 	msc::DevBuf lzrec;                                 // LZNT1 parse records per chunk (LZNT1_REC bytes: match tokens per window)
-	msc::DevBuf links, lasthead, mlen3, moff;          // Xpress-family match finder scratch (per 64 KiB link chunk)
+	msc::DevBuf links, lasthead, mlen3;                // Xpress-family match finder scratch (per 64 KiB link chunk; mlen3: one word per position, length - 3 | offset << 16)
 	msc::DevBuf wtok, wmat, wfar;                      // Xpress parse records per 64-position window (token mask, match mask, far length)
 	msc::DevBuf wrec, sbrec;                           // ... state / counts / prefixes per window (6 x u32), per super-block (tot 4 x u32, pre 3 x u64, seams)
 	msc::DevBuf tokbits, counts, extra, lens, codes, fb_list, fbflag;   // Xpress+Huffman per-chunk scratch
@@ -65,11 +69,21 @@ struct mscomp_amd_ctx {
 	bool profiling = false;
 	std::vector<msc::ProfRec> recs;
 	std::vector<hipEvent_t> free_events;
+	// every buffer above, once: bufs() and the names the scratch hooks report come from this one list
+#define MSC_CTX_BUFS(X) X(slots) X(slot_size) X(prefix) X(tile_sums) X(lzrec) X(links) X(lasthead) X(mlen3) X(wtok) X(wmat) X(wfar) X(wrec) X(sbrec) \
+	X(tokbits) X(counts) X(extra) X(lens) X(codes) X(fb_list) X(fbflag) X(dz_cin) X(dz_csize) X(dz_unit) X(dz_tok) X(dz_ntok) X(dz_xhc) X(dz_scr) \
+	X(lzg_bsum) X(lzg_dir) X(lzg_words) X(xps_buf) X(cp_tab) X(one_in) X(one_out) X(one_meta)
 	std::vector<msc::DevBuf*> bufs()
 	{
-		return { &slots, &slot_size, &prefix, &tile_sums, &lzrec, &links, &lasthead, &mlen3, &moff, &wtok, &wmat, &wfar, &wrec, &sbrec,
-		         &tokbits, &counts, &extra, &lens, &codes, &fb_list, &fbflag, &dz_cin, &dz_csize, &dz_unit, &dz_tok, &dz_ntok, &dz_xhc, &dz_scr,
-		         &lzg_bsum, &lzg_dir, &lzg_words, &xps_buf, &cp_tab, &one_in, &one_out, &one_meta };
+#define MSC_X(n) &n,
+		return { MSC_CTX_BUFS(MSC_X) };
+#undef MSC_X
+	}
+	std::vector<msc::ScratchEnt> scratch()
+	{
+#define MSC_X(n) { #n, &n, false },
+		return { MSC_CTX_BUFS(MSC_X) };
+#undef MSC_X
 	}
 	mscomp_amd_ctx() { for (msc::DevBuf* b : bufs()) { b->epoch = &epoch; } }
 };
@@ -142,6 +156,9 @@ void note_modes(mscomp_amd_plan* p);
 bool decode_dev_counts(MSCompFormat format, uint64_t N, uint64_t in_total_max, uint64_t O, bool sizing, uint64_t& I, uint64_t& chunks, uint64_t& toks, uint64_t& cands);
 void dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                 uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status);
+void scratch_of_plan(mscomp_amd_plan* p, int owner, std::vector<ScratchEnt>& v);
+// defined in blockobj.hip: the buffers of a block object (kind: MSCOMP_AMD_SCRATCH_BLOCKS ..) and its context; null: no such object
+mscomp_amd_ctx* scratch_of_object(int kind, void* obj, std::vector<ScratchEnt>& v);
 
 // One execution of a plan: its launches, given as `launch`. A plan that is executed repeatedly replays them as one hipGraph (the gaps between
 // the 4-9 launches are ~3 % of an LZNT1 pass): captured on the second execution and again whenever a pointer (args), the ctx scratch or a
