@@ -886,6 +886,88 @@ MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* dd, const mscomp_amd_b
                                       uint64_t* d_count     /* 4 */,
                                       int32_t*  d_status    /* n_res_total */);
 
+/* Diff: the deduper's second call. Which blocks of the resources of a container differ from the blocks AT THE SAME INDEX of the resources of
+ * its previous version (the base), without decoding a byte, answered as two extent lists mscomp_amd_splicer_splice_extents takes: the DELTA
+ * list, which cuts the changed blocks out of the new container, and the PATCH list, which puts base and delta together again -- "keep
+ * yesterday's container and what changed since" is diff, then one splice; "restore today's" is one more. The stored form of a block depends
+ * only on its data, the format and B, so between containers of ONE format and ONE block size (the caller's duty, as for splice) equal data
+ * means equal stored bytes, and equality is decided on the stored form. The tables tell most changed blocks; the only pass over the data is
+ * the compare that confirms the others, which reads the stored bytes of the blocks that did NOT change, in both versions, once.
+ *   Creation:     mscomp_amd_deduper_create_diff makes a mscomp_amd_deduper (destroyed by mscomp_amd_deduper_destroy, reported by the
+ *                 scratch hooks under MSCOMP_AMD_SCRATCH_DEDUPER) for n_pair pairs whose new resources have at most n_blocks_new blocks in
+ *                 all. Errors as mscomp_amd_deduper_create (there is no n_src), all checked before the context is used and with *dd
+ *                 cleared; n_pair and n_blocks_new are bounded by 0x7FFFFFF0. Such a deduper answers mscomp_amd_deduper_dedup with
+ *                 MSCOMP_ARG_ERROR and launches nothing, and a deduper made by mscomp_amd_deduper_create answers mscomp_amd_deduper_diff
+ *                 the same way.
+ *   Scratch:      reserved once, at creation, and never grown: 32 n_pair + 4 n_blocks_new + 64 ceil(n_blocks_new /
+ *                 MSCOMP_AMD_SPLICE_ROW_TILE) + 72 bytes (per pair its first row in the call's row numbering and the three counts in front
+ *                 of it; per new row a verdict word; eight words per tile of rows; 64 bytes of slack).
+ *   Sources:      base and next are HOST views, read on the host, passed by value, only read. The output arrays must not overlap a source
+ *                 array.
+ *   Notation:     pair p = (a, b) = d_pair[2 p], d_pair[2 p + 1]: resource a of base (MSCOMP_AMD_DIFF_NO_BASE: none) and resource b of
+ *                 next. B the block size; L_a, n_a and L_b, n_b the lengths and block counts (first[r + 1] - first[r]) of the two. Block k
+ *                 of a resource of length L has the data length e(k) = min(B, L - k B) and the stored length off[first + k + 1] -
+ *                 off[first + k].
+ *   Rules:        in this order:
+ *                   1. per pair, indices: MSCOMP_ARG_ERROR, no table entry of the pair read, when b >= next->n_res, or when a is not
+ *                      MSCOMP_AMD_DIFF_NO_BASE and a >= base->n_res;
+ *                   2. per pair, tables: dedup's rules 1-3 on resource b of next and, unless a is MSCOMP_AMD_DIFF_NO_BASE, on resource a of
+ *                      base; the pair gets the status of the first rule that refuses, b judged before a under each. Of base resource a the
+ *                      rows in front of n_b are judged by dedup's rule 3: the others are dropped (rule 5) and never looked at. No byte of a
+ *                      refused pair is read;
+ *                   3. room, the shape of splice-extents' rule 6: the saturating running total of n_b over the pairs that passed rule 1
+ *                      and dedup's rules 1 and 2, in pair order, including this pair and including pairs refused here, must not exceed
+ *                      n_blocks_new; otherwise MSCOMP_ARG_ERROR. (It is checked where the rows are numbered, in front of dedup's rule 3: a
+ *                      pair that rule refuses has counted.) A pair with n_b = 0 is never refused here;
+ *                   4. a refused pair has no extents in either list and d_changed[p] = 0. Pair indices never shift;
+ *                   5. equality: block k of an accepted pair is UNCHANGED when a is not MSCOMP_AMD_DIFF_NO_BASE, k < n_a, the data lengths
+ *                      e(k) are equal on both sides, the stored lengths are equal, the CRC words are equal -- when checksums take part --
+ *                      and the stored bytes are equal. Otherwise it is CHANGED. Base blocks at and behind n_b are dropped;
+ *                   6. runs: a RUN is a maximal stretch of consecutive blocks of one pair with the same verdict; every accepted pair with
+ *                      n_b > 0 is a sequence of runs. The PATCH extents of pair p are its runs in order: an unchanged run [k0, k0 + c) is
+ *                      (0, a, k0, c), a changed run is (1, p, i0, c) with i0 the number of changed blocks of the pair in front of k0. The
+ *                      DELTA extents of pair p are its changed runs in order, (0, b, k0, c). Counts are always explicit, never all-ones.
+ *                      d_delta_ext_first and d_patch_ext_first are the exclusive running counts of extents over the pairs, dense, entry
+ *                      n_pair the number of extents in use; the entries of d_delta_ext and d_patch_ext at and behind that number are not
+ *                      written. A run has at least one row, so neither list exceeds n_blocks_new extents;
+ *                   7. counts: d_changed[p] = the changed blocks of the pair; d_count[0] = the changed blocks of all accepted pairs,
+ *                      d_count[1] = the sum of n_b over the accepted pairs, d_count[2] = the stored bytes of all changed blocks -- the
+ *                      packed length of the delta container --, d_count[3] = the REFUTED: the blocks whose data length, stored length and
+ *                      -- when they take part -- CRC word agree but whose stored bytes differ. The four are the same from run to run.
+ *                 n_pair = 0 is legal and writes d_count = {0, 0, 0, 0} and entry 0 of the two running counts (where given).
+ *                 Consequence: mscomp_amd_splicer_splice_extents over the one source {next} with the delta lists writes a container D of
+ *                 n_pair resources whose resource p is the changed blocks of b in order. The same call over the sources {base, D} with the
+ *                 patch lists writes a container whose resource p has the length, the rows, the stored bytes and the CRC words of new
+ *                 resource b, for every accepted pair; when the pairs are (., 0), (., 1), ... (., next->n_res - 1) and all are accepted,
+ *                 its packed bytes and tables are byte for byte those of next. Splice-extents' rule 4 (only the last non-empty extent of
+ *                 a resource may end short) holds by construction: a short block is the last block of b, so it ends D's resource p when
+ *                 changed, and by the data-length clause of rule 5 a base block that is short where the new one is not is never carried.
+ *   Checksums:    they take part exactly when both views have a non-null d_block_crc; otherwise both arrays are ignored.
+ *   Execution:    as the deduper's: asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation, no
+ *                 synchronisation, nothing read back, seven launches fixed by the creation bounds (two when n_pair or n_blocks_new is 0):
+ *                 the seed, one workgroup -- rules 1-3 and the row numbering --; the rows' verdicts from the tables and the compare that
+ *                 confirms them, fixed grids; the runs in tiles of MSCOMP_AMD_SPLICE_ROW_TILE rows -- the tiles' sums, their running
+ *                 values (one workgroup), the rows --; the counts. Legal inside a caller's capture from the first execution, a graph of
+ *                 its own from the second outside one, captured again when an argument changes -- a field of a view counts as an
+ *                 argument. MSCOMP_ARG_ERROR for a null dd, base, next or d_count, a deduper made for dedup, any other null array when
+ *                 n_pair > 0 (d_delta_ext and d_patch_ext may be null while n_blocks_new is 0), or a view with a null table (or null
+ *                 d_packed with packed_len > 0) while its n_res > 0.
+ *   Left out:     content-addressed matching -- a block that moved to another index or another resource counts as changed; byte-granular
+ *                 deltas inside a block; more than one base per call; diff fused with the two splices in one call. */
+#define MSCOMP_AMD_DIFF_NO_BASE 0xFFFFFFFFFFFFFFFFull
+MSCompStatus mscomp_amd_deduper_create_diff(mscomp_amd_ctx* ctx, uint32_t block_size, size_t n_pair, uint64_t n_blocks_new, uint32_t flags,
+                                            mscomp_amd_deduper** dd);
+MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* dd,
+                                     const mscomp_amd_blocks_view* base, const mscomp_amd_blocks_view* next /* host, by value, only read */,
+                                     const uint64_t* d_pair            /* 2 n_pair: base resource a, new resource b */,
+                                     uint64_t* d_delta_ext_first       /* n_pair + 1 */,
+                                     uint64_t* d_delta_ext             /* 4 n_blocks_new */,
+                                     uint64_t* d_patch_ext_first       /* n_pair + 1 */,
+                                     uint64_t* d_patch_ext             /* 4 n_blocks_new */,
+                                     uint64_t* d_changed               /* n_pair: changed blocks of the pair */,
+                                     uint64_t* d_count                 /* 4 */,
+                                     int32_t*  d_status                /* n_pair */);
+
 /* Resource checksums from block checksums. After a write or a resize the block CRC-32s are current and the resource CRC-32s that
  * mscomp_amd_blocks_crc once wrote are stale; the block checksums determine them, and no data has to be read:
  *   d_res_crc[r] = XOR over the resource's blocks j of d_block_crc[j] x^(8 d_j)  (mod the CRC polynomial), d_j = the resource's bytes behind block j

@@ -16,4 +16,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   BlockWriter, blocks_write, blocks_resize, res_crc_dev, res_crc_from_blocks,
                   BlockSplicer, BlocksView, blocks_splice, MSCOMP_AMD_SPLICE_SRC_MAX, MSCOMP_AMD_SPLICE_ROW_TILE,
                   blocks_splice_extents, blocks_concat, blocks_split_at, blocks_cut_range,
-                  BlockDeduper, blocks_dedup)
+                  BlockDeduper, blocks_dedup,
+                  blocks_diff, blocks_delta, blocks_patch, MSCOMP_AMD_DIFF_NO_BASE)

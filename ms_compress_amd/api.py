@@ -48,11 +48,13 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_splicer_create", "mscomp_amd_splicer_destroy", "mscomp_amd_splicer_splice",
     "mscomp_amd_splicer_create_extents", "mscomp_amd_splicer_splice_extents",
     "mscomp_amd_deduper_create", "mscomp_amd_deduper_destroy", "mscomp_amd_deduper_dedup",
+    "mscomp_amd_deduper_create_diff", "mscomp_amd_deduper_diff",
     "mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report",
 ]
 MSCOMP_AMD_SPLICE_SRC_MAX = 4
 MSCOMP_AMD_SPLICE_ROW_TILE = 1024                              # rows of the new table per workgroup of splice_extents' row passes
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
+MSCOMP_AMD_DIFF_NO_BASE = (1 << 64) - 1                        # the base resource of a diff pair whose new resource has none
 
 
 class ScratchRec(C.Structure):
@@ -207,6 +209,10 @@ def load_library():
     lib.mscomp_amd_deduper_destroy.restype = None
     lib.mscomp_amd_deduper_dedup.argtypes = [C.c_void_p, C.POINTER(BlocksView)] + [C.c_void_p] * 5
     lib.mscomp_amd_deduper_dedup.restype = C.c_int
+    lib.mscomp_amd_deduper_create_diff.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_deduper_create_diff.restype = C.c_int
+    lib.mscomp_amd_deduper_diff.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.POINTER(BlocksView)] + [C.c_void_p] * 8
+    lib.mscomp_amd_deduper_diff.restype = C.c_int
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1096,6 +1102,113 @@ class BlockDeduper(_Handle):
             raise ValueError("one source per n_src")
         _ok(self.ctx.lib.mscomp_amd_deduper_dedup(self._h, _blocks_views(sources), *_ptrs(d_rep, d_new_index, d_pick, d_count, d_status)),
             "mscomp_amd_deduper_dedup")
+
+
+    @classmethod
+    def for_diff(cls, ctx, block_size, n_pair, n_blocks_new):
+        """A deduper for diff() (mscomp_amd_deduper_create_diff): ``n_pair`` pairs (base resource, new resource) whose new resources have
+        at most ``n_blocks_new`` blocks in all. Its scratch: 32 bytes per pair, 4 per new block and 64 per SPLICE_ROW_TILE of them, + 72.
+        It refuses dedup(), as a deduper made for dedup() refuses diff()."""
+        self = cls.__new__(cls)
+        _Handle.__init__(self, ctx)
+        self.block_size, self.n_pair, self.n_blocks_new = int(block_size), int(n_pair), int(n_blocks_new)
+        self.n_src, self.n_res_total, self.n_blocks_total = 2, self.n_pair, self.n_blocks_new
+        _ok(ctx.lib.mscomp_amd_deduper_create_diff(ctx._h, self.block_size, self.n_pair, self.n_blocks_new, 0, C.byref(self._h)),
+            "mscomp_amd_deduper_create_diff")
+        return self
+
+    def diff(self, base, new, d_pair, d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_changed, d_count, d_status):
+        """``base`` and ``new``: two sources as BlockSplicer.splice takes one. Pair p = (d_pair[2 p], d_pair[2 p + 1]) = (base resource or
+        MSCOMP_AMD_DIFF_NO_BASE, new resource). Block k of the new resource is unchanged when the base resource has a block k of the same
+        data length, stored length, CRC word (when both sources have checksums) and stored bytes. The answer is two extent lists in the
+        form BlockSplicer.splice_extents takes, one new resource per pair: d_delta_ext_first (n_pair + 1) / d_delta_ext (4 n_blocks_new),
+        over the one source [new], cut out the changed blocks; d_patch_ext_first / d_patch_ext, over the sources [base, that delta
+        container], put the new resources together again. d_changed (n_pair) = the changed blocks of a pair, d_count (4) = changed blocks,
+        blocks looked at, stored bytes of the changed blocks, blocks only the byte compare told apart; d_status[p] is MSCOMP_OK,
+        MSCOMP_ARG_ERROR (no such resource, a broken block_first entry, or no room within n_blocks_new) or MSCOMP_DATA_ERROR (a wrong
+        block count, a broken block_off entry), a refused pair having no extents."""
+        views = _blocks_views([base, new])
+        _ok(self.ctx.lib.mscomp_amd_deduper_diff(self._h, C.byref(views[0]), C.byref(views[1]), *_ptrs(d_pair, d_delta_ext_first, d_delta_ext, d_patch_ext_first,
+                                                                                                         d_patch_ext, d_changed, d_count, d_status)),
+            "mscomp_amd_deduper_diff")
+
+
+def _diff_pairs(base, new, pairs):
+    """the pairs of blocks_diff as (base resource or MSCOMP_AMD_DIFF_NO_BASE, new resource) of 64 bits each"""
+    M64 = MSCOMP_AMD_DIFF_NO_BASE
+    if pairs is None:
+        nb = len(base[3])
+        pairs = [(r if r < nb else None, r) for r in range(len(new[3]))]
+    return [(M64 if a is None else int(a) & M64, int(b) & M64) for a, b in pairs]
+
+
+def _extent_lists(first, ext, n):
+    """host lists, one per new resource, of (source, resource, first block, block count): what blocks_splice_extents takes"""
+    rows = [tuple(int(x) for x in e) for e in ext.reshape(-1, 4)[: int(first[n])]]
+    return [rows[int(first[p]): int(first[p + 1])] for p in range(n)]
+
+
+def blocks_diff(base, new, block_size, pairs=None, ctx=None):
+    """The blocks of ``new`` that differ from the blocks at the same index of ``base`` on the GPU (BlockDeduper.diff), no block decoded:
+    two containers of one format and ``block_size`` as blocks_splice takes one -- (packed, block_first, block_off, lengths, block_crc or
+    None) --, ``pairs`` a list of (base resource or None, new resource), by default (r, r) for the common resources and (None, r) for the
+    new resources behind the base's last. Returns host lists (delta_resources, patch_resources, changed, counts, statuses): the two
+    resource lists have the shape blocks_splice_extents takes -- blocks_splice_extents([new], delta_resources, block_size) is the delta
+    container, blocks_patch(base, delta, patch_resources, block_size) the new resources again."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    B = int(block_size)
+    pr = _diff_pairs(base, new, pairs)
+    n = len(pr)
+    new_lens = [int(x) for x in new[3]]
+    nbn = sum((new_lens[b] + B - 1) // B for _, b in pr if b < len(new_lens))
+    with_crc = base[4] is not None and new[4] is not None
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        srcs = []
+        for packed, first, off, lens, crc in (base, new):
+            lens = [int(x) for x in lens]
+            packed, d_packed = _dev_packed(packed, dev)
+            rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
+            srcs.append((d_packed, _dev_u64(first, len(lens) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(lens, 1, dev),
+                         _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(lens), rows))
+        dd = BlockDeduper.for_diff(ctx, B, n, nbn)
+        d_pair = _dev_u64(np.array(pr, dtype=np.uint64).reshape(-1), 2, dev)
+        d_df, d_pf = torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_de, d_pe = torch.zeros(max(1, 4 * nbn), dtype=torch.int64, device=dev), torch.zeros(max(1, 4 * nbn), dtype=torch.int64, device=dev)
+        d_ch, d_cnt = torch.zeros(max(1, n), dtype=torch.int64, device=dev), torch.zeros(4, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        dd.diff(srcs[0], srcs[1], d_pair, d_df, d_de, d_pf, d_pe, d_ch, d_cnt, d_st)
+        ctx.stream.synchronize()
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)
+        delta, patch = _extent_lists(u64(d_df), u64(d_de), n), _extent_lists(u64(d_pf), u64(d_pe), n)
+        changed, counts, st = [int(x) for x in u64(d_ch)[:n]], [int(x) for x in u64(d_cnt)], [int(x) for x in d_st.cpu().numpy()[:n]]
+        dd.close()
+    if own:
+        ctx.close()
+    return delta, patch, changed, counts, st
+
+
+def blocks_delta(base, new, block_size, pairs=None, ctx=None):
+    """The delta container of ``new`` against ``base`` -- per pair the changed blocks of the new resource, in order -- together with the
+    recipe that rebuilds the new resources from base + delta: blocks_diff, then blocks_splice_extents over [new]. Returns (delta,
+    patch_resources, changed, counts, statuses), delta = (packed, block_first, block_off, lengths, block_crc or None): a container as
+    blocks_patch and blocks_splice take one."""
+    own = ctx is None
+    ctx = ctx or Context()
+    delta_res, patch_res, changed, counts, st = blocks_diff(base, new, block_size, pairs=pairs, ctx=ctx)
+    with_crc = base[4] is not None and new[4] is not None
+    packed, first, off, lens, crc, _ = blocks_splice_extents([new if with_crc else tuple(new[:4]) + (None,)], delta_res, block_size, ctx=ctx)
+    if own:
+        ctx.close()
+    return (packed, first, off, lens, crc), patch_res, changed, counts, st
+
+
+def blocks_patch(base, delta, patch_resources, block_size, ctx=None):
+    """The new resources from ``base`` and the ``delta`` container and ``patch_resources`` of blocks_delta:
+    blocks_splice_extents([base, delta], patch_resources, block_size). Returns what blocks_splice returns."""
+    return blocks_splice_extents([base, delta], patch_resources, block_size, ctx=ctx)
 
 
 def blocks_dedup(containers, block_size, ctx=None):

@@ -567,10 +567,13 @@ MSCompStatus mscomp_amd_splicer_splice_extents(mscomp_amd_splicer* s, const msco
 struct mscomp_amd_deduper {
 	mscomp_amd_ctx* ctx = nullptr;
 	uint32_t shift = 0, n_src = 0, n_res = 0, nbt = 0;     // block_size = 1 << shift; the bounds n_res_total and n_blocks_total
+	bool diff = false;                                     // made by mscomp_amd_deduper_create_diff: n_res is n_pair, nbt is n_blocks_new, the scratch holds a DiffTab
 	mscomp_amd_plan run;
-	DevBuf tab;                                            // DedupTab
+	DevBuf tab;                                            // DedupTab, or DiffTab
 	DedupTab t{};
+	DiffTab f{};
 };
+static_assert(DF_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header states");
 
 // the columns of a deduper's tables from `base` on (n = n_res_total); returns where they end: from a null base, their bytes
 static uintptr_t dedup_tab(DedupTab& t, void* base, size_t n)
@@ -601,6 +604,32 @@ MSCompStatus mscomp_amd_deduper_create(mscomp_amd_ctx* c, uint32_t block_size, u
 	return MSCOMP_OK;
 }
 
+// the columns of a deduper made for diff from `base` on (n = n_pair, m = n_blocks_new); returns where they end: from a null base, their bytes
+static uintptr_t diff_tab(DiffTab& t, void* base, size_t n, size_t m)
+{
+	Carve k{reinterpret_cast<uintptr_t>(base)};
+	t.ufirst = k.q(n + 1); t.pfirst = k.q(3 * n); t.tsum = k.q(8 * (size_t)diff_row_tiles((uint32_t)m)); t.verdict = k.w(m);
+	return k.at;
+}
+
+MSCompStatus mscomp_amd_deduper_create_diff(mscomp_amd_ctx* c, uint32_t block_size, size_t n_pair, uint64_t n_blocks_new, uint32_t flags, mscomp_amd_deduper** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
+	if (!count_ok(n_pair) || !count_ok(n_blocks_new)) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
+	if (!d) { return MSCOMP_MEM_ERROR; }
+	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = 2; d->n_res = (uint32_t)n_pair; d->nbt = (uint32_t)n_blocks_new; d->diff = true;
+	d->run.ctx = c; d->run.n_units = 1;                    // (a call without pairs writes its counts: it replays too)
+	if (!d->tab.reserve(diff_tab(d->f, nullptr, n_pair, n_blocks_new) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	diff_tab(d->f, d->tab.p, n_pair, n_blocks_new);
+	*out = d.release();
+	return MSCOMP_OK;
+}
+
 void mscomp_amd_deduper_destroy(mscomp_amd_deduper* d)
 {
 	if (!d) { return; }
@@ -613,7 +642,7 @@ void mscomp_amd_deduper_destroy(mscomp_amd_deduper* d)
 MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* src, uint64_t* d_rep, uint64_t* d_new_index, uint64_t* d_pick,
                                       uint64_t* d_count, int32_t* d_status)
 {
-	if (!d || !src || !d_count) { return MSCOMP_ARG_ERROR; }
+	if (!d || d->diff || !src || !d_count) { return MSCOMP_ARG_ERROR; }
 	SpliceSrc k{};
 	uint64_t n = 0, rows = 0;                              // (at most four terms below 2^64 / 4 each once checked: no overflow)
 	bool with_crc = true;
@@ -643,6 +672,40 @@ MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* d, const mscomp_amd_bl
 		{ KernelTimer t(c, "dd_keys"); launch_dedup_keys(c->stream, k, N, d->n_res, d->nbt, with_crc, d->t, d_status, c->crc_blocks); }
 		{ KernelTimer t(c, "dd_confirm_kernel"); launch_dedup_confirm(c->stream, k, N, d->n_res, d->nbt, d->shift, with_crc, d->t, c->cpd_blocks); }
 		{ KernelTimer t(c, "dd_settle_kernel"); launch_dedup_settle(c->stream, k, N, d->n_res, with_crc, d->t, d_rep, d_new_index, d_pick, d_count); }
+	});
+}
+
+// Diff: the seed, the rows' verdicts from the tables, the compare that confirms the candidates, the three run passes tiled
+// over the new rows, the counts.
+MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* base, const mscomp_amd_blocks_view* next, const uint64_t* d_pair,
+                                     uint64_t* d_delta_ext_first, uint64_t* d_delta_ext, uint64_t* d_patch_ext_first, uint64_t* d_patch_ext, uint64_t* d_changed,
+                                     uint64_t* d_count, int32_t* d_status)
+{
+	if (!d || !d->diff || !base || !next || !d_count) { return MSCOMP_ARG_ERROR; }
+	if (d->n_res && (!d_pair || !d_delta_ext_first || !d_patch_ext_first || !d_changed || !d_status || (d->nbt && (!d_delta_ext || !d_patch_ext)))) { return MSCOMP_ARG_ERROR; }
+	const bool with_crc = base->d_block_crc && next->d_block_crc;
+	SpliceView v[2];
+	for (uint32_t i = 0; i < 2u; ++i) {
+		const mscomp_amd_blocks_view& s = i ? *next : *base;
+		if (s.n_res && (!s.d_block_first || !s.d_block_off || !s.d_res_len || (s.packed_len && !s.d_packed))) { return MSCOMP_ARG_ERROR; }
+		v[i] = { s.d_packed, s.packed_len, s.d_block_first, s.d_block_off, s.d_res_len, with_crc ? s.d_block_crc : nullptr, s.n_res, s.n_blocks_table };
+	}
+	mscomp_amd_ctx* c = d->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[24] = {};
+	memcpy(args, v, sizeof v);
+	const void* rest[8] = { d_pair, d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_changed, d_count, d_status };
+	memcpy(args + 16, rest, sizeof rest);
+	const uint32_t n = d->n_res, m = d->nbt;
+	return plan_run(&d->run, args, [&] {
+		{ KernelTimer t(c, "df_seed_kernel"); launch_diff_seed(c->stream, v[0], v[1], n, m, d->shift, d_pair, d->f, d_status); }
+		if (n && m) {
+			{ KernelTimer t(c, "df_verdict_kernel"); launch_diff_verdicts(c->stream, v[0], v[1], n, m, d->shift, with_crc, d_pair, d->f, d_status, c->crc_blocks); }
+			{ KernelTimer t(c, "df_confirm_kernel"); launch_diff_confirm(c->stream, v[0], v[1], n, m, d->shift, d_pair, d->f, d_status, c->cpd_blocks); }
+			{ KernelTimer t(c, "df_runs"); launch_diff_runs(c->stream, v[1], n, m, d_pair, d->f, d_status, d_delta_ext, d_patch_ext); }
+		}
+		{ KernelTimer t(c, "df_counts_kernel"); launch_diff_counts(c->stream, n, m, d->f, d_delta_ext_first, d_patch_ext_first, d_changed, d_count, c->crc_blocks); }
 	});
 }
 

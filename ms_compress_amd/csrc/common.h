@@ -324,6 +324,44 @@ __device__ __forceinline__ void cpd_move(uint8_t* __restrict__ dst, const uint8_
 	}
 }
 
+#define DD_PIECE_SHIFT 14u                                 // the confirm passes of dedup and diff compare in pieces of 16 KiB, as the raw copy and the gather move
+#define DD_SLICE_MIN   6u                                  // ... and a block takes six pieces at least: what it looks up per row is paid once per 96 KiB or less
+
+// Shared by dedup.hip and diff.hip. Whether the cnt bytes at a and at b differ, by NT threads (NT >= 128): the two sides have independent
+// alignment -- stored blocks are packed without padding --, so, as cpd_move moves them, a bytewise head up to a's next 16-byte boundary,
+// a body of 16-byte loads on a (16-byte loads on b too where it is aligned alike, loads of alignment 1 otherwise, four of either side in
+// flight per thread), a bytewise tail on the second wave. The answer is this thread's part: the caller folds it.
+template <uint32_t NT>
+__device__ __forceinline__ bool cpd_differs(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, u64 cnt, uint32_t tid)
+{
+	u64 head = (16u - ((uintptr_t)a & 15u)) & 15u;
+	if (head > cnt) { head = cnt; }
+	const u64 body = (cnt - head) >> 4, tail0 = head + body * 16u;
+	bool d = false;
+	if (tid < head) { d = a[tid] != b[tid]; }
+	if (tid >= 64u && tail0 + (tid - 64u) < cnt) { d = d || a[tail0 + (tid - 64u)] != b[tail0 + (tid - 64u)]; }
+	const bool same = (((uintptr_t)b + head) & 15u) == 0;
+	const uint4* __restrict__ pa = reinterpret_cast<const uint4*>(a + head);
+	const uint4* __restrict__ pb = reinterpret_cast<const uint4*>(b + head);
+	const cpd_u16* __restrict__ ub = reinterpret_cast<const cpd_u16*>(b + head);
+	for (u64 k0 = 0; k0 < body; k0 += 4u * NT) {
+		uint4 x[4], y[4];
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) {
+			const u64 k = k0 + j * NT + tid;
+			x[j] = y[j] = make_uint4(0, 0, 0, 0);
+			if (k < body) {
+				x[j] = pa[k];
+				if (same) { y[j] = pb[k]; }
+				else { const cpd_u16 t = ub[k]; y[j] = make_uint4(t.w[0], t.w[1], t.w[2], t.w[3]); }
+			}
+		}
+		#pragma unroll
+		for (uint32_t j = 0; j < 4u; ++j) { d = d || ((x[j].x ^ y[j].x) | (x[j].y ^ y[j].y) | (x[j].z ^ y[j].z) | (x[j].w ^ y[j].w)) != 0; }
+	}
+	return d;
+}
+
 // ---- shared by reader.hip and writer.hip: the action word of a unit, the piece of the byte-moving passes, and one wave's move ----
 #define RD_SKIP   0u                                      // not an owner (or no unit at all): nothing to decode, read or check
 #define RD_COPY   1u                                      // a raw block: read in d_packed

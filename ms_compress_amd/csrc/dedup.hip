@@ -7,8 +7,6 @@
 
 namespace msc {
 
-#define DD_PIECE_SHIFT 14u                                 // the confirm pass compares in pieces of 16 KiB, as the raw copy and the gather move
-#define DD_SLICE_MIN   6u                                  // ... and a block takes six pieces at least: what it looks up per row is paid once per 96 KiB or less
 
 // global resource g (< n0 + n1 + n2 + n3) as source and resource: the sources' resources are numbered back to back
 __device__ __forceinline__ void dd_locate(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, u64 g, u64& s, u64& r)
@@ -161,41 +159,6 @@ __global__ __launch_bounds__(256) void dd_cand_kernel(SpliceView v0, SpliceView 
 	}
 }
 
-// Whether the cnt bytes at a and at b differ, by NT threads (NT >= 128): the two sides have independent alignment -- stored blocks are
-// packed without padding --, so, as cpd_move moves them, a bytewise head up to a's next 16-byte boundary, a body of 16-byte loads on a
-// (16-byte loads on b too where it is aligned alike, loads of alignment 1 otherwise, four of either side in flight per thread), a bytewise
-// tail on the second wave. The answer is this thread's part: the caller folds it.
-template <uint32_t NT>
-__device__ __forceinline__ bool dd_differs(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, u64 cnt, uint32_t tid)
-{
-	u64 head = (16u - ((uintptr_t)a & 15u)) & 15u;
-	if (head > cnt) { head = cnt; }
-	const u64 body = (cnt - head) >> 4, tail0 = head + body * 16u;
-	bool d = false;
-	if (tid < head) { d = a[tid] != b[tid]; }
-	if (tid >= 64u && tail0 + (tid - 64u) < cnt) { d = d || a[tail0 + (tid - 64u)] != b[tail0 + (tid - 64u)]; }
-	const bool same = (((uintptr_t)b + head) & 15u) == 0;
-	const uint4* __restrict__ pa = reinterpret_cast<const uint4*>(a + head);
-	const uint4* __restrict__ pb = reinterpret_cast<const uint4*>(b + head);
-	const cpd_u16* __restrict__ ub = reinterpret_cast<const cpd_u16*>(b + head);
-	for (u64 k0 = 0; k0 < body; k0 += 4u * NT) {
-		uint4 x[4], y[4];
-		#pragma unroll
-		for (uint32_t j = 0; j < 4u; ++j) {
-			const u64 k = k0 + j * NT + tid;
-			x[j] = y[j] = make_uint4(0, 0, 0, 0);
-			if (k < body) {
-				x[j] = pa[k];
-				if (same) { y[j] = pb[k]; }
-				else { const cpd_u16 t = ub[k]; y[j] = make_uint4(t.w[0], t.w[1], t.w[2], t.w[3]); }
-			}
-		}
-		#pragma unroll
-		for (uint32_t j = 0; j < 4u; ++j) { d = d || ((x[j].x ^ y[j].x) | (x[j].y ^ y[j].y) | (x[j].z ^ y[j].z) | (x[j].w ^ y[j].w)) != 0; }
-	}
-	return d;
-}
-
 // Confirm: the (row, piece of 16 KiB) items of the same row numbering, cut into equal slices, one per block of a fixed grid; a block walks
 // the rows of its slice, and what it has to look up it looks up once per row (its resource once per resource). A row of an accepted
 // resource that is not its key's minimum is compared with the same row of the minimum: the stored lengths, the CRC words, then the
@@ -234,7 +197,7 @@ __global__ __launch_bounds__(CPD_THREADS) void dd_confirm_kernel(SpliceView v0, 
 			continue;
 		}
 		if (at >= len) { continue; }
-		if (dd_differs<CPD_THREADS>(v.packed + o0 + at, w.packed + c0 + at, (upto < len ? upto : len) - at, tid)) { flag[g] = 1u; }
+		if (cpd_differs<CPD_THREADS>(v.packed + o0 + at, w.packed + c0 + at, (upto < len ? upto : len) - at, tid)) { flag[g] = 1u; }
 	}
 }
 
@@ -255,7 +218,7 @@ __device__ bool dd_equal(const SpliceView& v0, const SpliceView& v1, const Splic
 	if (__syncthreads_or(d)) { return false; }
 	for (u64 k = 0; k < rows; ++k) {
 		const u64 o0 = v.off[f + k], len = v.off[f + k + 1u] - o0;
-		if (__syncthreads_or(dd_differs<DV_THREADS>(v.packed + o0, w.packed + w.off[fc + k], len, tid))) { return false; }
+		if (__syncthreads_or(cpd_differs<DV_THREADS>(v.packed + o0, w.packed + w.off[fc + k], len, tid))) { return false; }
 	}
 	return true;
 }

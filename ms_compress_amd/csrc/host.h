@@ -121,7 +121,7 @@ struct mscomp_amd_plan {
 	// the plan's launch sequence as a hipGraph (plan_run): captured on the plan's second execution, replayed while the
 	// arguments and the scratch buffers stay where they were
 	hipGraphExec_t gexec = nullptr;
-	const void* g_args[41] = {};                       // (api.hip: a host plan's four pointers, a dev plan's eight, a size dev plan's seven; blockobj.hip: a block container's eight and eleven; a block reader's twelve; a block writer's sixteen, and fourteen for its resize; a block splicer's forty: four views of eight words, and eight -- forty-one for its splice by extents; a block deduper's thirty-seven: the views, and five)
+	const void* g_args[41] = {};                       // (api.hip: a host plan's four pointers, a dev plan's eight, a size dev plan's seven; blockobj.hip: a block container's eight and eleven; a block reader's twelve; a block writer's sixteen, and fourteen for its resize; a block splicer's forty: four views of eight words, and eight -- forty-one for its splice by extents; a block deduper's thirty-seven: the views, and five -- twenty-four for its diff: two views, and eight)
 	uint64_t g_epoch = 0, g_mode = 0;
 	uint32_t executions = 0;
 	bool ran = false;                                  // executed at least once (mscomp_amd_debug_plan_paths: a dev plan's counts are those of its last execution)

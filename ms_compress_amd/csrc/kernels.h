@@ -399,6 +399,31 @@ void launch_dedup_confirm(hipStream_t st, const SpliceSrc& src, uint32_t n, uint
 // settle and emit (one block): rep, new_index (n each), pick (2 n_max, may be null when n is 0), count (4)
 void launch_dedup_settle(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, bool with_crc, const DedupTab& t, u64* rep, u64* new_index, u64* pick, u64* count);
 
+// mscomp_amd_deduper_diff, the deduper's second call (diff.hip): which blocks of the new resources differ from the blocks at the same
+// index of the base resources, answered as the delta and the patch extent lists. The scratch of a deduper made for it (blockobj.hip
+// diff_tab knows the layout); n = n_pair, m = n_blocks_new:
+#define DF_TILE DV_THREADS                             // rows per workgroup of the run passes (MSCOMP_AMD_SPLICE_ROW_TILE)
+inline uint32_t diff_row_tiles(uint32_t nbn) { return (nbn + DF_TILE - 1u) / DF_TILE; }
+struct DiffTab {
+	u64* ufirst;                                       // n + 1: first new row of every pair, in a numbering of the new rows of the pairs that passed rules 1-3
+	u64* pfirst;                                       // 3 n: the runs, changed runs and changed blocks in front of the pair's first row
+	u64* tsum;                                         // 8 diff_row_tiles(m): six sums and two maxima per tile of rows, then their running values
+	uint32_t* verdict;                                 // m: 1 = a changed block, 3 = one the confirm pass found
+};
+// The call in five stages, seven launches fixed by the creation bounds (two -- seed and counts -- when n_pair or n_blocks_new is 0; the
+// caller leaves the others out). seed (one block): rules 1-3, status (n_pair), t.ufirst
+void launch_diff_seed(hipStream_t st, const SpliceView& base, const SpliceView& next, uint32_t n_pair, uint32_t nbn, uint32_t shift, const u64* pair, const DiffTab& t, int32_t* status);
+// verdicts: the row checks of rule 2 and rule 5 without the bytes, a fixed grid over the new rows; `blocks` = crc_dev_blocks()
+void launch_diff_verdicts(hipStream_t st, const SpliceView& base, const SpliceView& next, uint32_t n_pair, uint32_t nbn, uint32_t shift, bool with_crc, const u64* pair,
+                          const DiffTab& t, int32_t* status, uint32_t blocks);
+// confirm: the byte compare, a fixed grid over (row, 16 KiB piece) items; `blocks` = compact_dev_blocks()
+void launch_diff_confirm(hipStream_t st, const SpliceView& base, const SpliceView& next, uint32_t n_pair, uint32_t nbn, uint32_t shift, const u64* pair, const DiffTab& t,
+                         const int32_t* status, uint32_t blocks);
+// runs (three launches: the tiles' sums, their running values in one block, the rows): delta_ext and patch_ext (4 n_blocks_new each), t.pfirst
+void launch_diff_runs(hipStream_t st, const SpliceView& next, uint32_t n_pair, uint32_t nbn, const u64* pair, const DiffTab& t, const int32_t* status, u64* delta_ext, u64* patch_ext);
+// counts: delta_first and patch_first (n_pair + 1, may be null when n_pair is 0), changed (n_pair), count (4)
+void launch_diff_counts(hipStream_t st, uint32_t n_pair, uint32_t nbn, const DiffTab& t, u64* delta_first, u64* patch_first, u64* changed, u64* count, uint32_t blocks);
+
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status
 // MSCOMP_ARG_ERROR), off[i] = its offset. in_off / off and status may be null.
