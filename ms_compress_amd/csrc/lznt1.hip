@@ -21,8 +21,10 @@
 //           position with a candidate that matched 16 bytes (and max_len > 16), the whole wave extends those candidates,
 //           256 bytes per step; when it lands on a position that still has unexamined candidates, the whole wave finishes
 //           that ONE position: 64 candidates per step (the lanes in front of the position's own entry; the step that holds it is the
-//           last), the same two stages, DPP max of (len, -position) = longest, oldest on ties, stop when
-//           max_len is reached. Positions covered by a match are never extended or finished;
+//           last), the same two stages. A step's candidates are younger than the best so far, and the older one wins on equal length, so
+//           only the lanes whose candidate is strictly longer than the best (and at least 3 bytes long) can change it: one compare and a
+//           ballot find them, and only a step that has such a lane reduces them, DPP max of (len, -position) = longest, oldest on ties
+//           (three steps of four have none). Stop when max_len is reached. Positions covered by a match are never extended or finished;
 //        3. tokens go straight to the chunk's scratch slot, placed by the closed form
 //           pos(t) = (t div 8 + 1) + sum size(u<t)   (mbcnt prefix popcounts); flag bits collect in a 16-entry LDS ring;
 //   D. header (0xB000|size-1), or the raw chunk (0x3000|n-1) when the running size reaches n; util.hip concatenates slots.
@@ -384,9 +386,17 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 						l2 = l2 >= 8u * LZ_S1 ? l3 : l2;
 						if (mL > 16u && l2 >= 128u && ((vmask >> lane) & (u64)1)) { const uint32_t l = lz_lcp_tail(s_data, qq, pL, maxL, it); l2 = (l < maxL ? l : maxL) << 3; }
 					}
-					uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(vmask));   // (a key below 3 << 12 is no match)
-					const uint32_t m = wave_max_u32(k2);
-					kbest = m > kbest ? m : kbest;                   // longest, then oldest (older blocks hold the larger 4095 - q)
+					// The step's candidates are younger than the best's, and the older one wins on equal length: only a candidate STRICTLY longer than the
+					// best (and at least 3 bytes long: a best below 3 is "no match" downstream, which sub-3 key it holds is never read) can change kbest.
+					// One compare and a ballot find those lanes, the winners; in three steps of four there are none and nothing is reduced
+					// (tools/dev/lz_best_study.c). (kbest >> 12) < maxL here, so need <= 8 maxL: a candidate that reached max_len always wins.
+					uint32_t need = (kbest >> 12) + 1u; need = (need > 3u ? need : 3u) << 3;    // in bits, on the scalar unit
+					const u64 win = __builtin_amdgcn_ballot_w64(l2 >= need) & vmask;
+					if (win) {
+						// longest, then oldest (older entries hold the larger 4095 - q); every winner's key is above the old kbest
+						uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(win));
+						kbest = wave_max_u32(k2);
+					}
 #ifdef LZ4_PROFILE_EVENTS
 					++nsteps; ntail += wave_max_u32(it);
 #endif
@@ -653,8 +663,8 @@ extern "C" void mscomp_amd_debug_lz4_prof(unsigned long long* out) { (void)hipMe
 static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: LZNT1_REC = two areas of 64 windows of match tokens");
 // (The kernel must stay at or below 96 scalar registers, of which it uses 93: the hardware hands them out in sixteens, 800 per SIMD, so the 97th
 // costs every CU its eighth block, while the compiler's own occupancy figure still says 8 up to 100. Round 13 in profiles/HISTORY.md: builds of this parse
-// at 98 and 100 ran 5.8 waves per CU-cycle instead of 6.8 and lost 5 to 7 % of the headline. Nothing guards it but the A/B run of a change: an
-// `amdgpu_num_sgpr` limit makes the compiler spill, which tests/test_lznt1_resources.py forbids.)
+// at 98 and 100 ran 5.8 waves per CU-cycle instead of 6.8 and lost 5 to 7 % of the headline. tests/test_lznt1_sgpr_budget.py reads the count of all
+// four instances; an `amdgpu_num_sgpr` limit is no way out: it makes the compiler spill, which tests/test_lznt1_resources.py forbids.)
 template <bool serial, bool DEV = false>                         // DEV: as lznt1_chunk_kernel
 __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                           uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size, uint16_t* __restrict__ recs)
