@@ -968,6 +968,88 @@ MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* dd,
                                      uint64_t* d_count                 /* 4 */,
                                      int32_t*  d_status                /* n_pair */);
 
+/* Block transcoders: a container brought to another block size, another codec, or both. Every call that combines containers -- splice,
+ * splice by extents, dedup, diff, delta, patch -- asks for one format and one block size; a transcoder is what gets a container there.
+ * It is out of place, like a writer: it reads a container of format F1 cut at B1 and writes a NEW one of format F2 cut at B2. Resource
+ * lengths do not change, and neither does any resource CRC-32 (mscomp_amd_res_crc_dev gives the same values for both containers).
+ * Between two LZNT1 containers most blocks are CARRIED -- their stored bytes move as they lie, nothing is decoded or encoded --, because
+ * an LZNT1 stream is the plain concatenation of its 4 KiB chunks' images and each image depends on that chunk's bytes alone.
+ *   Creation:     (ctx, F1, B1, F2, B2, n_res, n_blocks_table, n_blocks_new, groups_max, flags = 0). The checks of the other block objects
+ *                 for either (format, block size) pair and for the four counts (at most 0x7FFFFFF0), in the same order, before the
+ *                 context is used: MSCOMP_ARG_ERROR, also for F1 = F2 with B1 = B2 (nothing to change: that is a splice);
+ *                 MSCOMP_MEM_ERROR where groups_max G bytes are more than a dev plan can address. *tc is cleared on failure. A GROUP is
+ *                 an aligned span of G = max(B1, B2) bytes of a resource: on a join (B2 > B1) one new block with its G / B1 source
+ *                 members, on a split one source block with its G / B2 new blocks, with equal sizes one block of each. All scratch is
+ *                 reserved here, once, and never grows: a cache and a staging area of groups_max G bytes each, a decompress dev plan for
+ *                 F1 (groups_max G / B1 units) and a compress dev plan for F2 (groups_max G / B2 units) within groups_max G bytes each,
+ *                 and the transcoder's tables: 92 bytes per decode unit, 72 per encode unit, 4 per group of groups_max, 12 per entry of
+ *                 the coarser block table, 48 per entry of the new block table + 8 per MSCOMP_AMD_SPLICE_ROW_TILE of them, and 20 per
+ *                 resource + 48. The LZNT1 dictionary flavour is fixed here, as for mscomp_amd_writer_create.
+ *   Contract:     for a source written by mscomp_amd_blocks_compress with the same dictionary flavour whose blocks are healthy, the new
+ *                 container is byte for byte -- packed bytes, d_new_block_first, d_new_block_off and, with checksums, d_new_block_crc of
+ *                 every accepted resource -- what mscomp_amd_blocks_compress(F2, data, B2) and mscomp_amd_blocks_crc write for the data.
+ *   Rules:        per resource, in this order, each leaving the other resources alone (L = d_res_len[r]):
+ *                   0. the table as a whole, as the writer's rule 0: d_block_first[n_res] must not exceed n_blocks_table and
+ *                      d_block_first must not decrease anywhere. Otherwise every resource gets MSCOMP_ARG_ERROR, the new tables are all
+ *                      0, and nothing else is written;
+ *                   1. MSCOMP_DATA_ERROR: d_block_first[r + 1] - d_block_first[r] is not ceil(L / B1);
+ *                   2. MSCOMP_ARG_ERROR: the running total of ceil(L / B2) over ALL resources up to and including this one exceeds
+ *                      n_blocks_new;
+ *                   3. classes. A source block with stored length s and data length e is compressed-stored when 0 < s < e and raw-stored
+ *                      when s = e; any other entry (a decreasing table, an end beyond packed_len included) makes its resource
+ *                      MSCOMP_DATA_ERROR, unread.
+ *                      F1 = F2 = LZNT1, join: a new block whose members are all compressed-stored is carried: its stored bytes are the
+ *                      members', which lie adjacent. Any other new block is WORKED: its compressed-stored members are decoded into the
+ *                      cache, its raw-stored members are copied there, and it is encoded from the cache under the rule of
+ *                      mscomp_amd_blocks_compress (the counted bytes when shorter than the data, the raw block otherwise).
+ *                      F1 = F2 = LZNT1, split, raw-stored source block: every new block of it is encoded from the bytes where they lie.
+ *                      F1 = F2 = LZNT1, split, compressed-stored source block: its chunk headers are walked -- a little-endian uint16 h,
+ *                      image length (h & 0x0FFF) + 3. The images must tile the s stored bytes into exactly ceil(e / 4096) chunks, and
+ *                      no byte at or behind s is read; otherwise MSCOMP_DATA_ERROR. A new block whose chunks' images sum to less than
+ *                      its data length is carried as those images. When any new block of the source block is not carried, the source
+ *                      block is decoded once and those new blocks are stored raw from the decoded bytes; nothing is encoded.
+ *                      Every other pair of formats and sizes: every compressed-stored source block is decoded, every raw-stored one
+ *                      copied (read in place when its group has one source block), and every new block is encoded.
+ *                      Checksums: on a join a carried block's CRC-32 is its members' folded by x^(8 d), as mscomp_amd_res_crc_dev folds
+ *                      them; no data is read. Every DECODED source block is held to its old CRC-32 (MSCOMP_DATA_ERROR on a mismatch);
+ *                      a worked block's new CRC-32 is computed from its data. On a split with checksums every compressed-stored source
+ *                      block is decoded (its group is worked), held to its CRC-32, and the new blocks' CRC-32s are computed from the
+ *                      decoded bytes; raw-stored source blocks are read in place. Carrying still happens: only the decode is added.
+ *                      What carrying trusts: a carried block is not verified beyond the table checks and the header walk, exactly as
+ *                      splice carries bytes: damage inside it is carried along. And a carried block is only valid at its new size when
+ *                      every chunk but a resource's last holds 4096 bytes, as every LZNT1 stream of this library does;
+ *                   4. the budget: a group is worked when anything in it is decoded or encoded. The running total of worked groups
+ *                      over the resources that passed rules 1-3, up to and including this one, must not exceed groups_max; otherwise
+ *                      MSCOMP_ARG_ERROR (the reader's rule 5). groups_max = the group count of the whole container never refuses;
+ *                   5. verdicts before bytes: a source block that does not decode exactly as ms_decompress with capacity e to e bytes,
+ *                      or not to its checksum, makes its resource MSCOMP_DATA_ERROR. A resource that failed any rule has NO blocks in
+ *                      the new container, as a resource mscomp_amd_blocks_compress rejects: d_new_block_first[r + 1] =
+ *                      d_new_block_first[r]. d_new_block_off is the exclusive running sum of the new stored lengths, the entries above
+ *                      the count repeat the total; d_new_block_crc is 0 at and above the count;
+ *                   6. capacity, the rule of mscomp_amd_blocks_compress: a block that would end beyond new_cap is not written and its
+ *                      resource gets MSCOMP_BUF_ERROR; the tables still hold the full layout.
+ *   Counts:       mscomp_amd_transcoder_counts gives, for the last execution, out[0] = new blocks carried (of the accepted resources),
+ *                 out[1] = source blocks decoded, out[2] = new blocks encoded (both of the resources that passed rule 4); all 0 after
+ *                 a refused table. It synchronises the ctx stream; returns 0, or -1 for a null argument or a failed read.
+ *   Execution:    as the writer's: asynchronous on the ctx stream, kernels only, no allocation, no synchronisation, nothing read back, a
+ *                 launch sequence fixed by the creation bounds; legal inside a caller's capture from the first execution, a graph of its
+ *                 own from the second, captured again when an argument changes. d_new_block_first: n_res + 1, d_new_block_off:
+ *                 n_blocks_new + 1, d_status: n_res; the new arrays must not overlap the old ones. MSCOMP_ARG_ERROR for a null tc or a
+ *                 null required array (d_packed may be null when n_blocks_table is 0, d_new_packed when n_blocks_new is 0, d_res_len and
+ *                 d_status when n_res is 0), or when exactly one of d_block_crc and d_new_block_crc is null. */
+typedef struct mscomp_amd_transcoder mscomp_amd_transcoder;
+MSCompStatus mscomp_amd_transcoder_create(mscomp_amd_ctx* ctx, MSCompFormat format, uint32_t block_size, MSCompFormat new_format,
+                                          uint32_t new_block_size, size_t n_res, uint64_t n_blocks_table, uint64_t n_blocks_new,
+                                          uint64_t groups_max, uint32_t flags, mscomp_amd_transcoder** tc);
+void         mscomp_amd_transcoder_destroy(mscomp_amd_transcoder* tc);
+MSCompStatus mscomp_amd_transcoder_transcode(mscomp_amd_transcoder* tc, const uint8_t* d_packed, uint64_t packed_len,
+                                             const uint64_t* d_block_first, const uint64_t* d_block_off, const uint64_t* d_res_len,
+                                             const uint32_t* d_block_crc /* may be NULL */,
+                                             uint8_t* d_new_packed, uint64_t new_cap, uint64_t* d_new_block_first /* n_res + 1 */,
+                                             uint64_t* d_new_block_off /* n_blocks_new + 1 */,
+                                             uint32_t* d_new_block_crc /* NULL exactly when d_block_crc is */, int32_t* d_status /* n_res */);
+int          mscomp_amd_transcoder_counts(mscomp_amd_transcoder* tc, uint32_t out[3]);
+
 /* Resource checksums from block checksums. After a write or a resize the block CRC-32s are current and the resource CRC-32s that
  * mscomp_amd_blocks_crc once wrote are stale; the block checksums determine them, and no data has to be read:
  *   d_res_crc[r] = XOR over the resource's blocks j of d_block_crc[j] x^(8 d_j)  (mod the CRC polynomial), d_j = the resource's bytes behind block j

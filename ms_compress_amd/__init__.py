@@ -17,4 +17,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   BlockSplicer, BlocksView, blocks_splice, MSCOMP_AMD_SPLICE_SRC_MAX, MSCOMP_AMD_SPLICE_ROW_TILE,
                   blocks_splice_extents, blocks_concat, blocks_split_at, blocks_cut_range,
                   BlockDeduper, blocks_dedup,
+                  BlockTranscoder, blocks_transcode,
                   blocks_diff, blocks_delta, blocks_patch, MSCOMP_AMD_DIFF_NO_BASE)

@@ -49,6 +49,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_splicer_create_extents", "mscomp_amd_splicer_splice_extents",
     "mscomp_amd_deduper_create", "mscomp_amd_deduper_destroy", "mscomp_amd_deduper_dedup",
     "mscomp_amd_deduper_create_diff", "mscomp_amd_deduper_diff",
+    "mscomp_amd_transcoder_create", "mscomp_amd_transcoder_destroy", "mscomp_amd_transcoder_transcode", "mscomp_amd_transcoder_counts",
     "mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report",
 ]
 MSCOMP_AMD_SPLICE_SRC_MAX = 4
@@ -213,6 +214,15 @@ def load_library():
     lib.mscomp_amd_deduper_create_diff.restype = C.c_int
     lib.mscomp_amd_deduper_diff.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.POINTER(BlocksView)] + [C.c_void_p] * 8
     lib.mscomp_amd_deduper_diff.restype = C.c_int
+    lib.mscomp_amd_transcoder_create.restype = C.c_int
+    lib.mscomp_amd_transcoder_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                 C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_transcoder_destroy.restype = None
+    lib.mscomp_amd_transcoder_destroy.argtypes = [C.c_void_p]
+    lib.mscomp_amd_transcoder_transcode.restype = C.c_int
+    lib.mscomp_amd_transcoder_transcode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_uint64] + [C.c_void_p] * 4
+    lib.mscomp_amd_transcoder_counts.restype = C.c_int
+    lib.mscomp_amd_transcoder_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1244,6 +1254,92 @@ def blocks_dedup(containers, block_size, ctx=None):
     if own:
         ctx.close()
     return [int(x) for x in rep], [int(x) for x in idx], [(int(s), int(r)) for s, r in picks], counts, [int(x) for x in st]
+
+
+class BlockTranscoder(_Handle):
+    """A block transcoder (mscomp_amd_transcoder_create): a container of format ``fmt`` cut at ``block_size`` written again as format
+    ``new_fmt`` cut at ``new_block_size``, out of place. Made once for the tables of a container of ``n_res`` resources whose d_block_off
+    has ``n_blocks_table`` + 1 entries, a new table of ``n_blocks_new`` rows and at most ``groups_max`` worked groups per call (a group: an
+    aligned span of max(block_size, new_block_size) bytes of a resource in which anything is decoded or encoded). Between two LZNT1
+    containers most blocks are carried: their stored bytes move as they lie. All scratch is reserved here: a cache and a staging area of
+    groups_max groups each, two inner dev plans and the tables. transcode() enqueues kernels on the ctx stream and nothing else (legal
+    inside a capture of that stream). Arguments are torch CUDA tensors: uint8 data, int64 / uint64 tables, int32 statuses and checksums."""
+    _destroy = "mscomp_amd_transcoder_destroy"
+
+    def __init__(self, ctx, fmt, block_size, new_fmt, new_block_size, n_res, n_blocks_table, n_blocks_new, groups_max):
+        _Handle.__init__(self, ctx)
+        self.fmt, self.block_size, self.new_fmt, self.new_block_size = int(fmt), int(block_size), int(new_fmt), int(new_block_size)
+        self.n_res, self.n_blocks_table, self.n_blocks_new, self.groups_max = int(n_res), int(n_blocks_table), int(n_blocks_new), int(groups_max)
+        _ok(ctx.lib.mscomp_amd_transcoder_create(ctx._h, self.fmt, self.block_size, self.new_fmt, self.new_block_size, self.n_res, self.n_blocks_table,
+                                                 self.n_blocks_new, self.groups_max, 0, C.byref(self._h)), "mscomp_amd_transcoder_create")
+
+    def transcode(self, d_packed, d_block_first, d_block_off, d_res_len, d_new_packed, d_new_block_first, d_new_block_off, d_status, d_block_crc=None,
+                  d_new_block_crc=None, packed_len=None, new_cap=None):
+        """The old container (d_packed, d_block_first, d_block_off, d_res_len, d_block_crc) is only read; the new one is written to
+        d_new_packed (nothing at or behind ``new_cap``, default: all of it), d_new_block_first (n_res + 1), d_new_block_off
+        (n_blocks_new + 1) and d_new_block_crc (given exactly when d_block_crc is). d_status[r] is MSCOMP_OK, MSCOMP_DATA_ERROR (a wrong
+        block count, a broken table entry or chunk header, a block that does not decode or not to its checksum), MSCOMP_ARG_ERROR (no room
+        in the new table, or over the budget of groups_max) with resource r left without blocks, or MSCOMP_BUF_ERROR (a block did not fit
+        below new_cap)."""
+        plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
+        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
+        if d_new_packed is not None and cap > d_new_packed.numel():
+            raise ValueError("new_cap exceeds d_new_packed")
+        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_new_packed, d_new_block_first, d_new_block_off, d_new_block_crc, d_status)
+        _ok(self.ctx.lib.mscomp_amd_transcoder_transcode(self._h, p[0], plen, *p[1:6], cap, *p[6:]), "mscomp_amd_transcoder_transcode")
+
+    def counts(self):
+        """(new blocks carried, source blocks decoded, new blocks encoded) of the last transcode(); synchronizes the stream."""
+        out = (C.c_uint32 * 3)()
+        if self.ctx.lib.mscomp_amd_transcoder_counts(self._h, out) != 0:
+            raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_transcoder_counts")
+        return (int(out[0]), int(out[1]), int(out[2]))
+
+
+def blocks_transcode(container, block_size, new_block_size, new_fmt=None, ctx=None, groups_max=None, n_blocks_new=None, new_cap=None):
+    """Bring a block container to another block size and / or codec on the GPU (BlockTranscoder). ``container`` is (fmt, packed,
+    block_first, block_off, lengths, block_crc or None) as blocks_compress and blocks_crc return them; ``new_fmt`` defaults to fmt. The new
+    container gets checksums exactly when the old one has them. ``groups_max`` (default: every group of the container), ``n_blocks_new``
+    (default: what the lengths need) and ``new_cap`` (default: the sum of the lengths) are the transcoder's bounds. Returns numpy arrays
+    and lists (new_packed uint8, new_block_first uint64 of n + 1, new_block_off uint64, new_block_crc uint32 or None, statuses, counts)."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    fmt, packed, block_first, block_off, lengths, block_crc = container
+    new_fmt = fmt if new_fmt is None else new_fmt
+    lens = [int(x) for x in lengths]
+    n = len(lens)
+    B1, B2 = int(block_size), int(new_block_size)
+    G = max(B1, B2)
+    nbt = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
+    nbn = sum((x + B2 - 1) // B2 for x in lens) if n_blocks_new is None else int(n_blocks_new)
+    gmax = sum((x + G - 1) // G for x in lens) if groups_max is None else int(groups_max)
+    room = int(sum(lens)) if new_cap is None else int(new_cap)
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        tc = BlockTranscoder(ctx, fmt, B1, new_fmt, B2, n, nbt, nbn, gmax)
+        packed, d_packed = _dev_packed(packed, dev)
+        d_first, d_boff, d_len = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, nbt + 1, dev), _dev_u64(lens, 1, dev)
+        d_crc = d_ncrc = None
+        if block_crc is not None:
+            d_crc, d_ncrc = _dev_block_crc(block_crc, nbt, dev), torch.zeros(max(1, nbn), dtype=torch.int32, device=dev)
+        d_new = torch.zeros(room + 16, dtype=torch.uint8, device=dev)
+        d_nfirst = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_noff = torch.zeros(nbn + 1, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        tc.transcode(d_packed, d_first, d_boff, d_len, d_new, d_nfirst, d_noff, d_st, d_block_crc=d_crc, d_new_block_crc=d_ncrc,
+                     packed_len=len(packed), new_cap=room)
+        counts = tc.counts()
+        nfirst = d_nfirst.cpu().numpy().view(np.uint64).copy()
+        nb = int(nfirst[n])
+        noff = d_noff.cpu().numpy().view(np.uint64)[: nb + 1].copy()
+        new_packed = d_new.cpu().numpy()[: min(int(noff[nb]), room)].copy()
+        ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nb].copy()
+        h_st = d_st.cpu().numpy()
+        tc.close()
+    if own:
+        ctx.close()
+    return new_packed, nfirst, noff, ncrc, [int(x) for x in h_st[:n]], counts
 
 
 def res_crc_from_blocks(block_first, lengths, block_crc, block_size, ctx=None):

@@ -709,6 +709,144 @@ MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* d, const mscomp_amd_blo
 	});
 }
 
+// ---- block transcoders (include/mscomp_amd.h; kernels: transcode.hip, the fold in crc32.hip, the move in blocks.hip) ----
+// A transcoder holds what a writer holds -- a decompress dev plan for the old format, a compress dev plan for the new one, a cache and a
+// staging area -- sized by groups_max groups of G = max(B1, B2) bytes, its tables, and the graph of its call. Slot w of cache and staging
+// belongs to the w-th worked group of an execution; a unit's place in it follows from its block's place in the group, so neither inner
+// plan's tables are compacted.
+struct mscomp_amd_transcoder {
+	mscomp_amd_ctx* ctx = nullptr;
+	MSCompFormat f1 = MSCOMP_NONE, f2 = MSCOMP_NONE;
+	TcDims d{};
+	uint32_t dm = 0, em = 0;                           // the units of the inner plans: groups_max G / B1, groups_max G / B2
+	mscomp_amd_plan* dplan = nullptr; mscomp_amd_plan* cplan = nullptr;   // (null when groups_max is 0)
+	mscomp_amd_plan run;
+	DevBuf tab, cache, stage;                          // TranscodeTab; groups_max slots of G bytes each
+	TranscodeTab t{};
+	bool ran = false;
+};
+
+// the columns of a transcoder's tables from `base` on; returns where they end: from a null base, their bytes
+static uintptr_t transcode_tab(TranscodeTab& t, void* base, const TcDims& d, size_t dm, size_t em)
+{
+	const size_t n = d.n_res, ng = d.ngmax, m = d.nbn;
+	Carve k{reinterpret_cast<uintptr_t>(base)};
+	t.gfirst = k.q(n + 1); t.pfirst = k.q(n + 1);
+	t.plen = k.q(m); t.paddr = k.q(m); t.pjf = k.q(m); t.pdl = k.q(m); t.addr = k.q(m); t.tsum = k.q(splice_row_tiles((uint32_t)m));
+	t.d_in_off = k.q(dm); t.d_in_len = k.q(dm); t.d_out_off = k.q(dm); t.d_out_cap = k.q(dm); t.d_ulen = k.q(dm);
+	t.d_src = k.q(dm); t.d_clen = k.q(dm); t.d_cum = k.q(dm + 1); t.d_row = k.q(dm); t.d_raw = k.q(dm);
+	t.e_in_off = k.q(em); t.e_in_len = k.q(em); t.e_out_off = k.q(em); t.e_out_cap = k.q(em); t.e_ulen = k.q(em);
+	t.e_src = k.q(em); t.e_clen = k.q(em); t.e_cum = k.q(em + 1);
+	t.rstat = k.i(n); t.gres = k.w(ng); t.gwork = k.w(ng); t.gcum = k.w(ng); t.slot_group = k.w(d.gmax);
+	t.pkind = k.w(m); t.pcrc = k.w(m);
+	t.d_ustat = k.i(dm); t.d_act = k.w(dm); t.d_crc = k.w(dm); t.e_ustat = k.i(em); t.e_crc = k.w(em);
+	t.cnt = k.w(4);
+	return k.at;
+}
+
+MSCompStatus mscomp_amd_transcoder_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, MSCompFormat new_format, uint32_t new_block_size, size_t n_res,
+                                          uint64_t n_blocks_table, uint64_t n_blocks_new, uint64_t groups_max, uint32_t flags, mscomp_amd_transcoder** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!create_args_ok(c, format, block_size, flags) || !create_args_ok(c, new_format, new_block_size, flags)) { return MSCOMP_ARG_ERROR; }
+	if (!count_ok(n_res) || !count_ok(n_blocks_table) || !count_ok(n_blocks_new) || !count_ok(groups_max)) { return MSCOMP_ARG_ERROR; }
+	if (format == new_format && block_size == new_block_size) { return MSCOMP_ARG_ERROR; }   // (nothing to change: a splice)
+	TcDims d{};
+	d.n_res = (uint32_t)n_res; d.nbt = (uint32_t)n_blocks_table; d.nbn = (uint32_t)n_blocks_new; d.gmax = (uint32_t)groups_max;
+	d.s1 = (uint32_t)__builtin_ctz(block_size); d.s2 = (uint32_t)__builtin_ctz(new_block_size); d.sg = d.s1 > d.s2 ? d.s1 : d.s2;
+	d.ngmax = d.s2 > d.s1 ? d.nbn : d.nbt;                 // a group holds at least one block of the coarser table
+	d.mode = format != MSCOMP_LZNT1 || new_format != MSCOMP_LZNT1 ? TC_GENERIC : d.s2 > d.s1 ? TC_JOIN : TC_SPLIT;
+	const uint64_t dm = groups_max << (d.sg - d.s1), em = groups_max << (d.sg - d.s2), bytes = groups_max << d.sg;   // (< 2^50)
+	uint64_t I = 0, chunks = 0, toks = 0, cands = 0;
+	if (!count_ok(dm) || !count_ok(em) || !decode_dev_counts(format, dm, bytes, bytes, false, I, chunks, toks, cands)) { return MSCOMP_MEM_ERROR; }   // (what the inner plans would refuse: checked before the context is used)
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_transcoder> x(new (std::nothrow) mscomp_amd_transcoder());
+	if (!x) { return MSCOMP_MEM_ERROR; }
+	x->ctx = c; x->f1 = format; x->f2 = new_format; x->d = d; x->dm = (uint32_t)dm; x->em = (uint32_t)em;
+	x->run.ctx = c; x->run.n_units = 1;                    // (a call without resources writes an empty container: it replays too)
+	MSCompStatus st = MSCOMP_OK;
+	if (!x->tab.reserve(transcode_tab(x->t, nullptr, d, dm, em) + 64) || (bytes && (!x->cache.reserve(bytes + 64) || !x->stage.reserve(bytes + 64)))) { st = MSCOMP_MEM_ERROR; }
+	if (st == MSCOMP_OK && dm) { st = mscomp_amd_plan_create_decompress_dev(c, format, dm, bytes, bytes, &x->dplan); }
+	if (st == MSCOMP_OK && em) { st = mscomp_amd_plan_create_compress_dev(c, new_format, em, bytes, new_block_size, &x->cplan); }   // (fixes the LZNT1 dictionary flavour)
+	if (st != MSCOMP_OK) { (void)hipGetLastError(); mscomp_amd_transcoder_destroy(x.release()); return st; }
+	transcode_tab(x->t, x->tab.p, d, dm, em);
+	*out = x.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_transcoder_destroy(mscomp_amd_transcoder* x)
+{
+	if (!x) { return; }
+	DeviceGuard g(x->ctx->device);
+	(void)hipStreamSynchronize(x->ctx->stream);
+	mscomp_amd_plan_destroy(x->dplan); mscomp_amd_plan_destroy(x->cplan);
+	x->tab.release(); x->cache.release(); x->stage.release();
+	delete x;                                              // (run gives up its graph)
+}
+
+// The call: rules 0-3 from the tables, the slots and both inner plans' units, the writer's decode-into-cache /
+// encode-into-staging sequence over them with the CRC passes, the new tables tiled over their rows, the move.
+MSCompStatus mscomp_amd_transcoder_transcode(mscomp_amd_transcoder* x, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
+                                             const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc,
+                                             uint8_t* d_new_packed, uint64_t new_cap, uint64_t* d_new_block_first, uint64_t* d_new_block_off,
+                                             uint32_t* d_new_block_crc, int32_t* d_status)
+{
+	if (!x || !d_block_first || !d_block_off || !d_new_block_first || !d_new_block_off || (x->d.n_res && (!d_res_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if ((x->d.nbt && !d_packed) || (x->d.nbn && !d_new_packed)) { return MSCOMP_ARG_ERROR; }
+	if ((d_block_crc == nullptr) != (d_new_block_crc == nullptr)) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = x->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	if (x->dplan) { note_modes(x->dplan); x->dplan->ran = true; }
+	if (x->cplan) { x->cplan->ran = true; }
+	x->ran = true;
+	const void* args[12] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_new_packed,
+	                         reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc, d_status };
+	return plan_run(&x->run, args, [&] {
+		const TcDims& d = x->d;
+		const TranscodeTab& t = x->t;
+		const bool with_crc = d_block_crc != nullptr;
+		uint8_t* cache = static_cast<uint8_t*>(x->cache.p); uint8_t* stage = static_cast<uint8_t*>(x->stage.p);
+		{ KernelTimer k(c, "tc_res_kernel"); launch_tc_resources(c->stream, d, d_block_first, d_res_len, t); }
+		{ KernelTimer k(c, "tc_class_kernel"); launch_tc_classes(c->stream, d, d_packed, packed_len, d_block_first, d_block_off, d_res_len, with_crc, t); }
+		{ KernelTimer k(c, "tc_units"); launch_tc_units(c->stream, d, d_packed, cache, d_block_first, d_block_off, d_res_len, with_crc, t); }
+		// the worked groups: decoded (or copied) into the cache, held to their old checksums, encoded into the staging area, checksummed
+		if (x->dplan) { dev_launch(x->dplan, d_packed, t.d_in_off, t.d_in_len, cache, t.d_out_off, t.d_out_cap, t.d_ulen, t.d_ustat); }
+		{ KernelTimer k(c, "tc_gather_kernel"); launch_tc_gather(c->stream, d, cache, t, c->cpd_blocks); }
+		if (with_crc && x->dm) { crc_pass(c, x->dm, nullptr, t.d_src, t.d_clen, t.d_cum, t.d_crc); }   // (addresses as offsets from a null base)
+		{ KernelTimer k(c, "tc_judge_kernel"); launch_tc_judge(c->stream, d, d_block_crc, t); }
+		if (x->cplan) { dev_launch(x->cplan, nullptr, t.e_in_off, t.e_in_len, stage, t.e_out_off, t.e_out_cap, t.e_ulen, t.e_ustat); }
+		if (with_crc && x->em) { crc_pass(c, x->em, nullptr, t.e_src, t.e_clen, t.e_cum, t.e_crc); }
+		if (with_crc && d.mode == TC_JOIN) { KernelTimer k(c, "crc_foldruns_kernel"); launch_crc_fold_runs(c->stream, d.nbn, t.pfirst + d.n_res, d.s1, t.pjf, t.pdl, d_block_crc, t.pcrc); }
+		// the new tables and the bytes
+		{ KernelTimer k(c, "tc_first_kernel"); launch_tc_first(c->stream, d, d_res_len, t, d_new_block_first, d_new_block_off, d_status); }
+		if (d.nbn) {
+			const SpliceExtTab rows = { t.addr, nullptr, t.tsum, t.cnt + 3 };
+			{ KernelTimer k(c, "tc_tile_kernel"); launch_tc_tiles(c->stream, d, stage, d_res_len, with_crc, t, d_new_block_first, d_new_block_off, d_new_block_crc); }
+			{ KernelTimer k(c, "sx_tilescan_kernel"); launch_splice_tilescan(c->stream, d.nbn, rows); }
+			{ KernelTimer k(c, "tc_rows_kernel"); launch_tc_rows(c->stream, d, new_cap, t, d_new_block_first, d_new_block_off, d_new_block_crc, d_status); }
+		}
+		{ KernelTimer k(c, "bk_move_kernel"); launch_blocks_move(c->stream, d.nbn, new_cap, d_new_block_off, t.addr, d_new_packed, c->cpd_blocks); }
+	});
+}
+
+// new blocks carried, source blocks decoded and new blocks encoded by x's last execution (read back; none before the first, none for a
+// refused table)
+int mscomp_amd_transcoder_counts(mscomp_amd_transcoder* x, uint32_t out[3])
+{
+	if (!x || !out) { return -1; }
+	DeviceGuard g(x->ctx->device);
+	if (!g.ok || hipStreamSynchronize(x->ctx->stream) != hipSuccess) { return -1; }
+	out[0] = out[1] = out[2] = 0;
+	if (!x->ran) { return 0; }
+	uint32_t cnt[4] = {};
+	if (hipMemcpy(cnt, x->t.cnt, 16, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (cnt[3] == 0) { out[0] = cnt[0]; out[1] = cnt[1]; out[2] = cnt[2]; }
+	return 0;
+}
+
 // ---- the scratch hooks' view of the objects above (api.hip: mscomp_amd_debug_scratch_*) ----
 extern "C++" mscomp_amd_ctx* msc::scratch_of_object(int kind, void* obj, std::vector<ScratchEnt>& v)
 {

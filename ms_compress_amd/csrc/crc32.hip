@@ -257,6 +257,26 @@ __global__ __launch_bounds__(256) void rcrc_fold_kernel(uint32_t n_res, uint32_t
 	}
 }
 
+// The fold along runs of a table (kernels.h launch_crc_fold_runs), one thread per row: crc(A || B) = crc(A) x^(8 |B|) ^ crc(B), applied
+// piece by piece from the front -- every step but the last one by the same factor x^(8 B).
+__global__ __launch_bounds__(256) void crc_foldruns_kernel(uint32_t n, const u64* __restrict__ n_live, uint32_t shift, const u64* __restrict__ first, const u64* __restrict__ len,
+                                                          const uint32_t* __restrict__ crc_in, uint32_t* __restrict__ out)
+{
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= n || i >= n_live[0]) { return; }
+	const u64 f = first[i], L = len[i];
+	if (f == ~(u64)0) { return; }
+	const u64 B = (u64)1 << shift, m = (L + B - 1u) >> shift;
+	const uint32_t xb = crc_xpow(B << 3);
+	uint32_t v = 0;
+	for (u64 k = 0; k < m; ++k) {
+		const uint32_t c = crc_in[f + k];
+		if (v != 0) { v = crc_mul(v, k + 1u < m ? xb : crc_xpow((L - (k << shift)) << 3)); }
+		v ^= c;
+	}
+	out[i] = v;
+}
+
 // blocks of crc_kernel that are resident on the current device at once, four per CU at most: its grid
 uint32_t crc_dev_blocks()
 {
@@ -293,6 +313,12 @@ void launch_res_crc(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift
 	if (nbt == 0) { return; }
 	const uint32_t need = (nbt + 255u) / 256u;
 	hipLaunchKernelGGL(rcrc_fold_kernel, dim3(need < blocks ? need : blocks), dim3(256), 0, st, n_res, nbt, shift, block_first, res_len, block_crc, status, res_crc);
+}
+
+void launch_crc_fold_runs(hipStream_t st, uint32_t n, const u64* n_live, uint32_t shift, const u64* first, const u64* len, const uint32_t* crc_in, uint32_t* out)
+{
+	if (n == 0) { return; }
+	hipLaunchKernelGGL(crc_foldruns_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, n, n_live, shift, first, len, crc_in, out);
 }
 
 } // namespace msc

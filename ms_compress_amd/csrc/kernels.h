@@ -424,6 +424,53 @@ void launch_diff_runs(hipStream_t st, const SpliceView& next, uint32_t n_pair, u
 // counts: delta_first and patch_first (n_pair + 1, may be null when n_pair is 0), changed (n_pair), count (4)
 void launch_diff_counts(hipStream_t st, uint32_t n_pair, uint32_t nbn, const DiffTab& t, u64* delta_first, u64* patch_first, u64* changed, u64* count, uint32_t blocks);
 
+// ---- block transcoders (transcode.hip; mscomp_amd_transcoder_*) ----
+// What a transcoder is made for, by value in every kernel's arguments. A group is an aligned span of G = 1 << sg bytes of a resource
+// (sg = max(s1, s2)): md = G / B1 source blocks and me = G / B2 new blocks at most. mode: what may be carried.
+#define TC_GENERIC 0u                                     // every source block decoded, every new block encoded
+#define TC_JOIN    1u                                     // LZNT1 to LZNT1, B2 > B1: a new block whose members all shrank is carried
+#define TC_SPLIT   2u                                     // LZNT1 to LZNT1, B2 < B1: a new block whose chunk images shrink it is carried
+struct TcDims {
+	uint32_t n_res, nbt, nbn, ngmax, gmax;             // resources; entries of the old and of the new block table; the bound of the groups; groups_max
+	uint32_t s1, s2, sg, mode;
+};
+// The transcoder's own tables, in one buffer (blockobj.hip transcode_tab is the only place that knows the layout). Rows of the new table
+// are numbered twice: p-rows over the resources that passed rules 1 and 2 (what the class pass fills), final rows over the accepted ones.
+struct TranscodeTab {
+	u64 *gfirst, *pfirst;                              // n_res + 1 each: first group, first p-row of every resource that passed rules 1 and 2
+	int32_t* rstat;                                    // n_res: the resource's status, rule by rule
+	uint32_t *gres, *gwork, *gcum;                     // ngmax each: the group's resource; 1 = worked; worked groups up to and including it
+	uint32_t* slot_group;                              // gmax: the group in a slot of cache and staging, + 1 (0 = free)
+	u64 *plen, *paddr, *pjf, *pdl;                     // nbn each, per p-row: a carried row's stored length and address; first member row of a carried join (~0: none) and its data length
+	uint32_t *pkind, *pcrc;                            // nbn each: TC_ROW_*; the folded CRC-32 of a carried join
+	u64 *addr, *tsum;                                  // nbn, tiles: per final row where its stored bytes lie (launch_blocks_move); the row tiles' sums
+	u64 *d_in_off, *d_in_len, *d_out_off, *d_out_cap, *d_ulen;   // gmax md each: the inner decompress plan's unit tables and lengths
+	u64 *d_src, *d_clen, *d_cum, *d_row, *d_raw;       // ... what the CRC kernels read of a decoded member (d_cum: + 1), its row of the old table, a raw member's address
+	int32_t* d_ustat; uint32_t *d_act, *d_crc;         // ... the inner plan's status; kind | data length << 2 (copied raw into the cache, or decoded); the CRC-32 read
+	u64 *e_in_off, *e_in_len, *e_out_off, *e_out_cap, *e_ulen;   // gmax me each: the inner compress plan's unit tables and lengths
+	u64 *e_src, *e_clen, *e_cum;                       // ... the new block's data as an address, the bytes the CRC kernels read of it (e_cum: + 1)
+	int32_t* e_ustat; uint32_t* e_crc;
+	uint32_t* cnt;                                     // 4: new blocks carried, source blocks decoded, new blocks encoded; 1 = the table as a whole was refused
+};
+// rules 0-2 (one block): t.rstat, t.gfirst, t.pfirst; t.slot_group and t.cnt cleared
+void launch_tc_resources(hipStream_t st, const TcDims& d, const u64* block_first, const u64* res_len, const TranscodeTab& t);
+// rule 3, one thread per group: the members' table checks, the class of the group (the chunk header walk on a split) and its p-rows
+void launch_tc_classes(hipStream_t st, const TcDims& d, const uint8_t* packed, u64 packed_len, const u64* block_first, const u64* block_off, const u64* res_len,
+                       bool with_crc, const TranscodeTab& t);
+// rule 4 (one block): the worked groups' slots, then the unit tables of both inner plans and of the CRC kernels (two launches)
+void launch_tc_units(hipStream_t st, const TcDims& d, const uint8_t* packed, const uint8_t* cache, const u64* block_first, const u64* block_off, const u64* res_len,
+                     bool with_crc, const TranscodeTab& t);
+// behind the inner decompress plan: the raw members of the joined groups into the cache (`blocks` = compact_dev_blocks()); behind the CRC
+// kernels: a member that did not decode to its length, or not to its checksum, fails its resource (block_crc may be null)
+void launch_tc_gather(hipStream_t st, const TcDims& d, uint8_t* cache, const TranscodeTab& t, uint32_t blocks);
+void launch_tc_judge(hipStream_t st, const TcDims& d, const uint32_t* block_crc, const TranscodeTab& t);
+// rule 5 (one block): new_first (n_res + 1), status (n_res), new_off[0]; then the three row passes tiled over the new table as splice by
+// extents tiles them -- tiles, launch_splice_tilescan, rows: new_off (nbn + 1), new_crc (nbn, may be null), t.addr, rule 6
+void launch_tc_first(hipStream_t st, const TcDims& d, const u64* res_len, const TranscodeTab& t, u64* new_first, u64* new_off, int32_t* status);
+void launch_tc_tiles(hipStream_t st, const TcDims& d, const uint8_t* stage, const u64* res_len, bool with_crc, const TranscodeTab& t, const u64* new_first, u64* new_off,
+                     uint32_t* new_crc);
+void launch_tc_rows(hipStream_t st, const TcDims& d, u64 cap, const TranscodeTab& t, const u64* new_first, u64* new_off, uint32_t* new_crc, int32_t* status);
+
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status
 // MSCOMP_ARG_ERROR), off[i] = its offset. in_off / off and status may be null.
@@ -442,6 +489,11 @@ void launch_crc_units(hipStream_t st, uint32_t n, const uint8_t* base, const u64
 // resource behind block j) into the resource's word with an atomic XOR. `blocks` = crc_dev_blocks()
 void launch_res_crc(hipStream_t st, uint32_t n_res, uint32_t nbt, uint32_t shift, const u64* block_first, const u64* res_len, const uint32_t* block_crc,
                     uint32_t* res_crc, int32_t* status, uint32_t blocks);
+
+// The same fold along runs of any table (a transcoder's carried joins): out[i] = the CRC-32 of the len[i] bytes whose pieces of
+// 1 << shift bytes (the last one shorter) have the CRC-32s crc_in[first[i] ..], for the rows i < min(n, *n_live) with first[i] != ~0; the
+// other rows are left alone. One thread per row, no data read.
+void launch_crc_fold_runs(hipStream_t st, uint32_t n, const u64* n_live, uint32_t shift, const u64* first, const u64* len, const uint32_t* crc_in, uint32_t* out);
 
 // ---- utilities (util.hip) ----
 // prefix[0..n] = exclusive scan of sizes[0..n) as u64 (prefix[n] = total). block_sums: scratch of ceil(n/1024)+1 u64.
