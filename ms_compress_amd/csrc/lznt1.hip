@@ -245,7 +245,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	// max_len > 16 is extended only when the walk lands on its position (step 2), by the whole wave: inside a long repeat every lane has such
 	// candidates, and the walk visits one or two of them.
 	const uint32_t capb = (maxlen < 16u ? maxlen : 16u) << 3, cap1 = (maxlen < LZ_S1 ? maxlen : LZ_S1) << 3;
-	u64 m16[LZ_SELF];                                         // lanes whose candidate k exists and reached 16 bytes
+	uint32_t kk[LZ_SELF];                                     // candidate k's key, 0 if it does not exist; bit 16 (length 16): it reached 16 bytes
 	{
 		uint32_t lb[LZ_SELF];                                 // length in bits (the low three dropped below)
 		{
@@ -257,7 +257,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 		}
 		u64 more = 0;
 		#pragma unroll
-		for (uint32_t k = 0; k < LZ_SELF; ++k) { more |= __builtin_amdgcn_ballot_w64(lb[k] >= 8u * LZ_S1) & ex[k]; m16[k] = 0; }
+		for (uint32_t k = 0; k < LZ_SELF; ++k) { more |= __builtin_amdgcn_ballot_w64(lb[k] >= 8u * LZ_S1) & ex[k]; }
 		if (more & __builtin_amdgcn_ballot_w64(maxlen > LZ_S1)) {
 			const LzS2 a = lz_ld_s2(s_data, p);
 			LzS2 c[LZ_SELF];
@@ -267,13 +267,12 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 			for (uint32_t k = 0; k < LZ_SELF; ++k) {                     // (a candidate that stopped inside the first stage keeps its bits)
 				const uint32_t l2 = lz_diff_bits_s2(c[k].z ^ a.z, c[k].w ^ a.w, capb);
 				lb[k] = lb[k] >= 8u * LZ_S1 ? l2 : lb[k];
-				m16[k] = __builtin_amdgcn_ballot_w64(lb[k] >= 128u) & ex[k];
 			}
 		}
 		#pragma unroll
 		for (uint32_t k = 0; k < LZ_SELF; ++k) {
-			uint32_t kk; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(kk) : "v"(((lb[k] & ~7u) << 9) | (q[k] ^ 4095u)), "s"(ex[k]));
-			key = kk > key ? kk : key;
+			asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(kk[k]) : "v"(((lb[k] & ~7u) << 9) | (q[k] ^ 4095u)), "s"(ex[k]));
+			key = kk[k] > key ? kk[k] : key;
 		}
 	}
 	// 2. greedy walk; unresolved positions (a fifth older candidate exists and max_len was not reached) are finished by the whole wave
@@ -283,8 +282,10 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	// key < maxlen << 12; a long-pending lane's provisional key never reaches it.)
 	const u64 five = ex[LZ_SELF];
 	u64 un = five & __builtin_amdgcn_ballot_w64(key < (maxlen << 12));
-	const u64 lp = sgpr64((m16[0] | m16[1] | m16[2] | m16[3]) & __builtin_amdgcn_ballot_w64(maxlen > 16u));
-	static_assert(LZ_SELF == 4u, "the long-pending mask ORs four candidates' masks");
+	// (which candidates reached 16 bytes stays in the lanes, as bit 16 of the four keys -- a compare stops at 16 bytes, so the bit is "length 16", and
+	// the key of a candidate that does not exist is 0: as four 64-bit masks they were eight scalar registers held across the walk for its rarest stop.
+	// The best key has the bit iff one of the four has it.)
+	const u64 lp = sgpr64(__builtin_amdgcn_ballot_w64(key >= (16u << 12)) & __builtin_amdgcn_ballot_w64(maxlen > 16u));
 	u64 mm = __builtin_amdgcn_ballot_w64(key >= (3u << 12)) & ~un;              // resolved or long-pending positions that have a match
 	// The serial loop only decides which candidates are TAKEN; everything else (which positions are literal tokens)
 	// is derived in parallel afterwards.
@@ -341,11 +342,11 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 				// long-pending: extend its candidates that reached 16 bytes, oldest first, with the whole wave; the first one that reaches
 				// max_len cannot be beaten (an older one would have to be longer). Then it is unresolved only if a fifth candidate exists
 				// and max_len was not reached.
-				const uint32_t qv = s_bucket[sL + (lane & (LZ_SELF - 1u))];   // (its first four entries: the candidates above)
+				const uint32_t qv = s_bucket[sL + lane % LZ_SELF];           // (its first LZ_SELF entries: the candidates above)
 				uint32_t nst = 0;
 				#pragma unroll
 				for (uint32_t k = 0; k < LZ_SELF; ++k) {
-					if ((m16[k] >> mp) & (u64)1) {
+					if ((uint32_t)__builtin_amdgcn_readlane((int)kk[k], (int)mp) >> 16) {
 						const uint32_t qk = (uint32_t)__builtin_amdgcn_readlane((int)qv, (int)k);
 						const uint32_t l = lz_lcp_wave(s_data, qk, pL, 16u, maxL, lane, nst);
 						const uint32_t kk = (l << 12) | (qk ^ 4095u);
@@ -377,7 +378,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 					uint32_t l2 = lz_diff_bits_s1(c1.x ^ a0, c1.y ^ a1, cap1L);   // in bits
 					uint32_t it = 0;
 					// (max_len is tested afresh in every step, which the empty asm enforces: hoisted out of the loop, "max_len > 8" and "max_len > 16" become
-					// two 64-bit masks that live across it, 98 scalar registers instead of 94 -- see the note on 96 at lznt1_chunk4_kernel)
+					// two 64-bit masks that live across it, four more scalar registers -- see the note on blocks per CU at lznt1_chunk4_kernel)
 					uint32_t mL = maxL; asm volatile("" : "+s"(mL));
 					if (mL > LZ_S1 && (__builtin_amdgcn_ballot_w64(l2 >= 8u * LZ_S1) & vmask)) {
 						// (a candidate that stopped inside the first stage keeps its bits)
@@ -661,15 +662,18 @@ static_assert(LZ4_P1 <= LZ4_PMAX && LZ4_P2 - LZ4_P1 <= LZ4_PMAX && 64u - LZ4_P2 
 extern "C" void mscomp_amd_debug_lz4_prof(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lz4_prof), sizeof(unsigned long long) * LZ4_NPROF); unsigned long long z[LZ4_NPROF] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lz4_prof), z, sizeof z); }
 #endif
 static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: LZNT1_REC = two areas of 64 windows of match tokens");
-// (The kernel must stay at or below 96 scalar registers, of which it uses 93: the hardware hands them out in sixteens, 800 per SIMD, so the 97th
-// costs every CU its eighth block, while the compiler's own occupancy figure still says 8 up to 100. Round 13 in profiles/HISTORY.md: builds of this parse
-// at 98 and 100 ran 5.8 waves per CU-cycle instead of 6.8 and lost 5 to 7 % of the headline. tests/test_lznt1_sgpr_budget.py reads the count of all
-// four instances; an `amdgpu_num_sgpr` limit is no way out: it makes the compiler spill, which tests/test_lznt1_resources.py forbids.)
+// (Blocks per CU by the scalar registers: a SIMD has 800 and gives a wave its count rounded up to a multiple of 16, plus 16, so a CU admits
+// min(8, 800 / (ceil16(TotalSGPRs) + 16)) blocks of 256 threads: up to 80 registers 8 blocks, 81 to 96 SEVEN, 97 to 112 six -- while the compiler's own
+// occupancy figure says 8 up to 100. Rounds 7 to 14 took 96 for the limit of eight blocks and ran at seven (93 to 96 registers: 6.79 waves per busy
+// CU-cycle, 5.81 above 96; round 13 in profiles/HISTORY.md and its correction in round 15). Since round 15 the kernel uses 77 and runs at eight
+// (7.76): lz_window keeps "candidate k reached 16 bytes" in the lanes instead of four 64-bit masks, and what sort and parse never read waits in the
+// lanes of one vector register (LZ4_PARK below). tests/test_lznt1_sgpr80.py holds all four instances at 80, without spills: an `amdgpu_num_sgpr`
+// limit gets there too, by spilling, which tests/test_lznt1_resources.py forbids.)
 template <bool serial, bool DEV = false>                         // DEV: as lznt1_chunk_kernel
 __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                           uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size, uint16_t* __restrict__ recs)
 {
-	// One object, the chunk first (see the kernel above), 20 480 B -> 8 blocks per CU. The chunk has no pad: the reads that run past its
+	// One object, the chunk first (see the kernel above), 20 480 B -> 8 blocks per CU by the LDS. The chunk has no pad: the reads that run past its
 	// end (lz_ld128 / lds_ld32 reach up to 16 bytes beyond byte 4095, into the bucket array) and the bytes between n and 4096 only feed
 	// (a) keys of positions p with p + 3 <= n, whose fourth byte is masked off, (b) compares whose result is capped by
 	// max_len <= n - p (16-byte compares at 8 min(max_len, 16) bits, lz_lcp_tail clamped to max_len; a candidate q < p stops even
@@ -706,15 +710,24 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	uint16_t* const s_flagpos = s_cnt + 128;                               // [512] byte position of group g's flag byte
 	uint32_t* const s_flagacc = reinterpret_cast<uint32_t*>(s_cnt + 640);  // [512] its bits (1280 + 2048 B <= the ends' 6144 B)
 
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-	const uint32_t c = blockIdx.x;
+	const uint32_t tid = threadIdx.x, lane = tid & 63u;
+	uint32_t c, wv;                                                        // (not const: re-fetched from the parked lanes behind the parse)
+	c = blockIdx.x; wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
 	if (DEV && past_real_chunks(bt, c)) { if (tid == 0) { slot_size[c] = 0; } return; }
+	// What sort and parse never read -- the slot's and the size index's addresses, the chunk and wave numbers -- waits in the lanes of one vector
+	// register until the parse is over: held in scalar registers across it these six cost the kernel its eighth block (see above).
+	// LZ4_FETCH reads a lane back; the empty asm in front of it redefines the register there, so the read cannot be moved up to the entry again.
+	uint32_t park = 0;
+#define LZ4_PARK(i, v) { park = lane == (i) ? (uint32_t)(v) : park; }
+#define LZ4_FETCH(i) ({ asm volatile("" : "+v"(park)); (uint32_t)__builtin_amdgcn_readlane((int)park, (int)(i)); })
+	LZ4_PARK(0, (uintptr_t)slots) LZ4_PARK(1, (uintptr_t)slots >> 32) LZ4_PARK(2, (uintptr_t)slot_size) LZ4_PARK(3, (uintptr_t)slot_size >> 32)
+	LZ4_PARK(4, c) LZ4_PARK(5, wv)
+	asm volatile("" : "+v"(park));                                         // (and the selects that fill it stay here: left alone they sink to the first read)
 	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, c);
 	const u64 coff = (u64)(c - bt.chunk_prefix[u]) * 4096u;
 	const u64 left = bt.in_len[u] - coff;
 	const uint32_t n = left < 4096u ? (uint32_t)left : 4096u;
 	const uint8_t* __restrict__ src = d_in + bt.in_off[u] + coff;
-	uint8_t* __restrict__ img = slots + (u64)c * LZNT1_SLOT;
 	// the window's match tokens, in order: area 0 is written by the speculative parse of the window's own segment, area 1 by a seam
 	// repair or the cascade (s_rep says which holds). Two areas, because the repairing wave would otherwise race the speculative
 	// wave's global stores to the same words: its progress word in LDS does not wait for them.
@@ -875,7 +888,6 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 
 	// ---- C1. speculative parse of my segment ------------------------------------------------------------------------
 	const uint32_t nw = (n + 63u) >> 6;
-	const uint32_t w0 = wv * 16u, w1 = (w0 + 16u < nw) ? w0 + 16u : nw;
 	// one window: parse, record (the match tokens into area a_). Returns the parse position after it.
 #define LZ4_WINDOW(w_, entry_, cur_out, a_) { \
 		const uint32_t wb_ = (w_) * 64u; const uint32_t we_ = (wb_ + 64u < n) ? wb_ + 64u : n; \
@@ -929,6 +941,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	__syncthreads();
 	LZ4_T(11)
 	// ---- C3. (wave 0) cascade check, then tokens / bytes before every window -----------------------------------------
+	wv = LZ4_FETCH(5);
 	if (wv == 0) {
 		for (uint32_t j = 1; j < LZ4_NSEG && lz4_seg_start(j) < nw; ++j) {
 			uint32_t e2 = s_endc[lz4_seg_start(j) - 1u];
@@ -953,6 +966,11 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	__syncthreads();                                              // the packed ends are dead from here on: prefixes and flags take their place
 	LZ4_T(13)
 	for (uint32_t i = tid; i < 512u; i += 256u) { s_flagacc[i] = 0; }
+	// the last window is parsed: back come the wave and chunk numbers and the two addresses
+	wv = LZ4_FETCH(5); c = LZ4_FETCH(4);
+	const uint32_t w0 = wv * 16u, w1 = (w0 + 16u < nw) ? w0 + 16u : nw;
+	uint8_t* __restrict__ const img = reinterpret_cast<uint8_t*>((uintptr_t)LZ4_FETCH(0) | ((uintptr_t)LZ4_FETCH(1) << 32)) + (u64)c * LZNT1_SLOT;
+	uint32_t* __restrict__ const szp = reinterpret_cast<uint32_t*>((uintptr_t)LZ4_FETCH(2) | ((uintptr_t)LZ4_FETCH(3) << 32)) + c;
 	// ---- D0. the match tokens of my 16 windows, from the records in global memory (L2-warm: written by this block) into my piece of the dead
 	// bucket array, in ONE coalesced pass of dwords (a window's LZ4_MAXM tokens are 11 dwords; 176 per wave = three loads per lane, all in
 	// flight together, under wave 0's scans). Lane l < 16 knows window w0 + l: how many matches start in it and which area holds its tokens;
@@ -1028,10 +1046,12 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		}
 		total = 2u + n;
 	}
-	if (tid == 0) { slot_size[c] = total; }
+	if (tid == 0) { *szp = total; }
 	LZ4_T(18)
 	LZ4_TEND
 #undef LZ4_WINDOW
+#undef LZ4_PARK
+#undef LZ4_FETCH
 }
 
 // DEV = true: the instances of compress plans with device tables, compiled in lznt1_dev.hip (this file included with LZNT1_DEV_TU defined), so
