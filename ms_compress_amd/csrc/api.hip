@@ -222,7 +222,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());   // (every return below that is not the last one gives up the plan and what it holds)
 	if (!p) { return MSCOMP_MEM_ERROR; }
-	p->ctx = c; p->format = format; p->decompress = decompress; p->sizing = sizing; p->n_units = (uint32_t)n_units;
+	p->ctx = c; p->format = format; p->decompress = decompress; p->sizing = sizing; p->n_units = (uint32_t)n_units; p->run.never = n_units == 0;
 	p->lznt1_sa = !decompress && format == MSCOMP_LZNT1 && lznt1_sa_for(c);
 
 	const size_t host_words = n_units * 4 + (n_units + 2) / 2 + 1;
@@ -597,8 +597,8 @@ MSCompStatus mscomp_amd_plan_execute(mscomp_amd_plan* p, const uint8_t* d_in, ui
 	DeviceGuard g(p->ctx->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	if (p->decompress) { note_modes(p); }
-	const void* args[9] = { d_in, d_out, d_out_len, d_status };
-	return plan_run(p, args, [&] { (p->decompress ? decode_launch : compress_launch)(p, d_in, d_out, d_out_len, d_status); });
+	const void* args[8] = { d_in, d_out, d_out_len, d_status };
+	return plan_run(p->run, p->ctx, args, [&] { (p->decompress ? decode_launch : compress_launch)(p, d_in, d_out, d_out_len, d_status); });
 }
 
 MSCompStatus mscomp_amd_compress_batch(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units,
@@ -845,7 +845,7 @@ static MSCompStatus create_decode_dev(mscomp_amd_ctx* c, MSCompFormat format, si
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());
 	if (!p) { return MSCOMP_MEM_ERROR; }
-	p->ctx = c; p->format = format; p->decompress = true; p->sizing = sizing; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
+	p->ctx = c; p->format = format; p->decompress = true; p->sizing = sizing; p->dev = true; p->n_units = (uint32_t)N; p->run.never = N == 0; p->n_chunks = (uint32_t)chunks;
 	p->in_total_max = in_total_max; p->out_total_max = sizing ? 0 : out_total_max; p->total_in = in_total_max; p->xhc_slots = (uint32_t)cands;
 	p->large = (flags & MSCOMP_AMD_DEV_LARGE_UNITS) && format != MSCOMP_LZNT1;   // (LZNT1 has no optional paths: its dev plans run the host plan's kernels already)
 	bool ok = reserve_dev_tables(p.get());
@@ -896,7 +896,7 @@ MSCompStatus mscomp_amd_plan_create_compress_dev(mscomp_amd_ctx* c, MSCompFormat
 	if (chunks > 0x7FFFFFF0ull) { return MSCOMP_MEM_ERROR; }
 	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());
 	if (!p) { return MSCOMP_MEM_ERROR; }
-	p->ctx = c; p->format = format; p->decompress = false; p->dev = true; p->n_units = (uint32_t)N; p->n_chunks = (uint32_t)chunks;
+	p->ctx = c; p->format = format; p->decompress = false; p->dev = true; p->n_units = (uint32_t)N; p->run.never = N == 0; p->n_chunks = (uint32_t)chunks;
 	p->in_total_max = in_total_max; p->total_in = in_total_max; p->max_unit = U;   // (max_unit: the bound dv_ctables_kernel checks, and the Xpress finder as compress_launch chooses it)
 	p->lznt1_sa = format == MSCOMP_LZNT1 && lznt1_sa_for(c);
 	if (!reserve_dev_tables(p.get()) || !reserve_compress_scratch(c, format, N, chunks, p->lznt1_sa)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
@@ -942,8 +942,8 @@ MSCompStatus mscomp_amd_plan_execute_dev(mscomp_amd_plan* p, const uint8_t* d_in
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	if (p->decompress) { note_modes(p); }
 	p->ran = true;
-	const void* args[9] = { d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status };
-	return plan_run(p, args, [&] { dev_launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status); });
+	const void* args[8] = { d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status };
+	return plan_run(p->run, p->ctx, args, [&] { dev_launch(p, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status); });
 }
 
 MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -958,8 +958,8 @@ MSCompStatus mscomp_amd_plan_execute_size_dev(mscomp_amd_plan* p, const uint8_t*
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	note_modes(p);
 	p->ran = true;
-	const void* args[9] = { d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status };
-	return plan_run(p, args, [&] {
+	const void* args[8] = { d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status };
+	return plan_run(p->run, p->ctx, args, [&] {
 		{ KernelTimer t(c, "dv_tables_kernel"); launch_dev_stables(c->stream, (int)p->format, p->n_units, p->in_total_max, d_in_off, d_in_len, d_limit, static_cast<u64*>(p->tables.p),
 		                                                          const_cast<uint32_t*>(p->bt.chunk_prefix), p->tok_prefix, p->reject); }
 		run_dev_paths(p);
@@ -980,7 +980,7 @@ MSCompStatus mscomp_amd_plan_create_crc_dev(mscomp_amd_ctx* c, size_t n_units, u
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());
 	if (!p) { return MSCOMP_MEM_ERROR; }
-	p->ctx = c; p->dev = true; p->crc = true; p->n_units = (uint32_t)n_units; p->in_total_max = in_total_max; p->total_in = in_total_max;
+	p->ctx = c; p->dev = true; p->crc = true; p->n_units = (uint32_t)n_units; p->run.never = n_units == 0; p->in_total_max = in_total_max; p->total_in = in_total_max;
 	if (!p->tables.reserve((2 * n_units + 1) * 8)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	*out = p.release();
 	return MSCOMP_OK;
@@ -997,8 +997,8 @@ MSCompStatus mscomp_amd_plan_execute_crc_dev(mscomp_amd_plan* p, const uint8_t* 
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	p->ran = true;
-	const void* args[5] = { d_in, d_in_off, d_in_len, d_crc, d_status };
-	return plan_run(p, args, [&] {
+	const void* args[8] = { d_in, d_in_off, d_in_len, d_crc, d_status };
+	return plan_run(p->run, p->ctx, args, [&] {
 		u64* cum = static_cast<u64*>(p->tables.p); u64* off = cum + p->n_units + 1u;
 		{ KernelTimer t(c, "crc_tables_kernel"); launch_crc_tables(c->stream, p->n_units, p->in_total_max, d_in_off, d_in_len, off, cum, d_status); }
 		{ KernelTimer t(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, p->n_units, cum, d_crc, nullptr, nullptr); }
@@ -1254,7 +1254,7 @@ struct OneShotTls {
 		mscomp_amd_plan* p = nullptr;
 		const MSCompStatus s = plan_create_impl(ctx, f, dec, 1, &z, &in_len, &z, &out_cap, &p);
 		if (s != MSCOMP_OK) { return s; }
-		p->no_graph = true;
+		p->run.never = true;
 		if (plans.size() >= 8) {
 			size_t lru = 0;
 			for (size_t i = 1; i < plans.size(); ++i) { if (plans[i].used < plans[lru].used) { lru = i; } }

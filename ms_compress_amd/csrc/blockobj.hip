@@ -4,6 +4,8 @@
 
 using namespace msc;
 
+#pragma GCC visibility push(hidden)                     // this file's helpers: not exported, as what host.h adds to namespace msc
+
 // A table buffer handed out column by column, in the order asked for. The same code run from address 0 counts the bytes, so a layout is
 // written down once. u64 columns first, from an 8-byte-aligned base: every one of them stays aligned.
 struct Carve {
@@ -14,12 +16,76 @@ struct Carve {
 };
 
 // The checks every create starts with, on arguments alone: MSCOMP_ARG_ERROR before MSCOMP_MEM_ERROR, both before the context is used.
+static bool block_size_ok(uint32_t block_size) { return block_size >= 4096u && block_size <= 524288u && !(block_size & (block_size - 1u)); }
 static bool create_args_ok(const mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, uint32_t flags)
 {
-	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return false; }
+	if (!c || flags || !block_size_ok(block_size)) { return false; }
 	return format == MSCOMP_LZNT1 || format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF;
 }
 static bool count_ok(uint64_t n) { return n <= 0x7FFFFFF0u; }
+
+// Every destroy: on the object's device, its stream idle, `release` gives up what o (may be null) holds on the device; the delete, its graphs.
+template <class T, class Release> static void destroy_object(T* o, const Release& release)
+{
+	if (!o) { return; }
+	DeviceGuard g(o->ctx->device);
+	(void)hipStreamSynchronize(o->ctx->stream);
+	release();
+	delete o;
+}
+
+// The inner dev plans of an object that decodes or encodes blocks as units, and what they work on: dplan decodes n_d units within `total`
+// bytes on either side (a container: from the caller's bytes; else into the cache), cplan encodes n_c units of at most `unit` bytes within
+// `total` into the staging area. A plan without units and a buffer without bytes stay null. The object's calls run the plans' launches
+// (dev_launch) between their own passes, through plan_run with a record per call, so the inner plans never capture: the graph is the
+// call's, or the caller's.
+struct InnerPlans {
+	mscomp_amd_plan* dplan = nullptr; mscomp_amd_plan* cplan = nullptr;
+	DevBuf cache, stage;
+	void destroy() { mscomp_amd_plan_destroy(dplan); mscomp_amd_plan_destroy(cplan); dplan = cplan = nullptr; cache.release(); stage.release(); }
+	// a call is about to run these plans' launches (mscomp_amd_debug_decode_modes, mscomp_amd_debug_plan_paths)
+	void mark_ran(bool decode = true, bool encode = true)
+	{
+		if (decode && dplan) { note_modes(dplan); dplan->ran = true; }
+		if (encode && cplan) { cplan->ran = true; }
+	}
+	// the object's tables (`tab`) and the buffers, then the plans; on the first failure nothing is held, `tab` neither
+	MSCompStatus create(mscomp_amd_ctx* c, DevBuf& tab, uint64_t tab_bytes, uint64_t cache_bytes, uint64_t stage_bytes, uint64_t total, MSCompFormat format_d, uint64_t n_d,
+	                    MSCompFormat format_c, uint64_t n_c, uint64_t unit, bool compress_first = false)
+	{
+		MSCompStatus st = tab.reserve(tab_bytes) && (!cache_bytes || cache.reserve(cache_bytes)) && (!stage_bytes || stage.reserve(stage_bytes)) ? MSCOMP_OK : MSCOMP_MEM_ERROR;
+		for (int i = 0; i < 2 && st == MSCOMP_OK; ++i) {
+			if ((i == 0) != compress_first) { if (n_d) { st = mscomp_amd_plan_create_decompress_dev(c, format_d, n_d, total, total, &dplan); } }
+			else if (n_c) { st = mscomp_amd_plan_create_compress_dev(c, format_c, n_c, total, unit, &cplan); }   // (fixes the LZNT1 dictionary flavour)
+		}
+		if (st != MSCOMP_OK) { (void)hipGetLastError(); destroy(); tab.release(); }
+		return st;
+	}
+};
+
+// The views of a call, checked and packed as the kernels take them: with their checksums if they are wanted and every view has them, which
+// with_crc says. False: a view with a null table, or with stored bytes at a null address.
+static bool pack_views(const mscomp_amd_blocks_view* src, uint32_t n_src, bool want_crc, SpliceView* out, bool& with_crc)
+{
+	with_crc = want_crc;
+	for (uint32_t i = 0; i < n_src; ++i) {
+		const mscomp_amd_blocks_view& v = src[i];
+		if (v.n_res && (!v.d_block_first || !v.d_block_off || !v.d_res_len || (v.packed_len && !v.d_packed))) { return false; }
+		with_crc = with_crc && v.d_block_crc;
+	}
+	for (uint32_t i = 0; i < n_src; ++i) {
+		const mscomp_amd_blocks_view& v = src[i];
+		out[i] = { v.d_packed, v.packed_len, v.d_block_first, v.d_block_off, v.d_res_len, with_crc ? v.d_block_crc : nullptr, v.n_res, v.n_blocks_table };
+	}
+	return true;
+}
+// The graph key of a call that takes views: every field of them (the sources are read on the host and go into the kernel arguments by
+// value), then the rest of its arguments.
+template <size_t N, size_t R> static void view_args(const void* (&args)[N], const SpliceView* v, const void* const (&rest)[R])
+{
+	static_assert(N > R && (N - R) * sizeof(void*) % sizeof(SpliceView) == 0, "whole views, then the rest");
+	memcpy(args, v, (N - R) * sizeof(void*)); memcpy(args + (N - R), rest, sizeof rest);
+}
 
 // The CRC-32 of n units: crc[u] over the len[u] bytes at base + off[u]; cum (n + 1) is scratch. The table pass, the seeds, the bytes.
 static void crc_seeds(mscomp_amd_ctx* c, uint32_t n, u64 in_total_max, const u64* len, u64* cum, int32_t* status, uint32_t* crc, const u64* after, uint32_t* fac)
@@ -33,19 +99,19 @@ static void crc_pass(mscomp_amd_ctx* c, uint32_t n, const uint8_t* base, const u
 	{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, n, base, off, cum, crc, nullptr, nullptr, nullptr, c->crc_blocks); }
 }
 
+#pragma GCC visibility pop
+
 // ---- block containers (include/mscomp_amd.h; kernels: blocks.hip) ----
 // A container owns two inner dev plans over blocks as units -- compress: n_blocks_max units of at most block_size bytes; decompress: the same
-// number of units within in_total_max bytes on either side --, a staging area for the compressed blocks and its own tables. Its two calls
-// run the inner plans' launches (dev_launch) between their own passes, through plan_run with a record of their own (crun / drun: plans that
-// hold nothing but the graph of the call), so the inner plans never capture: the graph is the call's, or the caller's.
+// number of units within in_total_max bytes on either side --, a staging area for the compressed blocks and its own tables.
 struct mscomp_amd_blocks {
 	mscomp_amd_ctx* ctx = nullptr;
 	MSCompFormat format = MSCOMP_NONE;
 	uint32_t shift = 0, n_res = 0, n_blocks = 0;       // block_size = 1 << shift; n_blocks = n_blocks_max
 	uint64_t in_total_max = 0;
-	mscomp_amd_plan* cplan = nullptr; mscomp_amd_plan* dplan = nullptr;   // (null when n_blocks is 0)
-	mscomp_amd_plan crun, drun, krun, vrun;            // (krun: mscomp_amd_blocks_crc, vrun: _check)
-	DevBuf tab, stage;                                 // BlocksTab; staged compressed blocks: in_total_max + 16 n_res bytes
+	InnerPlans in;                                     // (no cache; the staged compressed blocks: in_total_max + 16 n_res bytes)
+	GraphRun<8> crun; GraphRun<11> drun; GraphRun<6> krun; GraphRun<8> vrun;   // compress, decompress, crc, check
+	DevBuf tab;                                        // BlocksTab
 	BlocksTab t{};
 };
 
@@ -73,26 +139,16 @@ MSCompStatus mscomp_amd_blocks_create(mscomp_amd_ctx* c, MSCompFormat format, ui
 	std::unique_ptr<mscomp_amd_blocks> b(new (std::nothrow) mscomp_amd_blocks());
 	if (!b) { return MSCOMP_MEM_ERROR; }
 	b->ctx = c; b->format = format; b->shift = (uint32_t)__builtin_ctz(block_size); b->n_res = (uint32_t)n_res; b->n_blocks = (uint32_t)M; b->in_total_max = in_total_max;
-	b->crun.ctx = b->drun.ctx = b->krun.ctx = b->vrun.ctx = c; b->crun.n_units = b->drun.n_units = b->krun.n_units = b->vrun.n_units = (uint32_t)n_res;
-	MSCompStatus st = MSCOMP_OK;
-	if (!b->tab.reserve(blocks_tab(b->t, nullptr, n_res, M) + 64) || !b->stage.reserve(in_total_max + 16 * (uint64_t)n_res + 64)) { st = MSCOMP_MEM_ERROR; }
-	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_compress_dev(c, format, M, in_total_max, block_size, &b->cplan); }
-	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, in_total_max, in_total_max, &b->dplan); }
-	if (st != MSCOMP_OK) { (void)hipGetLastError(); mscomp_amd_blocks_destroy(b.release()); return st; }
+	b->crun.never = b->drun.never = b->krun.never = b->vrun.never = n_res == 0;
+	const MSCompStatus st = b->in.create(c, b->tab, blocks_tab(b->t, nullptr, n_res, M) + 64, 0, in_total_max + 16 * (uint64_t)n_res + 64, in_total_max, format, M, format, M,
+	                                     block_size, true);
+	if (st != MSCOMP_OK) { return st; }
 	blocks_tab(b->t, b->tab.p, n_res, M);
 	*out = b.release();
 	return MSCOMP_OK;
 }
 
-void mscomp_amd_blocks_destroy(mscomp_amd_blocks* b)
-{
-	if (!b) { return; }
-	DeviceGuard g(b->ctx->device);
-	(void)hipStreamSynchronize(b->ctx->stream);
-	mscomp_amd_plan_destroy(b->cplan); mscomp_amd_plan_destroy(b->dplan);
-	b->tab.release(); b->stage.release();
-	delete b;                                              // (crun / drun give up their graphs)
-}
+void mscomp_amd_blocks_destroy(mscomp_amd_blocks* b) { destroy_object(b, [b] { b->in.destroy(); b->tab.release(); }); }
 
 uint64_t mscomp_amd_blocks_bound(const mscomp_amd_blocks* b) { return b ? b->n_blocks : 0; }
 
@@ -104,13 +160,13 @@ MSCompStatus mscomp_amd_blocks_compress(mscomp_amd_blocks* b, const uint8_t* d_i
 	mscomp_amd_ctx* c = b->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (b->cplan) { b->cplan->ran = true; }
+	b->in.mark_ran(false, true);
 	const void* args[8] = { d_in, d_res_off, d_res_len, d_packed, reinterpret_cast<const void*>((uintptr_t)packed_cap), d_block_first, d_block_off, d_status };
-	return plan_run(&b->crun, args, [&] {
+	return plan_run(b->crun, c, args, [&] {
 		const BlocksTab& t = b->t;
-		uint8_t* stage = static_cast<uint8_t*>(b->stage.p);
+		uint8_t* stage = static_cast<uint8_t*>(b->in.stage.p);
 		{ KernelTimer k(c, "bk_ctables"); launch_blocks_ctables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_off, d_res_len, d_block_first, t); }
-		if (b->cplan) { dev_launch(b->cplan, d_in, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (b->in.cplan) { dev_launch(b->in.cplan, d_in, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
 		{ KernelTimer k(c, "bk_select_kernel"); launch_blocks_select(c->stream, b->n_res, b->n_blocks, packed_cap, d_in, stage, d_block_first, t, d_block_off, d_status); }
 		{ KernelTimer k(c, "cpd_copy_kernel"); launch_pack_ptrs(c->stream, b->n_blocks, t.aux_b, t.aux_a, d_block_off, d_packed, packed_cap, c->cpd_blocks); }
 	});
@@ -126,14 +182,14 @@ MSCompStatus mscomp_amd_blocks_decompress(mscomp_amd_blocks* b, const uint8_t* d
 	mscomp_amd_ctx* c = b->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (b->dplan) { note_modes(b->dplan); b->dplan->ran = true; }
+	b->in.mark_ran(true, false);
 	const void* args[11] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_range,
 	                         d_out, d_out_off, d_out_cap, d_out_len, d_status };
-	return plan_run(&b->drun, args, [&] {
+	return plan_run(b->drun, c, args, [&] {
 		const BlocksTab& t = b->t;
 		{ KernelTimer k(c, "bk_dtables"); launch_blocks_dtables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, packed_len, d_res_len, d_block_first, d_block_off,
 		                                                        d_range, d_out_off, d_out_cap, t); }
-		if (b->dplan) { dev_launch(b->dplan, d_packed, t.in_off, t.in_len, d_out, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (b->in.dplan) { dev_launch(b->in.dplan, d_packed, t.in_off, t.in_len, d_out, t.out_off, t.out_cap, t.ulen, t.ustat); }
 		{ KernelTimer k(c, "bk_rawcopy_kernel"); launch_blocks_rawcopy(c->stream, b->n_blocks, b->shift, d_packed, d_out, t, c->cpd_blocks); }
 		{ KernelTimer k(c, "bk_dfold_kernel"); launch_blocks_dfold(c->stream, b->n_res, t, d_out_len, d_status); }
 	});
@@ -155,7 +211,7 @@ MSCompStatus mscomp_amd_blocks_crc(mscomp_amd_blocks* b, const uint8_t* d_data, 
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	const void* args[6] = { d_data, d_res_off, d_res_len, d_block_crc, d_res_crc, d_status };
-	return plan_run(&b->krun, args, [&] {
+	return plan_run(b->krun, c, args, [&] {
 		const BlocksTab& t = b->t;
 		{ KernelTimer k(c, "bk_ctables"); launch_blocks_ctables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_off, d_res_len, t.unit_first, t); }
 		{ KernelTimer k(c, "bk_crcgroups_kernel"); launch_blocks_crcgroups(c->stream, b->n_res, b->n_blocks, b->shift, d_res_len, t.unit_first, t); }
@@ -177,7 +233,7 @@ MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* b, const uint8_t* d_out,
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	const void* args[8] = { d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status };
-	return plan_run(&b->vrun, args, [&] {
+	return plan_run(b->vrun, c, args, [&] {
 		const BlocksTab& t = b->t;
 		{ KernelTimer k(c, "bk_ktables"); launch_blocks_ktables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_len, d_block_first, d_range, d_out_off, d_status, t); }
 		crc_pass(c, b->n_blocks, d_out, t.in_off, t.in_len, t.aux_a, t.ucrc);
@@ -189,25 +245,22 @@ MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* b, const uint8_t* d_out,
 // What a reader is and a writer starts from: one inner decompress dev plan over blocks_max units within blocks_max B bytes on either
 // side, the cache those units are decoded into and its own tables. Everything is sized by what one call may touch, nothing by what the
 // container holds but the 4 bytes per entry of its block table. A call runs the inner plan's launches (dev_launch) and the CRC kernels
-// between its own passes, through plan_run with a record of its own (run), as a container does.
+// between its own passes, as a container does.
 struct BlockAccess {
 	mscomp_amd_ctx* ctx = nullptr;
 	MSCompFormat format = MSCOMP_NONE;
 	uint32_t shift = 0, n_res = 0, nbt = 0, n_req = 0, m = 0;   // block_size = 1 << shift; nbt = n_blocks_table; m = blocks_max
-	mscomp_amd_plan* dplan = nullptr;                  // (null when blocks_max is 0)
-	mscomp_amd_plan run;
-	DevBuf tab, cache;                                 // ReaderTab, a writer's extras behind it; blocks_max slots of block_size bytes
+	InnerPlans in;                                     // (plans: null when blocks_max is 0; cache, a writer's staging area: blocks_max slots of block_size bytes)
+	DevBuf tab;                                        // ReaderTab, a writer's extras behind it
 	ReaderTab t{};
 	bool ran = false;
 };
-struct mscomp_amd_reader : BlockAccess {};
+struct mscomp_amd_reader : BlockAccess { GraphRun<12> run; };
 // A writer adds an inner compress dev plan over the same units (a dirty block is compressed from its cache slot into its staging slot), the
 // staging area and four more columns. Its call runs the reader's passes up to the fold, then its own. Its second call, resize, runs on
-// the same scratch with a record of its own (rrun: write and resize keep separate graphs) and two columns per resource.
+// the same scratch with a record of its own (write and resize keep separate graphs) and two columns per resource.
 struct mscomp_amd_writer : BlockAccess {
-	mscomp_amd_plan* cplan = nullptr;                  // (null when blocks_max is 0)
-	mscomp_amd_plan rrun;
-	DevBuf stage;                                      // blocks_max slots of block_size bytes
+	GraphRun<16> run; GraphRun<14> rrun;               // write, resize
 	uint32_t* head = nullptr; uint32_t* next = nullptr; uint32_t* dirty = nullptr; uint64_t* addr = nullptr;   // the rest of WriterTab
 	uint64_t* ru_first = nullptr; int32_t* rstat = nullptr;                          // the rest of ResizeTab
 	bool resized = false;                              // the last execution was a resize (mscomp_amd_writer_counts)
@@ -229,16 +282,6 @@ static uintptr_t access_tab(BlockAccess* a, mscomp_amd_writer* w, void* base)
 	return k.at;
 }
 
-// everything a (may be null) holds on the device, and a writer's too (the caller deletes the object)
-static void access_destroy(BlockAccess* a, mscomp_amd_writer* w)
-{
-	if (!a) { return; }
-	DeviceGuard g(a->ctx->device);
-	(void)hipStreamSynchronize(a->ctx->stream);
-	mscomp_amd_plan_destroy(a->dplan);
-	if (w) { mscomp_amd_plan_destroy(w->cplan); w->stage.release(); }
-	a->tab.release(); a->cache.release();
-}
 // Both creates, from the checks on: a is the caller's new object (null: out of memory, said where the caller would have found out), w the
 // same object when it is a writer. On failure nothing is held.
 static MSCompStatus access_create(BlockAccess* a, mscomp_amd_writer* w, mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res,
@@ -253,15 +296,10 @@ static MSCompStatus access_create(BlockAccess* a, mscomp_amd_writer* w, mscomp_a
 	if (!a) { return MSCOMP_MEM_ERROR; }
 	a->ctx = c; a->format = format; a->shift = (uint32_t)__builtin_ctz(block_size); a->n_res = (uint32_t)n_res; a->nbt = (uint32_t)n_blocks_table;
 	a->n_req = (uint32_t)n_req; a->m = (uint32_t)M;
-	a->run.ctx = c; a->run.n_units = (uint32_t)n_req;
-	if (w) { w->rrun.ctx = c; w->rrun.n_units = (uint32_t)n_res; }
-	MSCompStatus st = MSCOMP_OK;
-	if (!a->tab.reserve(access_tab(a, w, nullptr) + 64) || (M && (!a->cache.reserve(bytes + 64) || (w && !w->stage.reserve(bytes + 64))))) { st = MSCOMP_MEM_ERROR; }
-	if (st == MSCOMP_OK && M) { st = mscomp_amd_plan_create_decompress_dev(c, format, M, bytes, bytes, &a->dplan); }
-	if (st == MSCOMP_OK && M && w) { st = mscomp_amd_plan_create_compress_dev(c, format, M, bytes, block_size, &w->cplan); }   // (fixes the LZNT1 dictionary flavour)
-	if (st != MSCOMP_OK) { (void)hipGetLastError(); access_destroy(a, w); return st; }
-	access_tab(a, w, a->tab.p);
-	return MSCOMP_OK;
+	const uint64_t slots = M ? bytes + 64 : 0;
+	const MSCompStatus st = a->in.create(c, a->tab, access_tab(a, w, nullptr) + 64, slots, w ? slots : 0, bytes, format, M, format, w ? M : 0, block_size);
+	if (st == MSCOMP_OK) { access_tab(a, w, a->tab.p); }
+	return st;
 }
 // units, distinct blocks, and the decoded (a reader) or re-encoded (a writer) blocks of a's last execution (read back; none before the first,
 // none for a table a writer refused)
@@ -288,14 +326,14 @@ static void access_admit(BlockAccess* a, const uint8_t* d_packed, uint64_t packe
 {
 	mscomp_amd_ctx* c = a->ctx;
 	{ KernelTimer k(c, "rd_req_kernel"); launch_reader_requests(c->stream, a->n_req, a->n_res, a->nbt, a->m, a->shift, d_res_len, d_block_first, d_req, d_out_cap, a->t); }
-	{ KernelTimer k(c, "rd_units"); launch_reader_units(c->stream, a->n_req, a->nbt, a->m, a->shift, packed_len, d_packed, static_cast<uint8_t*>(a->cache.p), d_block_off, a->t); }
+	{ KernelTimer k(c, "rd_units"); launch_reader_units(c->stream, a->n_req, a->nbt, a->m, a->shift, packed_len, d_packed, static_cast<uint8_t*>(a->in.cache.p), d_block_off, a->t); }
 }
 // Decode and judge: the owners' blocks decoded into the cache, checksummed (d_block_crc may be null), then status and length per request.
 static void access_decode(BlockAccess* a, const uint8_t* d_packed, const uint32_t* d_block_crc, uint64_t* d_len, int32_t* d_status)
 {
 	mscomp_amd_ctx* c = a->ctx;
 	const ReaderTab& t = a->t;
-	if (a->dplan) { dev_launch(a->dplan, d_packed, t.in_off, t.in_len, static_cast<uint8_t*>(a->cache.p), t.out_off, t.out_cap, t.ulen, t.ustat); }
+	if (a->in.dplan) { dev_launch(a->in.dplan, d_packed, t.in_off, t.in_len, static_cast<uint8_t*>(a->in.cache.p), t.out_off, t.out_cap, t.ulen, t.ustat); }
 	if (d_block_crc && a->m) { crc_pass(c, a->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }   // the owners' blocks lie under two bases: their addresses go in as offsets from a null one
 	if (a->n_req) { KernelTimer k(c, "rd_fold_kernel"); launch_reader_fold(c->stream, a->n_req, d_block_crc, t, d_len, d_status); }
 }
@@ -307,14 +345,10 @@ MSCompStatus mscomp_amd_reader_create(mscomp_amd_ctx* c, MSCompFormat format, ui
 	*out = nullptr;
 	std::unique_ptr<mscomp_amd_reader> r(new (std::nothrow) mscomp_amd_reader());
 	const MSCompStatus st = access_create(r.get(), nullptr, c, format, block_size, n_res, n_blocks_table, n_req, blocks_max, flags);
-	if (st == MSCOMP_OK) { *out = r.release(); }
+	if (st == MSCOMP_OK) { r->run.never = n_req == 0; *out = r.release(); }
 	return st;
 }
-void mscomp_amd_reader_destroy(mscomp_amd_reader* r)
-{
-	access_destroy(r, nullptr);
-	delete r;                                              // (run gives up its graph)
-}
+void mscomp_amd_reader_destroy(mscomp_amd_reader* r) { destroy_object(r, [r] { r->in.destroy(); r->tab.release(); }); }
 
 MSCompStatus mscomp_amd_reader_read(mscomp_amd_reader* r, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
                                     const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_req,
@@ -327,11 +361,10 @@ MSCompStatus mscomp_amd_reader_read(mscomp_amd_reader* r, const uint8_t* d_packe
 	mscomp_amd_ctx* c = r->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (r->dplan) { note_modes(r->dplan); r->dplan->ran = true; }
-	r->ran = true;
+	r->in.mark_ran(); r->ran = true;
 	const void* args[12] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
 	                         d_out, d_out_off, d_out_cap, d_out_len, d_status };
-	return plan_run(&r->run, args, [&] {
+	return plan_run(r->run, c, args, [&] {
 		access_admit(r, d_packed, packed_len, d_block_first, d_block_off, d_res_len, d_req, d_out_cap);
 		access_decode(r, d_packed, d_block_crc, d_out_len, d_status);
 		{ KernelTimer k(c, "rd_gather_kernel"); launch_reader_gather(c->stream, r->n_req, r->m, r->shift, d_out, d_out_off, r->t, c->cpd_blocks); }
@@ -347,14 +380,10 @@ MSCompStatus mscomp_amd_writer_create(mscomp_amd_ctx* c, MSCompFormat format, ui
 	*out = nullptr;
 	std::unique_ptr<mscomp_amd_writer> w(new (std::nothrow) mscomp_amd_writer());
 	const MSCompStatus st = access_create(w.get(), w.get(), c, format, block_size, n_res, n_blocks_table, n_req, blocks_max, flags);
-	if (st == MSCOMP_OK) { *out = w.release(); }
+	if (st == MSCOMP_OK) { w->run.never = n_req == 0; w->rrun.never = n_res == 0; *out = w.release(); }
 	return st;
 }
-void mscomp_amd_writer_destroy(mscomp_amd_writer* w)
-{
-	access_destroy(w, w);
-	delete w;                                              // (run gives up its graph)
-}
+void mscomp_amd_writer_destroy(mscomp_amd_writer* w) { destroy_object(w, [w] { w->in.destroy(); w->tab.release(); }); }
 
 MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* w, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
                                      const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_req,
@@ -368,22 +397,21 @@ MSCompStatus mscomp_amd_writer_write(mscomp_amd_writer* w, const uint8_t* d_pack
 	mscomp_amd_ctx* c = w->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (w->dplan) { note_modes(w->dplan); w->dplan->ran = true; w->cplan->ran = true; }
-	w->ran = true; w->resized = false;
+	w->in.mark_ran(); w->ran = true; w->resized = false;
 	const void* args[16] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
 	                         d_src, d_src_off, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_off, d_new_block_crc,
 	                         d_written, d_status, d_res_status };
-	return plan_run(&w->run, args, [&] {
+	return plan_run(w->run, c, args, [&] {
 		const ReaderTab& t = w->t;
 		const WriterTab wt = { t, w->head, w->next, w->dirty, w->addr };
-		uint8_t* cache = static_cast<uint8_t*>(w->cache.p); uint8_t* stage = static_cast<uint8_t*>(w->stage.p);
+		uint8_t* cache = static_cast<uint8_t*>(w->in.cache.p); uint8_t* stage = static_cast<uint8_t*>(w->in.stage.p);
 		// the reader's passes: admission (without its capacity rule), owners, the owners' blocks decoded, checksummed and judged
 		access_admit(w, d_packed, packed_len, d_block_first, d_block_off, d_res_len, d_req, nullptr);
 		{ KernelTimer k(c, "wr_link"); launch_writer_link(c->stream, w->n_req, w->nbt, w->m, wt); }
 		access_decode(w, d_packed, d_block_crc, d_written, d_status);
 		// the writer's own: patch, re-encode and checksum the dirty blocks, lay out, move
 		{ KernelTimer k(c, "wr_patch"); launch_writer_patch(c->stream, w->n_req, w->m, w->shift, d_src, d_src_off, cache, wt, c->cpd_blocks); }
-		if (w->cplan) { dev_launch(w->cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (w->in.cplan) { dev_launch(w->in.cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
 		if (d_block_crc && w->m) { crc_pass(c, w->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }
 		{ KernelTimer k(c, "wr_layout_kernel"); launch_writer_layout(c->stream, w->n_req, w->n_res, w->nbt, w->m, w->shift, packed_len, new_cap, d_packed, stage, cache, d_block_first,
 		                                                             d_block_off, d_block_crc, wt, d_new_block_off, d_new_block_crc, d_written, d_status, d_res_status); }
@@ -408,22 +436,21 @@ MSCompStatus mscomp_amd_writer_resize(mscomp_amd_writer* w, const uint8_t* d_pac
 	mscomp_amd_ctx* c = w->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (w->dplan) { note_modes(w->dplan); w->dplan->ran = true; w->cplan->ran = true; }
-	w->ran = true; w->resized = true;
+	w->in.mark_ran(); w->ran = true; w->resized = true;
 	const void* args[14] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_want_len,
 	                         d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc,
 	                         d_new_res_len, d_res_status };
-	return plan_run(&w->rrun, args, [&] {
+	return plan_run(w->rrun, c, args, [&] {
 		const ReaderTab& t = w->t;
 		const ResizeTab rt = { { t, w->head, w->next, w->dirty, w->addr }, w->ru_first, w->rstat };
-		uint8_t* cache = static_cast<uint8_t*>(w->cache.p); uint8_t* stage = static_cast<uint8_t*>(w->stage.p);
+		uint8_t* cache = static_cast<uint8_t*>(w->in.cache.p); uint8_t* stage = static_cast<uint8_t*>(w->in.stage.p);
 		{ KernelTimer k(c, "rs_units"); launch_resize_units(c->stream, w->n_res, w->nbt, w->m, w->shift, packed_len, d_packed, cache, d_block_first, d_block_off,
 		                                                    d_res_len, d_want_len, rt); }
-		if (w->dplan) { dev_launch(w->dplan, d_packed, t.in_off, t.in_len, cache, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (w->in.dplan) { dev_launch(w->in.dplan, d_packed, t.in_off, t.in_len, cache, t.out_off, t.out_cap, t.ulen, t.ustat); }
 		if (d_block_crc && w->m) { crc_pass(c, w->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }
 		{ KernelTimer k(c, "rs_fold_kernel"); launch_resize_fold(c->stream, w->n_res, w->m, w->shift, d_block_first, d_res_len, d_want_len, d_block_crc, rt); }
 		{ KernelTimer k(c, "rs_fill"); launch_resize_fill(c->stream, w->n_res, w->m, w->shift, cache, rt, c->cpd_blocks); }
-		if (w->cplan) { dev_launch(w->cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		if (w->in.cplan) { dev_launch(w->in.cplan, cache, t.in_off, t.in_len, stage, t.out_off, t.out_cap, t.ulen, t.ustat); }
 		if (d_block_crc && w->m) { crc_pass(c, w->m, nullptr, t.src, t.clen, t.cum, t.ucrc); }
 		{ KernelTimer k(c, "rs_layout_kernel"); launch_resize_layout(c->stream, w->n_res, w->nbt, w->shift, packed_len, new_cap, d_packed, stage, cache, d_block_first, d_block_off,
 		                                                             d_res_len, d_want_len, d_block_crc, rt, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_res_status); }
@@ -432,17 +459,19 @@ MSCompStatus mscomp_amd_writer_resize(mscomp_amd_writer* w, const uint8_t* d_pac
 }
 
 // ---- block splicers (include/mscomp_amd.h; kernels: splice.hip, the move in blocks.hip) ----
-// A splicer holds one column -- the address of every new row's stored bytes -- and the graph of its call. The sources are read on the host
-// and go into the kernel arguments by value, so every field of a view is part of the graph's key.
+// A splicer holds one column -- the address of every new row's stored bytes -- and the graphs of its calls, keyed by every field of the
+// views (view_args).
+#pragma GCC visibility push(hidden)                     // (what the creates instantiate over the object -- std::unique_ptr's destructor -- is no export of the library)
 struct mscomp_amd_splicer {
 	mscomp_amd_ctx* ctx = nullptr;
 	uint32_t shift = 0, n_src = 0, n_pick = 0, nbt = 0;    // block_size = 1 << shift; nbt = n_blocks_table of the NEW container
 	uint32_t n_ext = 0;                                    // (a splicer made for extents: n_pick is its n_res)
 	bool extents = false;                                  // made by mscomp_amd_splicer_create_extents: the scratch holds a SpliceExtTab
-	mscomp_amd_plan run, xrun;                             // (splice and splice_extents keep separate graphs)
+	GraphRun<40> run; GraphRun<41> xrun;                   // splice, splice_extents: four views, and eight or nine words
 	DevBuf addr;                                           // u64 x nbt; a splicer made for extents: SpliceExtTab, the address column first
 	SpliceExtTab t{};
 };
+#pragma GCC visibility pop
 static_assert(sizeof(mscomp_amd_blocks_view) == sizeof(SpliceView) && sizeof(SpliceView) == 8 * sizeof(void*), "a view is eight words of the graph's key");
 static_assert(SX_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header states");
 
@@ -459,7 +488,7 @@ static MSCompStatus splicer_create(mscomp_amd_ctx* c, uint32_t block_size, uint3
                                    uint32_t flags, mscomp_amd_splicer** out)
 {
 	*out = nullptr;
-	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
+	if (!c || flags || !block_size_ok(block_size)) { return MSCOMP_ARG_ERROR; }
 	if (n_src == 0 || n_src > MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_pick) || !count_ok(n_ext) || !count_ok(n_blocks_table)) { return MSCOMP_ARG_ERROR; }
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
@@ -467,7 +496,6 @@ static MSCompStatus splicer_create(mscomp_amd_ctx* c, uint32_t block_size, uint3
 	if (!s) { return MSCOMP_MEM_ERROR; }
 	s->ctx = c; s->shift = (uint32_t)__builtin_ctz(block_size); s->n_src = n_src; s->n_pick = (uint32_t)n_pick; s->nbt = (uint32_t)n_blocks_table;
 	s->n_ext = (uint32_t)n_ext; s->extents = extents;
-	s->run.ctx = s->xrun.ctx = c; s->run.n_units = s->xrun.n_units = 1;   // (an empty pick list writes an empty container: it replays too)
 	const size_t bytes = extents ? splice_ext_tab(s->t, nullptr, n_blocks_table, n_ext) : 8 * (size_t)n_blocks_table;
 	if (!s->addr.reserve(bytes + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	if (extents) { splice_ext_tab(s->t, s->addr.p, n_blocks_table, n_ext); }
@@ -489,25 +517,13 @@ MSCompStatus mscomp_amd_splicer_create_extents(mscomp_amd_ctx* c, uint32_t block
 	return splicer_create(c, block_size, n_src, n_res, true, n_ext, n_blocks_table, flags, out);
 }
 
-void mscomp_amd_splicer_destroy(mscomp_amd_splicer* s)
-{
-	if (!s) { return; }
-	DeviceGuard g(s->ctx->device);
-	(void)hipStreamSynchronize(s->ctx->stream);
-	s->addr.release();
-	delete s;                                              // (run gives up its graph)
-}
+void mscomp_amd_splicer_destroy(mscomp_amd_splicer* s) { destroy_object(s, [s] { s->addr.release(); }); }
 
-// the views of a call as the kernels take them; false: a view with a null table, or without checksums where the new container gets them
-static bool splice_views(const mscomp_amd_splicer* s, const mscomp_amd_blocks_view* src, bool with_crc, SpliceSrc& k)
+// the views of a splicer's call; false: a view pack_views refuses, or without checksums where the new container gets them
+static bool splice_views(const mscomp_amd_splicer* s, const mscomp_amd_blocks_view* src, bool want_crc, SpliceSrc& k)
 {
-	for (uint32_t i = 0; i < s->n_src; ++i) {
-		const mscomp_amd_blocks_view& v = src[i];
-		if (v.n_res && (!v.d_block_first || !v.d_block_off || !v.d_res_len || (v.packed_len && !v.d_packed))) { return false; }
-		if (with_crc && !v.d_block_crc) { return false; }
-		k.v[i] = { v.d_packed, v.packed_len, v.d_block_first, v.d_block_off, v.d_res_len, with_crc ? v.d_block_crc : nullptr, v.n_res, v.n_blocks_table };
-	}
-	return true;
+	bool with_crc = false;
+	return pack_views(src, s->n_src, want_crc, k.v, with_crc) && with_crc == want_crc;
 }
 
 MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* s, const mscomp_amd_blocks_view* src, const uint64_t* d_pick, uint8_t* d_new_packed, uint64_t new_cap,
@@ -520,12 +536,10 @@ MSCompStatus mscomp_amd_splicer_splice(mscomp_amd_splicer* s, const mscomp_amd_b
 	mscomp_amd_ctx* c = s->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	const void* args[40] = {};
-	memcpy(args, &k, sizeof k);
-	const void* rest[8] = { d_pick, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_status };
-	memcpy(args + 32, rest, sizeof rest);
+	const void* args[40];
+	view_args(args, k.v, { d_pick, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_status });
 	u64* addr = static_cast<u64*>(s->addr.p);
-	return plan_run(&s->run, args, [&] {
+	return plan_run(s->run, c, args, [&] {
 		{ KernelTimer t(c, "sp_layout_kernel"); launch_splice_layout(c->stream, k, s->n_src, s->n_pick, s->nbt, s->shift, new_cap, d_pick, d_new_block_first, d_new_block_off,
 		                                                             d_new_block_crc, d_new_res_len, d_status, addr); }
 		{ KernelTimer t(c, "bk_move_kernel"); launch_blocks_move(c->stream, s->nbt, new_cap, d_new_block_off, addr, d_new_packed, c->cpd_blocks); }
@@ -544,12 +558,10 @@ MSCompStatus mscomp_amd_splicer_splice_extents(mscomp_amd_splicer* s, const msco
 	mscomp_amd_ctx* c = s->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	const void* args[41] = {};
-	memcpy(args, &k, sizeof k);
-	const void* rest[9] = { d_ext_first, d_ext, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc,
-	                        d_new_res_len, d_status };
-	memcpy(args + 32, rest, sizeof rest);
-	return plan_run(&s->xrun, args, [&] {
+	const void* args[41];
+	view_args(args, k.v, { d_ext_first, d_ext, d_new_packed, reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc,
+	                       d_new_res_len, d_status });
+	return plan_run(s->xrun, c, args, [&] {
 		{ KernelTimer t(c, "sx_extent_kernel"); launch_splice_extents(c->stream, k, s->n_src, s->n_pick, s->n_ext, s->nbt, s->shift, d_ext_first, d_ext, d_new_block_first,
 		                                                              d_new_block_off, d_new_res_len, d_status, s->t); }
 		if (s->nbt) {
@@ -562,17 +574,18 @@ MSCompStatus mscomp_amd_splicer_splice_extents(mscomp_amd_splicer* s, const msco
 }
 
 // ---- block dedupers (include/mscomp_amd.h; kernels: dedup.hip) ----
-// A deduper holds its tables -- sized by the bound of the resources alone -- and the graph of its call. The sources are read on the host
-// and go into the kernel arguments by value, as a splicer's.
+// A deduper holds its tables -- sized by the bound of the resources alone -- and the graph of its call, keyed as a splicer's.
+#pragma GCC visibility push(hidden)                     // (what the creates instantiate over the object -- std::unique_ptr's destructor -- is no export of the library)
 struct mscomp_amd_deduper {
 	mscomp_amd_ctx* ctx = nullptr;
 	uint32_t shift = 0, n_src = 0, n_res = 0, nbt = 0;     // block_size = 1 << shift; the bounds n_res_total and n_blocks_total
 	bool diff = false;                                     // made by mscomp_amd_deduper_create_diff: n_res is n_pair, nbt is n_blocks_new, the scratch holds a DiffTab
-	mscomp_amd_plan run;
+	GraphRun<37> run; GraphRun<24> frun;                   // dedup: four views, and five words; diff: two views, and eight
 	DevBuf tab;                                            // DedupTab, or DiffTab
 	DedupTab t{};
 	DiffTab f{};
 };
+#pragma GCC visibility pop
 static_assert(DF_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header states");
 
 // the columns of a deduper's tables from `base` on (n = n_res_total); returns where they end: from a null base, their bytes
@@ -590,14 +603,13 @@ MSCompStatus mscomp_amd_deduper_create(mscomp_amd_ctx* c, uint32_t block_size, u
 {
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
-	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
+	if (!c || flags || !block_size_ok(block_size)) { return MSCOMP_ARG_ERROR; }
 	if (n_src == 0 || n_src > MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_res_total) || !count_ok(n_blocks_total)) { return MSCOMP_ARG_ERROR; }
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
 	if (!d) { return MSCOMP_MEM_ERROR; }
 	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = n_src; d->n_res = (uint32_t)n_res_total; d->nbt = (uint32_t)n_blocks_total;
-	d->run.ctx = c; d->run.n_units = 1;                    // (a call without resources writes its counts: it replays too)
 	if (!d->tab.reserve(dedup_tab(d->t, nullptr, n_res_total) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	dedup_tab(d->t, d->tab.p, n_res_total);
 	*out = d.release();
@@ -616,58 +628,42 @@ MSCompStatus mscomp_amd_deduper_create_diff(mscomp_amd_ctx* c, uint32_t block_si
 {
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
-	if (!c || flags || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u))) { return MSCOMP_ARG_ERROR; }
+	if (!c || flags || !block_size_ok(block_size)) { return MSCOMP_ARG_ERROR; }
 	if (!count_ok(n_pair) || !count_ok(n_blocks_new)) { return MSCOMP_ARG_ERROR; }
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
 	if (!d) { return MSCOMP_MEM_ERROR; }
 	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = 2; d->n_res = (uint32_t)n_pair; d->nbt = (uint32_t)n_blocks_new; d->diff = true;
-	d->run.ctx = c; d->run.n_units = 1;                    // (a call without pairs writes its counts: it replays too)
 	if (!d->tab.reserve(diff_tab(d->f, nullptr, n_pair, n_blocks_new) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	diff_tab(d->f, d->tab.p, n_pair, n_blocks_new);
 	*out = d.release();
 	return MSCOMP_OK;
 }
 
-void mscomp_amd_deduper_destroy(mscomp_amd_deduper* d)
-{
-	if (!d) { return; }
-	DeviceGuard g(d->ctx->device);
-	(void)hipStreamSynchronize(d->ctx->stream);
-	d->tab.release();
-	delete d;                                              // (run gives up its graph)
-}
+void mscomp_amd_deduper_destroy(mscomp_amd_deduper* d) { destroy_object(d, [d] { d->tab.release(); }); }
 
 MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* src, uint64_t* d_rep, uint64_t* d_new_index, uint64_t* d_pick,
                                       uint64_t* d_count, int32_t* d_status)
 {
 	if (!d || d->diff || !src || !d_count) { return MSCOMP_ARG_ERROR; }
 	SpliceSrc k{};
+	bool with_crc = false;                                 // the checksums are used only if every view has them
+	if (!pack_views(src, d->n_src, true, k.v, with_crc)) { return MSCOMP_ARG_ERROR; }
 	uint64_t n = 0, rows = 0;                              // (at most four terms below 2^64 / 4 each once checked: no overflow)
-	bool with_crc = true;
 	for (uint32_t i = 0; i < d->n_src; ++i) {
-		const mscomp_amd_blocks_view& v = src[i];
-		if (v.n_res && (!v.d_block_first || !v.d_block_off || !v.d_res_len || (v.packed_len && !v.d_packed))) { return MSCOMP_ARG_ERROR; }
-		if (v.n_res > d->n_res || v.n_blocks_table > d->nbt) { return MSCOMP_ARG_ERROR; }
-		n += v.n_res; rows += v.n_blocks_table;
-		with_crc = with_crc && v.d_block_crc;
+		if (src[i].n_res > d->n_res || src[i].n_blocks_table > d->nbt) { return MSCOMP_ARG_ERROR; }
+		n += src[i].n_res; rows += src[i].n_blocks_table;
 	}
 	if (n > d->n_res || rows > d->nbt) { return MSCOMP_ARG_ERROR; }
 	if (n && (!d_rep || !d_new_index || !d_pick || !d_status)) { return MSCOMP_ARG_ERROR; }
-	for (uint32_t i = 0; i < d->n_src; ++i) {
-		const mscomp_amd_blocks_view& v = src[i];
-		k.v[i] = { v.d_packed, v.packed_len, v.d_block_first, v.d_block_off, v.d_res_len, with_crc ? v.d_block_crc : nullptr, v.n_res, v.n_blocks_table };
-	}
 	mscomp_amd_ctx* c = d->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	const void* args[40] = {};
-	memcpy(args, &k, sizeof k);
-	const void* rest[5] = { d_rep, d_new_index, d_pick, d_count, d_status };
-	memcpy(args + 32, rest, sizeof rest);
+	const void* args[37];
+	view_args(args, k.v, { d_rep, d_new_index, d_pick, d_count, d_status });
 	const uint32_t N = (uint32_t)n;
-	return plan_run(&d->run, args, [&] {
+	return plan_run(d->run, c, args, [&] {
 		{ KernelTimer t(c, "dd_judge"); launch_dedup_judge(c->stream, k, N, d->n_res, d->nbt, d->shift, d->t, d_status, c->crc_blocks); }
 		{ KernelTimer t(c, "dd_keys"); launch_dedup_keys(c->stream, k, N, d->n_res, d->nbt, with_crc, d->t, d_status, c->crc_blocks); }
 		{ KernelTimer t(c, "dd_confirm_kernel"); launch_dedup_confirm(c->stream, k, N, d->n_res, d->nbt, d->shift, with_crc, d->t, c->cpd_blocks); }
@@ -683,22 +679,17 @@ MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* d, const mscomp_amd_blo
 {
 	if (!d || !d->diff || !base || !next || !d_count) { return MSCOMP_ARG_ERROR; }
 	if (d->n_res && (!d_pair || !d_delta_ext_first || !d_patch_ext_first || !d_changed || !d_status || (d->nbt && (!d_delta_ext || !d_patch_ext)))) { return MSCOMP_ARG_ERROR; }
-	const bool with_crc = base->d_block_crc && next->d_block_crc;
+	const mscomp_amd_blocks_view src[2] = { *base, *next };
 	SpliceView v[2];
-	for (uint32_t i = 0; i < 2u; ++i) {
-		const mscomp_amd_blocks_view& s = i ? *next : *base;
-		if (s.n_res && (!s.d_block_first || !s.d_block_off || !s.d_res_len || (s.packed_len && !s.d_packed))) { return MSCOMP_ARG_ERROR; }
-		v[i] = { s.d_packed, s.packed_len, s.d_block_first, s.d_block_off, s.d_res_len, with_crc ? s.d_block_crc : nullptr, s.n_res, s.n_blocks_table };
-	}
+	bool with_crc = false;                                 // the checksums are used only if both views have them
+	if (!pack_views(src, 2, true, v, with_crc)) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_ctx* c = d->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	const void* args[24] = {};
-	memcpy(args, v, sizeof v);
-	const void* rest[8] = { d_pair, d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_changed, d_count, d_status };
-	memcpy(args + 16, rest, sizeof rest);
+	const void* args[24];
+	view_args(args, v, { d_pair, d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_changed, d_count, d_status });
 	const uint32_t n = d->n_res, m = d->nbt;
-	return plan_run(&d->run, args, [&] {
+	return plan_run(d->frun, c, args, [&] {
 		{ KernelTimer t(c, "df_seed_kernel"); launch_diff_seed(c->stream, v[0], v[1], n, m, d->shift, d_pair, d->f, d_status); }
 		if (n && m) {
 			{ KernelTimer t(c, "df_verdict_kernel"); launch_diff_verdicts(c->stream, v[0], v[1], n, m, d->shift, with_crc, d_pair, d->f, d_status, c->crc_blocks); }
@@ -719,9 +710,9 @@ struct mscomp_amd_transcoder {
 	MSCompFormat f1 = MSCOMP_NONE, f2 = MSCOMP_NONE;
 	TcDims d{};
 	uint32_t dm = 0, em = 0;                           // the units of the inner plans: groups_max G / B1, groups_max G / B2
-	mscomp_amd_plan* dplan = nullptr; mscomp_amd_plan* cplan = nullptr;   // (null when groups_max is 0)
-	mscomp_amd_plan run;
-	DevBuf tab, cache, stage;                          // TranscodeTab; groups_max slots of G bytes each
+	InnerPlans in;                                     // (plans: null when groups_max is 0; cache and staging area: groups_max slots of G bytes each)
+	GraphRun<12> run;
+	DevBuf tab;                                        // TranscodeTab
 	TranscodeTab t{};
 	bool ran = false;
 };
@@ -765,26 +756,15 @@ MSCompStatus mscomp_amd_transcoder_create(mscomp_amd_ctx* c, MSCompFormat format
 	std::unique_ptr<mscomp_amd_transcoder> x(new (std::nothrow) mscomp_amd_transcoder());
 	if (!x) { return MSCOMP_MEM_ERROR; }
 	x->ctx = c; x->f1 = format; x->f2 = new_format; x->d = d; x->dm = (uint32_t)dm; x->em = (uint32_t)em;
-	x->run.ctx = c; x->run.n_units = 1;                    // (a call without resources writes an empty container: it replays too)
-	MSCompStatus st = MSCOMP_OK;
-	if (!x->tab.reserve(transcode_tab(x->t, nullptr, d, dm, em) + 64) || (bytes && (!x->cache.reserve(bytes + 64) || !x->stage.reserve(bytes + 64)))) { st = MSCOMP_MEM_ERROR; }
-	if (st == MSCOMP_OK && dm) { st = mscomp_amd_plan_create_decompress_dev(c, format, dm, bytes, bytes, &x->dplan); }
-	if (st == MSCOMP_OK && em) { st = mscomp_amd_plan_create_compress_dev(c, new_format, em, bytes, new_block_size, &x->cplan); }   // (fixes the LZNT1 dictionary flavour)
-	if (st != MSCOMP_OK) { (void)hipGetLastError(); mscomp_amd_transcoder_destroy(x.release()); return st; }
+	const uint64_t slots = bytes ? bytes + 64 : 0;
+	const MSCompStatus st = x->in.create(c, x->tab, transcode_tab(x->t, nullptr, d, dm, em) + 64, slots, slots, bytes, format, dm, new_format, em, new_block_size);
+	if (st != MSCOMP_OK) { return st; }
 	transcode_tab(x->t, x->tab.p, d, dm, em);
 	*out = x.release();
 	return MSCOMP_OK;
 }
 
-void mscomp_amd_transcoder_destroy(mscomp_amd_transcoder* x)
-{
-	if (!x) { return; }
-	DeviceGuard g(x->ctx->device);
-	(void)hipStreamSynchronize(x->ctx->stream);
-	mscomp_amd_plan_destroy(x->dplan); mscomp_amd_plan_destroy(x->cplan);
-	x->tab.release(); x->cache.release(); x->stage.release();
-	delete x;                                              // (run gives up its graph)
-}
+void mscomp_amd_transcoder_destroy(mscomp_amd_transcoder* x) { destroy_object(x, [x] { x->in.destroy(); x->tab.release(); }); }
 
 // The call: rules 0-3 from the tables, the slots and both inner plans' units, the writer's decode-into-cache /
 // encode-into-staging sequence over them with the CRC passes, the new tables tiled over their rows, the move.
@@ -799,25 +779,23 @@ MSCompStatus mscomp_amd_transcoder_transcode(mscomp_amd_transcoder* x, const uin
 	mscomp_amd_ctx* c = x->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
-	if (x->dplan) { note_modes(x->dplan); x->dplan->ran = true; }
-	if (x->cplan) { x->cplan->ran = true; }
-	x->ran = true;
+	x->in.mark_ran(); x->ran = true;
 	const void* args[12] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_new_packed,
 	                         reinterpret_cast<const void*>((uintptr_t)new_cap), d_new_block_first, d_new_block_off, d_new_block_crc, d_status };
-	return plan_run(&x->run, args, [&] {
+	return plan_run(x->run, c, args, [&] {
 		const TcDims& d = x->d;
 		const TranscodeTab& t = x->t;
 		const bool with_crc = d_block_crc != nullptr;
-		uint8_t* cache = static_cast<uint8_t*>(x->cache.p); uint8_t* stage = static_cast<uint8_t*>(x->stage.p);
+		uint8_t* cache = static_cast<uint8_t*>(x->in.cache.p); uint8_t* stage = static_cast<uint8_t*>(x->in.stage.p);
 		{ KernelTimer k(c, "tc_res_kernel"); launch_tc_resources(c->stream, d, d_block_first, d_res_len, t); }
 		{ KernelTimer k(c, "tc_class_kernel"); launch_tc_classes(c->stream, d, d_packed, packed_len, d_block_first, d_block_off, d_res_len, with_crc, t); }
 		{ KernelTimer k(c, "tc_units"); launch_tc_units(c->stream, d, d_packed, cache, d_block_first, d_block_off, d_res_len, with_crc, t); }
 		// the worked groups: decoded (or copied) into the cache, held to their old checksums, encoded into the staging area, checksummed
-		if (x->dplan) { dev_launch(x->dplan, d_packed, t.d_in_off, t.d_in_len, cache, t.d_out_off, t.d_out_cap, t.d_ulen, t.d_ustat); }
+		if (x->in.dplan) { dev_launch(x->in.dplan, d_packed, t.d_in_off, t.d_in_len, cache, t.d_out_off, t.d_out_cap, t.d_ulen, t.d_ustat); }
 		{ KernelTimer k(c, "tc_gather_kernel"); launch_tc_gather(c->stream, d, cache, t, c->cpd_blocks); }
 		if (with_crc && x->dm) { crc_pass(c, x->dm, nullptr, t.d_src, t.d_clen, t.d_cum, t.d_crc); }   // (addresses as offsets from a null base)
 		{ KernelTimer k(c, "tc_judge_kernel"); launch_tc_judge(c->stream, d, d_block_crc, t); }
-		if (x->cplan) { dev_launch(x->cplan, nullptr, t.e_in_off, t.e_in_len, stage, t.e_out_off, t.e_out_cap, t.e_ulen, t.e_ustat); }
+		if (x->in.cplan) { dev_launch(x->in.cplan, nullptr, t.e_in_off, t.e_in_len, stage, t.e_out_off, t.e_out_cap, t.e_ulen, t.e_ustat); }
 		if (with_crc && x->em) { crc_pass(c, x->em, nullptr, t.e_src, t.e_clen, t.e_cum, t.e_crc); }
 		if (with_crc && d.mode == TC_JOIN) { KernelTimer k(c, "crc_foldruns_kernel"); launch_crc_fold_runs(c->stream, d.nbn, t.pfirst + d.n_res, d.s1, t.pjf, t.pdl, d_block_crc, t.pcrc); }
 		// the new tables and the bytes
@@ -850,18 +828,18 @@ int mscomp_amd_transcoder_counts(mscomp_amd_transcoder* x, uint32_t out[3])
 // ---- the scratch hooks' view of the objects above (api.hip: mscomp_amd_debug_scratch_*) ----
 extern "C++" mscomp_amd_ctx* msc::scratch_of_object(int kind, void* obj, std::vector<ScratchEnt>& v)
 {
-	const auto access = [&v](BlockAccess* a) { v.push_back(ScratchEnt{ "tab", &a->tab, false }); v.push_back(ScratchEnt{ "cache", &a->cache, false }); scratch_of_plan(a->dplan, 2, v); };
+	const auto access = [&v](BlockAccess* a) { v.push_back(ScratchEnt{ "tab", &a->tab, false }); v.push_back(ScratchEnt{ "cache", &a->in.cache, false }); scratch_of_plan(a->in.dplan, 2, v); };
 	switch (kind) {
 	case MSCOMP_AMD_SCRATCH_BLOCKS: {
 		mscomp_amd_blocks* b = static_cast<mscomp_amd_blocks*>(obj);
-		v.push_back(ScratchEnt{ "tab", &b->tab, false }); v.push_back(ScratchEnt{ "stage", &b->stage, false });
-		scratch_of_plan(b->cplan, 1, v); scratch_of_plan(b->dplan, 2, v);
+		v.push_back(ScratchEnt{ "tab", &b->tab, false }); v.push_back(ScratchEnt{ "stage", &b->in.stage, false });
+		scratch_of_plan(b->in.cplan, 1, v); scratch_of_plan(b->in.dplan, 2, v);
 		return b->ctx;
 	}
 	case MSCOMP_AMD_SCRATCH_READER: { mscomp_amd_reader* r = static_cast<mscomp_amd_reader*>(obj); access(r); return r->ctx; }
 	case MSCOMP_AMD_SCRATCH_WRITER: {
 		mscomp_amd_writer* w = static_cast<mscomp_amd_writer*>(obj);
-		access(w); v.push_back(ScratchEnt{ "stage", &w->stage, false }); scratch_of_plan(w->cplan, 1, v);
+		access(w); v.push_back(ScratchEnt{ "stage", &w->in.stage, false }); scratch_of_plan(w->in.cplan, 1, v);
 		return w->ctx;
 	}
 	case MSCOMP_AMD_SCRATCH_SPLICER: { mscomp_amd_splicer* s = static_cast<mscomp_amd_splicer*>(obj); v.push_back(ScratchEnt{ "addr", &s->addr, false }); return s->ctx; }
@@ -874,7 +852,7 @@ extern "C++" mscomp_amd_ctx* msc::scratch_of_object(int kind, void* obj, std::ve
 MSCompStatus mscomp_amd_res_crc_dev(mscomp_amd_ctx* c, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, const uint64_t* d_block_first,
                                     const uint64_t* d_res_len, const uint32_t* d_block_crc, uint32_t* d_res_crc, int32_t* d_status)
 {
-	if (!c || block_size < 4096u || block_size > 524288u || (block_size & (block_size - 1u)) || !count_ok(n_res) || !count_ok(n_blocks_table)) { return MSCOMP_ARG_ERROR; }
+	if (!c || !block_size_ok(block_size) || !count_ok(n_res) || !count_ok(n_blocks_table)) { return MSCOMP_ARG_ERROR; }
 	if (n_res && (!d_block_first || !d_res_len || !d_block_crc || !d_res_crc || !d_status)) { return MSCOMP_ARG_ERROR; }
 	if (n_res == 0) { return MSCOMP_OK; }                  // (nothing to report on)
 	DeviceGuard g(c->device);

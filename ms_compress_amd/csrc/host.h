@@ -37,6 +37,17 @@ struct ScratchEnt { const char* name; DevBuf* b; bool keeps; };
 
 struct ProfRec { const char* name; hipEvent_t a, b; };
 
+// The launch sequence of one call as a hipGraph (plan_run): captured on the call's second execution, replayed while its N argument words,
+// the context's scratch and the kernel switches stay where they were. Destroyed on the context's device, its stream idle.
+template <size_t N> struct GraphRun {
+	hipGraphExec_t exec = nullptr;
+	const void* args[N] = {};
+	uint64_t epoch = 0, mode = 0;                      // mscomp_amd_ctx::epoch and g_mode_epoch when `exec` was captured
+	uint32_t executions = 0;
+	bool never = false;                                // never replays: a call with nothing to report on; a one-shot plan (its buffer addresses change: it would be re-captured every time)
+	~GraphRun() { if (exec) { (void)hipGraphExecDestroy(exec); } }
+};
+
 } // namespace msc
 #pragma GCC visibility pop
 
@@ -103,7 +114,6 @@ struct mscomp_amd_plan {
 	uint64_t total_in = 0, max_unit = 0;               // (max_unit of a compress dev plan: the largest unit it takes)
 	bool lznt1_sa = false;                             // LZNT1: the suffix-array dictionary flavour -- fixed when the plan is created: a plan never changes its bytes under a running caller
 	bool matches_ready = false;                        // the caller has run the links + find kernels of this execution itself, range by range (the pipelined one-shot call): compress_launch skips them once
-	bool no_graph = false;                             // one-shot plans run with changing buffer addresses: a captured graph would be re-captured every time
 	msc::DevBuf tables;                                // in_off | in_len | out_off | out_cap | chunk_prefix; dev plans: what their table pass writes (reserve_dev_tables)
 	msc::DevBuf tokpre;                                // decompression by tokens (host plans): first token slot | first candidate slot | first token-scratch slot of every unit (n_units + 1 u64 each)
 	uint32_t xhc_slots = 0;                            // candidate chunk slots of the batch
@@ -118,15 +128,10 @@ struct mscomp_amd_plan {
 	msc::BatchTables bt{};
 	msc::u64* tok_prefix = nullptr; msc::u64* cand_prefix = nullptr; msc::u64* scr_prefix = nullptr;
 	uint32_t* reject = nullptr;
-	// the plan's launch sequence as a hipGraph (plan_run): captured on the plan's second execution, replayed while the
-	// arguments and the scratch buffers stay where they were
-	hipGraphExec_t gexec = nullptr;
-	const void* g_args[41] = {};                       // (api.hip: a host plan's four pointers, a dev plan's eight, a size dev plan's seven; blockobj.hip: a block container's eight and eleven; a block reader's twelve; a block writer's sixteen, and fourteen for its resize; a block splicer's forty: four views of eight words, and eight -- forty-one for its splice by extents; a block deduper's thirty-seven: the views, and five -- twenty-four for its diff: two views, and eight)
-	uint64_t g_epoch = 0, g_mode = 0;
-	uint32_t executions = 0;
+	msc::GraphRun<8> run;                              // the graph of the plan's execute call (a dev plan's eight pointers are the most an execute call takes)
 	bool ran = false;                                  // executed at least once (mscomp_amd_debug_plan_paths: a dev plan's counts are those of its last execution)
 	// (on the plan's device, its stream idle. mscomp_amd_plan_destroy hands `tables` to the context's pool first)
-	~mscomp_amd_plan() { if (gexec) { (void)hipGraphExecDestroy(gexec); } tables.release(); tokpre.release(); lzg_tab.release(); xps_tab.release(); }
+	~mscomp_amd_plan() { tables.release(); tokpre.release(); lzg_tab.release(); xps_tab.release(); }
 };
 
 #pragma GCC visibility push(hidden)
@@ -160,37 +165,35 @@ void scratch_of_plan(mscomp_amd_plan* p, int owner, std::vector<ScratchEnt>& v);
 // defined in blockobj.hip: the buffers of a block object (kind: MSCOMP_AMD_SCRATCH_BLOCKS ..) and its context; null: no such object
 mscomp_amd_ctx* scratch_of_object(int kind, void* obj, std::vector<ScratchEnt>& v);
 
-// One execution of a plan: its launches, given as `launch`. A plan that is executed repeatedly replays them as one hipGraph (the gaps between
-// the 4-9 launches are ~3 % of an LZNT1 pass): captured on the second execution and again whenever a pointer (args), the ctx scratch or a
-// kernel switch moved. Plain launches instead: on the first execution (one-time function attributes are set there), while profiling (the
-// per-kernel events are not part of a graph), with MSCOMP_AMD_NO_GRAPH, for no_graph plans, and while the caller captures the ctx stream (the
-// launches then go into the caller's graph; a stream whose capture state cannot be read counts as captured). Only executions that may replay
-// are counted.
+// One execution of a call: its launches, given as `launch`. A call that is executed repeatedly replays them as one hipGraph (the gaps between
+// the 4-9 launches are ~3 % of an LZNT1 pass): captured in the call's record `r` on the second execution and again whenever a word of
+// `args`, the ctx scratch or a kernel switch moved. Plain launches instead: on the first execution (one-time function attributes are set
+// there), while profiling (the per-kernel events are not part of a graph), with MSCOMP_AMD_NO_GRAPH, for records that never replay, and while
+// the caller captures the ctx stream (the launches then go into the caller's graph; a stream whose capture state cannot be read counts as
+// captured). Only executions that may replay are counted.
 extern "C++" template <class Launch, size_t N>
-static MSCompStatus plan_run(mscomp_amd_plan* p, const void* const (&args)[N], const Launch& launch)
+static MSCompStatus plan_run(GraphRun<N>& r, mscomp_amd_ctx* c, const void* const (&args)[N], const Launch& launch)
 {
-	static_assert(N <= sizeof p->g_args / sizeof p->g_args[0], "g_args holds the arguments of every caller");
-	mscomp_amd_ctx* c = p->ctx;
 	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
 	if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
 	static const bool no_graph = getenv("MSCOMP_AMD_NO_GRAPH") != nullptr;
-	if (cs == hipStreamCaptureStatusNone && !no_graph && !p->no_graph && !c->profiling && p->n_units && ++p->executions >= 2) {
+	if (cs == hipStreamCaptureStatusNone && !no_graph && !r.never && !c->profiling && ++r.executions >= 2) {
 		const uint64_t mode_now = g_mode_epoch.load(std::memory_order_acquire);
-		const bool same = p->gexec && p->g_epoch == c->epoch && p->g_mode == mode_now && memcmp(p->g_args, args, sizeof args) == 0;
+		const bool same = r.exec && r.epoch == c->epoch && r.mode == mode_now && memcmp(r.args, args, sizeof args) == 0;
 		if (!same) {
-			if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
+			if (r.exec) { (void)hipGraphExecDestroy(r.exec); r.exec = nullptr; }
 			hipGraph_t graph = nullptr;
 			if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
 				launch();
 				const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
-				if (ee == hipSuccess && graph && hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0) == hipSuccess) {
-					p->g_epoch = c->epoch; p->g_mode = mode_now; memcpy(p->g_args, args, sizeof args);
-				} else { p->gexec = nullptr; }
+				if (ee == hipSuccess && graph && hipGraphInstantiate(&r.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+					r.epoch = c->epoch; r.mode = mode_now; memcpy(r.args, args, sizeof args);
+				} else { r.exec = nullptr; }
 				if (graph) { (void)hipGraphDestroy(graph); }
 			}
 			(void)hipGetLastError();
 		}
-		if (p->gexec) { return hipGraphLaunch(p->gexec, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
+		if (r.exec) { return hipGraphLaunch(r.exec, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
 	}
 	launch();
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;

@@ -329,6 +329,62 @@ def test_repeats_and_arguments_changed(rigs, oracle, fmt):
     rd.close()
 
 
+@pytest.mark.parametrize("fmt", ["lznt1", "xpress_huff"])
+def test_replay_after_the_context_scratch_moved(fmt):
+    """a reader's graph is keyed by the context's scratch as a plan's is: three reads (plain, captured, replayed), then a compress dev plan
+    of a few hundred 64 KiB units on the same context, which grows the context's scratch, then two more reads (captured again, replayed) --
+    all five give the slices of the original bytes"""
+    import torch
+    import ms_compress_amd as m
+    f, B = FMTS[fmt], 4096
+    text = (b"the quick brown fox jumps over the lazy dog %d " * 400) % tuple(range(400))
+    bufs = [b"", text[:5000], text[5000: 5000 + 3 * B + 17]]
+    assert len(bufs[2]) == 3 * B + 17
+    s = torch.cuda.Stream()
+    ctx = m.Context(stream=s)
+    with torch.cuda.stream(s):
+        rig = Rig(ctx, f, B, bufs)
+        dev = rig.dev
+        reqs = [(1, 100, 4500), (2, B - 7, 2 * B + 9), (2, 3 * B, ALL)]
+        caps = [3 * B] * 3
+        ooff, room = rig.layout(caps)
+        rd = m.BlockReader(ctx, f, B, rig.n, rig.nbt, 3, rig.budget(reqs))
+        d_req, d_ooff, d_ocap = _d64(np.array(reqs, dtype=np.uint64).reshape(-1), dev), _d64(ooff, dev), _d64(caps, dev)
+        d_olen, d_st = torch.zeros(3, dtype=torch.int64, device=dev), torch.zeros(3, dtype=torch.int32, device=dev)
+        d_out = torch.empty(room, dtype=torch.uint8, device=dev)
+        image = np.full(room, FILL, dtype=np.uint8)
+        for q, want in enumerate(_slices(rig, reqs)):
+            assert len(want) == (4500, 2 * B + 9, 17)[q]
+            image[ooff[q]: ooff[q] + len(want)] = np.frombuffer(want, dtype=np.uint8)
+
+        def run():
+            d_out.fill_(FILL); d_olen.fill_(-1); d_st.fill_(77)
+            rd.read(rig.d_packed, rig.d_first, rig.d_boff, rig.d_len, d_req, d_out, d_ooff, d_ocap, d_olen, d_st, d_block_crc=rig.d_crc, packed_len=rig.plen)
+            s.synchronize()
+            assert d_st.cpu().tolist() == [0] * 3 and d_olen.cpu().tolist() == [4500, 2 * B + 9, 17]
+            assert (d_out.cpu().numpy() == image).all()
+        for _ in range(3):
+            run()
+        before = m.api.scratch_report(ctx, 0)
+        n, U = 300, 65536
+        big = m.CompressDevPlan(ctx, f, n, n * U, U)
+        cap = m.max_compressed_size(f, U)
+        d_in = torch.from_numpy(np.resize(np.frombuffer(text, dtype=np.uint8), n * U)).to(dev)
+        d_big = torch.empty(n * cap, dtype=torch.uint8, device=dev)
+        d_blen, d_bst = torch.zeros(n, dtype=torch.int64, device=dev), torch.full((n,), 77, dtype=torch.int32, device=dev)
+        big.execute(d_in, _d64(np.arange(n) * U, dev), _d64([U] * n, dev), d_big, _d64(np.arange(n) * cap, dev), _d64([cap] * n, dev), d_blen, d_bst)
+        s.synchronize()
+        assert not d_bst.cpu().numpy().any()
+        after = m.api.scratch_report(ctx, 0)
+        assert any(0 < before[k][1] < after[k][1] for k in before), "the larger plan moved none of the context's buffers"
+        for _ in range(2):
+            run()
+    big.close()
+    rd.close()
+    rig.close()
+    ctx.close()
+
+
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_compress_crc_and_read_in_one_captured_graph(oracle, fmt):
     """the container's compress and crc and the reader's read captured together, the reader's first execution inside the capture, then
