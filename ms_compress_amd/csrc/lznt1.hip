@@ -179,6 +179,10 @@ __device__ __forceinline__ uint32_t lz_diff_bits_s2(uint32_t xz, uint32_t xw, ui
 {
 	return min3u(ffbl_raw(xz) | 64u, ffbl_raw(xw) | 96u, capbits);
 }
+// Bit i (< 64) of a wave-uniform mask as 0 / 1 in a scalar register: no 64-bit `1 << i`, and the asm keeps the test after the shift a 32-bit one
+__device__ __forceinline__ uint32_t lz_bit64(u64 m, uint32_t i) { u64 t; asm("s_lshr_b64 %0, %1, %2" : "=s"(t) : "s"(m), "s"(i) : "scc"); return (uint32_t)t & 1u; }
+// 8 len + 8 on the scalar unit in one instruction
+__device__ __forceinline__ uint32_t lz_need_bits(uint32_t len) { uint32_t r; asm("s_lshl3_add_u32 %0, %1, 8" : "=s"(r) : "s"(len) : "scc"); return r; }
 // One window (64 positions, lane = position) of the lazy parse of a chunk: Find for the positions at / after the parse
 // position `entry` (the 4 oldest candidates per lane, the rest on demand), greedy walk, token mask. Returns the parse
 // position after the window; key = (len << 12) | (4095 - q) of this lane's match (valid where matchmask is set),
@@ -309,11 +313,14 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 		u64 rest; asm("s_lshr_b64 %0, %1, %2" : "=s"(rest) : "s"(un | mm), "s"(rel) : "scc");
 		mp = rest ? rel + ctz64(rest) : wn;
 	}
-	while (mp < wn) {
-		uint32_t st;
-		matchmask = sgpr64(matchmask);
+	// The loop has ONE exit, at its bottom, and the event is a plain `if` inside it: the finishing step holds a divergent branch, so this region's
+	// control flow is structurized, and every `break` of a uniform loop becomes a 64-bit flag that is set, selected, ANDed with exec and branched on
+	// (four scalar instructions for each; `asm goto`, which would make the stop a branch target, is dropped by this compiler's back end without a
+	// word). Conditions that cross a join are kept as 32-bit scalars, pinned by an empty asm, for the same reason.
+	if (mp < wn) do {
 		// v_readlane needs 4 wait states after the write of its lane select (mp): on the loop edge the five scalar
-		// instructions in between provide them, on entry the s_nop does.
+		// instructions in between provide them, on entry the s_nop does. The walk leaves on a stop that is pending (mp < wn), which the
+		// whole wave resolves, or behind the window (mp >= wn): no flag, mp tells.
 		asm volatile(
 			"s_nop 3\n\t"
 			"1:\n\t"
@@ -323,22 +330,17 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 			"v_readlane_b32 %[mp], %[J], %[mp]\n\t"
 			"s_cmp_lt_u32 %[mp], %[wn]\n\t"
 			"s_cbranch_scc1 1b\n\t"
-			"s_mov_b32 %[st], 0\n\t"
-			"s_branch 4f\n\t"
 			"3:\n\t"
-			"s_mov_b32 %[st], 1\n\t"
-			"4:\n\t"
-			: [mp] "+s"(mp), [mk] "+s"(matchmask), [st] "=&s"(st)
+			: [mp] "+s"(mp), [mk] "+s"(matchmask)
 			: [pend] "s"(pend), [wn] "s"(wn), [J] "v"(J)
 			: "scc");
-		if (st == 0) { break; }
-		{
+		if (mp < wn) {
 			const uint32_t sL = (uint32_t)__builtin_amdgcn_readlane((int)s, (int)mp);
 			const uint32_t maxL = (uint32_t)__builtin_amdgcn_readlane((int)maxlen, (int)mp);
 			const uint32_t pL = wbase + mp;
 			uint32_t kbest = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)mp);
-			bool fin = (un >> mp) & (u64)1;
-			if ((lp >> mp) & (u64)1) {
+			uint32_t fin = 1u;                                         // (a stop that is not long-pending is unresolved)
+			if (lz_bit64(lp, mp)) {
 				// long-pending: extend its candidates that reached 16 bytes, oldest first, with the whole wave; the first one that reaches
 				// max_len cannot be beaten (an older one would have to be longer). Then it is unresolved only if a fifth candidate exists
 				// and max_len was not reached.
@@ -354,68 +356,102 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 						if (l == maxL) { break; }
 					}
 				}
-				fin = ((un >> mp) & (u64)1) && kbest < (maxL << 12);   // (un's bit: the provisional key is below max_len, so it is `five`'s)
+				fin = kbest < (maxL << 12) ? lz_bit64(un, mp) : 0u;    // (un's bit: the provisional key is below max_len, so it is `five`'s)
 #ifdef LZ4_PROFILE_EVENTS
 				if (lane == 0) { atomicAdd(&g_lz4_prof[LZ4_NEV + 2], 1ull); atomicAdd(&g_lz4_prof[LZ4_NEV + 3], (unsigned long long)nst); }
 #endif
 			}
+			asm volatile("" : "+s"(fin));
 			if (fin) {
 				// finish position wbase+mp: the candidates after the first LZ_SELF of its bucket, oldest first, 64 per step
 				// (the own-entry rule again: the candidates of a step are the lanes below the first entry that is not < pL, and the step that holds
 				// pL's own entry is the last. fin implies a fifth candidate, so the own entry lies at or behind `base`, inside the array.)
 				// Two stages: every step compares the first 8 bytes; bytes 8..15 and the tail beyond 16 only in a step in which a candidate
-				// agreed on all of them and max_len allows more (a step holds few candidates that do: tools/dev/lz_stage_study.c).
+				// agreed on all of them (a step holds few candidates that do: tools/dev/lz_stage_study.c).
 				const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)o0, (int)mp), a1 = (uint32_t)__builtin_amdgcn_readlane((int)o1, (int)mp);
 #ifdef LZ4_PROFILE_EVENTS
 				uint32_t nsteps = 0, ntail = 0;
 #endif
-				const uint32_t capL = (maxL < 16u ? maxL : 16u) << 3, cap1L = (maxL < LZ_S1 ? maxL : LZ_S1) << 3;
-				for (uint32_t base = sL + LZ_SELF; ; base += 64u) {
+				const uint32_t cap1L = (maxL < LZ_S1 ? maxL : LZ_S1) << 3;
+				// The step's candidates are younger than the best's, and the older one wins on equal length: only a candidate STRICTLY longer than the
+				// best (and at least 3 bytes long: a best below 3 is "no match" downstream, which sub-3 key it holds is never read) can change kbest.
+				// `need` is that length in bits, a function of kbest: computed here and again only behind a winner.
+				// (kbest >> 12) < maxL here, so need <= 8 maxL: a candidate that reached max_len always wins.
+				uint32_t need = kbest >> 12; need = lz_need_bits(need > 2u ? need : 2u);
+				uint32_t base = sL + LZ_SELF;
+				u64 go;                                                // all-ones: another step
+				do {
 					const uint32_t qq = s_bucket[base + lane];         // unconditional load (past the array's end it reads the table: behind the own entry)
 					const u64 lt = __builtin_amdgcn_ballot_w64(qq < pL);
 					const u64 vmask = lt & ~(lt + 1u);                 // the lanes below the first one at or beyond pL's own entry
 					const LzS1 c1 = lz_ld_s1(s_data, qq);
 					uint32_t l2 = lz_diff_bits_s1(c1.x ^ a0, c1.y ^ a1, cap1L);   // in bits
 					uint32_t it = 0;
-					// (max_len is tested afresh in every step, which the empty asm enforces: hoisted out of the loop, "max_len > 8" and "max_len > 16" become
-					// two 64-bit masks that live across it, four more scalar registers -- see the note on blocks per CU at lznt1_chunk4_kernel)
-					uint32_t mL = maxL; asm volatile("" : "+s"(mL));
-					if (mL > LZ_S1 && (__builtin_amdgcn_ballot_w64(l2 >= 8u * LZ_S1) & vmask)) {
+					// (no test of max_len > 8 in front of the second stage: l2 is capped at 8 min(max_len, 8), so below 8 no candidate reaches 64 bits, and
+					// at exactly 8 the second stage's cap is 64 too and it hands every candidate the 64 it came with. A max_len below 9 exists only in the last
+					// 8 bytes of a chunk; the test was three scalar instructions of every step.)
+					if (__builtin_amdgcn_ballot_w64(l2 >= 8u * LZ_S1) & vmask) {
 						// (a candidate that stopped inside the first stage keeps its bits)
+						// (max_len is read afresh here, which the empty asm enforces: hoisted out of the loop, "max_len > 16" becomes a 64-bit mask that
+						// lives across it and the second stage's cap another register -- see the note on blocks per CU at lznt1_chunk4_kernel)
+						uint32_t mL = maxL; asm volatile("" : "+s"(mL));
 						const LzS2 a = lz_ld_s2(s_data, pL), c = lz_ld_s2(s_data, qq);
-						const uint32_t l3 = lz_diff_bits_s2(c.z ^ a.z, c.w ^ a.w, capL);
+						const uint32_t l3 = lz_diff_bits_s2(c.z ^ a.z, c.w ^ a.w, (mL < 16u ? mL : 16u) << 3);
 						l2 = l2 >= 8u * LZ_S1 ? l3 : l2;
 						if (mL > 16u && l2 >= 128u && ((vmask >> lane) & (u64)1)) { const uint32_t l = lz_lcp_tail(s_data, qq, pL, maxL, it); l2 = (l < maxL ? l : maxL) << 3; }
 					}
-					// The step's candidates are younger than the best's, and the older one wins on equal length: only a candidate STRICTLY longer than the
-					// best (and at least 3 bytes long: a best below 3 is "no match" downstream, which sub-3 key it holds is never read) can change kbest.
-					// One compare and a ballot find those lanes, the winners; in three steps of four there are none and nothing is reduced
-					// (tools/dev/lz_best_study.c). (kbest >> 12) < maxL here, so need <= 8 maxL: a candidate that reached max_len always wins.
-					uint32_t need = (kbest >> 12) + 1u; need = (need > 3u ? need : 3u) << 3;    // in bits, on the scalar unit
+					// One compare and a ballot find the winners; in three steps of four there are none and nothing is reduced (tools/dev/lz_best_study.c).
+					go = lt;                                           // (some entry not < pL: all older candidates seen)
 					const u64 win = __builtin_amdgcn_ballot_w64(l2 >= need) & vmask;
 					if (win) {
 						// longest, then oldest (older entries hold the larger 4095 - q); every winner's key is above the old kbest
 						uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(win));
 						kbest = wave_max_u32(k2);
+						const uint32_t len = kbest >> 12;               // >= 3
+						need = lz_need_bits(len);
+						go = len == maxL ? (u64)0 : go;                // max_len reached: nothing can beat it
 					}
 #ifdef LZ4_PROFILE_EVENTS
 					++nsteps; ntail += wave_max_u32(it);
 #endif
-					if ((kbest >> 12) == maxL || ~lt) { break; }     // max_len reached / all older candidates seen
-				}
+					base += 64u;
+					asm volatile("" : "+s"(go));                       // (one 64-bit compare and one branch: left to itself the compiler rebuilds the two conditions as flags)
+				} while (go == ~(u64)0);
 #ifdef LZ4_PROFILE_EVENTS
 				if (lane == 0) { atomicAdd(&g_lz4_prof[LZ4_NEV], (unsigned long long)nsteps); atomicAdd(&g_lz4_prof[LZ4_NEV + 1], (unsigned long long)ntail); }
 #endif
 			}
-			if (lane == mp) { key = kbest; }
-			un = sgpr64(un & ~(((u64)1) << mp));
-			// literals before mp are settled; mp itself is now resolved: take its match, or step over it as a literal
-			uint32_t nxs = mp + 1u;
-			if ((kbest >> 12) >= 3u) { matchmask |= ((u64)1) << mp; nxs = mp + (kbest >> 12); }
-			const u64 rest = nxs < 64u ? (un | mm) >> nxs : (u64)0;
-			mp = (uint32_t)__builtin_amdgcn_readfirstlane((int)(nxs >= wn ? nxs : (rest ? nxs + ctz64(rest) : wn)));
+			// mp is resolved now, and the literals before it are settled: clear its bit of `un`, write its key back (v_writelane takes its lane from m0 where
+			// the value comes from a scalar register too), take its match or step over it as a literal, and go to the first stop at or after the
+			// next token start. A next start at or beyond wn needs no guard: the shift count wraps, s_ff1 of zero is -1, and whatever (0 .. 64) is
+			// added to it, mp stays >= wn, which is all the loop asks.
+			{
+				uint32_t t; u64 rs;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"      // (m0 is a reserved register to the compiler, which uses it nowhere in these kernels)
+				asm volatile(
+					"s_bitset0_b64 %[un], %[mp]\n\t"
+					"s_mov_b32 m0, %[mp]\n\t"
+					"s_lshr_b32 %[t], %[kb], 12\n\t"
+					"s_cmp_gt_u32 %[t], 2\n\t"
+					"s_cselect_b32 %[t], %[t], 1\n\t"
+					"s_cbranch_scc0 5f\n\t"
+					"s_bitset1_b64 %[mk], %[mp]\n\t"
+					"5:\n\t"
+					"v_writelane_b32 %[key], %[kb], m0\n\t"
+					"s_add_u32 %[mp], %[mp], %[t]\n\t"
+					"s_or_b64 %[rs], %[un], %[mm]\n\t"
+					"s_lshr_b64 %[rs], %[rs], %[mp]\n\t"
+					"s_ff1_i32_b64 %[t], %[rs]\n\t"
+					"s_min_u32 %[t], %[t], 64\n\t"
+					"s_add_u32 %[mp], %[mp], %[t]\n\t"
+					: [un] "+s"(un), [mk] "+s"(matchmask), [mp] "+s"(mp), [key] "+v"(key), [t] "=&s"(t), [rs] "=&s"(rs)
+					: [kb] "s"(kbest), [mm] "s"(mm)
+					: "scc", "m0");
+#pragma clang diagnostic pop
+			}
 		}
-	}
+	} while (mp < wn);
 	// tokens of the window = positions >= entry that no taken match covers: covered <=> the furthest end of the taken
 	// matches starting at or before me lies beyond me and I am not such a start myself
 	matchmask = sgpr64(matchmask);
@@ -665,7 +701,7 @@ static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: L
 // (Blocks per CU by the scalar registers: a SIMD has 800 and gives a wave its count rounded up to a multiple of 16, plus 16, so a CU admits
 // min(8, 800 / (ceil16(TotalSGPRs) + 16)) blocks of 256 threads: up to 80 registers 8 blocks, 81 to 96 SEVEN, 97 to 112 six -- while the compiler's own
 // occupancy figure says 8 up to 100. Rounds 7 to 14 took 96 for the limit of eight blocks and ran at seven (93 to 96 registers: 6.79 waves per busy
-// CU-cycle, 5.81 above 96; round 13 in profiles/HISTORY.md and its correction in round 15). Since round 15 the kernel uses 77 and runs at eight
+// CU-cycle, 5.81 above 96; round 13 in profiles/HISTORY.md and its correction in round 15). Since round 15 the kernel uses 77 (76 since round 17) and runs at eight
 // (7.76): lz_window keeps "candidate k reached 16 bytes" in the lanes instead of four 64-bit masks, and what sort and parse never read waits in the
 // lanes of one vector register (LZ4_PARK below). tests/test_lznt1_sgpr80.py holds all four instances at 80, without spills: an `amdgpu_num_sgpr`
 // limit gets there too, by spilling, which tests/test_lznt1_resources.py forbids.)
