@@ -1158,6 +1158,10 @@ int          mscomp_amd_debug_scratch_report(int kind, void* object, int byte, m
  * lanes x {add, exchange}, keys drawn from nkeys <= 2048 values) that were served out of order: 0 on gfx950;
  * 0xFFFFFFFF if the check could not run. */
 uint32_t     mscomp_amd_debug_lds_lane_order(mscomp_amd_ctx* ctx, uint32_t seed, uint32_t blocks, uint32_t rounds, uint32_t nkeys);
+/* Hardware self-check: the LZNT1 match compares hand v_alignbyte_b32 a byte address as its shift and rely on the instruction reading bits
+ * [1:0] of it alone. Returns the number of results (256 low bytes x 16 settings of the bits above them x 4 dword pairs x {vector, scalar}
+ * operand, the dwords drawn from seed) that differ from {hi, lo} >> 8 (operand & 3): 0 on gfx950; 0xFFFFFFFF if the check could not run. */
+uint32_t     mscomp_amd_debug_alignbyte(mscomp_amd_ctx* ctx, uint32_t seed);
 /* A device that serves them in another order is not refused: the two kernels then issue that atomic one lane at a time (the same bytes, a
  * slower sort; csrc/kernels.h). Test hook: 1 = run that order-independent form on every device, 0 = back to the default. Process-wide. */
 void         mscomp_amd_debug_set_serial_atomics(int on);

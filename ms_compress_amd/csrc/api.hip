@@ -1205,6 +1205,16 @@ uint32_t mscomp_amd_debug_lds_lane_order(mscomp_amd_ctx* c, uint32_t seed, uint3
 	return run_lds_lane_order_check(c->stream, seed, blocks, rounds, nkeys, static_cast<uint32_t*>(c->slot_size.p));
 }
 
+// Hardware self-check (see util.hip): results of v_alignbyte_b32, over 256 low bytes x 16 settings of the bits above them x 4 dword pairs x
+// {vector, scalar} shift operand, that differ from {hi, lo} >> 8 (operand & 3); 0 on gfx950. 0xFFFFFFFF = the check could not run.
+uint32_t mscomp_amd_debug_alignbyte(mscomp_amd_ctx* c, uint32_t seed)
+{
+	if (!c) { return 0xFFFFFFFFu; }
+	DeviceGuard g(c->device);
+	if (!c->slot_size.reserve(ALIGNBYTE_CHECK_WORDS * sizeof(uint32_t))) { return 0xFFFFFFFFu; }
+	return run_alignbyte_check(c->stream, seed, static_cast<uint32_t*>(c->slot_size.p));
+}
+
 // ---- drop-in one-shot path (host pointers): H2D, one-unit batch on the GPU, D2H. No CPU encoder exists here. ----
 namespace {
 

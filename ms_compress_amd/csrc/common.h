@@ -60,6 +60,11 @@ __device__ __forceinline__ uint32_t first_nz_byte16(uint32_t x0, uint32_t x1, ui
 	return min3u(min3u(ffbl_raw(x0), a, b), c, 128u) >> 3;
 }
 
+// v_alignbyte_b32 with a BYTE ADDRESS as its shift: the instruction takes the byte shift from bits [1:0] of its third operand and ignores
+// the rest (the gfx9-family ISA documents say so; util.hip alignbyte_check_kernel asks the device, tests/test_gpu_alignbyte.py), so the
+// `& 3` in front of it is a vector instruction for nothing. The helper is the one place that relies on it: = {hi, lo} >> 8 (addr & 3).
+__device__ __forceinline__ uint32_t alignbyte_addr(uint32_t hi, uint32_t lo, uint32_t addr) { return __builtin_amdgcn_alignbyte(hi, lo, addr); }
+
 // 16 bytes at ANY byte offset of an LDS array whose base is 4-byte aligned. A byte-misaligned ds_read_b128 is replayed
 // by the LDS pipe (about 64 cycles; SQ_LDS_UNALIGNED_STALL was 77 % of the match finder's LDS cycles), so read 5 ALIGNED
 // dwords and funnel-shift (v_alignbyte).

@@ -506,6 +506,10 @@ void launch_concat_slots(hipStream_t st, const uint8_t* slots, uint32_t slot_str
 void launch_compact(hipStream_t st, const uint8_t* d_out, const u64* d_out_off, const uint32_t* d_tile_prefix, uint32_t n_units, uint32_t n_tiles,
                     const u64* d_out_len, u64* d_packed_off, uint8_t* d_packed);
 uint32_t run_lds_lane_order_check(hipStream_t st, uint32_t seed, uint32_t blocks, uint32_t rounds, uint32_t nkeys, uint32_t* d_bad);
+// v_alignbyte_b32 with operands that have bits above [1:0] set (util.hip): the number of results, of ALIGNBYTE_CHECK_WORDS written to d_out,
+// that differ from {hi, lo} >> 8 (operand & 3); 0xFFFFFFFF = the check could not run
+#define ALIGNBYTE_CHECK_WORDS (256u * 128u)
+uint32_t run_alignbyte_check(hipStream_t st, uint32_t seed, uint32_t* d_out);
 void launch_finalize_units(hipStream_t st, const u64* prefix, const BatchTables& bt, uint8_t* d_out,
                            u64* d_out_len, int32_t* d_status, int lznt1_eob);
 

@@ -87,20 +87,36 @@ __device__ __forceinline__ uint32_t lz_shift(uint32_t pos)
 // racing LDS accesses between lanes of one wave: relaxed wavefront-scope atomics (plain ds_read/ds_write in the ISA;
 // DS operations of a wave execute in program order) so the compiler neither forwards nor reorders them.
 __device__ __forceinline__ void     wst16(uint16_t* p, uint32_t v) { __hip_atomic_store(p, (uint16_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
-__device__ __forceinline__ uint32_t wld16(uint16_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+__device__ __forceinline__ uint16_t wld16(uint16_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ void     wst32(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ uint32_t wld32(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ void     wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront", "local"); }
 
+// A bucket entry of the window's eager scan stays 16 bits wide: the compiler selects the relaxed-atomic load (wld16) as an any-extending one and
+// puts an AND behind it wherever 32 zero-extended bits are asked for, although ds_read_u16 has zero-extended already. So nothing asks: the
+// entry travels as a dword whose upper half is UNDEFINED to the compiler (lz_entry32), and each of its readers takes the low bits alone -- the
+// "entry < position" compare selects the low word (SDWA, named here), the dword address is an AND with 0xFFC anyway, v_alignbyte_b32 reads
+// bits [1:0] of its shift (common.h alignbyte_addr) and lz_key's v_bitop3_b32 bits [11:0]. (One reader that asks for the zero-extended value
+// brings the AND back for all of them.)
+typedef uint16_t lz_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t lz_entry32(uint16_t e) { lz_u16x2 v; v.x = e; return __builtin_bit_cast(uint32_t, v); }
+__device__ __forceinline__ u64 lz_entry_below(uint32_t e, uint32_t p)   // the lanes whose entry is smaller than their p (< 65 536)
+{
+	u64 m; asm("v_cmp_gt_u32_sdwa %0, %1, %2 src0_sel:DWORD src1_sel:WORD_0" : "=s"(m) : "v"(p), "v"(e)); return m;
+}
 // 16 bytes at any byte offset of the chunk in LDS (common.h: lds_ld128), the offset taken modulo 4096: the AND that aligns the dword
 // address also keeps it inside the chunk, so callers need no select for candidates that do not exist (they are masked afterwards).
 __device__ __forceinline__ uint4 lz_ld128(const uint8_t* base, uint32_t off)
 {
 	const uint32_t* a = reinterpret_cast<const uint32_t*>(base + (off & 0xFFCu));
-	const uint32_t sh = off & 3u;
 	const uint32_t w0 = a[0], w1 = a[1], w2 = a[2], w3 = a[3], w4 = a[4];
-	return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
-	                  __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
+	return make_uint4(alignbyte_addr(w1, w0, off), alignbyte_addr(w2, w1, off), alignbyte_addr(w3, w2, off), alignbyte_addr(w4, w3, off));
+}
+// 4 bytes the same way (common.h: lds_ld32): the sort's read of a position's key
+__device__ __forceinline__ uint32_t lz_ld32(const uint8_t* base, uint32_t off)
+{
+	const uint32_t* a = reinterpret_cast<const uint32_t*>(base + (off & 0xFFCu));
+	return alignbyte_addr(a[1], a[0], off);
 }
 // Common prefix beyond the first 16 (equal) bytes of d[q..] and d[p..]: 16 bytes per step; the result may exceed maxlen
 // (callers clamp).
@@ -123,12 +139,12 @@ __device__ __forceinline__ uint32_t lz_lcp_tail(const uint8_t* d, uint32_t q, ui
 // p + maxlen <= n is clamped away. Returns min(common prefix, maxlen).
 __device__ __forceinline__ uint32_t lz_lcp_wave(const uint8_t* d, uint32_t q, uint32_t p, uint32_t l, uint32_t maxlen, uint32_t lane, uint32_t& steps)
 {
-	const uint32_t shq = (q + l) & 3u, shp = (p + l) & 3u;
+	const uint32_t shq = q + l, shp = p + l;                       // (as byte addresses: alignbyte_addr)
 	for (;;) {
 		const uint32_t oq = q + l + 4u * lane, op = p + l + 4u * lane;
 		const uint32_t* const aq = reinterpret_cast<const uint32_t*>(d + (oq & 0xFFCu));
 		const uint32_t* const ap = reinterpret_cast<const uint32_t*>(d + (op & 0xFFCu));
-		const uint32_t x = __builtin_amdgcn_alignbyte(aq[1], aq[0], shq) ^ __builtin_amdgcn_alignbyte(ap[1], ap[0], shp);
+		const uint32_t x = alignbyte_addr(aq[1], aq[0], shq) ^ alignbyte_addr(ap[1], ap[0], shp);
 		const u64 ne = __builtin_amdgcn_ballot_w64(x != 0u);
 		++steps;
 		if (ne) {
@@ -156,9 +172,8 @@ struct LzS1 { uint32_t x, y; };
 __device__ __forceinline__ LzS1 lz_ld_s1(const uint8_t* base, uint32_t off)
 {
 	const uint32_t* a = reinterpret_cast<const uint32_t*>(base + (off & 0xFFCu));
-	const uint32_t sh = off & 3u;
 	const uint32_t w0 = a[0], w1 = a[1], w2 = a[2];
-	return LzS1{ __builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh) };
+	return LzS1{ alignbyte_addr(w1, w0, off), alignbyte_addr(w2, w1, off) };
 }
 // first difference as a BIT index limited to capbits (<= 64), given the XOR of the two sides (lz_diff_bits16's form)
 __device__ __forceinline__ uint32_t lz_diff_bits_s1(uint32_t x0, uint32_t x1, uint32_t capbits)
@@ -170,14 +185,21 @@ struct LzS2 { uint32_t z, w; };
 __device__ __forceinline__ LzS2 lz_ld_s2(const uint8_t* base, uint32_t off)
 {
 	const uint32_t* a = reinterpret_cast<const uint32_t*>(base + (off & 0xFFCu));
-	const uint32_t sh = off & 3u;
 	const uint32_t w2 = a[2], w3 = a[3], w4 = a[4];
-	return LzS2{ __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh) };
+	return LzS2{ alignbyte_addr(w3, w2, off), alignbyte_addr(w4, w3, off) };
 }
 // first difference of bytes 8..15 as a bit index of the 16 bytes, limited to capbits (<= 128), for a pair whose first 8 bytes are equal
 __device__ __forceinline__ uint32_t lz_diff_bits_s2(uint32_t xz, uint32_t xw, uint32_t capbits)
 {
 	return min3u(ffbl_raw(xz) | 64u, ffbl_raw(xw) | 96u, capbits);
+}
+// The key (len << 12) | (4095 - q) of a candidate q (< 4096) that agrees on `bits` bits: with t = bits << 9 and c = 0xFFF it is "c ? ~q : t", bit
+// by bit -- ONE three-input boolean behind the shift (v_bitop3_b32). The low three bits of `bits` land below bit 12 and are selected away with
+// the rest, so no AND rounds them off first; and nothing of q above bit 11 is read, so a bucket entry needs no zero-extension for it.
+// (Named as an instruction: written as (t & ~c) | (~q & c) the compiler rounds t off with an AND of its own first. Truth table 0x74 = src1 ? ~src2 : src0.)
+__device__ __forceinline__ uint32_t lz_key(uint32_t bits, uint32_t q)
+{
+	uint32_t r; asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x74" : "=v"(r) : "v"(bits << 9), "s"(0xFFFu), "v"(q)); return r;
 }
 // Bit i (< 64) of a wave-uniform mask as 0 / 1 in a scalar register: no 64-bit `1 << i`, and the asm keeps the test after the shift a 32-bit one
 __device__ __forceinline__ uint32_t lz_bit64(u64 m, uint32_t i) { u64 t; asm("s_lshr_b64 %0, %1, %2" : "=s"(t) : "s"(m), "s"(i) : "scc"); return (uint32_t)t & 1u; }
@@ -235,14 +257,14 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	// What is read behind the own entry -- the next buckets' entries, the unused slots of a short chunk (leftovers of the sort's
 	// count words) or the first words of the table behind the array -- may be smaller than p and is cut off by the prefix.
 	// An inactive lane reads five entries of whatever bucket its bytes hash to: the mask of active lanes cuts them off.
-	uint32_t q[LZ_SELF + 1u];
+	uint32_t q[LZ_SELF + 1u];                                 // (their upper halves are undefined: lz_entry32)
 	u64 ex[LZ_SELF + 1u];                                     // lanes whose candidate j exists
 	#pragma unroll
 	// (five 2-byte reads, kept apart by the relaxed-atomic form: merged into an 8-byte + a 2-byte read, as the compiler does with plain loads, the 8-byte
 	// one is only 2-byte aligned and is replayed -- SQ_LDS_UNALIGNED_STALL 14 % of the LDS pipe's busy cycles, 54.4 against 53.3 ms on configs[4])
-	for (uint32_t j = 0; j <= LZ_SELF; ++j) { q[j] = wld16(const_cast<uint16_t*>(s_bucket) + s + j); }
+	for (uint32_t j = 0; j <= LZ_SELF; ++j) { q[j] = lz_entry32(wld16(const_cast<uint16_t*>(s_bucket) + s + j)); }
 	#pragma unroll
-	for (uint32_t j = 0; j <= LZ_SELF; ++j) { ex[j] = (j ? ex[j - 1u] : act) & __builtin_amdgcn_ballot_w64(q[j] < p); }
+	for (uint32_t j = 0; j <= LZ_SELF; ++j) { ex[j] = (j ? ex[j - 1u] : act) & lz_entry_below(q[j], p); }
 	// The compares stop at min(max_len, 16) bytes, in two stages: the first 8 bytes of the four candidates always; all 16 only if some lane of
 	// the wave has an existing candidate that agreed on the whole first stage while its max_len allows more (one wave-uniform test; then every
 	// lane compares bytes 8..15 of its four candidates). A candidate that reached 16 bytes with
@@ -275,7 +297,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 		}
 		#pragma unroll
 		for (uint32_t k = 0; k < LZ_SELF; ++k) {
-			asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(kk[k]) : "v"(((lb[k] & ~7u) << 9) | (q[k] ^ 4095u)), "s"(ex[k]));
+			asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(kk[k]) : "v"(lz_key(lb[k], q[k])), "s"(ex[k]));
 			key = kk[k] > key ? kk[k] : key;
 		}
 	}
@@ -398,14 +420,14 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 						const LzS2 a = lz_ld_s2(s_data, pL), c = lz_ld_s2(s_data, qq);
 						const uint32_t l3 = lz_diff_bits_s2(c.z ^ a.z, c.w ^ a.w, (mL < 16u ? mL : 16u) << 3);
 						l2 = l2 >= 8u * LZ_S1 ? l3 : l2;
-						if (mL > 16u && l2 >= 128u && ((vmask >> lane) & (u64)1)) { const uint32_t l = lz_lcp_tail(s_data, qq, pL, maxL, it); l2 = (l < maxL ? l : maxL) << 3; }
+						if (mL > 16u && l2 >= 128u && __builtin_amdgcn_inverse_ballot_w64(vmask)) { const uint32_t l = lz_lcp_tail(s_data, qq, pL, maxL, it); l2 = (l < maxL ? l : maxL) << 3; }
 					}
 					// One compare and a ballot find the winners; in three steps of four there are none and nothing is reduced (tools/dev/lz_best_study.c).
 					go = lt;                                           // (some entry not < pL: all older candidates seen)
 					const u64 win = __builtin_amdgcn_ballot_w64(l2 >= need) & vmask;
 					if (win) {
 						// longest, then oldest (older entries hold the larger 4095 - q); every winner's key is above the old kbest
-						uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(((l2 & ~7u) << 9) | (qq ^ 4095u)), "s"(win));
+						uint32_t k2; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(k2) : "v"(lz_key(l2, qq)), "s"(win));
 						kbest = wave_max_u32(k2);
 						const uint32_t len = kbest >> 12;               // >= 3
 						need = lz_need_bits(len);
@@ -824,7 +846,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			if (pb0 + j0 < pb1) {
 				uint32_t h[8], old[8];
 				#pragma unroll
-				for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { h[j] = lz_hash(lds_ld32(s_data, ((pb0 + j0 + j) * 64u + lane) & 4095u) & 0xFFFFFFu); } }
+				for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { h[j] = lz_hash(lz_ld32(s_data, (pb0 + j0 + j) * 64u + lane) & 0xFFFFFFu); } }
 				#pragma unroll
 				for (uint32_t j = 0; j < 8u; ++j) {
 					if (j0 + j < LZ4_PMAX) { const uint32_t b = pb0 + j0 + j; old[j] = lz_ordered_add<serial>(s_cw + h[j], 1u << fsh, b < pb1 && b * 64u + lane + 2u < n, lane); }
@@ -925,18 +947,27 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	// ---- C1. speculative parse of my segment ------------------------------------------------------------------------
 	const uint32_t nw = (n + 63u) >> 6;
 	// one window: parse, record (the match tokens into area a_). Returns the parse position after it.
+	// (The lanes that record are the match mask itself, as the exec mask: `(mask >> lane) & 1` is two ANDs with the lane's bit and a 64-bit
+	// compare in every lane. The record's base is a scalar pointer -- w_ and a_ are uniform -- so a lane adds a 32-bit offset to it.)
 #define LZ4_WINDOW(w_, entry_, cur_out, a_) { \
 		const uint32_t wb_ = (w_) * 64u; const uint32_t we_ = (wb_ + 64u < n) ? wb_ + 64u : n; \
 		if ((entry_) >= we_) { if (lane == 0) { s_tok[w_] = 0; s_mat[w_] = 0; } cur_out = (entry_); } \
 		else { \
 			LzWin r_; cur_out = lz_window<true>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); \
-			if ((r_.matchmask >> lane) & (u64)1) { \
+			if (__builtin_amdgcn_inverse_ballot_w64(r_.matchmask)) { \
 				const uint32_t p_ = wb_ + lane, best_ = r_.key >> 12; \
-				rec[((a_) * 64u + (w_)) * LZ4_MAXM + popc_below(r_.matchmask)] = (uint16_t)(((p_ - (4095u - (r_.key & 0xFFFu)) - 1u) << r_.shift) | (best_ - 3u)); \
+				uint16_t* __restrict__ const recw_ = rec + ((a_) * 64u + (w_)) * LZ4_MAXM; \
+				recw_[popc_below(r_.matchmask)] = (uint16_t)(((p_ - (4095u - (r_.key & 0xFFFu)) - 1u) << r_.shift) | (best_ - 3u)); \
 			} \
 			if (lane == 0) { s_tok[w_] = r_.tokmask; s_mat[w_] = r_.matchmask; } \
 		} \
 		if ((a_) && lane == 0) { s_rep[w_] = 1; } }
+	// The window loops run on the scalar unit: the window number, the parse position and what is read back from the control words (a recorded
+	// position, a progress word) are wave-uniform, and LZ4_UNI says so where each value is born -- a read of LDS lands in a vector register, and
+	// the loop's own increment, left to the compiler, is copied into both arms of the `lane == 0` store in front of it, which makes the counter a
+	// value joined under a divergent branch: window number and position then live in vector registers, the "window already behind the
+	// position" test and the loop's back edge become exec-mask code. Lane 0 still writes the records; the compares and branches around it are scalar.
+#define LZ4_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
 	// the segments are handed out in order (with four of them: one per wave)
 	for (;;) {
 		uint32_t seg = 0;
@@ -946,10 +977,10 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		if (a0 >= nw) { break; }
 		const uint32_t a1 = (lz4_seg_start(seg + 1u) < nw) ? lz4_seg_start(seg + 1u) : nw;
 		uint32_t entry = a0 * 64u;                                 // (exact for segment 0)
-		for (uint32_t w = a0; w < a1; ++w) {
+		for (uint32_t w = a0; w < a1; w = LZ4_UNI(w + 1u)) {
 			uint32_t cur;
 			LZ4_WINDOW(w, entry, cur, 0u)
-			entry = cur;
+			entry = LZ4_UNI(cur);
 			if (lane == 0) { s_endc[w] = (uint16_t)cur; }
 			wave_fence();
 			if (lane == 0) { __hip_atomic_store(&s_prog[seg], w + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -960,13 +991,13 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 			if (lane == 0) { s_used[seg + 1u] = entry; }
 			if (entry != a1 * 64u) {
 				const uint32_t wlim = (lz4_seg_start(seg + 2u) < nw) ? lz4_seg_start(seg + 2u) : nw;
-				for (uint32_t w = a1; w < wlim; ++w) {
-					while (__hip_atomic_load(&s_prog[seg + 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) <= w) { __builtin_amdgcn_s_sleep(2); }
+				for (uint32_t w = a1; w < wlim; w = LZ4_UNI(w + 1u)) {
+					while (LZ4_UNI(__hip_atomic_load(&s_prog[seg + 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) <= w) { __builtin_amdgcn_s_sleep(2); }
 					wave_fence();
-					const uint32_t spec = s_endc[w];
+					const uint32_t spec = LZ4_UNI(s_endc[w]);
 					uint32_t cur;
 					LZ4_WINDOW(w, entry, cur, 1u)
-					entry = cur;
+					entry = LZ4_UNI(cur);
 					if (lane == 0) { s_endc[w] = (uint16_t)cur; }
 					if (cur == spec) { break; }
 				}
@@ -980,14 +1011,14 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	wv = LZ4_FETCH(5);
 	if (wv == 0) {
 		for (uint32_t j = 1; j < LZ4_NSEG && lz4_seg_start(j) < nw; ++j) {
-			uint32_t e2 = s_endc[lz4_seg_start(j) - 1u];
-			if (e2 == s_used[j]) { continue; }                        // (else a repair ran through the whole of segment j-1: rare)
+			uint32_t e2 = LZ4_UNI(s_endc[lz4_seg_start(j) - 1u]);
+			if (e2 == LZ4_UNI(s_used[j])) { continue; }                        // (else a repair ran through the whole of segment j-1: rare)
 			uint32_t wl = lz4_seg_start(j);                           // first window NOT walked
-			for (uint32_t w = lz4_seg_start(j); w < nw; ++w) {
-				const uint32_t spec = s_endc[w];
+			for (uint32_t w = lz4_seg_start(j); w < nw; w = LZ4_UNI(w + 1u)) {
+				const uint32_t spec = LZ4_UNI(s_endc[w]);
 				uint32_t cur;
 				LZ4_WINDOW(w, e2, cur, 1u)
-				e2 = cur;
+				e2 = LZ4_UNI(cur);
 				if (lane == 0) { s_endc[w] = (uint16_t)cur; }
 				wave_fence();
 				wl = w + 1u;
@@ -1086,6 +1117,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	LZ4_T(18)
 	LZ4_TEND
 #undef LZ4_WINDOW
+#undef LZ4_UNI
 #undef LZ4_PARK
 #undef LZ4_FETCH
 }

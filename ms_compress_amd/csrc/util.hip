@@ -6,6 +6,7 @@
 #include "common.h"
 #include "kernels.h"
 #include <atomic>
+#include <vector>
 
 namespace msc {
 
@@ -216,6 +217,37 @@ uint32_t run_lds_lane_order_check(hipStream_t st, uint32_t seed, uint32_t blocks
 	uint32_t h = 0xFFFFFFFFu;
 	if (hipMemcpyAsync(&h, d_bad, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { return 0xFFFFFFFFu; }
 	return h;
+}
+
+// ---- hardware self-check: v_alignbyte_b32 -----------------------------------------------------------------------
+// lznt1.hip hands v_alignbyte_b32 a byte ADDRESS as its shift (common.h alignbyte_addr): the instruction is documented to take the byte shift
+// from bits [1:0] of its third operand. Block b asks for the operands whose low byte is b: lane l shifts dword pair l & 3 by operand kind
+// l >> 2 (kind 0 is b itself, the others put other bits above it, kind 15 all of them), once with the operand in a vector register and once
+// with a wave-uniform one; the host compares the 256 x 128 results with {hi, lo} >> 8 (operand & 3).
+__host__ __device__ inline uint32_t alignbyte_check_word(uint32_t seed, uint32_t i) { uint32_t x = (seed ^ (i * 0x9E3779B9u)) * 0x85EBCA6Bu; x ^= x >> 15; return x * 0xC2B2AE35u; }
+__host__ __device__ inline uint32_t alignbyte_check_operand(uint32_t kind, uint32_t b) { return b | (kind == 15u ? 0xFFFFFF00u : (kind * 0x9E3779B1u) & 0xFFFFFF00u); }
+__global__ __launch_bounds__(64) void alignbyte_check_kernel(uint32_t seed, uint32_t* __restrict__ out)
+{
+	const uint32_t lane = threadIdx.x, b = blockIdx.x, pair = lane & 3u;
+	const uint32_t lo = alignbyte_check_word(seed, 2u * pair), hi = alignbyte_check_word(seed, 2u * pair + 1u);
+	out[b * 128u + lane] = alignbyte_addr(hi, lo, alignbyte_check_operand(lane >> 2, b));
+	out[b * 128u + 64u + lane] = alignbyte_addr(hi, lo, alignbyte_check_operand(b & 15u, b));
+}
+uint32_t run_alignbyte_check(hipStream_t st, uint32_t seed, uint32_t* d_out)
+{
+	std::vector<uint32_t> h(ALIGNBYTE_CHECK_WORDS);
+	hipLaunchKernelGGL(alignbyte_check_kernel, dim3(256), dim3(64), 0, st, seed, d_out);
+	if (hipMemcpyAsync(h.data(), d_out, h.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { return 0xFFFFFFFFu; }
+	uint32_t bad = 0;
+	for (uint32_t b = 0; b < 256u; ++b) {
+		for (uint32_t i = 0; i < 128u; ++i) {
+			const uint32_t lane = i & 63u, pair = lane & 3u;
+			const uint64_t w = ((uint64_t)alignbyte_check_word(seed, 2u * pair + 1u) << 32) | alignbyte_check_word(seed, 2u * pair);
+			const uint32_t s = alignbyte_check_operand(i < 64u ? lane >> 2 : b & 15u, b);
+			bad += h[b * 128u + i] != (uint32_t)(w >> (8u * (s & 3u)));
+		}
+	}
+	return bad;
 }
 
 } // namespace msc
