@@ -143,14 +143,17 @@ int mscomp_amd_profile_read(mscomp_amd_ctx* c, const char** names, double* ms, u
 	return n;
 }
 
-// bt from the plan's table buffer and counts: in_off | in_len | out_off | out_cap (u64 x n_units each) | chunk_prefix (u32 x (n_units + 1))
-static void set_bt(mscomp_amd_plan* p)
+// `tables` of the plan, reserved for its kind and counts (tables_layout), and what the launch code reads of it: bt, the prefixes and reject
+// of a dev plan (the launch functions do not know where a creator put them)
+static bool reserve_tables(mscomp_amd_plan* p)
 {
-	const size_t n = p->n_units;
-	const u64* d = static_cast<const u64*>(p->tables.p);
-	p->bt.in_off = d; p->bt.in_len = d + n; p->bt.out_off = d + 2 * n; p->bt.out_cap = d + 3 * n;
-	p->bt.chunk_prefix = reinterpret_cast<const uint32_t*>(d + 4 * n);
-	p->bt.n_units = p->n_units; p->bt.n_chunks = p->n_chunks;
+	PlanCols t;
+	const bool scr = p->large && p->format == MSCOMP_XPRESS_HUFF && !p->sizing;
+	if (!p->tables.reserve(tables_layout(t, nullptr, p->n_units, p->dev, p->decompress, scr) + 8)) { return false; }
+	tables_layout(t, p->tables.p, p->n_units, p->dev, p->decompress, scr);
+	p->bt = { t.in_off, t.in_len, t.out_off, t.out_cap, t.chunk_prefix, p->n_units, p->n_chunks };
+	p->tok_prefix = t.tok_prefix; p->cand_prefix = t.cand_prefix; p->scr_prefix = t.scr_prefix; p->reject = t.reject;
+	return true;
 }
 // a table to a plan-owned buffer, waited for (the table is the caller's local)
 static bool upload(mscomp_amd_ctx* c, const DevBuf& b, const std::vector<uint64_t>& tab)
@@ -177,28 +180,29 @@ static bool reserve_compress_scratch(mscomp_amd_ctx* c, MSCompFormat format, siz
 		const size_t nw = n_chunks * 1024u + 64, ns = n_chunks + 1;
 		ok = c->wtok.reserve(nw * 8) && c->wmat.reserve(nw * 8) && c->wfar.reserve(nw * 4);
 		if (ok && xpress_emit_mode_for((uint32_t)n_units, (uint32_t)n_chunks) == 4) {    // the block-per-super-block kernels (launch_xpress_emit chooses from the same two numbers)
-			ok = c->wrec.reserve(nw * 6 * 4) && c->sbrec.reserve(ns * (16 + 24 + 16 * 8 * 4 + 16 * 2 * 8 + 8));
+			XpressWinBufs wb;
+			ok = c->wrec.reserve(wrec_layout(wb, nullptr, nw)) && c->sbrec.reserve(sbrec_layout(wb, nullptr, ns));
 		}
 	}
 	if (ok && format == MSCOMP_XPRESS_HUFF) {
 		const size_t nc = n_chunks + 1;
+		uint32_t* fb_count; uint32_t* fb_list;
 		ok = c->tokbits.reserve(nc * 1024 * 8) && c->counts.reserve(nc * 512 * 4) && c->extra.reserve(nc * 4) &&
-		     c->lens.reserve(nc * 512) && c->codes.reserve(nc * 1024) && c->fb_list.reserve(nc * 4 + 64) && c->fbflag.reserve(nc * 4);
+		     c->lens.reserve(nc * 512) && c->codes.reserve(nc * 1024) && c->fb_list.reserve(fb_list_layout(fb_count, fb_list, nullptr, n_chunks)) && c->fbflag.reserve(nc * 4);
 	}
 	return ok;
 }
-static bool reserve_lzd_scratch(mscomp_amd_ctx* c, size_t n_units, size_t n_chunks)   // the LZNT1 header chain (lzd_bufs), beside reserve_scan
+// decompress and size plans. LZNT1: the header chain (lzd_bufs) and its scan; Xpress formats: token counts, `slots` 32-bit tokens unless a size
+// plan asks (store), and for Xpress+Huffman the records of `cands` candidates (xhc_bufs)
+static bool reserve_decode_scratch(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, size_t n_chunks, uint64_t slots, uint64_t cands, bool store)
 {
-	return c->dz_cin.reserve(n_chunks * LZD_SLOTS * 4 + 64) && c->dz_csize.reserve(n_chunks * LZD_SLOTS * 2 + 64) &&
-	       c->dz_unit.reserve((n_chunks * (5 * LZD_K + 2) + n_units * 2 + 8) * 4);
-}
-static bool reserve_tokens(mscomp_amd_ctx* c, size_t n_units, uint64_t slots, bool store)   // Xpress formats: token counts; 32-bit tokens unless a size plan asks
-{
-	return (!store || c->dz_tok.reserve(slots * 4 + 256)) && c->dz_ntok.reserve((n_units + 1) * 8);
-}
-static bool reserve_xhc(mscomp_amd_ctx* c, size_t n_units, uint64_t cands)   // Xpress+Huffman candidate records (xhc_bufs)
-{
-	return c->dz_xhc.reserve((n_units + 1) * 8 + (size_t)cands * (4 * 4 + 3 * 8) + 64);
+	LzdBufs b; XhcBufs xb;
+	if (format == MSCOMP_LZNT1) {
+		return reserve_scan(c, n_chunks) && c->dz_cin.reserve(n_chunks * LZD_SLOTS * 4 + 64) && c->dz_csize.reserve(n_chunks * LZD_SLOTS * 2 + 64) &&
+		       c->dz_unit.reserve(dz_unit_layout(b, nullptr, n_units, n_chunks) + 24);
+	}
+	return (!store || c->dz_tok.reserve(slots * 4 + 256)) && c->dz_ntok.reserve((n_units + 1) * 8) &&
+	       (format != MSCOMP_XPRESS_HUFF || c->dz_xhc.reserve(dz_xhc_layout(xb, nullptr, n_units, cands) + 64));
 }
 
 // ---- the optional paths: their environment settings (read once), for host plans and for the bounds of dev plans with large units ----
@@ -209,6 +213,27 @@ static uint32_t xps_warm_env() { static const uint32_t b = [] { const char* e = 
 static uint64_t lzg_budget_env() { static const uint64_t b = [] { const char* e = getenv("MSCOMP_AMD_LZG_MAX_MB"); const long long v = e ? atoll(e) : 65536; return (uint64_t)(v < 0 ? 0 : v) << 20; }(); return b; }
 // the candidate token scratch: MSCOMP_AMD_XHC_SCR_MAX_MB, default 32 GiB; 0 = always walk twice
 static uint64_t xhc_scr_env() { static const uint64_t b = [] { const char* e = getenv("MSCOMP_AMD_XHC_SCR_MAX_MB"); const long long v = e ? atoll(e) : 32768; return (uint64_t)(v < 0 ? 0 : v) << 20; }(); return b; }
+// The table and the scratch of a plan's segment walk, for nb streams of sg segments in all, and of its all-CU stage, for nb units of tb token
+// blocks, tl tiles and wd words: the counts of a host plan, the bounds of a dev plan with large units (whose tables end with the counts of
+// an execution). false: not to be had, the plan's path stays off.
+static bool reserve_xps(mscomp_amd_plan* p, size_t nb, uint64_t sg)
+{
+	DevPaths d; XpsTables x;
+	if (!p->xps_tab.reserve(xps_tab_layout(d, nullptr, nb, p->large)) || !p->ctx->xps_buf.reserve(xps_buf_layout(x, nullptr, sg, nb, p->n_units) + 64)) { return false; }
+	xps_tab_layout(p->paths, p->xps_tab.p, nb, p->large);
+	p->paths.xps_max = p->xps_big = (uint32_t)nb; p->paths.xps_seg_max = p->xps_seg = (uint32_t)sg; p->paths.xps_seg_bytes = p->xps_seg_bytes = xps_seg_env(); p->xps_warm_bytes = xps_warm_env();
+	return true;
+}
+static bool reserve_lzg(mscomp_amd_plan* p, size_t nb, uint64_t tb, uint64_t tl, uint64_t wd)
+{
+	DevPaths d; LzgTables g;
+	mscomp_amd_ctx* c = p->ctx;
+	if (!p->lzg_tab.reserve(lzg_tab_layout(d, nullptr, nb, p->large)) || !c->lzg_bsum.reserve(tb * 8 + 64) || !c->lzg_dir.reserve(lzg_dir_layout(g, nullptr, tl) + 64) ||
+	    !c->lzg_words.reserve(lzg_words_layout(g, nullptr, wd, tl) + 64)) { p->lzg_tab.release(); (void)hipGetLastError(); return false; }
+	lzg_tab_layout(p->paths, p->lzg_tab.p, nb, p->large);
+	p->paths.lzg_max = p->lzg_big = (uint32_t)nb; p->paths.lzg_tb_max = p->lzg_tb = (uint32_t)tb; p->paths.lzg_tile_max = p->lzg_tiles = (uint32_t)tl; p->paths.lzg_word_max = p->lzg_words = wd;
+	return true;
+}
 
 static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, bool decompress, size_t n_units,
                                      const uint64_t* in_off, const uint64_t* in_len,
@@ -217,7 +242,7 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
 	if (!c || (n_units && (!in_off || !in_len || !out_off || !out_cap)) || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
-	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	if (!known_format(format)) { return MSCOMP_ARG_ERROR; }
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());   // (every return below that is not the last one gives up the plan and what it holds)
@@ -225,85 +250,83 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 	p->ctx = c; p->format = format; p->decompress = decompress; p->sizing = sizing; p->n_units = (uint32_t)n_units; p->run.never = n_units == 0;
 	p->lznt1_sa = !decompress && format == MSCOMP_LZNT1 && lznt1_sa_for(c);
 
-	const size_t host_words = n_units * 4 + (n_units + 2) / 2 + 1;
+	PlanCols hc;                                         // the columns in the staging memory, filled below
+	const size_t bytes = tables_layout(hc, nullptr, n_units, false, false, false) + 8;
 	std::vector<uint64_t> host;
 	uint64_t* h = nullptr;
 	if (!decompress) {                                   // compress plans: pinned staging, no stream wait (the decompress plans below upload more tables and wait as before)
 		if (c->h_tab_busy) { (void)hipEventSynchronize(c->h_tab_ev); c->h_tab_busy = false; }   // (the previous plan's copy: long done)
-		if (c->h_tab_cap < host_words * 8) {
+		if (c->h_tab_cap < bytes) {
 			if (c->h_tab) { (void)hipHostFree(c->h_tab); c->h_tab = nullptr; c->h_tab_cap = 0; }
-			const size_t want = host_words * 8 + host_words + 4096;
+			const size_t want = bytes + bytes / 8 + 4096;
 			if (hipHostMalloc(&c->h_tab, want, hipHostMallocDefault) == hipSuccess) { c->h_tab_cap = want; } else { c->h_tab = nullptr; (void)hipGetLastError(); }
 		}
 		if (c->h_tab && !c->h_tab_ev && hipEventCreateWithFlags(&c->h_tab_ev, hipEventDisableTiming) != hipSuccess) { c->h_tab_ev = nullptr; (void)hipGetLastError(); }
 		if (c->h_tab && c->h_tab_ev) { h = static_cast<uint64_t*>(c->h_tab); }
 	}
 	const bool pinned = h != nullptr;
-	if (!pinned) { host.resize(host_words); h = host.data(); }
-	uint32_t* h_cp = reinterpret_cast<uint32_t*>(h + 4 * n_units);
+	if (!pinned) { host.resize(bytes / 8); h = host.data(); }
+	tables_layout(hc, h, n_units, false, false, false);
 	uint64_t chunks = 0, total = 0;
 	for (size_t i = 0; i < n_units; ++i) {
-		h[i] = in_off[i]; h[n_units + i] = in_len[i]; h[2 * n_units + i] = out_off[i]; h[3 * n_units + i] = out_cap[i];
-		h_cp[i] = (uint32_t)chunks;
+		hc.in_off[i] = in_off[i]; hc.in_len[i] = in_len[i]; hc.out_off[i] = out_off[i]; hc.out_cap[i] = out_cap[i];
+		hc.chunk_prefix[i] = (uint32_t)chunks;
 		if (decompress && in_len[i] > 0xFFFFF000u) { return MSCOMP_ARG_ERROR; }   // offsets inside a unit are 32-bit (4 GiB - 4096 at most)
 		chunks += decompress ? decode_chunks(format, in_len[i]) : compress_chunks(format, in_len[i]);
 		total += in_len[i];
 		if (in_len[i] > p->max_unit) { p->max_unit = in_len[i]; }
 		if (chunks > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
 	}
-	h_cp[n_units] = (uint32_t)chunks;
+	hc.chunk_prefix[n_units] = (uint32_t)chunks;
 	p->n_chunks = (uint32_t)chunks;
 	p->total_in = total;
-	const size_t bytes = host_words * sizeof(uint64_t);
 	{	// the smallest pooled buffer that is large enough, else a new one
 		size_t best = c->table_pool.size();
 		for (size_t i = 0; i < c->table_pool.size(); ++i) { if (c->table_pool[i].cap >= bytes && (best == c->table_pool.size() || c->table_pool[i].cap < c->table_pool[best].cap)) { best = i; } }
 		if (best < c->table_pool.size()) { p->tables = c->table_pool[best]; p->tables.asked = 0; c->table_pool.erase(c->table_pool.begin() + (long)best); }   // (asked: this plan's own, from the reserve below)
 	}
-	if (!p->tables.reserve(bytes)) { return MSCOMP_MEM_ERROR; }
+	if (!reserve_tables(p.get())) { return MSCOMP_MEM_ERROR; }
 	if (hipMemcpyAsync(p->tables.p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { return MSCOMP_ERRNO; }
 	if (pinned) { if (hipEventRecord(c->h_tab_ev, c->stream) != hipSuccess) { return MSCOMP_ERRNO; } c->h_tab_busy = true; }
 	else if (hipStreamSynchronize(c->stream) != hipSuccess) { return MSCOMP_ERRNO; }
-	set_bt(p.get());
 
 	if (!decompress) {
 		if (!reserve_compress_scratch(c, format, n_units, p->n_chunks, p->lznt1_sa)) { return MSCOMP_MEM_ERROR; }
 		*out = p.release();
 		return MSCOMP_OK;
 	}
-	bool okd = reserve_scan(c, p->n_chunks);
-	if (okd && format == MSCOMP_LZNT1) { okd = reserve_lzd_scratch(c, n_units, p->n_chunks); }
+	bool okd = reserve_scan(c, p->n_chunks) && (format != MSCOMP_LZNT1 || reserve_decode_scratch(c, format, n_units, p->n_chunks, 0, 0, false));
 	if (okd && format != MSCOMP_LZNT1) {
 		// tokpre: first token slot | Xpress+Huffman: first candidate slot | first token-scratch slot of every unit. A size plan writes no
 		// tokens (its token prefix stays zero; an Xpress size plan has no table at all)
 		const bool xh = format == MSCOMP_XPRESS_HUFF;
-		const size_t row = n_units + 1;
-		std::vector<uint64_t> tp(xh ? 3 * row : sizing ? 0 : row);
+		const int rows = xh ? 3 : sizing ? 0 : 1;
+		PlanCols tc;                                       // its rows in `tp`, filled here, then in the plan's buffer
+		const size_t tp_bytes = tokpre_layout(tc, nullptr, n_units, rows);
+		std::vector<uint64_t> tp(tp_bytes / 8);
+		tokpre_layout(tc, tp.data(), n_units, rows);
 		uint64_t slots = 0, cands = 0, scr = 0;
-		for (size_t i = 0; i < n_units; ++i) {
-			if (!sizing) { tp[i] = slots; slots += token_slots(format, in_len[i], out_cap[i]); }
-			if (xh) {
-				const uint64_t most = candidate_slots(in_len[i], out_cap[i]);
-				tp[row + i] = cands; tp[2 * row + i] = scr;
-				cands += most;
-				if (!sizing) { scr += scratch_slots(in_len[i], out_cap[i]); }   // a buffer of several chunks: its candidates keep their tokens (no second walk)
-			}
+		for (size_t i = 0; i <= n_units; ++i) {
+			if (!sizing) { tc.tok_prefix[i] = slots; }
+			if (xh) { tc.cand_prefix[i] = cands; tc.scr_prefix[i] = scr; }
+			if (i == n_units) { break; }
+			if (!sizing) { slots += token_slots(format, in_len[i], out_cap[i]); }
+			if (xh) { cands += candidate_slots(in_len[i], out_cap[i]); }
+			if (xh && !sizing) { scr += scratch_slots(in_len[i], out_cap[i]); }   // a buffer of several chunks: its candidates keep their tokens (no second walk)
 		}
-		if (!sizing) { tp[n_units] = slots; }
-		if (xh) { tp[row + n_units] = cands; tp[2 * row + n_units] = scr; }
 		if (cands > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
 		p->xhc_slots = (uint32_t)cands;
-		okd = p->tokpre.reserve(tp.size() * 8) && reserve_tokens(c, n_units, slots, !sizing) && (!xh || reserve_xhc(c, n_units, cands));
+		okd = p->tokpre.reserve(tp_bytes) && reserve_decode_scratch(c, format, n_units, p->n_chunks, slots, cands, !sizing);
 		if (xh) {
 			// ... if that scratch is affordable: at most MSCOMP_AMD_XHC_SCR_MAX_MB (default 32 GiB; 0 = always walk twice) and at most half of
 			// what the device has free right now; a reservation that fails anyway switches the path off (the second walk needs no scratch)
 			const uint64_t need = scr * XHC_SCR * 4 + 64, scr_budget = optional_scratch_budget(xhc_scr_env(), c->dz_scr.cap);
-			if (scr && (need > scr_budget || !okd || !c->dz_scr.reserve(need))) { for (size_t i = 0; i <= n_units; ++i) { tp[2 * row + i] = 0; } scr = 0; }
+			if (scr && (need > scr_budget || !okd || !c->dz_scr.reserve(need))) { for (size_t i = 0; i <= n_units; ++i) { tc.scr_prefix[i] = 0; } scr = 0; }
 			p->xhc_scr = scr;
 		}
 		if (okd && !tp.empty() && !upload(c, p->tokpre, tp)) { return MSCOMP_ERRNO; }
-		p->tok_prefix = static_cast<u64*>(p->tokpre.p);
-		if (xh) { p->cand_prefix = p->tok_prefix + row; p->scr_prefix = p->tok_prefix + 2 * row; }
+		tokpre_layout(tc, p->tokpre.p, n_units, rows);
+		p->tok_prefix = tc.tok_prefix; p->cand_prefix = tc.cand_prefix; p->scr_prefix = tc.scr_prefix;
 	}
 	if (okd && !sizing && (format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF)) {
 		// units with room for LZG_MIN_CAP bytes or more get their bytes from all CUs (lzglobal.hip): 4 bytes of scratch per byte of capacity;
@@ -319,43 +342,35 @@ static MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, boo
 		for (uint32_t i : big) { tot += out_cap[i]; mx = out_cap[i] > mx ? out_cap[i] : mx; }
 		const bool pays = lzg_pays(tot, mx);
 		if (!big.empty() && pays && words * 4 <= budget) {
-			const size_t nb = big.size(), upad = (nb + 1) / 2;              // the unit list in whole u64 slots
-			std::vector<uint64_t> tab(upad + 3 * (nb + 1));
-			memcpy(tab.data(), big.data(), nb * 4);
-			uint64_t* tbp = tab.data() + upad; uint64_t* tlp = tbp + nb + 1; uint64_t* wdp = tlp + nb + 1;
+			const size_t nb = big.size();
+			DevPaths h;                                                   // the table's columns in `tab`
+			std::vector<uint64_t> tab(lzg_tab_layout(h, nullptr, nb, false) / 8);
+			lzg_tab_layout(h, tab.data(), nb, false);
+			memcpy(h.lzg_unit, big.data(), nb * 4);
 			uint64_t tb = 0, tl = 0, wd = 0;
-			for (size_t k = 0; k < nb; ++k) {
+			for (size_t k = 0; k <= nb; ++k) {
+				h.lzg_tb_prefix[k] = tb; h.lzg_tile_prefix[k] = tl; h.lzg_word_prefix[k] = wd;
+				if (k == nb) { break; }
 				const size_t i = big[k];
-				tbp[k] = tb; tlp[k] = tl; wdp[k] = wd;
 				tb += lzg_token_blocks(format, in_len[i], out_cap[i]); tl += lzg_tiles(out_cap[i]); wd += lzg_words(out_cap[i]);
 			}
-			tbp[nb] = tb; tlp[nb] = tl; wdp[nb] = wd;
-			if (tb < 0x7FFFFFF0ull && tl < 0x7FFFFFF0ull) {
-				// an allocation that fails here only switches this (optional) path off: the block-per-unit kernel takes the units instead
-				const bool got = p->lzg_tab.reserve(tab.size() * 8) && c->lzg_bsum.reserve(tb * 8 + 64) && c->lzg_dir.reserve(tl * 8 + 64) && c->lzg_words.reserve(wd * 4 + LZG_PASSES * 4 + tl + 64);
-				if (got && !upload(c, p->lzg_tab, tab)) { return MSCOMP_ERRNO; }
-				if (got) { p->lzg_big = (uint32_t)nb; p->lzg_tb = (uint32_t)tb; p->lzg_tiles = (uint32_t)tl; p->lzg_words = wd; }
-				else { p->lzg_tab.release(); (void)hipGetLastError(); }
-			}
+			if (tb < 0x7FFFFFF0ull && tl < 0x7FFFFFF0ull && reserve_lzg(p.get(), nb, tb, tl, wd) && !upload(c, p->lzg_tab, tab)) { return MSCOMP_ERRNO; }
 		}
 	}
 	if (okd && format == MSCOMP_XPRESS) {
 		std::vector<uint32_t> big;
 		for (size_t i = 0; i < n_units; ++i) { if (xps_takes(in_len[i])) { big.push_back((uint32_t)i); } }
 		if (!big.empty()) {
-			const size_t nb = big.size(), upad = (nb + 1) / 2;
-			std::vector<uint64_t> tab(upad + nb + 1);
-			memcpy(tab.data(), big.data(), nb * 4);
-			const uint32_t seg_b = xps_seg_env(), warm_b = xps_warm_env();
-			p->xps_seg_bytes = seg_b; p->xps_warm_bytes = warm_b;
+			const size_t nb = big.size();
+			DevPaths h;
+			std::vector<uint64_t> tab(xps_tab_layout(h, nullptr, nb, false) / 8);
+			xps_tab_layout(h, tab.data(), nb, false);
+			memcpy(h.xps_unit, big.data(), nb * 4);
+			const uint32_t seg_b = xps_seg_env();
 			uint64_t sg = 0;
-			for (size_t k = 0; k < nb; ++k) { tab[upad + k] = sg; sg += xps_segments(in_len[big[k]], seg_b); }
-			tab[upad + nb] = sg;
-			if (sg < 0x7FFFFFF0ull) {
-				okd = p->xps_tab.reserve(tab.size() * 8) && c->xps_buf.reserve(sg * XPS_SEG_BYTES + nb * 4 + n_units * 4 + 64);
-				if (okd && !upload(c, p->xps_tab, tab)) { return MSCOMP_ERRNO; }
-				if (okd) { p->xps_big = (uint32_t)nb; p->xps_seg = (uint32_t)sg; }
-			}
+			for (size_t k = 0; k <= nb; ++k) { h.xps_seg_prefix[k] = sg; if (k < nb) { sg += xps_segments(in_len[big[k]], seg_b); } }
+			okd = sg >= 0x7FFFFFF0ull || reserve_xps(p.get(), nb, sg);
+			if (okd && p->xps_big && !upload(c, p->xps_tab, tab)) { return MSCOMP_ERRNO; }
 		}
 	}
 	if (!okd) { return MSCOMP_MEM_ERROR; }
@@ -396,14 +411,12 @@ void mscomp_amd_plan_destroy(mscomp_amd_plan* p)
 static LzgTables lzg_tables(const mscomp_amd_plan* p, mscomp_amd_ctx* c)
 {
 	LzgTables g = {};
-	g.n_big = p->lzg_big; g.n_tb = p->lzg_tb; g.n_tiles = p->lzg_tiles; g.cnt = p->lzg_cnt;
+	const DevPaths& d = p->paths;
+	g.n_big = p->lzg_big; g.n_tb = p->lzg_tb; g.n_tiles = p->lzg_tiles; g.cnt = d.lzg_cnt;
 	if (!g.n_big) { return g; }
-	const size_t nb = g.n_big, upad = (nb + 1) / 2;
-	const uint64_t* t = static_cast<const uint64_t*>(p->lzg_tab.p);
-	g.unit = reinterpret_cast<const uint32_t*>(t); g.tb_prefix = t + upad; g.tile_prefix = g.tb_prefix + nb + 1; g.word_prefix = g.tile_prefix + nb + 1;
+	g.unit = d.lzg_unit; g.tb_prefix = d.lzg_tb_prefix; g.tile_prefix = d.lzg_tile_prefix; g.word_prefix = d.lzg_word_prefix;
 	g.bsum = static_cast<u64*>(c->lzg_bsum.p);
-	g.dir_tok = static_cast<uint32_t*>(c->lzg_dir.p); g.dir_pos = g.dir_tok + p->lzg_tiles;
-	g.words = static_cast<uint32_t*>(c->lzg_words.p); g.open = g.words + p->lzg_words; g.tile_pass = reinterpret_cast<uint8_t*>(g.open + LZG_PASSES);
+	lzg_dir_layout(g, c->lzg_dir.p, p->lzg_tiles); lzg_words_layout(g, c->lzg_words.p, p->lzg_words, p->lzg_tiles);
 	return g;
 }
 // the last stage of Xpress / Xpress+Huffman decompression: tokens -> bytes (a wave per small unit, a block per middle one, all CUs for the large ones)
@@ -421,17 +434,7 @@ static XpressWinBufs xpress_win_bufs(mscomp_amd_ctx* c, uint32_t n_chunks)
 {
 	XpressWinBufs b = {};
 	b.wtok = static_cast<u64*>(c->wtok.p); b.wmat = static_cast<u64*>(c->wmat.p); b.wfar = static_cast<uint32_t*>(c->wfar.p);
-	const size_t nw = (size_t)n_chunks * 1024u + 64, ns = (size_t)n_chunks + 1;
-	if (c->wrec.p && c->sbrec.p) {
-		uint32_t* w = static_cast<uint32_t*>(c->wrec.p);
-		b.wecur = w; b.weF = w + nw; b.wsum = w + 2 * nw; b.wnr = w + 3 * nw; b.ws0 = w + 4 * nw; b.ws1 = w + 5 * nw;
-		uint8_t* q = static_cast<uint8_t*>(c->sbrec.p);
-		b.sbpre = reinterpret_cast<u64*>(q); q += ns * 24;
-		b.seampos = reinterpret_cast<u64*>(q); q += ns * 16 * 2 * 8;
-		b.sbtot = reinterpret_cast<uint32_t*>(q); q += ns * 16;
-		b.seam = reinterpret_cast<uint32_t*>(q); q += ns * 16 * 8 * 4;
-		b.used = reinterpret_cast<uint32_t*>(q);
-	}
+	if (c->wrec.p && c->sbrec.p) { wrec_layout(b, c->wrec.p, (size_t)n_chunks * 1024u + 64); sbrec_layout(b, c->sbrec.p, (size_t)n_chunks + 1); }
 	return b;
 }
 
@@ -439,36 +442,21 @@ static XpressWinBufs xpress_win_bufs(mscomp_amd_ctx* c, uint32_t n_chunks)
 static LzdBufs lzd_bufs(mscomp_amd_ctx* c, const mscomp_amd_plan* p)
 {
 	LzdBufs b;
-	b.cin = static_cast<uint32_t*>(c->dz_cin.p); b.csize = static_cast<uint16_t*>(c->dz_csize.p);
-	const size_t nk = (size_t)p->n_chunks * LZD_K;
-	b.segL = static_cast<uint32_t*>(c->dz_unit.p); b.segE = b.segL + nk; b.segcnt = b.segE + nk; b.segstop = b.segcnt + nk; b.segoff = b.segstop + nk;
-	b.selcnt = b.segoff + nk; b.seloff = b.selcnt + p->n_chunks;
-	b.stop = b.seloff + p->n_chunks; b.irregular = b.stop + p->n_units + 1u;
-	b.flat = static_cast<u64*>(c->prefix.p);
+	b.cin = static_cast<uint32_t*>(c->dz_cin.p); b.csize = static_cast<uint16_t*>(c->dz_csize.p); b.flat = static_cast<u64*>(c->prefix.p);
+	dz_unit_layout(b, c->dz_unit.p, p->n_units, p->n_chunks);
 	return b;
 }
 // the candidate records of Xpress+Huffman decompression, laid out for the plan's candidate slots (the token scratch, if any, is set by the caller)
-static XhcBufs xhc_bufs(mscomp_amd_ctx* c, const mscomp_amd_plan* p)
-{
-	XhcBufs xb = {};
-	const size_t nu = (size_t)p->n_units + 1, ns = p->xhc_slots;
-	uint8_t* q = static_cast<uint8_t*>(c->dz_xhc.p);
-	xb.res_prod = reinterpret_cast<u64*>(q); q += ns * 8; xb.res_ntok = reinterpret_cast<u64*>(q); q += ns * 8; xb.tok_off = reinterpret_cast<u64*>(q); q += ns * 8;
-	xb.cand_pos = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_end = reinterpret_cast<uint32_t*>(q); q += ns * 4;
-	xb.res_reach = reinterpret_cast<uint32_t*>(q); q += ns * 4; xb.res_state = reinterpret_cast<uint32_t*>(q); q += ns * 4;
-	xb.cand_cnt = reinterpret_cast<uint32_t*>(q); q += nu * 4; xb.mode = reinterpret_cast<uint32_t*>(q);
-	return xb;
-}
+static XhcBufs xhc_bufs(mscomp_amd_ctx* c, const mscomp_amd_plan* p) { XhcBufs xb = {}; dz_xhc_layout(xb, c->dz_xhc.p, p->n_units, p->xhc_slots); return xb; }
 
 // the segment tables and scratch of the large Xpress streams of p (xps_*): none when the plan does not take that path
 static XpsTables xps_tables(const mscomp_amd_plan* p, mscomp_amd_ctx* c)
 {
 	XpsTables x = {};
 	if (!p->xps_big) { return x; }
-	const size_t nb = p->xps_big, upad = (nb + 1) / 2;
-	const uint64_t* t = static_cast<const uint64_t*>(p->xps_tab.p);
-	x.unit = reinterpret_cast<const uint32_t*>(t); x.seg_prefix = t + upad; x.n_big = p->xps_big; x.n_seg = p->xps_seg; x.seg_bytes = p->xps_seg_bytes; x.warm_bytes = p->xps_warm_bytes; x.cnt = p->xps_cnt;
-	x.seg = c->xps_buf.p; x.mode = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->xps_buf.p) + (size_t)p->xps_seg * XPS_SEG_BYTES); x.done = x.mode + nb;
+	const DevPaths& d = p->paths;
+	x.unit = d.xps_unit; x.seg_prefix = d.xps_seg_prefix; x.n_big = p->xps_big; x.n_seg = p->xps_seg; x.seg_bytes = p->xps_seg_bytes; x.warm_bytes = p->xps_warm_bytes; x.cnt = d.xps_cnt;
+	xps_buf_layout(x, c->xps_buf.p, p->xps_seg, p->xps_big, p->n_units);
 	return x;
 }
 
@@ -479,9 +467,9 @@ extern "C++" void msc::note_modes(mscomp_amd_plan* p)
 {
 	mscomp_amd_ctx* c = p->ctx;
 	c->dbg_mode = nullptr; c->dbg_mode_n = 0; c->dbg_mode_cnt = nullptr;
-	c->dbg_lzg_open = p->large && p->lzg_big ? static_cast<const uint32_t*>(c->lzg_words.p) + p->lzg_words : nullptr;
+	c->dbg_lzg_open = p->large && p->lzg_big ? lzg_tables(p, c).open : nullptr;
 	if (p->format == MSCOMP_XPRESS_HUFF && p->n_units) { c->dbg_mode = xhc_bufs(c, p).mode; c->dbg_mode_n = p->n_units; }
-	if (p->format == MSCOMP_XPRESS && p->xps_big && (p->sizing || p->large || g_xpd_mode.load(std::memory_order_relaxed) == 0)) { c->dbg_mode = xps_tables(p, c).mode; c->dbg_mode_n = p->xps_big; c->dbg_mode_cnt = p->xps_cnt; }
+	if (p->format == MSCOMP_XPRESS && p->xps_big && (p->sizing || p->large || g_xpd_mode.load(std::memory_order_relaxed) == 0)) { c->dbg_mode = xps_tables(p, c).mode; c->dbg_mode_n = p->xps_big; c->dbg_mode_cnt = p->paths.xps_cnt; }
 }
 
 // ---- the launch sequences: one per direction, for host-table and device-table plans alike ----
@@ -496,7 +484,7 @@ static void decode_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_ou
 	hipStream_t st = c->stream;
 	const u64* tp = p->tok_prefix; uint32_t* tok = static_cast<uint32_t*>(c->dz_tok.p); u64* ntok = static_cast<u64*>(c->dz_ntok.p);
 	const u64 gmin = p->lzg_big ? (u64)LZG_MIN_CAP : ~(u64)0;           // (host plans; p->large: the byte kernels read lzg_cnt instead)
-	const uint32_t* gcnt = p->large && p->lzg_big ? p->lzg_cnt : nullptr;
+	const uint32_t* gcnt = p->large && p->lzg_big ? p->paths.lzg_cnt : nullptr;
 	switch (p->format) {
 	case MSCOMP_LZNT1: {
 		const LzdBufs b = lzd_bufs(c, p);
@@ -575,7 +563,8 @@ static void compress_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_
 		u64* tokbits = static_cast<u64*>(c->tokbits.p); uint32_t* counts = static_cast<uint32_t*>(c->counts.p);
 		uint32_t* extra = static_cast<uint32_t*>(c->extra.p); uint8_t* lens = static_cast<uint8_t*>(c->lens.p);
 		uint16_t* codes = static_cast<uint16_t*>(c->codes.p); uint32_t* fbflag = static_cast<uint32_t*>(c->fbflag.p);
-		uint32_t* fb_count = static_cast<uint32_t*>(c->fb_list.p); uint32_t* fb_list = fb_count + 16;
+		uint32_t* fb_count; uint32_t* fb_list;
+		fb_list_layout(fb_count, fb_list, c->fb_list.p, p->n_chunks);
 		if (find) {
 			{ KernelTimer t(c, "xp_links_kernel"); launch_xp_links(st, d_in, p->bt, links, lasthead, dev); }
 			{ KernelTimer t(c, "xp_find_kernel"); launch_xp_find(st, d_in, p->bt, links, lasthead, mlen3, moff, 0xFFFFu, 1, dev); }
@@ -640,7 +629,7 @@ MSCompStatus mscomp_amd_plan_create_size(mscomp_amd_ctx* c, MSCompFormat format,
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
 	if (!c || (n_units && (!in_off || !in_len)) || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
-	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	if (!known_format(format)) { return MSCOMP_ARG_ERROR; }
 	std::vector<uint64_t> zero(n_units, 0), lim;
 	if (!limit) { lim.assign(n_units, ~(uint64_t)0); limit = lim.data(); }
 	return plan_create_impl(c, format, true, n_units, in_off, in_len, zero.data(), limit, out, true);
@@ -714,24 +703,7 @@ MSCompStatus mscomp_amd_decompressed_size_batch(mscomp_amd_ctx* c, MSCompFormat 
 }
 
 // ---- plans with device tables (include/mscomp_amd.h): created from bounds, tables built on the device by every execution ----
-// The plan holds its bounds and scratch sized for them; p->tables holds what the table pass (devplan.hip) writes each time:
-//   san (4 x n u64: in_off | in_len | out_off | out_cap, zero for a rejected unit) | chunk prefix (u32, n + 1) | decompress and size plans:
-//   token prefix | candidate prefix (u64, n + 1 each) | Xpress+Huffman decompress plans with large units: token-scratch prefix (u64, n + 1) |
-//   reject (u32, n)
-// and bt points into it with n_chunks = the bound (the kernels that are gridded by chunks return past chunk_prefix[n_units]). The only place
-// that knows this layout: the launch code reads p->bt, p->tok_prefix, p->cand_prefix and p->reject.
-static bool reserve_dev_tables(mscomp_amd_plan* p)
-{
-	const bool scr = p->large && p->format == MSCOMP_XPRESS_HUFF && !p->sizing;
-	const size_t n = p->n_units, cpw = (n + 2) / 2 + (p->decompress ? 1 : 0), tpw = p->decompress ? (scr ? 3 : 2) * (n + 1) : 0;
-	if (!p->tables.reserve((4 * n + cpw + tpw + (n + 1) / 2 + 1) * 8)) { return false; }
-	set_bt(p);
-	u64* tp = static_cast<u64*>(p->tables.p) + 4 * n + cpw;
-	if (p->decompress) { p->tok_prefix = tp; p->cand_prefix = tp + (n + 1); }
-	if (scr) { p->scr_prefix = tp + 2 * (n + 1); }
-	p->reject = reinterpret_cast<uint32_t*>(tp + tpw);
-	return true;
-}
+// The plan holds its bounds and scratch sized for them; p->tables holds what the table pass (devplan.hip) writes each time (tables_layout).
 
 // The optional paths of a dev plan with large units (Xpress formats): tables and scratch for the most that a batch within the plan's bounds
 // can put on each path, by the thresholds of common.h. N units, I input bytes, O bytes of capacity, toks token slots at most (create_decode_dev):
@@ -746,62 +718,31 @@ static bool reserve_dev_paths(mscomp_amd_plan* p, uint64_t N, uint64_t I, uint64
 {
 	mscomp_amd_ctx* c = p->ctx;
 	if (p->format == MSCOMP_XPRESS) {
-		const uint32_t seg_b = xps_seg_env();
-		const uint64_t nb = N < I / XPS_MIN_IN ? N : I / XPS_MIN_IN, sg = I / seg_b + nb;
-		if (nb && sg < 0x7FFFFFF0ull) {
-			const size_t upad = (nb + 1) / 2;
-			if (!p->xps_tab.reserve((upad + nb + 1 + 1) * 8) || !c->xps_buf.reserve(sg * XPS_SEG_BYTES + nb * 4 + N * 4 + 64)) { return false; }
-			p->xps_big = (uint32_t)nb; p->xps_seg = (uint32_t)sg; p->xps_seg_bytes = seg_b; p->xps_warm_bytes = xps_warm_env();
-			p->xps_cnt = reinterpret_cast<uint32_t*>(static_cast<uint64_t*>(p->xps_tab.p) + upad + nb + 1);
-		}
+		const uint64_t nb = N < I / XPS_MIN_IN ? N : I / XPS_MIN_IN, sg = I / xps_seg_env() + nb;
+		if (nb && sg < 0x7FFFFFF0ull && !reserve_xps(p, nb, sg)) { return false; }
 	}
 	if (p->sizing) { return true; }
 	const uint64_t B = N < O / LZG_MIN_CAP ? N : O / LZG_MIN_CAP;
 	if (B && O < (1ull << 60)) {
 		const uint64_t wd = O + 64 * B, tl = (O >> LZG_TILE_SHIFT) + B, tb = toks / 8192 + B;
 		const uint64_t budget = optional_scratch_budget(lzg_budget_env(), c->lzg_words.cap);
-		if (wd <= budget / 4 && tb < 0x7FFFFFF0ull && tl < 0x7FFFFFF0ull) {
-			const size_t upad = (B + 1) / 2;
-			const bool got = p->lzg_tab.reserve((upad + 3 * (B + 1) + 2) * 8) && c->lzg_bsum.reserve(tb * 8 + 64) && c->lzg_dir.reserve(tl * 8 + 64) && c->lzg_words.reserve(wd * 4 + LZG_PASSES * 4 + tl + 64);
-			if (got) {
-				p->lzg_big = (uint32_t)B; p->lzg_tb = (uint32_t)tb; p->lzg_tiles = (uint32_t)tl; p->lzg_words = wd;
-				p->lzg_cnt = reinterpret_cast<uint32_t*>(static_cast<uint64_t*>(p->lzg_tab.p) + upad + 3 * (B + 1));
-			} else { p->lzg_tab.release(); (void)hipGetLastError(); }
-		}
+		if (wd <= budget / 4 && tb < 0x7FFFFFF0ull && tl < 0x7FFFFFF0ull) { (void)reserve_lzg(p, B, tb, tl, wd); }
 	}
 	if (p->format == MSCOMP_XPRESS_HUFF) {
 		const uint64_t S = N < O / 65537u ? N : O / 65537u;
 		const uint64_t by_out = O / 65536u + 2 * S, by_len = I / 260u + S, most = by_out < by_len ? by_out : by_len, scr = most + most / 4 + 2 * S;
 		const uint64_t budget = optional_scratch_budget(xhc_scr_env(), c->dz_scr.cap);
 		if (S && scr <= budget / (XHC_SCR * 4ull) && scr * XHC_SCR * 4 + 64 <= budget) {
-			if (c->dz_scr.reserve(scr * XHC_SCR * 4 + 64)) { p->xhc_scr = scr; } else { (void)hipGetLastError(); }
+			if (c->dz_scr.reserve(scr * XHC_SCR * 4 + 64)) { p->xhc_scr = scr; p->paths.scr_prefix = p->scr_prefix; } else { (void)hipGetLastError(); }
 		}
 	}
 	return true;
-}
-// what the path pass of such a plan writes (kernels.h DevPaths): the parts whose path the plan has
-static DevPaths dev_paths(const mscomp_amd_plan* p)
-{
-	DevPaths d = {};
-	if (p->xps_big) {
-		uint64_t* t = static_cast<uint64_t*>(p->xps_tab.p);
-		d.xps_unit = reinterpret_cast<uint32_t*>(t); d.xps_seg_prefix = t + (p->xps_big + 1u) / 2u; d.xps_cnt = p->xps_cnt;
-		d.xps_seg_bytes = p->xps_seg_bytes; d.xps_max = p->xps_big; d.xps_seg_max = p->xps_seg;
-	}
-	if (p->lzg_big) {
-		uint64_t* t = static_cast<uint64_t*>(p->lzg_tab.p);
-		const size_t nb = p->lzg_big, upad = (nb + 1) / 2;
-		d.lzg_unit = reinterpret_cast<uint32_t*>(t); d.lzg_tb_prefix = t + upad; d.lzg_tile_prefix = d.lzg_tb_prefix + nb + 1; d.lzg_word_prefix = d.lzg_tile_prefix + nb + 1;
-		d.lzg_cnt = p->lzg_cnt; d.lzg_max = p->lzg_big; d.lzg_tb_max = p->lzg_tb; d.lzg_tile_max = p->lzg_tiles; d.lzg_word_max = p->lzg_words;
-	}
-	if (p->xhc_scr) { d.scr_prefix = p->scr_prefix; }
-	return d;
 }
 static void run_dev_paths(mscomp_amd_plan* p)
 {
 	if (!p->large || !(p->xps_big || p->lzg_big || p->xhc_scr)) { return; }
 	KernelTimer t(p->ctx, "dv_paths_kernel");
-	launch_dev_paths(p->ctx->stream, (int)p->format, p->n_units, static_cast<const u64*>(p->tables.p), dev_paths(p));
+	launch_dev_paths(p->ctx->stream, (int)p->format, p->n_units, static_cast<const u64*>(p->tables.p), p->paths);
 }
 
 // The bounds of a decompress dev plan's per-unit counts summed over the batch: every accepted unit has in_len <= 0xFFFFF000 and the accepted
@@ -836,7 +777,7 @@ static MSCompStatus create_decode_dev(mscomp_amd_ctx* c, MSCompFormat format, si
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
 	if (!c || n_units > 0x7FFFFFF0u || (flags & ~MSCOMP_AMD_DEV_LARGE_UNITS)) { return MSCOMP_ARG_ERROR; }
-	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	if (!known_format(format)) { return MSCOMP_ARG_ERROR; }
 	const uint64_t N = n_units;
 	uint64_t I = 0, chunks = 0, toks = 0, cands = 0;
 	if (!decode_dev_counts(format, N, in_total_max, out_total_max, sizing, I, chunks, toks, cands)) { return MSCOMP_MEM_ERROR; }   // (checked before the context is used)
@@ -848,10 +789,7 @@ static MSCompStatus create_decode_dev(mscomp_amd_ctx* c, MSCompFormat format, si
 	p->ctx = c; p->format = format; p->decompress = true; p->sizing = sizing; p->dev = true; p->n_units = (uint32_t)N; p->run.never = N == 0; p->n_chunks = (uint32_t)chunks;
 	p->in_total_max = in_total_max; p->out_total_max = sizing ? 0 : out_total_max; p->total_in = in_total_max; p->xhc_slots = (uint32_t)cands;
 	p->large = (flags & MSCOMP_AMD_DEV_LARGE_UNITS) && format != MSCOMP_LZNT1;   // (LZNT1 has no optional paths: its dev plans run the host plan's kernels already)
-	bool ok = reserve_dev_tables(p.get());
-	if (ok && format == MSCOMP_LZNT1) { ok = reserve_scan(c, chunks) && reserve_lzd_scratch(c, N, chunks); }
-	if (ok && format != MSCOMP_LZNT1) { ok = reserve_tokens(c, N, toks, !sizing); }
-	if (ok && format == MSCOMP_XPRESS_HUFF) { ok = reserve_xhc(c, N, cands); }
+	bool ok = reserve_tables(p.get()) && reserve_decode_scratch(c, format, N, chunks, toks, cands, !sizing);
 	if (ok && p->large) { ok = reserve_dev_paths(p.get(), N, I, O, toks); }
 	if (!ok) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	// the one-time kernel attributes of the instances this plan launches: set now, so that no first launch happens inside a caller's capture
@@ -886,7 +824,7 @@ MSCompStatus mscomp_amd_plan_create_compress_dev(mscomp_amd_ctx* c, MSCompFormat
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
 	if (!c || n_units > 0x7FFFFFF0u || in_unit_max == 0 || in_unit_max > 0xFFFFF000ull) { return MSCOMP_ARG_ERROR; }
-	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	if (!known_format(format)) { return MSCOMP_ARG_ERROR; }
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	// chunks of the accepted units: each has at most ceil(U / k), and as sum ceil(L / k) <= N + floor(sum L / k), at most N + floor(I / k) in all
@@ -899,7 +837,7 @@ MSCompStatus mscomp_amd_plan_create_compress_dev(mscomp_amd_ctx* c, MSCompFormat
 	p->ctx = c; p->format = format; p->decompress = false; p->dev = true; p->n_units = (uint32_t)N; p->run.never = N == 0; p->n_chunks = (uint32_t)chunks;
 	p->in_total_max = in_total_max; p->total_in = in_total_max; p->max_unit = U;   // (max_unit: the bound dv_ctables_kernel checks, and the Xpress finder as compress_launch chooses it)
 	p->lznt1_sa = format == MSCOMP_LZNT1 && lznt1_sa_for(c);
-	if (!reserve_dev_tables(p.get()) || !reserve_compress_scratch(c, format, N, chunks, p->lznt1_sa)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	if (!reserve_tables(p.get()) || !reserve_compress_scratch(c, format, N, chunks, p->lznt1_sa)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	// the one-time kernel attributes of the instances this plan launches: set now, so that no first launch happens inside a caller's capture
 	if (format == MSCOMP_LZNT1 && p->lznt1_sa) { prepare_lznt1_sa(true); }
 	if (format != MSCOMP_LZNT1) { prepare_xp_match(true); }
@@ -981,7 +919,8 @@ MSCompStatus mscomp_amd_plan_create_crc_dev(mscomp_amd_ctx* c, size_t n_units, u
 	std::unique_ptr<mscomp_amd_plan> p(new (std::nothrow) mscomp_amd_plan());
 	if (!p) { return MSCOMP_MEM_ERROR; }
 	p->ctx = c; p->dev = true; p->crc = true; p->n_units = (uint32_t)n_units; p->run.never = n_units == 0; p->in_total_max = in_total_max; p->total_in = in_total_max;
-	if (!p->tables.reserve((2 * n_units + 1) * 8)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	u64* cum; u64* off;
+	if (!p->tables.reserve(crc_tables_layout(cum, off, nullptr, n_units))) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
 	*out = p.release();
 	return MSCOMP_OK;
 }
@@ -999,7 +938,8 @@ MSCompStatus mscomp_amd_plan_execute_crc_dev(mscomp_amd_plan* p, const uint8_t* 
 	p->ran = true;
 	const void* args[8] = { d_in, d_in_off, d_in_len, d_crc, d_status };
 	return plan_run(p->run, p->ctx, args, [&] {
-		u64* cum = static_cast<u64*>(p->tables.p); u64* off = cum + p->n_units + 1u;
+		u64* cum; u64* off;
+		crc_tables_layout(cum, off, p->tables.p, p->n_units);
 		{ KernelTimer t(c, "crc_tables_kernel"); launch_crc_tables(c->stream, p->n_units, p->in_total_max, d_in_off, d_in_len, off, cum, d_status); }
 		{ KernelTimer t(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, p->n_units, cum, d_crc, nullptr, nullptr); }
 		{ KernelTimer t(c, "crc_kernel"); launch_crc_units(c->stream, p->n_units, d_in, off, cum, d_crc, nullptr, nullptr, nullptr, c->crc_blocks); }
@@ -1019,7 +959,7 @@ MSCompStatus mscomp_amd_plan_layout_dev(mscomp_amd_ctx* c, MSCompFormat format, 
                                         uint64_t* d_out_off, uint64_t* d_out_cap)
 {
 	if (!c || !d_out_off || (n_units && !d_in_len) || n_units > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
-	if (format != MSCOMP_LZNT1 && format != MSCOMP_XPRESS && format != MSCOMP_XPRESS_HUFF) { return MSCOMP_ARG_ERROR; }
+	if (!known_format(format)) { return MSCOMP_ARG_ERROR; }
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	launch_clayout_dev(c->stream, (int)format, d_in_len, (uint32_t)n_units, align, d_out_off, d_out_cap);
@@ -1031,8 +971,7 @@ uint64_t mscomp_amd_plan_layout(MSCompFormat format, size_t n_units, const uint6
 {
 	if (!align) { align = 1; }
 	uint64_t pos = 0;
-	const bool known = format == MSCOMP_NONE || format == MSCOMP_LZNT1 || format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF;
-	if (n_units && !known) { return (uint64_t)-1; }
+	if (n_units && format != MSCOMP_NONE && !known_format(format)) { return (uint64_t)-1; }
 	for (size_t i = 0; i < n_units; ++i) {
 		const uint64_t cap = layout_cap((int)format, in_len[i]);     // (common.h: the format's largest output; MSCOMP_NONE, the length)
 		if (out_off) { out_off[i] = pos; }
@@ -1049,20 +988,21 @@ MSCompStatus mscomp_amd_compact_batch(mscomp_amd_ctx* c, size_t n_units, const u
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	if (n_units == 0) { return hipMemsetAsync(d_packed_off, 0, 8, c->stream) == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO; }
-	std::vector<uint64_t> host(n_units + (n_units + 2) / 2 + 1);
-	uint32_t* tp = reinterpret_cast<uint32_t*>(host.data() + n_units);
+	u64* off; uint32_t* tp;                                // the table's columns in `host`, then in cp_tab
+	const size_t bytes = cp_tab_layout(off, tp, nullptr, n_units) + 8;
+	std::vector<uint64_t> host(bytes / 8);
+	cp_tab_layout(off, tp, host.data(), n_units);
 	uint64_t tiles = 0;
 	for (size_t i = 0; i < n_units; ++i) {
-		host[i] = out_off[i]; tp[i] = (uint32_t)tiles;
+		off[i] = out_off[i]; tp[i] = (uint32_t)tiles;
 		tiles += (out_cap[i] + 65535u) / 65536u;
 		if (tiles > 0x7FFFFFF0u) { return MSCOMP_ARG_ERROR; }
 	}
 	tp[n_units] = (uint32_t)tiles;
-	const size_t bytes = host.size() * sizeof(uint64_t);
 	if (!c->cp_tab.reserve(bytes)) { return MSCOMP_MEM_ERROR; }
 	if (hipMemcpyAsync(c->cp_tab.p, host.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { return MSCOMP_ERRNO; }
-	const u64* d_off = static_cast<const u64*>(c->cp_tab.p);
-	launch_compact(c->stream, d_out, d_off, reinterpret_cast<const uint32_t*>(d_off + n_units), (uint32_t)n_units, (uint32_t)tiles, d_out_len, d_packed_off, d_packed);
+	cp_tab_layout(off, tp, c->cp_tab.p, n_units);
+	launch_compact(c->stream, d_out, off, tp, (uint32_t)n_units, (uint32_t)tiles, d_out_len, d_packed_off, d_packed);
 	return hipGetLastError() == hipSuccess ? MSCOMP_OK : MSCOMP_ERRNO;
 }
 
@@ -1156,7 +1096,9 @@ int mscomp_amd_debug_lzg_open(mscomp_amd_ctx* c, uint64_t words, uint32_t* out)
 	if (!c || !out || !c->lzg_words.p) { return -1; }
 	DeviceGuard g(c->device);
 	if (!g.ok || hipStreamSynchronize(c->stream) != hipSuccess) { return -1; }
-	const uint32_t* open = c->dbg_lzg_open ? c->dbg_lzg_open : static_cast<uint32_t*>(c->lzg_words.p) + words;   // (a dev plan with large units keeps them behind the words of its bound)
+	LzgTables t;
+	lzg_words_layout(t, c->lzg_words.p, words, 0);
+	const uint32_t* open = c->dbg_lzg_open ? c->dbg_lzg_open : t.open;   // (a dev plan with large units keeps them behind the words of its bound)
 	return hipMemcpy(out, open, LZG_PASSES * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 int mscomp_amd_debug_plan_paths(mscomp_amd_plan* p, uint32_t out[3])
@@ -1170,8 +1112,8 @@ int mscomp_amd_debug_plan_paths(mscomp_amd_plan* p, uint32_t out[3])
 	out[0] = out[1] = out[2] = 0;
 	if (!p->ran) { return 0; }
 	uint64_t scr = 0;
-	if (p->xps_big && hipMemcpy(&out[0], p->xps_cnt, 4, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
-	if (p->lzg_big && hipMemcpy(&out[1], p->lzg_cnt, 4, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (p->xps_big && hipMemcpy(&out[0], p->paths.xps_cnt, 4, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	if (p->lzg_big && hipMemcpy(&out[1], p->paths.lzg_cnt, 4, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
 	if (p->xhc_scr && hipMemcpy(&scr, p->scr_prefix + p->n_units, 8, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
 	out[2] = (uint32_t)(scr < 0xFFFFFFFFull ? scr : 0xFFFFFFFFull);
 	return 0;

@@ -6,22 +6,9 @@ using namespace msc;
 
 #pragma GCC visibility push(hidden)                     // this file's helpers: not exported, as what host.h adds to namespace msc
 
-// A table buffer handed out column by column, in the order asked for. The same code run from address 0 counts the bytes, so a layout is
-// written down once. u64 columns first, from an 8-byte-aligned base: every one of them stays aligned.
-struct Carve {
-	uintptr_t at;
-	u64* q(size_t n) { u64* p = reinterpret_cast<u64*>(at); at += n * 8; return p; }
-	uint32_t* w(size_t n) { uint32_t* p = reinterpret_cast<uint32_t*>(at); at += n * 4; return p; }
-	int32_t* i(size_t n) { return reinterpret_cast<int32_t*>(w(n)); }
-};
-
 // The checks every create starts with, on arguments alone: MSCOMP_ARG_ERROR before MSCOMP_MEM_ERROR, both before the context is used.
 static bool block_size_ok(uint32_t block_size) { return block_size >= 4096u && block_size <= 524288u && !(block_size & (block_size - 1u)); }
-static bool create_args_ok(const mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, uint32_t flags)
-{
-	if (!c || flags || !block_size_ok(block_size)) { return false; }
-	return format == MSCOMP_LZNT1 || format == MSCOMP_XPRESS || format == MSCOMP_XPRESS_HUFF;
-}
+static bool create_args_ok(const mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, uint32_t flags) { return c && !flags && block_size_ok(block_size) && known_format(format); }
 static bool count_ok(uint64_t n) { return n <= 0x7FFFFFF0u; }
 
 // Every destroy: on the object's device, its stream idle, `release` gives up what o (may be null) holds on the device; the delete, its graphs.
@@ -118,7 +105,7 @@ struct mscomp_amd_blocks {
 // the columns of a container's tables from `base` on (n resources, m blocks at most); returns where they end: from a null base, their bytes
 static uintptr_t blocks_tab(BlocksTab& t, void* base, size_t n, size_t m)
 {
-	Carve k{reinterpret_cast<uintptr_t>(base)};
+	Carve k(base);
 	t.res_a = k.q(n); t.res_b = k.q(n); t.unit_first = k.q(n + 1);
 	t.in_off = k.q(m); t.in_len = k.q(m); t.out_off = k.q(m); t.out_cap = k.q(m); t.ulen = k.q(m); t.aux_a = k.q(m); t.aux_b = k.q(m);
 	t.rstat = k.i(n); t.ustat = k.i(m); t.act = k.w(m); t.ucrc = k.w(m);
@@ -270,7 +257,7 @@ struct mscomp_amd_writer : BlockAccess {
 static uintptr_t access_tab(BlockAccess* a, mscomp_amd_writer* w, void* base)
 {
 	const size_t n = a->n_req, m = a->m, nbt = a->nbt;
-	Carve k{reinterpret_cast<uintptr_t>(base)};
+	Carve k(base);
 	ReaderTab& t = a->t;
 	t.q_off = k.q(n); t.q_want = k.q(n); t.q_j0 = k.q(n); t.q_len = k.q(n); t.unit_first = k.q(n + 1);
 	t.in_off = k.q(m); t.in_len = k.q(m); t.out_off = k.q(m); t.out_cap = k.q(m); t.ulen = k.q(m); t.src = k.q(m); t.clen = k.q(m); t.cum = k.q(m + 1);
@@ -478,7 +465,7 @@ static_assert(SX_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header st
 // the columns of a splicer made for extents from `base` on; returns where they end: from a null base, their bytes
 static uintptr_t splice_ext_tab(SpliceExtTab& t, void* base, size_t nbt, size_t n_ext)
 {
-	Carve k{reinterpret_cast<uintptr_t>(base)};
+	Carve k(base);
 	t.addr = k.q(nbt); t.ext_row = k.q(n_ext + 1); t.tsum = k.q(splice_row_tiles((uint32_t)nbt)); t.flag = k.w(2);
 	return k.at;
 }
@@ -591,7 +578,7 @@ static_assert(DF_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header st
 // the columns of a deduper's tables from `base` on (n = n_res_total); returns where they end: from a null base, their bytes
 static uintptr_t dedup_tab(DedupTab& t, void* base, size_t n)
 {
-	Carve k{reinterpret_cast<uintptr_t>(base)};
+	Carve k(base);
 	t.slots = 2 * (u64)n + 64;
 	t.ufirst = k.q(n + 1); t.key = k.q(n); t.tkey = k.q(t.slots);
 	t.tmin = k.w(t.slots); t.slot_of = k.w(n); t.cand = k.w(n); t.flag = k.w(n); t.rlist = k.w(n);
@@ -619,7 +606,7 @@ MSCompStatus mscomp_amd_deduper_create(mscomp_amd_ctx* c, uint32_t block_size, u
 // the columns of a deduper made for diff from `base` on (n = n_pair, m = n_blocks_new); returns where they end: from a null base, their bytes
 static uintptr_t diff_tab(DiffTab& t, void* base, size_t n, size_t m)
 {
-	Carve k{reinterpret_cast<uintptr_t>(base)};
+	Carve k(base);
 	t.ufirst = k.q(n + 1); t.pfirst = k.q(3 * n); t.tsum = k.q(8 * (size_t)diff_row_tiles((uint32_t)m)); t.verdict = k.w(m);
 	return k.at;
 }
@@ -721,7 +708,7 @@ struct mscomp_amd_transcoder {
 static uintptr_t transcode_tab(TranscodeTab& t, void* base, const TcDims& d, size_t dm, size_t em)
 {
 	const size_t n = d.n_res, ng = d.ngmax, m = d.nbn;
-	Carve k{reinterpret_cast<uintptr_t>(base)};
+	Carve k(base);
 	t.gfirst = k.q(n + 1); t.pfirst = k.q(n + 1);
 	t.plen = k.q(m); t.paddr = k.q(m); t.pjf = k.q(m); t.pdl = k.q(m); t.addr = k.q(m); t.tsum = k.q(splice_row_tiles((uint32_t)m));
 	t.d_in_off = k.q(dm); t.d_in_len = k.q(dm); t.d_out_off = k.q(dm); t.d_out_cap = k.q(dm); t.d_ulen = k.q(dm);

@@ -32,6 +32,19 @@ struct DevBuf {
 	}
 	void release() { if (p) { (void)hipFree(p); if (epoch) { ++*epoch; } } p = nullptr; cap = 0; asked = 0; }
 };
+// A buffer handed out column by column, in the order asked for. The same code run from a null base counts the bytes, so a layout is
+// written down once. u64 columns first, from an 8-byte-aligned base: every one of them stays aligned (pad8 in front of one that follows a
+// narrower column).
+struct Carve {
+	uintptr_t at;
+	explicit Carve(const void* base) : at(reinterpret_cast<uintptr_t>(base)) {}
+	template <class T> T* col(size_t n) { T* p = reinterpret_cast<T*>(at); at += n * sizeof(T); return p; }
+	u64* q(size_t n) { return col<u64>(n); } uint32_t* w(size_t n) { return col<uint32_t>(n); } int32_t* i(size_t n) { return col<int32_t>(n); }
+	uint16_t* h(size_t n) { return col<uint16_t>(n); } uint8_t* b(size_t n) { return col<uint8_t>(n); }
+	void pad8() { at = (at + 7) & ~(uintptr_t)7; }         // (a u32 list in whole u64 slots)
+};
+inline bool known_format(MSCompFormat f) { return f == MSCOMP_LZNT1 || f == MSCOMP_XPRESS || f == MSCOMP_XPRESS_HUFF; }
+
 // one buffer of a scratch hook's target (mscomp_amd_debug_scratch_*): `keeps` = it holds what its creation uploaded (a host plan's tables)
 struct ScratchEnt { const char* name; DevBuf* b; bool keeps; };
 
@@ -107,14 +120,13 @@ struct mscomp_amd_plan {
 	bool dev = false;                                  // a plan whose tables are built on the device at every execution (mscomp_amd_plan_create_decompress_dev / _compress_dev; with sizing: _size_dev)
 	bool crc = false;                                  // a CRC plan (mscomp_amd_plan_create_crc_dev): a dev plan without a format; tables = cum (u64 x (n_units + 1)) | off (u64 x n_units)
 	bool large = false;                                // ... with MSCOMP_AMD_DEV_LARGE_UNITS: the tables of the optional paths are built there too (xhc_scr, lzg_*, xps_big / xps_seg hold the bounds
-	                                                   // they were reserved for, 0 = the path is off for the plan; the counts of an execution are in xps_cnt / lzg_cnt, device memory)
-	uint32_t* xps_cnt = nullptr; uint32_t* lzg_cnt = nullptr;   // (behind the prefix arrays of xps_tab / lzg_tab)
+	                                                   // they were reserved for, 0 = the path is off for the plan; the counts of an execution are in paths.xps_cnt / lzg_cnt, device memory)
 	uint64_t in_total_max = 0, out_total_max = 0;      // ... and the bounds its scratch was reserved for
 	uint32_t n_units = 0, n_chunks = 0;
 	uint64_t total_in = 0, max_unit = 0;               // (max_unit of a compress dev plan: the largest unit it takes)
 	bool lznt1_sa = false;                             // LZNT1: the suffix-array dictionary flavour -- fixed when the plan is created: a plan never changes its bytes under a running caller
 	bool matches_ready = false;                        // the caller has run the links + find kernels of this execution itself, range by range (the pipelined one-shot call): compress_launch skips them once
-	msc::DevBuf tables;                                // in_off | in_len | out_off | out_cap | chunk_prefix; dev plans: what their table pass writes (reserve_dev_tables)
+	msc::DevBuf tables;                                // in_off | in_len | out_off | out_cap | chunk_prefix; dev plans: what their table pass writes (tables_layout)
 	msc::DevBuf tokpre;                                // decompression by tokens (host plans): first token slot | first candidate slot | first token-scratch slot of every unit (n_units + 1 u64 each)
 	uint32_t xhc_slots = 0;                            // candidate chunk slots of the batch
 	uint64_t xhc_scr = 0;                              // token-scratch slots (candidates of multi-chunk buffers), 0 = none
@@ -123,6 +135,7 @@ struct mscomp_amd_plan {
 	uint64_t lzg_words = 0;
 	msc::DevBuf xps_tab;                               // xps_*: unit (u32 x n_big, padded) | seg_prefix (u64 x (n_big + 1))
 	uint32_t xps_big = 0, xps_seg = 0, xps_seg_bytes = 0, xps_warm_bytes = 0;
+	msc::DevPaths paths{};                             // the columns of xps_tab / lzg_tab and the bounds above, set when they are reserved: what a dev plan's path pass writes
 	// what the launch code reads, resolved when the plan is created (the launch functions do not know where a creator put it): the columns of
 	// `tables`; the prefixes, in tokpre for host plans and in `tables` for dev plans; reject (u32 x n_units), written by a dev plan's table pass
 	msc::BatchTables bt{};
@@ -136,6 +149,64 @@ struct mscomp_amd_plan {
 
 #pragma GCC visibility push(hidden)
 namespace msc {
+
+// ---- the layouts of every plan and context buffer with more than one column ----
+// One function per buffer, the only place that knows a column's offset: it fills the struct the launch code reads, from `base` on, and
+// returns where the columns end. From a null base that is their byte count: what the reserve() sites ask for, plus the pad they name. Host
+// code that builds a table before its upload runs the same function over its staging memory. Counts for a host plan, bounds for a dev plan.
+
+// `tables` of a plan, writable (the launch code reads them through p->bt and the plan's prefix fields). A host plan uploads
+//   in_off | in_len | out_off | out_cap (u64 x n each) | chunk_prefix (u32 x (n + 1))
+// and a dev plan holds what its table pass (devplan.hip) writes each time:
+//   san (4 x n u64: in_off | in_len | out_off | out_cap, zero for a rejected unit) | chunk prefix (u32, n + 1) | decompress and size plans:
+//   token prefix | candidate prefix (u64, n + 1 each) | Xpress+Huffman decompress plans with large units: token-scratch prefix (u64, n + 1) |
+//   reject (u32, n)
+// with bt.n_chunks = the bound (the kernels that are gridded by chunks return past chunk_prefix[n_units]).
+struct PlanCols { u64* in_off; u64* in_len; u64* out_off; u64* out_cap; uint32_t* chunk_prefix; u64* tok_prefix; u64* cand_prefix; u64* scr_prefix; uint32_t* reject; };
+inline uintptr_t tables_layout(PlanCols& t, void* base, size_t n, bool dev, bool decompress, bool scr)
+{
+	Carve k(base);
+	t = {};
+	t.in_off = k.q(n); t.in_len = k.q(n); t.out_off = k.q(n); t.out_cap = k.q(n); t.chunk_prefix = k.w(n + 1); k.pad8();
+	if (dev && decompress) { k.q(1); t.tok_prefix = k.q(n + 1); t.cand_prefix = k.q(n + 1); }   // (one slot in front of them stays unused)
+	if (dev && scr) { t.scr_prefix = k.q(n + 1); }
+	if (dev) { t.reject = k.w(n); k.pad8(); }
+	return k.at;
+}
+inline uintptr_t crc_tables_layout(u64*& cum, u64*& off, void* base, size_t n) { Carve k(base); cum = k.q(n + 1); off = k.q(n); return k.at; }   // `tables` of a CRC plan
+// `tokpre` of a host decode plan: `rows` of its three (one for Xpress, none for an Xpress size plan)
+inline uintptr_t tokpre_layout(PlanCols& t, void* base, size_t n, int rows)
+{ Carve k(base); t.tok_prefix = rows ? k.q(n + 1) : nullptr; t.cand_prefix = rows == 3 ? k.q(n + 1) : nullptr; t.scr_prefix = rows == 3 ? k.q(n + 1) : nullptr; return k.at; }
+// `lzg_tab` and `xps_tab`, writable (DevPaths; the launches of the paths read them through LzgTables / XpsTables): the units taken in whole
+// u64 slots, their prefixes and, for a dev plan with large units (cnt), the counts of an execution behind them
+inline uintptr_t lzg_tab_layout(DevPaths& d, void* base, size_t nb, bool cnt)
+{ Carve k(base); d.lzg_unit = k.w(nb); k.pad8(); d.lzg_tb_prefix = k.q(nb + 1); d.lzg_tile_prefix = k.q(nb + 1); d.lzg_word_prefix = k.q(nb + 1); d.lzg_cnt = cnt ? k.w(4) : nullptr; return k.at; }
+inline uintptr_t xps_tab_layout(DevPaths& d, void* base, size_t nb, bool cnt) { Carve k(base); d.xps_unit = k.w(nb); k.pad8(); d.xps_seg_prefix = k.q(nb + 1); d.xps_cnt = cnt ? k.w(2) : nullptr; return k.at; }
+// the context's scratch, as its members above say: nw windows, ns super-blocks
+inline uintptr_t wrec_layout(XpressWinBufs& b, void* base, size_t nw) { Carve k(base); b.wecur = k.w(nw); b.weF = k.w(nw); b.wsum = k.w(nw); b.wnr = k.w(nw); b.ws0 = k.w(nw); b.ws1 = k.w(nw); return k.at; }
+inline uintptr_t sbrec_layout(XpressWinBufs& b, void* base, size_t ns) { Carve k(base); b.sbpre = k.q(ns * 3); b.seampos = k.q(ns * 16 * 2); b.sbtot = k.w(ns * 4); b.seam = k.w(ns * 16 * 8); b.used = k.w(ns * 2); return k.at; }
+// dz_unit: LZD_K speculated chains per segment, five columns | the true chain per segment, two | stop, irregular per unit (+ 1 global flag)
+inline uintptr_t dz_unit_layout(LzdBufs& b, void* base, size_t n_units, size_t n_chunks)
+{
+	Carve k(base);
+	const size_t nk = n_chunks * LZD_K;
+	b.segL = k.w(nk); b.segE = k.w(nk); b.segcnt = k.w(nk); b.segstop = k.w(nk); b.segoff = k.w(nk); b.selcnt = k.w(n_chunks); b.seloff = k.w(n_chunks);
+	b.stop = k.w(n_units + 1); b.irregular = k.w(n_units + 1); return k.at;
+}
+// dz_xhc: the records of `cands` candidate chunk slots, u64 columns first | candidate count, path verdict per unit (n_units + 1 each)
+inline uintptr_t dz_xhc_layout(XhcBufs& xb, void* base, size_t n_units, size_t cands)
+{
+	Carve k(base);
+	xb.res_prod = k.q(cands); xb.res_ntok = k.q(cands); xb.tok_off = k.q(cands); xb.cand_pos = k.w(cands); xb.res_end = k.w(cands); xb.res_reach = k.w(cands);
+	xb.res_state = k.w(cands); xb.cand_cnt = k.w(n_units + 1); xb.mode = k.w(n_units + 1); return k.at;
+}
+inline uintptr_t xps_buf_layout(XpsTables& x, void* base, size_t n_seg, size_t nb, size_t n_units) { Carve k(base); x.seg = k.b(n_seg * XPS_SEG_BYTES); x.mode = k.w(nb); x.done = k.w(n_units); return k.at; }
+inline uintptr_t lzg_dir_layout(LzgTables& g, void* base, size_t tiles) { Carve k(base); g.dir_tok = k.w(tiles); g.dir_pos = k.w(tiles); return k.at; }
+inline uintptr_t lzg_words_layout(LzgTables& g, void* base, size_t words, size_t tiles) { Carve k(base); g.words = k.w(words); g.open = k.w(LZG_PASSES); g.tile_pass = k.b(tiles); return k.at; }
+// fb_list: 16 counters | the chunks the fallback kernel takes (one slot per chunk, and one)
+inline uintptr_t fb_list_layout(uint32_t*& count, uint32_t*& list, void* base, size_t n_chunks) { Carve k(base); count = k.w(16); list = k.w(n_chunks + 1); return k.at; }
+// cp_tab of mscomp_amd_compact_batch, its tile prefix in whole u64 slots
+inline uintptr_t cp_tab_layout(u64*& off, uint32_t*& tile_prefix, void* base, size_t n) { Carve k(base); off = k.q(n); tile_prefix = k.w(n + 1); k.pad8(); return k.at; }
 
 struct DeviceGuard {
 	int prev = -1; bool ok = true;
