@@ -725,8 +725,8 @@ static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: L
 // occupancy figure says 8 up to 100. Rounds 7 to 14 took 96 for the limit of eight blocks and ran at seven (93 to 96 registers: 6.79 waves per busy
 // CU-cycle, 5.81 above 96; round 13 in profiles/HISTORY.md and its correction in round 15). Since round 15 the kernel uses 77 (76 since round 17) and runs at eight
 // (7.76): lz_window keeps "candidate k reached 16 bytes" in the lanes instead of four 64-bit masks, and what sort and parse never read waits in the
-// lanes of one vector register (LZ4_PARK below). tests/test_lznt1_sgpr80.py holds all four instances at 80, without spills: an `amdgpu_num_sgpr`
-// limit gets there too, by spilling, which tests/test_lznt1_resources.py forbids.)
+// lanes of one vector register (LZ4_PARK below). tests/test_lznt1_resources.py holds all four instances at 80, without spills: an `amdgpu_num_sgpr`
+// limit gets there too, by spilling, which the same test forbids.)
 template <bool serial, bool DEV = false>                         // DEV: as lznt1_chunk_kernel
 __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
                                                           uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size, uint16_t* __restrict__ recs)

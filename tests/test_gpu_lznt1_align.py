@@ -6,7 +6,7 @@ that end at 3, 4, 5, 7, 8, 9, 15, 16, 17, 18, 19 and 20 bytes and at max_len (34
 bucket (the eager scan, and the whole-wave extension behind it) and once behind them (the finishing steps). Each chunk ends with a candidate
 whose 16 bytes straddle offsets 4095 / 4096 (the reads wrap modulo 4096) and a match that runs to the chunk's end; where q mod 4 is 0 the first
 candidate stands at position 0. Six more units end in a short last chunk of 1, 2, 3, 64, 65 and 4095 bytes, whose bucket array keeps leftovers
-of the sort behind the entries. Every chunk is placed on the CPU model of the bucket array that tests/test_gpu_lznt1_best.py keeps, the model's
+of the sort behind the entries. Every chunk is placed on the CPU model of the bucket array that tests/lznt1_model.py keeps, the model's
 parse must show each match where and as long as the case claims, the oracle's token starts and lengths must equal the model's, and the GPU
 tests compare byte for byte with the oracle in both kernel modes through a host-table plan, a device-table plan and the serial-atomics instance."""
 import functools
@@ -14,10 +14,9 @@ import functools
 import numpy as np
 import pytest
 
-import test_gpu_lznt1_best as B                      # the CPU model
-import test_gpu_lznt1_event as E                     # _parse (greedy parse on the model), _oracle_token_starts, _run (plans, guard bytes)
+import lznt1_model as M
+import lznt1_run as R
 
-LZNT1 = 2
 LENS = (3, 4, 5, 7, 8, 9, 15, 16, 17, 18, 19, 20, 40)   # 40: beyond max_len 34 of its position
 SHORT = (1, 2, 3, 64, 65, 4095)
 
@@ -29,48 +28,48 @@ def _copy(c, q, p, L):
 
 def _chunk(pm, qm, seed):
     """(chunk of 4096 bytes, {position: claimed match length}) for positions = pm and candidates = qm modulo 4"""
-    ks = B._keys()
+    ks = M.keys_of_bucket(M.BUCKET, M.NKEYS)
     for s in range(40):
         sd = seed + 104729 * s
-        c = B._filler(4096, sd).copy()
+        c = M.filler(4096, sd).copy()
         claim = {}
         # the sources from position qm on (position 0 where qm is 0): the eager ones, four old entries of the finishing cases' bucket, those
         at = 0 if qm == 0 else 4 + qm
         src = []
         for path in ("eager", "finish"):
             for i, L in enumerate(LENS + (24,)):                         # (the last one: the match at max_len 18, behind position 2048)
-                x = B._filler(L + 1, sd + 31 * i + (7 if path == "eager" else 11)).copy()
+                x = M.filler(L + 1, sd + 31 * i + (7 if path == "eager" else 11)).copy()
                 if path == "finish":
                     x[:3] = np.frombuffer(ks[40 + i], np.uint8)          # its own key of the one bucket: agrees with no other on 3 bytes
                 at += (qm - at) % 4
-                B._place(c, at, x)
+                M.place(c, at, x)
                 src.append((L, at, x, i == len(LENS)))
                 at += L + 3
             if path == "eager":                                          # (behind the eager sources, so that those stay among the four oldest)
                 for j in range(4):
-                    B._place(c, at, ks[j])
+                    M.place(c, at, ks[j])
                     at += 5
         assert at < 1000
         lo, hi = 1100, 2100
         for L, q, x, high in src:
             at = hi if high else lo
             at += (pm - at) % 4
-            B._place(c, at, x[:L])
+            M.place(c, at, x[:L])
             c[at + L] = x[L] ^ 0x55
-            claim[at] = min(L, B._maxlen(4096, at))
+            claim[at] = min(L, M.max_len(4096, at))
             assert claim[at] == (18 if high else min(L, 34))
             if high:
                 hi = at + L + 3
             else:
                 lo = at + L + 3
         assert lo < 2040 and hi < 2200
-        c[2300:4040] = np.resize(B._filler(24, sd + 5), 1740)            # (so that the chunk is not stored raw)
+        c[2300:4040] = np.resize(M.filler(24, sd + 5), 1740)            # (so that the chunk is not stored raw)
         q, p = 4080 + qm, 4088 + pm                                      # the candidate's 16 bytes straddle the chunk's end; max_len = n - p
         _copy(c, q, p, 4096 - p)
         claim[p] = 4096 - p
-        parse = E._parse(c)
+        parse = M.parse(c)
         if all(parse.get(p) == L for p, L in claim.items()):
-            fin = [p for p in claim if B._finish(c, p)["finish"]]
+            fin = [p for p in claim if M.finish(c, p)["finish"]]
             if len(fin) >= len(LENS):                                # (the second half went through finishing steps)
                 return c, claim
     raise AssertionError("no chunk for p mod 4 = %d, q mod 4 = %d" % (pm, qm))
@@ -86,33 +85,13 @@ def _built():
             out.append(("p mod 4 = %d, q mod 4 = %d" % (pm, qm), c.tobytes(), [claim]))
     first = _chunk(1, 2, 7777)[0]
     for k in SHORT:
-        tail = np.resize(B._filler(29, 600 + k), k).astype(np.uint8)     # a period of 29: matches at every alignment
+        tail = np.resize(M.filler(29, 600 + k), k).astype(np.uint8)     # a period of 29: matches at every alignment
         out.append(("short last chunk of %d bytes" % k, first.tobytes() + tail.tobytes(), [None, None]))
     return out
 
 
-def _chunk_streams(stream):
-    out, j = [], 0
-    while j + 2 <= len(stream):
-        hdr = stream[j] | (stream[j + 1] << 8)
-        if hdr == 0:
-            break
-        size = (hdr & 0xFFF) + 3
-        out.append(stream[j:j + size])
-        j += size
-    return out
-
-
-_ORACLE_OUT = {}
-
-
 def _expected(oracle):
-    if not _ORACLE_OUT:
-        for name, u, _ in _built():
-            es, exp = oracle.oracle_compress(LZNT1, u)
-            assert es == 0, name
-            _ORACLE_OUT[name] = exp
-    return _ORACLE_OUT
+    return {name: R.expected(oracle, u) for name, u, _ in _built()}
 
 
 def test_units_are_what_they_claim():
@@ -126,28 +105,23 @@ def test_units_are_what_they_claim():
 
 def test_the_oracle_parses_the_units_as_the_model_does(oracle):
     for name, u, claims in _built():
-        streams = _chunk_streams(_expected(oracle)[name])
+        streams = M.chunk_streams(_expected(oracle)[name])
         assert len(streams) == len(claims), name
         for k, (st, claim) in enumerate(zip(streams, claims)):
             chunk = np.frombuffer(u[4096 * k: 4096 * (k + 1)], np.uint8)
             if not st[1] & 0x80:                                         # stored raw: only the shortest chunks may be
                 assert len(chunk) <= 3, (name, k)
                 continue
-            got = E._oracle_token_starts(st)
-            assert got == E._parse(chunk), (name, k)
+            got = M.token_lengths(st)
+            assert got == M.parse(chunk), (name, k)
             for p, L in (claim or {}).items():
                 assert got.get(p) == L, (name, p, L, got.get(p))
         assert streams[0][1] & 0x80, name
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("path", ["host-tables", "device-tables", "serial-atomics"])
+@pytest.mark.parametrize("path", R.PATHS)
 @pytest.mark.parametrize("mode", [1, 2])
 def test_lznt1_alignments(oracle, gpu_ctx, mode, path):
     built = _built()
-    expected = _expected(oracle)
-    res = E._run(gpu_ctx, [u for _, u, _ in built], mode, path)
-    for (name, u, _), (s, g) in zip(built, res):
-        assert s == 0, (mode, path, name, s)
-        exp = expected[name]
-        assert g == exp, "mode %d, %s, %s (len %d): GPU bytes differ from the oracle (%d vs %d B)" % (mode, path, name, len(u), len(g), len(exp))
+    R.check_plan(oracle, gpu_ctx, [u for _, u, _ in built], mode, path, "alignments", names=[name for name, _, _ in built])

@@ -13,145 +13,13 @@ import functools
 import numpy as np
 import pytest
 
-LZNT1 = 2
-BITS = 12
-SELF = 4          # candidates a lane scans by itself; the wave finishes the rest 64 per step
-BUCKET = 3001
-
-
-def _hash(key24):
-    """the kernels' bucket of a 3-byte key (lznt1.hip lz_hash): bucket 0 stays empty, its keys go to bucket 1"""
-    h = ((key24 * 0x9E3779B1) & 0xFFFFFFFF) >> (32 - BITS)
-    return np.where(h == 0, 1, h)
-
-
-NKEYS = 160
-
-
-@functools.lru_cache(maxsize=None)
-def _keys():
-    """brute force over all 2^24 keys: NKEYS keys of BUCKET (as 3 bytes, little-endian) with three different bytes each"""
-    ks = np.flatnonzero(_hash(np.arange(1 << 24, dtype=np.uint64)) == BUCKET).astype(np.uint32)
-    out = []
-    for k in ks:
-        b = bytes([k & 0xFF, (k >> 8) & 0xFF, (k >> 16) & 0xFF])
-        if len(set(b)) == 3:
-            out.append(b)
-        if len(out) == NKEYS:
-            return out
-    raise AssertionError("bucket %d has fewer than %d keys" % (BUCKET, NKEYS))
-
-
-def _model(c):
-    """the sorted bucket array of a chunk: (array of positions by (hash, position), slot of every key position in it, its rank in its bucket)"""
-    c = np.asarray(c, dtype=np.uint32)
-    k = c[:-2] | (c[1:-1] << 8) | (c[2:] << 16)
-    h = _hash(k.astype(np.uint64))
-    pos = np.arange(len(h))
-    arr = np.lexsort((pos, h))
-    slot = np.empty(len(h), dtype=np.int64)
-    slot[arr] = pos
-    rank = slot - np.searchsorted(h[arr], h)
-    return arr, slot, rank
-
-
-def _lcp(c, q, p, lim):
-    n = 0
-    while n < lim and c[q + n] == c[p + n]:
-        n += 1
-    return n
-
-
-def _maxlen(n, p):
-    """max_len of position p of a chunk of n bytes (lznt1.hip lz_shift: the token split depends on the position)"""
-    shift = 12 if p <= 16 else 12 - ((p - 1).bit_length() - 4)
-    return min(n - p, (1 << shift) + 2)
-
-
-def _key(l, q):
-    return (l << 12) | (q ^ 4095)
-
-
-def _token_starts(c):
-    """the greedy parse of a chunk: the positions where a token starts (the best match of a position is the longest, at least 3 bytes, among the
-    older entries of its bucket)"""
-    n = len(c)
-    arr, slot, rank = _model(c)
-    c = np.concatenate([np.asarray(c, dtype=np.int32), np.full(4200, -1, np.int32)])
-    starts, p = set(), 0
-    while p < n:
-        starts.add(p)
-        best = 0
-        if p > 0 and p + 3 <= n and rank[p]:
-            q = arr[slot[p] - rank[p]:slot[p]]
-            lim = _maxlen(n, p)
-            while len(q) and best < lim:
-                q = q[c[q + best] == c[p + best]]
-                best += len(q) > 0
-        p += best if best >= 3 else 1
-    return starts
-
-
-def _finish(c, p):
-    """What the wave does when the greedy walk lands on position p, on the model of the bucket array: the eager scan of the four oldest
-    candidates (up to 16 bytes), the cooperative extension of those that reached 16 with max_len beyond, then the finishing steps, 64 candidates
-    each, the step that holds p's own entry the last. Per step: the threshold in bytes, the winners' lanes, whether the second compare stage
-    and the tail beyond 16 bytes run."""
-    n = len(c)
-    arr, slot, rank = _model(c)
-    r = int(rank[p])
-    cands = [int(q) for q in arr[slot[p] - r:slot[p]]]
-    maxl = _maxlen(n, p)
-    lens = [_lcp(c, q, p, maxl) for q in cands]
-    eager = list(zip(lens[:SELF], cands[:SELF]))
-    prov = max([_key(min(l, 16), q) for l, q in eager] + [0])            # the eager scan stops at 16 bytes
-    pending = maxl > 16 and any(l >= 16 for l, _ in eager)
-    unresolved = r > SELF and (prov >> 12) < maxl
-    best = max([prov] + [_key(l, q) for l, q in eager if l >= 16]) if pending else prov
-    res = {"rank": r, "cands": cands, "lens": lens, "maxl": maxl, "provisional": prov, "raised": best, "pending": pending,
-           "finish": unresolved and (best >> 12) < maxl, "steps": [], "left": 0}
-    if not res["finish"]:
-        res["best"] = best
-        return res
-    base = SELF
-    while True:
-        lanes = range(base, min(base + 64, r))
-        need = max((best >> 12) + 1, 3)
-        win = [j for j in lanes if lens[j] >= need]
-        res["steps"].append({"need": need, "winners": [j - base for j in win], "valid": len(lanes),
-                             "stage2": maxl > 8 and any(lens[j] >= 8 for j in lanes), "tail": maxl > 16 and any(lens[j] >= 16 for j in lanes)})
-        if win:
-            new = max(_key(lens[j], cands[j]) for j in win)
-            assert new > best
-            best = new
-        seen = max([res["raised"]] + [_key(lens[j], cands[j]) for j in range(min(base + 64, r))])
-        assert best == seen or (seen >> 12) < 3          # the same match as the maximum of the keys seen so far
-        if (best >> 12) == maxl or r < base + 64:
-            res["left"] = max(0, r - (base + 64))
-            break
-        base += 64
-    res["best"] = best
-    return res
+import lznt1_model as M
+import lznt1_run as R
+from lznt1_model import NKEYS, P18, P34, best_key as _key, filler as _filler, finish as _finish, place as _place
 
 
 def _kind(step):
     return ("none", "one", "several")[min(len(step["winners"]), 2)]
-
-
-def _filler(n, seed):
-    """random bytes whose trigrams are all different: every position a literal, no bucket fuller than chance makes it"""
-    for s in range(200):
-        r = np.random.default_rng(seed * 1000 + s).integers(0, 256, n, dtype=np.uint8)
-        if n < 3:
-            return r
-        k = r[:-2].astype(np.uint32) | (r[1:-1].astype(np.uint32) << 8) | (r[2:].astype(np.uint32) << 16)
-        if len(np.unique(k)) == len(k):
-            return r
-    raise AssertionError("no filler with distinct trigrams")
-
-
-def _place(c, at, b):
-    c[at:at + len(b)] = np.frombuffer(bytes(b), dtype=np.uint8)
 
 
 def _build(p, spec, seed, cut=None):
@@ -161,7 +29,7 @@ def _build(p, spec, seed, cut=None):
     cut: the chunk ends cut bytes behind p, and the candidates' bytes from `cut` on are zeros (what a compare past the end would look at)."""
     n = p + 64
     nc = len(spec)
-    ks = _keys()                                       # ks[j]: the colliding key of candidate j, ks[-1]: the position's own
+    ks = M.keys_of_bucket(M.BUCKET, NKEYS)                                       # ks[j]: the colliding key of candidate j, ks[-1]: the position's own
     assert nc < NKEYS
     for s in range(60):
         sd = seed + 7919 * s
@@ -191,13 +59,10 @@ def _build(p, spec, seed, cut=None):
             continue                                   # (a filler trigram fell into the bucket: next filler)
         if not all(l == w if w else l < 3 for l, w in zip(f["lens"], want)):
             continue
-        if p not in _token_starts(c):
+        if p not in M.greedy_token_starts(c):
             continue
         return c, f
     raise AssertionError("no unit for position %d, candidates %s" % (p, spec))
-
-
-P34, P18 = 1500, 3000                                  # target positions with max_len 34 and 18
 
 
 def _cases():
@@ -292,42 +157,15 @@ def test_units_are_one_or_two_chunks():
     assert all(len(u) <= 4096 * (1 + k) and k <= 1 for _, u, k, _ in _built())
 
 
-_expected = {}
-
-
-def _oracle_outputs(oracle, units):
-    """the oracle's bytes of every unit, computed once for both modes"""
-    if "out" not in _expected:
-        out = []
-        for i, u in enumerate(units):
-            es, exp = oracle.oracle_compress(LZNT1, u)
-            assert es == 0, (i, len(u), es)
-            out.append(exp)
-        _expected["out"] = out
-    return _expected["out"]
-
-
 def _chunk_is_compressed(stream, k):
     """whether chunk k of an LZNT1 stream is a compressed chunk (header bit 15), not a raw copy"""
-    at = 0
-    for _ in range(k):
-        at += 2 + (((stream[at] | stream[at + 1] << 8) & 0xFFF) + 1)
-    return bool(stream[at + 1] & 0x80)
+    return not list(M.walk_stream(stream))[k][2]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", [1, 2])
 def test_lznt1_finishing_steps_best(oracle, gpu_ctx, mode):
-    import ms_compress_amd as m
     built = _built()
-    units = [u for _, u, _, _ in built]
-    expected = _oracle_outputs(oracle, units)
-    gpu_ctx.lib.mscomp_amd_debug_set_lznt1(mode)
-    try:
-        got, st = m.compress_units(LZNT1, list(units), ctx=gpu_ctx)
-    finally:
-        gpu_ctx.lib.mscomp_amd_debug_set_lznt1(0)
-    for (name, u, k, _), g, s, exp in zip(built, got, st, expected):
-        assert s == 0, (name, len(u), s)
-        assert _chunk_is_compressed(exp, k), "%s: the target's chunk is stored raw and tests nothing" % name
-        assert g == exp, "mode %d, %s (len %d): GPU bytes differ from the oracle (%d vs %d B)" % (mode, name, len(u), len(g), len(exp))
+    for name, u, k, _ in built:
+        assert _chunk_is_compressed(R.expected(oracle, u), k), "%s: the target's chunk is stored raw and tests nothing" % name
+    R.check_batch(oracle, gpu_ctx, [u for _, u, _, _ in built], mode, 0, "finishing steps", names=[name for name, _, _, _ in built])

@@ -13,67 +13,15 @@ import functools
 import numpy as np
 import pytest
 
+import lznt1_model as M
+import lznt1_run as R
+from lznt1_model import BITS, bucket_model as _model, filler as _filler, keys_of_bucket as _keys, place as _place
+
 pytestmark = pytest.mark.gpu
-LZNT1 = 2
-BITS = 12
-SELF = 4          # candidates a lane scans by itself; the wave finishes the rest 64 per step
-
-
-def _hash(key24):
-    """the kernels' bucket of a 3-byte key (lznt1.hip lz_hash): bucket 0 stays empty, its keys go to bucket 1"""
-    h = ((key24 * 0x9E3779B1) & 0xFFFFFFFF) >> (32 - BITS)
-    return np.where(h == 0, 1, h)
-
-
-@functools.lru_cache(maxsize=None)
-def _all_hashes():
-    return _hash(np.arange(1 << 24, dtype=np.uint64))
-
-
-@functools.lru_cache(maxsize=None)
-def _keys(bucket, count):
-    """brute force over all 2^24 keys: `count` keys of `bucket` (as 3 bytes, little-endian) with three different bytes each"""
-    ks = np.flatnonzero(_all_hashes() == bucket).astype(np.uint32)
-    out = []
-    for k in ks:
-        b = bytes([k & 0xFF, (k >> 8) & 0xFF, (k >> 16) & 0xFF])
-        if len(set(b)) == 3:
-            out.append(b)
-        if len(out) == count:
-            return out
-    raise AssertionError("bucket %d has fewer than %d keys" % (bucket, count))
-
-
-def _model(c):
-    """the sorted bucket array of a chunk: (array of positions by (hash, position), slot of every key position in it, its rank in its bucket)"""
-    c = np.asarray(c, dtype=np.uint32)
-    k = c[:-2] | (c[1:-1] << 8) | (c[2:] << 16)
-    h = _hash(k.astype(np.uint64))
-    pos = np.arange(len(h))
-    arr = np.lexsort((pos, h))
-    slot = np.empty(len(h), dtype=np.int64)
-    slot[arr] = pos
-    rank = slot - np.searchsorted(h[arr], h)
-    return arr, slot, rank
 
 
 def _lcp(c, q, p):
-    n = 0
-    while p + n < len(c) and c[q + n] == c[p + n]:
-        n += 1
-    return n
-
-
-def _filler(n, seed):
-    """random bytes whose trigrams are all different: every position a literal, no bucket fuller than chance makes it"""
-    for s in range(200):
-        r = np.random.default_rng(seed * 1000 + s).integers(0, 256, n, dtype=np.uint8)
-        if n < 3:
-            return r
-        k = r[:-2].astype(np.uint32) | (r[1:-1].astype(np.uint32) << 8) | (r[2:].astype(np.uint32) << 16)
-        if len(np.unique(k)) == len(k):
-            return r
-    raise AssertionError("no filler with distinct trigrams")
+    return M.lcp(c, q, p, len(c) - p)
 
 
 def _repeats(c, lo, p, seed):
@@ -82,10 +30,6 @@ def _repeats(c, lo, p, seed):
     hi = p & ~63
     if hi - lo >= 48:
         c[lo:hi] = np.resize(_filler(24, seed + 5), hi - lo)
-
-
-def _place(c, at, b):
-    c[at:at + len(b)] = np.frombuffer(bytes(b), dtype=np.uint8)
 
 
 def _colliders(c, keys, first, stride):
@@ -223,32 +167,9 @@ def _units():
     return _validity_units() + _stage_units() + _split_units()
 
 
-_expected = {}
-
-
-def _oracle_outputs(oracle, units):
-    """the oracle's bytes of every unit, computed once for both modes"""
-    if "out" not in _expected:
-        out = []
-        for i, u in enumerate(units):
-            es, exp = oracle.oracle_compress(LZNT1, u)
-            assert es == 0, (i, len(u), es)
-            out.append(exp)
-        _expected["out"] = out
-    return _expected["out"]
-
-
 @pytest.mark.parametrize("mode", [1, 2])
 def test_lznt1_candidate_compares(oracle, gpu_ctx, mode):
-    import ms_compress_amd as m
     units = _units()
-    expected = _oracle_outputs(oracle, units)
-    gpu_ctx.lib.mscomp_amd_debug_set_lznt1(mode)
-    try:
-        got, st = m.compress_units(LZNT1, list(units), ctx=gpu_ctx)
-    finally:
-        gpu_ctx.lib.mscomp_amd_debug_set_lznt1(0)
-    for i, (u, g, s, exp) in enumerate(zip(units, got, st, expected)):
-        assert s == 0, (i, len(u), s)
-        assert len(u) < 256 or exp[1] & 0x80, "unit %d (len %d): its first chunk is stored raw and tests nothing" % (i, len(u))
-        assert g == exp, "mode %d unit %d (len %d): GPU bytes differ from the oracle (%d vs %d B)" % (mode, i, len(u), len(g), len(exp))
+    for i, u in enumerate(units):
+        assert len(u) < 256 or R.expected(oracle, u)[1] & 0x80, "unit %d (len %d): its first chunk is stored raw and tests nothing" % (i, len(u))
+    R.check_batch(oracle, gpu_ctx, units, mode, 0, "candidate compares")

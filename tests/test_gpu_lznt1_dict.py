@@ -5,36 +5,15 @@ seam-stress units of the four-wave kernel."""
 import numpy as np
 import pytest
 
+import lznt1_run as R
+from lznt1_model import BITS, keys_by_bucket as _keys_by_bucket, straddling_buckets as _straddling_buckets
+
 pytestmark = pytest.mark.gpu
-LZNT1 = 2
-BITS = 12
-
-
-def _hash(key24):
-    """the kernels' bucket of a 3-byte key (lznt1.hip lz_hash): bucket 0 stays empty, its keys go to bucket 1"""
-    h = ((key24 * 0x9E3779B1) & 0xFFFFFFFF) >> (32 - BITS)
-    return np.where(h == 0, 1, h)
-
-
-def _keys_by_bucket(targets, per_bucket):
-    """brute force over all 2^24 keys: up to `per_bucket` keys (as 3 bytes, little-endian) for every target bucket"""
-    keys = np.arange(1 << 24, dtype=np.uint64)
-    h = _hash(keys)
-    out = {}
-    for t in targets:
-        ks = keys[h == t][:per_bucket].astype(np.uint32)
-        out[t] = [bytes([k & 0xFF, (k >> 8) & 0xFF, (k >> 16) & 0xFF]) for k in ks]
-    return out
-
-
-def _straddling_buckets():
-    """buckets h whose two ends (bits 12 (h - 1) .. 12 (h + 1) of the packed table) cross a dword boundary"""
-    return [h for h in range(2, 1 << BITS) if (12 * (h - 1)) % 32 + 24 > 32][:6]
 
 
 def _units():
     rng = np.random.default_rng(12)
-    targets = [1, 2, (1 << BITS) - 1] + _straddling_buckets()
+    targets = [1, 2, (1 << BITS) - 1] + _straddling_buckets(6)
     kb = _keys_by_bucket(targets, 6)
     assert all(len(v) == 6 for v in kb.values())
     units = []
@@ -49,7 +28,7 @@ def _units():
     # all target buckets mixed, and pairs of neighbouring buckets (h - 1, h)
     allk = [k for t in targets for k in kb[t]]
     units.append(np.frombuffer(b"".join(allk[i] for i in rng.integers(0, len(allk), 6000)), dtype=np.uint8))
-    for h in _straddling_buckets()[:3]:
+    for h in _straddling_buckets(6)[:3]:
         pair = _keys_by_bucket([h - 1, h], 4)
         ks = pair[h - 1] + pair[h]
         units.append(np.frombuffer(b"".join(ks[i] for i in rng.integers(0, len(ks), 2500)), dtype=np.uint8))
@@ -78,14 +57,4 @@ def _units():
 
 @pytest.mark.parametrize("mode", [1, 2])
 def test_lznt1_dictionary_buckets(oracle, gpu_ctx, mode):
-    import ms_compress_amd as m
-    units = _units()
-    gpu_ctx.lib.mscomp_amd_debug_set_lznt1(mode)
-    try:
-        got, st = m.compress_units(LZNT1, units, ctx=gpu_ctx)
-    finally:
-        gpu_ctx.lib.mscomp_amd_debug_set_lznt1(0)
-    for i, (u, g, s) in enumerate(zip(units, got, st)):
-        es, exp = oracle.oracle_compress(LZNT1, u)
-        assert es == 0 and s == 0, (i, len(u), s)
-        assert g == exp, "mode %d unit %d (len %d): GPU bytes differ from the oracle (%d vs %d B)" % (mode, i, len(u), len(g), len(exp))
+    R.check_batch(oracle, gpu_ctx, _units(), mode, 0, "dictionary buckets")

@@ -4,7 +4,7 @@ into its lane, takes the match or steps over the position as a literal and finds
 walk leaves without a flag, the step loop keeps its threshold across steps and ends on one compare, the epilogue is one block that relies on
 shift counts wrapping. The units here put one event (or two, or three) on every edge of that code: where in the window it happens, where its
 match ends, what follows it, how the bucket's entries fall into steps, how the threshold moves, and the long-pending stops.
-Every unit is one chunk. Each builder places its positions on the CPU model of the bucket array that tests/test_gpu_lznt1_best.py keeps, proves
+Every unit is one chunk. Each builder places its positions on the CPU model of the bucket array that tests/lznt1_model.py keeps, proves
 there that the unit is what it claims (a unit that is not fails the CPU test), and the GPU tests compare all units with the oracle byte for byte
 in both chunk-kernel modes, through a plan with host tables, a plan with device tables and the serial-atomics instance."""
 import functools
@@ -12,82 +12,49 @@ import functools
 import numpy as np
 import pytest
 
-import test_gpu_lznt1_best as B                      # the CPU model: hash, sorted bucket array, eager scan, finishing steps, greedy parse
+import lznt1_model as M
+import lznt1_run as R
+from lznt1_model import BUCKET, NKEYS, P18, P34, SELF, parse as _parse
 
-LZNT1 = 2
-GUARD = 0xEE
-SELF = B.SELF
-LAST = 4095                                          # the last bucket: its youngest entry is the last slot of the bucket array
-SEAM = 21 * 64                                       # first position of segment 1 (lznt1.hip LZ4_B1: windows of 64 positions)
-P34 = B.P34                                          # max_len 34, lane 28 of its window
-
-
-@functools.lru_cache(maxsize=None)
-def _keys_of(bucket):
-    """B.NKEYS keys of a bucket (3 bytes, little-endian) with three different bytes each"""
-    if bucket == B.BUCKET:
-        return B._keys()
-    ks = np.flatnonzero(B._hash(np.arange(1 << 24, dtype=np.uint64)) == bucket).astype(np.uint32)
-    out = [bytes([k & 0xFF, (k >> 8) & 0xFF, (k >> 16) & 0xFF]) for k in ks]
-    out = [b for b in out if len(set(b)) == 3][:B.NKEYS]
-    assert len(out) == B.NKEYS
-    return out
-
-
-def _parse(c):
-    """the greedy parse of a chunk on the model: {token start: match length, 0 for a literal}"""
-    n = len(c)
-    arr, slot, rank = B._model(c)
-    c = np.concatenate([np.asarray(c, dtype=np.int32), np.full(4200, -1, np.int32)])
-    out, p = {}, 0
-    while p < n:
-        best = 0
-        if p > 0 and p + 3 <= n and rank[p]:
-            q = arr[slot[p] - rank[p]:slot[p]]
-            lim = B._maxlen(n, p)
-            while len(q) and best < lim:
-                q = q[c[q + best] == c[p + best]]
-                best += len(q) > 0
-        out[p] = best if best >= 3 else 0
-        p += best if best >= 3 else 1
-    return out
+LAST = (1 << M.BITS) - 1                             # the last bucket: its youngest entry is the last slot of the bucket array
+SEAM = 64 * M.SEG_FIRST_WINDOW[1]                    # first position of segment 1
 
 
 def _copies(b, after, k=6):
     """a `pre` step of _unit: k copies of the bytes b behind the candidates, each followed by a byte that differs from `after`"""
     def put(c, at):
         for _ in range(k):
-            B._place(c, at, b)
+            M.place(c, at, b)
             c[at + len(b)] = after ^ 0x55
             at += len(b) + 4
         return at
     return put
 
 
-def _unit(p, spec, seed, cut=None, fill_to=None, bucket=B.BUCKET, xpatch=None, pre=None, check=None):
-    """B._build with three more handles. A chunk of p + 64 bytes whose position p has len(spec) older entries in its bucket, oldest first: 0 = a
+def _unit(p, spec, seed, cut=None, fill_to=None, bucket=BUCKET, xpatch=None, pre=None, check=None):
+    """_build of tests/test_gpu_lznt1_best.py with three more handles. A chunk of p + 64 bytes whose position p has len(spec) older entries in its bucket, oldest first: 0 = a
     position of another key of the bucket, L >= 3 = a position that agrees with p on exactly L bytes; a 24-byte block repeats between the
     candidates and fill_to (default: the start of p's window, which then holds filler in front of p).
     xpatch(x, c): changes the bytes x that will stand at p, before the candidates copy them; pre(x) -> put(c, at): places more bytes behind
     the candidates; check(f, c, parse): what the unit claims, on the model -- a filler that misses it is replaced by the next."""
     n = p + 64
     nc = len(spec)
-    ks = _keys_of(bucket)
-    assert nc < B.NKEYS
+    ks = M.keys_of_bucket(bucket, NKEYS)
+    assert nc < NKEYS
     for s in range(80):
         sd = seed + 7919 * s
-        c = B._filler(n, sd).copy()
-        x = np.concatenate([np.frombuffer(ks[-1], dtype=np.uint8), B._filler(60, sd + 13)]).copy()
+        c = M.filler(n, sd).copy()
+        x = np.concatenate([np.frombuffer(ks[-1], dtype=np.uint8), M.filler(60, sd + 13)]).copy()
         if xpatch is not None:
             xpatch(x, c)
         at, where = 8, []
         for j, L in enumerate(spec):
             where.append(at)
             if L == 0:
-                B._place(c, at, ks[j])
+                M.place(c, at, ks[j])
                 at += 6
             else:
-                B._place(c, at, x[:L])
+                M.place(c, at, x[:L])
                 c[at + L] = x[L] ^ 0x55
                 if cut is not None:
                     c[at + cut:at + L + 1] = 0
@@ -96,11 +63,11 @@ def _unit(p, spec, seed, cut=None, fill_to=None, bucket=B.BUCKET, xpatch=None, p
             at = pre(x)(c, at)
         hi = p & ~63 if fill_to is None else fill_to
         assert hi - (at + 8) >= 48, "no room for the repeats in front of position %d" % p
-        c[at + 8:hi] = np.resize(B._filler(24, sd + 5), hi - (at + 8))
-        B._place(c, p, x[:min(len(x), n - p)])
+        c[at + 8:hi] = np.resize(M.filler(24, sd + 5), hi - (at + 8))
+        M.place(c, p, x[:min(len(x), n - p)])
         if cut is not None:
             c = c[:p + cut].copy()
-        f = B._finish(c, p)
+        f = M.finish(c, p)
         want = [min(L, cut) if cut is not None and L else L for L in spec]
         if f["rank"] != nc or f["cands"] != where:
             continue
@@ -151,10 +118,10 @@ def _cases():
     add("the event leaves a literal, the next stop is the next position", P34, Z * 7,
         lambda f, c, t: _event(f) and lens(f) < 3 and t[P34] == 0 and t.get(P34 + 1, 0) >= 3, pre=lambda x: _copies(x[1:5], int(x[5]), k=1))
     add("two events at adjacent positions", P34, Z * 7,
-        lambda f, c, t: _event(f) and t[P34] == 0 and _event(B._finish(c, P34 + 1)) and t.get(P34 + 1, 0) == 3,
+        lambda f, c, t: _event(f) and t[P34] == 0 and _event(M.finish(c, P34 + 1)) and t.get(P34 + 1, 0) == 3,
         pre=lambda x: _copies(x[1:4], int(x[4])))
     add("three events in one window with taken matches between them", P34, ONE,
-        lambda f, c, t: _event(f) and _event(B._finish(c, P34 + 6)) and _event(B._finish(c, P34 + 11))
+        lambda f, c, t: _event(f) and _event(M.finish(c, P34 + 6)) and _event(M.finish(c, P34 + 11))
         and (t.get(P34), t.get(P34 + 6), t.get(P34 + 11)) == (6, 5, 4) and (P34 + 15) // 64 == P34 // 64,
         pre=lambda x: (lambda c, at: _copies(x[11:15], int(x[15]))(c, _copies(x[6:11], int(x[11]))(c, at))))
     # -- bucket geometry of the step loop
@@ -167,14 +134,14 @@ def _cases():
     add("4 + 65 older entries", P34, Z * 4 + Z * 64 + [6],
         lambda f, c, t: _event(f) and [s["valid"] for s in f["steps"]] == [64, 1] and f["steps"][1]["winners"] == [0])
     add("the own entry is the last slot of the bucket array", P34, ONE,
-        lambda f, c, t: _event(f) and B._model(c)[1][P34] == len(c) - 3 and lens(f) == 6, bucket=LAST)
+        lambda f, c, t: _event(f) and M.bucket_model(c)[1][P34] == len(c) - 3 and lens(f) == 6, bucket=LAST)
     # -- the threshold and the early exit
     add("a winner in step 1 that step 2 beats by one byte", P34, [3, 0, 0, 0, 5] + Z * 63 + [6],
         lambda f, c, t: _event(f) and [s["need"] for s in f["steps"]] == [4, 6] and [len(s["winners"]) for s in f["steps"]] == [1, 1] and lens(f) == 6)
     add("a winner in step 1 that step 2 only ties", P34, [3, 0, 0, 0, 5] + Z * 63 + [5],
         lambda f, c, t: _event(f) and [s["need"] for s in f["steps"]] == [4, 6] and [len(s["winners"]) for s in f["steps"]] == [1, 0]
-        and f["best"] == B._key(5, f["cands"][4]))
-    add("a winner reaches max_len with candidates left behind", B.P18, Z * 4 + [0, 18, 0] + Z * 70,
+        and f["best"] == M.best_key(5, f["cands"][4]))
+    add("a winner reaches max_len with candidates left behind", P18, Z * 4 + [0, 18, 0] + Z * 70,
         lambda f, c, t: _event(f) and lens(f) == f["maxl"] == 18 and f["left"] > 0 and len(f["steps"]) == 1)
     for m in (3, 8, 9, 16, 17):
         add("max_len %d at the event" % m, 1500 - m, Z * 4 + [0, 30, 0], lambda f, c, t, m=m: _event(f) and lens(f) == f["maxl"] == m, cut=m)
@@ -202,113 +169,25 @@ def test_units_are_what_they_claim():
     assert len({u for _, u in built}) == len(built)
 
 
-_ORACLE_OUT = {}
-
-
 def _expected(oracle):
-    """the oracle's bytes of every unit, computed once for all modes and paths"""
-    if not _ORACLE_OUT:
-        for name, u in _built():
-            es, exp = oracle.oracle_compress(LZNT1, u)
-            assert es == 0, name
-            assert exp[1] & 0x80, "%s: the chunk is stored raw and tests nothing" % name
-            _ORACLE_OUT[name] = exp
-    return _ORACLE_OUT
-
-
-def _oracle_token_starts(stream):
-    """{token start: match length, 0 for a literal} of the one compressed chunk of an LZNT1 stream"""
-    hdr = stream[0] | (stream[1] << 8)
-    end = 2 + (hdr & 0xFFF) + 1
-    out, pos, j = {}, 0, 2
-    while j < end:
-        flags = stream[j]
-        j += 1
-        for b in range(8):
-            if j >= end:
-                break
-            if (flags >> b) & 1:
-                tok = stream[j] | (stream[j + 1] << 8)
-                j += 2
-                shift = 12 if pos <= 16 else 12 - ((pos - 1).bit_length() - 4)
-                out[pos] = (tok & ((1 << shift) - 1)) + 3
-                pos += out[pos]
-            else:
-                out[pos] = 0
-                j += 1
-                pos += 1
+    """{name: the oracle's bytes of the unit}"""
+    out = {name: R.expected(oracle, u) for name, u in _built()}
+    for name, exp in out.items():
+        assert exp[1] & 0x80, "%s: the chunk is stored raw and tests nothing" % name
     return out
 
 
 def test_the_oracle_parses_the_units_as_the_model_does(oracle):
     """what the builders proved on the model holds for the oracle's stream: the same token starts and match lengths"""
+    expected = _expected(oracle)
     for name, u in _built():
-        got = _oracle_token_starts(_expected(oracle)[name])
-        assert got == _parse(np.frombuffer(u, np.uint8)), name
-
-
-def _dt(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).copy()).cuda()
-
-
-def _run(gpu_ctx, units, mode, path):
-    """one batch of all units through one plan: [(status, output bytes)] per unit; input offsets odd, guard bytes between the capacities"""
-    import torch
-    import ms_compress_amd as m
-    in_off, pos = [], 1
-    for u in units:
-        in_off.append(pos)
-        pos += len(u)
-        pos += 1 if pos % 2 == 0 else 2
-    blob = np.zeros(pos + 32, np.uint8)
-    for u, o in zip(units, in_off):
-        blob[o: o + len(u)] = np.frombuffer(u, np.uint8)
-    caps = [m.max_compressed_size(LZNT1, len(u)) + 2 for u in units]
-    out_off, total = [], 16
-    for cp in caps:
-        out_off.append(total)
-        total += cp + 16
-    in_off, lens, out_off, caps = (np.array(a, np.uint64) for a in (in_off, [len(u) for u in units], out_off, caps))
-    n = len(units)
-    d_in = torch.from_numpy(blob).cuda()
-    d_out = torch.full((total,), GUARD, dtype=torch.uint8, device="cuda")
-    d_len = torch.full((n,), -1, dtype=torch.int64, device="cuda")
-    d_st = torch.full((n,), 77, dtype=torch.int32, device="cuda")
-    lib = gpu_ctx.lib
-    if path == "device-tables":
-        plan = m.CompressDevPlan(gpu_ctx, LZNT1, n, int(lens.sum()) + 8 * 4096, int(lens.max()))
-        tabs = [_dt(a) for a in (in_off, lens, out_off, caps)]
-    else:
-        plan = m.Plan(gpu_ctx, LZNT1, in_off, lens, out_off, caps)
-    lib.mscomp_amd_debug_set_lznt1(mode)
-    lib.mscomp_amd_debug_set_serial_atomics(1 if path == "serial-atomics" else 0)
-    try:
-        if path == "device-tables":
-            plan.execute(d_in, tabs[0], tabs[1], d_out, tabs[2], tabs[3], d_len, d_st)
-        else:
-            plan.execute(d_in, d_out, d_len, d_st)
-        torch.cuda.synchronize()
-        ln, st, out = d_len.cpu().numpy(), d_st.cpu().numpy(), d_out.cpu().numpy()
-    finally:
-        lib.mscomp_amd_debug_set_lznt1(0)
-        lib.mscomp_amd_debug_set_serial_atomics(0)
-        plan.close()
-    inside = np.zeros(len(out), bool)
-    for o, cp in zip(out_off, caps):
-        inside[int(o): int(o) + int(cp)] = True
-    assert (out[~inside] == GUARD).all(), (mode, path, np.nonzero(out[~inside] != GUARD)[0][:8])
-    return [(int(s), bytes(out[int(o): int(o) + max(int(l), 0)])) for s, l, o in zip(st, ln, out_off)]
+        assert M.token_lengths(expected[name]) == _parse(np.frombuffer(u, np.uint8)), name
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("path", ["host-tables", "device-tables", "serial-atomics"])
+@pytest.mark.parametrize("path", R.PATHS)
 @pytest.mark.parametrize("mode", [1, 2])
 def test_lznt1_finishing_event(oracle, gpu_ctx, mode, path):
     built = _built()
-    expected = _expected(oracle)
-    res = _run(gpu_ctx, [u for _, u in built], mode, path)
-    for (name, u), (s, g) in zip(built, res):
-        assert s == 0, (mode, path, name, s)
-        exp = expected[name]
-        assert g == exp, "mode %d, %s, %s (len %d): GPU bytes differ from the oracle (%d vs %d B)" % (mode, path, name, len(u), len(g), len(exp))
+    _expected(oracle)
+    R.check_plan(oracle, gpu_ctx, [u for _, u in built], mode, path, "finishing event", names=[name for name, _ in built])

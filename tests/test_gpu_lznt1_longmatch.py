@@ -6,14 +6,10 @@ of the four-wave kernel, ragged last chunks, and pieces of the long-repeat corpu
 import numpy as np
 import pytest
 
+import lznt1_run as R
+from lznt1_model import max_len
+
 pytestmark = pytest.mark.gpu
-LZNT1 = 2
-
-
-def _max_len(p, n=4096):
-    """lznt1.hip lz_window: max_len of position p (> 0) of a chunk of n bytes"""
-    shift = 12 if p <= 16 else 12 - ((p - 1).bit_length() - 4)
-    return min(n - p, (1 << shift) + 2)
 
 
 def _repeat(rng, p0, dist, length, n=4096):
@@ -31,7 +27,7 @@ def _units():
     units = []
     # one start in every max_len regime; lengths around 16 bytes, the 256-byte steps and max_len
     for p0 in (1, 5, 16, 17, 20, 32, 40, 64, 100, 128, 200, 256, 300, 512, 700, 1024, 1500, 2048, 3000, 4000):
-        ml = _max_len(p0)
+        ml = max_len(4096, p0)
         for length in sorted({15, 16, 17, 18, 255, 256, 257, 271, 272, 273, ml - 1, ml, ml + 1, 4096 - p0}):
             if length < 1 or p0 + length > 4096:
                 continue
@@ -80,14 +76,4 @@ def _corpus_pieces():
 
 @pytest.mark.parametrize("mode", [1, 2])
 def test_lznt1_long_matches(oracle, gpu_ctx, mode):
-    import ms_compress_amd as m
-    units = _units() + _corpus_pieces()
-    gpu_ctx.lib.mscomp_amd_debug_set_lznt1(mode)
-    try:
-        got, st = m.compress_units(LZNT1, units, ctx=gpu_ctx)
-    finally:
-        gpu_ctx.lib.mscomp_amd_debug_set_lznt1(0)
-    for i, (u, g, s) in enumerate(zip(units, got, st)):
-        es, exp = oracle.oracle_compress(LZNT1, u)
-        assert es == 0 and s == 0, (i, len(u), s)
-        assert g == exp, "mode %d unit %d (len %d): GPU bytes differ from the oracle (%d vs %d B)" % (mode, i, len(u), len(g), len(exp))
+    R.check_batch(oracle, gpu_ctx, _units() + _corpus_pieces(), mode, 0, "long matches")

@@ -4,7 +4,7 @@ wave-uniform. The units here walk those loops' edges: a match that covers one, t
 exactly at a window's end and one byte behind it, chunks of 1, 21, 22, 38, 52 and 64 windows (the segment boundaries and their neighbours),
 two chunks in which a match crosses every segment boundary (all three seams repaired), and one adversarial chunk whose speculative parse of
 segment 1 never meets the true one, so that the repair runs through the whole segment and wave 0's cascade re-walk takes over behind it.
-Every claim is shown on the CPU model of the bucket array that tests/test_gpu_lznt1_best.py keeps (the speculative parse of a segment is the
+Every claim is shown on the CPU model of the bucket array that tests/lznt1_model.py keeps (the speculative parse of a segment is the
 same greedy parse started at the segment's first position); the oracle's token starts and lengths must equal the model's, and the GPU tests
 compare byte for byte with the oracle in both kernel modes through a host-table plan, a device-table plan and the serial-atomics instance."""
 import functools
@@ -12,12 +12,10 @@ import functools
 import numpy as np
 import pytest
 
-import test_gpu_lznt1_best as B                      # the CPU model
-import test_gpu_lznt1_event as E                     # _parse, _oracle_token_starts, _run
-from test_gpu_lznt1_align import _chunk_streams
+import lznt1_model as M
+import lznt1_run as R
 
-LZNT1 = 2
-SEG = (0, 21, 38, 52, 64)                            # first windows of the segments (lznt1.hip LZ4_B1 .. LZ4_B3)
+SEG = M.SEG_FIRST_WINDOW                             # first windows of the segments, and the chunk's end
 
 
 def _text(n, seed):
@@ -39,21 +37,12 @@ def _periodic(c, p, L, d=7):
 
 def _after_windows(c, entry, w0, w1):
     """the greedy parse from `entry` over windows [w0, w1): the parse position after each window, as the kernel records it"""
-    n = len(c)
-    arr, slot, rank = B._model(c)
-    cc = np.concatenate([np.asarray(c, dtype=np.int32), np.full(4200, -1, np.int32)])
+    match = M.greedy_match(c)
     out, p = [], entry
     for w in range(w0, w1):
-        wend = min(64 * w + 64, n)
+        wend = min(64 * w + 64, len(c))
         while p < wend:
-            best = 0
-            if p > 0 and p + 3 <= n and rank[p]:
-                q = arr[slot[p] - rank[p]:slot[p]]
-                lim = B._maxlen(n, p)
-                while len(q) and best < lim:
-                    q = q[cc[q + best] == cc[p + best]]
-                    best += len(q) > 0
-            p += best if best >= 3 else 1
+            p += match(p) or 1
         out.append(p)
     return out
 
@@ -61,11 +50,11 @@ def _after_windows(c, entry, w0, w1):
 def _skip_unit(windows, seed):
     """a match that covers `windows` whole windows; returns (chunk, its start, its length)"""
     for s in range(40):
-        c = B._filler(2200, seed + 7919 * s).copy()
+        c = M.filler(2200, seed + 7919 * s).copy()
         p, L = (124, 64 * windows + 10) if windows <= 2 else (17, 64 * windows + 80)   # (max_len 514 at 124, 2050 at 17)
         _periodic(c, p, L)
-        c[p + L + 40:] = np.resize(B._filler(24, seed + 5), len(c) - (p + L + 40))
-        t = E._parse(c)
+        c[p + L + 40:] = np.resize(M.filler(24, seed + 5), len(c) - (p + L + 40))
+        t = M.parse(c)
         whole = [w for w in range(len(c) // 64) if p < 64 * w and 64 * w + 64 <= p + L]
         if t.get(p) == L and len(whole) == windows and (p + L) % 64 not in (0, 1):
             return c, p, L
@@ -75,12 +64,12 @@ def _skip_unit(windows, seed):
 def _end_unit(behind, seed):
     """a match that ends exactly at a window's end (behind = 0) or one byte behind it (1)"""
     for s in range(40):
-        c = B._filler(1024, seed + 7919 * s).copy()
+        c = M.filler(1024, seed + 7919 * s).copy()
         p = 300
         L = 320 + behind - p
         _periodic(c, p, L)
-        c[400:] = np.resize(B._filler(24, seed + 5), len(c) - 400)
-        t = E._parse(c)
+        c[400:] = np.resize(M.filler(24, seed + 5), len(c) - 400)
+        t = M.parse(c)
         if t.get(p) == L and (p + L) % 64 == behind:
             return c, p, L
     raise AssertionError("no unit")
@@ -92,7 +81,7 @@ def _seams_unit(seed):
         u = _text(8192, seed + s)
         ok = True
         for k in range(2):
-            t = E._parse(u[4096 * k: 4096 * k + 4096])
+            t = M.parse(u[4096 * k: 4096 * k + 4096])
             ok = ok and all(64 * w not in t for w in SEG[1:4])
         if ok:
             return u
@@ -102,7 +91,7 @@ def _seams_unit(seed):
 def _cascade_unit(seed):
     """filler, then one byte repeated from position 1100 on: back-to-back matches of max_len, so a parse that starts at another position never
     meets the true one. The speculative parse of segment 1 (from position 64 * 21) differs from the true parse behind EVERY window of the segment."""
-    c = B._filler(4096, seed).copy()
+    c = M.filler(4096, seed).copy()
     c[1100:] = 0x41
     true = _after_windows(c, 0, 0, 64)
     spec = _after_windows(c, 64 * SEG[1], SEG[1], SEG[2])
@@ -128,16 +117,8 @@ def _built():
     return out
 
 
-_ORACLE_OUT = {}
-
-
 def _expected(oracle):
-    if not _ORACLE_OUT:
-        for name, u in _built():
-            es, exp = oracle.oracle_compress(LZNT1, u)
-            assert es == 0, name
-            _ORACLE_OUT[name] = exp
-    return _ORACLE_OUT
+    return {name: R.expected(oracle, u) for name, u in _built()}
 
 
 def test_units_are_what_they_claim():
@@ -148,21 +129,16 @@ def test_units_are_what_they_claim():
 
 def test_the_oracle_parses_the_units_as_the_model_does(oracle):
     for name, u in _built():
-        streams = _chunk_streams(_expected(oracle)[name])
+        streams = M.chunk_streams(_expected(oracle)[name])
         assert len(streams) == (len(u) + 4095) // 4096, name
         for k, st in enumerate(streams):
             assert st[1] & 0x80, "%s: chunk %d is stored raw and tests nothing" % (name, k)
-            assert E._oracle_token_starts(st) == E._parse(np.frombuffer(u[4096 * k: 4096 * (k + 1)], np.uint8)), (name, k)
+            assert M.token_lengths(st) == M.parse(np.frombuffer(u[4096 * k: 4096 * (k + 1)], np.uint8)), (name, k)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("path", ["host-tables", "device-tables", "serial-atomics"])
+@pytest.mark.parametrize("path", R.PATHS)
 @pytest.mark.parametrize("mode", [1, 2])
 def test_lznt1_window_loops(oracle, gpu_ctx, mode, path):
     built = _built()
-    expected = _expected(oracle)
-    res = E._run(gpu_ctx, [u for _, u in built], mode, path)
-    for (name, u), (s, g) in zip(built, res):
-        assert s == 0, (mode, path, name, s)
-        exp = expected[name]
-        assert g == exp, "mode %d, %s, %s (len %d): GPU bytes differ from the oracle (%d vs %d B)" % (mode, path, name, len(u), len(g), len(exp))
+    R.check_plan(oracle, gpu_ctx, [u for _, u in built], mode, path, "window loops", names=[name for name, _ in built])

@@ -12,54 +12,16 @@ import numpy as np
 import pytest
 
 import cases
+import lznt1_model as M
+import lznt1_run as R
 import thresholds
+from lznt1_model import MAXM, PART_FIRST, keys_with_raw_hash as _keys_with_raw_hash, noise as _noise, place_key as _place
+from lznt1_run import expected as _expected
 
 pytestmark = pytest.mark.gpu
-LZNT1 = 2
-BITS = 12
-P1, P2 = 15 * 64, 39 * 64                            # first position of parts 1 and 2 (lznt1.hip LZ4_P1, LZ4_P2: batches of 64 positions)
+P1, P2 = PART_FIRST[1:]                              # first position of parts 1 and 2
 PARTS = ((0, P1), (P1, P2), (P2, 4096))
-MAXM = 22                                            # matches that can start in one window (lznt1.hip LZ4_MAXM)
 MODES = pytest.mark.parametrize("mode,serial", [(2, 0), (2, 1), (1, 0)])
-
-
-def _noise(seed, n=4096):
-    return bytearray(np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes())
-
-
-def _place(seed, key, positions, n=4096):
-    d = _noise(seed, n)
-    for p in positions:
-        d[p:p + 3] = key
-    return bytes(d[:n])
-
-
-_ORACLE_OUT = {}
-
-
-def _expected(oracle, u):
-    """the oracle's bytes of a unit, computed once per unit and shared by every test and mode"""
-    if u not in _ORACLE_OUT:
-        es, exp = oracle.oracle_compress(LZNT1, u)
-        assert es == 0
-        _ORACLE_OUT[u] = exp
-    return _ORACLE_OUT[u]
-
-
-def _check(oracle, gpu_ctx, units, mode, serial, what):
-    import ms_compress_amd as m
-    lib = gpu_ctx.lib
-    lib.mscomp_amd_debug_set_lznt1(mode)
-    lib.mscomp_amd_debug_set_serial_atomics(serial)
-    try:
-        got, st = m.compress_units(LZNT1, units, ctx=gpu_ctx)
-    finally:
-        lib.mscomp_amd_debug_set_lznt1(0)
-        lib.mscomp_amd_debug_set_serial_atomics(0)
-    for i, (u, g, s) in enumerate(zip(units, got, st)):
-        exp = _expected(oracle, u)
-        assert s == 0, (what, i, len(u), s)
-        assert g == exp, "%s, mode %d, serial %d, unit %d (len %d): GPU bytes differ from the oracle (%d vs %d B)" % (what, mode, serial, i, len(u), len(g), len(exp))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -98,25 +60,6 @@ def _occurrences_at_the_boundaries():
         d[b - 1:b + 3] = b"\xEE\xEE\xEE\xEE"                                             # the key at b - 1 and at b alone, overlapping
         units.append(bytes(d))
     return units
-
-
-def _raw_hash(key24):
-    return ((key24 * 0x9E3779B1) & 0xFFFFFFFF) >> (32 - BITS)
-
-
-_KEYS = {}
-
-
-def _keys_with_raw_hash(targets, per_bucket):
-    """brute force over all 2^24 keys, once: `per_bucket` keys (3 bytes, little-endian) per target value of the hash BEFORE 0 is mapped to 1"""
-    if not _KEYS:
-        keys = np.arange(1 << 24, dtype=np.uint64)
-        h = _raw_hash(keys)
-        for t in targets:
-            ks = keys[h == t][:per_bucket].astype(np.uint32)
-            assert len(ks) == per_bucket
-            _KEYS[t] = [bytes([int(k) & 0xFF, (int(k) >> 8) & 0xFF, (int(k) >> 16) & 0xFF]) for k in ks]
-    return _KEYS
 
 
 def _hash_0_1_4095():
@@ -162,28 +105,13 @@ def _trigram_chunk(shift=0, n=4096):
 
 def _match_counts_per_window(comp, n):
     """from the oracle's bytes of ONE compressed chunk: (tokens, list of match starts per window of 64 positions)"""
-    hdr = comp[0] | (comp[1] << 8)
-    assert hdr & 0x8000, "chunk stored raw"
-    end = 2 + (hdr & 0xFFF) + 1
-    i, pos, T = 2, 0, 0
+    _, _, raw, tokens = next(M.walk_stream(comp))
+    assert not raw, "chunk stored raw"
+    assert tokens[-1][0] + (tokens[-1][1] or 1) == n, (tokens[-1], n)
     per = [0] * ((n + 63) // 64)
-    while i < end:
-        flags = comp[i]; i += 1
-        for b in range(8):
-            if i >= end:
-                break
-            T += 1
-            if flags >> b & 1:
-                tok = comp[i] | (comp[i + 1] << 8); i += 2
-                sh = 12
-                while sh > 4 and (1 << (16 - sh)) < pos:
-                    sh -= 1
-                per[pos // 64] += 1
-                pos += (tok & ((1 << sh) - 1)) + 3
-            else:
-                i += 1; pos += 1
-    assert pos == n, (pos, n)
-    return T, per
+    for pos, length in tokens:
+        per[pos // 64] += length > 0
+    return len(tokens), per
 
 
 def _windows_without_and_full_of_matches(oracle):
@@ -244,47 +172,47 @@ def _ragged_last_chunks():
 # ---------------------------------------------------------------------------------------------------------------------
 @MODES
 def test_sort_one_key_in_every_position(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _one_key_everywhere(), mode, serial, "one key everywhere")
+    R.check_batch(oracle, gpu_ctx, _one_key_everywhere(), mode, serial, "one key everywhere")
 
 
 @MODES
 def test_sort_keys_confined_to_parts_and_pairs_of_parts(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _keys_in_parts(), mode, serial, "keys in parts")
+    R.check_batch(oracle, gpu_ctx, _keys_in_parts(), mode, serial, "keys in parts")
 
 
 @MODES
 def test_sort_occurrences_at_the_part_boundaries(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _occurrences_at_the_boundaries(), mode, serial, "occurrences at the boundaries")
+    R.check_batch(oracle, gpu_ctx, _occurrences_at_the_boundaries(), mode, serial, "occurrences at the boundaries")
 
 
 @MODES
 def test_sort_keys_with_raw_hash_0_1_and_4095(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _hash_0_1_4095(), mode, serial, "raw hash 0 / 1 / 4095")
+    R.check_batch(oracle, gpu_ctx, _hash_0_1_4095(), mode, serial, "raw hash 0 / 1 / 4095")
 
 
 @MODES
 def test_sort_chunk_lengths(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _chunk_lengths(), mode, serial, "chunk lengths")
+    R.check_batch(oracle, gpu_ctx, _chunk_lengths(), mode, serial, "chunk lengths")
 
 
 @MODES
 def test_emit_windows_without_a_match_and_with_the_most_matches(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _windows_without_and_full_of_matches(oracle), mode, serial, "no match / 22 matches")
+    R.check_batch(oracle, gpu_ctx, _windows_without_and_full_of_matches(oracle), mode, serial, "no match / 22 matches")
 
 
 @MODES
 def test_emit_tokens_from_the_repair_area(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _repair_area(), mode, serial, "repair area")
+    R.check_batch(oracle, gpu_ctx, _repair_area(), mode, serial, "repair area")
 
 
 @MODES
 def test_emit_after_a_cascade(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _cascade(), mode, serial, "cascade")
+    R.check_batch(oracle, gpu_ctx, _cascade(), mode, serial, "cascade")
 
 
 @MODES
 def test_emit_every_fill_of_the_last_flag_group(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _last_flag_group(oracle), mode, serial, "last flag group")
+    R.check_batch(oracle, gpu_ctx, _last_flag_group(oracle), mode, serial, "last flag group")
 
 
 @MODES
@@ -292,31 +220,17 @@ def test_emit_at_the_raw_threshold(oracle, gpu_ctx, mode, serial):
     units = _thresholds()
     sizes = sorted(len(_expected(oracle, u)) - len(u) for u in units)
     assert sizes[0] == 1 and sizes[-1] == 2, sizes            # 2-byte header + (n - 1) bytes, and the raw chunk's 2 + n
-    _check(oracle, gpu_ctx, units, mode, serial, "n - 1 / raw")
+    R.check_batch(oracle, gpu_ctx, units, mode, serial, "n - 1 / raw")
 
 
 @MODES
 def test_emit_ragged_last_chunks(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _ragged_last_chunks(), mode, serial, "ragged last chunks")
+    R.check_batch(oracle, gpu_ctx, _ragged_last_chunks(), mode, serial, "ragged last chunks")
 
 
 @MODES
 def test_repetitive_cases_64_concurrent_copies(oracle, gpu_ctx, mode, serial):
     """64 copies per batch, three passes, identical bytes in every copy of every pass (a race between the waves of a block -- sorting, or
     staging tokens while another wave still writes -- shows up in SOME copies of SOME passes)"""
-    import ms_compress_amd as m
     units = _repair_area() + _cascade()[:4] + [_trigram_chunk(1), bytes([0x61]) * 4096, (b"abc" * 1366)[:4096]]
-    want = [_expected(oracle, u) for u in units]
-    copies = 64
-    lib = gpu_ctx.lib
-    lib.mscomp_amd_debug_set_lznt1(mode)
-    lib.mscomp_amd_debug_set_serial_atomics(serial)
-    try:
-        for pas in range(3):
-            got, st = m.compress_units(LZNT1, [u for u in units for _ in range(copies)], ctx=gpu_ctx)
-            assert all(s == 0 for s in st)
-            bad = [i for i, g in enumerate(got) if g != want[i // copies]]
-            assert not bad, "pass %d, mode %d, serial %d: %d of %d copies differ from the oracle, first: copy %d of unit %d" % (pas, mode, serial, len(bad), len(got), bad[0] % copies, bad[0] // copies)
-    finally:
-        lib.mscomp_amd_debug_set_lznt1(0)
-        lib.mscomp_amd_debug_set_serial_atomics(0)
+    R.check_batch(oracle, gpu_ctx, units, mode, serial, "repetitive", copies=64, passes=3)

@@ -10,45 +10,12 @@ import numpy as np
 import pytest
 
 import cases
+import lznt1_run as R
+from lznt1_model import BITS, PART_FIRST, keys_with_raw_hash as _keys_with_raw_hash, noise as _noise, place_key as _place, straddling_buckets
 
 pytestmark = pytest.mark.gpu
-LZNT1 = 2
-BITS = 12
-P1, P2 = 960, 2496                                   # first position of parts 1 and 2 (lznt1.hip LZ4_P1, LZ4_P2: batches of 64 positions)
+P1, P2 = PART_FIRST[1:]                              # first position of parts 1 and 2
 PARTS = ((0, P1), (P1, P2), (P2, 4096))
-
-
-def _raw_hash(key24):
-    return ((key24 * 0x9E3779B1) & 0xFFFFFFFF) >> (32 - BITS)
-
-
-def _keys_with_raw_hash(targets, per_bucket):
-    """brute force over all 2^24 keys: `per_bucket` keys (3 bytes, little-endian) for every target value of the hash BEFORE 0 is mapped to 1"""
-    keys = np.arange(1 << 24, dtype=np.uint64)
-    h = _raw_hash(keys)
-    out = {}
-    for t in targets:
-        ks = keys[h == t][:per_bucket].astype(np.uint32)
-        assert len(ks) == per_bucket
-        out[t] = [bytes([int(k) & 0xFF, (int(k) >> 8) & 0xFF, (int(k) >> 16) & 0xFF]) for k in ks]
-    return out
-
-
-def _straddling_buckets():
-    """buckets h whose two ends (bits 12 (h - 1) .. 12 (h + 1) of the packed table) cross a dword boundary"""
-    return [h for h in range(2, 1 << BITS) if (12 * (h - 1)) % 32 + 24 > 32][:4]
-
-
-def _noise(seed, n=4096):
-    return bytearray(np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes())
-
-
-def _place(seed, key, positions, n=4096):
-    """seeded bytes with the 3-byte key at the given positions (each followed by bytes that differ from occurrence to occurrence)"""
-    d = _noise(seed, n)
-    for p in positions:
-        d[p:p + 3] = key
-    return bytes(d[:n])
 
 
 def _one_key_everywhere():
@@ -96,7 +63,7 @@ def _lengths_at_the_boundaries():
 
 def _first_last_and_straddling_buckets():
     rng = np.random.default_rng(21)
-    strad = _straddling_buckets()
+    strad = straddling_buckets(4)
     targets = [0, 1, (1 << BITS) - 1, (1 << BITS) - 2] + strad + [h - 1 for h in strad]
     kb = _keys_with_raw_hash(sorted(set(targets)), 6)
     units = []
@@ -120,62 +87,31 @@ def _repetitive():
                cases.few_distances(n=8192, dists=(2495, 2496, 1536, 1600, 16), seed=91, run=(100, 1200))])
 
 
-def _check(oracle, gpu_ctx, units, mode, serial, what):
-    import ms_compress_amd as m
-    lib = gpu_ctx.lib
-    lib.mscomp_amd_debug_set_lznt1(mode)
-    lib.mscomp_amd_debug_set_serial_atomics(serial)
-    try:
-        got, st = m.compress_units(LZNT1, units, ctx=gpu_ctx)
-    finally:
-        lib.mscomp_amd_debug_set_lznt1(0)
-        lib.mscomp_amd_debug_set_serial_atomics(0)
-    for i, (u, g, s) in enumerate(zip(units, got, st)):
-        es, exp = oracle.oracle_compress(LZNT1, u)
-        assert es == 0 and s == 0, (what, i, len(u), s)
-        assert g == exp, "%s, mode %d, serial %d, unit %d (len %d): GPU bytes differ from the oracle (%d vs %d B)" % (what, mode, serial, i, len(u), len(g), len(exp))
-
-
 MODES = pytest.mark.parametrize("mode,serial", [(1, 0), (2, 0), (1, 1), (2, 1)])
 
 
 @MODES
 def test_one_key_in_every_position(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _one_key_everywhere(), mode, serial, "one key everywhere")
+    R.check_batch(oracle, gpu_ctx, _one_key_everywhere(), mode, serial, "one key everywhere")
 
 
 @MODES
 def test_keys_confined_to_parts_and_across_part_boundaries(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _keys_in_parts(), mode, serial, "keys in parts")
+    R.check_batch(oracle, gpu_ctx, _keys_in_parts(), mode, serial, "keys in parts")
 
 
 @MODES
 def test_chunk_lengths_around_the_part_boundaries(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _lengths_at_the_boundaries(), mode, serial, "lengths at the boundaries")
+    R.check_batch(oracle, gpu_ctx, _lengths_at_the_boundaries(), mode, serial, "lengths at the boundaries")
 
 
 @MODES
 def test_first_last_and_dword_straddling_buckets(oracle, gpu_ctx, mode, serial):
-    _check(oracle, gpu_ctx, _first_last_and_straddling_buckets(), mode, serial, "first / last / straddling buckets")
+    R.check_batch(oracle, gpu_ctx, _first_last_and_straddling_buckets(), mode, serial, "first / last / straddling buckets")
 
 
 @MODES
 def test_repetitive_cases_many_concurrent_copies(oracle, gpu_ctx, mode, serial):
     """48 concurrent copies per batch, three passes, identical bytes in every copy of every pass (a race between the sorting waves shows up in
     SOME copies of SOME passes)."""
-    import ms_compress_amd as m
-    units = _repetitive()
-    want = [oracle.oracle_compress(LZNT1, u)[1] for u in units]
-    copies = 48
-    lib = gpu_ctx.lib
-    lib.mscomp_amd_debug_set_lznt1(mode)
-    lib.mscomp_amd_debug_set_serial_atomics(serial)
-    try:
-        for pas in range(3):
-            got, st = m.compress_units(LZNT1, [u for u in units for _ in range(copies)], ctx=gpu_ctx)
-            assert all(s == 0 for s in st)
-            bad = [i for i, g in enumerate(got) if g != want[i // copies]]
-            assert not bad, "pass %d, mode %d, serial %d: %d of %d copies differ from the oracle, first: copy %d of unit %d" % (pas, mode, serial, len(bad), len(got), bad[0] % copies, bad[0] // copies)
-    finally:
-        lib.mscomp_amd_debug_set_lznt1(0)
-        lib.mscomp_amd_debug_set_serial_atomics(0)
+    R.check_batch(oracle, gpu_ctx, _repetitive(), mode, serial, "repetitive", copies=48, passes=3)
