@@ -1036,18 +1036,26 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	// the last window is parsed: back come the wave and chunk numbers and the two addresses
 	wv = LZ4_FETCH(5); c = LZ4_FETCH(4);
 	const uint32_t w0 = wv * 16u, w1 = (w0 + 16u < nw) ? w0 + 16u : nw;
-	uint8_t* __restrict__ const img = reinterpret_cast<uint8_t*>((uintptr_t)LZ4_FETCH(0) | ((uintptr_t)LZ4_FETCH(1) << 32)) + (u64)c * LZNT1_SLOT;
-	uint32_t* __restrict__ const szp = reinterpret_cast<uint32_t*>((uintptr_t)LZ4_FETCH(2) | ((uintptr_t)LZ4_FETCH(3) << 32)) + c;
+	// (a pointer rebuilt from integers has lost its address space, and every store through it would be a FLAT one behind a 64-bit vector add, counted on
+	// lgkmcnt with the LDS reads: the two come back as GLOBAL pointers, so a store is global_store_* with this scalar base and a 32-bit lane offset)
+	typedef __attribute__((address_space(1))) uint8_t  g_u8;
+	typedef __attribute__((address_space(1))) uint32_t g_u32;
+	g_u8* __restrict__ const img = (g_u8*)((uintptr_t)LZ4_FETCH(0) | ((uintptr_t)LZ4_FETCH(1) << 32)) + (u64)c * LZNT1_SLOT;
+	g_u32* __restrict__ const szp = (g_u32*)((uintptr_t)LZ4_FETCH(2) | ((uintptr_t)LZ4_FETCH(3) << 32)) + c;
 	// ---- D0. the match tokens of my 16 windows, from the records in global memory (L2-warm: written by this block) into my piece of the dead
 	// bucket array, in ONE coalesced pass of dwords (a window's LZ4_MAXM tokens are 11 dwords; 176 per wave = three loads per lane, all in
 	// flight together, under wave 0's scans). Lane l < 16 knows window w0 + l: how many matches start in it and which area holds its tokens;
 	// a dword is fetched only if the window has a token for it. The emission loop then reads LDS alone.
 	static_assert(LZNT1_SLOT <= 0xFFFFFFFFu && (LZ4_MAXM & 1u) == 0 && LZ4_NSEG * 16u * LZ4_MAXM <= 4096u, "a window's tokens are whole dwords; four pieces fit the bucket array");
 	uint32_t* const s_ptk = reinterpret_cast<uint32_t*>(s_bucket) + wv * (16u * LZ4_MAXM / 2u);
+	// The emission loop's control words wait in the lanes as well: lane l (every 16 lanes alike) holds the token mask and the match mask of window
+	// w0 + l here, and the tokens and token bytes in front of it behind wave 0's scans below. An iteration reads them with v_readlane, so the loop
+	// tests and branches on the scalar unit and the masks are its exec masks.
+	const uint32_t wl0 = w0 + (lane & 15u);
+	const u64 tokv = wl0 < w1 ? s_tok[wl0] : (u64)0, matv = wl0 < w1 ? s_mat[wl0] : (u64)0;
 #ifndef LZ4_PROBE_EMIT
 	{
-		const uint32_t wl0 = w0 + (lane & 15u);
-		const uint32_t info = wl0 < w1 ? (uint32_t)__popcll(s_mat[wl0]) | ((uint32_t)s_rep[wl0] << 8) : 0u;
+		const uint32_t info = wl0 < w1 ? (uint32_t)__popcll(matv) | ((uint32_t)s_rep[wl0] << 8) : 0u;
 		const uint32_t* __restrict__ const rec32 = reinterpret_cast<const uint32_t*>(rec);
 		uint32_t v[3]; bool ld[3];
 		#pragma unroll
@@ -1078,38 +1086,52 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		// ---- D1. emission of my windows: pos(t) = 2 (header) + (t div 8 + 1) + sum size(u<t) --------------------------
 		// the match tokens come from my piece of LDS (D0): token k of window w at 16-bit index (w - w0) LZ4_MAXM + k. No global load and no
 		// dependent LDS read sit in the loop; the byte stores address the chunk's slot with one scalar base and 32-bit offsets.
+		// Every token lane reads its literal byte and a token word (a lane without a match reads the word behind the window's last token: inside the
+		// bucket array, never used), selects the low byte by the match mask and stores it; the match lanes then store the high byte and set their
+		// flag bit. One region under the token mask with the match lanes' inside it, and the flag-position store under its own test.
+		const uint32_t tsv = (uint32_t)s_T[wl0] | ((uint32_t)s_S[wl0] << 16);   // (wl0 < 64: wave 0 wrote all 64 entries)
+		const uint32_t nwin = LZ4_UNI(w1 > w0 ? w1 - w0 : 0u);
 		#pragma unroll 1
-		for (uint32_t w = w0; w < w1; ++w) {
-			const u64 tokmask = s_tok[w];
+		for (uint32_t k = 0; k < nwin; ++k) {
+			const u64 tokmask = ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tokv >> 32), (int)k) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tokv, (int)k);
 			if (tokmask == 0) { continue; }
-			const u64 matchmask = s_mat[w];
-			const bool is_tok = (tokmask >> lane) & (u64)1, is_m = (matchmask >> lane) & (u64)1;
+			const u64 matchmask = ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(matv >> 32), (int)k) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)matv, (int)k);
+			const uint32_t ts = (uint32_t)__builtin_amdgcn_readlane((int)tsv, (int)k);
 			const uint32_t tb = popc_below(tokmask), mbl = popc_below(matchmask);
-			const uint32_t t = (uint32_t)s_T[w] + tb;
-			const uint32_t pos = 3u + (t >> 3) + (uint32_t)s_S[w] + tb + mbl;
-			if (is_tok) {
+			const uint32_t t = (ts & 0xFFFFu) + tb;
+			const uint32_t pos = (3u + (ts >> 16)) + (t >> 3) + tb + mbl;     // (the window's part is scalar: added once)
+			if (__builtin_amdgcn_inverse_ballot_w64(tokmask)) {
 				if ((t & 7u) == 0) { s_flagpos[t >> 3] = (uint16_t)(pos - 1u); }
-				if (is_m) {
+				const uint32_t lit = s_data[(w0 + k) * 64u + lane];
 #ifdef LZ4_PROBE_EMIT   // dev-only, NOT exact, timing only: the emission without any token read
-					const uint32_t tok = 0x1003u;
+				const uint16_t tok = 0x1003u;
 #else
-					const uint32_t tok = reinterpret_cast<const uint16_t*>(s_ptk)[(w - w0) * LZ4_MAXM + mbl];
+				const uint16_t tok = reinterpret_cast<const uint16_t*>(s_ptk)[k * LZ4_MAXM + mbl];
 #endif
-					img[pos] = (uint8_t)tok; img[pos + 1u] = (uint8_t)(tok >> 8);
+				// (the mask itself selects; only the low byte is stored, so the token travels with an undefined upper half: lz_entry32)
+				uint32_t lo; asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(lo) : "v"(lit), "v"(lz_entry32(tok)), "s"(matchmask));
+				img[pos] = (uint8_t)lo;
+				if (__builtin_amdgcn_inverse_ballot_w64(matchmask)) {
+					// (the + 1 goes into the store's offset field. The offset is redefined inside this block: a value that arrives from the block above
+					// already widened to 64 bits is added to the base in vector registers)
+					uint32_t p1 = pos; asm("" : "+v"(p1));
+					(img + p1)[1] = (uint8_t)(tok >> 8);
 					atomicOr(&s_flagacc[t >> 3], 1u << (t & 7u));
-				} else { img[pos] = s_data[w * 64u + lane]; }
+				}
 			}
 		}
 		LZ4_T(16)
 		__syncthreads();
 		LZ4_T(17)
-		for (uint32_t g = tid; g < ((T + 7u) >> 3); g += 256u) { img[s_flagpos[g]] = (uint8_t)s_flagacc[g]; }
+		#pragma unroll 1
+		for (uint32_t g = tid; g < ((T + 7u) >> 3); g += 256u) { uint32_t fp = s_flagpos[g]; asm("" : "+v"(fp)); img[fp] = (uint8_t)s_flagacc[g]; }   // (at most 512 groups: two rounds; a 32-bit offset to the scalar base)
 		if (tid == 0) { img[0] = (uint8_t)(0xB000u | (csize - 1u)); img[1] = (uint8_t)((0xB000u | (csize - 1u)) >> 8); }
 		total = 2u + csize;
 	} else {
 		const uint32_t hdr = 0x3000u | (n - 1u);
 		for (uint32_t k = tid; k < (n + 2u + 3u) / 4u; k += 256u) {
-			reinterpret_cast<uint32_t*>(img)[k] = (k == 0) ? (hdr | (ld16(s_data) << 16)) : ld32(s_data + 4u * k - 2u);
+			uint32_t o = 4u * k; asm("" : "+v"(o));                     // (a 32-bit byte offset to the scalar base, kept from becoming a 64-bit induction variable)
+			*(g_u32*)(img + o) = (k == 0) ? (hdr | (ld16(s_data) << 16)) : ld32(s_data + 4u * k - 2u);
 		}
 		total = 2u + n;
 	}
