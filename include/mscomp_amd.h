@@ -869,8 +869,8 @@ MSCompStatus mscomp_amd_splicer_splice_extents(mscomp_amd_splicer* sp, const msc
  *                 its own from the second outside one, captured again when an argument changes -- a field of a view counts as an
  *                 argument. MSCOMP_ARG_ERROR for a null dd, src or d_count, any other null output array when N > 0, or a view with a
  *                 null table (or null d_packed with packed_len > 0) while its n_res > 0.
- *   Left out:     block-level sharing inside one container (the running-sum offset table cannot express two rows at one address); a
- *                 tiled settle stage -- the refuted are settled by ONE workgroup, each against the earlier unique ones of its key, whole
+ *   Left out:     (block-level sharing inside one container is mscomp_amd_deduper_match with no store, below: a container of the unique
+ *                 blocks and a recipe of extents say what the running-sum offset table cannot;) a tiled settle stage -- the refuted are settled by ONE workgroup, each against the earlier unique ones of its key, whole
  *                 resources compared one after the other: the floor of the call on adversarial inputs, as is the one workgroup that
  *                 scans the resources; tables whose resources overlap (damaged ones that still pass rules 1-3) are read once per
  *                 resource that claims a row, so the work follows the sum of n, not the table; dedup fused with splice in one call; more
@@ -952,8 +952,8 @@ MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* dd, const mscomp_amd_b
  *                 argument. MSCOMP_ARG_ERROR for a null dd, base, next or d_count, a deduper made for dedup, any other null array when
  *                 n_pair > 0 (d_delta_ext and d_patch_ext may be null while n_blocks_new is 0), or a view with a null table (or null
  *                 d_packed with packed_len > 0) while its n_res > 0.
- *   Left out:     content-addressed matching -- a block that moved to another index or another resource counts as changed; byte-granular
- *                 deltas inside a block; more than one base per call; diff fused with the two splices in one call. */
+ *   Left out:     (content-addressed matching -- a block that moved to another index or another resource counts as changed HERE -- is
+ *                 mscomp_amd_deduper_match, below;) byte-granular deltas inside a block; more than one base per call; diff fused with the two splices in one call. */
 #define MSCOMP_AMD_DIFF_NO_BASE 0xFFFFFFFFFFFFFFFFull
 MSCompStatus mscomp_amd_deduper_create_diff(mscomp_amd_ctx* ctx, uint32_t block_size, size_t n_pair, uint64_t n_blocks_new, uint32_t flags,
                                             mscomp_amd_deduper** dd);
@@ -968,8 +968,116 @@ MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* dd,
                                      uint64_t* d_count                 /* 4 */,
                                      int32_t*  d_status                /* n_pair */);
 
+/* Match: the deduper's third call. For every block of the resources of a container (next), whether an EQUAL block already lies in one of
+ * up to three store containers, earlier in next itself, or nowhere -- wherever that block lies: another index, another resource, another
+ * container --, without decoding a byte, answered as two extent lists mscomp_amd_splicer_splice_extents takes: the DELTA list, which cuts
+ * the blocks seen for the first time out of next, and the PATCH list, which puts the stores and the delta together again. "Keep what the
+ * stores do not have yet" is match, then one splice; "restore today's" is one more. With no store at all the call single-instances the
+ * blocks of ONE container into (D, recipe): the running-sum offset table cannot hold two rows at one address, a container of the unique
+ * blocks and a list of extents can. The stored form of a block depends only on its data, the format and B, so between containers of ONE
+ * format and ONE block size (the caller's duty, as for splice) equal data means equal stored bytes, and equality is decided on the stored
+ * form. Candidates come from the tables and 32 bytes per row; the only pass over the data is the compare that confirms a candidate.
+ *   Creation:     mscomp_amd_deduper_create_match makes a mscomp_amd_deduper (destroyed by mscomp_amd_deduper_destroy, reported by the
+ *                 scratch hooks under MSCOMP_AMD_SCRATCH_DEDUPER) for n_src stores and one next container with at most n_res_total
+ *                 resources and n_blocks_total table rows in all views together, of which next brings at most n_blocks_new.
+ *                 MSCOMP_ARG_ERROR, all checked before the context is used and with *dd cleared, for a null ctx or dd, a block_size that is
+ *                 not a power of two from 4096 to 524288, n_src above 3 (0 is legal: no store), non-zero flags, n_res_total or
+ *                 n_blocks_total above 0x7FFFFFF0, or n_blocks_new above n_blocks_total; MSCOMP_MEM_ERROR when the scratch cannot be
+ *                 reserved. Such a deduper answers mscomp_amd_deduper_dedup and mscomp_amd_deduper_diff with MSCOMP_ARG_ERROR and launches
+ *                 nothing, and a deduper made by either other create answers mscomp_amd_deduper_match the same way.
+ *   Scratch:      reserved once, at creation, and never grown: 48 n_res_total + 40 n_blocks_total + 4 n_blocks_new + 64 ceil(n_blocks_new /
+ *                 MSCOMP_AMD_SPLICE_ROW_TILE) + 848 bytes (per resource its first row in the call's row numbering and the five counts in
+ *                 front of it; per row its slot, its flag, its representative and its place in the list of the refuted, and a key table
+ *                 of 2 n_blocks_total + 64 slots of 12 bytes; per row of next its rank among the fresh rows of its tile; eight words per
+ *                 tile; the refuted count; 64 bytes of slack). No context buffer is used.
+ *   Sources:      store is a HOST array of n_src views (may be null when n_src is 0), next a HOST view; read on the host, passed by value,
+ *                 only read. The output arrays must not overlap a source array. The sum of all n_res must not exceed n_res_total, the
+ *                 sum of all n_blocks_table must not exceed n_blocks_total and next->n_blocks_table must not exceed n_blocks_new:
+ *                 otherwise MSCOMP_ARG_ERROR from the call, on the host, with nothing launched.
+ *   Notation:     the resources are numbered as dedup numbers them, the stores' back to back and then next's: resource r of store s is
+ *                 g = store[0].n_res + ... + store[s - 1].n_res + r, resource q of next is g = N_store + q; d_status has one entry per g.
+ *                 B, L, first, off and n as for dedup. Block k of a resource has the data length e(k) = min(B, L - k B) and the stored
+ *                 length off[first + k + 1] - off[first + k]. The ROWS of a call are the blocks of the accepted resources numbered densely
+ *                 in the order of g, block by block: every row of a store is smaller than every row of next.
+ *   Rules:        in this order:
+ *                   1.-3. dedup's rules 1-3 per resource g, store and next alike;
+ *                   4. room, the shape of diff's rule 3, because the scratch is per row: the saturating running total of n over the
+ *                      resources that passed rules 1 and 2, in the order of g, including this resource and including resources refused
+ *                      here, must not exceed n_blocks_total, and the same total over the resources of next alone must not exceed
+ *                      n_blocks_new; otherwise MSCOMP_ARG_ERROR. (It is checked where the rows are numbered, in front of rule 3: a
+ *                      resource that rule refuses has counted.) A resource with n = 0 is never refused here;
+ *                   5. a refused resource of a store contributes no rows: nothing is found in it, and no byte of it is read. A refused
+ *                      resource q of next has no extents in either list and d_class[3 q .. 3 q + 2] = 0: an empty resource of D and of
+ *                      the rebuilt container. Resource indices never shift;
+ *                   6. equality: two rows are EQUAL when their data lengths e(k) are equal, their stored lengths are equal, their CRC
+ *                      words are equal -- when checksums take part -- and their stored bytes are equal. rep(u) is the smallest row equal
+ *                      to u (u itself when there is none below it). A row u of next is FOUND when rep(u) is a row of a store, SHARED when
+ *                      rep(u) is a smaller row of next, FRESH when rep(u) = u;
+ *                   7. runs: a RUN is a maximal stretch of consecutive blocks of one resource of next with one class whose representatives
+ *                      are consecutive blocks of one resource (fresh blocks are their own); every accepted resource with n > 0 is a
+ *                      sequence of runs. The DELTA extents of resource q are its fresh runs [k0, k0 + c) in order, (0, q, k0, c), over
+ *                      the one source {next}: D has next->n_res resources, resource q of D the fresh blocks of q in order. The PATCH
+ *                      extents of resource q, over the sources {store[0], ..., store[n_src - 1], D}, are its runs in order: a found run
+ *                      is (s, r, k0, c), where its representatives lie; a fresh run is (n_src, q, i0, c) with i0 the number of fresh
+ *                      blocks of q in front of it; a shared run is (n_src, q', i', c) with q' the resource of next that holds its
+ *                      representatives and i' the number of fresh blocks of q' in front of the first of them. Counts are always
+ *                      explicit, never all-ones. d_delta_ext_first and d_patch_ext_first are the exclusive running counts of extents
+ *                      over the resources of next, dense, entry next->n_res the number of extents in use; the entries of d_delta_ext and
+ *                      d_patch_ext at and behind that number are not written. A run has at least one row, so neither list exceeds
+ *                      n_blocks_new extents;
+ *                   8. counts: d_class[3 q], [3 q + 1], [3 q + 2] = the found, shared and fresh blocks of resource q; d_count[0 .. 2] =
+ *                      their sums, d_count[3] = the rows of next looked at (the sum of n over its accepted resources), d_count[4] = the
+ *                      stored bytes of the fresh blocks -- the packed length of D --, d_count[5] = the refuted (below). All six and
+ *                      every extent are the same from run to run.
+ *                 A call whose views hold no resource writes d_count = {0, ...} and entry 0 of the two running counts (where given).
+ *                 Consequence: mscomp_amd_splicer_splice_extents over {next} with the delta lists writes D; the same call over
+ *                 {store..., D} with the patch lists writes a container whose resource q has the length, the rows, the stored bytes and
+ *                 the CRC words of resource q of next, for every accepted q; when every resource of next is accepted its packed bytes and
+ *                 tables are byte for byte those of next. Splice-extents' rule 4 (only the last non-empty extent of a resource may end
+ *                 short) holds by construction: a block with e(k) < B is the last block of its resource -- in next, in a store, and, when
+ *                 fresh, in D, whose resource q keeps the order of q. By the data-length clause of rule 6 a short block is only ever
+ *                 represented by a short block of the SAME data length, so an extent ends short exactly when it carries the last block of
+ *                 resource q, which only the last extent of q does; and no full block is ever represented by a short one.
+ *   Key:          the KEY TUPLE of a row is its data length, its stored length s, its CRC word when checksums take part, and its first
+ *                 min(16, s) and last min(16, s) stored bytes. Equal rows have equal tuples. The tuple is mixed into 64 bits; the
+ *                 candidate of a row is the smallest row with the same key. REFUTED, d_count[5], is the number of rows of accepted
+ *                 resources, stores included, that share their key with a smaller row but are not equal to the smallest such one. They
+ *                 are still answered exactly: rep is the smallest EQUAL row, whatever shares its key -- equal rows share a key, so a
+ *                 refuted row can only equal an earlier refuted row of its slot. (Two different tuples that meet in their 64 bits would
+ *                 count here too.)
+ *   Checksums:    they take part exactly when every view has a non-null d_block_crc; otherwise all the arrays are ignored.
+ *   Execution:    as the deduper's: asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation, no
+ *                 synchronisation, nothing read back, ten launches fixed by the creation bounds (three when n_blocks_total is 0, seven
+ *                 when n_blocks_new is 0): the key table cleared; the seed, one workgroup -- rules 1, 2 and 4 and the row numbering --;
+ *                 rule 3, the keys into the table, and the compare that confirms a row against its candidate, fixed grids over the rows;
+ *                 the settle, one workgroup; the runs in tiles of MSCOMP_AMD_SPLICE_ROW_TILE rows of next -- the tiles' sums, their
+ *                 running values (one workgroup), the rows --; the counts. The walk along the key table is bounded by its slot count: a
+ *                 damaged state may cost time and never spins. Minima are taken with atomics whose result does not depend on the order
+ *                 of arrival, everything is counted in scans. Legal inside a caller's capture from the first execution, a graph of its
+ *                 own from the second outside one, captured again when an argument changes -- a field of a view counts as an argument.
+ *                 MSCOMP_ARG_ERROR for a null dd, next or d_count, a null store when n_src > 0, a deduper made for dedup or diff, any
+ *                 other null array when n_res_total > 0 (d_delta_ext and d_patch_ext may be null while n_blocks_new is 0), or a view
+ *                 with a null table (or null d_packed with packed_len > 0) while its n_res > 0.
+ *   Left out:     a choice of representative that prefers longer runs -- the smallest equal row always wins, so a container full of equal
+ *                 blocks (zeros, say) gets one extent per block; byte-granular or shifted (not block-aligned) matches; a tiled settle --
+ *                 the refuted are settled by ONE workgroup, in ascending order, each against the earlier ones of its slot: the floor of
+ *                 the call on adversarial inputs, as is the one workgroup that lists them; match fused with its two splices in one
+ *                 call; more than three stores per call. */
+MSCompStatus mscomp_amd_deduper_create_match(mscomp_amd_ctx* ctx, uint32_t block_size, uint32_t n_src /* 0 .. 3 stores */, size_t n_res_total,
+                                             uint64_t n_blocks_total, uint64_t n_blocks_new, uint32_t flags, mscomp_amd_deduper** dd);
+MSCompStatus mscomp_amd_deduper_match(mscomp_amd_deduper* dd,
+                                      const mscomp_amd_blocks_view* store /* host array, n_src; may be NULL when n_src is 0 */,
+                                      const mscomp_amd_blocks_view* next  /* host, by value, only read */,
+                                      uint64_t* d_delta_ext_first       /* next->n_res + 1 */,
+                                      uint64_t* d_delta_ext             /* 4 n_blocks_new */,
+                                      uint64_t* d_patch_ext_first       /* next->n_res + 1 */,
+                                      uint64_t* d_patch_ext             /* 4 n_blocks_new */,
+                                      uint64_t* d_class                 /* 3 next->n_res: found, shared, fresh blocks of the resource */,
+                                      uint64_t* d_count                 /* 6: found, shared, fresh, rows looked at, fresh stored bytes, refuted */,
+                                      int32_t*  d_status                /* one per resource: the stores' back to back, then next's */);
+
 /* Block transcoders: a container brought to another block size, another codec, or both. Every call that combines containers -- splice,
- * splice by extents, dedup, diff, delta, patch -- asks for one format and one block size; a transcoder is what gets a container there.
+ * splice by extents, dedup, diff, match, delta, patch -- asks for one format and one block size; a transcoder is what gets a container there.
  * It is out of place, like a writer: it reads a container of format F1 cut at B1 and writes a NEW one of format F2 cut at B2. Resource
  * lengths do not change, and neither does any resource CRC-32 (mscomp_amd_res_crc_dev gives the same values for both containers).
  * Between two LZNT1 containers most blocks are CARRIED -- their stored bytes move as they lie, nothing is decoded or encoded --, because

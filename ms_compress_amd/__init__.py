@@ -18,4 +18,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   blocks_splice_extents, blocks_concat, blocks_split_at, blocks_cut_range,
                   BlockDeduper, blocks_dedup,
                   BlockTranscoder, blocks_transcode,
-                  blocks_diff, blocks_delta, blocks_patch, MSCOMP_AMD_DIFF_NO_BASE)
+                  blocks_diff, blocks_delta, blocks_patch, MSCOMP_AMD_DIFF_NO_BASE,
+                  blocks_match, blocks_match_delta, blocks_match_patch, blocks_single_instance)

@@ -49,6 +49,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_splicer_create_extents", "mscomp_amd_splicer_splice_extents",
     "mscomp_amd_deduper_create", "mscomp_amd_deduper_destroy", "mscomp_amd_deduper_dedup",
     "mscomp_amd_deduper_create_diff", "mscomp_amd_deduper_diff",
+    "mscomp_amd_deduper_create_match", "mscomp_amd_deduper_match",
     "mscomp_amd_transcoder_create", "mscomp_amd_transcoder_destroy", "mscomp_amd_transcoder_transcode", "mscomp_amd_transcoder_counts",
     "mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report",
 ]
@@ -214,6 +215,10 @@ def load_library():
     lib.mscomp_amd_deduper_create_diff.restype = C.c_int
     lib.mscomp_amd_deduper_diff.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.POINTER(BlocksView)] + [C.c_void_p] * 8
     lib.mscomp_amd_deduper_diff.restype = C.c_int
+    lib.mscomp_amd_deduper_create_match.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_deduper_create_match.restype = C.c_int
+    lib.mscomp_amd_deduper_match.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.POINTER(BlocksView)] + [C.c_void_p] * 7
+    lib.mscomp_amd_deduper_match.restype = C.c_int
     lib.mscomp_amd_transcoder_create.restype = C.c_int
     lib.mscomp_amd_transcoder_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                                  C.POINTER(C.c_void_p)]
@@ -1145,6 +1150,39 @@ class BlockDeduper(_Handle):
             "mscomp_amd_deduper_diff")
 
 
+    @classmethod
+    def for_match(cls, ctx, block_size, n_src, n_res_total, n_blocks_total, n_blocks_new):
+        """A deduper for match() (mscomp_amd_deduper_create_match): ``n_src`` (0 .. 3) stores and one new container with at most
+        ``n_res_total`` resources and ``n_blocks_total`` table rows in all of them together, the new container bringing at most
+        ``n_blocks_new`` rows. Its scratch: 48 bytes per resource, 40 per row, 4 per new row and 64 per SPLICE_ROW_TILE of them, + 848.
+        It refuses dedup() and diff(), as dedupers made for those refuse match()."""
+        self = cls.__new__(cls)
+        _Handle.__init__(self, ctx)
+        self.block_size, self.n_src, self.n_res_total = int(block_size), int(n_src), int(n_res_total)
+        self.n_blocks_total, self.n_blocks_new = int(n_blocks_total), int(n_blocks_new)
+        _ok(ctx.lib.mscomp_amd_deduper_create_match(ctx._h, self.block_size, self.n_src, self.n_res_total, self.n_blocks_total, self.n_blocks_new, 0,
+                                                    C.byref(self._h)), "mscomp_amd_deduper_create_match")
+        return self
+
+    def match(self, stores, new, d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_class, d_count, d_status):
+        """``stores``: n_src sources as BlockSplicer.splice takes them, ``new``: one more. A block of a resource of ``new`` is found when an
+        equal block -- same data length, stored length, CRC word (when every source has checksums) and stored bytes -- lies anywhere in a
+        store, shared when one lies earlier in ``new``, fresh otherwise. The answer is two extent lists in the form
+        BlockSplicer.splice_extents takes, one new resource per resource of ``new``: d_delta_ext_first (n_res + 1) / d_delta_ext
+        (4 n_blocks_new), over the one source [new], cut out the fresh blocks; d_patch_ext_first / d_patch_ext, over the sources
+        stores + [that delta container], put the resources of ``new`` together again. d_class (3 n_res) = found, shared and fresh blocks
+        per resource, d_count (6) = found, shared, fresh, blocks looked at, stored bytes of the fresh blocks, refuted candidates;
+        d_status, one entry per resource of the stores back to back and then of ``new``, is MSCOMP_OK, MSCOMP_ARG_ERROR (a broken
+        block_first entry, or no room within n_blocks_total or n_blocks_new) or MSCOMP_DATA_ERROR (a wrong block count, a broken block_off
+        entry): a refused resource of a store brings no blocks, one of ``new`` has no extents."""
+        if len(stores) != self.n_src:
+            raise ValueError("one store per n_src")
+        views = _blocks_views(list(stores) + [new])
+        _ok(self.ctx.lib.mscomp_amd_deduper_match(self._h, views if self.n_src else None, C.byref(views[self.n_src]),
+                                                  *_ptrs(d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_class, d_count, d_status)),
+            "mscomp_amd_deduper_match")
+
+
 def _diff_pairs(base, new, pairs):
     """the pairs of blocks_diff as (base resource or MSCOMP_AMD_DIFF_NO_BASE, new resource) of 64 bits each"""
     M64 = MSCOMP_AMD_DIFF_NO_BASE
@@ -1221,6 +1259,74 @@ def blocks_patch(base, delta, patch_resources, block_size, ctx=None):
     """The new resources from ``base`` and the ``delta`` container and ``patch_resources`` of blocks_delta:
     blocks_splice_extents([base, delta], patch_resources, block_size). Returns what blocks_splice returns."""
     return blocks_splice_extents([base, delta], patch_resources, block_size, ctx=ctx)
+
+
+def blocks_match(stores, new, block_size, ctx=None):
+    """For every block of ``new``, whether an equal block lies anywhere in one of the ``stores`` (0 .. 3 of them), earlier in ``new`` or
+    nowhere, on the GPU (BlockDeduper.match), no block decoded: containers of one format and ``block_size`` as blocks_splice takes them.
+    Returns host lists (delta_resources, patch_resources, classes, counts, statuses): the two resource lists have the shape
+    blocks_splice_extents takes -- blocks_splice_extents([new], delta_resources, block_size) is the delta container of the blocks seen for
+    the first time, blocks_match_patch(stores, delta, patch_resources, block_size) the resources of ``new`` again --, classes one (found,
+    shared, fresh) per resource of ``new``, counts the six of BlockDeduper.match, statuses one per resource of the stores back to back
+    and then of ``new``."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    B = int(block_size)
+    cons = list(stores) + [new]
+    with_crc = all(c[4] is not None for c in cons)
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+        srcs, n_all, rows_all = [], 0, 0
+        for packed, first, off, lens, crc in cons:
+            lens = [int(x) for x in lens]
+            packed, d_packed = _dev_packed(packed, dev)
+            rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
+            n_all += len(lens); rows_all += rows
+            srcs.append((d_packed, _dev_u64(first, len(lens) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(lens, 1, dev),
+                         _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(lens), rows))
+        n, nbn = srcs[-1][6], srcs[-1][7]
+        dd = BlockDeduper.for_match(ctx, B, len(stores), n_all, rows_all, nbn)
+        d_df, d_pf = torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_de, d_pe = torch.zeros(max(1, 4 * nbn), dtype=torch.int64, device=dev), torch.zeros(max(1, 4 * nbn), dtype=torch.int64, device=dev)
+        d_cl, d_cnt = torch.zeros(max(1, 3 * n), dtype=torch.int64, device=dev), torch.zeros(6, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(1, n_all), dtype=torch.int32, device=dev)
+        dd.match(srcs[:-1], srcs[-1], d_df, d_de, d_pf, d_pe, d_cl, d_cnt, d_st)
+        ctx.stream.synchronize()
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)
+        delta, patch = _extent_lists(u64(d_df), u64(d_de), n), _extent_lists(u64(d_pf), u64(d_pe), n)
+        classes = [tuple(int(x) for x in row) for row in u64(d_cl)[: 3 * n].reshape(-1, 3)]
+        counts, st = [int(x) for x in u64(d_cnt)], [int(x) for x in d_st.cpu().numpy()[:n_all]]
+        dd.close()
+    if own:
+        ctx.close()
+    return delta, patch, classes, counts, st
+
+
+def blocks_match_delta(stores, new, block_size, ctx=None):
+    """The delta container of ``new`` against the ``stores`` -- per resource the blocks no store holds and ``new`` has not held before, in
+    order -- together with the recipe that rebuilds ``new`` from stores + delta: blocks_match, then blocks_splice_extents over [new].
+    Returns (delta, patch_resources, classes, counts, statuses), delta = (packed, block_first, block_off, lengths, block_crc or None)."""
+    own = ctx is None
+    ctx = ctx or Context()
+    delta_res, patch_res, classes, counts, st = blocks_match(stores, new, block_size, ctx=ctx)
+    with_crc = all(c[4] is not None for c in list(stores) + [new])
+    packed, first, off, lens, crc, _ = blocks_splice_extents([new if with_crc else tuple(new[:4]) + (None,)], delta_res, block_size, ctx=ctx)
+    if own:
+        ctx.close()
+    return (packed, first, off, lens, crc), patch_res, classes, counts, st
+
+
+def blocks_match_patch(stores, delta, patch_resources, block_size, ctx=None):
+    """The resources of the new container from the ``stores`` and the ``delta`` container and ``patch_resources`` of blocks_match_delta:
+    blocks_splice_extents(stores + [delta], patch_resources, block_size). Returns what blocks_splice returns."""
+    return blocks_splice_extents(list(stores) + [delta], patch_resources, block_size, ctx=ctx)
+
+
+def blocks_single_instance(container, block_size, ctx=None):
+    """``container`` with every block stored once: blocks_match_delta([], container, block_size) -- the container of its unique blocks and
+    the recipe (over that container alone) that blocks_match_patch([], delta, recipe, block_size) rebuilds it from."""
+    return blocks_match_delta([], container, block_size, ctx=ctx)
 
 
 def blocks_dedup(containers, block_size, ctx=None):

@@ -567,13 +567,16 @@ struct mscomp_amd_deduper {
 	mscomp_amd_ctx* ctx = nullptr;
 	uint32_t shift = 0, n_src = 0, n_res = 0, nbt = 0;     // block_size = 1 << shift; the bounds n_res_total and n_blocks_total
 	bool diff = false;                                     // made by mscomp_amd_deduper_create_diff: n_res is n_pair, nbt is n_blocks_new, the scratch holds a DiffTab
-	GraphRun<37> run; GraphRun<24> frun;                   // dedup: four views, and five words; diff: two views, and eight
-	DevBuf tab;                                            // DedupTab, or DiffTab
+	bool match = false;                                    // made by mscomp_amd_deduper_create_match: n_src stores (0 .. 3), nbn is n_blocks_new, the scratch holds a MatchTab
+	uint32_t nbn = 0;
+	GraphRun<37> run; GraphRun<24> frun; GraphRun<39> mrun; // dedup: four views, and five words; diff: two views, and eight; match: four views, and seven
+	DevBuf tab;                                            // DedupTab, DiffTab or MatchTab
 	DedupTab t{};
 	DiffTab f{};
+	MatchTab m{};
 };
 #pragma GCC visibility pop
-static_assert(DF_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header states");
+static_assert(DF_TILE == MSCOMP_AMD_SPLICE_ROW_TILE && MT_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header states");
 
 // the columns of a deduper's tables from `base` on (n = n_res_total); returns where they end: from a null base, their bytes
 static uintptr_t dedup_tab(DedupTab& t, void* base, size_t n)
@@ -633,7 +636,7 @@ void mscomp_amd_deduper_destroy(mscomp_amd_deduper* d) { destroy_object(d, [d] {
 MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* src, uint64_t* d_rep, uint64_t* d_new_index, uint64_t* d_pick,
                                       uint64_t* d_count, int32_t* d_status)
 {
-	if (!d || d->diff || !src || !d_count) { return MSCOMP_ARG_ERROR; }
+	if (!d || d->diff || d->match || !src || !d_count) { return MSCOMP_ARG_ERROR; }
 	SpliceSrc k{};
 	bool with_crc = false;                                 // the checksums are used only if every view has them
 	if (!pack_views(src, d->n_src, true, k.v, with_crc)) { return MSCOMP_ARG_ERROR; }
@@ -664,7 +667,7 @@ MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* d, const mscomp_amd_blo
                                      uint64_t* d_delta_ext_first, uint64_t* d_delta_ext, uint64_t* d_patch_ext_first, uint64_t* d_patch_ext, uint64_t* d_changed,
                                      uint64_t* d_count, int32_t* d_status)
 {
-	if (!d || !d->diff || !base || !next || !d_count) { return MSCOMP_ARG_ERROR; }
+	if (!d || !d->diff || !base || !next || !d_count) { return MSCOMP_ARG_ERROR; }   // (a deduper made for dedup or for match)
 	if (d->n_res && (!d_pair || !d_delta_ext_first || !d_patch_ext_first || !d_changed || !d_status || (d->nbt && (!d_delta_ext || !d_patch_ext)))) { return MSCOMP_ARG_ERROR; }
 	const mscomp_amd_blocks_view src[2] = { *base, *next };
 	SpliceView v[2];
@@ -684,6 +687,77 @@ MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* d, const mscomp_amd_blo
 			{ KernelTimer t(c, "df_runs"); launch_diff_runs(c->stream, v[1], n, m, d_pair, d->f, d_status, d_delta_ext, d_patch_ext); }
 		}
 		{ KernelTimer t(c, "df_counts_kernel"); launch_diff_counts(c->stream, n, m, d->f, d_delta_ext_first, d_patch_ext_first, d_changed, d_count, c->crc_blocks); }
+	});
+}
+
+// the columns of a deduper made for match from `base` on (n = n_res_total, m = n_blocks_total, mn = n_blocks_new); returns where they end:
+// from a null base, their bytes
+static uintptr_t match_tab(MatchTab& t, void* base, size_t n, size_t m, size_t mn)
+{
+	Carve k(base);
+	const size_t slots = 2 * m + 64;
+	t.slots = slots < 0xFFFFFFF0u ? slots : 0xFFFFFFF0u;   // (a slot's index is a 32-bit word, and all-ones is "none")
+	t.ufirst = k.q(n + 1); t.pfirst = k.q(5 * n); t.tsum = k.q(8 * (size_t)match_row_tiles((uint32_t)mn)); t.tkey = k.q(slots); t.nref = k.q(1);
+	t.tmin = k.w(slots); t.slot_of = k.w(m); t.flag = k.w(m); t.rep = k.w(m); t.rlist = k.w(m); t.flocal = k.w(mn);
+	return k.at;
+}
+
+MSCompStatus mscomp_amd_deduper_create_match(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res_total, uint64_t n_blocks_total, uint64_t n_blocks_new,
+                                             uint32_t flags, mscomp_amd_deduper** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || !block_size_ok(block_size)) { return MSCOMP_ARG_ERROR; }
+	if (n_src >= MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_res_total) || !count_ok(n_blocks_total) || n_blocks_new > n_blocks_total) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
+	if (!d) { return MSCOMP_MEM_ERROR; }
+	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = n_src; d->n_res = (uint32_t)n_res_total; d->nbt = (uint32_t)n_blocks_total;
+	d->nbn = (uint32_t)n_blocks_new; d->match = true;
+	if (!d->tab.reserve(match_tab(d->m, nullptr, n_res_total, n_blocks_total, n_blocks_new) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	match_tab(d->m, d->tab.p, n_res_total, n_blocks_total, n_blocks_new);
+	*out = d.release();
+	return MSCOMP_OK;
+}
+
+// Match: the key table cleared, the seed, rule 3 over the rows, the rows' keys into the table, the compare that confirms a
+// row against its slot's smallest, the settle, the three run passes tiled over next's rows, the counts.
+MSCompStatus mscomp_amd_deduper_match(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* store, const mscomp_amd_blocks_view* next, uint64_t* d_delta_ext_first,
+                                      uint64_t* d_delta_ext, uint64_t* d_patch_ext_first, uint64_t* d_patch_ext, uint64_t* d_class, uint64_t* d_count, int32_t* d_status)
+{
+	if (!d || !d->match || !next || !d_count || (d->n_src && !store)) { return MSCOMP_ARG_ERROR; }
+	if (d->n_res && (!d_delta_ext_first || !d_patch_ext_first || !d_class || !d_status || (d->nbn && (!d_delta_ext || !d_patch_ext)))) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_blocks_view src[MSCOMP_AMD_SPLICE_SRC_MAX];
+	for (uint32_t i = 0; i < d->n_src; ++i) { src[i] = store[i]; }
+	src[d->n_src] = *next;
+	SpliceSrc k{};
+	bool with_crc = false;                                 // the checksums are used only if every view has them
+	if (!pack_views(src, d->n_src + 1, true, k.v, with_crc)) { return MSCOMP_ARG_ERROR; }
+	uint64_t n = 0, rows = 0;                              // (at most four terms below 2^64 / 4 each once checked: no overflow)
+	for (uint32_t i = 0; i <= d->n_src; ++i) {
+		if (src[i].n_res > d->n_res || src[i].n_blocks_table > d->nbt) { return MSCOMP_ARG_ERROR; }
+		n += src[i].n_res; rows += src[i].n_blocks_table;
+	}
+	if (n > d->n_res || rows > d->nbt || next->n_blocks_table > d->nbn) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = d->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[39];
+	view_args(args, k.v, { d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_class, d_count, d_status });
+	const uint32_t N = (uint32_t)n, n_store = (uint32_t)(n - next->n_res);
+	return plan_run(d->mrun, c, args, [&] {
+		const MatchTab& t = d->m;
+		{ KernelTimer tm(c, "dd_clear_kernel"); launch_dedup_clear(c->stream, t.slots, t.tkey, t.tmin, c->crc_blocks); }
+		{ KernelTimer tm(c, "mt_seed_kernel"); launch_match_seed(c->stream, k, N, n_store, d->nbt, d->nbn, d->shift, t, d_status); }
+		if (d->nbt) {
+			{ KernelTimer tm(c, "dd_rows_kernel"); launch_dedup_rule3(c->stream, k, N, d->nbt, t.ufirst, d_status, c->crc_blocks); }
+			{ KernelTimer tm(c, "mt_keys_kernel"); launch_match_keys(c->stream, k, N, d->nbt, d->shift, with_crc, t, d_status, c->crc_blocks); }
+			{ KernelTimer tm(c, "mt_confirm_kernel"); launch_match_confirm(c->stream, k, N, d->nbt, d->shift, with_crc, t, c->cpd_blocks); }
+			{ KernelTimer tm(c, "mt_settle_kernel"); launch_match_settle(c->stream, k, N, d->shift, with_crc, t); }
+		}
+		if (d->nbn) { KernelTimer tm(c, "mt_runs"); launch_match_runs(c->stream, k, d->n_src, N, n_store, d->nbn, d->shift, t, d_status, d_delta_ext, d_patch_ext); }
+		{ KernelTimer tm(c, "mt_counts_kernel"); launch_match_counts(c->stream, N, n_store, d->nbn, d->nbt != 0, t, d_delta_ext_first, d_patch_ext_first, d_class, d_count, c->crc_blocks); }
 	});
 }
 

@@ -273,6 +273,22 @@ __device__ __forceinline__ void dv_block_scan(u64 (&v)[K], u64 (&carry)[K], u64 
 	__syncthreads();
 }
 
+// inclusive running maximum over the block, continued from carry; carry becomes the maximum over everything so far in every thread
+// (diff.hip, match.hip: the row that starts the run a row ends)
+__device__ __forceinline__ void dv_block_max(u64& v, u64& carry, u64* s_m)
+{
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+	#pragma unroll
+	for (uint32_t d = 1; d < 64u; d <<= 1) { const u64 o = __shfl_up(v, d, 64); if (lane >= d && o > v) { v = o; } }
+	if (lane == 63u) { s_m[w] = v; }
+	__syncthreads();
+	u64 before = carry, tot = carry;
+	for (uint32_t i = 0; i < DV_WAVES; ++i) { const u64 x = s_m[i]; if (i < w && x > before) { before = x; } if (x > tot) { tot = x; } }
+	if (before > v) { v = before; }
+	carry = tot;
+	__syncthreads();
+}
+
 // largest r with first[r] <= b (first[0] = 0 <= b < first[n]): the resource that holds block b of a block container, or the request that
 // holds unit b of a block reader; empty ones in front of it are skipped (blocks.hip, reader.hip)
 __device__ __forceinline__ uint32_t res_of_block(const u64* __restrict__ first, uint32_t n, u64 b)

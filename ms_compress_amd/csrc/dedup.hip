@@ -8,19 +8,6 @@
 namespace msc {
 
 
-// global resource g (< n0 + n1 + n2 + n3) as source and resource: the sources' resources are numbered back to back
-__device__ __forceinline__ void dd_locate(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, u64 g, u64& s, u64& r)
-{
-	s = 0; r = g;
-	if (r >= v0.n_res) { r -= v0.n_res; s = 1; if (r >= v1.n_res) { r -= v1.n_res; s = 2; if (r >= v2.n_res) { r -= v2.n_res; s = 3; } } }
-}
-
-__device__ __forceinline__ u64 dd_mix(u64 x)                // (splitmix64's finaliser)
-{
-	x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-	return x;
-}
-
 __device__ __forceinline__ u64 dd_wave_xor(u64 v)
 {
 	#pragma unroll
@@ -94,14 +81,8 @@ __global__ __launch_bounds__(256) void dd_rows_kernel(SpliceView v0, SpliceView 
 			} else if (status[x] == 0) {
 				const u64 len = o1 - o0;
 				const uint8_t* p = v.packed + o0;
-				u64 w[4] = {0, 0, 0, 0};                                       // first 16 | last 16 stored bytes
-				if (len >= 16u) {
-					const cpd_u16 a = *reinterpret_cast<const cpd_u16*>(p), b = *reinterpret_cast<const cpd_u16*>(p + len - 16u);
-					w[0] = a.w[0] | (u64)a.w[1] << 32; w[1] = a.w[2] | (u64)a.w[3] << 32; w[2] = b.w[0] | (u64)b.w[1] << 32; w[3] = b.w[2] | (u64)b.w[3] << 32;
-				} else {
-					for (uint32_t i = 0; i < (uint32_t)len; ++i) { w[i >> 3] |= (u64)p[i] << ((i & 7u) * 8u); }
-					w[2] = w[0]; w[3] = w[1];
-				}
+				u64 w[4];                                                      // first 16 | last 16 stored bytes
+				dd_edges(p, len, w);
 				h = dd_mix(k + 1u);
 				h = dd_mix(h ^ len);
 				if (with_crc) { h = dd_mix(h ^ ((u64)v.crc[j] | (u64)1 << 32)); }
@@ -286,13 +267,23 @@ static dim3 dd_grid(u64 items, uint32_t per_block, uint32_t blocks)
 	return dim3((uint32_t)(need < blocks ? need : blocks));
 }
 
+void launch_dedup_clear(hipStream_t st, u64 slots, u64* tkey, uint32_t* tmin, uint32_t blocks)
+{
+	hipLaunchKernelGGL(dd_clear_kernel, dd_grid(slots, 256u, blocks), dim3(256), 0, st, slots, tkey, tmin);
+}
+
+void launch_dedup_rule3(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t rows_max, const u64* ufirst, int32_t* status, uint32_t blocks)
+{
+	hipLaunchKernelGGL(dd_rows_kernel<false>, dd_grid(rows_max, 256u, blocks), dim3(256), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, 0u, ufirst, static_cast<u64*>(nullptr), status);
+}
+
 void launch_dedup_judge(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, const DedupTab& t, int32_t* status, uint32_t blocks)
 {
 	if (n_max == 0) { return; }
-	hipLaunchKernelGGL(dd_clear_kernel, dd_grid(t.slots, 256u, blocks), dim3(256), 0, st, t.slots, t.tkey, t.tmin);
+	launch_dedup_clear(st, t.slots, t.tkey, t.tmin, blocks);
 	hipLaunchKernelGGL(dd_seed_kernel, dim3(1), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, shift, t.ufirst, t.key, t.flag, status);
 	if (rows_max == 0) { return; }
-	hipLaunchKernelGGL(dd_rows_kernel<false>, dd_grid(rows_max, 256u, blocks), dim3(256), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, 0u, t.ufirst, t.key, status);
+	launch_dedup_rule3(st, src, n, rows_max, t.ufirst, status, blocks);
 }
 
 void launch_dedup_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, bool with_crc, const DedupTab& t, int32_t* status, uint32_t blocks)

@@ -12,21 +12,6 @@ namespace msc {
 #define DF_REFUTED 2u                                      // ... and its tables said otherwise: the stored bytes did (always with DF_CHANGED)
 #define DF_NO_BASE (~(u64)0)
 
-// inclusive running maximum over the block, continued from carry; carry becomes the maximum over everything so far in every thread
-__device__ __forceinline__ void df_block_max(u64& v, u64& carry, u64* s_m)
-{
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-	#pragma unroll
-	for (uint32_t d = 1; d < 64u; d <<= 1) { const u64 o = __shfl_up(v, d, 64); if (lane >= d && o > v) { v = o; } }
-	if (lane == 63u) { s_m[w] = v; }
-	__syncthreads();
-	u64 before = carry, tot = carry;
-	for (uint32_t i = 0; i < DV_WAVES; ++i) { const u64 x = s_m[i]; if (i < w && x > before) { before = x; } if (x > tot) { tot = x; } }
-	if (before > v) { v = before; }
-	carry = tot;
-	__syncthreads();
-}
-
 // Seed, one block, in the shape of sp_layout_kernel and dd_seed_kernel: per pair rule 1, the table checks of rule 2 (the new resource
 // before the base resource within each), the room of rule 3 and the status, and ufirst (n_pair + 1): the new rows of the pairs that passed,
 // numbered densely in pair order -- this pass's own running sum, so that a damaged block_first cannot send the row passes' search astray.
@@ -164,8 +149,8 @@ __global__ __launch_bounds__(DV_THREADS) void df_tile_kernel(SpliceView next, ui
 	u64 a[6] = {r.starts ? 1u : 0u, r.starts && r.changed ? 1u : 0u, r.live && r.changed ? 1u : 0u, bytes, r.live ? 1u : 0u, r.refuted ? 1u : 0u}, sum[6] = {0, 0, 0, 0, 0, 0};
 	dv_block_scan<6>(a, sum, s_w);
 	u64 m0 = r.starts ? u + 1u : 0, m1 = r.live && r.k == 0 ? a[2] - (r.changed ? 1u : 0u) + 1u : 0, c0 = 0, c1 = 0;
-	df_block_max(m0, c0, s_w[0]);
-	df_block_max(m1, c1, s_w[0]);
+	dv_block_max(m0, c0, s_w[0]);
+	dv_block_max(m1, c1, s_w[0]);
 	if (threadIdx.x == 0) {
 		u64* t = tsum + 8u * (u64)blockIdx.x;
 		#pragma unroll
@@ -189,8 +174,8 @@ __global__ __launch_bounds__(DV_THREADS) void df_tilescan_kernel(uint32_t tiles,
 		if (live) { m0 = tsum[8u * g + 6u]; m1 = tsum[8u * g + 7u]; }
 		dv_block_scan<6>(a, run, s_w);
 		if (m1) { m1 += a[2] - own; }                                      // the changed blocks in front of the tile
-		df_block_max(m0, c0, s_w[0]);
-		df_block_max(m1, c1, s_w[0]);
+		dv_block_max(m0, c0, s_w[0]);
+		dv_block_max(m1, c1, s_w[0]);
 		if (live) {
 			#pragma unroll
 			for (uint32_t i = 0; i < 6u; ++i) { tsum[8u * g + i] = a[i]; }
@@ -216,8 +201,8 @@ __global__ __launch_bounds__(DV_THREADS) void df_runs_kernel(uint32_t n_pair, co
 	if (blockIdx.x) { sum[0] = before[0]; sum[1] = before[1]; sum[2] = before[2]; c0 = before[6]; c1 = before[7]; }
 	dv_block_scan<3>(a, sum, s_w);
 	u64 m0 = r.starts ? u + 1u : 0, m1 = r.live && r.k == 0 ? a[2] - own[2] + 1u : 0;
-	df_block_max(m0, c0, s_w[0]);
-	df_block_max(m1, c1, s_w[0]);
+	dv_block_max(m0, c0, s_w[0]);
+	dv_block_max(m1, c1, s_w[0]);
 	if (u < ufirst[n_pair] && r.k == 0) { pfirst[3u * (u64)r.p] = a[0] - own[0]; pfirst[3u * (u64)r.p + 1u] = a[1] - own[1]; pfirst[3u * (u64)r.p + 2u] = a[2] - own[2]; }
 	if (!r.ends) { return; }
 	const u64 u0 = m0 - 1u, cnt = u - u0 + 1u, k0 = u0 - ufirst[r.p];          // the run [u0, u]: a run lies in one pair

@@ -349,6 +349,30 @@ __device__ __forceinline__ SpliceView sp_view(const SpliceView& v0, const Splice
 	return SpliceView{ SP_PICK(packed), SP_PICK(packed_len), SP_PICK(first), SP_PICK(off), SP_PICK(res_len), SP_PICK(crc), SP_PICK(n_res), SP_PICK(nbt) };
 }
 #undef SP_PICK
+// Shared by dedup.hip and match.hip. Global resource g (< n0 + n1 + n2 + n3) as source and resource: the sources' resources are numbered
+// back to back
+__device__ __forceinline__ void dd_locate(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, u64 g, u64& s, u64& r)
+{
+	s = 0; r = g;
+	if (r >= v0.n_res) { r -= v0.n_res; s = 1; if (r >= v1.n_res) { r -= v1.n_res; s = 2; if (r >= v2.n_res) { r -= v2.n_res; s = 3; } } }
+}
+__device__ __forceinline__ u64 dd_mix(u64 x)                // (splitmix64's finaliser)
+{
+	x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+	return x;
+}
+// the first min(16, len) stored bytes of a row in w[0], w[1] and the last min(16, len) in w[2], w[3]: the part of a key tuple that is data
+__device__ __forceinline__ void dd_edges(const uint8_t* __restrict__ p, u64 len, u64 (&w)[4])
+{
+	w[0] = w[1] = w[2] = w[3] = 0;
+	if (len >= 16u) {
+		const cpd_u16 a = *reinterpret_cast<const cpd_u16*>(p), b = *reinterpret_cast<const cpd_u16*>(p + len - 16u);
+		w[0] = a.w[0] | (u64)a.w[1] << 32; w[1] = a.w[2] | (u64)a.w[3] << 32; w[2] = b.w[0] | (u64)b.w[1] << 32; w[3] = b.w[2] | (u64)b.w[3] << 32;
+	} else {
+		for (uint32_t i = 0; i < (uint32_t)len; ++i) { w[i >> 3] |= (u64)p[i] << ((i & 7u) * 8u); }
+		w[2] = w[0]; w[3] = w[1];
+	}
+}
 // one block: rules 1-3 per pick (pick: 2 n_pick, source and resource), new_first (n_pick + 1), new_len and status (n_pick), then per NEW row
 // new_off (nbt + 1), new_crc (nbt, may be null) and addr (nbt, for launch_blocks_move), then rule 7
 void launch_splice_layout(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n_pick, uint32_t nbt, uint32_t shift, u64 cap, const u64* pick,
@@ -392,6 +416,10 @@ struct DedupTab {
 // with an empty one); n = the resources of this call (<= n_max), status = d_status, which the stages read back.
 // judge: the key table cleared, rules 1 and 2 and the row numbering (one block), rule 3 (a fixed grid over the rows); `blocks` = crc_dev_blocks()
 void launch_dedup_judge(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, const DedupTab& t, int32_t* status, uint32_t blocks);
+// the two row-independent pieces of judge, as mscomp_amd_deduper_match launches them over tables of its own: a key table cleared; rule 3 over
+// the rows of the numbering ufirst (n + 1)
+void launch_dedup_clear(hipStream_t st, u64 slots, u64* tkey, uint32_t* tmin, uint32_t blocks);
+void launch_dedup_rule3(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t rows_max, const u64* ufirst, int32_t* status, uint32_t blocks);
 // keys: the accepted resources' keys (the same grid over the rows), the keys into the table, the candidates (a thread per resource)
 void launch_dedup_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, bool with_crc, const DedupTab& t, int32_t* status, uint32_t blocks);
 // confirm: the byte compare, a fixed grid over (row, 16 KiB piece) items; `blocks` = compact_dev_blocks()
@@ -423,6 +451,40 @@ void launch_diff_confirm(hipStream_t st, const SpliceView& base, const SpliceVie
 void launch_diff_runs(hipStream_t st, const SpliceView& next, uint32_t n_pair, uint32_t nbn, const u64* pair, const DiffTab& t, const int32_t* status, u64* delta_ext, u64* patch_ext);
 // counts: delta_first and patch_first (n_pair + 1, may be null when n_pair is 0), changed (n_pair), count (4)
 void launch_diff_counts(hipStream_t st, uint32_t n_pair, uint32_t nbn, const DiffTab& t, u64* delta_first, u64* patch_first, u64* changed, u64* count, uint32_t blocks);
+
+// mscomp_amd_deduper_match, the deduper's third call (match.hip): for every block of the resources of `next`, whether an equal block lies in
+// one of up to three store containers (found), earlier in next (shared) or nowhere (fresh), answered as the delta and the patch extent
+// lists. The views travel as a splicer's, the stores first and next at index n_src. The scratch of a deduper made for it (blockobj.hip
+// match_tab knows the layout); n = n_res_total, m = n_blocks_total, mn = n_blocks_new:
+#define MT_TILE DV_THREADS                             // rows per workgroup of the run passes (MSCOMP_AMD_SPLICE_ROW_TILE)
+inline uint32_t match_row_tiles(uint32_t nbn) { return (nbn + MT_TILE - 1u) / MT_TILE; }
+struct MatchTab {
+	u64* ufirst;                                       // n + 1: first row of every resource, in a numbering of the rows of the resources that passed rules 1, 2 and 4
+	u64* pfirst;                                       // 5 n: per resource of next the patch runs, fresh runs, found, shared and fresh blocks in front of its first row
+	u64* tsum;                                         // 8 match_row_tiles(mn): seven sums and one maximum per tile of next's rows, then their running values
+	u64* tkey;                                         // slots: the key a slot was claimed for (0 = empty)
+	u64* nref;                                         // 1: the refuted rows of the execution
+	uint32_t* tmin;                                    // slots: the smallest row with the slot's key
+	uint32_t *slot_of, *flag, *rep, *rlist;            // m each: the row's slot (all-ones: none); 1 = not equal to its slot's smallest row; rep(u); the refuted rows, ascending
+	uint32_t* flocal;                                  // mn: the fresh rows of its tile in front of a row of next
+	u64 slots;
+};
+// The call in six stages, ten launches fixed by the creation bounds (three when n_blocks_total is 0, seven when n_blocks_new is 0; the
+// caller leaves the others out, and launches launch_dedup_clear in front and launch_dedup_rule3 behind the seed).
+// seed (one block): rules 1, 2 and 4, status (n), t.ufirst; n_store = the resources of the stores
+void launch_match_seed(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_store, uint32_t nbt, uint32_t nbn, uint32_t shift, const MatchTab& t, int32_t* status);
+// keys: per row of an accepted resource its key into the table and itself into its slot's minimum; t.slot_of, t.flag; `blocks` = crc_dev_blocks()
+void launch_match_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t nbt, uint32_t shift, bool with_crc, const MatchTab& t, const int32_t* status, uint32_t blocks);
+// confirm: a row against its slot's smallest row, a fixed grid over (row, 16 KiB piece) items; t.flag, and t.rep as the tables give it; `blocks` = compact_dev_blocks()
+void launch_match_confirm(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t nbt, uint32_t shift, bool with_crc, const MatchTab& t, uint32_t blocks);
+// settle (one block): the flagged rows listed and answered exactly in t.rep, t.nref
+void launch_match_settle(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t shift, bool with_crc, const MatchTab& t);
+// runs (three launches over next's rows: the tiles' sums, their running values in one block, the rows): delta_ext and patch_ext (4 mn each), t.pfirst
+void launch_match_runs(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n, uint32_t n_store, uint32_t nbn, uint32_t shift, const MatchTab& t, const int32_t* status,
+                       u64* delta_ext, u64* patch_ext);
+// counts: delta_first and patch_first (next's n_res + 1, may be null when n is 0), cls (3 per resource of next), count (6); `settled`: t.nref was written
+void launch_match_counts(hipStream_t st, uint32_t n, uint32_t n_store, uint32_t nbn, bool settled, const MatchTab& t, u64* delta_first, u64* patch_first, u64* cls, u64* count,
+                         uint32_t blocks);
 
 // ---- block transcoders (transcode.hip; mscomp_amd_transcoder_*) ----
 // What a transcoder is made for, by value in every kernel's arguments. A group is an aligned span of G = 1 << sg bytes of a resource
