@@ -8,6 +8,7 @@ PyTorch is plumbing only: device memory (``torch.empty(..., device="cuda")``), t
 ``torch.distributed``. There is NO CPU encoder behind these functions: if the HIP extension is missing or no
 GPU is visible they raise.
 """
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -391,6 +392,43 @@ def _ok(st, name):
         raise MSCompError(st, name)
 
 
+@contextlib.contextmanager
+def _call(ctx, enter=True):
+    """The frame of a host convenience: ``ctx`` or, for None, a Context of its own that is closed on the way out; the context's device and
+    stream are torch's current ones inside (not with ``enter`` False: a wrapper whose inner calls enter them). Yields (ctx, torch device)."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context()
+    dev = torch.device("cuda", ctx.device)
+    try:
+        if enter:
+            with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+                yield ctx, dev
+        else:
+            yield ctx, dev
+    finally:
+        if own:
+            ctx.close()
+
+
+def _three_counts(obj, export):
+    """the three uint32 counters ``export`` reads from the object ``obj`` (the call synchronizes the stream)"""
+    out = (C.c_uint32 * 3)()
+    if getattr(obj.ctx.lib, export)(obj._h, out) != 0:
+        raise MSCompError(MSCOMP_ERRNO, export)
+    return (int(out[0]), int(out[1]), int(out[2]))
+
+
+def _byte_bounds(d_packed=None, packed_len=None, d_new_packed=None, new_cap=None):
+    """(packed_len, new_cap) as a call passes them on: each defaults to all of its tensor (0 without one), and a new_cap beyond
+    d_new_packed is refused."""
+    plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
+    cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
+    if d_new_packed is not None and cap > d_new_packed.numel():
+        raise ValueError("new_cap exceeds d_new_packed")
+    return plen, cap
+
+
 class _Handle:
     """An object of the library that lives in a context: ``ctx``, the handle ``_h`` and the export that destroys it."""
     _destroy = "mscomp_amd_plan_destroy"
@@ -584,11 +622,8 @@ def blocks_compress(fmt, buffers, block_size, ctx=None):
     packed[block_off[block_first[r] + j] : block_off[block_first[r] + j + 1]], the bytes of ms_compress for that block when they are
     shorter than the block, the block itself otherwise."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     n = len(buffers)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         d_in, d_off, d_len, lens = _upload_unit_tables(buffers, dev)
         total = int(sum(lens))
         bk = BlockContainer(ctx, fmt, block_size, n, total)
@@ -604,19 +639,14 @@ def blocks_compress(fmt, buffers, block_size, ctx=None):
         packed = d_packed.cpu().numpy()[: int(boff[nb])].copy()
         st = d_st.cpu().numpy()[:n].copy()
         bk.close()
-    if own:
-        ctx.close()
     return packed, first, boff, st
 
 
 def crc32_units(units, ctx=None):
     """zlib's crc32 of every byte string of a list, computed on the GPU (CrcDevPlan). Returns a numpy uint32 array."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     n = len(units)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         d_in, d_off, d_len, lens = _upload_unit_tables(units, dev)
         d_crc = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
@@ -625,8 +655,6 @@ def crc32_units(units, ctx=None):
         ctx.stream.synchronize()
         out, st = d_crc.cpu().numpy().view(np.uint32)[:n].copy(), d_st.cpu().numpy()[:n]
         plan.close()
-    if own:
-        ctx.close()
     if st.any():
         raise MSCompError(int(st[st != 0][0]), "mscomp_amd_plan_execute_crc_dev")
     return out
@@ -636,11 +664,8 @@ def blocks_crc(fmt, buffers, block_size, ctx=None):
     """The checksums a block container keeps beside a list of byte strings (one resource each), computed on the GPU. Returns numpy uint32
     arrays (block_crc of nb entries, in the block order of blocks_compress; res_crc of n): zlib's crc32 of every block and of every resource."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     n = len(buffers)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         d_in, d_off, d_len, lens = _upload_unit_tables(buffers, dev)
         bk = BlockContainer(ctx, fmt, block_size, n, int(sum(lens)))
         d_bcrc = torch.zeros(max(1, bk.n_blocks_max), dtype=torch.int32, device=dev)
@@ -651,8 +676,6 @@ def blocks_crc(fmt, buffers, block_size, ctx=None):
         nb = sum((x + block_size - 1) // block_size for x in lens)
         out = d_bcrc.cpu().numpy().view(np.uint32)[:nb].copy(), d_rcrc.cpu().numpy().view(np.uint32)[:n].copy()
         bk.close()
-    if own:
-        ctx.close()
     return out
 
 
@@ -662,14 +685,11 @@ def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, 
     it): the decoded blocks are held to these checksums, and a resource with a mismatch gets MSCOMP_DATA_ERROR. Returns (list of bytes, or
     None where the status is not MSCOMP_OK; list of status)."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     n = len(lengths)
     lens = [int(x) for x in lengths]
     total = int(sum(lens))
     out_off, out_total = pack_offsets(lens)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         bk = BlockContainer(ctx, fmt, block_size, n, total)
         packed, d_packed = _dev_packed(packed, dev)
         d_first, d_boff = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, bk.n_blocks_max + 1, dev)
@@ -685,13 +705,11 @@ def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, 
         h_out, h_len, h_st = d_out.cpu().numpy(), d_olen.cpu().numpy(), d_st.cpu().numpy()
         bk.close()
     res = [bytes(h_out[int(out_off[i]): int(out_off[i]) + int(h_len[i])]) if h_st[i] == MSCOMP_OK else None for i in range(n)]
-    if own:
-        ctx.close()
     return res, [int(x) for x in h_st[:n]]
 
 
 class _BlockAccess(_Handle):
-    """What BlockReader and BlockWriter share: the arguments they are made with, and counts()."""
+    """What BlockReader and BlockWriter share: the arguments they are made with; ``_counts`` names the export their counts() read."""
 
     def __init__(self, ctx, fmt, block_size, n_res, n_blocks_table, n_req, blocks_max):
         _Handle.__init__(self, ctx)
@@ -699,12 +717,6 @@ class _BlockAccess(_Handle):
         self.n_res, self.n_blocks_table, self.n_req, self.blocks_max = int(n_res), int(n_blocks_table), int(n_req), int(blocks_max)
         _ok(getattr(ctx.lib, self._create)(ctx._h, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_req, self.blocks_max, 0,
                                            C.byref(self._h)), self._create)
-
-    def _read_counts(self):
-        out = (C.c_uint32 * 3)()
-        if getattr(self.ctx.lib, self._counts)(self._h, out) != 0:
-            raise MSCompError(MSCOMP_ERRNO, self._counts)
-        return (int(out[0]), int(out[1]), int(out[2]))
 
 
 class BlockReader(_BlockAccess):
@@ -723,13 +735,13 @@ class BlockReader(_BlockAccess):
         over the budget of blocks_max), MSCOMP_BUF_ERROR (more than d_out_cap[q]) or MSCOMP_DATA_ERROR (a damaged table or block; with
         ``d_block_crc``, as BlockContainer.crc wrote it, a block whose CRC-32 differs) with d_out_len[q] = 0 and nothing written.
         ``packed_len``: the valid bytes of d_packed (default: all of it)."""
-        plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
+        plen, _ = _byte_bounds(d_packed, packed_len)
         p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_out, d_out_off, d_out_cap, d_out_len, d_status)
         _ok(self.ctx.lib.mscomp_amd_reader_read(self._h, p[0], plen, *p[1:]), "mscomp_amd_reader_read")
 
     def counts(self):
         """(units, distinct blocks, blocks decoded rather than raw) of the last read(); synchronizes the stream."""
-        return self._read_counts()
+        return _three_counts(self, self._counts)
 
 
 def blocks_read(fmt, packed, block_first, block_off, lengths, block_size, requests, ctx=None, block_crc=None):
@@ -737,8 +749,6 @@ def blocks_read(fmt, packed, block_first, block_off, lengths, block_size, reques
     as pread does; ``lengths`` are the resources' original lengths. ``block_crc`` (optional, as blocks_crc returns it): every block read is
     held to its checksum. Returns (list of bytes, or None where the status is not MSCOMP_OK; list of status)."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     n, nq = len(lengths), len(requests)
     lens = [int(x) for x in lengths]
     B = int(block_size)
@@ -747,8 +757,7 @@ def blocks_read(fmt, packed, block_first, block_off, lengths, block_size, reques
     wants, blocks = _covering_blocks(reqs, lens, B)            # (the capacities, and the budget)
     out_off, out_total = pack_offsets(wants)
     nbt = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         rd = BlockReader(ctx, fmt, B, n, nbt, nq, blocks)
         packed, d_packed = _dev_packed(packed, dev)
         d_first, d_boff, d_len = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, nbt + 1, dev), _dev_u64(lens, 1, dev)
@@ -763,8 +772,6 @@ def blocks_read(fmt, packed, block_first, block_off, lengths, block_size, reques
         h_out, h_len, h_st = d_out.cpu().numpy(), d_olen.cpu().numpy(), d_st.cpu().numpy()
         rd.close()
     res = [bytes(h_out[int(out_off[i]): int(out_off[i]) + int(h_len[i])]) if h_st[i] == MSCOMP_OK else None for i in range(nq)]
-    if own:
-        ctx.close()
     return res, [int(x) for x in h_st[:nq]]
 
 
@@ -787,10 +794,7 @@ class BlockWriter(_BlockAccess):
         the budget of blocks_max) or MSCOMP_DATA_ERROR (a damaged table or block) with d_written[q] = 0 and no byte of the request
         applied. d_res_status[r] is MSCOMP_BUF_ERROR when a block of the resource did not fit below new_cap. A touched block is decoded,
         patched in request order and encoded again; every other block keeps its stored bytes."""
-        plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
-        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
-        if d_new_packed is not None and cap > d_new_packed.numel():
-            raise ValueError("new_cap exceeds d_new_packed")
+        plen, cap = _byte_bounds(d_packed, packed_len, d_new_packed, new_cap)
         p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_src, d_src_off, d_new_packed, d_new_block_off, d_new_block_crc,
                   d_written, d_status, d_res_status)
         _ok(self.ctx.lib.mscomp_amd_writer_write(self._h, p[0], plen, *p[1:9], cap, *p[9:]), "mscomp_amd_writer_write")
@@ -804,10 +808,7 @@ class BlockWriter(_BlockAccess):
         it) or MSCOMP_ARG_ERROR (over the budget of blocks_max changed and fresh blocks) with the resource carried as it was, or
         MSCOMP_BUF_ERROR (a block did not fit below new_cap); all MSCOMP_ARG_ERROR with zeroed tables when the new table needs more than
         n_blocks_table rows. Only the block the new end falls into is decoded; it and the fresh blocks are encoded."""
-        plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
-        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
-        if d_new_packed is not None and cap > d_new_packed.numel():
-            raise ValueError("new_cap exceeds d_new_packed")
+        plen, cap = _byte_bounds(d_packed, packed_len, d_new_packed, new_cap)
         p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_want_len, d_new_packed, d_new_block_first, d_new_block_off,
                   d_new_block_crc, d_new_res_len, d_res_status)
         _ok(self.ctx.lib.mscomp_amd_writer_resize(self._h, p[0], plen, *p[1:7], cap, *p[7:]), "mscomp_amd_writer_resize")
@@ -815,7 +816,7 @@ class BlockWriter(_BlockAccess):
     def counts(self):
         """(units, distinct blocks touched, blocks encoded again) of the last write(), or (units, changed blocks decoded, blocks encoded) of
         the last resize(); synchronizes the stream."""
-        return self._read_counts()
+        return _three_counts(self, self._counts)
 
 
 def blocks_write(fmt, packed, block_first, block_off, lengths, block_size, writes, ctx=None, block_crc=None):
@@ -825,8 +826,6 @@ def blocks_write(fmt, packed, block_first, block_off, lengths, block_size, write
     lists (new_packed uint8, new_block_off uint64, new_block_crc uint32 or None, written, statuses, res_statuses): the new container
     shares block_first and lengths with the old one."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     n, nq = len(lengths), len(writes)
     lens = [int(x) for x in lengths]
     B = int(block_size)
@@ -836,8 +835,7 @@ def blocks_write(fmt, packed, block_first, block_off, lengths, block_size, write
     src_off, src_total = pack_offsets([len(b) for _, _, b in writes])
     nbt = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
     total = int(sum(lens))
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         wr = BlockWriter(ctx, fmt, B, n, nbt, nq, blocks)
         packed, d_packed = _dev_packed(packed, dev)
         h_src = np.zeros(src_total + 16, dtype=np.uint8)
@@ -846,24 +844,17 @@ def blocks_write(fmt, packed, block_first, block_off, lengths, block_size, write
         d_src = torch.from_numpy(h_src).to(dev)
         d_first, d_boff, d_len = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, nbt + 1, dev), _dev_u64(lens, 1, dev)
         d_req, d_soff = _dev_u64(np.array(reqs, dtype=np.uint64), 3, dev), _dev_u64(src_off, 1, dev)
-        d_crc = d_ncrc = None
-        if block_crc is not None:
-            d_crc, d_ncrc = _dev_block_crc(block_crc, nbt, dev), torch.zeros(max(1, nbt), dtype=torch.int32, device=dev)
-        d_new = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
-        d_noff = torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
+        d_crc = None if block_crc is None else _dev_block_crc(block_crc, nbt, dev)
+        d_new, _, d_noff, d_ncrc = _new_container(dev, None, nbt, total, block_crc is not None)
         d_wr = torch.zeros(max(1, nq), dtype=torch.int64, device=dev)
         d_st = torch.zeros(max(1, nq), dtype=torch.int32, device=dev)
         d_rst = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         wr.write(d_packed, d_first, d_boff, d_len, d_req, d_src, d_soff, d_new, d_noff, d_wr, d_st, d_rst, d_block_crc=d_crc, d_new_block_crc=d_ncrc,
                  packed_len=len(packed), new_cap=total)
         ctx.stream.synchronize()
-        noff = d_noff.cpu().numpy().view(np.uint64).copy()
-        new_packed = d_new.cpu().numpy()[: min(int(noff[nbt]), total)].copy()
-        ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nbt].copy()
+        new_packed, _, noff, ncrc = _fetch_container(d_new, None, d_noff, d_ncrc, total)
         h_wr, h_st, h_rst = d_wr.cpu().numpy().view(np.uint64), d_st.cpu().numpy(), d_rst.cpu().numpy()
         wr.close()
-    if own:
-        ctx.close()
     return new_packed, noff, ncrc, [int(x) for x in h_wr[:nq]], [int(x) for x in h_st[:nq]], [int(x) for x in h_rst[:n]]
 
 
@@ -873,8 +864,6 @@ def blocks_resize(fmt, packed, block_first, block_off, lengths, block_size, new_
     container gets checksums too). Returns numpy arrays and lists (new_packed uint8, new_block_off uint64, new_block_crc uint32 or None,
     new_first uint64 of n + 1, new_lengths, res_statuses); the tables have as many rows as the resized container needs."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     n = len(lengths)
     lens, want = [int(x) for x in lengths], [int(x) for x in new_lengths]
     if len(want) != n:
@@ -886,31 +875,20 @@ def blocks_resize(fmt, packed, block_first, block_off, lengths, block_size, new_
     nb_old = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
     nbt = max(nb_old, sum(blocks(max(a, b)) for a, b in zip(lens, want)))
     room = sum(max(a, b) for a, b in zip(lens, want))
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         wr = BlockWriter(ctx, fmt, B, n, nbt, 0, budget)
         packed, d_packed = _dev_packed(packed, dev)
         d_first, d_boff, d_len, d_want = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, nbt + 1, dev), _dev_u64(lens, 1, dev), _dev_u64(want, 1, dev)
-        d_crc = d_ncrc = None
-        if block_crc is not None:
-            d_crc, d_ncrc = _dev_block_crc(block_crc, nbt, dev), torch.zeros(max(1, nbt), dtype=torch.int32, device=dev)
-        d_new = torch.zeros(room + 16, dtype=torch.uint8, device=dev)
-        d_nfirst = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        d_noff = torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
+        d_crc = None if block_crc is None else _dev_block_crc(block_crc, nbt, dev)
+        d_new, d_nfirst, d_noff, d_ncrc = _new_container(dev, n, nbt, room, block_crc is not None)
         d_nlen = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
         d_rst = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         wr.resize(d_packed, d_first, d_boff, d_len, d_want, d_new, d_nfirst, d_noff, d_nlen, d_rst, d_block_crc=d_crc, d_new_block_crc=d_ncrc,
                   packed_len=len(packed), new_cap=room)
         ctx.stream.synchronize()
-        nfirst = d_nfirst.cpu().numpy().view(np.uint64).copy()
-        nb = int(nfirst[n])
-        noff = d_noff.cpu().numpy().view(np.uint64)[: nb + 1].copy()
-        new_packed = d_new.cpu().numpy()[: min(int(noff[nb]), room)].copy()
-        ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nb].copy()
+        new_packed, nfirst, noff, ncrc = _fetch_container(d_new, d_nfirst, d_noff, d_ncrc, room)
         h_len, h_rst = d_nlen.cpu().numpy().view(np.uint64), d_rst.cpu().numpy()
         wr.close()
-    if own:
-        ctx.close()
     return new_packed, noff, ncrc, nfirst, [int(x) for x in h_len[:n]], [int(x) for x in h_rst[:n]]
 
 
@@ -954,9 +932,7 @@ class BlockSplicer(_Handle):
         default: all of it). d_status[p] is MSCOMP_OK, MSCOMP_ARG_ERROR (no such source or resource, a broken table entry, or no room in
         the new table) or MSCOMP_DATA_ERROR (a wrong block count) with pick p an empty resource, or MSCOMP_BUF_ERROR (a block did not fit
         below new_cap)."""
-        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
-        if d_new_packed is not None and cap > d_new_packed.numel():
-            raise ValueError("new_cap exceeds d_new_packed")
+        _, cap = _byte_bounds(d_new_packed=d_new_packed, new_cap=new_cap)
         if len(sources) != self.n_src:
             raise ValueError("one source per n_src")
         views = _blocks_views(sources)
@@ -984,9 +960,7 @@ class BlockSplicer(_Handle):
         are splice()'s, per new resource. d_status[q] is MSCOMP_OK, MSCOMP_ARG_ERROR (no such source, resource or block range, a broken
         table entry, an extent that ends short in front of another, or no room in the new table) or MSCOMP_DATA_ERROR (a wrong block
         count) with resource q empty, or MSCOMP_BUF_ERROR (a block did not fit below new_cap)."""
-        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
-        if d_new_packed is not None and cap > d_new_packed.numel():
-            raise ValueError("new_cap exceeds d_new_packed")
+        _, cap = _byte_bounds(d_new_packed=d_new_packed, new_cap=new_cap)
         if len(sources) != self.n_src:
             raise ValueError("one source per n_src")
         views = _blocks_views(sources)
@@ -997,36 +971,18 @@ class BlockSplicer(_Handle):
 def _splice_host(containers, n_new, nbt, room, ctx, make, run):
     """what blocks_splice and blocks_splice_extents share: the sources uploaded, the new arrays made, ``run`` called, the results fetched"""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
-    lens = [[int(x) for x in c[3]] for c in containers]
     with_crc = all(c[4] is not None for c in containers)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         sp = make(ctx)
-        srcs = []
-        for (packed, first, off, _, crc), ln in zip(containers, lens):
-            packed, d_packed = _dev_packed(packed, dev)
-            rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
-            srcs.append((d_packed, _dev_u64(first, len(ln) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(ln, 1, dev),
-                         _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(ln), rows))
-        d_new = torch.zeros(room + 16, dtype=torch.uint8, device=dev)
-        d_nfirst = torch.zeros(n_new + 1, dtype=torch.int64, device=dev)
-        d_noff = torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
-        d_ncrc = torch.zeros(max(1, nbt), dtype=torch.int32, device=dev) if with_crc else None
+        srcs, _, _ = _upload_containers(containers, dev, with_crc)
+        d_new, d_nfirst, d_noff, d_ncrc = _new_container(dev, n_new, nbt, room, with_crc)
         d_nlen = torch.zeros(max(1, n_new), dtype=torch.int64, device=dev)
         d_st = torch.zeros(max(1, n_new), dtype=torch.int32, device=dev)
         run(sp, srcs, dev, d_new, d_nfirst, d_noff, d_nlen, d_st, d_ncrc)
         ctx.stream.synchronize()
-        nfirst = d_nfirst.cpu().numpy().view(np.uint64).copy()
-        nb = int(nfirst[n_new])
-        noff = d_noff.cpu().numpy().view(np.uint64)[: nb + 1].copy()
-        new_packed = d_new.cpu().numpy()[: min(int(noff[nb]), room)].copy()
-        ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nb].copy()
+        new_packed, nfirst, noff, ncrc = _fetch_container(d_new, d_nfirst, d_noff, d_ncrc, room)
         h_len, h_st = d_nlen.cpu().numpy().view(np.uint64), d_st.cpu().numpy()
         sp.close()
-    if own:
-        ctx.close()
     return new_packed, nfirst, noff, [int(x) for x in h_len[:n_new]], ncrc, [int(x) for x in h_st[:n_new]]
 
 
@@ -1206,23 +1162,14 @@ def blocks_diff(base, new, block_size, pairs=None, ctx=None):
     resource lists have the shape blocks_splice_extents takes -- blocks_splice_extents([new], delta_resources, block_size) is the delta
     container, blocks_patch(base, delta, patch_resources, block_size) the new resources again."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     B = int(block_size)
     pr = _diff_pairs(base, new, pairs)
     n = len(pr)
     new_lens = [int(x) for x in new[3]]
     nbn = sum((new_lens[b] + B - 1) // B for _, b in pr if b < len(new_lens))
     with_crc = base[4] is not None and new[4] is not None
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
-        srcs = []
-        for packed, first, off, lens, crc in (base, new):
-            lens = [int(x) for x in lens]
-            packed, d_packed = _dev_packed(packed, dev)
-            rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
-            srcs.append((d_packed, _dev_u64(first, len(lens) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(lens, 1, dev),
-                         _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(lens), rows))
+    with _call(ctx) as (ctx, dev):
+        srcs, _, _ = _upload_containers((base, new), dev, with_crc)
         dd = BlockDeduper.for_diff(ctx, B, n, nbn)
         d_pair = _dev_u64(np.array(pr, dtype=np.uint64).reshape(-1), 2, dev)
         d_df, d_pf = torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(n + 1, dtype=torch.int64, device=dev)
@@ -1235,8 +1182,6 @@ def blocks_diff(base, new, block_size, pairs=None, ctx=None):
         delta, patch = _extent_lists(u64(d_df), u64(d_de), n), _extent_lists(u64(d_pf), u64(d_pe), n)
         changed, counts, st = [int(x) for x in u64(d_ch)[:n]], [int(x) for x in u64(d_cnt)], [int(x) for x in d_st.cpu().numpy()[:n]]
         dd.close()
-    if own:
-        ctx.close()
     return delta, patch, changed, counts, st
 
 
@@ -1245,13 +1190,10 @@ def blocks_delta(base, new, block_size, pairs=None, ctx=None):
     recipe that rebuilds the new resources from base + delta: blocks_diff, then blocks_splice_extents over [new]. Returns (delta,
     patch_resources, changed, counts, statuses), delta = (packed, block_first, block_off, lengths, block_crc or None): a container as
     blocks_patch and blocks_splice take one."""
-    own = ctx is None
-    ctx = ctx or Context()
-    delta_res, patch_res, changed, counts, st = blocks_diff(base, new, block_size, pairs=pairs, ctx=ctx)
-    with_crc = base[4] is not None and new[4] is not None
-    packed, first, off, lens, crc, _ = blocks_splice_extents([new if with_crc else tuple(new[:4]) + (None,)], delta_res, block_size, ctx=ctx)
-    if own:
-        ctx.close()
+    with _call(ctx, enter=False) as (ctx, _):
+        delta_res, patch_res, changed, counts, st = blocks_diff(base, new, block_size, pairs=pairs, ctx=ctx)
+        with_crc = base[4] is not None and new[4] is not None
+        packed, first, off, lens, crc, _ = blocks_splice_extents([new if with_crc else tuple(new[:4]) + (None,)], delta_res, block_size, ctx=ctx)
     return (packed, first, off, lens, crc), patch_res, changed, counts, st
 
 
@@ -1270,21 +1212,11 @@ def blocks_match(stores, new, block_size, ctx=None):
     shared, fresh) per resource of ``new``, counts the six of BlockDeduper.match, statuses one per resource of the stores back to back
     and then of ``new``."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     B = int(block_size)
     cons = list(stores) + [new]
     with_crc = all(c[4] is not None for c in cons)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
-        srcs, n_all, rows_all = [], 0, 0
-        for packed, first, off, lens, crc in cons:
-            lens = [int(x) for x in lens]
-            packed, d_packed = _dev_packed(packed, dev)
-            rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
-            n_all += len(lens); rows_all += rows
-            srcs.append((d_packed, _dev_u64(first, len(lens) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(lens, 1, dev),
-                         _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(lens), rows))
+    with _call(ctx) as (ctx, dev):
+        srcs, n_all, rows_all = _upload_containers(cons, dev, with_crc)
         n, nbn = srcs[-1][6], srcs[-1][7]
         dd = BlockDeduper.for_match(ctx, B, len(stores), n_all, rows_all, nbn)
         d_df, d_pf = torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(n + 1, dtype=torch.int64, device=dev)
@@ -1298,8 +1230,6 @@ def blocks_match(stores, new, block_size, ctx=None):
         classes = [tuple(int(x) for x in row) for row in u64(d_cl)[: 3 * n].reshape(-1, 3)]
         counts, st = [int(x) for x in u64(d_cnt)], [int(x) for x in d_st.cpu().numpy()[:n_all]]
         dd.close()
-    if own:
-        ctx.close()
     return delta, patch, classes, counts, st
 
 
@@ -1307,13 +1237,10 @@ def blocks_match_delta(stores, new, block_size, ctx=None):
     """The delta container of ``new`` against the ``stores`` -- per resource the blocks no store holds and ``new`` has not held before, in
     order -- together with the recipe that rebuilds ``new`` from stores + delta: blocks_match, then blocks_splice_extents over [new].
     Returns (delta, patch_resources, classes, counts, statuses), delta = (packed, block_first, block_off, lengths, block_crc or None)."""
-    own = ctx is None
-    ctx = ctx or Context()
-    delta_res, patch_res, classes, counts, st = blocks_match(stores, new, block_size, ctx=ctx)
-    with_crc = all(c[4] is not None for c in list(stores) + [new])
-    packed, first, off, lens, crc, _ = blocks_splice_extents([new if with_crc else tuple(new[:4]) + (None,)], delta_res, block_size, ctx=ctx)
-    if own:
-        ctx.close()
+    with _call(ctx, enter=False) as (ctx, _):
+        delta_res, patch_res, classes, counts, st = blocks_match(stores, new, block_size, ctx=ctx)
+        with_crc = all(c[4] is not None for c in list(stores) + [new])
+        packed, first, off, lens, crc, _ = blocks_splice_extents([new if with_crc else tuple(new[:4]) + (None,)], delta_res, block_size, ctx=ctx)
     return (packed, first, off, lens, crc), patch_res, classes, counts, st
 
 
@@ -1335,20 +1262,9 @@ def blocks_dedup(containers, block_size, ctx=None):
     statuses): blocks_splice(containers, picks, block_size) is the merged container with one copy of everything, and resource g of the
     sources is its resource new_index[g]."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
-    lens = [[int(x) for x in c[3]] for c in containers]
-    n = sum(len(ln) for ln in lens)
     with_crc = all(c[4] is not None for c in containers)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
-        srcs, rows_all = [], 0
-        for (packed, first, off, _, crc), ln in zip(containers, lens):
-            packed, d_packed = _dev_packed(packed, dev)
-            rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
-            rows_all += rows
-            srcs.append((d_packed, _dev_u64(first, len(ln) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(ln, 1, dev),
-                         _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(ln), rows))
+    with _call(ctx) as (ctx, dev):
+        srcs, n, rows_all = _upload_containers(containers, dev, with_crc)
         dd = BlockDeduper(ctx, block_size, len(containers), n, rows_all)
         d_rep, d_idx = torch.zeros(max(1, n), dtype=torch.int64, device=dev), torch.zeros(max(1, n), dtype=torch.int64, device=dev)
         d_pick, d_cnt = torch.zeros(max(1, 2 * n), dtype=torch.int64, device=dev), torch.zeros(4, dtype=torch.int64, device=dev)
@@ -1359,8 +1275,6 @@ def blocks_dedup(containers, block_size, ctx=None):
         picks = d_pick.cpu().numpy().view(np.uint64)[: 2 * counts[0]].reshape(-1, 2)
         rep, idx, st = d_rep.cpu().numpy().view(np.uint64)[:n], d_idx.cpu().numpy().view(np.uint64)[:n], d_st.cpu().numpy()[:n]
         dd.close()
-    if own:
-        ctx.close()
     return [int(x) for x in rep], [int(x) for x in idx], [(int(s), int(r)) for s, r in picks], counts, [int(x) for x in st]
 
 
@@ -1389,19 +1303,13 @@ class BlockTranscoder(_Handle):
         block count, a broken table entry or chunk header, a block that does not decode or not to its checksum), MSCOMP_ARG_ERROR (no room
         in the new table, or over the budget of groups_max) with resource r left without blocks, or MSCOMP_BUF_ERROR (a block did not fit
         below new_cap)."""
-        plen = (0 if d_packed is None else d_packed.numel()) if packed_len is None else int(packed_len)
-        cap = (0 if d_new_packed is None else d_new_packed.numel()) if new_cap is None else int(new_cap)
-        if d_new_packed is not None and cap > d_new_packed.numel():
-            raise ValueError("new_cap exceeds d_new_packed")
+        plen, cap = _byte_bounds(d_packed, packed_len, d_new_packed, new_cap)
         p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_new_packed, d_new_block_first, d_new_block_off, d_new_block_crc, d_status)
         _ok(self.ctx.lib.mscomp_amd_transcoder_transcode(self._h, p[0], plen, *p[1:6], cap, *p[6:]), "mscomp_amd_transcoder_transcode")
 
     def counts(self):
         """(new blocks carried, source blocks decoded, new blocks encoded) of the last transcode(); synchronizes the stream."""
-        out = (C.c_uint32 * 3)()
-        if self.ctx.lib.mscomp_amd_transcoder_counts(self._h, out) != 0:
-            raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_transcoder_counts")
-        return (int(out[0]), int(out[1]), int(out[2]))
+        return _three_counts(self, "mscomp_amd_transcoder_counts")
 
 
 def blocks_transcode(container, block_size, new_block_size, new_fmt=None, ctx=None, groups_max=None, n_blocks_new=None, new_cap=None):
@@ -1411,8 +1319,6 @@ def blocks_transcode(container, block_size, new_block_size, new_fmt=None, ctx=No
     (default: what the lengths need) and ``new_cap`` (default: the sum of the lengths) are the transcoder's bounds. Returns numpy arrays
     and lists (new_packed uint8, new_block_first uint64 of n + 1, new_block_off uint64, new_block_crc uint32 or None, statuses, counts)."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     fmt, packed, block_first, block_off, lengths, block_crc = container
     new_fmt = fmt if new_fmt is None else new_fmt
     lens = [int(x) for x in lengths]
@@ -1423,30 +1329,19 @@ def blocks_transcode(container, block_size, new_block_size, new_fmt=None, ctx=No
     nbn = sum((x + B2 - 1) // B2 for x in lens) if n_blocks_new is None else int(n_blocks_new)
     gmax = sum((x + G - 1) // G for x in lens) if groups_max is None else int(groups_max)
     room = int(sum(lens)) if new_cap is None else int(new_cap)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         tc = BlockTranscoder(ctx, fmt, B1, new_fmt, B2, n, nbt, nbn, gmax)
         packed, d_packed = _dev_packed(packed, dev)
         d_first, d_boff, d_len = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, nbt + 1, dev), _dev_u64(lens, 1, dev)
-        d_crc = d_ncrc = None
-        if block_crc is not None:
-            d_crc, d_ncrc = _dev_block_crc(block_crc, nbt, dev), torch.zeros(max(1, nbn), dtype=torch.int32, device=dev)
-        d_new = torch.zeros(room + 16, dtype=torch.uint8, device=dev)
-        d_nfirst = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        d_noff = torch.zeros(nbn + 1, dtype=torch.int64, device=dev)
+        d_crc = None if block_crc is None else _dev_block_crc(block_crc, nbt, dev)
+        d_new, d_nfirst, d_noff, d_ncrc = _new_container(dev, n, nbn, room, block_crc is not None)
         d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
         tc.transcode(d_packed, d_first, d_boff, d_len, d_new, d_nfirst, d_noff, d_st, d_block_crc=d_crc, d_new_block_crc=d_ncrc,
                      packed_len=len(packed), new_cap=room)
         counts = tc.counts()
-        nfirst = d_nfirst.cpu().numpy().view(np.uint64).copy()
-        nb = int(nfirst[n])
-        noff = d_noff.cpu().numpy().view(np.uint64)[: nb + 1].copy()
-        new_packed = d_new.cpu().numpy()[: min(int(noff[nb]), room)].copy()
-        ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nb].copy()
+        new_packed, nfirst, noff, ncrc = _fetch_container(d_new, d_nfirst, d_noff, d_ncrc, room)
         h_st = d_st.cpu().numpy()
         tc.close()
-    if own:
-        ctx.close()
     return new_packed, nfirst, noff, ncrc, [int(x) for x in h_st[:n]], counts
 
 
@@ -1454,12 +1349,9 @@ def res_crc_from_blocks(block_first, lengths, block_crc, block_size, ctx=None):
     """zlib's crc32 of every whole resource of a block container from its block checksums alone (mscomp_amd_res_crc_dev): no data is read.
     Returns (numpy uint32 array of n, list of status)."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     n = len(lengths)
     nbt = len(np.asarray(block_crc).reshape(-1))
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         d_first, d_len = _dev_u64(block_first, n + 1, dev), _dev_u64([int(x) for x in lengths], 1, dev)
         d_bcrc = _dev_block_crc(block_crc, nbt, dev)
         d_rcrc = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
@@ -1467,8 +1359,6 @@ def res_crc_from_blocks(block_first, lengths, block_crc, block_size, ctx=None):
         res_crc_dev(ctx, block_size, n, nbt, d_first, d_len, d_bcrc, d_rcrc, d_st)
         ctx.stream.synchronize()
         out, st = d_rcrc.cpu().numpy().view(np.uint32)[:n].copy(), [int(x) for x in d_st.cpu().numpy()[:n]]
-    if own:
-        ctx.close()
     return out, st
 
 
@@ -1482,10 +1372,7 @@ def res_crc_dev(ctx, block_size, n_res, n_blocks_table, d_block_first, d_res_len
 def plan_paths(plan):
     """mscomp_amd_debug_plan_paths (test hook; synchronizes the stream): what the last execution of a decompress or size plan of any kind put
     on the optional paths -- (units walked by segments, units on the all-CU byte stage, candidate slots with token scratch)."""
-    out = (C.c_uint32 * 3)()
-    if plan.ctx.lib.mscomp_amd_debug_plan_paths(plan._h, out) != 0:
-        raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_debug_plan_paths")
-    return (int(out[0]), int(out[1]), int(out[2]))
+    return _three_counts(plan, "mscomp_amd_debug_plan_paths")
 
 
 def _scratch_target(target):
@@ -1629,6 +1516,42 @@ def _dev_block_crc(block_crc, n, dev):
     return torch.from_numpy(h_crc.view(np.int32).copy()).to(dev)
 
 
+def _upload_containers(containers, dev, with_crc):
+    """Containers (packed, block_first, block_off, lengths, block_crc or None) on the device, as the source tuples BlockSplicer.splice takes
+    with every field stated -- checksums only ``with_crc`` --, and the resources and table rows of all of them: (sources, n_res, rows)."""
+    srcs, n_all, rows_all = [], 0, 0
+    for packed, first, off, lens, crc in containers:
+        lens = [int(x) for x in lens]
+        packed, d_packed = _dev_packed(packed, dev)
+        rows = max(0, len(np.asarray(off).reshape(-1)) - 1)
+        n_all += len(lens)
+        rows_all += rows
+        srcs.append((d_packed, _dev_u64(first, len(lens) + 1, dev), _dev_u64(off, rows + 1, dev), _dev_u64(lens, 1, dev),
+                     _dev_block_crc(crc, rows, dev) if with_crc else None, len(packed), len(lens), rows))
+    return srcs, n_all, rows_all
+
+
+def _new_container(dev, n_new, nbt, room, with_crc):
+    """The zeroed device arrays a call writes a new container into: (d_new_packed of room + 16 bytes, d_new_block_first of n_new + 1 entries --
+    None for n_new None: a write keeps the old one --, d_new_block_off of nbt + 1, d_new_block_crc of nbt, one at least, or None)."""
+    import torch
+    return (torch.zeros(room + 16, dtype=torch.uint8, device=dev),
+            None if n_new is None else torch.zeros(n_new + 1, dtype=torch.int64, device=dev),
+            torch.zeros(nbt + 1, dtype=torch.int64, device=dev),
+            torch.zeros(max(1, nbt), dtype=torch.int32, device=dev) if with_crc else None)
+
+
+def _fetch_container(d_new, d_nfirst, d_noff, d_ncrc, room):
+    """Those arrays on the host, cut to the nb blocks the new block_first counts (without one: to every row of the table): (new_packed,
+    new_first uint64 or None, new_block_off uint64 of nb + 1, new_block_crc uint32 of nb or None)."""
+    nfirst = None if d_nfirst is None else d_nfirst.cpu().numpy().view(np.uint64).copy()
+    nb = d_noff.numel() - 1 if nfirst is None else int(nfirst[-1])
+    noff = d_noff.cpu().numpy().view(np.uint64)[: nb + 1].copy()
+    new_packed = d_new.cpu().numpy()[: min(int(noff[nb]), room)].copy()
+    ncrc = None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[:nb].copy()
+    return new_packed, nfirst, noff, ncrc
+
+
 def _covering_blocks(reqs, lens, B):
     """Per (resource, offset, length) request the bytes it wants once clipped to its resource, and the blocks of ``B`` bytes that cover all
     of them, counted per request (unshared)."""
@@ -1647,11 +1570,8 @@ def decompressed_sizes(fmt, units, limits=None, ctx=None):
     no limit) is the capacity each is judged at. Returns numpy arrays (out_lens uint64, needs uint64, statuses int32): the status and
     length ms_decompress would return with *out_len = limit, and the smallest capacity that decodes (0 where the status is not OK)."""
     import torch
-    own = ctx is None
-    ctx = ctx or Context()
     n = len(units)
-    dev = torch.device("cuda", ctx.device)
-    with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+    with _call(ctx) as (ctx, dev):
         d_in, in_off, lens = _upload_units(units, dev)
         d_len = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
         d_need = torch.zeros(max(1, n), dtype=torch.int64, device=dev)
@@ -1661,8 +1581,6 @@ def decompressed_sizes(fmt, units, limits=None, ctx=None):
         ctx.stream.synchronize()
         out = (d_len.cpu().numpy().view(np.uint64)[:n].copy(), d_need.cpu().numpy().view(np.uint64)[:n].copy(), d_st.cpu().numpy()[:n].copy())
         plan.close()
-    if own:
-        ctx.close()
     return out
 
 
@@ -1670,17 +1588,14 @@ def decompress_units_auto(fmt, units, limits=None, ctx=None):
     """Decompress a list of compressed buffers whose sizes are not known: sizes them first (decompressed_sizes, at ``limits``), then
     decodes with capacity ``need`` for every unit, outputs back to back. Returns what decompress_units returns; a unit that is not
     MSCOMP_OK at its limit gets None and its status from the size pass."""
-    own = ctx is None
-    ctx = ctx or Context()
-    _, need, st = decompressed_sizes(fmt, units, limits, ctx=ctx)
-    ok = [i for i in range(len(units)) if st[i] == MSCOMP_OK]
-    res, status = [None] * len(units), [int(x) for x in st]
-    if ok:
-        got, gst = decompress_units(fmt, [units[i] for i in ok], [int(need[i]) for i in ok], ctx=ctx)
-        for i, g, s in zip(ok, got, gst):
-            res[i], status[i] = g, s
-    if own:
-        ctx.close()
+    with _call(ctx, enter=False) as (ctx, _):
+        _, need, st = decompressed_sizes(fmt, units, limits, ctx=ctx)
+        ok = [i for i in range(len(units)) if st[i] == MSCOMP_OK]
+        res, status = [None] * len(units), [int(x) for x in st]
+        if ok:
+            got, gst = decompress_units(fmt, [units[i] for i in ok], [int(need[i]) for i in ok], ctx=ctx)
+            for i, g, s in zip(ok, got, gst):
+                res[i], status[i] = g, s
     return res, status
 
 

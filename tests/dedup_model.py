@@ -5,7 +5,11 @@ header defines it. Dedup never encodes or decodes, so no oracle is called. Not c
 A source is what splice_model.model_splice takes: (packed, packed_len, block_first, block_off, lengths, block_crc or None, n_res,
 n_blocks_table).
 """
+import numpy as np
+
 import blocks_model as M
+import read_model as R
+from splice_model import ORDER2
 
 OK, ARG, DATA = M.OK, M.ARG, M.DATA
 M64 = M.M64
@@ -107,3 +111,26 @@ def same_ends(bufs, B):
             b[at + e - k: at + e] = bufs[0][at + e - k: at + e]
         out.append(bytes(b))
     return out
+
+
+# ---- the cases the CPU and the GPU tests share ----
+EMPTY = 0                                                      # row of R.RECIPES; the last one, 11, is empty too
+
+
+def raw_source(bufs, B, spare=2):
+    """bufs as a container whose blocks are all stored raw, with `spare` unused table rows, as a source tuple of splice_model"""
+    first, off = [0], [0]
+    for b in bufs:
+        for at in range(0, len(b), B):
+            off.append(off[-1] + min(B, len(b) - at))
+        first.append(len(off) - 1)
+    nbt = len(off) - 1 + spare
+    off += [off[-1]] * spare
+    return (b"".join(bufs), off[-1], np.array(first, dtype=np.uint64), np.array(off, dtype=np.uint64), [len(b) for b in bufs],
+            R.block_crcs(bufs, B, nbt), len(bufs), nbt)
+
+
+def expect_two_orders(n):
+    """rep of two containers that hold the same n buffers, the second in the order ORDER2, the last buffer empty like the first"""
+    rep = list(range(n - 1)) + [EMPTY]
+    return rep + [rep[k] for k in ORDER2]

@@ -7,6 +7,7 @@ A source is splice_model's: (packed, packed_len, block_first, block_off, lengths
 import numpy as np
 
 import blocks_model as M
+import read_model as R
 
 OK, ARG, DATA, BUF = M.OK, M.ARG, M.DATA, M.BUF
 M64 = M.M64
@@ -104,3 +105,40 @@ def model_splice_extents(sources, ext_first, ext, B, n_ext, n_blocks_table, new_
     crc += [0] * (n_blocks_table - nb)
     return {"packed": b"".join(pieces), "first": np.array(first, dtype=np.uint64), "off": np.array(off, dtype=np.uint64),
             "crc": np.array(crc, dtype=np.uint32) if with_crc else None, "new_len": new_len, "status": status, "reached": reached}
+
+
+# ---- the cases the CPU and the GPU tests share ----
+ONE, BP1, MIXED, ZEROS5, TEXT, MIXED5 = 1, 4, 5, 6, 7, 9        # rows of R.RECIPES: 1 byte, B + 1, 3 B + 17, 5 B zeros, 3 B + 17, 5 B mixed
+X3B, X3B5 = len(R.RECIPES), len(R.RECIPES) + 1                  # the two lengths R.RECIPES lacks: 3 B and 3 B + 5
+EXTRA = [{"id": "text_3b", "kind": "text", "seed": 31, "mult": 3, "add": 0}, {"id": "mixed_3b5", "kind": "mixed", "seed": 32, "mult": 3, "add": 5}]
+
+
+def buffers(B):
+    """the resources of source 0: R.RECIPES (lengths 0, 1, B - 1, B, B + 1, 3 B + 17, 5 B) and the two extra ones; source 1 holds them reversed"""
+    return R.buffers(B) + [M.build(r, B) for r in EXTRA]
+
+
+def in1(r):
+    return X3B5 - r                                            # resource r of source 0 is this resource of source 1
+
+
+def source(oracle, f, B, bufs):
+    total = sum(len(b) for b in bufs)
+    packed, first, off, st = M.model_compress(oracle, f, bufs, B, total, total)
+    assert not st.any()
+    nbt = len(bufs) + total // B
+    return (packed, len(packed), first, off, [len(b) for b in bufs], R.block_crcs(bufs, B, nbt), len(bufs), nbt)
+
+
+def healthy_lists(n):
+    """extent lists that every rule accepts, by name: each is a list of new resources"""
+    return {
+        "identity": [[(0, r, 0, None)] for r in range(n)],
+        "join": [[(0, X3B, 0, None), (1, in1(X3B5), 0, None)]],
+        "split": [[(0, X3B5, 0, 2)], [(0, X3B5, 2, None)]],
+        "cut_middle": [[(0, X3B, 0, 1), (0, X3B, 2, None)]],
+        "insert": [[(0, X3B5, 0, 1), (1, in1(MIXED5), 2, 1), (0, X3B5, 1, None)]],
+        "duplicate": [[(0, X3B5, 1, 1), (0, X3B5, 1, 1), (1, in1(X3B5), 3, None)]],
+        "empties": [[], [(0, X3B, 0, 0), (0, X3B, 3, None), (0, ONE, 0, None)], [(1, in1(X3B), 3, 0)], [(0, 0, 0, None)], []],
+        "short_last": [[(0, X3B, 1, 2), (0, BP1, 0, None)], [(0, ZEROS5, 0, 2)], [(0, BP1, 0, None), (0, X3B, 0, 0)]],
+    }

@@ -172,3 +172,14 @@ def model_res_crc(block_first, lengths, block_crc, B, n_blocks_table):
                 c ^= crc_mul(int(block_crc[f0 + k]), crc_xpow(8 * (L - min(L, (k + 1) * B))))
             out.append(c); st.append(OK)
     return np.array(out, dtype=np.uint32), st
+
+
+# ---- the cases the CPU and the GPU tests share ----
+SPARE = 16
+WANTS = (lambda L, B: 0, lambda L, B: 1, lambda L, B: max(0, L - 1), lambda L, B: L, lambda L, B: L + 1, lambda L, B: L // B * B,
+         lambda L, B: (L + B - 1) // B * B, lambda L, B: L + B, lambda L, B: L + 2 * B + 5)
+
+
+def mixes(lens, B):
+    """nine batches of wanted lengths: every resource meets every entry of WANTS once, shrinking and growing ones side by side"""
+    return [[WANTS[(r + v) % len(WANTS)](L, B) for r, L in enumerate(lens)] for v in range(len(WANTS))]

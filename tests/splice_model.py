@@ -7,6 +7,8 @@ A source is (packed, packed_len, block_first, block_off, lengths, block_crc or N
 import numpy as np
 
 import blocks_model as M
+import read_model as R
+import write_model as W
 
 OK, ARG, DATA, BUF = M.OK, M.ARG, M.DATA, M.BUF
 M64 = M.M64
@@ -67,3 +69,39 @@ def model_splice(sources, picks, B, n_blocks_table, new_cap, with_crc=True):
     crc += [0] * (n_blocks_table - nb)
     return {"packed": b"".join(pieces), "first": np.array(first, dtype=np.uint64), "off": np.array(off, dtype=np.uint64),
             "crc": np.array(crc, dtype=np.uint32) if with_crc else None, "new_len": new_len, "status": status, "reached": reached}
+
+
+# ---- the cases the CPU and the GPU tests share ----
+MIXED = 5                                                      # row of R.RECIPES: 3 B + 17, raw and compressed blocks
+ORDER2 = [7, 0, 9, 3, 5, 11, 1, 6, 10, 2, 8, 4]                  # the second container holds the same buffers in this order
+
+
+def source(oracle, f, B, order=None):
+    """(buffers, source tuple of splice_model) of R.RECIPES, in ``order``, as the container model compresses and checksums them"""
+    if order is None:
+        bufs, packed, first, off, nbt, crc = W.container(oracle, f, B)
+    else:
+        bufs = [R.buffers(B)[i] for i in order]
+        total = sum(len(b) for b in bufs)
+        packed, first, off, st = M.model_compress(oracle, f, bufs, B, total, total)
+        assert not st.any()
+        nbt = len(bufs) + total // B
+        crc = R.block_crcs(bufs, B, nbt)
+    return bufs, (packed, len(packed), first, off, [len(b) for b in bufs], crc, len(bufs), nbt)
+
+
+def pick_lists(n):
+    """identity; a permutation with a deletion and a duplicate; an interleaved merge of two containers"""
+    perm = [(0, r) for r in (9, 2, 7, 7, 0, 11, 5, 3, 10, 1, 8, 4)]          # without 6, with 7 twice
+    merge = [((k + 1) % 2, ORDER2.index(k) if (k + 1) % 2 else k) for k in range(n)] + [(1, 0), (0, MIXED)]
+    return [(0, r) for r in range(n)], perm, merge
+
+
+def expect(oracle, f, B, data, nbt):
+    """the consequence: (packed, first, off [nbt + 1], crc [nbt]) of the container model over ``data``"""
+    total = sum(len(b) for b in data)
+    packed, first, off, st = M.model_compress(oracle, f, data, B, total, total)
+    nb = int(first[-1])
+    assert not st.any() and nb <= nbt
+    off = np.concatenate([off[: nb + 1], np.full(max(0, nbt - nb), off[nb], dtype=np.uint64)])[: nbt + 1]
+    return packed, first, off, R.block_crcs(data, B, nbt)

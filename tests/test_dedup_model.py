@@ -11,9 +11,10 @@ import blocks_model as M
 import dedup_model as D
 import read_model as R
 import splice_model as S
-from test_splice_model import ORDER2, source
+from dedup_model import raw_source, expect_two_orders
+from splice_model import ORDER2, source
 
-EMPTY, EMPTY_AGAIN, MIXED = 0, 11, 5                            # rows of R.RECIPES
+EMPTY, EMPTY_AGAIN, MIXED = D.EMPTY, 11, 5                      # rows of R.RECIPES
 
 
 @pytest.fixture(scope="module")
@@ -24,29 +25,10 @@ def api():
     return api
 
 
-def raw_source(bufs, B, spare=2):
-    """bufs as a container whose blocks are all stored raw, with `spare` unused table rows, as a source tuple of splice_model"""
-    first, off = [0], [0]
-    for b in bufs:
-        for at in range(0, len(b), B):
-            off.append(off[-1] + min(B, len(b) - at))
-        first.append(len(off) - 1)
-    nbt = len(off) - 1 + spare
-    off += [off[-1]] * spare
-    return (b"".join(bufs), off[-1], np.array(first, dtype=np.uint64), np.array(off, dtype=np.uint64), [len(b) for b in bufs],
-            R.block_crcs(bufs, B, nbt), len(bufs), nbt)
-
-
 def spliced(sources, d, B, with_crc):
     """the picks of a dedup result, padding included, spliced by the splice model into a table with room for everything"""
     picks = [(d["pick"][2 * p], d["pick"][2 * p + 1]) for p in range(len(d["pick"]) // 2)]
     return S.model_splice(sources, picks, B, sum(int(s[7]) for s in sources), 1 << 40, with_crc=with_crc)
-
-
-def expect_two_orders(n):
-    """rep of two containers that hold the same n buffers, the second in the order ORDER2, the last buffer empty like the first"""
-    rep = list(range(n - 1)) + [EMPTY]
-    return rep + [rep[k] for k in ORDER2]
 
 
 @pytest.mark.parametrize("with_crc", (True, False))

@@ -10,8 +10,8 @@ import blocks_model as M
 import dedup_model as D
 import diff_model as F
 import read_model as R
-from test_dedup_model import raw_source
-from test_extents_model import source
+from dedup_model import raw_source
+from extents_model import source
 
 NO = F.NO_BASE
 

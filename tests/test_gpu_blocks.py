@@ -4,120 +4,10 @@ import numpy as np
 import pytest
 
 import blocks_model as M
+from blocks_rig import BlockRig, d64, fixture_bufs, FMTS, FILL
 
 pytestmark = pytest.mark.gpu
-FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
-GUARD, FILL = 64, 0xA5
 RANGES = [None, (0, 1), (1, 2), (2, 100), (1000, 5), (1, 0)]     # whole; one block; the middle; clipped at the end; beyond the end; an empty count
-
-
-def _d64(a, dev):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).copy()).to(dev)
-
-
-class Rig:
-    """one BlockContainer with device buffers that stay where they are: load() / set_*() rewrite their contents in place"""
-
-    def __init__(self, ctx, fmt, B, n, in_total_max, in_room=None, out_room=None):
-        import torch
-        import ms_compress_amd as m
-        self.ctx, self.fmt, self.B, self.n, self.itm = ctx, fmt, B, n, in_total_max
-        self.dev = dev = torch.device("cuda", ctx.device)
-        self.bk = m.BlockContainer(ctx, fmt, B, n, in_total_max)
-        self.nbmax = self.bk.n_blocks_max
-        assert self.nbmax == n + in_total_max // B
-        in_room = in_room or in_total_max
-        z64 = lambda k: torch.zeros(max(1, k), dtype=torch.int64, device=dev)
-        self.d_in = torch.zeros(in_room + 3 * n + 64, dtype=torch.uint8, device=dev)
-        self.d_off, self.d_len = z64(n), z64(n)
-        self.d_packed = torch.zeros(in_room + GUARD, dtype=torch.uint8, device=dev)
-        self.d_first, self.d_boff, self.d_cst = z64(n + 1), z64(self.nbmax + 1), torch.zeros(max(1, n), dtype=torch.int32, device=dev)
-        self.d_out = torch.zeros((out_room or in_room) + (GUARD + 16) * (n + 1), dtype=torch.uint8, device=dev)
-        self.d_ooff, self.d_ocap, self.d_olen, self.d_range = z64(n), z64(n), z64(n), z64(2 * n)
-        self.d_dst = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
-
-    def load(self, bufs):
-        """resources at odd offsets (every source alignment), the buffers refilled"""
-        import torch
-        assert len(bufs) == self.n
-        self.bufs, self.lens = bufs, [len(b) for b in bufs]
-        off, pos = [], 1
-        for b in bufs:
-            off.append(pos)
-            pos += len(b) + 3
-        blob = np.full(self.d_in.numel(), 0x5A, dtype=np.uint8)
-        for b, o in zip(bufs, off):
-            blob[o: o + len(b)] = np.frombuffer(b, dtype=np.uint8)
-        self.d_in.copy_(torch.from_numpy(blob))
-        self.d_off.copy_(_d64(off or [0], self.dev)); self.d_len.copy_(_d64(self.lens or [0], self.dev))
-
-    def compress(self, packed_cap=None):
-        self.d_packed.fill_(FILL); self.d_first.fill_(-1); self.d_boff.fill_(-1); self.d_cst.fill_(77)
-        self.cap = self.d_packed.numel() - GUARD if packed_cap is None else packed_cap
-        self.bk.compress(self.d_in, self.d_off, self.d_len, self.d_packed, self.d_first, self.d_boff, self.d_cst, packed_cap=self.cap)
-
-    def compressed(self):
-        self.ctx.stream.synchronize()
-        return (self.d_packed.cpu().numpy(), self.d_first.cpu().numpy().view(np.uint64), self.d_boff.cpu().numpy().view(np.uint64),
-                self.d_cst.cpu().numpy()[: self.n])
-
-    def check_compress(self, oracle, packed_cap=None):
-        """run, and compare everything with the model; returns the model's (packed, first, off, status)"""
-        self.compress(packed_cap)
-        packed, first, off, st = self.compressed()
-        mp, mf, mo, ms = M.model_compress(oracle, self.fmt, self.bufs, self.B, self.itm, self.cap)
-        assert (first == mf).all() and (off == mo).all(), "tables"
-        assert [int(x) for x in st] == [int(x) for x in ms], "statuses"
-        assert bytes(packed[: len(mp)]) == mp, "packed bytes"
-        assert (packed[len(mp):] == FILL).all(), "written behind the last block that fits / behind packed_cap"
-        return mp, mf, mo, ms
-
-    def set_out(self, caps):
-        self.caps = [int(c) for c in caps]
-        off, pos = [], GUARD + 5
-        for c in self.caps:
-            off.append(pos)
-            pos += c + GUARD
-        assert pos <= self.d_out.numel()
-        self.ooff = off
-        self.d_ooff.copy_(_d64(off or [0], self.dev)); self.d_ocap.copy_(_d64(self.caps or [0], self.dev))
-
-    def decompress(self, ranges=None, packed_len=None, first=None, boff=None, packed=None):
-        self.d_out.fill_(FILL); self.d_olen.fill_(-1); self.d_dst.fill_(77)
-        if ranges is not None:
-            self.d_range.copy_(_d64(np.array(ranges, dtype=np.uint64).reshape(-1), self.dev))
-        self.bk.decompress(self.d_packed if packed is None else packed, self.d_first if first is None else first, self.d_boff if boff is None else boff,
-                           self.d_len, self.d_out, self.d_ooff, self.d_ocap, self.d_olen, self.d_dst,
-                           d_range=None if ranges is None else self.d_range, packed_len=packed_len)
-        self.ctx.stream.synchronize()
-        return self.d_out.cpu().numpy(), self.d_olen.cpu().numpy().view(np.uint64)[: self.n], self.d_dst.cpu().numpy()[: self.n]
-
-    def check_decompress(self, oracle, model_args, ranges=None, **kw):
-        """model_args = (packed bytes, packed_len, first, off) the model decodes; kw: what the device call gets in their place"""
-        out, olen, st = self.decompress(ranges, packed_len=model_args[1], **kw)
-        mo, ms = M.model_decompress(oracle, self.fmt, model_args[0], model_args[1], model_args[2], model_args[3], self.lens, self.B, self.itm, self.caps, ranges)
-        assert [int(x) for x in st] == ms, ("statuses", [int(x) for x in st], ms)
-        keep = np.ones(len(out), dtype=bool)
-        for r in range(self.n):
-            o, c = self.ooff[r], self.caps[r]
-            keep[o: o + c] = False
-            if ms[r] == 0:
-                assert int(olen[r]) == len(mo[r]) and bytes(out[o: o + len(mo[r])]) == mo[r], ("bytes of resource", r)
-                assert (out[o + len(mo[r]): o + c] == FILL).all(), ("written behind the range of resource", r)
-            else:
-                assert int(olen[r]) == 0
-                if ms[r] in (M.ARG, M.BUF):
-                    assert (out[o: o + c] == FILL).all(), ("a rejected resource was written", r)
-        assert (out[keep] == FILL).all(), "written outside every capacity"
-        return mo, ms
-
-    def close(self):
-        self.bk.close()
-
-
-def _fixture_bufs(fixture, fmt, B):
-    return [M.build(r, B) for r in M.recipes_for(fixture, fmt, B)]
 
 
 @pytest.fixture(scope="module")
@@ -129,9 +19,9 @@ def fixture():
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_fixture_compress_and_ranged_decode(gpu_ctx, oracle, fixture, fmt, B):
     f = FMTS[fmt]
-    bufs = _fixture_bufs(fixture, f, B)
+    bufs = fixture_bufs(fixture, f, B)
     total = sum(len(b) for b in bufs)
-    rig = Rig(gpu_ctx, f, B, len(bufs), total)
+    rig = BlockRig(gpu_ctx, f, B, len(bufs), total)
     rig.load(bufs)
     mp, mf, mo, ms = rig.check_compress(oracle)
     assert not ms.any() and len(mp) == int(mo[-1])
@@ -155,10 +45,10 @@ def test_fixture_compress_and_ranged_decode(gpu_ctx, oracle, fixture, fmt, B):
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_short_packed_cap_and_rejects(gpu_ctx, oracle, fixture, fmt):
     f, B = FMTS[fmt], 4096
-    bufs = _fixture_bufs(fixture, f, B)
+    bufs = fixture_bufs(fixture, f, B)
     lens = [len(b) for b in bufs]
     total = sum(lens)
-    rig = Rig(gpu_ctx, f, B, len(bufs), total)
+    rig = BlockRig(gpu_ctx, f, B, len(bufs), total)
     rig.load(bufs)
     _, mf, mo, _ = rig.check_compress(oracle)
     for cap in (0, 1, int(mo[int(mf[6])]) + 5, int(mo[int(mf[9]) + 1]), int(mo[-1]) - 1):
@@ -167,7 +57,7 @@ def test_short_packed_cap_and_rejects(gpu_ctx, oracle, fixture, fmt):
     rig.close()
     # the resource that crosses in_total_max and every one behind it: rejected; the earlier ones: as before
     cut = sum(lens[:9]) - 1
-    rig = Rig(gpu_ctx, f, B, len(bufs), cut, in_room=total)
+    rig = BlockRig(gpu_ctx, f, B, len(bufs), cut, in_room=total)
     rig.load(bufs)
     mp, mf, mo, ms = rig.check_compress(oracle)
     assert [int(s) for s in ms] == [0] * 8 + [M.ARG] * (len(bufs) - 8)
@@ -181,10 +71,10 @@ def test_short_packed_cap_and_rejects(gpu_ctx, oracle, fixture, fmt):
 def test_damaged_tables_and_payload(gpu_ctx, oracle, fixture, fmt):
     import torch
     f, B = FMTS[fmt], 4096
-    bufs = _fixture_bufs(fixture, f, B)
+    bufs = fixture_bufs(fixture, f, B)
     lens = [len(b) for b in bufs]
     n, total = len(bufs), sum(lens)
-    rig = Rig(gpu_ctx, f, B, n, total)
+    rig = BlockRig(gpu_ctx, f, B, n, total)
     rig.load(bufs)
     mp, mf, mo, ms = rig.check_compress(oracle)
     rig.set_out(lens)
@@ -194,8 +84,8 @@ def test_damaged_tables_and_payload(gpu_ctx, oracle, fixture, fmt):
     comp = next(k for k in range(j, int(mf[target + 1])) if int(mo[k + 1] - mo[k]) < min(B, lens[target] - (k - j) * B))
 
     def tables(first=None, off=None):
-        return (mp, len(mp), mf if first is None else first, mo if off is None else off), dict(first=None if first is None else _d64(first, dev),
-                                                                                                boff=None if off is None else _d64(off, dev))
+        return (mp, len(mp), mf if first is None else first, mo if off is None else off), dict(first=None if first is None else d64(first, dev),
+                                                                                                boff=None if off is None else d64(off, dev))
     # a decreasing offset
     bad = mo.copy(); bad[j + 1] = bad[j] - 1
     a, kw = tables(off=bad)
@@ -248,9 +138,9 @@ def test_damaged_tables_and_payload(gpu_ctx, oracle, fixture, fmt):
 def test_repeats_and_tables_changed_in_place(gpu_ctx, oracle, fixture, fmt):
     """five executions of one object give the same; then the inputs and tables change behind the same pointers"""
     f, B = FMTS[fmt], 32768
-    bufs = _fixture_bufs(fixture, f, B)
+    bufs = fixture_bufs(fixture, f, B)
     n, total = len(bufs), sum(len(b) for b in bufs)
-    rig = Rig(gpu_ctx, f, B, n, total)
+    rig = BlockRig(gpu_ctx, f, B, n, total)
     rig.load(bufs)
     rig.set_out([len(b) for b in bufs])
     seen = set()
@@ -278,12 +168,12 @@ def test_compress_and_decompress_in_one_captured_graph(gpu_ctx, oracle, fixture,
     import torch
     import ms_compress_amd as m
     f, B = FMTS[fmt], 65536
-    base = _fixture_bufs(fixture, f, B)
+    base = fixture_bufs(fixture, f, B)
     n, total = len(base), sum(len(b) for b in base)
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        rig = Rig(ctx, f, B, n, total)
+        rig = BlockRig(ctx, f, B, n, total)
         rig.load(base)
         rig.set_out([len(b) for b in base])
         rig.d_packed.fill_(FILL); rig.d_out.fill_(FILL)
@@ -318,9 +208,9 @@ def test_tables_compose_with_layout_and_compact_dev(gpu_ctx, oracle, fixture):
     the blocks at 16-byte starts), all on the device"""
     import ms_compress_amd as m
     f, B = 3, 4096
-    bufs = _fixture_bufs(fixture, f, B)
+    bufs = fixture_bufs(fixture, f, B)
     total = sum(len(b) for b in bufs)
-    rig = Rig(gpu_ctx, f, B, len(bufs), total)
+    rig = BlockRig(gpu_ctx, f, B, len(bufs), total)
     rig.load(bufs)
     mp, mf, mo, ms = rig.check_compress(oracle)
     d_slen = rig.d_boff[1:] - rig.d_boff[:-1]
@@ -337,7 +227,7 @@ def test_tables_compose_with_layout_and_compact_dev(gpu_ctx, oracle, fixture):
 def test_host_conveniences(gpu_ctx, oracle, fixture):
     import ms_compress_amd as m
     f, B = 2, 4096
-    bufs = _fixture_bufs(fixture, f, B)
+    bufs = fixture_bufs(fixture, f, B)
     total = sum(len(b) for b in bufs)
     packed, first, off, st = m.blocks_compress(f, bufs, B, ctx=gpu_ctx)
     mp, mf, mo, ms = M.model_compress(oracle, f, bufs, B, total, total)

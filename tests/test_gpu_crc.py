@@ -1,13 +1,13 @@
 """GPU: CRC-32 of batches in HBM (CrcDevPlan) and the block container's checksums (BlockContainer.crc / .check) against zlib.crc32
 (tests/crc_model.py). Integer work: every value must be equal.
-The container tests stand on test_gpu_blocks.py's rig and recipes (Rig, _fixture_bufs, _d64, FMTS, FILL are imported from it, so that both files
-drive one container the same way): a change to those helpers changes these tests too."""
+The container tests stand on the rig and recipes of tests/blocks_rig.py that test_gpu_blocks.py drives too (BlockRig under CrcRig,
+fixture_bufs under crc_bufs): both files drive one container the same way."""
 import numpy as np
 import pytest
 
 import blocks_model as M
 import crc_model as K
-from test_gpu_blocks import FILL, FMTS, Rig, _d64, _fixture_bufs
+from blocks_rig import CrcRig, crc_bufs, d64, u32, FILL, FMTS
 
 pytestmark = pytest.mark.gpu
 SMALL = [0, 1, 2, 3, 4, 5, 7, 8, 15, 16, 17, 63, 64, 65, 255, 256, 4095, 4096, 4097]
@@ -21,10 +21,6 @@ def fixture():
 def _i32(n, dev, fill=0):
     import torch
     return torch.full((max(1, n),), fill, dtype=torch.int32, device=dev)
-
-
-def _u32(t, n):
-    return t.cpu().numpy().view(np.uint32)[:n]
 
 
 class PlanRig:
@@ -44,12 +40,12 @@ class PlanRig:
     def run(self, mem, offs, lens):
         import torch
         self.d_in[: len(mem)].copy_(torch.from_numpy(mem))
-        self.d_off.copy_(_d64(offs, self.dev)); self.d_len.copy_(_d64(lens, self.dev))
+        self.d_off.copy_(d64(offs, self.dev)); self.d_len.copy_(d64(lens, self.dev))
         self.d_crc.fill_(0x5A5A5A5A); self.d_st.fill_(77)
         self.plan.execute(self.d_in, self.d_off, self.d_len, self.d_crc, self.d_st)
         self.ctx.stream.synchronize()
         want, wst = K.units(mem, offs, lens, self.itm)
-        got, st = _u32(self.d_crc, self.n), self.d_st.cpu().numpy()[: self.n]
+        got, st = u32(self.d_crc, self.n), self.d_st.cpu().numpy()[: self.n]
         bad = np.nonzero(got != want)[0]
         assert len(bad) == 0, ("crc of units", [(int(i), int(offs[i]), int(lens[i]), hex(int(got[i])), hex(int(want[i]))) for i in bad[:8]])
         assert (st == wst).all()
@@ -121,7 +117,7 @@ def test_null_required_arrays_are_refused(gpu_ctx, fixture):
         assert lib.mscomp_amd_plan_execute_crc_dev(rig.plan._h, *q) == m.MSCOMP_ARG_ERROR, k
     assert lib.mscomp_amd_plan_execute_crc_dev(rig.plan._h, *p) == m.MSCOMP_OK
     rig.plan.close()
-    bufs = _bufs(fixture, 2, 4096)
+    bufs = crc_bufs(fixture, 2, 4096)
     r = CrcRig(gpu_ctx, 2, 4096, len(bufs), sum(len(b) for b in bufs))
     r.load(bufs)
     r.set_out([len(b) for b in bufs])
@@ -172,47 +168,11 @@ def test_plan_five_executions_changed_in_place(gpu_ctx):
     rig.plan.close()
 
 
-def _bufs(fixture, f, B):
-    return _fixture_bufs(fixture, f, B) + [np.random.RandomState(77).bytes(2 * B + 100)]   # (one incompressible resource added)
-
-
-class CrcRig(Rig):
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self.d_bcrc, self.d_rcrc, self.d_kst = _i32(self.nbmax, self.dev), _i32(self.n, self.dev), _i32(self.n, self.dev)
-
-    def crc(self):
-        self.d_bcrc.fill_(0x5A5A5A5A); self.d_rcrc.fill_(0x5A5A5A5A); self.d_kst.fill_(77)
-        self.bk.crc(self.d_in, self.d_off, self.d_len, self.d_bcrc, self.d_kst, d_res_crc=self.d_rcrc)
-
-    def check_crc(self):
-        self.crc()
-        self.ctx.stream.synchronize()
-        bc, rc, st = K.blocks(self.bufs, self.B, self.itm)
-        assert (_u32(self.d_bcrc, self.nbmax) == bc).all(), "block crcs"
-        assert (_u32(self.d_rcrc, self.n) == rc).all(), "resource crcs"
-        assert (self.d_kst.cpu().numpy()[: self.n] == st).all()
-        return bc, rc, st
-
-    def decode_and_check(self, ranges=None, packed=None):
-        """decompress, then check with the same tables; returns (statuses after decompress, statuses and lengths after check)"""
-        out, olen, st = self.decompress(ranges, packed_len=self.d_packed.numel() - 64, packed=packed)
-        self.bk.check(self.d_out, self.d_ooff, self.d_len, self.d_first, self.d_bcrc, self.d_olen, self.d_dst,
-                      d_range=None if ranges is None else self.d_range)
-        self.ctx.stream.synchronize()
-        st2, olen2 = self.d_dst.cpu().numpy()[: self.n], self.d_olen.cpu().numpy().view(np.uint64)[: self.n]
-        ms, ml = K.check(out, self.ooff, self.lens, self.d_first.cpu().numpy().view(np.uint64), _u32(self.d_bcrc, self.nbmax), st, olen,
-                         self.B, self.itm, ranges)
-        assert [int(x) for x in st2] == ms and [int(x) for x in olen2] == ml, ("check against the model", [int(x) for x in st2], ms)
-        assert (self.d_out.cpu().numpy() == out).all(), "check wrote to the output"
-        return [int(x) for x in st], [int(x) for x in st2], [int(x) for x in olen2]
-
-
 @pytest.mark.parametrize("B", (4096, 65536))
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_container_crc_roundtrip_and_ranges(gpu_ctx, oracle, fixture, fmt, B):
     f = FMTS[fmt]
-    bufs = _bufs(fixture, f, B)
+    bufs = crc_bufs(fixture, f, B)
     n, total = len(bufs), sum(len(b) for b in bufs)
     rig = CrcRig(gpu_ctx, f, B, n, total)
     rig.load(bufs)
@@ -234,7 +194,7 @@ def test_container_crc_roundtrip_and_ranges(gpu_ctx, oracle, fixture, fmt, B):
 
 def test_container_crc_rejects_as_compress_does(gpu_ctx, oracle, fixture):
     f, B = 2, 4096
-    bufs = _bufs(fixture, f, B)
+    bufs = crc_bufs(fixture, f, B)
     lens = [len(b) for b in bufs]
     cut = sum(lens[:9]) - 1
     rig = CrcRig(gpu_ctx, f, B, len(bufs), cut, in_room=sum(lens))
@@ -250,7 +210,7 @@ def test_container_crc_rejects_as_compress_does(gpu_ctx, oracle, fixture):
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_damage_that_the_decoders_accept(gpu_ctx, oracle, fixture, fmt):
     f, B = FMTS[fmt], 4096
-    bufs = _bufs(fixture, f, B)
+    bufs = crc_bufs(fixture, f, B)
     n, lens, total = len(bufs), [len(b) for b in bufs], sum(len(b) for b in bufs)
     mp, mf, mo, ms = M.model_compress(oracle, f, bufs, B, total, total)
     raw = K.find_raw_block(mf, mo, lens, B)
@@ -274,7 +234,7 @@ def test_damage_that_the_decoders_accept(gpu_ctx, oracle, fixture, fmt):
 def test_check_leaves_failed_resources_alone(gpu_ctx, oracle, fixture):
     """statuses alone: a resource that is not MSCOMP_OK on entry keeps its status and its length, whatever its bytes are"""
     f, B = 3, 4096
-    bufs = _bufs(fixture, f, B)
+    bufs = crc_bufs(fixture, f, B)
     n, lens = len(bufs), [len(b) for b in bufs]
     rig = CrcRig(gpu_ctx, f, B, n, sum(lens))
     rig.load(bufs)
@@ -302,7 +262,7 @@ def test_four_calls_in_one_captured_graph(gpu_ctx, oracle, fixture, fmt):
     import torch
     import ms_compress_amd as m
     f, B = FMTS[fmt], 65536
-    base = _bufs(fixture, f, B)
+    base = crc_bufs(fixture, f, B)
     n, total = len(base), sum(len(b) for b in base)
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
@@ -328,7 +288,7 @@ def test_four_calls_in_one_captured_graph(gpu_ctx, oracle, fixture, fmt):
             g.replay()
         s.synchronize()
         bc, rc, st = K.blocks(bufs, B, total)
-        assert (_u32(rig.d_bcrc, rig.nbmax) == bc).all() and (_u32(rig.d_rcrc, n) == rc).all(), k
+        assert (u32(rig.d_bcrc, rig.nbmax) == bc).all() and (u32(rig.d_rcrc, n) == rc).all(), k
         out, olen, dst = rig.d_out.cpu().numpy(), rig.d_olen.cpu().numpy(), rig.d_dst.cpu().numpy()
         for r, b in enumerate(bufs):
             assert dst[r] == 0 and int(olen[r]) == len(b) and bytes(out[rig.ooff[r]: rig.ooff[r] + len(b)]) == b, (k, r)
@@ -340,7 +300,7 @@ def test_four_calls_in_one_captured_graph(gpu_ctx, oracle, fixture, fmt):
 def test_python_conveniences(gpu_ctx, oracle, fixture):
     import ms_compress_amd as m
     f, B = 2, 4096
-    bufs = _bufs(fixture, f, B)
+    bufs = crc_bufs(fixture, f, B)
     bc, rc = m.blocks_crc(f, bufs, B, ctx=gpu_ctx)
     wb, wr, _ = K.blocks(bufs, B, sum(len(b) for b in bufs))
     assert (bc == wb[: len(bc)]).all() and len(bc) == sum((len(b) + B - 1) // B for b in bufs) and (rc == wr).all()

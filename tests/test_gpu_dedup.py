@@ -1,6 +1,6 @@
 """GPU: mscomp_amd_deduper_dedup against the model of tests/dedup_model.py -- every entry of the five outputs compared with sentinel-filled
 arrays that are longer than the call may write (so a write behind N, or behind 2 n_res_total in d_pick, fails) -- on the containers of
-tests/test_gpu_read.Rig; then the picks spliced on the GPU by a splicer made for n_res_total picks, held to the header's consequence and,
+tests/blocks_rig.Container; then the picks spliced on the GPU by a splicer made for n_res_total picks, held to the header's consequence and,
 where the sources are healthy, byte for byte to BlockContainer.compress + .crc of the unique data."""
 import numpy as np
 import pytest
@@ -9,67 +9,12 @@ import blocks_model as M
 import dedup_model as D
 import read_model as R
 import splice_model as S
-from test_gpu_read import Rig, FMTS, BLOCKS, MIXED
-from test_gpu_splice import Splices, Src
-from test_splice_model import ORDER2
+from blocks_rig import Container, Splices, check_dedup, dedup_outs, dedup_views, memo, DEDUP_EXACT, FMTS, BLOCKS, MIXED, SENT
+from dedup_model import EMPTY, expect_two_orders
+from splice_model import ORDER2
 
 pytestmark = pytest.mark.gpu
-SENT, SENT32, GUARD = 0x7777777777777777, 77, 5               # what the outputs hold before a call, and how far behind their ends they are watched
-EMPTY = 0                                                       # row of R.RECIPES; the last one, 11, is empty too
 M64 = M.M64
-
-
-class Outs:
-    """the five output arrays of a deduper made for n_max resources, sentinel-filled, with GUARD entries behind each"""
-
-    def __init__(self, dev, n_max):
-        import torch
-        self.n_max = n_max
-        self.rep, self.idx = (torch.full((n_max + GUARD,), SENT, dtype=torch.int64, device=dev) for _ in range(2))
-        self.pick = torch.full((2 * n_max + GUARD,), SENT, dtype=torch.int64, device=dev)
-        self.count = torch.full((4 + GUARD,), SENT, dtype=torch.int64, device=dev)
-        self.status = torch.full((n_max + GUARD,), SENT32, dtype=torch.int32, device=dev)
-
-    def tensors(self):
-        return self.rep, self.idx, self.pick, self.count, self.status
-
-    def reset(self):
-        for t in self.tensors():
-            t.fill_(SENT32 if t is self.status else SENT)
-
-    def pull(self):
-        u64 = lambda t: [int(x) for x in t.cpu().numpy().view(np.uint64)]
-        return {"rep": u64(self.rep), "new_index": u64(self.idx), "pick": u64(self.pick), "count": u64(self.count),
-                "status": [int(x) for x in self.status.cpu().numpy()]}
-
-    def untouched(self):
-        got = self.pull()
-        return all(set(got[k]) == {SENT} for k in ("rep", "new_index", "pick", "count")) and set(got["status"]) == {SENT32}
-
-
-def views(srcs, with_crc):
-    return [s.dev_tuple if with_crc else s.dev_tuple[:4] + (None,) + s.dev_tuple[5:] for s in srcs]
-
-
-def check_dedup(zs, srcs, with_crc=True, n_max=None, rows_max=None, deduper=None, outs=None):
-    """one call compared with the model, entry for entry; returns (model, Outs)"""
-    N, rows = sum(s.n_res for s in srcs), sum(s.nbt for s in srcs)
-    n_max = N if n_max is None else n_max
-    dd = deduper or zs.m.BlockDeduper(zs.ctx, zs.B, len(srcs), n_max, rows if rows_max is None else rows_max)
-    outs = outs or Outs(zs.dev, n_max)
-    outs.reset()
-    dd.dedup(views(srcs, with_crc), *outs.tensors())
-    zs.ctx.stream.synchronize()
-    if deduper is None:
-        dd.close()
-    mo = D.model_dedup([s.model() for s in srcs], zs.B, with_crc, n_res_total=n_max)
-    got = outs.pull()
-    for k in ("rep", "new_index"):
-        assert got[k] == mo[k] + [SENT] * (n_max - N + GUARD), (k, got[k], mo[k])
-    assert got["status"] == mo["status"] + [SENT32] * (n_max - N + GUARD), ("status", got["status"], mo["status"])
-    assert got["pick"] == mo["pick"] + [SENT] * GUARD, ("pick", got["pick"], mo["pick"])
-    assert got["count"] == mo["count"] + [SENT] * GUARD, ("count", got["count"], mo["count"])
-    return mo, outs
 
 
 def splice_picks(zs, srcs, mo, outs, with_crc=True, healthy=None):
@@ -80,9 +25,9 @@ def splice_picks(zs, srcs, mo, outs, with_crc=True, healthy=None):
     total = sum(int(models[s][4][r]) for s, r in picks[: mo["count"][0]])     # the unique resources' data bytes
     nbt = npk + total // zs.B if healthy else sum(s.nbt for s in srcs)          # (healthy: the table BlockContainer makes for that data)
     so = zs.outputs(npk, nbt)
-    d_new, d_first, d_off, d_crc, d_len, d_st = so
+    d_new, d_first, d_off, d_crc, d_len, d_st = so.tensors()
     sp = zs.m.BlockSplicer(zs.ctx, zs.B, len(srcs), npk, nbt)
-    sp.splice(views(srcs, with_crc), outs.pick, d_new, d_first, d_off, d_len, d_st, d_new_block_crc=d_crc if with_crc else None, new_cap=zs.room)
+    sp.splice(dedup_views(srcs, with_crc), outs["pick"], d_new, d_first, d_off, d_len, d_st, d_new_block_crc=d_crc if with_crc else None, new_cap=zs.room)
     got = zs.pull(so)
     sp.close()
     ms = S.model_splice(models, picks, zs.B, nbt, zs.room, with_crc=with_crc)
@@ -94,22 +39,9 @@ def splice_picks(zs, srcs, mo, outs, with_crc=True, healthy=None):
     return got
 
 
-def expect_two_orders(n):
-    rep = list(range(n - 1)) + [EMPTY]
-    return rep + [rep[k] for k in ORDER2]
-
-
 @pytest.fixture(scope="module")
 def rigs(gpu_ctx):
-    made = {}
-
-    def get(fmt, B):
-        if (fmt, B) not in made:
-            made[(fmt, B)] = Splices(gpu_ctx, FMTS[fmt], B)
-        return made[(fmt, B)]
-    yield get
-    for z in made.values():
-        z.close()
+    yield from memo(lambda fmt, B: Splices(gpu_ctx, FMTS[fmt], B))
 
 
 @pytest.mark.parametrize("B", BLOCKS)
@@ -182,8 +114,8 @@ def test_refusals(rigs, fmt, B):
     j = int(rig.first[MIXED])
     past = rig.off.copy(); past[j + 2:] = np.uint64(rig.plen + 1)          # rule 3: row 1 of MIXED ends beyond packed_len, and so does every row behind it
     back = rig.off.copy(); back[j + 2] = back[j + 1] - np.uint64(1)        # rule 3: a decreasing entry inside MIXED
-    for hurt, bad in ((Src(rig, first=falling), {3: M.ARG, 2: M.DATA}), (Src(rig, first=beyond), {n - 1: M.ARG}), (Src(rig, lens=odd), {MIXED: M.DATA}),
-                      (Src(rig, off=past), {r: M.DATA for r in range(MIXED, n) if lens[r]}), (Src(rig, off=back), {MIXED: M.DATA})):
+    for hurt, bad in ((rig.edited(first=falling), {3: M.ARG, 2: M.DATA}), (rig.edited(first=beyond), {n - 1: M.ARG}), (rig.edited(lens=odd), {MIXED: M.DATA}),
+                      (rig.edited(off=past), {r: M.DATA for r in range(MIXED, n) if lens[r]}), (rig.edited(off=back), {MIXED: M.DATA})):
         srcs = [hurt, zs.src[1]]
         mo, outs = check_dedup(zs, srcs)
         assert mo["status"] == [bad.get(r, 0) for r in range(n)] + [0] * n
@@ -201,7 +133,7 @@ def test_alignment(gpu_ctx, fmt, B):
     """one resource of raw and compressed rows alone in a container, and fifteen copies of it in another behind resources of 1 .. 16 bytes
     that put them at every other residue mod 16; then single stored bytes of a compressed row flipped"""
     x = R.buffers(B)[MIXED]
-    alone = Rig(gpu_ctx, FMTS[fmt], B, [x])
+    alone = Container.make(gpu_ctx, FMTS[fmt], B, [x])
     size, rs, bufs, at = alone.plen, np.random.RandomState(5), [], 0
     for k in range(1, 16):
         pad = (k - at) % 16 or 16
@@ -220,7 +152,7 @@ def test_alignment(gpu_ctx, fmt, B):
 
     def flipped(rig, base, where):
         hurt = bytearray(rig.packed); hurt[base + where] ^= 0x40
-        return Src(rig, packed=bytes(hurt))
+        return rig.edited(packed=bytes(hurt))
     for where, refuted in ((o0, 0), (o1 - 1, 0), ((o0 + o1) // 2, 15)):      # a first or last byte changes the key; a middle one only the bytes
         mo, outs = check_dedup(zs, [flipped(one, 0, where), zs.src[1]])
         assert [mo["rep"][2 + 2 * k] for k in range(15)] == [2] * 15 and mo["count"][3] == refuted
@@ -239,24 +171,24 @@ def test_bounds(rigs):
     assert mo["pick"][2 * (n - 1):] == [M64] * (2 * (n + 6))
     splice_picks(zs, zs.src, mo, outs, healthy=[r.bufs for r in zs.rig])
     # no resources at all
-    none = [Src(r, n_res=0, nbt=0) for r in zs.rig]
+    none = [r.edited(lens=[], nbt=0) for r in zs.rig]
     mo, outs = check_dedup(zs, none, n_max=3, rows_max=0)
     assert mo["count"] == [0, 0, 0, 0] and mo["pick"] == [M64] * 6
     mo, outs = check_dedup(zs, none, n_max=0, rows_max=0)
     assert mo["count"] == [0, 0, 0, 0] and mo["pick"] == []
     dd = m.BlockDeduper(zs.ctx, B, 2, 0, 0)
     cnt = torch.full((4,), SENT, dtype=torch.int64, device=zs.dev)
-    dd.dedup(views(none, True), None, None, None, cnt, None)       # N = 0: d_count alone is required
+    dd.dedup(dedup_views(none, True), None, None, None, cnt, None)       # N = 0: d_count alone is required
     zs.ctx.stream.synchronize()
     assert cnt.cpu().tolist() == [0, 0, 0, 0]
     dd.close()
     # refused on the host, nothing launched: too many resources, too many rows, each output missing in turn, a view without a table
-    outs = Outs(zs.dev, 2 * n)
+    outs = dedup_outs(zs.dev, 2 * n)
     full = outs.tensors()
     missing = [full[:k] + (None,) + full[k + 1:] for k in range(5)]
-    for n_max, rows_max, srcs, args in ((2 * n - 1, rows, views(zs.src, True), full), (2 * n, rows - 1, views(zs.src, True), full),
-                                        *[(2 * n, rows, views(zs.src, True), a) for a in missing],
-                                        (2 * n, rows, [zs.src[0].dev_tuple, zs.src[1].dev_tuple[:1] + (None,) + zs.src[1].dev_tuple[2:]], outs.tensors())):
+    for n_max, rows_max, srcs, args in ((2 * n - 1, rows, dedup_views(zs.src, True), full), (2 * n, rows - 1, dedup_views(zs.src, True), full),
+                                        *[(2 * n, rows, dedup_views(zs.src, True), a) for a in missing],
+                                        (2 * n, rows, [zs.src[0].view(), zs.src[1].view()[:1] + (None,) + zs.src[1].view()[2:]], outs.tensors())):
         dd = m.BlockDeduper(zs.ctx, B, 2, n_max, rows_max)
         with pytest.raises(m.MSCompError) as e:
             dd.dedup(srcs, *args)
@@ -280,7 +212,7 @@ def test_a_row_longer_than_a_block(gpu_ctx, B):
     assert stored_raw(zs.rig[0]) and stored_raw(zs.rig[1]) and 4 * B + 100 >= max(B, 16384)
 
     def one_row(rig):
-        return Src(rig, first=np.array([0, 1], dtype=np.uint64), off=np.array([0] + [5 * B] * rig.nbt, dtype=np.uint64), lens=[B], n_res=1)
+        return rig.edited(first=np.array([0, 1], dtype=np.uint64), off=np.array([0] + [5 * B] * rig.nbt, dtype=np.uint64), lens=[B])
     for srcs, rep, refuted in (([one_row(zs.rig[0]), one_row(zs.rig[1])], [0, 1], 1), ([one_row(zs.rig[0]), one_row(zs.rig[0])], [0, 0], 0)):
         for with_crc in (True, False):
             mo, outs = check_dedup(zs, srcs, with_crc)
@@ -300,10 +232,10 @@ def test_three_executions_are_identical(rigs, fmt):
     j = int(one.first[MIXED])
     where = (int(one.off[j + 1]) + int(one.off[j + 2])) // 2       # a middle byte of MIXED's compressed row: same key, other bytes
     hurt = bytearray(one.packed); hurt[where] ^= 0x01
-    srcs = [Src(one, packed=bytes(hurt)), zs.src[1]]
+    srcs = [one.edited(packed=bytes(hurt)), zs.src[1]]
     N, rows = 2 * one.n, sum(s.nbt for s in srcs)
     dd = zs.m.BlockDeduper(zs.ctx, B, 2, N + 2, rows)
-    outs = Outs(zs.dev, N + 2)
+    outs = dedup_outs(zs.dev, N + 2)
     seen = []
     for _ in range(3):
         mo, _ = check_dedup(zs, srcs, deduper=dd, outs=outs, n_max=N + 2)
@@ -326,30 +258,28 @@ def test_dedup_and_splice_in_one_captured_graph(fmt):
         zs = Splices(ctx, f, B)
         n, dev = zs.rig[0].n, zs.dev
         N, rows = 2 * n, sum(x.nbt for x in zs.src)
-        outs = Outs(dev, N)
+        outs = dedup_outs(dev, N)
         dd = m.BlockDeduper(ctx, B, 2, N, rows)
         unique = sum(zs.rig[0].lens)
         nbt = N + unique // B
         sp = m.BlockSplicer(ctx, B, 2, N, nbt)
         so = zs.outputs(N, nbt)
-        d_new, d_first, d_off, d_crc, d_len, d_st = so
+        d_new, d_first, d_off, d_crc, d_len, d_st = so.tensors()
     s.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=s):
-        dd.dedup(views(zs.src, True), *outs.tensors())
-        sp.splice(views(zs.src, True), outs.pick, d_new, d_first, d_off, d_len, d_st, d_new_block_crc=d_crc, new_cap=zs.room)
+        dd.dedup(dedup_views(zs.src, True), *outs.tensors())
+        sp.splice(dedup_views(zs.src, True), outs["pick"], d_new, d_first, d_off, d_len, d_st, d_new_block_crc=d_crc, new_cap=zs.room)
     mo = D.model_dedup([x.model() for x in zs.src], B, True, n_res_total=N)
     picks = [(mo["pick"][2 * p], mo["pick"][2 * p + 1]) for p in range(N)]
     ms = S.model_splice([x.model() for x in zs.src], picks, B, nbt, zs.room)
     for k in range(2):
         with torch.cuda.stream(s):
             outs.reset()
-            d_new.fill_(0xA5); d_first.fill_(-1); d_off.fill_(-1); d_crc.fill_(0x55555555); d_len.fill_(-1); d_st.fill_(77)
+            so.fill()
             g.replay()
         s.synchronize()
-        got = outs.pull()
-        assert got["rep"] == mo["rep"] + [SENT] * GUARD and got["new_index"] == mo["new_index"] + [SENT] * GUARD, k
-        assert got["pick"] == mo["pick"] + [SENT] * GUARD and got["count"] == mo["count"] + [SENT] * GUARD and got["status"] == mo["status"] + [SENT32] * GUARD, k
+        outs.against(mo, exact=DEDUP_EXACT)
         new = zs.pull(so)
         zs.compare(new, ms, N, nbt)
         with torch.cuda.stream(s):

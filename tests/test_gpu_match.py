@@ -2,7 +2,7 @@
 arrays that are longer than the call may write (so a write behind the extents in use, or behind the last resource, fails) --, then the two
 splices the header's consequence speaks of run on the GPU from the call's own device arrays: the delta lists over {new}, the patch lists
 over {stores..., delta}; the rebuilt container is held to the extents model and, wherever every resource of new is accepted, byte for byte
-to the new container. The containers are made by the GPU's blocks_compress / blocks_crc; the helpers are those of tests/test_gpu_diff.py."""
+to the new container. The containers are made by the GPU's blocks_compress / blocks_crc; the helpers are those of tests/blocks_rig.py."""
 import numpy as np
 import pytest
 
@@ -11,7 +11,7 @@ import dedup_model as D
 import diff_model as F
 import match_model as T
 import read_model as R
-from test_gpu_diff import FMTS, GUARD, POISONS, SENT, SENT32, Con, Spliced, d64, rand, recipe, soft
+from blocks_rig import Container, ListOuts, Spliced, d64, memo, rand, recipe, soft, FMTS, POISONS, SENT
 
 pytestmark = pytest.mark.gpu
 FOUND, SHARED, FRESH = T.FOUND, T.SHARED, T.FRESH
@@ -19,75 +19,34 @@ SHAPES = (("lznt1", 4096), ("xpress", 4096), ("xpress_huff", 4096), ("xpress", 6
 TILE = 1024
 
 
-class Side:
-    """a container as one view of a call: with or without its checksums, with the table rows and the packed length the view states"""
-
-    def __init__(self, con, crc=True, nbt=None, plen=None):
-        self.con, self.crc, self.nbt, self.plen = con, crc, con.nbt if nbt is None else nbt, con.cap if plen is None else plen
-
-    def view(self):
-        c = self.con
-        return (c.d_packed, c.d_first, c.d_off, c.d_len, c.d_crc if self.crc else None, self.plen, c.n, self.nbt)
-
-    def model(self):
-        c = self.con
-        packed = (bytes(c.packed) + bytes(c.cap - c.plen))[: self.plen]
-        return (packed, self.plen, c.first, c.off, c.lens, c.crc if self.crc else None, c.n, self.nbt)
+EXACT, PREFIXES = ("delta_first", "patch_first", "cls", "count"), ("delta_ext", "patch_ext")
 
 
-def side(x):
-    return x if isinstance(x, Side) else Side(x)
+def Side(con, crc=True, nbt=None, plen=None):
+    """a container as one view of a call states it: with or without its checksums, with other table rows or another packed length"""
+    return con.edited(with_crc=crc, nbt=nbt, plen=plen)
 
 
-class Outs:
-    """the seven output arrays of a match of n_new resources of new among n_all, within `room` new blocks, sentinel-filled, with GUARD entries
-    behind each"""
-
-    def __init__(self, dev, n_new, n_all, room):
-        import torch
-        full = lambda k: torch.full((k + GUARD,), SENT, dtype=torch.int64, device=dev)
-        self.n_new, self.n_all, self.room = n_new, n_all, room
-        self.dfirst, self.dext, self.pfirst, self.pext, self.cls, self.count = full(n_new + 1), full(4 * room), full(n_new + 1), full(4 * room), full(3 * n_new), full(6)
-        self.status = torch.full((n_all + GUARD,), SENT32, dtype=torch.int32, device=dev)
-
-    def tensors(self):
-        return self.dfirst, self.dext, self.pfirst, self.pext, self.cls, self.count, self.status
-
-    def reset(self):
-        for t in self.tensors():
-            t.fill_(SENT32 if t is self.status else SENT)
-
-    def pull(self):
-        u64 = lambda t: [int(x) for x in t.cpu().numpy().view(np.uint64)]
-        return {"delta_first": u64(self.dfirst), "delta_ext": u64(self.dext), "patch_first": u64(self.pfirst), "patch_ext": u64(self.pext),
-                "cls": u64(self.cls), "count": u64(self.count), "status": [int(x) for x in self.status.cpu().numpy()]}
-
-    def untouched(self):
-        got = self.pull()
-        return all(set(v) == {SENT32 if k == "status" else SENT} for k, v in got.items())
+def Outs(dev, n_new, n_all, room):
+    """the seven output arrays of a match of n_new resources of new among n_all, within `room` new blocks, sentinel-filled and guarded"""
+    outs = ListOuts(dev, {"delta_first": n_new + 1, "delta_ext": 4 * room, "patch_first": n_new + 1, "patch_ext": 4 * room, "cls": 3 * n_new, "count": 6}, n_all)
+    outs.room = room
+    return outs
 
 
 def against_model(got, mo):
-    flat = lambda ext: [int(x) for e in ext for x in e]
-    for k in ("delta_first", "patch_first", "cls", "count"):
-        assert got[k] == mo[k] + [SENT] * GUARD, (k, got[k], mo[k])
-    for k in ("delta_ext", "patch_ext"):
-        want = flat(mo[k])
-        assert got[k][: len(want)] == want, (k, got[k][: len(want)], mo[k])
-        assert set(got[k][len(want):]) <= {SENT}, (k, "written behind the extents in use")
-    assert got["status"] == mo["status"] + [SENT32] * GUARD, ("status", got["status"], mo["status"])
+    ListOuts.compare(got, mo, exact=EXACT, prefixes=PREFIXES)
 
 
 def check_match(stores, new, total=None, room=None, dd=None, outs=None):
-    """one call compared with the model, array for array; returns (model, Outs). stores / new: Con or Side"""
+    """one call compared with the model, array for array; returns (model, Outs)"""
     import ms_compress_amd as m
-    stores, new = [side(s) for s in stores], side(new)
-    ctx, B, dev = new.con.ctx, new.con.B, new.con.dev
+    ctx, B, dev = new.ctx, new.B, new.dev
     room = new.nbt if room is None else room
     total = sum(s.nbt for s in stores) + max(room, new.nbt) if total is None else total
-    n_all = sum(s.con.n for s in stores) + new.con.n
+    n_all = sum(s.n for s in stores) + new.n
     deduper = dd or m.BlockDeduper.for_match(ctx, B, len(stores), n_all, total, room)
-    outs = outs or Outs(dev, new.con.n, n_all, room)
+    outs = outs or Outs(dev, new.n, n_all, room)
     outs.reset()
     deduper.match([s.view() for s in stores], new.view(), *outs.tensors())
     ctx.stream.synchronize()
@@ -101,17 +60,17 @@ def check_match(stores, new, total=None, room=None, dd=None, outs=None):
 def rebuild(stores, new, mo, outs, same=None):
     """the header's consequence on the GPU, from the device arrays the match left: the delta container out of {new}, then stores + delta"""
     import ms_compress_amd as m
-    stores, new = [side(s) for s in stores], side(new)
-    ctx, B, n, room = new.con.ctx, new.con.B, new.con.n, outs.room
-    with_crc = all(s.crc for s in stores + [new])
+    stores = list(stores)
+    ctx, B, n, room = new.ctx, new.B, new.n, outs.room
+    with_crc = all(s.with_crc for s in stores + [new])
     models = [s.model() for s in stores]
     md, mb = T.model_delta_and_patch(models, new.model(), mo, B, room, with_crc)
-    delta = Spliced(new.con.dev, n, room, len(md["packed"]) + 32, with_crc)
-    built = Spliced(new.con.dev, n, room, len(mb["packed"]) + 32, with_crc)
-    cut = lambda s: s.view() if with_crc else s.view()[:4] + (None,) + s.view()[5:]
+    delta = Spliced(new.dev, n, room, len(md["packed"]) + 32, with_crc)
+    built = Spliced(new.dev, n, room, len(mb["packed"]) + 32, with_crc)
+    cut = lambda s: s.view(crc=with_crc)
     s1, s2 = m.BlockSplicer.for_extents(ctx, B, 1, n, room, room), m.BlockSplicer.for_extents(ctx, B, len(stores) + 1, n, room, room)
-    delta.run(s1, [cut(new)], outs.dfirst, outs.dext)
-    built.run(s2, [cut(s) for s in stores] + [delta.view()], outs.pfirst, outs.pext)
+    delta.run(s1, [cut(new)], outs["delta_first"], outs["delta_ext"])
+    built.run(s2, [cut(s) for s in stores] + [delta.view()], outs["patch_first"], outs["patch_ext"])
     ctx.stream.synchronize()
     s1.close(); s2.close()
     delta.against(md, "delta")
@@ -120,45 +79,38 @@ def rebuild(stores, new, mo, outs, same=None):
     T.holds_consequence(models, new.model(), mo, B, room, with_crc)
     same = all(s == 0 for s in mo["status"][mo["n_store"]:]) if same is None else same
     if same:
-        c = new.con
         got = built.as_built()
-        got["packed"] = got["packed"][: c.plen]
-        F.same_container(got, c.model(with_crc)[:1] + (c.plen,) + c.model(with_crc)[2:], with_crc)
-        assert int(got["off"][int(got["first"][c.n])]) == c.plen
+        got["packed"] = got["packed"][: new.plen]
+        F.same_container(got, new.model(with_crc, plen=new.plen)[:1] + (new.plen,) + new.model(with_crc)[2:], with_crc)
+        assert int(got["off"][int(got["first"][new.n])]) == new.plen
     return md, mb
 
 
 @pytest.fixture(scope="module")
 def cons(gpu_ctx):
     """containers by name, made once"""
-    made = {}
-
-    def get(key, make):
-        if key not in made:
-            made[key] = make()
-        return made[key]
-    return get
+    yield from memo()
 
 
 def raw_con(ctx, bufs, B=4096, f=3, crc=None):
     """random buffers as a container: every block is stored raw, the stored bytes are the data"""
-    con = Con.make(ctx, f, B, bufs)
+    con = Container.via_host(ctx, f, B, bufs)
     assert bytes(con.packed) == b"".join(bufs)
-    return con if crc is None else Con(ctx, f, B, con.packed, con.first, con.off, con.lens, np.full(con.nbt, crc, dtype=np.uint32))
+    return con if crc is None else con.edited(crc=np.full(con.nbt, crc, dtype=np.uint32))
 
 
 @pytest.mark.parametrize("fmt,B", SHAPES)
 def test_identity_and_moves(gpu_ctx, cons, fmt, B):
     """resources of 0, 1, B - 1, B, B + 1, 3 B + 17 and 5 B bytes, raw and compressed blocks side by side"""
     bufs = R.buffers(B)
-    store = cons((fmt, B, "recipes"), lambda: Con.make(gpu_ctx, FMTS[fmt], B, bufs))
+    store = cons((fmt, B, "recipes"), lambda: Container.via_host(gpu_ctx, FMTS[fmt], B, bufs))
     rows = sum(store.blocks(r) for r in range(store.n))
     for crc in (True, False):
         mo, outs = check_match([Side(store, crc)], Side(store, crc))              # identity: all found, D has no rows
         assert mo["count"][:5] == [rows, 0, 0, rows, 0] and mo["delta_ext"] == [] and mo["status"] == [0] * (2 * store.n)
         rebuild([Side(store, crc)], Side(store, crc), mo, outs)
     moved = [bufs[k] for k in (9, 0, 5, 3, 11, 1)] + [rand(31, B) + bufs[7], bufs[8][: 2 * B] + bufs[4], bufs[7][2 * B: 3 * B] + bufs[2]]
-    new = cons((fmt, B, "moved"), lambda: Con.make(gpu_ctx, FMTS[fmt], B, moved))
+    new = cons((fmt, B, "moved"), lambda: Container.via_host(gpu_ctx, FMTS[fmt], B, moved))
     for crc in (True, False):
         mo, outs = check_match([Side(store, crc)], Side(new, crc))
         assert mo["count"][1:3] == [0, 1] and mo["count"][5] == 0
@@ -184,7 +136,7 @@ def test_sharing(gpu_ctx):
     mo, outs = check_match([raw_con(gpu_ctx, [y])], thrice)
     assert mo["classes"] == [[FRESH, SHARED], [FRESH, SHARED]] and mo["patch_ext"] == [(1, 0, 0, 1), (1, 0, 0, 1), (1, 1, 0, 1), (1, 0, 0, 1)]
     rebuild([raw_con(gpu_ctx, [y])], thrice, mo, outs)
-    zeros = Con.make(gpu_ctx, 2, B, [bytes(5 * B)])                                  # the smallest equal row always wins: one extent per block
+    zeros = Container.via_host(gpu_ctx, 2, B, [bytes(5 * B)])                                  # the smallest equal row always wins: one extent per block
     mo, outs = check_match([], zeros)
     assert mo["patch_ext"] == [(0, 0, 0, 1)] * 5 and mo["count"][:3] == [0, 4, 1]
     rebuild([], zeros, mo, outs)
@@ -237,7 +189,7 @@ def test_refuted_chain(gpu_ctx, crc):
 def test_damaged_tables(gpu_ctx, cons):
     B, fmt = 4096, "xpress"
     bufs = [rand(41, 2 * B), rand(42, 3 * B + 17), rand(43, B), b"", soft(44, B + 1)]
-    good = cons((fmt, B, "damage"), lambda: Con.make(gpu_ctx, FMTS[fmt], B, bufs))
+    good = cons((fmt, B, "damage"), lambda: Container.via_host(gpu_ctx, FMTS[fmt], B, bufs))
     n, lens = good.n, good.lens
     falling = good.first.copy(); falling[1] = falling[2] + np.uint64(1)               # resource 1 by rule 1; resource 0 gets rows too many: rule 2
     odd = list(lens); odd[1] += B                                                    # rule 2
@@ -276,14 +228,14 @@ def test_tiles(gpu_ctx):
     B, f = 4096, FMTS["lznt1"]
     rows = 2 * TILE + 3
     s, fr = soft(1, rows * B), soft(2, 10 * B)
-    store = Con.make(gpu_ctx, f, B, [s])
-    wide = Con.make(gpu_ctx, f, B, [fr[:B] + s[: (rows - 1) * B]])
+    store = Container.via_host(gpu_ctx, f, B, [s])
+    wide = Container.via_host(gpu_ctx, f, B, [fr[:B] + s[: (rows - 1) * B]])
     mo, outs = check_match([store], wide)
     assert mo["patch_ext"] == [(1, 0, 0, 1), (0, 0, 0, rows - 1)] and mo["delta_ext"] == [(0, 0, 0, 1)]
     rebuild([store], wide, mo, outs)
     tail = rows - (TILE + 6)
     data = fr + s[10 * B: TILE * B] + fr[2 * B: 8 * B] + s[100 * B: (100 + tail) * B]
-    edge = Con.make(gpu_ctx, f, B, [data])
+    edge = Container.via_host(gpu_ctx, f, B, [data])
     assert edge.blocks(0) == rows
     mo, outs = check_match([store], edge)
     assert mo["patch_ext"] == [(1, 0, 0, 10), (0, 0, 10, TILE - 10), (1, 0, 2, 6), (0, 0, 100, tail)] and mo["count"][:3] == [rows - 16, 6, 10]
@@ -298,7 +250,7 @@ def test_degenerate(gpu_ctx, cons):
     import ms_compress_amd as m
     B = 4096
     some = raw_con(gpu_ctx, [rand(61, B + 5), rand(62, 3 * B)])
-    none = Con(gpu_ctx, 3, B, b"", [0], [0], [], [])
+    none = Container.from_host(gpu_ctx, 3, B, b"", [0], [0], [], [])
     mo, outs = check_match([some], none)                                            # an empty new container
     assert mo["count"] == [0] * 6 and mo["delta_first"] == [0] and mo["patch_first"] == [0]
     mo, outs = check_match([none, none, none], some)                                # stores without a resource
@@ -324,9 +276,9 @@ def busy_case(gpu_ctx, cons, fmt, B=4096):
     bufs = R.buffers(B)
     x1 = rand(21, B)
     x2, x3 = D.crc_twin(x1, 1000), D.crc_twin(x1, 2000)                             # equal CRC words, equal ends, other bytes: one key tuple
-    s0 = cons((fmt, B, "busy0"), lambda: Con.make(gpu_ctx, FMTS[fmt], B, [bufs[5], bufs[7], x1 + x2]))
-    s1 = cons((fmt, B, "busy1"), lambda: Con.make(gpu_ctx, FMTS[fmt], B, [bufs[9], bufs[4], bufs[8]]))
-    new = cons((fmt, B, "busy2"), lambda: Con.make(gpu_ctx, FMTS[fmt], B, [rand(71, B) + bufs[7], bufs[9][B: 3 * B] + rand(72, 2 * B) + bufs[4], x2 + x3 + x3,
+    s0 = cons((fmt, B, "busy0"), lambda: Container.via_host(gpu_ctx, FMTS[fmt], B, [bufs[5], bufs[7], x1 + x2]))
+    s1 = cons((fmt, B, "busy1"), lambda: Container.via_host(gpu_ctx, FMTS[fmt], B, [bufs[9], bufs[4], bufs[8]]))
+    new = cons((fmt, B, "busy2"), lambda: Container.via_host(gpu_ctx, FMTS[fmt], B, [rand(71, B) + bufs[7], bufs[9][B: 3 * B] + rand(72, 2 * B) + bufs[4], x2 + x3 + x3,
                                                                           b"", bufs[8], rand(72, 2 * B)]))
     odd = list(s1.lens); odd[2] += B
     cut = list(new.lens); cut[3] = 1
@@ -338,9 +290,9 @@ def test_five_executions_are_identical(gpu_ctx, cons, fmt):
     """the first execution launches, the later ones replay the object's graph; a changed field of a view captures again"""
     import ms_compress_amd as m
     stores, new = busy_case(gpu_ctx, cons, fmt)
-    room, total, n_all = new.nbt + 3, stores[0].nbt + stores[1].nbt + new.nbt + 5, stores[0].con.n + stores[1].con.n + new.con.n + 2
-    dd = m.BlockDeduper.for_match(gpu_ctx, new.con.B, 2, n_all, total, room)
-    outs = Outs(new.con.dev, new.con.n, n_all - 2, room)
+    room, total, n_all = new.nbt + 3, stores[0].nbt + stores[1].nbt + new.nbt + 5, stores[0].n + stores[1].n + new.n + 2
+    dd = m.BlockDeduper.for_match(gpu_ctx, new.B, 2, n_all, total, room)
+    outs = Outs(new.dev, new.n, n_all - 2, room)
     seen = []
     for _ in range(5):
         mo, _ = check_match(stores, new, total=total, room=room, dd=dd, outs=outs)
@@ -349,7 +301,7 @@ def test_five_executions_are_identical(gpu_ctx, cons, fmt):
     assert mo["count"][0] == 9 and mo["count"][1] == 3 and mo["count"][2] == 4 + 4           # bufs[8] fell with its store resource: its four blocks are fresh
     assert all(s == seen[0] for s in seen)
     rebuild(stores, new, mo, outs)
-    short = Side(new.con, plen=new.plen - 1)                                        # one field of one view changed: captured again, and answered for what it says
+    short = Side(new, plen=new.cap - 1)                                        # one field of one view changed: captured again, and answered for what it says
     mo2, _ = check_match(stores, short, total=total, room=room, dd=dd, outs=outs)
     assert mo2["status"][-1] == M.DATA and mo2["status"][:-1] == mo["status"][:-1]
     mo3, _ = check_match(stores, new, total=total, room=room, dd=dd, outs=outs)
@@ -362,9 +314,9 @@ def test_scratch_contract(gpu_ctx, cons, fmt):
     """the scheme of tests/test_gpu_scratch.py: what an execution reads from the scratch it has written itself, and no pass touches the slack"""
     import ms_compress_amd as m
     stores, new = busy_case(gpu_ctx, cons, fmt)
-    room, total, n_all = new.nbt + 3, stores[0].nbt + stores[1].nbt + new.nbt + 5, stores[0].con.n + stores[1].con.n + new.con.n
-    dd = m.BlockDeduper.for_match(gpu_ctx, new.con.B, 2, n_all, total, room)
-    outs = Outs(new.con.dev, new.con.n, n_all, room)
+    room, total, n_all = new.nbt + 3, stores[0].nbt + stores[1].nbt + new.nbt + 5, stores[0].n + stores[1].n + new.n
+    dd = m.BlockDeduper.for_match(gpu_ctx, new.B, 2, n_all, total, room)
+    outs = Outs(new.dev, new.n, n_all, room)
     check_match(stores, new, total=total, room=room, dd=dd, outs=outs)
     first = outs.pull()
     rep = m.api.scratch_report(dd, 0)
@@ -391,8 +343,8 @@ def test_wrong_kinds_and_nulls(gpu_ctx, cons):
     spare = lambda k: torch.full((k,), SENT, dtype=torch.int64, device=dev)
     kinds = {"dedup": m.BlockDeduper(gpu_ctx, B, 2, 2 * n, 2 * good.nbt), "diff": m.BlockDeduper.for_diff(gpu_ctx, B, n, good.nbt),
              "match": m.BlockDeduper.for_match(gpu_ctx, B, 1, 2 * n, 2 * good.nbt, good.nbt)}
-    calls = {"dedup": lambda dd: dd.dedup([v] * dd.n_src, spare(2 * n), spare(2 * n), spare(4 * n), outs.count, outs.status),
-             "diff": lambda dd: dd.diff(v, v, pair, outs.dfirst, outs.dext, outs.pfirst, outs.pext, spare(n), outs.count, outs.status),
+    calls = {"dedup": lambda dd: dd.dedup([v] * dd.n_src, spare(2 * n), spare(2 * n), spare(4 * n), outs["count"], outs.status),
+             "diff": lambda dd: dd.diff(v, v, pair, outs["delta_first"], outs["delta_ext"], outs["patch_first"], outs["patch_ext"], spare(n), outs["count"], outs.status),
              "match": lambda dd: dd.match([v] * dd.n_src, v, *full)}
     for made, dd in kinds.items():
         for call, run in calls.items():
@@ -442,10 +394,10 @@ def test_match_and_both_splices_in_one_captured_graph(fmt):
         b = [recipe("mixed", 31, 6, 33, B), recipe("text", 33, 2, 0, B)]
         fresh = rand(91, B)
         shape = lambda src: [src[1] + src[0][: 2 * B], fresh + src[0][2 * B: 4 * B] + fresh]     # the same lengths for either set
-        sets = [(Con.make(ctx, f, B, src), Con.make(ctx, f, B, shape(src))) for src in (a, b)]
+        sets = [(Container.via_host(ctx, f, B, src), Container.via_host(ctx, f, B, shape(src))) for src in (a, b)]
         assert sets[0][0].lens == sets[1][0].lens and sets[0][1].lens == sets[1][1].lens
         cap = max(c.plen for pair in sets for c in pair) + 100
-        slots = [Con(ctx, f, B, c.packed, c.first, c.off, c.lens, c.crc, cap=cap) for c in sets[0]]
+        slots = [Container.from_host(ctx, f, B, c.packed, c.first, c.off, c.lens, c.crc, cap=cap) for c in sets[0]]
         n, room, n_all = slots[1].n, slots[1].nbt, slots[0].n + slots[1].n
         outs = Outs(slots[1].dev, n, n_all, room)
         dd = m.BlockDeduper.for_match(ctx, B, 1, n_all, slots[0].nbt + room, room)
@@ -455,17 +407,17 @@ def test_match_and_both_splices_in_one_captured_graph(fmt):
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=s):
         dd.match([slots[0].view()], slots[1].view(), *outs.tensors())
-        delta.run(s1, [slots[1].view()], outs.dfirst, outs.dext)
-        built.run(s2, [slots[0].view(), delta.view()], outs.pfirst, outs.pext)
+        delta.run(s1, [slots[1].view()], outs["delta_first"], outs["delta_ext"])
+        built.run(s2, [slots[0].view(), delta.view()], outs["patch_first"], outs["patch_ext"])
     for k, (store, new) in enumerate((sets[0], sets[1], sets[0])):
         with torch.cuda.stream(s):
             for slot, con in zip(slots, (store, new)):
                 slot.d_packed.fill_(0x3C); slot.d_packed[: con.plen] = con.d_packed[: con.plen]
-                slot.d_first.copy_(con.d_first); slot.d_off.copy_(con.d_off); slot.d_crc.copy_(con.d_crc)
+                slot.d_first.copy_(con.d_first); slot.d_boff.copy_(con.d_boff); slot.d_crc.copy_(con.d_crc)
             outs.reset(); delta.fill(); built.fill()
             g.replay()
         s.synchronize()
-        held = [Con(ctx, f, B, bytes(c.packed) + b"\x3C" * (cap - c.plen), c.first, c.off, c.lens, c.crc).model() for c in (store, new)]   # what the slots hold
+        held = [Container.from_host(ctx, f, B, c.packed + b"\x3C" * (cap - c.plen), c.first, c.off, c.lens, c.crc).model() for c in (store, new)]   # what the slots hold
         mo = T.model_match(held[:1], held[1], B, slots[0].nbt + room, room, True)
         against_model(outs.pull(), mo)
         assert mo["count"][:3] == [new.blocks(0) + 2, 1, 1], k

@@ -6,174 +6,28 @@ import pytest
 
 import blocks_model as M
 import read_model as R
+from blocks_rig import ReadRig, d64, flip, geometry, memo, same_image, slices, FMTS, BLOCKS, FILL, ALL, MIXED, TEXT, ZEROS5, MIXED5, RANDOM1
 
 pytestmark = pytest.mark.gpu
-FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
-BLOCKS = (4096, 65536)
-GUARD, FILL = 48, 0xA5
-ALL = M.M64
-MIXED, TEXT, ZEROS5, MIXED5, RANDOM1 = 5, 7, 6, 9, 3            # rows of R.RECIPES: 3 B + 17 mixed / text, 5 B zeros / mixed, one raw block
-
-
-def _d64(a, dev):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).copy()).to(dev)
-
-
-class Rig:
-    """the container of R.buffers(B), compressed and checksummed on the GPU once; read() / check() run request batches against it"""
-
-    def __init__(self, ctx, fmt, B, bufs=None):
-        import torch
-        import ms_compress_amd as m
-        self.m, self.ctx, self.fmt, self.B = m, ctx, fmt, B
-        self.dev = dev = torch.device("cuda", ctx.device)
-        self.bufs = bufs = R.buffers(B) if bufs is None else bufs
-        self.n, self.lens = len(bufs), [len(b) for b in bufs]
-        self.total = total = sum(self.lens)
-        self.bk = m.BlockContainer(ctx, fmt, B, self.n, total)
-        self.nbt = self.bk.n_blocks_max
-        self.d_in = torch.zeros(total + 3 * self.n + 64, dtype=torch.uint8, device=dev)
-        self.d_off, self.d_len = _d64([0] * self.n, dev), _d64(self.lens, dev)
-        self.d_packed = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
-        self.d_first, self.d_boff = _d64([0] * (self.n + 1), dev), _d64([0] * (self.nbt + 1), dev)
-        self.d_cst = torch.zeros(self.n, dtype=torch.int32, device=dev)
-        self.d_crc = torch.zeros(max(1, self.nbt), dtype=torch.int32, device=dev)
-        self.load(bufs)
-        self.compress()
-        ctx.stream.synchronize()
-        self.pull()
-
-    def load(self, bufs):
-        import torch
-        self.bufs, self.lens = bufs, [len(b) for b in bufs]
-        off, pos = [], 1
-        for b in bufs:
-            off.append(pos)
-            pos += len(b) + 3
-        blob = np.full(self.d_in.numel(), 0x5A, dtype=np.uint8)
-        for b, o in zip(bufs, off):
-            blob[o: o + len(b)] = np.frombuffer(b, dtype=np.uint8)
-        self.d_in.copy_(torch.from_numpy(blob))
-        self.d_off.copy_(_d64(off, self.dev)); self.d_len.copy_(_d64(self.lens, self.dev))
-
-    def compress(self):
-        self.bk.compress(self.d_in, self.d_off, self.d_len, self.d_packed, self.d_first, self.d_boff, self.d_cst, packed_cap=self.total)
-        self.bk.crc(self.d_in, self.d_off, self.d_len, self.d_crc, self.d_cst)
-
-    def pull(self):
-        """the container as the host sees it: what the model reads"""
-        self.first = self.d_first.cpu().numpy().view(np.uint64).copy()
-        self.off = self.d_boff.cpu().numpy().view(np.uint64).copy()
-        self.plen = int(self.off[int(self.first[-1])])
-        self.packed = bytes(self.d_packed.cpu().numpy()[: self.plen])
-        self.crc = self.d_crc.cpu().numpy().view(np.uint32).copy()
-        assert not self.d_cst.cpu().numpy().any()
-        assert (self.crc == R.block_crcs(self.bufs, self.B, self.nbt)).all()
-
-    def wants(self, reqs):
-        out = []
-        for r, o, ln in reqs:
-            L = self.lens[r] if r < self.n else 0
-            out.append(min(ln, L - min(o, L)))
-        return out
-
-    def budget(self, reqs):
-        return sum(len(R.covering(min(o, self.lens[r]), w, self.B)) for (r, o, ln), w in zip(reqs, self.wants(reqs)) if w and r < self.n)
-
-    def layout(self, caps, residues=None):
-        off, pos = [], GUARD
-        for q, c in enumerate(caps):
-            pos = (pos + 15) // 16 * 16 + (residues[q] if residues else (7 * q + 3) % 16)
-            off.append(pos)
-            pos += c + GUARD
-        return off, pos + 16
-
-    def read(self, reqs, blocks_max=None, caps=None, crc=False, residues=None, first=None, boff=None, packed=None, packed_len=None, reader=None, d_out=None):
-        import torch
-        caps = self.wants(reqs) if caps is None else caps
-        blocks_max = self.budget(reqs) if blocks_max is None else blocks_max
-        ooff, room = self.layout(caps, residues)
-        rd = reader or self.m.BlockReader(self.ctx, self.fmt, self.B, self.n, self.nbt, len(reqs), blocks_max)
-        d_out = torch.empty(room, dtype=torch.uint8, device=self.dev) if d_out is None else d_out
-        d_out.fill_(FILL)
-        nq = max(1, len(reqs))
-        d_req = _d64(np.array(reqs, dtype=np.uint64).reshape(-1) if reqs else [0, 0, 0], self.dev)
-        d_ooff, d_ocap = _d64(ooff or [0], self.dev), _d64(caps or [0], self.dev)
-        d_olen = torch.full((nq,), -1, dtype=torch.int64, device=self.dev)
-        d_st = torch.full((nq,), 77, dtype=torch.int32, device=self.dev)
-        rd.read(self.d_packed if packed is None else packed, self.d_first if first is None else _d64(first, self.dev),
-                self.d_boff if boff is None else _d64(boff, self.dev), self.d_len, d_req, d_out, d_ooff, d_ocap, d_olen, d_st,
-                d_block_crc=self.d_crc if crc else None, packed_len=self.plen if packed_len is None else packed_len)
-        counts = rd.counts()
-        if reader is None:
-            rd.close()
-        return d_out.cpu().numpy(), d_olen.cpu().numpy().view(np.uint64)[: len(reqs)], [int(x) for x in d_st.cpu().numpy()[: len(reqs)]], ooff, counts
-
-    def check(self, oracle, reqs, blocks_max=None, caps=None, crc=False, model_packed=None, **kw):
-        """run, and compare statuses, lengths, counts and the WHOLE output buffer with the model; returns (outputs, statuses, counts)"""
-        caps = self.wants(reqs) if caps is None else caps
-        blocks_max = self.budget(reqs) if blocks_max is None else blocks_max
-        out, olen, st, ooff, counts = self.read(reqs, blocks_max, caps, crc, **kw)
-        mo, ms, mc = R.model_read(oracle, self.fmt, self.packed if model_packed is None else model_packed,
-                                  self.plen if kw.get("packed_len") is None else kw["packed_len"],
-                                  self.first if kw.get("first") is None else kw["first"], self.off if kw.get("boff") is None else kw["boff"],
-                                  self.lens, self.B, self.nbt, reqs, caps, blocks_max, self.crc if crc else None)
-        assert st == ms, ("statuses", st, ms)
-        image = np.full(len(out), FILL, dtype=np.uint8)
-        for q, o in enumerate(mo):
-            assert int(olen[q]) == (len(o) if ms[q] == 0 else 0), ("length of request", q)
-            if ms[q] == 0 and o:
-                image[ooff[q]: ooff[q] + len(o)] = np.frombuffer(o, dtype=np.uint8)
-        bad = np.nonzero(out != image)[0]
-        assert bad.size == 0, ("output differs from the model at byte", int(bad[0]), "request offsets", ooff)
-        assert counts == mc, ("counts", counts, mc)
-        return mo, ms, mc
-
-    def close(self):
-        self.bk.close()
 
 
 @pytest.fixture(scope="module")
 def rigs(gpu_ctx):
-    made = {}
-
-    def get(fmt, B):
-        if (fmt, B) not in made:
-            made[(fmt, B)] = Rig(gpu_ctx, FMTS[fmt], B)
-        return made[(fmt, B)]
-    yield get
-    for r in made.values():
-        r.close()
-
-
-def _slices(rig, reqs):
-    return [rig.bufs[r][o: o + min(ln, rig.lens[r])] for r, o, ln in reqs]
-
-
-def _geometry(rig):
-    B, reqs = rig.B, []
-    for r, L in enumerate(rig.lens):                              # every resource: whole, at and behind its end, nothing, its first and last byte
-        reqs += [(r, 0, ALL), (r, L, 5), (r, L + 7, ALL), (r, 3, 0), (r, 0, 1), (r, max(0, L - 1), 1), (r, B - 1, 1), (r, B, 1)]
-    for r in (MIXED, TEXT, MIXED5):
-        reqs += [(r, B + 100, 50), (r, B - 3, 10), (r, B - 1, 2 * B + 2), (r, B, B), (r, 0, 2 * B), (r, 2 * B, B), (r, 1, B - 1), (r, B, 2 * B + 17)]
-    for r in (MIXED, TEXT):                                       # the short last block
-        reqs += [(r, 3 * B, 17), (r, 3 * B + 5, 100), (r, 3 * B - 1, 2), (r, 3 * B + 16, 1)]
-    return reqs
+    yield from memo(lambda fmt, B: ReadRig.make(gpu_ctx, FMTS[fmt], B, R.buffers(B)))
 
 
 @pytest.mark.parametrize("B", BLOCKS)
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_geometry(rigs, oracle, fmt, B):
     rig = rigs(fmt, B)
-    reqs = _geometry(rig)
+    reqs = geometry(rig)
     order = np.random.RandomState(3).permutation(len(reqs))       # the same resource named many times, unsorted
     reqs = [reqs[i] for i in order]
     mo, ms, mc = rig.check(oracle, reqs)
-    assert ms == [0] * len(reqs) and mo == _slices(rig, reqs)
+    assert ms == [0] * len(reqs) and mo == slices(rig, reqs)
     assert mc[0] == rig.budget(reqs) and 0 < mc[2] < mc[1] <= int(rig.first[-1])      # raw and decoded blocks, each once
     mo, ms, _ = rig.check(oracle, reqs, crc=True)
-    assert ms == [0] * len(reqs) and mo == _slices(rig, reqs)
+    assert ms == [0] * len(reqs) and mo == slices(rig, reqs)
 
 
 @pytest.mark.parametrize("B", BLOCKS)
@@ -189,7 +43,7 @@ def test_every_source_and_destination_residue(rigs, oracle, fmt, B):
             reqs += [(MIXED, B - 24 + a, 40), (MIXED, 64 + a, 40 - d), (MIXED, B + 160 + a, 25 + d)]
             res += [d, d, d]
     mo, ms, _ = rig.check(oracle, reqs, residues=res)
-    assert ms == [0] * len(reqs) and mo == _slices(rig, reqs)
+    assert ms == [0] * len(reqs) and mo == slices(rig, reqs)
 
 
 @pytest.mark.parametrize("B", BLOCKS)
@@ -200,7 +54,7 @@ def test_sharing(rigs, oracle, fmt, B):
     reqs += [(MIXED5, 0, 2 * B), (MIXED5, B, 2 * B), (MIXED5, 2 * B + 5, 2 * B), (MIXED5, 4 * B, B)]   # neighbours overlapping by one block
     reqs += [(ZEROS5, 10, 5 * B - 20), (ZEROS5, 0, ALL), (MIXED, 0, ALL), (MIXED, B - 1, 2)]
     mo, ms, (units, distinct, decoded) = rig.check(oracle, reqs, crc=True)
-    assert ms == [0] * len(reqs) and mo == _slices(rig, reqs)
+    assert ms == [0] * len(reqs) and mo == slices(rig, reqs)
     assert units == 16 + 2 + 2 + 3 + 1 + 5 + 5 + 4 + 2 and distinct == 1 + 5 + 5 + 4
     stored = [int(rig.off[k + 1] - rig.off[k]) for k in range(int(rig.first[-1]))]
     sizes = lambda r: [(stored[int(rig.first[r]) + k], min(B, rig.lens[r] - k * B)) for k in range((rig.lens[r] + B - 1) // B)]
@@ -229,23 +83,11 @@ def test_rejects(rigs, oracle, fmt, B):
                        (3, [0, M.ARG, M.ARG, M.ARG, M.ARG, 0, M.ARG, M.ARG]), (0, [M.ARG] * 5 + [0, M.ARG, M.ARG]), (10, [0, M.ARG, 0, M.ARG, 0, 0, 0, 0])):
         mo, ms, _ = rig.check(oracle, reqs, caps=caps, blocks_max=bmax)
         assert ms == want, (bmax, ms)
-        assert [o for o, s in zip(mo, ms) if s == 0] == [b for b, s in zip(_slices(rig, [q if q[0] < rig.n else (0, 0, 0) for q in reqs]), ms) if s == 0]
+        assert [o for o, s in zip(mo, ms) if s == 0] == [b for b, s in zip(slices(rig, [q if q[0] < rig.n else (0, 0, 0) for q in reqs]), ms) if s == 0]
     # a request that fails the budget does not stop an empty one behind it, and BUF is decided before the budget
     caps[4] -= 1
     assert rig.check(oracle, reqs, caps=caps, blocks_max=5)[1] == [0, M.ARG, 0, M.ARG, M.BUF, 0, 0, M.ARG]
     assert rig.check(oracle, [], blocks_max=4)[1] == []           # no requests: MSCOMP_OK, nothing done
-
-
-def _flip(oracle, rig, j, e, decodes):
-    """a byte of stored block j whose flip the reference's decoder takes with defined behaviour: to other bytes (decodes) or to an error"""
-    o0, o1 = int(rig.off[j]), int(rig.off[j + 1])
-    good = oracle.oracle_decompress_ex(rig.fmt, rig.packed[o0:o1], e)[1]
-    for p in range(o1 - o0 - 1, -1, -1):
-        blk = bytearray(rig.packed[o0:o1]); blk[p] ^= 0x01
-        ds, got, undefined = oracle.oracle_decompress_ex(rig.fmt, bytes(blk), e)
-        if not undefined and ((ds == 0 and len(got) == e and got != good) if decodes else (ds != 0 or len(got) != e)):
-            return o0 + p
-    raise AssertionError("no such byte in this block")
 
 
 @pytest.mark.parametrize("B", BLOCKS)
@@ -278,7 +120,7 @@ def test_damage(rigs, oracle, fmt, B):
     assert rig.check(oracle, reqs + [(rig.n - 1, 0, 1)], first=bad)[1] == [0] * len(reqs) + [M.ARG]
     # payload: a flipped byte in a raw block, a flipped literal in a compressed one -- seen with checksums only; a broken stream -- seen always
     e1 = B
-    for at, blocks, always in ((int(off[j]) + 77, {0}, False), (_flip(oracle, rig, j + 1, e1, True), {1}, False), (_flip(oracle, rig, j + 1, e1, False), {1}, True)):
+    for at, blocks, always in ((int(off[j]) + 77, {0}, False), (flip(oracle, rig, j + 1, e1, True), {1}, False), (flip(oracle, rig, j + 1, e1, False), {1}, True)):
         hurt = bytearray(rig.packed); hurt[at] ^= 0x01
         d_hurt = rig.d_packed.clone(); d_hurt[at] = int(hurt[at])
         assert rig.check(oracle, reqs, packed=d_hurt, model_packed=bytes(hurt))[1] == (hit(blocks) if always else [0] * len(reqs))
@@ -287,7 +129,7 @@ def test_damage(rigs, oracle, fmt, B):
         few = [q for q, c in zip(reqs, covers) if not c & blocks]
         for crc in (False, True):
             mo, ms, _ = rig.check(oracle, few, packed=d_hurt, model_packed=bytes(hurt), crc=crc)
-            assert ms == [0] * len(few) and mo == _slices(rig, few)
+            assert ms == [0] * len(few) and mo == slices(rig, few)
 
 
 @pytest.mark.parametrize("fmt", list(FMTS))
@@ -303,22 +145,20 @@ def test_repeats_and_arguments_changed(rigs, oracle, fmt):
     caps = [5 * B] * 5
     ooff, room = rig.layout(caps)
     rd = rig.m.BlockReader(rig.ctx, rig.fmt, B, rig.n, rig.nbt, 5, 12)
-    d_req, d_ooff, d_ocap = _d64([0] * 15, dev), _d64(ooff, dev), _d64(caps, dev)
+    d_req, d_ooff, d_ocap = d64([0] * 15, dev), d64(ooff, dev), d64(caps, dev)
     d_olen, d_st = torch.zeros(5, dtype=torch.int64, device=dev), torch.zeros(5, dtype=torch.int32, device=dev)
     outs = [torch.empty(room, dtype=torch.uint8, device=dev) for _ in range(2)]
 
     def run(reqs, d_out, crc):
-        d_req.copy_(_d64(np.array(reqs, dtype=np.uint64).reshape(-1), dev))
+        d_req.copy_(d64(np.array(reqs, dtype=np.uint64).reshape(-1), dev))
         d_out.fill_(FILL); d_olen.fill_(-1); d_st.fill_(77)
         rd.read(rig.d_packed, rig.d_first, rig.d_boff, rig.d_len, d_req, d_out, d_ooff, d_ocap, d_olen, d_st, d_block_crc=rig.d_crc if crc else None,
                 packed_len=rig.plen)
         rig.ctx.stream.synchronize()
         out, olen, st = d_out.cpu().numpy(), d_olen.cpu().numpy(), d_st.cpu().numpy()
-        image = np.full(room, FILL, dtype=np.uint8)
-        for q, want in enumerate(_slices(rig, reqs)):
+        for q, want in enumerate(slices(rig, reqs)):
             assert st[q] == 0 and int(olen[q]) == len(want), (q, st)
-            image[ooff[q]: ooff[q] + len(want)] = np.frombuffer(want, dtype=np.uint8)
-        assert (out == image).all()
+        same_image(out, list(zip(ooff, slices(rig, reqs))), FILL, "output")
     for _ in range(3):
         run(sets[0], outs[0], True)
     for k in (1, 0, 1):                                           # the table rewritten in place: the same graph
@@ -343,17 +183,17 @@ def test_replay_after_the_context_scratch_moved(fmt):
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        rig = Rig(ctx, f, B, bufs)
+        rig = ReadRig.make(ctx, f, B, bufs)
         dev = rig.dev
         reqs = [(1, 100, 4500), (2, B - 7, 2 * B + 9), (2, 3 * B, ALL)]
         caps = [3 * B] * 3
         ooff, room = rig.layout(caps)
         rd = m.BlockReader(ctx, f, B, rig.n, rig.nbt, 3, rig.budget(reqs))
-        d_req, d_ooff, d_ocap = _d64(np.array(reqs, dtype=np.uint64).reshape(-1), dev), _d64(ooff, dev), _d64(caps, dev)
+        d_req, d_ooff, d_ocap = d64(np.array(reqs, dtype=np.uint64).reshape(-1), dev), d64(ooff, dev), d64(caps, dev)
         d_olen, d_st = torch.zeros(3, dtype=torch.int64, device=dev), torch.zeros(3, dtype=torch.int32, device=dev)
         d_out = torch.empty(room, dtype=torch.uint8, device=dev)
         image = np.full(room, FILL, dtype=np.uint8)
-        for q, want in enumerate(_slices(rig, reqs)):
+        for q, want in enumerate(slices(rig, reqs)):
             assert len(want) == (4500, 2 * B + 9, 17)[q]
             image[ooff[q]: ooff[q] + len(want)] = np.frombuffer(want, dtype=np.uint8)
 
@@ -372,7 +212,7 @@ def test_replay_after_the_context_scratch_moved(fmt):
         d_in = torch.from_numpy(np.resize(np.frombuffer(text, dtype=np.uint8), n * U)).to(dev)
         d_big = torch.empty(n * cap, dtype=torch.uint8, device=dev)
         d_blen, d_bst = torch.zeros(n, dtype=torch.int64, device=dev), torch.full((n,), 77, dtype=torch.int32, device=dev)
-        big.execute(d_in, _d64(np.arange(n) * U, dev), _d64([U] * n, dev), d_big, _d64(np.arange(n) * cap, dev), _d64([cap] * n, dev), d_blen, d_bst)
+        big.execute(d_in, d64(np.arange(n) * U, dev), d64([U] * n, dev), d_big, d64(np.arange(n) * cap, dev), d64([cap] * n, dev), d_blen, d_bst)
         s.synchronize()
         assert not d_bst.cpu().numpy().any()
         after = m.api.scratch_report(ctx, 0)
@@ -396,12 +236,12 @@ def test_compress_crc_and_read_in_one_captured_graph(oracle, fmt):
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        rig = Rig(ctx, f, B, base)
+        rig = ReadRig.make(ctx, f, B, base)
         reqs = [(MIXED, B - 5, 2 * B), (TEXT, 17, 300), (MIXED5, 0, ALL), (0, 0, 5), (MIXED, 0, B), (3, 0, ALL), (TEXT, 2 * B + 9, ALL)]
         caps = [5 * B] * len(reqs)
         ooff, room = rig.layout(caps)
         rd = m.BlockReader(ctx, f, B, rig.n, rig.nbt, len(reqs), 24)
-        d_req, d_ooff, d_ocap = _d64(np.array(reqs, dtype=np.uint64).reshape(-1), rig.dev), _d64(ooff, rig.dev), _d64(caps, rig.dev)
+        d_req, d_ooff, d_ocap = d64(np.array(reqs, dtype=np.uint64).reshape(-1), rig.dev), d64(ooff, rig.dev), d64(caps, rig.dev)
         d_olen, d_st = torch.zeros(len(reqs), dtype=torch.int64, device=rig.dev), torch.zeros(len(reqs), dtype=torch.int32, device=rig.dev)
         d_out = torch.empty(room, dtype=torch.uint8, device=rig.dev)
     s.synchronize()
@@ -417,11 +257,9 @@ def test_compress_crc_and_read_in_one_captured_graph(oracle, fmt):
             g.replay()
         s.synchronize()
         out, olen, st = d_out.cpu().numpy(), d_olen.cpu().numpy(), d_st.cpu().numpy()
-        image = np.full(room, FILL, dtype=np.uint8)
-        for q, want in enumerate(_slices(rig, reqs)):
+        for q, want in enumerate(slices(rig, reqs)):
             assert st[q] == 0 and int(olen[q]) == len(want), (k, q, st)
-            image[ooff[q]: ooff[q] + len(want)] = np.frombuffer(want, dtype=np.uint8)
-        assert (out == image).all(), k
+        same_image(out, list(zip(ooff, slices(rig, reqs))), FILL, ("output of replay", k))
     del g
     rd.close()
     rig.close()

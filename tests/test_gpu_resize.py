@@ -1,6 +1,6 @@
 """GPU: mscomp_amd_writer_resize against the model of tests/resize_model.py -- the whole new packed buffer compared with a sentinel image (so a
 byte at or behind new_cap, or behind the container's end, fails), every entry of the four new tables, d_res_status and the counts -- on the
-container of tests/test_gpu_read.Rig with a table of 16 spare rows and blocks_max = 24; where the container is healthy also byte for byte
+container of tests/blocks_rig.Container with a table of 16 spare rows and blocks_max = 24; where the container is healthy also byte for byte
 against BlockContainer.compress + .crc of the resized data, and every new container is read back. mscomp_amd_res_crc_dev against zlib.crc32."""
 import zlib
 
@@ -11,125 +11,10 @@ import blocks_model as M
 import read_model as R
 import resize_model as Z
 import write_model as W
-from test_gpu_read import Rig, _d64, FMTS, BLOCKS, FILL, ALL, MIXED, TEXT, ZEROS5, MIXED5, RANDOM1
-from test_gpu_write import long_runs_rig
-from test_resize_model import SPARE, mixes
+from blocks_rig import Container, Resizes, d64, long_runs, memo, BUDGET, FMTS, BLOCKS, FILL, ALL, MIXED, TEXT, ZEROS5, MIXED5
+from resize_model import SPARE, mixes
 
 pytestmark = pytest.mark.gpu
-BUDGET = 24
-
-
-def _i32(a, dev):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32).copy()).to(dev)
-
-
-class Resizes:
-    """resize calls against the container of a test_gpu_read.Rig, its tables widened to nb + SPARE rows"""
-
-    def __init__(self, rig):
-        self.rig = rig
-        nb = int(rig.first[-1])
-        self.nbt = nb + SPARE
-        self.off = np.concatenate([rig.off[: nb + 1], np.full(SPARE, rig.off[nb], dtype=np.uint64)])
-        self.crc = np.concatenate([rig.crc[:nb], np.zeros(SPARE, dtype=np.uint32)])
-        self.d_boff, self.d_crc = _d64(self.off, rig.dev), _i32(self.crc, rig.dev)
-        self.room = rig.total + BUDGET * rig.B                   # what the resources can hold after one call
-        self.big = rig.m.BlockContainer(rig.ctx, rig.fmt, rig.B, rig.n, self.room)
-
-    def outputs(self):
-        import torch
-        rig, dev = self.rig, self.rig.dev
-        return (torch.full((self.room + 64,), FILL, dtype=torch.uint8, device=dev), torch.full((rig.n + 1,), -1, dtype=torch.int64, device=dev),
-                torch.full((self.nbt + 1,), -1, dtype=torch.int64, device=dev), torch.full((self.nbt,), 0x55555555, dtype=torch.int32, device=dev),
-                torch.full((rig.n,), -1, dtype=torch.int64, device=dev), torch.full((rig.n,), 77, dtype=torch.int32, device=dev))
-
-    def run(self, want, blocks_max=BUDGET, crc=True, new_cap=None, first=None, boff=None, packed=None, lens=None, writer=None):
-        rig, dev = self.rig, self.rig.dev
-        d_new, d_nfirst, d_noff, d_ncrc, d_nlen, d_rst = self.outputs()
-        wr = writer or rig.m.BlockWriter(rig.ctx, rig.fmt, rig.B, rig.n, self.nbt, 0, blocks_max)
-        wr.resize(rig.d_packed if packed is None else packed, rig.d_first if first is None else _d64(first, dev),
-                  self.d_boff if boff is None else _d64(boff, dev), rig.d_len if lens is None else _d64(lens, dev), _d64(want, dev),
-                  d_new, d_nfirst, d_noff, d_nlen, d_rst, d_block_crc=self.d_crc if crc else None, d_new_block_crc=d_ncrc if crc else None,
-                  packed_len=rig.plen, new_cap=self.room if new_cap is None else new_cap)
-        counts = wr.counts()
-        if writer is None:
-            wr.close()
-        return {"d": (d_new, d_nfirst, d_noff, d_ncrc, d_nlen), "image": d_new.cpu().numpy(), "first": d_nfirst.cpu().numpy().view(np.uint64),
-                "off": d_noff.cpu().numpy().view(np.uint64), "crc": d_ncrc.cpu().numpy().view(np.uint32) if crc else None,
-                "new_len": [int(x) for x in d_nlen.cpu().numpy().view(np.uint64)], "res_status": [int(x) for x in d_rst.cpu().numpy()], "counts": counts}
-
-    def check(self, oracle, want, blocks_max=BUDGET, crc=True, new_cap=None, model_packed=None, read_back=True, **kw):
-        """run, compare everything the call wrote with the model, and read every resource of the new container back"""
-        rig = self.rig
-        cap = self.room if new_cap is None else new_cap
-        got = self.run(want, blocks_max, crc, cap, **kw)
-        lens = rig.lens if kw.get("lens") is None else kw["lens"]
-        mo = Z.model_resize(oracle, rig.fmt, rig.packed if model_packed is None else model_packed, rig.plen,
-                            rig.first if kw.get("first") is None else kw["first"], self.off if kw.get("boff") is None else kw["boff"], lens, rig.B,
-                            self.nbt, want, blocks_max, cap, self.crc if crc else None)
-        for key in ("res_status", "new_len", "counts"):
-            assert got[key] == mo[key], (key, got[key], mo[key])
-        assert (got["first"] == mo["first"]).all(), ("first", got["first"], mo["first"])
-        assert (got["off"] == mo["off"]).all(), ("offsets", got["off"], mo["off"])
-        if crc:
-            assert (got["crc"] == mo["crc"]).all(), ("checksums", np.nonzero(got["crc"] != mo["crc"])[0])
-        image = np.full(len(got["image"]), FILL, dtype=np.uint8)
-        image[: len(mo["packed"])] = np.frombuffer(mo["packed"], dtype=np.uint8)
-        bad = np.nonzero(got["image"] != image)[0]
-        assert bad.size == 0, ("new packed bytes differ from the model at", int(bad[0]), "of", len(mo["packed"]))
-        if read_back and not any(mo["res_status"]) and model_packed is None and kw.get("boff") is None:
-            self.read_back(got, Z.resized(rig.bufs, mo["new_len"]))
-        return mo, got
-
-    def read_back(self, got, data):
-        rig = self.rig
-        nb = int(got["first"][-1])
-        out, st = rig.m.blocks_read(rig.fmt, got["image"][: int(got["off"][nb])], got["first"], got["off"], [len(b) for b in data], rig.B,
-                                    [(r, 0, ALL) for r in range(rig.n)], ctx=rig.ctx, block_crc=got["crc"])
-        assert st == [0] * rig.n and out == data
-
-    def fresh(self, bufs):
-        """BlockContainer.compress + .crc of these resources, in tensors of their own: (packed, first, off, crc) on the host"""
-        import torch
-        rig, dev = self.rig, self.rig.dev
-        lens = [len(b) for b in bufs]
-        blob = np.frombuffer(b"".join(bufs), dtype=np.uint8)
-        d_in = torch.zeros(self.room + 64, dtype=torch.uint8, device=dev)
-        if len(blob):
-            d_in[: len(blob)] = torch.from_numpy(blob.copy()).to(dev)
-        d_off, d_len = _d64(np.cumsum([0] + lens[:-1]), dev), _d64(lens, dev)
-        d_packed = torch.zeros(self.room + 64, dtype=torch.uint8, device=dev)
-        nbm = self.big.n_blocks_max
-        d_first, d_boff = _d64([0] * (rig.n + 1), dev), _d64([0] * (nbm + 1), dev)
-        d_st, d_crc = torch.zeros(rig.n, dtype=torch.int32, device=dev), torch.zeros(nbm, dtype=torch.int32, device=dev)
-        self.big.compress(d_in, d_off, d_len, d_packed, d_first, d_boff, d_st, packed_cap=self.room)
-        self.big.crc(d_in, d_off, d_len, d_crc, d_st)
-        rig.ctx.stream.synchronize()
-        assert not d_st.cpu().numpy().any()
-        off = d_boff.cpu().numpy().view(np.uint64)
-        return bytes(d_packed.cpu().numpy()[: int(off[-1])]), d_first.cpu().numpy().view(np.uint64), off, d_crc.cpu().numpy().view(np.uint32)
-
-    def check_consequence(self, got, data):
-        """the header's consequence: the new container is what compress and crc write for the resized data"""
-        packed, first, off, crc = self.fresh(data)
-        nb = int(first[-1])
-        assert (got["first"] == first).all() and (got["off"][: nb + 1] == off[: nb + 1]).all() and (got["off"][nb:] == off[nb]).all()
-        assert bytes(got["image"][: len(packed)]) == packed
-        assert got["crc"] is None or ((got["crc"][:nb] == crc[:nb]).all() and not got["crc"][nb:].any())
-
-    def res_crc(self, d_first, d_len, d_crc):
-        import torch
-        rig = self.rig
-        d_out = torch.full((rig.n,), 0x33333333, dtype=torch.int32, device=rig.dev)
-        d_st = torch.full((rig.n,), 77, dtype=torch.int32, device=rig.dev)
-        rig.m.res_crc_dev(rig.ctx, rig.B, rig.n, self.nbt, d_first, d_len, d_crc, d_out, d_st)
-        rig.ctx.stream.synchronize()
-        return [int(x) for x in d_out.cpu().numpy().view(np.uint32)], [int(x) for x in d_st.cpu().numpy()]
-
-    def close(self):
-        self.big.close()
-        self.rig.close()
 
 
 def _counts(lens, want, B):
@@ -140,21 +25,13 @@ def _counts(lens, want, B):
 
 @pytest.fixture(scope="module")
 def rigs(gpu_ctx):
-    made = {}
-
-    def get(fmt, B):
-        if (fmt, B) not in made:
-            made[(fmt, B)] = Resizes(Rig(gpu_ctx, FMTS[fmt], B))
-        return made[(fmt, B)]
-    yield get
-    for z in made.values():
-        z.close()
+    yield from memo(lambda fmt, B: Resizes(Container.make(gpu_ctx, FMTS[fmt], B, R.buffers(B))))
 
 
 @pytest.mark.parametrize("B", BLOCKS)
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_geometry(rigs, oracle, fmt, B):
-    """per resource every wanted length of test_resize_model.WANTS -- cuts inside the tail block, inside a full block and at a boundary,
+    """per resource every wanted length of resize_model.WANTS -- cuts inside the tail block, inside a full block and at a boundary,
     extension of a partial and of an aligned tail and of an empty resource, truncation to nothing --, mixed in one call"""
     zs = rigs(fmt, B)
     rig = zs.rig
@@ -165,7 +42,7 @@ def test_geometry(rigs, oracle, fmt, B):
             data = Z.resized(rig.bufs, want)
             zs.check_consequence(got, data)
             if crc:                                               # the resource checksums, from the new block checksums alone
-                d_new, d_nfirst, d_noff, d_ncrc, d_nlen = got["d"]
+                d_new, d_nfirst, d_noff, d_ncrc, d_nlen, _ = got["d"]
                 assert zs.res_crc(d_nfirst, d_nlen, d_ncrc) == ([zlib.crc32(b) for b in data], [0] * rig.n)
     # a cut exactly at a block boundary has no changed block and decodes nothing; W = 0 drops everything
     want = list(rig.lens); want[MIXED] = 2 * B; want[MIXED5] = 0; want[TEXT] = 3 * B
@@ -281,10 +158,10 @@ def test_damage(rigs, oracle, fmt, B):
 
 
 def test_long_runs_and_slice_edges(gpu_ctx, oracle):
-    """the move pass where its runs matter, on the container of test_gpu_write.long_runs_rig: (a) 311 clean rows in one run that is shifted by
+    """the move pass where its runs matter, on the container of blocks_rig.long_runs: (a) 311 clean rows in one run that is shifted by
     a row as well as by bytes; (b) a clean run that ends at its resource's changed block, the resource behind it a run at another distance;
     (c) the long resource carried with MSCOMP_DATA_ERROR between two that change; (d) as (b), new_cap inside the long resource"""
-    rig, g = long_runs_rig(gpu_ctx)
+    rig, g = long_runs(Container, gpu_ctx)
     zs, B, lens = Resizes(rig), rig.B, rig.lens
     # (a) the first cut to 1 byte, the last extended by 2 B + 5
     want = [1, lens[1], lens[2] + 2 * B + 5]
@@ -346,14 +223,14 @@ def test_repeats_and_ping_pong(rigs, oracle, fmt):
     blob = np.zeros(sroom, dtype=np.uint8)
     for o, s in zip(soff, srcs):
         blob[o: o + len(s)] = np.frombuffer(s, dtype=np.uint8)
-    d_src, d_soff, d_req = torch.from_numpy(blob).to(dev), _d64(soff, dev), _d64(np.array(reqs, dtype=np.uint64).reshape(-1), dev)
+    d_src, d_soff, d_req = torch.from_numpy(blob).to(dev), d64(soff, dev), d64(np.array(reqs, dtype=np.uint64).reshape(-1), dev)
     d_wr, d_st = torch.zeros(2, dtype=torch.int64, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)
     d_rst = torch.zeros(rig.n, dtype=torch.int32, device=dev)
     wr = rig.m.BlockWriter(rig.ctx, rig.fmt, B, rig.n, zs.nbt, 2, BUDGET)
     b_new, b_first, b_off, b_crc, b_len, b_rst = zs.outputs()
     a_new, _, a_off, a_crc, _, _ = zs.outputs()
     c_new, c_first, c_off, c_crc, c_len, c_rst = zs.outputs()
-    d_want1 = _d64(want1, dev)
+    d_want1 = d64(want1, dev)
     for _ in range(5):
         wr.resize(rig.d_packed, rig.d_first, zs.d_boff, rig.d_len, d_want1, b_new, b_first, b_off, b_len, b_rst, d_block_crc=zs.d_crc, d_new_block_crc=b_crc,
                   packed_len=rig.plen, new_cap=zs.room)
@@ -362,7 +239,7 @@ def test_repeats_and_ping_pong(rigs, oracle, fmt):
         wr.write(b_new, b_first, b_off, b_len, d_req, d_src, d_soff, a_new, a_off, d_wr, d_st, d_rst, d_block_crc=b_crc, d_new_block_crc=a_crc,
                  packed_len=zs.room, new_cap=zs.room)
     assert not d_st.cpu().numpy().any() and not d_rst.cpu().numpy().any() and [int(x) for x in d_wr.cpu().numpy()] == wants
-    d_want2 = _d64(rig.lens, dev)
+    d_want2 = d64(rig.lens, dev)
     for _ in range(5):
         wr.resize(a_new, b_first, a_off, b_len, d_want2, c_new, c_first, c_off, c_len, c_rst, d_block_crc=a_crc, d_new_block_crc=c_crc, packed_len=zs.room,
                   new_cap=zs.room)
@@ -388,13 +265,13 @@ def test_compress_crc_resize_res_crc_and_read_in_one_captured_graph(oracle, fmt)
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        rig = Rig(ctx, f, B, base)
+        rig = Container.make(ctx, f, B, base)
         dev, n, nbt = rig.dev, rig.n, rig.nbt
         L = rig.lens[MIXED]
         want = list(rig.lens); want[MIXED] = L + B + 9; want[TEXT] = B + 3; want[0] = 2 * B
         room = rig.total + 4 * B
         wr = m.BlockWriter(ctx, f, B, n, nbt, 0, 8)
-        d_want = _d64(want, dev)
+        d_want = d64(want, dev)
         d_new = torch.empty(room + 64, dtype=torch.uint8, device=dev)
         d_nfirst, d_noff = torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
         d_ncrc, d_nlen = torch.zeros(nbt, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev)
@@ -403,7 +280,7 @@ def test_compress_crc_resize_res_crc_and_read_in_one_captured_graph(oracle, fmt)
         caps = [30, B + 3, 2, 5 * B]
         ooff, oroom = rig.layout(caps)
         rd = m.BlockReader(ctx, f, B, n, nbt, len(reads), 16)
-        d_rreq, d_ooff, d_ocap = _d64(np.array(reads, dtype=np.uint64).reshape(-1), dev), _d64(ooff, dev), _d64(caps, dev)
+        d_rreq, d_ooff, d_ocap = d64(np.array(reads, dtype=np.uint64).reshape(-1), dev), d64(ooff, dev), d64(caps, dev)
         d_olen, d_ost = torch.zeros(len(reads), dtype=torch.int64, device=dev), torch.zeros(len(reads), dtype=torch.int32, device=dev)
         d_out = torch.empty(oroom, dtype=torch.uint8, device=dev)
     s.synchronize()
@@ -456,11 +333,11 @@ def test_res_crc(rigs, oracle, fmt, B):
     assert [int(x) for x in d_rcrc.cpu().numpy().view(np.uint32)] == want
     # the rejects: a wrong count (here and in the next resource), a table entry beyond the table
     bad = rig.first.copy(); bad[MIXED + 1] -= np.uint64(1)
-    got = zs.res_crc(_d64(bad, rig.dev), rig.d_len, zs.d_crc)
+    got = zs.res_crc(d64(bad, rig.dev), rig.d_len, zs.d_crc)
     mo = Z.model_res_crc(bad, lens, zs.crc, B, zs.nbt)
     assert got == ([int(x) for x in mo[0]], mo[1]) and got[1][MIXED] == got[1][MIXED + 1] == M.DATA and got[0][MIXED] == 0
     bad = rig.first.copy(); bad[n] = np.uint64(zs.nbt + 1)
-    got = zs.res_crc(_d64(bad, rig.dev), rig.d_len, zs.d_crc)
+    got = zs.res_crc(d64(bad, rig.dev), rig.d_len, zs.d_crc)
     mo = Z.model_res_crc(bad, lens, zs.crc, B, zs.nbt)
     assert got == ([int(x) for x in mo[0]], mo[1]) and got[1][n - 1] == M.ARG
 

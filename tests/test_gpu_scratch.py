@@ -18,11 +18,12 @@ import pytest
 
 import cases
 import test_foreign_streams as tf
-from test_gpu_crc import CrcRig, K, _bufs, _u32
-from test_gpu_blocks import _d64
+import crc_model as K
 from test_gpu_decompress_dev import GUARD, _dt, _layout
 from test_gpu_dev_large_units import LZG_MIN_CAP, XPS_MIN_IN
 import blocks_model as M
+import blocks_rig as G
+import read_model as R
 
 pytestmark = pytest.mark.gpu
 FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
@@ -457,7 +458,7 @@ def test_crc_dev_plan_one_long_unit_and_many_short_ones(ctx):
         d_crc.fill_(0x5A5A5A5A); d_st.fill_(77)
         plan.execute(d_in, d_off, d_len, d_crc, d_st)
         ctx.stream.synchronize()
-        return _u32(d_crc, n), d_st.cpu().numpy()
+        return G.u32(d_crc, n), d_st.cpu().numpy()
 
     def check(res):
         assert (res[0] == want).all() and (res[1] == wst).all()
@@ -515,17 +516,17 @@ def test_layout_and_compact_dev_and_compact_batch(oracle, ctx):
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_block_container(oracle, ctx, fixture, fmt):
     """B = 4096, the committed blocks fixture: crc, compress, decompress and check on one container whose bounds are the batch's, against
-    the models of tests/test_gpu_blocks.py and tests/test_gpu_crc.py; then a decompress from an offset table with a decreasing entry"""
+    the models of tests/blocks_model.py and tests/crc_model.py, through the CrcRig of tests/blocks_rig.py; then a decompress from an offset table with a decreasing entry"""
     f, B = FMTS[fmt], 4096
-    bufs = _bufs(fixture, f, B)
+    bufs = G.crc_bufs(fixture, f, B)
     n, lens, total = len(bufs), [len(b) for b in bufs], sum(len(b) for b in bufs)
-    rig = CrcRig(ctx, f, B, n, total)
+    rig = G.CrcRig(ctx, f, B, n, total)
     rig.load(bufs)
     rig.set_out(lens)
     mp, mf, mo, ms = M.model_compress(oracle, f, bufs, B, total, total)
     j = int(mf[8])
     bad = mo.copy(); bad[j + 1] = bad[j] - 1
-    d_bad = _d64(bad, rig.dev)
+    d_bad = G.d64(bad, rig.dev)
     # once, unpoisoned: everything against its model
     rig.check_crc()
     rig.check_compress(oracle, packed_cap=total)
@@ -539,7 +540,7 @@ def test_block_container(oracle, ctx, fixture, fmt):
     def run_crc():
         rig.crc()
         rig.ctx.stream.synchronize()
-        return _u32(rig.d_bcrc, rig.nbmax).copy(), _u32(rig.d_rcrc, n).copy(), rig.d_kst.cpu().numpy()
+        return G.u32(rig.d_bcrc, rig.nbmax).copy(), G.u32(rig.d_rcrc, n).copy(), rig.d_kst.cpu().numpy()
 
     def run_compress():
         rig.compress(packed_cap=total)
@@ -562,9 +563,9 @@ def test_block_container(oracle, ctx, fixture, fmt):
 
 
 # ---- readers, writers, splicers, dedupers ------------------------------------------------------------------------------------------------------
-# The source containers are those of the modules that own the operations (tests/test_gpu_read.Rig and what is built on it), made once on the
+# The source containers and the operation rigs are those of tests/blocks_rig.py (Container and what is built on it), made once on the
 # session's context; the object under test lives on the case's fresh context, with bounds equal to its call. Every execution, poisoned or
-# not, is compared with that module's model by that module's own check.
+# not, is compared with the operation's model by that rig's own check.
 B4 = 4096
 
 
@@ -580,15 +581,12 @@ def _flat(*parts):
 
 @pytest.fixture(scope="module")
 def sources(gpu_ctx):
-    import test_gpu_read as TR
-    import test_gpu_splice as TS
-    import test_gpu_splice_extents as TX
     made = {}
 
     def get(kind, fmt):
         if (kind, fmt) not in made:
-            made[(kind, fmt)] = {"read": lambda: TR.Rig(gpu_ctx, FMTS[fmt], B4), "splice": lambda: TS.Splices(gpu_ctx, FMTS[fmt], B4),
-                                 "extents": lambda: TX.Extents(gpu_ctx, FMTS[fmt], B4)}[kind]()
+            made[(kind, fmt)] = {"read": lambda: G.ReadRig.make(gpu_ctx, FMTS[fmt], B4, R.buffers(B4)), "splice": lambda: G.Splices(gpu_ctx, FMTS[fmt], B4),
+                                 "extents": lambda: G.Extents(gpu_ctx, FMTS[fmt], B4)}[kind]()
         return made[(kind, fmt)]
     yield get
     for v in made.values():
@@ -597,8 +595,7 @@ def sources(gpu_ctx):
 
 def _falling(rig):
     """the offset table with a decreasing entry in the resource of raw and compressed blocks (the `damage` tests of the owning modules)"""
-    import test_gpu_read as TR
-    j = int(rig.first[TR.MIXED])
+    j = int(rig.first[G.MIXED])
     bad = rig.off.copy(); bad[j + 2] = bad[j + 1] - np.uint64(1)
     return bad
 
@@ -607,9 +604,8 @@ def _falling(rig):
 def test_block_reader(oracle, ctx, sources, fmt):
     import torch
     import ms_compress_amd as m
-    import test_gpu_read as TR
     rig = sources("read", fmt)
-    reqs = TR._geometry(rig)
+    reqs = G.geometry(rig)
     reqs = [reqs[i] for i in np.random.RandomState(3).permutation(len(reqs))]
     bmax = rig.budget(reqs)
     rd = m.BlockReader(ctx, rig.fmt, B4, rig.n, rig.nbt, len(reqs), bmax)
@@ -618,7 +614,7 @@ def test_block_reader(oracle, ctx, sources, fmt):
 
     def run():
         mo, ms, mc = rig.check(oracle, reqs, blocks_max=bmax, crc=True, reader=rd, d_out=d_out)
-        assert ms == [0] * len(reqs) and mo == TR._slices(rig, reqs)
+        assert ms == [0] * len(reqs) and mo == G.slices(rig, reqs)
         return np.array(ms), np.array(list(mc)), np.frombuffer(b"".join(mo), np.uint8)
 
     def run_damaged():
@@ -633,18 +629,15 @@ def test_block_reader(oracle, ctx, sources, fmt):
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_block_writer_write_and_resize(oracle, ctx, sources, fmt):
     import ms_compress_amd as m
-    import test_gpu_read as TR
-    import test_gpu_write as TW
-    import test_gpu_resize as TZ
     rig = sources("read", fmt)
-    ws = TW.Writes(rig)
-    B, L = B4, rig.lens[TR.MIXED]
-    reqs = [(TR.MIXED, 0, 10), (TR.MIXED, B // 2, 100), (TR.MIXED, B - 3, 10), (TR.MIXED5, B - 1, B + 2), (TR.MIXED, L - 1, 1), (TR.TEXT, B, B),
-            (TR.ZEROS5, 0, TR.ALL), (TR.TEXT, 2 * B + 5, TR.ALL), (TR.RANDOM1, 0, B), (TR.MIXED5, 3 * B, B)]
-    srcs = TW._sources(rig, reqs, 21, [1, 2, 1, 2, 1, 1, 2, 0, 0, 1])
+    ws = G.Writes(rig)
+    B, L = B4, rig.lens[G.MIXED]
+    reqs = [(G.MIXED, 0, 10), (G.MIXED, B // 2, 100), (G.MIXED, B - 3, 10), (G.MIXED5, B - 1, B + 2), (G.MIXED, L - 1, 1), (G.TEXT, B, B),
+            (G.ZEROS5, 0, G.ALL), (G.TEXT, 2 * B + 5, G.ALL), (G.RANDOM1, 0, B), (G.MIXED5, 3 * B, B)]
+    srcs = G.sources(rig, reqs, 21, [1, 2, 1, 2, 1, 1, 2, 0, 0, 1])
     bmax = rig.budget(reqs)
     wr = m.BlockWriter(ctx, rig.fmt, B, rig.n, rig.nbt, len(reqs), bmax)
-    at = TR._flip(oracle, rig, int(rig.first[TR.MIXED]) + 1, B, False)     # a broken stream in the compressed block: refused with and without checksums
+    at = G.flip(oracle, rig, int(rig.first[G.MIXED]) + 1, B, False)     # a broken stream in the compressed block: refused with and without checksums
     hurt = bytearray(rig.packed); hurt[at] ^= 0x01
     d_hurt = rig.d_packed.clone(); d_hurt[at] = int(hurt[at])
 
@@ -661,19 +654,19 @@ def test_block_writer_write_and_resize(oracle, ctx, sources, fmt):
     claims = tuple(sorted(set(CLAIMS[("compress", f)] + CLAIMS[("decode", f)]) - {"dz_scr"}))
     cycle(ctx, [run, run_damaged], claims, [(wr, True)])
     wr.close()
-    # resize, on a writer of its own: a table of SPARE more rows, no requests, TZ.BUDGET blocks
-    zs = TZ.Resizes.__new__(TZ.Resizes)                               # (Resizes without its second container: only run / check are used)
+    # resize, on a writer of its own: a table of SPARE more rows, no requests, G.BUDGET blocks
+    zs = G.Resizes.__new__(G.Resizes)                               # (Resizes without its second container: only run / check are used)
     zs.rig = rig
     nb = int(rig.first[-1])
-    zs.nbt = nb + TZ.SPARE
-    zs.off = np.concatenate([rig.off[: nb + 1], np.full(TZ.SPARE, rig.off[nb], dtype=np.uint64)])
-    zs.crc = np.concatenate([rig.crc[:nb], np.zeros(TZ.SPARE, dtype=np.uint32)])
-    zs.d_boff, zs.d_crc = _d64(zs.off, rig.dev), TZ._i32(zs.crc, rig.dev)
-    zs.room = rig.total + TZ.BUDGET * B
+    zs.nbt = nb + G.SPARE
+    zs.off = np.concatenate([rig.off[: nb + 1], np.full(G.SPARE, rig.off[nb], dtype=np.uint64)])
+    zs.crc = np.concatenate([rig.crc[:nb], np.zeros(G.SPARE, dtype=np.uint32)])
+    zs.d_boff, zs.d_crc = G.d64(zs.off, rig.dev), G.i32(zs.crc, rig.dev)
+    zs.room = rig.total + G.BUDGET * B
     want = list(rig.lens)
-    want[TR.MIXED] = B + 100; want[TR.TEXT] = rig.lens[TR.TEXT] + 2 * B + 9; want[TR.ZEROS5] = 0; want[TR.RANDOM1] = B // 2
-    wz = m.BlockWriter(ctx, rig.fmt, B, rig.n, zs.nbt, 0, TZ.BUDGET)
-    bad = zs.off.copy(); j = int(rig.first[TR.MIXED]); bad[j + 2] = bad[j + 1] - np.uint64(1)
+    want[G.MIXED] = B + 100; want[G.TEXT] = rig.lens[G.TEXT] + 2 * B + 9; want[G.ZEROS5] = 0; want[G.RANDOM1] = B // 2
+    wz = m.BlockWriter(ctx, rig.fmt, B, rig.n, zs.nbt, 0, G.BUDGET)
+    bad = zs.off.copy(); j = int(rig.first[G.MIXED]); bad[j + 2] = bad[j + 1] - np.uint64(1)
 
     def run_resize():
         mo, got = zs.check(oracle, want, read_back=False, writer=wz)
@@ -690,15 +683,14 @@ def test_block_writer_write_and_resize(oracle, ctx, sources, fmt):
 
 def test_block_splicer_by_picks_and_by_extents(ctx, sources):
     import ms_compress_amd as m
-    import test_gpu_splice as TS
     import extents_model as X
-    from test_extents_model import healthy_lists
-    from test_splice_model import pick_lists
+    from extents_model import healthy_lists
+    from splice_model import pick_lists
     zs = sources("splice", "lznt1")
     picks = pick_lists(zs.rig[0].n)[2]                             # by turns from the second container and the first
     nbt = zs.table_for(picks)
     sp = m.BlockSplicer(ctx, B4, 2, len(picks), nbt)
-    hurt = [TS.Src(zs.rig[0], off=_falling(zs.rig[0])), zs.src[1]]
+    hurt = [zs.rig[0].edited(off=_falling(zs.rig[0])), zs.src[1]]
 
     def run():
         mo, got = zs.check(picks, nbt, splicer=sp)
@@ -714,7 +706,7 @@ def test_block_splicer_by_picks_and_by_extents(ctx, sources):
     ef, ext = X.flat(resources)
     nbt = xs.table_for(resources)
     sx = m.BlockSplicer.for_extents(ctx, B4, 2, len(resources), len(ext), nbt)
-    hurt_x = [TS.Src(xs.rig[0], off=_falling(xs.rig[0])), xs.src[1]]
+    hurt_x = [xs.rig[0].edited(off=_falling(xs.rig[0])), xs.src[1]]
 
     def run_extents(srcs):
         got = xs.run(sx, srcs, ef, ext, xs.outputs(len(resources), nbt), xs.room)
@@ -727,21 +719,19 @@ def test_block_splicer_by_picks_and_by_extents(ctx, sources):
 
 def test_block_deduper(ctx, sources):
     import ms_compress_amd as m
-    import test_gpu_dedup as TD
-    import test_gpu_splice as TS
     zs = sources("splice", "lznt1")
-    n, rows = sum(s.n_res for s in zs.src), sum(s.nbt for s in zs.src)
+    n, rows = sum(s.n for s in zs.src), sum(s.nbt for s in zs.src)
     dd = m.BlockDeduper(ctx, B4, 2, n, rows)
-    outs = TD.Outs(zs.dev, n)
-    hurt = [TS.Src(zs.rig[0], off=_falling(zs.rig[0])), zs.src[1]]
+    outs = G.dedup_outs(zs.dev, n)
+    hurt = [zs.rig[0].edited(off=_falling(zs.rig[0])), zs.src[1]]
 
     def run():
-        mo, _ = TD.check_dedup(zs, zs.src, deduper=dd, outs=outs)
+        mo, _ = G.check_dedup(zs, zs.src, deduper=dd, outs=outs)
         assert mo["status"] == [0] * n and mo["count"][0] == zs.rig[0].n - 1
         return _flat(mo)
 
     def run_damaged():
-        return _flat(TD.check_dedup(zs, hurt, deduper=dd, outs=outs)[0])
+        return _flat(G.check_dedup(zs, hurt, deduper=dd, outs=outs)[0])
     cycle(ctx, [run, run_damaged], (), [(dd, True)])
     dd.close()
 

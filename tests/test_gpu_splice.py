@@ -1,6 +1,6 @@
 """GPU: mscomp_amd_splicer_splice against the model of tests/splice_model.py -- the whole new packed buffer and every entry of the three new
 tables, the checksums, the lengths and the statuses compared with sentinel images (so a byte at or behind new_cap, or behind the
-container's end, fails) -- on two containers of tests/test_gpu_read.Rig that hold the same buffers in two orders; where the sources are
+container's end, fails) -- on two containers of tests/blocks_rig.Container that hold the same buffers in two orders; where the sources are
 healthy also byte for byte against BlockContainer.compress + .crc of the picked data."""
 import zlib
 
@@ -10,132 +10,15 @@ import pytest
 import blocks_model as M
 import read_model as R
 import splice_model as S
-from test_gpu_read import Rig, _d64, FMTS, BLOCKS, FILL, ALL, MIXED, TEXT, ZEROS5
-from test_splice_model import ORDER2, pick_lists
+from blocks_rig import Container, Splices, d64, memo, FMTS, BLOCKS, FILL, ST_FILL, ALL, MIXED, TEXT, ZEROS5
+from splice_model import ORDER2, pick_lists
 
 pytestmark = pytest.mark.gpu
 
 
-class Src:
-    """one source of a splice: the container of a Rig, some of its tables edited on the host"""
-
-    def __init__(self, rig, first=None, off=None, lens=None, packed=None, crc=True, n_res=None, nbt=None):
-        dev = rig.dev
-        self.first, self.off, self.lens = rig.first if first is None else first, rig.off if off is None else off, rig.lens if lens is None else lens
-        self.packed, self.plen, self.crc = rig.packed if packed is None else packed, rig.plen, rig.crc
-        self.n_res, self.nbt = rig.n if n_res is None else n_res, rig.nbt if nbt is None else nbt
-        d_packed = rig.d_packed
-        if packed is not None:
-            import torch
-            d_packed = rig.d_packed.clone()
-            d_packed[: rig.plen] = torch.from_numpy(np.frombuffer(packed, dtype=np.uint8).copy()).to(dev)
-        self.dev_tuple = (d_packed, rig.d_first if first is None else _d64(first, dev), rig.d_boff if off is None else _d64(off, dev),
-                          rig.d_len if lens is None else _d64(lens, dev), rig.d_crc if crc else None, rig.plen, self.n_res, self.nbt)
-
-    def model(self):
-        return (self.packed, self.plen, self.first, self.off, self.lens, self.crc, self.n_res, self.nbt)
-
-
-class Splices:
-    """splice calls against two Rigs: rig[0] holds R.buffers(B), rig[1] the same buffers in the order ORDER2"""
-
-    def __init__(self, ctx, fmt, B, bufs0=None, bufs1=None):
-        base = R.buffers(B)
-        self.rig = [Rig(ctx, fmt, B, bufs0 or base), Rig(ctx, fmt, B, bufs1 or [base[i] for i in ORDER2])]
-        self.m, self.ctx, self.fmt, self.B, self.dev = self.rig[0].m, ctx, fmt, B, self.rig[0].dev
-        self.room = 2 * max(r.total for r in self.rig) + 3 * B
-        self.src = [Src(r) for r in self.rig]
-
-    def outputs(self, npk, nbt):
-        import torch
-        dev = self.dev
-        return (torch.full((self.room + 64,), FILL, dtype=torch.uint8, device=dev), torch.full((npk + 1,), -1, dtype=torch.int64, device=dev),
-                torch.full((nbt + 1,), -1, dtype=torch.int64, device=dev), torch.full((max(1, nbt),), 0x55555555, dtype=torch.int32, device=dev),
-                torch.full((max(1, npk),), -1, dtype=torch.int64, device=dev), torch.full((max(1, npk),), 77, dtype=torch.int32, device=dev))
-
-    def pull(self, outs):
-        d_new, d_first, d_off, d_crc, d_len, d_st = outs
-        self.ctx.stream.synchronize()
-        return {"d": outs, "image": d_new.cpu().numpy(), "first": d_first.cpu().numpy().view(np.uint64), "off": d_off.cpu().numpy().view(np.uint64),
-                "crc": d_crc.cpu().numpy().view(np.uint32), "new_len": [int(x) for x in d_len.cpu().numpy().view(np.uint64)],
-                "status": [int(x) for x in d_st.cpu().numpy()]}
-
-    def compare(self, got, mo, npk, nbt, crc=True):
-        """everything the call wrote, and everything it must not have written, against the model"""
-        assert got["status"] == (mo["status"] if npk else [77]), ("statuses", got["status"], mo["status"])
-        assert got["new_len"] == (mo["new_len"] if npk else [M.M64]), ("lengths", got["new_len"], mo["new_len"])
-        assert (got["first"] == mo["first"]).all(), ("first", got["first"], mo["first"])
-        assert (got["off"] == mo["off"]).all(), ("offsets", got["off"], mo["off"])
-        want = mo["crc"] if crc and nbt else np.full(max(1, nbt), 0x55555555, dtype=np.uint32)
-        assert (got["crc"] == want).all(), ("checksums", np.nonzero(got["crc"] != want)[0])
-        image = np.full(len(got["image"]), FILL, dtype=np.uint8)
-        image[: len(mo["packed"])] = np.frombuffer(mo["packed"], dtype=np.uint8)
-        bad = np.nonzero(got["image"] != image)[0]
-        assert bad.size == 0, ("new packed bytes differ from the model at", int(bad[0]), "of", len(mo["packed"]))
-
-    def check(self, picks, nbt, srcs=None, cap=None, crc=True, splicer=None):
-        """run, and compare with the model; returns (model, outputs)"""
-        srcs = self.src if srcs is None else srcs
-        npk = len(picks)
-        cap = self.room if cap is None else cap
-        outs = self.outputs(npk, nbt)
-        d_new, d_first, d_off, d_crc, d_len, d_st = outs
-        sp = splicer or self.m.BlockSplicer(self.ctx, self.B, len(srcs), npk, nbt)
-        d_pick = _d64(np.array(picks, dtype=np.uint64).reshape(-1) if picks else [0, 0], self.dev)
-        sp.splice([s.dev_tuple for s in srcs], d_pick, d_new, d_first, d_off, d_len, d_st, d_new_block_crc=d_crc if crc else None, new_cap=cap)
-        got = self.pull(outs)
-        if splicer is None:
-            sp.close()
-        mo = S.model_splice([s.model() for s in srcs], picks, self.B, nbt, cap, with_crc=crc)
-        self.compare(got, mo, npk, nbt, crc)
-        return mo, got
-
-    def data(self, picks):
-        return S.picked([r.bufs for r in self.rig], picks)
-
-    def table_for(self, picks):
-        """the rows of the container BlockContainer makes for the picked data: n_blocks_max = n + total // B"""
-        return len(picks) + sum(len(b) for b in self.data(picks)) // self.B
-
-    def check_consequence(self, got, data, nbt):
-        """the header's consequence: the new container is what compress and crc write for the picked data, whole tables included"""
-        import torch
-        dev, n = self.dev, len(data)
-        lens = [len(b) for b in data]
-        total = sum(lens)
-        bk = self.m.BlockContainer(self.ctx, self.fmt, self.B, n, total)
-        assert bk.n_blocks_max == nbt
-        d_in = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
-        d_in[:total] = torch.from_numpy(np.frombuffer(b"".join(data), dtype=np.uint8).copy()).to(dev)
-        d_off, d_len = _d64(np.cumsum([0] + lens[:-1]), dev), _d64(lens, dev)
-        d_packed = torch.full((len(got["image"]),), FILL, dtype=torch.uint8, device=dev)
-        d_first, d_boff = _d64([0] * (n + 1), dev), _d64([0] * (nbt + 1), dev)
-        d_st, d_crc = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(nbt, dtype=torch.int32, device=dev)
-        bk.compress(d_in, d_off, d_len, d_packed, d_first, d_boff, d_st, packed_cap=total)
-        bk.crc(d_in, d_off, d_len, d_crc, d_st)
-        self.ctx.stream.synchronize()
-        bk.close()
-        assert not d_st.cpu().numpy().any()
-        assert (got["first"] == d_first.cpu().numpy().view(np.uint64)).all() and (got["off"] == d_boff.cpu().numpy().view(np.uint64)).all()
-        end = int(got["off"][-1])
-        assert (got["crc"] == d_crc.cpu().numpy().view(np.uint32)).all() and (got["image"][:end] == d_packed.cpu().numpy()[:end]).all()
-
-    def close(self):
-        for r in self.rig:
-            r.close()
-
-
 @pytest.fixture(scope="module")
 def rigs(gpu_ctx):
-    made = {}
-
-    def get(fmt, B):
-        if (fmt, B) not in made:
-            made[(fmt, B)] = Splices(gpu_ctx, FMTS[fmt], B)
-        return made[(fmt, B)]
-    yield get
-    for z in made.values():
-        z.close()
+    yield from memo(lambda fmt, B: Splices(gpu_ctx, FMTS[fmt], B))
 
 
 @pytest.mark.parametrize("B", BLOCKS)
@@ -185,12 +68,12 @@ def test_rejects(rigs, fmt, B):
     falling = rig.first.copy(); falling[3] = falling[4] + np.uint64(1)
     beyond = rig.first.copy(); beyond[n] = np.uint64(rig.nbt + 1)
     for picks, src0 in (([(0, 1), (2, 0), (0, 4)], None), ([(0, 1), (0, n), (1, 4)], None), ([(0, 1), (0, 1 << 63), (0, 4)], None), ([(0, 1), (1 << 40, 1), (0, 4)], None),
-                        ([(0, 1), (0, 3), (0, 4)], Src(rig, first=falling)), ([(0, 1), (0, n - 1), (0, 4)], Src(rig, first=beyond))):
+                        ([(0, 1), (0, 3), (0, 4)], rig.edited(first=falling)), ([(0, 1), (0, n - 1), (0, 4)], rig.edited(first=beyond))):
         mo, got = zs.check(picks, 8, srcs=[src0 or zs.src[0], zs.src[1]])
         assert mo["status"] == [0, M.ARG, 0] and mo["new_len"][1] == 0 and int(got["first"][1]) == int(got["first"][2])
     # rule 2: a length that asks for one block more than the table has
     odd = list(lens); odd[MIXED] += B
-    mo, got = zs.check([(0, MIXED), (0, TEXT), (1, 0)], 12, srcs=[Src(rig, lens=odd), zs.src[1]])
+    mo, got = zs.check([(0, MIXED), (0, TEXT), (1, 0)], 12, srcs=[rig.edited(lens=odd), zs.src[1]])
     assert mo["status"] == [M.DATA, 0, 0] and mo["new_len"] == [0, lens[TEXT], lens[TEXT]] and list(got["first"]) == [0, 0, 4, 8]
     # rule 3 crossed mid-list: counts 4, 5, 4, 1, 0 against 8 rows; then a table filled to its last row
     mo, got = zs.check([(0, MIXED), (0, ZEROS5), (1, 0), (0, 1), (0, 0)], 8)
@@ -212,10 +95,10 @@ def test_rejects(rigs, fmt, B):
     assert list(got["first"]) == [0] and not got["off"].any() and not got["crc"].any()
     zs.check([], 0)
     # a view without checksums beside a non-null d_new_block_crc: refused on the host, nothing written
-    outs = zs.outputs(2, 8)
+    outs = zs.outputs(2, 8).tensors()
     sp = zs.m.BlockSplicer(zs.ctx, B, 2, 2, 8)
     with pytest.raises(zs.m.MSCompError) as e:
-        sp.splice([zs.src[0].dev_tuple, Src(zs.rig[1], crc=False).dev_tuple], _d64([0, 1, 1, 1], zs.dev), outs[0], outs[1], outs[2], outs[4], outs[5], d_new_block_crc=outs[3])
+        sp.splice([zs.src[0].view(), zs.rig[1].view(crc=False)], d64([0, 1, 1, 1], zs.dev), outs[0], outs[1], outs[2], outs[4], outs[5], d_new_block_crc=outs[3])
     assert e.value.status == zs.m.MSCOMP_ARG_ERROR
     sp.close()
     torch.cuda.synchronize()
@@ -234,12 +117,12 @@ def test_damage(rigs, fmt, B):
     falling = rig.off.copy(); falling[j + 2] = falling[j + 1] - np.uint64(1)
     past = rig.off.copy(); past[j + 4:] = np.uint64(rig.plen + 1)
     for bad, row in ((falling, 1), (past, 3)):
-        mo, got = zs.check(picks, 16, srcs=[Src(rig, off=bad), zs.src[1]])
+        mo, got = zs.check(picks, 16, srcs=[rig.edited(off=bad), zs.src[1]])
         for g in (int(got["first"][1]), int(got["first"][3])):
             assert mo["status"] == [0] * 4 and int(got["off"][g + row + 1]) == int(got["off"][g + row])
     # a flipped stored byte is carried as it is; a reader with checksums answers MSCOMP_DATA_ERROR for exactly the requests that cover it
     hurt = bytearray(rig.packed); hurt[int(rig.off[j]) + 77] ^= 0x01
-    mo, got = zs.check(picks, 16, srcs=[Src(rig, packed=bytes(hurt)), zs.src[1]])
+    mo, got = zs.check(picks, 16, srcs=[rig.edited(packed=bytes(hurt)), zs.src[1]])
     assert mo["status"] == [0] * 4
     nb = int(got["first"][-1])
     reqs = [(0, 0, ALL), (1, 0, 10), (1, B - 1, 1), (1, B, ALL), (2, 0, ALL), (3, B - 5, 10), (3, 2 * B, 40)]
@@ -279,20 +162,20 @@ def test_repeats_and_ping_pong(rigs, fmt):
     picks_a, picks_b = pick_lists(n)[2], [(s ^ 1, (r * 5 + 3) % n) for s, r in pick_lists(n)[2]]
     npk, nbt = len(picks_a), max(zs.table_for(picks_a), zs.table_for(picks_b)) + 2
     sp = zs.m.BlockSplicer(zs.ctx, B, 2, npk, nbt)
-    srcs = [s.dev_tuple for s in zs.src]
-    d_pick = _d64(np.array(picks_a, dtype=np.uint64).reshape(-1), zs.dev)
+    srcs = [s.view() for s in zs.src]
+    d_pick = d64(np.array(picks_a, dtype=np.uint64).reshape(-1), zs.dev)
     outs = [zs.outputs(npk, nbt), zs.outputs(npk, nbt)]
 
     def run(o, picks):
-        d_new, d_first, d_off, d_crc, d_len, d_st = o
-        d_new.fill_(FILL); d_first.fill_(-1); d_off.fill_(-1); d_crc.fill_(0x55555555); d_len.fill_(-1); d_st.fill_(77)
+        d_new, d_first, d_off, d_crc, d_len, d_st = o.tensors()
+        o.fill()
         sp.splice(srcs, d_pick, d_new, d_first, d_off, d_len, d_st, d_new_block_crc=d_crc, new_cap=zs.room)
         mo = S.model_splice([s.model() for s in zs.src], picks, B, nbt, zs.room)
         assert mo["status"] == [0] * npk
         zs.compare(zs.pull(o), mo, npk, nbt)
     for _ in range(3):
         run(outs[0], picks_a)
-    d_pick.copy_(_d64(np.array(picks_b, dtype=np.uint64).reshape(-1), zs.dev))
+    d_pick.copy_(d64(np.array(picks_b, dtype=np.uint64).reshape(-1), zs.dev))
     for _ in range(2):
         run(outs[0], picks_b)
     for o in (outs[1], outs[1], outs[0]):
@@ -311,7 +194,7 @@ def test_compress_crc_splice_read_in_one_captured_graph(oracle, fmt):
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        rig = Rig(ctx, f, B, base)
+        rig = Container.make(ctx, f, B, base)
         dev, n = rig.dev, rig.n
         picks = [(0, MIXED), (0, 0), (0, TEXT), (0, MIXED), (0, ZEROS5), (0, 1)]
         npk = len(picks)
@@ -319,7 +202,7 @@ def test_compress_crc_splice_read_in_one_captured_graph(oracle, fmt):
         room = sum(lens)
         nbt = npk + room // B
         sp = m.BlockSplicer(ctx, B, 1, npk, nbt)
-        d_pick = _d64(np.array(picks, dtype=np.uint64).reshape(-1), dev)
+        d_pick = d64(np.array(picks, dtype=np.uint64).reshape(-1), dev)
         d_new = torch.empty(room + 64, dtype=torch.uint8, device=dev)
         d_nfirst, d_noff = torch.zeros(npk + 1, dtype=torch.int64, device=dev), torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
         d_ncrc, d_nlen = torch.zeros(nbt, dtype=torch.int32, device=dev), torch.zeros(npk, dtype=torch.int64, device=dev)
@@ -328,7 +211,7 @@ def test_compress_crc_splice_read_in_one_captured_graph(oracle, fmt):
         caps = [30, lens[2], 17, lens[4], 1]
         ooff, oroom = rig.layout(caps)
         rd = m.BlockReader(ctx, f, B, npk, nbt, len(reads), 16)
-        d_rreq, d_ooff, d_ocap = _d64(np.array(reads, dtype=np.uint64).reshape(-1), dev), _d64(ooff, dev), _d64(caps, dev)
+        d_rreq, d_ooff, d_ocap = d64(np.array(reads, dtype=np.uint64).reshape(-1), dev), d64(ooff, dev), d64(caps, dev)
         d_olen, d_ost = torch.zeros(len(reads), dtype=torch.int64, device=dev), torch.zeros(len(reads), dtype=torch.int32, device=dev)
         d_out = torch.empty(oroom, dtype=torch.uint8, device=dev)
         src = (rig.d_packed, rig.d_first, rig.d_boff, rig.d_len, rig.d_crc, rig.total, n, rig.nbt)
@@ -372,7 +255,7 @@ def test_res_crc_of_a_spliced_container(rigs, fmt, B):
     mo, got = zs.check(picks, nbt)
     d_new, d_first, d_off, d_crc, d_len, d_st = got["d"]
     d_rcrc = torch.full((npk,), 0x33333333, dtype=torch.int32, device=zs.dev)
-    d_rst = torch.full((npk,), 77, dtype=torch.int32, device=zs.dev)
+    d_rst = torch.full((npk,), ST_FILL, dtype=torch.int32, device=zs.dev)
     zs.m.res_crc_dev(zs.ctx, B, npk, nbt, d_first, d_len, d_crc, d_rcrc, d_rst)
     zs.ctx.stream.synchronize()
     assert not d_rst.cpu().numpy().any()

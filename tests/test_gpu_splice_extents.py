@@ -1,6 +1,6 @@
 """GPU: mscomp_amd_splicer_splice_extents against the model of tests/extents_model.py -- the whole new packed buffer and every entry of the
 three new tables, the checksums, the lengths and the statuses compared with sentinel images, as tests/test_gpu_splice.py does for picks --
-on two containers of tests/test_gpu_read.Rig: the buffers of tests/test_extents_model.py (the lengths 0, 1, B - 1, B, B + 1, 3 B, 3 B + 5,
+on two containers of tests/blocks_rig.Container: the buffers of tests/extents_model.py (the lengths 0, 1, B - 1, B, B + 1, 3 B, 3 B + 5,
 3 B + 17 and 5 B) and the same reversed. Where the sources are healthy also byte for byte against BlockContainer.compress + .crc of the
 concatenated extent data."""
 import zlib
@@ -10,62 +10,17 @@ import pytest
 
 import blocks_model as M
 import extents_model as X
-from test_extents_model import buffers, healthy_lists, in1, ONE, BP1, MIXED, ZEROS5, TEXT, X3B, X3B5
-from test_gpu_read import Rig, _d64, FMTS, BLOCKS, FILL, ALL
-from test_gpu_splice import Splices, Src
+from blocks_rig import Container, Extents, Splices, d64, memo, FMTS, BLOCKS, FILL, ST_FILL, ALL
+from extents_model import buffers, healthy_lists, in1, ONE, BP1, MIXED, ZEROS5, TEXT, X3B, X3B5
 
 pytestmark = pytest.mark.gpu
 HEALTHY = [(0, TEXT, 1, 2)]                                     # beside every refused resource: two blocks that must come through
 HEALTHY_F = [(1, 0, 0, 2)]                                      # the same for the `filler` containers
 
 
-class Extents(Splices):
-    """splice_extents calls against two Rigs: rig[0] holds buffers(B), rig[1] the same reversed"""
-
-    def __init__(self, ctx, fmt, B, bufs0=None, bufs1=None):
-        base = buffers(B)
-        Splices.__init__(self, ctx, fmt, B, bufs0 or base, bufs1 or base[::-1])
-
-    def run(self, sp, srcs, ext_first, ext, outs, cap, crc=True):
-        d_new, d_first, d_off, d_crc, d_len, d_st = outs
-        d_ext = _d64(np.array(ext, dtype=np.uint64).reshape(-1) if ext else [0, 0, 0, 0], self.dev)
-        sp.splice_extents([s.dev_tuple for s in srcs], _d64(ext_first, self.dev), d_ext, d_new, d_first, d_off, d_len, d_st,
-                          d_new_block_crc=d_crc if crc else None, new_cap=cap)
-        return self.pull(outs)
-
-    def check(self, resources, nbt, srcs=None, cap=None, crc=True, ext_first=None, n_ext=None):
-        """run, and compare with the model; returns (model, outputs)"""
-        srcs = self.src if srcs is None else srcs
-        ef, ext = X.flat(resources)
-        ef = ef if ext_first is None else ext_first
-        n_res, n_ext = len(resources), len(ext) if n_ext is None else n_ext
-        cap = self.room if cap is None else cap
-        sp = self.m.BlockSplicer.for_extents(self.ctx, self.B, len(srcs), n_res, n_ext, nbt)
-        got = self.run(sp, srcs, ef, ext, self.outputs(n_res, nbt), cap, crc)
-        sp.close()
-        mo = X.model_splice_extents([s.model() for s in srcs], ef, ext, self.B, n_ext, nbt, cap, with_crc=crc)
-        self.compare(got, mo, n_res, nbt, crc)
-        return mo, got
-
-    def data(self, resources):
-        return X.extent_data([r.bufs for r in self.rig], resources, self.B)
-
-    def table_for(self, resources):
-        """the rows of the container BlockContainer makes for the extent data: n_blocks_max = n + total // B"""
-        return len(resources) + sum(len(b) for b in self.data(resources)) // self.B
-
-
 @pytest.fixture(scope="module")
 def rigs(gpu_ctx):
-    made = {}
-
-    def get(fmt, B):
-        if (fmt, B) not in made:
-            made[(fmt, B)] = Extents(gpu_ctx, FMTS[fmt], B)
-        return made[(fmt, B)]
-    yield get
-    for z in made.values():
-        z.close()
+    yield from memo(lambda fmt, B: Extents(gpu_ctx, FMTS[fmt], B))
 
 
 @pytest.mark.parametrize("B", BLOCKS)
@@ -117,7 +72,7 @@ def test_rejects(rigs, fmt, B):
     # rule 1 from a broken source table, rule 2 from a wrong length
     falling = rig.first.copy(); falling[3] = falling[4] + np.uint64(1)
     odd = list(rig.lens); odd[MIXED] += B
-    for src0, bad, st in ((Src(rig, first=falling), (0, 3, 0, None), M.ARG), (Src(rig, lens=odd), (0, MIXED, 0, 1), M.DATA)):
+    for src0, bad, st in ((rig.edited(first=falling), (0, 3, 0, None), M.ARG), (rig.edited(lens=odd), (0, MIXED, 0, 1), M.DATA)):
         mo, got = zs.check([[(0, X3B, 0, 1), bad], HEALTHY], 8, srcs=[src0, zs.src[1]])
         assert mo["status"] == [st, 0] and mo["new_len"] == [0, two] and list(got["first"]) == [0, 0, 2]
     # rule 4: a B + 1 resource in front of another extent, and as the last one
@@ -144,7 +99,7 @@ def test_rejects(rigs, fmt, B):
     # a damaged off entry is an empty row
     j = int(rig.first[TEXT])
     hurt = rig.off.copy(); hurt[j + 2] = hurt[j + 1] - np.uint64(1)
-    mo, got = zs.check([HEALTHY, [(0, TEXT, 0, None)]], 8, srcs=[Src(rig, off=hurt), zs.src[1]])
+    mo, got = zs.check([HEALTHY, [(0, TEXT, 0, None)]], 8, srcs=[rig.edited(off=hurt), zs.src[1]])
     assert mo["status"] == [0, 0] and int(got["off"][1]) == int(got["off"][0]) and int(got["off"][4]) == int(got["off"][3])
     # no resources: an empty container, all of the offset and checksum tables written
     mo, got = zs.check([], 5)
@@ -211,22 +166,22 @@ def test_repeats_and_a_changed_view(rigs, fmt):
     sp = zs.m.BlockSplicer.for_extents(zs.ctx, B, 2, n_res, n_ext, nbt)
     outs = zs.outputs(n_res, nbt)
     ef_a, ext_a = X.flat(res_a)
-    d_ef, d_ext = _d64(ef_a, zs.dev), _d64(np.array(ext_a + [(0, 0, 0, 0)] * (n_ext - len(ext_a)), dtype=np.uint64).reshape(-1), zs.dev)
+    d_ef, d_ext = d64(ef_a, zs.dev), d64(np.array(ext_a + [(0, 0, 0, 0)] * (n_ext - len(ext_a)), dtype=np.uint64).reshape(-1), zs.dev)
     j = int(zs.rig[0].first[X3B5])
     hurt = zs.rig[0].off.copy(); hurt[j + 1] = hurt[j] - np.uint64(1)
 
     def run(resources, srcs):
-        d_new, d_first, d_off, d_crc, d_len, d_st = outs
-        d_new.fill_(FILL); d_first.fill_(-1); d_off.fill_(-1); d_crc.fill_(0x55555555); d_len.fill_(-1); d_st.fill_(77)
+        d_new, d_first, d_off, d_crc, d_len, d_st = outs.tensors()
+        outs.fill()
         ef, ext = X.flat(resources)
-        d_ef.copy_(_d64(ef, zs.dev)); d_ext[: 4 * len(ext)] = _d64(np.array(ext, dtype=np.uint64).reshape(-1), zs.dev)
-        sp.splice_extents([s.dev_tuple for s in srcs], d_ef, d_ext, d_new, d_first, d_off, d_len, d_st, d_new_block_crc=d_crc, new_cap=zs.room)
+        d_ef.copy_(d64(ef, zs.dev)); d_ext[: 4 * len(ext)] = d64(np.array(ext, dtype=np.uint64).reshape(-1), zs.dev)
+        sp.splice_extents([s.view() for s in srcs], d_ef, d_ext, d_new, d_first, d_off, d_len, d_st, d_new_block_crc=d_crc, new_cap=zs.room)
         mo = X.model_splice_extents([s.model() for s in srcs], ef, ext, B, n_ext, nbt, zs.room)
         assert mo["status"] == [0] * n_res
         zs.compare(zs.pull(outs), mo, n_res, nbt)
     for resources in (res_a, res_a, res_a, res_b, res_b):
         run(resources, zs.src)
-    other = [Src(zs.rig[0], off=hurt), zs.src[1]]
+    other = [zs.rig[0].edited(off=hurt), zs.src[1]]
     for srcs in (other, other, zs.src):
         run(res_a, srcs)
     picks = [(0, X3B), (1, 0), (0, 0), (0, ONE)]                  # splice() on a splicer made for extents: n_pick = n_res
@@ -249,14 +204,14 @@ def test_compress_crc_splice_extents_read_in_one_captured_graph(oracle, fmt):
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        rig = Rig(ctx, f, B, base)
+        rig = Container.make(ctx, f, B, base)
         dev, n = rig.dev, rig.n
         n_res = len(resources)
         lens = [len(b) for b in X.extent_data([base], resources, B)]
         room = sum(lens)
         nbt = n_res + room // B
         sp = m.BlockSplicer.for_extents(ctx, B, 1, n_res, len(ext), nbt)
-        d_ef, d_ext = _d64(ef, dev), _d64(np.array(ext, dtype=np.uint64).reshape(-1), dev)
+        d_ef, d_ext = d64(ef, dev), d64(np.array(ext, dtype=np.uint64).reshape(-1), dev)
         d_new = torch.empty(room + 64, dtype=torch.uint8, device=dev)
         d_nfirst, d_noff = torch.zeros(n_res + 1, dtype=torch.int64, device=dev), torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
         d_ncrc, d_nlen = torch.zeros(nbt, dtype=torch.int32, device=dev), torch.zeros(n_res, dtype=torch.int64, device=dev)
@@ -265,7 +220,7 @@ def test_compress_crc_splice_extents_read_in_one_captured_graph(oracle, fmt):
         caps = [30, 20, lens[3], 1, 5]
         ooff, oroom = rig.layout(caps)
         rd = m.BlockReader(ctx, f, B, n_res, nbt, len(reads), 16)
-        d_rreq, d_ooff, d_ocap = _d64(np.array(reads, dtype=np.uint64).reshape(-1), dev), _d64(ooff, dev), _d64(caps, dev)
+        d_rreq, d_ooff, d_ocap = d64(np.array(reads, dtype=np.uint64).reshape(-1), dev), d64(ooff, dev), d64(caps, dev)
         d_olen, d_ost = torch.zeros(len(reads), dtype=torch.int64, device=dev), torch.zeros(len(reads), dtype=torch.int32, device=dev)
         d_out = torch.empty(oroom, dtype=torch.uint8, device=dev)
         src = (rig.d_packed, rig.d_first, rig.d_boff, rig.d_len, rig.d_crc, rig.total, n, rig.nbt)
@@ -310,7 +265,7 @@ def test_res_crc_of_an_extent_container(rigs, fmt, B):
     mo, got = zs.check(resources, nbt)
     d_new, d_first, d_off, d_crc, d_len, d_st = got["d"]
     d_rcrc = torch.full((n_res,), 0x33333333, dtype=torch.int32, device=zs.dev)
-    d_rst = torch.full((n_res,), 77, dtype=torch.int32, device=zs.dev)
+    d_rst = torch.full((n_res,), ST_FILL, dtype=torch.int32, device=zs.dev)
     zs.m.res_crc_dev(zs.ctx, B, n_res, nbt, d_first, d_len, d_crc, d_rcrc, d_rst)
     zs.ctx.stream.synchronize()
     assert not d_rst.cpu().numpy().any()

@@ -7,24 +7,10 @@ import pytest
 import blocks_model as M
 import thresholds as T
 import transcode_model as X
+from blocks_rig import NewContainer, d64, d8, i32, mixed, rand, text
 
 pytestmark = pytest.mark.gpu
 LZNT1, XPRESS, XHUFF = 2, 3, 4
-FILL = 0xA5
-
-
-def text(seed, n):
-    return M._text(np.random.RandomState(seed), n)
-
-
-def rand(seed, n):
-    return np.random.RandomState(seed).bytes(n)
-
-
-def mixed(seed, n, B=4096, period=2):
-    """blocks of B bytes by turns random and text (every period-th one random)"""
-    rs = np.random.RandomState(seed)
-    return b"".join(rs.bytes(min(B, n - at)) if (at // B) % period == 0 else M._text(rs, min(B, n - at)) for at in range(0, n, B))
 
 
 def threshold_chunks(count):
@@ -43,20 +29,6 @@ class Source:
         self.fmt, self.B, self.bufs, self.lens = fmt, B, list(bufs), [len(b) for b in bufs]
         self.packed, self.first, self.off, self.crc = X.fresh(oracle, fmt, self.bufs, B, with_crc)
         self.nbt = len(self.off) - 1
-
-
-def d64(a, dev, least=1):
-    import torch
-    h = np.zeros(max(least, len(a)), dtype=np.uint64)
-    h[: len(a)] = np.asarray(a, dtype=np.uint64)
-    return torch.from_numpy(h.view(np.int64)).to(dev)
-
-
-def d8(b, dev):
-    import torch
-    h = np.zeros(len(b) + 16, dtype=np.uint8)
-    h[: len(b)] = np.frombuffer(bytes(b), dtype=np.uint8)
-    return torch.from_numpy(h).to(dev)
 
 
 class Case:
@@ -92,27 +64,21 @@ class Run(Case):
         with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
             self.tc = m.BlockTranscoder(ctx, src.fmt, src.B, f2, B2, self.n, src.nbt, self.nbn, self.gmax)
             self.d_packed, self.d_first, self.d_off, self.d_len = d8(self.packed, dev), d64(self.first, dev), d64(src.off, dev), d64(self.lens, dev)
-            self.d_crc = None if self.crc is None else torch.from_numpy(np.concatenate([self.crc, np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
-            self.room = sum(src.lens) + 64
-            self.d_new = torch.empty(self.room, dtype=torch.uint8, device=dev)
-            self.d_nfirst = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
-            self.d_noff = torch.empty(self.nbn + 1, dtype=torch.int64, device=dev)
-            self.d_ncrc = None if self.crc is None else torch.empty(max(1, self.nbn), dtype=torch.int32, device=dev)
-            self.d_st = torch.empty(max(1, self.n), dtype=torch.int32, device=dev)
+            self.d_crc = None if self.crc is None else i32(np.concatenate([self.crc, np.zeros(1, np.uint32)]), dev)
+            self.out = NewContainer(dev, self.n, self.nbn, sum(src.lens), crc=self.crc is not None, lens=False, fill=-77)
 
     def launch(self):
-        self.tc.transcode(self.d_packed, self.d_first, self.d_off, self.d_len, self.d_new, self.d_nfirst, self.d_noff, self.d_st, d_block_crc=self.d_crc,
-                          d_new_block_crc=self.d_ncrc, packed_len=len(self.packed), new_cap=self.cap)
+        d_new, d_nfirst, d_noff, d_ncrc, _, d_st = self.out.tensors()
+        self.tc.transcode(self.d_packed, self.d_first, self.d_off, self.d_len, d_new, d_nfirst, d_noff, d_st, d_block_crc=self.d_crc,
+                          d_new_block_crc=d_ncrc, packed_len=len(self.packed), new_cap=self.cap)
 
     def poison(self):
-        for t in (self.d_new, self.d_nfirst, self.d_noff, self.d_st) + (() if self.d_ncrc is None else (self.d_ncrc,)):
-            t.fill_(FILL if t.dtype.itemsize == 1 else -77)
+        self.out.fill()
 
     def fetch(self):
+        """everything the call wrote, whole (NewContainer.pull): the status and checksum arrays have one entry at least"""
         self.ctx.stream.synchronize()
-        return dict(image=self.d_new.cpu().numpy(), first=self.d_nfirst.cpu().numpy().view(np.uint64), off=self.d_noff.cpu().numpy().view(np.uint64),
-                    crc=None if self.d_ncrc is None else self.d_ncrc.cpu().numpy().view(np.uint32)[: self.nbn],
-                    status=[int(x) for x in self.d_st.cpu().numpy()[: self.n]])
+        return self.out.pull()
 
     def go(self):
         import torch
@@ -128,17 +94,11 @@ class Run(Case):
 
 
 def same(got, want):
-    """everything the call wrote against the model's tuple; nothing behind the bytes that were written"""
+    """everything the call wrote against the model's tuple, sentinels and the whole image included (NewContainer.compare)"""
     packed, first, off, crc, status, counts = want
-    assert got["status"] == [int(s) for s in status]
-    assert (got["first"] == first).all()
-    assert (got["off"] == off).all()
-    if crc is not None:
-        assert (got["crc"] == crc).all()
+    NewContainer.compare(got, dict(packed=packed, first=first, off=off, crc=crc, status=status), "transcoded", len(status), len(off) - 1,
+                         crc=crc is not None, fills=(-77, -77, -77))
     assert got["counts"] == counts
-    assert bytes(got["image"][: len(packed)]) == packed
-    total = int(off[-1])
-    assert (got["image"][max(len(packed), total):] == FILL).all()
 
 
 def check(ctx, oracle, src, f2, B2, with_crc=True, **kw):
@@ -148,6 +108,7 @@ def check(ctx, oracle, src, f2, B2, with_crc=True, **kw):
     got, want = run.go(), run.model(oracle)
     run.close()
     same(got, want)
+    got["status"] = got["status"][: run.n]                          # (without resources the one entry still holds its fill: compared above)
     if run.n and got["status"] == [0] * run.n and not kw:
         packed, first, off, crc = X.fresh(oracle, f2, src.bufs, B2, with_crc)
         nb = int(first[-1])

@@ -8,117 +8,15 @@ import pytest
 import blocks_model as M
 import read_model as R
 import write_model as W
-from test_gpu_read import Rig, _d64, _flip, FMTS, BLOCKS, FILL, ALL, MIXED, TEXT, ZEROS5, MIXED5, RANDOM1
+from blocks_rig import Container, Writes, d64, flip, long_runs, memo, sources, FMTS, BLOCKS, FILL, ALL, MIXED, TEXT, ZEROS5, MIXED5, RANDOM1
 
 pytestmark = pytest.mark.gpu
 ONE, EMPTY = 1, 0                                               # rows of R.RECIPES: the 1-byte resource, an empty one
 
 
-class Writes:
-    """write batches against the container of a test_gpu_read.Rig (or against another container of the same resources: cont=)"""
-
-    def __init__(self, rig):
-        self.rig = rig
-
-    def run(self, reqs, srcs, blocks_max=None, crc=True, new_cap=None, first=None, boff=None, packed=None, packed_len=None, residues=None, writer=None,
-            cont=None):
-        import torch
-        rig = self.rig
-        dev, nq = rig.dev, max(1, len(reqs))
-        wants = rig.wants(reqs)
-        blocks_max = rig.budget(reqs) if blocks_max is None else blocks_max
-        soff, room = rig.layout(wants, residues)
-        blob = np.full(room, 0xEE, dtype=np.uint8)
-        for o, w, s in zip(soff, wants, srcs):
-            blob[o: o + w] = np.frombuffer(bytes(s[:w]), dtype=np.uint8)
-        d_src, d_soff = torch.from_numpy(blob).to(dev), _d64(soff or [0], dev)
-        d_req = _d64(np.array(reqs, dtype=np.uint64).reshape(-1) if reqs else [0, 0, 0], dev)
-        cap = rig.total if new_cap is None else new_cap
-        d_new = torch.full((rig.total + 64,), FILL, dtype=torch.uint8, device=dev)
-        d_noff = torch.full((rig.nbt + 1,), -1, dtype=torch.int64, device=dev)
-        d_ncrc = torch.full((max(1, rig.nbt),), 0x55555555, dtype=torch.int32, device=dev) if crc else None
-        d_wr = torch.full((nq,), -1, dtype=torch.int64, device=dev)
-        d_st = torch.full((nq,), 77, dtype=torch.int32, device=dev)
-        d_rst = torch.full((rig.n,), 77, dtype=torch.int32, device=dev)
-        d_packed, plen, d_boff, d_crc = cont or (rig.d_packed if packed is None else packed, rig.plen if packed_len is None else packed_len,
-                                                 rig.d_boff if boff is None else _d64(boff, dev), rig.d_crc)
-        wr = writer or rig.m.BlockWriter(rig.ctx, rig.fmt, rig.B, rig.n, rig.nbt, len(reqs), blocks_max)
-        wr.write(d_packed, rig.d_first if first is None else _d64(first, dev), d_boff, rig.d_len, d_req, d_src, d_soff, d_new, d_noff, d_wr, d_st, d_rst,
-                 d_block_crc=d_crc if crc else None, d_new_block_crc=d_ncrc, packed_len=plen, new_cap=cap)
-        counts = wr.counts()
-        if writer is None:
-            wr.close()
-        return {"d": (d_new, d_noff, d_ncrc), "image": d_new.cpu().numpy(), "off": d_noff.cpu().numpy().view(np.uint64),
-                "crc": None if d_ncrc is None else d_ncrc.cpu().numpy().view(np.uint32)[: rig.nbt],
-                "written": [int(x) for x in d_wr.cpu().numpy().view(np.uint64)[: len(reqs)]],
-                "status": [int(x) for x in d_st.cpu().numpy()[: len(reqs)]], "res_status": [int(x) for x in d_rst.cpu().numpy()], "counts": counts}
-
-    def check(self, oracle, reqs, srcs, blocks_max=None, crc=True, new_cap=None, model_cont=None, model_packed=None, **kw):
-        """run, and compare everything the call wrote with the model; returns (what the model says, what the device said)"""
-        rig = self.rig
-        blocks_max = rig.budget(reqs) if blocks_max is None else blocks_max
-        cap = rig.total if new_cap is None else new_cap
-        got = self.run(reqs, srcs, blocks_max, crc, cap, **kw)
-        packed, plen, off, bcrc = model_cont or (rig.packed if model_packed is None else model_packed,
-                                                 rig.plen if kw.get("packed_len") is None else kw["packed_len"],
-                                                 rig.off if kw.get("boff") is None else kw["boff"], rig.crc)
-        mo = W.model_write(oracle, rig.fmt, packed, plen, rig.first if kw.get("first") is None else kw["first"], off, rig.lens, rig.B, rig.nbt,
-                           reqs, srcs, blocks_max, cap, bcrc if crc else None)
-        for key in ("status", "written", "res_status", "counts"):
-            assert got[key] == mo[key], (key, got[key], mo[key])
-        assert (got["off"] == mo["off"]).all(), ("offsets", got["off"], mo["off"])
-        if crc:
-            assert (got["crc"] == mo["crc"]).all(), ("checksums", np.nonzero(got["crc"] != mo["crc"])[0])
-        image = np.full(len(got["image"]), FILL, dtype=np.uint8)
-        image[: len(mo["packed"])] = np.frombuffer(mo["packed"], dtype=np.uint8)
-        bad = np.nonzero(got["image"] != image)[0]
-        assert bad.size == 0, ("new packed bytes differ from the model at", int(bad[0]), "of", len(mo["packed"]))
-        return mo, got
-
-    def fresh(self, bufs):
-        """BlockContainer.compress + .crc of other bytes of the same lengths, in tensors of their own: (packed, off, crc) on the host"""
-        import torch
-        rig = self.rig
-        dev = rig.dev
-        blob = np.frombuffer(b"".join(bufs), dtype=np.uint8)
-        d_in = torch.zeros(rig.total + 64, dtype=torch.uint8, device=dev)
-        d_in[: len(blob)] = torch.from_numpy(blob.copy()).to(dev)
-        d_off = _d64(np.cumsum([0] + rig.lens[:-1]), dev)
-        d_packed = torch.zeros(rig.total + 64, dtype=torch.uint8, device=dev)
-        d_first, d_boff = _d64([0] * (rig.n + 1), dev), _d64([0] * (rig.nbt + 1), dev)
-        d_st, d_crc = torch.zeros(rig.n, dtype=torch.int32, device=dev), torch.zeros(max(1, rig.nbt), dtype=torch.int32, device=dev)
-        rig.bk.compress(d_in, d_off, rig.d_len, d_packed, d_first, d_boff, d_st, packed_cap=rig.total)
-        rig.bk.crc(d_in, d_off, rig.d_len, d_crc, d_st)
-        rig.ctx.stream.synchronize()
-        off = d_boff.cpu().numpy().view(np.uint64)
-        return bytes(d_packed.cpu().numpy()[: int(off[-1])]), off, d_crc.cpu().numpy().view(np.uint32)[: rig.nbt]
-
-    def check_rule_10(self, got, reqs, srcs):
-        packed, off, crc = self.fresh(W.patched(self.rig.bufs, reqs, srcs))
-        assert (got["off"] == off).all() and bytes(got["image"][: len(packed)]) == packed
-        assert got["crc"] is None or (got["crc"] == crc).all()
-
-
 @pytest.fixture(scope="module")
 def rigs(gpu_ctx):
-    made = {}
-
-    def get(fmt, B):
-        if (fmt, B) not in made:
-            made[(fmt, B)] = Writes(Rig(gpu_ctx, FMTS[fmt], B))
-        return made[(fmt, B)]
-    yield get
-    for w in made.values():
-        w.rig.close()
-
-
-def _sources(rig, reqs, seed, kinds=None):
-    rs = np.random.RandomState(seed)
-    out = []
-    for q, w in enumerate(rig.wants(reqs)):
-        kind = kinds[q] if kinds else q % 3
-        out.append(bytes(w) if kind == 0 else rs.bytes(w) if kind == 1 else (b"written text " * (w // 13 + 1))[:w])
-    return out
+    yield from memo(lambda fmt, B: Writes(Container.make(gpu_ctx, FMTS[fmt], B, R.buffers(B))))
 
 
 @pytest.mark.parametrize("B", BLOCKS)
@@ -131,7 +29,7 @@ def test_geometry(rigs, oracle, fmt, B):
             (TEXT, 2 * B + 5, ALL), (MIXED, L + 9, 50), (MIXED, L, ALL), (TEXT, 3 * B + 3, 100), (ONE, 0, 1), (ONE, 0, ALL), (EMPTY, 0, 8), (TEXT, 9, 0),
             (RANDOM1, 0, B), (MIXED5, 3 * B, B)]
     kinds = [1, 2, 1, 2, 1, 1, 2, 0, 1, 1, 1, 1, 2, 1, 1, 0, 1]     # zeros over the raw random block, random bytes over text blocks
-    srcs = _sources(rig, reqs, 21, kinds)
+    srcs = sources(rig, reqs, 21, kinds)
     for crc in (True, False):
         mo, got = ws.check(oracle, reqs, srcs, crc=crc)
         assert mo["status"] == [0] * len(reqs) and mo["written"] == rig.wants(reqs) and mo["res_status"] == [0] * rig.n
@@ -153,7 +51,7 @@ def test_every_source_and_destination_residue(rigs, oracle, fmt, B):
                 r = (MIXED, TEXT)[(a + d + i) % 2]
                 reqs.append((r, 16 * ((a * 16 + d) * 7 % 200) + ((a + i) % 2) * B + d, ln))
                 res.append(a)
-    srcs = _sources(rig, reqs, 5, [1] * len(reqs))
+    srcs = sources(rig, reqs, 5, [1] * len(reqs))
     mo, got = ws.check(oracle, reqs, srcs, residues=res)
     assert mo["status"] == [0] * len(reqs)
     ws.check_rule_10(got, reqs, srcs)
@@ -184,14 +82,14 @@ def test_rejects(rigs, oracle, fmt, B):
     ws = rigs(fmt, B)
     rig = ws.rig
     reqs = [(MIXED, 5, 100), (rig.n, 0, 10), (TEXT, B - 1, B + 2), (ALL, 0, 1), (MIXED5, 7, 3 * B), (0, 0, 9), (TEXT, 3 * B, ALL), (RANDOM1, 1, 50)]
-    srcs = _sources(rig, [q if q[0] < rig.n else (0, 0, 0) for q in reqs], 8)
+    srcs = sources(rig, [q if q[0] < rig.n else (0, 0, 0) for q in reqs], 8)
     assert ws.check(oracle, reqs, srcs, blocks_max=64)[0]["status"] == [0, M.ARG, 0, M.ARG, 0, 0, 0, 0]
     # the budget: covering blocks 1, -, 3, -, 4, 0, 1, 1 -- the requests before the first one past it are applied, those behind it refused
     for bmax, want in ((9, [0, M.ARG, 0, M.ARG, 0, 0, 0, M.ARG]), (8, [0, M.ARG, 0, M.ARG, 0, 0, M.ARG, M.ARG]), (4, [0, M.ARG, 0, M.ARG, M.ARG, 0, M.ARG, M.ARG]),
                        (0, [M.ARG] * 5 + [0, M.ARG, M.ARG])):
         mo, got = ws.check(oracle, reqs, srcs, blocks_max=bmax)
         assert mo["status"] == want, (bmax, mo["status"])
-        packed, off, crc = ws.fresh(W.patched(rig.bufs, reqs, srcs, [s == 0 for s in want]))
+        packed, _, off, crc = rig.fresh(W.patched(rig.bufs, reqs, srcs, [s == 0 for s in want]))
         assert (got["off"] == off).all() and bytes(got["image"][: len(packed)]) == packed and (got["crc"] == crc).all()
     # a resource whose block count is wrong: its requests fail, the others are applied
     bad = rig.first.copy(); bad[MIXED + 1] -= np.uint64(1)
@@ -218,11 +116,11 @@ def test_damage(rigs, oracle, fmt, B):
     reqs = [(MIXED, 0, 10), (MIXED, B - 1, 2), (MIXED, B + 9, B - 9), (MIXED, 2 * B, 5), (TEXT, 0, ALL), (MIXED, 2 * B - 4, 8), (MIXED, 3 * B, ALL),
             (MIXED + 1, 0, 4 * B)]
     covers = [{0}, {0, 1}, {1}, {2}, set(), {1, 2}, {3}, set()]
-    srcs = _sources(rig, reqs, 13)
+    srcs = sources(rig, reqs, 13)
     hit = lambda blocks: [M.DATA if c & blocks else 0 for c in covers]
     # chosen on the CPU so that the model itself refuses: a flipped byte of the raw block and a flipped literal of the compressed one show
     # with checksums only, a broken stream always
-    for at, blocks, always in ((int(rig.off[j]) + 77, {0}, False), (_flip(oracle, rig, j + 1, B, True), {1}, False), (_flip(oracle, rig, j + 1, B, False), {1}, True)):
+    for at, blocks, always in ((int(rig.off[j]) + 77, {0}, False), (flip(oracle, rig, j + 1, B, True), {1}, False), (flip(oracle, rig, j + 1, B, False), {1}, True)):
         hurt = bytearray(rig.packed); hurt[at] ^= 0x01
         d_hurt = rig.d_packed.clone(); d_hurt[at] = int(hurt[at])
         for crc in (True, False):
@@ -234,7 +132,7 @@ def test_damage(rigs, oracle, fmt, B):
                 assert bytes(got["image"][int(got["off"][b]): int(got["off"][b + 1])]) == bytes(hurt[int(rig.off[b]): int(rig.off[b + 1])])
                 assert not crc or got["crc"][b] == rig.crc[b]
     # request 5 spans the compressed block 1 (damaged above) and the healthy raw block 2: with 3 refused too, block 2 stays clean
-    hurt = bytearray(rig.packed); at = _flip(oracle, rig, j + 1, B, False); hurt[at] ^= 0x01
+    hurt = bytearray(rig.packed); at = flip(oracle, rig, j + 1, B, False); hurt[at] ^= 0x01
     d_hurt = rig.d_packed.clone(); d_hurt[at] = int(hurt[at])
     few = [reqs[5], reqs[0]]
     mo, got = ws.check(oracle, few, [srcs[5], srcs[0]], packed=d_hurt, model_packed=bytes(hurt))
@@ -253,24 +151,11 @@ def test_damage(rigs, oracle, fmt, B):
     assert (got["image"][int(full["off"][int(rig.first[-1]) - 1]):] == FILL).all()
 
 
-def long_runs_rig(ctx):
-    """(Rig, first row of the long resource) of test_gpu_splice's test_long_runs_and_slice_edges container, with its shape assertions: B = 4096,
-    Xpress, a small text resource, one of 311 blocks -- random and text by turns, then 150 blocks of zeros (hundreds of rows within one
-    4096-byte slice of the new container), then text --, a small random one"""
-    B = 4096
-    long = (M.build({"kind": "mixed", "seed": 21, "mult": 100, "add": 0}, B) + bytes(150 * B) + M.build({"kind": "text", "seed": 22, "mult": 60, "add": 17}, B))
-    small = [M.build({"kind": "text", "seed": 23, "mult": 1, "add": 5}, B), M.build({"kind": "random", "seed": 24, "mult": 0, "add": 77}, B)]
-    rig = Rig(ctx, FMTS["xpress"], B, [small[0], long, small[1]])
-    stored = np.diff(rig.off[: int(rig.first[-1]) + 1].astype(np.int64))
-    assert int(rig.first[2] - rig.first[1]) == 311 and len(set(stored.tolist())) > 20 and (stored[120:240] < 64).all()
-    return rig, int(rig.first[1])
-
-
 def test_long_runs_and_slice_edges(gpu_ctx, oracle):
-    """the move pass where its runs matter, on the container of long_runs_rig, one writer per case: (a) clean runs longer than 64 rows between
+    """the move pass where its runs matter, on the container of blocks_rig.long_runs, one writer per case: (a) clean runs longer than 64 rows between
     dirty rows, one of them among hundreds of rows that share a 4096-byte slice; (b) every row behind the first shifted by a constant that
     is no multiple of 16; (c) three raw dirty blocks in consecutive cache slots; (d) as (a), new_cap inside the long resource"""
-    rig, g = long_runs_rig(gpu_ctx)
+    rig, g = long_runs(Container, gpu_ctx)
     ws, B, LONG = Writes(rig), rig.B, 1
     stored = lambda off, j: int(off[j + 1] - off[j])
     rs = np.random.RandomState(31)
@@ -312,11 +197,11 @@ def test_repeats_and_ping_pong(rigs, oracle, fmt):
             [(ZEROS5, 1, 3 * B), (ONE, 0, 1), (TEXT, 0, 1), (MIXED, 2 * B - 1, 2), (MIXED5, 5, 5)]]
     wr = rig.m.BlockWriter(rig.ctx, rig.fmt, B, rig.n, rig.nbt, 5, 12)
     for k in (0, 0, 1, 2, 1):
-        srcs = _sources(rig, sets[k], 30 + k)
+        srcs = sources(rig, sets[k], 30 + k)
         mo, got = ws.check(oracle, sets[k], srcs, blocks_max=12, writer=wr)
         assert mo["status"] == [0] * 5
     # ping-pong
-    s0, s1 = _sources(rig, sets[0], 40), _sources(rig, sets[1], 41)
+    s0, s1 = sources(rig, sets[0], 40), sources(rig, sets[1], 41)
     mo0, got0 = ws.check(oracle, sets[0], s0, blocks_max=12, writer=wr)
     d_new, d_noff, d_ncrc = got0["d"]
     plen0 = int(mo0["off"][-1])
@@ -342,13 +227,13 @@ def test_compress_crc_write_and_read_in_one_captured_graph(oracle, fmt):
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        rig = Rig(ctx, f, B, base)
+        rig = Container.make(ctx, f, B, base)
         dev = rig.dev
         reqs = [(MIXED, B - 5, 2 * B), (TEXT, 17, 300), (MIXED5, 0, ALL), (0, 0, 5), (MIXED, 0, B), (RANDOM1, 0, ALL), (TEXT, 2 * B + 9, ALL)]
         wants = rig.wants(reqs)
         soff, sroom = rig.layout(wants)
         wr = m.BlockWriter(ctx, f, B, rig.n, rig.nbt, len(reqs), 24)
-        d_req, d_soff = _d64(np.array(reqs, dtype=np.uint64).reshape(-1), dev), _d64(soff, dev)
+        d_req, d_soff = d64(np.array(reqs, dtype=np.uint64).reshape(-1), dev), d64(soff, dev)
         d_src = torch.zeros(sroom, dtype=torch.uint8, device=dev)
         d_new = torch.empty(rig.total + 64, dtype=torch.uint8, device=dev)
         d_noff, d_ncrc = torch.zeros(rig.nbt + 1, dtype=torch.int64, device=dev), torch.zeros(max(1, rig.nbt), dtype=torch.int32, device=dev)
@@ -357,7 +242,7 @@ def test_compress_crc_write_and_read_in_one_captured_graph(oracle, fmt):
         reads = [(r, 0, ALL) for r in range(rig.n)]
         ooff, oroom = rig.layout(rig.lens)
         rd = m.BlockReader(ctx, f, B, rig.n, rig.nbt, rig.n, int(rig.first[-1]))
-        d_rreq, d_ooff, d_ocap = _d64(np.array(reads, dtype=np.uint64).reshape(-1), dev), _d64(ooff, dev), _d64(rig.lens, dev)
+        d_rreq, d_ooff, d_ocap = d64(np.array(reads, dtype=np.uint64).reshape(-1), dev), d64(ooff, dev), d64(rig.lens, dev)
         d_olen, d_ost = torch.zeros(rig.n, dtype=torch.int64, device=dev), torch.zeros(rig.n, dtype=torch.int32, device=dev)
         d_out = torch.empty(oroom, dtype=torch.uint8, device=dev)
     s.synchronize()
@@ -368,7 +253,7 @@ def test_compress_crc_write_and_read_in_one_captured_graph(oracle, fmt):
                  d_new_block_crc=d_ncrc, packed_len=rig.total, new_cap=rig.total)
         rd.read(d_new, rig.d_first, d_noff, rig.d_len, d_rreq, d_out, d_ooff, d_ocap, d_olen, d_ost, d_block_crc=d_ncrc, packed_len=rig.total)
     for k in range(2):
-        srcs = _sources(rig, reqs, 50 + k, [(q + k) % 3 for q in range(len(reqs))])
+        srcs = sources(rig, reqs, 50 + k, [(q + k) % 3 for q in range(len(reqs))])
         blob = np.zeros(sroom, dtype=np.uint8)
         for o, sb in zip(soff, srcs):
             blob[o: o + len(sb)] = np.frombuffer(sb, dtype=np.uint8)

@@ -12,8 +12,8 @@ import dedup_model as D
 import diff_model as F
 import match_model as T
 import read_model as R
-from test_dedup_model import raw_source
-from test_extents_model import source
+from dedup_model import raw_source
+from extents_model import source
 
 FOUND, SHARED, FRESH = T.FOUND, T.SHARED, T.FRESH
 

@@ -11,12 +11,10 @@ import blocks_model as M
 import read_model as R
 import resize_model as Z
 import write_model as W
+from resize_model import SPARE, WANTS, mixes
 
 FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
 MIXED, TEXT, ZEROS5, RANDOM1 = 5, 7, 6, 3                       # rows of R.RECIPES
-SPARE = 16
-WANTS = (lambda L, B: 0, lambda L, B: 1, lambda L, B: max(0, L - 1), lambda L, B: L, lambda L, B: L + 1, lambda L, B: L // B * B,
-         lambda L, B: (L + B - 1) // B * B, lambda L, B: L + B, lambda L, B: L + 2 * B + 5)
 
 
 @pytest.fixture(scope="module")
@@ -25,11 +23,6 @@ def api():
     from ms_compress_amd import api
     assert "mscomp_amd_writer_resize" in api.EXPORTS and "mscomp_amd_res_crc_dev" in api.EXPORTS
     return api
-
-
-def mixes(lens, B):
-    """nine batches of wanted lengths: every resource meets every entry of WANTS once, shrinking and growing ones side by side"""
-    return [[WANTS[(r + v) % len(WANTS)](L, B) for r, L in enumerate(lens)] for v in range(len(WANTS))]
 
 
 def table(oracle, f, B):
