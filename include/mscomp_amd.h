@@ -478,6 +478,62 @@ MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* bk, const uint8_t* d_out
                                      const uint64_t* d_block_first, const uint64_t* d_range, const uint32_t* d_block_crc,
                                      uint64_t* d_out_len, int32_t* d_status /* in and out */);
 
+/* Salvage: the container's fifth call. Decompress and check answer per resource -- one flipped byte in one block of a 50 MB resource is
+ * MSCOMP_DATA_ERROR, d_out_len = 0 and unspecified bytes for all of it, and nothing says which block is bad. Salvage decodes everything
+ * that can be decoded and gives a verdict per BLOCK, so that damage costs the damaged blocks and nothing else, and so that a second copy of
+ * the container need be looked at only where this one is bad (d_only).
+ *   Creation:     none of its own: any container serves (mscomp_amd_blocks_create).
+ *   Scratch:      none of its own either. Every column of the container's tables is a temporary of one call, and the existing ones
+ *                 suffice: 68 bytes per possible block + 28 per resource, as stated above.
+ *   Sources:      d_packed, packed_len, d_block_first, d_block_off, d_res_len, d_out, d_out_off, d_out_cap as decompress takes them;
+ *                 d_block_crc (n_blocks_max entries, may be NULL) as check takes it; d_only (n_blocks_max entries, may be NULL): a mask over
+ *                 the container's rows -- in practice the d_verdict array another salvage wrote for a copy of the same shape.
+ *   Notation:     L = d_res_len[r]; row j = d_block_first[r] + k is block k of resource r, with data length e = min(B, L - k B).
+ *   Rules:        in this order, each resource leaving the others alone:
+ *                   1. decompress's per-resource checks 1-3 with d_range = NULL (bounds: MSCOMP_ARG_ERROR; block count: MSCOMP_DATA_ERROR;
+ *                      L > d_out_cap[r]: MSCOMP_BUF_ERROR). Such a resource has d_out_len = 0 and d_bad = 0, every one of its rows that can
+ *                      be named is SKIPPED, and nothing of it is read or written.
+ *                   2. Row j of an accepted resource is judged unless d_only is given and d_only[j] == MSCOMP_AMD_BLOCK_GOOD. An unjudged
+ *                      row is SKIPPED: nothing of it is read, and its bytes in d_out are not touched.
+ *                   3. A judged row's verdict is the first that applies of TABLE (decompress's step 4 refuses the row by its table
+ *                      entries: a decreasing table, an end beyond packed_len, s > e, s = 0; the row is never read), DECODE (the decoder's
+ *                      status is not MSCOMP_OK, or its length is not e) and CRC (only with d_block_crc: the e bytes, copied or decoded,
+ *                      do not have the CRC-32 d_block_crc[j]); else GOOD.
+ *                   4. The e bytes of a GOOD row at d_out + d_out_off[r] + k B are the block's data. The e bytes of a judged bad row are
+ *                      ZERO: a failed decoder may have written inside its capacity, so the row is zero-filled after the verdict. Nothing
+ *                      is written outside [d_out_off[r], d_out_off[r] + L).
+ *                   5. Per accepted resource d_out_len[r] = L WHATEVER ITS ROWS SAY -- this is the point of the call, and it differs from
+ *                      decompress, where a bad block leaves d_out_len[r] = 0 --, d_bad[r] = its judged bad rows, and d_status[r] is
+ *                      MSCOMP_OK when d_bad[r] is 0, MSCOMP_DATA_ERROR otherwise.
+ *                   6. d_verdict: all n_blocks_max entries are written; those at and behind d_block_first[n_res], and every entry not
+ *                      named above, are SKIPPED. (Two accepted resources can name the same row only when d_block_first is damaged; the
+ *                      row then holds the verdict of either.)
+ *                   7. d_count[0..3] = rows judged, rows bad, data bytes zero-filled, accepted resources with d_bad > 0: the same from
+ *                      run to run.
+ *   Consequence:  where d_status[r] is MSCOMP_OK and d_only is NULL, the L bytes are what decompress + check write, and salvage replaces
+ *                 the two. The d_verdict arrays of a container and its copies are what mscomp_amd_deduper_repair takes.
+ *   Checksums:    as check's: over the data, read back from d_out. Without d_block_crc no row is CRC, and a raw block is never bad but
+ *                 by its table entries. A damaged CRC word and damaged data give the same verdict.
+ *   Execution:    as the container's other calls: a launch sequence fixed by the creation bounds -- the decompress table pass with the mask,
+ *                 the inner decompress plan, the raw copy, a units pass, the CRC passes (left out, as a launch-time decision, when
+ *                 d_block_crc is NULL), the verdicts, the zero-fill, the fold --, kernels only, vector stores only, no memset or copy
+ *                 node, nothing allocated, nothing read back; legal inside a capture from the first execution, a graph of its own
+ *                 otherwise. MSCOMP_ARG_ERROR for a null bk or a null required array (d_packed and d_out may be null when in_total_max
+ *                 is 0, d_block_crc and d_only always). With n_res = 0 the call returns MSCOMP_OK and writes nothing, d_count included.
+ *   Left out:     telling a damaged CRC word from damaged data; byte-granular salvage inside a block (a bad row is all zeros); repairing
+ *                 the d_block_first of a refused resource; fusing salvage, repair and splice in one call. */
+#define MSCOMP_AMD_BLOCK_GOOD    0u
+#define MSCOMP_AMD_BLOCK_TABLE   1u   /* failed a table check of decompress step 4; never read */
+#define MSCOMP_AMD_BLOCK_DECODE  2u   /* decoder status other than MSCOMP_OK, or a length other than e */
+#define MSCOMP_AMD_BLOCK_CRC     3u   /* copied or decoded to e bytes, CRC-32 differs from d_block_crc[row] */
+#define MSCOMP_AMD_BLOCK_SKIPPED 4u   /* not judged: nothing read, nothing written */
+MSCompStatus mscomp_amd_blocks_salvage(mscomp_amd_blocks* bk, const uint8_t* d_packed, uint64_t packed_len,
+                                       const uint64_t* d_block_first, const uint64_t* d_block_off, const uint64_t* d_res_len,
+                                       const uint32_t* d_block_crc /* may be NULL */, const uint32_t* d_only /* n_blocks_max, may be NULL */,
+                                       uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+                                       uint64_t* d_out_len, uint32_t* d_bad /* n_res */, uint32_t* d_verdict /* n_blocks_max */,
+                                       uint64_t* d_count /* 4 */, int32_t* d_status);
+
 /* Block readers: byte-range reads from a block container, batched. A request q = (r, off, len) asks for the bytes [off, off + len) of
  * resource r, as pread does; one call serves n_req of them, scattered over any resources in any order, and writes exactly those bytes. The
  * reader is an object of its own, sized by what one call READS: it needs no mscomp_amd_blocks object, only the tables a container wrote and
@@ -1075,6 +1131,63 @@ MSCompStatus mscomp_amd_deduper_match(mscomp_amd_deduper* dd,
                                       uint64_t* d_class                 /* 3 next->n_res: found, shared, fresh blocks of the resource */,
                                       uint64_t* d_count                 /* 6: found, shared, fresh, rows looked at, fresh stored bytes, refuted */,
                                       int32_t*  d_status                /* one per resource: the stores' back to back, then next's */);
+
+/* Repair: the deduper's fourth call. From the verdicts mscomp_amd_blocks_salvage gave for a container (the primary, src[0]) and for up to
+ * three copies of it (the mirrors: a mirror, the previous full container, the container a patch was built from), the extent list that
+ * takes every bad row of the primary from the first mirror whose row is good. A table-only call: no stored byte is read. With salvage in
+ * front and mscomp_amd_splicer_splice_extents behind, damage is found, located and mended on the device with no host between the stages.
+ *   Creation:     block_size as everywhere; n_src = 1 .. MSCOMP_AMD_SPLICE_SRC_MAX sources, the primary first; n_res = the resources of
+ *                 the answer (those of the primary); n_blocks_new bounds their rows; flags must be 0. MSCOMP_ARG_ERROR, before the context
+ *                 is used and with *dd cleared, for a null ctx or dd, a bad block_size, n_src of 0 or above 4, non-zero flags, or a count
+ *                 above 0x7FFFFFF0. A deduper made here answers dedup, diff and match with MSCOMP_ARG_ERROR, and dedupers made for those
+ *                 answer repair the same way.
+ *   Scratch:      reserved at creation under MSCOMP_AMD_SCRATCH_DEDUPER, once: diff's formula with n_res for n_pair -- 32 bytes per
+ *                 resource, 4 per row of n_blocks_new and 64 per MSCOMP_AMD_SPLICE_ROW_TILE of them, + 72.
+ *   Sources:      views as a splicer takes them, only read; d_verdict[s] (host array of n_src device arrays) has src[s].n_blocks_table
+ *                 entries, as salvage wrote them for source s (a mirror salvaged with d_only = the primary's verdicts serves: SKIPPED is
+ *                 not GOOD, and only the rows the primary lacks are asked for).
+ *   Notation:     diff's. first_s, off_s, L_s, crc_s: the tables of source s; n = the rows of resource r of the primary; B = block_size.
+ *   Rules:          0. r >= src[0].n_res: MSCOMP_ARG_ERROR, no table entry read.
+ *                   1. Resource r of the primary is held to dedup's rules 1-2: first_0[r] > first_0[r + 1] or first_0[r + 1] >
+ *                      n_blocks_table: MSCOMP_ARG_ERROR; first_0[r + 1] - first_0[r] != ceil(L_0 / B): MSCOMP_DATA_ERROR. A refused
+ *                      resource has no extents and d_fixed = d_lost = 0.
+ *                   2. Room, diff's rule 3: the saturating running total of n over the resources that passed rule 1, in order and
+ *                      including this one, must not exceed n_blocks_new: MSCOMP_ARG_ERROR otherwise.
+ *                   3. Choice. For row k of an accepted resource, c(k) is the lowest s whose copy is usable. s = 0 is usable when
+ *                      d_verdict[0][first_0[r] + k] == MSCOMP_AMD_BLOCK_GOOD. s >= 1 is usable when r < src[s].n_res, resource r of
+ *                      source s passes rule 1, L_s == L_0, d_verdict[s][first_s[r] + k] == MSCOMP_AMD_BLOCK_GOOD and -- when checksums
+ *                      take part -- crc_s[first_s[r] + k] == crc_0[first_0[r] + k]. If no source is usable the row is LOST and
+ *                      c(k) = 0: the primary's row is carried as it is, so repair never makes a container worse, and indices and
+ *                      lengths never shift.
+ *                   4. Runs. The extents of r are the maximal stretches of equal c, in order, written as (c, r, k0, count) with explicit
+ *                      counts; d_ext_first (n_res + 1) is dense, as diff's: d_ext_first[n_res] extents in all.
+ *                   5. d_fixed[r] = rows with c > 0, d_lost[r] = lost rows; d_status[r] is MSCOMP_OK when nothing is lost,
+ *                      MSCOMP_DATA_ERROR otherwise.
+ *                   6. d_count[0..3] = rows fixed, rows lost, stored bytes of the fixed rows in their mirrors, accepted resources with a
+ *                      lost row.
+ *   Consequence:  mscomp_amd_splicer_splice_extents over the same views with these lists writes a container of the primary's shape.
+ *                 Assume every source was written by mscomp_amd_blocks_compress + _crc from the same data with one format and B, and was
+ *                 then damaged in stored bytes, offset-table entries or CRC words: if no row is lost, the new packed bytes, tables and
+ *                 checksums are BYTE FOR BYTE the undamaged container. Splice-extents' rule 4 holds by construction: equal L means equal
+ *                 e at equal k.
+ *   Checksums:    take part when every view brings d_block_crc: a mirror's row whose CRC word differs from the primary's is not usable.
+ *                 (The word compared is the table's, not the data's: salvage held the data to it.)
+ *   Execution:    as diff's: asynchronous on the ctx stream, kernels only, six launches fixed by the creation bounds -- seed, choice, the
+ *                 three run passes in tiles of MSCOMP_AMD_SPLICE_ROW_TILE rows (the middle one is diff's), counts; two, seed and counts,
+ *                 when n_res or n_blocks_new is 0 --, nothing allocated or read back; legal inside a capture from the first execution,
+ *                 a graph of its own otherwise. MSCOMP_ARG_ERROR for a null dd, src, d_verdict or d_count, a view pack refuses, a null
+ *                 d_verdict[s] of a source with rows, or a null required array (d_ext may be null when n_blocks_new is 0, every array
+ *                 per resource when n_res is 0).
+ *   Left out:     telling a damaged CRC word from damaged data (a primary row with a damaged word is replaced only by a mirror row
+ *                 that carries the same damaged word; else it is lost); byte-granular salvage inside a block; repairing a refused
+ *                 resource's block_first; fusing salvage, repair and splice in one call; more than three mirrors. */
+MSCompStatus mscomp_amd_deduper_create_repair(mscomp_amd_ctx* ctx, uint32_t block_size, uint32_t n_src /* 1 .. 4 */, size_t n_res,
+                                              uint64_t n_blocks_new, uint32_t flags, mscomp_amd_deduper** dd);
+MSCompStatus mscomp_amd_deduper_repair(mscomp_amd_deduper* dd, const mscomp_amd_blocks_view* src /* host array, n_src; src[0] is the primary */,
+                                       const uint32_t* const* d_verdict /* host array of n_src device arrays, src[s].n_blocks_table entries each */,
+                                       uint64_t* d_ext_first /* n_res + 1 */, uint64_t* d_ext /* 4 n_blocks_new */,
+                                       uint64_t* d_fixed /* n_res */, uint64_t* d_lost /* n_res */, uint64_t* d_count /* 4 */,
+                                       int32_t* d_status /* n_res */);
 
 /* Block transcoders: a container brought to another block size, another codec, or both. Every call that combines containers -- splice,
  * splice by extents, dedup, diff, match, delta, patch -- asks for one format and one block size; a transcoder is what gets a container there.

@@ -10,7 +10,8 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   MSCompError, load_library, max_compressed_size, compress, compress_units, compress_units_host, decompress_units_host, HostViews, pack_offsets, decompress, decompress_units, compact_batch,
                   Context, Plan, SizePlan, decompressed_sizes, decompress_units_auto, DevPlan, layout_dev,
                   CompressDevPlan, plan_layout_dev, SizeDevPlan, compact_dev,
-                  BlockContainer, blocks_compress, blocks_decompress,
+                  BlockContainer, blocks_compress, blocks_decompress, blocks_salvage, blocks_repair,
+                  MSCOMP_AMD_BLOCK_GOOD, MSCOMP_AMD_BLOCK_TABLE, MSCOMP_AMD_BLOCK_DECODE, MSCOMP_AMD_BLOCK_CRC, MSCOMP_AMD_BLOCK_SKIPPED,
                   CrcDevPlan, crc32_units, blocks_crc,
                   BlockReader, blocks_read,
                   BlockWriter, blocks_write, blocks_resize, res_crc_dev, res_crc_from_blocks,

@@ -43,6 +43,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_plan_create_decompress_dev_ex", "mscomp_amd_plan_create_size_dev_ex", "mscomp_amd_debug_plan_paths",
     "mscomp_amd_blocks_create", "mscomp_amd_blocks_destroy", "mscomp_amd_blocks_bound", "mscomp_amd_blocks_compress", "mscomp_amd_blocks_decompress",
     "mscomp_amd_plan_create_crc_dev", "mscomp_amd_plan_execute_crc_dev", "mscomp_amd_blocks_crc", "mscomp_amd_blocks_check",
+    "mscomp_amd_blocks_salvage",
     "mscomp_amd_reader_create", "mscomp_amd_reader_destroy", "mscomp_amd_reader_read", "mscomp_amd_reader_counts",
     "mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_write", "mscomp_amd_writer_counts",
     "mscomp_amd_writer_resize", "mscomp_amd_res_crc_dev",
@@ -51,6 +52,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_deduper_create", "mscomp_amd_deduper_destroy", "mscomp_amd_deduper_dedup",
     "mscomp_amd_deduper_create_diff", "mscomp_amd_deduper_diff",
     "mscomp_amd_deduper_create_match", "mscomp_amd_deduper_match",
+    "mscomp_amd_deduper_create_repair", "mscomp_amd_deduper_repair",
     "mscomp_amd_transcoder_create", "mscomp_amd_transcoder_destroy", "mscomp_amd_transcoder_transcode", "mscomp_amd_transcoder_counts",
     "mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report",
 ]
@@ -58,6 +60,8 @@ MSCOMP_AMD_SPLICE_SRC_MAX = 4
 MSCOMP_AMD_SPLICE_ROW_TILE = 1024                              # rows of the new table per workgroup of splice_extents' row passes
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 MSCOMP_AMD_DIFF_NO_BASE = (1 << 64) - 1                        # the base resource of a diff pair whose new resource has none
+# the verdict of a row (BlockContainer.salvage): good; refused by its table entries; did not decode; decoded to other bytes; not judged
+MSCOMP_AMD_BLOCK_GOOD, MSCOMP_AMD_BLOCK_TABLE, MSCOMP_AMD_BLOCK_DECODE, MSCOMP_AMD_BLOCK_CRC, MSCOMP_AMD_BLOCK_SKIPPED = 0, 1, 2, 3, 4
 
 
 class ScratchRec(C.Structure):
@@ -176,6 +180,8 @@ def load_library():
     lib.mscomp_amd_blocks_crc.restype = C.c_int
     lib.mscomp_amd_blocks_check.argtypes = [C.c_void_p] + [C.c_void_p] * 8
     lib.mscomp_amd_blocks_check.restype = C.c_int
+    lib.mscomp_amd_blocks_salvage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 13
+    lib.mscomp_amd_blocks_salvage.restype = C.c_int
     lib.mscomp_amd_reader_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
     lib.mscomp_amd_reader_create.restype = C.c_int
     lib.mscomp_amd_reader_destroy.argtypes = [C.c_void_p]
@@ -220,6 +226,10 @@ def load_library():
     lib.mscomp_amd_deduper_create_match.restype = C.c_int
     lib.mscomp_amd_deduper_match.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.POINTER(BlocksView)] + [C.c_void_p] * 7
     lib.mscomp_amd_deduper_match.restype = C.c_int
+    lib.mscomp_amd_deduper_create_repair.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_deduper_create_repair.restype = C.c_int
+    lib.mscomp_amd_deduper_repair.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.POINTER(C.c_void_p)] + [C.c_void_p] * 6
+    lib.mscomp_amd_deduper_repair.restype = C.c_int
     lib.mscomp_amd_transcoder_create.restype = C.c_int
     lib.mscomp_amd_transcoder_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                                  C.POINTER(C.c_void_p)]
@@ -615,6 +625,19 @@ class BlockContainer(_Handle):
         p = _ptrs(d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status)
         _ok(self.ctx.lib.mscomp_amd_blocks_check(self._h, *p), "mscomp_amd_blocks_check")
 
+    def salvage(self, d_packed, d_block_first, d_block_off, d_res_len, d_out, d_out_off, d_out_cap, d_out_len, d_bad, d_verdict, d_count, d_status,
+                d_block_crc=None, d_only=None, packed_len=None):
+        """Decodes every block that can be decoded and says which could not: d_verdict (int32, n_blocks_max) holds MSCOMP_AMD_BLOCK_GOOD,
+        _TABLE, _DECODE, _CRC (only with ``d_block_crc``) or _SKIPPED per row of the table. A resource that decompress's checks 1-3 refuse
+        keeps that status with d_out_len = 0 and d_bad = 0 and is neither read nor written; every other resource has d_out_len[r] = its
+        length whatever its rows say, its good rows' data in place, ZEROS in its judged bad rows, d_bad[r] (int32, n_res) = their number
+        and d_status[r] MSCOMP_OK without one, MSCOMP_DATA_ERROR otherwise. ``d_only`` (int32, n_blocks_max; the d_verdict of a copy of the
+        same shape): rows it marks GOOD are not judged, not read and not written. d_count (int64, 4) = rows judged, rows bad, bytes
+        zero-filled, resources with a bad row."""
+        plen = d_packed.numel() if packed_len is None else int(packed_len)
+        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_only, d_out, d_out_off, d_out_cap, d_out_len, d_bad, d_verdict, d_count, d_status)
+        _ok(self.ctx.lib.mscomp_amd_blocks_salvage(self._h, p[0], plen, *p[1:]), "mscomp_amd_blocks_salvage")
+
 
 def blocks_compress(fmt, buffers, block_size, ctx=None):
     """The block container of a list of byte strings (one resource each), built on the GPU. Returns numpy arrays (packed uint8, block_first
@@ -706,6 +729,48 @@ def blocks_decompress(fmt, packed, block_first, block_off, lengths, block_size, 
         bk.close()
     res = [bytes(h_out[int(out_off[i]): int(out_off[i]) + int(h_len[i])]) if h_st[i] == MSCOMP_OK else None for i in range(n)]
     return res, [int(x) for x in h_st[:n]]
+
+
+def blocks_salvage(fmt, packed, block_first, block_off, lengths, block_size, ctx=None, block_crc=None, only=None):
+    """Salvage a block container on the GPU (BlockContainer.salvage): every block that can be decoded is, and the others are named.
+    ``block_crc`` (optional, as blocks_crc returns it) holds the decoded blocks to their checksums; ``only`` (optional: the verdicts of a
+    copy of the same shape) leaves out the rows it marks MSCOMP_AMD_BLOCK_GOOD. Returns (buffers: bytes of the resource's length with
+    zeros in the bad rows and in the rows left out, or None for a resource refused as a whole; verdicts: a numpy uint32 array with one
+    entry per row of block_off; bad: list; statuses: list; counts: list of 4)."""
+    import torch
+    n = len(lengths)
+    lens = [int(x) for x in lengths]
+    total = int(sum(lens))
+    out_off, out_total = pack_offsets(lens)
+    with _call(ctx) as (ctx, dev):
+        bk = BlockContainer(ctx, fmt, block_size, n, total)
+        nbm = bk.n_blocks_max
+        packed, d_packed = _dev_packed(packed, dev)
+        d_first, d_boff = _dev_u64(block_first, n + 1, dev), _dev_u64(block_off, nbm + 1, dev)
+        d_len, d_ooff, d_ocap = _dev_u64(lens, 1, dev), _dev_u64(out_off, 1, dev), _dev_u64(lens, 1, dev)
+        d_crc = None if block_crc is None else _dev_block_crc(block_crc, nbm, dev)
+        d_only = None
+        if only is not None:                                       # (rows behind the mask's own are judged)
+            h_only = np.full(max(1, nbm), MSCOMP_AMD_BLOCK_SKIPPED, dtype=np.uint32)
+            k = min(len(only), nbm)
+            h_only[:k] = np.asarray(only, dtype=np.uint32)[:k]
+            d_only = torch.from_numpy(h_only.view(np.int32).copy()).to(dev)
+        d_out = torch.zeros(out_total + 16, dtype=torch.uint8, device=dev)
+        d_olen, d_cnt = torch.zeros(max(1, n), dtype=torch.int64, device=dev), torch.zeros(4, dtype=torch.int64, device=dev)
+        d_bad, d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev), torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        d_ver = torch.full((max(1, nbm),), MSCOMP_AMD_BLOCK_SKIPPED, dtype=torch.int32, device=dev)
+        bk.salvage(d_packed, d_first, d_boff, d_len, d_out, d_ooff, d_ocap, d_olen, d_bad, d_ver, d_cnt, d_st, d_block_crc=d_crc, d_only=d_only,
+                   packed_len=len(packed))
+        ctx.stream.synchronize()
+        h_out, h_len, h_st, h_bad = d_out.cpu().numpy(), d_olen.cpu().numpy(), d_st.cpu().numpy(), d_bad.cpu().numpy()
+        rows = max(0, len(np.asarray(block_off).reshape(-1)) - 1)
+        ver = np.full(rows, MSCOMP_AMD_BLOCK_SKIPPED, dtype=np.uint32)
+        ver[: min(rows, nbm)] = d_ver.cpu().numpy().view(np.uint32)[: min(rows, nbm)]
+        counts = [int(x) for x in d_cnt.cpu().numpy()]
+        bk.close()
+    accepted = lambda i: h_st[i] == MSCOMP_OK or (h_st[i] == MSCOMP_DATA_ERROR and h_bad[i] > 0)
+    res = [bytes(h_out[int(out_off[i]): int(out_off[i]) + int(h_len[i])]) if accepted(i) else None for i in range(n)]
+    return res, ver, [int(x) for x in h_bad[:n]], [int(x) for x in h_st[:n]], counts
 
 
 class _BlockAccess(_Handle):
@@ -1139,6 +1204,35 @@ class BlockDeduper(_Handle):
             "mscomp_amd_deduper_match")
 
 
+    @classmethod
+    def for_repair(cls, ctx, block_size, n_src, n_res, n_blocks_new):
+        """A deduper for repair() (mscomp_amd_deduper_create_repair): ``n_src`` (1 .. 4) sources, the primary first, whose ``n_res``
+        resources have at most ``n_blocks_new`` rows in all. Its scratch is diff's: 32 bytes per resource, 4 per row and 64 per
+        SPLICE_ROW_TILE of them, + 72. It refuses dedup(), diff() and match(), as dedupers made for those refuse repair()."""
+        self = cls.__new__(cls)
+        _Handle.__init__(self, ctx)
+        self.block_size, self.n_src, self.n_res, self.n_blocks_new = int(block_size), int(n_src), int(n_res), int(n_blocks_new)
+        self.n_res_total, self.n_blocks_total = self.n_res, self.n_blocks_new
+        _ok(ctx.lib.mscomp_amd_deduper_create_repair(ctx._h, self.block_size, self.n_src, self.n_res, self.n_blocks_new, 0, C.byref(self._h)),
+            "mscomp_amd_deduper_create_repair")
+        return self
+
+    def repair(self, sources, d_verdicts, d_ext_first, d_ext, d_fixed, d_lost, d_count, d_status):
+        """``sources``: n_src sources as BlockSplicer.splice takes them, the primary first; ``d_verdicts``: per source the d_verdict array
+        BlockContainer.salvage wrote for it (int32, one entry per table row). Row k of resource r is taken from the lowest source whose
+        row is MSCOMP_AMD_BLOCK_GOOD -- a mirror counts only where it has the resource with the primary's length and, when every source
+        has checksums, the primary's CRC word --; a row no source has is lost and stays the primary's. The answer is one extent list in
+        the form BlockSplicer.splice_extents takes over the same sources: d_ext_first (n_res + 1), d_ext (4 n_blocks_new). d_fixed /
+        d_lost (n_res) = the rows taken from a mirror / lost, d_count (4) = rows fixed, rows lost, stored bytes of the fixed rows,
+        resources with a lost row; d_status[r] is MSCOMP_OK, MSCOMP_DATA_ERROR (a lost row, or a wrong block count) or MSCOMP_ARG_ERROR
+        (no such resource, a broken block_first entry, or no room within n_blocks_new), a refused resource having no extents."""
+        if len(sources) != self.n_src or len(d_verdicts) != self.n_src:
+            raise ValueError("one source and one verdict array per n_src")
+        q = (C.c_void_p * self.n_src)(*[None if t is None else t.data_ptr() for t in d_verdicts])
+        _ok(self.ctx.lib.mscomp_amd_deduper_repair(self._h, _blocks_views(sources), q, *_ptrs(d_ext_first, d_ext, d_fixed, d_lost, d_count, d_status)),
+            "mscomp_amd_deduper_repair")
+
+
 def _diff_pairs(base, new, pairs):
     """the pairs of blocks_diff as (base resource or MSCOMP_AMD_DIFF_NO_BASE, new resource) of 64 bits each"""
     M64 = MSCOMP_AMD_DIFF_NO_BASE
@@ -1201,6 +1295,45 @@ def blocks_patch(base, delta, patch_resources, block_size, ctx=None):
     """The new resources from ``base`` and the ``delta`` container and ``patch_resources`` of blocks_delta:
     blocks_splice_extents([base, delta], patch_resources, block_size). Returns what blocks_splice returns."""
     return blocks_splice_extents([base, delta], patch_resources, block_size, ctx=ctx)
+
+
+def blocks_repair(fmt, containers, block_size, ctx=None):
+    """Mend a damaged block container from up to three copies on the GPU: ``containers`` = [primary, mirror, ...], each (packed,
+    block_first, block_off, lengths, block_crc or None) of format ``fmt`` and ``block_size``. The primary is salvaged (blocks_salvage); each
+    mirror is salvaged only in the rows the primary lacks when its lengths are the primary's, and whole otherwise; BlockDeduper.repair
+    picks every row's source and blocks_splice_extents builds the container. Returns (container, report): container = (packed,
+    block_first, block_off, lengths, block_crc or None) as the other calls take one; report = a dict with the verdict arrays
+    ("verdicts", one per container), the extent lists ("resources"), "fixed" and "lost" per resource, "counts" (rows fixed, rows
+    lost, stored bytes of the fixed rows, resources with a lost row) and "statuses" (MSCOMP_OK: whole again; MSCOMP_DATA_ERROR: rows
+    lost, which stay the primary's)."""
+    import torch
+    B = int(block_size)
+    with_crc = all(c[4] is not None for c in containers)
+    lens0 = [int(x) for x in containers[0][3]]
+    n = len(lens0)
+    nbn = sum((L + B - 1) // B for L in lens0)
+    with _call(ctx, enter=False) as (ctx, dev):
+        verdicts = []
+        for i, (packed, first, off, lens, crc) in enumerate(containers):
+            same = i > 0 and [int(x) for x in lens] == lens0
+            verdicts.append(blocks_salvage(fmt, packed, first, off, lens, B, ctx=ctx, block_crc=crc, only=verdicts[0] if same else None)[1])
+        with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+            srcs, _, _ = _upload_containers(containers, dev, with_crc)
+            d_ver = [_dev_block_crc(v, len(v), dev) for v in verdicts]
+            dd = BlockDeduper.for_repair(ctx, B, len(containers), n, nbn)
+            d_ef, d_ext = torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(max(1, 4 * nbn), dtype=torch.int64, device=dev)
+            d_fix, d_lost = torch.zeros(max(1, n), dtype=torch.int64, device=dev), torch.zeros(max(1, n), dtype=torch.int64, device=dev)
+            d_cnt, d_st = torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+            dd.repair(srcs, d_ver, d_ef, d_ext, d_fix, d_lost, d_cnt, d_st)
+            ctx.stream.synchronize()
+            u64 = lambda t: t.cpu().numpy().view(np.uint64)
+            resources = _extent_lists(u64(d_ef), u64(d_ext), n)
+            report = {"verdicts": verdicts, "resources": resources, "fixed": [int(x) for x in u64(d_fix)[:n]], "lost": [int(x) for x in u64(d_lost)[:n]],
+                      "counts": [int(x) for x in u64(d_cnt)], "statuses": [int(x) for x in d_st.cpu().numpy()[:n]]}
+            dd.close()
+        cons = containers if with_crc else [tuple(c[:4]) + (None,) for c in containers]
+        packed, first, off, lens, crc, _ = blocks_splice_extents(cons, resources, B, ctx=ctx)
+    return (packed, first, off, lens, crc), report
 
 
 def blocks_match(stores, new, block_size, ctx=None):

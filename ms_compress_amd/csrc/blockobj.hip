@@ -97,7 +97,7 @@ struct mscomp_amd_blocks {
 	uint32_t shift = 0, n_res = 0, n_blocks = 0;       // block_size = 1 << shift; n_blocks = n_blocks_max
 	uint64_t in_total_max = 0;
 	InnerPlans in;                                     // (no cache; the staged compressed blocks: in_total_max + 16 n_res bytes)
-	GraphRun<8> crun; GraphRun<11> drun; GraphRun<6> krun; GraphRun<8> vrun;   // compress, decompress, crc, check
+	GraphRun<8> crun; GraphRun<11> drun; GraphRun<6> krun; GraphRun<8> vrun; GraphRun<15> srun;   // compress, decompress, crc, check, salvage
 	DevBuf tab;                                        // BlocksTab
 	BlocksTab t{};
 };
@@ -126,7 +126,7 @@ MSCompStatus mscomp_amd_blocks_create(mscomp_amd_ctx* c, MSCompFormat format, ui
 	std::unique_ptr<mscomp_amd_blocks> b(new (std::nothrow) mscomp_amd_blocks());
 	if (!b) { return MSCOMP_MEM_ERROR; }
 	b->ctx = c; b->format = format; b->shift = (uint32_t)__builtin_ctz(block_size); b->n_res = (uint32_t)n_res; b->n_blocks = (uint32_t)M; b->in_total_max = in_total_max;
-	b->crun.never = b->drun.never = b->krun.never = b->vrun.never = n_res == 0;
+	b->crun.never = b->drun.never = b->krun.never = b->vrun.never = b->srun.never = n_res == 0;
 	const MSCompStatus st = b->in.create(c, b->tab, blocks_tab(b->t, nullptr, n_res, M) + 64, 0, in_total_max + 16 * (uint64_t)n_res + 64, in_total_max, format, M, format, M,
 	                                     block_size, true);
 	if (st != MSCOMP_OK) { return st; }
@@ -175,7 +175,7 @@ MSCompStatus mscomp_amd_blocks_decompress(mscomp_amd_blocks* b, const uint8_t* d
 	return plan_run(b->drun, c, args, [&] {
 		const BlocksTab& t = b->t;
 		{ KernelTimer k(c, "bk_dtables"); launch_blocks_dtables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, packed_len, d_res_len, d_block_first, d_block_off,
-		                                                        d_range, d_out_off, d_out_cap, t); }
+		                                                        d_range, d_out_off, d_out_cap, nullptr, t); }
 		if (b->in.dplan) { dev_launch(b->in.dplan, d_packed, t.in_off, t.in_len, d_out, t.out_off, t.out_cap, t.ulen, t.ustat); }
 		{ KernelTimer k(c, "bk_rawcopy_kernel"); launch_blocks_rawcopy(c->stream, b->n_blocks, b->shift, d_packed, d_out, t, c->cpd_blocks); }
 		{ KernelTimer k(c, "bk_dfold_kernel"); launch_blocks_dfold(c->stream, b->n_res, t, d_out_len, d_status); }
@@ -225,6 +225,39 @@ MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* b, const uint8_t* d_out,
 		{ KernelTimer k(c, "bk_ktables"); launch_blocks_ktables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_len, d_block_first, d_range, d_out_off, d_status, t); }
 		crc_pass(c, b->n_blocks, d_out, t.in_off, t.in_len, t.aux_a, t.ucrc);
 		{ KernelTimer k(c, "bk_kfold_kernel"); launch_blocks_kfold(c->stream, b->n_res, d_block_crc, t, d_out_len, d_status); }
+	});
+}
+
+// Salvage, the container's fifth call: decompress's passes with d_range = NULL and the mask up to the raw copy, then a verdict per row where
+// decompress folds them away. The columns after the raw copy:
+//   salvage t.in_off / t.in_len = the blocks in d_out the CRC kernels read, t.out_off = the unit's row, t.aux_a .. = cum, t.ucrc = what was read and
+//           then the unit's verdict; t.ustat / t.ulen / t.act live from the inner plan to the verdict, t.unit_first / t.rstat / t.res_a to the fold
+static_assert(SV_GOOD == MSCOMP_AMD_BLOCK_GOOD && SV_TABLE == MSCOMP_AMD_BLOCK_TABLE && SV_DECODE == MSCOMP_AMD_BLOCK_DECODE && SV_CRC == MSCOMP_AMD_BLOCK_CRC &&
+              SV_SKIPPED == MSCOMP_AMD_BLOCK_SKIPPED, "the verdicts the header states");
+MSCompStatus mscomp_amd_blocks_salvage(mscomp_amd_blocks* b, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first, const uint64_t* d_block_off,
+                                       const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint32_t* d_only, uint8_t* d_out, const uint64_t* d_out_off,
+                                       const uint64_t* d_out_cap, uint64_t* d_out_len, uint32_t* d_bad, uint32_t* d_verdict, uint64_t* d_count, int32_t* d_status)
+{
+	if (!b || !d_block_first || !d_block_off || (b->n_res && (!d_res_len || !d_out_off || !d_out_cap || !d_out_len || !d_bad || !d_verdict || !d_count || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (b->in_total_max && (!d_packed || !d_out)) { return MSCOMP_ARG_ERROR; }
+	if (b->n_res == 0) { return MSCOMP_OK; }               // (nothing to report on: no resource, no row, and d_count is not written)
+	mscomp_amd_ctx* c = b->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	b->in.mark_ran(true, false);
+	const void* args[15] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_only,
+	                         d_out, d_out_off, d_out_cap, d_out_len, d_bad, d_verdict, d_count, d_status };
+	return plan_run(b->srun, c, args, [&] {
+		const BlocksTab& t = b->t;
+		{ KernelTimer k(c, "bk_dtables"); launch_blocks_dtables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, packed_len, d_res_len, d_block_first, d_block_off,
+		                                                        nullptr, d_out_off, d_out_cap, d_only, t); }
+		if (b->in.dplan) { dev_launch(b->in.dplan, d_packed, t.in_off, t.in_len, d_out, t.out_off, t.out_cap, t.ulen, t.ustat); }
+		{ KernelTimer k(c, "bk_rawcopy_kernel"); launch_blocks_rawcopy(c->stream, b->n_blocks, b->shift, d_packed, d_out, t, c->cpd_blocks); }
+		{ KernelTimer k(c, "bk_sunits_kernel"); launch_blocks_sunits(c->stream, b->n_res, b->n_blocks, b->shift, d_block_first, d_out_off, t, d_verdict, d_count); }
+		if (d_block_crc) { crc_pass(c, b->n_blocks, d_out, t.in_off, t.in_len, t.aux_a, t.ucrc); }
+		{ KernelTimer k(c, "bk_sverdict_kernel"); launch_blocks_sverdict(c->stream, b->n_res, b->n_blocks, d_block_crc, t, d_verdict); }
+		{ KernelTimer k(c, "bk_szero_kernel"); launch_blocks_szero(c->stream, b->n_blocks, b->shift, d_out, t, c->cpd_blocks); }
+		{ KernelTimer k(c, "bk_sfold_kernel"); launch_blocks_sfold(c->stream, b->n_res, t, d_out_len, d_bad, d_status, d_count); }
 	});
 }
 
@@ -568,8 +601,10 @@ struct mscomp_amd_deduper {
 	uint32_t shift = 0, n_src = 0, n_res = 0, nbt = 0;     // block_size = 1 << shift; the bounds n_res_total and n_blocks_total
 	bool diff = false;                                     // made by mscomp_amd_deduper_create_diff: n_res is n_pair, nbt is n_blocks_new, the scratch holds a DiffTab
 	bool match = false;                                    // made by mscomp_amd_deduper_create_match: n_src stores (0 .. 3), nbn is n_blocks_new, the scratch holds a MatchTab
+	bool repair = false;                                   // made by mscomp_amd_deduper_create_repair: n_res and nbt (= n_blocks_new) bound the primary, the scratch holds a DiffTab
 	uint32_t nbn = 0;
 	GraphRun<37> run; GraphRun<24> frun; GraphRun<39> mrun; // dedup: four views, and five words; diff: two views, and eight; match: four views, and seven
+	GraphRun<42> rrun;                                      // repair: four views, four verdict arrays, and six words
 	DevBuf tab;                                            // DedupTab, DiffTab or MatchTab
 	DedupTab t{};
 	DiffTab f{};
@@ -636,7 +671,7 @@ void mscomp_amd_deduper_destroy(mscomp_amd_deduper* d) { destroy_object(d, [d] {
 MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* src, uint64_t* d_rep, uint64_t* d_new_index, uint64_t* d_pick,
                                       uint64_t* d_count, int32_t* d_status)
 {
-	if (!d || d->diff || d->match || !src || !d_count) { return MSCOMP_ARG_ERROR; }
+	if (!d || d->diff || d->match || d->repair || !src || !d_count) { return MSCOMP_ARG_ERROR; }
 	SpliceSrc k{};
 	bool with_crc = false;                                 // the checksums are used only if every view has them
 	if (!pack_views(src, d->n_src, true, k.v, with_crc)) { return MSCOMP_ARG_ERROR; }
@@ -667,7 +702,7 @@ MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* d, const mscomp_amd_blo
                                      uint64_t* d_delta_ext_first, uint64_t* d_delta_ext, uint64_t* d_patch_ext_first, uint64_t* d_patch_ext, uint64_t* d_changed,
                                      uint64_t* d_count, int32_t* d_status)
 {
-	if (!d || !d->diff || !base || !next || !d_count) { return MSCOMP_ARG_ERROR; }   // (a deduper made for dedup or for match)
+	if (!d || !d->diff || !base || !next || !d_count) { return MSCOMP_ARG_ERROR; }   // (a deduper made for dedup, for match or for repair)
 	if (d->n_res && (!d_pair || !d_delta_ext_first || !d_patch_ext_first || !d_changed || !d_status || (d->nbt && (!d_delta_ext || !d_patch_ext)))) { return MSCOMP_ARG_ERROR; }
 	const mscomp_amd_blocks_view src[2] = { *base, *next };
 	SpliceView v[2];
@@ -758,6 +793,55 @@ MSCompStatus mscomp_amd_deduper_match(mscomp_amd_deduper* d, const mscomp_amd_bl
 		}
 		if (d->nbn) { KernelTimer tm(c, "mt_runs"); launch_match_runs(c->stream, k, d->n_src, N, n_store, d->nbn, d->shift, t, d_status, d_delta_ext, d_patch_ext); }
 		{ KernelTimer tm(c, "mt_counts_kernel"); launch_match_counts(c->stream, N, n_store, d->nbn, d->nbt != 0, t, d_delta_ext_first, d_patch_ext_first, d_class, d_count, c->crc_blocks); }
+	});
+}
+
+MSCompStatus mscomp_amd_deduper_create_repair(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res, uint64_t n_blocks_new, uint32_t flags,
+                                              mscomp_amd_deduper** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || !block_size_ok(block_size)) { return MSCOMP_ARG_ERROR; }
+	if (n_src == 0 || n_src > MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_res) || !count_ok(n_blocks_new)) { return MSCOMP_ARG_ERROR; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
+	if (!d) { return MSCOMP_MEM_ERROR; }
+	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = n_src; d->n_res = (uint32_t)n_res; d->nbt = (uint32_t)n_blocks_new; d->repair = true;
+	if (!d->tab.reserve(diff_tab(d->f, nullptr, n_res, n_blocks_new) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	diff_tab(d->f, d->tab.p, n_res, n_blocks_new);
+	*out = d.release();
+	return MSCOMP_OK;
+}
+
+// Repair: the seed, the rows' choices from the tables and the verdicts, the three run passes tiled over the primary's rows
+// (the middle one is diff's), the counts.
+MSCompStatus mscomp_amd_deduper_repair(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* src, const uint32_t* const* d_verdict, uint64_t* d_ext_first, uint64_t* d_ext,
+                                       uint64_t* d_fixed, uint64_t* d_lost, uint64_t* d_count, int32_t* d_status)
+{
+	if (!d || !d->repair || !src || !d_verdict || !d_count) { return MSCOMP_ARG_ERROR; }   // (a deduper made for dedup, for diff or for match)
+	if (d->n_res && (!d_ext_first || !d_fixed || !d_lost || !d_status || (d->nbt && !d_ext))) { return MSCOMP_ARG_ERROR; }
+	SpliceSrc k{};
+	bool with_crc = false;                                 // the checksums take part only if every view has them
+	if (!pack_views(src, d->n_src, true, k.v, with_crc)) { return MSCOMP_ARG_ERROR; }
+	const uint32_t* q[4] = { nullptr, nullptr, nullptr, nullptr };
+	for (uint32_t i = 0; i < d->n_src; ++i) {
+		if (src[i].n_res && src[i].n_blocks_table && !d_verdict[i]) { return MSCOMP_ARG_ERROR; }
+		q[i] = d_verdict[i];
+	}
+	mscomp_amd_ctx* c = d->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[42];
+	view_args(args, k.v, { q[0], q[1], q[2], q[3], d_ext_first, d_ext, d_fixed, d_lost, d_count, d_status });
+	const uint32_t n = d->n_res, m = d->nbt;
+	return plan_run(d->rrun, c, args, [&] {
+		{ KernelTimer t(c, "rp_seed_kernel"); launch_repair_seed(c->stream, k.v[0], n, m, d->shift, d->f, d_status, d_count); }
+		if (n && m) {
+			{ KernelTimer t(c, "rp_choice_kernel"); launch_repair_choice(c->stream, k, q, d->n_src, n, m, d->shift, with_crc, d->f, c->crc_blocks); }
+			{ KernelTimer t(c, "rp_runs"); launch_repair_runs(c->stream, k, n, m, d->f, d_ext); }
+		}
+		{ KernelTimer t(c, "rp_counts_kernel"); launch_repair_counts(c->stream, n, m, d->f, d_ext_first, d_fixed, d_lost, d_count, d_status, c->crc_blocks); }
 	});
 }
 

@@ -135,10 +135,11 @@ __global__ __launch_bounds__(DV_THREADS) void bk_dres_kernel(uint32_t n, uint32_
 // The inner decompress plan's unit tables and the action words, one thread per possible unit. A block whose stored length s equals its data
 // length e is copied, 0 < s < e is decoded into capacity e at its final place; everything else -- a decreasing table, an end beyond
 // packed_len, s > e, s = 0 -- fails the resource without a byte of the block being read. Only blocks to decode reach the inner plan with a
-// length; all other units are empty there, with capacity 0.
+// length; all other units are empty there, with capacity 0. `only` (salvage's mask over the container's rows, else null): a row it marks
+// good is not judged -- BK_SKIP with its data length, nothing read.
 __global__ __launch_bounds__(256) void bk_dunits_kernel(uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 packed_len, const u64* __restrict__ res_len,
                                                        const u64* __restrict__ block_first, const u64* __restrict__ block_off, const u64* __restrict__ d_out_off,
-                                                       const u64* __restrict__ unit_first, const u64* __restrict__ rf,
+                                                       const u64* __restrict__ unit_first, const u64* __restrict__ rf, const uint32_t* __restrict__ only,
                                                        u64* __restrict__ in_off, u64* __restrict__ in_len, u64* __restrict__ out_off, u64* __restrict__ out_cap,
                                                        u64* __restrict__ raw_src, u64* __restrict__ raw_dst, uint32_t* __restrict__ act)
 {
@@ -152,7 +153,8 @@ __global__ __launch_bounds__(256) void bk_dunits_kernel(uint32_t n_res, uint32_t
 		const u64 k = u - unit_first[r], jb = rf[r] + k, j = block_first[r] + jb;    // (j < block_first[r + 1] <= nbmax: bk_dres_kernel)
 		const u64 left = res_len[r] - (jb << shift), e = left < B ? left : B;
 		const u64 o0 = block_off[j], o1 = block_off[j + 1u], dst = d_out_off[r] + (k << shift);
-		if (o1 < o0 || o1 > packed_len) { a = BK_FAIL; }
+		if (only && only[j] == SV_GOOD) { a = BK_SKIP; }                   // salvage: a row the mask leaves out is an empty unit, with its data length
+		else if (o1 < o0 || o1 > packed_len) { a = BK_FAIL; }
 		else {
 			const u64 s = o1 - o0;
 			if (s == e) { a = BK_COPY; rs = o0; rd = dst; }
@@ -291,6 +293,95 @@ __global__ __launch_bounds__(256) void bk_kfold_kernel(uint32_t n_res, const u64
 	if (lane == 0 && (st != 0 || any_bad)) { d_status[r] = st != 0 ? st : -3; d_out_len[r] = 0; }   // MSCOMP_DATA_ERROR
 }
 
+// ---- salvage (mscomp_amd_blocks_salvage): verdicts per block behind the decompress passes, d_range = NULL ----
+// Behind the raw copy, one thread per possible unit: the CRC columns pointed at the blocks in d_out -- a block that was copied, or decoded
+// to its length, is read over its e bytes, every other unit is empty --, the row a unit answers to (`which`), every verdict SKIPPED until
+// the verdict pass says otherwise, and the four counts cleared. The raw columns and the inner plan's tables are free from here on; ustat,
+// ulen and act are not.
+__global__ __launch_bounds__(256) void bk_sunits_kernel(uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* __restrict__ block_first, const u64* __restrict__ d_out_off,
+                                                       const u64* __restrict__ unit_first, const uint32_t* __restrict__ act, const u64* __restrict__ dlen,
+                                                       const int32_t* __restrict__ dstat, u64* __restrict__ in_off, u64* __restrict__ in_len, u64* __restrict__ which,
+                                                       uint32_t* __restrict__ verdict, u64* __restrict__ count)
+{
+	const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+	if (u >= nbmax) { return; }
+	if (u == 0) { count[0] = count[1] = count[2] = count[3] = 0; }
+	u64 io = 0, il = 0, j = 0;
+	if (u < unit_first[n_res]) {
+		const uint32_t r = res_of_block(unit_first, n_res, u), a = act[u], kind = a & 3u;
+		const u64 k = u - unit_first[r], e = a >> 2;
+		j = block_first[r] + k;                                            // (< block_first[r + 1] <= nbmax: bk_dres_kernel)
+		io = d_out_off[r] + (k << shift);
+		if (kind == BK_COPY || (kind == BK_DECODE && dstat[u] == 0 && dlen[u] == e)) { il = e; }
+	}
+	in_off[u] = io; in_len[u] = il; which[u] = j; verdict[u] = SV_SKIPPED;
+}
+
+// Behind the CRC kernels (or the pass above, without checksums), one thread per possible row: the first of TABLE, DECODE, CRC that applies,
+// else GOOD, into d_verdict at the unit's row and -- for the two passes behind -- into the unit's own word, where the CRC-32 stood. A
+// masked unit and a unit behind the real count are SKIPPED there.
+__global__ __launch_bounds__(256) void bk_sverdict_kernel(uint32_t n_res, uint32_t nbmax, const u64* __restrict__ unit_first, const uint32_t* __restrict__ act,
+                                                         const u64* __restrict__ dlen, const int32_t* __restrict__ dstat, const u64* __restrict__ which,
+                                                         const uint32_t* __restrict__ block_crc, uint32_t* __restrict__ ucrc, uint32_t* __restrict__ verdict)
+{
+	const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+	if (u >= nbmax) { return; }
+	uint32_t v = SV_SKIPPED;
+	if (u < unit_first[n_res]) {
+		const uint32_t a = act[u], kind = a & 3u;
+		if (kind != BK_SKIP) {
+			const u64 j = which[u];
+			if (kind == BK_FAIL) { v = SV_TABLE; }
+			else if (kind == BK_DECODE && (dstat[u] != 0 || dlen[u] != (u64)(a >> 2))) { v = SV_DECODE; }
+			else { v = block_crc && ucrc[u] != block_crc[j] ? SV_CRC : SV_GOOD; }
+			verdict[j] = v;
+		}
+	}
+	ucrc[u] = v;
+}
+
+// The e bytes of every judged bad row zeroed -- a failed decoder may have written inside its capacity --, in the shape of bk_rawcopy_kernel:
+// pieces of 16 KiB round robin over a grid fixed by the CU count, 16-byte stores behind a bytewise head.
+__global__ __launch_bounds__(CPD_THREADS) void bk_szero_kernel(uint32_t nbmax, uint32_t ppu_shift, uint8_t* __restrict__ out, const u64* __restrict__ dst,
+                                                              const uint32_t* __restrict__ act, const uint32_t* __restrict__ uv)
+{
+	const u64 items = (u64)nbmax << ppu_shift;
+	for (u64 i = blockIdx.x; i < items; i += gridDim.x) {
+		const uint32_t u = (uint32_t)(i >> ppu_shift), v = uv[u];
+		const u64 at = (i & (((u64)1 << ppu_shift) - 1u)) << BK_PIECE_SHIFT, e = act[u] >> 2;
+		if (v == SV_GOOD || v == SV_SKIPPED || at >= e) { continue; }
+		const u64 cnt = e - at < ((u64)1 << BK_PIECE_SHIFT) ? e - at : (u64)1 << BK_PIECE_SHIFT;
+		cpd_move<true>(out + dst[u] + at, nullptr, cnt, threadIdx.x);
+	}
+}
+
+// One wave per resource: its judged and its bad rows counted, d_out_len = L for every accepted resource whatever its rows say, d_bad,
+// d_status, and the resource's share of the four counts (sums of whole numbers: the same from run to run).
+__global__ __launch_bounds__(256) void bk_sfold_kernel(uint32_t n_res, const u64* __restrict__ unit_first, const uint32_t* __restrict__ act, const uint32_t* __restrict__ uv,
+                                                      const int32_t* __restrict__ rstat, const u64* __restrict__ want, u64* __restrict__ d_out_len,
+                                                      uint32_t* __restrict__ d_bad, int32_t* __restrict__ d_status, u64* count)
+{
+	const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+	if (r >= n_res) { return; }
+	const int32_t st = rstat[r];
+	u64 judged = 0, bad = 0, zeroed = 0;
+	if (st == 0) {
+		for (u64 u = unit_first[r] + lane; u < unit_first[r + 1u]; u += 64u) {
+			const uint32_t v = uv[u];
+			if (v != SV_SKIPPED) { ++judged; }
+			if (v != SV_SKIPPED && v != SV_GOOD) { ++bad; zeroed += act[u] >> 2; }
+		}
+	}
+	#pragma unroll
+	for (uint32_t d = 32u; d; d >>= 1) { judged += __shfl_down(judged, d, 64); bad += __shfl_down(bad, d, 64); zeroed += __shfl_down(zeroed, d, 64); }
+	if (lane == 0) {
+		d_out_len[r] = st == 0 ? want[r] : 0; d_bad[r] = (uint32_t)bad; d_status[r] = st != 0 ? st : bad ? -3 : 0;   // MSCOMP_DATA_ERROR
+		unsigned long long* c = reinterpret_cast<unsigned long long*>(count);
+		if (judged) { atomicAdd(c, (unsigned long long)judged); }
+		if (bad) { atomicAdd(c + 1, (unsigned long long)bad); atomicAdd(c + 2, (unsigned long long)zeroed); atomicAdd(c + 3, 1ull); }
+	}
+}
+
 // ---- move (the last pass of mscomp_amd_writer_write, _writer_resize and mscomp_amd_splicer_splice) ----
 // The only pass over a whole new container, and it knows nothing of where a row's bytes come from: the call's layout pass wrote addr[row],
 // the address of the row's stored bytes, or 0 for a row that is not moved (nothing stored, unreadable, or ending beyond cap). The new byte
@@ -351,13 +442,14 @@ void launch_blocks_select(hipStream_t st, uint32_t n_res, uint32_t nbmax, u64 ca
 }
 
 void launch_blocks_dtables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, u64 packed_len, const u64* res_len,
-                           const u64* block_first, const u64* block_off, const u64* range, const u64* d_out_off, const u64* d_out_cap, const BlocksTab& t)
+                           const u64* block_first, const u64* block_off, const u64* range, const u64* d_out_off, const u64* d_out_cap, const uint32_t* only,
+                           const BlocksTab& t)
 {
 	hipLaunchKernelGGL(bk_dres_kernel, dim3(1), dim3(DV_THREADS), 0, st, n_res, nbmax, shift, in_max, res_len, block_first, range, d_out_cap,
 	                   t.unit_first, t.res_b, t.res_a, t.rstat);
 	if (nbmax == 0) { return; }
 	hipLaunchKernelGGL(bk_dunits_kernel, dim3((nbmax + 255u) / 256u), dim3(256), 0, st, n_res, nbmax, shift, packed_len, res_len, block_first, block_off, d_out_off,
-	                   t.unit_first, t.res_b, t.in_off, t.in_len, t.out_off, t.out_cap, t.aux_a, t.aux_b, t.act);
+	                   t.unit_first, t.res_b, only, t.in_off, t.in_len, t.out_off, t.out_cap, t.aux_a, t.aux_b, t.act);
 }
 
 void launch_blocks_rawcopy(hipStream_t st, uint32_t nbmax, uint32_t shift, const uint8_t* packed, uint8_t* out, const BlocksTab& t, uint32_t blocks)
@@ -372,6 +464,30 @@ void launch_blocks_dfold(hipStream_t st, uint32_t n_res, const BlocksTab& t, u64
 {
 	if (n_res == 0) { return; }
 	hipLaunchKernelGGL(bk_dfold_kernel, dim3((n_res + 3u) / 4u), dim3(256), 0, st, n_res, t.unit_first, t.act, t.ulen, t.ustat, t.rstat, t.res_a, d_out_len, d_status);
+}
+
+void launch_blocks_sunits(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* block_first, const u64* d_out_off, const BlocksTab& t,
+                          uint32_t* verdict, u64* count)
+{
+	hipLaunchKernelGGL(bk_sunits_kernel, dim3((nbmax + 255u) / 256u), dim3(256), 0, st, n_res, nbmax, shift, block_first, d_out_off, t.unit_first, t.act, t.ulen, t.ustat,
+	                   t.in_off, t.in_len, t.out_off, verdict, count);
+}
+
+void launch_blocks_sverdict(hipStream_t st, uint32_t n_res, uint32_t nbmax, const uint32_t* block_crc, const BlocksTab& t, uint32_t* verdict)
+{
+	hipLaunchKernelGGL(bk_sverdict_kernel, dim3((nbmax + 255u) / 256u), dim3(256), 0, st, n_res, nbmax, t.unit_first, t.act, t.ulen, t.ustat, t.out_off, block_crc, t.ucrc, verdict);
+}
+
+void launch_blocks_szero(hipStream_t st, uint32_t nbmax, uint32_t shift, uint8_t* out, const BlocksTab& t, uint32_t blocks)
+{
+	const uint32_t ppu_shift = shift > BK_PIECE_SHIFT ? shift - BK_PIECE_SHIFT : 0u;
+	const u64 items = (u64)nbmax << ppu_shift;
+	hipLaunchKernelGGL(bk_szero_kernel, dim3((uint32_t)(items < blocks ? items : blocks)), dim3(CPD_THREADS), 0, st, nbmax, ppu_shift, out, t.in_off, t.act, t.ucrc);
+}
+
+void launch_blocks_sfold(hipStream_t st, uint32_t n_res, const BlocksTab& t, u64* d_out_len, uint32_t* d_bad, int32_t* d_status, u64* count)
+{
+	hipLaunchKernelGGL(bk_sfold_kernel, dim3((n_res + 3u) / 4u), dim3(256), 0, st, n_res, t.unit_first, t.act, t.ucrc, t.rstat, t.res_a, d_out_len, d_bad, d_status, count);
 }
 
 void launch_blocks_crcgroups(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* res_len, const u64* block_first, const BlocksTab& t)

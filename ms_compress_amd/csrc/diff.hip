@@ -263,11 +263,16 @@ void launch_diff_confirm(hipStream_t st, const SpliceView& base, const SpliceVie
 	hipLaunchKernelGGL(df_confirm_kernel, df_grid((u64)nbn << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, base, next, n_pair, ppu_shift, pair, t.ufirst, status, t.verdict);
 }
 
+void launch_diff_tilescan(hipStream_t st, uint32_t tiles, u64* tsum)
+{
+	hipLaunchKernelGGL(df_tilescan_kernel, dim3(1), dim3(DV_THREADS), 0, st, tiles, tsum);
+}
+
 void launch_diff_runs(hipStream_t st, const SpliceView& next, uint32_t n_pair, uint32_t nbn, const u64* pair, const DiffTab& t, const int32_t* status, u64* delta_ext, u64* patch_ext)
 {
 	const uint32_t tiles = diff_row_tiles(nbn);
 	hipLaunchKernelGGL(df_tile_kernel, dim3(tiles), dim3(DV_THREADS), 0, st, next, n_pair, pair, t.ufirst, status, t.verdict, t.tsum);
-	hipLaunchKernelGGL(df_tilescan_kernel, dim3(1), dim3(DV_THREADS), 0, st, tiles, t.tsum);
+	launch_diff_tilescan(st, tiles, t.tsum);
 	hipLaunchKernelGGL(df_runs_kernel, dim3(tiles), dim3(DV_THREADS), 0, st, n_pair, pair, t.ufirst, status, t.verdict, t.tsum, t.pfirst, delta_ext, patch_ext);
 }
 

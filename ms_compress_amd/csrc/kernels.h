@@ -245,10 +245,28 @@ void launch_blocks_select(hipStream_t st, uint32_t n_res, uint32_t nbmax, u64 ca
                           const BlocksTab& t, u64* block_off, int32_t* d_status);
 // decompress, in front of the inner plan: the per-resource checks and the range, then unit tables and action words (two launches)
 void launch_blocks_dtables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, u64 packed_len, const u64* res_len,
-                           const u64* block_first, const u64* block_off, const u64* range, const u64* d_out_off, const u64* d_out_cap, const BlocksTab& t);
+                           const u64* block_first, const u64* block_off, const u64* range, const u64* d_out_off, const u64* d_out_cap, const uint32_t* only,
+                           const BlocksTab& t);
 // decompress, behind it: raw blocks to their places (`blocks` = compact_dev_blocks()), then status and length per resource
 void launch_blocks_rawcopy(hipStream_t st, uint32_t nbmax, uint32_t shift, const uint8_t* packed, uint8_t* out, const BlocksTab& t, uint32_t blocks);
 void launch_blocks_dfold(hipStream_t st, uint32_t n_res, const BlocksTab& t, u64* d_out_len, int32_t* d_status);
+// salvage (mscomp_amd_blocks_salvage): launch_blocks_dtables with range null and `only` = the mask over the container's rows (may be null: the
+// rows it marks SV_GOOD become empty units), the inner plan and launch_blocks_rawcopy as decompress runs them, then four passes of its own.
+// The verdict of a row (MSCOMP_AMD_BLOCK_*):
+#define SV_GOOD    0u
+#define SV_TABLE   1u
+#define SV_DECODE  2u
+#define SV_CRC     3u
+#define SV_SKIPPED 4u
+// units: the CRC columns over the blocks in d_out that can be read (t.in_off = where every unit's block lies, t.in_len), t.out_off = the
+// unit's row, verdict (nbmax) all SV_SKIPPED, count (4) cleared. t.ustat, t.ulen and t.act stay as the inner plan and the table pass left them
+void launch_blocks_sunits(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* block_first, const u64* d_out_off, const BlocksTab& t,
+                          uint32_t* verdict, u64* count);
+// behind the CRC kernels (block_crc null: behind the pass above): the judged rows' verdicts into verdict and, per unit, into t.ucrc
+void launch_blocks_sverdict(hipStream_t st, uint32_t n_res, uint32_t nbmax, const uint32_t* block_crc, const BlocksTab& t, uint32_t* verdict);
+// the judged bad rows zeroed in d_out (`blocks` = compact_dev_blocks()), then length, bad rows and status per resource and the counts
+void launch_blocks_szero(hipStream_t st, uint32_t nbmax, uint32_t shift, uint8_t* out, const BlocksTab& t, uint32_t blocks);
+void launch_blocks_sfold(hipStream_t st, uint32_t n_res, const BlocksTab& t, u64* d_out_len, uint32_t* d_bad, int32_t* d_status, u64* count);
 // crc, behind launch_blocks_ctables: per block its resource (t.act) and the resource's bytes behind it (t.ulen), for launch_crc_units
 void launch_blocks_crcgroups(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* res_len, const u64* block_first, const BlocksTab& t);
 // check, in front of the CRC kernels: checks 1 and 2 and the clipped range of the resources that are MSCOMP_OK in d_status (t.unit_first, t.res_b,
@@ -449,8 +467,25 @@ void launch_diff_confirm(hipStream_t st, const SpliceView& base, const SpliceVie
                          const int32_t* status, uint32_t blocks);
 // runs (three launches: the tiles' sums, their running values in one block, the rows): delta_ext and patch_ext (4 n_blocks_new each), t.pfirst
 void launch_diff_runs(hipStream_t st, const SpliceView& next, uint32_t n_pair, uint32_t nbn, const u64* pair, const DiffTab& t, const int32_t* status, u64* delta_ext, u64* patch_ext);
+// the middle launch of the runs alone, for a call that lays its tiles out as diff does (repair.hip): per tile eight words -- six sums, the
+// last row that starts a run + 1, a count diff carries behind it (0: none) -- turned into their running values in place (one block)
+void launch_diff_tilescan(hipStream_t st, uint32_t tiles, u64* tsum);
 // counts: delta_first and patch_first (n_pair + 1, may be null when n_pair is 0), changed (n_pair), count (4)
 void launch_diff_counts(hipStream_t st, uint32_t n_pair, uint32_t nbn, const DiffTab& t, u64* delta_first, u64* patch_first, u64* changed, u64* count, uint32_t blocks);
+
+// mscomp_amd_deduper_repair, the deduper's fourth call (repair.hip): from the verdicts of a container and up to three copies
+// (mscomp_amd_blocks_salvage), the extent list that takes every bad row from the first copy whose row is good. Its scratch is a DiffTab
+// (n = n_res, m = n_blocks_new; verdict holds a row's choice: source | 4 when lost). Four stages, six launches fixed by the creation
+// bounds (two -- seed and counts -- when n_res or n_blocks_new is 0; the caller leaves the others out).
+// seed (one block): rules 1 and 2, status (n_res), t.ufirst; count[3] cleared
+void launch_repair_seed(hipStream_t st, const SpliceView& primary, uint32_t n_res, uint32_t nbn, uint32_t shift, const DiffTab& t, int32_t* status, u64* count);
+// choice: rule 3, a fixed grid over the rows; verdict[s] = the salvage verdicts of source s; `blocks` = crc_dev_blocks()
+void launch_repair_choice(hipStream_t st, const SpliceSrc& src, const uint32_t* const (&verdict)[4], uint32_t n_src, uint32_t n_res, uint32_t nbn, uint32_t shift, bool with_crc,
+                          const DiffTab& t, uint32_t blocks);
+// runs (three launches: the tiles' sums, launch_diff_tilescan, the rows): ext (4 n_blocks_new), t.pfirst
+void launch_repair_runs(hipStream_t st, const SpliceSrc& src, uint32_t n_res, uint32_t nbn, const DiffTab& t, u64* ext);
+// counts: ext_first (n_res + 1, may be null when n_res is 0), fixed and lost (n_res), count (4), and MSCOMP_DATA_ERROR for a resource with a lost row
+void launch_repair_counts(hipStream_t st, uint32_t n_res, uint32_t nbn, const DiffTab& t, u64* ext_first, u64* fixed, u64* lost, u64* count, int32_t* status, uint32_t blocks);
 
 // mscomp_amd_deduper_match, the deduper's third call (match.hip): for every block of the resources of `next`, whether an equal block lies in
 // one of up to three store containers (found), earlier in next (shared) or nowhere (fresh), answered as the delta and the patch extent
