@@ -493,13 +493,13 @@ struct mscomp_amd_splicer {
 };
 #pragma GCC visibility pop
 static_assert(sizeof(mscomp_amd_blocks_view) == sizeof(SpliceView) && sizeof(SpliceView) == 8 * sizeof(void*), "a view is eight words of the graph's key");
-static_assert(SX_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header states");
+static_assert(ROW_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header states");
 
 // the columns of a splicer made for extents from `base` on; returns where they end: from a null base, their bytes
 static uintptr_t splice_ext_tab(SpliceExtTab& t, void* base, size_t nbt, size_t n_ext)
 {
 	Carve k(base);
-	t.addr = k.q(nbt); t.ext_row = k.q(n_ext + 1); t.tsum = k.q(splice_row_tiles((uint32_t)nbt)); t.flag = k.w(2);
+	t.addr = k.q(nbt); t.ext_row = k.q(n_ext + 1); t.tsum = k.q(row_tiles((uint32_t)nbt)); t.flag = k.w(2);
 	return k.at;
 }
 
@@ -596,12 +596,16 @@ MSCompStatus mscomp_amd_splicer_splice_extents(mscomp_amd_splicer* s, const msco
 // ---- block dedupers (include/mscomp_amd.h; kernels: dedup.hip) ----
 // A deduper holds its tables -- sized by the bound of the resources alone -- and the graph of its call, keyed as a splicer's.
 #pragma GCC visibility push(hidden)                     // (what the creates instantiate over the object -- std::unique_ptr's destructor -- is no export of the library)
+enum DeduperKind {                                      // the call a deduper was made for; it refuses the other three
+	DEDUPER_DEDUP,                                         // mscomp_amd_deduper_create: the scratch holds a DedupTab
+	DEDUPER_DIFF,                                          // _create_diff: n_res is n_pair, nbt is n_blocks_new, the scratch holds a DiffTab
+	DEDUPER_MATCH,                                         // _create_match: n_src stores (0 .. 3), nbn is n_blocks_new, the scratch holds a MatchTab
+	DEDUPER_REPAIR                                         // _create_repair: n_res and nbt (= n_blocks_new) bound the primary, the scratch holds a DiffTab
+};
 struct mscomp_amd_deduper {
 	mscomp_amd_ctx* ctx = nullptr;
 	uint32_t shift = 0, n_src = 0, n_res = 0, nbt = 0;     // block_size = 1 << shift; the bounds n_res_total and n_blocks_total
-	bool diff = false;                                     // made by mscomp_amd_deduper_create_diff: n_res is n_pair, nbt is n_blocks_new, the scratch holds a DiffTab
-	bool match = false;                                    // made by mscomp_amd_deduper_create_match: n_src stores (0 .. 3), nbn is n_blocks_new, the scratch holds a MatchTab
-	bool repair = false;                                   // made by mscomp_amd_deduper_create_repair: n_res and nbt (= n_blocks_new) bound the primary, the scratch holds a DiffTab
+	DeduperKind kind = DEDUPER_DEDUP;
 	uint32_t nbn = 0;
 	GraphRun<37> run; GraphRun<24> frun; GraphRun<39> mrun; // dedup: four views, and five words; diff: two views, and eight; match: four views, and seven
 	GraphRun<42> rrun;                                      // repair: four views, four verdict arrays, and six words
@@ -611,7 +615,6 @@ struct mscomp_amd_deduper {
 	MatchTab m{};
 };
 #pragma GCC visibility pop
-static_assert(DF_TILE == MSCOMP_AMD_SPLICE_ROW_TILE && MT_TILE == MSCOMP_AMD_SPLICE_ROW_TILE, "the row tile the header states");
 
 // the columns of a deduper's tables from `base` on (n = n_res_total); returns where they end: from a null base, their bytes
 static uintptr_t dedup_tab(DedupTab& t, void* base, size_t n)
@@ -623,64 +626,106 @@ static uintptr_t dedup_tab(DedupTab& t, void* base, size_t n)
 	return k.at;
 }
 
-MSCompStatus mscomp_amd_deduper_create(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res_total, uint64_t n_blocks_total, uint32_t flags,
-                                       mscomp_amd_deduper** out)
-{
-	if (!out) { return MSCOMP_ARG_ERROR; }
-	*out = nullptr;
-	if (!c || flags || !block_size_ok(block_size)) { return MSCOMP_ARG_ERROR; }
-	if (n_src == 0 || n_src > MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_res_total) || !count_ok(n_blocks_total)) { return MSCOMP_ARG_ERROR; }
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
-	if (!d) { return MSCOMP_MEM_ERROR; }
-	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = n_src; d->n_res = (uint32_t)n_res_total; d->nbt = (uint32_t)n_blocks_total;
-	if (!d->tab.reserve(dedup_tab(d->t, nullptr, n_res_total) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
-	dedup_tab(d->t, d->tab.p, n_res_total);
-	*out = d.release();
-	return MSCOMP_OK;
-}
-
 // the columns of a deduper made for diff from `base` on (n = n_pair, m = n_blocks_new); returns where they end: from a null base, their bytes
 static uintptr_t diff_tab(DiffTab& t, void* base, size_t n, size_t m)
 {
 	Carve k(base);
-	t.ufirst = k.q(n + 1); t.pfirst = k.q(3 * n); t.tsum = k.q(8 * (size_t)diff_row_tiles((uint32_t)m)); t.verdict = k.w(m);
+	t.ufirst = k.q(n + 1); t.pfirst = k.q(3 * n); t.tsum = k.q(8 * (size_t)row_tiles((uint32_t)m)); t.verdict = k.w(m);
 	return k.at;
 }
 
-MSCompStatus mscomp_amd_deduper_create_diff(mscomp_amd_ctx* c, uint32_t block_size, size_t n_pair, uint64_t n_blocks_new, uint32_t flags, mscomp_amd_deduper** out)
+// the columns of a deduper made for match from `base` on (n = n_res_total, m = n_blocks_total, mn = n_blocks_new); returns where they end:
+// from a null base, their bytes
+static uintptr_t match_tab(MatchTab& t, void* base, size_t n, size_t m, size_t mn)
+{
+	Carve k(base);
+	const size_t slots = 2 * m + 64;
+	t.slots = slots < 0xFFFFFFF0u ? slots : 0xFFFFFFF0u;   // (a slot's index is a 32-bit word, and all-ones is "none")
+	t.ufirst = k.q(n + 1); t.pfirst = k.q(5 * n); t.tsum = k.q(8 * (size_t)row_tiles((uint32_t)mn)); t.tkey = k.q(slots); t.nref = k.q(1);
+	t.tmin = k.w(slots); t.slot_of = k.w(m); t.flag = k.w(m); t.rep = k.w(m); t.rlist = k.w(m); t.flocal = k.w(mn);
+	return k.at;
+}
+
+// The four creates: args_ok = the create's own check of its counts; fill(d, base) sets the bounds in d and lays the columns of its tables
+// out from `base` on, returning where they end: from a null base, their bytes.
+template <class Fill>
+static MSCompStatus deduper_create(mscomp_amd_ctx* c, uint32_t block_size, uint32_t flags, mscomp_amd_deduper** out, DeduperKind kind, bool args_ok, Fill fill)
 {
 	if (!out) { return MSCOMP_ARG_ERROR; }
 	*out = nullptr;
-	if (!c || flags || !block_size_ok(block_size)) { return MSCOMP_ARG_ERROR; }
-	if (!count_ok(n_pair) || !count_ok(n_blocks_new)) { return MSCOMP_ARG_ERROR; }
+	if (!c || flags || !block_size_ok(block_size) || !args_ok) { return MSCOMP_ARG_ERROR; }
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
 	if (!d) { return MSCOMP_MEM_ERROR; }
-	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = 2; d->n_res = (uint32_t)n_pair; d->nbt = (uint32_t)n_blocks_new; d->diff = true;
-	if (!d->tab.reserve(diff_tab(d->f, nullptr, n_pair, n_blocks_new) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
-	diff_tab(d->f, d->tab.p, n_pair, n_blocks_new);
+	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->kind = kind;
+	if (!d->tab.reserve(fill(*d, nullptr) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	fill(*d, d->tab.p);
 	*out = d.release();
 	return MSCOMP_OK;
 }
 
+MSCompStatus mscomp_amd_deduper_create(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res_total, uint64_t n_blocks_total, uint32_t flags,
+                                       mscomp_amd_deduper** out)
+{
+	const bool args_ok = n_src != 0 && n_src <= MSCOMP_AMD_SPLICE_SRC_MAX && count_ok(n_res_total) && count_ok(n_blocks_total);
+	return deduper_create(c, block_size, flags, out, DEDUPER_DEDUP, args_ok, [&](mscomp_amd_deduper& d, void* base) {
+		d.n_src = n_src; d.n_res = (uint32_t)n_res_total; d.nbt = (uint32_t)n_blocks_total;
+		return dedup_tab(d.t, base, n_res_total);
+	});
+}
+
+MSCompStatus mscomp_amd_deduper_create_diff(mscomp_amd_ctx* c, uint32_t block_size, size_t n_pair, uint64_t n_blocks_new, uint32_t flags, mscomp_amd_deduper** out)
+{
+	return deduper_create(c, block_size, flags, out, DEDUPER_DIFF, count_ok(n_pair) && count_ok(n_blocks_new), [&](mscomp_amd_deduper& d, void* base) {
+		d.n_src = 2; d.n_res = (uint32_t)n_pair; d.nbt = (uint32_t)n_blocks_new;
+		return diff_tab(d.f, base, n_pair, n_blocks_new);
+	});
+}
+
+MSCompStatus mscomp_amd_deduper_create_match(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res_total, uint64_t n_blocks_total, uint64_t n_blocks_new,
+                                             uint32_t flags, mscomp_amd_deduper** out)
+{
+	const bool args_ok = n_src < MSCOMP_AMD_SPLICE_SRC_MAX && count_ok(n_res_total) && count_ok(n_blocks_total) && n_blocks_new <= n_blocks_total;
+	return deduper_create(c, block_size, flags, out, DEDUPER_MATCH, args_ok, [&](mscomp_amd_deduper& d, void* base) {
+		d.n_src = n_src; d.n_res = (uint32_t)n_res_total; d.nbt = (uint32_t)n_blocks_total; d.nbn = (uint32_t)n_blocks_new;
+		return match_tab(d.m, base, n_res_total, n_blocks_total, n_blocks_new);
+	});
+}
+
+MSCompStatus mscomp_amd_deduper_create_repair(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res, uint64_t n_blocks_new, uint32_t flags,
+                                              mscomp_amd_deduper** out)
+{
+	const bool args_ok = n_src != 0 && n_src <= MSCOMP_AMD_SPLICE_SRC_MAX && count_ok(n_res) && count_ok(n_blocks_new);
+	return deduper_create(c, block_size, flags, out, DEDUPER_REPAIR, args_ok, [&](mscomp_amd_deduper& d, void* base) {
+		d.n_src = n_src; d.n_res = (uint32_t)n_res; d.nbt = (uint32_t)n_blocks_new;
+		return diff_tab(d.f, base, n_res, n_blocks_new);
+	});
+}
+
 void mscomp_amd_deduper_destroy(mscomp_amd_deduper* d) { destroy_object(d, [d] { d->tab.release(); }); }
+
+// whether every one of the n_views views lies within the deduper's bounds n_res and nbt, and their sums do; n = the resources of the call
+static bool views_within(const mscomp_amd_deduper* d, const mscomp_amd_blocks_view* src, uint32_t n_views, uint64_t& n)
+{
+	uint64_t rows = 0;                                     // (at most four terms below 2^64 / 4 each once checked: no overflow)
+	n = 0;
+	for (uint32_t i = 0; i < n_views; ++i) {
+		if (src[i].n_res > d->n_res || src[i].n_blocks_table > d->nbt) { return false; }
+		n += src[i].n_res; rows += src[i].n_blocks_table;
+	}
+	return n <= d->n_res && rows <= d->nbt;
+}
 
 MSCompStatus mscomp_amd_deduper_dedup(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* src, uint64_t* d_rep, uint64_t* d_new_index, uint64_t* d_pick,
                                       uint64_t* d_count, int32_t* d_status)
 {
-	if (!d || d->diff || d->match || d->repair || !src || !d_count) { return MSCOMP_ARG_ERROR; }
+	if (!d || d->kind != DEDUPER_DEDUP || !src || !d_count) { return MSCOMP_ARG_ERROR; }
 	SpliceSrc k{};
 	bool with_crc = false;                                 // the checksums are used only if every view has them
 	if (!pack_views(src, d->n_src, true, k.v, with_crc)) { return MSCOMP_ARG_ERROR; }
-	uint64_t n = 0, rows = 0;                              // (at most four terms below 2^64 / 4 each once checked: no overflow)
-	for (uint32_t i = 0; i < d->n_src; ++i) {
-		if (src[i].n_res > d->n_res || src[i].n_blocks_table > d->nbt) { return MSCOMP_ARG_ERROR; }
-		n += src[i].n_res; rows += src[i].n_blocks_table;
-	}
-	if (n > d->n_res || rows > d->nbt) { return MSCOMP_ARG_ERROR; }
+	uint64_t n = 0;
+	if (!views_within(d, src, d->n_src, n)) { return MSCOMP_ARG_ERROR; }
 	if (n && (!d_rep || !d_new_index || !d_pick || !d_status)) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_ctx* c = d->ctx;
 	DeviceGuard g(c->device);
@@ -702,7 +747,7 @@ MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* d, const mscomp_amd_blo
                                      uint64_t* d_delta_ext_first, uint64_t* d_delta_ext, uint64_t* d_patch_ext_first, uint64_t* d_patch_ext, uint64_t* d_changed,
                                      uint64_t* d_count, int32_t* d_status)
 {
-	if (!d || !d->diff || !base || !next || !d_count) { return MSCOMP_ARG_ERROR; }   // (a deduper made for dedup, for match or for repair)
+	if (!d || d->kind != DEDUPER_DIFF || !base || !next || !d_count) { return MSCOMP_ARG_ERROR; }   // (a deduper made for dedup, for match or for repair)
 	if (d->n_res && (!d_pair || !d_delta_ext_first || !d_patch_ext_first || !d_changed || !d_status || (d->nbt && (!d_delta_ext || !d_patch_ext)))) { return MSCOMP_ARG_ERROR; }
 	const mscomp_amd_blocks_view src[2] = { *base, *next };
 	SpliceView v[2];
@@ -725,43 +770,12 @@ MSCompStatus mscomp_amd_deduper_diff(mscomp_amd_deduper* d, const mscomp_amd_blo
 	});
 }
 
-// the columns of a deduper made for match from `base` on (n = n_res_total, m = n_blocks_total, mn = n_blocks_new); returns where they end:
-// from a null base, their bytes
-static uintptr_t match_tab(MatchTab& t, void* base, size_t n, size_t m, size_t mn)
-{
-	Carve k(base);
-	const size_t slots = 2 * m + 64;
-	t.slots = slots < 0xFFFFFFF0u ? slots : 0xFFFFFFF0u;   // (a slot's index is a 32-bit word, and all-ones is "none")
-	t.ufirst = k.q(n + 1); t.pfirst = k.q(5 * n); t.tsum = k.q(8 * (size_t)match_row_tiles((uint32_t)mn)); t.tkey = k.q(slots); t.nref = k.q(1);
-	t.tmin = k.w(slots); t.slot_of = k.w(m); t.flag = k.w(m); t.rep = k.w(m); t.rlist = k.w(m); t.flocal = k.w(mn);
-	return k.at;
-}
-
-MSCompStatus mscomp_amd_deduper_create_match(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res_total, uint64_t n_blocks_total, uint64_t n_blocks_new,
-                                             uint32_t flags, mscomp_amd_deduper** out)
-{
-	if (!out) { return MSCOMP_ARG_ERROR; }
-	*out = nullptr;
-	if (!c || flags || !block_size_ok(block_size)) { return MSCOMP_ARG_ERROR; }
-	if (n_src >= MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_res_total) || !count_ok(n_blocks_total) || n_blocks_new > n_blocks_total) { return MSCOMP_ARG_ERROR; }
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
-	if (!d) { return MSCOMP_MEM_ERROR; }
-	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = n_src; d->n_res = (uint32_t)n_res_total; d->nbt = (uint32_t)n_blocks_total;
-	d->nbn = (uint32_t)n_blocks_new; d->match = true;
-	if (!d->tab.reserve(match_tab(d->m, nullptr, n_res_total, n_blocks_total, n_blocks_new) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
-	match_tab(d->m, d->tab.p, n_res_total, n_blocks_total, n_blocks_new);
-	*out = d.release();
-	return MSCOMP_OK;
-}
-
 // Match: the key table cleared, the seed, rule 3 over the rows, the rows' keys into the table, the compare that confirms a
 // row against its slot's smallest, the settle, the three run passes tiled over next's rows, the counts.
 MSCompStatus mscomp_amd_deduper_match(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* store, const mscomp_amd_blocks_view* next, uint64_t* d_delta_ext_first,
                                       uint64_t* d_delta_ext, uint64_t* d_patch_ext_first, uint64_t* d_patch_ext, uint64_t* d_class, uint64_t* d_count, int32_t* d_status)
 {
-	if (!d || !d->match || !next || !d_count || (d->n_src && !store)) { return MSCOMP_ARG_ERROR; }
+	if (!d || d->kind != DEDUPER_MATCH || !next || !d_count || (d->n_src && !store)) { return MSCOMP_ARG_ERROR; }
 	if (d->n_res && (!d_delta_ext_first || !d_patch_ext_first || !d_class || !d_status || (d->nbn && (!d_delta_ext || !d_patch_ext)))) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_blocks_view src[MSCOMP_AMD_SPLICE_SRC_MAX];
 	for (uint32_t i = 0; i < d->n_src; ++i) { src[i] = store[i]; }
@@ -769,12 +783,8 @@ MSCompStatus mscomp_amd_deduper_match(mscomp_amd_deduper* d, const mscomp_amd_bl
 	SpliceSrc k{};
 	bool with_crc = false;                                 // the checksums are used only if every view has them
 	if (!pack_views(src, d->n_src + 1, true, k.v, with_crc)) { return MSCOMP_ARG_ERROR; }
-	uint64_t n = 0, rows = 0;                              // (at most four terms below 2^64 / 4 each once checked: no overflow)
-	for (uint32_t i = 0; i <= d->n_src; ++i) {
-		if (src[i].n_res > d->n_res || src[i].n_blocks_table > d->nbt) { return MSCOMP_ARG_ERROR; }
-		n += src[i].n_res; rows += src[i].n_blocks_table;
-	}
-	if (n > d->n_res || rows > d->nbt || next->n_blocks_table > d->nbn) { return MSCOMP_ARG_ERROR; }
+	uint64_t n = 0;
+	if (!views_within(d, src, d->n_src + 1, n) || next->n_blocks_table > d->nbn) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_ctx* c = d->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
@@ -796,30 +806,12 @@ MSCompStatus mscomp_amd_deduper_match(mscomp_amd_deduper* d, const mscomp_amd_bl
 	});
 }
 
-MSCompStatus mscomp_amd_deduper_create_repair(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res, uint64_t n_blocks_new, uint32_t flags,
-                                              mscomp_amd_deduper** out)
-{
-	if (!out) { return MSCOMP_ARG_ERROR; }
-	*out = nullptr;
-	if (!c || flags || !block_size_ok(block_size)) { return MSCOMP_ARG_ERROR; }
-	if (n_src == 0 || n_src > MSCOMP_AMD_SPLICE_SRC_MAX || !count_ok(n_res) || !count_ok(n_blocks_new)) { return MSCOMP_ARG_ERROR; }
-	DeviceGuard g(c->device);
-	if (!g.ok) { return MSCOMP_ERRNO; }
-	std::unique_ptr<mscomp_amd_deduper> d(new (std::nothrow) mscomp_amd_deduper());
-	if (!d) { return MSCOMP_MEM_ERROR; }
-	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_src = n_src; d->n_res = (uint32_t)n_res; d->nbt = (uint32_t)n_blocks_new; d->repair = true;
-	if (!d->tab.reserve(diff_tab(d->f, nullptr, n_res, n_blocks_new) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
-	diff_tab(d->f, d->tab.p, n_res, n_blocks_new);
-	*out = d.release();
-	return MSCOMP_OK;
-}
-
 // Repair: the seed, the rows' choices from the tables and the verdicts, the three run passes tiled over the primary's rows
 // (the middle one is diff's), the counts.
 MSCompStatus mscomp_amd_deduper_repair(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* src, const uint32_t* const* d_verdict, uint64_t* d_ext_first, uint64_t* d_ext,
                                        uint64_t* d_fixed, uint64_t* d_lost, uint64_t* d_count, int32_t* d_status)
 {
-	if (!d || !d->repair || !src || !d_verdict || !d_count) { return MSCOMP_ARG_ERROR; }   // (a deduper made for dedup, for diff or for match)
+	if (!d || d->kind != DEDUPER_REPAIR || !src || !d_verdict || !d_count) { return MSCOMP_ARG_ERROR; }   // (a deduper made for dedup, for diff or for match)
 	if (d->n_res && (!d_ext_first || !d_fixed || !d_lost || !d_status || (d->nbt && !d_ext))) { return MSCOMP_ARG_ERROR; }
 	SpliceSrc k{};
 	bool with_crc = false;                                 // the checksums take part only if every view has them
@@ -868,7 +860,7 @@ static uintptr_t transcode_tab(TranscodeTab& t, void* base, const TcDims& d, siz
 	const size_t n = d.n_res, ng = d.ngmax, m = d.nbn;
 	Carve k(base);
 	t.gfirst = k.q(n + 1); t.pfirst = k.q(n + 1);
-	t.plen = k.q(m); t.paddr = k.q(m); t.pjf = k.q(m); t.pdl = k.q(m); t.addr = k.q(m); t.tsum = k.q(splice_row_tiles((uint32_t)m));
+	t.plen = k.q(m); t.paddr = k.q(m); t.pjf = k.q(m); t.pdl = k.q(m); t.addr = k.q(m); t.tsum = k.q(row_tiles((uint32_t)m));
 	t.d_in_off = k.q(dm); t.d_in_len = k.q(dm); t.d_out_off = k.q(dm); t.d_out_cap = k.q(dm); t.d_ulen = k.q(dm);
 	t.d_src = k.q(dm); t.d_clen = k.q(dm); t.d_cum = k.q(dm + 1); t.d_row = k.q(dm); t.d_raw = k.q(dm);
 	t.e_in_off = k.q(em); t.e_in_len = k.q(em); t.e_out_off = k.q(em); t.e_out_cap = k.q(em); t.e_ulen = k.q(em);

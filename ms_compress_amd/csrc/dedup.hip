@@ -2,8 +2,8 @@
 // of one format and one block size hold the same bytes, decided on the STORED form -- the stored form of a block depends only on its data,
 // the format and the block size -- and answered as a pick list a splicer takes. Candidates come from the tables and 32 bytes per row (a
 // 64-bit key per resource, an open-addressing table over the keys); the only pass over the data is the compare that confirms a candidate.
-// The sources travel by value in the kernel arguments, as a splicer's. DESIGN.md 4.13.
-#include "kernels.h"
+// The sources travel by value in the kernel arguments, as one SpliceSrc that a lane indexes (kernels.h sp_view). DESIGN.md 4.13.
+#include "rowpass.h"
 
 namespace msc {
 
@@ -21,37 +21,19 @@ __global__ __launch_bounds__(256) void dd_clear_kernel(u64 slots, u64* __restric
 	for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < slots; i += (u64)gridDim.x * 256u) { tkey[i] = 0; tmin[i] = 0xFFFFFFFFu; }
 }
 
-// Seed, one block, in the shape of sp_layout_kernel: rules 1 and 2 per resource, the status, the key word seeded with L, the mismatch flag
-// cleared, and ufirst (n + 1): the rows of the resources that passed, numbered densely in resource order -- this pass's own running sum, so
-// that a damaged block_first cannot send the row passes' search astray (bk_dres_kernel).
-__global__ __launch_bounds__(DV_THREADS) void dd_seed_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t shift,
+// Seed, one block: rules 1 and 2 per resource, the status, the key word seeded with L, the mismatch flag cleared, and ufirst (n + 1): the
+// rows of the resources that passed, numbered densely in resource order (no room rule: rule 1 keeps a resource's rows within its view's
+// table, and the host has held the views' tables against the creation bound).
+__global__ __launch_bounds__(DV_THREADS) void dd_seed_kernel(SpliceSrc src, uint32_t n, uint32_t shift,
                                                             u64* __restrict__ ufirst, u64* __restrict__ key, uint32_t* __restrict__ flag, int32_t* __restrict__ status)
 {
-	__shared__ u64 s_w[1][DV_WAVES];
-	const uint32_t tid = threadIdx.x;
-	const u64 B = (u64)1 << shift;
-	u64 run[1] = {0};
-	if (tid == 0) { ufirst[0] = 0; }
-	for (uint32_t base = 0; base < n; base += DV_THREADS) {
-		const uint32_t g = base + tid;
-		const bool live = g < n;
-		u64 rows = 0, L = 0;
-		int32_t st = 0;
-		if (live) {
-			u64 s, r;
-			dd_locate(v0, v1, v2, g, s, r);
-			const SpliceView v = sp_view(v0, v1, v2, v3, s);
-			const u64 f0 = v.first[r], f1 = v.first[r + 1u];
-			if (f0 > f1 || f1 > v.nbt) { st = -2; }                          // rule 1: MSCOMP_ARG_ERROR
-			else {
-				L = v.res_len[r]; rows = f1 - f0;
-				if (rows != (L >> shift) + ((L & (B - 1u)) ? 1u : 0u)) { st = -3; rows = 0; }   // rule 2: MSCOMP_DATA_ERROR
-			}
-		}
-		u64 a[1] = {rows};
-		dv_block_scan<1>(a, run, s_w);
-		if (live) { ufirst[g + 1u] = a[0]; key[g] = st == 0 ? dd_mix(L ^ 0x9E3779B97F4A7C15ull) : 0; flag[g] = 0; status[g] = st; }
-	}
+	seed_numbering<0>(n, 0, 0, ufirst, status, [&](uint32_t g, u64& rows, bool&) {
+		u64 s, r, f0, L;
+		dd_locate(src, g, s, r);
+		const int32_t st = view_rows(sp_view(src, s), r, shift, f0, rows, L);
+		key[g] = st == 0 ? dd_mix(L ^ 0x9E3779B97F4A7C15ull) : 0; flag[g] = 0;
+		return st;
+	});
 }
 
 // The row passes: a fixed grid dealt over the ROWS of the resources that passed rules 1 and 2, so that one resource of a million rows
@@ -60,7 +42,7 @@ __global__ __launch_bounds__(DV_THREADS) void dd_seed_kernel(SpliceView v0, Spli
 // resources that are still accepted fold a 64-bit mix of (row number, stored length, CRC word, first and last min(16, s) stored bytes)
 // into their resource's key word with an atomic XOR; a wave whose 64 rows share one resource folds them in registers first.
 template <bool KEY>
-__global__ __launch_bounds__(256) void dd_rows_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t with_crc,
+__global__ __launch_bounds__(256) void dd_rows_kernel(SpliceSrc src, uint32_t n, uint32_t with_crc,
                                                      const u64* __restrict__ ufirst, u64* __restrict__ key, int32_t* status)
 {
 	const uint32_t lane = threadIdx.x & 63u;
@@ -72,8 +54,8 @@ __global__ __launch_bounds__(256) void dd_rows_kernel(SpliceView v0, SpliceView 
 		if (u < units) {
 			const uint32_t x = res_of_block(ufirst, n, u);
 			u64 s, r;
-			dd_locate(v0, v1, v2, x, s, r);
-			const SpliceView v = sp_view(v0, v1, v2, v3, s);
+			dd_locate(src, x, s, r);
+			const SpliceView v = sp_view(src, s);
 			const u64 k = u - ufirst[x], j = v.first[r] + k;                  // (j < first[r + 1] <= v.nbt: rule 1)
 			const u64 o0 = v.off[j], o1 = v.off[j + 1u];
 			if (!KEY) {
@@ -122,7 +104,7 @@ __global__ __launch_bounds__(256) void dd_insert_kernel(uint32_t n, u64 slots, c
 
 // behind it, one thread per resource: the candidate -- the smallest accepted resource with the same key, itself for a refused one -- and
 // the first thing that can tell two resources of one key apart: their lengths
-__global__ __launch_bounds__(256) void dd_cand_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, const int32_t* __restrict__ status,
+__global__ __launch_bounds__(256) void dd_cand_kernel(SpliceSrc src, uint32_t n, const int32_t* __restrict__ status,
                                                      const uint32_t* __restrict__ tmin, const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ cand,
                                                      uint32_t* __restrict__ flag)
 {
@@ -132,64 +114,53 @@ __global__ __launch_bounds__(256) void dd_cand_kernel(SpliceView v0, SpliceView 
 			c = tmin[slot_of[g]];
 			if (c != (uint32_t)g) {
 				u64 s, r, sc, rc;
-				dd_locate(v0, v1, v2, g, s, r); dd_locate(v0, v1, v2, c, sc, rc);
-				if (sp_view(v0, v1, v2, v3, s).res_len[r] != sp_view(v0, v1, v2, v3, sc).res_len[rc]) { flag[g] = 1u; }
+				dd_locate(src, g, s, r); dd_locate(src, c, sc, rc);
+				if (sp_view(src, s).res_len[r] != sp_view(src, sc).res_len[rc]) { flag[g] = 1u; }
 			}
 		}
 		cand[g] = c;
 	}
 }
 
-// Confirm: the (row, piece of 16 KiB) items of the same row numbering, cut into equal slices, one per block of a fixed grid; a block walks
-// the rows of its slice, and what it has to look up it looks up once per row (its resource once per resource). A row of an accepted
-// resource that is not its key's minimum is compared with the same row of the minimum: the stored lengths, the CRC words, then the
-// pieces of the slice as one stretch of bytes. A mismatch sets the resource's flag: every writer stores the same value, so no ordering is
-// needed. A workgroup looks at the flag before it starts a row and skips it when set -- what that saves is time alone: the flag ends as
-// 1 exactly when something differs. (A flag set by dd_cand_kernel says that the lengths differ: then the two resources' rows do not pair
-// up, and no row of the resource is looked at.)
-__global__ __launch_bounds__(CPD_THREADS) void dd_confirm_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t ppu_shift, uint32_t with_crc,
+// Confirm: the slices of the same row numbering (confirm_slices); what a workgroup has to look up it looks up once per row (its resource
+// once per resource). A row of an accepted resource that is not its key's minimum is compared with the same row of the minimum: the
+// stored lengths, the CRC words, then the pieces of the slice as one stretch of bytes. A mismatch sets the resource's flag: every writer
+// stores the same value, so no ordering is needed. A workgroup looks at the flag before it starts a row and skips it when set -- what
+// that saves is time alone: the flag ends as 1 exactly when something differs. (A flag set by dd_cand_kernel says that the lengths
+// differ: then the two resources' rows do not pair up, and no row of the resource is looked at.)
+__global__ __launch_bounds__(CPD_THREADS) void dd_confirm_kernel(SpliceSrc src, uint32_t n, uint32_t ppu_shift, uint32_t with_crc,
                                                                 const u64* __restrict__ ufirst, const uint32_t* __restrict__ cand, uint32_t* flag)
 {
 	const uint32_t tid = threadIdx.x;
-	const u64 units = ufirst[n] < ((u64)1 << 56) ? ufirst[n] : (u64)1 << 56, items = units << ppu_shift;
-	u64 per = (items + gridDim.x - 1u) / gridDim.x;
-	per = per < DD_SLICE_MIN ? DD_SLICE_MIN : per;
-	const u64 lo = (u64)blockIdx.x * per;
-	if (lo >= items) { return; }
-	const u64 hi = items - lo < per ? items : lo + per;
+	const u64 units = ufirst[n] < ((u64)1 << 56) ? ufirst[n] : (u64)1 << 56;
 	uint32_t g = 0;
 	u64 g_end = 0;                                                         // the rows below g_end that are not below ufirst[g] are g's
-	for (u64 i = lo; i < hi; ) {
-		const u64 u = i >> ppu_shift, next = (u + 1u) << ppu_shift, end = next < hi ? next : hi;   // the row's items in this slice: [i, end)
-		// (a row's last piece runs to the end of the row: nothing bounds a stored length but packed_len, so a row of a damaged table that passes
-		// rule 3 may be longer than its pieces -- one workgroup then takes the rest)
-		const u64 at = (i - (u << ppu_shift)) << DD_PIECE_SHIFT, upto = end == next ? ~(u64)0 : (end - (u << ppu_shift)) << DD_PIECE_SHIFT;
-		i = end;
+	confirm_slices(units, ppu_shift, [&](u64 u, u64 at, u64 upto) {
 		if (u >= g_end) { g = res_of_block(ufirst, n, u); g_end = ufirst[g + 1u]; }
 		const uint32_t c = cand[g];
-		if (c == g || flag[g] != 0) { continue; }
+		if (c == g || flag[g] != 0) { return; }
 		u64 s, r, sc, rc;
-		dd_locate(v0, v1, v2, g, s, r); dd_locate(v0, v1, v2, c, sc, rc);
-		const SpliceView v = sp_view(v0, v1, v2, v3, s), w = sp_view(v0, v1, v2, v3, sc);
+		dd_locate(src, g, s, r); dd_locate(src, c, sc, rc);
+		const SpliceView v = sp_view(src, s), w = sp_view(src, sc);
 		const u64 k = u - ufirst[g], j = v.first[r] + k, jc = w.first[rc] + k;  // (equal lengths, both accepted: equal row counts)
 		const u64 o0 = v.off[j], len = v.off[j + 1u] - o0, c0 = w.off[jc], clen = w.off[jc + 1u] - c0;
 		if (len != clen || (with_crc && v.crc[j] != w.crc[jc])) {
 			if (tid == 0) { flag[g] = 1u; }
-			continue;
+			return;
 		}
-		if (at >= len) { continue; }
+		if (at >= len) { return; }
 		if (cpd_differs<CPD_THREADS>(v.packed + o0 + at, w.packed + c0 + at, (upto < len ? upto : len) - at, tid)) { flag[g] = 1u; }
-	}
+	});
 }
 
 // whether accepted resources g and c are equal, by the whole block (every thread calls it and gets the same answer): the lengths, then
 // row by row the stored lengths and the CRC words, then the stored bytes
-__device__ bool dd_equal(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, const SpliceView& v3, uint32_t with_crc, uint32_t g, uint32_t c)
+__device__ bool dd_equal(const SpliceSrc& src, uint32_t with_crc, uint32_t g, uint32_t c)
 {
 	const uint32_t tid = threadIdx.x;
 	u64 s, r, sc, rc;
-	dd_locate(v0, v1, v2, g, s, r); dd_locate(v0, v1, v2, c, sc, rc);
-	const SpliceView v = sp_view(v0, v1, v2, v3, s), w = sp_view(v0, v1, v2, v3, sc);
+	dd_locate(src, g, s, r); dd_locate(src, c, sc, rc);
+	const SpliceView v = sp_view(src, s), w = sp_view(src, sc);
 	if (v.res_len[r] != w.res_len[rc]) { return false; }
 	const u64 f = v.first[r], rows = v.first[r + 1u] - f, fc = w.first[rc];
 	bool d = false;
@@ -206,10 +177,9 @@ __device__ bool dd_equal(const SpliceView& v0, const SpliceView& v1, const Splic
 
 // Settle and emit, one block. The representatives the flags decide (a refused resource: itself; its key's minimum: itself; a confirmed
 // one: the minimum) and the list of the REFUTED -- accepted, not the minimum, not equal to it -- in ascending order; count[3] is its
-// length. The refuted are then answered exactly, one after the other: equal resources share their key, so the only resources a refuted
-// one can still be equal to are the earlier refuted ones of its slot that stayed their own representative. Then the scan over
-// rep[g] == g: new_index, pick with its padding up to 2 n_max, count.
-__global__ __launch_bounds__(DV_THREADS) void dd_settle_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t n_max, uint32_t with_crc,
+// length. The refuted are then answered exactly (settle_refuted). Then the scan over rep[g] == g: new_index, pick with its padding up to
+// 2 n_max, count.
+__global__ __launch_bounds__(DV_THREADS) void dd_settle_kernel(SpliceSrc src, uint32_t n, uint32_t n_max, uint32_t with_crc,
                                                               const uint32_t* __restrict__ cand, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ slot_of,
                                                               uint32_t* rlist, u64* rep, u64* new_index, u64* __restrict__ pick,
                                                               u64* __restrict__ count)
@@ -230,26 +200,15 @@ __global__ __launch_bounds__(DV_THREADS) void dd_settle_kernel(SpliceView v0, Sp
 		dv_block_scan<1>(a, nref, s_w);
 		if (refuted) { rlist[a[0] - 1u] = g; }
 	}
-	__syncthreads();                                                     // rlist and rep are read back below, by other threads of this block
-	for (u64 i = 0; i < nref[0]; ++i) {
-		const uint32_t g = rlist[i];
-		uint32_t to = g;
-		for (u64 j = 0; j < i; ++j) {
-			const uint32_t c = rlist[j];
-			if (slot_of[c] == slot_of[g] && rep[c] == c && dd_equal(v0, v1, v2, v3, with_crc, g, c)) { to = c; break; }
-		}
-		__syncthreads();                                                   // (every thread has read rep before one of them writes it)
-		if (tid == 0) { rep[g] = to; }
-		__syncthreads();
-	}
+	settle_refuted(rlist, nref[0], slot_of, rep, [&](uint32_t g, uint32_t c) { return dd_equal(src, with_crc, g, c); });
 	u64 tot[2] = {0, 0};                                                   // unique resources | stored bytes of the others
 	for (uint32_t base = 0; base < n; base += DV_THREADS) {
 		const uint32_t g = base + tid;
 		const bool live = g < n, uniq = live && rep[g] == g;
 		u64 s = 0, r = 0, saved = 0;
 		if (live) {
-			dd_locate(v0, v1, v2, g, s, r);
-			if (!uniq) { const SpliceView v = sp_view(v0, v1, v2, v3, s); saved = v.off[v.first[r + 1u]] - v.off[v.first[r]]; }   // (accepted: its offsets only grow)
+			dd_locate(src, g, s, r);
+			if (!uniq) { const SpliceView v = sp_view(src, s); saved = v.off[v.first[r + 1u]] - v.off[v.first[r]]; }   // (accepted: its offsets only grow)
 		}
 		u64 a[2] = {uniq ? 1u : 0u, saved};
 		dv_block_scan<2>(a, tot, s_w);
@@ -261,27 +220,21 @@ __global__ __launch_bounds__(DV_THREADS) void dd_settle_kernel(SpliceView v0, Sp
 	if (tid == 0) { count[0] = tot[0]; count[1] = n; count[2] = tot[1]; count[3] = nref[0]; }
 }
 
-static dim3 dd_grid(u64 items, uint32_t per_block, uint32_t blocks)
-{
-	const u64 need = (items + per_block - 1u) / per_block;
-	return dim3((uint32_t)(need < blocks ? need : blocks));
-}
-
 void launch_dedup_clear(hipStream_t st, u64 slots, u64* tkey, uint32_t* tmin, uint32_t blocks)
 {
-	hipLaunchKernelGGL(dd_clear_kernel, dd_grid(slots, 256u, blocks), dim3(256), 0, st, slots, tkey, tmin);
+	hipLaunchKernelGGL(dd_clear_kernel, fixed_grid(slots, 256u, blocks), dim3(256), 0, st, slots, tkey, tmin);
 }
 
 void launch_dedup_rule3(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t rows_max, const u64* ufirst, int32_t* status, uint32_t blocks)
 {
-	hipLaunchKernelGGL(dd_rows_kernel<false>, dd_grid(rows_max, 256u, blocks), dim3(256), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, 0u, ufirst, static_cast<u64*>(nullptr), status);
+	hipLaunchKernelGGL(dd_rows_kernel<false>, fixed_grid(rows_max, 256u, blocks), dim3(256), 0, st, src, n, 0u, ufirst, static_cast<u64*>(nullptr), status);
 }
 
 void launch_dedup_judge(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, const DedupTab& t, int32_t* status, uint32_t blocks)
 {
 	if (n_max == 0) { return; }
 	launch_dedup_clear(st, t.slots, t.tkey, t.tmin, blocks);
-	hipLaunchKernelGGL(dd_seed_kernel, dim3(1), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, shift, t.ufirst, t.key, t.flag, status);
+	hipLaunchKernelGGL(dd_seed_kernel, dim3(1), dim3(DV_THREADS), 0, st, src, n, shift, t.ufirst, t.key, t.flag, status);
 	if (rows_max == 0) { return; }
 	launch_dedup_rule3(st, src, n, rows_max, t.ufirst, status, blocks);
 }
@@ -290,23 +243,23 @@ void launch_dedup_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_
 {
 	if (n_max == 0) { return; }
 	if (rows_max) {
-		hipLaunchKernelGGL(dd_rows_kernel<true>, dd_grid(rows_max, 256u, blocks), dim3(256), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, with_crc ? 1u : 0u, t.ufirst, t.key, status);
+		hipLaunchKernelGGL(dd_rows_kernel<true>, fixed_grid(rows_max, 256u, blocks), dim3(256), 0, st, src, n, with_crc ? 1u : 0u, t.ufirst, t.key, status);
 	}
-	hipLaunchKernelGGL(dd_insert_kernel, dd_grid(n_max, 256u, blocks), dim3(256), 0, st, n, t.slots, t.key, status, t.tkey, t.tmin, t.slot_of);
-	hipLaunchKernelGGL(dd_cand_kernel, dd_grid(n_max, 256u, blocks), dim3(256), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, status, t.tmin, t.slot_of, t.cand, t.flag);
+	hipLaunchKernelGGL(dd_insert_kernel, fixed_grid(n_max, 256u, blocks), dim3(256), 0, st, n, t.slots, t.key, status, t.tkey, t.tmin, t.slot_of);
+	hipLaunchKernelGGL(dd_cand_kernel, fixed_grid(n_max, 256u, blocks), dim3(256), 0, st, src, n, status, t.tmin, t.slot_of, t.cand, t.flag);
 }
 
 void launch_dedup_confirm(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, bool with_crc, const DedupTab& t, uint32_t blocks)
 {
 	if (n_max == 0 || rows_max == 0) { return; }
 	const uint32_t ppu_shift = shift > DD_PIECE_SHIFT ? shift - DD_PIECE_SHIFT : 0u;
-	hipLaunchKernelGGL(dd_confirm_kernel, dd_grid((u64)rows_max << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, ppu_shift,
+	hipLaunchKernelGGL(dd_confirm_kernel, fixed_grid((u64)rows_max << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, src, n, ppu_shift,
 	                   with_crc ? 1u : 0u, t.ufirst, t.cand, t.flag);
 }
 
 void launch_dedup_settle(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, bool with_crc, const DedupTab& t, u64* rep, u64* new_index, u64* pick, u64* count)
 {
-	hipLaunchKernelGGL(dd_settle_kernel, dim3(1), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, n_max, with_crc ? 1u : 0u, t.cand, t.flag, t.slot_of, t.rlist,
+	hipLaunchKernelGGL(dd_settle_kernel, dim3(1), dim3(DV_THREADS), 0, st, src, n, n_max, with_crc ? 1u : 0u, t.cand, t.flag, t.slot_of, t.rlist,
 	                   rep, new_index, pick, count);
 }
 

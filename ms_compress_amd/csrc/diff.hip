@@ -4,7 +4,7 @@
 // made for extents takes: the changed blocks alone (the delta), and base + delta put together again (the patch). Everything but one pass
 // reads the tables alone; the only pass over the data is the compare that confirms an unchanged block. The two views travel by value in
 // the kernel arguments, as a splicer's. DESIGN.md 4.16.
-#include "kernels.h"
+#include "rowpass.h"
 
 namespace msc {
 
@@ -12,45 +12,27 @@ namespace msc {
 #define DF_REFUTED 2u                                      // ... and its tables said otherwise: the stored bytes did (always with DF_CHANGED)
 #define DF_NO_BASE (~(u64)0)
 
-// Seed, one block, in the shape of sp_layout_kernel and dd_seed_kernel: per pair rule 1, the table checks of rule 2 (the new resource
-// before the base resource within each), the room of rule 3 and the status, and ufirst (n_pair + 1): the new rows of the pairs that passed,
-// numbered densely in pair order -- this pass's own running sum, so that a damaged block_first cannot send the row passes' search astray.
-__global__ __launch_bounds__(DV_THREADS) void df_seed_kernel(SpliceView base, SpliceView next, uint32_t n_pair, uint32_t nbn, uint32_t shift, const u64* __restrict__ pair,
+// Seed, one block: per pair rule 1, the table checks of rule 2 (the new resource before the base resource within each), the room of
+// rule 3 and the status, and ufirst (n_pair + 1): the new rows of the pairs that passed, numbered densely in pair order. src: base, next.
+// The two sides are one loop over a lane's index into src: written out side by side the kernel spills eight scalar registers, whichever
+// way the views reach it. The loop costs the seed 0.5 us of 8.4 on an MI355X: the base side's loads follow the new side's.
+__global__ __launch_bounds__(DV_THREADS) void df_seed_kernel(SpliceSrc src, uint32_t n_pair, uint32_t nbn, uint32_t shift, const u64* __restrict__ pair,
                                                             u64* __restrict__ ufirst, int32_t* __restrict__ status)
 {
-	__shared__ u64 s_w[1][DV_WAVES];
-	const uint32_t tid = threadIdx.x;
-	const u64 B = (u64)1 << shift;
-	u64 run[1] = {0}, rows[1] = {0};
-	if (tid == 0) { ufirst[0] = 0; }
-	for (uint32_t at = 0; at < n_pair; at += DV_THREADS) {
-		const uint32_t p = at + tid;
-		const bool live = p < n_pair;
-		u64 n = 0;
+	seed_numbering<1>(n_pair, nbn, 0, ufirst, status, [&](uint32_t p, u64& rows, bool&) {
 		int32_t st = 0;
-		if (live) {
-			const u64 a = pair[2u * (u64)p], b = pair[2u * (u64)p + 1u];
-			const bool with_a = a != DF_NO_BASE;
-			if (b >= next.n_res || (with_a && a >= base.n_res)) { st = -2; }                       // rule 1: no table entry of the pair is read
-			else {
-				const u64 f0 = next.first[b], f1 = next.first[b + 1u];
-				u64 g0 = 0, g1 = 0;
-				if (with_a) { g0 = base.first[a]; g1 = base.first[a + 1u]; }
-				if (f0 > f1 || f1 > next.nbt || g0 > g1 || g1 > base.nbt) { st = -2; }               // rule 2, dedup's rule 1
-				else {
-					const u64 L = next.res_len[b], La = with_a ? base.res_len[a] : 0;
-					const bool ok_b = f1 - f0 == (L >> shift) + ((L & (B - 1u)) ? 1u : 0u), ok_a = g1 - g0 == (La >> shift) + ((La & (B - 1u)) ? 1u : 0u);
-					if (ok_b && ok_a) { n = f1 - f0; } else { st = -3; }                              // rule 2, dedup's rule 2
-				}
-			}
+		for (uint32_t side = 2; side-- && st != -2; ) {                       // the new resource, then the base resource
+			const u64 r = pair[2u * (u64)p + side];
+			if (side == 0 && r == DF_NO_BASE) { break; }
+			const SpliceView& v = sp_view(src, side);
+			u64 f0, n, L;
+			const int32_t s1 = r < v.n_res ? view_rows(v, r, shift, f0, n, L) : -2;   // rule 1: no table entry of a resource the view does not have is read
+			if (side) { rows = n; }
+			if (s1 == -2 || st == 0) { st = s1; }                               // rule 2: rule 1 of either side before rule 2 of either
 		}
-		u64 t[1] = {n};
-		dv_block_scan<1>(t, run, s_w);
-		if (n && t[0] > nbn) { st = -2; n = 0; }                              // rule 3: the total includes this pair and the ones refused here
-		u64 r[1] = {n};
-		dv_block_scan<1>(r, rows, s_w);
-		if (live) { ufirst[p + 1u] = r[0]; status[p] = st; }
-	}
+		if (st) { rows = 0; }
+		return st;
+	});
 }
 
 // Row verdicts from the tables: a fixed grid dealt over the new rows of the numbering, a row finds its pair by binary search in ufirst.
@@ -83,36 +65,25 @@ __global__ __launch_bounds__(256) void df_verdict_kernel(SpliceView base, Splice
 	}
 }
 
-// Confirm, the only pass over data: the (row, piece of 16 KiB) items of the numbering cut into equal slices, one per block of a fixed grid,
-// as dd_confirm_kernel cuts them. A candidate row of an accepted pair has its stored bytes compared with the base row's, the pieces of the
-// slice as one stretch; a mismatch stores changed + refuted into the row's verdict. Every writer stores the same value, so no ordering is
-// needed; a workgroup that finds the row settled skips it, which saves time alone.
+// Confirm, the only pass over data: the slices of the numbering (confirm_slices). A candidate row of an accepted pair has its stored bytes
+// compared with the base row's, the pieces of the slice as one stretch; a mismatch stores changed + refuted into the row's verdict. Every
+// writer stores the same value, so no ordering is needed; a workgroup that finds the row settled skips it, which saves time alone.
 __global__ __launch_bounds__(CPD_THREADS) void df_confirm_kernel(SpliceView base, SpliceView next, uint32_t n_pair, uint32_t ppu_shift, const u64* __restrict__ pair,
                                                                 const u64* __restrict__ ufirst, const int32_t* __restrict__ status, uint32_t* verdict)
 {
 	const uint32_t tid = threadIdx.x;
-	const u64 units = ufirst[n_pair], items = units << ppu_shift;          // (units <= n_blocks_new < 2^31)
-	u64 per = (items + gridDim.x - 1u) / gridDim.x;
-	per = per < DD_SLICE_MIN ? DD_SLICE_MIN : per;
-	const u64 lo = (u64)blockIdx.x * per;
-	if (lo >= items) { return; }
-	const u64 hi = items - lo < per ? items : lo + per;
 	uint32_t p = 0;
 	u64 p_end = 0;                                                         // the rows below p_end that are not below ufirst[p] are p's
 	bool live = false;
-	for (u64 i = lo; i < hi; ) {
-		const u64 u = i >> ppu_shift, nxt = (u + 1u) << ppu_shift, end = nxt < hi ? nxt : hi;   // the row's items in this slice: [i, end)
-		// (a row's last piece runs to the end of the row: nothing bounds a stored length but packed_len)
-		const u64 at = (i - (u << ppu_shift)) << DD_PIECE_SHIFT, upto = end == nxt ? ~(u64)0 : (end - (u << ppu_shift)) << DD_PIECE_SHIFT;
-		i = end;
+	confirm_slices(ufirst[n_pair], ppu_shift, [&](u64 u, u64 at, u64 upto) {  // (units <= n_blocks_new < 2^31)
 		if (u >= p_end) { p = res_of_block(ufirst, n_pair, u); p_end = ufirst[p + 1u]; live = status[p] == 0; }
-		if (!live || verdict[u] != 0) { continue; }                        // a refused pair: no byte of it is read
+		if (!live || verdict[u] != 0) { return; }                          // a refused pair: no byte of it is read
 		const u64 a = pair[2u * (u64)p], b = pair[2u * (u64)p + 1u], k = u - ufirst[p];
 		const u64 j = next.first[b] + k, ja = base.first[a] + k;             // (a candidate: the base has the block)
 		const u64 o0 = next.off[j], len = next.off[j + 1u] - o0, c0 = base.off[ja];   // (a candidate: equal stored lengths)
-		if (at >= len) { continue; }
+		if (at >= len) { return; }
 		if (cpd_differs<CPD_THREADS>(next.packed + o0 + at, base.packed + c0 + at, (upto < len ? upto : len) - at, tid)) { verdict[u] = DF_CHANGED | DF_REFUTED; }
-	}
+	});
 }
 
 // What row u of the numbering is to the run passes. A row of a pair that a row check refused is no row at all.
@@ -135,53 +106,21 @@ __device__ __forceinline__ DfRow df_row(uint32_t n_pair, const u64* __restrict__
 	return r;
 }
 
-// Runs, the tiled layout of splice by extents. Tile g of DF_TILE rows, eight words: the sums of run starts, changed-run starts, changed
-// blocks, changed stored bytes, rows of accepted pairs and refuted rows; then two maxima -- the last row of the tile that starts a run, + 1,
-// and the tile's count of changed blocks in front of the last row of the tile that is the first of its pair, + 1 (0: the tile has none).
+// Runs (RunScan). Tile g of ROW_TILE rows, eight words: the sums of run starts, changed-run starts, changed blocks, changed stored bytes,
+// rows of accepted pairs and refuted rows; then two maxima -- the last row of the tile that starts a run, + 1, and the tile's count of
+// changed blocks in front of the last row of the tile that is the first of its pair, + 1 (0: the tile has none).
 __global__ __launch_bounds__(DV_THREADS) void df_tile_kernel(SpliceView next, uint32_t n_pair, const u64* __restrict__ pair, const u64* __restrict__ ufirst,
                                                             const int32_t* __restrict__ status, const uint32_t* __restrict__ verdict, u64* __restrict__ tsum)
 {
 	__shared__ u64 s_w[6][DV_WAVES];
-	const u64 u = (u64)blockIdx.x * DF_TILE + threadIdx.x;
+	const u64 u = (u64)blockIdx.x * ROW_TILE + threadIdx.x;
 	const DfRow r = df_row(n_pair, ufirst, status, verdict, u);
 	u64 bytes = 0;
 	if (r.live && r.changed) { const u64 j = next.first[pair[2u * (u64)r.p + 1u]] + r.k; bytes = next.off[j + 1u] - next.off[j]; }
 	u64 a[6] = {r.starts ? 1u : 0u, r.starts && r.changed ? 1u : 0u, r.live && r.changed ? 1u : 0u, bytes, r.live ? 1u : 0u, r.refuted ? 1u : 0u}, sum[6] = {0, 0, 0, 0, 0, 0};
 	dv_block_scan<6>(a, sum, s_w);
-	u64 m0 = r.starts ? u + 1u : 0, m1 = r.live && r.k == 0 ? a[2] - (r.changed ? 1u : 0u) + 1u : 0, c0 = 0, c1 = 0;
-	dv_block_max(m0, c0, s_w[0]);
-	dv_block_max(m1, c1, s_w[0]);
-	if (threadIdx.x == 0) {
-		u64* t = tsum + 8u * (u64)blockIdx.x;
-		#pragma unroll
-		for (uint32_t i = 0; i < 6u; ++i) { t[i] = sum[i]; }
-		t[6] = c0; t[7] = c1;
-	}
-}
-
-// the running sums and maxima of the tiles' words, in place (one workgroup); the second maximum becomes a count over the whole numbering
-__global__ __launch_bounds__(DV_THREADS) void df_tilescan_kernel(uint32_t tiles, u64* tsum)
-{
-	__shared__ u64 s_w[6][DV_WAVES];
-	u64 run[6] = {0, 0, 0, 0, 0, 0}, c0 = 0, c1 = 0;
-	for (uint32_t at = 0; at < tiles; at += DV_THREADS) {
-		const uint32_t g = at + threadIdx.x;
-		const bool live = g < tiles;
-		u64 a[6], m0 = 0, m1 = 0;
-		#pragma unroll
-		for (uint32_t i = 0; i < 6u; ++i) { a[i] = live ? tsum[8u * g + i] : 0; }
-		const u64 own = a[2];
-		if (live) { m0 = tsum[8u * g + 6u]; m1 = tsum[8u * g + 7u]; }
-		dv_block_scan<6>(a, run, s_w);
-		if (m1) { m1 += a[2] - own; }                                      // the changed blocks in front of the tile
-		dv_block_max(m0, c0, s_w[0]);
-		dv_block_max(m1, c1, s_w[0]);
-		if (live) {
-			#pragma unroll
-			for (uint32_t i = 0; i < 6u; ++i) { tsum[8u * g + i] = a[i]; }
-			tsum[8u * g + 6u] = m0; tsum[8u * g + 7u] = m1;
-		}
-	}
+	u64 m[2] = {r.starts ? u + 1u : 0, r.live && r.k == 0 ? a[2] - (r.changed ? 1u : 0u) + 1u : 0};
+	RunScan<6>::tile<6>(tsum, sum, m, s_w[0]);
 }
 
 // The rows again, with the sums in front of the tile. The row that ENDS a run writes its extents, whole: the run's first row is the
@@ -193,17 +132,14 @@ __global__ __launch_bounds__(DV_THREADS) void df_runs_kernel(uint32_t n_pair, co
                                                             u64* __restrict__ delta_ext, u64* __restrict__ patch_ext)
 {
 	__shared__ u64 s_w[3][DV_WAVES];
-	const u64 u = (u64)blockIdx.x * DF_TILE + threadIdx.x;
-	const u64* before = tsum + 8u * (u64)(blockIdx.x ? blockIdx.x - 1u : 0u);
+	const u64 u = (u64)blockIdx.x * ROW_TILE + threadIdx.x;
 	const DfRow r = df_row(n_pair, ufirst, status, verdict, u);
 	const u64 own[3] = {r.starts ? 1u : 0u, r.starts && r.changed ? 1u : 0u, r.live && r.changed ? 1u : 0u};
-	u64 a[3] = {own[0], own[1], own[2]}, sum[3] = {0, 0, 0}, c0 = 0, c1 = 0;
-	if (blockIdx.x) { sum[0] = before[0]; sum[1] = before[1]; sum[2] = before[2]; c0 = before[6]; c1 = before[7]; }
-	dv_block_scan<3>(a, sum, s_w);
-	u64 m0 = r.starts ? u + 1u : 0, m1 = r.live && r.k == 0 ? a[2] - own[2] + 1u : 0;
-	dv_block_max(m0, c0, s_w[0]);
+	u64 a[3], c1 = blockIdx.x ? tsum[8u * (u64)(blockIdx.x - 1u) + 7u] : 0;
+	const u64 m0 = RunScan<3>::head<6>(tsum, u, own, a, s_w);
+	u64 m1 = r.live && r.k == 0 ? a[2] - own[2] + 1u : 0;
 	dv_block_max(m1, c1, s_w[0]);
-	if (u < ufirst[n_pair] && r.k == 0) { pfirst[3u * (u64)r.p] = a[0] - own[0]; pfirst[3u * (u64)r.p + 1u] = a[1] - own[1]; pfirst[3u * (u64)r.p + 2u] = a[2] - own[2]; }
+	if (u < ufirst[n_pair] && r.k == 0) { RunScan<3>::front(pfirst + 3u * (u64)r.p, a, own); }
 	if (!r.ends) { return; }
 	const u64 u0 = m0 - 1u, cnt = u - u0 + 1u, k0 = u0 - ufirst[r.p];          // the run [u0, u]: a run lies in one pair
 	u64* pe = patch_ext + 4u * (a[0] - 1u);                                // (fewer runs than rows: inside 4 n_blocks_new)
@@ -216,8 +152,7 @@ __global__ __launch_bounds__(DV_THREADS) void df_runs_kernel(uint32_t n_pair, co
 	}
 }
 
-// Counts, one thread per pair and one more: the counts in front of pair p are those its first row left -- the first row of the next pair
-// that has rows, for a pair without --, or the totals behind the last row.
+// Counts, one thread per pair and one more (counts_in_front): what lies in front of pair p and of pair p + 1.
 __global__ __launch_bounds__(256) void df_counts_kernel(uint32_t n_pair, uint32_t tiles, const u64* __restrict__ ufirst, const u64* __restrict__ tsum, const u64* __restrict__ pfirst,
                                                        u64* __restrict__ delta_first, u64* __restrict__ patch_first, u64* __restrict__ changed, u64* __restrict__ count)
 {
@@ -226,51 +161,42 @@ __global__ __launch_bounds__(256) void df_counts_kernel(uint32_t n_pair, uint32_
 	u64 tot[6] = {0, 0, 0, 0, 0, 0};
 	if (tiles) { for (uint32_t i = 0; i < 6u; ++i) { tot[i] = total[i]; } }
 	for (u64 p = (u64)blockIdx.x * 256u + threadIdx.x; p <= n_pair; p += (u64)gridDim.x * 256u) {
-		u64 at[2][3];
-		for (uint32_t i = 0; i < 2u; ++i) {
-			const u64 row = ufirst[p + i < n_pair ? p + i : n_pair];
-			if (row >= units) { at[i][0] = tot[0]; at[i][1] = tot[1]; at[i][2] = tot[2]; }
-			else { const u64* f = pfirst + 3u * (u64)res_of_block(ufirst, n_pair, row); at[i][0] = f[0]; at[i][1] = f[1]; at[i][2] = f[2]; }
-		}
-		if (patch_first) { patch_first[p] = at[0][0]; }
-		if (delta_first) { delta_first[p] = at[0][1]; }
-		if (p < n_pair) { changed[p] = at[1][2] - at[0][2]; }
+		u64 at[3], behind[3];
+		counts_in_front(ufirst, n_pair, units, pfirst, tot, ufirst[p], at);
+		counts_in_front(ufirst, n_pair, units, pfirst, tot, ufirst[p < n_pair ? p + 1u : n_pair], behind);
+		if (patch_first) { patch_first[p] = at[0]; }
+		if (delta_first) { delta_first[p] = at[1]; }
+		if (p < n_pair) { changed[p] = behind[2] - at[2]; }
 		else { count[0] = tot[2]; count[1] = tot[4]; count[2] = tot[3]; count[3] = tot[5]; }
 	}
 }
 
-static dim3 df_grid(u64 items, uint32_t per_block, uint32_t blocks)
-{
-	const u64 need = (items + per_block - 1u) / per_block;
-	return dim3((uint32_t)(need < blocks ? need : blocks));
-}
-
 void launch_diff_seed(hipStream_t st, const SpliceView& base, const SpliceView& next, uint32_t n_pair, uint32_t nbn, uint32_t shift, const u64* pair, const DiffTab& t, int32_t* status)
 {
-	hipLaunchKernelGGL(df_seed_kernel, dim3(1), dim3(DV_THREADS), 0, st, base, next, n_pair, nbn, shift, pair, t.ufirst, status);
+	hipLaunchKernelGGL(df_seed_kernel, dim3(1), dim3(DV_THREADS), 0, st, SpliceSrc{{base, next}}, n_pair, nbn, shift, pair, t.ufirst, status);
 }
 
 void launch_diff_verdicts(hipStream_t st, const SpliceView& base, const SpliceView& next, uint32_t n_pair, uint32_t nbn, uint32_t shift, bool with_crc, const u64* pair,
                           const DiffTab& t, int32_t* status, uint32_t blocks)
 {
-	hipLaunchKernelGGL(df_verdict_kernel, df_grid(nbn, 256u, blocks), dim3(256), 0, st, base, next, n_pair, shift, with_crc ? 1u : 0u, pair, t.ufirst, t.verdict, status);
+	hipLaunchKernelGGL(df_verdict_kernel, fixed_grid(nbn, 256u, blocks), dim3(256), 0, st, base, next, n_pair, shift, with_crc ? 1u : 0u, pair, t.ufirst, t.verdict, status);
 }
 
 void launch_diff_confirm(hipStream_t st, const SpliceView& base, const SpliceView& next, uint32_t n_pair, uint32_t nbn, uint32_t shift, const u64* pair, const DiffTab& t,
                          const int32_t* status, uint32_t blocks)
 {
 	const uint32_t ppu_shift = shift > DD_PIECE_SHIFT ? shift - DD_PIECE_SHIFT : 0u;
-	hipLaunchKernelGGL(df_confirm_kernel, df_grid((u64)nbn << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, base, next, n_pair, ppu_shift, pair, t.ufirst, status, t.verdict);
+	hipLaunchKernelGGL(df_confirm_kernel, fixed_grid((u64)nbn << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, base, next, n_pair, ppu_shift, pair, t.ufirst, status, t.verdict);
 }
 
 void launch_diff_tilescan(hipStream_t st, uint32_t tiles, u64* tsum)
 {
-	hipLaunchKernelGGL(df_tilescan_kernel, dim3(1), dim3(DV_THREADS), 0, st, tiles, tsum);
+	hipLaunchKernelGGL((rows_tilescan_kernel<6, 2>), dim3(1), dim3(DV_THREADS), 0, st, tiles, tsum);
 }
 
 void launch_diff_runs(hipStream_t st, const SpliceView& next, uint32_t n_pair, uint32_t nbn, const u64* pair, const DiffTab& t, const int32_t* status, u64* delta_ext, u64* patch_ext)
 {
-	const uint32_t tiles = diff_row_tiles(nbn);
+	const uint32_t tiles = row_tiles(nbn);
 	hipLaunchKernelGGL(df_tile_kernel, dim3(tiles), dim3(DV_THREADS), 0, st, next, n_pair, pair, t.ufirst, status, t.verdict, t.tsum);
 	launch_diff_tilescan(st, tiles, t.tsum);
 	hipLaunchKernelGGL(df_runs_kernel, dim3(tiles), dim3(DV_THREADS), 0, st, n_pair, pair, t.ufirst, status, t.verdict, t.tsum, t.pfirst, delta_ext, patch_ext);
@@ -278,7 +204,7 @@ void launch_diff_runs(hipStream_t st, const SpliceView& next, uint32_t n_pair, u
 
 void launch_diff_counts(hipStream_t st, uint32_t n_pair, uint32_t nbn, const DiffTab& t, u64* delta_first, u64* patch_first, u64* changed, u64* count, uint32_t blocks)
 {
-	hipLaunchKernelGGL(df_counts_kernel, df_grid((u64)n_pair + 1u, 256u, blocks), dim3(256), 0, st, n_pair, n_pair ? diff_row_tiles(nbn) : 0u, t.ufirst, t.tsum, t.pfirst,
+	hipLaunchKernelGGL(df_counts_kernel, fixed_grid((u64)n_pair + 1u, 256u, blocks), dim3(256), 0, st, n_pair, n_pair ? row_tiles(nbn) : 0u, t.ufirst, t.tsum, t.pfirst,
 	                   delta_first, patch_first, changed, count);
 }
 

@@ -221,6 +221,15 @@ void launch_dev_ctables(hipStream_t st, int format, uint32_t n, u64 in_total_max
 void launch_clayout_dev(hipStream_t st, int format, const u64* in_len, uint32_t n, u64 align, u64* off, u64* cap);
 
 // ---- block containers (blocks.hip; mscomp_amd_blocks_*) ----
+// a fixed grid: the workgroups that `items` need at per_block each, `blocks` at most (a kernel on one walks its items with the grid's stride)
+inline dim3 fixed_grid(u64 items, uint32_t per_block, uint32_t blocks)
+{
+	const u64 need = (items + per_block - 1u) / per_block;
+	return dim3((uint32_t)(need < blocks ? need : blocks));
+}
+// the passes tiled over the rows of a table -- of splice by extents, of a transcoder, and the run passes of diff, match and repair (rowpass.h)
+#define ROW_TILE DV_THREADS                            // rows per workgroup (MSCOMP_AMD_SPLICE_ROW_TILE)
+inline uint32_t row_tiles(uint32_t rows) { return (rows + ROW_TILE - 1u) / ROW_TILE; }
 // The container's own tables, in one buffer (blockobj.hip blocks_tab is the only place that knows the layout). n = resources, m = the bound of
 // the blocks; the seven unit columns are what the inner dev plans read and write, with the container's blocks (compress) or the blocks in
 // range (decompress) as units.
@@ -367,6 +376,10 @@ __device__ __forceinline__ SpliceView sp_view(const SpliceView& v0, const Splice
 	return SpliceView{ SP_PICK(packed), SP_PICK(packed_len), SP_PICK(first), SP_PICK(off), SP_PICK(res_len), SP_PICK(crc), SP_PICK(n_res), SP_PICK(nbt) };
 }
 #undef SP_PICK
+// The same for a kernel that takes the sources as ONE argument, a SpliceSrc by value: the compiler then reads a view's field where it lies,
+// in the kernel-argument segment, at the lane's s -- no scratch copy, and not all four views held in scalar registers for the selects (64
+// of 106: the kernels of dedup.hip and match.hip that did spilled up to 38 of them)
+__device__ __forceinline__ const SpliceView& sp_view(const SpliceSrc& src, u64 s) { return src.v[s]; }
 // Shared by dedup.hip and match.hip. Global resource g (< n0 + n1 + n2 + n3) as source and resource: the sources' resources are numbered
 // back to back
 __device__ __forceinline__ void dd_locate(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, u64 g, u64& s, u64& r)
@@ -374,6 +387,7 @@ __device__ __forceinline__ void dd_locate(const SpliceView& v0, const SpliceView
 	s = 0; r = g;
 	if (r >= v0.n_res) { r -= v0.n_res; s = 1; if (r >= v1.n_res) { r -= v1.n_res; s = 2; if (r >= v2.n_res) { r -= v2.n_res; s = 3; } } }
 }
+__device__ __forceinline__ void dd_locate(const SpliceSrc& src, u64 g, u64& s, u64& r) { dd_locate(src.v[0], src.v[1], src.v[2], g, s, r); }
 __device__ __forceinline__ u64 dd_mix(u64 x)                // (splitmix64's finaliser)
 {
 	x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
@@ -398,18 +412,16 @@ void launch_splice_layout(hipStream_t st, const SpliceSrc& src, uint32_t n_src, 
 
 // mscomp_amd_splicer_splice_extents: a new resource is a list of extents (source, resource, first block, block count). The splicer's
 // scratch for it (blockobj.hip splice_ext_tab knows the layout):
-#define SX_TILE DV_THREADS                             // rows per workgroup of the row passes (MSCOMP_AMD_SPLICE_ROW_TILE)
-inline uint32_t splice_row_tiles(uint32_t nbt) { return (nbt + SX_TILE - 1u) / SX_TILE; }
 struct SpliceExtTab {
 	u64* addr;                                         // nbt: where a new row's stored bytes lie (0 = nothing to move): launch_blocks_move
 	u64* ext_row;                                      // n_ext + 1: the running counts of the extent pass, then every extent's first new row
-	u64* tsum;                                         // splice_row_tiles(nbt): the stored bytes of a tile of rows, then their running sum
+	u64* tsum;                                         // row_tiles(nbt): the stored bytes of a tile of rows, then their running sum
 	uint32_t* flag;                                    // 1: the extent table as a whole was refused (rule 0)
 };
 // the extent pass (one block): rules 0-6, new_first (n_res + 1), new_len and status (n_res), new_off[0], t.ext_row, t.flag
 void launch_splice_extents(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n_res, uint32_t n_ext, uint32_t nbt, uint32_t shift, const u64* ext_first,
                            const u64* ext, u64* new_first, u64* new_off, u64* new_len, int32_t* status, const SpliceExtTab& t);
-// behind it, the three-launch scan over the NEW table's rows in tiles of SX_TILE (nbt > 0). tiles: per row its stored length (left in
+// behind it, the three-launch scan over the NEW table's rows in tiles of ROW_TILE (nbt > 0). tiles: per row its stored length (left in
 // new_off[row + 1]), new_crc (nbt, may be null) and t.addr, per tile its sum; tilescan (one block): the running sum of the tile sums; rows:
 // new_off (nbt + 1) and the capacity rule
 void launch_splice_tiles(hipStream_t st, const SpliceSrc& src, uint32_t n_res, uint32_t nbt, const u64* ext_first, const u64* ext, const u64* new_first, u64* new_off,
@@ -448,12 +460,10 @@ void launch_dedup_settle(hipStream_t st, const SpliceSrc& src, uint32_t n, uint3
 // mscomp_amd_deduper_diff, the deduper's second call (diff.hip): which blocks of the new resources differ from the blocks at the same
 // index of the base resources, answered as the delta and the patch extent lists. The scratch of a deduper made for it (blockobj.hip
 // diff_tab knows the layout); n = n_pair, m = n_blocks_new:
-#define DF_TILE DV_THREADS                             // rows per workgroup of the run passes (MSCOMP_AMD_SPLICE_ROW_TILE)
-inline uint32_t diff_row_tiles(uint32_t nbn) { return (nbn + DF_TILE - 1u) / DF_TILE; }
 struct DiffTab {
 	u64* ufirst;                                       // n + 1: first new row of every pair, in a numbering of the new rows of the pairs that passed rules 1-3
 	u64* pfirst;                                       // 3 n: the runs, changed runs and changed blocks in front of the pair's first row
-	u64* tsum;                                         // 8 diff_row_tiles(m): six sums and two maxima per tile of rows, then their running values
+	u64* tsum;                                         // 8 row_tiles(m): six sums and two maxima per tile of rows, then their running values
 	uint32_t* verdict;                                 // m: 1 = a changed block, 3 = one the confirm pass found
 };
 // The call in five stages, seven launches fixed by the creation bounds (two -- seed and counts -- when n_pair or n_blocks_new is 0; the
@@ -467,8 +477,9 @@ void launch_diff_confirm(hipStream_t st, const SpliceView& base, const SpliceVie
                          const int32_t* status, uint32_t blocks);
 // runs (three launches: the tiles' sums, their running values in one block, the rows): delta_ext and patch_ext (4 n_blocks_new each), t.pfirst
 void launch_diff_runs(hipStream_t st, const SpliceView& next, uint32_t n_pair, uint32_t nbn, const u64* pair, const DiffTab& t, const int32_t* status, u64* delta_ext, u64* patch_ext);
-// the middle launch of the runs alone, for a call that lays its tiles out as diff does (repair.hip): per tile eight words -- six sums, the
-// last row that starts a run + 1, a count diff carries behind it (0: none) -- turned into their running values in place (one block)
+// the middle launch of the runs alone, rows_tilescan_kernel<6, 2> (rowpass.h), for a call that lays its tiles out as diff does (repair.hip):
+// per tile eight words -- six sums, the last row that starts a run + 1, a count diff carries behind it (0: none) -- turned into their
+// running values in place (one block)
 void launch_diff_tilescan(hipStream_t st, uint32_t tiles, u64* tsum);
 // counts: delta_first and patch_first (n_pair + 1, may be null when n_pair is 0), changed (n_pair), count (4)
 void launch_diff_counts(hipStream_t st, uint32_t n_pair, uint32_t nbn, const DiffTab& t, u64* delta_first, u64* patch_first, u64* changed, u64* count, uint32_t blocks);
@@ -491,12 +502,10 @@ void launch_repair_counts(hipStream_t st, uint32_t n_res, uint32_t nbn, const Di
 // one of up to three store containers (found), earlier in next (shared) or nowhere (fresh), answered as the delta and the patch extent
 // lists. The views travel as a splicer's, the stores first and next at index n_src. The scratch of a deduper made for it (blockobj.hip
 // match_tab knows the layout); n = n_res_total, m = n_blocks_total, mn = n_blocks_new:
-#define MT_TILE DV_THREADS                             // rows per workgroup of the run passes (MSCOMP_AMD_SPLICE_ROW_TILE)
-inline uint32_t match_row_tiles(uint32_t nbn) { return (nbn + MT_TILE - 1u) / MT_TILE; }
 struct MatchTab {
 	u64* ufirst;                                       // n + 1: first row of every resource, in a numbering of the rows of the resources that passed rules 1, 2 and 4
 	u64* pfirst;                                       // 5 n: per resource of next the patch runs, fresh runs, found, shared and fresh blocks in front of its first row
-	u64* tsum;                                         // 8 match_row_tiles(mn): seven sums and one maximum per tile of next's rows, then their running values
+	u64* tsum;                                         // 8 row_tiles(mn): seven sums and one maximum per tile of next's rows, then their running values
 	u64* tkey;                                         // slots: the key a slot was claimed for (0 = empty)
 	u64* nref;                                         // 1: the refuted rows of the execution
 	uint32_t* tmin;                                    // slots: the smallest row with the slot's key

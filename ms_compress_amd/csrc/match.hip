@@ -3,9 +3,9 @@
 // nowhere, decided on the STORED form -- the stored form of a block depends only on its data, the format and the block size -- and answered
 // as two extent lists a splicer made for extents takes: the blocks seen for the first time (the delta), and stores + delta put together
 // again (the patch). The unit is the ROW: dedup's key table, candidates and confirm pass over the rows of all views instead of their
-// resources, diff's tiled run passes over the rows of next. The views travel by value in the kernel arguments, as a splicer's, the stores
-// first and next behind them. DESIGN.md 4.18.
-#include "kernels.h"
+// resources, diff's tiled run passes over the rows of next. The views travel by value in the kernel arguments, as one SpliceSrc that a lane indexes
+// (kernels.h sp_view), the stores first and next behind them. DESIGN.md 4.18.
+#include "rowpass.h"
 
 namespace msc {
 
@@ -20,57 +20,34 @@ struct MtRow {
 	u64 len, e;                                            // stored length, data length
 	uint32_t crc, x;                                       // CRC word (0 without checksums), global resource
 };
-__device__ __forceinline__ MtRow mt_row_of(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, const SpliceView& v3, uint32_t x, uint32_t shift, uint32_t with_crc,
+__device__ __forceinline__ MtRow mt_row_of(const SpliceSrc& src, uint32_t x, uint32_t shift, uint32_t with_crc,
                                            const u64* __restrict__ ufirst, u64 u)
 {
 	u64 s, r;
-	dd_locate(v0, v1, v2, x, s, r);
-	const SpliceView v = sp_view(v0, v1, v2, v3, s);
+	dd_locate(src, x, s, r);
+	const SpliceView v = sp_view(src, s);
 	const u64 k = u - ufirst[x], j = v.first[r] + k;                       // (j < first[r + 1] <= v.nbt: rule 1)
 	const u64 o0 = v.off[j], L = v.res_len[r] - (k << shift), B = (u64)1 << shift;   // (k is a block of the resource: rule 2)
 	return MtRow{ v.packed + o0, v.off[j + 1u] - o0, L < B ? L : B, with_crc ? v.crc[j] : 0u, x };
 }
-__device__ __forceinline__ MtRow mt_row(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, const SpliceView& v3, uint32_t n, uint32_t shift, uint32_t with_crc,
+__device__ __forceinline__ MtRow mt_row(const SpliceSrc& src, uint32_t n, uint32_t shift, uint32_t with_crc,
                                         const u64* __restrict__ ufirst, u64 u)
 {
-	return mt_row_of(v0, v1, v2, v3, res_of_block(ufirst, n, u), shift, with_crc, ufirst, u);
+	return mt_row_of(src, res_of_block(ufirst, n, u), shift, with_crc, ufirst, u);
 }
 
-// Seed, one block, in the shape of dd_seed_kernel and df_seed_kernel: dedup's rules 1 and 2 per resource, the room of rule 4 -- over all
-// rows against nbt, over next's (the resources from n_store on) against nbn as well --, the status, and ufirst (n + 1): the rows of the
-// resources that passed, numbered densely in resource order.
-__global__ __launch_bounds__(DV_THREADS) void mt_seed_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t n_store, uint32_t nbt, uint32_t nbn,
+// Seed, one block: dedup's rules 1 and 2 per resource, the room of rule 4 -- over all rows against nbt, over next's (the resources from
+// n_store on) against nbn as well --, the status, and ufirst (n + 1): the rows of the resources that passed, numbered densely in
+// resource order.
+__global__ __launch_bounds__(DV_THREADS) void mt_seed_kernel(SpliceSrc src, uint32_t n, uint32_t n_store, uint32_t nbt, uint32_t nbn,
                                                             uint32_t shift, u64* __restrict__ ufirst, int32_t* __restrict__ status)
 {
-	__shared__ u64 s_w[2][DV_WAVES];
-	const uint32_t tid = threadIdx.x;
-	const u64 B = (u64)1 << shift;
-	u64 run[2] = {0, 0}, kept[1] = {0};
-	if (tid == 0) { ufirst[0] = 0; }
-	for (uint32_t base = 0; base < n; base += DV_THREADS) {
-		const uint32_t g = base + tid;
-		const bool live = g < n, of_next = g >= n_store;
-		u64 rows = 0;
-		int32_t st = 0;
-		if (live) {
-			u64 s, r;
-			dd_locate(v0, v1, v2, g, s, r);
-			const SpliceView v = sp_view(v0, v1, v2, v3, s);
-			const u64 f0 = v.first[r], f1 = v.first[r + 1u];
-			if (f0 > f1 || f1 > v.nbt) { st = -2; }                          // rule 1: MSCOMP_ARG_ERROR
-			else {
-				const u64 L = v.res_len[r];
-				rows = f1 - f0;
-				if (rows != (L >> shift) + ((L & (B - 1u)) ? 1u : 0u)) { st = -3; rows = 0; }   // rule 2: MSCOMP_DATA_ERROR
-			}
-		}
-		u64 t[2] = {rows, of_next ? rows : 0};
-		dv_block_scan<2>(t, run, s_w);
-		if (rows && (t[0] > nbt || (of_next && t[1] > nbn))) { st = -2; rows = 0; }   // rule 4: the totals include this resource and the ones refused here
-		u64 a[1] = {rows};
-		dv_block_scan<1>(a, kept, s_w);
-		if (live) { ufirst[g + 1u] = a[0]; status[g] = st; }
-	}
+	seed_numbering<2>(n, nbt, nbn, ufirst, status, [&](uint32_t g, u64& rows, bool& of_next) {
+		u64 s, r, f0, L;
+		dd_locate(src, g, s, r);
+		of_next = g >= n_store;
+		return view_rows(sp_view(src, s), r, shift, f0, rows, L);
+	});
 }
 
 // Keys, a fixed grid dealt over the rows: a row of an accepted resource mixes its key tuple -- data length, stored length, CRC word when
@@ -79,7 +56,7 @@ __global__ __launch_bounds__(DV_THREADS) void mt_seed_kernel(SpliceView v0, Spli
 // holds one key, so two rows share a slot exactly when they share their key, and the minimum does not depend on the order of arrival. The
 // walk is bounded by the slot count: the table has more slots than there are rows, so it ends long before, and on a damaged state it ends
 // all the same -- the row then has no slot and is its own representative.
-__global__ __launch_bounds__(256) void mt_keys_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t shift, uint32_t with_crc, u64 slots,
+__global__ __launch_bounds__(256) void mt_keys_kernel(SpliceSrc src, uint32_t n, uint32_t shift, uint32_t with_crc, u64 slots,
                                                      const u64* __restrict__ ufirst, const int32_t* __restrict__ status, u64* tkey, uint32_t* tmin,
                                                      uint32_t* __restrict__ slot_of, uint32_t* __restrict__ flag)
 {
@@ -88,7 +65,7 @@ __global__ __launch_bounds__(256) void mt_keys_kernel(SpliceView v0, SpliceView 
 		const uint32_t x = res_of_block(ufirst, n, u);
 		uint32_t slot = MT_NONE;
 		if (status[x] == 0) {
-			const MtRow a = mt_row_of(v0, v1, v2, v3, x, shift, with_crc, ufirst, u);
+			const MtRow a = mt_row_of(src, x, shift, with_crc, ufirst, u);
 			u64 w[4];
 			dd_edges(a.p, a.len, w);
 			u64 h = dd_mix(a.e ^ 0x9E3779B97F4A7C15ull);
@@ -108,63 +85,51 @@ __global__ __launch_bounds__(256) void mt_keys_kernel(SpliceView v0, SpliceView 
 	}
 }
 
-// Confirm, the only pass over data: the (row, piece of 16 KiB) items of the numbering cut into equal slices, one per block of a fixed grid,
-// as dd_confirm_kernel cuts them. A row that is not its slot's smallest is compared with that row: the data lengths, the stored lengths,
-// the CRC words, then the pieces of the slice as one stretch of bytes. A mismatch sets the row's flag: every writer stores the same value,
-// so no ordering is needed; a workgroup that finds the flag set skips the row, which saves time alone. The workgroup that holds a row's
-// first piece leaves the representative the tables give in rep -- the candidate, or the row itself where it has none --, for the settle
-// to correct where a flag is set. Rows that follow one another mostly have candidates that do, so both resources are looked up once per
-// resource, not once per row.
-__global__ __launch_bounds__(CPD_THREADS) void mt_confirm_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t shift, uint32_t ppu_shift,
+// Confirm, the only pass over data: the slices of the numbering (confirm_slices). A row that is not its slot's smallest is compared with
+// that row: the data lengths, the stored lengths, the CRC words, then the pieces of the slice as one stretch of bytes. A mismatch sets
+// the row's flag: every writer stores the same value, so no ordering is needed; a workgroup that finds the flag set skips the row, which
+// saves time alone. The workgroup that holds a row's first piece leaves the representative the tables give in rep -- the candidate, or
+// the row itself where it has none --, for the settle to correct where a flag is set. Rows that follow one another mostly have
+// candidates that do, so both resources are looked up once per resource, not once per row.
+__global__ __launch_bounds__(CPD_THREADS) void mt_confirm_kernel(SpliceSrc src, uint32_t n, uint32_t shift, uint32_t ppu_shift,
                                                                 uint32_t with_crc, const u64* __restrict__ ufirst, const uint32_t* __restrict__ slot_of,
                                                                 const uint32_t* __restrict__ tmin, uint32_t* flag, uint32_t* __restrict__ rep)
 {
 	const uint32_t tid = threadIdx.x;
-	const u64 units = ufirst[n], items = units << ppu_shift;               // (units <= n_blocks_total < 2^31)
-	u64 per = (items + gridDim.x - 1u) / gridDim.x;
-	per = per < DD_SLICE_MIN ? DD_SLICE_MIN : per;
-	const u64 lo = (u64)blockIdx.x * per;
-	if (lo >= items) { return; }
-	const u64 hi = items - lo < per ? items : lo + per;
 	uint32_t x = 0, cx = 0;
 	u64 x_end = 0, c_lo = 0, c_end = 0;                                    // the rows below x_end that are not below ufirst[x] are x's; [c_lo, c_end) are cx's
-	for (u64 i = lo; i < hi; ) {
-		const u64 u = i >> ppu_shift, nxt = (u + 1u) << ppu_shift, end = nxt < hi ? nxt : hi;   // the row's items in this slice: [i, end)
-		// (a row's last piece runs to the end of the row: nothing bounds a stored length but packed_len)
-		const u64 at = (i - (u << ppu_shift)) << DD_PIECE_SHIFT, upto = end == nxt ? ~(u64)0 : (end - (u << ppu_shift)) << DD_PIECE_SHIFT;
-		i = end;
+	confirm_slices(ufirst[n], ppu_shift, [&](u64 u, u64 at, u64 upto) {      // (units <= n_blocks_total < 2^31)
 		const uint32_t slot = slot_of[u];
 		const uint32_t c = slot == MT_NONE ? (uint32_t)u : tmin[slot];     // (no slot: a refused resource, no byte of it is read)
 		const bool cand = c < u;                                           // (c > u: a damaged table; the row stands for itself)
 		if (at == 0 && tid == 0) { rep[u] = cand ? c : (uint32_t)u; }
-		if (!cand || flag[u] != 0) { continue; }
+		if (!cand || flag[u] != 0) { return; }
 		if (u >= x_end) { x = res_of_block(ufirst, n, u); x_end = ufirst[x + 1u]; }
 		if (c < c_lo || c >= c_end) { cx = res_of_block(ufirst, n, c); c_lo = ufirst[cx]; c_end = ufirst[cx + 1u]; }
-		const MtRow a = mt_row_of(v0, v1, v2, v3, x, shift, with_crc, ufirst, u), b = mt_row_of(v0, v1, v2, v3, cx, shift, with_crc, ufirst, c);
+		const MtRow a = mt_row_of(src, x, shift, with_crc, ufirst, u), b = mt_row_of(src, cx, shift, with_crc, ufirst, c);
 		if (a.e != b.e || a.len != b.len || a.crc != b.crc) {
 			if (tid == 0) { flag[u] = 1u; }
-			continue;
+			return;
 		}
-		if (at >= a.len) { continue; }
+		if (at >= a.len) { return; }
 		if (cpd_differs<CPD_THREADS>(a.p + at, b.p + at, (upto < a.len ? upto : a.len) - at, tid)) { flag[u] = 1u; }
-	}
+	});
 }
 
 // whether rows g and c of accepted resources are equal, by the whole block (every thread calls it and gets the same answer)
-__device__ bool mt_equal(const SpliceView& v0, const SpliceView& v1, const SpliceView& v2, const SpliceView& v3, uint32_t n, uint32_t shift, uint32_t with_crc,
+__device__ bool mt_equal(const SpliceSrc& src, uint32_t n, uint32_t shift, uint32_t with_crc,
                          const u64* __restrict__ ufirst, uint32_t g, uint32_t c)
 {
-	const MtRow a = mt_row(v0, v1, v2, v3, n, shift, with_crc, ufirst, g), b = mt_row(v0, v1, v2, v3, n, shift, with_crc, ufirst, c);
+	const MtRow a = mt_row(src, n, shift, with_crc, ufirst, g), b = mt_row(src, n, shift, with_crc, ufirst, c);
 	if (a.e != b.e || a.len != b.len || a.crc != b.crc) { return false; }
 	return !__syncthreads_or(cpd_differs<DV_THREADS>(a.p, b.p, a.len, threadIdx.x));
 }
 
 // Settle, one block. The list of the REFUTED -- the rows whose flag the confirm pass set: not the smallest of their slot, not equal to it
 // -- in ascending order, eight rows per thread and step; every other row keeps the representative the confirm pass left. The refuted,
-// their own representatives to begin with, are then answered exactly, one after the other: equal rows share their key, so the only rows
-// a refuted one can still be equal to are the earlier refuted ones of its slot that stayed their own representative.
+// their own representatives to begin with, are then answered exactly (settle_refuted).
 #define MT_SETTLE_ROWS 8u
-__global__ __launch_bounds__(DV_THREADS) void mt_settle_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t shift, uint32_t with_crc,
+__global__ __launch_bounds__(DV_THREADS) void mt_settle_kernel(SpliceSrc src, uint32_t n, uint32_t shift, uint32_t with_crc,
                                                               const u64* __restrict__ ufirst, const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ flag,
                                                               uint32_t* rlist, uint32_t* rep, u64* __restrict__ nref_out)
 {
@@ -182,18 +147,7 @@ __global__ __launch_bounds__(DV_THREADS) void mt_settle_kernel(SpliceView v0, Sp
 		u64 at = a[0] - (u64)__popc(mask);
 		for (uint32_t i = 0; i < MT_SETTLE_ROWS; ++i) { if (mask >> i & 1u) { rlist[at++] = (uint32_t)(u0 + i); rep[u0 + i] = (uint32_t)(u0 + i); } }
 	}
-	__syncthreads();                                                     // rlist and rep are read back below, by other threads of this block
-	for (u64 i = 0; i < nref[0]; ++i) {
-		const uint32_t g = rlist[i];
-		uint32_t to = g;
-		for (u64 j = 0; j < i; ++j) {
-			const uint32_t c = rlist[j];
-			if (slot_of[c] == slot_of[g] && rep[c] == c && mt_equal(v0, v1, v2, v3, n, shift, with_crc, ufirst, g, c)) { to = c; break; }
-		}
-		__syncthreads();                                                   // (every thread has read rep before one of them writes it)
-		if (tid == 0) { rep[g] = to; }
-		__syncthreads();
-	}
+	settle_refuted(rlist, nref[0], slot_of, rep, [&](uint32_t g, uint32_t c) { return mt_equal(src, n, shift, with_crc, ufirst, g, c); });
 	if (tid == 0) { nref_out[0] = nref[0]; }
 }
 
@@ -228,58 +182,31 @@ __device__ __forceinline__ MtRun mt_run(uint32_t n, const u64* __restrict__ ufir
 	return r;
 }
 
-// Runs, the tiled layout of splice by extents and of diff. Tile b of MT_TILE rows of next, eight words: the sums of run starts, fresh-run
-// starts, found, shared and fresh blocks, fresh stored bytes and rows of accepted resources; then a maximum -- the last row of the tile
-// that starts a run, + 1 (0: the tile has none). Every row leaves the fresh rows of its tile in front of it in flocal: with the tiles'
-// running sums that is its rank among all fresh rows, which a shared run in ANOTHER tile asks its representative for.
-__global__ __launch_bounds__(DV_THREADS) void mt_tile_kernel(SpliceView v0, SpliceView v1, SpliceView v2, SpliceView v3, uint32_t n, uint32_t n_store, uint32_t nbn, uint32_t shift,
+// Runs (RunScan). Tile b of ROW_TILE rows of next, eight words: the sums of run starts, fresh-run starts, found, shared and fresh blocks,
+// fresh stored bytes and rows of accepted resources; then a maximum -- the last row of the tile that starts a run, + 1 (0: the tile has
+// none). Every row leaves the fresh rows of its tile in front of it in flocal: with the tiles' running sums that is its rank among all
+// fresh rows, which a shared run in ANOTHER tile asks its representative for.
+__global__ __launch_bounds__(DV_THREADS) void mt_tile_kernel(SpliceSrc src, uint32_t n, uint32_t n_store, uint32_t nbn, uint32_t shift,
                                                             const u64* __restrict__ ufirst, const int32_t* __restrict__ status, const uint32_t* __restrict__ rep,
                                                             u64* __restrict__ tsum, uint32_t* __restrict__ flocal)
 {
 	__shared__ u64 s_w[7][DV_WAVES];
-	const u64 u0 = ufirst[n_store], t = (u64)blockIdx.x * MT_TILE + threadIdx.x;
+	const u64 u0 = ufirst[n_store], t = (u64)blockIdx.x * ROW_TILE + threadIdx.x;
 	const MtRun r = mt_run(n, ufirst, status, rep, u0, t);
 	const bool fresh = r.live && r.cls == MT_FRESH;
-	const u64 bytes = fresh ? mt_row_of(v0, v1, v2, v3, r.g, shift, 0u, ufirst, u0 + t).len : 0;
+	const u64 bytes = fresh ? mt_row_of(src, r.g, shift, 0u, ufirst, u0 + t).len : 0;
 	u64 a[7] = {r.starts ? 1u : 0u, r.starts && fresh ? 1u : 0u, r.live && r.cls == MT_FOUND ? 1u : 0u, r.live && r.cls == MT_SHARED ? 1u : 0u, fresh ? 1u : 0u, bytes,
 	            r.live ? 1u : 0u}, sum[7] = {0, 0, 0, 0, 0, 0, 0};
 	dv_block_scan<7>(a, sum, s_w);
 	if (t < nbn) { flocal[t] = (uint32_t)(a[4] - (fresh ? 1u : 0u)); }
-	u64 m0 = r.starts ? t + 1u : 0, c0 = 0;
-	dv_block_max(m0, c0, s_w[0]);
-	if (threadIdx.x == 0) {
-		u64* w = tsum + 8u * (u64)blockIdx.x;
-		#pragma unroll
-		for (uint32_t i = 0; i < 7u; ++i) { w[i] = sum[i]; }
-		w[7] = c0;
-	}
-}
-
-// the running sums and the running maximum of the tiles' words, in place (one workgroup)
-__global__ __launch_bounds__(DV_THREADS) void mt_tilescan_kernel(uint32_t tiles, u64* tsum)
-{
-	__shared__ u64 s_w[7][DV_WAVES];
-	u64 run[7] = {0, 0, 0, 0, 0, 0, 0}, c0 = 0;
-	for (uint32_t at = 0; at < tiles; at += DV_THREADS) {
-		const uint32_t b = at + threadIdx.x;
-		const bool live = b < tiles;
-		u64 a[7], m0 = live ? tsum[8u * (u64)b + 7u] : 0;
-		#pragma unroll
-		for (uint32_t i = 0; i < 7u; ++i) { a[i] = live ? tsum[8u * (u64)b + i] : 0; }
-		dv_block_scan<7>(a, run, s_w);
-		dv_block_max(m0, c0, s_w[0]);
-		if (live) {
-			#pragma unroll
-			for (uint32_t i = 0; i < 7u; ++i) { tsum[8u * (u64)b + i] = a[i]; }
-			tsum[8u * (u64)b + 7u] = m0;
-		}
-	}
+	u64 m[1] = {r.starts ? t + 1u : 0};
+	RunScan<7>::tile<7>(tsum, sum, m, s_w[0]);
 }
 
 // the fresh rows of next in front of its row t (t < nbn, a row of the numbering)
 __device__ __forceinline__ u64 mt_rank(const u64* __restrict__ tsum, const uint32_t* __restrict__ flocal, u64 t)
 {
-	const u64 b = t / MT_TILE;
+	const u64 b = t / ROW_TILE;
 	return (b ? tsum[8u * (b - 1u) + 4u] : 0) + flocal[t];
 }
 
@@ -293,25 +220,13 @@ __global__ __launch_bounds__(DV_THREADS) void mt_runs_kernel(SpliceView v0, Spli
                                                             u64* __restrict__ delta_ext, u64* __restrict__ patch_ext)
 {
 	__shared__ u64 s_w[5][DV_WAVES];
-	const u64 u0 = ufirst[n_store], t = (u64)blockIdx.x * MT_TILE + threadIdx.x;
-	const u64* before = tsum + 8u * (u64)(blockIdx.x ? blockIdx.x - 1u : 0u);
+	const u64 u0 = ufirst[n_store], t = (u64)blockIdx.x * ROW_TILE + threadIdx.x;
 	const MtRun r = mt_run(n, ufirst, status, rep, u0, t);
 	const bool fresh = r.live && r.cls == MT_FRESH;
 	const u64 own[5] = {r.starts ? 1u : 0u, r.starts && fresh ? 1u : 0u, r.live && r.cls == MT_FOUND ? 1u : 0u, r.live && r.cls == MT_SHARED ? 1u : 0u, fresh ? 1u : 0u};
-	u64 a[5] = {own[0], own[1], own[2], own[3], own[4]}, sum[5] = {0, 0, 0, 0, 0}, c0 = 0;
-	if (blockIdx.x) {
-		#pragma unroll
-		for (uint32_t i = 0; i < 5u; ++i) { sum[i] = before[i]; }
-		c0 = before[7];
-	}
-	dv_block_scan<5>(a, sum, s_w);
-	u64 m0 = r.starts ? t + 1u : 0;
-	dv_block_max(m0, c0, s_w[0]);
-	if (r.valid && r.k == 0) {
-		u64* f = pfirst + 5u * (u64)(r.g - n_store);
-		#pragma unroll
-		for (uint32_t i = 0; i < 5u; ++i) { f[i] = a[i] - own[i]; }
-	}
+	u64 a[5];
+	const u64 m0 = RunScan<5>::head<7>(tsum, t, own, a, s_w);
+	if (r.valid && r.k == 0) { RunScan<5>::front(pfirst + 5u * (u64)(r.g - n_store), a, own); }
 	if (!r.ends) { return; }
 	const u64 t0 = m0 - 1u, cnt = t - t0 + 1u, q = r.g - n_store;             // the run [t0, t]: a run lies in one resource
 	u64* pe = patch_ext + 4u * (a[0] - 1u);                                // (fewer runs than rows: inside 4 n_blocks_new)
@@ -332,67 +247,59 @@ __global__ __launch_bounds__(DV_THREADS) void mt_runs_kernel(SpliceView v0, Spli
 	}
 }
 
-// Counts, one thread per resource of next and one more: the counts in front of resource q are those its first row left -- the first row of
-// the next resource that has rows, for a resource without --, or the totals behind the last row.
+// Counts, one thread per resource of next and one more (counts_in_front, over next's part of the numbering): what lies in front of
+// resource q and of resource q + 1.
 __global__ __launch_bounds__(256) void mt_counts_kernel(uint32_t n, uint32_t n_store, uint32_t tiles, const u64* __restrict__ ufirst, const u64* __restrict__ tsum,
                                                        const u64* __restrict__ pfirst, const u64* __restrict__ nref, u64* __restrict__ delta_first,
                                                        u64* __restrict__ patch_first, u64* __restrict__ cls, u64* __restrict__ count)
 {
-	const u64 units = ufirst[n];
+	const u64 units = tiles ? ufirst[n] : 0;                                // (no tile: no row of next, and nothing left in pfirst)
 	const uint32_t n_next = n - n_store;
+	const u64* nfirst = ufirst + n_store;                                   // first row of every resource of next (n_next + 1)
 	const u64* total = tsum + 8u * (u64)(tiles ? tiles - 1u : 0u);
 	u64 tot[7] = {0, 0, 0, 0, 0, 0, 0};
 	if (tiles) { for (uint32_t i = 0; i < 7u; ++i) { tot[i] = total[i]; } }
 	for (u64 q = (u64)blockIdx.x * 256u + threadIdx.x; q <= n_next; q += (u64)gridDim.x * 256u) {
-		u64 at[2][5];
-		for (uint32_t i = 0; i < 2u; ++i) {
-			const u64 row = ufirst[n_store + (q + i < n_next ? q + i : n_next)];
-			if (row >= units || tiles == 0) { for (uint32_t j = 0; j < 5u; ++j) { at[i][j] = tot[j]; } }
-			else { const u64* f = pfirst + 5u * (u64)(res_of_block(ufirst, n, row) - n_store); for (uint32_t j = 0; j < 5u; ++j) { at[i][j] = f[j]; } }
-		}
-		if (patch_first) { patch_first[q] = at[0][0]; }
-		if (delta_first) { delta_first[q] = at[0][1]; }
-		if (q < n_next) { cls[3u * q] = at[1][2] - at[0][2]; cls[3u * q + 1u] = at[1][3] - at[0][3]; cls[3u * q + 2u] = at[1][4] - at[0][4]; }
+		u64 at[5], behind[5];
+		counts_in_front(nfirst, n_next, units, pfirst, tot, nfirst[q], at);
+		counts_in_front(nfirst, n_next, units, pfirst, tot, nfirst[q < n_next ? q + 1u : n_next], behind);
+		if (patch_first) { patch_first[q] = at[0]; }
+		if (delta_first) { delta_first[q] = at[1]; }
+		if (q < n_next) { cls[3u * q] = behind[2] - at[2]; cls[3u * q + 1u] = behind[3] - at[3]; cls[3u * q + 2u] = behind[4] - at[4]; }
 		else { count[0] = tot[2]; count[1] = tot[3]; count[2] = tot[4]; count[3] = tot[6]; count[4] = tot[5]; count[5] = nref ? nref[0] : 0; }
 	}
 }
 
-static dim3 mt_grid(u64 items, uint32_t per_block, uint32_t blocks)
-{
-	const u64 need = (items + per_block - 1u) / per_block;
-	return dim3((uint32_t)(need < blocks ? need : blocks));
-}
-
 void launch_match_seed(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_store, uint32_t nbt, uint32_t nbn, uint32_t shift, const MatchTab& t, int32_t* status)
 {
-	hipLaunchKernelGGL(mt_seed_kernel, dim3(1), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, n_store, nbt, nbn, shift, t.ufirst, status);
+	hipLaunchKernelGGL(mt_seed_kernel, dim3(1), dim3(DV_THREADS), 0, st, src, n, n_store, nbt, nbn, shift, t.ufirst, status);
 }
 
 void launch_match_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t nbt, uint32_t shift, bool with_crc, const MatchTab& t, const int32_t* status, uint32_t blocks)
 {
-	hipLaunchKernelGGL(mt_keys_kernel, mt_grid(nbt, 256u, blocks), dim3(256), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, shift, with_crc ? 1u : 0u, t.slots, t.ufirst, status,
+	hipLaunchKernelGGL(mt_keys_kernel, fixed_grid(nbt, 256u, blocks), dim3(256), 0, st, src, n, shift, with_crc ? 1u : 0u, t.slots, t.ufirst, status,
 	                   t.tkey, t.tmin, t.slot_of, t.flag);
 }
 
 void launch_match_confirm(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t nbt, uint32_t shift, bool with_crc, const MatchTab& t, uint32_t blocks)
 {
 	const uint32_t ppu_shift = shift > DD_PIECE_SHIFT ? shift - DD_PIECE_SHIFT : 0u;
-	hipLaunchKernelGGL(mt_confirm_kernel, mt_grid((u64)nbt << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, shift, ppu_shift,
+	hipLaunchKernelGGL(mt_confirm_kernel, fixed_grid((u64)nbt << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, src, n, shift, ppu_shift,
 	                   with_crc ? 1u : 0u, t.ufirst, t.slot_of, t.tmin, t.flag, t.rep);
 }
 
 void launch_match_settle(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t shift, bool with_crc, const MatchTab& t)
 {
-	hipLaunchKernelGGL(mt_settle_kernel, dim3(1), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, shift, with_crc ? 1u : 0u, t.ufirst, t.slot_of, t.flag, t.rlist,
+	hipLaunchKernelGGL(mt_settle_kernel, dim3(1), dim3(DV_THREADS), 0, st, src, n, shift, with_crc ? 1u : 0u, t.ufirst, t.slot_of, t.flag, t.rlist,
 	                   t.rep, t.nref);
 }
 
 void launch_match_runs(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n, uint32_t n_store, uint32_t nbn, uint32_t shift, const MatchTab& t, const int32_t* status,
                        u64* delta_ext, u64* patch_ext)
 {
-	const uint32_t tiles = match_row_tiles(nbn);
-	hipLaunchKernelGGL(mt_tile_kernel, dim3(tiles), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n, n_store, nbn, shift, t.ufirst, status, t.rep, t.tsum, t.flocal);
-	hipLaunchKernelGGL(mt_tilescan_kernel, dim3(1), dim3(DV_THREADS), 0, st, tiles, t.tsum);
+	const uint32_t tiles = row_tiles(nbn);
+	hipLaunchKernelGGL(mt_tile_kernel, dim3(tiles), dim3(DV_THREADS), 0, st, src, n, n_store, nbn, shift, t.ufirst, status, t.rep, t.tsum, t.flocal);
+	hipLaunchKernelGGL((rows_tilescan_kernel<7, -1>), dim3(1), dim3(DV_THREADS), 0, st, tiles, t.tsum);
 	hipLaunchKernelGGL(mt_runs_kernel, dim3(tiles), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], n_src, n, n_store, t.ufirst, status, t.rep, t.tsum, t.flocal, t.pfirst,
 	                   delta_ext, patch_ext);
 }
@@ -400,7 +307,7 @@ void launch_match_runs(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uin
 void launch_match_counts(hipStream_t st, uint32_t n, uint32_t n_store, uint32_t nbn, bool settled, const MatchTab& t, u64* delta_first, u64* patch_first, u64* cls, u64* count,
                          uint32_t blocks)
 {
-	hipLaunchKernelGGL(mt_counts_kernel, mt_grid((u64)(n - n_store) + 1u, 256u, blocks), dim3(256), 0, st, n, n_store, match_row_tiles(nbn), t.ufirst, t.tsum, t.pfirst,
+	hipLaunchKernelGGL(mt_counts_kernel, fixed_grid((u64)(n - n_store) + 1u, 256u, blocks), dim3(256), 0, st, n, n_store, row_tiles(nbn), t.ufirst, t.tsum, t.pfirst,
 	                   settled ? t.nref : static_cast<const u64*>(nullptr), delta_first, patch_first, cls, count);
 }
 

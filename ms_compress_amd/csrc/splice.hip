@@ -83,7 +83,7 @@ void launch_splice_layout(hipStream_t st, const SpliceSrc& src, uint32_t n_src, 
 
 // ---- splice by block extents (mscomp_amd_splicer_splice_extents) ----
 // A new resource is a list of extents (source, resource, first block k0, block count c). The extent pass -- one workgroup, extents are few
-// next to rows -- judges them and lays the resources out; the row passes are tiled over a grid of SX_TILE rows per workgroup, the
+// next to rows -- judges them and lays the resources out; the row passes are tiled over a grid of ROW_TILE rows per workgroup, the
 // three-launch scan: tile sums, their scan, the rows. The move is bk_move_kernel, as for picks.
 //
 // The extent column w (n_ext + 1 words) carries every running count of the extent pass, then the extents' first new rows. While the pass
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(DV_THREADS) void sx_tile_kernel(SpliceView v0, Spli
 {
 	__shared__ u64 s_w[1][DV_WAVES];
 	if (flag[0]) { return; }                                           // rule 0 (the same in every thread)
-	const uint32_t j = blockIdx.x * SX_TILE + threadIdx.x;
+	const uint32_t j = blockIdx.x * ROW_TILE + threadIdx.x;
 	u64 len = 0, at = 0;
 	uint32_t crc = 0;
 	if (j < nbt && j < new_first[n_res]) { sx_row(v0, v1, v2, v3, ext, w, ext_first[0], ext_first[n_res], new_crc != nullptr, j, len, at, crc); }
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(DV_THREADS) void sx_tile_kernel(SpliceView v0, Spli
 	if (threadIdx.x == 0) { tsum[blockIdx.x] = sum[0]; }
 }
 
-// the running sum of the tile sums, in place (one workgroup: a tile sum per SX_TILE rows)
+// the running sum of the tile sums, in place (one workgroup: a tile sum per ROW_TILE rows)
 __global__ __launch_bounds__(DV_THREADS) void sx_tilescan_kernel(uint32_t tiles, u64* tsum, const uint32_t* __restrict__ flag)
 {
 	__shared__ u64 s_w[1][DV_WAVES];
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(DV_THREADS) void sx_rows_kernel(uint32_t n_res, uin
                                                             const u64* __restrict__ w, const u64* __restrict__ tsum, const uint32_t* __restrict__ flag)
 {
 	__shared__ u64 s_w[1][DV_WAVES];
-	const uint32_t j = blockIdx.x * SX_TILE + threadIdx.x;
+	const uint32_t j = blockIdx.x * ROW_TILE + threadIdx.x;
 	if (flag[0]) {
 		if (j < nbt) { new_off[j + 1u] = 0; if (new_crc) { new_crc[j] = 0; } }
 		return;
@@ -299,19 +299,19 @@ void launch_splice_extents(hipStream_t st, const SpliceSrc& src, uint32_t n_src,
 void launch_splice_tiles(hipStream_t st, const SpliceSrc& src, uint32_t n_res, uint32_t nbt, const u64* ext_first, const u64* ext, const u64* new_first, u64* new_off,
                          uint32_t* new_crc, const SpliceExtTab& t)
 {
-	hipLaunchKernelGGL(sx_tile_kernel, dim3(splice_row_tiles(nbt)), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n_res, nbt, ext_first, ext, new_first,
+	hipLaunchKernelGGL(sx_tile_kernel, dim3(row_tiles(nbt)), dim3(DV_THREADS), 0, st, src.v[0], src.v[1], src.v[2], src.v[3], n_res, nbt, ext_first, ext, new_first,
 	                   new_off, new_crc, t.addr, t.ext_row, t.tsum, t.flag);
 }
 
 void launch_splice_tilescan(hipStream_t st, uint32_t nbt, const SpliceExtTab& t)
 {
-	hipLaunchKernelGGL(sx_tilescan_kernel, dim3(1), dim3(DV_THREADS), 0, st, splice_row_tiles(nbt), t.tsum, t.flag);
+	hipLaunchKernelGGL(sx_tilescan_kernel, dim3(1), dim3(DV_THREADS), 0, st, row_tiles(nbt), t.tsum, t.flag);
 }
 
 void launch_splice_rows(hipStream_t st, uint32_t n_res, uint32_t nbt, u64 cap, const u64* ext_first, const u64* new_first, u64* new_off, uint32_t* new_crc, int32_t* status,
                         const SpliceExtTab& t)
 {
-	hipLaunchKernelGGL(sx_rows_kernel, dim3(splice_row_tiles(nbt)), dim3(DV_THREADS), 0, st, n_res, nbt, cap, ext_first, new_first, new_off, new_crc, t.addr, status,
+	hipLaunchKernelGGL(sx_rows_kernel, dim3(row_tiles(nbt)), dim3(DV_THREADS), 0, st, n_res, nbt, cap, ext_first, new_first, new_off, new_crc, t.addr, status,
 	                   t.ext_row, t.tsum, t.flag);
 }
 

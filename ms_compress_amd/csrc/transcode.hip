@@ -355,12 +355,12 @@ void launch_tc_first(hipStream_t st, const TcDims& d, const u64* res_len, const 
 void launch_tc_tiles(hipStream_t st, const TcDims& d, const uint8_t* stage, const u64* res_len, bool with_crc, const TranscodeTab& t, const u64* new_first, u64* new_off,
                      uint32_t* new_crc)
 {
-	hipLaunchKernelGGL(tc_tile_kernel, dim3(splice_row_tiles(d.nbn)), dim3(DV_THREADS), 0, st, d, stage, res_len, with_crc, t, new_first, new_off, new_crc);
+	hipLaunchKernelGGL(tc_tile_kernel, dim3(row_tiles(d.nbn)), dim3(DV_THREADS), 0, st, d, stage, res_len, with_crc, t, new_first, new_off, new_crc);
 }
 
 void launch_tc_rows(hipStream_t st, const TcDims& d, u64 cap, const TranscodeTab& t, const u64* new_first, u64* new_off, uint32_t* new_crc, int32_t* status)
 {
-	hipLaunchKernelGGL(tc_rows_kernel, dim3(splice_row_tiles(d.nbn)), dim3(DV_THREADS), 0, st, d, cap, new_first, new_off, new_crc, t.addr, status, t.tsum, t.cnt);
+	hipLaunchKernelGGL(tc_rows_kernel, dim3(row_tiles(d.nbn)), dim3(DV_THREADS), 0, st, d, cap, new_first, new_off, new_crc, t.addr, status, t.tsum, t.cnt);
 }
 
 } // namespace msc

@@ -704,6 +704,26 @@ class ListOuts:
         return got
 
 
+def same_lists(outs, want):
+    """a ListOuts against closed-form expectations, whole and in numpy (ListOuts.compare goes entry by entry in Python lists: not for a
+    call over a million rows): every list named in ``want`` -- the statuses under "status" -- begins with want's entries and holds
+    nothing but its sentinel behind them"""
+    for k, w in want.items():
+        got = outs.status.cpu().numpy() if k == "status" else outs[k].cpu().numpy().view(np.uint64)
+        w = np.asarray(w, dtype=got.dtype).reshape(-1)
+        bad = np.nonzero(got[: len(w)] != w)[0]
+        assert bad.size == 0, (k, "differs at entry", int(bad[0]), int(got[bad[0]]), int(w[bad[0]]))
+        assert (got[len(w):] == (SENT32 if k == "status" else SENT)).all(), (k, "written behind the entries in use")
+
+
+def table_only(ctx, B, rows):
+    """a Container of hand-made tables and no stored byte: resource r has rows[r] whole blocks, each of stored length 0 (packed_len 0,
+    every block_off 0, every checksum 0). The table-only passes of the dedupers take it at a million rows."""
+    nbt = int(sum(rows))
+    return Container.from_host(ctx, FMTS["xpress"], B, b"", np.concatenate([[0], np.cumsum(rows)]), np.zeros(nbt + 1, dtype=np.uint64),
+                               [int(k) * B for k in rows], np.zeros(nbt, dtype=np.uint32))
+
+
 # ---- readers --------------------------------------------------------------------------------------------------------------------------------
 class ReadRig(Container):
     """a container made on the GPU once (ReadRig.make); read() / check() run request batches against it"""

@@ -126,6 +126,23 @@ def test_list_outs_refuses_one_changed_entry(key, at):
         G.ListOuts.compare(got, list_model(), exact=("rep", "ext_first"), prefixes=("ext",))
 
 
+def test_same_lists_is_list_outs_compare_in_numpy():
+    """the closed-form comparison of the million-row tests: the answer, then one changed entry, one written guard and one written status"""
+    torch = pytest.importorskip("torch")
+    want = {"rep": [0, 1], "ext": [0, 0, 0, 2], "status": [0, -3]}
+
+    def outs():
+        o = G.ListOuts(torch.device("cpu"), {"rep": 2, "ext": 8}, 2)
+        o["rep"][:2] = torch.tensor([0, 1]); o["ext"][:4] = torch.tensor([0, 0, 0, 2]); o.status[:2] = torch.tensor([0, -3], dtype=torch.int32)
+        return o
+    G.same_lists(outs(), want)
+    for key, at in (("rep", 1), ("rep", 2), ("ext", 3), ("ext", 4), ("ext", -1), ("status", 1), ("status", -1)):
+        o = outs()
+        (o.status if key == "status" else o[key])[at] = 9
+        with pytest.raises(AssertionError):
+            G.same_lists(o, want)
+
+
 def test_d64_pads_with_zeros_to_the_least_length():
     torch = pytest.importorskip("torch")
     cpu = torch.device("cpu")

@@ -12,7 +12,7 @@ import dedup_model as D
 import diff_model as F
 import read_model as R
 
-from blocks_rig import Container, ListOuts, Spliced, d64, flipped, memo, rand, recipe, soft, FMTS, BLOCKS, MIXED, POISONS, SENT
+from blocks_rig import Container, ListOuts, Spliced, d64, flipped, memo, rand, recipe, same_lists, soft, table_only, FMTS, BLOCKS, MIXED, POISONS, SENT
 
 pytestmark = pytest.mark.gpu
 NO = F.NO_BASE
@@ -167,6 +167,32 @@ def test_tile_boundaries(gpu_ctx):
     mo, outs = check_diff(base, base, [(NO, 0), (1, 1), (NO, 0)], room=rows + 2 * T)      # one run per pair, each longer than a tile
     assert mo["patch_ext"] == [(1, 0, 0, T), (0, 1, 0, rows), (1, 2, 0, T)]
     rebuild(base, base, [(NO, 0), (1, 1), (NO, 0)], mo, outs)
+
+
+def test_tile_scan_second_trip(gpu_ctx):
+    """1024 * 1024 + 3 new rows, hand-made tables and no stored byte: the one-workgroup scan over the tiles' words takes a second trip of
+    1024 tiles. Resource 0 has all rows but three, resource 1 the last three -- its first row is the first of the second trip's first
+    tile --, and neither pair has a base: one changed run per pair. The patch extent of pair 1 starts at block 0 of the delta's
+    resource 1 only if the count of changed blocks in front of the pair is carried over the trips with its running sum. The
+    expectations are closed forms; the same construction at 2 * 1024 + 3 rows is held to the model first, which is what they rest on."""
+    import ms_compress_amd as m
+    B, pairs = 4096, [(NO, 0), (NO, 1)]
+
+    def case(rows):
+        want = {"delta_first": [0, 1, 2], "delta_ext": [0, 0, 0, rows - 3, 0, 1, 0, 3], "patch_first": [0, 1, 2], "patch_ext": [1, 0, 0, rows - 3, 1, 1, 0, 3],
+                "changed": [rows - 3, 3], "count": [rows, rows, 0, 0], "status": [0, 0]}
+        return table_only(gpu_ctx, B, [rows - 3, 3]), want
+
+    con, want = case(2 * 1024 + 3)
+    _, outs = check_diff(con, con, pairs)
+    same_lists(outs, want)
+    rows = 1024 * 1024 + 3
+    con, want = case(rows)
+    dd, outs = m.BlockDeduper.for_diff(gpu_ctx, B, 2, rows), Outs(con.dev, 2, rows)
+    dd.diff(con.view(), con.view(), d_pairs(pairs, con.dev), *outs.tensors())
+    gpu_ctx.stream.synchronize()
+    dd.close()
+    same_lists(outs, want)
 
 
 @pytest.mark.parametrize("B", BLOCKS)

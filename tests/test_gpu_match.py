@@ -11,7 +11,7 @@ import dedup_model as D
 import diff_model as F
 import match_model as T
 import read_model as R
-from blocks_rig import Container, ListOuts, Spliced, d64, memo, rand, recipe, soft, FMTS, POISONS, SENT
+from blocks_rig import Container, ListOuts, Spliced, d64, memo, rand, recipe, same_lists, soft, table_only, FMTS, POISONS, SENT
 
 pytestmark = pytest.mark.gpu
 FOUND, SHARED, FRESH = T.FOUND, T.SHARED, T.FRESH
@@ -243,6 +243,32 @@ def test_tiles(gpu_ctx):
     mo, outs = check_match([], edge)                                                # no store: a shared run of 924 rows whose representatives lie a tile back
     assert mo["patch_ext"] == [(0, 0, 0, TILE), (0, 0, 2, 6), (0, 0, 100, TILE - 100), (0, 0, TILE, tail - (TILE - 100))]
     rebuild([], edge, mo, outs)
+
+
+def test_tile_scan_second_trip(gpu_ctx):
+    """1024 * 1024 + 3 rows of next, hand-made tables and no stored byte, no store: the one-workgroup scan over the tiles' words takes a
+    second trip of 1024 tiles. Every row has the stored length 0, so all share one key: row 0 is fresh, and every later row is a shared
+    run of one row whose representative is row 0 -- a patch extent per row, its place in the list the running sum carried over the
+    trips. The expectations are closed forms; the same construction at 2 * 1024 + 3 rows is held to the model first, which is what
+    they rest on."""
+    import ms_compress_amd as m
+    B = 4096
+
+    def case(rows):
+        want = {"delta_first": [0, 1], "delta_ext": [0, 0, 0, 1], "patch_first": [0, rows], "patch_ext": np.tile(np.array([0, 0, 0, 1], dtype=np.uint64), rows),
+                "cls": [0, rows - 1, 1], "count": [0, rows - 1, 1, rows, 0, 0], "status": [0]}
+        return table_only(gpu_ctx, B, [rows]), want
+
+    con, want = case(2 * TILE + 3)
+    _, outs = check_match([], con)
+    same_lists(outs, want)
+    rows = TILE * TILE + 3
+    con, want = case(rows)
+    dd, outs = m.BlockDeduper.for_match(gpu_ctx, B, 0, 1, rows, rows), Outs(con.dev, 1, 1, rows)
+    dd.match([], con.view(), *outs.tensors())
+    gpu_ctx.stream.synchronize()
+    dd.close()
+    same_lists(outs, want)
 
 
 def test_degenerate(gpu_ctx, cons):

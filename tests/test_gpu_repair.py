@@ -11,7 +11,7 @@ import read_model as R
 import repair_model as P
 from repair_model import GOOD, TABLE, DECODE, CRC, SKIPPED
 
-from blocks_rig import Container, Spliced, d64, i32, memo, recipe, text, FMTS, FILL, POISONS, SENT, SENT32, ST_FILL
+from blocks_rig import Container, Spliced, d64, i32, memo, recipe, same_lists, table_only, text, FMTS, FILL, POISONS, SENT, SENT32, ST_FILL
 from repair_rig import SalvageOuts, check_repair, check_salvage, damaged, rebuild, repair_outs
 
 pytestmark = pytest.mark.gpu
@@ -138,6 +138,34 @@ def test_run_tiles_change_at_their_seams(gpu_ctx, cons):
     mo, outs = check_repair([h, h], [v0, v1])
     assert mo["lost"] == [0, 2, 0] and mo["fixed"] == [0, 52, 0] and mo["ext_first"][2] - mo["ext_first"][1] == 105
     rebuild([h, h], mo, outs)
+
+
+def test_tile_scan_second_trip(gpu_ctx):
+    """1024 * 1024 + 3 rows, hand-made tables and no stored byte: the one-workgroup scan over the tiles' words takes a second trip of
+    1024 tiles. One resource, every verdict GOOD but a DECODE stretch of four rows that straddles row 1024 * 1024 -- the first row of the
+    second trip's first tile --, mended by one mirror: three extents, whose place in the list and whose first rows are the running sum
+    and the running maximum carried from the first trip. The expectations are closed forms; the same construction at 2 * 1024 + 3 rows
+    is held to the model first, which is what the closed forms rest on."""
+    import ms_compress_amd as m
+
+    def case(rows):
+        seam = rows - 3
+        good = np.full(rows, GOOD, dtype=np.uint32)
+        v0 = good.copy(); v0[seam - 2: seam + 2] = DECODE
+        want = {"ext_first": [0, 3], "ext": [0, 0, 0, seam - 2, 1, 0, seam - 2, 4, 0, 0, seam + 2, 1], "fixed": [4], "lost": [0],
+                "count": [4, 0, 0, 0], "status": [0]}
+        return table_only(gpu_ctx, B, [rows]), [v0, good], want
+
+    con, verdicts, want = case(2 * 1024 + 3)
+    _, outs = check_repair([con, con], verdicts)
+    same_lists(outs, want)
+    rows = 1024 * 1024 + 3
+    con, verdicts, want = case(rows)
+    dd, outs = m.BlockDeduper.for_repair(gpu_ctx, B, 2, 1, rows), repair_outs(con.dev, 1, rows)
+    dd.repair([con.view(), con.view()], [i32(v, con.dev) for v in verdicts], *outs.tensors())
+    gpu_ctx.stream.synchronize()
+    dd.close()
+    same_lists(outs, want)
 
 
 def test_more_resources_than_one_scan_pass(gpu_ctx, oracle, cons):
