@@ -1271,6 +1271,99 @@ MSCompStatus mscomp_amd_transcoder_transcode(mscomp_amd_transcoder* tc, const ui
                                              uint32_t* d_new_block_crc /* NULL exactly when d_block_crc is */, int32_t* d_status /* n_res */);
 int          mscomp_amd_transcoder_counts(mscomp_amd_transcoder* tc, uint32_t out[3]);
 
+/* Sync: find the blocks of ONE store container at ANY byte offset of raw new data. diff compares blocks at the same index, match blocks
+ * by content at any index; both decide on the stored form and see only block-aligned data: one byte inserted at the front of a resource
+ * and every block behind it differs. The store's d_block_crc -- zlib's CRC-32 of every block's data -- is the signature rsync would send,
+ * and CRC-32 rolls: with raw(M) the register after M from 0,
+ *   crc32(M[p : p + B]) = raw(M[: p + B]) ^ raw(M[: p]) x^(8B) ^ seed(B)          (mod the CRC polynomial)
+ * so a syncer evaluates the checksum of the B-byte window at every byte position of a batch of raw units in HBM against a key table of the
+ * store's block checksums, confirms the candidates byte for byte against the decoded store blocks, and answers with a recipe the reader
+ * applies: hits -- requests of mscomp_amd_reader_read with their output offsets -- and the literal runs between them.
+ *   Creation:     (ctx, format, block_size, n_res, n_blocks_table, n_units, in_total_max, n_cand_max, flags = 0): the store's format, block
+ *                 size B and table bounds as for mscomp_amd_reader_create; at most n_units raw units of in_total_max bytes together per
+ *                 call; at most n_cand_max candidates are kept, confirmed and answered per call. The checks of every other create, in
+ *                 their order, before the context is used and with *sy cleared: MSCOMP_ARG_ERROR for a null ctx or sy, a format or
+ *                 block_size no container takes, non-zero flags, or n_res, n_blocks_table, n_units or n_cand_max above 0x7FFFFFF0;
+ *                 MSCOMP_MEM_ERROR for in_total_max of 2^50 or more, in_total_max / MSCOMP_AMD_SYNC_TILE + n_units above 0x7FFFFFF0,
+ *                 or where n_cand_max B bytes are more than a dev plan can address.
+ *   Scratch:      all reserved here, once, and never grown; no context buffer and no scratch-hook kind. The reader core -- what
+ *                 mscomp_amd_reader_create reserves for n_req = blocks_max = n_cand_max: an inner decompress dev plan, a cache of
+ *                 n_cand_max B bytes, 88 + 44 bytes of tables per candidate and 4 per block-table entry -- and the syncer's own tables:
+ *                   8 n_res + 12 slots + 40 n_units + 56 n_cand_max + 68 tiles + 4 pieces + 38064 bytes,
+ *                   slots = 2 n_blocks_table + 64 rounded up to a power of two,
+ *                   tiles = in_total_max / MSCOMP_AMD_SYNC_TILE + n_units, pieces = in_total_max / 64 + n_units
+ *                 (a key table of `slots` slots of 12 bytes; the units' numberings; per tile of the scan eight words and
+ *                 a register; per 64 bytes of input one register, raw(unit[: 64 j]); per candidate its position, unit, row, flag and
+ *                 the reader core's request, length and status; a bitmap of 2^18 bits, two per word of the table, and 5 KiB of constants of B: the table that takes
+ *                 a byte out of a window and four that multiply a register by x^(8B), written at creation).
+ *   Sources:      store is ONE HOST view, read on the host, passed by value, only read; store->n_res and store->n_blocks_table must not
+ *                 exceed the creation bounds and d_block_crc is required: otherwise MSCOMP_ARG_ERROR from the call, nothing launched.
+ *                 Several stores: splice them first. Unit u is the d_in_len[u] bytes at d_in + d_in_off[u], at any alignment.
+ *   Rules:        in this order (B, L, first, off as for dedup; M = a unit, len = its length):
+ *                   1. store: dedup's rules 1 and 2 per resource and match's rule 3 per row, into d_res_status (store->n_res entries):
+ *                      MSCOMP_ARG_ERROR for a first entry beyond n_blocks_table or decreasing, MSCOMP_DATA_ERROR for a block count other
+ *                      than ceil(L / B) or a row that is not off[j] <= off[j + 1] <= packed_len. A refused resource contributes no
+ *                      rows. The rows of the accepted resources are numbered densely in resource order. An ELIGIBLE row has B bytes
+ *                      of data; a resource's short last block never takes part. A slot of the key table holds one CRC word and the
+ *                      SMALLEST eligible row that has it (the claim-and-minimum scheme of match's key table);
+ *                   2. units: the dev plans' bounds rule. A unit whose running total of d_in_len, itself included, exceeds in_total_max
+ *                      gets MSCOMP_ARG_ERROR in d_status, no hits and no literal runs; every other unit MSCOMP_OK;
+ *                   3. raw candidates: position p of unit u is one when p + B <= len and the table holds crc32(M[p : p + B]); its row
+ *                      c(u, p) is that slot's row;
+ *                   4. thinning: of a maximal run of consecutive positions p0, p0 + 1, ... that are all raw candidates with the same
+ *                      row, only p0 + i B survive. (Without it a stretch of zeros longer than 2 B makes every position a candidate;
+ *                      thinning leaves the positions a greedy walk would take.) Runs cross every seam of the scan;
+ *                   5. the cap: the thinned candidates, ordered by (unit, position), are ranked by counts and scans, not by atomics;
+ *                      the first n_cand_max are KEPT, the rest dropped. A capped call still answers with a valid recipe, only a
+ *                      poorer one;
+ *                   6. confirm: the rows of the kept candidates are decoded once each, however many candidates share a row, by the
+ *                      reader's own passes over requests (r, k B, B), held to d_block_crc. A kept candidate is CONFIRMED when its row's
+ *                      request is MSCOMP_OK -- decoded (or, stored raw, read) to B bytes with the right CRC-32 -- AND the B bytes of the
+ *                      unit at p equal those bytes, compared in pieces of 16 KiB. Anything else is refuted: a miss, no other row is
+ *                      tried;
+ *                   7. selection, rsync's greedy walk: per unit, over its kept candidates in order of p, a confirmed one with
+ *                      p >= end is a HIT and sets end = p + B; end starts at 0;
+ *                   8. output: hits in (unit, position) order. d_hit_first (n_units + 1) is the exclusive running count of hits per
+ *                      unit, entry n_units the total. For hit i, d_req[3 i ..] = (r, k B, B) and d_req_off[i] = d_in_off[u] + p: the
+ *                      d_req and d_out_off of mscomp_amd_reader_read. The literal runs are the gaps: per unit, in order,
+ *                      d_lit[2 i ..] = (d_in_off[u] + p, length) for every maximal stretch no hit covers; a run of length 0 is not
+ *                      written. d_lit_first (n_units + 1) is indexed as d_hit_first. A unit shorter than B is one literal run, an empty
+ *                      unit has none. Entries of d_req, d_req_off and d_lit at and behind the totals are not written. There are at most
+ *                      n_cand_max hits and at most n_cand_max + n_units literal runs: size d_req (3 n_cand_max), d_req_off (n_cand_max)
+ *                      and d_lit (2 (n_cand_max + n_units)) so;
+ *                   9. counts: d_count[0 .. 7] = raw candidates, thinned, kept, confirmed, hits, literal runs, literal bytes, distinct
+ *                      rows the reader core was asked for. All are the same from run to run.
+ *   Consequence:  fill a buffer with the literal runs copied to their offsets, then run mscomp_amd_reader_read on the store with
+ *                 d_req, d_req_off as d_out_off and capacities of B: the buffer then holds every accepted unit byte for byte at
+ *                 d_in_off[u].
+ *   Counts:       mscomp_amd_syncer_counts gives, for the last execution, out[0] = kept candidates, out[1] = distinct rows,
+ *                 out[2] = hits. It synchronises the ctx stream; returns 0, or -1 for a null argument or a failed read.
+ *   Execution:    asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation, no synchronisation, nothing
+ *                 read back, a launch sequence fixed by the creation bounds: the table and bitmap cleared, the seed (one workgroup),
+ *                 rule 3 and the keys (fixed grids over the rows); the units' table pass (one workgroup); the boundary registers --
+ *                 raw() of every 64-byte piece and every tile of MSCOMP_AMD_SYNC_TILE bytes, the tiles' running values (one
+ *                 workgroup), the pieces' --; the scan, a wave per tile and 64 positions per lane, twice -- a tile pass that counts, a
+ *                 tile scan (one workgroup), a runs pass that writes the kept candidates --; the requests; the reader's admission,
+ *                 inner plan, CRC kernels and fold; the compare; the selection with the lists (one workgroup, a thread per unit).
+ *                 No array is stored per position. The walk along the key table is bounded by its slot count. Legal inside a
+ *                 caller's capture from the first execution, a graph of its own from the second outside one, captured again when an
+ *                 argument changes -- a field of the view counts as an argument. MSCOMP_ARG_ERROR for a null sy, store, d_hit_first,
+ *                 d_lit_first or d_count, and for any other null array the creation bounds give a size above 0.
+ *   Left out:     several stores per call; a second row behind a refuted candidate (a forged or damaged row hides an equal healthy one
+ *                 behind it); short last blocks; non-constant periodic data with a period below B floods the thinned list -- the cap
+ *                 bounds it, and the candidates behind the cap are lost, not retried; hits written as a container. */
+#define MSCOMP_AMD_SYNC_TILE 4096u
+typedef struct mscomp_amd_syncer mscomp_amd_syncer;
+MSCompStatus mscomp_amd_syncer_create(mscomp_amd_ctx* ctx, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table,
+                                      size_t n_units, uint64_t in_total_max, uint64_t n_cand_max, uint32_t flags, mscomp_amd_syncer** sy);
+void         mscomp_amd_syncer_destroy(mscomp_amd_syncer* sy);
+MSCompStatus mscomp_amd_syncer_sync(mscomp_amd_syncer* sy, const mscomp_amd_blocks_view* store /* host, by value, only read */,
+                                    const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                    uint64_t* d_hit_first /* n_units + 1 */, uint64_t* d_req /* 3 per hit */, uint64_t* d_req_off /* 1 per hit */,
+                                    uint64_t* d_lit_first /* n_units + 1 */, uint64_t* d_lit /* 2 per run */, uint64_t* d_count /* 8 */,
+                                    int32_t* d_res_status /* store->n_res */, int32_t* d_status /* n_units */);
+int          mscomp_amd_syncer_counts(mscomp_amd_syncer* sy, uint32_t out[3]);
+
 /* Resource checksums from block checksums. After a write or a resize the block CRC-32s are current and the resource CRC-32s that
  * mscomp_amd_blocks_crc once wrote are stale; the block checksums determine them, and no data has to be read:
  *   d_res_crc[r] = XOR over the resource's blocks j of d_block_crc[j] x^(8 d_j)  (mod the CRC polynomial), d_j = the resource's bytes behind block j

@@ -20,4 +20,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   BlockDeduper, blocks_dedup,
                   BlockTranscoder, blocks_transcode,
                   blocks_diff, blocks_delta, blocks_patch, MSCOMP_AMD_DIFF_NO_BASE,
-                  blocks_match, blocks_match_delta, blocks_match_patch, blocks_single_instance)
+                  blocks_match, blocks_match_delta, blocks_match_patch, blocks_single_instance,
+                  BlockSyncer, blocks_sync, blocks_sync_delta, blocks_sync_patch, MSCOMP_AMD_SYNC_TILE)

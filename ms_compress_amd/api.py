@@ -54,10 +54,12 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_deduper_create_match", "mscomp_amd_deduper_match",
     "mscomp_amd_deduper_create_repair", "mscomp_amd_deduper_repair",
     "mscomp_amd_transcoder_create", "mscomp_amd_transcoder_destroy", "mscomp_amd_transcoder_transcode", "mscomp_amd_transcoder_counts",
+    "mscomp_amd_syncer_create", "mscomp_amd_syncer_destroy", "mscomp_amd_syncer_sync", "mscomp_amd_syncer_counts",
     "mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report",
 ]
 MSCOMP_AMD_SPLICE_SRC_MAX = 4
 MSCOMP_AMD_SPLICE_ROW_TILE = 1024                              # rows of the new table per workgroup of splice_extents' row passes
+MSCOMP_AMD_SYNC_TILE = 4096                                    # positions per wave of a syncer's scan: its seams
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 MSCOMP_AMD_DIFF_NO_BASE = (1 << 64) - 1                        # the base resource of a diff pair whose new resource has none
 # the verdict of a row (BlockContainer.salvage): good; refused by its table entries; did not decode; decoded to other bytes; not judged
@@ -239,6 +241,15 @@ def load_library():
     lib.mscomp_amd_transcoder_transcode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_uint64] + [C.c_void_p] * 4
     lib.mscomp_amd_transcoder_counts.restype = C.c_int
     lib.mscomp_amd_transcoder_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.mscomp_amd_syncer_create.restype = C.c_int
+    lib.mscomp_amd_syncer_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32,
+                                             C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_syncer_destroy.restype = None
+    lib.mscomp_amd_syncer_destroy.argtypes = [C.c_void_p]
+    lib.mscomp_amd_syncer_sync.restype = C.c_int
+    lib.mscomp_amd_syncer_sync.argtypes = [C.c_void_p, C.POINTER(BlocksView)] + [C.c_void_p] * 11
+    lib.mscomp_amd_syncer_counts.restype = C.c_int
+    lib.mscomp_amd_syncer_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1476,6 +1487,106 @@ def blocks_transcode(container, block_size, new_block_size, new_fmt=None, ctx=No
         h_st = d_st.cpu().numpy()
         tc.close()
     return new_packed, nfirst, noff, ncrc, [int(x) for x in h_st[:n]], counts
+
+
+class BlockSyncer(_Handle):
+    """A block syncer (mscomp_amd_syncer_create): the blocks of ONE store container of format ``fmt`` and ``block_size`` -- ``n_res``
+    resources, ``n_blocks_table`` table rows, checksums required -- found at any byte offset of up to ``n_units`` raw units of
+    ``in_total_max`` bytes together, by a rolling CRC-32 over every position; at most ``n_cand_max`` candidates are kept, confirmed byte
+    for byte against the decoded store blocks and answered. All scratch is reserved here: a reader's for n_cand_max requests of one block
+    each, and 8 n_res + 12 per slot of the key table (2 n_blocks_table + 64 rounded up to a power of two) + 40 n_units + 56 n_cand_max +
+    68 per MSCOMP_AMD_SYNC_TILE bytes of input + 4 per 64 bytes + 38064 bytes of tables. sync() enqueues kernels on the ctx stream and nothing else (legal inside a capture of that stream)."""
+    _destroy = "mscomp_amd_syncer_destroy"
+
+    def __init__(self, ctx, fmt, block_size, n_res, n_blocks_table, n_units, in_total_max, n_cand_max):
+        _Handle.__init__(self, ctx)
+        self.fmt, self.block_size, self.n_res, self.n_blocks_table = int(fmt), int(block_size), int(n_res), int(n_blocks_table)
+        self.n_units, self.in_total_max, self.n_cand_max = int(n_units), int(in_total_max), int(n_cand_max)
+        _ok(ctx.lib.mscomp_amd_syncer_create(ctx._h, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_units, self.in_total_max,
+                                             self.n_cand_max, 0, C.byref(self._h)), "mscomp_amd_syncer_create")
+
+    def sync(self, store, d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first, d_lit, d_count, d_res_status, d_status):
+        """``store``: one source as BlockSplicer.splice takes them, with its checksums. Unit u = the d_in_len[u] bytes at d_in +
+        d_in_off[u]. The answer is a recipe: hit i -- d_hit_first (n_units + 1) counts them per unit -- says that the block_size bytes
+        at d_req_off[i] of the batch are the bytes of request d_req[3 i ..] = (resource, offset, block_size) of the store, in the form
+        BlockReader.read takes both arrays; the literal runs d_lit[2 i ..] = (offset in the batch, length), counted by d_lit_first, are
+        the bytes no hit covers. d_count (8): raw candidates, thinned, kept, confirmed, hits, literal runs, literal bytes, distinct rows;
+        d_res_status one entry per resource of the store, d_status one per unit (MSCOMP_ARG_ERROR: over in_total_max)."""
+        views = _blocks_views([store])
+        _ok(self.ctx.lib.mscomp_amd_syncer_sync(self._h, C.byref(views[0]), *_ptrs(d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first,
+                                                                                   d_lit, d_count, d_res_status, d_status)), "mscomp_amd_syncer_sync")
+
+    def counts(self):
+        """(kept candidates, distinct rows, hits) of the last sync(); synchronizes the stream."""
+        return _three_counts(self, "mscomp_amd_syncer_counts")
+
+
+def blocks_sync(store, buffers, block_size, n_cand_max=None, ctx=None, fmt=None):
+    """Find the blocks of the container ``store`` = (packed, block_first, block_off, lengths, block_crc), written in format ``fmt`` at
+    ``block_size``, at any byte offset of the raw ``buffers`` on the GPU (BlockSyncer). ``n_cand_max`` defaults to a bound no input
+    reaches short of periodic floods: two candidates per block of input and eight per buffer. Returns host lists (hits, literals,
+    counts, res_statuses, statuses): hits[u] = [(p, r, k)] -- the block_size bytes at p of buffer u are block k of resource r of the
+    store --, literals[u] = [(p, length)] the stretches no hit covers."""
+    import torch
+    if fmt is None:
+        raise ValueError("fmt: the format the store was written in (its blocks are decoded)")
+    B = int(block_size)
+    bufs = [bytes(b) for b in buffers]
+    nu, total = len(bufs), sum(len(b) for b in bufs)
+    nc = 2 * (total // B) + 8 * nu if n_cand_max is None else int(n_cand_max)
+    with _call(ctx) as (ctx, dev):
+        srcs, n, rows = _upload_containers([store], dev, True)
+        d_in, in_off, lens = _upload_units(bufs, dev)
+        d_off, d_len = _dev_u64(in_off, 1, dev), _dev_u64(lens, 1, dev)
+        sy = BlockSyncer(ctx, fmt, B, n, rows, nu, total, nc)
+        z64 = lambda k: torch.zeros(max(1, k), dtype=torch.int64, device=dev)
+        d_hf, d_req, d_roff, d_lf, d_lit, d_cnt = z64(nu + 1), z64(3 * nc), z64(nc), z64(nu + 1), z64(2 * (nc + nu)), z64(8)
+        d_rst, d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev), torch.zeros(max(1, nu), dtype=torch.int32, device=dev)
+        sy.sync(srcs[0], d_in, d_off, d_len, d_hf, d_req, d_roff, d_lf, d_lit, d_cnt, d_rst, d_st)
+        ctx.stream.synchronize()
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)
+        hf, req, roff, lf, lit, cnt = u64(d_hf), u64(d_req), u64(d_roff), u64(d_lf), u64(d_lit), u64(d_cnt)
+        rst, st = [int(x) for x in d_rst.cpu().numpy()[:n]], [int(x) for x in d_st.cpu().numpy()[:nu]]
+        sy.close()
+    hits = [[(int(roff[i]) - int(in_off[u]), int(req[3 * i]), int(req[3 * i + 1]) // B) for i in range(int(hf[u]), int(hf[u + 1]))] for u in range(nu)]
+    lits = [[(int(lit[2 * i]) - int(in_off[u]), int(lit[2 * i + 1])) for i in range(int(lf[u]), int(lf[u + 1]))] for u in range(nu)]
+    return hits, lits, [int(x) for x in cnt], rst, st
+
+
+def blocks_sync_delta(store, buffers, block_size, n_cand_max=None, ctx=None, fmt=None):
+    """What has to travel to rebuild ``buffers`` where ``store`` is: blocks_sync, then the literal bytes cut out of the buffers. Returns
+    (recipe, literal_bytes): recipe = (lengths, hits, literals) as blocks_sync returns them, literal_bytes the runs' bytes back to back in
+    (buffer, position) order."""
+    hits, lits, _, _, st = blocks_sync(store, buffers, block_size, n_cand_max=n_cand_max, ctx=ctx, fmt=fmt)
+    if any(st):
+        raise MSCompError(next(s for s in st if s), "blocks_sync")
+    data = b"".join(bytes(b)[p: p + ln] for b, runs in zip(buffers, lits) for p, ln in runs)
+    return ([len(b) for b in buffers], hits, lits), data
+
+
+def blocks_sync_patch(store, recipe, literal_bytes, block_size, ctx=None, fmt=None):
+    """The buffers of blocks_sync_delta again: the hits read from ``store`` on the GPU (blocks_read, every block held to its checksum),
+    the literal runs taken from ``literal_bytes``. Returns the list of buffers."""
+    if fmt is None:
+        raise ValueError("fmt: the format the store was written in (its blocks are decoded)")
+    lengths, hits, lits = recipe
+    B = int(block_size)
+    packed, first, off, lens, crc = store
+    reqs = [(r, k * B, B) for hs in hits for _, r, k in hs]
+    got, st = blocks_read(fmt, packed, first, off, lens, B, reqs, ctx=ctx, block_crc=crc) if reqs else ([], [])
+    if any(st):
+        raise MSCompError(next(s for s in st if s), "blocks_read")
+    out, at, q = [], 0, 0
+    for L, hs, runs in zip(lengths, hits, lits):
+        buf = bytearray(L)
+        for p, _, _ in hs:
+            buf[p: p + B] = got[q]
+            q += 1
+        for p, ln in runs:
+            buf[p: p + ln] = literal_bytes[at: at + ln]
+            at += ln
+        out.append(bytes(buf))
+    return out
 
 
 def res_crc_from_blocks(block_first, lengths, block_crc, block_size, ctx=None):

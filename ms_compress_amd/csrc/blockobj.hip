@@ -962,6 +962,121 @@ int mscomp_amd_transcoder_counts(mscomp_amd_transcoder* x, uint32_t out[3])
 	return 0;
 }
 
+// ---- block syncers (include/mscomp_amd.h; kernels: sync.hip, the reader's passes in reader.hip) ----
+// A syncer is a reader core -- BlockAccess with n_cand_max requests of one block each: the inner decompress dev plan, the cache, the
+// reader's tables -- beside tables of its own: the key table and bitmap of the store's checksums, the numberings and boundary registers of
+// the units, the words of the scan's tiles, the kept candidates. The per-block-size constants of the scan are written here, once.
+struct mscomp_amd_syncer : BlockAccess {
+	uint32_t n_units = 0;
+	uint64_t in_total_max = 0;
+	GraphRun<20> run;                                  // one view, and twelve words
+	DevBuf stab;                                       // SyncTab
+	SyncTab s{};
+};
+static_assert(SYNC_TILE == MSCOMP_AMD_SYNC_TILE && SYNC_TILE <= 4096u, "the tile the header states, within the smallest block size");
+
+// the columns of a syncer's tables from `base` on; returns where they end: from a null base, their bytes
+static uintptr_t sync_tab(SyncTab& t, void* base, size_t n, size_t nbt, size_t nu, size_t nc, uint64_t in_total_max)
+{
+	Carve k(base);
+	size_t slots = 64;
+	uint32_t slot_shift = 32u - 6u;
+	while (slots < 2 * nbt + 64) { slots <<= 1; --slot_shift; }          // (at most 2^32: nbt <= 0x7FFFFFF0)
+	const size_t tiles = (size_t)(in_total_max / SYNC_TILE) + nu, pieces = (size_t)(in_total_max / SYNC_RUN) + nu;
+	t.slots = slots; t.slot_shift = slot_shift; t.tiles_max = (uint32_t)tiles;
+	t.ufirst = k.q(n + 1); t.tkey = k.q(slots); t.cum = k.q(nu + 1); t.uoff = k.q(nu); t.ulen = k.q(nu); t.pfirst = k.q(nu + 1); t.tfirst = k.q(nu + 1);
+	t.tword = k.q(8 * tiles); t.cpos = k.q(nc); t.req = k.q(3 * nc); t.qlen = k.q(nc); t.count = k.q(8);
+	t.tmin = k.w(slots); t.bits = k.w(SYNC_BIT_WORDS); t.consts = k.w(SYNC_CONSTS); t.pabs = k.w(pieces); t.traw = k.w(tiles);
+	t.cunit = k.w(nc); t.crow = k.w(nc); t.flag = k.w(nc); t.qstat = k.i(nc);
+	return k.at;
+}
+
+MSCompStatus mscomp_amd_syncer_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_units,
+                                      uint64_t in_total_max, uint64_t n_cand_max, uint32_t flags, mscomp_amd_syncer** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!create_args_ok(c, format, block_size, flags) || !count_ok(n_res) || !count_ok(n_blocks_table) || !count_ok(n_units) || !count_ok(n_cand_max)) { return MSCOMP_ARG_ERROR; }
+	if (in_total_max >> 50 || !count_ok(in_total_max / SYNC_TILE + n_units)) { return MSCOMP_MEM_ERROR; }   // (the tiles are numbered in 32 bits; checked before the context is used)
+	std::unique_ptr<mscomp_amd_syncer> y(new (std::nothrow) mscomp_amd_syncer());
+	MSCompStatus st = access_create(y.get(), nullptr, c, format, block_size, n_res, n_blocks_table, (size_t)n_cand_max, n_cand_max, flags);
+	if (st != MSCOMP_OK) { return st; }
+	DeviceGuard g(c->device);
+	if (!g.ok) { st = MSCOMP_ERRNO; }
+	y->n_units = (uint32_t)n_units; y->in_total_max = in_total_max; y->run.never = false;
+	if (st == MSCOMP_OK && !y->stab.reserve(sync_tab(y->s, nullptr, n_res, n_blocks_table, n_units, n_cand_max, in_total_max) + 64)) { (void)hipGetLastError(); st = MSCOMP_MEM_ERROR; }
+	if (st == MSCOMP_OK) {
+		sync_tab(y->s, y->stab.p, n_res, n_blocks_table, n_units, n_cand_max, in_total_max);
+		uint32_t consts[SYNC_CONSTS];
+		sync_host_consts(y->shift, consts);
+		if (hipMemset(y->s.count, 0, 64) != hipSuccess || hipMemcpy(y->s.consts, consts, sizeof consts, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = MSCOMP_ERRNO; }
+	}
+	if (st != MSCOMP_OK) { y->in.destroy(); y->tab.release(); y->stab.release(); return st; }
+	*out = y.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_syncer_destroy(mscomp_amd_syncer* y) { destroy_object(y, [y] { y->in.destroy(); y->tab.release(); y->stab.release(); }); }
+
+// The call: the store's table and bitmap, the units' numberings, the boundary registers, the scan -- tile pass, tile
+// scan, runs pass --, the kept candidates' rows through the reader core, the compare, the greedy selection with the lists.
+MSCompStatus mscomp_amd_syncer_sync(mscomp_amd_syncer* y, const mscomp_amd_blocks_view* store, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                    uint64_t* d_hit_first, uint64_t* d_req, uint64_t* d_req_off, uint64_t* d_lit_first, uint64_t* d_lit, uint64_t* d_count,
+                                    int32_t* d_res_status, int32_t* d_status)
+{
+	if (!y || !store || !d_hit_first || !d_lit_first || !d_count) { return MSCOMP_ARG_ERROR; }
+	if (y->n_units && (!d_in_off || !d_in_len || !d_status || !d_lit)) { return MSCOMP_ARG_ERROR; }
+	if ((y->in_total_max && !d_in) || (y->m && (!d_req || !d_req_off)) || (y->n_res && !d_res_status)) { return MSCOMP_ARG_ERROR; }
+	SpliceView v[1];
+	bool with_crc = false;
+	if (!pack_views(store, 1, true, v, with_crc) || !with_crc) { return MSCOMP_ARG_ERROR; }   // the checksums are the signature: required
+	if (store->n_res > y->n_res || store->n_blocks_table > y->nbt) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = y->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	y->in.mark_ran(); y->ran = true;
+	const void* args[20];
+	view_args(args, v, { d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first, d_lit, d_count, d_res_status, d_status,
+	                     static_cast<const void*>(nullptr) });
+	const uint32_t n = (uint32_t)store->n_res;
+	return plan_run(y->run, c, args, [&] {
+		const SyncTab& t = y->s;
+		SpliceSrc src{};
+		src.v[0] = v[0];
+		{ KernelTimer k(c, "sy_clear_kernel"); launch_sync_clear(c->stream, t, c->crc_blocks); }
+		{ KernelTimer k(c, "sy_seed_kernel"); launch_sync_seed(c->stream, v[0], n, y->shift, t, d_res_status); }
+		if (y->nbt && n) {
+			{ KernelTimer k(c, "dd_rows_kernel"); launch_dedup_rule3(c->stream, src, n, y->nbt, t.ufirst, d_res_status, c->crc_blocks); }
+			{ KernelTimer k(c, "sy_keys_kernel"); launch_sync_keys(c->stream, v[0], n, y->nbt, y->shift, t, d_res_status, c->crc_blocks); }
+		}
+		{ KernelTimer k(c, "sy_units_kernel"); launch_sync_units(c->stream, y->n_units, y->shift, y->in_total_max, d_in_off, d_in_len, t, d_status); }
+		{ KernelTimer k(c, "sy_bounds"); launch_sync_bounds(c->stream, y->n_units, d_in, t, c->crc_blocks); }
+		{ KernelTimer k(c, "sy_scan"); launch_sync_scan(c->stream, y->n_units, y->m, y->shift, d_in, t, c->crc_blocks); }
+		if (y->m) {
+			{ KernelTimer k(c, "sy_req_kernel"); launch_sync_requests(c->stream, n, y->m, y->shift, t); }
+			access_admit(y, v[0].packed, v[0].packed_len, v[0].first, v[0].off, v[0].res_len, t.req, nullptr);
+			access_decode(y, v[0].packed, v[0].crc, t.qlen, t.qstat);
+			{ KernelTimer k(c, "sy_confirm_kernel"); launch_sync_confirm(c->stream, y->m, y->shift, d_in, t, y->t, c->cpd_blocks); }
+		}
+		{ KernelTimer k(c, "sy_select_kernel"); launch_sync_select(c->stream, y->n_units, y->shift, t, d_status, y->m ? y->t.cnt : nullptr, d_hit_first, d_req, d_req_off,
+		                                                         d_lit_first, d_lit, d_count); }
+	});
+}
+
+// kept candidates, distinct rows decoded or read, and hits of y's last execution (read back; none before the first)
+int mscomp_amd_syncer_counts(mscomp_amd_syncer* y, uint32_t out[3])
+{
+	if (!y || !out) { return -1; }
+	DeviceGuard g(y->ctx->device);
+	if (!g.ok || hipStreamSynchronize(y->ctx->stream) != hipSuccess) { return -1; }
+	out[0] = out[1] = out[2] = 0;
+	if (!y->ran) { return 0; }
+	uint64_t cnt[8] = {};
+	if (hipMemcpy(cnt, y->s.count, sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
+	out[0] = (uint32_t)cnt[2]; out[1] = (uint32_t)cnt[7]; out[2] = (uint32_t)cnt[4];
+	return 0;
+}
+
 // ---- the scratch hooks' view of the objects above (api.hip: mscomp_amd_debug_scratch_*) ----
 extern "C++" mscomp_amd_ctx* msc::scratch_of_object(int kind, void* obj, std::vector<ScratchEnt>& v)
 {

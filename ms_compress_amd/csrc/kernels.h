@@ -577,6 +577,59 @@ void launch_tc_tiles(hipStream_t st, const TcDims& d, const uint8_t* stage, cons
                      uint32_t* new_crc);
 void launch_tc_rows(hipStream_t st, const TcDims& d, u64 cap, const TranscodeTab& t, const u64* new_first, u64* new_off, uint32_t* new_crc, int32_t* status);
 
+// ---- block syncers (sync.hip; mscomp_amd_syncer_*) ----
+// A rolling scan of raw units against the block checksums of ONE store. A PIECE is SYNC_RUN bytes of a unit -- what a lane of the scan
+// walks --, a TILE SYNC_TILE bytes, 64 pieces -- what a wave walks. A unit of L >= B bytes has L / SYNC_RUN + 1 piece boundaries and
+// L / SYNC_TILE + 1 tiles; a shorter one has none. A position of the scan is named by its TILE COORDINATE, tile * SYNC_TILE + offset in
+// the tile: it grows with (unit, position).
+#define SYNC_TILE      4096u                               // positions a wave of the scan owns (MSCOMP_AMD_SYNC_TILE); no more than the smallest block size
+#define SYNC_RUN       64u                                 // ... and a lane of it
+#ifndef SYNC_BITS_LOG
+#define SYNC_BITS_LOG  18u                                 // the prefilter bitmap: 2^18 bits, 32 KiB of LDS (a build may state another size to measure it)
+#endif
+#define SYNC_BIT_WORDS (1u << (SYNC_BITS_LOG - 5u))
+#define SYNC_CONSTS    (5u * 256u + 4u)                    // per block size: tb[256], mb[4][256], the seed word (and three words of padding)
+// The syncer's own tables, in one buffer (blockobj.hip sync_tab is the only place that knows the layout). n = n_res, nu = n_units, nc =
+// n_cand_max; tiles_max = in_total_max / SYNC_TILE + nu, pieces_max = in_total_max / SYNC_RUN + nu.
+struct SyncTab {
+	u64* ufirst;                                       // n + 1: first row of every store resource, in a numbering of the rows of the resources that passed rules 1 and 2
+	u64* tkey;                                         // slots: (CRC word ^ seed) | 1 << 32 a slot was claimed for (0 = empty)
+	uint32_t* tmin;                                    // slots: the smallest eligible row with the slot's word
+	uint32_t* bits;                                    // SYNC_BIT_WORDS: the bits at the word's low and at its high SYNC_BITS_LOG bits are set for every word in the table
+	uint32_t* consts;                                  // SYNC_CONSTS, written once at creation (sync_host_consts)
+	u64 *cum, *uoff, *ulen;                            // nu + 1, nu, nu: running sum of the accepted lengths; offset and length of a unit (0, 0 when refused)
+	u64 *pfirst, *tfirst;                              // nu + 1 each: first piece boundary, first tile of every unit
+	uint32_t* pabs;                                    // pieces_max: raw(unit[: piece boundary])
+	uint32_t* traw;                                    // tiles_max: raw(tile), then raw(unit[: tile])
+	u64* tword;                                        // 8 tiles_max: what the tile pass leaves per tile and the tile scan adds (sync.hip SW_*)
+	u64* cpos; uint32_t *cunit, *crow, *flag;          // nc each: a kept candidate's position, unit and row; 1 = its bytes differ from the decoded row's
+	u64 *req, *qlen; int32_t* qstat;                   // 3 nc, nc, nc: the reader core's requests, lengths and statuses
+	u64* count;                                        // 8: d_count of the last execution
+	u64 slots;                                         // a power of two, 2^(32 - slot_shift)
+	uint32_t slot_shift;
+	uint32_t tiles_max;
+};
+// the per-block-size constants of the scan, on the host (SYNC_CONSTS words): tb[b] = raw(b) x^(8B) -- the byte that leaves a window --,
+// mb[k][b] = (b in byte k of a register) x^(8B), crc_seed(B)
+void sync_host_consts(uint32_t shift, uint32_t* out);
+// The call in five stages, every grid fixed by the creation bounds. store (three launches and launch_dedup_rule3 between the first two):
+// the key table and the bitmap cleared; the seed, one workgroup -- rules 1 and 2, status (n_res), t.ufirst --; the eligible rows' words into table and bitmap
+void launch_sync_clear(hipStream_t st, const SyncTab& t, uint32_t blocks);
+void launch_sync_seed(hipStream_t st, const SpliceView& v, uint32_t n, uint32_t shift, const SyncTab& t, int32_t* status);
+void launch_sync_keys(hipStream_t st, const SpliceView& v, uint32_t n, uint32_t nbt, uint32_t shift, const SyncTab& t, const int32_t* status, uint32_t blocks);
+// units (one workgroup): the bounds rule, status (n_units), t.cum .. t.tfirst
+void launch_sync_units(hipStream_t st, uint32_t n_units, uint32_t shift, u64 in_total_max, const u64* in_off, const u64* in_len, const SyncTab& t, int32_t* status);
+// boundaries (three launches): raw() of every piece and tile; the tiles' running values per unit (one workgroup); t.pabs
+void launch_sync_bounds(hipStream_t st, uint32_t n_units, const uint8_t* in, const SyncTab& t, uint32_t blocks);
+// scan (three launches): the tile pass, the tile scan (one workgroup: t.count[0 .. 2]), the runs pass, which writes the kept candidates
+void launch_sync_scan(hipStream_t st, uint32_t n_units, uint32_t n_cand, uint32_t shift, const uint8_t* in, const SyncTab& t, uint32_t blocks);
+// confirm, around the reader core's passes: in front of them the requests (t.req, t.flag cleared); behind them the compare in pieces of 16 KiB
+void launch_sync_requests(hipStream_t st, uint32_t n, uint32_t n_cand, uint32_t shift, const SyncTab& t);
+void launch_sync_confirm(hipStream_t st, uint32_t n_cand, uint32_t shift, const uint8_t* in, const SyncTab& t, const ReaderTab& r, uint32_t blocks);
+// select and emit (one workgroup): the greedy walk per unit, the hits, the literal runs, the counts (distinct: the reader core's count of owners, may be null)
+void launch_sync_select(hipStream_t st, uint32_t n_units, uint32_t shift, const SyncTab& t, const int32_t* status, const uint32_t* distinct, u64* hit_first, u64* req, u64* req_off,
+                        u64* lit_first, u64* lit, u64* count);
+
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status
 // MSCOMP_ARG_ERROR), off[i] = its offset. in_off / off and status may be null.
