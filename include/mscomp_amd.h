@@ -1364,6 +1364,86 @@ MSCompStatus mscomp_amd_syncer_sync(mscomp_amd_syncer* sy, const mscomp_amd_bloc
                                     int32_t* d_res_status /* store->n_res */, int32_t* d_status /* n_units */);
 int          mscomp_amd_syncer_counts(mscomp_amd_syncer* sy, uint32_t out[3]);
 
+/* Digests: a strong hash per block beside the CRC-32, and a syncer that confirms by it. The CRC-32 column is the weak half of rsync's
+ * signature -- it rolls, and finds candidates --; a syncer made by mscomp_amd_syncer_create has to confirm each of them byte for byte and
+ * so decodes the store's rows. The digest column is the strong half: 128 bits per block over the block's DATA, like the CRCs, so it
+ * survives a transcode to another codec or a move to another container. digest(D) of a block D of 1 <= e <= 524288 bytes is BLAKE2s in
+ * its tree mode (RFC 7693, parameter block): leaf size MSCOMP_AMD_DIGEST_LEAF = 1024, two levels (depth 2), unlimited fan-out (0), inner
+ * and final length 16, no key, salt or personalisation; leaf i = the bytes [1024 i, 1024 i + 1024) of D with node_offset i, node_depth 0,
+ * the last leaf with last_node; the root hashes the leaves' 16-byte digests back to back with node_offset 0, node_depth 1, last_node --
+ * also over a single leaf. Python's hashlib.blake2s takes these parameters by name (tests/digest_model.py). On the device a digest is four
+ * uint32 words h0 .. h3; as bytes, little-endian words in order, they are the 16 bytes of the hash. A digest column is
+ * uint32_t[4 n_blocks_table], entry j for the block at d_block_off[j].
+ *   Creation:     digester (ctx, block_size, n_res, in_total_max, flags = 0): the bounds of mscomp_amd_blocks_create without a format,
+ *                 n_blocks_max = n_res + in_total_max / block_size. Digest syncer (ctx, block_size, n_res, n_blocks_table, n_units,
+ *                 in_total_max, n_cand_max, flags = 0): the arguments of mscomp_amd_syncer_create without a format. The checks of every
+ *                 other create, in their order, before the context is used and with the out pointer cleared: MSCOMP_ARG_ERROR for a
+ *                 null ctx or out pointer, a block_size that is not a power of two from 4096 to 524288, non-zero flags, or a count
+ *                 (n_res; a syncer's n_blocks_table, n_units, n_cand_max) above 0x7FFFFFF0; MSCOMP_MEM_ERROR for in_total_max of 2^50 or
+ *                 more, a digester's n_blocks_max above 0x7FFFFFF0, a syncer's in_total_max / MSCOMP_AMD_SYNC_TILE + n_units above
+ *                 0x7FFFFFF0.
+ *   Scratch:      all reserved at creation, once, and never grown; no context buffer and no scratch-hook kind. A digester, with
+ *                 m = n_blocks_max:
+ *                   m (16 block_size / 1024 + 56) + 20 n_res + 72 bytes
+ *                 (16 bytes per possible leaf; per possible block its offset, length and three more table words and a digest for
+ *                 check; the per-resource words of the container's table passes). The container's own scratch does not change. A
+ *                 digest syncer has NO reader core -- no inner plan, no cache of n_cand_max B bytes, no reader's tables --: the
+ *                 syncer's own tables as stated for mscomp_amd_syncer_create, and
+ *                   n_cand_max (16 block_size / 1024 + 32) + 64 bytes
+ *                 (per kept candidate a unit-table entry of 16 bytes, block_size / 1024 leaf digests and one window digest).
+ *   Sources:      blocks takes the resources as mscomp_amd_blocks_crc does, check the decoded output and the tables as
+ *                 mscomp_amd_blocks_check does. sync_digest takes the store as mscomp_amd_syncer_sync does, and d_block_digest
+ *                 (4 store->n_blocks_table words) as an argument of its own: mscomp_amd_blocks_view is not changed. d_block_crc is
+ *                 still required -- the scan's key table is built from it -- and store->d_packed is never dereferenced and may be NULL.
+ *   Rules:        blocks answers word for word as mscomp_amd_blocks_crc, a digest for a CRC word: the same acceptance of resources
+ *                 (MSCOMP_ARG_ERROR past in_total_max, no blocks), the same numbering of blocks; entries at and behind the real block
+ *                 count are four zero words; there is no resource digest. check follows mscomp_amd_blocks_check exactly: a resource
+ *                 that is not MSCOMP_OK on entry is left alone, checks 1 and 2 and the clipped range are the same, the digest of block
+ *                 k of the range (first block f) is compared with d_block_digest[4 (d_block_first[r] + f + k) ..], and a mismatch gives
+ *                 MSCOMP_DATA_ERROR with d_out_len[r] = 0; nothing else is written. sync_digest: rules 1-5 and 7-9 of
+ *                 mscomp_amd_syncer_sync, unchanged, and
+ *                   6. a kept candidate (u, p, row) is CONFIRMED when digest(M_u[p : p + B]) equals the four words at the table row
+ *                      of `row`; anything else is refuted. Every kept window is hashed once: d_count[7] and counts()[1] are the kept
+ *                      count.
+ *                 Kinds: mscomp_amd_syncer_sync on a digest syncer, and mscomp_amd_syncer_sync_digest on a syncer made by
+ *                 mscomp_amd_syncer_create, return MSCOMP_ARG_ERROR with nothing launched. Destroy and counts are the existing calls.
+ *   Consequence:  on a healthy store every output of sync_digest but d_count[7] equals what mscomp_amd_syncer_sync writes for the same
+ *                 arguments, and the recipe rebuilds the units as stated there. A stored byte that was damaged after the digests were
+ *                 taken does not change the answer: the reader that later applies the recipe holds the row to its CRC-32.
+ *   Execution:    as the container's and the syncer's calls: asynchronous on the ctx stream, kernels only (no memset or copy node), no
+ *                 allocation, nothing read back, a launch sequence fixed by the creation bounds; legal inside a caller's capture from
+ *                 the first execution, a graph of its own from the second outside one. blocks: the container's table pass (two
+ *                 launches), the leaf pass -- a fixed grid dealt over the leaf slots, a lane per leaf of up to 16 compressions, every
+ *                 64-byte message block read with four 16-byte loads at any alignment --, the root pass -- a lane per block over its
+ *                 16 ceil(e / 1024) bytes of leaf digests: 1 compression at 4096, 128 at 524288, the latency floor of a call --, which
+ *                 also writes the statuses. check: the check's table pass, the leaves, the roots, the fold (a wave per resource).
+ *                 sync_digest: the syncer's passes 1-4 and 6, and for pass 5 the requests, the kept windows as a unit table, the
+ *                 leaves, the roots, a compare of 16 bytes per candidate. MSCOMP_ARG_ERROR for a null object and for any null array
+ *                 the creation bounds give a size above 0 (d_block_digest: n_blocks_max, n_blocks_table). n_res = 0: blocks and check
+ *                 return MSCOMP_OK and launch nothing.
+ *   Left out:     units above 524288 bytes and a resource digest (a tree over the block digests is a later step); dedup, diff and
+ *                 match confirming by digest, or matching across codecs by digest; salvage verdicts by digest; writers, resize,
+ *                 splice and transcode carrying the digest column (recompute it with the digester); keyed digests. A digest syncer
+ *                 never reads the store: a row damaged after its digest was taken is still offered as a hit, and it is the reader
+ *                 applying the recipe, held to d_block_crc, that refuses it. */
+#define MSCOMP_AMD_DIGEST_LEAF 1024u
+typedef struct mscomp_amd_digester mscomp_amd_digester;
+MSCompStatus mscomp_amd_digester_create(mscomp_amd_ctx* ctx, uint32_t block_size, size_t n_res, uint64_t in_total_max, uint32_t flags,
+                                        mscomp_amd_digester** dg);
+void         mscomp_amd_digester_destroy(mscomp_amd_digester* dg);
+MSCompStatus mscomp_amd_digester_blocks(mscomp_amd_digester* dg, const uint8_t* d_data, const uint64_t* d_res_off, const uint64_t* d_res_len,
+                                        uint32_t* d_block_digest /* 4 n_blocks_max */, int32_t* d_status);
+MSCompStatus mscomp_amd_digester_check(mscomp_amd_digester* dg, const uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_res_len,
+                                       const uint64_t* d_block_first, const uint64_t* d_range, const uint32_t* d_block_digest,
+                                       uint64_t* d_out_len, int32_t* d_status /* in and out */);
+MSCompStatus mscomp_amd_syncer_create_digest(mscomp_amd_ctx* ctx, uint32_t block_size, size_t n_res, uint64_t n_blocks_table,
+                                             size_t n_units, uint64_t in_total_max, uint64_t n_cand_max, uint32_t flags, mscomp_amd_syncer** sy);
+MSCompStatus mscomp_amd_syncer_sync_digest(mscomp_amd_syncer* sy, const mscomp_amd_blocks_view* store,
+                                           const uint32_t* d_block_digest /* 4 store->n_blocks_table */,
+                                           const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                           uint64_t* d_hit_first, uint64_t* d_req, uint64_t* d_req_off, uint64_t* d_lit_first, uint64_t* d_lit,
+                                           uint64_t* d_count, int32_t* d_res_status, int32_t* d_status);
+
 /* Resource checksums from block checksums. After a write or a resize the block CRC-32s are current and the resource CRC-32s that
  * mscomp_amd_blocks_crc once wrote are stale; the block checksums determine them, and no data has to be read:
  *   d_res_crc[r] = XOR over the resource's blocks j of d_block_crc[j] x^(8 d_j)  (mod the CRC polynomial), d_j = the resource's bytes behind block j

@@ -55,11 +55,14 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_deduper_create_repair", "mscomp_amd_deduper_repair",
     "mscomp_amd_transcoder_create", "mscomp_amd_transcoder_destroy", "mscomp_amd_transcoder_transcode", "mscomp_amd_transcoder_counts",
     "mscomp_amd_syncer_create", "mscomp_amd_syncer_destroy", "mscomp_amd_syncer_sync", "mscomp_amd_syncer_counts",
+    "mscomp_amd_digester_create", "mscomp_amd_digester_destroy", "mscomp_amd_digester_blocks", "mscomp_amd_digester_check",
+    "mscomp_amd_syncer_create_digest", "mscomp_amd_syncer_sync_digest",
     "mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report",
 ]
 MSCOMP_AMD_SPLICE_SRC_MAX = 4
 MSCOMP_AMD_SPLICE_ROW_TILE = 1024                              # rows of the new table per workgroup of splice_extents' row passes
 MSCOMP_AMD_SYNC_TILE = 4096                                    # positions per wave of a syncer's scan: its seams
+MSCOMP_AMD_DIGEST_LEAF = 1024                                  # bytes per leaf of a block digest's tree
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 MSCOMP_AMD_DIFF_NO_BASE = (1 << 64) - 1                        # the base resource of a diff pair whose new resource has none
 # the verdict of a row (BlockContainer.salvage): good; refused by its table entries; did not decode; decoded to other bytes; not judged
@@ -250,6 +253,19 @@ def load_library():
     lib.mscomp_amd_syncer_sync.argtypes = [C.c_void_p, C.POINTER(BlocksView)] + [C.c_void_p] * 11
     lib.mscomp_amd_syncer_counts.restype = C.c_int
     lib.mscomp_amd_syncer_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.mscomp_amd_digester_create.restype = C.c_int
+    lib.mscomp_amd_digester_create.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_digester_destroy.restype = None
+    lib.mscomp_amd_digester_destroy.argtypes = [C.c_void_p]
+    lib.mscomp_amd_digester_blocks.restype = C.c_int
+    lib.mscomp_amd_digester_blocks.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+    lib.mscomp_amd_digester_check.restype = C.c_int
+    lib.mscomp_amd_digester_check.argtypes = [C.c_void_p] + [C.c_void_p] * 8
+    lib.mscomp_amd_syncer_create_digest.restype = C.c_int
+    lib.mscomp_amd_syncer_create_digest.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                    C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_syncer_sync_digest.restype = C.c_int
+    lib.mscomp_amd_syncer_sync_digest.argtypes = [C.c_void_p, C.POINTER(BlocksView)] + [C.c_void_p] * 12
     lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mscomp_amd_plan_layout.restype = C.c_uint64
     lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1517,18 +1533,96 @@ class BlockSyncer(_Handle):
                                                                                    d_lit, d_count, d_res_status, d_status)), "mscomp_amd_syncer_sync")
 
     def counts(self):
-        """(kept candidates, distinct rows, hits) of the last sync(); synchronizes the stream."""
+        """(kept candidates, distinct rows, hits) of the last sync(); synchronizes the stream. A digest syncer hashes every kept window
+        once: its second count is the kept count."""
         return _three_counts(self, "mscomp_amd_syncer_counts")
 
+    @classmethod
+    def for_digest(cls, ctx, block_size, n_res, n_blocks_table, n_units, in_total_max, n_cand_max):
+        """A syncer that confirms by digest (mscomp_amd_syncer_create_digest): the same bounds without a format. No reader core is
+        reserved -- no inner plan, no cache of n_cand_max blocks --: the syncer's own tables and n_cand_max (16 block_size / 1024 + 32)
+        + 64 bytes. Only sync_digest() runs on it."""
+        self = cls.__new__(cls)
+        _Handle.__init__(self, ctx)
+        self.fmt, self.block_size, self.n_res, self.n_blocks_table = None, int(block_size), int(n_res), int(n_blocks_table)
+        self.n_units, self.in_total_max, self.n_cand_max = int(n_units), int(in_total_max), int(n_cand_max)
+        _ok(ctx.lib.mscomp_amd_syncer_create_digest(ctx._h, self.block_size, self.n_res, self.n_blocks_table, self.n_units, self.in_total_max,
+                                                    self.n_cand_max, 0, C.byref(self._h)), "mscomp_amd_syncer_create_digest")
+        return self
 
-def blocks_sync(store, buffers, block_size, n_cand_max=None, ctx=None, fmt=None):
+    def sync_digest(self, store, d_block_digest, d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first, d_lit, d_count, d_res_status,
+                    d_status):
+        """sync() on a syncer made by for_digest: a kept candidate is confirmed when the digest of its window of the new data equals the
+        four words of ``d_block_digest`` (int32, 4 per table row, as BlockDigester.blocks writes them) at its row. The store's bytes are
+        never read -- its d_packed may be None --, its checksums still are: the scan is built from them. d_count[7] = the kept count."""
+        views = _blocks_views([store])
+        _ok(self.ctx.lib.mscomp_amd_syncer_sync_digest(self._h, C.byref(views[0]), *_ptrs(d_block_digest, d_in, d_in_off, d_in_len, d_hit_first, d_req,
+                                                                                          d_req_off, d_lit_first, d_lit, d_count, d_res_status, d_status)),
+            "mscomp_amd_syncer_sync_digest")
+
+
+class BlockDigester(_Handle):
+    """A block digester (mscomp_amd_digester_create): the 128-bit BLAKE2s tree digest of every block of ``block_size`` bytes of up to
+    ``n_res`` resources of ``in_total_max`` bytes together -- over the blocks' DATA, like the checksums. A digest is four int32 words;
+    viewed as bytes they are the hash. ``n_blocks_max`` = n_res + in_total_max // block_size. All scratch is reserved here:
+    n_blocks_max (16 block_size / 1024 + 56) + 20 n_res + 72 bytes. Both calls enqueue kernels on the ctx stream and nothing else."""
+    _destroy = "mscomp_amd_digester_destroy"
+
+    def __init__(self, ctx, block_size, n_res, in_total_max):
+        _Handle.__init__(self, ctx)
+        self.block_size, self.n_res, self.in_total_max = int(block_size), int(n_res), int(in_total_max)
+        _ok(ctx.lib.mscomp_amd_digester_create(ctx._h, self.block_size, self.n_res, self.in_total_max, 0, C.byref(self._h)), "mscomp_amd_digester_create")
+        self.n_blocks_max = self.n_res + self.in_total_max // self.block_size
+
+    def blocks(self, d_data, d_res_off, d_res_len, d_block_digest, d_status):
+        """As BlockContainer.crc, a digest for a checksum: d_block_digest (int32, 4 n_blocks_max; entry j belongs to the block compress puts at
+        d_block_off[j], the entries behind the last block are zeros) and d_status (n_res: MSCOMP_OK, or MSCOMP_ARG_ERROR past in_total_max)."""
+        _ok(self.ctx.lib.mscomp_amd_digester_blocks(self._h, *_ptrs(d_data, d_res_off, d_res_len, d_block_digest, d_status)), "mscomp_amd_digester_blocks")
+
+    def check(self, d_out, d_out_off, d_res_len, d_block_first, d_block_digest, d_out_len, d_status, d_range=None):
+        """As BlockContainer.check: every block of the (clipped) range of every resource that is MSCOMP_OK in d_status is read back from
+        d_out and held to d_block_digest; a mismatch turns the resource into MSCOMP_DATA_ERROR with d_out_len = 0."""
+        p = _ptrs(d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_digest, d_out_len, d_status)
+        _ok(self.ctx.lib.mscomp_amd_digester_check(self._h, *p), "mscomp_amd_digester_check")
+
+
+def blocks_digest(buffers, block_size, ctx=None):
+    """The digest column of a list of byte strings (one resource each), computed on the GPU (BlockDigester): a numpy uint32 array of
+    shape (nb, 4) in the block order of blocks_compress; row j viewed as bytes is the BLAKE2s tree digest of block j."""
+    import torch
+    n = len(buffers)
+    with _call(ctx) as (ctx, dev):
+        d_in, d_off, d_len, lens = _upload_unit_tables(buffers, dev)
+        dg = BlockDigester(ctx, block_size, n, int(sum(lens)))
+        d_dig = torch.zeros(max(1, 4 * dg.n_blocks_max), dtype=torch.int32, device=dev)
+        d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        dg.blocks(d_in, d_off, d_len, d_dig, d_st)
+        ctx.stream.synchronize()
+        nb = sum((x + block_size - 1) // block_size for x in lens)
+        out = d_dig.cpu().numpy().view(np.uint32)[: 4 * nb].reshape(nb, 4).copy()
+        dg.close()
+    return out
+
+
+def _dev_block_digest(block_digest, n, dev):
+    """``block_digest`` (rows of four words) cut or zero-padded to ``n`` rows (one at least), as an int32 device tensor of 4 n words."""
+    import torch
+    h = np.zeros(4 * max(1, n), dtype=np.uint32)
+    a = np.asarray(block_digest, dtype=np.uint32).reshape(-1)
+    k = min(len(a), 4 * n)
+    h[:k] = a[:k]
+    return torch.from_numpy(h.view(np.int32).copy()).to(dev)
+
+
+def blocks_sync(store, buffers, block_size, n_cand_max=None, ctx=None, fmt=None, block_digest=None):
     """Find the blocks of the container ``store`` = (packed, block_first, block_off, lengths, block_crc), written in format ``fmt`` at
     ``block_size``, at any byte offset of the raw ``buffers`` on the GPU (BlockSyncer). ``n_cand_max`` defaults to a bound no input
     reaches short of periodic floods: two candidates per block of input and eight per buffer. Returns host lists (hits, literals,
     counts, res_statuses, statuses): hits[u] = [(p, r, k)] -- the block_size bytes at p of buffer u are block k of resource r of the
-    store --, literals[u] = [(p, length)] the stretches no hit covers."""
+    store --, literals[u] = [(p, length)] the stretches no hit covers. ``block_digest`` (as blocks_digest returns it for the store's data):
+    the candidates are confirmed by digest instead (BlockSyncer.for_digest) -- no stored byte is read, and ``fmt`` is not needed."""
     import torch
-    if fmt is None:
+    if fmt is None and block_digest is None:
         raise ValueError("fmt: the format the store was written in (its blocks are decoded)")
     B = int(block_size)
     bufs = [bytes(b) for b in buffers]
@@ -1538,11 +1632,14 @@ def blocks_sync(store, buffers, block_size, n_cand_max=None, ctx=None, fmt=None)
         srcs, n, rows = _upload_containers([store], dev, True)
         d_in, in_off, lens = _upload_units(bufs, dev)
         d_off, d_len = _dev_u64(in_off, 1, dev), _dev_u64(lens, 1, dev)
-        sy = BlockSyncer(ctx, fmt, B, n, rows, nu, total, nc)
+        sy = BlockSyncer(ctx, fmt, B, n, rows, nu, total, nc) if block_digest is None else BlockSyncer.for_digest(ctx, B, n, rows, nu, total, nc)
         z64 = lambda k: torch.zeros(max(1, k), dtype=torch.int64, device=dev)
         d_hf, d_req, d_roff, d_lf, d_lit, d_cnt = z64(nu + 1), z64(3 * nc), z64(nc), z64(nu + 1), z64(2 * (nc + nu)), z64(8)
         d_rst, d_st = torch.zeros(max(1, n), dtype=torch.int32, device=dev), torch.zeros(max(1, nu), dtype=torch.int32, device=dev)
-        sy.sync(srcs[0], d_in, d_off, d_len, d_hf, d_req, d_roff, d_lf, d_lit, d_cnt, d_rst, d_st)
+        if block_digest is None:
+            sy.sync(srcs[0], d_in, d_off, d_len, d_hf, d_req, d_roff, d_lf, d_lit, d_cnt, d_rst, d_st)
+        else:
+            sy.sync_digest(srcs[0], _dev_block_digest(block_digest, rows, dev), d_in, d_off, d_len, d_hf, d_req, d_roff, d_lf, d_lit, d_cnt, d_rst, d_st)
         ctx.stream.synchronize()
         u64 = lambda t: t.cpu().numpy().view(np.uint64)
         hf, req, roff, lf, lit, cnt = u64(d_hf), u64(d_req), u64(d_roff), u64(d_lf), u64(d_lit), u64(d_cnt)
@@ -1553,20 +1650,21 @@ def blocks_sync(store, buffers, block_size, n_cand_max=None, ctx=None, fmt=None)
     return hits, lits, [int(x) for x in cnt], rst, st
 
 
-def blocks_sync_delta(store, buffers, block_size, n_cand_max=None, ctx=None, fmt=None):
+def blocks_sync_delta(store, buffers, block_size, n_cand_max=None, ctx=None, fmt=None, block_digest=None):
     """What has to travel to rebuild ``buffers`` where ``store`` is: blocks_sync, then the literal bytes cut out of the buffers. Returns
     (recipe, literal_bytes): recipe = (lengths, hits, literals) as blocks_sync returns them, literal_bytes the runs' bytes back to back in
-    (buffer, position) order."""
-    hits, lits, _, _, st = blocks_sync(store, buffers, block_size, n_cand_max=n_cand_max, ctx=ctx, fmt=fmt)
+    (buffer, position) order. ``block_digest``: as for blocks_sync -- confirmed by digest, without ``fmt``."""
+    hits, lits, _, _, st = blocks_sync(store, buffers, block_size, n_cand_max=n_cand_max, ctx=ctx, fmt=fmt, block_digest=block_digest)
     if any(st):
         raise MSCompError(next(s for s in st if s), "blocks_sync")
     data = b"".join(bytes(b)[p: p + ln] for b, runs in zip(buffers, lits) for p, ln in runs)
     return ([len(b) for b in buffers], hits, lits), data
 
 
-def blocks_sync_patch(store, recipe, literal_bytes, block_size, ctx=None, fmt=None):
+def blocks_sync_patch(store, recipe, literal_bytes, block_size, ctx=None, fmt=None, block_digest=None):
     """The buffers of blocks_sync_delta again: the hits read from ``store`` on the GPU (blocks_read, every block held to its checksum),
-    the literal runs taken from ``literal_bytes``. Returns the list of buffers."""
+    the literal runs taken from ``literal_bytes``. Returns the list of buffers. ``block_digest`` (the store's digest column): the blocks
+    read are held to their digests too (blocks_digest over them), MSCOMP_DATA_ERROR otherwise; reading still decodes, so ``fmt`` stays."""
     if fmt is None:
         raise ValueError("fmt: the format the store was written in (its blocks are decoded)")
     lengths, hits, lits = recipe
@@ -1576,6 +1674,11 @@ def blocks_sync_patch(store, recipe, literal_bytes, block_size, ctx=None, fmt=No
     got, st = blocks_read(fmt, packed, first, off, lens, B, reqs, ctx=ctx, block_crc=crc) if reqs else ([], [])
     if any(st):
         raise MSCompError(next(s for s in st if s), "blocks_read")
+    if block_digest is not None and reqs:
+        want = np.asarray(block_digest, dtype=np.uint32).reshape(-1, 4)
+        rows = [int(first[r]) + k for hs in hits for _, r, k in hs]
+        if not np.array_equal(blocks_digest(got, B, ctx=ctx), want[rows]):
+            raise MSCompError(MSCOMP_DATA_ERROR, "blocks_digest")
     out, at, q = [], 0, 0
     for L, hs, runs in zip(lengths, hits, lits):
         buf = bytearray(L)

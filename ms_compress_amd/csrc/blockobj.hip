@@ -966,12 +966,18 @@ int mscomp_amd_transcoder_counts(mscomp_amd_transcoder* x, uint32_t out[3])
 // A syncer is a reader core -- BlockAccess with n_cand_max requests of one block each: the inner decompress dev plan, the cache, the
 // reader's tables -- beside tables of its own: the key table and bitmap of the store's checksums, the numberings and boundary registers of
 // the units, the words of the scan's tiles, the kept candidates. The per-block-size constants of the scan are written here, once.
+// A DIGEST syncer (mscomp_amd_syncer_create_digest) has no reader core: of BlockAccess it holds the bounds alone -- no inner plan, no
+// cache, no reader's tables --, and beside the syncer's tables a unit table, the leaf digests and a digest per kept candidate (digest.hip).
 struct mscomp_amd_syncer : BlockAccess {
 	uint32_t n_units = 0;
 	uint64_t in_total_max = 0;
+	bool digest = false;                               // confirms by digest: only mscomp_amd_syncer_sync_digest runs on it, and only on it
 	GraphRun<20> run;                                  // one view, and twelve words
 	DevBuf stab;                                       // SyncTab
 	SyncTab s{};
+	DevBuf dtab;                                       // a digest syncer's: sync_digest_tab
+	DigestTab d{};
+	u64* doff = nullptr; u64* dlen = nullptr;          // (d.off, d.len, writable)
 };
 static_assert(SYNC_TILE == MSCOMP_AMD_SYNC_TILE && SYNC_TILE <= 4096u, "the tile the header states, within the smallest block size");
 
@@ -991,53 +997,92 @@ static uintptr_t sync_tab(SyncTab& t, void* base, size_t n, size_t nbt, size_t n
 	return k.at;
 }
 
-MSCompStatus mscomp_amd_syncer_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_units,
-                                      uint64_t in_total_max, uint64_t n_cand_max, uint32_t flags, mscomp_amd_syncer** out)
+// what a digest syncer adds to them, from `base` on (nc = n_cand_max; y->s laid out): the 16-byte columns first, so that they stay aligned
+static uintptr_t sync_digest_tab(mscomp_amd_syncer* y, void* base, size_t nc, uint32_t shift)
 {
-	if (!out) { return MSCOMP_ARG_ERROR; }
+	Carve k(base);
+	y->d.leaf = k.w(4 * (nc << (shift - DG_LEAF_SHIFT))); y->d.out = k.w(4 * nc); y->doff = k.q(nc); y->dlen = k.q(nc);
+	y->d.off = y->doff; y->d.len = y->dlen; y->d.count = y->s.count + 2; y->d.n_max = (uint32_t)nc; y->d.shift = shift;   // (count[2]: the kept candidates)
+	return k.at;
+}
+
+// both creates, from the null check of `out` on. A digest syncer takes no format and reserves no reader core.
+static MSCompStatus syncer_create(mscomp_amd_ctx* c, bool digest, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_units,
+                                  uint64_t in_total_max, uint64_t n_cand_max, uint32_t flags, mscomp_amd_syncer** out)
+{
 	*out = nullptr;
-	if (!create_args_ok(c, format, block_size, flags) || !count_ok(n_res) || !count_ok(n_blocks_table) || !count_ok(n_units) || !count_ok(n_cand_max)) { return MSCOMP_ARG_ERROR; }
+	if (digest ? !c || flags || !block_size_ok(block_size) : !create_args_ok(c, format, block_size, flags)) { return MSCOMP_ARG_ERROR; }
+	if (!count_ok(n_res) || !count_ok(n_blocks_table) || !count_ok(n_units) || !count_ok(n_cand_max)) { return MSCOMP_ARG_ERROR; }
 	if (in_total_max >> 50 || !count_ok(in_total_max / SYNC_TILE + n_units)) { return MSCOMP_MEM_ERROR; }   // (the tiles are numbered in 32 bits; checked before the context is used)
 	std::unique_ptr<mscomp_amd_syncer> y(new (std::nothrow) mscomp_amd_syncer());
-	MSCompStatus st = access_create(y.get(), nullptr, c, format, block_size, n_res, n_blocks_table, (size_t)n_cand_max, n_cand_max, flags);
-	if (st != MSCOMP_OK) { return st; }
+	MSCompStatus st = MSCOMP_OK;
+	if (!digest) {
+		st = access_create(y.get(), nullptr, c, format, block_size, n_res, n_blocks_table, (size_t)n_cand_max, n_cand_max, flags);
+		if (st != MSCOMP_OK) { return st; }
+	}
 	DeviceGuard g(c->device);
 	if (!g.ok) { st = MSCOMP_ERRNO; }
+	if (digest) {                                                          // the bounds of BlockAccess, and nothing else of it
+		if (!y) { return MSCOMP_MEM_ERROR; }
+		y->ctx = c; y->shift = (uint32_t)__builtin_ctz(block_size); y->n_res = (uint32_t)n_res; y->nbt = (uint32_t)n_blocks_table;
+		y->n_req = y->m = (uint32_t)n_cand_max; y->digest = true;
+	}
 	y->n_units = (uint32_t)n_units; y->in_total_max = in_total_max; y->run.never = false;
 	if (st == MSCOMP_OK && !y->stab.reserve(sync_tab(y->s, nullptr, n_res, n_blocks_table, n_units, n_cand_max, in_total_max) + 64)) { (void)hipGetLastError(); st = MSCOMP_MEM_ERROR; }
+	if (st == MSCOMP_OK && digest && !y->dtab.reserve(sync_digest_tab(y.get(), nullptr, n_cand_max, y->shift) + 64)) { (void)hipGetLastError(); st = MSCOMP_MEM_ERROR; }
 	if (st == MSCOMP_OK) {
 		sync_tab(y->s, y->stab.p, n_res, n_blocks_table, n_units, n_cand_max, in_total_max);
+		if (digest) { sync_digest_tab(y.get(), y->dtab.p, n_cand_max, y->shift); }
 		uint32_t consts[SYNC_CONSTS];
 		sync_host_consts(y->shift, consts);
 		if (hipMemset(y->s.count, 0, 64) != hipSuccess || hipMemcpy(y->s.consts, consts, sizeof consts, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = MSCOMP_ERRNO; }
 	}
-	if (st != MSCOMP_OK) { y->in.destroy(); y->tab.release(); y->stab.release(); return st; }
+	if (st != MSCOMP_OK) { y->in.destroy(); y->tab.release(); y->stab.release(); y->dtab.release(); return st; }
 	*out = y.release();
 	return MSCOMP_OK;
 }
 
-void mscomp_amd_syncer_destroy(mscomp_amd_syncer* y) { destroy_object(y, [y] { y->in.destroy(); y->tab.release(); y->stab.release(); }); }
+MSCompStatus mscomp_amd_syncer_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_units,
+                                      uint64_t in_total_max, uint64_t n_cand_max, uint32_t flags, mscomp_amd_syncer** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	return syncer_create(c, false, format, block_size, n_res, n_blocks_table, n_units, in_total_max, n_cand_max, flags, out);
+}
+
+MSCompStatus mscomp_amd_syncer_create_digest(mscomp_amd_ctx* c, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_units, uint64_t in_total_max,
+                                             uint64_t n_cand_max, uint32_t flags, mscomp_amd_syncer** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	return syncer_create(c, true, MSCOMP_NONE, block_size, n_res, n_blocks_table, n_units, in_total_max, n_cand_max, flags, out);
+}
+
+void mscomp_amd_syncer_destroy(mscomp_amd_syncer* y) { destroy_object(y, [y] { y->in.destroy(); y->tab.release(); y->stab.release(); y->dtab.release(); }); }
 
 // The call: the store's table and bitmap, the units' numberings, the boundary registers, the scan -- tile pass, tile
 // scan, runs pass --, the kept candidates' rows through the reader core, the compare, the greedy selection with the lists.
-MSCompStatus mscomp_amd_syncer_sync(mscomp_amd_syncer* y, const mscomp_amd_blocks_view* store, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
-                                    uint64_t* d_hit_first, uint64_t* d_req, uint64_t* d_req_off, uint64_t* d_lit_first, uint64_t* d_lit, uint64_t* d_count,
-                                    int32_t* d_res_status, int32_t* d_status)
+// Both calls; `digest`: which of them. With it, rule 6 is the digest of the window against d_block_digest, the store's
+// bytes are never dereferenced -- its view is packed without them -- and the reader core's passes are left out.
+static MSCompStatus syncer_run(mscomp_amd_syncer* y, bool digest, const mscomp_amd_blocks_view* store, const uint32_t* d_block_digest, const uint8_t* d_in,
+                               const uint64_t* d_in_off, const uint64_t* d_in_len, uint64_t* d_hit_first, uint64_t* d_req, uint64_t* d_req_off, uint64_t* d_lit_first,
+                               uint64_t* d_lit, uint64_t* d_count, int32_t* d_res_status, int32_t* d_status)
 {
-	if (!y || !store || !d_hit_first || !d_lit_first || !d_count) { return MSCOMP_ARG_ERROR; }
+	if (!y || !store || !d_hit_first || !d_lit_first || !d_count || y->digest != digest) { return MSCOMP_ARG_ERROR; }
 	if (y->n_units && (!d_in_off || !d_in_len || !d_status || !d_lit)) { return MSCOMP_ARG_ERROR; }
 	if ((y->in_total_max && !d_in) || (y->m && (!d_req || !d_req_off)) || (y->n_res && !d_res_status)) { return MSCOMP_ARG_ERROR; }
 	SpliceView v[1];
 	bool with_crc = false;
-	if (!pack_views(store, 1, true, v, with_crc) || !with_crc) { return MSCOMP_ARG_ERROR; }   // the checksums are the signature: required
-	if (store->n_res > y->n_res || store->n_blocks_table > y->nbt) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_blocks_view sv = *store;
+	if (digest) { sv.d_packed = nullptr; sv.packed_len = 0; }                 // (the rows are still judged against store->packed_len, below)
+	if (!pack_views(&sv, 1, true, v, with_crc) || !with_crc) { return MSCOMP_ARG_ERROR; }   // the checksums are the signature: required
+	if (digest) { v[0].packed_len = store->packed_len; }
+	if (store->n_res > y->n_res || store->n_blocks_table > y->nbt || (digest && y->nbt && !d_block_digest)) { return MSCOMP_ARG_ERROR; }
 	mscomp_amd_ctx* c = y->ctx;
 	DeviceGuard g(c->device);
 	if (!g.ok) { return MSCOMP_ERRNO; }
 	y->in.mark_ran(); y->ran = true;
 	const void* args[20];
 	view_args(args, v, { d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first, d_lit, d_count, d_res_status, d_status,
-	                     static_cast<const void*>(nullptr) });
+	                     static_cast<const void*>(d_block_digest) });
 	const uint32_t n = (uint32_t)store->n_res;
 	return plan_run(y->run, c, args, [&] {
 		const SyncTab& t = y->s;
@@ -1052,15 +1097,37 @@ MSCompStatus mscomp_amd_syncer_sync(mscomp_amd_syncer* y, const mscomp_amd_block
 		{ KernelTimer k(c, "sy_units_kernel"); launch_sync_units(c->stream, y->n_units, y->shift, y->in_total_max, d_in_off, d_in_len, t, d_status); }
 		{ KernelTimer k(c, "sy_bounds"); launch_sync_bounds(c->stream, y->n_units, d_in, t, c->crc_blocks); }
 		{ KernelTimer k(c, "sy_scan"); launch_sync_scan(c->stream, y->n_units, y->m, y->shift, d_in, t, c->crc_blocks); }
-		if (y->m) {
+		if (y->m && !digest) {
 			{ KernelTimer k(c, "sy_req_kernel"); launch_sync_requests(c->stream, n, y->m, y->shift, t); }
 			access_admit(y, v[0].packed, v[0].packed_len, v[0].first, v[0].off, v[0].res_len, t.req, nullptr);
 			access_decode(y, v[0].packed, v[0].crc, t.qlen, t.qstat);
 			{ KernelTimer k(c, "sy_confirm_kernel"); launch_sync_confirm(c->stream, y->m, y->shift, d_in, t, y->t, c->cpd_blocks); }
+		} else if (y->m) {
+			{ KernelTimer k(c, "sy_req_kernel"); launch_sync_requests(c->stream, n, y->m, y->shift, t); }
+			{ KernelTimer k(c, "sy_dunits_kernel"); launch_sync_digest_units(c->stream, n, y->m, y->shift, t, y->doff, y->dlen); }
+			{ KernelTimer k(c, "dg_leaf_kernel"); launch_digest_leaves(c->stream, d_in, y->d, c->crc_blocks); }
+			{ KernelTimer k(c, "dg_root_kernel"); launch_digest_roots(c->stream, y->d, y->d.out, 0, nullptr, nullptr); }
+			{ KernelTimer k(c, "sy_dcompare_kernel"); launch_sync_digest_compare(c->stream, v[0], n, y->m, d_block_digest, t, y->d.out); }
 		}
-		{ KernelTimer k(c, "sy_select_kernel"); launch_sync_select(c->stream, y->n_units, y->shift, t, d_status, y->m ? y->t.cnt : nullptr, d_hit_first, d_req, d_req_off,
+		// (count[7]: the reader core's count of owners; a digest syncer hashes every kept window once, so the low word of count[2])
+		const uint32_t* distinct = !y->m ? nullptr : digest ? reinterpret_cast<const uint32_t*>(t.count + 2) : y->t.cnt;
+		{ KernelTimer k(c, "sy_select_kernel"); launch_sync_select(c->stream, y->n_units, y->shift, t, d_status, distinct, d_hit_first, d_req, d_req_off,
 		                                                         d_lit_first, d_lit, d_count); }
 	});
+}
+
+MSCompStatus mscomp_amd_syncer_sync(mscomp_amd_syncer* y, const mscomp_amd_blocks_view* store, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                    uint64_t* d_hit_first, uint64_t* d_req, uint64_t* d_req_off, uint64_t* d_lit_first, uint64_t* d_lit, uint64_t* d_count,
+                                    int32_t* d_res_status, int32_t* d_status)
+{
+	return syncer_run(y, false, store, nullptr, d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first, d_lit, d_count, d_res_status, d_status);
+}
+
+MSCompStatus mscomp_amd_syncer_sync_digest(mscomp_amd_syncer* y, const mscomp_amd_blocks_view* store, const uint32_t* d_block_digest, const uint8_t* d_in,
+                                           const uint64_t* d_in_off, const uint64_t* d_in_len, uint64_t* d_hit_first, uint64_t* d_req, uint64_t* d_req_off,
+                                           uint64_t* d_lit_first, uint64_t* d_lit, uint64_t* d_count, int32_t* d_res_status, int32_t* d_status)
+{
+	return syncer_run(y, true, store, d_block_digest, d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first, d_lit, d_count, d_res_status, d_status);
 }
 
 // kept candidates, distinct rows decoded or read, and hits of y's last execution (read back; none before the first)
@@ -1075,6 +1142,97 @@ int mscomp_amd_syncer_counts(mscomp_amd_syncer* y, uint32_t out[3])
 	if (hipMemcpy(cnt, y->s.count, sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess) { return -1; }
 	out[0] = (uint32_t)cnt[2]; out[1] = (uint32_t)cnt[7]; out[2] = (uint32_t)cnt[4];
 	return 0;
+}
+
+// ---- block digesters (include/mscomp_amd.h; kernels: digest.hip, the table passes in blocks.hip) ----
+// A digester writes and checks the digest column of a container's blocks, as mscomp_amd_blocks_crc and _check write and check the CRC
+// column, with the container's table passes over tables of its own: the columns of BlocksTab those passes touch, a leaf digest per
+// possible leaf and -- for check -- a digest per possible block. No inner plan, no staging area.
+#pragma GCC visibility push(hidden)
+struct mscomp_amd_digester {
+	mscomp_amd_ctx* ctx = nullptr;
+	uint32_t shift = 0, n_res = 0, n_blocks = 0;       // block_size = 1 << shift; n_blocks = n_blocks_max
+	uint64_t in_total_max = 0;
+	GraphRun<5> brun; GraphRun<8> krun;                // blocks, check
+	DevBuf tab;                                        // digest_tab
+	BlocksTab t{};                                     // (the columns the inner plans, compress and decompress alone use stay null)
+	DigestTab d{};
+};
+#pragma GCC visibility pop
+
+// the columns of a digester's tables from `base` on (n resources, m blocks at most), the 16-byte columns first; returns where they end
+static uintptr_t digest_tab(mscomp_amd_digester* g, void* base, size_t n, size_t m)
+{
+	Carve k(base);
+	BlocksTab& t = g->t;
+	g->d.leaf = k.w(4 * (m << (g->shift - DG_LEAF_SHIFT))); g->d.out = k.w(4 * m);
+	t.res_a = k.q(n); t.res_b = k.q(n); t.unit_first = k.q(n + 1);
+	t.in_off = k.q(m); t.in_len = k.q(m); t.out_off = k.q(m); t.out_cap = k.q(m); t.ulen = k.q(m);
+	t.rstat = k.i(n);
+	g->d.off = t.in_off; g->d.len = t.in_len; g->d.count = t.unit_first + n; g->d.n_max = (uint32_t)m; g->d.shift = g->shift;
+	return k.at;
+}
+
+MSCompStatus mscomp_amd_digester_create(mscomp_amd_ctx* c, uint32_t block_size, size_t n_res, uint64_t in_total_max, uint32_t flags, mscomp_amd_digester** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || !block_size_ok(block_size) || !count_ok(n_res)) { return MSCOMP_ARG_ERROR; }
+	if (in_total_max >> 50 || in_total_max / block_size > 0x7FFFFFF0ull - n_res) { return MSCOMP_MEM_ERROR; }   // (checked before the context is used)
+	const uint64_t M = n_res + in_total_max / block_size;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_digester> d(new (std::nothrow) mscomp_amd_digester());
+	if (!d) { return MSCOMP_MEM_ERROR; }
+	d->ctx = c; d->shift = (uint32_t)__builtin_ctz(block_size); d->n_res = (uint32_t)n_res; d->n_blocks = (uint32_t)M; d->in_total_max = in_total_max;
+	d->brun.never = d->krun.never = n_res == 0;
+	if (!d->tab.reserve(digest_tab(d.get(), nullptr, n_res, M) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	digest_tab(d.get(), d->tab.p, n_res, M);
+	*out = d.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_digester_destroy(mscomp_amd_digester* d) { destroy_object(d, [d] { d->tab.release(); }); }
+
+// blocks: the container's compress tables (t.unit_first = block_first, t.in_off / t.in_len = the blocks, t.rstat), the leaves, the roots
+// straight into the caller's column, with the statuses. check: the container's check tables (t.unit_first / t.res_b = units and first
+// block of the clipped ranges, t.in_off / t.in_len = the blocks in d_out, t.ulen = their entry of d_block_digest), the leaves, the roots
+// into d.out, the fold.
+MSCompStatus mscomp_amd_digester_blocks(mscomp_amd_digester* d, const uint8_t* d_data, const uint64_t* d_res_off, const uint64_t* d_res_len, uint32_t* d_block_digest,
+                                        int32_t* d_status)
+{
+	if (!d || (d->n_blocks && !d_block_digest) || (d->n_res && (!d_res_off || !d_res_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (d->in_total_max && !d_data) { return MSCOMP_ARG_ERROR; }
+	if (d->n_res == 0) { return MSCOMP_OK; }               // (no resource, no block: n_blocks_max is 0 too)
+	mscomp_amd_ctx* c = d->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[5] = { d_data, d_res_off, d_res_len, d_block_digest, d_status };
+	return plan_run(d->brun, c, args, [&] {
+		const BlocksTab& t = d->t;
+		{ KernelTimer k(c, "bk_ctables"); launch_blocks_ctables(c->stream, d->n_res, d->n_blocks, d->shift, d->in_total_max, d_res_off, d_res_len, t.unit_first, t); }
+		{ KernelTimer k(c, "dg_leaf_kernel"); launch_digest_leaves(c->stream, d_data, d->d, c->crc_blocks); }
+		{ KernelTimer k(c, "dg_root_kernel"); launch_digest_roots(c->stream, d->d, d_block_digest, d->n_res, t.rstat, d_status); }
+	});
+}
+
+MSCompStatus mscomp_amd_digester_check(mscomp_amd_digester* d, const uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_res_len, const uint64_t* d_block_first,
+                                       const uint64_t* d_range, const uint32_t* d_block_digest, uint64_t* d_out_len, int32_t* d_status)
+{
+	if (!d || !d_block_first || (d->n_blocks && !d_block_digest) || (d->n_res && (!d_out_off || !d_res_len || !d_out_len || !d_status))) { return MSCOMP_ARG_ERROR; }
+	if (d->in_total_max && !d_out) { return MSCOMP_ARG_ERROR; }
+	if (d->n_res == 0) { return MSCOMP_OK; }
+	mscomp_amd_ctx* c = d->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[8] = { d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_digest, d_out_len, d_status };
+	return plan_run(d->krun, c, args, [&] {
+		const BlocksTab& t = d->t;
+		{ KernelTimer k(c, "bk_ktables"); launch_blocks_ktables(c->stream, d->n_res, d->n_blocks, d->shift, d->in_total_max, d_res_len, d_block_first, d_range, d_out_off, d_status, t); }
+		{ KernelTimer k(c, "dg_leaf_kernel"); launch_digest_leaves(c->stream, d_out, d->d, c->crc_blocks); }
+		{ KernelTimer k(c, "dg_root_kernel"); launch_digest_roots(c->stream, d->d, d->d.out, 0, nullptr, nullptr); }
+		{ KernelTimer k(c, "dg_kfold_kernel"); launch_digest_kfold(c->stream, d->n_res, d_block_digest, t, d->d, d_out_len, d_status); }
+	});
 }
 
 // ---- the scratch hooks' view of the objects above (api.hip: mscomp_amd_debug_scratch_*) ----

@@ -221,7 +221,6 @@ __global__ __launch_bounds__(256) void bk_crcgroups_kernel(uint32_t n_res, uint3
 	grp[b] = g; after[b] = a;
 }
 
-#define BK_LEAVE 1                                        // (rstat of a resource that was not MSCOMP_OK on entry to check: not a status)
 // check: bk_dres_kernel's checks 1 and 2 and its clipped range for the resources that are MSCOMP_OK on entry; the others have no units
 __global__ __launch_bounds__(DV_THREADS) void bk_kres_kernel(uint32_t n, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* __restrict__ res_len,
                                                             const u64* __restrict__ block_first, const u64* __restrict__ range, const int32_t* __restrict__ d_status,

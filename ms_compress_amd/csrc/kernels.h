@@ -280,6 +280,7 @@ void launch_blocks_sfold(hipStream_t st, uint32_t n_res, const BlocksTab& t, u64
 void launch_blocks_crcgroups(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, const u64* res_len, const u64* block_first, const BlocksTab& t);
 // check, in front of the CRC kernels: checks 1 and 2 and the clipped range of the resources that are MSCOMP_OK in d_status (t.unit_first, t.res_b,
 // t.rstat), then per unit where the block lies in the output (t.in_off, t.in_len) and its entry of d_block_crc (t.ulen); behind them: the verdicts
+#define BK_LEAVE 1                                        // (t.rstat of a resource that was not MSCOMP_OK on entry to check: not a status)
 void launch_blocks_ktables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* res_len, const u64* block_first,
                            const u64* range, const u64* d_out_off, const int32_t* d_status, const BlocksTab& t);
 void launch_blocks_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_crc, const BlocksTab& t, u64* d_out_len, int32_t* d_status);
@@ -629,6 +630,36 @@ void launch_sync_confirm(hipStream_t st, uint32_t n_cand, uint32_t shift, const 
 // select and emit (one workgroup): the greedy walk per unit, the hits, the literal runs, the counts (distinct: the reader core's count of owners, may be null)
 void launch_sync_select(hipStream_t st, uint32_t n_units, uint32_t shift, const SyncTab& t, const int32_t* status, const uint32_t* distinct, u64* hit_first, u64* req, u64* req_off,
                         u64* lit_first, u64* lit, u64* count);
+
+// the digest syncer's pass 5 around the digest kernels (digest.hip): behind launch_sync_requests, the unit table -- off / len (n_cand
+// each) = the B-byte window of every kept candidate in the new data, (0, 0) behind the kept ones -- and t.qstat (MSCOMP_OK, or
+// MSCOMP_DATA_ERROR for a row outside the numbering); behind the root pass, the window's digest in wdig (4 per candidate) against the
+// four words at the candidate's table row in block_digest: a mismatch sets t.flag. No stored byte is read.
+void launch_sync_digest_units(hipStream_t st, uint32_t n, uint32_t n_cand, uint32_t shift, const SyncTab& t, u64* off, u64* len);
+void launch_sync_digest_compare(hipStream_t st, const SpliceView& v, uint32_t n, uint32_t n_cand, const uint32_t* block_digest, const SyncTab& t, const uint32_t* wdig);
+
+// ---- BLAKE2s block digests (digest.hip; mscomp_amd_digester_*, mscomp_amd_syncer_sync_digest) ----
+// digest(D) of a unit of 1 <= e <= B bytes: BLAKE2s in tree mode, leaves of DG_LEAF bytes, two levels, unlimited fan-out, 16 bytes inner
+// and final, no key. The passes work on a device unit table: unit u = len[u] bytes at base + off[u] for u < min(*count, n_max), and its
+// leaf k has the slot (u << (shift - 10)) + k of `leaf`, whatever the other units' lengths: no numbering pass, and 16 B / 1024 bytes of
+// scratch per possible unit.
+#define DG_LEAF       1024u
+#define DG_LEAF_SHIFT 10u
+struct DigestTab {
+	const u64* off; const u64* len;                    // n_max each
+	const u64* count;                                  // 1: the units of this execution
+	uint32_t* leaf;                                    // 4 (n_max << (shift - 10)): the leaves' inner digests
+	uint32_t* out;                                     // 4 n_max: a scratch column for the units' digests (check, sync); blocks writes the caller's
+	uint32_t n_max, shift;
+};
+// the leaf pass: a fixed grid dealt over the leaf slots, a lane per leaf of up to 16 compressions; `blocks` = crc_dev_blocks()
+void launch_digest_leaves(hipStream_t st, const uint8_t* base, const DigestTab& d, uint32_t blocks);
+// the root pass, a lane per unit over its 16 n bytes of leaf digests: out[4 u ..] (n_max entries; four zero words at and behind *count
+// and for an empty unit). rstat (n_res, may be null): copied to d_status by the same launch
+void launch_digest_roots(hipStream_t st, const DigestTab& d, uint32_t* out, uint32_t n_res, const int32_t* rstat, int32_t* d_status);
+// check, behind the root pass (bk_kfold_kernel with a digest for a CRC word): a failed table check, or a block whose digest in d.out is not
+// the one at block_digest[4 t.ulen[u] ..], into d_status and d_out_len
+void launch_digest_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_digest, const BlocksTab& t, const DigestTab& d, u64* d_out_len, int32_t* d_status);
 
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status

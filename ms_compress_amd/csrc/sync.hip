@@ -5,7 +5,8 @@
 // and W rolls: W(p + 1) = W(p) x^8 ^ raw(M[p + B]) ^ raw(M[p]) x^(8B) -- two table lookups per position, t0[(W ^ hi) & 255] and tb[lo].
 // The boundary passes leave raw(M[: q]) at every 64th byte, so every lane of the scan starts a run of 64 positions from two words; the
 // scan walks the positions twice (a tile pass that counts, a runs pass that writes), with a tile scan between them, and stores nothing
-// per position. Candidates are confirmed against the rows the reader core decodes (reader.hip, unchanged). DESIGN.md 4.20.
+// per position. Candidates are confirmed against the rows the reader core decodes (reader.hip, unchanged) -- or, by a digest syncer,
+// by the BLAKE2s digest of their window against the store's digest column (digest.hip), without a stored byte. DESIGN.md 4.20, 4.21.
 #include "rowpass.h"
 #include "crcmath.h"
 
@@ -449,6 +450,35 @@ __global__ __launch_bounds__(CPD_THREADS) void sy_confirm_kernel(uint32_t shift,
 	});
 }
 
+// ---- confirm by digest (mscomp_amd_syncer_sync_digest; the digest kernels: digest.hip) ----
+// Behind sy_req_kernel, one thread per slot of the kept list: the window of a kept candidate as a unit of the digest passes, and the
+// status the reader core would have written -- MSCOMP_OK, since nothing is decoded; a row outside the numbering is refuted.
+__global__ __launch_bounds__(256) void sy_dunits_kernel(uint32_t n, uint32_t ncand, uint32_t shift, SyncTab t, u64* __restrict__ off, u64* __restrict__ len)
+{
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= ncand) { return; }
+	u64 o = 0, l = 0;
+	int32_t st = 0;
+	if (i < t.count[2]) {
+		o = t.uoff[t.cunit[i]] + t.cpos[i]; l = (u64)1 << shift;               // (cpos + B <= ulen: rule 3)
+		if (t.crow[i] >= t.ufirst[n]) { st = -3; }                             // MSCOMP_DATA_ERROR
+	}
+	off[i] = o; len[i] = l; t.qstat[i] = st;
+}
+
+// Behind the root pass, one thread per kept candidate: its window's digest against the four words at its row of the store's table
+__global__ __launch_bounds__(256) void sy_dcompare_kernel(SpliceView v, uint32_t n, uint32_t ncand, const uint32_t* __restrict__ block_digest, SyncTab t,
+                                                         const uint32_t* __restrict__ wdig)
+{
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= ncand || i >= t.count[2] || t.qstat[i] != 0) { return; }
+	const u64 row = t.crow[i];
+	const uint32_t x = res_of_block(t.ufirst, n, row);
+	const uint32_t* a = wdig + 4u * (u64)i;
+	const uint32_t* b = block_digest + 4u * (v.first[x] + (row - t.ufirst[x]));   // (first[x] + k < first[x + 1] <= v.nbt: rule 1)
+	if (a[0] != b[0] || a[1] != b[1] || a[2] != b[2] || a[3] != b[3]) { t.flag[i] = 1u; }
+}
+
 // ---- select and emit ----
 // the first slot of the kept list (sorted by unit, then position) that belongs to unit u or a later one
 __device__ __forceinline__ u64 sy_lower(const uint32_t* __restrict__ cunit, u64 kept, uint32_t u)
@@ -602,6 +632,18 @@ void launch_sync_confirm(hipStream_t st, uint32_t n_cand, uint32_t shift, const 
 	if (n_cand == 0) { return; }
 	const uint32_t ppu_shift = shift > DD_PIECE_SHIFT ? shift - DD_PIECE_SHIFT : 0u;
 	hipLaunchKernelGGL(sy_confirm_kernel, fixed_grid((u64)n_cand << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, shift, ppu_shift, in, t, r);
+}
+
+void launch_sync_digest_units(hipStream_t st, uint32_t n, uint32_t n_cand, uint32_t shift, const SyncTab& t, u64* off, u64* len)
+{
+	if (n_cand == 0) { return; }
+	hipLaunchKernelGGL(sy_dunits_kernel, dim3((n_cand + 255u) / 256u), dim3(256), 0, st, n, n_cand, shift, t, off, len);
+}
+
+void launch_sync_digest_compare(hipStream_t st, const SpliceView& v, uint32_t n, uint32_t n_cand, const uint32_t* block_digest, const SyncTab& t, const uint32_t* wdig)
+{
+	if (n_cand == 0) { return; }
+	hipLaunchKernelGGL(sy_dcompare_kernel, dim3((n_cand + 255u) / 256u), dim3(256), 0, st, v, n, n_cand, block_digest, t, wdig);
 }
 
 void launch_sync_select(hipStream_t st, uint32_t n_units, uint32_t shift, const SyncTab& t, const int32_t* status, const uint32_t* distinct, u64* hit_first, u64* req, u64* req_off,
