@@ -224,7 +224,7 @@ MSCompStatus mscomp_amd_blocks_check(mscomp_amd_blocks* b, const uint8_t* d_out,
 		const BlocksTab& t = b->t;
 		{ KernelTimer k(c, "bk_ktables"); launch_blocks_ktables(c->stream, b->n_res, b->n_blocks, b->shift, b->in_total_max, d_res_len, d_block_first, d_range, d_out_off, d_status, t); }
 		crc_pass(c, b->n_blocks, d_out, t.in_off, t.in_len, t.aux_a, t.ucrc);
-		{ KernelTimer k(c, "bk_kfold_kernel"); launch_blocks_kfold(c->stream, b->n_res, d_block_crc, t, d_out_len, d_status); }
+		{ KernelTimer k(c, "bk_kfold_kernel"); launch_blocks_kfold(c->stream, b->n_res, t.ucrc, d_block_crc, 1, t, d_out_len, d_status); }
 	});
 }
 
@@ -620,9 +620,9 @@ struct mscomp_amd_deduper {
 static uintptr_t dedup_tab(DedupTab& t, void* base, size_t n)
 {
 	Carve k(base);
-	t.slots = 2 * (u64)n + 64;
-	t.ufirst = k.q(n + 1); t.key = k.q(n); t.tkey = k.q(t.slots);
-	t.tmin = k.w(t.slots); t.slot_of = k.w(n); t.cand = k.w(n); t.flag = k.w(n); t.rlist = k.w(n);
+	t.kt.slots = 2 * (u64)n + 64;
+	t.ufirst = k.q(n + 1); t.key = k.q(n); t.kt.key = k.q(t.kt.slots);
+	t.kt.min = k.w(t.kt.slots); t.slot_of = k.w(n); t.cand = k.w(n); t.flag = k.w(n); t.rlist = k.w(n);
 	return k.at;
 }
 
@@ -640,9 +640,9 @@ static uintptr_t match_tab(MatchTab& t, void* base, size_t n, size_t m, size_t m
 {
 	Carve k(base);
 	const size_t slots = 2 * m + 64;
-	t.slots = slots < 0xFFFFFFF0u ? slots : 0xFFFFFFF0u;   // (a slot's index is a 32-bit word, and all-ones is "none")
-	t.ufirst = k.q(n + 1); t.pfirst = k.q(5 * n); t.tsum = k.q(8 * (size_t)row_tiles((uint32_t)mn)); t.tkey = k.q(slots); t.nref = k.q(1);
-	t.tmin = k.w(slots); t.slot_of = k.w(m); t.flag = k.w(m); t.rep = k.w(m); t.rlist = k.w(m); t.flocal = k.w(mn);
+	t.kt.slots = slots < 0xFFFFFFF0u ? slots : 0xFFFFFFF0u;   // (a slot's index is a 32-bit word, and all-ones is KT_NONE)
+	t.ufirst = k.q(n + 1); t.pfirst = k.q(5 * n); t.tsum = k.q(8 * (size_t)row_tiles((uint32_t)mn)); t.kt.key = k.q(slots); t.nref = k.q(1);
+	t.kt.min = k.w(slots); t.slot_of = k.w(m); t.flag = k.w(m); t.rep = k.w(m); t.rlist = k.w(m); t.flocal = k.w(mn);
 	return k.at;
 }
 
@@ -793,7 +793,7 @@ MSCompStatus mscomp_amd_deduper_match(mscomp_amd_deduper* d, const mscomp_amd_bl
 	const uint32_t N = (uint32_t)n, n_store = (uint32_t)(n - next->n_res);
 	return plan_run(d->mrun, c, args, [&] {
 		const MatchTab& t = d->m;
-		{ KernelTimer tm(c, "dd_clear_kernel"); launch_dedup_clear(c->stream, t.slots, t.tkey, t.tmin, c->crc_blocks); }
+		{ KernelTimer tm(c, "dd_clear_kernel"); launch_dedup_clear(c->stream, t.kt, c->crc_blocks); }
 		{ KernelTimer tm(c, "mt_seed_kernel"); launch_match_seed(c->stream, k, N, n_store, d->nbt, d->nbn, d->shift, t, d_status); }
 		if (d->nbt) {
 			{ KernelTimer tm(c, "dd_rows_kernel"); launch_dedup_rule3(c->stream, k, N, d->nbt, t.ufirst, d_status, c->crc_blocks); }
@@ -989,10 +989,10 @@ static uintptr_t sync_tab(SyncTab& t, void* base, size_t n, size_t nbt, size_t n
 	uint32_t slot_shift = 32u - 6u;
 	while (slots < 2 * nbt + 64) { slots <<= 1; --slot_shift; }          // (at most 2^32: nbt <= 0x7FFFFFF0)
 	const size_t tiles = (size_t)(in_total_max / SYNC_TILE) + nu, pieces = (size_t)(in_total_max / SYNC_RUN) + nu;
-	t.slots = slots; t.slot_shift = slot_shift; t.tiles_max = (uint32_t)tiles;
-	t.ufirst = k.q(n + 1); t.tkey = k.q(slots); t.cum = k.q(nu + 1); t.uoff = k.q(nu); t.ulen = k.q(nu); t.pfirst = k.q(nu + 1); t.tfirst = k.q(nu + 1);
+	t.kt.slots = slots; t.slot_shift = slot_shift; t.tiles_max = (uint32_t)tiles;
+	t.ufirst = k.q(n + 1); t.kt.key = k.q(slots); t.cum = k.q(nu + 1); t.uoff = k.q(nu); t.ulen = k.q(nu); t.pfirst = k.q(nu + 1); t.tfirst = k.q(nu + 1);
 	t.tword = k.q(8 * tiles); t.cpos = k.q(nc); t.req = k.q(3 * nc); t.qlen = k.q(nc); t.count = k.q(8);
-	t.tmin = k.w(slots); t.bits = k.w(SYNC_BIT_WORDS); t.consts = k.w(SYNC_CONSTS); t.pabs = k.w(pieces); t.traw = k.w(tiles);
+	t.kt.min = k.w(slots); t.bits = k.w(SYNC_BIT_WORDS); t.consts = k.w(SYNC_CONSTS); t.pabs = k.w(pieces); t.traw = k.w(tiles);
 	t.cunit = k.w(nc); t.crow = k.w(nc); t.flag = k.w(nc); t.qstat = k.i(nc);
 	return k.at;
 }
@@ -1231,7 +1231,7 @@ MSCompStatus mscomp_amd_digester_check(mscomp_amd_digester* d, const uint8_t* d_
 		{ KernelTimer k(c, "bk_ktables"); launch_blocks_ktables(c->stream, d->n_res, d->n_blocks, d->shift, d->in_total_max, d_res_len, d_block_first, d_range, d_out_off, d_status, t); }
 		{ KernelTimer k(c, "dg_leaf_kernel"); launch_digest_leaves(c->stream, d_out, d->d, c->crc_blocks); }
 		{ KernelTimer k(c, "dg_root_kernel"); launch_digest_roots(c->stream, d->d, d->d.out, 0, nullptr, nullptr); }
-		{ KernelTimer k(c, "dg_kfold_kernel"); launch_digest_kfold(c->stream, d->n_res, d_block_digest, t, d->d, d_out_len, d_status); }
+		{ KernelTimer k(c, "dg_kfold_kernel"); launch_blocks_kfold(c->stream, d->n_res, d->d.out, d_block_digest, 4, t, d_out_len, d_status); }
 	});
 }
 

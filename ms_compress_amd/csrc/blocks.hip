@@ -277,17 +277,26 @@ __global__ __launch_bounds__(256) void bk_kunits_kernel(uint32_t n_res, uint32_t
 	in_off[u] = io; in_len[u] = il; which[u] = j;
 }
 
-// ... one wave per resource, behind the CRC kernels: a failed table check, or a block whose CRC is not the one given, into d_status and
-// d_out_len. A resource that passes, or was not MSCOMP_OK on entry, is not written.
-__global__ __launch_bounds__(256) void bk_kfold_kernel(uint32_t n_res, const u64* __restrict__ unit_first, const u64* __restrict__ which, const uint32_t* __restrict__ ucrc,
-                                                      const uint32_t* __restrict__ block_crc, const int32_t* __restrict__ rstat, u64* __restrict__ d_out_len, int32_t* __restrict__ d_status)
+// ... one wave per resource, behind the CRC kernels (W = 1: an entry is a CRC word) or a digester's root pass (W = 4: a digest): a failed
+// table check, or a block whose entry in `read` is not the one given, into d_status and d_out_len. A resource that passes, or was not
+// MSCOMP_OK on entry, is not written.
+template <uint32_t W>
+__global__ __launch_bounds__(256) void bk_kfold_kernel(uint32_t n_res, const u64* __restrict__ unit_first, const u64* __restrict__ which, const uint32_t* __restrict__ read,
+                                                      const uint32_t* __restrict__ given, const int32_t* __restrict__ rstat, u64* __restrict__ d_out_len, int32_t* __restrict__ d_status)
 {
 	const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
 	if (r >= n_res) { return; }
 	const int32_t st = rstat[r];
 	if (st == BK_LEAVE) { return; }
 	bool bad = false;
-	if (st == 0) { for (u64 u = unit_first[r] + lane; u < unit_first[r + 1u]; u += 64u) { if (ucrc[u] != block_crc[which[u]]) { bad = true; } } }
+	if (st == 0) {
+		for (u64 u = unit_first[r] + lane; u < unit_first[r + 1u]; u += 64u) {
+			const uint32_t* a = read + W * u;
+			const uint32_t* b = given + W * which[u];
+			#pragma unroll
+			for (uint32_t i = 0; i < W; ++i) { if (a[i] != b[i]) { bad = true; } }
+		}
+	}
 	const bool any_bad = __ballot(bad) != 0;
 	if (lane == 0 && (st != 0 || any_bad)) { d_status[r] = st != 0 ? st : -3; d_out_len[r] = 0; }   // MSCOMP_DATA_ERROR
 }
@@ -504,10 +513,11 @@ void launch_blocks_ktables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint3
 	                   t.in_off, t.in_len, t.ulen);
 }
 
-void launch_blocks_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_crc, const BlocksTab& t, u64* d_out_len, int32_t* d_status)
+void launch_blocks_kfold(hipStream_t st, uint32_t n_res, const uint32_t* read, const uint32_t* given, uint32_t words, const BlocksTab& t, u64* d_out_len, int32_t* d_status)
 {
 	if (n_res == 0) { return; }
-	hipLaunchKernelGGL(bk_kfold_kernel, dim3((n_res + 3u) / 4u), dim3(256), 0, st, n_res, t.unit_first, t.ulen, t.ucrc, block_crc, t.rstat, d_out_len, d_status);
+	hipLaunchKernelGGL(words == 4u ? bk_kfold_kernel<4u> : bk_kfold_kernel<1u>, dim3((n_res + 3u) / 4u), dim3(256), 0, st, n_res, t.unit_first, t.ulen, read, given, t.rstat,
+	                   d_out_len, d_status);
 }
 
 } // namespace msc

@@ -23,6 +23,14 @@ __device__ __forceinline__ u64 sgpr64(u64 v)   // tell the compiler a wave-unifo
 {
 	return ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
+// op over the values of all 64 lanes, in every lane (a butterfly; op associative and commutative, v of 32 or 64 bits)
+template <class T, class Op>
+__device__ __forceinline__ T wave_all(T v, Op op)
+{
+	#pragma unroll
+	for (uint32_t d = 32u; d; d >>= 1) { v = op(v, __shfl_xor(v, d, 64)); }
+	return v;
+}
 
 // DPP scans over the 64 lanes: row_shr 1,2,4,8 then row_bcast 15/31, the max/add folded into the DPP instruction itself
 // (the builtin form costs v_mov + v_mov_dpp + op per step). A lane whose DPP source is out of range or whose row is

@@ -87,7 +87,7 @@ __device__ __forceinline__ void crc_part(const uint32_t (*t)[256], const uint32_
 		}
 		st = crc_mul(st, c[lane]);
 	}
-	body = wave_xor(st);
+	body = wave_all(st, [](uint32_t a, uint32_t b) { return a ^ b; });
 	uint32_t ts = 0;
 	for (uint32_t j = 0; j < tlen; ++j) { const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)tb, (int)j); ts = (ts >> 8) ^ t[0][(ts ^ b) & 255u]; }
 	tail = ts;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void rcrc_fold_kernel(uint32_t n_res, uint32_t
 		}
 		const uint32_t r0 = uniform(r);
 		if (__ballot(r != r0) == 0) {
-			v = wave_xor(v);
+			v = wave_all(v, [](uint32_t a, uint32_t b) { return a ^ b; });
 			if (lane == 0 && r0 != 0xFFFFFFFFu && v != 0) { atomicXor(&res_crc[r0], v); }
 		} else if (r != 0xFFFFFFFFu && v != 0) { atomicXor(&res_crc[r], v); }
 	}

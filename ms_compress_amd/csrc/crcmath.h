@@ -79,11 +79,5 @@ __device__ __forceinline__ uint4 crc_load_front(uintptr_t q, uintptr_t p)
 	if (q + 16u > p) { for (uint32_t j = (uint32_t)(p - q); j < 16u; ++j) { w[j >> 2] |= (uint32_t)*reinterpret_cast<const uint8_t*>(q + j) << (8u * (j & 3u)); } }
 	return make_uint4(w[0], w[1], w[2], w[3]);
 }
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
-{
-	#pragma unroll
-	for (uint32_t d = 32; d; d >>= 1) { v ^= __shfl_xor(v, d, 64); }
-	return v;
-}
 
 } // namespace msc

@@ -1,25 +1,14 @@
 // dedup.hip -- the passes of a block deduper (mscomp_amd_deduper_*, include/mscomp_amd.h): which resources of up to four block containers
 // of one format and one block size hold the same bytes, decided on the STORED form -- the stored form of a block depends only on its data,
 // the format and the block size -- and answered as a pick list a splicer takes. Candidates come from the tables and 32 bytes per row (a
-// 64-bit key per resource, an open-addressing table over the keys); the only pass over the data is the compare that confirms a candidate.
+// 64-bit key per resource, the key table over the keys: rowpass.h kt_*); the only pass over the data is the compare that confirms a candidate.
 // The sources travel by value in the kernel arguments, as one SpliceSrc that a lane indexes (kernels.h sp_view). DESIGN.md 4.13.
 #include "rowpass.h"
 
 namespace msc {
 
-
-__device__ __forceinline__ u64 dd_wave_xor(u64 v)
-{
-	#pragma unroll
-	for (uint32_t d = 32u; d; d >>= 1) { v ^= __shfl_xor(v, d, 64); }
-	return v;
-}
-
-// the key table: every slot empty, no index yet
-__global__ __launch_bounds__(256) void dd_clear_kernel(u64 slots, u64* __restrict__ tkey, uint32_t* __restrict__ tmin)
-{
-	for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < slots; i += (u64)gridDim.x * 256u) { tkey[i] = 0; tmin[i] = 0xFFFFFFFFu; }
-}
+// a key table cleared: dedup's, match's
+__global__ __launch_bounds__(256) void dd_clear_kernel(KeyTable kt) { kt_clear(kt); }
 
 // Seed, one block: rules 1 and 2 per resource, the status, the key word seeded with L, the mismatch flag cleared, and ufirst (n + 1): the
 // rows of the resources that passed, numbered densely in resource order (no room rule: rule 1 keeps a resource's rows within its view's
@@ -45,11 +34,11 @@ template <bool KEY>
 __global__ __launch_bounds__(256) void dd_rows_kernel(SpliceSrc src, uint32_t n, uint32_t with_crc,
                                                      const u64* __restrict__ ufirst, u64* __restrict__ key, int32_t* status)
 {
-	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t lane = threadIdx.x & 63u, none = ~0u;                      // (none: a lane without a row to fold)
 	const u64 units = ufirst[n], step = (u64)gridDim.x * 256u;
 	for (u64 base = (u64)blockIdx.x * 256u + (threadIdx.x & ~63u); base < units; base += step) {
 		const u64 u = base + lane;
-		uint32_t g = 0xFFFFFFFFu;
+		uint32_t g = none;
 		u64 h = 0;
 		if (u < units) {
 			const uint32_t x = res_of_block(ufirst, n, u);
@@ -61,56 +50,41 @@ __global__ __launch_bounds__(256) void dd_rows_kernel(SpliceSrc src, uint32_t n,
 			if (!KEY) {
 				if (!(o0 <= o1 && o1 <= v.packed_len)) { status[x] = -3; }     // rule 3: MSCOMP_DATA_ERROR
 			} else if (status[x] == 0) {
-				const u64 len = o1 - o0;
-				const uint8_t* p = v.packed + o0;
-				u64 w[4];                                                      // first 16 | last 16 stored bytes
-				dd_edges(p, len, w);
-				h = dd_mix(k + 1u);
-				h = dd_mix(h ^ len);
-				if (with_crc) { h = dd_mix(h ^ ((u64)v.crc[j] | (u64)1 << 32)); }
-				h = dd_mix(h ^ w[0]); h = dd_mix(h ^ w[1]); h = dd_mix(h ^ w[2]); h = dd_mix(h ^ w[3]);
+				h = row_key(dd_mix(k + 1u), o1 - o0, with_crc, with_crc ? v.crc[j] : 0u, v.packed + o0);
 				g = x;
 			}
 		}
 		if (KEY) {
 			const uint32_t g0 = uniform(g);
 			if (__ballot(g != g0) == 0) {
-				h = dd_wave_xor(h);
-				if (lane == 0 && g0 != 0xFFFFFFFFu) { atomicXor(reinterpret_cast<unsigned long long*>(&key[g0]), (unsigned long long)h); }
-			} else if (g != 0xFFFFFFFFu) { atomicXor(reinterpret_cast<unsigned long long*>(&key[g]), (unsigned long long)h); }
+				h = wave_all(h, [](u64 a, u64 b) { return a ^ b; });
+				if (lane == 0 && g0 != none) { atomicXor(reinterpret_cast<unsigned long long*>(&key[g0]), (unsigned long long)h); }
+			} else if (g != none) { atomicXor(reinterpret_cast<unsigned long long*>(&key[g]), (unsigned long long)h); }
 		}
 	}
 }
 
-// One thread per accepted resource: its key into the open-addressing table -- a 64-bit compare-and-swap claims an empty slot for the key,
-// linear probing past slots of other keys --, and its index into the slot's minimum. A slot holds one key, so two resources share a slot
-// exactly when they share their key; the minimum does not depend on the order of arrival.
-__global__ __launch_bounds__(256) void dd_insert_kernel(uint32_t n, u64 slots, const u64* __restrict__ key, const int32_t* __restrict__ status,
-                                                       u64* tkey, uint32_t* tmin, uint32_t* __restrict__ slot_of)
+// One thread per accepted resource: it claims its key's slot of the key table and puts its index into the slot's minimum. (No slot: a
+// damaged table; the resource is then its own candidate.)
+__global__ __launch_bounds__(256) void dd_insert_kernel(uint32_t n, KeyTable kt, const u64* __restrict__ key, const int32_t* __restrict__ status, uint32_t* __restrict__ slot_of)
 {
 	for (u64 g = (u64)blockIdx.x * 256u + threadIdx.x; g < n; g += (u64)gridDim.x * 256u) {
 		if (status[g] != 0) { continue; }
-		const u64 kk = key[g] ? key[g] : 1u;                                  // (0 is the empty slot)
-		u64 at = dd_mix(kk) % slots;
-		for (;;) {
-			const u64 was = atomicCAS(reinterpret_cast<unsigned long long*>(&tkey[at]), 0ull, (unsigned long long)kk);
-			if (was == 0 || was == kk) { break; }
-			at = at + 1u == slots ? 0 : at + 1u;                                // (the table has more slots than there are resources: the walk ends)
-		}
-		atomicMin(&tmin[at], (uint32_t)g);
-		slot_of[g] = (uint32_t)at;
+		const uint32_t slot = kt_claim(kt, key[g], dd_mix(kt_key(key[g])) % kt.slots);
+		if (slot != KT_NONE) { atomicMin(&kt.min[slot], (uint32_t)g); }
+		slot_of[g] = slot;
 	}
 }
 
-// behind it, one thread per resource: the candidate -- the smallest accepted resource with the same key, itself for a refused one -- and
-// the first thing that can tell two resources of one key apart: their lengths
+// behind it, one thread per resource: the candidate -- the smallest accepted resource with the same key, itself for a refused one or one
+// without a slot -- and the first thing that can tell two resources of one key apart: their lengths
 __global__ __launch_bounds__(256) void dd_cand_kernel(SpliceSrc src, uint32_t n, const int32_t* __restrict__ status,
                                                      const uint32_t* __restrict__ tmin, const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ cand,
                                                      uint32_t* __restrict__ flag)
 {
 	for (u64 g = (u64)blockIdx.x * 256u + threadIdx.x; g < n; g += (u64)gridDim.x * 256u) {
 		uint32_t c = (uint32_t)g;
-		if (status[g] == 0) {
+		if (status[g] == 0 && slot_of[g] != KT_NONE) {
 			c = tmin[slot_of[g]];
 			if (c != (uint32_t)g) {
 				u64 s, r, sc, rc;
@@ -220,9 +194,9 @@ __global__ __launch_bounds__(DV_THREADS) void dd_settle_kernel(SpliceSrc src, ui
 	if (tid == 0) { count[0] = tot[0]; count[1] = n; count[2] = tot[1]; count[3] = nref[0]; }
 }
 
-void launch_dedup_clear(hipStream_t st, u64 slots, u64* tkey, uint32_t* tmin, uint32_t blocks)
+void launch_dedup_clear(hipStream_t st, const KeyTable& kt, uint32_t blocks)
 {
-	hipLaunchKernelGGL(dd_clear_kernel, fixed_grid(slots, 256u, blocks), dim3(256), 0, st, slots, tkey, tmin);
+	hipLaunchKernelGGL(dd_clear_kernel, fixed_grid(kt.slots, 256u, blocks), dim3(256), 0, st, kt);
 }
 
 void launch_dedup_rule3(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t rows_max, const u64* ufirst, int32_t* status, uint32_t blocks)
@@ -233,7 +207,7 @@ void launch_dedup_rule3(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32
 void launch_dedup_judge(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, const DedupTab& t, int32_t* status, uint32_t blocks)
 {
 	if (n_max == 0) { return; }
-	launch_dedup_clear(st, t.slots, t.tkey, t.tmin, blocks);
+	launch_dedup_clear(st, t.kt, blocks);
 	hipLaunchKernelGGL(dd_seed_kernel, dim3(1), dim3(DV_THREADS), 0, st, src, n, shift, t.ufirst, t.key, t.flag, status);
 	if (rows_max == 0) { return; }
 	launch_dedup_rule3(st, src, n, rows_max, t.ufirst, status, blocks);
@@ -245,8 +219,8 @@ void launch_dedup_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_
 	if (rows_max) {
 		hipLaunchKernelGGL(dd_rows_kernel<true>, fixed_grid(rows_max, 256u, blocks), dim3(256), 0, st, src, n, with_crc ? 1u : 0u, t.ufirst, t.key, status);
 	}
-	hipLaunchKernelGGL(dd_insert_kernel, fixed_grid(n_max, 256u, blocks), dim3(256), 0, st, n, t.slots, t.key, status, t.tkey, t.tmin, t.slot_of);
-	hipLaunchKernelGGL(dd_cand_kernel, fixed_grid(n_max, 256u, blocks), dim3(256), 0, st, src, n, status, t.tmin, t.slot_of, t.cand, t.flag);
+	hipLaunchKernelGGL(dd_insert_kernel, fixed_grid(n_max, 256u, blocks), dim3(256), 0, st, n, t.kt, t.key, status, t.slot_of);
+	hipLaunchKernelGGL(dd_cand_kernel, fixed_grid(n_max, 256u, blocks), dim3(256), 0, st, src, n, status, t.kt.min, t.slot_of, t.cand, t.flag);
 }
 
 void launch_dedup_confirm(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, bool with_crc, const DedupTab& t, uint32_t blocks)

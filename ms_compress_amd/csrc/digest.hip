@@ -139,27 +139,6 @@ __global__ __launch_bounds__(DG_ROOT_THREADS) void dg_root_kernel(DigestTab d, u
 	out[4u * (u64)u] = h[0]; out[4u * (u64)u + 1u] = h[1]; out[4u * (u64)u + 2u] = h[2]; out[4u * (u64)u + 3u] = h[3];
 }
 
-// check, one wave per resource behind the root pass -- bk_kfold_kernel with four words for one
-__global__ __launch_bounds__(256) void dg_kfold_kernel(uint32_t n_res, const u64* __restrict__ unit_first, const u64* __restrict__ which, const uint32_t* __restrict__ udig,
-                                                      const uint32_t* __restrict__ block_digest, const int32_t* __restrict__ rstat, u64* __restrict__ d_out_len,
-                                                      int32_t* __restrict__ d_status)
-{
-	const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-	if (r >= n_res) { return; }
-	const int32_t st = rstat[r];
-	if (st == BK_LEAVE) { return; }
-	bool bad = false;
-	if (st == 0) {
-		for (u64 u = unit_first[r] + lane; u < unit_first[r + 1u]; u += 64u) {
-			const uint32_t* a = udig + 4u * u;
-			const uint32_t* b = block_digest + 4u * which[u];
-			if (a[0] != b[0] || a[1] != b[1] || a[2] != b[2] || a[3] != b[3]) { bad = true; }
-		}
-	}
-	const bool any_bad = __ballot(bad) != 0;
-	if (lane == 0 && (st != 0 || any_bad)) { d_status[r] = st != 0 ? st : -3; d_out_len[r] = 0; }   // MSCOMP_DATA_ERROR
-}
-
 void launch_digest_leaves(hipStream_t st, const uint8_t* base, const DigestTab& d, uint32_t blocks)
 {
 	if (d.n_max == 0) { return; }
@@ -171,12 +150,6 @@ void launch_digest_roots(hipStream_t st, const DigestTab& d, uint32_t* out, uint
 	const uint32_t items = d.n_max > n_res || !rstat ? d.n_max : n_res;
 	if (items == 0) { return; }
 	hipLaunchKernelGGL(dg_root_kernel, dim3((items + DG_ROOT_THREADS - 1u) / DG_ROOT_THREADS), dim3(DG_ROOT_THREADS), 0, st, d, out, n_res, rstat, d_status);
-}
-
-void launch_digest_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_digest, const BlocksTab& t, const DigestTab& d, u64* d_out_len, int32_t* d_status)
-{
-	if (n_res == 0) { return; }
-	hipLaunchKernelGGL(dg_kfold_kernel, dim3((n_res + 3u) / 4u), dim3(256), 0, st, n_res, t.unit_first, t.ulen, d.out, block_digest, t.rstat, d_out_len, d_status);
 }
 
 } // namespace msc

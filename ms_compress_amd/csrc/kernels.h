@@ -283,7 +283,8 @@ void launch_blocks_crcgroups(hipStream_t st, uint32_t n_res, uint32_t nbmax, uin
 #define BK_LEAVE 1                                        // (t.rstat of a resource that was not MSCOMP_OK on entry to check: not a status)
 void launch_blocks_ktables(hipStream_t st, uint32_t n_res, uint32_t nbmax, uint32_t shift, u64 in_max, const u64* res_len, const u64* block_first,
                            const u64* range, const u64* d_out_off, const int32_t* d_status, const BlocksTab& t);
-void launch_blocks_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_crc, const BlocksTab& t, u64* d_out_len, int32_t* d_status);
+// (an entry is `words` words, 1 or 4: `read` holds the units' entries as they were computed -- t.ucrc, or a digester's d.out --, `given` the caller's column)
+void launch_blocks_kfold(hipStream_t st, uint32_t n_res, const uint32_t* read, const uint32_t* given, uint32_t words, const BlocksTab& t, u64* d_out_len, int32_t* d_status);
 // the last pass of a write, a resize and a splice: every row of the new table (nbt) with a non-zero addr[row] to dst + new_off[row], runs of rows
 // whose addr - new_off is constant as one copy; nothing at or behind dst + cap (`blocks` = compact_dev_blocks())
 void launch_blocks_move(hipStream_t st, uint32_t nbt, u64 cap, const u64* new_off, const u64* addr, uint8_t* dst, uint32_t blocks);
@@ -406,6 +407,17 @@ __device__ __forceinline__ void dd_edges(const uint8_t* __restrict__ p, u64 len,
 		w[2] = w[0]; w[3] = w[1];
 	}
 }
+// the key of a row, mixed into the caller's seed h: its stored length, its CRC word (bit 32 set) when checksums take part, and the edges
+// of its len stored bytes at p
+__device__ __forceinline__ u64 row_key(u64 h, u64 len, uint32_t with_crc, uint32_t crc, const uint8_t* __restrict__ p)
+{
+	u64 w[4];
+	dd_edges(p, len, w);
+	h = dd_mix(h ^ len);
+	if (with_crc) { h = dd_mix(h ^ ((u64)crc | (u64)1 << 32)); }
+	h = dd_mix(h ^ w[0]); h = dd_mix(h ^ w[1]); h = dd_mix(h ^ w[2]); h = dd_mix(h ^ w[3]);
+	return h;
+}
 // one block: rules 1-3 per pick (pick: 2 n_pick, source and resource), new_first (n_pick + 1), new_len and status (n_pick), then per NEW row
 // new_off (nbt + 1), new_crc (nbt, may be null) and addr (nbt, for launch_blocks_move), then rule 7
 void launch_splice_layout(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uint32_t n_pick, uint32_t nbt, uint32_t shift, u64 cap, const u64* pick,
@@ -431,25 +443,35 @@ void launch_splice_tilescan(hipStream_t st, uint32_t nbt, const SpliceExtTab& t)
 void launch_splice_rows(hipStream_t st, uint32_t n_res, uint32_t nbt, u64 cap, const u64* ext_first, const u64* new_first, u64* new_off, uint32_t* new_crc, int32_t* status,
                         const SpliceExtTab& t);
 
+// ---- the key table of dedup, match and sync ("The key table"; its device functions: rowpass.h kt_*) ----
+// Open addressing over 64-bit keys, with the smallest item of every key. The carve functions of blockobj.hip size it: more slots than
+// there can be keys, 2^32 at most -- a slot is named by a 32-bit word, and all-ones is no slot. (Only a syncer for more than 2^30 store
+// blocks has 2^32 slots. A key whose walk ends on the last of them has no slot, in claim and find alike: its blocks are not found.)
+#define KT_NONE 0xFFFFFFFFu                                // no slot (a walk that found none); in `min`: no item yet
+struct KeyTable {
+	u64* key;                                          // slots: the key a slot was claimed for (0 = empty)
+	uint32_t* min;                                     // slots: the smallest item that came with the slot's key
+	u64 slots;
+};
+// every slot empty (a fixed grid over the slots; `blocks` = crc_dev_blocks())
+void launch_dedup_clear(hipStream_t st, const KeyTable& kt, uint32_t blocks);
+
 // ---- block dedupers (dedup.hip; mscomp_amd_deduper_*) ----
 // The deduper's own tables, in one buffer (blockobj.hip dedup_tab is the only place that knows the layout). n = n_res_total, the bound of
-// the resources of all sources together; slots = 2 n + 64, the key table.
+// the resources of all sources together; the key table has 2 n + 64 slots, its items are resources.
 struct DedupTab {
 	u64* ufirst;                                       // n + 1: first row of every resource, in a numbering of the rows of the resources that passed rules 1 and 2
 	u64* key;                                          // n: the resource's 64-bit key
-	u64* tkey;                                         // slots: the key a slot was claimed for (0 = empty)
-	uint32_t* tmin;                                    // slots: the smallest resource with the slot's key
-	uint32_t *slot_of, *cand, *flag;                   // n each: the resource's slot; the smallest accepted resource with its key; 1 = not equal to that one
+	KeyTable kt;
+	uint32_t *slot_of, *cand, *flag;                   // n each: the resource's slot (KT_NONE: none); the smallest accepted resource with its key; 1 = not equal to that one
 	uint32_t* rlist;                                   // n: the refuted resources, ascending
-	u64 slots;
 };
 // The call in four stages, eight launches fixed by n_max and rows_max (the creation bounds; every grid is sized by them, none is launched
 // with an empty one); n = the resources of this call (<= n_max), status = d_status, which the stages read back.
 // judge: the key table cleared, rules 1 and 2 and the row numbering (one block), rule 3 (a fixed grid over the rows); `blocks` = crc_dev_blocks()
 void launch_dedup_judge(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, uint32_t shift, const DedupTab& t, int32_t* status, uint32_t blocks);
-// the two row-independent pieces of judge, as mscomp_amd_deduper_match launches them over tables of its own: a key table cleared; rule 3 over
-// the rows of the numbering ufirst (n + 1)
-void launch_dedup_clear(hipStream_t st, u64 slots, u64* tkey, uint32_t* tmin, uint32_t blocks);
+// the second of judge's row passes alone, as match and sync launch it over tables of their own: rule 3 over the rows of the numbering
+// ufirst (n + 1)
 void launch_dedup_rule3(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t rows_max, const u64* ufirst, int32_t* status, uint32_t blocks);
 // keys: the accepted resources' keys (the same grid over the rows), the keys into the table, the candidates (a thread per resource)
 void launch_dedup_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t n_max, uint32_t rows_max, bool with_crc, const DedupTab& t, int32_t* status, uint32_t blocks);
@@ -507,12 +529,10 @@ struct MatchTab {
 	u64* ufirst;                                       // n + 1: first row of every resource, in a numbering of the rows of the resources that passed rules 1, 2 and 4
 	u64* pfirst;                                       // 5 n: per resource of next the patch runs, fresh runs, found, shared and fresh blocks in front of its first row
 	u64* tsum;                                         // 8 row_tiles(mn): seven sums and one maximum per tile of next's rows, then their running values
-	u64* tkey;                                         // slots: the key a slot was claimed for (0 = empty)
+	KeyTable kt;                                       // 2 m + 64 slots; its items are rows
 	u64* nref;                                         // 1: the refuted rows of the execution
-	uint32_t* tmin;                                    // slots: the smallest row with the slot's key
-	uint32_t *slot_of, *flag, *rep, *rlist;            // m each: the row's slot (all-ones: none); 1 = not equal to its slot's smallest row; rep(u); the refuted rows, ascending
+	uint32_t *slot_of, *flag, *rep, *rlist;            // m each: the row's slot (KT_NONE: none); 1 = not equal to its slot's smallest row; rep(u); the refuted rows, ascending
 	uint32_t* flocal;                                  // mn: the fresh rows of its tile in front of a row of next
-	u64 slots;
 };
 // The call in six stages, ten launches fixed by the creation bounds (three when n_blocks_total is 0, seven when n_blocks_new is 0; the
 // caller leaves the others out, and launches launch_dedup_clear in front and launch_dedup_rule3 behind the seed).
@@ -594,9 +614,8 @@ void launch_tc_rows(hipStream_t st, const TcDims& d, u64 cap, const TranscodeTab
 // n_cand_max; tiles_max = in_total_max / SYNC_TILE + nu, pieces_max = in_total_max / SYNC_RUN + nu.
 struct SyncTab {
 	u64* ufirst;                                       // n + 1: first row of every store resource, in a numbering of the rows of the resources that passed rules 1 and 2
-	u64* tkey;                                         // slots: (CRC word ^ seed) | 1 << 32 a slot was claimed for (0 = empty)
-	uint32_t* tmin;                                    // slots: the smallest eligible row with the slot's word
-	uint32_t* bits;                                    // SYNC_BIT_WORDS: the bits at the word's low and at its high SYNC_BITS_LOG bits are set for every word in the table
+	KeyTable kt;                                       // a power of two of slots, 2^(32 - slot_shift); a key is (CRC word ^ seed) | 1 << 32, its items are the eligible rows
+	uint32_t* bits;                                   // SYNC_BIT_WORDS: the bits at the word's low and at its high SYNC_BITS_LOG bits are set for every word in the table
 	uint32_t* consts;                                  // SYNC_CONSTS, written once at creation (sync_host_consts)
 	u64 *cum, *uoff, *ulen;                            // nu + 1, nu, nu: running sum of the accepted lengths; offset and length of a unit (0, 0 when refused)
 	u64 *pfirst, *tfirst;                              // nu + 1 each: first piece boundary, first tile of every unit
@@ -606,8 +625,7 @@ struct SyncTab {
 	u64* cpos; uint32_t *cunit, *crow, *flag;          // nc each: a kept candidate's position, unit and row; 1 = its bytes differ from the decoded row's
 	u64 *req, *qlen; int32_t* qstat;                   // 3 nc, nc, nc: the reader core's requests, lengths and statuses
 	u64* count;                                        // 8: d_count of the last execution
-	u64 slots;                                         // a power of two, 2^(32 - slot_shift)
-	uint32_t slot_shift;
+	uint32_t slot_shift;                               // where a word's walk begins: (word * 0x9E3779B1) >> slot_shift
 	uint32_t tiles_max;
 };
 // the per-block-size constants of the scan, on the host (SYNC_CONSTS words): tb[b] = raw(b) x^(8B) -- the byte that leaves a window --,
@@ -657,9 +675,7 @@ void launch_digest_leaves(hipStream_t st, const uint8_t* base, const DigestTab& 
 // the root pass, a lane per unit over its 16 n bytes of leaf digests: out[4 u ..] (n_max entries; four zero words at and behind *count
 // and for an empty unit). rstat (n_res, may be null): copied to d_status by the same launch
 void launch_digest_roots(hipStream_t st, const DigestTab& d, uint32_t* out, uint32_t n_res, const int32_t* rstat, int32_t* d_status);
-// check, behind the root pass (bk_kfold_kernel with a digest for a CRC word): a failed table check, or a block whose digest in d.out is not
-// the one at block_digest[4 t.ulen[u] ..], into d_status and d_out_len
-void launch_digest_kfold(hipStream_t st, uint32_t n_res, const uint32_t* block_digest, const BlocksTab& t, const DigestTab& d, u64* d_out_len, int32_t* d_status);
+// (check, behind the root pass: launch_blocks_kfold over d.out and the caller's block_digest, four words per entry)
 
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status

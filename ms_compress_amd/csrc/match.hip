@@ -2,14 +2,13 @@
 // of the resources of a block container (next), whether an equal block lies in one of up to three store containers, earlier in next, or
 // nowhere, decided on the STORED form -- the stored form of a block depends only on its data, the format and the block size -- and answered
 // as two extent lists a splicer made for extents takes: the blocks seen for the first time (the delta), and stores + delta put together
-// again (the patch). The unit is the ROW: dedup's key table, candidates and confirm pass over the rows of all views instead of their
+// again (the patch). The unit is the ROW: the key table (rowpass.h kt_*), dedup's candidates and confirm pass over the rows of all views instead of their
 // resources, diff's tiled run passes over the rows of next. The views travel by value in the kernel arguments, as one SpliceSrc that a lane indexes
 // (kernels.h sp_view), the stores first and next behind them. DESIGN.md 4.18.
 #include "rowpass.h"
 
 namespace msc {
 
-#define MT_NONE   0xFFFFFFFFu                              // slot_of: the row is in no slot (a refused resource, or a table walk that found no room)
 #define MT_FOUND  0u                                       // class of a row of next: its representative is a row of a store ...
 #define MT_SHARED 1u                                       // ... an earlier row of next ...
 #define MT_FRESH  2u                                       // ... itself
@@ -50,36 +49,23 @@ __global__ __launch_bounds__(DV_THREADS) void mt_seed_kernel(SpliceSrc src, uint
 	});
 }
 
-// Keys, a fixed grid dealt over the rows: a row of an accepted resource mixes its key tuple -- data length, stored length, CRC word when
-// checksums take part, first and last min(16, s) stored bytes -- into 64 bits, claims a slot of the open-addressing table for the key (a
-// 64-bit compare-and-swap on an empty slot, linear probing past slots of other keys) and puts its number into the slot's minimum. A slot
-// holds one key, so two rows share a slot exactly when they share their key, and the minimum does not depend on the order of arrival. The
-// walk is bounded by the slot count: the table has more slots than there are rows, so it ends long before, and on a damaged state it ends
-// all the same -- the row then has no slot and is its own representative.
-__global__ __launch_bounds__(256) void mt_keys_kernel(SpliceSrc src, uint32_t n, uint32_t shift, uint32_t with_crc, u64 slots,
-                                                     const u64* __restrict__ ufirst, const int32_t* __restrict__ status, u64* tkey, uint32_t* tmin,
+// Keys, a fixed grid dealt over the rows: a row of an accepted resource mixes its key tuple -- data length, then row_key's: stored length,
+// CRC word when checksums take part, first and last min(16, s) stored bytes -- into 64 bits, claims the key's slot of the key table and
+// puts its number into the slot's minimum. A row of a refused resource has no slot, and neither has one whose walk found none (a damaged
+// table): it is its own representative.
+__global__ __launch_bounds__(256) void mt_keys_kernel(SpliceSrc src, uint32_t n, uint32_t shift, uint32_t with_crc, KeyTable kt,
+                                                     const u64* __restrict__ ufirst, const int32_t* __restrict__ status,
                                                      uint32_t* __restrict__ slot_of, uint32_t* __restrict__ flag)
 {
 	const u64 units = ufirst[n];
 	for (u64 u = (u64)blockIdx.x * 256u + threadIdx.x; u < units; u += (u64)gridDim.x * 256u) {
 		const uint32_t x = res_of_block(ufirst, n, u);
-		uint32_t slot = MT_NONE;
+		uint32_t slot = KT_NONE;
 		if (status[x] == 0) {
 			const MtRow a = mt_row_of(src, x, shift, with_crc, ufirst, u);
-			u64 w[4];
-			dd_edges(a.p, a.len, w);
-			u64 h = dd_mix(a.e ^ 0x9E3779B97F4A7C15ull);
-			h = dd_mix(h ^ a.len);
-			if (with_crc) { h = dd_mix(h ^ ((u64)a.crc | (u64)1 << 32)); }
-			h = dd_mix(h ^ w[0]); h = dd_mix(h ^ w[1]); h = dd_mix(h ^ w[2]); h = dd_mix(h ^ w[3]);
-			const u64 kk = h ? h : 1u;                                         // (0 is the empty slot)
-			u64 at = dd_mix(kk) % slots;
-			for (u64 probe = 0; probe < slots; ++probe) {
-				const u64 was = atomicCAS(reinterpret_cast<unsigned long long*>(&tkey[at]), 0ull, (unsigned long long)kk);
-				if (was == 0 || was == kk) { slot = (uint32_t)at; break; }
-				at = at + 1u == slots ? 0 : at + 1u;
-			}
-			if (slot != MT_NONE) { atomicMin(&tmin[slot], (uint32_t)u); }
+			const u64 h = row_key(dd_mix(a.e ^ 0x9E3779B97F4A7C15ull), a.len, with_crc, a.crc, a.p);
+			slot = kt_claim(kt, h, dd_mix(kt_key(h)) % kt.slots);
+			if (slot != KT_NONE) { atomicMin(&kt.min[slot], (uint32_t)u); }
 		}
 		slot_of[u] = slot; flag[u] = 0;
 	}
@@ -100,7 +86,7 @@ __global__ __launch_bounds__(CPD_THREADS) void mt_confirm_kernel(SpliceSrc src, 
 	u64 x_end = 0, c_lo = 0, c_end = 0;                                    // the rows below x_end that are not below ufirst[x] are x's; [c_lo, c_end) are cx's
 	confirm_slices(ufirst[n], ppu_shift, [&](u64 u, u64 at, u64 upto) {      // (units <= n_blocks_total < 2^31)
 		const uint32_t slot = slot_of[u];
-		const uint32_t c = slot == MT_NONE ? (uint32_t)u : tmin[slot];     // (no slot: a refused resource, no byte of it is read)
+		const uint32_t c = slot == KT_NONE ? (uint32_t)u : tmin[slot];     // (no slot: a refused resource, no byte of it is read)
 		const bool cand = c < u;                                           // (c > u: a damaged table; the row stands for itself)
 		if (at == 0 && tid == 0) { rep[u] = cand ? c : (uint32_t)u; }
 		if (!cand || flag[u] != 0) { return; }
@@ -277,15 +263,15 @@ void launch_match_seed(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_
 
 void launch_match_keys(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t nbt, uint32_t shift, bool with_crc, const MatchTab& t, const int32_t* status, uint32_t blocks)
 {
-	hipLaunchKernelGGL(mt_keys_kernel, fixed_grid(nbt, 256u, blocks), dim3(256), 0, st, src, n, shift, with_crc ? 1u : 0u, t.slots, t.ufirst, status,
-	                   t.tkey, t.tmin, t.slot_of, t.flag);
+	hipLaunchKernelGGL(mt_keys_kernel, fixed_grid(nbt, 256u, blocks), dim3(256), 0, st, src, n, shift, with_crc ? 1u : 0u, t.kt, t.ufirst, status,
+	                   t.slot_of, t.flag);
 }
 
 void launch_match_confirm(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t nbt, uint32_t shift, bool with_crc, const MatchTab& t, uint32_t blocks)
 {
 	const uint32_t ppu_shift = shift > DD_PIECE_SHIFT ? shift - DD_PIECE_SHIFT : 0u;
 	hipLaunchKernelGGL(mt_confirm_kernel, fixed_grid((u64)nbt << ppu_shift, DD_SLICE_MIN, blocks), dim3(CPD_THREADS), 0, st, src, n, shift, ppu_shift,
-	                   with_crc ? 1u : 0u, t.ufirst, t.slot_of, t.tmin, t.flag, t.rep);
+	                   with_crc ? 1u : 0u, t.ufirst, t.slot_of, t.kt.min, t.flag, t.rep);
 }
 
 void launch_match_settle(hipStream_t st, const SpliceSrc& src, uint32_t n, uint32_t shift, bool with_crc, const MatchTab& t)

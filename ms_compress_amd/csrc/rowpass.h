@@ -1,11 +1,48 @@
-// rowpass.h -- what the passes of the four deduper calls share (dedup.hip, diff.hip, match.hip, repair.hip): the table rules of a resource,
-// the dense row numbering of the seed, the slices of the confirm passes, the settle of the refuted list, and the three run passes' frame
-// -- a tile pass, the tile scan, a runs pass -- with the counts behind them. Device code only, inlined into each caller's kernels; a file
-// keeps what is its own: what a row IS in that call, its class, and what a finished run writes.
+// rowpass.h -- what the passes of the four deduper calls and of sync share (dedup.hip, diff.hip, match.hip, repair.hip, sync.hip): the
+// table rules of a resource, the dense row numbering of the seed, the key table's clear, claim and find, the slices of the confirm passes,
+// the settle of the refuted list, and the three run passes' frame -- a tile pass, the tile scan, a runs pass -- with the counts behind
+// them. Device code only, inlined into each caller's kernels; a file keeps what is its own: what a row IS in that call, its class, and
+// what a finished run writes.
 #pragma once
 #include "kernels.h"
 
 namespace msc {
+
+// ---- the key table (kernels.h KeyTable; DESIGN.md 4.13, "The key table") ----
+// The walk for a key begins at the slot `at` its caller's start-slot function names (< t.slots) and goes on slot by slot, around the
+// table's end; it takes t.slots steps at most, so it ends on any table, whatever a damaged one holds. A caller does its own atomicMin on
+// t.min[slot], and what else follows a claim.
+__device__ __forceinline__ u64 kt_key(u64 key) { return key ? key : 1u; }   // (0 is the empty slot: key 0 is kept as key 1)
+// the body of a fixed grid of 256 threads a block over the slots: every slot empty, no item yet
+__device__ __forceinline__ void kt_clear(const KeyTable& t)
+{
+	for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < t.slots; i += (u64)gridDim.x * 256u) { t.key[i] = 0; t.min[i] = KT_NONE; }
+}
+// The slot of `key`, claimed where no walk came with the key before: a 64-bit compare-and-swap on an empty slot, past the slots of other
+// keys. A slot holds one key, so two items share a slot exactly when they share their key. KT_NONE: no slot in t.slots steps.
+__device__ __forceinline__ uint32_t kt_claim(const KeyTable& t, u64 key, u64 at)
+{
+	const u64 kk = kt_key(key);
+	for (u64 probe = 0; probe < t.slots; ++probe) {
+		const u64 was = atomicCAS(reinterpret_cast<unsigned long long*>(&t.key[at]), 0ull, (unsigned long long)kk);
+		if (was == 0 || was == kk) { return (uint32_t)at; }
+		at = at + 1u == t.slots ? 0 : at + 1u;
+	}
+	return KT_NONE;
+}
+// The same walk without a write, behind the claims: the slot that holds `key`, KT_NONE when the walk meets an empty slot first -- where a
+// claim of the key would have ended -- or finds none.
+__device__ __forceinline__ uint32_t kt_find(const KeyTable& t, u64 key, u64 at)
+{
+	const u64 kk = kt_key(key);
+	u64 k = 0;
+	for (u64 probe = 0; probe < t.slots; ++probe) {
+		k = t.key[at];
+		if (k == kk || k == 0) { break; }
+		at = at + 1u == t.slots ? 0 : at + 1u;
+	}
+	return k == kk ? (uint32_t)at : KT_NONE;                             // (a walk that ran out stands behind a slot of another key)
+}
 
 // Rules 1 and 2 for resource r of one view: 0, or the status that refuses it; f0 = its first row, n = its rows (0 when refused), L = its
 // length (0 when rule 1 refuses it)

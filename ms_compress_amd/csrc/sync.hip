@@ -5,7 +5,7 @@
 // and W rolls: W(p + 1) = W(p) x^8 ^ raw(M[p + B]) ^ raw(M[p]) x^(8B) -- two table lookups per position, t0[(W ^ hi) & 255] and tb[lo].
 // The boundary passes leave raw(M[: q]) at every 64th byte, so every lane of the scan starts a run of 64 positions from two words; the
 // scan walks the positions twice (a tile pass that counts, a runs pass that writes), with a tile scan between them, and stores nothing
-// per position. Candidates are confirmed against the rows the reader core decodes (reader.hip, unchanged) -- or, by a digest syncer,
+// per position. The store's words lie in the key table dedup and match use (rowpass.h kt_*). Candidates are confirmed against the rows the reader core decodes (reader.hip, unchanged) -- or, by a digest syncer,
 // by the BLAKE2s digest of their window against the store's digest column (digest.hip), without a stored byte. DESIGN.md 4.20, 4.21.
 #include "rowpass.h"
 #include "crcmath.h"
@@ -13,7 +13,7 @@
 namespace msc {
 
 #define SY_THREADS 256u                                   // four waves, a tile each
-#define SY_NONE    0xFFFFFFFFu
+#define SY_NONE    0xFFFFFFFFu                            // a lane of the scan: no position of it starts a segment
 #define SY_X       0xFFFFFFFEu                            // the state in front of a lane's first position: no state (a state is 0, or a row + 1)
 #define SY_BMASK   ((1u << SYNC_BITS_LOG) - 1u)            // a word's two bits of the bitmap: at its low and at its high SYNC_BITS_LOG bits
 #define SY_BHIGH   (32u - SYNC_BITS_LOG)
@@ -27,27 +27,9 @@ namespace msc {
 #define SW_BASE  5u                                       // thinned candidates in front of the tile
 #define SW_ENTER 6u                                       // where the segment of the tile's first position starts, as a tile coordinate + 1
 
-__device__ __forceinline__ uint32_t sy_wave_sum(uint32_t v)
-{
-	#pragma unroll
-	for (uint32_t d = 32; d; d >>= 1) { v += __shfl_xor(v, d, 64); }
-	return v;
-}
-__device__ __forceinline__ uint32_t sy_wave_min(uint32_t v)
-{
-	#pragma unroll
-	for (uint32_t d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
-	return v;
-}
-__device__ __forceinline__ u64 sy_wave_max(u64 v)
-{
-	#pragma unroll
-	for (uint32_t d = 32; d; d >>= 1) { const u64 o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
-	return v;
-}
-
 // ---- the store: key table and bitmap ----
-// where the walk for word w begins: the table has a power of two of slots, 2^(32 - slot_shift)
+// the key of word w (never 0), and where its walk begins: the table has a power of two of slots, 2^(32 - slot_shift)
+__device__ __forceinline__ u64 sy_key(uint32_t w) { return (u64)w | (u64)1 << 32; }
 __device__ __forceinline__ u64 sy_slot(uint32_t w, uint32_t slot_shift) { return slot_shift >= 32u ? 0u : (u64)((w * 0x9E3779B1u) >> slot_shift); }
 // whether the bitmap may hold word w: two bits, at the word's low and at its high bits (the second is read only behind a set first)
 __device__ __forceinline__ bool sy_maybe(const uint32_t* s_bits, uint32_t w)
@@ -57,7 +39,7 @@ __device__ __forceinline__ bool sy_maybe(const uint32_t* s_bits, uint32_t w)
 }
 __global__ __launch_bounds__(256) void sy_clear_kernel(SyncTab t)
 {
-	for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < t.slots; i += (u64)gridDim.x * 256u) { t.tkey[i] = 0; t.tmin[i] = SY_NONE; }
+	kt_clear(t.kt);
 	for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < SYNC_BIT_WORDS; i += (u64)gridDim.x * 256u) { t.bits[i] = 0; }
 }
 
@@ -71,9 +53,9 @@ __global__ __launch_bounds__(DV_THREADS) void sy_seed_kernel(SpliceView v, uint3
 	});
 }
 
-// Keys, a fixed grid dealt over the rows (mt_keys_kernel's scheme): an eligible row -- B bytes of data -- of an accepted resource claims a
-// slot for its word (a 64-bit compare-and-swap on an empty slot, linear probing past slots of other words), puts its number into the
-// slot's minimum and sets the word's two bits. The word is the CRC word with the seed of a B-byte message taken off: what the scan rolls.
+// Keys, a fixed grid dealt over the rows (mt_keys_kernel's scheme): an eligible row -- B bytes of data -- of an accepted resource claims
+// its word's slot of the key table, puts its number into the slot's minimum and sets the word's two bits. The word is the CRC word with
+// the seed of a B-byte message taken off: what the scan rolls.
 __global__ __launch_bounds__(256) void sy_keys_kernel(SpliceView v, uint32_t n, uint32_t shift, SyncTab t, const int32_t* __restrict__ status)
 {
 	const u64 units = t.ufirst[n];
@@ -84,32 +66,21 @@ __global__ __launch_bounds__(256) void sy_keys_kernel(SpliceView v, uint32_t n, 
 		const u64 k = u - t.ufirst[x];
 		if (((k + 1u) << shift) > v.res_len[x]) { continue; }                // the short last block never takes part
 		const uint32_t w = v.crc[v.first[x] + k] ^ seed;                     // (first[x] + k < first[x + 1] <= v.nbt: rule 1)
-		const u64 kk = (u64)w | (u64)1 << 32;
-		u64 at = sy_slot(w, t.slot_shift);
-		for (u64 probe = 0; probe < t.slots; ++probe) {
-			const u64 was = atomicCAS(reinterpret_cast<unsigned long long*>(&t.tkey[at]), 0ull, (unsigned long long)kk);
-			if (was == 0 || was == kk) {
-				atomicMin(&t.tmin[at], (uint32_t)u);
-				atomicOr(&t.bits[(w & SY_BMASK) >> 5], 1u << (w & 31u)); atomicOr(&t.bits[(w >> SY_BHIGH) >> 5], 1u << ((w >> SY_BHIGH) & 31u));
-				break;
-			}
-			at = (at + 1u) & (t.slots - 1u);
-		}
+		const uint32_t slot = kt_claim(t.kt, sy_key(w), sy_slot(w, t.slot_shift));
+		if (slot == KT_NONE) { continue; }
+		atomicMin(&t.kt.min[slot], (uint32_t)u);
+		atomicOr(&t.bits[(w & SY_BMASK) >> 5], 1u << (w & 31u)); atomicOr(&t.bits[(w >> SY_BHIGH) >> 5], 1u << ((w >> SY_BHIGH) & 31u));
 	}
 }
 
-// the row + 1 the table holds for word w, 0 when it holds none (the rare path of the scan: only behind a set bit)
-__device__ __noinline__ uint32_t sy_probe(const u64* __restrict__ tkey, const uint32_t* __restrict__ tmin, u64 slots, uint32_t slot_shift, uint32_t w)
+// the row + 1 the table holds for word w, 0 when it holds none (the rare path of the scan: only behind a set bit; a function of its own,
+// called: inlined, its walk would take its registers from the sweep's)
+__device__ __noinline__ uint32_t sy_probe(KeyTable kt, uint32_t slot_shift, uint32_t w)
 {
-	const u64 kk = (u64)w | (u64)1 << 32;
-	u64 at = sy_slot(w, slot_shift);
-	for (u64 probe = 0; probe < slots; ++probe) {
-		const u64 k = tkey[at];
-		if (k == 0) { return 0; }
-		if (k == kk) { const uint32_t r = tmin[at]; return r >= 0x7FFFFFF0u ? 0u : r + 1u; }
-		at = (at + 1u) & (slots - 1u);
-	}
-	return 0;
+	const uint32_t slot = kt_find(kt, sy_key(w), sy_slot(w, slot_shift));
+	if (slot == KT_NONE) { return 0; }
+	const uint32_t r = kt.min[slot];
+	return r >= 0x7FFFFFF0u ? 0u : r + 1u;
 }
 
 // ---- the units ----
@@ -271,7 +242,7 @@ __device__ __forceinline__ void sy_sweep(const uint32_t* s_t0, const uint32_t* s
 			const bool live = i < nvalid;
 			uint32_t st = 0;
 			if (live && sy_maybe(s_bits, W)) {
-				st = sy_probe(t.tkey, t.tmin, t.slots, t.slot_shift, W);
+				st = sy_probe(t.kt, t.slot_shift, W);
 				if (st) { ++z.nraw; }
 			}
 			if (live && st != prev) {
@@ -335,10 +306,11 @@ __global__ __launch_bounds__(SY_THREADS) void sy_scan_kernel(uint32_t n, uint32_
 		const bool sf = lane > 0 && valid && z.f != prev_l;                   // the lane's first position starts a segment (lane 0: the tile scan's to say)
 		u64 m = z.last != SY_NONE ? G + z.last + 1u : sf ? G + 1u : 0u;
 		if (!WRITE) {
-			const uint32_t raw = sy_wave_sum(z.nraw), loc = sy_wave_sum(z.nint + (sf && z.f ? 1u : 0u)), nvt = sy_wave_sum(nvalid);
+			const auto sum = [](uint32_t a, uint32_t b) { return a + b; };
+			const uint32_t raw = wave_all(z.nraw, sum), loc = wave_all(z.nint + (sf && z.f ? 1u : 0u), sum), nvt = wave_all(nvalid, sum);
 			const uint32_t nvl = (uint32_t)__popcll(__ballot(valid));
-			const u64 mx = sy_wave_max(m);
-			uint32_t ext = sy_wave_min(!valid ? SY_NONE : sf ? a_off : z.last != SY_NONE ? a_off + z.lead : SY_NONE);
+			const u64 mx = wave_all(m, [](u64 a, u64 b) { return b > a ? b : a; });
+			uint32_t ext = wave_all(!valid ? SY_NONE : sf ? a_off : z.last != SY_NONE ? a_off + z.lead : SY_NONE, [](uint32_t a, uint32_t b) { return b < a ? b : a; });
 			ext = ext < nvt ? ext : nvt;
 			const uint32_t F = __shfl(z.f, 0, 64), Lst = __shfl(z.l, nvl ? (int)nvl - 1 : 0, 64);
 			if (lane == 0) {
@@ -587,7 +559,7 @@ void sync_host_consts(uint32_t shift, uint32_t* out)
 
 void launch_sync_clear(hipStream_t st, const SyncTab& t, uint32_t blocks)
 {
-	hipLaunchKernelGGL(sy_clear_kernel, fixed_grid(t.slots > SYNC_BIT_WORDS ? t.slots : SYNC_BIT_WORDS, 256u, blocks), dim3(256), 0, st, t);
+	hipLaunchKernelGGL(sy_clear_kernel, fixed_grid(t.kt.slots > SYNC_BIT_WORDS ? t.kt.slots : SYNC_BIT_WORDS, 256u, blocks), dim3(256), 0, st, t);
 }
 
 void launch_sync_seed(hipStream_t st, const SpliceView& v, uint32_t n, uint32_t shift, const SyncTab& t, int32_t* status)

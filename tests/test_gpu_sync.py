@@ -3,6 +3,8 @@ that are longer than the call may write --, then the header's consequence on the
 the call's own d_req / d_req_off, and the batch compared byte for byte. The stores are made by the GPU's blocks_compress / blocks_crc;
 the helpers are those of tests/blocks_rig.py, the cases those of sync_model.cases (which tests/test_sync_model.py holds to the
 consequence without a device)."""
+import zlib
+
 import numpy as np
 import pytest
 
@@ -183,6 +185,25 @@ def test_bounds_and_duplicates(gpu_ctx, oracle, made):
     assert mo["status"] == [0, 0, M.ARG] and mo["hits"] == [[(1, 0, 1)], [(0, 0, 1)], []] and mo["literals"][2] == []
     rig.rebuild(store, mo)
     rig.close()
+
+
+def test_probe_chain_crosses_the_table_end(gpu_ctx, oracle, made):
+    """three store blocks whose words all start their walk at the last slot of a 128-slot key table: the claims end in slots 127, 0 and 1,
+    and the scan's read-only walk has to follow them around the end, whatever order the claims came in"""
+    B, SLOTS, SHIFT = 4096, 128, 25                                             # (n_blocks_table <= 32: 2 * 32 + 64 slots)
+    word = lambda b: zlib.crc32(b) ^ zlib.crc32(bytes(B))
+    start = lambda b: ((word(b) * 0x9E3779B1) & 0xFFFFFFFF) >> SHIFT
+    rs, blocks = np.random.RandomState(20261020), []
+    while len(blocks) < 3:
+        b = rs.bytes(B)
+        if start(b) == SLOTS - 1 and word(b) not in [word(x) for x in blocks]:
+            blocks.append(b)
+    store = made(("wrap",), lambda: Container.make(gpu_ctx, FMTS["xpress"], B, [b"".join(blocks)]))
+    assert store.n == 1 and 3 <= store.nbt <= 32 and [start(b) for b in blocks] == [SLOTS - 1] * 3 and len({word(b) for b in blocks}) == 3
+    assert [int(c) for c in store.crc[:3]] == [zlib.crc32(b) for b in blocks]
+    unit = b"\x07" + blocks[2] + b"fill2" + blocks[1] + b"fill1" + blocks[0]
+    mo, _ = run_case(oracle, made, store, "wrap", [unit])
+    assert mo["hits"] == [[(1, 0, 2), (1 + B + 5, 0, 1), (1 + 2 * (B + 5), 0, 0)]] and mo["count"][4] == 3
 
 
 def test_state_and_graphs(gpu_ctx, oracle, made):

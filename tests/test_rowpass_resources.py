@@ -1,7 +1,7 @@
-"""CPU: the resources of the deduper calls' kernels (dedup.hip, diff.hip, match.hip, repair.hip) as the compiler reports them for gfx950,
-compiled with the Makefile's flags. What the four files share lives in rowpass.h as function templates over functors, inlined into every
-kernel; where such a template goes wrong it does so silently -- an array passed by reference that ends in scratch memory, a struct that
-is spilled -- and this is where it shows: no kernel may use scratch memory, but for the 40 bytes per lane that mt_keys_kernel,
+"""CPU: the resources of the deduper calls' kernels (dedup.hip, diff.hip, match.hip, repair.hip), of the syncer's (sync.hip), which walks
+the same key table, and of the digest passes (digest.hip) as the compiler reports them for gfx950, compiled with the Makefile's flags.
+What the files share lives in rowpass.h as function templates over functors, inlined into every kernel; where such a template goes
+wrong it does so silently -- an array passed by reference that ends in scratch memory, a struct that is spilled -- and this is where it shows: no kernel may use scratch memory, but for the 40 bytes per lane that mt_keys_kernel,
 mt_confirm_kernel and mt_settle_kernel were written with, and no kernel may spill registers. Registers and occupancy are
 not pinned. Each file is compiled once.
 
@@ -19,7 +19,7 @@ import pytest
 
 from test_lznt1_resources import CSRC, HIPCC, _makefile_flags
 
-FILES = ("dedup", "diff", "match", "repair")
+FILES = ("dedup", "diff", "match", "repair", "sync", "digest")
 EACH = pytest.mark.parametrize("name", FILES)
 SCRATCH_KNOWN = ("mt_keys_kernel", "mt_confirm_kernel", "mt_settle_kernel")      # 40 bytes per lane each, at most
 # the kernels a file must be found to hold, by substring: a renamed kernel must not slip out of the checks
@@ -27,7 +27,10 @@ HOLDS = {"dedup": ("dd_seed_kernel", "dd_rows_kernel", "dd_insert_kernel", "dd_c
          "diff": ("df_seed_kernel", "df_verdict_kernel", "df_confirm_kernel", "df_tile_kernel", "rows_tilescan_kernel", "df_runs_kernel", "df_counts_kernel"),
          "match": ("mt_seed_kernel", "mt_keys_kernel", "mt_confirm_kernel", "mt_settle_kernel", "mt_tile_kernel", "rows_tilescan_kernel", "mt_runs_kernel",
                    "mt_counts_kernel"),
-         "repair": ("rp_seed_kernel", "rp_choice_kernel", "rp_tile_kernel", "rp_runs_kernel", "rp_counts_kernel")}
+         "repair": ("rp_seed_kernel", "rp_choice_kernel", "rp_tile_kernel", "rp_runs_kernel", "rp_counts_kernel"),
+         "sync": ("sy_clear_kernel", "sy_seed_kernel", "sy_keys_kernel", "sy_units_kernel", "sy_piece_kernel", "sy_pre_kernel", "sy_abs_kernel", "sy_scan_kernel",
+                  "sy_tilescan_kernel", "sy_req_kernel", "sy_confirm_kernel", "sy_dunits_kernel", "sy_dcompare_kernel", "sy_select_kernel"),
+         "digest": ("dg_leaf_kernel", "dg_root_kernel")}
 
 
 @functools.lru_cache(maxsize=None)
