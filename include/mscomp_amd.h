@@ -1444,6 +1444,115 @@ MSCompStatus mscomp_amd_syncer_sync_digest(mscomp_amd_syncer* sy, const mscomp_a
                                            uint64_t* d_hit_first, uint64_t* d_req, uint64_t* d_req_off, uint64_t* d_lit_first, uint64_t* d_lit,
                                            uint64_t* d_count, int32_t* d_res_status, int32_t* d_status);
 
+/* Parity: Reed-Solomon parity rows beside a container, and lost rows back from them without a mirror. Salvage says which rows are bad and
+ * repair mends them from a second full copy; a parity object closes the gap for the user who keeps ONE container: m parity rows for every
+ * k stored rows -- m / k extra space instead of 100 % --, from which up to m lost rows per group are rebuilt. Like splice and dedup it
+ * works on the STORED bytes: no format, no decoder. The code is RAID-6's, extended to three parities: GF(2^8) with polynomial 0x11D and
+ * alpha = 2, P_p[x] = XOR_i alpha^(p i) D_i[x] for parity p < m over the members i < k of a group, D_i[x] = stored byte x of member i and 0
+ * at and behind its stored length. The matrix alpha^(p i) is a Vandermonde one in distinct non-zero points, and for m <= 3 every choice of
+ * e <= m missing members and ANY e of the parities is solvable (squaring is injective in characteristic 2; cubing is not, hence the cap).
+ * Rebuild does not write a mended container: it writes a SPARSE MIRROR -- a view of the primary's shape in which every row it did not
+ * rebuild has stored length 0 -- and the verdicts of that view, which mscomp_amd_deduper_repair and mscomp_amd_splicer_splice_extents take
+ * as they take any mirror.
+ *   Creation:     block_size as everywhere; n_blocks_table = the rows of the tables of every view the object will see; k = 1 ..
+ *                 MSCOMP_AMD_PARITY_K_MAX members per group, m = 1 .. MSCOMP_AMD_PARITY_M_MAX parity rows per group; flags must be 0.
+ *                 MSCOMP_ARG_ERROR, before the context is used and with *pr cleared, for a null ctx or pr, a block_size that is not a
+ *                 power of two from 4096 to 524288, k of 0 or above 255, m of 0 or above 3, non-zero flags, or n_blocks_table above
+ *                 0x7FFFFFF0; MSCOMP_MEM_ERROR when m G_max exceeds 0x7FFFFFF0 or the scratch cannot be reserved. G_max =
+ *                 ceil(n_blocks_table / k). mscomp_amd_parity_bound: out[0] = m G_max parity rows, out[1] = m G_max block_size parity
+ *                 bytes, the most a build writes; 0, or -1 for a null argument.
+ *   Scratch:      reserved at creation, once, and never grown: 28 bytes per parity row of m G_max (its length, the bytes and the running
+ *                 sum the CRC unit kernels read, its CRC-32), 12 per row of n_blocks_table (rebuild: the length it rebuilds, a flag),
+ *                 24 per group of G_max (rebuild: the list of damaged groups with their inverse matrices), + 72. No inner plan: the
+ *                 parity rows are units of the CRC kernels of mscomp_amd_blocks_crc, launched directly. The scratch hooks do not list it.
+ *   Sources:      src: a view as a splicer takes one, only read; d_block_crc is not read. build writes the parity SET: d_par (16-byte
+ *                 aligned, par_cap bytes), d_par_off (m G_max + 1), d_par_crc (m G_max), d_row_len (n_blocks_table), d_par_head (4).
+ *                 rebuild reads the set and d_verdict (n_blocks_table entries, as mscomp_amd_blocks_salvage wrote them for src).
+ *   Notation:     off = src.d_block_off, B = block_size, nb = src.d_block_first[src.n_res] (a device value), G = ceil(nb / k). GROUPS ARE
+ *                 INTERLEAVED: row j is member i = j / G of group g = j % G, so a burst that destroys up to G consecutive rows costs
+ *                 every group one member. Parity row q = g m + p. plen_g = the largest d_row_len of group g, rounded up to 16.
+ *   Rules:        build --
+ *                   0. nb > n_blocks_table, or src.n_blocks_table != n_blocks_table: d_status = MSCOMP_ARG_ERROR, d_par_head all zero,
+ *                      every d_par_off 0, and nothing else is written.
+ *                   1. d_row_len[j] = off[j + 1] - off[j] when j < nb, off[j] <= off[j + 1] <= packed_len and the length is at most B;
+ *                      0 otherwise (such a row is never read) and at and behind nb.
+ *                   2. Parity row q has plen_g bytes; d_par_off[0 .. m G] is the running sum, the entries above it, up to m G_max,
+ *                      repeat the total. Every offset is a multiple of 16.
+ *                   3. The bytes are the code's; pad bytes are the XOR of zeros, 0. No byte of d_packed outside a row's [off[j], off[j]
+ *                      + d_row_len[j]) is read: tails are masked.
+ *                   4. A parity row that would end beyond par_cap is not written at all, nothing at or behind par_cap ever is, and
+ *                      d_status = MSCOMP_BUF_ERROR; the tables hold the full layout (the rule of mscomp_amd_compact_dev).
+ *                   5. d_par_crc[q] = the CRC-32 (zlib's) of the plen_g bytes of row q; 0 at and behind m G and for a row rule 4 did
+ *                      not write.
+ *                   6. d_par_head = {nb, G, k, m}; d_status = MSCOMP_OK when rules 0 and 4 did not speak.
+ *                 rebuild --
+ *                   0. Build's rule 0 holds, with MSCOMP_ARG_ERROR; a d_par_head other than {nb, ceil(nb / k), k, m} -- parity of
+ *                      another container or of another shape -- answers MSCOMP_DATA_ERROR. In both cases d_fix_block_off is all 0,
+ *                      d_fix_verdict all MSCOMP_AMD_BLOCK_SKIPPED and d_count all 0.
+ *                   1. Row j < nb is PRESENT when d_verdict[j] == MSCOMP_AMD_BLOCK_GOOD, off[j] <= off[j + 1] <= packed_len and
+ *                      off[j + 1] - off[j] == d_row_len[j]; every other row j < nb is MISSING.
+ *                   2. Parity row q is USABLE when d_par_off[q] <= d_par_off[q + 1] <= par_len, d_par_off[q] is a multiple of 16, its
+ *                      length is plen_g as recomputed from d_row_len, and its CRC-32 equals d_par_crc[q]. An unusable row is never used.
+ *                   3. Group g has e missing members and u usable parity rows. e = 0: nothing to do. 0 < e <= u: every missing member
+ *                      is rebuilt with the e lowest-numbered usable parity rows -- the syndromes, the Horner pass over the present
+ *                      members XOR the parity rows, times the inverse of the e x e matrix alpha^(p_a i_b). e > u: the group is
+ *                      UNRECOVERABLE and none of its rows is rebuilt.
+ *                   4. d_fix_block_off[0 .. nb] is the running sum of d_row_len[j] over the rebuilt rows j and of 0 over all others;
+ *                      the entries above nb repeat the total. d_fix_packed holds the rebuilt rows' d_row_len[j] bytes in row order.
+ *                   5. A rebuilt row that would end beyond fix_cap is not written: its verdict is SKIPPED and d_status is
+ *                      MSCOMP_BUF_ERROR. (It still has its place in the tables and is counted as rebuilt.)
+ *                   6. All n_blocks_table entries of d_fix_verdict are written: MSCOMP_AMD_BLOCK_GOOD for a row rebuilt and written,
+ *                      MSCOMP_AMD_BLOCK_SKIPPED for every other row.
+ *                   7. d_count[0..5] = rows missing, rows rebuilt, groups with a missing row, groups unrecoverable, parity rows
+ *                      unusable (of the m G there are), stored bytes rebuilt. They are sums: the same from run to run.
+ *                   8. d_status is the first that applies of rule 0, MSCOMP_BUF_ERROR (rule 5), MSCOMP_DATA_ERROR (some group
+ *                      unrecoverable), MSCOMP_OK.
+ *   Consequence:  the view {d_fix_packed, d_fix_block_off[nb], src.d_block_first, d_fix_block_off, src.d_res_len, src.d_block_crc} with
+ *                 d_fix_verdict is a mirror as mscomp_amd_deduper_repair takes one, and parity composes with real mirrors: it is one
+ *                 more source. Assume the container was written by mscomp_amd_blocks_compress + _crc, parity was built from it, and it
+ *                 was then damaged in stored bytes or offset-table entries; assume the verdicts are salvage's with checksums. If no
+ *                 group is unrecoverable, repair over {primary, fix view} followed by mscomp_amd_splicer_splice_extents writes BYTE FOR
+ *                 BYTE the undamaged container: packed bytes, tables and checksums. Salvaging the fix view with d_only = the primary's
+ *                 verdicts holds every rebuilt row to its CRC-32; a row that was not rebuilt has stored length 0 there and comes out
+ *                 MSCOMP_AMD_BLOCK_TABLE, hence lost.
+ *   Checksums:    d_par_crc guards the parity rows, by the CRC unit kernels over (d_par, d_par_off, plen) as a unit table; the
+ *                 container's d_block_crc takes part only through the verdicts. Without d_block_crc salvage cannot see a flipped raw
+ *                 byte, and a present row that is silently wrong makes every row rebuilt from its group wrong: parity is as good as
+ *                 the verdicts.
+ *   Execution:    as every other object's: asynchronous on the ctx stream, kernels only (no memset or copy node), no allocation,
+ *                 nothing read back, a launch sequence fixed by the creation bounds; legal inside a caller's capture from the first
+ *                 execution, a graph of its own from the second outside one, captured again when an argument or a view field changes.
+ *                 build, nine launches: the row lengths, the groups' maxima, their running sum (one workgroup, in tiles), the CRC
+ *                 units, the parity pass -- a fixed grid dealt over (group, column tile of 4096 bytes) items, a lane owning 16 bytes
+ *                 of the column, 16-byte loads at any alignment with several in flight, m aligned 16-byte stores --, the three CRC
+ *                 launches, the header. rebuild, nine: the groups' maxima, the parity rows' table check, the three CRC launches, the
+ *                 damage pass (a lane per group: presence, counts, the damaged-group list and its inverse matrices), the fix table's
+ *                 running sum, the solve pass over the listed groups only, the verdicts and counts. Healthy groups cost nothing but
+ *                 their share of the fixed launches. MSCOMP_ARG_ERROR for a null object, a null view, a view pack refuses, a d_par
+ *                 that is not 16-byte aligned, or any null array whose size by the creation bounds is above 0 (d_par_head, d_count
+ *                 and d_status always). With n_blocks_table = 0 both calls return MSCOMP_OK and write only the header, the counts
+ *                 and the status, in one and two launches.
+ *   Left out:     damage to the parity set's own tables (d_par_off, d_par_crc, d_row_len, d_par_head) and to d_block_first / d_res_len
+ *                 -- small metadata the caller keeps twice; telling a damaged CRC word from damaged data (as in repair, a row whose
+ *                 CRC word is damaged is rebuilt to the same bytes and is still refused by a later salvage); m > 3, which is not
+ *                 solvable in general; updating parity in place after a write -- build again; parity over the data instead of the
+ *                 stored form; fusing salvage, rebuild, repair and splice in one call. */
+#define MSCOMP_AMD_PARITY_K_MAX 255u
+#define MSCOMP_AMD_PARITY_M_MAX 3u
+typedef struct mscomp_amd_parity mscomp_amd_parity;
+MSCompStatus mscomp_amd_parity_create(mscomp_amd_ctx* ctx, uint32_t block_size, uint64_t n_blocks_table, uint32_t k, uint32_t m,
+                                      uint32_t flags, mscomp_amd_parity** pr);
+void         mscomp_amd_parity_destroy(mscomp_amd_parity* pr);
+int          mscomp_amd_parity_bound(const mscomp_amd_parity* pr, uint64_t out[2]);   /* parity rows m*G_max, parity bytes m*G_max*block_size */
+MSCompStatus mscomp_amd_parity_build(mscomp_amd_parity* pr, const mscomp_amd_blocks_view* src,
+                                     uint8_t* d_par, uint64_t par_cap, uint64_t* d_par_off /* m*G_max + 1 */, uint32_t* d_par_crc /* m*G_max */,
+                                     uint32_t* d_row_len /* n_blocks_table */, uint64_t* d_par_head /* 4 */, int32_t* d_status /* 1 */);
+MSCompStatus mscomp_amd_parity_rebuild(mscomp_amd_parity* pr, const mscomp_amd_blocks_view* src, const uint32_t* d_verdict /* n_blocks_table */,
+                                       const uint8_t* d_par, uint64_t par_len, const uint64_t* d_par_off, const uint32_t* d_par_crc,
+                                       const uint32_t* d_row_len, const uint64_t* d_par_head,
+                                       uint8_t* d_fix_packed, uint64_t fix_cap, uint64_t* d_fix_block_off /* n_blocks_table + 1 */,
+                                       uint32_t* d_fix_verdict /* n_blocks_table */, uint64_t* d_count /* 6 */, int32_t* d_status /* 1 */);
+
 /* Resource checksums from block checksums. After a write or a resize the block CRC-32s are current and the resource CRC-32s that
  * mscomp_amd_blocks_crc once wrote are stale; the block checksums determine them, and no data has to be read:
  *   d_res_crc[r] = XOR over the resource's blocks j of d_block_crc[j] x^(8 d_j)  (mod the CRC polynomial), d_j = the resource's bytes behind block j

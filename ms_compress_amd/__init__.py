@@ -22,4 +22,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   blocks_diff, blocks_delta, blocks_patch, MSCOMP_AMD_DIFF_NO_BASE,
                   blocks_match, blocks_match_delta, blocks_match_patch, blocks_single_instance,
                   BlockSyncer, blocks_sync, blocks_sync_delta, blocks_sync_patch, MSCOMP_AMD_SYNC_TILE,
-                  BlockDigester, blocks_digest, MSCOMP_AMD_DIGEST_LEAF)
+                  BlockDigester, blocks_digest, MSCOMP_AMD_DIGEST_LEAF,
+                  BlockParity, blocks_parity, blocks_rebuild, MSCOMP_AMD_PARITY_K_MAX, MSCOMP_AMD_PARITY_M_MAX)

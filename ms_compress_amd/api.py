@@ -57,12 +57,14 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "mscomp_amd_syncer_create", "mscomp_amd_syncer_destroy", "mscomp_amd_syncer_sync", "mscomp_amd_syncer_counts",
     "mscomp_amd_digester_create", "mscomp_amd_digester_destroy", "mscomp_amd_digester_blocks", "mscomp_amd_digester_check",
     "mscomp_amd_syncer_create_digest", "mscomp_amd_syncer_sync_digest",
+    "mscomp_amd_parity_create", "mscomp_amd_parity_destroy", "mscomp_amd_parity_bound", "mscomp_amd_parity_build", "mscomp_amd_parity_rebuild",
     "mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report",
 ]
 MSCOMP_AMD_SPLICE_SRC_MAX = 4
 MSCOMP_AMD_SPLICE_ROW_TILE = 1024                              # rows of the new table per workgroup of splice_extents' row passes
 MSCOMP_AMD_SYNC_TILE = 4096                                    # positions per wave of a syncer's scan: its seams
 MSCOMP_AMD_DIGEST_LEAF = 1024                                  # bytes per leaf of a block digest's tree
+MSCOMP_AMD_PARITY_K_MAX, MSCOMP_AMD_PARITY_M_MAX = 255, 3           # members and parity rows per group of a BlockParity
 MSCOMP_AMD_DEV_LARGE_UNITS = 1
 MSCOMP_AMD_DIFF_NO_BASE = (1 << 64) - 1                        # the base resource of a diff pair whose new resource has none
 # the verdict of a row (BlockContainer.salvage): good; refused by its table entries; did not decode; decoded to other bytes; not judged
@@ -315,6 +317,17 @@ def load_library():
     lib.mscomp_amd_debug_lzd_walked.restype = C.c_uint32
     lib.mscomp_amd_debug_decode_modes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.mscomp_amd_debug_decode_modes.restype = C.c_int
+    lib.mscomp_amd_parity_create.restype = C.c_int
+    lib.mscomp_amd_parity_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.mscomp_amd_parity_destroy.restype = None
+    lib.mscomp_amd_parity_destroy.argtypes = [C.c_void_p]
+    lib.mscomp_amd_parity_bound.restype = C.c_int
+    lib.mscomp_amd_parity_bound.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.mscomp_amd_parity_build.restype = C.c_int
+    lib.mscomp_amd_parity_build.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
+    lib.mscomp_amd_parity_rebuild.restype = C.c_int
+    lib.mscomp_amd_parity_rebuild.argtypes = ([C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 +
+                                              [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4)
     lib.mscomp_amd_debug_scratch_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
     lib.mscomp_amd_debug_scratch_names.restype = C.c_int
     lib.mscomp_amd_debug_scratch_poison.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int]
@@ -1324,7 +1337,7 @@ def blocks_patch(base, delta, patch_resources, block_size, ctx=None):
     return blocks_splice_extents([base, delta], patch_resources, block_size, ctx=ctx)
 
 
-def blocks_repair(fmt, containers, block_size, ctx=None):
+def blocks_repair(fmt, containers, block_size, ctx=None, _verdicts0=None):
     """Mend a damaged block container from up to three copies on the GPU: ``containers`` = [primary, mirror, ...], each (packed,
     block_first, block_off, lengths, block_crc or None) of format ``fmt`` and ``block_size``. The primary is salvaged (blocks_salvage); each
     mirror is salvaged only in the rows the primary lacks when its lengths are the primary's, and whole otherwise; BlockDeduper.repair
@@ -1343,6 +1356,9 @@ def blocks_repair(fmt, containers, block_size, ctx=None):
         verdicts = []
         for i, (packed, first, off, lens, crc) in enumerate(containers):
             same = i > 0 and [int(x) for x in lens] == lens0
+            if i == 0 and _verdicts0 is not None:                   # (blocks_rebuild has salvaged the primary already)
+                verdicts.append(_verdicts0)
+                continue
             verdicts.append(blocks_salvage(fmt, packed, first, off, lens, B, ctx=ctx, block_crc=crc, only=verdicts[0] if same else None)[1])
         with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
             srcs, _, _ = _upload_containers(containers, dev, with_crc)
@@ -1690,6 +1706,125 @@ def blocks_sync_patch(store, recipe, literal_bytes, block_size, ctx=None, fmt=No
             at += ln
         out.append(bytes(buf))
     return out
+
+
+class BlockParity(_Handle):
+    """Reed-Solomon parity rows beside a block container (mscomp_amd_parity_create): ``m`` (1 .. 3) parity rows for every ``k`` (1 .. 255)
+    stored rows of a table of ``n_blocks_table`` rows, over the STORED bytes -- no format, no decoder --, and up to m lost rows per group
+    back from them without a mirror. GF(2^8), polynomial 0x11D, alpha = 2: P_p = XOR_i alpha^(p i) D_i. Groups are interleaved: with nb
+    rows and G = ceil(nb / k) groups, row j is member j // G of group j % G. All scratch is reserved here: 28 bytes per parity row of
+    m ceil(n_blocks_table / k), 12 per table row, 24 per group, + 72. Both calls enqueue kernels on the ctx stream and nothing else."""
+    _destroy = "mscomp_amd_parity_destroy"
+
+    def __init__(self, ctx, block_size, n_blocks_table, k, m):
+        _Handle.__init__(self, ctx)
+        self.block_size, self.n_blocks_table, self.k, self.m = int(block_size), int(n_blocks_table), int(k), int(m)
+        _ok(ctx.lib.mscomp_amd_parity_create(ctx._h, self.block_size, self.n_blocks_table, self.k, self.m, 0, C.byref(self._h)), "mscomp_amd_parity_create")
+
+    def bound(self):
+        """(parity rows, parity bytes) a build writes at most: m G_max and m G_max block_size"""
+        out = (C.c_uint64 * 2)()
+        if self.ctx.lib.mscomp_amd_parity_bound(self._h, out) != 0:
+            raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_parity_bound")
+        return int(out[0]), int(out[1])
+
+    def build(self, source, d_par, d_par_off, d_par_crc, d_row_len, d_par_head, d_status, par_cap=None):
+        """``source``: the container as BlockSplicer.splice takes one. Writes the parity set: d_par (uint8, 16-byte aligned; ``par_cap``
+        bytes of it, by default all), d_par_off (int64, rows + 1), d_par_crc (int32, rows: zlib's CRC-32 of every parity row), d_row_len
+        (int32, n_blocks_table: the stored length the parity was taken over, 0 for a row the table refuses), d_par_head (int64, 4: nb,
+        G, k, m) and d_status (int32, 1: MSCOMP_OK; MSCOMP_BUF_ERROR when a parity row ends beyond par_cap -- it is not written, the
+        tables hold the full layout --; MSCOMP_ARG_ERROR when the container has more rows than n_blocks_table or a table of another size)."""
+        cap = (0 if d_par is None else d_par.numel()) if par_cap is None else int(par_cap)
+        if d_par is not None and cap > d_par.numel():
+            raise ValueError("par_cap exceeds d_par")
+        p = _ptrs(d_par, d_par_off, d_par_crc, d_row_len, d_par_head, d_status)
+        _ok(self.ctx.lib.mscomp_amd_parity_build(self._h, _blocks_views([source]), p[0], cap, *p[1:]), "mscomp_amd_parity_build")
+
+    def rebuild(self, source, d_verdict, d_par, d_par_off, d_par_crc, d_row_len, d_par_head, d_fix_packed, d_fix_block_off, d_fix_verdict, d_count,
+                d_status, par_len=None, fix_cap=None):
+        """``source`` and ``d_verdict``: the damaged container and the verdicts BlockContainer.salvage gave for it; then the parity set as
+        build wrote it. A row is missing when its verdict is not GOOD or its table entries are not what d_row_len says; a group with e
+        missing rows and at least e parity rows that pass their CRC-32 gets them back. The answer is a SPARSE MIRROR: d_fix_packed (the
+        rebuilt rows' stored bytes in row order, ``fix_cap`` bytes of it at most), d_fix_block_off (int64, n_blocks_table + 1: stored
+        length 0 for every row not rebuilt) and d_fix_verdict (int32, n_blocks_table: GOOD for a row rebuilt and written, SKIPPED
+        otherwise) -- see fix_view. d_count (int64, 6) = rows missing, rows rebuilt, groups with a missing row, groups unrecoverable,
+        parity rows unusable, stored bytes rebuilt; d_status (int32, 1) = MSCOMP_OK, MSCOMP_BUF_ERROR (a rebuilt row beyond fix_cap),
+        MSCOMP_DATA_ERROR (a group lost more rows than it has usable parity; or parity of another container), MSCOMP_ARG_ERROR."""
+        plen, cap = _byte_bounds(d_par, par_len, d_fix_packed, fix_cap)
+        p = _ptrs(d_verdict, d_par, d_par_off, d_par_crc, d_row_len, d_par_head, d_fix_packed, d_fix_block_off, d_fix_verdict, d_count, d_status)
+        _ok(self.ctx.lib.mscomp_amd_parity_rebuild(self._h, _blocks_views([source]), p[0], p[1], plen, *p[2:7], cap, *p[7:]), "mscomp_amd_parity_rebuild")
+
+    @staticmethod
+    def fix_view(source, d_fix_packed, d_fix_block_off, fix_len=None):
+        """The sparse mirror rebuild wrote, as a source of BlockDeduper.repair and BlockSplicer.splice_extents beside ``source`` (the
+        primary, a full source tuple): its d_block_first, d_res_len and d_block_crc with the fix's stored bytes and offset table.
+        ``fix_len``: d_fix_block_off[nb] when the caller knows it (by default all of d_fix_packed: every offset lies inside it)."""
+        s = tuple(source)
+        return (d_fix_packed, s[1], d_fix_block_off, s[3], s[4] if len(s) > 4 else None, d_fix_packed.numel() if fix_len is None else int(fix_len),
+                s[6] if len(s) > 6 else None, s[7] if len(s) > 7 else None)
+
+
+def blocks_parity(container, block_size, k, m, ctx=None):
+    """The parity set of ``container`` = (packed, block_first, block_off, lengths, ...) on the GPU (BlockParity.build): (par, par_off,
+    par_crc, row_len, head) as numpy arrays -- par (uint8) cut to its length par_off[-1], par_off (uint64, m G + 1), par_crc (uint32,
+    m G), row_len (uint32, one per table row), head (uint64: nb, G, k, m). Keep it beside the container; blocks_rebuild takes it."""
+    import torch
+    packed, first, off, lens = container[:4]
+    with _call(ctx) as (ctx, dev):
+        srcs, _, nbt = _upload_containers([(packed, first, off, lens, None)], dev, False)
+        pr = BlockParity(ctx, block_size, nbt, k, m)
+        rows, room = pr.bound()
+        d_par = torch.zeros(room + 16, dtype=torch.uint8, device=dev)
+        d_off, d_crc = torch.zeros(rows + 1, dtype=torch.int64, device=dev), torch.zeros(max(1, rows), dtype=torch.int32, device=dev)
+        d_rl, d_head, d_st = torch.zeros(max(1, nbt), dtype=torch.int32, device=dev), torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+        pr.build(srcs[0], d_par, d_off, d_crc, d_rl, d_head, d_st, par_cap=room)
+        ctx.stream.synchronize()
+        _ok(int(d_st.cpu()[0]), "mscomp_amd_parity_build")
+        par_off = d_off.cpu().numpy().view(np.uint64).copy()
+        out = (d_par.cpu().numpy()[: int(par_off[-1])].copy(), par_off, d_crc.cpu().numpy().view(np.uint32)[:rows].copy(),
+               d_rl.cpu().numpy().view(np.uint32)[:nbt].copy(), d_head.cpu().numpy().view(np.uint64).copy())
+        pr.close()
+    return out
+
+
+def blocks_rebuild(fmt, container, parity, block_size, ctx=None, mirrors=()):
+    """Mend a damaged block container from its parity set on the GPU, without a second copy: ``container`` = (packed, block_first,
+    block_off, lengths, block_crc or None), ``parity`` as blocks_parity returned it. The container is salvaged (blocks_salvage),
+    BlockParity.rebuild writes the sparse mirror of the rows it can give back, and blocks_repair over [container, mirror, *mirrors] --
+    which salvages the mirror in the rows the container lacks, holding every rebuilt row to its CRC-32 -- and blocks_splice_extents
+    build the container. ``mirrors``: up to two real copies, asked only for what parity could not give. Returns (container, report):
+    blocks_repair's, plus "rebuild_counts" (rows missing, rows rebuilt, groups with a missing row, groups unrecoverable, parity rows
+    unusable, stored bytes rebuilt) and "rebuild_status"."""
+    import torch
+    B = int(block_size)
+    packed, first, off, lens, crc = container
+    par, par_off, par_crc, row_len, head = parity
+    k, m = int(head[2]), int(head[3])
+    with _call(ctx, enter=False) as (ctx, dev):
+        ver0 = blocks_salvage(fmt, packed, first, off, lens, B, ctx=ctx, block_crc=crc)[1]
+        with torch.cuda.device(ctx.device), torch.cuda.stream(ctx.stream):
+            srcs, _, nbt = _upload_containers([(packed, first, off, lens, None)], dev, False)
+            pr = BlockParity(ctx, B, nbt, k, m)
+            rows = pr.bound()[0]
+            par = np.ascontiguousarray(par, dtype=np.uint8)
+            d_par = torch.zeros(len(par) + 16, dtype=torch.uint8, device=dev)
+            if len(par):
+                d_par[: len(par)] = torch.from_numpy(par.copy()).to(dev)
+            d_poff, d_pcrc, d_rl = _dev_u64(par_off, rows + 1, dev), _dev_block_crc(par_crc, rows, dev), _dev_block_crc(row_len, nbt, dev)
+            d_head, d_ver = _dev_u64(head, 4, dev), _dev_block_crc(ver0, nbt, dev)
+            room = int(np.asarray(row_len, dtype=np.uint64).sum())
+            d_fix, d_foff = torch.zeros(room + 16, dtype=torch.uint8, device=dev), torch.zeros(nbt + 1, dtype=torch.int64, device=dev)
+            d_fver = torch.full((max(1, nbt),), MSCOMP_AMD_BLOCK_SKIPPED, dtype=torch.int32, device=dev)
+            d_cnt, d_st = torch.zeros(6, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+            pr.rebuild(srcs[0], d_ver, d_par, d_poff, d_pcrc, d_rl, d_head, d_fix, d_foff, d_fver, d_cnt, d_st, par_len=len(par), fix_cap=room)
+            ctx.stream.synchronize()
+            fix_off = d_foff.cpu().numpy().view(np.uint64).copy()
+            fix = (d_fix.cpu().numpy()[: int(fix_off[-1])].copy(), first, fix_off, lens, crc)
+            counts, status = [int(x) for x in d_cnt.cpu().numpy()], int(d_st.cpu()[0])
+            pr.close()
+        new, report = blocks_repair(fmt, [container, fix] + list(mirrors), B, ctx=ctx, _verdicts0=ver0)
+    report["rebuild_counts"], report["rebuild_status"] = counts, status
+    return new, report
 
 
 def res_crc_from_blocks(block_first, lengths, block_crc, block_size, ctx=None):

@@ -1235,6 +1235,133 @@ MSCompStatus mscomp_amd_digester_check(mscomp_amd_digester* d, const uint8_t* d_
 	});
 }
 
+// ---- parity rows (include/mscomp_amd.h; kernels: parity.hip, the CRC unit kernels of crc32.hip) ----
+// A parity object holds the table words of both calls and nothing else: no inner plan, no cache, no staging area -- the digester's shape.
+#pragma GCC visibility push(hidden)
+struct mscomp_amd_parity {
+	mscomp_amd_ctx* ctx = nullptr;
+	uint32_t block_size = 0;
+	GraphRun<15> brun; GraphRun<21> rrun;              // build, rebuild: the view, then the rest
+	DevBuf tab;                                        // parity_tab
+	ParityTab t{};
+};
+#pragma GCC visibility pop
+
+// the columns of a parity object's tables from `base` on (t.nbt, t.gmax, t.m set); returns where they end
+static uintptr_t parity_tab(ParityTab& t, void* base)
+{
+	Carve k(base);
+	const size_t Q = (size_t)t.gmax * t.m;
+	t.plen = k.q(Q); t.clen = k.q(Q); t.cum = k.q(Q + 1); t.fixlen = k.q(t.nbt); t.count = k.q(8);
+	t.pcrc = k.w(Q); t.rflag = k.w(t.nbt); t.grec = k.w(6 * (size_t)t.gmax); k.pad8();
+	return k.at;
+}
+
+MSCompStatus mscomp_amd_parity_create(mscomp_amd_ctx* c, uint32_t block_size, uint64_t n_blocks_table, uint32_t k, uint32_t m, uint32_t flags, mscomp_amd_parity** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!c || flags || !block_size_ok(block_size) || k < 1u || k > MSCOMP_AMD_PARITY_K_MAX || m < 1u || m > MSCOMP_AMD_PARITY_M_MAX || !count_ok(n_blocks_table)) { return MSCOMP_ARG_ERROR; }
+	const uint64_t gmax = (n_blocks_table + k - 1u) / k;
+	if (!count_ok(gmax * m)) { return MSCOMP_MEM_ERROR; }                  // (checked before the context is used: the parity rows are CRC units, counted in 32 bits)
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	std::unique_ptr<mscomp_amd_parity> pr(new (std::nothrow) mscomp_amd_parity());
+	if (!pr) { return MSCOMP_MEM_ERROR; }
+	pr->ctx = c; pr->block_size = block_size;
+	ParityTab& t = pr->t;
+	t.nbt = (uint32_t)n_blocks_table; t.gmax = (uint32_t)gmax; t.k = k; t.m = m; t.shift = (uint32_t)__builtin_ctz(block_size);
+	if (!pr->tab.reserve(parity_tab(t, nullptr) + 64)) { (void)hipGetLastError(); return MSCOMP_MEM_ERROR; }
+	parity_tab(t, pr->tab.p);
+	*out = pr.release();
+	return MSCOMP_OK;
+}
+
+void mscomp_amd_parity_destroy(mscomp_amd_parity* pr) { destroy_object(pr, [pr] { pr->tab.release(); }); }
+
+int mscomp_amd_parity_bound(const mscomp_amd_parity* pr, uint64_t out[2])
+{
+	if (!pr || !out) { return -1; }
+	out[0] = (uint64_t)pr->t.gmax * pr->t.m; out[1] = out[0] * pr->block_size;
+	return 0;
+}
+
+// The CRC-32 of the parity rows into t.pcrc, t.clen bytes of each: crc_pass with the parity scan for its table pass (a unit table of
+// lengths alone needs none of that pass's bounds checks, and the scan takes an eighth of its serial steps)
+static void parity_crc(mscomp_amd_ctx* c, const ParityTab& t, uint32_t Q, const uint8_t* par, const u64* par_off)
+{
+	{ KernelTimer k(c, "pa_scan_kernel"); launch_parity_scan(c->stream, Q, t.clen, t.cum); }
+	{ KernelTimer k(c, "crc_seed_kernel"); launch_crc_seeds(c->stream, Q, t.cum, t.pcrc, nullptr, nullptr); }
+	{ KernelTimer k(c, "crc_kernel"); launch_crc_units(c->stream, Q, par, par_off, t.cum, t.pcrc, nullptr, nullptr, nullptr, c->crc_blocks); }
+}
+
+// what both calls ask of their view: one pack_views takes, and MSCOMP_ARG_ERROR otherwise; `mis`: rule 0's half that the host knows
+static bool parity_view(const mscomp_amd_parity* pr, const mscomp_amd_blocks_view* src, SpliceView& v, bool& mis)
+{
+	bool with_crc = false;
+	if (!src || !pack_views(src, 1, false, &v, with_crc)) { return false; }
+	mis = src->n_blocks_table != pr->t.nbt;
+	return true;
+}
+
+MSCompStatus mscomp_amd_parity_build(mscomp_amd_parity* pr, const mscomp_amd_blocks_view* src, uint8_t* d_par, uint64_t par_cap, uint64_t* d_par_off, uint32_t* d_par_crc,
+                                     uint32_t* d_row_len, uint64_t* d_par_head, int32_t* d_status)
+{
+	SpliceView v; bool mis = false;
+	if (!pr || !d_par_head || !d_status || !parity_view(pr, src, v, mis)) { return MSCOMP_ARG_ERROR; }
+	const ParityTab& t = pr->t;
+	const uint32_t Q = t.gmax * t.m;
+	if (t.nbt && (!d_par_off || !d_par_crc || !d_row_len || (par_cap && !d_par) || (reinterpret_cast<uintptr_t>(d_par) & 15u))) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = pr->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[15];
+	view_args(args, &v, { static_cast<const void*>(d_par), reinterpret_cast<const void*>(static_cast<uintptr_t>(par_cap)), static_cast<const void*>(d_par_off),
+	                      static_cast<const void*>(d_par_crc), static_cast<const void*>(d_row_len), static_cast<const void*>(d_par_head), static_cast<const void*>(d_status) });
+	return plan_run(pr->brun, c, args, [&] {
+		if (t.nbt) {
+			{ KernelTimer k(c, "pa_rows_kernel"); launch_parity_rows(c->stream, v, t, mis, d_row_len, c->crc_blocks); }
+			{ KernelTimer k(c, "pa_groups_kernel"); launch_parity_groups(c->stream, v, t, mis, d_row_len, nullptr, c->crc_blocks); }
+			{ KernelTimer k(c, "pa_scan_kernel"); launch_parity_scan(c->stream, Q, t.plen, d_par_off); }
+			{ KernelTimer k(c, "pa_units_kernel"); launch_parity_units(c->stream, t, d_par_off, par_cap, c->crc_blocks); }
+			{ KernelTimer k(c, "pa_build_kernel"); launch_parity_build(c->stream, v, t, mis, d_row_len, d_par, par_cap, d_par_off, c->crc_blocks); }
+			parity_crc(c, t, Q, d_par, d_par_off);
+		}
+		{ KernelTimer k(c, "pa_head_kernel"); launch_parity_head(c->stream, v, t, mis, d_par_off, par_cap, d_par_crc, d_par_head, d_status, c->crc_blocks); }
+	});
+}
+
+MSCompStatus mscomp_amd_parity_rebuild(mscomp_amd_parity* pr, const mscomp_amd_blocks_view* src, const uint32_t* d_verdict, const uint8_t* d_par, uint64_t par_len,
+                                       const uint64_t* d_par_off, const uint32_t* d_par_crc, const uint32_t* d_row_len, const uint64_t* d_par_head, uint8_t* d_fix_packed,
+                                       uint64_t fix_cap, uint64_t* d_fix_block_off, uint32_t* d_fix_verdict, uint64_t* d_count, int32_t* d_status)
+{
+	SpliceView v; bool mis = false;
+	if (!pr || !d_par_head || !d_count || !d_status || !parity_view(pr, src, v, mis)) { return MSCOMP_ARG_ERROR; }
+	const ParityTab& t = pr->t;
+	const uint32_t Q = t.gmax * t.m;
+	if (t.nbt && (!d_verdict || !d_par_off || !d_par_crc || !d_row_len || !d_fix_block_off || !d_fix_verdict || (par_len && !d_par) || (fix_cap && !d_fix_packed) ||
+	              (reinterpret_cast<uintptr_t>(d_par) & 15u))) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = pr->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[21];
+	view_args(args, &v, { static_cast<const void*>(d_verdict), static_cast<const void*>(d_par), reinterpret_cast<const void*>(static_cast<uintptr_t>(par_len)),
+	                      static_cast<const void*>(d_par_off), static_cast<const void*>(d_par_crc), static_cast<const void*>(d_row_len), static_cast<const void*>(d_par_head),
+	                      static_cast<const void*>(d_fix_packed), reinterpret_cast<const void*>(static_cast<uintptr_t>(fix_cap)), static_cast<const void*>(d_fix_block_off),
+	                      static_cast<const void*>(d_fix_verdict), static_cast<const void*>(d_count), static_cast<const void*>(d_status) });
+	return plan_run(pr->rrun, c, args, [&] {
+		if (t.nbt) { KernelTimer k(c, "pa_groups_kernel"); launch_parity_groups(c->stream, v, t, mis, d_row_len, d_par_head, c->crc_blocks); }
+		{ KernelTimer k(c, "pa_check_kernel"); launch_parity_check(c->stream, t, d_par_off, par_len, c->crc_blocks); }
+		if (t.nbt) {
+			parity_crc(c, t, Q, d_par, d_par_off);
+			{ KernelTimer k(c, "pa_damage_kernel"); launch_parity_damage(c->stream, v, t, mis, d_verdict, d_par_off, par_len, d_par_crc, d_row_len, d_par_head, c->crc_blocks); }
+			{ KernelTimer k(c, "pa_scan_kernel"); launch_parity_scan(c->stream, t.nbt, t.fixlen, d_fix_block_off); }
+			{ KernelTimer k(c, "pa_solve_kernel"); launch_parity_solve(c->stream, v, t, mis, d_par, d_par_off, d_row_len, d_par_head, d_fix_packed, fix_cap, d_fix_block_off, c->crc_blocks); }
+		}
+		{ KernelTimer k(c, "pa_tail_kernel"); launch_parity_tail(c->stream, v, t, mis, d_par_head, fix_cap, d_fix_block_off, d_fix_verdict, d_count, d_status, c->crc_blocks); }
+	});
+}
+
 // ---- the scratch hooks' view of the objects above (api.hip: mscomp_amd_debug_scratch_*) ----
 extern "C++" mscomp_amd_ctx* msc::scratch_of_object(int kind, void* obj, std::vector<ScratchEnt>& v)
 {

@@ -677,6 +677,42 @@ void launch_digest_leaves(hipStream_t st, const uint8_t* base, const DigestTab& 
 void launch_digest_roots(hipStream_t st, const DigestTab& d, uint32_t* out, uint32_t n_res, const int32_t* rstat, int32_t* d_status);
 // (check, behind the root pass: launch_blocks_kfold over d.out and the caller's block_digest, four words per entry)
 
+// ---- Reed-Solomon parity rows (parity.hip, gfmath.h; mscomp_amd_parity_*) ----
+// m parity rows per group of k table rows, over the STORED bytes: P_p = XOR_i alpha^(p i) D_i in GF(2^8). Row j of the nb rows the
+// container has is member j / G of group j % G, G = ceil(nb / k): nb is a device value, so every pass works G out for itself and is
+// gridded by gmax = ceil(nbt / k). Parity row q = g m + p. The scratch of a parity object (blockobj.hip parity_tab knows the layout),
+// Q = m gmax:
+struct ParityTab {
+	u64 *plen, *clen, *cum;                            // Q, Q, Q + 1: a parity row's length by the row lengths; the bytes the CRC kernels read of it; their running sum
+	u64* fixlen;                                       // nbt: rebuild, the stored length of a row it rebuilds, else 0
+	u64* count;                                        // 8: rebuild, d_count[0..5], then the listed groups
+	uint32_t* pcrc;                                    // Q: the CRC-32 read of every parity row
+	uint32_t* rflag;                                   // nbt: rebuild, 1 = the row is rebuilt
+	uint32_t* grec;                                    // 6 gmax: rebuild, a record per listed (damaged, recoverable) group: e | parities, members, three rows of the inverse, g
+	uint32_t nbt, gmax, k, m, shift;
+};
+#define PA_TILE_SHIFT 12u                              // a workgroup item of the parity and solve passes: 4096 bytes of a group's column
+// build (nine launches with the three of the CRC pass between units and head; the caller runs that one). rows: rule 1, row_len (nbt);
+// groups: t.plen; scan: the running sum of t.plen is par_off (one workgroup; out: n + 1 entries); units: t.clen by rule 4; parity: the bytes, a fixed grid
+// dealt over (group, column tile); head: par_crc from t.pcrc, par_head and the status. `mis`: the view's table is not of nbt rows (rule 0)
+void launch_parity_rows(hipStream_t st, const SpliceView& v, const ParityTab& t, bool mis, uint32_t* row_len, uint32_t blocks);
+void launch_parity_groups(hipStream_t st, const SpliceView& v, const ParityTab& t, bool mis, const uint32_t* row_len, const u64* head, uint32_t blocks);
+void launch_parity_scan(hipStream_t st, u64 n, const u64* len, u64* out);
+void launch_parity_units(hipStream_t st, const ParityTab& t, const u64* par_off, u64 par_cap, uint32_t blocks);
+void launch_parity_build(hipStream_t st, const SpliceView& v, const ParityTab& t, bool mis, const uint32_t* row_len, uint8_t* par, u64 par_cap, const u64* par_off, uint32_t blocks);
+void launch_parity_head(hipStream_t st, const SpliceView& v, const ParityTab& t, bool mis, const u64* par_off, u64 par_cap, uint32_t* par_crc, u64* par_head, int32_t* status,
+                        uint32_t blocks);
+// rebuild: launch_parity_groups with the caller's header (rule 0), then -- check: t.clen by rule 2's table half, t.fixlen, t.rflag and
+// t.count cleared; the CRC pass into t.pcrc; damage: a lane per group, rules 1-3, the records and counts; launch_parity_scan over t.fixlen
+// gives fix_off; solve: a fixed grid dealt over (listed group, column tile); tail: the verdicts, the counts and the status
+void launch_parity_check(hipStream_t st, const ParityTab& t, const u64* par_off, u64 par_len, uint32_t blocks);
+void launch_parity_damage(hipStream_t st, const SpliceView& v, const ParityTab& t, bool mis, const uint32_t* verdict, const u64* par_off, u64 par_len, const uint32_t* par_crc,
+                          const uint32_t* row_len, const u64* head, uint32_t blocks);
+void launch_parity_solve(hipStream_t st, const SpliceView& v, const ParityTab& t, bool mis, const uint8_t* par, const u64* par_off, const uint32_t* row_len, const u64* head,
+                         uint8_t* fix, u64 fix_cap, const u64* fix_off, uint32_t blocks);
+void launch_parity_tail(hipStream_t st, const SpliceView& v, const ParityTab& t, bool mis, const u64* head, u64 fix_cap, const u64* fix_off, uint32_t* fix_verdict, u64* count,
+                        int32_t* status, uint32_t blocks);
+
 // ---- CRC-32 of units in HBM (crc32.hip; mscomp_amd_plan_*_crc_dev, mscomp_amd_blocks_crc / _check) ----
 // the table pass, one block: cum[0..n] = running sum of the accepted in_len (a unit whose running total exceeds in_total_max: length 0, status
 // MSCOMP_ARG_ERROR), off[i] = its offset. in_off / off and status may be null.
