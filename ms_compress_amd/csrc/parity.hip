@@ -115,16 +115,27 @@ __global__ __launch_bounds__(DV_THREADS) void pa_scan_kernel(u64 n, const u64* _
 	if (threadIdx.x == 0) { out[0] = 0; }
 	for (u64 base = 0; base < n; base += (u64)DV_THREADS * PA_SCAN_PER) {
 		const u64 at = base + (u64)threadIdx.x * PA_SCAN_PER;
+		const bool all = at + PA_SCAN_PER <= n;                                 // (a lane whose entries all exist: no test per entry, no eight masks kept across the scan)
 		u64 v[PA_SCAN_PER];
-		#pragma unroll
-		for (uint32_t j = 0; j < PA_SCAN_PER; ++j) { v[j] = at + j < n ? len[at + j] : 0; }
+		if (all) {
+			#pragma unroll
+			for (uint32_t j = 0; j < PA_SCAN_PER; ++j) { v[j] = len[at + j]; }
+		} else {
+			#pragma unroll
+			for (uint32_t j = 0; j < PA_SCAN_PER; ++j) { v[j] = at + j < n ? len[at + j] : 0; }
+		}
 		#pragma unroll
 		for (uint32_t j = 1; j < PA_SCAN_PER; ++j) { v[j] += v[j - 1u]; }
 		u64 tot[1] = {v[PA_SCAN_PER - 1u]};
 		dv_block_scan<1>(tot, run, s_w);                                     // up to and including this lane's entries
 		const u64 before = tot[0] - v[PA_SCAN_PER - 1u];
-		#pragma unroll
-		for (uint32_t j = 0; j < PA_SCAN_PER; ++j) { if (at + j < n) { out[at + j + 1u] = before + v[j]; } }
+		if (all) {
+			#pragma unroll
+			for (uint32_t j = 0; j < PA_SCAN_PER; ++j) { out[at + j + 1u] = before + v[j]; }
+		} else {
+			#pragma unroll
+			for (uint32_t j = 0; j < PA_SCAN_PER; ++j) { if (at + j < n) { out[at + j + 1u] = before + v[j]; } }
+		}
 	}
 }
 

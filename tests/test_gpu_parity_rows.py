@@ -14,7 +14,7 @@ import repair_model as P
 from repair_model import GOOD, TABLE, CRC, SKIPPED
 
 from blocks_rig import Container, Spliced, d64, flip, i32, memo, mixed, rand, soft, text, FMTS, FILL
-from parity_rig import FixOuts, ParitySet, check_build, check_rebuild, fix_container
+from parity_rig import FixOuts, ParitySet, check_build, check_rebuild, fix_container, synthetic
 from repair_rig import SalvageOuts, check_repair, check_salvage, rebuild, repair_outs
 
 pytestmark = pytest.mark.gpu
@@ -121,11 +121,7 @@ def test_build_at_64k_and_the_column_tile_seam(gpu_ctx, made):
         check_build(pr, h, what=("64k", k, m))
         pr.close()
     for plen in (4080, 4096, 4112, 8192, 8208):
-        lens = [plen - 3, 100, plen - 16, 1, 4000, 17]
-        off = np.concatenate([[3], 3 + np.cumsum(lens)]).astype(np.uint64)        # (the first row at residue 3)
-        packed = rand(plen, int(off[-1]))
-        syn = Container.from_host(gpu_ctx, f, Bb, packed, [0, 6], off, [6 * Bb], np.zeros(6, dtype=np.uint32))
-        syn.d_packed[syn.plen:] = FILL
+        syn = synthetic(gpu_ctx, f, Bb, [plen - 3, 100, plen - 16, 1, 4000, 17], plen)   # (the first row at residue 3)
         pr = mm.BlockParity(gpu_ctx, Bb, 6, 6, 3)
         mo, _ = check_build(pr, syn, what=("seam", plen))
         assert mo["par_off"][1] == plen

@@ -1,7 +1,8 @@
 """CPU: the parity model (tests/parity_model.py), which the GPU tests compare mscomp_amd_parity_build and _rebuild with array for array.
 The field and the code are pinned here -- the packed "times alpha" of the kernels against the table product, Horner against the defining
 sum -- and so is the reason for the cap of three parity rows: every erasure pattern of up to three rows is solvable with ANY parities of
-{0, 1, 2}, exhaustively at k = 255, and a fourth parity alpha^(3 i) is not. Then round trips on small containers of tests/blocks_model.py."""
+{0, 1, 2}, exhaustively at k = 255, and a fourth parity alpha^(3 i) is not. Then round trips on small containers of tests/blocks_model.py, and the synthetic tables of
+tests/test_gpu_parity_edges.py (tests/parity_rig.py) with the assertions that they reach the branches they are named for."""
 import itertools
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 
 import extents_model as X
 import parity_model as Y
+import parity_rig as G
 import read_model as R
 import repair_model as P
 
@@ -195,3 +197,88 @@ def test_fix_view_and_repair_give_the_healthy_container(api, oracle, src):
         mr = P.model_repair([dam, fix], [ver, second], B, n, nb)
         assert not any(mr["status"]) and mr["count"][:2] == [6, 0]
         P.holds_consequence([dam, fix], mr, B, src)
+
+
+# ---- the inputs of tests/test_gpu_parity_edges.py (tests/parity_rig.py) through the model alone: build, erase, rebuild, rows back ----------
+def _round_trip(s, mb, rows, k, m, Bs, pset=None, want_used=None, lost_group=None):
+    """rebuild of ``rows`` lost from the synthetic source s; every row of a recoverable group comes back with its stored bytes"""
+    dam, ver = G.lose_host(s, rows)
+    mo = Y.model_rebuild(dam, ver, pset or mb["set"], Bs, k, m, 1 << 40)
+    nb = int(s[2][-1])
+    Gn = (nb + k - 1) // k
+    back = [j for j in rows if j % Gn != lost_group]
+    assert mo["rebuilt"] == sorted(back) and mo["unrecoverable"] == ([] if lost_group is None else [lost_group])
+    assert mo["status"] == (Y.OK if lost_group is None else Y.DATA)
+    fix = Y.fix_source(s, mo)
+    for j in back:
+        assert _stored(fix, j) == _stored(s, j), j
+    if want_used is not None:
+        assert mo["used"] == want_used, (mo["used"], want_used)
+    return mo
+
+
+def test_edges_every_parity_subset_at_high_member_indices(api):
+    lens = G.subset_table()
+    s = G.synthetic_host(G.SUB_B, lens, 51)
+    for m in (3, 2):
+        cases = G.subset_cases(m)
+        G.subset_conditions(lens, cases, m)
+        mb = Y.model_build(s, G.SUB_B, G.SUB_K, m, 1 << 40)
+        assert mb["head"] == [G.SUB_NB, 2, G.SUB_K, m] and mb["par_off"][m] == m * 4096
+        seen = set()
+        for usable, lost0, lost1 in cases:
+            pset = G.spoiled(mb["set"], G.spoil(mb["par_off"], m, 0, usable))
+            used = {0: list(usable[: len(lost0)])}
+            if lost1:
+                used[1] = list(range(len(lost1)))
+            mo = _round_trip(s, mb, G.subset_rows(lost0, lost1), G.SUB_K, m, G.SUB_B, pset, used)
+            assert mo["count"][4] == m - len(usable)
+            seen.add(tuple(mo["used"][0]))
+        assert seen == (set(G.SUBSETS) if m == 3 else {(0,), (1,), (0, 1)})
+    mb = Y.model_build(s, G.SUB_B, G.SUB_K, 3, 1 << 40)
+    for usable, lost0, lost1 in G.subset_overflows():
+        assert len(lost0) == len(usable) + 1
+        _round_trip(s, mb, G.subset_rows(lost0, lost1), G.SUB_K, 3, G.SUB_B, G.spoiled(mb["set"], G.spoil(mb["par_off"], 3, 0, usable)), {1: [0]}, lost_group=0)
+
+
+def test_edges_every_member_position_of_small_groups(api):
+    for nb in range(1, 10):
+        s = G.synthetic_host(B, G.SMALL_LENS[:nb], 60 + nb)
+        mb = Y.model_build(s, B, nb, 1, 1 << 40)
+        assert mb["head"] == [nb, 1, nb, 1]
+        for j in range(nb):
+            _round_trip(s, mb, [j], nb, 1, B, want_used={0: [0]})
+
+
+def test_edges_rebuild_across_column_tiles(api):
+    tables = G.tile_tables()
+    G.tile_conditions(tables)
+    for plen, lens in tables:
+        s = G.synthetic_host(G.TILE_B, lens, plen)
+        for (k, m), losses in G.TILE_LOSSES.items():
+            mb = Y.model_build(s, G.TILE_B, k, m, 1 << 40)
+            assert mb["par_off"][1] == plen
+            for rows in losses:
+                _round_trip(s, mb, rows, k, m, G.TILE_B)
+
+
+@pytest.mark.parametrize("k,m", list(G.BIG_SHAPES))
+def test_edges_tables_past_one_scan_tile(api, k, m):
+    lens = G.big_table()
+    s = G.synthetic_host(G.BIG_B, lens, 71, nbt=G.BIG_NBT)
+    rows, X, spoil_n = G.big_losses(k, m)
+    listed = G.big_conditions(k, m, rows, X)
+    mb = Y.model_build(s, G.BIG_B, k, m, 1 << 40)
+    assert len(mb["par_off"]) == Y.geometry(G.BIG_NBT, k, m)[1] + 1 and mb["row_len"][G.BIG_NB:] == [0] * 3
+    pset = G.spoiled(mb["set"], G.spoil(mb["par_off"], m, X, range(m - spoil_n)))
+    mo = _round_trip(s, mb, rows, k, m, G.BIG_B, pset, lost_group=X)
+    assert len(mo["used"]) == listed and mo["count"][2:5] == [listed + 1, 1, spoil_n] and mo["fix_off"][-1] == sum(int(lens[j]) for j in mo["rebuilt"])
+
+
+def test_edges_alignment_matrix(api):
+    lens, start = G.align_table()
+    s = G.synthetic_host(G.ALIGN_B, lens, 81)
+    assert np.array_equal(np.asarray(s[3][: G.ALIGN_NB], dtype=np.int64) % 16, start)
+    k, m = G.ALIGN_SHAPE
+    mb = Y.model_build(s, G.ALIGN_B, k, m, 1 << 40)
+    _round_trip(s, mb, G.align_losses(lens, start), k, m, G.ALIGN_B)
