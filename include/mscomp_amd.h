@@ -1617,6 +1617,9 @@ void         mscomp_amd_debug_set_finder(int mode);
 void         mscomp_amd_debug_set_one_shot(int mode);
 /* Test hook: the LZNT1 chunk stage has two bit-identical kernels (one wave / four waves per 4 KiB chunk). 0 = default, 1 / 2 = force. */
 void         mscomp_amd_debug_set_lznt1(int mode);
+/* Test hook: the LZNT1 chunk images are moved to their places by a grid that is fixed by the device, every block taking tiles of 64 chunks
+ * b, b + grid, ...; n > 0 = at most n blocks (a block's second tile then runs in a batch of 65 chunks and more), 0 = default. Same bytes. */
+void         mscomp_amd_debug_set_place_blocks(int n);
 /* Test hook: LZNT1 decompression finds the chunk headers by walking speculated chains per 48 KiB segment of the input; a segment
  * whose speculation held nothing usable is walked again by one lane. Returns how many segments that happened to since the last call
  * (synchronizes the stream). */

@@ -35,7 +35,7 @@ EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the libra
     "ms_deflate_init", "ms_deflate", "ms_deflate_end", "lznt1_deflate_init", "lznt1_deflate", "lznt1_deflate_end",
     "xpress_deflate_init", "xpress_deflate", "xpress_deflate_end", "xpress_inflate_init", "xpress_inflate", "xpress_inflate_end",
     "ms_decompress", "lznt1_decompress", "xpress_decompress", "xpress_huff_decompress", "mscomp_amd_plan_create_decompress", "mscomp_amd_decompress_batch",
-    "mscomp_amd_version", "mscomp_amd_debug_xpress_matches", "mscomp_amd_debug_huff_lengths", "mscomp_amd_debug_huff_lengths_slow", "mscomp_amd_debug_lds_lane_order", "mscomp_amd_debug_alignbyte", "mscomp_amd_debug_set_xpress_emit", "mscomp_amd_debug_set_lznt1", "mscomp_amd_debug_set_serial_atomics", "mscomp_amd_compress_units_host", "mscomp_amd_decompress_units_host", "mscomp_amd_host_pool_release", "mscomp_amd_debug_set_finder", "mscomp_amd_debug_set_one_shot", "mscomp_amd_debug_set_xpress_decoder", "mscomp_amd_debug_lzg_open", "mscomp_amd_set_lznt1_sa_dict", "mscomp_amd_get_lznt1_sa_dict", "mscomp_amd_ctx_set_lznt1_sa_dict", "mscomp_amd_debug_hooks_enabled", "mscomp_amd_debug_lzd_walked", "mscomp_amd_debug_decode_modes",
+    "mscomp_amd_version", "mscomp_amd_debug_xpress_matches", "mscomp_amd_debug_huff_lengths", "mscomp_amd_debug_huff_lengths_slow", "mscomp_amd_debug_lds_lane_order", "mscomp_amd_debug_alignbyte", "mscomp_amd_debug_set_xpress_emit", "mscomp_amd_debug_set_lznt1", "mscomp_amd_debug_set_place_blocks", "mscomp_amd_debug_set_serial_atomics", "mscomp_amd_compress_units_host", "mscomp_amd_decompress_units_host", "mscomp_amd_host_pool_release", "mscomp_amd_debug_set_finder", "mscomp_amd_debug_set_one_shot", "mscomp_amd_debug_set_xpress_decoder", "mscomp_amd_debug_lzg_open", "mscomp_amd_set_lznt1_sa_dict", "mscomp_amd_get_lznt1_sa_dict", "mscomp_amd_ctx_set_lznt1_sa_dict", "mscomp_amd_debug_hooks_enabled", "mscomp_amd_debug_lzd_walked", "mscomp_amd_debug_decode_modes",
     "mscomp_amd_plan_create_size", "mscomp_amd_plan_execute_size", "mscomp_amd_decompressed_size_batch",
     "mscomp_amd_plan_create_decompress_dev", "mscomp_amd_plan_execute_dev", "mscomp_amd_layout_dev",
     "mscomp_amd_plan_create_compress_dev", "mscomp_amd_plan_layout_dev",
@@ -311,6 +311,8 @@ def load_library():
     lib.mscomp_amd_debug_set_one_shot.restype = None
     lib.mscomp_amd_debug_set_lznt1.argtypes = [C.c_int]
     lib.mscomp_amd_debug_set_lznt1.restype = None
+    lib.mscomp_amd_debug_set_place_blocks.argtypes = [C.c_int]
+    lib.mscomp_amd_debug_set_place_blocks.restype = None
     lib.mscomp_amd_debug_set_serial_atomics.argtypes = [C.c_int]
     lib.mscomp_amd_debug_set_serial_atomics.restype = None
     lib.mscomp_amd_debug_lzd_walked.argtypes = [C.c_void_p]

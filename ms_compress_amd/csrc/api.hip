@@ -105,6 +105,7 @@ MSCompStatus mscomp_amd_ctx_create(int device, void* hip_stream, mscomp_amd_ctx*
 	c->device = device; c->stream = (hipStream_t)hip_stream;
 	c->cpd_blocks = compact_dev_blocks();
 	c->crc_blocks = crc_dev_blocks();
+	(void)place_blocks(false); (void)place_blocks(true);           // (the grid of the LZNT1 placement, kept per device in util.hip: asked here, not inside a capture)
 	*out = c;
 	return MSCOMP_OK;
 }
@@ -1136,6 +1137,8 @@ void mscomp_amd_debug_set_lznt1(int mode) { if (!test_hooks_on()) { return; } se
 // Test hook: 1 = the order-independent form of the LZNT1 bucket sort and the Xpress chain links on every device (what a device that fails the
 // lane-order self-check gets), 0 = back to one atomic per 64 positions
 void mscomp_amd_debug_set_serial_atomics(int on) { if (!test_hooks_on()) { return; } set_serial_atomics(-1, on); g_mode_epoch.fetch_add(1, std::memory_order_acq_rel); }
+// Test hook: at most n blocks for the LZNT1 placement (util.hip concat_slots_kernel), so that a block takes a second tile in a small batch; 0 = the device's grid
+void mscomp_amd_debug_set_place_blocks(int n) { if (!test_hooks_on()) { return; } set_place_blocks(n); g_mode_epoch.fetch_add(1, std::memory_order_acq_rel); }
 
 // Hardware self-check (see util.hip): lanes whose returning LDS atomic was NOT served in lane order, summed over
 // blocks x rounds x 64 lanes x {add, exchange}; 0 on gfx950. 0xFFFFFFFF = the check could not run.

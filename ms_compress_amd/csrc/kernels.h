@@ -740,9 +740,12 @@ void launch_crc_fold_runs(hipStream_t st, uint32_t n, const u64* n_live, uint32_
 // ---- utilities (util.hip) ----
 // prefix[0..n] = exclusive scan of sizes[0..n) as u64 (prefix[n] = total). block_sums: scratch of ceil(n/1024)+1 u64.
 void launch_scan_sizes(hipStream_t st, const uint32_t* sizes, u64* prefix, uint32_t n, u64* block_sums);
-// Concatenate the chunk images of every unit into the caller's output (skips units that do not fit).
+// Concatenate the chunk images of every unit into the caller's output (skips units that do not fit): a fixed grid over tiles of 64 chunks,
+// place_blocks() of the device and instance, capped by the tiles of the batch and by the test hook (set_place_blocks, 0 = no cap)
 void launch_concat_slots(hipStream_t st, const uint8_t* slots, uint32_t slot_stride, const uint32_t* slot_size,
                          const u64* prefix, const BatchTables& bt, uint8_t* d_out, bool dev = false);
+uint32_t place_blocks(bool dev);
+void set_place_blocks(int n);
 // Per unit: out_len, status (OK / BUF_ERROR); LZNT1 also appends the uncounted 00 00 End_of_buffer when room.
 // outputs of a batch packed back to back: packed_off[0..n] (device), bytes of unit u at d_packed + packed_off[u]
 void launch_compact(hipStream_t st, const uint8_t* d_out, const u64* d_out_off, const uint32_t* d_tile_prefix, uint32_t n_units, uint32_t n_tiles,

@@ -74,29 +74,88 @@ void launch_scan_sizes(hipStream_t st, const uint32_t* sizes, u64* prefix, uint3
 	hipLaunchKernelGGL(scan_add_kernel, dim3((n + 256u) / 256u), dim3(256), 0, st, prefix, n, tile_sums, nt);
 }
 
-// one wave per chunk image (DEV: the chunks past the batch's real count return, common.h past_real_chunks)
+// ---- placement of the chunk images ----
+// A grid that is fixed by the device (place_blocks below) walks the batch in tiles of 64 consecutive chunks: block b takes the tiles b,
+// b + grid, ..., so every block gets a sample of all units. Per tile a wave reads the 64 offsets and sizes with one coalesced load each and
+// finds the unit of its first chunk by one binary search on the scalar path; the unit's row (out_off, out_cap, start and total of its
+// images) comes from scalar loads and is read again only where a chunk reaches chunk_prefix[u + 1]. The four waves of a block take the
+// images w, w + 4, ... of the tile, one wave per image (common.h rd_wave_move: a bytewise head up to the destination's next 16-byte boundary,
+// a body of 16-byte stores with the image's loads -- at most four per lane for the 4 098 bytes of a raw chunk -- issued before the first
+// store, a bytewise tail): no byte of a slot behind its image is read and no byte of d_out is read at all (the one-shot zero-copy path hands
+// the caller's mapped host memory in). A unit whose images exceed its capacity gets no byte (BUF_ERROR, finalize_units_kernel).
+// DEV: the chunks past the batch's real count (common.h past_real_chunks) belong to no unit and to no tile.
+#define PLACE_TILE 64u
+
+struct PlaceUnit { uint32_t u, end; u64 start, off; bool fits; };     // end = chunk_prefix[u + 1]; start = the offset of the unit's first image
+__device__ __forceinline__ PlaceUnit place_unit(const BatchTables& bt, const u64* __restrict__ prefix, uint32_t lo, uint32_t c)
+{
+	uint32_t hi = bt.n_units;                                           // invariant: chunk_prefix[lo] <= c < chunk_prefix[hi]
+	while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (bt.chunk_prefix[mid] <= c) { lo = mid; } else { hi = mid; } }
+	PlaceUnit r;
+	r.u = lo; r.end = bt.chunk_prefix[lo + 1u];
+	r.start = prefix[bt.chunk_prefix[lo]]; r.off = bt.out_off[lo];
+	r.fits = prefix[r.end] - r.start <= bt.out_cap[lo];
+	return r;
+}
+
 template <bool DEV = false>
 __global__ __launch_bounds__(256) void concat_slots_kernel(const uint8_t* __restrict__ slots, uint32_t slot_stride,
                                                           const uint32_t* __restrict__ slot_size, const u64* __restrict__ prefix,
                                                           BatchTables bt, uint8_t* __restrict__ d_out)
 {
-	const uint32_t c = blockIdx.x * 4u + (threadIdx.x >> 6);
-	if (c >= bt.n_chunks || (DEV && past_real_chunks(bt, c))) { return; }
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, c);
-	const u64 ustart = prefix[bt.chunk_prefix[u]];
-	const u64 utotal = prefix[bt.chunk_prefix[u + 1]] - ustart;
-	const u64 cap = bt.out_cap[u];
-	if (utotal > cap) { return; }                               // BUF_ERROR unit: output unspecified
-	copy_from_aligned(d_out + bt.out_off[u] + (prefix[c] - ustart), slots + (u64)c * slot_stride, slot_size[c], lane, 64u);
+	const uint32_t lane = threadIdx.x & 63u, w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	uint32_t n = bt.n_chunks;
+	if (DEV) { const uint32_t real = bt.chunk_prefix[bt.n_units]; n = real < n ? real : n; }
+	const uint32_t n_tiles = (n + PLACE_TILE - 1u) / PLACE_TILE;
+	for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+		const uint32_t c0 = t * PLACE_TILE;
+		if (c0 + w >= n) { continue; }
+		const bool in = c0 + lane < n;
+		const u64 my_pre = in ? prefix[c0 + lane] : 0;
+		const uint32_t my_size = in ? slot_size[c0 + lane] : 0u;
+		PlaceUnit pu = place_unit(bt, prefix, 0u, c0 + w);
+		for (uint32_t i = w; i < PLACE_TILE && c0 + i < n; i += 4u) {
+			const uint32_t c = c0 + i;
+			if (c >= pu.end) { pu = place_unit(bt, prefix, pu.u + 1u, c); }   // (chunk_prefix[u + 1] <= c: the search starts there)
+			const uint32_t size = (uint32_t)__builtin_amdgcn_readlane((int)my_size, (int)i);
+			const u64 pre = (u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_pre, (int)i) | ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(my_pre >> 32), (int)i) << 32);
+			if (pu.fits && size) { rd_wave_move(d_out + pu.off + (pre - pu.start), slots + (u64)c * slot_stride, size, lane); }
+		}
+	}
+}
+
+// blocks of concat_slots_kernel that are resident on the current device at once: its grid, asked once per device and instance (a context
+// asks when it is created: never inside a capture). The test hook caps it (0 = no cap), so that a small batch gives a block a second tile.
+static std::atomic<uint32_t> g_place_grid[2][64];
+static std::atomic<int> g_place_cap;
+void set_place_blocks(int n) { g_place_cap.store(n > 0 ? n : 0, std::memory_order_relaxed); }
+uint32_t place_blocks(bool dev)
+{
+	int d = 0, cus = 0, per_cu = 0;
+	if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; }
+	std::atomic<uint32_t>& slot = g_place_grid[dev ? 1 : 0][d >= 0 && d < 64 ? d : 63];
+	uint32_t g = slot.load(std::memory_order_relaxed);
+	if (g == 0) {
+		if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
+		const hipError_t e = dev ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, concat_slots_kernel<true>, 256, 0)
+		                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, concat_slots_kernel<false>, 256, 0);
+		if (e != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 8; }
+		g = (uint32_t)cus * (uint32_t)per_cu;
+		slot.store(g, std::memory_order_relaxed);
+	}
+	return g;
 }
 
 void launch_concat_slots(hipStream_t st, const uint8_t* slots, uint32_t slot_stride, const uint32_t* slot_size,
                          const u64* prefix, const BatchTables& bt, uint8_t* d_out, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
-	if (dev) { hipLaunchKernelGGL(concat_slots_kernel<true>, dim3((bt.n_chunks + 3u) / 4u), dim3(256), 0, st, slots, slot_stride, slot_size, prefix, bt, d_out); }
-	else { hipLaunchKernelGGL(concat_slots_kernel<false>, dim3((bt.n_chunks + 3u) / 4u), dim3(256), 0, st, slots, slot_stride, slot_size, prefix, bt, d_out); }
+	const uint32_t tiles = (bt.n_chunks + PLACE_TILE - 1u) / PLACE_TILE, cap = (uint32_t)g_place_cap.load(std::memory_order_relaxed);
+	uint32_t grid = place_blocks(dev);
+	if (grid > tiles) { grid = tiles; }
+	if (cap && grid > cap) { grid = cap; }
+	if (dev) { hipLaunchKernelGGL(concat_slots_kernel<true>, dim3(grid), dim3(256), 0, st, slots, slot_stride, slot_size, prefix, bt, d_out); }
+	else { hipLaunchKernelGGL(concat_slots_kernel<false>, dim3(grid), dim3(256), 0, st, slots, slot_stride, slot_size, prefix, bt, d_out); }
 }
 
 __global__ __launch_bounds__(256) void finalize_units_kernel(const u64* __restrict__ prefix, BatchTables bt, uint8_t* __restrict__ d_out,
