@@ -118,6 +118,14 @@ __device__ __forceinline__ uint32_t lz_ld32(const uint8_t* base, uint32_t off)
 	const uint32_t* a = reinterpret_cast<const uint32_t*>(base + (off & 0xFFCu));
 	return alignbyte_addr(a[1], a[0], off);
 }
+// The same for the sort's batches, position 64 b + lane: `a4` is the aligned dword that holds it, 64 b + (lane & ~3) -- one address per round of
+// batches, the batch in the read's offset field -- and the lane number is the shift operand: v_alignbyte_b32 reads bits [1:0] of it alone, so no
+// instruction puts the batch's base into it (the compiler cannot know: it made a v_or_b32 per batch)
+__device__ __forceinline__ uint32_t lz_ld32_lane(const uint8_t* a4, uint32_t lane)
+{
+	const uint32_t* a = reinterpret_cast<const uint32_t*>(a4);
+	return alignbyte_addr(a[1], a[0], lane);
+}
 // Common prefix beyond the first 16 (equal) bytes of d[q..] and d[p..]: 16 bytes per step; the result may exceed maxlen
 // (callers clamp).
 __device__ __forceinline__ uint32_t lz_lcp_tail(const uint8_t* d, uint32_t q, uint32_t p, uint32_t maxlen, uint32_t& it)
@@ -212,13 +220,17 @@ __device__ __forceinline__ uint32_t lz_need_bits(uint32_t len) { uint32_t r; asm
 // A position needs the START of its bucket, the end of the bucket in front of it, from `tbl`: u16 per bucket (packed = false), or 12-bit fields,
 // bucket h at bit 12 h (packed = true: the field at bit 12 (h - 1) lies inside the two dwords from (12 (h - 1)) / 32 on -- one read2 and one
 // v_alignbit, which takes its shift modulo 32). The field of bucket 4094 ends in the last dword of the table: the dword after it is read and shifted out.
+// FULL: the chunk has 4096 bytes (the four-wave kernel's full-chunk body; `n` is not read). Every window then has 64 positions, so the window's
+// end, its length `wn` and the range mask need no minimum and no select; only window 0 has a position without a candidate (position 0) and only
+// window 63 has lanes without a key (62 and 63: positions 4094 and 4095), each one scalar test.
 struct LzWin { uint32_t key, o0, shift; u64 tokmask, matchmask; };
-template <bool packed>
+template <bool packed, bool FULL = false>
 __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void* tbl, const uint16_t* s_bucket, uint32_t n, uint32_t lane,
                                               uint32_t wbase, uint32_t entry, LzWin& r)
 {
+	if (FULL) { n = 4096u; }
 	entry = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry); wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);   // (uniform: keeps the walk's bookkeeping on the scalar unit)
-	const uint32_t wend = (wbase + 64u < n) ? wbase + 64u : n;
+	const uint32_t wend = FULL ? wbase + 64u : ((wbase + 64u < n) ? wbase + 64u : n);
 	const uint32_t p = wbase + lane;
 	const LzS1 own = lz_ld_s1(s_data, p);                        // (aligned dword reads: a misaligned read is replayed; bytes 8..15 are read by a second stage)
 	const uint32_t o0 = own.x, o1 = own.y;
@@ -229,9 +241,18 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	// its bucket up, active or not (any 3 bytes hash to a bucket of the table), and an inactive lane's max_len is never used.
 	uint32_t rel;                                                // the next token start, relative to the window (entry < wend here: < 64)
 	asm("s_max_u32 %0, %1, %2\n\ts_sub_u32 %0, %0, %2" : "=&s"(rel) : "s"(entry), "s"(wbase) : "scc");   // (a saturating subtract would go to the vector unit)
-	const uint32_t lo = (wbase == 0 && rel == 0) ? 1u : rel;
-	const uint32_t hi = n > wbase + 2u ? (n - wbase - 2u < 64u ? n - wbase - 2u : 64u) : 0u;                          // lanes [lo, hi)
-	const u64 act = sgpr64((~(u64)0 << lo) & (hi >= 64u ? ~(u64)0 : (((u64)1 << hi) - 1u)));
+	u64 act;
+	if (FULL) {
+		uint32_t lo;                                               // position 0: window 0 alone. The OR itself sets the condition (left to the compiler a compare follows it)
+		asm("s_or_b32 %0, %1, %2\n\ts_cselect_b32 %0, %2, 1" : "=&s"(lo) : "s"(wbase), "s"(rel) : "scc");
+		const uint32_t top = wbase == 4032u ? 0x3FFFFFFFu : 0xFFFFFFFFu;   // lanes 62 and 63 of window 63 are no keys
+		const u64 m = ~(u64)0 << lo;
+		act = sgpr64(((u64)((uint32_t)(m >> 32) & top) << 32) | (uint32_t)m);
+	} else {
+		const uint32_t lo = (wbase == 0 && rel == 0) ? 1u : rel;
+		const uint32_t hi = n > wbase + 2u ? (n - wbase - 2u < 64u ? n - wbase - 2u : 64u) : 0u;                      // lanes [lo, hi)
+		act = sgpr64((~(u64)0 << lo) & (hi >= 64u ? ~(u64)0 : (((u64)1 << hi) - 1u)));
+	}
 	const uint32_t maxlen = (n - p < mask3) ? n - p : mask3;
 	uint32_t s;
 	{
@@ -316,7 +337,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	// The serial loop only decides which candidates are TAKEN; everything else (which positions are literal tokens)
 	// is derived in parallel afterwards.
 	u64 matchmask = 0;
-	const uint32_t wn = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wend - wbase));
+	const uint32_t wn = FULL ? 64u : (uint32_t)__builtin_amdgcn_readfirstlane((int)(wend - wbase));
 	// Every resolved match lane precomputes where the walk goes after taking it: the first stop (match, unresolved or long-pending
 	// position) at or after its end, relative to the window (>= wn leaves it). The scalar walk is then one v_readlane per taken
 	// match; it leaves the asm block on an unresolved or long-pending position (st = 1), which the whole wave resolves. Stops are
@@ -343,19 +364,22 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 		// v_readlane needs 4 wait states after the write of its lane select (mp): on the loop edge the five scalar
 		// instructions in between provide them, on entry the s_nop does. The walk leaves on a stop that is pending (mp < wn), which the
 		// whole wave resolves, or behind the window (mp >= wn): no flag, mp tells.
-		asm volatile(
-			"s_nop 3\n\t"
-			"1:\n\t"
-			"s_bitcmp1_b64 %[pend], %[mp]\n\t"
-			"s_cbranch_scc1 3f\n\t"
-			"s_bitset1_b64 %[mk], %[mp]\n\t"
-			"v_readlane_b32 %[mp], %[J], %[mp]\n\t"
-			"s_cmp_lt_u32 %[mp], %[wn]\n\t"
-			"s_cbranch_scc1 1b\n\t"
+#define LZ_WALK(WN_) \
+			"s_nop 3\n\t" \
+			"1:\n\t" \
+			"s_bitcmp1_b64 %[pend], %[mp]\n\t" \
+			"s_cbranch_scc1 3f\n\t" \
+			"s_bitset1_b64 %[mk], %[mp]\n\t" \
+			"v_readlane_b32 %[mp], %[J], %[mp]\n\t" \
+			"s_cmp_lt_u32 %[mp], " WN_ "\n\t" \
+			"s_cbranch_scc1 1b\n\t" \
 			"3:\n\t"
-			: [mp] "+s"(mp), [mk] "+s"(matchmask)
-			: [pend] "s"(pend), [wn] "s"(wn), [J] "v"(J)
-			: "scc");
+		if (FULL) {                                                // (the window's length is the inline constant 64: no register holds it across the walk)
+			asm volatile(LZ_WALK("64") : [mp] "+s"(mp), [mk] "+s"(matchmask) : [pend] "s"(pend), [J] "v"(J) : "scc");
+		} else {
+			asm volatile(LZ_WALK("%[wn]") : [mp] "+s"(mp), [mk] "+s"(matchmask) : [pend] "s"(pend), [wn] "s"(wn), [J] "v"(J) : "scc");
+		}
+#undef LZ_WALK
 		if (mp < wn) {
 			const uint32_t sL = (uint32_t)__builtin_amdgcn_readlane((int)s, (int)mp);
 			const uint32_t maxL = (uint32_t)__builtin_amdgcn_readlane((int)maxlen, (int)mp);
@@ -479,7 +503,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	matchmask = sgpr64(matchmask);
 	uint32_t mend; asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(mend) : "v"(p + (key >> 12)), "s"(matchmask));   // the mask itself selects: no per-lane bit test
 	const uint32_t reach = wave_incl_scan_max(mend);
-	const u64 range = (~(u64)0 << rel) & (wn >= 64u ? ~(u64)0 : (((u64)1 << wn) - 1u));     // entry <= p < wend, on the scalar unit
+	const u64 range = FULL ? ~(u64)0 << rel : (~(u64)0 << rel) & (wn >= 64u ? ~(u64)0 : (((u64)1 << wn) - 1u));     // entry <= p < wend, on the scalar unit
 	const u64 tokmask = range & (matchmask | __builtin_amdgcn_ballot_w64(reach <= p));
 	const uint32_t wreach = (uint32_t)__builtin_amdgcn_readlane((int)reach, 63);
 	const uint32_t cur = wreach > wend ? wreach : wend;
@@ -726,38 +750,73 @@ static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: L
 // CU-cycle, 5.81 above 96; round 13 in profiles/HISTORY.md and its correction in round 15). Since round 15 the kernel uses 77 (76 since round 17) and runs at eight
 // (7.76): lz_window keeps "candidate k reached 16 bytes" in the lanes instead of four 64-bit masks, and what sort and parse never read waits in the
 // lanes of one vector register (LZ4_PARK below). tests/test_lznt1_resources.py holds all four instances at 80, without spills: an `amdgpu_num_sgpr`
-// limit gets there too, by spilling, which the same test forbids.)
-template <bool serial, bool DEV = false>                         // DEV: as lznt1_chunk_kernel
-__global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
-                                                          uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size, uint16_t* __restrict__ recs)
+// limit gets there too, by spilling, which the same test forbids. 68 since round 18; 72 since round 23, with two bodies behind one branch.)
+// One LDS object, the chunk first (see the kernel above), 20 480 B -> 8 blocks per CU by the LDS. The chunk has no pad: the reads that run past its
+// end (lz_ld128 / lds_ld32 reach up to 16 bytes beyond byte 4095, into the bucket array) and the bytes between n and 4096 only feed
+// (a) keys of positions p with p + 3 <= n, whose fourth byte is masked off, (b) compares whose result is capped by
+// max_len <= n - p (16-byte compares at 8 min(max_len, 16) bits, lz_lcp_tail clamped to max_len; a candidate q < p stops even
+// earlier), (c) the raw chunk's copy, whose dwords past 2 + n land in the slot's slack and are never concatenated.
+// (Declared here, not in the kernel: the kernel owns the one __shared__ object and hands it to whichever of its two bodies runs.)
+struct Lz4Ctl {                                                            // parse state, polled or small
+	u64      tok[64], mat[64];                                             // token / match mask per window
+	uint16_t endc[64];                                                     // parse position after the window
+	uint32_t prog[LZ4_NSEG];                                               // windows finished in segment j (index + 1)
+	uint32_t used[LZ4_NSEG];                                               // entry position the seam in front of segment j was repaired against
+	uint32_t segctr;                                                       // next segment to hand out
+	uint32_t total[2];
+	uint8_t  rep[64];                                                      // the window's match tokens are in the repair area (1) or the speculative one (0)
+};
+struct __attribute__((aligned(16))) Lz4Lds {
+	uint8_t  data[4096];
+	uint16_t bucket[4096];
+	union {
+		uint16_t cnt[LZ_TBL];                                              // after the parse: prefixes and flags (below)
+		struct { uint32_t ends[LZ_TBL * 12u / 32u]; Lz4Ctl ctl; } parse;   // parse: the ends as 12-bit fields, then the control words
+	} t;
+};
+static_assert(LZ_TBL == 4096u, "the pack below hands 16 bucket ends to each of 256 threads");
+static_assert(sizeof(Lz4Lds) <= 20480, "eight blocks per CU");
+static_assert(offsetof(Lz4Lds, t) == offsetof(Lz4Lds, bucket) + sizeof(Lz4Lds::bucket) && sizeof(Lz4Lds::bucket) + sizeof(Lz4Lds::t) == LZ_TBL * sizeof(uint32_t),
+              "the sort's count words (one dword per bucket) lie over the bucket array and the union behind it");
+// What sort and parse never read -- the slot's and the size index's addresses, the chunk and wave numbers -- waits in the lanes of one vector
+// register until the parse is over: held in scalar registers across it these six cost the kernel its eighth block (see above). Lanes 6 to 10
+// carry what the kernel hands to its body: the chunk's address, the record's address and the chunk's length (lz4_chunk_body).
+// LZ4_FETCH reads a lane back; the empty asm in front of it redefines the register there, so the read cannot be moved up to the entry again.
+#define LZ4_PARK(i, v) { park = lane == (i) ? (uint32_t)(v) : park; }
+#define LZ4_FETCH(i) ({ asm volatile("" : "+v"(park)); (uint32_t)__builtin_amdgcn_readlane((int)park, (int)(i)); })
+// FULL slots of the sort: slot i of a wave's part is batch pb0 + i, in the round of eight from i & ~7 on. A round runs in the waves whose part is
+// longer than its first slot; slot i needs the test "batch inside my part" only if one of those parts ends at or before i. (With 15 / 24 / 25
+// batches: slot 15 alone, where wave 0's part has ended.) And in a full chunk the only positions without a key are lanes 62 and 63 of batch 63,
+// the last slot of the last part.
+__host__ __device__ constexpr bool lz4_slot_sure(uint32_t i)
 {
-	// One object, the chunk first (see the kernel above), 20 480 B -> 8 blocks per CU by the LDS. The chunk has no pad: the reads that run past its
-	// end (lz_ld128 / lds_ld32 reach up to 16 bytes beyond byte 4095, into the bucket array) and the bytes between n and 4096 only feed
-	// (a) keys of positions p with p + 3 <= n, whose fourth byte is masked off, (b) compares whose result is capped by
-	// max_len <= n - p (16-byte compares at 8 min(max_len, 16) bits, lz_lcp_tail clamped to max_len; a candidate q < p stops even
-	// earlier), (c) the raw chunk's copy, whose dwords past 2 + n land in the slot's slack and are never concatenated.
-	struct Ctl {                                                           // parse state, polled or small
-		u64      tok[64], mat[64];                                         // token / match mask per window
-		uint16_t endc[64];                                                 // parse position after the window
-		uint32_t prog[LZ4_NSEG];                                           // windows finished in segment j (index + 1)
-		uint32_t used[LZ4_NSEG];                                           // entry position the seam in front of segment j was repaired against
-		uint32_t segctr;                                                   // next segment to hand out
-		uint32_t total[2];
-		uint8_t  rep[64];                                                  // the window's match tokens are in the repair area (1) or the speculative one (0)
-	};
-	struct __attribute__((aligned(16))) Lds {
-		uint8_t  data[4096];
-		uint16_t bucket[4096];
-		union {
-			uint16_t cnt[LZ_TBL];                                          // after the parse: prefixes and flags (below)
-			struct { uint32_t ends[LZ_TBL * 12u / 32u]; Ctl ctl; } parse;   // parse: the ends as 12-bit fields, then the control words
-		} t;
-	};
-	static_assert(LZ_TBL == 4096u, "the pack below hands 16 bucket ends to each of 256 threads");
-	static_assert(sizeof(Lds) <= 20480, "eight blocks per CU");
-	static_assert(offsetof(Lds, t) == offsetof(Lds, bucket) + sizeof(Lds::bucket) && sizeof(Lds::bucket) + sizeof(Lds::t) == LZ_TBL * sizeof(uint32_t),
-	              "the sort's count words (one dword per bucket) lie over the bucket array and the union behind it");
-	__shared__ Lds L;
+	const uint32_t j0 = i & ~7u, l0 = LZ4_P1, l1 = LZ4_P2 - LZ4_P1, l2 = 64u - LZ4_P2;
+	return !(l0 > j0 && l0 <= i) && !(l1 > j0 && l1 <= i) && !(l2 > j0 && l2 <= i);
+}
+#define LZ4_LAST_SLOT (64u - LZ4_P2 - 1u)
+// The kernel's body from section A on. FULL: the chunk has 4096 bytes and `n` is that literal everywhere (the argument is not read): 827 744 of the
+// headline's 827 936 chunks. The other body is the code for any n; the kernel takes one wave-uniform branch between them.
+template <bool serial, bool DEV, bool FULL>
+__device__ __forceinline__ void lz4_chunk_body(Lz4Lds& L, uint32_t park, const uint32_t tid, const uint32_t lane, uint32_t wv)
+{
+	// (the chunk's address, its length and the record's address arrive in the parked lanes too. The kernel's branch is structurized with the
+	// divergent code inside the bodies: the compiler lays the body for any n in front and the full-chunk body behind it under a 64-bit flag, so as
+	// scalar arguments these five were live across the whole of the first body, and with them the kernel had 82 scalar registers: seven blocks.
+	// From the lanes it has 72.)
+	// (as GLOBAL pointers: a pointer rebuilt from integers has lost its address space, and every access through it would be a FLAT one -- see section D)
+	typedef __attribute__((address_space(1))) const uint8_t  gc_u8;
+	typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+	typedef __attribute__((address_space(1))) const u32x4    gc_u4;
+	typedef __attribute__((address_space(1))) const uint32_t gc_u32;
+	typedef __attribute__((address_space(1))) uint16_t       g_u16;
+	gc_u8* __restrict__ const src = (gc_u8*)((uintptr_t)LZ4_FETCH(6) | ((uintptr_t)LZ4_FETCH(7) << 32));
+	g_u16* __restrict__ const rec = (g_u16*)((uintptr_t)LZ4_FETCH(8) | ((uintptr_t)LZ4_FETCH(9) << 32));
+	const uint32_t n = FULL ? 4096u : LZ4_FETCH(10);
+	// (an assembler comment at both ends of each body, no instruction: it tells the two copies apart in the listing, where the census of a body is taken)
+#define LZ4_BODY_EDGE(what) { if (FULL) { asm volatile("; lznt1 full-chunk body " what); } else { asm volatile("; lznt1 any-length body " what); } }
+	LZ4_BODY_EDGE("begins")
+	typedef Lz4Ctl Ctl;
+	uint32_t c;                                                            // (re-fetched from the parked lanes behind the parse, like wv)
 	uint32_t* const s_cw = reinterpret_cast<uint32_t*>(L.bucket);         // [LZ_TBL] the sort's count words (section B)
 	uint8_t* const s_data = L.data; uint16_t* const s_cnt = L.t.cnt; uint16_t* const s_bucket = L.bucket;
 	Ctl& C = L.t.parse.ctl;
@@ -768,28 +827,6 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	uint16_t* const s_flagpos = s_cnt + 128;                               // [512] byte position of group g's flag byte
 	uint32_t* const s_flagacc = reinterpret_cast<uint32_t*>(s_cnt + 640);  // [512] its bits (1280 + 2048 B <= the ends' 6144 B)
 
-	const uint32_t tid = threadIdx.x, lane = tid & 63u;
-	uint32_t c, wv;                                                        // (not const: re-fetched from the parked lanes behind the parse)
-	c = blockIdx.x; wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-	if (DEV && past_real_chunks(bt, c)) { if (tid == 0) { slot_size[c] = 0; } return; }
-	// What sort and parse never read -- the slot's and the size index's addresses, the chunk and wave numbers -- waits in the lanes of one vector
-	// register until the parse is over: held in scalar registers across it these six cost the kernel its eighth block (see above).
-	// LZ4_FETCH reads a lane back; the empty asm in front of it redefines the register there, so the read cannot be moved up to the entry again.
-	uint32_t park = 0;
-#define LZ4_PARK(i, v) { park = lane == (i) ? (uint32_t)(v) : park; }
-#define LZ4_FETCH(i) ({ asm volatile("" : "+v"(park)); (uint32_t)__builtin_amdgcn_readlane((int)park, (int)(i)); })
-	LZ4_PARK(0, (uintptr_t)slots) LZ4_PARK(1, (uintptr_t)slots >> 32) LZ4_PARK(2, (uintptr_t)slot_size) LZ4_PARK(3, (uintptr_t)slot_size >> 32)
-	LZ4_PARK(4, c) LZ4_PARK(5, wv)
-	asm volatile("" : "+v"(park));                                         // (and the selects that fill it stay here: left alone they sink to the first read)
-	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, c);
-	const u64 coff = (u64)(c - bt.chunk_prefix[u]) * 4096u;
-	const u64 left = bt.in_len[u] - coff;
-	const uint32_t n = left < 4096u ? (uint32_t)left : 4096u;
-	const uint8_t* __restrict__ src = d_in + bt.in_off[u] + coff;
-	// the window's match tokens, in order: area 0 is written by the speculative parse of the window's own segment, area 1 by a seam
-	// repair or the cascade (s_rep says which holds). Two areas, because the repairing wave would otherwise race the speculative
-	// wave's global stores to the same words: its progress word in LDS does not wait for them.
-	uint16_t* __restrict__ rec = recs + (u64)c * (LZNT1_REC / sizeof(uint16_t));
 
 #ifdef LZ4_PROFILE
 	uint32_t z_prev; asm volatile("v_mov_b32 %0, %1" : "=v"(z_prev) : "s"((uint32_t)__builtin_readcyclecounter()));   // (the low dword: a phase is far below 2^32 cycles)
@@ -803,7 +840,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	// ---- A. stage the chunk, clear the count table (all waves) ------------------------------------------------------
 	{
 		const uint32_t nvec = (((uintptr_t)src & 15u) == 0) ? (n & ~15u) : 0u;
-		for (uint32_t i = tid * 16u; i < nvec; i += 4096u) { *reinterpret_cast<uint4*>(s_data + i) = *reinterpret_cast<const uint4*>(src + i); }
+		for (uint32_t i = tid * 16u; i < nvec; i += 4096u) { *reinterpret_cast<u32x4*>(s_data + i) = *(gc_u4*)(src + i); }
 		for (uint32_t i = nvec + tid; i < n; i += 256u) { s_data[i] = src[i]; }
 		for (uint32_t i = n + tid; i < 4096u; i += 256u) { s_data[i] = 0; }
 		for (uint32_t i = tid * 4u; i < LZ_TBL; i += 1024u) { *reinterpret_cast<uint4*>(s_cw + i) = make_uint4(0, 0, 0, 0); }
@@ -841,15 +878,25 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 		for (uint32_t i = 0; i < LZ4_PMAX; ++i) { hr[i] = 0; }
 		// B1. rounds of 8 batches: their atomics are issued back to back (DS operations of a wave execute in order; the wavefront-scope
 		// form keeps the compiler from waiting for each one). An inactive lane's rank stays 0. This is the ONLY place that hashes a position.
+		// FULL: a slot that is surely a batch of the wave's part carries no predicate, so its atomic stands under no exec-mask bracket and its `old` is not
+		// zeroed first; batch 63 keeps the position test (lanes 62 and 63). The atomic's operand is made once per wave, in a register of its own
+		// (left to the compiler it is moved there again in every batch).
+		uint32_t inc = 1u << fsh;
+		if (FULL) { asm("v_mov_b32 %0, %1" : "=v"(inc) : "s"(1u << fsh)); }
 		#pragma unroll
 		for (uint32_t j0 = 0; j0 < LZ4_PMAX; j0 += 8u) {
 			if (pb0 + j0 < pb1) {
 				uint32_t h[8], old[8];
 				#pragma unroll
-				for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { h[j] = lz_hash(lz_ld32(s_data, (pb0 + j0 + j) * 64u + lane) & 0xFFFFFFu); } }
+				for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { h[j] = lz_hash(lz_ld32_lane(s_data + (pb0 + j0) * 64u + (lane & 0x3Cu) + 64u * j, lane) & 0xFFFFFFu); } }   // (batches below 64: inside the chunk)
 				#pragma unroll
 				for (uint32_t j = 0; j < 8u; ++j) {
-					if (j0 + j < LZ4_PMAX) { const uint32_t b = pb0 + j0 + j; old[j] = lz_ordered_add<serial>(s_cw + h[j], 1u << fsh, b < pb1 && b * 64u + lane + 2u < n, lane); }
+					if (j0 + j < LZ4_PMAX) {
+						const uint32_t b = pb0 + j0 + j;
+						const bool act = FULL ? (lz4_slot_sure(j0 + j) || b < pb1) && (j0 + j != LZ4_LAST_SLOT || b * 64u + lane + 2u < n)
+						                      : b < pb1 && b * 64u + lane + 2u < n;
+						old[j] = lz_ordered_add<serial>(s_cw + h[j], inc, act, lane);
+					}
 				}
 				#pragma unroll
 				for (uint32_t j = 0; j < 8u; ++j) { if (j0 + j < LZ4_PMAX) { hr[j0 + j] = (h[j] << 12) | ((old[j] >> fsh) & fm); } }
@@ -933,7 +980,9 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 				for (uint32_t j = 0; j < 8u; ++j) {
 					if (j0 + j < LZ4_PMAX) {
 						const uint32_t b = pb0 + j0 + j, p = b * 64u + lane;
-						if (b < pb1 && p + 2u < n) { s_bucket[st[j] + (hr[j0 + j] & 0xFFFu)] = (uint16_t)p; }
+						const bool act = FULL ? (lz4_slot_sure(j0 + j) || b < pb1) && (j0 + j != LZ4_LAST_SLOT || p + 2u < n)   // (B1's predicate)
+						                      : b < pb1 && p + 2u < n;
+						if (act) { s_bucket[st[j] + (hr[j0 + j] & 0xFFFu)] = (uint16_t)p; }
 					}
 				}
 			}
@@ -950,13 +999,13 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	// (The lanes that record are the match mask itself, as the exec mask: `(mask >> lane) & 1` is two ANDs with the lane's bit and a 64-bit
 	// compare in every lane. The record's base is a scalar pointer -- w_ and a_ are uniform -- so a lane adds a 32-bit offset to it.)
 #define LZ4_WINDOW(w_, entry_, cur_out, a_) { \
-		const uint32_t wb_ = (w_) * 64u; const uint32_t we_ = (wb_ + 64u < n) ? wb_ + 64u : n; \
+		const uint32_t wb_ = (w_) * 64u; const uint32_t we_ = FULL ? wb_ + 64u : ((wb_ + 64u < n) ? wb_ + 64u : n); \
 		if ((entry_) >= we_) { if (lane == 0) { s_tok[w_] = 0; s_mat[w_] = 0; } cur_out = (entry_); } \
 		else { \
-			LzWin r_; cur_out = lz_window<true>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); \
+			LzWin r_; cur_out = lz_window<true, FULL>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); \
 			if (__builtin_amdgcn_inverse_ballot_w64(r_.matchmask)) { \
 				const uint32_t p_ = wb_ + lane, best_ = r_.key >> 12; \
-				uint16_t* __restrict__ const recw_ = rec + ((a_) * 64u + (w_)) * LZ4_MAXM; \
+				g_u16* __restrict__ const recw_ = rec + ((a_) * 64u + (w_)) * LZ4_MAXM; \
 				recw_[popc_below(r_.matchmask)] = (uint16_t)(((p_ - (4095u - (r_.key & 0xFFFu)) - 1u) << r_.shift) | (best_ - 3u)); \
 			} \
 			if (lane == 0) { s_tok[w_] = r_.tokmask; s_mat[w_] = r_.matchmask; } \
@@ -1056,7 +1105,7 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 #ifndef LZ4_PROBE_EMIT
 	{
 		const uint32_t info = wl0 < w1 ? (uint32_t)__popcll(matv) | ((uint32_t)s_rep[wl0] << 8) : 0u;
-		const uint32_t* __restrict__ const rec32 = reinterpret_cast<const uint32_t*>(rec);
+		gc_u32* __restrict__ const rec32 = (gc_u32*)rec;
 		uint32_t v[3]; bool ld[3];
 		#pragma unroll
 		for (uint32_t k = 0; k < 3u; ++k) {
@@ -1138,8 +1187,38 @@ __global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __rest
 	if (tid == 0) { *szp = total; }
 	LZ4_T(18)
 	LZ4_TEND
+	LZ4_BODY_EDGE("ends")
+#undef LZ4_BODY_EDGE
 #undef LZ4_WINDOW
 #undef LZ4_UNI
+}
+
+template <bool serial, bool DEV = false>                         // DEV: as lznt1_chunk_kernel
+__global__ __launch_bounds__(256) void lznt1_chunk4_kernel(const uint8_t* __restrict__ d_in, BatchTables bt,
+                                                          uint8_t* __restrict__ slots, uint32_t* __restrict__ slot_size, uint16_t* __restrict__ recs)
+{
+	__shared__ Lz4Lds L;
+	const uint32_t tid = threadIdx.x, lane = tid & 63u;
+	const uint32_t c = blockIdx.x, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+	if (DEV && past_real_chunks(bt, c)) { if (tid == 0) { slot_size[c] = 0; } return; }
+	uint32_t park = 0;
+	LZ4_PARK(0, (uintptr_t)slots) LZ4_PARK(1, (uintptr_t)slots >> 32) LZ4_PARK(2, (uintptr_t)slot_size) LZ4_PARK(3, (uintptr_t)slot_size >> 32)
+	LZ4_PARK(4, c) LZ4_PARK(5, wv)
+	const uint32_t u = unit_of_chunk(bt.chunk_prefix, bt.n_units, c);
+	const u64 coff = (u64)(c - bt.chunk_prefix[u]) * 4096u;
+	const u64 left = bt.in_len[u] - coff;
+	const uint32_t n = left < 4096u ? (uint32_t)left : 4096u;
+	const uint8_t* __restrict__ src = d_in + bt.in_off[u] + coff;
+	// the window's match tokens, in order: area 0 is written by the speculative parse of the window's own segment, area 1 by a seam
+	// repair or the cascade (s_rep says which holds). Two areas, because the repairing wave would otherwise race the speculative
+	// wave's global stores to the same words: its progress word in LDS does not wait for them.
+	uint16_t* __restrict__ rec = recs + (u64)c * (LZNT1_REC / sizeof(uint16_t));
+	// Two bodies, one wave-uniform branch: every chunk of a unit but its last has 4096 bytes, and with that literal for n the window prologue, the
+	// sort's predicates and the geometry are constants. Only a unit's last chunk can take the other body, the code for any n.
+	LZ4_PARK(6, (uintptr_t)src) LZ4_PARK(7, (uintptr_t)src >> 32) LZ4_PARK(8, (uintptr_t)rec) LZ4_PARK(9, (uintptr_t)rec >> 32) LZ4_PARK(10, n)
+	asm volatile("" : "+v"(park));                                         // (and the selects that fill it stay here: left alone they sink to the first read)
+	if ((uint32_t)__builtin_amdgcn_readfirstlane((int)n) == 4096u) { lz4_chunk_body<serial, DEV, true>(L, park, tid, lane, wv); }
+	else { lz4_chunk_body<serial, DEV, false>(L, park, tid, lane, wv); }
 #undef LZ4_PARK
 #undef LZ4_FETCH
 }
