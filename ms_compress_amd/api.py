@@ -11,6 +11,7 @@ GPU is visible they raise.
 import contextlib
 import ctypes as C
 import os
+import re
 import weakref
 
 import numpy as np
@@ -24,42 +25,146 @@ MSCOMP_OK, MSCOMP_ERRNO, MSCOMP_ARG_ERROR, MSCOMP_DATA_ERROR, MSCOMP_MEM_ERROR, 
 FORMATS = {"lznt1": MSCOMP_LZNT1, "xpress": MSCOMP_XPRESS, "xpress_huff": MSCOMP_XPRESS_HUFF}
 CHUNK = {MSCOMP_LZNT1: 4096, MSCOMP_XPRESS: 65536, MSCOMP_XPRESS_HUFF: 65536}
 
-EXPORTS = [  # every symbol include/mscomp_amd.h declares (tests check the library exports all of them)
-    "ms_compress", "ms_max_compressed_size",
-    "lznt1_compress", "lznt1_max_compressed_size", "xpress_compress", "xpress_max_compressed_size",
-    "xpress_huff_compress", "xpress_huff_max_compressed_size",
-    "mscomp_amd_ctx_create", "mscomp_amd_ctx_destroy", "mscomp_amd_plan_create", "mscomp_amd_plan_destroy",
-    "mscomp_amd_plan_execute", "mscomp_amd_compress_batch", "mscomp_amd_profile_enable", "mscomp_amd_profile_read",
-    "mscomp_amd_plan_layout", "mscomp_amd_compact_batch",
-    "ms_inflate_init", "ms_inflate", "ms_inflate_end", "lznt1_inflate_init", "lznt1_inflate", "lznt1_inflate_end",
-    "ms_deflate_init", "ms_deflate", "ms_deflate_end", "lznt1_deflate_init", "lznt1_deflate", "lznt1_deflate_end",
-    "xpress_deflate_init", "xpress_deflate", "xpress_deflate_end", "xpress_inflate_init", "xpress_inflate", "xpress_inflate_end",
-    "ms_decompress", "lznt1_decompress", "xpress_decompress", "xpress_huff_decompress", "mscomp_amd_plan_create_decompress", "mscomp_amd_decompress_batch",
-    "mscomp_amd_version", "mscomp_amd_debug_xpress_matches", "mscomp_amd_debug_huff_lengths", "mscomp_amd_debug_huff_lengths_slow", "mscomp_amd_debug_lds_lane_order", "mscomp_amd_debug_alignbyte", "mscomp_amd_debug_set_xpress_emit", "mscomp_amd_debug_set_lznt1", "mscomp_amd_debug_set_place_blocks", "mscomp_amd_debug_set_serial_atomics", "mscomp_amd_compress_units_host", "mscomp_amd_decompress_units_host", "mscomp_amd_host_pool_release", "mscomp_amd_debug_set_finder", "mscomp_amd_debug_set_one_shot", "mscomp_amd_debug_set_xpress_decoder", "mscomp_amd_debug_lzg_open", "mscomp_amd_set_lznt1_sa_dict", "mscomp_amd_get_lznt1_sa_dict", "mscomp_amd_ctx_set_lznt1_sa_dict", "mscomp_amd_debug_hooks_enabled", "mscomp_amd_debug_lzd_walked", "mscomp_amd_debug_decode_modes",
-    "mscomp_amd_plan_create_size", "mscomp_amd_plan_execute_size", "mscomp_amd_decompressed_size_batch",
-    "mscomp_amd_plan_create_decompress_dev", "mscomp_amd_plan_execute_dev", "mscomp_amd_layout_dev",
-    "mscomp_amd_plan_create_compress_dev", "mscomp_amd_plan_layout_dev",
-    "mscomp_amd_plan_create_size_dev", "mscomp_amd_plan_execute_size_dev", "mscomp_amd_compact_dev",
-    "mscomp_amd_plan_create_decompress_dev_ex", "mscomp_amd_plan_create_size_dev_ex", "mscomp_amd_debug_plan_paths",
-    "mscomp_amd_blocks_create", "mscomp_amd_blocks_destroy", "mscomp_amd_blocks_bound", "mscomp_amd_blocks_compress", "mscomp_amd_blocks_decompress",
-    "mscomp_amd_plan_create_crc_dev", "mscomp_amd_plan_execute_crc_dev", "mscomp_amd_blocks_crc", "mscomp_amd_blocks_check",
-    "mscomp_amd_blocks_salvage",
-    "mscomp_amd_reader_create", "mscomp_amd_reader_destroy", "mscomp_amd_reader_read", "mscomp_amd_reader_counts",
-    "mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_write", "mscomp_amd_writer_counts",
-    "mscomp_amd_writer_resize", "mscomp_amd_res_crc_dev",
-    "mscomp_amd_splicer_create", "mscomp_amd_splicer_destroy", "mscomp_amd_splicer_splice",
-    "mscomp_amd_splicer_create_extents", "mscomp_amd_splicer_splice_extents",
-    "mscomp_amd_deduper_create", "mscomp_amd_deduper_destroy", "mscomp_amd_deduper_dedup",
-    "mscomp_amd_deduper_create_diff", "mscomp_amd_deduper_diff",
-    "mscomp_amd_deduper_create_match", "mscomp_amd_deduper_match",
-    "mscomp_amd_deduper_create_repair", "mscomp_amd_deduper_repair",
-    "mscomp_amd_transcoder_create", "mscomp_amd_transcoder_destroy", "mscomp_amd_transcoder_transcode", "mscomp_amd_transcoder_counts",
-    "mscomp_amd_syncer_create", "mscomp_amd_syncer_destroy", "mscomp_amd_syncer_sync", "mscomp_amd_syncer_counts",
-    "mscomp_amd_digester_create", "mscomp_amd_digester_destroy", "mscomp_amd_digester_blocks", "mscomp_amd_digester_check",
-    "mscomp_amd_syncer_create_digest", "mscomp_amd_syncer_sync_digest",
-    "mscomp_amd_parity_create", "mscomp_amd_parity_destroy", "mscomp_amd_parity_bound", "mscomp_amd_parity_build", "mscomp_amd_parity_rebuild",
-    "mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report",
-]
+# The C ABI, once: every function include/mscomp_amd.h declares, in its order, as "return type:argument types" in the codes of _CODES
+# below (a number repeats the letter before it: "v4" is "vvvv"). tests/test_binding.py holds every entry to the header's prototype.
+SIGNATURES = {
+    "ms_compress":                              "i:ivzvZ",
+    "ms_max_compressed_size":                   "z:iz",
+    "lznt1_compress":                           "i:vzvZ",
+    "lznt1_max_compressed_size":                "z:z",
+    "xpress_compress":                          "i:vzvZ",
+    "xpress_max_compressed_size":               "z:z",
+    "xpress_huff_compress":                     "i:vzvZ",
+    "xpress_huff_max_compressed_size":          "z:z",
+    "ms_decompress":                            "i:ivzvZ",
+    "lznt1_decompress":                         "i:vzvZ",
+    "xpress_decompress":                        "i:vzvZ",
+    "xpress_huff_decompress":                   "i:vzvZ",
+    "ms_deflate_init":                          "i:iv",
+    "ms_deflate":                               "i:vi",
+    "ms_deflate_end":                           "i:v",
+    "lznt1_deflate_init":                       "i:v",
+    "lznt1_deflate":                            "i:vi",
+    "lznt1_deflate_end":                        "i:v",
+    "xpress_deflate_init":                      "i:v",
+    "xpress_deflate":                           "i:vi",
+    "xpress_deflate_end":                       "i:v",
+    "xpress_inflate_init":                      "i:v",
+    "xpress_inflate":                           "i:v",
+    "xpress_inflate_end":                       "i:v",
+    "ms_inflate_init":                          "i:iv",
+    "ms_inflate":                               "i:v",
+    "ms_inflate_end":                           "i:v",
+    "lznt1_inflate_init":                       "i:v",
+    "lznt1_inflate":                            "i:v",
+    "lznt1_inflate_end":                        "i:v",
+    "mscomp_amd_ctx_create":                    "i:ivH",
+    "mscomp_amd_ctx_destroy":                   "-:v",
+    "mscomp_amd_plan_create":                   "i:vizv4H",
+    "mscomp_amd_plan_destroy":                  "-:v",
+    "mscomp_amd_plan_execute":                  "i:v5",
+    "mscomp_amd_compress_units_host":           "i:iivzv6",
+    "mscomp_amd_decompress_units_host":         "i:iivzv6",
+    "mscomp_amd_host_pool_release":             "-:",
+    "mscomp_amd_compress_batch":                "i:vizv8",
+    "mscomp_amd_plan_create_decompress":        "i:vizv4H",
+    "mscomp_amd_decompress_batch":              "i:vizv8",
+    "mscomp_amd_plan_create_size":              "i:vizvvvH",
+    "mscomp_amd_plan_execute_size":             "i:v5",
+    "mscomp_amd_decompressed_size_batch":       "i:vizv7",
+    "mscomp_amd_plan_create_decompress_dev":    "i:vizqqH",
+    "mscomp_amd_plan_execute_dev":              "i:v9",
+    "mscomp_amd_layout_dev":                    "i:vzvqv",
+    "mscomp_amd_plan_create_size_dev":          "i:vizqH",
+    "mscomp_amd_plan_execute_size_dev":         "i:v8",
+    "mscomp_amd_plan_create_decompress_dev_ex": "i:vizqquH",
+    "mscomp_amd_plan_create_size_dev_ex":       "i:vizquH",
+    "mscomp_amd_plan_create_compress_dev":      "i:vizqqH",
+    "mscomp_amd_plan_layout_dev":               "i:vizvqvv",
+    "mscomp_amd_plan_layout":                   "q:izvqvv",
+    "mscomp_amd_compact_batch":                 "i:vzv6",
+    "mscomp_amd_compact_dev":                   "i:vzvvvqvqv",
+    "mscomp_amd_plan_create_crc_dev":           "i:vzqH",
+    "mscomp_amd_plan_execute_crc_dev":          "i:v6",
+    "mscomp_amd_blocks_create":                 "i:viuzquH",
+    "mscomp_amd_blocks_destroy":                "-:v",
+    "mscomp_amd_blocks_bound":                  "q:v",
+    "mscomp_amd_blocks_compress":               "i:v5qvvv",
+    "mscomp_amd_blocks_decompress":             "i:vvqv9",
+    "mscomp_amd_blocks_crc":                    "i:v7",
+    "mscomp_amd_blocks_check":                  "i:v9",
+    "mscomp_amd_blocks_salvage":                "i:vvqv13",
+    "mscomp_amd_reader_create":                 "i:viuzqzquH",
+    "mscomp_amd_reader_destroy":                "-:v",
+    "mscomp_amd_reader_read":                   "i:vvqv10",
+    "mscomp_amd_reader_counts":                 "i:vU",
+    "mscomp_amd_writer_create":                 "i:viuzqzquH",
+    "mscomp_amd_writer_destroy":                "-:v",
+    "mscomp_amd_writer_write":                  "i:vvqv8qv5",
+    "mscomp_amd_writer_counts":                 "i:vU",
+    "mscomp_amd_writer_resize":                 "i:vvqv6qv5",
+    "mscomp_amd_splicer_create":                "i:vuuzquH",
+    "mscomp_amd_splicer_destroy":               "-:v",
+    "mscomp_amd_splicer_splice":                "i:vBvvqv5",
+    "mscomp_amd_splicer_create_extents":        "i:vuuzzquH",
+    "mscomp_amd_splicer_splice_extents":        "i:vBvvvqv5",
+    "mscomp_amd_deduper_create":                "i:vuuzquH",
+    "mscomp_amd_deduper_destroy":               "-:v",
+    "mscomp_amd_deduper_dedup":                 "i:vBv5",
+    "mscomp_amd_deduper_create_diff":           "i:vuzquH",
+    "mscomp_amd_deduper_diff":                  "i:vBBv8",
+    "mscomp_amd_deduper_create_match":          "i:vuuzqquH",
+    "mscomp_amd_deduper_match":                 "i:vBBv7",
+    "mscomp_amd_deduper_create_repair":         "i:vuuzquH",
+    "mscomp_amd_deduper_repair":                "i:vBHv6",
+    "mscomp_amd_transcoder_create":             "i:viuiuzqqquH",
+    "mscomp_amd_transcoder_destroy":            "-:v",
+    "mscomp_amd_transcoder_transcode":          "i:vvqv5qv4",
+    "mscomp_amd_transcoder_counts":             "i:vU",
+    "mscomp_amd_syncer_create":                 "i:viuzqzqquH",
+    "mscomp_amd_syncer_destroy":                "-:v",
+    "mscomp_amd_syncer_sync":                   "i:vBv11",
+    "mscomp_amd_syncer_counts":                 "i:vU",
+    "mscomp_amd_digester_create":               "i:vuzquH",
+    "mscomp_amd_digester_destroy":              "-:v",
+    "mscomp_amd_digester_blocks":               "i:v6",
+    "mscomp_amd_digester_check":                "i:v9",
+    "mscomp_amd_syncer_create_digest":          "i:vuzqzqquH",
+    "mscomp_amd_syncer_sync_digest":            "i:vBv12",
+    "mscomp_amd_parity_create":                 "i:vuquuuH",
+    "mscomp_amd_parity_destroy":                "-:v",
+    "mscomp_amd_parity_bound":                  "i:vQ",
+    "mscomp_amd_parity_build":                  "i:vBvqv5",
+    "mscomp_amd_parity_rebuild":                "i:vBvvqv5qv4",
+    "mscomp_amd_res_crc_dev":                   "i:vuzqv5",
+    "mscomp_amd_profile_enable":                "-:vi",
+    "mscomp_amd_profile_read":                  "i:v4i",
+    "mscomp_amd_debug_xpress_matches":          "i:vvzuivv",
+    "mscomp_amd_debug_huff_lengths":            "i:vvzv",
+    "mscomp_amd_debug_huff_lengths_slow":       "i:vvzv",
+    "mscomp_amd_debug_hooks_enabled":           "i:",
+    "mscomp_amd_debug_set_xpress_emit":         "-:i",
+    "mscomp_amd_set_lznt1_sa_dict":             "-:i",
+    "mscomp_amd_get_lznt1_sa_dict":             "i:",
+    "mscomp_amd_ctx_set_lznt1_sa_dict":         "i:vi",
+    "mscomp_amd_debug_set_xpress_decoder":      "-:i",
+    "mscomp_amd_debug_lzg_open":                "i:vqv",
+    "mscomp_amd_debug_set_finder":              "-:i",
+    "mscomp_amd_debug_set_one_shot":            "-:i",
+    "mscomp_amd_debug_set_lznt1":               "-:i",
+    "mscomp_amd_debug_set_place_blocks":        "-:i",
+    "mscomp_amd_debug_lzd_walked":              "u:v",
+    "mscomp_amd_debug_decode_modes":            "i:vvz",
+    "mscomp_amd_debug_plan_paths":              "i:vU",
+    "mscomp_amd_debug_scratch_names":           "i:Si",
+    "mscomp_amd_debug_scratch_poison":          "i:ivii",
+    "mscomp_amd_debug_scratch_report":          "i:iviRi",
+    "mscomp_amd_debug_lds_lane_order":          "u:vu4",
+    "mscomp_amd_debug_alignbyte":               "u:vu",
+    "mscomp_amd_debug_set_serial_atomics":      "-:i",
+    "mscomp_amd_version":                       "s:",
+}
+EXPORTS = list(SIGNATURES)  # every symbol include/mscomp_amd.h declares (tests check the library exports all of them)
 MSCOMP_AMD_SPLICE_SRC_MAX = 4
 MSCOMP_AMD_SPLICE_ROW_TILE = 1024                              # rows of the new table per workgroup of splice_extents' row passes
 MSCOMP_AMD_SYNC_TILE = 4096                                    # positions per wave of a syncer's scan: its seams
@@ -80,6 +185,19 @@ class BlocksView(C.Structure):
     """mscomp_amd_blocks_view: one source container of a splice, as device addresses"""
     _fields_ = [("d_packed", C.c_void_p), ("packed_len", C.c_uint64), ("d_block_first", C.c_void_p), ("d_block_off", C.c_void_p),
                 ("d_res_len", C.c_void_p), ("d_block_crc", C.c_void_p), ("n_res", C.c_uint64), ("n_blocks_table", C.c_uint64)]
+
+
+# the type codes of SIGNATURES: scalars (int and the enums; size_t; uint64_t; uint32_t), void and const char* as return types, an untyped
+# pointer (lower case), and the typed pointers a caller passes a ctypes array, structure or byref() for (upper case)
+_CODES = {"i": C.c_int, "z": C.c_size_t, "q": C.c_uint64, "u": C.c_uint32, "-": None, "s": C.c_char_p, "v": C.c_void_p,
+          "H": C.POINTER(C.c_void_p), "B": C.POINTER(BlocksView), "R": C.POINTER(ScratchRec), "U": C.POINTER(C.c_uint32),
+          "Q": C.POINTER(C.c_uint64), "S": C.POINTER(C.c_char_p), "Z": C.POINTER(C.c_size_t)}
+
+
+def signature(name):
+    """(restype, argtypes) of an export, as ctypes classes, from SIGNATURES"""
+    ret, _, args = SIGNATURES[name].partition(":")
+    return _CODES[ret], [_CODES[c] for c, n in re.findall(r"(\D)(\d*)", args) for _ in range(int(n or 1))]
 
 
 class MSCompError(RuntimeError):
@@ -104,238 +222,10 @@ def load_library():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    one_shot = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
-    lib.ms_compress.argtypes = [C.c_int] + one_shot
-    lib.ms_compress.restype = C.c_int
-    lib.ms_max_compressed_size.argtypes = [C.c_int, C.c_size_t]
-    lib.ms_max_compressed_size.restype = C.c_size_t
-    for name in ("lznt1", "xpress", "xpress_huff"):
-        f = getattr(lib, name + "_compress")
-        f.argtypes = one_shot
-        f.restype = C.c_int
-        g = getattr(lib, name + "_max_compressed_size")
-        g.argtypes = [C.c_size_t]
-        g.restype = C.c_size_t
-    lib.mscomp_amd_ctx_create.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_ctx_create.restype = C.c_int
-    lib.mscomp_amd_ctx_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_ctx_destroy.restype = None
-    lib.mscomp_amd_plan_create.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_plan_create.restype = C.c_int
-    lib.mscomp_amd_plan_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_plan_destroy.restype = None
-    lib.mscomp_amd_plan_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_plan_execute.restype = C.c_int
-    lib.mscomp_amd_compress_batch.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_compress_batch.restype = C.c_int
-    lib.ms_decompress.argtypes = [C.c_int] + one_shot
-    lib.ms_decompress.restype = C.c_int
-    for name in ("lznt1", "xpress", "xpress_huff"):
-        f = getattr(lib, name + "_decompress")
-        f.argtypes = one_shot
-        f.restype = C.c_int
-    lib.mscomp_amd_plan_create_decompress.argtypes = lib.mscomp_amd_plan_create.argtypes
-    lib.mscomp_amd_plan_create_decompress.restype = C.c_int
-    lib.mscomp_amd_decompress_batch.argtypes = lib.mscomp_amd_compress_batch.argtypes
-    lib.mscomp_amd_decompress_batch.restype = C.c_int
-    lib.mscomp_amd_plan_create_size.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_plan_create_size.restype = C.c_int
-    lib.mscomp_amd_plan_execute_size.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_plan_execute_size.restype = C.c_int
-    lib.mscomp_amd_decompressed_size_batch.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                       C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_decompressed_size_batch.restype = C.c_int
-    lib.mscomp_amd_plan_create_decompress_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_plan_create_decompress_dev.restype = C.c_int
-    lib.mscomp_amd_plan_execute_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 8
-    lib.mscomp_amd_plan_execute_dev.restype = C.c_int
-    lib.mscomp_amd_layout_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.mscomp_amd_layout_dev.restype = C.c_int
-    lib.mscomp_amd_plan_create_compress_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_plan_create_compress_dev.restype = C.c_int
-    lib.mscomp_amd_plan_layout_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_plan_layout_dev.restype = C.c_int
-    lib.mscomp_amd_plan_create_size_dev.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_plan_create_size_dev.restype = C.c_int
-    lib.mscomp_amd_plan_create_decompress_dev_ex.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_plan_create_decompress_dev_ex.restype = C.c_int
-    lib.mscomp_amd_plan_create_size_dev_ex.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_plan_create_size_dev_ex.restype = C.c_int
-    lib.mscomp_amd_debug_plan_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.mscomp_amd_debug_plan_paths.restype = C.c_int
-    lib.mscomp_amd_plan_execute_size_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 7
-    lib.mscomp_amd_plan_execute_size_dev.restype = C.c_int
-    lib.mscomp_amd_compact_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.mscomp_amd_compact_dev.restype = C.c_int
-    lib.mscomp_amd_blocks_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_blocks_create.restype = C.c_int
-    lib.mscomp_amd_blocks_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_blocks_destroy.restype = None
-    lib.mscomp_amd_blocks_bound.argtypes = [C.c_void_p]
-    lib.mscomp_amd_blocks_bound.restype = C.c_uint64
-    lib.mscomp_amd_blocks_compress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_blocks_compress.restype = C.c_int
-    lib.mscomp_amd_blocks_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9
-    lib.mscomp_amd_blocks_decompress.restype = C.c_int
-    lib.mscomp_amd_plan_create_crc_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_plan_create_crc_dev.restype = C.c_int
-    lib.mscomp_amd_plan_execute_crc_dev.argtypes = [C.c_void_p] + [C.c_void_p] * 5
-    lib.mscomp_amd_plan_execute_crc_dev.restype = C.c_int
-    lib.mscomp_amd_blocks_crc.argtypes = [C.c_void_p] + [C.c_void_p] * 6
-    lib.mscomp_amd_blocks_crc.restype = C.c_int
-    lib.mscomp_amd_blocks_check.argtypes = [C.c_void_p] + [C.c_void_p] * 8
-    lib.mscomp_amd_blocks_check.restype = C.c_int
-    lib.mscomp_amd_blocks_salvage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 13
-    lib.mscomp_amd_blocks_salvage.restype = C.c_int
-    lib.mscomp_amd_reader_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_reader_create.restype = C.c_int
-    lib.mscomp_amd_reader_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_reader_destroy.restype = None
-    lib.mscomp_amd_reader_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 10
-    lib.mscomp_amd_reader_read.restype = C.c_int
-    lib.mscomp_amd_reader_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.mscomp_amd_reader_counts.restype = C.c_int
-    lib.mscomp_amd_writer_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_writer_create.restype = C.c_int
-    lib.mscomp_amd_writer_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_writer_destroy.restype = None
-    lib.mscomp_amd_writer_write.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 8 + [C.c_uint64] + [C.c_void_p] * 5
-    lib.mscomp_amd_writer_write.restype = C.c_int
-    lib.mscomp_amd_writer_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.mscomp_amd_writer_counts.restype = C.c_int
-    lib.mscomp_amd_writer_resize.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 5
-    lib.mscomp_amd_writer_resize.restype = C.c_int
-    lib.mscomp_amd_res_crc_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint64] + [C.c_void_p] * 5
-    lib.mscomp_amd_res_crc_dev.restype = C.c_int
-    lib.mscomp_amd_splicer_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_splicer_create.restype = C.c_int
-    lib.mscomp_amd_splicer_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_splicer_destroy.restype = None
-    lib.mscomp_amd_splicer_splice.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
-    lib.mscomp_amd_splicer_splice.restype = C.c_int
-    lib.mscomp_amd_splicer_create_extents.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_splicer_create_extents.restype = C.c_int
-    lib.mscomp_amd_splicer_splice_extents.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
-    lib.mscomp_amd_splicer_splice_extents.restype = C.c_int
-    lib.mscomp_amd_deduper_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_deduper_create.restype = C.c_int
-    lib.mscomp_amd_deduper_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_deduper_destroy.restype = None
-    lib.mscomp_amd_deduper_dedup.argtypes = [C.c_void_p, C.POINTER(BlocksView)] + [C.c_void_p] * 5
-    lib.mscomp_amd_deduper_dedup.restype = C.c_int
-    lib.mscomp_amd_deduper_create_diff.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_deduper_create_diff.restype = C.c_int
-    lib.mscomp_amd_deduper_diff.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.POINTER(BlocksView)] + [C.c_void_p] * 8
-    lib.mscomp_amd_deduper_diff.restype = C.c_int
-    lib.mscomp_amd_deduper_create_match.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_deduper_create_match.restype = C.c_int
-    lib.mscomp_amd_deduper_match.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.POINTER(BlocksView)] + [C.c_void_p] * 7
-    lib.mscomp_amd_deduper_match.restype = C.c_int
-    lib.mscomp_amd_deduper_create_repair.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_deduper_create_repair.restype = C.c_int
-    lib.mscomp_amd_deduper_repair.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.POINTER(C.c_void_p)] + [C.c_void_p] * 6
-    lib.mscomp_amd_deduper_repair.restype = C.c_int
-    lib.mscomp_amd_transcoder_create.restype = C.c_int
-    lib.mscomp_amd_transcoder_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
-                                                 C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_transcoder_destroy.restype = None
-    lib.mscomp_amd_transcoder_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_transcoder_transcode.restype = C.c_int
-    lib.mscomp_amd_transcoder_transcode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_uint64] + [C.c_void_p] * 4
-    lib.mscomp_amd_transcoder_counts.restype = C.c_int
-    lib.mscomp_amd_transcoder_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.mscomp_amd_syncer_create.restype = C.c_int
-    lib.mscomp_amd_syncer_create.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32,
-                                             C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_syncer_destroy.restype = None
-    lib.mscomp_amd_syncer_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_syncer_sync.restype = C.c_int
-    lib.mscomp_amd_syncer_sync.argtypes = [C.c_void_p, C.POINTER(BlocksView)] + [C.c_void_p] * 11
-    lib.mscomp_amd_syncer_counts.restype = C.c_int
-    lib.mscomp_amd_syncer_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.mscomp_amd_digester_create.restype = C.c_int
-    lib.mscomp_amd_digester_create.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_digester_destroy.restype = None
-    lib.mscomp_amd_digester_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_digester_blocks.restype = C.c_int
-    lib.mscomp_amd_digester_blocks.argtypes = [C.c_void_p] + [C.c_void_p] * 5
-    lib.mscomp_amd_digester_check.restype = C.c_int
-    lib.mscomp_amd_digester_check.argtypes = [C.c_void_p] + [C.c_void_p] * 8
-    lib.mscomp_amd_syncer_create_digest.restype = C.c_int
-    lib.mscomp_amd_syncer_create_digest.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint64, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32,
-                                                    C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_syncer_sync_digest.restype = C.c_int
-    lib.mscomp_amd_syncer_sync_digest.argtypes = [C.c_void_p, C.POINTER(BlocksView)] + [C.c_void_p] * 12
-    lib.mscomp_amd_plan_layout.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_plan_layout.restype = C.c_uint64
-    lib.mscomp_amd_compact_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_compact_batch.restype = C.c_int
-    lib.mscomp_amd_profile_enable.argtypes = [C.c_void_p, C.c_int]
-    lib.mscomp_amd_profile_enable.restype = None
-    lib.mscomp_amd_profile_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.mscomp_amd_profile_read.restype = C.c_int
-    lib.mscomp_amd_version.restype = C.c_char_p
-    lib.mscomp_amd_debug_xpress_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_debug_xpress_matches.restype = C.c_int
-    lib.mscomp_amd_debug_huff_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.mscomp_amd_debug_huff_lengths.restype = C.c_int
-    lib.mscomp_amd_debug_huff_lengths_slow.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.mscomp_amd_debug_huff_lengths_slow.restype = C.c_int
-    lib.mscomp_amd_debug_lds_lane_order.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
-    lib.mscomp_amd_debug_lds_lane_order.restype = C.c_uint32
-    lib.mscomp_amd_debug_alignbyte.argtypes = [C.c_void_p, C.c_uint32]
-    lib.mscomp_amd_debug_alignbyte.restype = C.c_uint32
-    lib.mscomp_amd_debug_set_xpress_emit.argtypes = [C.c_int]
-    lib.mscomp_amd_debug_set_xpress_emit.restype = None
-    lib.mscomp_amd_set_lznt1_sa_dict.argtypes = [C.c_int]
-    lib.mscomp_amd_set_lznt1_sa_dict.restype = None
-    lib.mscomp_amd_get_lznt1_sa_dict.argtypes = []
-    lib.mscomp_amd_get_lznt1_sa_dict.restype = C.c_int
-    lib.mscomp_amd_ctx_set_lznt1_sa_dict.argtypes = [C.c_void_p, C.c_int]
-    lib.mscomp_amd_ctx_set_lznt1_sa_dict.restype = C.c_int
-    lib.mscomp_amd_debug_hooks_enabled.argtypes = []
-    lib.mscomp_amd_debug_hooks_enabled.restype = C.c_int
-    lib.mscomp_amd_debug_set_xpress_decoder.argtypes = [C.c_int]
-    lib.mscomp_amd_debug_set_xpress_decoder.restype = None
-    lib.mscomp_amd_debug_set_finder.argtypes = [C.c_int]
-    lib.mscomp_amd_debug_set_finder.restype = None
-    lib.mscomp_amd_compress_units_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mscomp_amd_compress_units_host.restype = C.c_int
-    lib.mscomp_amd_decompress_units_host.argtypes = lib.mscomp_amd_compress_units_host.argtypes
-    lib.mscomp_amd_decompress_units_host.restype = C.c_int
-    lib.mscomp_amd_host_pool_release.argtypes = []
-    lib.mscomp_amd_host_pool_release.restype = None
-    lib.mscomp_amd_debug_set_one_shot.argtypes = [C.c_int]
-    lib.mscomp_amd_debug_set_one_shot.restype = None
-    lib.mscomp_amd_debug_set_lznt1.argtypes = [C.c_int]
-    lib.mscomp_amd_debug_set_lznt1.restype = None
-    lib.mscomp_amd_debug_set_place_blocks.argtypes = [C.c_int]
-    lib.mscomp_amd_debug_set_place_blocks.restype = None
-    lib.mscomp_amd_debug_set_serial_atomics.argtypes = [C.c_int]
-    lib.mscomp_amd_debug_set_serial_atomics.restype = None
-    lib.mscomp_amd_debug_lzd_walked.argtypes = [C.c_void_p]
-    lib.mscomp_amd_debug_lzd_walked.restype = C.c_uint32
-    lib.mscomp_amd_debug_decode_modes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.mscomp_amd_debug_decode_modes.restype = C.c_int
-    lib.mscomp_amd_parity_create.restype = C.c_int
-    lib.mscomp_amd_parity_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.mscomp_amd_parity_destroy.restype = None
-    lib.mscomp_amd_parity_destroy.argtypes = [C.c_void_p]
-    lib.mscomp_amd_parity_bound.restype = C.c_int
-    lib.mscomp_amd_parity_bound.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.mscomp_amd_parity_build.restype = C.c_int
-    lib.mscomp_amd_parity_build.argtypes = [C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
-    lib.mscomp_amd_parity_rebuild.restype = C.c_int
-    lib.mscomp_amd_parity_rebuild.argtypes = ([C.c_void_p, C.POINTER(BlocksView), C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 +
-                                              [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4)
-    lib.mscomp_amd_debug_scratch_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
-    lib.mscomp_amd_debug_scratch_names.restype = C.c_int
-    lib.mscomp_amd_debug_scratch_poison.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int]
-    lib.mscomp_amd_debug_scratch_poison.restype = C.c_int
-    lib.mscomp_amd_debug_scratch_report.argtypes = [C.c_int, C.c_void_p, C.c_int, C.POINTER(ScratchRec), C.c_int]
-    lib.mscomp_amd_debug_scratch_report.restype = C.c_int
+    for name in SIGNATURES:
+        if hasattr(lib, name):                 # (build() and tests/test_abi.py report a symbol the library lacks; calling it raises)
+            f = getattr(lib, name)
+            f.restype, f.argtypes = signature(name)
     _lib = lib
     return lib
 
@@ -398,9 +288,7 @@ class Context:
         self.stream = s
         self._h = C.c_void_p()
         self._handles = weakref.WeakSet()                  # the plans and block objects that live in this context (_Handle)
-        st = self.lib.mscomp_amd_ctx_create(self.device, C.c_void_p(s.cuda_stream), C.byref(self._h))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_ctx_create")
+        _run(self, "mscomp_amd_ctx_create", self.device, C.c_void_p(s.cuda_stream), C.byref(self._h))
 
     def close(self):
         """Destroys the context, and first whatever still lives in it: an object's destroy call reads its context."""
@@ -418,9 +306,7 @@ class Context:
 
     def set_lznt1_sa_dict(self, on):
         """LZNT1 dictionary flavour of the plans this context creates from now on: True / False, None = the process default."""
-        st = self.lib.mscomp_amd_ctx_set_lznt1_sa_dict(self._h, -1 if on is None else int(bool(on)))
-        if st != MSCOMP_OK:
-            raise MSCompError(st, "mscomp_amd_ctx_set_lznt1_sa_dict")
+        _run(self, "mscomp_amd_ctx_set_lznt1_sa_dict", self._h, -1 if on is None else int(bool(on)))
 
     def profile_enable(self, on=True):
         self.lib.mscomp_amd_profile_enable(self._h, 1 if on else 0)
@@ -435,13 +321,12 @@ class Context:
         return {names[i].decode(): (ms[i], cnt[i]) for i in range(n)}
 
 
-def _ptrs(*tensors):
-    return [None if t is None else C.c_void_p(t.data_ptr()) for t in tensors]
-
-
-def _ok(st, name):
+def _run(ctx, export, *args):
+    """Calls ``export`` of the context's library with ``args`` in the prototype's order: a torch tensor goes as its data pointer, None as
+    NULL, ints and ctypes values as they are. Raises MSCompError(status, export) unless the status is MSCOMP_OK."""
+    st = getattr(ctx.lib, export)(*[C.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a for a in args])
     if st != MSCOMP_OK:
-        raise MSCompError(st, name)
+        raise MSCompError(st, export)
 
 
 @contextlib.contextmanager
@@ -466,8 +351,7 @@ def _call(ctx, enter=True):
 def _three_counts(obj, export):
     """the three uint32 counters ``export`` reads from the object ``obj`` (the call synchronizes the stream)"""
     out = (C.c_uint32 * 3)()
-    if getattr(obj.ctx.lib, export)(obj._h, out) != 0:
-        raise MSCompError(MSCOMP_ERRNO, export)
+    _run(obj.ctx, export, obj._h, out)         # (these answer 0 or MSCOMP_ERRNO)
     return (int(out[0]), int(out[1]), int(out[2]))
 
 
@@ -488,6 +372,14 @@ class _Handle:
     def __init__(self, ctx):
         self.ctx, self._h = ctx, C.c_void_p()
         ctx._handles.add(self)
+
+    def _make(self, export, *args):
+        """the create call ``export(ctx, *args, &handle)``"""
+        _run(self.ctx, export, self.ctx._h, *args, C.byref(self._h))
+
+    def _run(self, export, *args):
+        """the call ``export(handle, *args)``: _run above"""
+        _run(self.ctx, export, self._h, *args)
 
     def close(self):
         if self._h:
@@ -511,12 +403,11 @@ class Plan(_Handle):
         assert all(a.ndim == 1 and a.shape == arrs[0].shape for a in arrs)
         self.in_off, self.in_len, self.out_off, self.out_cap = arrs
         self.n_units = len(self.in_off)
-        create = ctx.lib.mscomp_amd_plan_create_decompress if decompress else ctx.lib.mscomp_amd_plan_create
-        _ok(create(ctx._h, self.fmt, self.n_units, *[a.ctypes.data for a in arrs], C.byref(self._h)), "mscomp_amd_plan_create")
+        self._make("mscomp_amd_plan_create_decompress" if decompress else "mscomp_amd_plan_create", self.fmt, self.n_units, *[a.ctypes.data for a in arrs])
 
     def execute(self, d_in, d_out, d_out_len, d_status):
         """Enqueue on the ctx stream. Arguments are torch CUDA tensors (uint8, uint8, int64/uint64[n], int32[n])."""
-        _ok(self.ctx.lib.mscomp_amd_plan_execute(self._h, *_ptrs(d_in, d_out, d_out_len, d_status)), "mscomp_amd_plan_execute")
+        self._run("mscomp_amd_plan_execute", d_in, d_out, d_out_len, d_status)
 
 
 class SizePlan(_Handle):
@@ -532,13 +423,12 @@ class SizePlan(_Handle):
         self.limit = None if limit is None else np.ascontiguousarray(limit, dtype=np.uint64)
         assert self.limit is None or self.limit.shape == self.in_off.shape
         self.n_units = len(self.in_off)
-        _ok(ctx.lib.mscomp_amd_plan_create_size(ctx._h, self.fmt, self.n_units, self.in_off.ctypes.data, self.in_len.ctypes.data,
-                                                None if self.limit is None else self.limit.ctypes.data, C.byref(self._h)),
-            "mscomp_amd_plan_create_size")
+        self._make("mscomp_amd_plan_create_size", self.fmt, self.n_units, self.in_off.ctypes.data, self.in_len.ctypes.data,
+                   None if self.limit is None else self.limit.ctypes.data)
 
     def execute(self, d_in, d_out_len, d_need, d_status):
         """Enqueue on the ctx stream. Arguments are torch CUDA tensors (uint8, int64/uint64[n], int64/uint64[n], int32[n])."""
-        _ok(self.ctx.lib.mscomp_amd_plan_execute_size(self._h, *_ptrs(d_in, d_out_len, d_need, d_status)), "mscomp_amd_plan_execute_size")
+        self._run("mscomp_amd_plan_execute_size", d_in, d_out_len, d_need, d_status)
 
 
 class DevPlan(_Handle):
@@ -553,17 +443,14 @@ class DevPlan(_Handle):
         self.in_total_max, self.out_total_max = int(in_total_max), int(out_total_max)
         self.large_units = bool(large_units)
         if self.large_units:
-            st = ctx.lib.mscomp_amd_plan_create_decompress_dev_ex(ctx._h, self.fmt, self.n_units, self.in_total_max, self.out_total_max,
-                                                                  MSCOMP_AMD_DEV_LARGE_UNITS, C.byref(self._h))
+            self._make("mscomp_amd_plan_create_decompress_dev_ex", self.fmt, self.n_units, self.in_total_max, self.out_total_max, MSCOMP_AMD_DEV_LARGE_UNITS)
         else:
-            st = ctx.lib.mscomp_amd_plan_create_decompress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.out_total_max, C.byref(self._h))
-        _ok(st, "mscomp_amd_plan_create_decompress_dev")
+            self._make("mscomp_amd_plan_create_decompress_dev", self.fmt, self.n_units, self.in_total_max, self.out_total_max)
 
     def execute(self, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status):
         """Enqueue on the ctx stream (nothing is synchronized or read back). Arguments are torch CUDA tensors: uint8 input and output, int64 /
         uint64 tables of n_units entries (offsets, lengths, capacities; results d_out_len), int32 d_status."""
-        ptrs = _ptrs(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status)
-        _ok(self.ctx.lib.mscomp_amd_plan_execute_dev(self._h, *ptrs), "mscomp_amd_plan_execute_dev")
+        self._run("mscomp_amd_plan_execute_dev", d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status)
 
 
 class CompressDevPlan(DevPlan):
@@ -574,8 +461,7 @@ class CompressDevPlan(DevPlan):
         _Handle.__init__(self, ctx)
         self.fmt, self.n_units = int(fmt), int(n_units)
         self.in_total_max, self.in_unit_max = int(in_total_max), int(in_unit_max)
-        _ok(ctx.lib.mscomp_amd_plan_create_compress_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, self.in_unit_max, C.byref(self._h)),
-            "mscomp_amd_plan_create_compress_dev")
+        self._make("mscomp_amd_plan_create_compress_dev", self.fmt, self.n_units, self.in_total_max, self.in_unit_max)
 
 
 class SizeDevPlan(DevPlan):
@@ -589,16 +475,14 @@ class SizeDevPlan(DevPlan):
         self.in_total_max = int(in_total_max)
         self.large_units = bool(large_units)
         if self.large_units:
-            st = ctx.lib.mscomp_amd_plan_create_size_dev_ex(ctx._h, self.fmt, self.n_units, self.in_total_max, MSCOMP_AMD_DEV_LARGE_UNITS, C.byref(self._h))
+            self._make("mscomp_amd_plan_create_size_dev_ex", self.fmt, self.n_units, self.in_total_max, MSCOMP_AMD_DEV_LARGE_UNITS)
         else:
-            st = ctx.lib.mscomp_amd_plan_create_size_dev(ctx._h, self.fmt, self.n_units, self.in_total_max, C.byref(self._h))
-        _ok(st, "mscomp_amd_plan_create_size_dev")
+            self._make("mscomp_amd_plan_create_size_dev", self.fmt, self.n_units, self.in_total_max)
 
     def execute(self, d_in, d_in_off, d_in_len, d_out_len, d_need, d_status, d_limit=None):
         """Enqueue on the ctx stream (nothing is synchronized or read back). Arguments are torch CUDA tensors: uint8 input, int64 / uint64
         tables of n_units entries (offsets, lengths, d_limit or None = no limit; results d_out_len, d_need), int32 d_status."""
-        ptrs = _ptrs(d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status)
-        _ok(self.ctx.lib.mscomp_amd_plan_execute_size_dev(self._h, *ptrs), "mscomp_amd_plan_execute_size_dev")
+        self._run("mscomp_amd_plan_execute_size_dev", d_in, d_in_off, d_in_len, d_limit, d_out_len, d_need, d_status)
 
 
 class CrcDevPlan(DevPlan):
@@ -608,12 +492,12 @@ class CrcDevPlan(DevPlan):
     def __init__(self, ctx, n_units, in_total_max):
         _Handle.__init__(self, ctx)
         self.n_units, self.in_total_max = int(n_units), int(in_total_max)
-        _ok(ctx.lib.mscomp_amd_plan_create_crc_dev(ctx._h, self.n_units, self.in_total_max, C.byref(self._h)), "mscomp_amd_plan_create_crc_dev")
+        self._make("mscomp_amd_plan_create_crc_dev", self.n_units, self.in_total_max)
 
     def execute(self, d_in, d_in_off, d_in_len, d_crc, d_status):
         """Enqueue on the ctx stream (nothing is synchronized or read back). Arguments are torch CUDA tensors: uint8 input, int64 / uint64
         offsets and lengths of n_units entries, int32 d_crc (the 32 bits of each CRC) and int32 d_status."""
-        _ok(self.ctx.lib.mscomp_amd_plan_execute_crc_dev(self._h, *_ptrs(d_in, d_in_off, d_in_len, d_crc, d_status)), "mscomp_amd_plan_execute_crc_dev")
+        self._run("mscomp_amd_plan_execute_crc_dev", d_in, d_in_off, d_in_len, d_crc, d_status)
 
 
 class BlockContainer(_Handle):
@@ -630,8 +514,7 @@ class BlockContainer(_Handle):
         _Handle.__init__(self, ctx)
         self.fmt, self.block_size = int(fmt), int(block_size)
         self.n_res, self.in_total_max = int(n_res), int(in_total_max)
-        _ok(ctx.lib.mscomp_amd_blocks_create(ctx._h, self.fmt, self.block_size, self.n_res, self.in_total_max, 0, C.byref(self._h)),
-            "mscomp_amd_blocks_create")
+        self._make("mscomp_amd_blocks_create", self.fmt, self.block_size, self.n_res, self.in_total_max, 0)
         self.n_blocks_max = int(ctx.lib.mscomp_amd_blocks_bound(self._h))
 
     def compress(self, d_in, d_res_off, d_res_len, d_packed, d_block_first, d_block_off, d_status, packed_cap=None):
@@ -642,8 +525,7 @@ class BlockContainer(_Handle):
         cap = d_packed.numel() if packed_cap is None else int(packed_cap)
         if cap > d_packed.numel():
             raise ValueError("packed_cap exceeds d_packed")
-        p = _ptrs(d_in, d_res_off, d_res_len, d_packed, d_block_first, d_block_off, d_status)
-        _ok(self.ctx.lib.mscomp_amd_blocks_compress(self._h, *p[:4], cap, *p[4:]), "mscomp_amd_blocks_compress")
+        self._run("mscomp_amd_blocks_compress", d_in, d_res_off, d_res_len, d_packed, cap, d_block_first, d_block_off, d_status)
 
     def decompress(self, d_packed, d_block_first, d_block_off, d_res_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_range=None,
                    packed_len=None):
@@ -652,20 +534,19 @@ class BlockContainer(_Handle):
         MSCOMP_ARG_ERROR (beyond the creation bounds), MSCOMP_DATA_ERROR (a damaged table or payload) or MSCOMP_BUF_ERROR (capacity), with
         d_out_len[r] = 0. ``packed_len``: the valid bytes of d_packed (default: all of it)."""
         plen = d_packed.numel() if packed_len is None else int(packed_len)
-        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_range, d_out, d_out_off, d_out_cap, d_out_len, d_status)
-        _ok(self.ctx.lib.mscomp_amd_blocks_decompress(self._h, p[0], plen, *p[1:]), "mscomp_amd_blocks_decompress")
+        self._run("mscomp_amd_blocks_decompress", d_packed, plen, d_block_first, d_block_off, d_res_len, d_range, d_out, d_out_off, d_out_cap, d_out_len,
+                  d_status)
 
     def crc(self, d_data, d_res_off, d_res_len, d_block_crc, d_status, d_res_crc=None):
         """CRC-32 of the uncompressed blocks of the resources (as compress takes them): d_block_crc (int32, n_blocks_max; entry j belongs to the
         block compress puts at d_block_off[j], the entries behind the last block are 0), d_res_crc (optional, int32, n_res: the CRC-32 of
         every whole resource, from the same pass) and d_status (n_res: MSCOMP_OK, or MSCOMP_ARG_ERROR as compress gives it)."""
-        _ok(self.ctx.lib.mscomp_amd_blocks_crc(self._h, *_ptrs(d_data, d_res_off, d_res_len, d_block_crc, d_res_crc, d_status)), "mscomp_amd_blocks_crc")
+        self._run("mscomp_amd_blocks_crc", d_data, d_res_off, d_res_len, d_block_crc, d_res_crc, d_status)
 
     def check(self, d_out, d_out_off, d_res_len, d_block_first, d_block_crc, d_out_len, d_status, d_range=None):
         """After decompress, with its tables and results: every block of the (clipped) range of every resource that is MSCOMP_OK in d_status
         is read back from d_out and held to d_block_crc; a mismatch turns the resource into MSCOMP_DATA_ERROR with d_out_len = 0."""
-        p = _ptrs(d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status)
-        _ok(self.ctx.lib.mscomp_amd_blocks_check(self._h, *p), "mscomp_amd_blocks_check")
+        self._run("mscomp_amd_blocks_check", d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_crc, d_out_len, d_status)
 
     def salvage(self, d_packed, d_block_first, d_block_off, d_res_len, d_out, d_out_off, d_out_cap, d_out_len, d_bad, d_verdict, d_count, d_status,
                 d_block_crc=None, d_only=None, packed_len=None):
@@ -677,8 +558,8 @@ class BlockContainer(_Handle):
         same shape): rows it marks GOOD are not judged, not read and not written. d_count (int64, 4) = rows judged, rows bad, bytes
         zero-filled, resources with a bad row."""
         plen = d_packed.numel() if packed_len is None else int(packed_len)
-        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_only, d_out, d_out_off, d_out_cap, d_out_len, d_bad, d_verdict, d_count, d_status)
-        _ok(self.ctx.lib.mscomp_amd_blocks_salvage(self._h, p[0], plen, *p[1:]), "mscomp_amd_blocks_salvage")
+        self._run("mscomp_amd_blocks_salvage", d_packed, plen, d_block_first, d_block_off, d_res_len, d_block_crc, d_only, d_out, d_out_off, d_out_cap,
+                  d_out_len, d_bad, d_verdict, d_count, d_status)
 
 
 def blocks_compress(fmt, buffers, block_size, ctx=None):
@@ -822,8 +703,7 @@ class _BlockAccess(_Handle):
         _Handle.__init__(self, ctx)
         self.fmt, self.block_size = int(fmt), int(block_size)
         self.n_res, self.n_blocks_table, self.n_req, self.blocks_max = int(n_res), int(n_blocks_table), int(n_req), int(blocks_max)
-        _ok(getattr(ctx.lib, self._create)(ctx._h, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_req, self.blocks_max, 0,
-                                           C.byref(self._h)), self._create)
+        self._make(self._create, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_req, self.blocks_max, 0)
 
 
 class BlockReader(_BlockAccess):
@@ -843,8 +723,8 @@ class BlockReader(_BlockAccess):
         ``d_block_crc``, as BlockContainer.crc wrote it, a block whose CRC-32 differs) with d_out_len[q] = 0 and nothing written.
         ``packed_len``: the valid bytes of d_packed (default: all of it)."""
         plen, _ = _byte_bounds(d_packed, packed_len)
-        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_out, d_out_off, d_out_cap, d_out_len, d_status)
-        _ok(self.ctx.lib.mscomp_amd_reader_read(self._h, p[0], plen, *p[1:]), "mscomp_amd_reader_read")
+        self._run("mscomp_amd_reader_read", d_packed, plen, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_out, d_out_off, d_out_cap,
+                  d_out_len, d_status)
 
     def counts(self):
         """(units, distinct blocks, blocks decoded rather than raw) of the last read(); synchronizes the stream."""
@@ -902,9 +782,8 @@ class BlockWriter(_BlockAccess):
         applied. d_res_status[r] is MSCOMP_BUF_ERROR when a block of the resource did not fit below new_cap. A touched block is decoded,
         patched in request order and encoded again; every other block keeps its stored bytes."""
         plen, cap = _byte_bounds(d_packed, packed_len, d_new_packed, new_cap)
-        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_src, d_src_off, d_new_packed, d_new_block_off, d_new_block_crc,
-                  d_written, d_status, d_res_status)
-        _ok(self.ctx.lib.mscomp_amd_writer_write(self._h, p[0], plen, *p[1:9], cap, *p[9:]), "mscomp_amd_writer_write")
+        self._run("mscomp_amd_writer_write", d_packed, plen, d_block_first, d_block_off, d_res_len, d_block_crc, d_req, d_src, d_src_off, d_new_packed, cap,
+                  d_new_block_off, d_new_block_crc, d_written, d_status, d_res_status)
 
     def resize(self, d_packed, d_block_first, d_block_off, d_res_len, d_want_len, d_new_packed, d_new_block_first, d_new_block_off, d_new_res_len,
                d_res_status, d_block_crc=None, d_new_block_crc=None, packed_len=None, new_cap=None):
@@ -916,9 +795,8 @@ class BlockWriter(_BlockAccess):
         MSCOMP_BUF_ERROR (a block did not fit below new_cap); all MSCOMP_ARG_ERROR with zeroed tables when the new table needs more than
         n_blocks_table rows. Only the block the new end falls into is decoded; it and the fresh blocks are encoded."""
         plen, cap = _byte_bounds(d_packed, packed_len, d_new_packed, new_cap)
-        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_want_len, d_new_packed, d_new_block_first, d_new_block_off,
-                  d_new_block_crc, d_new_res_len, d_res_status)
-        _ok(self.ctx.lib.mscomp_amd_writer_resize(self._h, p[0], plen, *p[1:7], cap, *p[7:]), "mscomp_amd_writer_resize")
+        self._run("mscomp_amd_writer_resize", d_packed, plen, d_block_first, d_block_off, d_res_len, d_block_crc, d_want_len, d_new_packed, cap,
+                  d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_res_status)
 
     def counts(self):
         """(units, distinct blocks touched, blocks encoded again) of the last write(), or (units, changed blocks decoded, blocks encoded) of
@@ -1027,8 +905,7 @@ class BlockSplicer(_Handle):
     def __init__(self, ctx, block_size, n_src, n_pick, n_blocks_table):
         _Handle.__init__(self, ctx)
         self.block_size, self.n_src, self.n_pick, self.n_blocks_table = int(block_size), int(n_src), int(n_pick), int(n_blocks_table)
-        _ok(ctx.lib.mscomp_amd_splicer_create(ctx._h, self.block_size, self.n_src, self.n_pick, self.n_blocks_table, 0, C.byref(self._h)),
-            "mscomp_amd_splicer_create")
+        self._make("mscomp_amd_splicer_create", self.block_size, self.n_src, self.n_pick, self.n_blocks_table, 0)
 
     def splice(self, sources, d_pick, d_new_packed, d_new_block_first, d_new_block_off, d_new_res_len, d_status, d_new_block_crc=None, new_cap=None):
         """``sources``: n_src tuples (d_packed, d_block_first, d_block_off, d_res_len, d_block_crc or None, packed_len or None = all of
@@ -1042,9 +919,8 @@ class BlockSplicer(_Handle):
         _, cap = _byte_bounds(d_new_packed=d_new_packed, new_cap=new_cap)
         if len(sources) != self.n_src:
             raise ValueError("one source per n_src")
-        views = _blocks_views(sources)
-        p = _ptrs(d_pick, d_new_packed, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_status)
-        _ok(self.ctx.lib.mscomp_amd_splicer_splice(self._h, views, p[0], p[1], cap, *p[2:]), "mscomp_amd_splicer_splice")
+        self._run("mscomp_amd_splicer_splice", _blocks_views(sources), d_pick, d_new_packed, cap, d_new_block_first, d_new_block_off, d_new_block_crc,
+                  d_new_res_len, d_status)
 
 
     @classmethod
@@ -1056,8 +932,7 @@ class BlockSplicer(_Handle):
         _Handle.__init__(self, ctx)
         self.block_size, self.n_src, self.n_pick, self.n_blocks_table = int(block_size), int(n_src), int(n_res), int(n_blocks_table)
         self.n_res, self.n_ext = int(n_res), int(n_ext)
-        _ok(ctx.lib.mscomp_amd_splicer_create_extents(ctx._h, self.block_size, self.n_src, self.n_res, self.n_ext, self.n_blocks_table, 0, C.byref(self._h)),
-            "mscomp_amd_splicer_create_extents")
+        self._make("mscomp_amd_splicer_create_extents", self.block_size, self.n_src, self.n_res, self.n_ext, self.n_blocks_table, 0)
         return self
 
     def splice_extents(self, sources, d_ext_first, d_ext, d_new_packed, d_new_block_first, d_new_block_off, d_new_res_len, d_status, d_new_block_crc=None,
@@ -1070,9 +945,8 @@ class BlockSplicer(_Handle):
         _, cap = _byte_bounds(d_new_packed=d_new_packed, new_cap=new_cap)
         if len(sources) != self.n_src:
             raise ValueError("one source per n_src")
-        views = _blocks_views(sources)
-        p = _ptrs(d_ext_first, d_ext, d_new_packed, d_new_block_first, d_new_block_off, d_new_block_crc, d_new_res_len, d_status)
-        _ok(self.ctx.lib.mscomp_amd_splicer_splice_extents(self._h, views, p[0], p[1], p[2], cap, *p[3:]), "mscomp_amd_splicer_splice_extents")
+        self._run("mscomp_amd_splicer_splice_extents", _blocks_views(sources), d_ext_first, d_ext, d_new_packed, cap, d_new_block_first, d_new_block_off,
+                  d_new_block_crc, d_new_res_len, d_status)
 
 
 def _splice_host(containers, n_new, nbt, room, ctx, make, run):
@@ -1168,8 +1042,7 @@ class BlockDeduper(_Handle):
     def __init__(self, ctx, block_size, n_src, n_res_total, n_blocks_total):
         _Handle.__init__(self, ctx)
         self.block_size, self.n_src, self.n_res_total, self.n_blocks_total = int(block_size), int(n_src), int(n_res_total), int(n_blocks_total)
-        _ok(ctx.lib.mscomp_amd_deduper_create(ctx._h, self.block_size, self.n_src, self.n_res_total, self.n_blocks_total, 0, C.byref(self._h)),
-            "mscomp_amd_deduper_create")
+        self._make("mscomp_amd_deduper_create", self.block_size, self.n_src, self.n_res_total, self.n_blocks_total, 0)
 
     def dedup(self, sources, d_rep, d_new_index, d_pick, d_count, d_status):
         """``sources``: as BlockSplicer.splice takes them; their resources are numbered back to back, g = 0 .. N - 1. d_rep[g] = the smallest
@@ -1180,8 +1053,7 @@ class BlockDeduper(_Handle):
         Checksums take part in the comparison when every source has them."""
         if len(sources) != self.n_src:
             raise ValueError("one source per n_src")
-        _ok(self.ctx.lib.mscomp_amd_deduper_dedup(self._h, _blocks_views(sources), *_ptrs(d_rep, d_new_index, d_pick, d_count, d_status)),
-            "mscomp_amd_deduper_dedup")
+        self._run("mscomp_amd_deduper_dedup", _blocks_views(sources), d_rep, d_new_index, d_pick, d_count, d_status)
 
 
     @classmethod
@@ -1193,8 +1065,7 @@ class BlockDeduper(_Handle):
         _Handle.__init__(self, ctx)
         self.block_size, self.n_pair, self.n_blocks_new = int(block_size), int(n_pair), int(n_blocks_new)
         self.n_src, self.n_res_total, self.n_blocks_total = 2, self.n_pair, self.n_blocks_new
-        _ok(ctx.lib.mscomp_amd_deduper_create_diff(ctx._h, self.block_size, self.n_pair, self.n_blocks_new, 0, C.byref(self._h)),
-            "mscomp_amd_deduper_create_diff")
+        self._make("mscomp_amd_deduper_create_diff", self.block_size, self.n_pair, self.n_blocks_new, 0)
         return self
 
     def diff(self, base, new, d_pair, d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_changed, d_count, d_status):
@@ -1208,9 +1079,8 @@ class BlockDeduper(_Handle):
         MSCOMP_ARG_ERROR (no such resource, a broken block_first entry, or no room within n_blocks_new) or MSCOMP_DATA_ERROR (a wrong
         block count, a broken block_off entry), a refused pair having no extents."""
         views = _blocks_views([base, new])
-        _ok(self.ctx.lib.mscomp_amd_deduper_diff(self._h, C.byref(views[0]), C.byref(views[1]), *_ptrs(d_pair, d_delta_ext_first, d_delta_ext, d_patch_ext_first,
-                                                                                                         d_patch_ext, d_changed, d_count, d_status)),
-            "mscomp_amd_deduper_diff")
+        self._run("mscomp_amd_deduper_diff", C.byref(views[0]), C.byref(views[1]), d_pair, d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext,
+                  d_changed, d_count, d_status)
 
 
     @classmethod
@@ -1223,8 +1093,7 @@ class BlockDeduper(_Handle):
         _Handle.__init__(self, ctx)
         self.block_size, self.n_src, self.n_res_total = int(block_size), int(n_src), int(n_res_total)
         self.n_blocks_total, self.n_blocks_new = int(n_blocks_total), int(n_blocks_new)
-        _ok(ctx.lib.mscomp_amd_deduper_create_match(ctx._h, self.block_size, self.n_src, self.n_res_total, self.n_blocks_total, self.n_blocks_new, 0,
-                                                    C.byref(self._h)), "mscomp_amd_deduper_create_match")
+        self._make("mscomp_amd_deduper_create_match", self.block_size, self.n_src, self.n_res_total, self.n_blocks_total, self.n_blocks_new, 0)
         return self
 
     def match(self, stores, new, d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_class, d_count, d_status):
@@ -1241,9 +1110,8 @@ class BlockDeduper(_Handle):
         if len(stores) != self.n_src:
             raise ValueError("one store per n_src")
         views = _blocks_views(list(stores) + [new])
-        _ok(self.ctx.lib.mscomp_amd_deduper_match(self._h, views if self.n_src else None, C.byref(views[self.n_src]),
-                                                  *_ptrs(d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_class, d_count, d_status)),
-            "mscomp_amd_deduper_match")
+        self._run("mscomp_amd_deduper_match", views if self.n_src else None, C.byref(views[self.n_src]), d_delta_ext_first, d_delta_ext, d_patch_ext_first,
+                  d_patch_ext, d_class, d_count, d_status)
 
 
     @classmethod
@@ -1255,8 +1123,7 @@ class BlockDeduper(_Handle):
         _Handle.__init__(self, ctx)
         self.block_size, self.n_src, self.n_res, self.n_blocks_new = int(block_size), int(n_src), int(n_res), int(n_blocks_new)
         self.n_res_total, self.n_blocks_total = self.n_res, self.n_blocks_new
-        _ok(ctx.lib.mscomp_amd_deduper_create_repair(ctx._h, self.block_size, self.n_src, self.n_res, self.n_blocks_new, 0, C.byref(self._h)),
-            "mscomp_amd_deduper_create_repair")
+        self._make("mscomp_amd_deduper_create_repair", self.block_size, self.n_src, self.n_res, self.n_blocks_new, 0)
         return self
 
     def repair(self, sources, d_verdicts, d_ext_first, d_ext, d_fixed, d_lost, d_count, d_status):
@@ -1271,8 +1138,7 @@ class BlockDeduper(_Handle):
         if len(sources) != self.n_src or len(d_verdicts) != self.n_src:
             raise ValueError("one source and one verdict array per n_src")
         q = (C.c_void_p * self.n_src)(*[None if t is None else t.data_ptr() for t in d_verdicts])
-        _ok(self.ctx.lib.mscomp_amd_deduper_repair(self._h, _blocks_views(sources), q, *_ptrs(d_ext_first, d_ext, d_fixed, d_lost, d_count, d_status)),
-            "mscomp_amd_deduper_repair")
+        self._run("mscomp_amd_deduper_repair", _blocks_views(sources), q, d_ext_first, d_ext, d_fixed, d_lost, d_count, d_status)
 
 
 def _diff_pairs(base, new, pairs):
@@ -1470,8 +1336,8 @@ class BlockTranscoder(_Handle):
         _Handle.__init__(self, ctx)
         self.fmt, self.block_size, self.new_fmt, self.new_block_size = int(fmt), int(block_size), int(new_fmt), int(new_block_size)
         self.n_res, self.n_blocks_table, self.n_blocks_new, self.groups_max = int(n_res), int(n_blocks_table), int(n_blocks_new), int(groups_max)
-        _ok(ctx.lib.mscomp_amd_transcoder_create(ctx._h, self.fmt, self.block_size, self.new_fmt, self.new_block_size, self.n_res, self.n_blocks_table,
-                                                 self.n_blocks_new, self.groups_max, 0, C.byref(self._h)), "mscomp_amd_transcoder_create")
+        self._make("mscomp_amd_transcoder_create", self.fmt, self.block_size, self.new_fmt, self.new_block_size, self.n_res, self.n_blocks_table,
+                   self.n_blocks_new, self.groups_max, 0)
 
     def transcode(self, d_packed, d_block_first, d_block_off, d_res_len, d_new_packed, d_new_block_first, d_new_block_off, d_status, d_block_crc=None,
                   d_new_block_crc=None, packed_len=None, new_cap=None):
@@ -1482,8 +1348,8 @@ class BlockTranscoder(_Handle):
         in the new table, or over the budget of groups_max) with resource r left without blocks, or MSCOMP_BUF_ERROR (a block did not fit
         below new_cap)."""
         plen, cap = _byte_bounds(d_packed, packed_len, d_new_packed, new_cap)
-        p = _ptrs(d_packed, d_block_first, d_block_off, d_res_len, d_block_crc, d_new_packed, d_new_block_first, d_new_block_off, d_new_block_crc, d_status)
-        _ok(self.ctx.lib.mscomp_amd_transcoder_transcode(self._h, p[0], plen, *p[1:6], cap, *p[6:]), "mscomp_amd_transcoder_transcode")
+        self._run("mscomp_amd_transcoder_transcode", d_packed, plen, d_block_first, d_block_off, d_res_len, d_block_crc, d_new_packed, cap,
+                  d_new_block_first, d_new_block_off, d_new_block_crc, d_status)
 
     def counts(self):
         """(new blocks carried, source blocks decoded, new blocks encoded) of the last transcode(); synchronizes the stream."""
@@ -1536,8 +1402,8 @@ class BlockSyncer(_Handle):
         _Handle.__init__(self, ctx)
         self.fmt, self.block_size, self.n_res, self.n_blocks_table = int(fmt), int(block_size), int(n_res), int(n_blocks_table)
         self.n_units, self.in_total_max, self.n_cand_max = int(n_units), int(in_total_max), int(n_cand_max)
-        _ok(ctx.lib.mscomp_amd_syncer_create(ctx._h, self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_units, self.in_total_max,
-                                             self.n_cand_max, 0, C.byref(self._h)), "mscomp_amd_syncer_create")
+        self._make("mscomp_amd_syncer_create", self.fmt, self.block_size, self.n_res, self.n_blocks_table, self.n_units, self.in_total_max,
+                   self.n_cand_max, 0)
 
     def sync(self, store, d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first, d_lit, d_count, d_res_status, d_status):
         """``store``: one source as BlockSplicer.splice takes them, with its checksums. Unit u = the d_in_len[u] bytes at d_in +
@@ -1546,9 +1412,8 @@ class BlockSyncer(_Handle):
         BlockReader.read takes both arrays; the literal runs d_lit[2 i ..] = (offset in the batch, length), counted by d_lit_first, are
         the bytes no hit covers. d_count (8): raw candidates, thinned, kept, confirmed, hits, literal runs, literal bytes, distinct rows;
         d_res_status one entry per resource of the store, d_status one per unit (MSCOMP_ARG_ERROR: over in_total_max)."""
-        views = _blocks_views([store])
-        _ok(self.ctx.lib.mscomp_amd_syncer_sync(self._h, C.byref(views[0]), *_ptrs(d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first,
-                                                                                   d_lit, d_count, d_res_status, d_status)), "mscomp_amd_syncer_sync")
+        self._run("mscomp_amd_syncer_sync", _blocks_views([store]), d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first, d_lit, d_count,
+                  d_res_status, d_status)
 
     def counts(self):
         """(kept candidates, distinct rows, hits) of the last sync(); synchronizes the stream. A digest syncer hashes every kept window
@@ -1564,8 +1429,7 @@ class BlockSyncer(_Handle):
         _Handle.__init__(self, ctx)
         self.fmt, self.block_size, self.n_res, self.n_blocks_table = None, int(block_size), int(n_res), int(n_blocks_table)
         self.n_units, self.in_total_max, self.n_cand_max = int(n_units), int(in_total_max), int(n_cand_max)
-        _ok(ctx.lib.mscomp_amd_syncer_create_digest(ctx._h, self.block_size, self.n_res, self.n_blocks_table, self.n_units, self.in_total_max,
-                                                    self.n_cand_max, 0, C.byref(self._h)), "mscomp_amd_syncer_create_digest")
+        self._make("mscomp_amd_syncer_create_digest", self.block_size, self.n_res, self.n_blocks_table, self.n_units, self.in_total_max, self.n_cand_max, 0)
         return self
 
     def sync_digest(self, store, d_block_digest, d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off, d_lit_first, d_lit, d_count, d_res_status,
@@ -1573,10 +1437,8 @@ class BlockSyncer(_Handle):
         """sync() on a syncer made by for_digest: a kept candidate is confirmed when the digest of its window of the new data equals the
         four words of ``d_block_digest`` (int32, 4 per table row, as BlockDigester.blocks writes them) at its row. The store's bytes are
         never read -- its d_packed may be None --, its checksums still are: the scan is built from them. d_count[7] = the kept count."""
-        views = _blocks_views([store])
-        _ok(self.ctx.lib.mscomp_amd_syncer_sync_digest(self._h, C.byref(views[0]), *_ptrs(d_block_digest, d_in, d_in_off, d_in_len, d_hit_first, d_req,
-                                                                                          d_req_off, d_lit_first, d_lit, d_count, d_res_status, d_status)),
-            "mscomp_amd_syncer_sync_digest")
+        self._run("mscomp_amd_syncer_sync_digest", _blocks_views([store]), d_block_digest, d_in, d_in_off, d_in_len, d_hit_first, d_req, d_req_off,
+                  d_lit_first, d_lit, d_count, d_res_status, d_status)
 
 
 class BlockDigester(_Handle):
@@ -1589,19 +1451,18 @@ class BlockDigester(_Handle):
     def __init__(self, ctx, block_size, n_res, in_total_max):
         _Handle.__init__(self, ctx)
         self.block_size, self.n_res, self.in_total_max = int(block_size), int(n_res), int(in_total_max)
-        _ok(ctx.lib.mscomp_amd_digester_create(ctx._h, self.block_size, self.n_res, self.in_total_max, 0, C.byref(self._h)), "mscomp_amd_digester_create")
+        self._make("mscomp_amd_digester_create", self.block_size, self.n_res, self.in_total_max, 0)
         self.n_blocks_max = self.n_res + self.in_total_max // self.block_size
 
     def blocks(self, d_data, d_res_off, d_res_len, d_block_digest, d_status):
         """As BlockContainer.crc, a digest for a checksum: d_block_digest (int32, 4 n_blocks_max; entry j belongs to the block compress puts at
         d_block_off[j], the entries behind the last block are zeros) and d_status (n_res: MSCOMP_OK, or MSCOMP_ARG_ERROR past in_total_max)."""
-        _ok(self.ctx.lib.mscomp_amd_digester_blocks(self._h, *_ptrs(d_data, d_res_off, d_res_len, d_block_digest, d_status)), "mscomp_amd_digester_blocks")
+        self._run("mscomp_amd_digester_blocks", d_data, d_res_off, d_res_len, d_block_digest, d_status)
 
     def check(self, d_out, d_out_off, d_res_len, d_block_first, d_block_digest, d_out_len, d_status, d_range=None):
         """As BlockContainer.check: every block of the (clipped) range of every resource that is MSCOMP_OK in d_status is read back from
         d_out and held to d_block_digest; a mismatch turns the resource into MSCOMP_DATA_ERROR with d_out_len = 0."""
-        p = _ptrs(d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_digest, d_out_len, d_status)
-        _ok(self.ctx.lib.mscomp_amd_digester_check(self._h, *p), "mscomp_amd_digester_check")
+        self._run("mscomp_amd_digester_check", d_out, d_out_off, d_res_len, d_block_first, d_range, d_block_digest, d_out_len, d_status)
 
 
 def blocks_digest(buffers, block_size, ctx=None):
@@ -1721,13 +1582,12 @@ class BlockParity(_Handle):
     def __init__(self, ctx, block_size, n_blocks_table, k, m):
         _Handle.__init__(self, ctx)
         self.block_size, self.n_blocks_table, self.k, self.m = int(block_size), int(n_blocks_table), int(k), int(m)
-        _ok(ctx.lib.mscomp_amd_parity_create(ctx._h, self.block_size, self.n_blocks_table, self.k, self.m, 0, C.byref(self._h)), "mscomp_amd_parity_create")
+        self._make("mscomp_amd_parity_create", self.block_size, self.n_blocks_table, self.k, self.m, 0)
 
     def bound(self):
         """(parity rows, parity bytes) a build writes at most: m G_max and m G_max block_size"""
         out = (C.c_uint64 * 2)()
-        if self.ctx.lib.mscomp_amd_parity_bound(self._h, out) != 0:
-            raise MSCompError(MSCOMP_ERRNO, "mscomp_amd_parity_bound")
+        self._run("mscomp_amd_parity_bound", out)           # (answers 0 or MSCOMP_ERRNO)
         return int(out[0]), int(out[1])
 
     def build(self, source, d_par, d_par_off, d_par_crc, d_row_len, d_par_head, d_status, par_cap=None):
@@ -1739,8 +1599,7 @@ class BlockParity(_Handle):
         cap = (0 if d_par is None else d_par.numel()) if par_cap is None else int(par_cap)
         if d_par is not None and cap > d_par.numel():
             raise ValueError("par_cap exceeds d_par")
-        p = _ptrs(d_par, d_par_off, d_par_crc, d_row_len, d_par_head, d_status)
-        _ok(self.ctx.lib.mscomp_amd_parity_build(self._h, _blocks_views([source]), p[0], cap, *p[1:]), "mscomp_amd_parity_build")
+        self._run("mscomp_amd_parity_build", _blocks_views([source]), d_par, cap, d_par_off, d_par_crc, d_row_len, d_par_head, d_status)
 
     def rebuild(self, source, d_verdict, d_par, d_par_off, d_par_crc, d_row_len, d_par_head, d_fix_packed, d_fix_block_off, d_fix_verdict, d_count,
                 d_status, par_len=None, fix_cap=None):
@@ -1753,8 +1612,8 @@ class BlockParity(_Handle):
         parity rows unusable, stored bytes rebuilt; d_status (int32, 1) = MSCOMP_OK, MSCOMP_BUF_ERROR (a rebuilt row beyond fix_cap),
         MSCOMP_DATA_ERROR (a group lost more rows than it has usable parity; or parity of another container), MSCOMP_ARG_ERROR."""
         plen, cap = _byte_bounds(d_par, par_len, d_fix_packed, fix_cap)
-        p = _ptrs(d_verdict, d_par, d_par_off, d_par_crc, d_row_len, d_par_head, d_fix_packed, d_fix_block_off, d_fix_verdict, d_count, d_status)
-        _ok(self.ctx.lib.mscomp_amd_parity_rebuild(self._h, _blocks_views([source]), p[0], p[1], plen, *p[2:7], cap, *p[7:]), "mscomp_amd_parity_rebuild")
+        self._run("mscomp_amd_parity_rebuild", _blocks_views([source]), d_verdict, d_par, plen, d_par_off, d_par_crc, d_row_len, d_par_head, d_fix_packed, cap,
+                  d_fix_block_off, d_fix_verdict, d_count, d_status)
 
     @staticmethod
     def fix_view(source, d_fix_packed, d_fix_block_off, fix_len=None):
@@ -1781,7 +1640,8 @@ def blocks_parity(container, block_size, k, m, ctx=None):
         d_rl, d_head, d_st = torch.zeros(max(1, nbt), dtype=torch.int32, device=dev), torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
         pr.build(srcs[0], d_par, d_off, d_crc, d_rl, d_head, d_st, par_cap=room)
         ctx.stream.synchronize()
-        _ok(int(d_st.cpu()[0]), "mscomp_amd_parity_build")
+        if int(d_st.cpu()[0]) != MSCOMP_OK:                      # (the status build wrote on the device)
+            raise MSCompError(int(d_st.cpu()[0]), "mscomp_amd_parity_build")
         par_off = d_off.cpu().numpy().view(np.uint64).copy()
         out = (d_par.cpu().numpy()[: int(par_off[-1])].copy(), par_off, d_crc.cpu().numpy().view(np.uint32)[:rows].copy(),
                d_rl.cpu().numpy().view(np.uint32)[:nbt].copy(), d_head.cpu().numpy().view(np.uint64).copy())
@@ -1849,8 +1709,7 @@ def res_crc_from_blocks(block_first, lengths, block_crc, block_size, ctx=None):
 def res_crc_dev(ctx, block_size, n_res, n_blocks_table, d_block_first, d_res_len, d_block_crc, d_res_crc, d_status):
     """mscomp_amd_res_crc_dev on torch CUDA tensors: d_res_crc[r] (int32) = the CRC-32 of resource r from d_block_crc, d_status[r] MSCOMP_OK,
     MSCOMP_ARG_ERROR (a table entry beyond n_blocks_table) or MSCOMP_DATA_ERROR (a wrong block count). Kernels on the ctx stream only."""
-    _ok(ctx.lib.mscomp_amd_res_crc_dev(ctx._h, int(block_size), int(n_res), int(n_blocks_table),
-                                       *_ptrs(d_block_first, d_res_len, d_block_crc, d_res_crc, d_status)), "mscomp_amd_res_crc_dev")
+    _run(ctx, "mscomp_amd_res_crc_dev", ctx._h, int(block_size), int(n_res), int(n_blocks_table), d_block_first, d_res_len, d_block_crc, d_res_crc, d_status)
 
 
 def plan_paths(plan):
@@ -1917,10 +1776,7 @@ def compact_dev(ctx, d_src, d_src_off, d_len, align=1, d_packed=None, d_packed_o
         raise ValueError("packed_cap exceeds d_packed")
     if d_packed_off is None:
         d_packed_off = torch.empty(n + 1, dtype=torch.int64, device=d_len.device)
-    st = ctx.lib.mscomp_amd_compact_dev(ctx._h, n, C.c_void_p(d_src.data_ptr()), C.c_void_p(d_src_off.data_ptr()), C.c_void_p(d_len.data_ptr()),
-                                        align, C.c_void_p(d_packed.data_ptr()), int(packed_cap), C.c_void_p(d_packed_off.data_ptr()))
-    if st != MSCOMP_OK:
-        raise MSCompError(st, "mscomp_amd_compact_dev")
+    _run(ctx, "mscomp_amd_compact_dev", ctx._h, n, d_src, d_src_off, d_len, align, d_packed, int(packed_cap), d_packed_off)
     return d_packed, d_packed_off
 
 
@@ -1934,10 +1790,7 @@ def plan_layout_dev(ctx, fmt, d_in_len, align=16, d_off=None, d_cap=None):
         d_off = torch.empty(n + 1, dtype=torch.int64, device=d_in_len.device)
     if d_cap is None:
         d_cap = torch.empty(n, dtype=torch.int64, device=d_in_len.device)
-    st = ctx.lib.mscomp_amd_plan_layout_dev(ctx._h, int(fmt), n, C.c_void_p(d_in_len.data_ptr()), int(align),
-                                            C.c_void_p(d_off.data_ptr()), C.c_void_p(d_cap.data_ptr()))
-    if st != MSCOMP_OK:
-        raise MSCompError(st, "mscomp_amd_plan_layout_dev")
+    _run(ctx, "mscomp_amd_plan_layout_dev", ctx._h, int(fmt), n, d_in_len, int(align), d_off, d_cap)
     return d_off, d_cap
 
 
@@ -1948,9 +1801,7 @@ def layout_dev(ctx, d_cap, align=16, d_off=None):
     n = d_cap.numel()
     if d_off is None:
         d_off = torch.empty(n + 1, dtype=torch.int64, device=d_cap.device)
-    st = ctx.lib.mscomp_amd_layout_dev(ctx._h, n, C.c_void_p(d_cap.data_ptr()), int(align), C.c_void_p(d_off.data_ptr()))
-    if st != MSCOMP_OK:
-        raise MSCompError(st, "mscomp_amd_layout_dev")
+    _run(ctx, "mscomp_amd_layout_dev", ctx._h, n, d_cap, int(align), d_off)
     return d_off
 
 
@@ -2093,10 +1944,7 @@ def compact_batch(ctx, out_off, out_cap, d_out, d_out_len):
     dev = torch.device("cuda", ctx.device)
     d_packed = torch.empty(int(out_cap.sum()) + 16, dtype=torch.uint8, device=dev)
     d_poff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    st = ctx.lib.mscomp_amd_compact_batch(ctx._h, n, C.c_void_p(d_out.data_ptr()), out_off.ctypes.data, out_cap.ctypes.data,
-                                          C.c_void_p(d_out_len.data_ptr()), C.c_void_p(d_packed.data_ptr()), C.c_void_p(d_poff.data_ptr()))
-    if st != MSCOMP_OK:
-        raise MSCompError(st, "mscomp_amd_compact_batch")
+    _run(ctx, "mscomp_amd_compact_batch", ctx._h, n, d_out, out_off.ctypes.data, out_cap.ctypes.data, d_out_len, d_packed, d_poff)
     return d_packed, d_poff
 
 

@@ -2,17 +2,15 @@
 before it touches a device."""
 import ctypes as C
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_blocks_create", "mscomp_amd_blocks_destroy", "mscomp_amd_blocks_bound", "mscomp_amd_blocks_compress", "mscomp_amd_blocks_decompress")
 
 
 def test_blocks_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    hdr = R.check_declared(lib, NAMES)
     assert "typedef struct mscomp_amd_blocks mscomp_amd_blocks;" in hdr
     assert m.BlockContainer is not None and callable(m.blocks_compress) and callable(m.blocks_decompress)
 

@@ -2,17 +2,15 @@
 the header and named in api.EXPORTS, and refuse bad arguments before they touch a device."""
 import ctypes as C
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_plan_create_compress_dev", "mscomp_amd_plan_layout_dev")
 
 
 def test_compress_dev_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    R.check_declared(lib, NAMES)
     assert m.CompressDevPlan is not None and callable(m.plan_layout_dev)
 
 

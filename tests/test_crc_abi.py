@@ -5,6 +5,7 @@ import zlib
 
 import numpy as np
 
+import abi_rig as R
 import blocks_model as M
 import crc_model as K
 
@@ -14,11 +15,7 @@ NAMES = ("mscomp_amd_plan_create_crc_dev", "mscomp_amd_plan_execute_crc_dev", "m
 def test_crc_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(K.HEADER).read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    R.check_declared(lib, NAMES)
     for s in ("CrcDevPlan", "crc32_units", "blocks_crc"):
         assert getattr(m, s) is not None, s
     assert callable(m.BlockContainer.crc) and callable(m.BlockContainer.check)

@@ -2,17 +2,15 @@
 declared in the header and named in api.EXPORTS, and refuse bad arguments before they touch a device."""
 import ctypes as C
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_plan_create_decompress_dev", "mscomp_amd_plan_execute_dev", "mscomp_amd_layout_dev")
 
 
 def test_dev_plan_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    R.check_declared(lib, NAMES)
     assert m.DevPlan is not None and callable(m.layout_dev)
 
 

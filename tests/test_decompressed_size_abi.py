@@ -4,17 +4,15 @@ import ctypes as C
 
 import numpy as np
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_plan_create_size", "mscomp_amd_plan_execute_size", "mscomp_amd_decompressed_size_batch")
 
 
 def test_size_query_is_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    R.check_declared(lib, NAMES)
     assert callable(m.decompressed_sizes) and callable(m.decompress_units_auto) and m.SizePlan is not None
 
 

@@ -2,7 +2,8 @@
 arguments before they touch a device -- in the manner of tests/test_splice_abi.py. (The refusals of a call that need a deduper, and with it
 a device, are in tests/test_gpu_dedup.py.)"""
 import ctypes as C
-import re
+
+import abi_rig as R
 
 NAMES = ("mscomp_amd_deduper_create", "mscomp_amd_deduper_destroy", "mscomp_amd_deduper_dedup")
 PROTOTYPES = (
@@ -17,13 +18,7 @@ PROTOTYPES = (
 def test_dedup_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))        # the header without comments, on one line ...
-    flat = flat.replace(" ,", ",").replace(" )", ")")                            # ... and without the gaps they leave
-    for s, proto in zip(NAMES, PROTOTYPES):
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert proto in flat, s
+    hdr = R.check_declared(lib, NAMES, PROTOTYPES)
     assert "typedef struct mscomp_amd_deduper mscomp_amd_deduper;" in hdr
     assert hdr.index("mscomp_amd_splicer_splice(") < hdr.index("mscomp_amd_deduper_create(") < hdr.index("mscomp_amd_res_crc_dev(")   # behind the splicer's section
     assert callable(m.BlockDeduper.dedup) and callable(m.blocks_dedup)

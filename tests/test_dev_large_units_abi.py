@@ -2,23 +2,18 @@
 mscomp_amd_plan_create_size_dev_ex and the test hook mscomp_amd_debug_plan_paths are declared, exported and bound; the argument checks of
 the two creators, which need no GPU."""
 import ctypes as C
-import os
 import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_rig as R
+
 NAMES = ("mscomp_amd_plan_create_decompress_dev_ex", "mscomp_amd_plan_create_size_dev_ex", "mscomp_amd_debug_plan_paths")
 
 
 def test_the_three_names_are_declared_exported_and_bound():
     import ms_compress_amd as m
     lib = m.load_library()
-    header = open(os.path.join(ROOT, "include", "mscomp_amd.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    for name in NAMES:
-        assert re.search(r"\b%s\s*\(" % name, code), name + " is not declared in include/mscomp_amd.h"
-        assert hasattr(lib, name), "libmscomp_amd.so does not export " + name
-        assert name in m.api.EXPORTS
-    assert re.search(r"#define\s+MSCOMP_AMD_DEV_LARGE_UNITS\s+1u\b", code)
+    R.check_declared(lib, NAMES)
+    assert re.search(r"#define\s+MSCOMP_AMD_DEV_LARGE_UNITS\s+1u\b", R.flat_header())
     assert m.api.MSCOMP_AMD_DEV_LARGE_UNITS == 1
 
 

@@ -2,7 +2,8 @@
 and refuse bad arguments before they touch a device -- in the manner of tests/test_dedup_abi.py. (The refusals of a call that need a
 deduper, and with it a device, are in tests/test_gpu_diff.py.)"""
 import ctypes as C
-import re
+
+import abi_rig as R
 
 NAMES = ("mscomp_amd_deduper_create_diff", "mscomp_amd_deduper_diff")
 PROTOTYPES = (
@@ -17,13 +18,7 @@ PROTOTYPES = (
 def test_diff_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))        # the header without comments, on one line ...
-    flat = flat.replace(" ,", ",").replace(" )", ")")                            # ... and without the gaps they leave
-    for s, proto in zip(NAMES, PROTOTYPES):
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert proto in flat, s
+    hdr = R.check_declared(lib, NAMES, PROTOTYPES)
     assert "#define MSCOMP_AMD_DIFF_NO_BASE 0xFFFFFFFFFFFFFFFFull" in hdr and m.MSCOMP_AMD_DIFF_NO_BASE == 0xFFFFFFFFFFFFFFFF
     assert hdr.index("mscomp_amd_deduper_dedup(") < hdr.index("mscomp_amd_deduper_create_diff(") < hdr.index("mscomp_amd_res_crc_dev(")   # behind the deduper's section
     for part in ("Creation:", "Scratch:", "Sources:", "Notation:", "Rules:", "Consequence:", "Checksums:", "Execution:", "Left out:"):

@@ -4,6 +4,8 @@ tests/test_sync_abi.py. (The refusals of a call that need an object, and with it
 import ctypes as C
 import re
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_digester_create", "mscomp_amd_digester_destroy", "mscomp_amd_digester_blocks", "mscomp_amd_digester_check",
          "mscomp_amd_syncer_create_digest", "mscomp_amd_syncer_sync_digest")
 PROTOTYPES = (
@@ -25,13 +27,7 @@ PROTOTYPES = (
 def test_digest_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))        # the header without comments, on one line ...
-    flat = flat.replace(" ,", ",").replace(" )", ")")                            # ... and without the gaps they leave
-    for s, proto in zip(NAMES, PROTOTYPES):
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert proto in flat, s
+    hdr = R.check_declared(lib, NAMES, PROTOTYPES)
     # behind the syncer's section, in front of the resource checksums
     assert hdr.index("mscomp_amd_syncer_counts(") < hdr.index("/* Digests:") < hdr.index("mscomp_amd_digester_create(") < hdr.index("/* Resource checksums")
     section = hdr[hdr.index("/* Digests:"): hdr.index("MSCompStatus mscomp_amd_digester_create(")]

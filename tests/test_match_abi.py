@@ -2,7 +2,8 @@
 and refuse bad arguments before they touch a device -- in the manner of tests/test_diff_abi.py. (The refusals of a call that need a
 deduper, and with it a device, are in tests/test_gpu_match.py.)"""
 import ctypes as C
-import re
+
+import abi_rig as R
 
 NAMES = ("mscomp_amd_deduper_create_match", "mscomp_amd_deduper_match")
 PROTOTYPES = (
@@ -17,13 +18,7 @@ PROTOTYPES = (
 def test_match_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))        # the header without comments, on one line ...
-    flat = flat.replace(" ,", ",").replace(" )", ")")                            # ... and without the gaps they leave
-    for s, proto in zip(NAMES, PROTOTYPES):
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert proto in flat, s
+    hdr = R.check_declared(lib, NAMES, PROTOTYPES)
     # behind diff's section, in front of the transcoder's
     assert hdr.index("mscomp_amd_deduper_diff(") < hdr.index("mscomp_amd_deduper_create_match(") < hdr.index("mscomp_amd_deduper_match(")
     assert hdr.index("mscomp_amd_deduper_match(mscomp_amd_deduper* dd") < hdr.index("typedef struct mscomp_amd_transcoder")

@@ -5,6 +5,8 @@ tests/test_gpu_parity_rows.py.)"""
 import ctypes as C
 import re
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_parity_create", "mscomp_amd_parity_destroy", "mscomp_amd_parity_bound", "mscomp_amd_parity_build", "mscomp_amd_parity_rebuild")
 PROTOTYPES = (
     "MSCompStatus mscomp_amd_parity_create(mscomp_amd_ctx* ctx, uint32_t block_size, uint64_t n_blocks_table, uint32_t k, uint32_t m, "
@@ -26,13 +28,7 @@ LEFT_OUT = ("d_par_off, d_par_crc, d_row_len, d_par_head", "d_block_first / d_re
 def test_parity_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))        # the header without comments, on one line ...
-    flat = flat.replace(" ,", ",").replace(" )", ")")                            # ... and without the gaps they leave
-    for s, proto in zip(NAMES, PROTOTYPES):
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert proto in flat, s
+    hdr, flat = R.check_declared(lib, NAMES, PROTOTYPES), R.flat_header()
     for name, value in (("K_MAX", 255), ("M_MAX", 3)):
         assert re.search(r"#define MSCOMP_AMD_PARITY_%s +%du\b" % (name, value), hdr), name
         assert getattr(m, "MSCOMP_AMD_PARITY_" + name) == value

@@ -2,17 +2,15 @@
 before it touches a device."""
 import ctypes as C
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_reader_create", "mscomp_amd_reader_destroy", "mscomp_amd_reader_read", "mscomp_amd_reader_counts")
 
 
 def test_reader_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    hdr = R.check_declared(lib, NAMES)
     assert "typedef struct mscomp_amd_reader mscomp_amd_reader;" in hdr
     assert m.BlockReader is not None and callable(m.blocks_read)
 

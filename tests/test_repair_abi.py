@@ -4,6 +4,8 @@ tests/test_diff_abi.py. (The refusals that need a container or a deduper, and wi
 import ctypes as C
 import re
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_blocks_salvage", "mscomp_amd_deduper_create_repair", "mscomp_amd_deduper_repair")
 PROTOTYPES = (
     "MSCompStatus mscomp_amd_blocks_salvage(mscomp_amd_blocks* bk, const uint8_t* d_packed, uint64_t packed_len, "
@@ -22,13 +24,7 @@ PARTS = ("Creation:", "Scratch:", "Sources:", "Notation:", "Rules:", "Consequenc
 def test_repair_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))        # the header without comments, on one line ...
-    flat = flat.replace(" ,", ",").replace(" )", ")")                            # ... and without the gaps they leave
-    for s, proto in zip(NAMES, PROTOTYPES):
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert proto in flat, s
+    hdr = R.check_declared(lib, NAMES, PROTOTYPES)
     for name, value in VERDICTS:
         assert re.search(r"#define MSCOMP_AMD_BLOCK_%s +%du\b" % (name, value), hdr), name
         assert getattr(m, "MSCOMP_AMD_BLOCK_" + name) == value

@@ -2,17 +2,15 @@
 arguments before they touch a device -- in the manner of tests/test_writer_abi.py. The creators still take no flags."""
 import ctypes as C
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_writer_resize", "mscomp_amd_res_crc_dev")
 
 
 def test_resize_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    R.check_declared(lib, NAMES)
     assert callable(m.BlockWriter.resize) and callable(m.blocks_resize) and callable(m.res_crc_from_blocks) and callable(m.res_crc_dev)
 
 

@@ -8,6 +8,8 @@ import re
 import subprocess
 import sys
 
+import abi_rig as R
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("mscomp_amd_debug_scratch_names", "mscomp_amd_debug_scratch_poison", "mscomp_amd_debug_scratch_report")
 PROTOTYPES = (
@@ -34,13 +36,8 @@ def _ctx_members():
 def test_scratch_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
-    flat = flat.replace(" ,", ",").replace(" )", ")")
-    for s, proto in zip(NAMES, PROTOTYPES):
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert proto in flat, s
+    R.check_declared(lib, NAMES, PROTOTYPES)
+    flat = R.flat_header()
     for k, name in enumerate(KINDS):
         assert "#define MSCOMP_AMD_SCRATCH_%s %d " % (name, k) in flat + " ", name
     assert "typedef struct mscomp_amd_scratch_rec { const char* name; uint64_t asked, cap, changed; } mscomp_amd_scratch_rec;" in flat

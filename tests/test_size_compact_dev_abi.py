@@ -2,6 +2,8 @@
 exported, declared in the header and named in api.EXPORTS, and refuse bad arguments before they touch a device."""
 import ctypes as C
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_plan_create_size_dev", "mscomp_amd_plan_execute_size_dev", "mscomp_amd_compact_dev")
 FAKE = C.c_void_p(8)                                              # a non-null pointer that must never be followed
 
@@ -9,11 +11,8 @@ FAKE = C.c_void_p(8)                                              # a non-null p
 def test_size_compact_dev_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
+    R.check_declared(lib, NAMES)
     for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
         assert getattr(lib, s).argtypes is not None and getattr(lib, s).restype is C.c_int, s
     assert m.SizeDevPlan is not None and callable(m.compact_dev)
     assert m.SizeDevPlan.execute is not m.DevPlan.execute

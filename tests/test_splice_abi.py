@@ -2,17 +2,15 @@
 touch a device -- in the manner of tests/test_resize_abi.py."""
 import ctypes as C
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_splicer_create", "mscomp_amd_splicer_destroy", "mscomp_amd_splicer_splice")
 
 
 def test_splice_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    hdr = R.check_declared(lib, NAMES)
     assert "#define MSCOMP_AMD_SPLICE_SRC_MAX 4u" in hdr and "mscomp_amd_blocks_view" in hdr and m.MSCOMP_AMD_SPLICE_SRC_MAX == 4
     assert callable(m.BlockSplicer.splice) and callable(m.blocks_splice)
     assert C.sizeof(m.BlocksView) == 64                           # eight words, as the header lays them out

@@ -4,17 +4,15 @@ import ctypes as C
 
 import pytest
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_splicer_create_extents", "mscomp_amd_splicer_splice_extents")
 
 
 def test_extents_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    hdr = R.check_declared(lib, NAMES)
     assert "#define MSCOMP_AMD_SPLICE_ROW_TILE %du" % m.MSCOMP_AMD_SPLICE_ROW_TILE in hdr
     assert callable(m.BlockSplicer.for_extents) and callable(m.BlockSplicer.splice_extents)
     assert all(callable(f) for f in (m.blocks_splice_extents, m.blocks_concat, m.blocks_split_at, m.blocks_cut_range))

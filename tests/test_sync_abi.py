@@ -4,6 +4,8 @@ and with it a device, are in tests/test_gpu_sync.py.)"""
 import ctypes as C
 import re
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_syncer_create", "mscomp_amd_syncer_destroy", "mscomp_amd_syncer_sync", "mscomp_amd_syncer_counts")
 PROTOTYPES = (
     "MSCompStatus mscomp_amd_syncer_create(mscomp_amd_ctx* ctx, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, "
@@ -19,13 +21,7 @@ PROTOTYPES = (
 def test_sync_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))        # the header without comments, on one line ...
-    flat = flat.replace(" ,", ",").replace(" )", ")")                            # ... and without the gaps they leave
-    for s, proto in zip(NAMES, PROTOTYPES):
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert proto in flat, s
+    hdr = R.check_declared(lib, NAMES, PROTOTYPES)
     # behind the transcoder's section, in front of the resource checksums
     assert hdr.index("mscomp_amd_transcoder_counts(") < hdr.index("mscomp_amd_syncer_create(") < hdr.index("mscomp_amd_res_crc_dev(mscomp_amd_ctx* ctx")
     section = hdr[hdr.index("/* Sync:"): hdr.index("MSCompStatus mscomp_amd_syncer_create(")]

@@ -2,7 +2,8 @@
 refuse bad arguments before they touch a device -- in the manner of tests/test_diff_abi.py. (The refusals of a call that need a
 transcoder, and with it a device, are in tests/test_gpu_transcode.py.)"""
 import ctypes as C
-import re
+
+import abi_rig as R
 
 NAMES = ("mscomp_amd_transcoder_create", "mscomp_amd_transcoder_destroy", "mscomp_amd_transcoder_transcode", "mscomp_amd_transcoder_counts")
 PROTOTYPES = (
@@ -22,13 +23,7 @@ LZNT1, XPRESS, XHUFF = 2, 3, 4
 def test_transcoder_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    flat = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))        # the header without comments, on one line ...
-    flat = flat.replace(" ,", ",").replace(" )", ")")                            # ... and without the gaps they leave
-    for s, proto in zip(NAMES, PROTOTYPES):
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert proto in flat, s
+    hdr = R.check_declared(lib, NAMES, PROTOTYPES)
     assert hdr.index("mscomp_amd_deduper_diff(") < hdr.index("mscomp_amd_transcoder_create(") < hdr.index("mscomp_amd_res_crc_dev(")   # behind the deduper's section
     doc = hdr[hdr.index("/* Block transcoders:"): hdr.index("typedef struct mscomp_amd_transcoder")]
     for part in ("Creation:", "Contract:", "Rules:", "Counts:", "Execution:", "What carrying trusts"):

@@ -2,17 +2,15 @@
 before it touches a device -- the ladder of tests/test_reader_abi.py, which mscomp_amd_writer_create follows check for check."""
 import ctypes as C
 
+import abi_rig as R
+
 NAMES = ("mscomp_amd_writer_create", "mscomp_amd_writer_destroy", "mscomp_amd_writer_write", "mscomp_amd_writer_counts")
 
 
 def test_writer_symbols_are_exported_and_declared():
     import ms_compress_amd as m
     lib = m.load_library()
-    hdr = open(m.api.HERE + "/../include/mscomp_amd.h").read()
-    for s in NAMES:
-        assert hasattr(lib, s), s
-        assert s in m.api.EXPORTS, s
-        assert s + "(" in hdr, s
+    hdr = R.check_declared(lib, NAMES)
     assert "typedef struct mscomp_amd_writer mscomp_amd_writer;" in hdr
     assert m.BlockWriter is not None and callable(m.blocks_write)
 
