@@ -1613,7 +1613,7 @@ int          mscomp_amd_debug_lzg_open(mscomp_amd_ctx* ctx, uint64_t words, uint
 void         mscomp_amd_debug_set_finder(int mode);
 /* Test hook: how a host-pointer ms_compress(MSCOMP_LZNT1) of a large buffer (>= 36 MiB) runs. 0 = default (the caller's buffers are mapped
  * into the GPU's address space, one launch; falls back to 1 when the mapping fails), 1 = always in slices on three streams
- * (csrc/api.hip lznt1_compress_pipelined; the same as MSCOMP_AMD_ONE_ZEROCOPY=0 in the environment). Same bytes and statuses. Process-wide. */
+ * (csrc/oneshot.hip lznt1_compress_pipelined; the same as MSCOMP_AMD_ONE_ZEROCOPY=0 in the environment). Same bytes and statuses. Process-wide. */
 void         mscomp_amd_debug_set_one_shot(int mode);
 /* Test hook: the LZNT1 chunk stage has two bit-identical kernels (one wave / four waves per 4 KiB chunk). 0 = default, 1 / 2 = force. */
 void         mscomp_amd_debug_set_lznt1(int mode);

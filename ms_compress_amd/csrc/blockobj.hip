@@ -1,5 +1,5 @@
 // blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h): containers, readers, writers, splicers and dedupers. Host orchestration only, as
-// api.hip: each call runs the launches of inner dev plans (dev_launch) between its own passes, through plan_run.
+// plan_dev.hip: each call runs the launches of inner dev plans (dev_launch) between its own passes, through plan_run.
 #include "host.h"
 
 using namespace msc;
@@ -1362,7 +1362,7 @@ MSCompStatus mscomp_amd_parity_rebuild(mscomp_amd_parity* pr, const mscomp_amd_b
 	});
 }
 
-// ---- the scratch hooks' view of the objects above (api.hip: mscomp_amd_debug_scratch_*) ----
+// ---- the scratch hooks' view of the objects above (hooks.hip: mscomp_amd_debug_scratch_*) ----
 extern "C++" mscomp_amd_ctx* msc::scratch_of_object(int kind, void* obj, std::vector<ScratchEnt>& v)
 {
 	const auto access = [&v](BlockAccess* a) { v.push_back(ScratchEnt{ "tab", &a->tab, false }); v.push_back(ScratchEnt{ "cache", &a->in.cache, false }); scratch_of_plan(a->in.dplan, 2, v); };

@@ -1,6 +1,6 @@
 // blocks.hip -- the table, select, raw-copy and fold passes of a block container (mscomp_amd_blocks_*, include/mscomp_amd.h): a batch of
 // resources cut into blocks of B = 1 << shift bytes, every block compressed on its own or stored raw, packed back to back behind a table of
-// offsets. The two big stages are a compress and a decompress dev plan over the blocks as units (api.hip runs them between these passes,
+// offsets. The two big stages are a compress and a decompress dev plan over the blocks as units (blockobj.hip runs them between these passes,
 // unchanged); the pack pass is compaction's copy with a source address per unit (devplan.hip cpd_copy_kernel<true>). DESIGN.md 4.7.
 #include "kernels.h"
 

@@ -118,7 +118,7 @@ struct BatchTables {
 };
 
 // ---- the counts a plan is sized by ------------------------------------------------------------------------
-// One definition for the host (api.hip: exact tables of host plans, bounds of dev plans) and for the table passes that build the same
+// One definition for the host (plan.hip, plan_dev.hip: exact tables of host plans, bounds of dev plans) and for the table passes that build the same
 // tables on the device (devplan.hip): a dev plan gives the host plan's bytes and statuses because both take their counts from here.
 // `format` is the MSCompFormat value: 2 LZNT1, 3 Xpress, 4 Xpress+Huffman.
 #define LZD_SEG        49152u                             // LZNT1 decompression: input bytes per segment of the header walk
@@ -150,7 +150,7 @@ __host__ __device__ inline u64 candidate_slots(u64 len, u64 cap)
 	return most + most / 4u + 2u;
 }
 // ---- the optional paths of a decompress / size plan --------------------------------------------------------
-// Which units take them and what they add to the path's tables: api.hip plan_create_impl decides with these on the host, the path pass of a
+// Which units take them and what they add to the path's tables: plan.hip plan_create_impl decides with these on the host, the path pass of a
 // dev plan with large units (devplan.hip dv_paths_kernel) on the device, so both make the same decisions for the same per-unit values.
 #define XPS_MIN_IN (512u << 10)                           // Xpress streams with at least this much input are walked by segments (xpress_decode.hip, xps_*)
 #define LZG_MIN_CAP (1u << 20)                            // units with at least this much output capacity get their bytes from all CUs (lzglobal.hip), when the plan has the scratch for it

@@ -28,7 +28,7 @@ __global__ __launch_bounds__(DV_THREADS) void dv_tables_kernel(int format, uint3
 		dv_block_scan<2>(r, run, s_w);                                   // running totals up to and including unit i
 		const bool rej = live && (len > 0xFFFFF000ull || r[0] > in_max || (!SIZING && r[1] > out_max));
 		const u64 L = rej ? 0 : len, C = rej ? 0 : cap;                  // a rejected unit is an empty unit without room
-		// the counts of a host plan (common.h; api.hip plan_create_impl): chunks; token slots; Xpress+Huffman candidate slots
+		// the counts of a host plan (common.h; plan.hip plan_create_impl): chunks; token slots; Xpress+Huffman candidate slots
 		u64 c[3] = {0, 0, 0};
 		if (live) {
 			if (format == 2) { c[0] = decode_chunks(2, L); }

@@ -1,5 +1,6 @@
-// host.h -- what the host files of the library share (api.hip, blockobj.hip): the context, the plan, their helpers and plan_run.
-// Internal: not installed, not part of include/. What it adds to namespace msc is not exported from the library (hidden visibility).
+// host.h -- what the host files of the library share (ctx, plan, launch, plan_dev, hooks, oneshot, blockobj, hostbatch .hip): the context,
+// the plan, their helpers, plan_run and what one host file takes from another; the kernel files take the switch table and the environment
+// accessors from it. Internal: not installed, not part of include/. What it adds to namespace msc is not exported (hidden visibility).
 #pragma once
 #include "../../include/mscomp_amd.h"
 #include "kernels.h"
@@ -13,8 +14,22 @@
 #pragma GCC visibility push(hidden)
 namespace msc {
 
-// the process-wide half of a captured graph's age (api.hip defines it, beside the test hooks that bump it): ONE object for all host files
-extern std::atomic<uint64_t> g_mode_epoch;
+// The process-wide kernel switches (hooks.hip defines the object, beside the mscomp_amd_debug_set_* hooks that store into it): each picks
+// between bit-identical kernels for the tests, and the launchers read theirs with a relaxed load -- any thread may call a hook while other
+// threads execute plans. `epoch` is the process-wide half of a captured graph's age: a hipGraph of a plan holds raw scratch pointers and a
+// kernel choice, and two counters say when it is stale: the context's own epoch (bumped whenever one of ITS device buffers moves; a context
+// is used by one host thread at a time, so a plain counter) and this one, bumped by every hook that switches kernels.
+struct Switches {
+	std::atomic<int> finder{1};                        // 1 = default (Xpress units up to 64 KiB: the lazy finder, xpress_lazy.hip), 2 = Find for every position everywhere
+	std::atomic<int> xpd{0};                           // Xpress decompression: 0 = tokens a flag word at a time + copy kernels (default; large streams by segments), 1 = xpd_kernel (a token at a time, bytes in the same wave), 2 = as 0 without the segments
+	std::atomic<int> lznt1{0};                         // LZNT1 chunk kernel: 0 = default, 1 = one wave per chunk, 2 = four waves per chunk
+	std::atomic<int> xpress_emit{0};                   // Xpress parse/emit: 0 = by batch size, 1 = one wave per unit, 2 / 3 = 4 / 16 waves per unit, 4 = a block per super-block
+	std::atomic<int> place_cap{0};                     // at most this many blocks for the LZNT1 placement (util.hip concat_slots_kernel), 0 = the device's grid
+	std::atomic<int> one_zero_copy{1};                 // large host-pointer calls: 1 = caller buffers mapped, one launch / uploads in ranges (default), 0 = slices on three streams / one copy (MSCOMP_AMD_ONE_ZEROCOPY=0)
+	std::atomic<int> lznt1_sa_default{0};              // 1 = LZNT1 compresses with the suffix-array dictionary flavour (lznt1_sa.hip; the reference's MSCOMP_WITH_LZNT1_SA_DICT build) where a context says nothing (MSCOMP_AMD_LZNT1_SA_DICT)
+	std::atomic<uint64_t> epoch{1};
+};
+extern Switches g_sw;
 
 struct DevBuf {
 	void* p = nullptr; size_t cap = 0;
@@ -55,7 +70,7 @@ struct ProfRec { const char* name; hipEvent_t a, b; };
 template <size_t N> struct GraphRun {
 	hipGraphExec_t exec = nullptr;
 	const void* args[N] = {};
-	uint64_t epoch = 0, mode = 0;                      // mscomp_amd_ctx::epoch and g_mode_epoch when `exec` was captured
+	uint64_t epoch = 0, mode = 0;                      // mscomp_amd_ctx::epoch and g_sw.epoch when `exec` was captured
 	uint32_t executions = 0;
 	bool never = false;                                // never replays: a call with nothing to report on; a one-shot plan (its buffer addresses change: it would be re-captured every time)
 	~GraphRun() { if (exec) { (void)hipGraphExecDestroy(exec); } }
@@ -226,15 +241,46 @@ struct KernelTimer {
 	~KernelTimer() { if (c->profiling) { (void)hipEventRecord(r.b, c->stream); c->recs.push_back(r); } }
 };
 
-// defined in api.hip, where their comments are
+// ---- what one host file takes from another: defined in the file named, where the comments are ----
+// hooks.hip: the gate of the test hooks, the environment (one accessor per MSCOMP_AMD_* variable: INTEGRATION.md 5), a plan's own buffers
+#define HB_SLOTS 8                                     // sub-batches in flight per device range (hostbatch.hip), the most and the default of MSCOMP_AMD_HOST_SLOTS
 bool test_hooks_on();
+uint64_t env_lzg_budget(); uint64_t env_xhc_scr_budget(); bool env_no_graph(); size_t env_one_slice(); size_t env_one_ranged_min(); uint32_t env_one_range_chunks();
+size_t env_host_batch_bytes(); size_t env_host_slots(); bool env_host_order(); bool env_host_trace();
+uint32_t env_xps_seg(); uint32_t env_xps_warm(); uint32_t env_xps_rounds(); uint32_t env_lzb_min_bytes(); uint32_t env_lzg_hops();
+void scratch_of_plan(mscomp_amd_plan* p, int owner, std::vector<ScratchEnt>& v);
+// ctx.hip
+bool lznt1_sa_for(const mscomp_amd_ctx* c);
+uint64_t optional_scratch_budget(uint64_t env_cap, size_t already_held);
+// plan.hip
+bool reserve_tables(mscomp_amd_plan* p);
+bool reserve_compress_scratch(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, size_t n_chunks, bool lznt1_sa);
+bool reserve_decode_scratch(mscomp_amd_ctx* c, MSCompFormat format, size_t n_units, size_t n_chunks, uint64_t slots, uint64_t cands, bool store);
+bool reserve_xps(mscomp_amd_plan* p, size_t nb, uint64_t sg);
+bool reserve_lzg(mscomp_amd_plan* p, size_t nb, uint64_t tb, uint64_t tl, uint64_t wd);
+MSCompStatus plan_create_impl(mscomp_amd_ctx* c, MSCompFormat format, bool decompress, size_t n_units, const uint64_t* in_off, const uint64_t* in_len,
+                              const uint64_t* out_off, const uint64_t* out_cap, mscomp_amd_plan** out, bool sizing = false);
+// launch.hip
 void note_modes(mscomp_amd_plan* p);
+void decode_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status);
+void compress_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint8_t* d_out, uint64_t* d_out_len, int32_t* d_status);
+void size_launch(mscomp_amd_plan* p, const uint8_t* d_in, uint64_t* d_out_len, uint64_t* d_need, int32_t* d_status);
+// plan_dev.hip
 bool decode_dev_counts(MSCompFormat format, uint64_t N, uint64_t in_total_max, uint64_t O, bool sizing, uint64_t& I, uint64_t& chunks, uint64_t& toks, uint64_t& cands);
 void dev_launch(mscomp_amd_plan* p, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                 uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, int32_t* d_status);
-void scratch_of_plan(mscomp_amd_plan* p, int owner, std::vector<ScratchEnt>& v);
-// defined in blockobj.hip: the buffers of a block object (kind: MSCOMP_AMD_SCRATCH_BLOCKS ..) and its context; null: no such object
+// oneshot.hip: the calling thread's one-shot context (null: it has made no such call); host_pins_hold / _release are below this block
+mscomp_amd_ctx* one_shot_ctx();
+// blockobj.hip: the buffers of a block object (kind: MSCOMP_AMD_SCRATCH_BLOCKS ..) and its context; null: no such object
 mscomp_amd_ctx* scratch_of_object(int kind, void* obj, std::vector<ScratchEnt>& v);
+
+// what opens every plan creator: *out cleared, then the context, the unit count and the format (a CRC plan has none: true)
+inline bool creator_args(mscomp_amd_ctx* c, size_t n_units, bool format_ok, mscomp_amd_plan** out)
+{
+	if (!out) { return false; }
+	*out = nullptr;
+	return c && n_units <= 0x7FFFFFF0u && format_ok;
+}
 
 // One execution of a call: its launches, given as `launch`. A call that is executed repeatedly replays them as one hipGraph (the gaps between
 // the 4-9 launches are ~3 % of an LZNT1 pass): captured in the call's record `r` on the second execution and again whenever a word of
@@ -247,9 +293,8 @@ static MSCompStatus plan_run(GraphRun<N>& r, mscomp_amd_ctx* c, const void* cons
 {
 	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
 	if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-	static const bool no_graph = getenv("MSCOMP_AMD_NO_GRAPH") != nullptr;
-	if (cs == hipStreamCaptureStatusNone && !no_graph && !r.never && !c->profiling && ++r.executions >= 2) {
-		const uint64_t mode_now = g_mode_epoch.load(std::memory_order_acquire);
+	if (cs == hipStreamCaptureStatusNone && !env_no_graph() && !r.never && !c->profiling && ++r.executions >= 2) {
+		const uint64_t mode_now = g_sw.epoch.load(std::memory_order_acquire);
 		const bool same = r.exec && r.epoch == c->epoch && r.mode == mode_now && memcmp(r.args, args, sizeof args) == 0;
 		if (!same) {
 			if (r.exec) { (void)hipGraphExecDestroy(r.exec); r.exec = nullptr; }
@@ -272,3 +317,10 @@ static MSCompStatus plan_run(GraphRun<N>& r, mscomp_amd_ctx* c, const void* cons
 
 } // namespace msc
 #pragma GCC visibility pop
+
+namespace msc {
+// oneshot.hip, for the other host paths (hostbatch.hip): keep every registration (page-lock) that a large one-shot call holds on caller memory
+// and that overlaps [ptr, ptr + n) alive until the returned token is given back (nullptr: nothing overlapped). Dynamic symbols of the library: outside the hidden block.
+void* host_pins_hold(const void* ptr, size_t n);
+void host_pins_release(void* token);
+}

@@ -1,6 +1,6 @@
 // hostbatch.hip -- mscomp_amd_compress_units_host: n independent units given by HOST pointers, compressed on one or several GPUs of this
 // process (SURVEY.md 8e "Multi-GPU" + 8f-3 "host pipeline"): the caller-facing form of the per-GPU shard that bench.py runs one process per
-// GPU. Host orchestration only -- every output byte comes from the HIP kernels behind the batch interface of api.hip.
+// GPU. Host orchestration only -- every output byte comes from the HIP kernels behind the batch interface of plan.hip.
 //
 // The reference has no counterpart: ms_compress (/root/reference/src/mscomp.cpp:113-117) is one buffer per call on one thread. Each unit
 // here is exactly one such call (same bytes, same MSCOMP_OK / MSCOMP_BUF_ERROR, the uncounted LZNT1 00 00 behind the stream when the
@@ -19,8 +19,7 @@
 // This file is compiled WITH C++ exceptions (csrc/Makefile; the rest of the library is -fno-exceptions): it builds std::vector tables and
 // starts std::threads inside extern "C" entries, and an allocation or thread-creation failure there must come back as MSCOMP_MEM_ERROR,
 // not end the caller's process. Every thread body and both entries catch; threads that did start are always joined.
-#include "../../include/mscomp_amd.h"
-#include <hip/hip_runtime.h>
+#include "host.h"
 #include <new>
 #include <algorithm>
 #include <atomic>
@@ -33,14 +32,7 @@
 #include <thread>
 #include <vector>
 
-namespace msc {       // api.hip: registrations (page-locks) other threads' large one-shot calls hold on caller memory
-void* host_pins_hold(const void* ptr, size_t n);
-void host_pins_release(void* token);
-}
-
 namespace {
-
-#define HB_SLOTS 8                                        // sub-batches in flight per device range
 
 // One sub-batch in flight: its own context (stream `ex`, scratch), device buffers and pinned result words. Kept between calls.
 struct Slot {
@@ -141,8 +133,7 @@ struct Batch { size_t b0, b1; std::vector<uint64_t> in_off, in_len, out_off, out
 // where one batch costs 8.6
 size_t batch_bytes(MSCompFormat format, bool decompress)
 {
-	static const long env = [] { const char* e = getenv("MSCOMP_AMD_HOST_BATCH_MB"); const long x = e ? atol(e) : 0; return (x >= 1 && x <= 65536) ? x : 0L; }();
-	if (env) { return (size_t)env << 20; }
+	if (msc::env_host_batch_bytes()) { return msc::env_host_batch_bytes(); }
 	return (size_t)((format == MSCOMP_XPRESS_HUFF && !decompress) ? 96 : 32) << 20;
 }
 
@@ -203,7 +194,7 @@ MSCompStatus run_range(Worker* w, const Job& j, size_t u0, size_t u1, bool on_ca
 	if (nb == 0) { return MSCOMP_OK; }
 	// the sub-batch with the largest UNIT first: the kernels of a large file (Xpress+Huffman: its chunks form one chain of serial stages) are the
 	// critical path of the range, everything else runs beside them (stable: equal sub-batches keep the caller's order)
-	if (!(getenv("MSCOMP_AMD_HOST_ORDER") && *getenv("MSCOMP_AMD_HOST_ORDER") == '0')) {
+	if (msc::env_host_order()) {                                 // (MSCOMP_AMD_HOST_ORDER=0: the caller's order)
 		std::vector<uint64_t> big(nb, 0);
 		for (size_t k = 0; k < nb; ++k) { for (uint64_t l : batches[k].in_len) { if (l > big[k]) { big[k] = l; } } }
 		std::vector<size_t> ord(nb);
@@ -213,11 +204,11 @@ MSCompStatus run_range(Worker* w, const Job& j, size_t u0, size_t u1, bool on_ca
 		for (size_t k = 0; k < nb; ++k) { sorted.push_back(std::move(batches[ord[k]])); }
 		batches.swap(sorted);
 	}
-	static const size_t nslots = [] { const char* e = getenv("MSCOMP_AMD_HOST_SLOTS"); const long x = e ? atol(e) : HB_SLOTS; return (size_t)(x >= 1 && x <= HB_SLOTS ? x : HB_SLOTS); }();   // sub-batches in flight (212 MB corpus, 32 MiB sub-batches: 2 / 4 / 8 slots -> Xpress 11.7 / 9.3 / 8.5 ms, Xpress+Huffman 23.9 / 16.4 / 14.2 ms)
+	const size_t nslots = msc::env_host_slots();                 // MSCOMP_AMD_HOST_SLOTS: sub-batches in flight (212 MB corpus, 32 MiB sub-batches: 2 / 4 / 8 slots -> Xpress 11.7 / 9.3 / 8.5 ms, Xpress+Huffman 23.9 / 16.4 / 14.2 ms)
 
 	std::mutex mu; std::condition_variable cv;
 	std::vector<char> uploaded(nb, 0), launched(nb, 0);
-	static const bool trace = getenv("MSCOMP_AMD_HOST_TRACE") != nullptr;   // dev: a time line of the sub-batches on stderr
+	const bool trace = msc::env_host_trace();                    // MSCOMP_AMD_HOST_TRACE, dev: a time line of the sub-batches on stderr
 	const auto t_zero = std::chrono::steady_clock::now();
 	auto now_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_zero).count(); };
 	std::vector<double> tl(trace ? nb * 6 : 0, 0.0);                      // upload begin / end, launch begin / end, kernels done, download end
@@ -353,7 +344,7 @@ MSCompStatus run_range(Worker* w, const Job& j, size_t u0, size_t u1, bool on_ca
 	for (auto& b : batches) { if (b.plan) { mscomp_amd_plan_destroy(b.plan); b.plan = nullptr; } }
 	(void)hipGetLastError();
 	(void)is_failed;
-	if (failed == MSCOMP_OK) {                                   // the few units that need more room than 16 x their input: the one-shot decoder (it grows its staging: api.hip one_shot)
+	if (failed == MSCOMP_OK) {                                   // the few units that need more room than 16 x their input: the one-shot decoder (it grows its staging: oneshot.hip one_shot)
 		for (size_t u : again) {
 			size_t len = j.out_caps[u];
 			const MSCompStatus r = j.format == MSCOMP_LZNT1 ? lznt1_decompress(j.in_ptrs[u], j.in_lens[u], j.out_ptrs[u], &len)

@@ -16,7 +16,7 @@ struct PerDeviceOnce {
 
 // ---- lane order of same-address LDS atomics (util.hip) ----
 // The LZNT1 bucket sort and the Xpress chain links hand out slots / links with ONE returning LDS atomic per 64 positions and need the
-// same-address atomics of that instruction served in lane order -- what gfx950 does, checked once per device (api.hip lane_order_verdict). On
+// same-address atomics of that instruction served in lane order -- what gfx950 does, checked once per device (ctx.hip lane_order_verdict). On
 // a device that fails the check (or when the test hook says so) the same kernels issue the atomic one lane at a time, in a 64-step loop: DS
 // operations of a wave execute in program order, which IS architectural. Same bytes, slower sort.
 bool serial_atomics_on_current_device();
@@ -24,7 +24,6 @@ void set_serial_atomics(int device, int on);           // on: 1 = one lane at a 
 
 // ---- LZNT1 (lznt1.hip) ----
 #define LZNT1_SLOT 4352u     // scratch bytes per 4 KiB chunk image (2 B header + <=4096 B payload + emit slack)
-void set_lznt1_mode(int mode);
 #define LZNT1_REC  5632u     // scratch bytes of parse records per 4 KiB chunk (four-wave kernel: match tokens of 64 windows, two areas)
 // dev (here and below): a compress plan with device-built tables -- bt.n_chunks is its bound, and the chunk-gridded kernels return past
 // chunk_prefix[n_units] (their DEV instances; host plans run the original ones). prepare_*: the one-time LDS attributes of a launcher's kernels.
@@ -50,7 +49,6 @@ void prepare_xp_lazy2(bool dev);
 
 
 // ---- Xpress stream emission (xpress_emit.hip): one wavefront per unit ----
-void set_xpress_emit_mode(int mode);
 int xpress_emit_mode_for(uint32_t n_units, uint32_t n_chunks);
 // per-window / per-super-block records of the Xpress parse (see xpress_emit.hip); the last 10 only for the block-per-super-block kernels
 struct XpressWinBufs { u64* wtok; u64* wmat; uint32_t* wfar; uint32_t* wecur; uint32_t* weF; uint32_t* wsum; uint32_t* wnr; uint32_t* ws0; uint32_t* ws1;
@@ -146,6 +144,7 @@ void launch_xhd_size(hipStream_t st, const uint8_t* d_in, const BatchTables& bt,
 // ---- tokens -> bytes of both Xpress formats (lz_copy.hip): lz_copy_kernel, a wave per unit, and lz_copy_block_kernel, a block per larger one ----
 // Units of lzg_min_cap output bytes and more are left to lzglobal.hip; with lzg_cnt (a dev plan with large units) the DEV instances, which leave the
 // units of LZG_MIN_CAP and more when lzg_cnt[0] != 0
+#define LZB_MIN_KB 32                                     // units with at least this much output take the block kernel (MSCOMP_AMD_LZB_MIN_KB overrides, for measurements): a wave per unit, lz_copy_kernel, takes 3.8 ms for a 64 KiB unit; the block 57 us: 3 239 units 4.0 -> 1.6 ms
 void launch_lz_copy(hipStream_t st, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, u64 lzg_min_cap, const uint32_t* lzg_cnt);
 void launch_lz_copy_block(hipStream_t st, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, u64 lzg_min_cap, const uint32_t* lzg_cnt);
 void prepare_lz_copy_block();                             // the one-time LDS attribute of lz_copy_block_kernel
@@ -172,6 +171,7 @@ void prepare_lz_copy_global(bool dev);                    // the one-time LDS at
 // Each picks the DEV instances from g.cnt and launches nothing when g.n_big == 0.
 void launch_lzg_directory(hipStream_t st, const LzgTables& g, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status);
 void launch_lzg_expand(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out);
+#define LZG_HOPS 8u                                       // hops per pointer pass (MSCOMP_AMD_LZG_HOPS overrides, for measurements)
 void launch_lzg_jump(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out);
 
 // ---- plans with device-built tables (devplan.hip) ----
@@ -741,11 +741,10 @@ void launch_crc_fold_runs(hipStream_t st, uint32_t n, const u64* n_live, uint32_
 // prefix[0..n] = exclusive scan of sizes[0..n) as u64 (prefix[n] = total). block_sums: scratch of ceil(n/1024)+1 u64.
 void launch_scan_sizes(hipStream_t st, const uint32_t* sizes, u64* prefix, uint32_t n, u64* block_sums);
 // Concatenate the chunk images of every unit into the caller's output (skips units that do not fit): a fixed grid over tiles of 64 chunks,
-// place_blocks() of the device and instance, capped by the tiles of the batch and by the test hook (set_place_blocks, 0 = no cap)
+// place_blocks() of the device and instance, capped by the tiles of the batch and by the test hook (host.h Switches: place_cap, 0 = no cap)
 void launch_concat_slots(hipStream_t st, const uint8_t* slots, uint32_t slot_stride, const uint32_t* slot_size,
                          const u64* prefix, const BatchTables& bt, uint8_t* d_out, bool dev = false);
 uint32_t place_blocks(bool dev);
-void set_place_blocks(int n);
 // Per unit: out_len, status (OK / BUF_ERROR); LZNT1 also appends the uncounted 00 00 End_of_buffer when room.
 // outputs of a batch packed back to back: packed_off[0..n] (device), bytes of unit u at d_packed + packed_off[u]
 void launch_compact(hipStream_t st, const uint8_t* d_out, const u64* d_out_off, const uint32_t* d_tile_prefix, uint32_t n_units, uint32_t n_tiles,

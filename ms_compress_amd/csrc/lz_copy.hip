@@ -3,6 +3,7 @@
 //   lz_copy_kernel        a wave per unit, 64 bytes at a time (sources chased with ds_bpermute / LDS / HBM)       [comments at the kernels]
 //   lz_copy_block_kernel  a block per unit of LZB_MIN_KB and more, 8 KiB at a time
 #include "kernels.h"
+#include "host.h"
 
 namespace msc {
 
@@ -107,17 +108,11 @@ __global__ __launch_bounds__(64) void lz_copy_kernel(BatchTables bt, const u64* 
 // match offset back -- in the last 64 KiB of output, kept in an LDS ring (offsets reach at most 65535 back: resolved), or inside the tile
 // (a pointer); pointers are then jumped (ptr = ptr[ptr], at most 13 rounds, usually 2-4) until every byte has its value. One word per byte
 // holds "value" or "pointer", so a racing read sees one or the other, both of which are right.
-#define LZB_MIN_KB 32                                             // (a wave per unit, lz_copy_kernel, takes 3.8 ms for a 64 KiB unit; the block 57 us: 3 239 units 4.0 -> 1.6 ms)
 #define LZB_T    8192u
 #ifndef LZB_NT
 #define LZB_NT   1024u
 #endif
 #define LZB_RING 73728u                                            // 65536 + LZB_T, a multiple of LZB_T: a tile never wraps
-static uint32_t lzb_min_bytes()                                    // units with at least this much output take the block kernel (MSCOMP_AMD_LZB_MIN_KB overrides, for measurements)
-{
-	static const uint32_t v = [] { const char* e = getenv("MSCOMP_AMD_LZB_MIN_KB"); const long k = e ? atol(e) : 0; return (uint32_t)((k > 0 && k < (1 << 20) ? k : LZB_MIN_KB) << 10); }();
-	return v;
-}
 struct LzbLds {
 	__attribute__((aligned(16))) uint8_t ring[LZB_RING];
 	uint32_t info[LZB_T];                                          // token word at its start position; later: 0x80000000 | value, or the in-tile source
@@ -316,15 +311,15 @@ void launch_lz_copy(hipStream_t st, const BatchTables& bt, const u64* tok_prefix
 {
 	if (bt.n_units == 0) { return; }
 	prepare_lz_copy_block();
-	if (lzg_cnt) { hipLaunchKernelGGL(lz_copy_kernel<true>, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), LzgMin<true>{ lzg_cnt }); }
-	else { hipLaunchKernelGGL(lz_copy_kernel<false>, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), LzgMin<false>{ lzg_min_cap }); }
+	if (lzg_cnt) { hipLaunchKernelGGL(lz_copy_kernel<true>, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, env_lzb_min_bytes(), LzgMin<true>{ lzg_cnt }); }
+	else { hipLaunchKernelGGL(lz_copy_kernel<false>, dim3(bt.n_units), dim3(64), 0, st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, env_lzb_min_bytes(), LzgMin<false>{ lzg_min_cap }); }
 }
 void launch_lz_copy_block(hipStream_t st, const BatchTables& bt, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out, u64 lzg_min_cap, const uint32_t* lzg_cnt)
 {
 	if (bt.n_units == 0) { return; }
 	prepare_lz_copy_block();
-	if (lzg_cnt) { hipLaunchKernelGGL(lz_copy_block_kernel<true>, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), LzgMin<true>{ lzg_cnt }); }
-	else { hipLaunchKernelGGL(lz_copy_block_kernel<false>, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, lzb_min_bytes(), LzgMin<false>{ lzg_min_cap }); }
+	if (lzg_cnt) { hipLaunchKernelGGL(lz_copy_block_kernel<true>, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, env_lzb_min_bytes(), LzgMin<true>{ lzg_cnt }); }
+	else { hipLaunchKernelGGL(lz_copy_block_kernel<false>, dim3(bt.n_units), dim3(LZB_NT), sizeof(LzbLds), st, bt, tok_prefix, tok, ntok, d_out_len, d_status, d_out, env_lzb_min_bytes(), LzgMin<false>{ lzg_min_cap }); }
 }
 
 } // namespace msc

@@ -16,6 +16,7 @@
 // Scratch: 4 bytes per output byte of the units taken (capacity >= LZG_MIN_CAP; the plan gives up the path when that exceeds its budget).
 #include "common.h"
 #include "kernels.h"
+#include "host.h"
 
 namespace msc {
 
@@ -261,7 +262,6 @@ __global__ __launch_bounds__(LZG_NT) void lzg_expand_kernel(LzgTables g, BatchTa
 }
 
 // ---- pointer passes ------------------------------------------------------------------------------------------------------------------------
-#define LZG_HOPS 8u
 template <bool DEV>
 __global__ __launch_bounds__(256) void lzg_jump_kernel(LzgTables g, BatchTables bt, const u64* __restrict__ d_out_len, const int32_t* __restrict__ d_status,
                                                       uint8_t* __restrict__ d_out, uint32_t pass, uint32_t hops)
@@ -326,7 +326,7 @@ static void lzg_directory(hipStream_t st, const LzgTables& g, const u64* tok_pre
 template <bool DEV>
 static void lzg_jump(hipStream_t st, const LzgTables& g, const BatchTables& bt, const u64* d_out_len, const int32_t* d_status, uint8_t* d_out)
 {
-	static const uint32_t hops = [] { const char* e = getenv("MSCOMP_AMD_LZG_HOPS"); const long v = e ? atol(e) : 0; return (uint32_t)(v > 0 && v < 1000 ? v : LZG_HOPS); }();
+	const uint32_t hops = env_lzg_hops();                                 // (LZG_HOPS, or MSCOMP_AMD_LZG_HOPS)
 	for (uint32_t pass = 0; pass < LZG_PASSES; ++pass) { hipLaunchKernelGGL(lzg_jump_kernel<DEV>, dim3(g.n_tiles < 4096u ? g.n_tiles : 4096u), dim3(256), 0, st, g, bt, d_out_len, d_status, d_out, pass, hops); }
 }
 void launch_lzg_directory(hipStream_t st, const LzgTables& g, const u64* tok_prefix, const uint32_t* tok, const u64* ntok, const u64* d_out_len, const int32_t* d_status)

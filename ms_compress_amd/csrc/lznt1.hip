@@ -30,6 +30,7 @@
 //   D. header (0xB000|size-1), or the raw chunk (0x3000|n-1) when the running size reaches n; util.hip concatenates slots.
 #include "common.h"
 #include "kernels.h"
+#include "host.h"
 
 namespace msc {
 
@@ -1240,12 +1241,11 @@ static void launch_lznt1_chunks_t(hipStream_t st, const uint8_t* d_in, const Bat
 void launch_lznt1_chunks_dev(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs,
                              int mode, bool serial);
 #ifndef LZNT1_DEV_TU
-static int g_lznt1_mode = 0;                                     // 0 = default, 1 = one wave per chunk, 2 = four waves per chunk (tests)
-void set_lznt1_mode(int mode) { g_lznt1_mode = mode; }
 void launch_lznt1_chunks(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, uint8_t* slots, uint32_t* slot_size, uint16_t* recs, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
-	const int mode = g_lznt1_mode ? g_lznt1_mode : 2;                 // four waves per chunk: 1.43 vs 1.74 ms on the headline workload
+	const int forced = g_sw.lznt1.load(std::memory_order_relaxed);   // (host.h Switches: 0 = default, 1 = one wave per chunk, 2 = four waves per chunk)
+	const int mode = forced ? forced : 2;                             // four waves per chunk: 1.43 vs 1.74 ms on the headline workload
 	const bool serial = serial_atomics_on_current_device();
 	if (dev) { launch_lznt1_chunks_dev(st, d_in, bt, slots, slot_size, recs, mode, serial); }
 	else { launch_lznt1_chunks_t<false>(st, d_in, bt, slots, slot_size, recs, mode, serial); }

@@ -1,6 +1,6 @@
 // reader.hip -- the passes of a block reader (mscomp_amd_reader_*, include/mscomp_amd.h): a batch of byte-range requests against the tables
 // a block container wrote. The requests are checked and counted, every covering block gets one owner among the (request, block) pairs that
-// want it, the owners' blocks are decoded into a cache by a decompress dev plan over them as units (api.hip runs it between these passes,
+// want it, the owners' blocks are decoded into a cache by a decompress dev plan over them as units (blockobj.hip runs it between these passes,
 // unchanged) or read where they lie when stored raw, optionally held to their CRC-32 (crc32.hip, unchanged), the verdicts are folded per
 // request, and only then the slices move to the caller's buffer. DESIGN.md 4.9.
 #include "kernels.h"

@@ -5,6 +5,7 @@
 // "sizes -> exclusive scan -> copy/encode at the final offset".
 #include "common.h"
 #include "kernels.h"
+#include "host.h"
 #include <atomic>
 #include <vector>
 
@@ -125,10 +126,9 @@ __global__ __launch_bounds__(256) void concat_slots_kernel(const uint8_t* __rest
 }
 
 // blocks of concat_slots_kernel that are resident on the current device at once: its grid, asked once per device and instance (a context
-// asks when it is created: never inside a capture). The test hook caps it (0 = no cap), so that a small batch gives a block a second tile.
+// asks when it is created: never inside a capture). The test hook caps it (host.h Switches: place_cap, 0 = no cap), so that a small batch
+// gives a block a second tile.
 static std::atomic<uint32_t> g_place_grid[2][64];
-static std::atomic<int> g_place_cap;
-void set_place_blocks(int n) { g_place_cap.store(n > 0 ? n : 0, std::memory_order_relaxed); }
 uint32_t place_blocks(bool dev)
 {
 	int d = 0, cus = 0, per_cu = 0;
@@ -150,7 +150,7 @@ void launch_concat_slots(hipStream_t st, const uint8_t* slots, uint32_t slot_str
                          const u64* prefix, const BatchTables& bt, uint8_t* d_out, bool dev)
 {
 	if (bt.n_chunks == 0) { return; }
-	const uint32_t tiles = (bt.n_chunks + PLACE_TILE - 1u) / PLACE_TILE, cap = (uint32_t)g_place_cap.load(std::memory_order_relaxed);
+	const uint32_t tiles = (bt.n_chunks + PLACE_TILE - 1u) / PLACE_TILE, cap = (uint32_t)g_sw.place_cap.load(std::memory_order_relaxed);
 	uint32_t grid = place_blocks(dev);
 	if (grid > tiles) { grid = tiles; }
 	if (cap && grid > cap) { grid = cap; }
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(64) void lds_lane_order_kernel(uint32_t seed, uint3
 	if (nbad) { atomicAdd(bad, nbad); }
 }
 
-// Two sources, kept apart: the device's own self-check (per device, set once by api.hip lane_order_verdict, never cleared) and
+// Two sources, kept apart: the device's own self-check (per device, set once by ctx.hip lane_order_verdict, never cleared) and
 // the test hook (process-wide, mscomp_amd_debug_set_serial_atomics). The hook's "off" only withdraws the hook: a device that failed its
 // check keeps the order-independent kernels -- wrong bytes must never leave silently.
 static std::atomic<int> g_serial_verdict[64];

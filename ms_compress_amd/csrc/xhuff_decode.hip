@@ -549,7 +549,7 @@ __global__ __launch_bounds__(256) void xhc_gather_kernel(BatchTables bt, const u
 	for (uint32_t i = threadIdx.x; i < cnt; i += 256u) { to[i] = from[i]; }
 }
 
-// ---- launchers: one per stage, in the order they run (api.hip decode_launch / size_launch) ---------------------------------------------
+// ---- launchers: one per stage, in the order they run (launch.hip decode_launch / size_launch) ---------------------------------------------
 void launch_xhc_mark(hipStream_t st, const uint8_t* d_in, const BatchTables& bt, const u64* cand_prefix, const XhcBufs& xb, bool dev)
 {
 	if (bt.n_units == 0) { return; }

@@ -14,6 +14,7 @@
 // evaluated with mbcnt popcounts and a DPP add-scan; the flag word in progress is kept in scalar registers.
 #include "common.h"
 #include "kernels.h"
+#include "host.h"
 
 namespace msc {
 
@@ -1169,15 +1170,14 @@ __global__ __launch_bounds__(64) void xe3_stitch_kernel(BatchTables bt, Xe3 x, u
 	}
 }
 
-static int g_xpress_emit_mode = 0;                               // 0 = by batch size, 1 = one wave per unit, 2 / 3 = 4 / 16 waves per unit, 4 = a block per super-block (tests)
-// Which parse/emit kernels a batch gets. Few units, or long ones (on average more than four 64 KiB super-blocks each):
+// Which parse/emit kernels a batch gets, unless the test hook says (host.h Switches: xpress_emit). Few units, or long ones (on average more than four 64 KiB super-blocks each):
 // a block per super-block, so that a long stream is spread over the GPU (needs 24 B of records per 64 input bytes).
 // Otherwise the per-unit kernels: four waves per unit up to 1024 units, one wave per unit beyond (a full GPU is
 // issue-bound and the multi-wave kernels spend more wave-cycles; at 3 239 units of 64 KiB the three variants are within
 // 10 % of each other: 5.5 / 5.6 / 6.2 ms per pass).
 int xpress_emit_mode_for(uint32_t n_units, uint32_t n_chunks)
 {
-	if (g_xpress_emit_mode) { return g_xpress_emit_mode; }
+	if (const int forced = g_sw.xpress_emit.load(std::memory_order_relaxed)) { return forced; }
 	if ((n_units <= 64u || n_chunks >= 4u * n_units) && n_chunks <= 32768u) { return 4; }
 	// (round 6 sweep, units of 64 KiB spread over the corpus, ms per pass one wave / four waves per unit -- tools/dev/gpu_emit_sweep.py: 256 units 1.59 / 1.03,
 	// 512: 1.72 / 1.19, 768: 2.44 / 2.13, 1024: 2.64 / 2.49, 1536: 3.02 / 3.16, 2048: 3.09 / 3.22, 3239: 4.05 / 4.76, 6478: 7.25 / 8.97 -- the crossover lies
@@ -1209,6 +1209,5 @@ void launch_xpress_emit(hipStream_t st, const uint8_t* d_in, const BatchTables& 
 		hipLaunchKernelGGL(xe3_stitch_kernel, dim3(bt.n_units), dim3(64), 0, st, bt, x, d_out);
 	}
 }
-void set_xpress_emit_mode(int mode) { g_xpress_emit_mode = mode; }
 
 } // namespace msc

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(NT) void xp_find_kernel(const uint8_t* __restrict__
 	// across groups the chunks stay round-robin over the XCDs (cheap and expensive files are spread evenly).
 	uint32_t bid = blockIdx.x;
 	if ((bid | 127u) < gridDim.x) { const uint32_t wi = bid & 127u; bid = (bid & ~127u) + (wi & 7u) * 16u + (wi >> 3); }
-	bid += tile_base;                                                         // (a launch over a RANGE of chunks: the pipelined one-shot call, api.hip)
+	bid += tile_base;                                                         // (a launch over a RANGE of chunks: the pipelined one-shot call, oneshot.hip)
 	constexpr uint32_t TPC = 65536u / XP_TILE;                                // tiles per chunk
 	const uint32_t lc = bid / TPC;
 	const uint32_t tstart = (bid % TPC) * XP_TILE;                            // tile start inside the chunk

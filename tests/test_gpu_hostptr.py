@@ -1,7 +1,7 @@
 """-m gpu: the drop-in host-pointer entry points on LARGE buffers (mscomp.h:59: ms_compress with plain host pointers) and fixed-seed
 slices of the three end-of-round soaks (tools/dev/fuzz_*.py), so that every product path has a committed test:
 
-* ms_compress(MSCOMP_LZNT1) of mozilla (51 220 480 B) through BOTH large-buffer paths of csrc/api.hip -- the caller's buffers mapped and
+* ms_compress(MSCOMP_LZNT1) of mozilla (51 220 480 B) through BOTH large-buffer paths of csrc/oneshot.hip -- the caller's buffers mapped and
   one launch (lznt1_zero_copy, the default) and the slices on three streams (lznt1_compress_pipelined, mscomp_amd_debug_set_one_shot(1)
   == MSCOMP_AMD_ONE_ZEROCOPY=0): bytes against the REAL reference's digest (tests/golden/corpus_full.json), the uncounted 00 00
   End_of_buffer behind the stream (lznt1_compress.cpp:270), exact / one short / half capacities -> MSCOMP_BUF_ERROR with nothing written
@@ -102,7 +102,7 @@ def test_four_threads_compress_large_buffers_at_once(gpu_ctx):
 
 def test_two_threads_compress_the_same_input_at_once(gpu_ctx, mozilla):
     """legal in the reference (only in / out must not alias): both calls page-lock the SAME input range -- the registration is shared and
-    outlives the first call to finish (csrc/api.hip HostPins); through the mapped path and through the slices"""
+    outlives the first call to finish (csrc/oneshot.hip HostPins); through the mapped path and through the slices"""
     import ms_compress_amd as m
     lib = m.load_library()
     g = GOLD["mozilla"]["lznt1"]
@@ -127,7 +127,7 @@ def test_two_threads_compress_the_same_input_at_once(gpu_ctx, mozilla):
 def test_host_batch_beside_a_large_one_shot_call_on_the_same_input(gpu_ctx, mozilla):
     """one thread compresses mozilla with the large host-pointer LZNT1 call (which page-locks its input for the duration), another reads the
     SAME input through the host-batch entry at the same time (legal: inputs may be shared): the batch entry's staged copies keep the other
-    call's registration alive (csrc/api.hip host_pins_hold); every result against the reference's digests"""
+    call's registration alive (csrc/oneshot.hip host_pins_hold); every result against the reference's digests"""
     import ms_compress_amd as m
     lib = m.load_library()
     g2, g4 = GOLD["mozilla"]["lznt1"], GOLD["mozilla"]["xpress_huff"]
@@ -170,7 +170,7 @@ def test_whole_file_host_pointer_xpress_formats(gpu_ctx, fmt, key):
 @pytest.mark.parametrize("fmt,key", [(3, "xpress"), (4, "xpress_huff")])
 def test_ranged_upload_of_large_xpress_calls(gpu_ctx, mozilla, fmt, key):
     """Round 6: ms_compress(Xpress / Xpress+Huffman) of a buffer of 8 MiB or more uploads it in ranges of 256 chunks and runs the chain links and
-    Find of a range under the upload of the next (csrc/api.hip one_shot). The bytes must be the batch path's and the reference's: mozilla (51 MB, 7
+    Find of a range under the upload of the next (csrc/oneshot.hip one_shot). The bytes must be the batch path's and the reference's: mozilla (51 MB, 7
     ranges) against the reference's digest; sizes at and around the range boundaries and the switch-over size against the one-copy form of the
     same call (mscomp_amd_debug_set_one_shot(1)) and the HBM-resident batch path."""
     import ms_compress_amd as m

@@ -15,7 +15,7 @@ import thresholds as T
 
 pytestmark = pytest.mark.gpu
 BUF_ERROR = -5
-XH_FB_BLOCKS = 256                                           # csrc/api.hip: the grid of the fallback kernel
+XH_FB_BLOCKS = 256                                           # csrc/launch.hip: the grid of the fallback kernel
 
 
 @pytest.fixture(scope="module")

@@ -1,6 +1,6 @@
 """Dev helper (GPU box): Xpress over the real-file corpus in sub-batches of N units under every (finder, emit kernel) combination, each unit's
 bytes against the reference's; the first units that differ are dumped to gpurun_out/bad_units/ (input + both outputs) for analysis on the CPU."""
-import os as _os; _os.environ.setdefault("MSCOMP_AMD_TEST_HOOKS", "1")   # (the kernel switches: csrc/api.hip test_hooks_on)
+import os as _os; _os.environ.setdefault("MSCOMP_AMD_TEST_HOOKS", "1")   # (the kernel switches: csrc/hooks.hip test_hooks_on)
 import os
 import sys
 import time
