@@ -4,15 +4,9 @@ captured graph."""
 import numpy as np
 import pytest
 
+from plans_rig import FMTS, GUARD, dt
+
 pytestmark = pytest.mark.gpu
-FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
-GUARD = 0xEE
-
-
-def _dt(a):
-    """a uint64 host table as an int64 CUDA tensor"""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint64)).view(np.int64).copy()).cuda()
 
 
 def _u64(t):
@@ -39,7 +33,7 @@ def _run(ctx, d_src, src_off, lens, align, cap=None, slack=4096):
     room = total if cap is None else cap
     d_packed = torch.full((max(total, room) + slack,), GUARD, dtype=torch.uint8, device="cuda")
     d_off = torch.full((len(lens) + 1,), -1, dtype=torch.int64, device="cuda")
-    m.compact_dev(ctx, d_src, _dt(src_off), _dt(lens), align, d_packed, d_off, packed_cap=room)
+    m.compact_dev(ctx, d_src, dt(src_off), dt(lens), align, d_packed, d_off, packed_cap=room)
     torch.cuda.synchronize()
     return _u64(d_off), d_packed.cpu().numpy(), room
 
@@ -217,8 +211,8 @@ def test_whole_chain_in_one_captured_graph():
         def load(batch):
             _, _, blob, c_off, c_len = batch
             d_comp[: len(blob)].copy_(torch.from_numpy(blob))
-            d_coff.copy_(_dt(c_off))
-            d_clen.copy_(_dt(c_len))
+            d_coff.copy_(dt(c_off))
+            d_clen.copy_(dt(c_len))
             for t in (d_plain, d_x, d_packed, d_back):
                 t.fill_(GUARD)
             for t in S:

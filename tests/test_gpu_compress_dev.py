@@ -7,116 +7,17 @@ import numpy as np
 import pytest
 
 import cases
+import plans_rig as PR
+from plans_rig import FMTS, GUARD
 
 pytestmark = pytest.mark.gpu
-FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
-GUARD = 0xEE
-GAP = 48                                                             # guard bytes between the capacities of two units
-
-
-def _dt(a):
-    """a uint64 host table as an int64 CUDA tensor"""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint64)).view(np.int64).copy()).cuda()
-
-
-def _layout(units, caps):
-    import ms_compress_amd as m
-    lens = [len(u) for u in units]
-    in_off, in_total = m.pack_offsets(lens)
-    out_off, pos = np.zeros(len(caps), np.uint64), GAP
-    for i, c in enumerate(caps):
-        out_off[i] = pos
-        pos += int(c) + GAP
-    blob = np.zeros(in_total + 16, np.uint8)
-    for u, o in zip(units, in_off):
-        blob[int(o): int(o) + len(u)] = np.frombuffer(bytes(u), np.uint8)
-    return blob, in_off, np.array(lens, np.uint64), out_off, np.array(caps, np.uint64), pos + GAP
-
-
-def _host(ctx, f, blob, in_off, lens, out_off, caps, out_total):
-    """a fresh host-table compress plan: (out_len, status, output bytes incl. guards)"""
-    import torch
-    import ms_compress_amd as m
-    n = len(lens)
-    d_in = torch.from_numpy(blob).cuda()
-    d_out = torch.full((out_total,), GUARD, dtype=torch.uint8, device="cuda")
-    d_len = torch.zeros(max(1, n), dtype=torch.int64, device="cuda")
-    d_st = torch.zeros(max(1, n), dtype=torch.int32, device="cuda")
-    plan = m.Plan(ctx, f, in_off, lens, out_off, caps)
-    plan.execute(d_in, d_out, d_len, d_st)
-    torch.cuda.synchronize()
-    plan.close()
-    return d_len.cpu().numpy()[:n], d_st.cpu().numpy()[:n], d_out.cpu().numpy()
-
-
-class DevRun:
-    """one compress dev plan and the device buffers of its batches: tables and bytes are rewritten in place between executions"""
-
-    def __init__(self, ctx, f, n, in_bytes, out_bytes, in_max, unit_max):
-        import torch
-        import ms_compress_amd as m
-        self.plan = m.CompressDevPlan(ctx, f, n, in_max, unit_max)
-        self.n = n
-        self.d_in = torch.zeros(in_bytes, dtype=torch.uint8, device="cuda")
-        self.d_out = torch.full((out_bytes,), GUARD, dtype=torch.uint8, device="cuda")
-        self.tabs = [torch.zeros(max(1, n), dtype=torch.int64, device="cuda") for _ in range(4)]
-        self.d_len = torch.zeros(max(1, n), dtype=torch.int64, device="cuda")
-        self.d_st = torch.full((max(1, n),), 77, dtype=torch.int32, device="cuda")
-
-    def load(self, blob, in_off, lens, out_off, caps):
-        import torch
-        self.d_in[: len(blob)].copy_(torch.from_numpy(blob))
-        for t, a in zip(self.tabs, (in_off, lens, out_off, caps)):
-            t[: self.n].copy_(_dt(a))
-        self.d_out.fill_(GUARD)
-        self.d_st.fill_(77)
-
-    def execute(self):
-        i_off, i_len, o_off, o_cap = self.tabs
-        self.plan.execute(self.d_in, i_off, i_len, self.d_out, o_off, o_cap, self.d_len, self.d_st)
-
-    def result(self):
-        import torch
-        torch.cuda.synchronize()
-        return self.d_len.cpu().numpy()[: self.n], self.d_st.cpu().numpy()[: self.n], self.d_out.cpu().numpy()
-
-
-def _same(host, dev, out_off, caps, out_total, accepted=None):
-    hl, hs, ho = host
-    dl, ds, do = dev
-    n = len(caps)
-    inside = np.zeros(len(do), bool)
-    for i in range(n):
-        if accepted is not None and not accepted[i]:
-            assert ds[i] == -2 and dl[i] == 0, (i, ds[i], dl[i])
-            continue
-        assert (ds[i], dl[i]) == (hs[i], hl[i]), (i, ds[i], hs[i], dl[i], hl[i])
-        o = int(out_off[i])
-        if hs[i] == 0:
-            end = min(int(caps[i]), int(hl[i]) + 2)                  # (LZNT1's uncounted 00 00 included)
-            assert bytes(do[o: o + end]) == bytes(ho[o: o + end]), i
-        inside[o: o + int(caps[i])] = True
-    outside = ~inside
-    outside[out_total:] = True
-    assert (do[outside] == GUARD).all(), np.nonzero(do[outside] != GUARD)[0][:8]
-
-
-def _corpus(sizes):
-    from ms_compress_amd import corpus
-    data = corpus.by_name("mozilla", sum(sizes) + 1000).tobytes()
-    out, pos = [], 0
-    for s in sizes:
-        out.append(data[pos: pos + s])
-        pos += s
-    return out
 
 
 def _exact(ctx, f, units):
     """the exact compressed length of every unit (a host plan at the largest capacity)"""
     import ms_compress_amd as m
     caps = [m.max_compressed_size(f, len(u)) + 2 for u in units]
-    hl, hs, _ = _host(ctx, f, *_layout(units, caps))
+    hl, hs, _ = PR.host_run(ctx, f, PR.layout(units, caps), "compress")
     assert (hs == 0).all()
     return [int(x) for x in hl]
 
@@ -143,13 +44,15 @@ def _with_caps(ctx, f, units, every):
 
 def _check(ctx, f, units, caps, unit_max, in_max=None):
     import torch
-    blob, in_off, lens, out_off, caps, out_total = _layout(units, caps)
-    host = _host(ctx, f, blob, in_off, lens, out_off, caps, out_total)
-    r = DevRun(ctx, f, len(units), len(blob), out_total + 4096, int(lens.sum()) if in_max is None else in_max, unit_max)
-    r.load(blob, in_off, lens, out_off, caps)
+    import ms_compress_amd as m
+    batch = PR.layout(units, caps)
+    host = PR.host_run(ctx, f, batch, "compress")
+    plan = m.CompressDevPlan(ctx, f, len(units), int(batch.lens.sum()) if in_max is None else in_max, unit_max)
+    r = PR.DevRun(plan, len(batch.blob), batch.out_total + 4096)
+    r.load(batch)
     r.execute()
     dev = r.result()
-    _same(host, dev, out_off, caps, out_total)
+    PR.same(host, dev, batch, tail=2)
     r.plan.close()
     del r
     torch.cuda.synchronize()
@@ -166,7 +69,7 @@ def test_compress_dev_plan_matches_host_plan(gpu_ctx, fmt):
     with in_unit_max = 64 KiB on the units up to 64 KiB (the lazy Xpress finder), once with in_unit_max = 3 MB on all of them."""
     f = FMTS[fmt]
     edge = cases.edge_cases()
-    corp = _corpus(CORPUS_SIZES)
+    corp = PR.corpus_units(CORPUS_SIZES)
     units = edge + corp
     every = set(range(len(edge), len(units)))
     small = [u for u in units if len(u) <= 65536]
@@ -187,11 +90,11 @@ def test_xpress_emit_modes_by_batch_shape(gpu_ctx, shape):
     f = 3
     rnd = random.Random(17)
     if shape == "few_long":
-        units, unit_max = _corpus((700 << 10, 3 << 20, 1 << 20, 200_000)), 3 << 20
+        units, unit_max = PR.corpus_units((700 << 10, 3 << 20, 1 << 20, 200_000)), 3 << 20
     elif shape == "300x64k":
-        units, unit_max = _corpus((65536,) * 300), 65536
+        units, unit_max = PR.corpus_units((65536,) * 300), 65536
     else:
-        units, unit_max = _corpus(tuple(rnd.randint(4096, 65536) for _ in range(1500))), 65536
+        units, unit_max = PR.corpus_units(tuple(rnd.randint(4096, 65536) for _ in range(1500))), 65536
     caps = [m.max_compressed_size(f, len(u)) for u in units]
     st = _check(gpu_ctx, f, units, caps, unit_max)[1]
     assert (st == 0).all()
@@ -203,7 +106,7 @@ def test_one_compress_dev_plan_several_batches(gpu_ctx, fmt):
     place (the second and third executions replay the plan's own graph): each result is that of a fresh host plan"""
     import ms_compress_amd as m
     f = FMTS[fmt]
-    pool = cases.edge_cases(seed=4) + _corpus((65536, 100_000, 131072))
+    pool = cases.edge_cases(seed=4) + PR.corpus_units((65536, 100_000, 131072))
     rnd = np.random.default_rng(3)
     n = 150
     batches = []
@@ -211,14 +114,14 @@ def test_one_compress_dev_plan_several_batches(gpu_ctx, fmt):
         pick = rnd.choice(len(pool), n, replace=False)
         units = [pool[i] for i in pick]
         caps = [m.max_compressed_size(f, len(u)) - int(rnd.integers(0, 40)) * b for u in units]
-        batches.append(_layout(units, [max(0, c) for c in caps]))
+        batches.append(PR.layout(units, [max(0, c) for c in caps]))
     in_max = max(int(x[2].sum()) for x in batches)
-    r = DevRun(gpu_ctx, f, n, max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096, in_max, max(len(u) for u in pool))
-    for blob, in_off, lens, out_off, caps, out_total in batches:
-        r.load(blob, in_off, lens, out_off, caps)
+    r = PR.DevRun(m.CompressDevPlan(gpu_ctx, f, n, in_max, max(len(u) for u in pool)), max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096)
+    for batch in batches:
+        r.load(batch)
         r.execute()
         dev = r.result()
-        _same(_host(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total), dev, out_off, caps, out_total)
+        PR.same(PR.host_run(gpu_ctx, f, batch, "compress"), dev, batch, tail=2)
     r.plan.close()
 
 
@@ -228,30 +131,31 @@ def test_units_past_the_bounds_are_refused(gpu_ctx, fmt):
     get MSCOMP_ARG_ERROR with length 0, the others compress as with a host plan, nothing is written outside the accepted capacities"""
     import ms_compress_amd as m
     f = FMTS[fmt]
-    units = [u for u in cases.edge_cases(seed=6) if 8 < len(u) <= 65536][::5][:40] + _corpus((30_000, 65536, 70_000))
+    units = [u for u in cases.edge_cases(seed=6) if 8 < len(u) <= 65536][::5][:40] + PR.corpus_units((30_000, 65536, 70_000))
     n = len(units)
     caps = [m.max_compressed_size(f, len(u)) + 2 for u in units]
-    blob, in_off, lens, out_off, caps, out_total = _layout(units, caps)
-    host = _host(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
+    batch = PR.layout(units, caps)
+    blob, in_off, lens, out_off, caps, out_total = batch
+    host = PR.host_run(gpu_ctx, f, batch, "compress")
     unit_max = 65536
     acc = lens <= unit_max
     assert not acc[-1] and acc[:-1].all()
     mid = n // 2                                                      # a long in_len in the middle, over the input of the units behind it
     lens_bad = lens.copy()
     lens_bad[mid] = unit_max + 1
-    r = DevRun(gpu_ctx, f, n, len(blob) + unit_max, out_total + 4096, int(lens_bad.sum()), unit_max)
-    r.load(blob, in_off, lens_bad, out_off, caps)
+    r = PR.DevRun(m.CompressDevPlan(gpu_ctx, f, n, int(lens_bad.sum()), unit_max), len(blob) + unit_max, out_total + 4096)
+    r.load(batch._replace(lens=lens_bad))
     r.execute()
     a = acc.copy()
     a[mid] = False
-    _same(host, r.result(), out_off, caps, out_total, a)
+    PR.same(host, r.result(), batch, a, tail=2)
     r.plan.close()
     cut = 3 * n // 4                                                  # in_total_max crossed inside unit `cut`
     in_max = int(lens[:cut].sum()) + int(lens[cut]) // 2
-    r = DevRun(gpu_ctx, f, n, len(blob), out_total + 4096, in_max, unit_max)
-    r.load(blob, in_off, lens, out_off, caps)
+    r = PR.DevRun(m.CompressDevPlan(gpu_ctx, f, n, in_max, unit_max), len(blob), out_total + 4096)
+    r.load(batch)
     r.execute()
-    _same(host, r.result(), out_off, caps, out_total, acc & (np.cumsum(lens) <= in_max))
+    PR.same(host, r.result(), batch, acc & (np.cumsum(lens) <= in_max), tail=2)
     r.plan.close()
 
 
@@ -260,7 +164,7 @@ def test_lznt1_suffix_array_flavour(gpu_ctx):
     import ms_compress_amd as m
     ctx = m.Context()
     ctx.set_lznt1_sa_dict(True)
-    units = cases.edge_cases(seed=7)[::3] + _corpus((0, 4097, 65537, 300_000))
+    units = cases.edge_cases(seed=7)[::3] + PR.corpus_units((0, 4097, 65537, 300_000))
     u, c = _with_caps(ctx, 2, units, set(range(len(units) - 4, len(units))))
     _check(ctx, 2, u, c, 300_000)
     ctx.close()
@@ -279,7 +183,7 @@ def test_plan_kinds_are_kept_apart(gpu_ctx):
     dev = m.CompressDevPlan(gpu_ctx, 2, n, 64, 32)
     d_in = torch.zeros(64, dtype=torch.uint8, device="cuda")
     d_out = torch.full((64,), GUARD, dtype=torch.uint8, device="cuda")
-    t = [_dt(off), _dt(ln), _dt(off), _dt(ln)]
+    t = [PR.dt(off), PR.dt(ln), PR.dt(off), PR.dt(ln)]
     d_len = torch.full((n,), 5, dtype=torch.int64, device="cuda")
     d_need = torch.full((n,), 5, dtype=torch.int64, device="cuda")
     d_st = torch.full((n,), 77, dtype=torch.int32, device="cuda")
@@ -305,30 +209,30 @@ def test_compress_dev_plan_in_a_captured_graph(gpu_ctx, fmt):
     import torch
     import ms_compress_amd as m
     f = FMTS[fmt]
-    pool = cases.edge_cases(seed=8) + _corpus((65536, 65537, 200_000))
+    pool = cases.edge_cases(seed=8) + PR.corpus_units((65536, 65537, 200_000))
     rnd = np.random.default_rng(8)
     n = 96
     batches = []
     for b in range(3):
         pick = rnd.choice(len(pool), n, replace=False)
         units = [pool[i] for i in pick]
-        batches.append(_layout(units, [max(0, m.max_compressed_size(f, len(u)) - 30 * b) for u in units]))
+        batches.append(PR.layout(units, [max(0, m.max_compressed_size(f, len(u)) - 30 * b) for u in units]))
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        r = DevRun(ctx, f, n, max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096,
-                   max(int(x[2].sum()) for x in batches), 200_000)
-        r.load(*batches[0][:5])
+        r = PR.DevRun(m.CompressDevPlan(ctx, f, n, max(int(x[2].sum()) for x in batches), 200_000),
+                      max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096)
+        r.load(batches[0])
     s.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=s):
         r.execute()
-    for blob, in_off, lens, out_off, caps, out_total in batches:
+    for batch in batches:
         with torch.cuda.stream(s):
-            r.load(blob, in_off, lens, out_off, caps)
+            r.load(batch)
             g.replay()
         s.synchronize()
-        _same(_host(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total), r.result(), out_off, caps, out_total)
+        PR.same(PR.host_run(gpu_ctx, f, batch, "compress"), r.result(), batch, tail=2)
     del g
     r.plan.close()
     ctx.close()
@@ -340,7 +244,7 @@ def test_transcode_lznt1_to_xpress_huff_on_the_device(gpu_ctx):
     compressed ones those of a host compress of the plain units"""
     import torch
     import ms_compress_amd as m
-    plain = _corpus(CORPUS_SIZES[1:7] + (300_000,)) + [bytes(5000), b"abc" * 999]
+    plain = PR.corpus_units(CORPUS_SIZES[1:7] + (300_000,)) + [bytes(5000), b"abc" * 999]
     n = len(plain)
     comp, st = m.compress_units(2, plain)
     assert all(s == 0 for s in st)
@@ -351,8 +255,8 @@ def test_transcode_lznt1_to_xpress_huff_on_the_device(gpu_ctx):
     blob = np.zeros(c_total + 16, np.uint8)
     for c, o in zip(comp, c_off):
         blob[int(o): int(o) + len(c)] = np.frombuffer(c, np.uint8)
-    d_comp, d_coff, d_clen = torch.from_numpy(blob).cuda(), _dt(c_off), _dt([len(c) for c in comp])
-    d_poff, d_pcap = _dt(p_off), _dt([len(p) for p in plain])
+    d_comp, d_coff, d_clen = torch.from_numpy(blob).cuda(), PR.dt(c_off), PR.dt([len(c) for c in comp])
+    d_poff, d_pcap = PR.dt(p_off), PR.dt([len(p) for p in plain])
     plain_total = sum(len(p) for p in plain)
     x_total = sum(m.max_compressed_size(4, len(p)) for p in plain) + 16 * n + 64
     d_plain = torch.full((p_total + 64,), GUARD, dtype=torch.uint8, device="cuda")
@@ -398,11 +302,11 @@ def test_plan_layout_dev_matches_host_layout(gpu_ctx, fmt, align):
     off = np.zeros(n, np.uint64)
     cap = np.zeros(n, np.uint64)
     total = lib.mscomp_amd_plan_layout(f, n, lens.ctypes.data, align, off.ctypes.data, cap.ctypes.data)
-    d_off, d_cap = m.plan_layout_dev(gpu_ctx, f, _dt(lens), align)
+    d_off, d_cap = m.plan_layout_dev(gpu_ctx, f, PR.dt(lens), align)
     torch.cuda.synchronize()
     got_off, got_cap = d_off.cpu().numpy().view(np.uint64), d_cap.cpu().numpy().view(np.uint64)
     assert (got_cap == cap).all() and (got_off[:n] == off).all() and int(got_off[n]) == int(total)
     d_off2 = torch.zeros(n + 1, dtype=torch.int64, device="cuda")    # d_out_cap may be NULL
-    assert lib.mscomp_amd_plan_layout_dev(gpu_ctx._h, f, n, C.c_void_p(_dt(lens).data_ptr()), align, C.c_void_p(d_off2.data_ptr()), None) == 0
+    assert lib.mscomp_amd_plan_layout_dev(gpu_ctx._h, f, n, C.c_void_p(PR.dt(lens).data_ptr()), align, C.c_void_p(d_off2.data_ptr()), None) == 0
     torch.cuda.synchronize()
     assert (d_off2.cpu().numpy().view(np.uint64) == got_off).all()

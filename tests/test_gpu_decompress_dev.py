@@ -6,109 +6,11 @@ import numpy as np
 import pytest
 
 import cases
+import plans_rig as PR
+from plans_rig import FMTS, GUARD
 
 pytestmark = pytest.mark.gpu
-FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
-GUARD = 0xEE
-GAP = 48                                                             # guard bytes between the capacities of two units
-
-
-def _dt(a):
-    """a uint64 host table as an int64 CUDA tensor"""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint64)).view(np.int64).copy()).cuda()
-
-
-def _layout(units, caps):
-    import ms_compress_amd as m
-    lens = [len(u) for u in units]
-    in_off, in_total = m.pack_offsets(lens)
-    out_off, pos = np.zeros(len(caps), np.uint64), GAP
-    for i, c in enumerate(caps):
-        out_off[i] = pos
-        pos += int(c) + GAP
-    blob = np.zeros(in_total + 16, np.uint8)
-    for u, o in zip(units, in_off):
-        blob[int(o): int(o) + len(u)] = np.frombuffer(bytes(u), np.uint8)
-    return blob, in_off, np.array(lens, np.uint64), out_off, np.array(caps, np.uint64), pos + GAP
-
-
-def _host(ctx, f, blob, in_off, lens, out_off, caps, out_total):
-    """a fresh host-table decompress plan: (out_len, status, output bytes incl. guards)"""
-    import torch
-    import ms_compress_amd as m
-    n = len(lens)
-    d_in = torch.from_numpy(blob).cuda()
-    d_out = torch.full((out_total,), GUARD, dtype=torch.uint8, device="cuda")
-    d_len = torch.zeros(max(1, n), dtype=torch.int64, device="cuda")
-    d_st = torch.zeros(max(1, n), dtype=torch.int32, device="cuda")
-    plan = m.Plan(ctx, f, in_off, lens, out_off, caps, decompress=True)
-    plan.execute(d_in, d_out, d_len, d_st)
-    torch.cuda.synchronize()
-    plan.close()
-    return d_len.cpu().numpy()[:n], d_st.cpu().numpy()[:n], d_out.cpu().numpy()
-
-
-class DevRun:
-    """one dev plan and the device buffers of its batches: tables and bytes are rewritten in place between executions"""
-
-    def __init__(self, ctx, f, n, in_bytes, out_bytes, in_max, out_max):
-        import torch
-        import ms_compress_amd as m
-        self.plan = m.DevPlan(ctx, f, n, in_max, out_max)
-        self.n = n
-        self.d_in = torch.zeros(in_bytes, dtype=torch.uint8, device="cuda")
-        self.d_out = torch.full((out_bytes,), GUARD, dtype=torch.uint8, device="cuda")
-        self.tabs = [torch.zeros(max(1, n), dtype=torch.int64, device="cuda") for _ in range(4)]
-        self.d_len = torch.zeros(max(1, n), dtype=torch.int64, device="cuda")
-        self.d_st = torch.full((max(1, n),), 77, dtype=torch.int32, device="cuda")
-
-    def load(self, blob, in_off, lens, out_off, caps):
-        import torch
-        self.d_in[: len(blob)].copy_(torch.from_numpy(blob))
-        for t, a in zip(self.tabs, (in_off, lens, out_off, caps)):
-            t[: self.n].copy_(_dt(a))
-        self.d_out.fill_(GUARD)
-
-    def execute(self):
-        i_off, i_len, o_off, o_cap = self.tabs
-        self.plan.execute(self.d_in, i_off, i_len, self.d_out, o_off, o_cap, self.d_len, self.d_st)
-
-    def result(self):
-        import torch
-        torch.cuda.synchronize()
-        return self.d_len.cpu().numpy()[: self.n], self.d_st.cpu().numpy()[: self.n], self.d_out.cpu().numpy()
-
-
-def _same(host, dev, out_off, caps, out_total, accepted=None):
-    hl, hs, ho = host
-    dl, ds, do = dev
-    n = len(caps)
-    inside = np.zeros(len(do), bool)
-    for i in range(n):
-        if accepted is not None and not accepted[i]:
-            assert ds[i] == -2 and dl[i] == 0, (i, ds[i], dl[i])
-            continue
-        assert (ds[i], dl[i]) == (hs[i], hl[i]), (i, ds[i], hs[i], dl[i], hl[i])
-        o = int(out_off[i])
-        if hs[i] == 0:
-            assert bytes(do[o: o + int(dl[i])]) == bytes(ho[o: o + int(hl[i])]), i
-        inside[o: o + int(caps[i])] = True
-    outside = ~inside
-    outside[out_total:] = True
-    assert (do[outside] == GUARD).all(), np.nonzero(do[outside] != GUARD)[0][:8]
-
-
-def _corpus_units(m, f, sizes=(65536, 700 << 10, 3 << 20)):
-    from ms_compress_amd import corpus
-    data = corpus.by_name("mozilla", sum(sizes) + 1000).tobytes()
-    plain, pos = [], 0
-    for s in sizes:
-        plain.append(data[pos: pos + s])
-        pos += s
-    comp, st = m.compress_units(f, plain)
-    assert all(s == 0 for s in st)
-    return plain, comp
+SIZES = (65536, 700 << 10, 3 << 20)
 
 
 @pytest.mark.parametrize("fmt", list(FMTS))
@@ -118,16 +20,17 @@ def test_dev_plan_matches_host_plan(oracle, gpu_ctx, fmt):
     import ms_compress_amd as m
     f = FMTS[fmt]
     streams = cases.decode_streams(f, lambda d: oracle.oracle_compress(f, d)[1])
-    plain, comp = _corpus_units(m, f)
+    plain, comp = PR.corpus_streams(f, SIZES)
     units = [s for s, _ in streams] + comp
     caps = [c for _, c in streams] + [len(p) for p in plain]
-    blob, in_off, lens, out_off, caps, out_total = _layout(units, caps)
-    host = _host(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
-    r = DevRun(gpu_ctx, f, len(units), len(blob), out_total + 4096, int(lens.sum()), int(caps.sum()))
-    r.load(blob, in_off, lens, out_off, caps)
+    batch = PR.layout(units, caps)
+    blob, in_off, lens, out_off, caps, out_total = batch
+    host = PR.host_run(gpu_ctx, f, batch, "decode")
+    r = PR.DevRun(m.DevPlan(gpu_ctx, f, len(units), int(lens.sum()), int(caps.sum())), len(blob), out_total + 4096)
+    r.load(batch)
     r.execute()
     dev = r.result()
-    _same(host, dev, out_off, caps, out_total)
+    PR.same(host, dev, batch)
     assert (dev[1][-3:] == 0).all() and all(bytes(dev[2][int(out_off[-3 + k]): int(out_off[-3 + k]) + len(plain[k])]) == plain[k] for k in range(3))
     assert sum(int(s) == 0 for s in dev[1]) > 50
 
@@ -146,15 +49,15 @@ def test_one_dev_plan_several_batches(oracle, gpu_ctx, fmt):
         pick = rnd.choice(len(streams), n, replace=False)
         units = [streams[i][0] for i in pick]
         caps = [streams[i][1] + int(rnd.integers(0, 3)) * b for i in pick]
-        batches.append(_layout(units, caps))
+        batches.append(PR.layout(units, caps))
     in_max = max(int(x[2].sum()) for x in batches)
     out_max = max(int(x[4].sum()) for x in batches)
-    r = DevRun(gpu_ctx, f, n, max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096, in_max, out_max)
-    for blob, in_off, lens, out_off, caps, out_total in batches:
-        r.load(blob, in_off, lens, out_off, caps)
+    r = PR.DevRun(m.DevPlan(gpu_ctx, f, n, in_max, out_max), max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096)
+    for batch in batches:
+        r.load(batch)
         r.execute()
         dev = r.result()
-        _same(_host(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total), dev, out_off, caps, out_total)
+        PR.same(PR.host_run(gpu_ctx, f, batch, "decode"), dev, batch)
 
 
 @pytest.mark.parametrize("fmt", list(FMTS))
@@ -169,14 +72,14 @@ def test_chains_stay_on_the_device(gpu_ctx, fmt):
     cuts = [0, 1, 4097, 70_000, 200_000, 200_100, 600_000, 1_200_000]
     plain = [data[a:b] for a, b in zip(cuts, cuts[1:])] + [bytes(5000), b"abc" * 999]
     n = len(plain)
-    blob, in_off, lens, _, _, _ = _layout(plain, [0] * n)
+    blob, in_off, lens, _, _, _ = PR.layout(plain, [0] * n)
     cap = [m.max_compressed_size(f, len(u)) + 2 for u in plain]
     c_off, c_total = m.pack_offsets(cap)
     d_plain = torch.from_numpy(blob).cuda()
     d_comp = torch.zeros(c_total + 16, dtype=torch.uint8, device="cuda")
     d_clen = torch.zeros(n, dtype=torch.int64, device="cuda")
     d_cst = torch.zeros(n, dtype=torch.int32, device="cuda")
-    d_plain_off, d_plain_len = _dt(in_off), _dt(lens)
+    d_plain_off, d_plain_len = PR.dt(in_off), PR.dt(lens)
     cplan = m.Plan(gpu_ctx, f, in_off, lens, c_off, cap)
     cplan.execute(d_plain, d_comp, d_clen, d_cst)
     d_packed, d_poff = m.compact_batch(gpu_ctx, c_off, cap, d_comp, d_clen)
@@ -222,33 +125,35 @@ def test_units_past_the_bounds_are_refused(oracle, gpu_ctx, fmt):
     """an in_len above 0xFFFFF000, and running totals that cross in_total_max / out_total_max partway: those units get MSCOMP_ARG_ERROR
     with length 0, the others decode as with a host plan, and nothing is written outside the accepted units' capacities"""
     import torch
+    import ms_compress_amd as m
     f = FMTS[fmt]
     streams = [s for s in cases.decode_streams(f, lambda d: oracle.oracle_compress(f, d)[1], n_corrupt=0) if len(s[0]) > 8 and s[1] > 8][::7][:40]
     units, caps = [s for s, _ in streams], [c for _, c in streams]
     n = len(units)
-    blob, in_off, lens, out_off, caps, out_total = _layout(units, caps)
-    host = _host(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
+    batch = PR.layout(units, caps)
+    blob, in_off, lens, out_off, caps, out_total = batch
+    host = PR.host_run(gpu_ctx, f, batch, "decode")
     big = 0xFFFFF000 + 1
     # the unit with the long in_len spans an input buffer that really is that long (zeros), its capacity is small
-    r = DevRun(gpu_ctx, f, n, big + len(blob) + 64, out_total + 4096, big + int(lens.sum()), int(caps.sum()))
+    r = PR.DevRun(m.DevPlan(gpu_ctx, f, n, big + int(lens.sum()), int(caps.sum())), big + len(blob) + 64, out_total + 4096)
     lens_bad = lens.copy()
     lens_bad[3] = big
     in_off_bad = in_off.copy()
     in_off_bad[3] = 0
-    r.load(blob, in_off_bad, lens_bad, out_off, caps)
+    r.load(batch._replace(in_off=in_off_bad, lens=lens_bad))
     r.execute()
     acc = np.ones(n, bool)
     acc[3] = False
-    _same(host, r.result(), out_off, caps, out_total, acc)
+    PR.same(host, r.result(), batch, acc)
 
     for in_cut, out_cut in ((n // 2, None), (None, 2 * n // 3), (n // 4, n // 3)):
         in_max = int(lens[: in_cut].sum()) + int(lens[in_cut]) // 2 if in_cut is not None else int(lens.sum())
         out_max = int(caps[: out_cut].sum()) + int(caps[out_cut]) // 2 if out_cut is not None else int(caps.sum())
         lim = min(x for x in (in_cut, out_cut, n) if x is not None)
-        r = DevRun(gpu_ctx, f, n, len(blob), out_total + 4096, in_max, out_max)
-        r.load(blob, in_off, lens, out_off, caps)
+        r = PR.DevRun(m.DevPlan(gpu_ctx, f, n, in_max, out_max), len(blob), out_total + 4096)
+        r.load(batch)
         r.execute()
-        _same(host, r.result(), out_off, caps, out_total, np.arange(n) < lim)
+        PR.same(host, r.result(), batch, np.arange(n) < lim)
     del r
     torch.cuda.synchronize()
 
@@ -267,7 +172,7 @@ def test_plan_kinds_are_kept_apart(gpu_ctx):
     dev = m.DevPlan(gpu_ctx, 2, n, 64, 64)
     d_in = torch.zeros(64, dtype=torch.uint8, device="cuda")
     d_out = torch.full((64,), GUARD, dtype=torch.uint8, device="cuda")
-    t = [_dt(off), _dt(ln), _dt(off), _dt(ln)]
+    t = [PR.dt(off), PR.dt(ln), PR.dt(off), PR.dt(ln)]
     d_len = torch.full((n,), 5, dtype=torch.int64, device="cuda")
     d_need = torch.full((n,), 5, dtype=torch.int64, device="cuda")
     d_st = torch.full((n,), 77, dtype=torch.int32, device="cuda")
@@ -298,25 +203,24 @@ def test_dev_plan_in_a_captured_graph(oracle, gpu_ctx, fmt):
     batches = []
     for _ in range(3):
         pick = rnd.choice(len(streams), n, replace=False)
-        batches.append(_layout([streams[i][0] for i in pick], [streams[i][1] for i in pick]))
+        batches.append(PR.layout([streams[i][0] for i in pick], [streams[i][1] for i in pick]))
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        r = DevRun(ctx, f, n, max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096,
-                   max(int(x[2].sum()) for x in batches), max(int(x[4].sum()) for x in batches))
-        r.load(*batches[0][:5])
+        r = PR.DevRun(m.DevPlan(ctx, f, n, max(int(x[2].sum()) for x in batches), max(int(x[4].sum()) for x in batches)),
+                      max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096)
+        r.load(batches[0])
         r.execute()                                                   # (once outside the capture)
     s.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=s):
         r.execute()
-    for blob, in_off, lens, out_off, caps, out_total in batches[1:] + batches[:1]:
+    for batch in batches[1:] + batches[:1]:
         with torch.cuda.stream(s):
-            r.load(blob, in_off, lens, out_off, caps)
-            r.d_st.fill_(77)
+            r.load(batch)
             g.replay()
         s.synchronize()
-        _same(_host(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total), r.result(), out_off, caps, out_total)
+        PR.same(PR.host_run(gpu_ctx, f, batch, "decode"), r.result(), batch)
     del g
     r.plan.close()
     ctx.close()

@@ -13,29 +13,13 @@ import numpy as np
 import pytest
 
 import cases
-from test_gpu_decompress_dev import GUARD, _dt, _layout, _same
+import plans_rig as PR
+from plans_rig import FMTS, GUARD
 
 pytestmark = pytest.mark.gpu
-FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
 XFMTS = ["xpress", "xpress_huff"]
-XPS_MIN_IN, LZG_MIN_CAP = 512 << 10, 1 << 20
 SIZES = (65536, 700 << 10, 3 << 20, 12 << 20)
 _cache = {}
-
-
-def _corpus(m, ctx, f):
-    """corpus units of 64 KiB, 700 KiB, 3 MB and 12 MB and their streams (made once per format)"""
-    if f not in _cache:
-        from ms_compress_amd import corpus
-        data = corpus.by_name("mozilla", sum(SIZES) + 1000).tobytes()
-        plain, pos = [], 0
-        for s in SIZES:
-            plain.append(data[pos: pos + s])
-            pos += s
-        comp, st = m.compress_units(f, plain, ctx=ctx)
-        assert all(s == 0 for s in st)
-        _cache[f] = (plain, comp)
-    return _cache[f]
 
 
 def _small(m, ctx, f, count):
@@ -50,78 +34,11 @@ def _small(m, ctx, f, count):
     return _cache[key]
 
 
-def _assert_large(f, stream, cap):
-    """the unit really takes the paths this file is about"""
-    assert cap >= LZG_MIN_CAP, cap
-    if f == 3:
-        assert len(stream) >= XPS_MIN_IN, len(stream)
-
-
-def _modes(ctx, cap=8):
-    out = (C.c_uint32 * cap)()
-    k = ctx.lib.mscomp_amd_debug_decode_modes(ctx._h, out, cap)
-    assert k >= 0
-    return [int(x) for x in out[: min(k, cap)]]
-
-
-def _host_run(ctx, f, blob, in_off, lens, out_off, caps, out_bytes):
-    """a fresh host-table decompress plan: ((out_len, status, output bytes incl. guards), paths, decode modes)"""
-    import torch
-    import ms_compress_amd as m
-    n = len(lens)
-    d_in = torch.from_numpy(blob).cuda()
-    d_out = torch.full((out_bytes,), GUARD, dtype=torch.uint8, device="cuda")
-    d_len = torch.zeros(max(1, n), dtype=torch.int64, device="cuda")
-    d_st = torch.zeros(max(1, n), dtype=torch.int32, device="cuda")
-    plan = m.Plan(ctx, f, in_off, lens, out_off, caps, decompress=True)
-    plan.execute(d_in, d_out, d_len, d_st)
-    torch.cuda.synchronize()
-    paths, modes = m.api.plan_paths(plan), _modes(ctx)
-    plan.close()
-    return (d_len.cpu().numpy()[:n], d_st.cpu().numpy()[:n], d_out.cpu().numpy()), paths, modes
-
-
-class LargeRun:
-    """one dev plan (large_units unless told otherwise) and the device buffers of its batches, rewritten in place between executions"""
-
-    def __init__(self, ctx, f, n, in_bytes, out_bytes, in_max, out_max, large_units=True):
-        import torch
-        import ms_compress_amd as m
-        self.plan = m.DevPlan(ctx, f, n, in_max, out_max, large_units=large_units)
-        self.n = n
-        self.d_in = torch.zeros(in_bytes, dtype=torch.uint8, device="cuda")
-        self.d_out = torch.full((out_bytes,), GUARD, dtype=torch.uint8, device="cuda")
-        self.tabs = [torch.zeros(max(1, n), dtype=torch.int64, device="cuda") for _ in range(4)]
-        self.d_len = torch.zeros(max(1, n), dtype=torch.int64, device="cuda")
-        self.d_st = torch.full((max(1, n),), 77, dtype=torch.int32, device="cuda")
-
-    def load(self, blob, in_off, lens, out_off, caps):
-        import torch
-        self.d_in[: len(blob)].copy_(torch.from_numpy(blob))
-        for t, a in zip(self.tabs, (in_off, lens, out_off, caps)):
-            t[: self.n].copy_(_dt(a))
-        self.d_out.fill_(GUARD)
-        self.d_st.fill_(77)
-
-    def execute(self):
-        i_off, i_len, o_off, o_cap = self.tabs
-        self.plan.execute(self.d_in, i_off, i_len, self.d_out, o_off, o_cap, self.d_len, self.d_st)
-
-    def result(self):
-        import torch
-        torch.cuda.synchronize()
-        return self.d_len.cpu().numpy()[: self.n], self.d_st.cpu().numpy()[: self.n], self.d_out.cpu().numpy()
-
-    def paths(self):
-        import ms_compress_amd as m
-        return m.api.plan_paths(self.plan)
-
-
 def _mixed_batch(m, ctx, oracle, f, order=0):
     """the decode families and the corpus units (exact, one short, generous capacities), the large ones at places that depend on `order`"""
-    plain, comp = _corpus(m, ctx, f)
-    _assert_large(f, comp[2], len(plain[2]))
-    _assert_large(f, comp[3], len(plain[3]))
+    plain, comp = PR.corpus_streams(f, SIZES, ctx)
+    PR.assert_large(f, comp[2], len(plain[2]))
+    PR.assert_large(f, comp[3], len(plain[3]))
     streams = cases.decode_streams(f, lambda d: oracle.oracle_compress(f, d)[1], n_corrupt=20)
     big = [(comp[0], len(plain[0])), (comp[1], len(plain[1])), (comp[2], len(plain[2])), (comp[3], len(plain[3])),
            (comp[2], len(plain[2]) - 1), (comp[2], len(plain[2]) + (1 << 20)), (comp[3], len(plain[3]) + 5000)]
@@ -140,14 +57,15 @@ def test_same_results_as_a_host_plan(oracle, gpu_ctx, fmt):
     import ms_compress_amd as m
     f = FMTS[fmt]
     pairs = _mixed_batch(m, gpu_ctx, oracle, f)
-    blob, in_off, lens, out_off, caps, out_total = _layout([s for s, _ in pairs], [c for _, c in pairs])
-    host, hpaths, _ = _host_run(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
-    r = LargeRun(gpu_ctx, f, len(pairs), len(blob), out_total + 4096, int(lens.sum()), int(caps.sum()))
-    r.load(blob, in_off, lens, out_off, caps)
+    batch = PR.layout([s for s, _ in pairs], [c for _, c in pairs])
+    blob, in_off, lens, out_off, caps, out_total = batch
+    host, hpaths, _ = PR.host_run(gpu_ctx, f, batch, "decode", want_paths=True)
+    r = PR.DevRun(m.DevPlan(gpu_ctx, f, len(pairs), int(lens.sum()), int(caps.sum()), large_units=True), len(blob), out_total + 4096)
+    r.load(batch)
     r.execute()
     dev = r.result()
-    _same(host, dev, out_off, caps, out_total)
-    assert r.paths() == hpaths and hpaths[1] >= 4 and (f != 3 or hpaths[0] >= 4), (r.paths(), hpaths)
+    PR.same(host, dev, batch)
+    assert m.api.plan_paths(r.plan) == hpaths and hpaths[1] >= 4 and (f != 3 or hpaths[0] >= 4), (m.api.plan_paths(r.plan), hpaths)
     n_big = 0
     for i, (stream, cap) in enumerate(pairs):
         if cap >= 60000 and len(stream) > 30000:                    # the corpus units, against the oracle
@@ -162,9 +80,9 @@ def test_same_results_as_a_host_plan(oracle, gpu_ctx, fmt):
 
 
 def _one_large_among_small(m, ctx, f, count=3000):
-    plain, comp = _corpus(m, ctx, f)
+    plain, comp = PR.corpus_streams(f, SIZES, ctx)
     sp, sc = _small(m, ctx, f, count)
-    _assert_large(f, comp[3], len(plain[3]))
+    PR.assert_large(f, comp[3], len(plain[3]))
     units = sc[: count // 2] + [comp[3]] + sc[count // 2:]
     caps = [len(p) for p in sp[: count // 2]] + [len(plain[3])] + [len(p) for p in sp[count // 2:]]
     return units, caps, count // 2
@@ -179,30 +97,31 @@ def test_same_paths_as_a_host_plan(oracle, gpu_ctx, fmt):
     import torch
     import ms_compress_amd as m
     f = FMTS[fmt]
-    plain, comp = _corpus(m, gpu_ctx, f)
+    plain, comp = PR.corpus_streams(f, SIZES, gpu_ctx)
     # (a)
     units, caps, at = _one_large_among_small(m, gpu_ctx, f)
-    blob, in_off, lens, out_off, caps, out_total = _layout(units, caps)
-    host, hpaths, hmodes = _host_run(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
+    batch = PR.layout(units, caps)
+    blob, in_off, lens, out_off, caps, out_total = batch
+    host, hpaths, hmodes = PR.host_run(gpu_ctx, f, batch, "decode", want_paths=True)
     assert hpaths[0] == (1 if f == 3 else 0) and hpaths[1] == 1 and (f == 3 or hpaths[2] > 0), hpaths
-    r = LargeRun(gpu_ctx, f, len(units), len(blob), out_total + 4096, int(lens.sum()), int(caps.sum()))
-    r.load(blob, in_off, lens, out_off, caps)
+    r = PR.DevRun(m.DevPlan(gpu_ctx, f, len(units), int(lens.sum()), int(caps.sum()), large_units=True), len(blob), out_total + 4096)
+    r.load(batch)
     r.execute()
     dev = r.result()
-    assert r.paths() == hpaths, (r.paths(), hpaths)
+    assert m.api.plan_paths(r.plan) == hpaths, (m.api.plan_paths(r.plan), hpaths)
     if f == 3:
-        assert _modes(gpu_ctx) == [2] and hmodes == [2]
+        assert PR.decode_modes(gpu_ctx) == [2] and hmodes == [2]
     opened = (C.c_uint32 * 33)()
     gpu_ctx.lib.mscomp_amd_debug_lzg_open.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
     assert gpu_ctx.lib.mscomp_amd_debug_lzg_open(gpu_ctx._h, int(caps[at]) + 64, opened) == 0
     opened = list(opened)
     assert opened[0] > 0 and 0 in opened and all(x == 0 for x in opened[opened.index(0):]), opened   # the path ran, took several passes, and ended
-    _same(host, dev, out_off, caps, out_total)
+    PR.same(host, dev, batch)
     assert dev[1][at] == 0 and bytes(dev[2][int(out_off[at]): int(out_off[at]) + len(plain[3])]) == plain[3]
     r.plan.close()
-    plainp = LargeRun(gpu_ctx, f, len(units), len(blob), out_total + 4096, int(lens.sum()), int(caps.sum()), large_units=False)
-    plainp.load(blob, in_off, lens, out_off, caps)
-    assert plainp.paths() == (0, 0, 0)
+    plainp = PR.DevRun(m.DevPlan(gpu_ctx, f, len(units), int(lens.sum()), int(caps.sum())), len(blob), out_total + 4096)
+    plainp.load(batch)
+    assert m.api.plan_paths(plainp.plan) == (0, 0, 0)
     plainp.plan.close()                                              # (not executed: the one-wave walk of 12 MB is what the flag is for)
     del r, plainp
 
@@ -210,7 +129,7 @@ def test_same_paths_as_a_host_plan(oracle, gpu_ctx, fmt):
     one = plain[3][: 1 << 20]
     c1, st = m.compress_units(f, [one], ctx=gpu_ctx)
     assert st[0] == 0
-    _assert_large(f, c1[0], len(one))
+    PR.assert_large(f, c1[0], len(one))
     n = 300
     blob = np.zeros(len(c1[0]) + 16, np.uint8)
     blob[: len(c1[0])] = np.frombuffer(c1[0], np.uint8)
@@ -227,43 +146,45 @@ def test_same_paths_as_a_host_plan(oracle, gpu_ctx, fmt):
     hpaths = m.api.plan_paths(hp)
     hp.close()
     assert hpaths[0] == (n if f == 3 else 0) and hpaths[1] == 0, hpaths
-    r = LargeRun(gpu_ctx, f, n, len(blob), out_total, int(lens.sum()), int(caps.sum()))
-    r.load(blob, in_off, lens, out_off, caps)
+    r = PR.DevRun(m.DevPlan(gpu_ctx, f, n, int(lens.sum()), int(caps.sum()), large_units=True), len(blob), out_total)
+    r.load(PR.Batch(blob, in_off, lens, out_off, caps, out_total))
     r.execute()
     torch.cuda.synchronize()
-    assert r.paths() == hpaths, (r.paths(), hpaths)
-    assert torch.equal(r.d_out, h_out) and torch.equal(r.d_len, h_len) and torch.equal(r.d_st, h_st)
+    assert m.api.plan_paths(r.plan) == hpaths, (m.api.plan_paths(r.plan), hpaths)
+    mine = slice(PR.PAD, PR.PAD + n)                                  # (compared on the device: 300 MiB of output stay there)
+    assert torch.equal(r.d_out, h_out) and torch.equal(r.d_len[mine], h_len) and torch.equal(r.d_st[mine], h_st)
     assert (h_st.cpu().numpy() == 0).all() and bytes(r.d_out[int(out_off[n - 1]): int(out_off[n - 1]) + len(one)].cpu().numpy()) == one
     r.plan.close()
     del r, h_out
 
     # (c) small units only
     sp, sc = _small(m, gpu_ctx, f, 3000)
-    blob, in_off, lens, out_off, caps, out_total = _layout(sc[:500], [len(p) for p in sp[:500]])
-    host, hpaths, _ = _host_run(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
-    r = LargeRun(gpu_ctx, f, 500, len(blob), out_total + 4096, 64 << 20, 64 << 20)   # (bounds with room for large units: none comes)
-    r.load(blob, in_off, lens, out_off, caps)
+    batch = PR.layout(sc[:500], [len(p) for p in sp[:500]])
+    host, hpaths, _ = PR.host_run(gpu_ctx, f, batch, "decode", want_paths=True)
+    r = PR.DevRun(m.DevPlan(gpu_ctx, f, 500, 64 << 20, 64 << 20, large_units=True), len(batch.blob), batch.out_total + 4096)   # (bounds with room for large units: none comes)
+    r.load(batch)
     r.execute()
-    _same(host, r.result(), out_off, caps, out_total)
-    assert r.paths() == hpaths == (0, 0, 0)
+    PR.same(host, r.result(), batch)
+    assert m.api.plan_paths(r.plan) == hpaths == (0, 0, 0)
     r.plan.close()
     del r
 
     # (d) a capacity of 0xFFFFFF00 and more: its bytes end long before the buffer does
-    _assert_large(f, comp[2], len(plain[2]))
+    PR.assert_large(f, comp[2], len(plain[2]))
     units = [comp[2], sc[0], comp[1]]
     caps = np.array([len(plain[2]), len(sp[0]), 0xFFFFFF00], np.uint64)
-    blob, in_off, lens, _, _, _ = _layout(units, [0, 0, 0])
+    blob, in_off, lens, _, _, _ = PR.layout(units, [0, 0, 0])
     out_off = np.array([64, len(plain[2]) + 128, len(plain[2]) + len(sp[0]) + 192], np.uint64)
     out_bytes = int(out_off[2]) + len(plain[1]) + 4096
-    host, hpaths, _ = _host_run(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_bytes)
+    batch = PR.Batch(blob, in_off, lens, out_off, caps, out_bytes)
+    host, hpaths, _ = PR.host_run(gpu_ctx, f, batch, "decode", want_paths=True)
     assert hpaths[1] == 0 and hpaths[0] == (1 if f == 3 else 0), hpaths
     ctx = m.Context()                                               # (a plan of its own: its all-CU scratch for more than 4 GiB goes away with the context)
-    r = LargeRun(ctx, f, 3, len(blob), out_bytes, int(lens.sum()), int(caps.sum()))
-    r.load(blob, in_off, lens, out_off, caps)
+    r = PR.DevRun(m.DevPlan(ctx, f, 3, int(lens.sum()), int(caps.sum()), large_units=True), len(blob), out_bytes)
+    r.load(batch)
     r.execute()
     dl, ds, do = r.result()
-    assert r.paths() == hpaths, (r.paths(), hpaths)
+    assert m.api.plan_paths(r.plan) == hpaths, (m.api.plan_paths(r.plan), hpaths)
     assert list(ds) == [0, 0, 0] == list(host[1]) and list(dl) == list(host[0]) == [len(plain[2]), len(sp[0]), len(plain[1])]
     assert (do == host[2]).all()
     assert bytes(do[int(out_off[2]): int(out_off[2]) + len(plain[1])]) == plain[1] and bytes(do[64: 64 + len(plain[2])]) == plain[2]
@@ -285,17 +206,17 @@ def test_one_plan_changing_batches(oracle, gpu_ctx, fmt):
     without = (streams * 2)[:n]
     others = _mixed_batch(m, gpu_ctx, oracle, f, 3)
     assert len(without) == n == len(others) and [c for _, c in others] != [c for _, c in with_large]
-    batches = [_layout([s for s, _ in b], [c for _, c in b]) for b in (with_large, without, others)]
-    r = LargeRun(gpu_ctx, f, n, max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096,
-                 max(int(x[2].sum()) for x in batches), max(int(x[4].sum()) for x in batches))
+    batches = [PR.layout([s for s, _ in b], [c for _, c in b]) for b in (with_large, without, others)]
+    r = PR.DevRun(m.DevPlan(gpu_ctx, f, n, max(int(x[2].sum()) for x in batches), max(int(x[4].sum()) for x in batches), large_units=True),
+                  max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096)
     seen = []
-    for blob, in_off, lens, out_off, caps, out_total in batches:
-        r.load(blob, in_off, lens, out_off, caps)
+    for batch in batches:
+        r.load(batch)
         r.execute()
         dev = r.result()
-        host, hpaths, _ = _host_run(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
-        _same(host, dev, out_off, caps, out_total)
-        assert r.paths() == hpaths, (r.paths(), hpaths)
+        host, hpaths, _ = PR.host_run(gpu_ctx, f, batch, "decode", want_paths=True)
+        PR.same(host, dev, batch)
+        assert m.api.plan_paths(r.plan) == hpaths, (m.api.plan_paths(r.plan), hpaths)
         seen.append(hpaths)
     assert seen[0][1] >= 4 and seen[1][1] == 0 and seen[2][1] >= 4 and (f != 3 or (seen[0][0] >= 4 and seen[1][0] == 0))
     r.plan.close()
@@ -315,26 +236,26 @@ def test_in_a_callers_graph(oracle, gpu_ctx, fmt):
     else:
         sets = [_mixed_batch(m, gpu_ctx, oracle, f, 0), _mixed_batch(m, gpu_ctx, oracle, f, 2), _mixed_batch(m, gpu_ctx, oracle, f, 5)]
     n = len(sets[0])
-    batches = [_layout([s for s, _ in b], [c for _, c in b]) for b in sets]
+    batches = [PR.layout([s for s, _ in b], [c for _, c in b]) for b in sets]
     s = torch.cuda.Stream()
     ctx = m.Context(stream=s)
     with torch.cuda.stream(s):
-        r = LargeRun(ctx, f, n, max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096,
-                     max(int(x[2].sum()) for x in batches), max(int(x[4].sum()) for x in batches))
-        r.load(*batches[0][:5])
+        r = PR.DevRun(m.DevPlan(ctx, f, n, max(int(x[2].sum()) for x in batches), max(int(x[4].sum()) for x in batches), large_units=True),
+                      max(len(x[0]) for x in batches), max(x[5] for x in batches) + 4096)
+        r.load(batches[0])
         r.execute()                                                   # (once outside the capture)
     s.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=s):
         r.execute()
-    for blob, in_off, lens, out_off, caps, out_total in batches[1:] + batches[:1]:
+    for batch in batches[1:] + batches[:1]:
         with torch.cuda.stream(s):
-            r.load(blob, in_off, lens, out_off, caps)
+            r.load(batch)
             g.replay()
         s.synchronize()
-        host, hpaths, _ = _host_run(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
-        _same(host, r.result(), out_off, caps, out_total)
-        assert r.paths() == (hpaths if f != 2 else (0, 0, 0)), (r.paths(), hpaths)
+        host, hpaths, _ = PR.host_run(gpu_ctx, f, batch, "decode", want_paths=True)
+        PR.same(host, r.result(), batch)
+        assert m.api.plan_paths(r.plan) == (hpaths if f != 2 else (0, 0, 0)), (m.api.plan_paths(r.plan), hpaths)
     del g
     r.plan.close()
     ctx.close()
@@ -346,26 +267,27 @@ def test_rejected_large_units_take_no_path(oracle, gpu_ctx, fmt):
     length 0, nothing written, not counted by plan_paths; the units before it decode as with a host plan, the empty ones behind it too"""
     import ms_compress_amd as m
     f = FMTS[fmt]
-    plain, comp = _corpus(m, gpu_ctx, f)
+    plain, comp = PR.corpus_streams(f, SIZES, gpu_ctx)
     sp, sc = _small(m, gpu_ctx, f, 3000)
-    _assert_large(f, comp[2], len(plain[2]))
+    PR.assert_large(f, comp[2], len(plain[2]))
     units = [sc[0], comp[2], sc[1], comp[2], b"", b""]
     caps = [len(sp[0]), len(plain[2]), len(sp[1]), len(plain[2]), 0, 0]
-    blob, in_off, lens, out_off, caps, out_total = _layout(units, caps)
-    host, hpaths, _ = _host_run(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
+    batch = PR.layout(units, caps)
+    blob, in_off, lens, out_off, caps, out_total = batch
+    host, hpaths, _ = PR.host_run(gpu_ctx, f, batch, "decode", want_paths=True)
     assert hpaths[0] == (2 if f == 3 else 0) and hpaths[1] == 2, hpaths
     # (an empty unit behind the rejected one adds nothing to a running total, but the total it is judged at is past the bound: rejected too)
     acc_behind = np.array([True, True, True, False, False, False])
     for in_max, out_max in ((int(lens[:4].sum()) - 1, int(caps.sum())), (int(lens.sum()), int(caps[:4].sum()) - 1)):
-        r = LargeRun(gpu_ctx, f, len(units), len(blob), out_total + 4096, in_max, out_max)
-        r.load(blob, in_off, lens, out_off, caps)
+        r = PR.DevRun(m.DevPlan(gpu_ctx, f, len(units), in_max, out_max, large_units=True), len(blob), out_total + 4096)
+        r.load(batch)
         r.execute()
         dev = r.result()
-        _same(host, dev, out_off, caps, out_total, acc_behind)
+        PR.same(host, dev, batch, acc_behind)
         assert list(dev[1][:3]) == [0, 0, 0] and dev[1][3] == -2 and dev[0][3] == 0
         o = int(out_off[3])
         assert (dev[2][o: o + int(caps[3])] == GUARD).all()
-        got = r.paths()
+        got = m.api.plan_paths(r.plan)
         assert got[0] == (1 if f == 3 else 0) and got[1] == 1, got
         r.plan.close()
 
@@ -375,26 +297,24 @@ def test_size_plans_walk_large_streams_by_segments(gpu_ctx, fmt):
     """SizeDevPlan(large_units=True) on one 12 MB unit among 3 000 small ones: status, length and need equal the host size plan's, with
     and without limits, and at limits just below and at the large unit's length; the large Xpress stream is sized by segments"""
     import ms_compress_amd as m
-    from test_gpu_size_dev import SizeRun, _host as _size_host, _pack, _same as _size_same
     f = FMTS[fmt]
-    plain, _ = _corpus(m, gpu_ctx, f)
+    plain, _ = PR.corpus_streams(f, SIZES, gpu_ctx)
     units, caps, at = _one_large_among_small(m, gpu_ctx, f)
-    blob, in_off, lens = _pack(units)
+    batch = PR.layout(units)
     caps = np.array(caps, np.uint64)
 
-    r = SizeRun(gpu_ctx, f, len(units), len(blob), int(lens.sum()))
-    r.plan.close()                                                  # (SizeRun makes a plain size dev plan: the same buffers, a plan with the flag)
-    r.plan = m.SizeDevPlan(gpu_ctx, f, len(units), int(lens.sum()), large_units=True)
+    r = PR.DevRun(m.SizeDevPlan(gpu_ctx, f, len(units), int(batch.lens.sum()), large_units=True), len(batch.blob), 0)
     below, at_len = caps.copy(), caps.copy()
     below[at] = len(plain[3]) - 1
     for limits in (None, caps, below, at_len):
-        host = _size_host(gpu_ctx, f, blob, in_off, lens, limits)
-        hmodes = _modes(gpu_ctx)
-        r.load(blob, in_off, lens, limits)
+        b = batch._replace(caps=limits)
+        host = PR.host_run(gpu_ctx, f, b, "size")
+        hmodes = PR.decode_modes(gpu_ctx)
+        r.load(b)
         r.execute(limited=limits is not None)
         dev = r.result()
-        dmodes = _modes(gpu_ctx)
-        _size_same(host, dev)
+        dmodes = PR.decode_modes(gpu_ctx)
+        PR.same_sizes(host, dev)
         paths = m.api.plan_paths(r.plan)
         assert paths == ((1, 0, 0) if f == 3 else (0, 0, 0)), paths
         if f == 3:
@@ -402,9 +322,9 @@ def test_size_plans_walk_large_streams_by_segments(gpu_ctx, fmt):
             if limits is not below:
                 assert dmodes == [2]
         if limits is not below:
-            assert dev[2][at] == 0 and int(dev[0][at]) == len(plain[3]) == int(dev[1][at])
+            assert dev[1][at] == 0 and int(dev[0][at]) == len(plain[3]) == int(dev[3][at])
         else:
-            assert dev[2][at] != 0
+            assert dev[1][at] != 0
     r.plan.close()
 
 
@@ -413,28 +333,28 @@ import os, sys
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import numpy as np, torch
 import ms_compress_amd as m
-from test_gpu_dev_large_units import LargeRun, _corpus, _host_run, _assert_large
-from test_gpu_decompress_dev import _layout, _same
+import plans_rig as PR
 ctx = m.Context()
 for f in (3, 4):
-    plain, comp = _corpus(m, ctx, f)
-    _assert_large(f, comp[2], len(plain[2])); _assert_large(f, comp[3], len(plain[3]))
+    plain, comp = PR.corpus_streams(f, %r, ctx)
+    PR.assert_large(f, comp[2], len(plain[2])); PR.assert_large(f, comp[3], len(plain[3]))
     units, caps = [comp[0], comp[3], comp[1], comp[2]], [len(plain[0]), len(plain[3]), len(plain[1]), len(plain[2])]
-    blob, in_off, lens, out_off, caps, out_total = _layout(units, caps)
-    host, hpaths, _ = _host_run(ctx, f, blob, in_off, lens, out_off, caps, out_total)
-    r = LargeRun(ctx, f, 4, len(blob), out_total + 4096, int(lens.sum()), int(caps.sum()))
-    r.load(blob, in_off, lens, out_off, caps)
+    batch = PR.layout(units, caps)
+    blob, in_off, lens, out_off, caps, out_total = batch
+    host, hpaths, _ = PR.host_run(ctx, f, batch, "decode", want_paths=True)
+    r = PR.DevRun(m.DevPlan(ctx, f, 4, int(lens.sum()), int(caps.sum()), large_units=True), len(blob), out_total + 4096)
+    r.load(batch)
     r.execute()
     dev = r.result()
-    _same(host, dev, out_off, caps, out_total)
+    PR.same(host, dev, batch)
     for k, i in enumerate((0, 3, 1, 2)):
         assert dev[1][k] == 0 and bytes(dev[2][int(out_off[k]): int(out_off[k]) + len(plain[i])]) == plain[i]
-    got = r.paths()
+    got = m.api.plan_paths(r.plan)
     assert got == hpaths and got[1] == 0 and got[2] == 0 and got[0] == (2 if f == 3 else 0), (got, hpaths)
     r.plan.close()
 ctx.close()
 print("BUDGETS-OFF-OK")
-"""
+""" % (SIZES,)
 
 
 def test_budgets_off(gpu_ctx):
@@ -453,16 +373,16 @@ def test_the_whole_chain_with_a_large_unit(gpu_ctx, fmt):
     import torch
     import ms_compress_amd as m
     f = FMTS[fmt]
-    plain, comp = _corpus(m, gpu_ctx, f)
+    plain, comp = PR.corpus_streams(f, SIZES, gpu_ctx)
     sp, sc = _small(m, gpu_ctx, f, 3000)
-    _assert_large(f, comp[3], len(plain[3]))
-    _assert_large(f, comp[2], len(plain[2]))
+    PR.assert_large(f, comp[3], len(plain[3]))
+    PR.assert_large(f, comp[2], len(plain[2]))
     orig = [sp[0], plain[3], sp[1], plain[1], plain[2], sp[2]]
     units = [sc[0], comp[3], sc[1], comp[1], comp[2], sc[2]]
     n = len(units)
-    blob, in_off, lens, _, _, _ = _layout(units, [0] * n)
+    blob, in_off, lens, _, _, _ = PR.layout(units, [0] * n)
     total_plain = sum(len(p) for p in orig)
-    d_in, d_in_off, d_in_len = torch.from_numpy(blob).cuda(), _dt(in_off), _dt(lens)
+    d_in, d_in_off, d_in_len = torch.from_numpy(blob).cuda(), PR.dt(in_off), PR.dt(lens)
     Z = lambda dt=torch.int64: torch.zeros(n, dtype=dt, device="cuda")  # noqa: E731
     d_slen, d_need, d_sst = Z(), Z(), Z(torch.int32)
     d_len1, d_st1, d_clen, d_cst, d_len2, d_st2 = Z(), Z(torch.int32), Z(), Z(torch.int32), Z(), Z(torch.int32)

@@ -7,13 +7,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import plans_rig as PR
 import test_foreign_streams as tf
+from plans_rig import FMTS, LZG_MIN_CAP, XPS_MIN_IN
 from refanswers import digest
 
 pytestmark = pytest.mark.gpu
-FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
-XPS_MIN_IN = 512 << 10                                               # csrc/kernels.h
-LZG_MIN_CAP = 1 << 20
 XHC_SERIAL, XHC_SPEC = 1, 2
 
 
@@ -126,17 +125,18 @@ def test_size_query_agrees_with_the_decoder(oracle, gpu_ctx, fmt):
 
 @pytest.mark.parametrize("fmt", list(FMTS))
 def test_device_table_plan_matches_host_plan(oracle, gpu_ctx, fmt):
-    import test_gpu_decompress_dev as td
+    import ms_compress_amd as m
     f = FMTS[fmt]
     fam, _ = tf.family(f)
     units, caps = [s.data for s in fam], [s.cap for s in fam]
-    blob, in_off, lens, out_off, caps, out_total = td._layout(units, caps)
-    host = td._host(gpu_ctx, f, blob, in_off, lens, out_off, caps, out_total)
-    r = td.DevRun(gpu_ctx, f, len(units), len(blob), out_total + 4096, int(lens.sum()), int(caps.sum()))
-    r.load(blob, in_off, lens, out_off, caps)
+    batch = PR.layout(units, caps)
+    blob, in_off, lens, out_off, caps, out_total = batch
+    host = PR.host_run(gpu_ctx, f, batch, "decode")
+    r = PR.DevRun(m.DevPlan(gpu_ctx, f, len(units), int(lens.sum()), int(caps.sum())), len(blob), out_total + 4096)
+    r.load(batch)
     r.execute()
     dev = r.result()
-    td._same(host, dev, out_off, caps, out_total)
+    PR.same(host, dev, batch)
     for i, s in enumerate(fam):
         if s.plain is not None:
             o = int(out_off[i])

@@ -5,6 +5,8 @@ import hashlib
 import numpy as np
 import pytest
 
+import plans_rig as PR
+
 pytestmark = pytest.mark.gpu
 
 
@@ -25,20 +27,11 @@ def _oracle_units(oracle, fmt, blob, in_off, in_len, threads=32):
 
 
 def _gpu_units(m, ctx, fmt, blob, in_off, in_len):
-    import torch
     caps = [m.max_compressed_size(fmt, int(x)) + 2 for x in in_len]
     out_off, out_total = m.pack_offsets(caps)
-    dev = torch.device("cuda", ctx.device)
-    d_in = torch.from_numpy(blob).to(dev)
-    d_out = torch.zeros(out_total + 16, dtype=torch.uint8, device=dev)
-    d_len = torch.zeros(len(in_len), dtype=torch.int64, device=dev)
-    d_st = torch.zeros(len(in_len), dtype=torch.int32, device=dev)
-    plan = m.Plan(ctx, fmt, in_off, in_len, out_off, caps)
-    plan.execute(d_in, d_out, d_len, d_st)
-    torch.cuda.synchronize()
-    plan.close()
-    assert bool((d_st == 0).all().item())
-    return d_out.cpu().numpy(), out_off, d_len.cpu().numpy()
+    out_len, st, out = PR.host_run(ctx, fmt, PR.Batch(blob, in_off, in_len, out_off, caps, out_total + 16), "compress")
+    assert (st == 0).all()
+    return out, out_off, out_len
 
 
 def _compare(m, oracle, ctx, fmt, blob, in_off, in_len, roundtrip_units=4):

@@ -19,14 +19,13 @@ import pytest
 import cases
 import test_foreign_streams as tf
 import crc_model as K
-from test_gpu_decompress_dev import GUARD, _dt, _layout
-from test_gpu_dev_large_units import LZG_MIN_CAP, XPS_MIN_IN
 import blocks_model as M
 import blocks_rig as G
+import plans_rig as PR
 import read_model as R
+from plans_rig import FMTS, GUARD, LZG_MIN_CAP, XPS_MIN_IN
 
 pytestmark = pytest.mark.gpu
-FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
 POISONS = (0x00, 0xFF, 0xA5)
 
 SCAN = ("prefix", "tile_sums")
@@ -152,43 +151,7 @@ def cycle(ctx, runs, claims, targets=(), check=None):
         _slack_clean(t, 0x11, "control")
 
 
-class HostRun:
-    """one host-table plan (compress, decompress or size) and the device buffers of its batch"""
-
-    def __init__(self, ctx, f, units, caps, kind):
-        import torch
-        import ms_compress_amd as m
-        self.ctx, self.n = ctx, len(units)
-        blob, in_off, lens, out_off, caps, self.out_total = _layout(units, caps)
-        self.out_off, self.caps = out_off, caps
-        self.d_in = torch.from_numpy(blob).cuda()
-        self.d_out = torch.empty(self.out_total, dtype=torch.uint8, device="cuda")
-        self.d_len = torch.empty(max(1, self.n), dtype=torch.int64, device="cuda")
-        self.d_need = torch.empty(max(1, self.n), dtype=torch.int64, device="cuda")
-        self.d_st = torch.empty(max(1, self.n), dtype=torch.int32, device="cuda")
-        self.size = kind == "size"
-        self.plan = m.SizePlan(ctx, f, in_off, lens, caps) if self.size else m.Plan(ctx, f, in_off, lens, out_off, caps, decompress=kind == "decode")
-
-    def run(self):
-        self.d_out.fill_(GUARD); self.d_len.fill_(-7); self.d_need.fill_(-7); self.d_st.fill_(-9)
-        if self.size:
-            self.plan.execute(self.d_in, self.d_len, self.d_need, self.d_st)
-        else:
-            self.plan.execute(self.d_in, self.d_out, self.d_len, self.d_st)
-        self.ctx.stream.synchronize()
-        return self.d_len.cpu().numpy(), self.d_st.cpu().numpy(), self.d_out.cpu().numpy(), self.d_need.cpu().numpy()
-
-    def unit(self, res, i):
-        return bytes(res[2][int(self.out_off[i]): int(self.out_off[i]) + int(res[0][i])])
-
-    def guards_intact(self, res):
-        keep = np.ones(self.out_total, bool)
-        for o, c in zip(self.out_off, self.caps):
-            keep[int(o): int(o) + int(c)] = False
-        assert (res[2][keep] == GUARD).all(), "written outside every capacity"
-
-
-def _check_against(run, want, rejected=()):
+def _check_against(batch, want, rejected=()):
     """want[i] = (status, bytes): status and length of every unit, its bytes where the status is MSCOMP_OK; guards; rejected units: ARG_ERROR, 0"""
     def check(res):
         for i, (ws, wb) in enumerate(want):
@@ -197,8 +160,8 @@ def _check_against(run, want, rejected=()):
                 continue
             assert int(res[1][i]) == ws, (i, int(res[1][i]), ws)
             if ws == 0:
-                assert int(res[0][i]) == len(wb) and run.unit(res, i) == wb, i
-        run.guards_intact(res)
+                assert int(res[0][i]) == len(wb) and PR.unit(res, batch, i) == wb, i
+        PR.guards_intact(res, batch)
     return check
 
 
@@ -251,9 +214,10 @@ def test_compress_host_plan(oracle, ctx, fmt, caps, hook):
             setter(hook[1])
         if sa:
             ctx.set_lznt1_sa_dict(True)
-        r = HostRun(ctx, f, units, cap, "compress")
-        cycle(ctx, r.run, _compress_claims(fmt, hook), [(r.plan, False)], _check_against(r, want))
-        r.plan.close()
+        batch = PR.layout(units, cap)
+        plan = PR.host_plan(ctx, f, batch, "compress")
+        cycle(ctx, lambda: PR.host_execute(plan, batch), _compress_claims(fmt, hook), [(plan, False)], _check_against(batch, want))
+        plan.close()
     finally:
         if setter:
             setter(1 if hook[0] == "finder" else 0)
@@ -281,16 +245,17 @@ def test_decode_and_size_host_plans(oracle, ctx, fmt, kind, family):
     f = FMTS[fmt]
     units, caps, want = _decode_batch(oracle, f, family)
     assert sum(s == 0 for s, _ in want) > 20 and sum(s != 0 for s, _ in want) > 20
-    r = HostRun(ctx, f, units, caps, kind)
+    batch = PR.layout(units, caps)
+    plan = PR.host_plan(ctx, f, batch, kind)
     if kind == "decode":
-        check = _check_against(r, want)
+        check = _check_against(batch, want)
     else:
         def check(res):
             for i, (ws, wb) in enumerate(want):
                 assert (int(res[1][i]), int(res[0][i])) == (ws, len(wb) if ws == 0 else 0), i
             assert (res[2] == GUARD).all()
-    cycle(ctx, r.run, CLAIMS[(kind, f)], [(r.plan, False)], check)
-    r.plan.close()
+    cycle(ctx, lambda: PR.host_execute(plan, batch), CLAIMS[(kind, f)], [(plan, False)], check)
+    plan.close()
 
 
 def _large_units(oracle, f):
@@ -316,14 +281,15 @@ def test_large_unit_decode_host_plan(oracle, ctx, fmt):
     f = FMTS[fmt]
     units, caps, want = _large_units(oracle, f)
     assert want[1][0] == 0 and want[4][0] == -5
-    r = HostRun(ctx, f, units, caps, "decode")
-    paths = m.api.plan_paths(r.plan)
+    batch = PR.layout(units, caps)
+    plan = PR.host_plan(ctx, f, batch, "decode")
+    paths = m.api.plan_paths(plan)
     assert paths[1] == 3 and (paths[0] == 2 if f == 3 else paths[2] > 0), paths     # (the half stream is below 512 KiB)
     ctx.lib.mscomp_amd_debug_lzg_open.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
     words = sum(c + 64 for c in caps if c >= LZG_MIN_CAP)
 
     def run():                                                         # ... with what the debug hooks say of the paths: the per-unit verdicts, the words open after each pointer pass
-        res = r.run()
+        res = PR.host_execute(plan, batch)
         modes, opened = np.zeros(8, np.uint32), np.zeros(33, np.uint32)
         k = ctx.lib.mscomp_amd_debug_decode_modes(ctx._h, modes.ctypes.data, 8)
         assert k >= 0 and ctx.lib.mscomp_amd_debug_lzg_open(ctx._h, words, opened.ctypes.data) == 0
@@ -331,8 +297,8 @@ def test_large_unit_decode_host_plan(oracle, ctx, fmt):
         assert opened[0] > 0 and 0 in opened and not any(opened[opened.index(0):]), opened   # the all-CU stage ran, counted from zero, and ended
         assert all(a >= b for a, b in zip(opened, opened[1:])), opened
         return res + (modes[: min(k, 8)].copy(),)
-    cycle(ctx, run, CLAIMS[("large", f)], [(r.plan, False)], _check_against(r, want))
-    r.plan.close()
+    cycle(ctx, run, CLAIMS[("large", f)], [(plan, False)], _check_against(batch, want))
+    plan.close()
 
 
 def test_lznt1_header_walk_fallback(oracle, ctx):
@@ -344,43 +310,15 @@ def test_lznt1_header_walk_fallback(oracle, ctx):
     caps = [4096 * 60, 2 * len(text) + 4096 * 60, 4096 * 60]
     want = [oracle.oracle_decompress_ex(2, u, c)[:2] for u, c in zip(units, caps)]
     assert want[0][0] == 0 and want[1][0] == 0 and want[2][0] != 0
-    r = HostRun(ctx, 2, units, caps, "decode")
+    batch = PR.layout(units, caps)
+    plan = PR.host_plan(ctx, 2, batch, "decode")
     ctx.lib.mscomp_amd_debug_lzd_walked(ctx._h)
-    cycle(ctx, r.run, CLAIMS[("decode", 2)], [(r.plan, False)], _check_against(r, want))
+    cycle(ctx, lambda: PR.host_execute(plan, batch), CLAIMS[("decode", 2)], [(plan, False)], _check_against(batch, want))
     assert ctx.lib.mscomp_amd_debug_lzd_walked(ctx._h) >= 3
-    r.plan.close()
+    plan.close()
 
 
 # ---- device-table plans --------------------------------------------------------------------------------------------------------------------
-class DevRunner:
-    """one dev plan of any kind, its unit tables fed from tensors"""
-
-    def __init__(self, ctx, plan, kind, units, caps):
-        import torch
-        self.ctx, self.plan, self.kind, self.n = ctx, plan, kind, len(units)
-        blob, in_off, lens, out_off, caps, self.out_total = _layout(units, caps)
-        self.out_off, self.caps = out_off, caps
-        self.d_in = torch.from_numpy(blob).cuda()
-        self.tabs = [_dt(a) for a in (in_off, lens, out_off, caps)]
-        self.d_out = torch.empty(self.out_total, dtype=torch.uint8, device="cuda")
-        self.d_len = torch.empty(self.n, dtype=torch.int64, device="cuda")
-        self.d_need = torch.empty(self.n, dtype=torch.int64, device="cuda")
-        self.d_st = torch.empty(self.n, dtype=torch.int32, device="cuda")
-
-    def run(self):
-        self.d_out.fill_(GUARD); self.d_len.fill_(-7); self.d_need.fill_(-7); self.d_st.fill_(-9)
-        i_off, i_len, o_off, o_cap = self.tabs
-        if self.kind == "size":
-            self.plan.execute(self.d_in, i_off, i_len, self.d_len, self.d_need, self.d_st, d_limit=o_cap)
-        else:
-            self.plan.execute(self.d_in, i_off, i_len, self.d_out, o_off, o_cap, self.d_len, self.d_st)
-        self.ctx.stream.synchronize()
-        return self.d_len.cpu().numpy(), self.d_st.cpu().numpy(), self.d_out.cpu().numpy(), self.d_need.cpu().numpy()
-
-    unit = HostRun.unit
-    guards_intact = HostRun.guards_intact
-
-
 @pytest.mark.parametrize("large", [False, True], ids=["plain", "large_units"])
 @pytest.mark.parametrize("kind", ["decode", "size"])
 @pytest.mark.parametrize("fmt", list(FMTS))
@@ -403,9 +341,10 @@ def test_decode_and_size_dev_plans(oracle, ctx, fmt, kind, large):
         plan = m.DevPlan(ctx, f, n, in_max, out_max, large_units=large)
     else:
         plan = m.SizeDevPlan(ctx, f, n, in_max, large_units=large)
-    r = DevRunner(ctx, plan, kind, units, caps)
+    batch = PR.layout(units, caps)
+    r = PR.DevRun(plan, len(batch.blob), batch.out_total)
     if kind == "decode":
-        check = _check_against(r, want, rejected={n - 1})
+        check = _check_against(batch, want, rejected={n - 1})
     else:
         def check(res):
             for i, (ws, wb) in enumerate(want[:-1]):
@@ -417,7 +356,7 @@ def test_decode_and_size_dev_plans(oracle, ctx, fmt, kind, large):
         claims = claims + ("xps_buf",)
     if not large and kind == "decode":
         claims = tuple(c for c in claims if c != "dz_scr")            # (the token scratch is one of the optional paths)
-    cycle(ctx, r.run, claims, [(plan, True)], check)
+    cycle(ctx, lambda: r.run(batch), claims, [(plan, True)], check)
     if large and f != 2:
         paths = m.api.plan_paths(plan)
         assert (paths[0] == 2 if f == 3 else True) and (kind == "size" or (paths[1] == 3 and (f == 3 or paths[2] > 0))), paths
@@ -435,8 +374,9 @@ def test_compress_dev_plan(oracle, ctx, fmt):
     units, want = units + [bytes(longest + 1)], want + [(0, b"")]
     n = len(units)
     plan = m.CompressDevPlan(ctx, f, n, sum(len(u) for u in units[:-1]), longest)
-    r = DevRunner(ctx, plan, "compress", units, caps + [longest + 600])
-    cycle(ctx, r.run, CLAIMS[("compress", f)], [(plan, True)], _check_against(r, want, rejected={n - 1}))
+    batch = PR.layout(units, caps + [longest + 600])
+    r = PR.DevRun(plan, len(batch.blob), batch.out_total)
+    cycle(ctx, lambda: r.run(batch), CLAIMS[("compress", f)], [(plan, True)], _check_against(batch, want, rejected={n - 1}))
     plan.close()
 
 
@@ -449,7 +389,7 @@ def test_crc_dev_plan_one_long_unit_and_many_short_ones(ctx):
     lens = [(3 << 20) - 11] + [40] * 600 + [77]                       # the last unit crosses in_total_max: rejected
     n = len(offs)
     plan = m.CrcDevPlan(ctx, n, sum(lens[:-1]))
-    d_in, d_off, d_len = torch.from_numpy(mem).cuda(), _dt(offs), _dt(lens)
+    d_in, d_off, d_len = torch.from_numpy(mem).cuda(), PR.dt(offs), PR.dt(lens)
     d_crc, d_st = torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")
     want, wst = K.units(mem, offs, lens, sum(lens[:-1]))
     assert not wst[:-1].any() and wst[-1] == -2
@@ -476,8 +416,8 @@ def test_layout_and_compact_dev_and_compact_batch(oracle, ctx):
     f = 4
     units, ref = _compress_units(), _compress_want(oracle, f)[0]
     n = len(units)
-    blob, in_off, lens, _, _, _ = _layout(units, [0] * n)
-    d_in, d_ioff, d_ilen = torch.from_numpy(blob).cuda(), _dt(in_off), _dt(lens)
+    blob, in_off, lens, _, _, _ = PR.layout(units, [0] * n)
+    d_in, d_ioff, d_ilen = torch.from_numpy(blob).cuda(), PR.dt(in_off), PR.dt(lens)
     h_off, h_cap = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
     total = int(m.load_library().mscomp_amd_plan_layout(f, n, lens.ctypes.data, 16, h_off.ctypes.data, h_cap.ctypes.data))
     plan = m.CompressDevPlan(ctx, f, n, int(lens.sum()), int(lens.max()))

@@ -6,94 +6,10 @@ import numpy as np
 import pytest
 
 import cases
+import plans_rig as PR
+from plans_rig import FMTS
 
 pytestmark = pytest.mark.gpu
-FMTS = {"lznt1": 2, "xpress": 3, "xpress_huff": 4}
-PAD = 8                                                              # guard entries in front of and behind every result array
-G_LEN, G_ST = 0x5A5A5A5A5A5A5A5A, 77
-ARG = -2
-
-
-def _dt(a):
-    """a uint64 host table as an int64 CUDA tensor"""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint64)).view(np.int64).copy()).cuda()
-
-
-def _pack(units):
-    import ms_compress_amd as m
-    lens = [len(u) for u in units]
-    in_off, in_total = m.pack_offsets(lens)
-    blob = np.zeros(in_total + 16, np.uint8)
-    for u, o in zip(units, in_off):
-        blob[int(o): int(o) + len(u)] = np.frombuffer(bytes(u), np.uint8)
-    return blob, in_off, np.array(lens, np.uint64)
-
-
-def _host(ctx, f, blob, in_off, lens, limits):
-    """a fresh host-table size plan: (out_len, need, status)"""
-    import torch
-    import ms_compress_amd as m
-    n = len(lens)
-    d_in = torch.from_numpy(blob).cuda()
-    d_len = torch.zeros(max(1, n), dtype=torch.int64, device="cuda")
-    d_need = torch.zeros(max(1, n), dtype=torch.int64, device="cuda")
-    d_st = torch.zeros(max(1, n), dtype=torch.int32, device="cuda")
-    plan = m.SizePlan(ctx, f, in_off, lens, limits)
-    plan.execute(d_in, d_len, d_need, d_st)
-    torch.cuda.synchronize()
-    plan.close()
-    return d_len.cpu().numpy()[:n].view(np.uint64), d_need.cpu().numpy()[:n].view(np.uint64), d_st.cpu().numpy()[:n]
-
-
-class SizeRun:
-    """one size dev plan and the device buffers of its batches: tables and bytes are rewritten in place between executions; the three
-    result arrays sit between guard entries"""
-
-    def __init__(self, ctx, f, n, in_bytes, in_max):
-        import torch
-        import ms_compress_amd as m
-        self.plan = m.SizeDevPlan(ctx, f, n, in_max)
-        self.n = n
-        self.d_in = torch.zeros(max(16, in_bytes), dtype=torch.uint8, device="cuda")
-        self.tabs = [torch.zeros(max(1, n), dtype=torch.int64, device="cuda") for _ in range(3)]
-        self.d_len = torch.full((n + 2 * PAD,), G_LEN, dtype=torch.int64, device="cuda")
-        self.d_need = torch.full((n + 2 * PAD,), G_LEN, dtype=torch.int64, device="cuda")
-        self.d_st = torch.full((n + 2 * PAD,), G_ST, dtype=torch.int32, device="cuda")
-
-    def load(self, blob, in_off, lens, limits=None):
-        import torch
-        self.d_in[: len(blob)].copy_(torch.from_numpy(blob))
-        for t, a in zip(self.tabs, (in_off, lens, limits)):
-            if a is not None:
-                t[: self.n].copy_(_dt(a))
-        for t, v in ((self.d_len, G_LEN), (self.d_need, G_LEN), (self.d_st, G_ST)):
-            t.fill_(v)
-
-    def execute(self, limited=True):
-        n = self.n
-        self.plan.execute(self.d_in, self.tabs[0], self.tabs[1], self.d_len[PAD: PAD + n], self.d_need[PAD: PAD + n], self.d_st[PAD: PAD + n],
-                          self.tabs[2] if limited else None)
-
-    def result(self):
-        """(out_len, need, status) of the n units; the guard entries around them must be untouched"""
-        import torch
-        torch.cuda.synchronize()
-        n = self.n
-        ln, need, st = self.d_len.cpu().numpy(), self.d_need.cpu().numpy(), self.d_st.cpu().numpy()
-        for a, v in ((ln, G_LEN), (need, G_LEN), (st, G_ST)):
-            assert (a[:PAD] == v).all() and (a[PAD + n:] == v).all(), "guard entries overwritten"
-        return ln[PAD: PAD + n].view(np.uint64), need[PAD: PAD + n].view(np.uint64), st[PAD: PAD + n]
-
-
-def _same(host, dev, accepted=None):
-    hl, hn, hs = host
-    dl, dn, ds = dev
-    for i in range(len(hs)):
-        if accepted is not None and not accepted[i]:
-            assert (ds[i], dl[i], dn[i]) == (ARG, 0, 0), (i, ds[i], dl[i], dn[i])
-            continue
-        assert (ds[i], dl[i], dn[i]) == (hs[i], hl[i], hn[i]), (i, ds[i], hs[i], dl[i], hl[i], dn[i], hn[i])
 
 
 @pytest.mark.parametrize("fmt", list(FMTS))
@@ -104,17 +20,18 @@ def test_size_dev_plan_matches_host_size_plan(oracle, gpu_ctx, fmt):
     streams = cases.decode_streams(f, lambda d: oracle.oracle_compress(f, d)[1])
     units = [s for s, _ in streams] + [b"", b"\x00", b"\x41"]
     caps = np.array([c for _, c in streams] + [0, 5, 5], np.uint64)
-    blob, in_off, lens = _pack(units)
-    r = SizeRun(gpu_ctx, f, len(units), len(blob), int(lens.sum()))
-    for limits in (caps, None):
-        host = _host(gpu_ctx, f, blob, in_off, lens, limits)
-        r.load(blob, in_off, lens, limits)
-        r.execute(limited=limits is not None)
+    import ms_compress_amd as m
+    batch = PR.layout(units, caps)
+    r = PR.DevRun(m.SizeDevPlan(gpu_ctx, f, len(units), int(batch.lens.sum())), len(batch.blob), 0)
+    for b in (batch, batch._replace(caps=None)):
+        host = PR.host_run(gpu_ctx, f, b, "size")
+        r.load(b)
+        r.execute(limited=b.caps is not None)
         dev = r.result()
-        _same(host, dev)
-        assert sum(int(s) == 0 for s in dev[2]) > 50
+        PR.same_sizes(host, dev)
+        assert sum(int(s) == 0 for s in dev[1]) > 50
         if f == 2:                                                  # streams that end in the End_of_buffer header need one byte more than they give
-            plus = [i for i in range(len(units)) if dev[2][i] == 0 and dev[1][i] == dev[0][i] + 1]
+            plus = [i for i in range(len(units)) if dev[1][i] == 0 and dev[3][i] == dev[0][i] + 1]
             assert plus and all(units[i].endswith(b"\0\0") for i in plus)
     r.plan.close()
 
@@ -123,6 +40,7 @@ def test_size_dev_plan_matches_host_size_plan(oracle, gpu_ctx, fmt):
 def test_one_size_dev_plan_several_batches(oracle, gpu_ctx, fmt):
     """one plan of 120 units, five batches of 90 to 110 live units (the rest have in_len 0), tables and bytes rewritten in place on the device
     (from the second execution on the plan's own graph is replayed): each result is that of a fresh host size plan"""
+    import ms_compress_amd as m
     f = FMTS[fmt]
     streams = cases.decode_streams(f, lambda d: oracle.oracle_compress(f, d)[1], n_corrupt=20)
     rnd = np.random.default_rng(4)
@@ -133,12 +51,12 @@ def test_one_size_dev_plan_several_batches(oracle, gpu_ctx, fmt):
         pick = rnd.choice(len(streams), live, replace=False)
         units = [streams[i][0] for i in pick] + [b""] * (n - live)
         limits = np.array([streams[i][1] + int(rnd.integers(0, 3)) * b for i in pick] + [0] * (n - live), np.uint64)
-        batches.append(_pack(units) + (limits,))
-    r = SizeRun(gpu_ctx, f, n, max(len(x[0]) for x in batches), max(int(x[2].sum()) for x in batches))
-    for blob, in_off, lens, limits in batches:
-        r.load(blob, in_off, lens, limits)
+        batches.append(PR.layout(units, limits))
+    r = PR.DevRun(m.SizeDevPlan(gpu_ctx, f, n, max(int(x[2].sum()) for x in batches)), max(len(x[0]) for x in batches), 0)
+    for batch in batches:
+        r.load(batch)
         r.execute()
-        _same(_host(gpu_ctx, f, blob, in_off, lens, limits), r.result())
+        PR.same_sizes(PR.host_run(gpu_ctx, f, batch, "size"), r.result())
     r.plan.close()
 
 
@@ -153,18 +71,19 @@ def test_units_past_the_bounds_are_refused(oracle, gpu_ctx, fmt):
     streams = [s for s in cases.decode_streams(f, lambda d: oracle.oracle_compress(f, d)[1], n_corrupt=0) if len(s[0]) > 8 and s[1] > 8][::7][:40]
     units, caps = [s for s, _ in streams], np.array([c for _, c in streams], np.uint64)
     n = len(units)
-    blob, in_off, lens = _pack(units)
-    host = _host(gpu_ctx, f, blob, in_off, lens, caps)
+    batch = PR.layout(units, caps)
+    blob, in_off, lens, out_off, caps, _ = batch
+    host = PR.host_run(gpu_ctx, f, batch, "size")
     big = 0xFFFFF000 + 1
     ctx = m.Context()                                               # (its scratch for 4 GiB of input goes away with it)
-    r = SizeRun(ctx, f, n, len(blob), big + int(lens.sum()))
+    r = PR.DevRun(m.SizeDevPlan(ctx, f, n, big + int(lens.sum())), len(blob), 0)
     lens_bad = lens.copy()
     lens_bad[3] = big
-    r.load(blob, in_off, lens_bad, caps)
+    r.load(batch._replace(lens=lens_bad))
     r.execute()
     acc = np.ones(n, bool)
     acc[3] = False
-    _same(host, r.result(), acc)
+    PR.same_sizes(host, r.result(), acc)
     r.plan.close()
     del r
     torch.cuda.synchronize()
@@ -172,20 +91,20 @@ def test_units_past_the_bounds_are_refused(oracle, gpu_ctx, fmt):
 
     for cut in (n // 2, n // 4, 0):
         in_max = int(lens[:cut].sum()) + int(lens[cut]) // 2
-        r = SizeRun(gpu_ctx, f, n, len(blob), in_max)
-        r.load(blob, in_off, lens, caps)
+        r = PR.DevRun(m.SizeDevPlan(gpu_ctx, f, n, in_max), len(blob), 0)
+        r.load(batch)
         r.execute()
-        _same(host, r.result(), np.arange(n) < cut)
+        PR.same_sizes(host, r.result(), np.arange(n) < cut)
         r.plan.close()
 
-    r = SizeRun(gpu_ctx, f, 1, len(blob), int(lens[5]))              # one unit
-    r.load(blob, in_off[5:6], lens[5:6], caps[5:6])
+    r = PR.DevRun(m.SizeDevPlan(gpu_ctx, f, 1, int(lens[5])), len(blob), 0)      # one unit
+    r.load(batch._replace(in_off=in_off[5:6], lens=lens[5:6], out_off=out_off[5:6], caps=caps[5:6]))
     r.execute()
-    _same(tuple(x[5:6] for x in host), r.result())
+    PR.same_sizes(tuple(x[5:6] for x in host), r.result())
     r.plan.close()
-    r = SizeRun(gpu_ctx, f, 0, 16, 0)                                # no unit: nothing is enqueued, nothing written
+    r = PR.DevRun(m.SizeDevPlan(gpu_ctx, f, 0, 0), 16, 0)            # no unit: nothing is enqueued, nothing written
     r.execute()
-    assert len(r.result()[2]) == 0
+    assert len(r.result()[1]) == 0
     r.plan.close()
 
 
@@ -209,19 +128,19 @@ def test_large_units_among_small_ones(gpu_ctx, fmt):
     comp, st = m.compress_units(f, plain, ctx=gpu_ctx)
     assert all(s == 0 for s in st)
     assert 800_000 < len(comp[1500]) < 1_300_000, len(comp[1500])
-    blob, in_off, lens = _pack(comp)
-    host = _host(gpu_ctx, f, blob, in_off, lens, None)
+    batch = PR.layout(comp)
+    host = PR.host_run(gpu_ctx, f, batch, "size")
     modes = (C.c_uint32 * 8)()
     if f == 3:                                                      # the host plan took the segment path for the large stream ...
         assert gpu_ctx.lib.mscomp_amd_debug_decode_modes(gpu_ctx._h, modes, 8) == 1 and modes[0] == 2
-    r = SizeRun(gpu_ctx, f, len(comp), len(blob), int(lens.sum()))
-    r.load(blob, in_off, lens)
+    r = PR.DevRun(m.SizeDevPlan(gpu_ctx, f, len(comp), int(batch.lens.sum())), len(batch.blob), 0)
+    r.load(batch)
     r.execute(limited=False)
     dev = r.result()
     if f == 3:                                                      # ... and the dev plan has no such path
         assert gpu_ctx.lib.mscomp_amd_debug_decode_modes(gpu_ctx._h, modes, 8) == 0
-    _same(host, dev)
-    assert (dev[2] == 0).all() and [int(x) for x in dev[0]] == [len(p) for p in plain] and (dev[1] == dev[0]).all()
+    PR.same_sizes(host, dev)
+    assert (dev[1] == 0).all() and [int(x) for x in dev[0]] == [len(p) for p in plain] and (dev[3] == dev[0]).all()
     r.plan.close()
 
 
@@ -242,7 +161,7 @@ def test_plan_kinds_are_kept_apart(gpu_ctx):
              "dev_s": m.SizeDevPlan(gpu_ctx, 2, n, 64)}
     d_in = torch.zeros(64, dtype=torch.uint8, device="cuda")
     d_out = torch.full((64,), 0xEE, dtype=torch.uint8, device="cuda")
-    t = [_dt(off), _dt(ln), _dt(off), _dt(ln)]
+    t = [PR.dt(off), PR.dt(ln), PR.dt(off), PR.dt(ln)]
     d_len = torch.full((n,), 5, dtype=torch.int64, device="cuda")
     d_need = torch.full((n,), 5, dtype=torch.int64, device="cuda")
     d_st = torch.full((n,), 77, dtype=torch.int32, device="cuda")
