@@ -91,6 +91,8 @@ __device__ __forceinline__ void     wst16(uint16_t* p, uint32_t v) { __hip_atomi
 __device__ __forceinline__ uint16_t wld16(uint16_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ void     wst32(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ uint32_t wld32(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+__device__ __forceinline__ void     wst8(uint8_t* p, uint32_t v) { __hip_atomic_store(p, (uint8_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+__device__ __forceinline__ void     wst64(u64* p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 __device__ __forceinline__ void     wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront", "local"); }
 
 // A bucket entry of the window's eager scan stays 16 bits wide: the compiler selects the relaxed-atomic load (wld16) as an any-extending one and
@@ -225,7 +227,10 @@ __device__ __forceinline__ uint32_t lz_need_bits(uint32_t len) { uint32_t r; asm
 // end, its length `wn` and the range mask need no minimum and no select; only window 0 has a position without a candidate (position 0) and only
 // window 63 has lanes without a key (62 and 63: positions 4094 and 4095), each one scalar test.
 struct LzWin { uint32_t key, o0, shift; u64 tokmask, matchmask; };
-template <bool packed, bool FULL = false>
+// INNER (with FULL only): the window is one of 1 to 62 of a full chunk. No position 0 and no lanes without a key, so the active lanes are those
+// from the next token start on; and every position lies below 4078, where the chunk's end never cuts max_len and max_len is at least 18: the two
+// compare stages stop at the literals 64 and 128 bits, and "max_len > 8" and "max_len > 16" hold in every lane, so their ballots are not taken.
+template <bool packed, bool FULL = false, bool INNER = false>
 __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void* tbl, const uint16_t* s_bucket, uint32_t n, uint32_t lane,
                                               uint32_t wbase, uint32_t entry, LzWin& r)
 {
@@ -243,7 +248,10 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	uint32_t rel;                                                // the next token start, relative to the window (entry < wend here: < 64)
 	asm("s_max_u32 %0, %1, %2\n\ts_sub_u32 %0, %0, %2" : "=&s"(rel) : "s"(entry), "s"(wbase) : "scc");   // (a saturating subtract would go to the vector unit)
 	u64 act;
-	if (FULL) {
+	static_assert(FULL || !INNER, "an interior window is a window of a full chunk");
+	if (INNER) {
+		act = sgpr64(~(u64)0 << rel);
+	} else if (FULL) {
 		uint32_t lo;                                               // position 0: window 0 alone. The OR itself sets the condition (left to the compiler a compare follows it)
 		asm("s_or_b32 %0, %1, %2\n\ts_cselect_b32 %0, %2, 1" : "=&s"(lo) : "s"(wbase), "s"(rel) : "scc");
 		const uint32_t top = wbase == 4032u ? 0x3FFFFFFFu : 0xFFFFFFFFu;   // lanes 62 and 63 of window 63 are no keys
@@ -254,7 +262,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 		const uint32_t hi = n > wbase + 2u ? (n - wbase - 2u < 64u ? n - wbase - 2u : 64u) : 0u;                      // lanes [lo, hi)
 		act = sgpr64((~(u64)0 << lo) & (hi >= 64u ? ~(u64)0 : (((u64)1 << hi) - 1u)));
 	}
-	const uint32_t maxlen = (n - p < mask3) ? n - p : mask3;
+	const uint32_t maxlen = INNER ? mask3 : (n - p < mask3) ? n - p : mask3;
 	uint32_t s;
 	{
 		const uint32_t h = lz_hash(o0 & 0xFFFFFFu);              // >= 1
@@ -292,7 +300,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	// lane compares bytes 8..15 of its four candidates). A candidate that reached 16 bytes with
 	// max_len > 16 is extended only when the walk lands on its position (step 2), by the whole wave: inside a long repeat every lane has such
 	// candidates, and the walk visits one or two of them.
-	const uint32_t capb = (maxlen < 16u ? maxlen : 16u) << 3, cap1 = (maxlen < LZ_S1 ? maxlen : LZ_S1) << 3;
+	const uint32_t capb = INNER ? 128u : (maxlen < 16u ? maxlen : 16u) << 3, cap1 = INNER ? 8u * LZ_S1 : (maxlen < LZ_S1 ? maxlen : LZ_S1) << 3;
 	uint32_t kk[LZ_SELF];                                     // candidate k's key, 0 if it does not exist; bit 16 (length 16): it reached 16 bytes
 	{
 		uint32_t lb[LZ_SELF];                                 // length in bits (the low three dropped below)
@@ -306,7 +314,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 		u64 more = 0;
 		#pragma unroll
 		for (uint32_t k = 0; k < LZ_SELF; ++k) { more |= __builtin_amdgcn_ballot_w64(lb[k] >= 8u * LZ_S1) & ex[k]; }
-		if (more & __builtin_amdgcn_ballot_w64(maxlen > LZ_S1)) {
+		if (INNER ? more : more & __builtin_amdgcn_ballot_w64(maxlen > LZ_S1)) {
 			const LzS2 a = lz_ld_s2(s_data, p);
 			LzS2 c[LZ_SELF];
 			#pragma unroll
@@ -333,7 +341,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	// (which candidates reached 16 bytes stays in the lanes, as bit 16 of the four keys -- a compare stops at 16 bytes, so the bit is "length 16", and
 	// the key of a candidate that does not exist is 0: as four 64-bit masks they were eight scalar registers held across the walk for its rarest stop.
 	// The best key has the bit iff one of the four has it.)
-	const u64 lp = sgpr64(__builtin_amdgcn_ballot_w64(key >= (16u << 12)) & __builtin_amdgcn_ballot_w64(maxlen > 16u));
+	const u64 lp = sgpr64(INNER ? __builtin_amdgcn_ballot_w64(key >= (16u << 12)) : __builtin_amdgcn_ballot_w64(key >= (16u << 12)) & __builtin_amdgcn_ballot_w64(maxlen > 16u));
 	u64 mm = __builtin_amdgcn_ballot_w64(key >= (3u << 12)) & ~un;              // resolved or long-pending positions that have a match
 	// The serial loop only decides which candidates are TAKEN; everything else (which positions are literal tokens)
 	// is derived in parallel afterwards.
@@ -751,7 +759,7 @@ static_assert(LZNT1_REC == 2u * 64u * LZ4_MAXM * sizeof(uint16_t), "kernels.h: L
 // CU-cycle, 5.81 above 96; round 13 in profiles/HISTORY.md and its correction in round 15). Since round 15 the kernel uses 77 (76 since round 17) and runs at eight
 // (7.76): lz_window keeps "candidate k reached 16 bytes" in the lanes instead of four 64-bit masks, and what sort and parse never read waits in the
 // lanes of one vector register (LZ4_PARK below). tests/test_lznt1_resources.py holds all four instances at 80, without spills: an `amdgpu_num_sgpr`
-// limit gets there too, by spilling, which the same test forbids. 68 since round 18; 72 since round 23, with two bodies behind one branch.)
+// limit gets there too, by spilling, which the same test forbids. 68 since round 18; 72 since round 23, with two bodies behind one branch; 70 since round 25.)
 // One LDS object, the chunk first (see the kernel above), 20 480 B -> 8 blocks per CU by the LDS. The chunk has no pad: the reads that run past its
 // end (lz_ld128 / lds_ld32 reach up to 16 bytes beyond byte 4095, into the bucket array) and the bytes between n and 4096 only feed
 // (a) keys of positions p with p + 3 <= n, whose fourth byte is masked off, (b) compares whose result is capped by
@@ -996,27 +1004,42 @@ __device__ __forceinline__ void lz4_chunk_body(Lz4Lds& L, uint32_t park, const u
 
 	// ---- C1. speculative parse of my segment ------------------------------------------------------------------------
 	const uint32_t nw = (n + 63u) >> 6;
-	// one window: parse, record (the match tokens into area a_). Returns the parse position after it.
+	// one window: parse, record (the match tokens into area a_). Hands back the parse position after it, wave-uniform.
 	// (The lanes that record are the match mask itself, as the exec mask: `(mask >> lane) & 1` is two ANDs with the lane's bit and a 64-bit
 	// compare in every lane. The record's base is a scalar pointer -- w_ and a_ are uniform -- so a lane adds a 32-bit offset to it.)
-#define LZ4_WINDOW(w_, entry_, cur_out, a_) { \
+	// The two arms -- the window lies behind the position already (a match covers it whole), or it is parsed -- only PRODUCE the token mask, the match
+	// mask and the position; one store sequence behind their join writes the window's control words, EVERY lane the same value to the same address
+	// (relaxed wavefront-scope stores: plain ds_write, no LDS cycle more than one lane's -- SQ_LDS_BANK_CONFLICT is the same to the digit). Under
+	// `lane == 0` in each arm these were three divergent regions per window: the structurizer merged the arms' stores into one region fed by 64-bit
+	// flags, turned the uniform "behind the position" test into flag code and bracketed every store with an exec save and restore -- 10
+	// scalar instructions per window by the counters (profiles/HISTORY.md round 25). The record store keeps its region: it is per-lane work.
+	// in_ (with FULL): the loop may run windows 1 to 62 through lz_window's INNER copy, picked by one scalar test on w_. The speculative loop alone
+	// says so: each copy is 4 to 6 KB of code, and tests/test_lznt1_full_listing.py holds the kernel below 64 KB.
+#define LZ4_WINDOW(w_, entry_, cur_out, a_, in_) { \
 		const uint32_t wb_ = (w_) * 64u; const uint32_t we_ = FULL ? wb_ + 64u : ((wb_ + 64u < n) ? wb_ + 64u : n); \
-		if ((entry_) >= we_) { if (lane == 0) { s_tok[w_] = 0; s_mat[w_] = 0; } cur_out = (entry_); } \
+		u64 tk_ = 0, mt_ = 0; \
+		if ((entry_) >= we_) { cur_out = (entry_); } \
 		else { \
-			LzWin r_; cur_out = lz_window<true, FULL>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); \
+			LzWin r_; \
+			if (FULL && (in_) && (w_) - 1u < 62u) { cur_out = lz_window<true, true, true>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); } \
+			else { cur_out = lz_window<true, FULL>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); } \
 			if (__builtin_amdgcn_inverse_ballot_w64(r_.matchmask)) { \
 				const uint32_t p_ = wb_ + lane, best_ = r_.key >> 12; \
 				g_u16* __restrict__ const recw_ = rec + ((a_) * 64u + (w_)) * LZ4_MAXM; \
 				recw_[popc_below(r_.matchmask)] = (uint16_t)(((p_ - (4095u - (r_.key & 0xFFFu)) - 1u) << r_.shift) | (best_ - 3u)); \
 			} \
-			if (lane == 0) { s_tok[w_] = r_.tokmask; s_mat[w_] = r_.matchmask; } \
+			tk_ = r_.tokmask; mt_ = r_.matchmask; \
 		} \
-		if ((a_) && lane == 0) { s_rep[w_] = 1; } }
+		cur_out = LZ4_UNI(cur_out); \
+		wst64(&s_tok[w_], tk_); wst64(&s_mat[w_], mt_); wst16(&s_endc[w_], cur_out); \
+		if (a_) { wst8(&s_rep[w_], 1u); } }
 	// The window loops run on the scalar unit: the window number, the parse position and what is read back from the control words (a recorded
 	// position, a progress word) are wave-uniform, and LZ4_UNI says so where each value is born -- a read of LDS lands in a vector register, and
 	// the loop's own increment, left to the compiler, is copied into both arms of the `lane == 0` store in front of it, which makes the counter a
 	// value joined under a divergent branch: window number and position then live in vector registers, the "window already behind the
-	// position" test and the loop's back edge become exec-mask code. Lane 0 still writes the records; the compares and branches around it are scalar.
+	// position" test and the loop's back edge become exec-mask code. Since round 25 no `lane == 0` store is left in the loops (LZ4_WINDOW above; the
+	// progress word the same way, by the workgroup-scope store it always was): masks and position first, wave_fence(), then the progress word -- DS
+	// operations of a wave execute in program order, which is all the seam protocol asks.
 #define LZ4_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
 	// the segments are handed out in order (with four of them: one per wave)
 	for (;;) {
@@ -1029,11 +1052,10 @@ __device__ __forceinline__ void lz4_chunk_body(Lz4Lds& L, uint32_t park, const u
 		uint32_t entry = a0 * 64u;                                 // (exact for segment 0)
 		for (uint32_t w = a0; w < a1; w = LZ4_UNI(w + 1u)) {
 			uint32_t cur;
-			LZ4_WINDOW(w, entry, cur, 0u)
-			entry = LZ4_UNI(cur);
-			if (lane == 0) { s_endc[w] = (uint16_t)cur; }
+			LZ4_WINDOW(w, entry, cur, 0u, 1)
+			entry = cur;
 			wave_fence();
-			if (lane == 0) { __hip_atomic_store(&s_prog[seg], w + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+			__hip_atomic_store(&s_prog[seg], w + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 		}
 		// repair the seam behind my segment: continue with my position (true unless my own segment never re-synchronised)
 		// into the next segment until the position after a window equals the recorded one
@@ -1046,9 +1068,8 @@ __device__ __forceinline__ void lz4_chunk_body(Lz4Lds& L, uint32_t park, const u
 					wave_fence();
 					const uint32_t spec = LZ4_UNI(s_endc[w]);
 					uint32_t cur;
-					LZ4_WINDOW(w, entry, cur, 1u)
-					entry = LZ4_UNI(cur);
-					if (lane == 0) { s_endc[w] = (uint16_t)cur; }
+					LZ4_WINDOW(w, entry, cur, 1u, 0)
+					entry = cur;
 					if (cur == spec) { break; }
 				}
 			}
@@ -1067,9 +1088,8 @@ __device__ __forceinline__ void lz4_chunk_body(Lz4Lds& L, uint32_t park, const u
 			for (uint32_t w = lz4_seg_start(j); w < nw; w = LZ4_UNI(w + 1u)) {
 				const uint32_t spec = LZ4_UNI(s_endc[w]);
 				uint32_t cur;
-				LZ4_WINDOW(w, e2, cur, 1u)
-				e2 = LZ4_UNI(cur);
-				if (lane == 0) { s_endc[w] = (uint16_t)cur; }
+				LZ4_WINDOW(w, e2, cur, 1u, 0)
+				e2 = cur;
 				wave_fence();
 				wl = w + 1u;
 				if (cur == spec) { break; }
