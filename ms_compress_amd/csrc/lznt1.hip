@@ -230,6 +230,8 @@ struct LzWin { uint32_t key, o0, shift; u64 tokmask, matchmask; };
 // INNER (with FULL only): the window is one of 1 to 62 of a full chunk. No position 0 and no lanes without a key, so the active lanes are those
 // from the next token start on; and every position lies below 4078, where the chunk's end never cuts max_len and max_len is at least 18: the two
 // compare stages stop at the literals 64 and 128 bits, and "max_len > 8" and "max_len > 16" hold in every lane, so their ballots are not taken.
+// And it is none of the windows 1, 2, 4, 8, 16 and 32: all 64 lanes have one token split, made from the window's base on the scalar unit.
+// (The first stage's literal cap is not applied either: see the argument at the place.)
 template <bool packed, bool FULL = false, bool INNER = false>
 __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void* tbl, const uint16_t* s_bucket, uint32_t n, uint32_t lane,
                                               uint32_t wbase, uint32_t entry, LzWin& r)
@@ -240,7 +242,12 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 	const uint32_t p = wbase + lane;
 	const LzS1 own = lz_ld_s1(s_data, p);                        // (aligned dword reads: a misaligned read is replayed; bytes 8..15 are read by a second stage)
 	const uint32_t o0 = own.x, o1 = own.y;
-	const uint32_t shift = lz_shift(p);
+	// (INNER: the split is the window's, not the lane's. lz_shift(p) is a function of the bit length of p - 1, which inside the window 64 w .. 64 w + 63
+	// changes at lane 0 alone, and only where 64 w is a power of two: LZ4_WINDOW keeps windows 1, 2, 4, 8, 16 and 32 out of this copy, and in every
+	// other interior window p - 1 is as long as wbase in all 64 lanes. wbase >= 192, so the count is at most 24 and the minimum with 12 never
+	// wins. shift, max_len and max_len << 12 are scalar registers then: no lane computes them, and the event below reads no lane for max_len.)
+	uint32_t shift;
+	if (INNER) { shift = (uint32_t)__builtin_clz(wbase) - 16u; } else { shift = lz_shift(p); }
 	const uint32_t mask3 = (1u << shift) + 2u;
 	// my candidates: the entries from bucket[s] on that are < p (ascending). A position is ACTIVE if entry <= p, 0 < p and p + 3 <= n: ranges of the
 	// window, so the mask of active lanes comes from the scalar unit, and it is applied once, to the candidates' existence below. Every lane looks
@@ -309,7 +316,15 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 			#pragma unroll
 			for (uint32_t k = 0; k < LZ_SELF; ++k) { c[k] = lz_ld_s1(s_data, q[k]); }
 			#pragma unroll
-			for (uint32_t k = 0; k < LZ_SELF; ++k) { lb[k] = lz_diff_bits_s1(c[k].x ^ o0, c[k].y ^ o1, cap1); }
+			for (uint32_t k = 0; k < LZ_SELF; ++k) {
+				// INNER: no cap. What it kept out is a value above 64 (v_ffbl_b32 of 0 is -1), and none reaches lz_key: a lane whose candidate exists and
+				// agreed on all 64 bits makes `more` non-zero, `more` alone decides the second stage here, and inside it every lane with lb >= 64,
+				// its candidate existing or not, takes l2, which capb caps; where the second stage does not run, only candidates that do not exist
+				// can hold such a value, and their key is 0 by the select on ex[k] below, whatever lb says. (Elsewhere a lane with max_len <= 8
+				// relies on the cap: its candidate of 64 equal bits is not looked at again.)
+				const uint32_t x0 = c[k].x ^ o0, x1 = c[k].y ^ o1;
+				if (INNER) { const uint32_t a = ffbl_raw(x0), b = ffbl_raw(x1) | 32u; lb[k] = a < b ? a : b; } else { lb[k] = lz_diff_bits_s1(x0, x1, cap1); }
+			}
 		}
 		u64 more = 0;
 		#pragma unroll
@@ -391,7 +406,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 #undef LZ_WALK
 		if (mp < wn) {
 			const uint32_t sL = (uint32_t)__builtin_amdgcn_readlane((int)s, (int)mp);
-			const uint32_t maxL = (uint32_t)__builtin_amdgcn_readlane((int)maxlen, (int)mp);
+			const uint32_t maxL = INNER ? maxlen : (uint32_t)__builtin_amdgcn_readlane((int)maxlen, (int)mp);   // (INNER: the window's, a scalar already)
 			const uint32_t pL = wbase + mp;
 			uint32_t kbest = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)mp);
 			uint32_t fin = 1u;                                         // (a stop that is not long-pending is unresolved)
@@ -427,7 +442,7 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 #ifdef LZ4_PROFILE_EVENTS
 				uint32_t nsteps = 0, ntail = 0;
 #endif
-				const uint32_t cap1L = (maxL < LZ_S1 ? maxL : LZ_S1) << 3;
+				const uint32_t cap1L = (maxL < LZ_S1 ? maxL : LZ_S1) << 3;   // (not read by the INNER copy: see the step's first stage below)
 				// The step's candidates are younger than the best's, and the older one wins on equal length: only a candidate STRICTLY longer than the
 				// best (and at least 3 bytes long: a best below 3 is "no match" downstream, which sub-3 key it holds is never read) can change kbest.
 				// `need` is that length in bits, a function of kbest: computed here and again only behind a winner.
@@ -440,7 +455,11 @@ __device__ __forceinline__ uint32_t lz_window(const uint8_t* s_data, const void*
 					const u64 lt = __builtin_amdgcn_ballot_w64(qq < pL);
 					const u64 vmask = lt & ~(lt + 1u);                 // the lanes below the first one at or beyond pL's own entry
 					const LzS1 c1 = lz_ld_s1(s_data, qq);
-					uint32_t l2 = lz_diff_bits_s1(c1.x ^ a0, c1.y ^ a1, cap1L);   // in bits
+					// (INNER: no cap, as in the window's first stage and for its reason: a lane of vmask that agreed on all 64 bits starts the second
+					// stage, where every lane with l2 >= 64 takes l3; where it does not run, only lanes outside vmask can hold more than 64, and `win`
+					// never has them. With the literal 64 as the cap the compiler makes two v_min_u32 of the v_min3_u32.)
+					uint32_t l2;                                       // in bits
+					if (INNER) { const uint32_t f0 = ffbl_raw(c1.x ^ a0), f1 = ffbl_raw(c1.y ^ a1) | 32u; l2 = f0 < f1 ? f0 : f1; } else { l2 = lz_diff_bits_s1(c1.x ^ a0, c1.y ^ a1, cap1L); }
 					uint32_t it = 0;
 					// (no test of max_len > 8 in front of the second stage: l2 is capped at 8 min(max_len, 8), so below 8 no candidate reaches 64 bits, and
 					// at exactly 8 the second stage's cap is 64 too and it hands every candidate the 64 it came with. A max_len below 9 exists only in the last
@@ -1015,13 +1034,16 @@ __device__ __forceinline__ void lz4_chunk_body(Lz4Lds& L, uint32_t park, const u
 	// scalar instructions per window by the counters (profiles/HISTORY.md round 25). The record store keeps its region: it is per-lane work.
 	// in_ (with FULL): the loop may run windows 1 to 62 through lz_window's INNER copy, picked by one scalar test on w_. The speculative loop alone
 	// says so: each copy is 4 to 6 KB of code, and tests/test_lznt1_full_listing.py holds the kernel below 64 KB.
+	// (which windows: 1 to 62 but 1, 2, 4, 8, 16 and 32, where lane 0 has a larger split than lanes 1 to 63 -- lz_window, INNER. One bit of a
+	// constant mask: written as `w < 63 && (w & (w - 1))` the two conditions become 64-bit flags, eight scalar instructions per window.)
+#define LZ4_INNER_WINDOWS 0x7FFFFFFEFFFEFEE8ull
 #define LZ4_WINDOW(w_, entry_, cur_out, a_, in_) { \
 		const uint32_t wb_ = (w_) * 64u; const uint32_t we_ = FULL ? wb_ + 64u : ((wb_ + 64u < n) ? wb_ + 64u : n); \
 		u64 tk_ = 0, mt_ = 0; \
 		if ((entry_) >= we_) { cur_out = (entry_); } \
 		else { \
 			LzWin r_; \
-			if (FULL && (in_) && (w_) - 1u < 62u) { cur_out = lz_window<true, true, true>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); } \
+			if (FULL && (in_) && lz_bit64(LZ4_INNER_WINDOWS, (w_))) { cur_out = lz_window<true, true, true>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); } \
 			else { cur_out = lz_window<true, FULL>(s_data, tbl, s_bucket, n, lane, wb_, (entry_), r_); } \
 			if (__builtin_amdgcn_inverse_ballot_w64(r_.matchmask)) { \
 				const uint32_t p_ = wb_ + lane, best_ = r_.key >> 12; \
@@ -1211,6 +1233,7 @@ __device__ __forceinline__ void lz4_chunk_body(Lz4Lds& L, uint32_t park, const u
 	LZ4_BODY_EDGE("ends")
 #undef LZ4_BODY_EDGE
 #undef LZ4_WINDOW
+#undef LZ4_INNER_WINDOWS
 #undef LZ4_UNI
 }
 
