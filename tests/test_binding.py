@@ -119,8 +119,8 @@ def test_load_library_binds_every_entry(monkeypatch):
     import torch  # noqa: F401  (load_library imports it, and it opens its own libraries through ctypes.CDLL)
     import ms_compress_amd as m
     lib = _Unbound()
-    monkeypatch.setattr(m.api, "_lib", None)
-    monkeypatch.setattr(m.api, "LIB_PATH", __file__)
+    monkeypatch.setattr(m.api._abi, "_lib", None)                # (the loader's own module: api only imports its names)
+    monkeypatch.setattr(m.api._abi, "LIB_PATH", __file__)
     monkeypatch.setattr(C, "CDLL", lambda path: lib)
     assert m.api.load_library() is lib
     assert sorted(lib.functions) == sorted(m.api.EXPORTS)
