@@ -3,7 +3,7 @@ Xpress+Huffman, bit-exact with coderforlife/ms-compress, behind that library's `
 
 Only the compress hot path is here: ``csrc/`` holds the HIP kernels and the C-ABI
 (``libmscomp_amd.so``, declared in ``include/mscomp_amd.h``); ``api.py`` is the host-side mirror of the
-reference interface, a facade over ``_abi.py``, ``_core.py``, ``plans.py``, ``blocks.py`` and ``blocks_host.py``; ``corpus.py`` the synthetic Silesia-shaped bench input; ``sharding.py`` the per-GPU split.
+reference interface, a facade over ``_abi.py``, ``_core.py``, ``plans.py``, ``blocks.py``, ``blocks_host.py`` and ``device.py``; ``corpus.py`` the synthetic Silesia-shaped bench input; ``sharding.py`` the per-GPU split.
 """
 from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, MSCOMP_OK, MSCOMP_ERRNO,  # noqa: F401
                   MSCOMP_ARG_ERROR, MSCOMP_DATA_ERROR, MSCOMP_MEM_ERROR, MSCOMP_BUF_ERROR, FORMATS, CHUNK,
@@ -23,4 +23,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   blocks_match, blocks_match_delta, blocks_match_patch, blocks_single_instance,
                   BlockSyncer, blocks_sync, blocks_sync_delta, blocks_sync_patch, MSCOMP_AMD_SYNC_TILE,
                   BlockDigester, blocks_digest, MSCOMP_AMD_DIGEST_LEAF,
-                  BlockParity, blocks_parity, blocks_rebuild, MSCOMP_AMD_PARITY_K_MAX, MSCOMP_AMD_PARITY_M_MAX)
+                  BlockParity, blocks_parity, blocks_rebuild, MSCOMP_AMD_PARITY_K_MAX, MSCOMP_AMD_PARITY_M_MAX,
+                  device, DeviceBlocks, BlockOps, BlockDiff)

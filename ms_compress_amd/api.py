@@ -6,6 +6,7 @@ every name lives in the module of its concern --
   plans.py        the plan classes and *_dev calls, their host conveniences, the host-batch entry, the plan and scratch hooks
   blocks.py       the block objects, as thin wrappers over device tensors
   blocks_host.py  the blocks_* host conveniences
+  device.py       DeviceBlocks and BlockOps: containers that stay in device memory from call to call
 
 Mirrors the reference's own ctypes fixture (/root/reference/test/compressors.py:187-251: ``OpenSrc.Compress`` ->
 ``ms_compress``; default output buffer, status codes) so that the parity tests read like the reference's tests,
@@ -17,7 +18,7 @@ GPU is visible they raise.
 
 The loader's state (``_lib``) is _abi's alone: a copy here would go stale, so a test that stands in for the library patches _abi.
 """
-from . import _abi, _core, blocks, blocks_host, plans  # noqa: F401
+from . import _abi, _core, blocks, blocks_host, device, plans  # noqa: F401
 from ._abi import (HERE, LIB_PATH, MSCOMP_NONE, MSCOMP_RESERVED, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, MSCOMP_OK, MSCOMP_ERRNO,  # noqa: F401
                    MSCOMP_ARG_ERROR, MSCOMP_DATA_ERROR, MSCOMP_MEM_ERROR, MSCOMP_BUF_ERROR, FORMATS, CHUNK, SIGNATURES, EXPORTS,
                    MSCOMP_AMD_SPLICE_SRC_MAX, MSCOMP_AMD_SPLICE_ROW_TILE, MSCOMP_AMD_SYNC_TILE, MSCOMP_AMD_DIGEST_LEAF, MSCOMP_AMD_PARITY_K_MAX,
@@ -37,3 +38,4 @@ from .blocks_host import (blocks_compress, blocks_crc, blocks_decompress, blocks
                           _extent_lists, blocks_diff, blocks_delta, blocks_patch, blocks_repair, blocks_match, blocks_match_delta,
                           blocks_match_patch, blocks_single_instance, blocks_dedup, blocks_transcode, blocks_digest, _dev_block_digest,
                           blocks_sync, blocks_sync_delta, blocks_sync_patch, blocks_parity, blocks_rebuild, res_crc_from_blocks)
+from .device import BlockDiff, BlockOps, DeviceBlocks  # noqa: F401
