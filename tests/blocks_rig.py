@@ -157,7 +157,9 @@ def fresh(ctx, bk, bufs):
 class Container:
     """A block container, on the host as the models read it (packed bytes, first, off, lens, crc; n resources, nbt table rows, plen stored
     bytes) and on the device as a view takes it (d_packed, d_first, d_boff, d_len, d_crc). ``cap`` is the packed length a view states,
-    ``with_crc`` whether it brings its checksums; edited() gives copies that state something else."""
+    ``with_crc`` whether it brings its checksums; edited() gives copies that state something else, far() one whose stored bytes lie
+    at ``base`` of a large arena."""
+    base = 0
 
     @classmethod
     def make(cls, ctx, fmt, B, bufs):
@@ -262,6 +264,20 @@ class Container:
         c.with_crc = self.with_crc if with_crc is None else with_crc
         return c
 
+    def far(self, arena, base):
+        """a copy whose stored bytes lie at byte ``base`` of ``arena`` (a far_rig arena; the caller writes them there): d_packed is the
+        arena, every entry of off is shifted by base -- off[0] = base is what the header's rules admit --, plen = cap = base + the stored
+        length, and ``packed``, which the models read and model() hands them, is a FarBytes. Everything else is shared."""
+        from far_rig import FarBytes
+        assert not self.base
+        c = copy.copy(self)
+        c.bk, c.base = None, int(base)
+        c.off = self.off + np.uint64(base)
+        c.d_packed, c.d_boff = arena.t, d64(c.off, self.dev)
+        c.plen = c.cap = base + self.plen
+        c.packed = FarBytes(base, self.packed)
+        return c
+
     def view(self, crc=None, nbt=None, plen=None):
         """the source tuple a splicer or deduper takes, every field stated; crc / nbt / plen default to what the container states"""
         crc = self.with_crc if crc is None else crc
@@ -271,7 +287,10 @@ class Container:
     def model(self, crc=None, nbt=None, plen=None):
         """the same view as the models take a source: the stored bytes are followed by the zeros of the device buffer up to plen"""
         crc, plen = self.with_crc if crc is None else crc, self.cap if plen is None else plen
-        packed = (self.packed + bytes(max(0, plen - self.plen)))[:plen]
+        if self.base:
+            packed = type(self.packed)(self.base, (self.packed.data + bytes(max(0, plen - self.plen)))[:max(0, plen - self.base)])
+        else:
+            packed = (self.packed + bytes(max(0, plen - self.plen)))[:plen]
         return (packed, plen, self.first, self.off, self.lens, self.crc if crc else None, self.n, self.nbt if nbt is None else nbt)
 
     def host(self):
