@@ -1,6 +1,7 @@
-// blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h): containers, readers, writers, splicers and dedupers. Host orchestration only, as
+// blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h, mscomp_amd_search.h): containers, readers, searchers, writers, splicers and dedupers. Host orchestration only, as
 // plan_dev.hip: each call runs the launches of inner dev plans (dev_launch) between its own passes, through plan_run.
 #include "host.h"
+#include "../../include/mscomp_amd_search.h"
 
 using namespace msc;
 
@@ -392,6 +393,82 @@ MSCompStatus mscomp_amd_reader_read(mscomp_amd_reader* r, const uint8_t* d_packe
 }
 
 int mscomp_amd_reader_counts(mscomp_amd_reader* r, uint32_t out[3]) { return access_counts(r, nullptr, out); }
+
+// ---- block searchers (include/mscomp_amd_search.h; kernels: search.hip, the reader's passes in reader.hip) ----
+// A searcher is a reader core -- the inner decompress dev plan, the cache, the reader's tables -- beside columns of its own in a
+// second buffer: the pattern tables and one running-sum entry per (unit, tile) item of blocks_max units. Its call is the reader's with
+// another admission in front and the scan passes in place of the gather.
+static_assert(SR_PAT_MAX == MSCOMP_AMD_SEARCH_PAT_MAX && SR_LEN_MAX == MSCOMP_AMD_SEARCH_LEN_MAX, "the bounds the header states");
+struct mscomp_amd_searcher : BlockAccess {
+	GraphRun<14> run;
+	uint32_t n_pat = 0, len_max = 0;
+	uint64_t hits_max = 0;
+	DevBuf cols;                                       // SearchTab
+	SearchTab s{};
+};
+// the searcher's columns from `base` on (items: blocks_max << (shift - SR_TILE_SHIFT)); returns where they end: from a null base, their bytes
+static uintptr_t search_tab(SearchTab& s, void* base, uint64_t items)
+{
+	Carve k(base);
+	s.mask = k.q(4 * 256); s.aux = k.q(8); s.poff = k.q(SR_PAT_MAX); s.first = k.q((size_t)items + 1); s.plen = k.w(SR_PAT_MAX);
+	return k.at;
+}
+
+MSCompStatus mscomp_amd_searcher_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_req,
+                                        uint64_t blocks_max, uint32_t n_pat, uint32_t len_max, uint64_t hits_max, uint32_t flags, mscomp_amd_searcher** out)
+{
+	if (!out) { return MSCOMP_ARG_ERROR; }
+	*out = nullptr;
+	if (!create_args_ok(c, format, block_size, flags) || !count_ok(n_res) || !count_ok(n_blocks_table) || !count_ok(n_req) || !count_ok(blocks_max)) { return MSCOMP_ARG_ERROR; }
+	if (n_pat < 1 || n_pat > SR_PAT_MAX || len_max < 1 || len_max > SR_LEN_MAX || !count_ok(hits_max)) { return MSCOMP_ARG_ERROR; }
+	std::unique_ptr<mscomp_amd_searcher> sr(new (std::nothrow) mscomp_amd_searcher());
+	MSCompStatus st = access_create(sr.get(), nullptr, c, format, block_size, n_res, n_blocks_table, n_req, blocks_max, flags);
+	if (st != MSCOMP_OK) { return st; }
+	DeviceGuard g(c->device);
+	const uint64_t items = blocks_max << (sr->shift - SR_TILE_SHIFT);      // (< 2^38)
+	if (!g.ok || !sr->cols.reserve(search_tab(sr->s, nullptr, items) + 64)) {
+		(void)hipGetLastError();
+		sr->in.destroy(); sr->tab.release();
+		return g.ok ? MSCOMP_MEM_ERROR : MSCOMP_ERRNO;
+	}
+	search_tab(sr->s, sr->cols.p, items);
+	sr->n_pat = n_pat; sr->len_max = len_max; sr->hits_max = hits_max; sr->run.never = n_req == 0;
+	*out = sr.release();
+	return MSCOMP_OK;
+}
+void mscomp_amd_searcher_destroy(mscomp_amd_searcher* sr) { destroy_object(sr, [sr] { sr->in.destroy(); sr->tab.release(); sr->cols.release(); }); }
+
+MSCompStatus mscomp_amd_searcher_search(mscomp_amd_searcher* sr, const uint8_t* d_packed, uint64_t packed_len, const uint64_t* d_block_first,
+                                        const uint64_t* d_block_off, const uint64_t* d_res_len, const uint32_t* d_block_crc, const uint64_t* d_req,
+                                        const uint8_t* d_pat, const uint64_t* d_pat_off, uint64_t* d_hits, uint64_t* d_req_hits, uint64_t* d_count,
+                                        int32_t* d_pat_status, int32_t* d_status)
+{
+	if (!sr || !d_block_first || !d_block_off || (sr->n_res && !d_res_len)) { return MSCOMP_ARG_ERROR; }
+	if (sr->n_req && (!d_req || !d_req_hits || !d_status)) { return MSCOMP_ARG_ERROR; }
+	if (!d_pat || !d_pat_off || !d_count || !d_pat_status || (sr->hits_max && !d_hits) || (sr->m && !d_packed)) { return MSCOMP_ARG_ERROR; }
+	if (sr->n_req == 0) { return MSCOMP_OK; }              // (nothing to report on)
+	mscomp_amd_ctx* c = sr->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	sr->in.mark_ran(); sr->ran = true;
+	const void* args[14] = { d_packed, reinterpret_cast<const void*>((uintptr_t)packed_len), d_block_first, d_block_off, d_res_len, d_block_crc, d_req,
+	                         d_pat, d_pat_off, d_hits, d_req_hits, d_count, d_pat_status, d_status };
+	return plan_run(sr->run, c, args, [&] {
+		const ReaderTab& t = sr->t;
+		const SearchTab& s = sr->s;
+		// the reader's passes with the searcher's admission: the look-ahead's blocks are units as any other
+		{ KernelTimer k(c, "sr_req_kernel"); launch_search_requests(c->stream, sr->n_req, sr->n_res, sr->nbt, sr->m, sr->shift, sr->len_max - 1u, d_res_len, d_block_first, d_req, t); }
+		{ KernelTimer k(c, "rd_units"); launch_reader_units(c->stream, sr->n_req, sr->nbt, sr->m, sr->shift, packed_len, d_packed, static_cast<uint8_t*>(sr->in.cache.p), d_block_off, t); }
+		{ KernelTimer k(c, "sr_pat_kernel"); launch_search_patterns(c->stream, sr->n_pat, sr->len_max, d_pat, d_pat_off, s, d_pat_status); }
+		access_decode(sr, d_packed, d_block_crc, d_req_hits, d_status);    // (the fold's lengths land in d_req_hits: the sum pass overwrites every one)
+		// the searcher's own: count, sum, emit
+		{ KernelTimer k(c, "sr_count_kernel"); launch_search_count(c->stream, sr->n_req, sr->m, sr->shift, sr->n_pat, sr->len_max, d_pat, s, t, c->cpd_blocks); }
+		{ KernelTimer k(c, "sr_sum_kernel"); launch_search_sum(c->stream, sr->n_req, sr->shift, sr->hits_max, s, t, d_req_hits, d_count); }
+		{ KernelTimer k(c, "sr_emit_kernel"); launch_search_emit(c->stream, sr->n_req, sr->m, sr->shift, sr->n_pat, sr->len_max, sr->hits_max, d_pat, s, t, d_hits, c->cpd_blocks); }
+	});
+}
+
+int mscomp_amd_searcher_counts(mscomp_amd_searcher* sr, uint32_t out[3]) { return access_counts(sr, nullptr, out); }
 
 MSCompStatus mscomp_amd_writer_create(mscomp_amd_ctx* c, MSCompFormat format, uint32_t block_size, size_t n_res, uint64_t n_blocks_table, size_t n_req,
                                       uint64_t blocks_max, uint32_t flags, mscomp_amd_writer** out)

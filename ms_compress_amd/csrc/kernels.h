@@ -315,6 +315,34 @@ void launch_reader_units(hipStream_t st, uint32_t n_req, uint32_t nbt, uint32_t 
 void launch_reader_fold(hipStream_t st, uint32_t n_req, const uint32_t* block_crc, const ReaderTab& t, u64* d_out_len, int32_t* d_status);
 void launch_reader_gather(hipStream_t st, uint32_t n_req, uint32_t m, uint32_t shift, uint8_t* out, const u64* out_off, const ReaderTab& t, uint32_t blocks);
 
+// ---- block searchers (search.hip; mscomp_amd_searcher_*, include/mscomp_amd_search.h) ----
+// A searcher admits, shares, decodes and judges with the reader's passes on a ReaderTab of its own -- its admission counts the blocks of
+// the look-ahead too --, and scans where the reader gathers. Its own columns (blockobj.hip search_tab knows the layout): an item is one
+// (unit, tile) pair, tile = SR_TILE positions of the unit's block, item = (unit << (shift - SR_TILE_SHIFT)) + tile.
+#define SR_PAT_MAX    64u                                 // MSCOMP_AMD_SEARCH_PAT_MAX: one bit of a mask word per pattern
+#define SR_LEN_MAX    256u                                // MSCOMP_AMD_SEARCH_LEN_MAX
+#define SR_TILE_SHIFT 12u                                 // the smallest block: a tile never spans two blocks
+#define SR_TILE       (1u << SR_TILE_SHIFT)
+struct SearchTab {
+	u64* mask;                                         // 4 x 256: mask[k][b], bit p = pattern p has byte b at position k or is shorter than k + 1; a refused pattern has no bit
+	u64* aux;                                          // 8: [a], a < 4: the patterns of length 1 .. a; [4]: those longer than 4 (the filter does not settle them)
+	u64* poff;                                         // SR_PAT_MAX: d_pat_off[p]
+	u64* first;                                        // items + 1: hits per item from the count pass, then their running sum (the item's first record)
+	uint32_t* plen;                                    // SR_PAT_MAX: the pattern's length, 0 for a refused one and behind n_pat
+};
+// admission: launch_reader_requests without the capacity rule, the budget counting the blocks that cover `look` more bytes (one block)
+void launch_search_requests(hipStream_t st, uint32_t n_req, uint32_t n_res, uint32_t nbt, uint32_t m, uint32_t shift, uint32_t look, const u64* res_len,
+                            const u64* block_first, const u64* req, const ReaderTab& t);
+// the patterns validated (pat_status), s.mask, s.aux, s.poff, s.plen (one block)
+void launch_search_patterns(hipStream_t st, uint32_t n_pat, uint32_t len_max, const uint8_t* pat, const u64* pat_off, const SearchTab& s, int32_t* pat_status);
+// behind the fold: the hits per item (a fixed grid of `blocks` dealt over the items, a wave per item), their running sum with req_hits
+// and count (one block, then a thread per request), the records below hits_max (the fixed grid again)
+void launch_search_count(hipStream_t st, uint32_t n_req, uint32_t m, uint32_t shift, uint32_t n_pat, uint32_t len_max, const uint8_t* pat, const SearchTab& s, const ReaderTab& t,
+                         uint32_t blocks);
+void launch_search_sum(hipStream_t st, uint32_t n_req, uint32_t shift, u64 hits_max, const SearchTab& s, const ReaderTab& t, u64* req_hits, u64* count);
+void launch_search_emit(hipStream_t st, uint32_t n_req, uint32_t m, uint32_t shift, uint32_t n_pat, uint32_t len_max, u64 hits_max, const uint8_t* pat, const SearchTab& s,
+                        const ReaderTab& t, u64* hits, uint32_t blocks);
+
 // ---- block writers (writer.hip; mscomp_amd_writer_*) ----
 // A writer admits, shares, decodes and judges with the reader's passes, on a ReaderTab of its own, and adds four columns to it
 // (blockobj.hip access_tab knows the layout).
