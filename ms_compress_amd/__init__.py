@@ -3,7 +3,7 @@ Xpress+Huffman, bit-exact with coderforlife/ms-compress, behind that library's `
 
 Only the compress hot path is here: ``csrc/`` holds the HIP kernels and the C-ABI
 (``libmscomp_amd.so``, declared in ``include/mscomp_amd.h``); ``api.py`` is the host-side mirror of the
-reference interface, a facade over ``_abi.py``, ``_core.py``, ``plans.py``, ``blocks.py``, ``blocks_host.py`` and ``device.py``; ``search.py`` binds the block searchers of ``include/mscomp_amd_search.h``; ``corpus.py`` the synthetic Silesia-shaped bench input; ``sharding.py`` the per-GPU split.
+reference interface, a facade over ``_abi.py``, ``_core.py``, ``plans.py``, ``blocks.py``, ``blocks_host.py`` and ``device.py``; ``search.py`` binds the block searchers of ``include/mscomp_amd_search.h``, ``match_digest.py`` match by block digest of ``include/mscomp_amd_match_digest.h``; ``corpus.py`` the synthetic Silesia-shaped bench input; ``sharding.py`` the per-GPU split.
 """
 from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, MSCOMP_OK, MSCOMP_ERRNO,  # noqa: F401
                   MSCOMP_ARG_ERROR, MSCOMP_DATA_ERROR, MSCOMP_MEM_ERROR, MSCOMP_BUF_ERROR, FORMATS, CHUNK,
@@ -27,3 +27,5 @@ from .api import (MSCOMP_NONE, MSCOMP_LZNT1, MSCOMP_XPRESS, MSCOMP_XPRESS_HUFF, 
                   device, DeviceBlocks, BlockOps, BlockDiff)
 from . import search  # noqa: F401  (the binding of include/mscomp_amd_search.h: a module of its own beside api)
 from .search import BlockSearcher, blocks_search, MSCOMP_AMD_SEARCH_PAT_MAX, MSCOMP_AMD_SEARCH_LEN_MAX  # noqa: F401
+from . import match_digest  # noqa: F401  (the binding of include/mscomp_amd_match_digest.h, likewise)
+from .match_digest import BlockDigestMatcher, blocks_match_digest, blocks_match_digest_delta  # noqa: F401

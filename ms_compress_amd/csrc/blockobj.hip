@@ -1,7 +1,8 @@
-// blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h, mscomp_amd_search.h): containers, readers, searchers, writers, splicers and dedupers. Host orchestration only, as
+// blockobj.hip -- the block objects of the C-ABI (include/mscomp_amd.h, mscomp_amd_search.h, mscomp_amd_match_digest.h): containers, readers, searchers, writers, splicers and dedupers. Host orchestration only, as
 // plan_dev.hip: each call runs the launches of inner dev plans (dev_launch) between its own passes, through plan_run.
 #include "host.h"
 #include "../../include/mscomp_amd_search.h"
+#include "../../include/mscomp_amd_match_digest.h"
 
 using namespace msc;
 
@@ -673,11 +674,12 @@ MSCompStatus mscomp_amd_splicer_splice_extents(mscomp_amd_splicer* s, const msco
 // ---- block dedupers (include/mscomp_amd.h; kernels: dedup.hip) ----
 // A deduper holds its tables -- sized by the bound of the resources alone -- and the graph of its call, keyed as a splicer's.
 #pragma GCC visibility push(hidden)                     // (what the creates instantiate over the object -- std::unique_ptr's destructor -- is no export of the library)
-enum DeduperKind {                                      // the call a deduper was made for; it refuses the other three
+enum DeduperKind {                                      // the call a deduper was made for; it refuses the other four
 	DEDUPER_DEDUP,                                         // mscomp_amd_deduper_create: the scratch holds a DedupTab
 	DEDUPER_DIFF,                                          // _create_diff: n_res is n_pair, nbt is n_blocks_new, the scratch holds a DiffTab
 	DEDUPER_MATCH,                                         // _create_match: n_src stores (0 .. 3), nbn is n_blocks_new, the scratch holds a MatchTab
-	DEDUPER_REPAIR                                         // _create_repair: n_res and nbt (= n_blocks_new) bound the primary, the scratch holds a DiffTab
+	DEDUPER_REPAIR,                                        // _create_repair: n_res and nbt (= n_blocks_new) bound the primary, the scratch holds a DiffTab
+	DEDUPER_MATCH_DIGEST                                   // _create_match_digest (mscomp_amd_match_digest.h): match's bounds and match's MatchTab
 };
 struct mscomp_amd_deduper {
 	mscomp_amd_ctx* ctx = nullptr;
@@ -686,6 +688,7 @@ struct mscomp_amd_deduper {
 	uint32_t nbn = 0;
 	GraphRun<37> run; GraphRun<24> frun; GraphRun<39> mrun; // dedup: four views, and five words; diff: two views, and eight; match: four views, and seven
 	GraphRun<42> rrun;                                      // repair: four views, four verdict arrays, and six words
+	GraphRun<43> grun;                                      // match by digest: four views, four digest columns, and seven words
 	DevBuf tab;                                            // DedupTab, DiffTab or MatchTab
 	DedupTab t{};
 	DiffTab f{};
@@ -723,7 +726,7 @@ static uintptr_t match_tab(MatchTab& t, void* base, size_t n, size_t m, size_t m
 	return k.at;
 }
 
-// The four creates: args_ok = the create's own check of its counts; fill(d, base) sets the bounds in d and lays the columns of its tables
+// The five creates: args_ok = the create's own check of its counts; fill(d, base) sets the bounds in d and lays the columns of its tables
 // out from `base` on, returning where they end: from a null base, their bytes.
 template <class Fill>
 static MSCompStatus deduper_create(mscomp_amd_ctx* c, uint32_t block_size, uint32_t flags, mscomp_amd_deduper** out, DeduperKind kind, bool args_ok, Fill fill)
@@ -765,6 +768,17 @@ MSCompStatus mscomp_amd_deduper_create_match(mscomp_amd_ctx* c, uint32_t block_s
 {
 	const bool args_ok = n_src < MSCOMP_AMD_SPLICE_SRC_MAX && count_ok(n_res_total) && count_ok(n_blocks_total) && n_blocks_new <= n_blocks_total;
 	return deduper_create(c, block_size, flags, out, DEDUPER_MATCH, args_ok, [&](mscomp_amd_deduper& d, void* base) {
+		d.n_src = n_src; d.n_res = (uint32_t)n_res_total; d.nbt = (uint32_t)n_blocks_total; d.nbn = (uint32_t)n_blocks_new;
+		return match_tab(d.m, base, n_res_total, n_blocks_total, n_blocks_new);
+	});
+}
+
+// (the checks, the bounds and the scratch of mscomp_amd_deduper_create_match: the passes that are its own read columns the caller brings)
+MSCompStatus mscomp_amd_deduper_create_match_digest(mscomp_amd_ctx* c, uint32_t block_size, uint32_t n_src, size_t n_res_total, uint64_t n_blocks_total,
+                                                    uint64_t n_blocks_new, uint32_t flags, mscomp_amd_deduper** out)
+{
+	const bool args_ok = n_src < MSCOMP_AMD_SPLICE_SRC_MAX && count_ok(n_res_total) && count_ok(n_blocks_total) && n_blocks_new <= n_blocks_total;
+	return deduper_create(c, block_size, flags, out, DEDUPER_MATCH_DIGEST, args_ok, [&](mscomp_amd_deduper& d, void* base) {
 		d.n_src = n_src; d.n_res = (uint32_t)n_res_total; d.nbt = (uint32_t)n_blocks_total; d.nbn = (uint32_t)n_blocks_new;
 		return match_tab(d.m, base, n_res_total, n_blocks_total, n_blocks_new);
 	});
@@ -877,6 +891,49 @@ MSCompStatus mscomp_amd_deduper_match(mscomp_amd_deduper* d, const mscomp_amd_bl
 			{ KernelTimer tm(c, "mt_keys_kernel"); launch_match_keys(c->stream, k, N, d->nbt, d->shift, with_crc, t, d_status, c->crc_blocks); }
 			{ KernelTimer tm(c, "mt_confirm_kernel"); launch_match_confirm(c->stream, k, N, d->nbt, d->shift, with_crc, t, c->cpd_blocks); }
 			{ KernelTimer tm(c, "mt_settle_kernel"); launch_match_settle(c->stream, k, N, d->shift, with_crc, t); }
+		}
+		if (d->nbn) { KernelTimer tm(c, "mt_runs"); launch_match_runs(c->stream, k, d->n_src, N, n_store, d->nbn, d->shift, t, d_status, d_delta_ext, d_patch_ext); }
+		{ KernelTimer tm(c, "mt_counts_kernel"); launch_match_counts(c->stream, N, n_store, d->nbn, d->nbt != 0, t, d_delta_ext_first, d_patch_ext_first, d_class, d_count, c->crc_blocks); }
+	});
+}
+
+// Match by digest (include/mscomp_amd_match_digest.h): match's ten launches with keys, confirm and settle over the views'
+// digest columns. No kernel dereferences a view's stored bytes: they go in as null, and the packed length alone stays, for rule 3.
+MSCompStatus mscomp_amd_deduper_match_digest(mscomp_amd_deduper* d, const mscomp_amd_blocks_view* store, const uint32_t* const* d_store_digest,
+                                             const mscomp_amd_blocks_view* next, const uint32_t* d_next_digest, uint64_t* d_delta_ext_first, uint64_t* d_delta_ext,
+                                             uint64_t* d_patch_ext_first, uint64_t* d_patch_ext, uint64_t* d_class, uint64_t* d_count, int32_t* d_status)
+{
+	if (!d || d->kind != DEDUPER_MATCH_DIGEST || !next || !d_count || (d->n_src && (!store || !d_store_digest))) { return MSCOMP_ARG_ERROR; }
+	if (d->n_res && (!d_delta_ext_first || !d_patch_ext_first || !d_class || !d_status || (d->nbn && (!d_delta_ext || !d_patch_ext)))) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_blocks_view src[MSCOMP_AMD_SPLICE_SRC_MAX];
+	DigestCols cols{};
+	for (uint32_t i = 0; i <= d->n_src; ++i) {
+		src[i] = i < d->n_src ? store[i] : *next;
+		cols.c[i] = i < d->n_src ? d_store_digest[i] : d_next_digest;
+		if ((src[i].n_res && !cols.c[i]) || (uintptr_t)cols.c[i] % 16u) { return MSCOMP_ARG_ERROR; }
+		src[i].d_packed = nullptr; src[i].packed_len = 0;                  // (pack_views asks for stored bytes where it is told of some)
+	}
+	SpliceSrc k{};
+	bool with_crc = false;                                 // no checksum takes part: the views go without their CRC columns
+	if (!pack_views(src, d->n_src + 1, false, k.v, with_crc)) { return MSCOMP_ARG_ERROR; }
+	for (uint32_t i = 0; i <= d->n_src; ++i) { k.v[i].packed_len = src[i].packed_len = i < d->n_src ? store[i].packed_len : next->packed_len; }
+	uint64_t n = 0;
+	if (!views_within(d, src, d->n_src + 1, n) || next->n_blocks_table > d->nbn) { return MSCOMP_ARG_ERROR; }
+	mscomp_amd_ctx* c = d->ctx;
+	DeviceGuard g(c->device);
+	if (!g.ok) { return MSCOMP_ERRNO; }
+	const void* args[43];
+	view_args(args, k.v, { cols.c[0], cols.c[1], cols.c[2], cols.c[3], d_delta_ext_first, d_delta_ext, d_patch_ext_first, d_patch_ext, d_class, d_count, d_status });
+	const uint32_t N = (uint32_t)n, n_store = (uint32_t)(n - next->n_res);
+	return plan_run(d->grun, c, args, [&] {
+		const MatchTab& t = d->m;
+		{ KernelTimer tm(c, "dd_clear_kernel"); launch_dedup_clear(c->stream, t.kt, c->crc_blocks); }
+		{ KernelTimer tm(c, "mt_seed_kernel"); launch_match_seed(c->stream, k, N, n_store, d->nbt, d->nbn, d->shift, t, d_status); }
+		if (d->nbt) {
+			{ KernelTimer tm(c, "dd_rows_kernel"); launch_dedup_rule3(c->stream, k, N, d->nbt, t.ufirst, d_status, c->crc_blocks); }
+			{ KernelTimer tm(c, "md_keys_kernel"); launch_match_digest_keys(c->stream, k, cols, N, d->nbt, d->shift, t, d_status, c->crc_blocks); }
+			{ KernelTimer tm(c, "md_confirm_kernel"); launch_match_digest_confirm(c->stream, k, cols, N, d->nbt, d->shift, t, c->crc_blocks); }
+			{ KernelTimer tm(c, "md_settle_kernel"); launch_match_digest_settle(c->stream, k, cols, N, d->shift, t); }
 		}
 		if (d->nbn) { KernelTimer tm(c, "mt_runs"); launch_match_runs(c->stream, k, d->n_src, N, n_store, d->nbn, d->shift, t, d_status, d_delta_ext, d_patch_ext); }
 		{ KernelTimer tm(c, "mt_counts_kernel"); launch_match_counts(c->stream, N, n_store, d->nbn, d->nbt != 0, t, d_delta_ext_first, d_patch_ext_first, d_class, d_count, c->crc_blocks); }

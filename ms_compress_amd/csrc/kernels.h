@@ -579,6 +579,16 @@ void launch_match_runs(hipStream_t st, const SpliceSrc& src, uint32_t n_src, uin
 void launch_match_counts(hipStream_t st, uint32_t n, uint32_t n_store, uint32_t nbn, bool settled, const MatchTab& t, u64* delta_first, u64* patch_first, u64* cls, u64* count,
                          uint32_t blocks);
 
+// mscomp_amd_deduper_match_digest (match_digest.hip; include/mscomp_amd_match_digest.h): match with equality decided by a row's data length
+// and its 16 bytes of a digest column, no stored byte read. The views' columns, 4 nbt words each and 16-byte aligned, travel by value
+// beside the SpliceSrc, column s belonging to view s; the scratch is a MatchTab. Keys, confirm and settle are its own -- fixed grids with
+// a lane per row, `blocks` = crc_dev_blocks(), and one block --; the other seven launches are match's, in match's order.
+struct DigestCols { const uint32_t* c[4]; };
+void launch_match_digest_keys(hipStream_t st, const SpliceSrc& src, const DigestCols& cols, uint32_t n, uint32_t nbt, uint32_t shift, const MatchTab& t,
+                              const int32_t* status, uint32_t blocks);
+void launch_match_digest_confirm(hipStream_t st, const SpliceSrc& src, const DigestCols& cols, uint32_t n, uint32_t nbt, uint32_t shift, const MatchTab& t, uint32_t blocks);
+void launch_match_digest_settle(hipStream_t st, const SpliceSrc& src, const DigestCols& cols, uint32_t n, uint32_t shift, const MatchTab& t);
+
 // ---- block transcoders (transcode.hip; mscomp_amd_transcoder_*) ----
 // What a transcoder is made for, by value in every kernel's arguments. A group is an aligned span of G = 1 << sg bytes of a resource
 // (sg = max(s1, s2)): md = G / B1 source blocks and me = G / B2 new blocks at most. mode: what may be carried.
